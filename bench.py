@@ -303,6 +303,30 @@ def measure_secondary(name, stream, device, steps=5, warmup=2):
         eng.close()
 
 
+DUMP_MAX_ELEMS = 3 << 20      # per flat vector: 12 MB of fp32, so loss + weights + both Adam moments stay under 64 MB
+
+
+def dump_sample(n, k=DUMP_MAX_ELEMS, seed=0):
+    """Indices of a flat vector of n elements that --dump-outputs writes: all of them when n <= k, else k of them, sorted,
+    drawn with a fixed seed (the same for every build of the same workload)."""
+    if n <= k:
+        return np.arange(n)
+    return np.sort(np.random.default_rng(seed).choice(n, size=k, replace=False))
+
+
+def dump_outputs(out_dir, eng, loss):
+    """What the timed path hands its caller after the last timed step: the mean CTC loss, the weights Adam produced and
+    Adam's two moment estimates (float32; the flat vectors sampled by dump_sample when large).  The gradient buffer is
+    consumed by the Adam step (nasr_get_grads refuses it afterwards); the moments carry it."""
+    os.makedirs(out_dir, exist_ok=True)
+    params = eng.get_params()
+    m, v, _ = eng.get_adam_state()
+    idx = dump_sample(params.size)
+    np.save(os.path.join(out_dir, 'loss.npy'), np.array([loss], np.float32))
+    for name, x in (('params', params), ('adam_m', m), ('adam_v', v)):
+        np.save(os.path.join(out_dir, name + '.npy'), np.ascontiguousarray(x[idx], np.float32))
+
+
 PROFILE_FILES = {'pmc': 'pmc_traffic.json', 'stamps': 'persist_stamps.json'}
 
 
@@ -332,6 +356,9 @@ def main():
                          'on a side stream under the rest of the backward pass, each released after the next persistent '
                          'BPTT launch (bucketed) or as soon as it is complete (bucketed-eager); auto times these three during '
                          'warm-up; lib = the same buckets through the library\'s own RCCL communicator (nasr_comm_*), opt-in')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last timed step returned (loss, updated weights, Adam '
+                         'moments; a fixed seeded sample of each when the weights are large) as DIR/<name>.npy')
     args = ap.parse_args()
 
     import torch
@@ -460,6 +487,8 @@ def main():
         loss = eng.get_loss()
     except Exception as exc:              # noqa: BLE001
         rank_error = str(exc)[:200]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, eng, loss)
     # what every rank ran: a rank that fell back to the per-step kernels (or saw void steps) slows the whole job and
     # would be invisible in rank 0's line otherwise
     aborts, rearms = eng.persist_stats()

@@ -143,6 +143,23 @@ def test_bench_algorithmic_bytes_cover_the_dense_stages():
     assert Ad > A and Wd == 40 * sd.param_count() and Rd == 2 * 500 * 2 * 4 * 2048 * 2048 * 4
 
 
+def test_bench_dump_sample_is_fixed_and_bounded():
+    """--dump-outputs: small vectors are written whole, large ones as the same sorted seeded sample on every run, and
+    loss + weights + both Adam moments stay under 64 MB for every workload."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location('bench', os.path.join(ROOT, 'bench.py'))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    assert bench.dump_sample(1000).tolist() == list(range(1000))
+    n = bench.workload_spec('bilstm3x500')[0].param_count()
+    a, b = bench.dump_sample(n), bench.dump_sample(n)
+    assert np.array_equal(a, b) and a.size == bench.DUMP_MAX_ELEMS
+    assert np.all(np.diff(a) > 0) and a[0] >= 0 and a[-1] < n
+    for name in ('bilstm3x500', 'literal', 'lstm3', 'deepspeech'):
+        m = bench.workload_spec(name)[0].param_count()
+        assert 4 * (1 + 3 * bench.dump_sample(m).size) <= 64 << 20
+
+
 def test_collective_without_process_group_offers_no_bucketed_reducer():
     """Single process (no torch.distributed group): the bucketed exchange is not offered, the plain path is used."""
     from neuralasr_amd.parallel import Collective
