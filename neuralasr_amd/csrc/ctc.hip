@@ -46,23 +46,11 @@ __device__ __forceinline__ float lse3(float a, float b, float c) {
 
 // lane l <- lane l-1 / l+1 as ONE DPP move (wave_shr:1 / wave_shl:1; the first / last lane gets `edge`) instead of a
 // ds_bpermute round trip through the LDS crossbar: the two neighbour exchanges of a lattice step are on its dependent chain
-template <bool DPP>
 __device__ __forceinline__ float lane_up1(float v, float edge) {
-  if constexpr (DPP) {
-    return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(edge), __float_as_int(v), 0x138, 0xf, 0xf, false));
-  } else {
-    const float r = __shfl_up(v, 1);
-    return (threadIdx.x & 63) == 0 ? edge : r;
-  }
+  return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(edge), __float_as_int(v), 0x138, 0xf, 0xf, false));
 }
-template <bool DPP>
 __device__ __forceinline__ float lane_down1(float v, float edge) {
-  if constexpr (DPP) {
-    return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(edge), __float_as_int(v), 0x130, 0xf, 0xf, false));
-  } else {
-    const float r = __shfl_down(v, 1);
-    return (threadIdx.x & 63) == 63 ? edge : r;
-  }
+  return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(edge), __float_as_int(v), 0x130, 0xf, 0xf, false));
 }
 
 __device__ __forceinline__ float wave_max(float v) {
@@ -91,13 +79,9 @@ __device__ __forceinline__ float wave_sum(float v) {
   return v;
 }
 
-// the engineered lattice (2b) wants its workspaces, 32-float emission rows with a spare column to park idle states on, two
-// states per lane at least and DPP (NASR_CTC_FAST=0 / NASR_CTC_DPP=0: the plain one of (2))
-static bool ctc_fast_ok(const CtcDims& d) {
-  static const bool off = (getenv("NASR_CTC_FAST") && getenv("NASR_CTC_FAST")[0] == '0') ||
-                          (getenv("NASR_CTC_DPP") && getenv("NASR_CTC_DPP")[0] == '0');
-  return !off && d.lprobs && d.goff && d.Cp == 32 && d.C <= 31 && d.KS >= 2;
-}
+// the engineered lattice (2b) wants its workspaces, 32-float emission rows with a spare column to park idle states on and
+// two states per lane at least; otherwise the plain one of (2) runs
+static bool ctc_fast_ok(const CtcDims& d) { return d.lprobs && d.goff && d.Cp == 32 && d.C <= 31 && d.KS >= 2; }
 
 // ------------------------------------------------------------------ (1) log partition per row
 // (lprobs, or NULL: the row's emissions in the form the engineered lattice (2b) reads them too, log2 y(t,k) =
@@ -139,7 +123,7 @@ void launch_ctc_logz(const CtcDims& d, const float* logits, const int* seq_len, 
 #ifndef NASR_CTC_GROUP
 #define NASR_CTC_GROUP 4   // 8 (twice the prefetch distance, rescale every 8 frames): same time - the lattice is not waiting for its emissions
 #endif
-template <int KS, bool DPP>
+template <int KS>
 __device__ __forceinline__ void ctc_ab_log(
     const float* __restrict__ logits, const float* __restrict__ logz, const int* __restrict__ labels,
     const int* __restrict__ label_len, const int* __restrict__ seq_len, float* __restrict__ alpha,
@@ -201,7 +185,7 @@ __device__ __forceinline__ void ctc_ab_log(
     float m = a[0];
 #pragma unroll
     for (int i = 1; i < KS; ++i) m = fmaxf(m, a[i]);
-    m = DPP ? wave_max_dpp(m) : wave_max(m);
+    m = wave_max_dpp(m);
 #pragma unroll
     for (int i = 0; i < KS; ++i) a[i] = a[i] > 0.5f * NEG ? a[i] - m : NEG;
     o += (double)m;
@@ -235,8 +219,8 @@ __device__ __forceinline__ void ctc_ab_log(
       for (int k = 0; k < G; ++k) {
         const int t = t0 + k;
         const bool live = t < Tb;
-        float p1 = lane_up1<DPP>(a[KS - 1], NEG);
-        float p2 = (KS >= 2) ? lane_up1<DPP>(a[KS >= 2 ? KS - 2 : 0], NEG) : __shfl_up(a[0], 2);
+        float p1 = lane_up1(a[KS - 1], NEG);
+        float p2 = (KS >= 2) ? lane_up1(a[KS >= 2 ? KS - 2 : 0], NEG) : __shfl_up(a[0], 2);
         if (KS == 1 && lane <= 1) p2 = NEG;
         float na[KS];
 #pragma unroll
@@ -294,8 +278,8 @@ __device__ __forceinline__ void ctc_ab_log(
         float bb[KS];
 #pragma unroll
         for (int i = 0; i < KS; ++i) bb[i] = bt[i] + e[k][i];      // states past S: NEG + NEG, rescaled back to NEG every group
-        float n1 = lane_down1<DPP>(bb[0], NEG);
-        float n2 = (KS >= 2) ? lane_down1<DPP>(bb[KS >= 2 ? 1 : 0], NEG) : __shfl_down(bb[0], 2);
+        float n1 = lane_down1(bb[0], NEG);
+        float n2 = (KS >= 2) ? lane_down1(bb[KS >= 2 ? 1 : 0], NEG) : __shfl_down(bb[0], 2);
         if (KS == 1 && lane >= 62) n2 = NEG;
         float nb[KS];
 #pragma unroll
@@ -361,8 +345,8 @@ __device__ __forceinline__ void fast_store(float* base, unsigned voff, const flo
   }
 }
 // lane l <- lane l-1 / l+1 with `edge` at the wave's first / last lane, as in lane_up1 / lane_down1
-__device__ __forceinline__ float fast_up(float v) { return lane_up1<true>(v, NEG); }
-__device__ __forceinline__ float fast_down(float v) { return lane_down1<true>(v, NEG); }
+__device__ __forceinline__ float fast_up(float v) { return lane_up1(v, NEG); }
+__device__ __forceinline__ float fast_down(float v) { return lane_down1(v, NEG); }
 
 // log2(2^a + 2^b + 2^c)
 __device__ __forceinline__ float lse3_2(float a, float b, float c) {
@@ -567,7 +551,7 @@ __device__ __forceinline__ void ctc_fast_loader(const float* __restrict__ lprobs
 }
 
 // one workgroup per utterance: wave 0 = alpha, wave 1 = beta, (FAST) wave 2 = the emissions' loader
-template <int KS, bool DPP, bool FAST>
+template <int KS, bool FAST>
 __global__ __launch_bounds__(FAST ? 192 : 128) void ctc_alpha_beta_kernel(
     const float* __restrict__ logits, const float* __restrict__ logz, const float* __restrict__ lprobs,
     const int* __restrict__ labels, const int* __restrict__ label_len, const int* __restrict__ seq_len,
@@ -589,25 +573,23 @@ __global__ __launch_bounds__(FAST ? 192 : 128) void ctc_alpha_beta_kernel(
     else
       ctc_fast_loader(lprobs, seq_len, Bp, ring, sync);
   } else {
-    ctc_ab_log<KS, DPP>(logits, logz, labels, label_len, seq_len, alpha, beta, aoff, boff, nll, logp_out, Bp, Cp, C, Lmax, Tws, fin);
+    ctc_ab_log<KS>(logits, logz, labels, label_len, seq_len, alpha, beta, aoff, boff, nll, logp_out, Bp, Cp, C, Lmax, Tws, fin);
   }
 }
 
 void launch_ctc_alpha_beta(const CtcDims& d, const float* logits, const float* logz, const int* labels,
                            const int* label_len, const int* seq_len, float* alpha, float* beta, double* aoff,
                            double* boff, float* nll, double* logp, hipStream_t st) {
-  static const bool no_dpp = getenv("NASR_CTC_DPP") && getenv("NASR_CTC_DPP")[0] == '0';
   const bool fast = ctc_fast_ok(d);
   const int KG = d.Tws / FAST_G + 3;
-#define NASR_AB2(K, D, F)                                                                                                \
-  hipLaunchKernelGGL((ctc_alpha_beta_kernel<K, D, F>), dim3(d.B), dim3(F ? 192 : 128), 0, st, logits, logz, d.lprobs, labels, \
+#define NASR_AB2(K, F)                                                                                                   \
+  hipLaunchKernelGGL((ctc_alpha_beta_kernel<K, F>), dim3(d.B), dim3(F ? 192 : 128), 0, st, logits, logz, d.lprobs, labels, \
                      label_len, seq_len, alpha, beta, aoff, boff, d.goff, nll, logp, d.Bp, d.Cp, d.C, d.Lmax, d.Tws, KG)
 #define NASR_AB(K)                                                                                                       \
-  if (fast) NASR_AB2(K, true, true);                                                                                     \
-  else if (no_dpp) NASR_AB2(K, false, false);                                                                            \
-  else NASR_AB2(K, true, false)
+  if (fast) NASR_AB2(K, true);                                                                                           \
+  else NASR_AB2(K, false)
   switch (d.KS) {
-    case 1: NASR_AB2(1, true, false); break;
+    case 1: NASR_AB2(1, false); break;
     case 2: NASR_AB(2); break;
     case 3: NASR_AB(3); break;
     case 4: NASR_AB(4); break;
@@ -618,7 +600,6 @@ void launch_ctc_alpha_beta(const CtcDims& d, const float* logits, const float* l
     case 9: case 10: case 11: case 12: NASR_AB(12); break;
     default: NASR_AB(16); break;
   }
-#undef NASR_AB2
 #undef NASR_AB2
 #undef NASR_AB
 }

@@ -380,11 +380,9 @@ void launch_gather_rows(float* dst, const float* src, const int* map, int n, flo
 // 256 tiles of the step, 8 waves, one block per CU.  <4,1,3>: a 128 x 192 tile on THREE waves and 80 KB of LDS - what fits on
 // a CU beside a workgroup of the persistent recurrence (lstm_persist.hip: 5 waves, two of them on one SIMD), for weight
 // gradients that run under the BPTT launch of the layer below (nasr_api.hip, weight_grads on the side stream).
-// DBG (diagnostics of the co-residency experiment, NASR_SIDE_DBG, side launches only): 1 = no operand DMA after the first
-// step, 2 = no MFMAs - results are garbage, timing only.
 // CMAP: the result rows are scattered by p.c_map (compacted rows of a ragged batch) - its own instantiations: the test per
 // stored element cost the plain epilogue 3 us a launch.
-template <int TMW, int WM, int WN, int DBG = 0, bool CMAP = false>
+template <int TMW, int WM, int WN, bool CMAP = false>
 __global__ __launch_bounds__(64 * WM * WN, (WM * WN + 3) / 4) void gemm_tph_kernel(GemmTPHParams p) {
   extern __shared__ __attribute__((aligned(1024))) unsigned char lds[];
   constexpr int TM = 32 * TMW * WM, TN = 64 * WN;
@@ -460,7 +458,7 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN + 3) / 4) void gemm_tph_kern
     const int buf = ((kb - kb0) >> 1) & 1;
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
-    if (kb + 2 < kb1 && !(DBG & 1)) issue(kb + 2, buf ^ 1);   // (issued after the first fragment reads instead: 2 % slower)
+    if (kb + 2 < kb1) issue(kb + 2, buf ^ 1);   // (issued after the first fragment reads instead: 2 % slower)
 #pragma unroll
     for (int kk = 0; kk < 2; ++kk) {
       f16x8 a[TMW][2], b[2][2];
@@ -476,10 +474,7 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN + 3) / 4) void gemm_tph_kern
 #pragma unroll
       for (int i = 0; i < TMW; ++i)
 #pragma unroll
-        for (int j = 0; j < 2; ++j) {
-          if constexpr (DBG & 2) acc[i][j][0] += (float)a[i][0][0] * (float)b[j][1][0];
-          else acc[i][j] = chain3(acc[i][j], a[i], b[j]);
-        }
+        for (int j = 0; j < 2; ++j) acc[i][j] = chain3(acc[i][j], a[i], b[j]);
     }
   }
 
@@ -518,22 +513,22 @@ constexpr int TPH_LDS_SIDE = 2 * 40 * HTB;     // <4,1,3>: (4 + 6) row blocks x 
 hipError_t gemm_tph_prepare() {
   hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_tph_kernel<4, 2, 4>),
                                      hipFuncAttributeMaxDynamicSharedMemorySize, TPH_LDS);
-  for (const void* f : {reinterpret_cast<const void*>(&gemm_tph_kernel<3, 2, 4>), reinterpret_cast<const void*>(&gemm_tph_kernel<4, 2, 4, 0, true>),
-                        reinterpret_cast<const void*>(&gemm_tph_kernel<3, 2, 4, 0, true>)})
+  for (const void* f : {reinterpret_cast<const void*>(&gemm_tph_kernel<3, 2, 4>), reinterpret_cast<const void*>(&gemm_tph_kernel<4, 2, 4, true>),
+                        reinterpret_cast<const void*>(&gemm_tph_kernel<3, 2, 4, true>)})
     if (e == hipSuccess) e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, TPH_LDS);
-  for (const void* f : {reinterpret_cast<const void*>(&gemm_tph_kernel<4, 1, 3>), reinterpret_cast<const void*>(&gemm_tph_kernel<4, 1, 3, 1>),
-                        reinterpret_cast<const void*>(&gemm_tph_kernel<4, 1, 3, 2>), reinterpret_cast<const void*>(&gemm_tph_kernel<4, 1, 3, 3>)})
-    if (e == hipSuccess) e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, TPH_LDS_SIDE);
+  if (e == hipSuccess)
+    e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_tph_kernel<4, 1, 3>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                            TPH_LDS_SIDE);
   return e;
 }
 
 // K split by a cost model in units of one k-step of one block: blocks run in rounds of 256 (one per CU), every slice keeps
 // >= 32 k-blocks, and each slab costs a write + a read of M x N floats at ~4 TB/s; slices are even numbers of k-blocks
-int gemm_tph_pick_split(int M, int N, int K, int nbatch, bool side) {
-  const int tm = side ? 128 : gemm_tp_tile_rows(M), tn = side ? 192 : 256;
+int gemm_tph_pick_split(int M, int N, int K, int nbatch) {
+  const int tm = gemm_tp_tile_rows(M), tn = 256;
   const int tiles = ((M + tm - 1) / tm) * ((N + tn - 1) / tn) * (nbatch > 1 ? 2 : 1);
   const int kbs = (K + 15) / 16;
-  const double kstep = side ? 0.9e-6 : 1.3e-6 * tm / 256.0;     // one step = two k-blocks of one block
+  const double kstep = 1.3e-6 * tm / 256.0;     // one step = two k-blocks of one block
   const double slab = (double)(nbatch > 1 ? 2 : 1) * M * N * 8.0 / 4e12 / kstep;
   int best = 1;
   double best_cost = 1e30;
@@ -569,12 +564,11 @@ void launch_gemm_tph(const GemmTPHDesc& g, hipStream_t st) {
   p.gx = (int)grid.x; p.gy = (int)grid.y; p.gz = (int)grid.z;
   p.pr = p.pc = p.pz = 1; p.sr = p.gy; p.sc = p.gx; p.sz = p.gz;
   {
-    static const int mode = [] { const char* e = getenv("NASR_GEMM_SWZ"); return e ? atoi(e) : 1; }();
     // process grid with the least fabric traffic pc * |A| + pr * |B| (an XCD fetches the A tiles of its rows once for all
     // of its columns and vice versa; K slices replicate nothing) among those that pad the grid by at most 1/8
     double best = 1e300;
     const long long total = (long long)p.gx * p.gy * p.gz;
-    for (int pz = 1; pz <= 8 && mode; pz *= 2)
+    for (int pz = 1; pz <= 8; pz *= 2)
       for (int pr = 1; pr * pz <= 8; pr *= 2) {
         const int pc = 8 / (pz * pr);
         const int sr = (p.gy + pr - 1) / pr, sc = (p.gx + pc - 1) / pc, sz = (p.gz + pz - 1) / pz;
@@ -585,15 +579,11 @@ void launch_gemm_tph(const GemmTPHDesc& g, hipStream_t st) {
       }
     if (p.swz) grid = dim3(8 * p.sr * p.sc * p.sz, 1, 1);
   }
-  static const int side_dbg = [] { const char* e = getenv("NASR_SIDE_DBG"); return e ? atoi(e) : 0; }();
   // rows scattered in the epilogue: main-stream products only (gemm_xproj, gemm_dx); a K-split one scatters in its reduction
   const bool scatter = g.c_map && p.split_k == 1 && !g.side;
-  if (g.side && side_dbg == 1) hipLaunchKernelGGL((gemm_tph_kernel<4, 1, 3, 1>), grid, dim3(192), TPH_LDS_SIDE, st, p);
-  else if (g.side && side_dbg == 2) hipLaunchKernelGGL((gemm_tph_kernel<4, 1, 3, 2>), grid, dim3(192), TPH_LDS_SIDE, st, p);
-  else if (g.side && side_dbg == 3) hipLaunchKernelGGL((gemm_tph_kernel<4, 1, 3, 3>), grid, dim3(192), TPH_LDS_SIDE, st, p);
-  else if (g.side) hipLaunchKernelGGL((gemm_tph_kernel<4, 1, 3>), grid, dim3(192), TPH_LDS_SIDE, st, p);
-  else if (scatter && tm == 192) hipLaunchKernelGGL((gemm_tph_kernel<3, 2, 4, 0, true>), grid, dim3(512), TPH_LDS, st, p);
-  else if (scatter) hipLaunchKernelGGL((gemm_tph_kernel<4, 2, 4, 0, true>), grid, dim3(512), TPH_LDS, st, p);
+  if (g.side) hipLaunchKernelGGL((gemm_tph_kernel<4, 1, 3>), grid, dim3(192), TPH_LDS_SIDE, st, p);
+  else if (scatter && tm == 192) hipLaunchKernelGGL((gemm_tph_kernel<3, 2, 4, true>), grid, dim3(512), TPH_LDS, st, p);
+  else if (scatter) hipLaunchKernelGGL((gemm_tph_kernel<4, 2, 4, true>), grid, dim3(512), TPH_LDS, st, p);
   else if (tm == 192) hipLaunchKernelGGL((gemm_tph_kernel<3, 2, 4>), grid, dim3(512), TPH_LDS, st, p);
   else hipLaunchKernelGGL((gemm_tph_kernel<4, 2, 4>), grid, dim3(512), TPH_LDS, st, p);
   if (p.split_k > 1) {

@@ -90,7 +90,7 @@ struct GemmTPHDesc {
   const int* c_map;         // (or NULL) output row m goes to row c_map[m] of C (-1: dropped); nbatch == 1 only
 };
 hipError_t gemm_tph_prepare();
-int gemm_tph_pick_split(int M, int N, int K, int nbatch = 1, bool side = false);
+int gemm_tph_pick_split(int M, int N, int K, int nbatch = 1);
 void launch_gemm_tph(const GemmTPHDesc& g, hipStream_t st);
 
 // ---- LSTM recurrence (lstm.hip) ----
@@ -141,11 +141,12 @@ void launch_lstm_persist_fwd(const LstmDims& dm, const float* Upf, const float* 
 void launch_lstm_persist_bwd(const LstmDims& dm, const float* Upb, const float* gates, float* dgbuf, const float* cbuf,
                              const float* dout, const int* seq_len, float* xch, PersistCtl* ctl, unsigned* sticky,
                              float* fault, hipStream_t st, bool ctl_zeroed = false, float* rowpart = nullptr,
-                             float* colpart = nullptr);   // ctl_zeroed: the caller cleared *ctl AND persist_px_bytes of xch
+                             float* colpart = nullptr, bool lean = false);   // ctl_zeroed: the caller cleared *ctl AND persist_px_bytes of xch
 // rowpart [D*32][T*Bp], colpart [8/D][D*4Hp] (or NULL): partial maxima of |dG| per frame row / per gate column, written by the
 // kernel's memory wave; launch_tph_scales_from_parts turns them into operand scales (persist_dgmax_floats sizes both)
+// lean: at Hp = 512 the launch declares only the 24 KB of LDS it uses instead of 96 KB, so that another kernel's workgroup
+// can share its CUs (the weight gradients of the side stream)
 size_t persist_dgmax_floats(int T, int Bp, int Hp, int D);
-void persist_set_bwd_lean(bool lean);            // BPTT launches declare 24 KB of LDS instead of 96 KB (process-wide)
 
 // ---- wide persistent forward recurrence (lstm_wide.hip): Hp = 2048, one launch per direction over all 256 CUs ----
 struct WideCtl {               // device words, zeroed before every launch

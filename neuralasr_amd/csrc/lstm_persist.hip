@@ -255,7 +255,6 @@ struct PersistGeom {
 constexpr int PERSIST_LDS_BYTES = 96 * 1024;   // > half of the CU's 160 KB: one workgroup per CU
 constexpr int PERSIST_LDS_LEAN = 24 * 1024;    // what the kernels use (LDS map below: 20.1 KB): leaves room for a 3-wave GEMM
                                                // workgroup on the same CU (gemm_tph.hip <4,1,3>)
-static bool g_bwd_lean = false;                // persist_set_bwd_lean
 
 // LDS map (floats): red [2][4][4][64] | adg [2][256] | side [2][64][8] | xgb [2][64][4] | pfb [2][64][8] | info[8]
 constexpr int LDS_RED = 0, LDS_ADG = 2 * 4 * 4 * 64, LDS_SIDE = LDS_ADG + 2 * 256, LDS_XGB = LDS_SIDE + 2 * 64 * 8,
@@ -879,10 +878,6 @@ static PersistGeom make_geom(const LstmDims& dm, bool bwd) {
   return g;
 }
 
-// lean = true: the BPTT launches declare only the LDS they use, so that another kernel's workgroup can share their CUs.
-// Only for Hp = 512, where the kernel's 5 x 220 VGPRs alone keep it at one workgroup per CU.
-void persist_set_bwd_lean(bool lean) { g_bwd_lean = lean; }
-
 size_t persist_dgmax_floats(int T, int Bp, int Hp, int D) { return (size_t)D * 32 * T * Bp + (size_t)(8 / D) * D * 4 * Hp; }
 
 size_t persist_px_bytes() { return (size_t)8 * 2 * 32 * 32 * 64 * sizeof(float); }   // the BPTT kernel's exchange buffer
@@ -942,7 +937,7 @@ void launch_lstm_persist_fwd(const LstmDims& dm, const float* Upf, const float* 
 
 void launch_lstm_persist_bwd(const LstmDims& dm, const float* Upb, const float* gates, float* dgbuf, const float* cbuf,
                              const float* dout, const int* seq_len, float* xch, PersistCtl* ctl, unsigned* sticky,
-                             float* fault, hipStream_t st, bool ctl_zeroed, float* rowpart, float* colpart) {
+                             float* fault, hipStream_t st, bool ctl_zeroed, float* rowpart, float* colpart, bool lean) {
   PersistGeom gm = make_geom(dm, true);
   gm.fault = fault;
   if (!ctl_zeroed) (void)hipMemsetAsync(ctl, 0, sizeof(PersistCtl), st);
@@ -950,7 +945,7 @@ void launch_lstm_persist_bwd(const LstmDims& dm, const float* Upb, const float* 
   if (NASR_BWD_EPOCH && !ctl_zeroed) (void)hipMemsetAsync(xch, 0, persist_px_bytes(), st);
   dim3 grid(256), block(320);
   // (lean only at Hp = 512, where the kernel's 5 x 220 VGPRs alone keep it at one workgroup per CU)
-  const int bwd_lds = (g_bwd_lean && dm.Hp == 512) ? PERSIST_LDS_LEAN : PERSIST_LDS_BYTES;
+  const int bwd_lds = (lean && dm.Hp == 512) ? PERSIST_LDS_LEAN : PERSIST_LDS_BYTES;
 #define NASR_PB(NUV)                                                                                                   \
   hipLaunchKernelGGL((lstm_persist_bwd_kernel<NUV>), grid, block, bwd_lds, st, Upb, gates, dgbuf, cbuf, dout, \
                      seq_len, xch, ctl, sticky, gm, rowpart, colpart)

@@ -90,13 +90,10 @@ int nasr_create(const nasr_model_cfg* cfg, int device_id, void* stream, nasr_han
     return code;
   };
   if (hipSetDevice(device_id) != hipSuccess) return bail(NASR_ERR_HIP, "hipSetDevice failed");
-  if (stream) {
-    h->st = reinterpret_cast<hipStream_t>(stream);
-  } else {
-    if (hipStreamCreateWithFlags(&h->st, hipStreamNonBlocking) != hipSuccess)
-      return bail(NASR_ERR_HIP, "hipStreamCreate failed");
-    h->own_stream = true;
-  }
+  if (stream)
+    h->st.borrow(reinterpret_cast<hipStream_t>(stream));
+  else if (hipStreamCreateWithFlags(h->st.out(), hipStreamNonBlocking) != hipSuccess)
+    return bail(NASR_ERR_HIP, "hipStreamCreate failed");
   if (build_layout(h) != NASR_OK) return bail(NASR_ERR_ARG, t_err);
   {
     const char* ec = getenv("NASR_COMPACT");
@@ -135,20 +132,20 @@ int nasr_create(const nasr_model_cfg* cfg, int device_id, void* stream, nasr_han
         h->off_dftp[i] = df; df += tph_bytes(h->dWp[i], h->dIp[i]);
         h->off_dbtp[i] = db; if (i > 0 || h->npre == 0) db += tph_bytes(h->dIp[i], h->dWp[i]);
       }
-      if (hipMalloc(&h->WfTP, of) != hipSuccess ||
-          hipMalloc(&h->WbTP, std::max<size_t>(ob, 1024)) != hipSuccess ||
-          hipMalloc(&h->DfTP, std::max<size_t>(df, 1024)) != hipSuccess ||
-          hipMalloc(&h->DbTP, std::max<size_t>(db, 1024)) != hipSuccess)
+      if (hipMalloc(h->WfTP.out(), of) != hipSuccess ||
+          hipMalloc(h->WbTP.out(), std::max<size_t>(ob, 1024)) != hipSuccess ||
+          hipMalloc(h->DfTP.out(), std::max<size_t>(df, 1024)) != hipSuccess ||
+          hipMalloc(h->DbTP.out(), std::max<size_t>(db, 1024)) != hipSuccess)
         return bail(NASR_ERR_HIP, "hipMalloc of the tiled weight planes failed");
     }
   }
   const size_t nb = (size_t)h->np_int * 4;
   const size_t gb = nb + GRAD_HEAD * 4;   // the gradient buffer starts with the fault word (+ padding): see nasr_grad_device_count
   const size_t ub = (size_t)h->L * h->D * h->Hp * h->N4 * 4;
-  if (hipMalloc(&h->P, nb) != hipSuccess || hipMalloc(&h->M, nb) != hipSuccess || hipMalloc(&h->V, nb) != hipSuccess ||
-      hipMalloc(&h->Gbase, gb) != hipSuccess || hipMalloc(&h->Uf, ub) != hipSuccess || hipMalloc(&h->Ub, ub) != hipSuccess)
+  if (hipMalloc(h->P.out(), nb) != hipSuccess || hipMalloc(h->M.out(), nb) != hipSuccess || hipMalloc(h->V.out(), nb) != hipSuccess ||
+      hipMalloc(h->Gbase.out(), gb) != hipSuccess || hipMalloc(h->Uf.out(), ub) != hipSuccess || hipMalloc(h->Ub.out(), ub) != hipSuccess)
     return bail(NASR_ERR_HIP, "hipMalloc of parameter buffers failed");
-  if (hipMalloc(&h->adam_dev, sizeof(AdamDev)) != hipSuccess) return bail(NASR_ERR_HIP, "hipMalloc of the Adam state failed");
+  if (hipMalloc(h->adam_dev.out(), sizeof(AdamDev)) != hipSuccess) return bail(NASR_ERR_HIP, "hipMalloc of the Adam state failed");
   (void)hipMemsetAsync(h->adam_dev, 0, sizeof(AdamDev), h->st);
   (void)hipMemsetAsync(h->P, 0, nb, h->st);
   (void)hipMemsetAsync(h->M, 0, nb, h->st);
@@ -180,7 +177,7 @@ int nasr_create(const nasr_model_cfg* cfg, int device_id, void* stream, nasr_han
     }
     h->ev_bucket.resize(h->buckets.size());
     for (auto& e2 : h->ev_bucket)
-      if (hipEventCreateWithFlags(&e2, hipEventDisableTiming) != hipSuccess) return bail(NASR_ERR_HIP, "hipEventCreate failed");
+      if (hipEventCreateWithFlags(e2.out(), hipEventDisableTiming) != hipSuccess) return bail(NASR_ERR_HIP, "hipEventCreate failed");
   }
   (void)hipMemsetAsync(h->Uf, 0, ub, h->st);
   (void)hipMemsetAsync(h->Ub, 0, ub, h->st);
@@ -191,12 +188,12 @@ int nasr_create(const nasr_model_cfg* cfg, int device_id, void* stream, nasr_han
       h->imf = persist_image_floats(h->Hp, false);
       h->imb = persist_image_floats(h->Hp, true);
       const size_t nk = (size_t)h->L * h->D;
-      if (persist_prepare() != hipSuccess || hipMalloc(&h->Upf, nk * h->imf * 4) != hipSuccess ||
-          hipMalloc(&h->Upb, nk * h->imb * 4) != hipSuccess ||
-          hipMalloc(&h->xchf, (size_t)h->L * persist_hx_bytes(h->Hp)) != hipSuccess ||
-          hipMalloc(&h->xchb, (size_t)h->L * persist_px_bytes()) != hipSuccess ||
-          hipMalloc(&h->pctl, (size_t)(1 + 2 * h->L) * sizeof(PersistCtl)) != hipSuccess ||   // [0] census, then one per layer pass
-          hipHostMalloc(&h->perr, 64, hipHostMallocMapped) != hipSuccess)
+      if (persist_prepare() != hipSuccess || hipMalloc(h->Upf.out(), nk * h->imf * 4) != hipSuccess ||
+          hipMalloc(h->Upb.out(), nk * h->imb * 4) != hipSuccess ||
+          hipMalloc(h->xchf.out(), (size_t)h->L * persist_hx_bytes(h->Hp)) != hipSuccess ||
+          hipMalloc(h->xchb.out(), (size_t)h->L * persist_px_bytes()) != hipSuccess ||
+          hipMalloc(h->pctl.out(), (size_t)(1 + 2 * h->L) * sizeof(PersistCtl)) != hipSuccess ||   // [0] census, then one per layer pass
+          hipHostMalloc(h->perr.out(), 64, hipHostMallocMapped) != hipSuccess)
         return bail(NASR_ERR_HIP, "allocation of the persistent-recurrence buffers failed");
       *h->perr = 0;
       const char* er = getenv("NASR_REC");
@@ -205,7 +202,7 @@ int nasr_create(const nasr_model_cfg* cfg, int device_id, void* stream, nasr_han
         bool g2 = false;
         size_t wsf = 0;
         for (size_t k = 0; k < nk; ++k) wsf += tph_scale_ws_floats(h->Hp, h->N4);
-        if (hipMalloc(&h->Ucs, nk * h->N4 * 4) != hipSuccess || hipMalloc(&h->Ucinv, nk * h->N4 * 4) != hipSuccess ||
+        if (hipMalloc(h->Ucs.out(), nk * h->N4 * 4) != hipSuccess || hipMalloc(h->Ucinv.out(), nk * h->N4 * 4) != hipSuccess ||
             !h->scws.ensure(wsf * 4, &g2))
           return bail(NASR_ERR_HIP, "allocation of the recurrent-weight scales failed");
         (void)hipMemsetAsync(h->Ucs, 0, nk * h->N4 * 4, h->st);
@@ -225,14 +222,14 @@ int nasr_create(const nasr_model_cfg* cfg, int device_id, void* stream, nasr_han
       bool g2 = false;
       size_t wsf = 0;
       for (size_t k = 0; k < nk; ++k) wsf += tph_scale_ws_floats(h->Hp, h->N4);
-      if (wide_prepare() != hipSuccess || hipMalloc(&h->Uw, nk * wide_image_bytes(h->Hp)) != hipSuccess ||
-          hipMalloc(&h->whx, wide_hx_bytes(64)) != hipSuccess || hipMalloc(&h->wpart, wide_part_bytes(64)) != hipSuccess ||
-          hipMalloc(&h->wctl, sizeof(WideCtl)) != hipSuccess || hipMalloc(&h->Uwb, nk * wide_image_bytes(h->Hp)) != hipSuccess ||
-          hipMalloc(&h->wpx, wide_px_bytes(64)) != hipSuccess || hipMalloc(&h->Urs, nk * h->Hp * 4) != hipSuccess ||
-          hipMalloc(&h->Urinv, nk * h->Hp * 4) != hipSuccess || hipMalloc(&h->wsrow, 2 * 64 * 4) != hipSuccess ||
-          hipMalloc(&h->Ucs, nk * h->N4 * 4) != hipSuccess ||
-          hipMalloc(&h->Ucinv, nk * h->N4 * 4) != hipSuccess || !h->scws.ensure(wsf * 4, &g2) ||
-          (!h->perr && hipHostMalloc(&h->perr, 64, hipHostMallocMapped) != hipSuccess))
+      if (wide_prepare() != hipSuccess || hipMalloc(h->Uw.out(), nk * wide_image_bytes(h->Hp)) != hipSuccess ||
+          hipMalloc(h->whx.out(), wide_hx_bytes(64)) != hipSuccess || hipMalloc(h->wpart.out(), wide_part_bytes(64)) != hipSuccess ||
+          hipMalloc(h->wctl.out(), sizeof(WideCtl)) != hipSuccess || hipMalloc(h->Uwb.out(), nk * wide_image_bytes(h->Hp)) != hipSuccess ||
+          hipMalloc(h->wpx.out(), wide_px_bytes(64)) != hipSuccess || hipMalloc(h->Urs.out(), nk * h->Hp * 4) != hipSuccess ||
+          hipMalloc(h->Urinv.out(), nk * h->Hp * 4) != hipSuccess || hipMalloc(h->wsrow.out(), 2 * 64 * 4) != hipSuccess ||
+          hipMalloc(h->Ucs.out(), nk * h->N4 * 4) != hipSuccess ||
+          hipMalloc(h->Ucinv.out(), nk * h->N4 * 4) != hipSuccess || !h->scws.ensure(wsf * 4, &g2) ||
+          (!h->perr && hipHostMalloc(h->perr.out(), 64, hipHostMallocMapped) != hipSuccess))
         return bail(NASR_ERR_HIP, "allocation of the wide persistent-recurrence buffers failed");
       *h->perr = 0;
       (void)hipMemsetAsync(h->whx, 0, wide_hx_bytes(64), h->st);
@@ -247,59 +244,57 @@ int nasr_create(const nasr_model_cfg* cfg, int device_id, void* stream, nasr_han
   h->cbuf.resize(h->L);
   h->Ybuf.resize(h->ndense);
   h->dYbuf.resize(h->ndense);
-  if (hipStreamCreateWithFlags(&h->cst, hipStreamNonBlocking) != hipSuccess) return bail(NASR_ERR_HIP, "hipStreamCreate (copy stream) failed");
-  if (hipStreamCreateWithFlags(&h->d2h, hipStreamNonBlocking) != hipSuccess ||
-      hipEventCreateWithFlags(&h->ev_snap, hipEventDisableTiming) != hipSuccess)
+  if (hipStreamCreateWithFlags(h->cst.out(), hipStreamNonBlocking) != hipSuccess) return bail(NASR_ERR_HIP, "hipStreamCreate (copy stream) failed");
+  if (hipStreamCreateWithFlags(h->d2h.out(), hipStreamNonBlocking) != hipSuccess ||
+      hipEventCreateWithFlags(h->ev_snap.out(), hipEventDisableTiming) != hipSuccess)
     return bail(NASR_ERR_HIP, "hipStreamCreate (results stream) failed");
   {
     const char* eo = getenv("NASR_WGRAD_OVERLAP");
     const bool eligible = h->persist && h->Hp == 512 && h->L > 1;
     h->wg_overlap = eligible && !(eo && eo[0] == '0');          // on unless NASR_WGRAD_OVERLAP=0 (nasr_set_wgrad_overlap)
-    h->ev_wg.assign(h->L, nullptr);
+    h->ev_wg.resize(h->L);
     h->wg_pending.assign(h->L, 0);
     if (eligible) {
       int lo = 0, hi = 0;
       (void)hipDeviceGetStreamPriorityRange(&lo, &hi);          // lo = lowest priority (largest number)
-      if (hipStreamCreateWithPriority(&h->wst, hipStreamNonBlocking, lo) != hipSuccess ||
-          hipEventCreateWithFlags(&h->ev_dx, hipEventDisableTiming) != hipSuccess)
+      if (hipStreamCreateWithPriority(h->wst.out(), hipStreamNonBlocking, lo) != hipSuccess ||
+          hipEventCreateWithFlags(h->ev_dx.out(), hipEventDisableTiming) != hipSuccess)
         return bail(NASR_ERR_HIP, "set-up of the weight-gradient side stream failed");
       for (auto& e : h->ev_wg)
-        if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) return bail(NASR_ERR_HIP, "hipEventCreate failed");
-      persist_set_bwd_lean(true);
+        if (hipEventCreateWithFlags(e.out(), hipEventDisableTiming) != hipSuccess) return bail(NASR_ERR_HIP, "hipEventCreate failed");
+      h->bwd_lean = true;
     }
   }
   for (BatchSlot& bs : h->slots)
-    if (hipEventCreateWithFlags(&bs.ev_copy, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&bs.ev_released, hipEventDisableTiming) != hipSuccess)
+    if (hipEventCreateWithFlags(bs.ev_copy.out(), hipEventDisableTiming) != hipSuccess ||
+        hipEventCreateWithFlags(bs.ev_released.out(), hipEventDisableTiming) != hipSuccess)
       return bail(NASR_ERR_HIP, "hipEventCreate failed");
   for (auto& r : h->res) {
-    if (hipHostMalloc(reinterpret_cast<void**>(&r.stamp), 64, hipHostMallocMapped) != hipSuccess)
+    if (hipHostMalloc(r.stamp.out(), 64, hipHostMallocMapped) != hipSuccess)
       return bail(NASR_ERR_HIP, "set-up of the step-result stamps failed");
     *r.stamp = 0;
   }
   for (auto& e : h->endw) {
-    if (hipHostMalloc(reinterpret_cast<void**>(&e.host), 64, hipHostMallocMapped) != hipSuccess)
+    if (hipHostMalloc(e.host.out(), 64, hipHostMallocMapped) != hipSuccess)
       return bail(NASR_ERR_HIP, "set-up of the step-end words failed");
-    e.stamp = reinterpret_cast<uint32_t*>(e.host) + 8;
+    e.stamp = reinterpret_cast<uint32_t*>(e.host.get()) + 8;
     *e.host = 0.f;
     *e.stamp = 0;
   }
-  (void)hipEventCreate(&h->ev_total_a);
-  (void)hipEventCreate(&h->ev_total_b);
+  (void)hipEventCreate(h->ev_total_a.out());
+  (void)hipEventCreate(h->ev_total_b.out());
   memset(&h->last_times, 0, sizeof(h->last_times));
   if (hipStreamSynchronize(h->st) != hipSuccess) return bail(NASR_ERR_HIP, "stream synchronize failed in create");
+  if (h->persist || h->wide) {
+    const char* er = getenv("NASR_PERSIST_REARM");
+    h->rearm_after = er && *er ? std::max<long long>(0, atoll(er)) : 200;
+  }
   if (h->persist) {
     if (!persist_census(h)) h->persist = false;
     h->persist_ok = h->persist;
     h->persist_wanted = h->persist;
-    const char* er = getenv("NASR_PERSIST_REARM");
-    h->rearm_after = er && *er ? std::max<long long>(0, atoll(er)) : 200;
     const char* eb = getenv("NASR_BUCKET_DEFER");
     h->bucket_defer = !(eb && eb[0] == '0');
-  }
-  if (h->wide) {
-    const char* er = getenv("NASR_PERSIST_REARM");
-    h->rearm_after = er && *er ? std::max<long long>(0, atoll(er)) : 200;
   }
   *out = h;
   return NASR_OK;
@@ -308,77 +303,11 @@ int nasr_create(const nasr_model_cfg* cfg, int device_id, void* stream, nasr_han
 int nasr_destroy(nasr_handle h) {
   if (!h) return NASR_OK;
   (void)hipSetDevice(h->device);
-  if (h->st) (void)hipStreamSynchronize(h->st);
-  for (hipEvent_t e : h->ev_bucket) (void)hipEventDestroy(e);
-  drop_graphs(h);
-  for (float* p : {h->P, h->M, h->V, h->Gbase, h->Uf, h->Ub, h->Upf, h->Upb, h->xchf, h->xchb, h->Ucs, h->Ucinv})
-    if (p) (void)hipFree(p);
-  if (h->WfTP) (void)hipFree(h->WfTP);
-  if (h->WbTP) (void)hipFree(h->WbTP);
-  if (h->DfTP) (void)hipFree(h->DfTP);
-  if (h->DbTP) (void)hipFree(h->DbTP);
-  h->DTP.release();
-  for (auto& b : h->Ybuf) b.release();
-  for (auto& b : h->dYbuf) b.release();
-  if (h->pctl) (void)hipFree(h->pctl);
-  if (h->Uw) (void)hipFree(h->Uw);
-  if (h->Uwb) (void)hipFree(h->Uwb);
-  if (h->wpx) (void)hipFree(h->wpx);
-  for (float* p : {h->Urs, h->Urinv, h->wsrow})
-    if (p) (void)hipFree(p);
-  if (h->whx) (void)hipFree(h->whx);
-  if (h->wpart) (void)hipFree(h->wpart);
-  if (h->wctl) (void)hipFree(h->wctl);
-  if (h->perr) (void)hipHostFree(h->perr);
-  for (DevBuf* b : {&h->XTP, &h->X0TTP, &h->GTP, &h->GTTP, &h->scws, &h->GTTP2, &h->csws2, &h->slabs2}) b->release();
-  h->sc_gc2.release();
-  h->sc_cr.release(); h->sc_cx.release(); h->OTS.release();
-  if (h->wst) { (void)hipStreamSynchronize(h->wst); (void)hipStreamDestroy(h->wst); }
-  if (h->ev_dx) (void)hipEventDestroy(h->ev_dx);
-  for (hipEvent_t e : h->ev_wg) if (e) (void)hipEventDestroy(e);
-  for (auto& b : h->OTT) b.release();
-  for (nasr_ctx::SV* v : {&h->sc15, &h->sc_x0r, &h->sc_x0c, &h->sc_gr, &h->sc_gc}) v->release();
-  for (auto* vec : {&h->sc_yr, &h->sc_yc, &h->sc_wr, &h->sc_wc, &h->sc_dr, &h->sc_dc})
-    for (auto& v : *vec) v.release();
+  for (const Stream* s : {&h->st, &h->cst, &h->d2h, &h->wst})
+    if (*s) (void)hipStreamSynchronize(*s);
   (void)nasr_comm_destroy(h);
-  if (h->adam_dev) (void)hipFree(h->adam_dev);
-  if (h->d2h) {
-    (void)hipStreamSynchronize(h->d2h);
-    (void)hipStreamDestroy(h->d2h);
-  }
-  if (h->ev_snap) (void)hipEventDestroy(h->ev_snap);
-  h->logits_snap.release();
-  for (auto& r : h->res) {
-    if (r.host) (void)hipHostFree(r.host);
-    if (r.stamp) (void)hipHostFree(r.stamp);
-    if (r.ev_lg) (void)hipEventDestroy(r.ev_lg);
-  }
-  for (auto& e : h->endw)
-    if (e.host) (void)hipHostFree(e.host);
-  if (h->cst) {
-    (void)hipStreamSynchronize(h->cst);
-    (void)hipStreamDestroy(h->cst);
-  }
-  for (BatchSlot& bs : h->slots) {
-    bs.dfeats.release();
-    bs.dmeta.release();
-    if (bs.hfeats) (void)hipHostFree(bs.hfeats);
-    if (bs.hmeta) (void)hipHostFree(bs.hmeta);
-    if (bs.ev_copy) (void)hipEventDestroy(bs.ev_copy);
-    if (bs.ev_released) (void)hipEventDestroy(bs.ev_released);
-  }
-  for (DevBuf* b : {&h->seqbuf, &h->X0, &h->dout, &h->hstate, &h->partial, &h->dcstate, &h->dgbuf, &h->logits, &h->logz,
-                    &h->alpha, &h->beta, &h->aoff, &h->boff, &h->logp, &h->nll, &h->loss, &h->slabs, &h->ctcprobs, &h->ctckexp,
-                    &h->csws, &h->amax, &h->ids, &h->lens, &h->stage, &h->dgmax})
-    b->release();
-  for (auto& b : h->gates) b.release();
-  for (auto& b : h->outb) b.release();
-  for (auto& b : h->cbuf) b.release();
-  for (hipEvent_t e : h->ev_pool) (void)hipEventDestroy(e);
-  if (h->ev_total_a) (void)hipEventDestroy(h->ev_total_a);
-  if (h->ev_total_b) (void)hipEventDestroy(h->ev_total_b);
-  if (h->own_stream && h->st) (void)hipStreamDestroy(h->st);
-  delete h;
+  drop_graphs(h);
+  delete h;   // the owners in nasr_ctx release its memory, streams and events
   return NASR_OK;
 }
 
@@ -674,7 +603,7 @@ int nasr_get_step_results(nasr_handle h, float* loss_out, int* fault_out, int32_
   if (!r.valid) return h->fail(NASR_ERR_STATE, "nasr_get_step_results: no step with nasr_set_step_decode(1) has been enqueued");
   // the forward pass + CTC of the step; its backward pass may still run
   if (!wait_stamp(r.stamp, r.seq, 60.0)) return h->fail(NASR_ERR_HIP, "nasr_get_step_results: the step's results did not arrive within 60 s");
-  const char* hp = static_cast<const char*>(r.host);
+  const char* hp = static_cast<const char*>(r.host.get());
   float fault;
   memcpy(&fault, hp + 4, 4);
   if (loss_out) memcpy(loss_out, hp, 4);
@@ -818,7 +747,7 @@ int nasr_get_step_logits(nasr_handle h, float* logits_out) {
   if (!wait_stamp(r.stamp, r.seq, 60.0)) return h->fail(NASR_ERR_HIP, "nasr_get_step_logits: the step's results did not arrive within 60 s");
   HIPCHK(h, hipEventSynchronize(r.ev_lg));          // the logits travel on a stream of their own (ctc_forward)
   const size_t ids_bytes = 8 + (size_t)r.Bp * 4 + (size_t)r.B * r.Tp * 4;
-  const float* src = reinterpret_cast<const float*>(static_cast<const char*>(r.host) + (ids_bytes + 255) / 256 * 256);
+  const float* src = reinterpret_cast<const float*>(static_cast<const char*>(r.host.get()) + (ids_bytes + 255) / 256 * 256);
   for (int t = 0; t < r.Tp; ++t)
     for (int b = 0; b < r.B; ++b)
       memcpy(logits_out + ((size_t)t * r.B + b) * h->C, src + ((size_t)t * r.Bp + b) * h->Cp, (size_t)h->C * 4);

@@ -120,13 +120,11 @@ int validate_batch(nasr_ctx* h, const int32_t* seq_len, const int32_t* labels, c
   return NASR_OK;
 }
 
-bool pinned_ensure(void** p, size_t* cap, size_t bytes) {
+bool pinned_ensure(Pinned<void>& p, size_t* cap, size_t bytes) {
   if (bytes <= *cap) return true;
-  if (*p) (void)hipHostFree(*p);
-  *p = nullptr;
   *cap = 0;
   const size_t want = bytes + bytes / 8;
-  if (hipHostMalloc(p, want, hipHostMallocMapped) != hipSuccess) return false;   // (kernels write step results into it)
+  if (hipHostMalloc(p.out(), want, hipHostMallocMapped) != hipSuccess) return false;   // (kernels write step results into it)
   *cap = want;
   return true;
 }
@@ -193,12 +191,12 @@ int slot_fill(nasr_ctx* h, BatchSlot* s, const float* feats, const int32_t* seq_
   const size_t nfeat = centre ? (size_t)B * T * ncep + B : (size_t)B * T * h->F;
   bool grew = false;
   if (!s->dmeta.ensure(nmeta * 4, &grew) || !s->dfeats.ensure(nfeat * 4, &grew) ||
-      !pinned_ensure(&s->hmeta, &s->hmeta_cap, nmeta * 4) ||
-      (pinned_feats && !pinned_ensure(&s->hfeats, &s->hfeats_cap, nfeat * 4)))
+      !pinned_ensure(s->hmeta, &s->hmeta_cap, nmeta * 4) ||
+      (pinned_feats && !pinned_ensure(s->hfeats, &s->hfeats_cap, nfeat * 4)))
     return h->fail(NASR_ERR_HIP, "allocation of a batch slot failed");
   if (s->copy_valid) HIPCHK(h, hipEventSynchronize(s->ev_copy));          // the pinned mirrors are free to overwrite
   if (s->released_valid && cs != h->st) HIPCHK(h, hipStreamWaitEvent(cs, s->ev_released, 0));   // and the device side unread
-  int32_t* m = static_cast<int32_t*>(s->hmeta);
+  int32_t* m = static_cast<int32_t*>(s->hmeta.get());
   memset(m, 0, nmeta * 4);
   s->frames = 0;
   for (int b = 0; b < B; ++b) {
@@ -250,7 +248,7 @@ int slot_fill(nasr_ctx* h, BatchSlot* s, const float* feats, const int32_t* seq_
     const size_t nc = (size_t)B * T * ncep;
     if (pinned_feats) {
       memcpy(s->hfeats, centre, nc * 4);
-      memcpy(static_cast<float*>(s->hfeats) + nc, pad_value, (size_t)B * 4);
+      memcpy(static_cast<float*>(s->hfeats.get()) + nc, pad_value, (size_t)B * 4);
       HIPCHK(h, hipMemcpyAsync(s->dfeats.p, s->hfeats, (nc + B) * 4, hipMemcpyHostToDevice, cs));
     } else {
       HIPCHK(h, hipMemcpyAsync(s->dfeats.p, centre, nc * 4, hipMemcpyHostToDevice, cs));
@@ -307,7 +305,7 @@ int slot_commit(nasr_ctx* h, BatchSlot* s) {
     h->total_valid = false;
   }
   h->h_seq.assign((size_t)Bp, 0);
-  const int32_t* hm = static_cast<const int32_t*>(s->hmeta);
+  const int32_t* hm = static_cast<const int32_t*>(s->hmeta.get());
   for (int b = 0; b < B; ++b) h->h_seq[b] = hm[s->o_seq + b];
   h->frames = s->frames;
   {

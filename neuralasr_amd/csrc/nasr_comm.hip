@@ -85,14 +85,14 @@ int nasr_comm_init(nasr_handle h, const void* id128, int rank, int nranks) {
   h->comm = c;
   h->comm_rank = rank;
   h->comm_n = nranks;
-  HIPCHK(h, hipStreamCreateWithFlags(&h->comm_st, hipStreamNonBlocking));
-  HIPCHK(h, hipEventCreateWithFlags(&h->ev_comm, hipEventDisableTiming));
-  HIPCHK(h, hipMalloc(&h->comm_scratch, 64 * sizeof(float)));
+  HIPCHK(h, hipStreamCreateWithFlags(h->comm_st.out(), hipStreamNonBlocking));
+  HIPCHK(h, hipEventCreateWithFlags(h->ev_comm.out(), hipEventDisableTiming));
+  HIPCHK(h, hipMalloc(h->comm_scratch.out(), 64 * sizeof(float)));
   if (r.CommSplit) {                      // collective over all ranks of `comm`: every rank gets here (same library everywhere)
     void* c2 = nullptr;
     if (r.CommSplit(c, 0, rank, &c2, nullptr) == 0 && c2) {
       h->comm2 = c2;
-      HIPCHK(h, hipStreamCreateWithFlags(&h->comm_st2, hipStreamNonBlocking));
+      HIPCHK(h, hipStreamCreateWithFlags(h->comm_st2.out(), hipStreamNonBlocking));
     }
   }
   return NASR_OK;
@@ -147,14 +147,12 @@ int nasr_comm_destroy(nasr_handle h) {
   if (h->comm_st2) (void)hipStreamSynchronize(h->comm_st2);
   if (h->comm2) (void)rccl().CommDestroy(h->comm2);
   h->comm2 = nullptr;
-  if (h->comm_st2) (void)hipStreamDestroy(h->comm_st2);
-  h->comm_st2 = nullptr;
+  h->comm_st2.reset();
   (void)rccl().CommDestroy(h->comm);
   h->comm = nullptr;
-  if (h->comm_st) (void)hipStreamDestroy(h->comm_st);
-  if (h->ev_comm) (void)hipEventDestroy(h->ev_comm);
-  if (h->comm_scratch) (void)hipFree(h->comm_scratch);
-  h->comm_st = nullptr; h->ev_comm = nullptr; h->comm_scratch = nullptr;
+  h->comm_st.reset();
+  h->ev_comm.reset();
+  h->comm_scratch.reset();
   h->comm_n = 1; h->comm_rank = 0;
   return NASR_OK;
 }

@@ -38,14 +38,68 @@ extern thread_local const void* t_err_handle;
 
 inline int rup(int x, int m) { return (x + m - 1) / m * m; }
 
+// Owners of the handle's HIP resources: each releases what it holds when it goes (nasr_destroy ends in `delete h`) and
+// converts to the raw pointer / handle, so use sites read h->P, h->Gbase + GRAD_HEAD, h->ev_snap as they would a raw
+// member.  out() releases what is held and hands the slot to a create call: hipMalloc(h->P.out(), bytes).
+template <typename T, hipError_t (*Free)(T)>
+class Owned {
+ public:
+  Owned() = default;
+  Owned(const Owned&) = delete;
+  Owned& operator=(const Owned&) = delete;
+  Owned(Owned&& o) noexcept : v_(o.v_) { o.v_ = T{}; }
+  Owned& operator=(Owned&& o) noexcept { std::swap(v_, o.v_); return *this; }
+  ~Owned() { reset(); }
+  void reset() {
+    if (v_) (void)Free(v_);
+    v_ = T{};
+  }
+  T* out() { reset(); return &v_; }
+  T get() const { return v_; }
+  operator T() const { return v_; }
+
+ private:
+  T v_{};
+};
+template <typename T> hipError_t free_device(T* p) { return hipFree(p); }
+template <typename T> hipError_t free_pinned(T* p) { return hipHostFree(p); }
+template <typename T> using DevPtr = Owned<T*, free_device<T>>;     // hipMalloc
+template <typename T> using Pinned = Owned<T*, free_pinned<T>>;     // hipHostMalloc
+using Event = Owned<hipEvent_t, hipEventDestroy>;
+
+// A stream the handle made (out()) and destroys, or the caller's (borrow()), which outlives the handle.
+class Stream {
+ public:
+  Stream() = default;
+  Stream(const Stream&) = delete;
+  Stream& operator=(const Stream&) = delete;
+  ~Stream() { reset(); }
+  void reset() {
+    if (s_ && own_) (void)hipStreamDestroy(s_);
+    s_ = nullptr;
+    own_ = false;
+  }
+  hipStream_t* out() { reset(); own_ = true; return &s_; }
+  void borrow(hipStream_t s) { reset(); s_ = s; }
+  operator hipStream_t() const { return s_; }
+
+ private:
+  hipStream_t s_ = nullptr;
+  bool own_ = false;
+};
+
 struct DevBuf {
   void* p = nullptr;
   size_t cap = 0;
+  DevBuf() = default;
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  DevBuf(DevBuf&& o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+  DevBuf& operator=(DevBuf&& o) noexcept { std::swap(p, o.p); std::swap(cap, o.cap); return *this; }
+  ~DevBuf() { release(); }
   bool ensure(size_t bytes, bool* grew) {
     if (bytes <= cap) return true;
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
+    release();
     size_t want = bytes + bytes / 8;  // head room: fewer re-allocations for ragged T
     if (hipMalloc(&p, want) != hipSuccess) {
       if (hipMalloc(&p, bytes) != hipSuccess) return false;
@@ -93,9 +147,9 @@ constexpr int NSTAGE = 2;
 enum SlotState { SLOT_FREE = 0, SLOT_FILLING, SLOT_STAGED, SLOT_RESIDENT };
 struct BatchSlot {
   DevBuf dfeats, dmeta;
-  void *hfeats = nullptr, *hmeta = nullptr;      // hipHostMalloc
+  Pinned<void> hfeats, hmeta;
   size_t hfeats_cap = 0, hmeta_cap = 0;
-  hipEvent_t ev_copy = nullptr, ev_released = nullptr;
+  Event ev_copy, ev_released;
   bool copy_valid = false, released_valid = false;
   int state = SLOT_FREE;
   unsigned gen = 0;                              // ticket = slot index | gen << 8
@@ -120,12 +174,11 @@ struct nasr_ctx {
 
   nasr_model_cfg cfg;
   int device = 0;
-  hipStream_t st = nullptr;
-  bool own_stream = false;
+  Stream st;
   // Bulk GEMMs (input projections, input / weight gradients, dense stages): fp32 products from two fp16 planes per
   // operand and three MFMA products (gemm_tph.hip); the planes are tiled copies made once per operand.
-  unsigned char* WfTP = nullptr;       // per layer planes of Wx^T [D*N4][Ip]: B operand of the input GEMM
-  unsigned char* WbTP = nullptr;       // per layer (l >= 1) planes of Wx [Ip][D*N4]: B operand of the input-gradient GEMM
+  DevPtr<unsigned char> WfTP;          // per layer planes of Wx^T [D*N4][Ip]: B operand of the input GEMM
+  DevPtr<unsigned char> WbTP;          // per layer (l >= 1) planes of Wx [Ip][D*N4]: B operand of the input-gradient GEMM
   std::vector<size_t> off_wftp, off_wbtp;
   // Persistent recurrence (lstm_persist.hip): one launch per layer pass instead of T step launches.  Needs the full
   // 8 XCD x 32 CU chip and Hp <= 512; NASR_PERSIST=0 keeps the per-step kernels.
@@ -138,40 +191,40 @@ struct nasr_ctx {
   bool persist_wanted = false;         // the persistent mode is what this handle should run when the device allows it
   int64_t rearm_after = 0, rearm_wait = 0, clean_steps = 0;
   int persist_aborts = 0, persist_rearms = 0;
-  float *Upf = nullptr, *Upb = nullptr;   // [L][D] operand images
+  DevPtr<float> Upf, Upb;              // [L][D] operand images
   // forward recurrence on fp16 planes of U (v_mfma_f32_4x4x4_16B_f16, lstm_persist.hip): column scales / inverse scales of
   // every (layer, direction) matrix, [L*D][N4] each, measured after every optimiser step.  NASR_REC=f32 keeps fp32 MFMAs.
   bool rec_f16 = false;
-  float *Ucs = nullptr, *Ucinv = nullptr;
+  DevPtr<float> Ucs, Ucinv;
   size_t imf = 0, imb = 0;             // floats per (layer, direction) image
   // the hand-offs validate themselves by epoch bits (lstm_persist.hip) and start from cleared buffers: one buffer per
   // layer pass, all of a pass cleared in one go
-  float* xchf = nullptr;               // [L] h exchange buffers of the forward launches (persist_hx_bytes each)
-  float* xchb = nullptr;               // [L] partial-sum exchange buffers of the BPTT launches (persist_px_bytes each)
-  PersistCtl* pctl = nullptr;
+  DevPtr<float> xchf;                  // [L] h exchange buffers of the forward launches (persist_hx_bytes each)
+  DevPtr<float> xchb;                  // [L] partial-sum exchange buffers of the BPTT launches (persist_px_bytes each)
+  DevPtr<PersistCtl> pctl;
   // Wide persistent FORWARD recurrence (lstm_wide.hip): Hp = 2048 (DeepSpeech's cell count), one launch per direction
   // with U resident in the registers of all 256 CUs; the BPTT of such a layer stays on the per-step kernels.  NASR_WIDE=0
   // (or NASR_PERSIST=0) keeps the per-step forward kernels.  Shares the abort / re-arm bookkeeping above.
   bool wide = false, wide_wanted = false;
-  unsigned char* Uw = nullptr;         // [L][D] forward operand images (wide_image_bytes each)
-  unsigned char* Uwb = nullptr;        // [L][D] BPTT operand images (U^T fragments under per-row scales)
-  float *Urs = nullptr, *Urinv = nullptr;   // [L*D][Hp] row scales of every recurrent matrix and their inverses
-  float* wsrow = nullptr;              // [D][64] dG scale per (direction, utterance) of the running BPTT pass
-  void* whx = nullptr;                 // h exchange
-  float* wpart = nullptr;              // cross-XCD inboxes: partial sums (forward) / dG planes (BPTT)
-  void* wpx = nullptr;                 // BPTT: partial dh through the XCD's L2
-  WideCtl* wctl = nullptr;
-  unsigned* perr = nullptr;            // host-mapped sticky error word
+  DevPtr<unsigned char> Uw;            // [L][D] forward operand images (wide_image_bytes each)
+  DevPtr<unsigned char> Uwb;           // [L][D] BPTT operand images (U^T fragments under per-row scales)
+  DevPtr<float> Urs, Urinv;            // [L*D][Hp] row scales of every recurrent matrix and their inverses
+  DevPtr<float> wsrow;                 // [D][64] dG scale per (direction, utterance) of the running BPTT pass
+  DevPtr<void> whx;                    // h exchange
+  DevPtr<float> wpart;                 // cross-XCD inboxes: partial sums (forward) / dG planes (BPTT)
+  DevPtr<void> wpx;                    // BPTT: partial dh through the XCD's L2
+  DevPtr<WideCtl> wctl;
+  Pinned<unsigned> perr;               // host-mapped sticky error word
   // in-library gradient exchange (nasr_comm_*): one RCCL rank per handle, collectives on a side stream
   void* comm = nullptr;                  // ncclComm_t
   // nasr_comm_mean's own communicator (ncclCommSplit of `comm`, same ranks) and stream: the two host floats of a step do
   // not queue up behind the step's gradient buckets.  NULL (old librccl): the mean shares `comm` and waits for them.
   void* comm2 = nullptr;
-  hipStream_t comm_st2 = nullptr;
+  Stream comm_st2;
   int comm_rank = 0, comm_n = 1;
-  hipStream_t comm_st = nullptr;
-  hipEvent_t ev_comm = nullptr;
-  float* comm_scratch = nullptr;         // 64 floats for nasr_comm_mean
+  Stream comm_st;
+  Event ev_comm;
+  DevPtr<float> comm_scratch;            // 64 floats for nasr_comm_mean
 
   // model dims
   int F, Fp, H, Hp, N4, D, L, C, Cp, Pin, Pinp;
@@ -191,18 +244,18 @@ struct nasr_ctx {
   std::vector<int> dWid, dWp, dIn, dIp;
   std::vector<int64_t> off_dw, off_db;
   std::vector<size_t> off_dftp, off_dbtp;
-  unsigned char *DfTP = nullptr, *DbTP = nullptr;   // TP of W_i^T [dWp][dIp] and of W_i [dIp][dWp]
+  DevPtr<unsigned char> DfTP, DbTP;      // TP of W_i^T [dWp][dIp] and of W_i [dIp][dWp]
   std::vector<DevBuf> Ybuf, dYbuf;       // stage outputs and their gradients [R][dWp]
   DevBuf DTP;                            // scratch: TP of a stage input with the frame index as contraction index
   uint32_t drop_seed = 4567u, drop_counter = 0;   // random_seed of networks/deepspeech.py:26
 
-  float *P = nullptr, *M = nullptr, *V = nullptr, *G = nullptr, *Uf = nullptr, *Ub = nullptr;
+  DevPtr<float> P, M, V, Uf, Ub;
+  float* G = nullptr;                        // Gbase + GRAD_HEAD
   // Every operand row of a plane GEMM carries a power-of-two scale (device floats, scale and 1/scale), measured per step
   // for everything whose range is not known in advance.
   struct SV {
     DevBuf s, inv;
     bool ensure(size_t n) { bool g = false; return s.ensure(n * 4, &g) && inv.ensure(n * 4, &g); }
-    void release() { s.release(); inv.release(); }
     float* sp() const { return s.as<float>(); }
     float* ip() const { return inv.as<float>(); }
   };
@@ -217,10 +270,10 @@ struct nasr_ctx {
   int gttp_layer = -1;                       // layer whose transposed dG planes gemm_dx has just written (fused split)
   int dgmax_layer = -1;                      // layer whose |dG| maxima the persistent BPTT kernel has left in `dgmax`
   DevBuf dgmax;                              // [D*32][R] row parts | [8/D][D*N4] column parts (persist_dgmax_floats)
-  float* Gbase = nullptr;                    // allocation behind G: [GRAD_HEAD floats, [0] = fault word][np_int gradients]
+  DevPtr<float> Gbase;                       // allocation behind G: [GRAD_HEAD floats, [0] = fault word][np_int gradients]
   // gradient buckets: (offset, count) in floats from Gbase, in the order backward() completes them; one event each
   std::vector<std::pair<int64_t, int64_t>> buckets;
-  std::vector<hipEvent_t> ev_bucket;
+  std::vector<Event> ev_bucket;
   std::vector<int> bucket_of_layer;          // LSTM layer -> bucket whose last gradients are that layer's (-1: none)
   // Persistent mode: bucket(l)'s event is recorded AFTER the persistent BPTT launch of layer l-1 instead of right after
   // weight_grads(l), so that a collective released by it co-runs with the GEMM phase of layer l-1, not with the launch
@@ -228,17 +281,17 @@ struct nasr_ctx {
   bool bucket_defer = true;
   // Adam's step count t lives ON THE DEVICE (AdamDev, optim.hip): the launch that finds the step's fault word set leaves
   // it alone, so a void step never enters the bias correction - whenever the host learns about it.
-  AdamDev* adam_dev = nullptr;
+  DevPtr<AdamDev> adam_dev;
   float lr;
   // Results of a step without waiting for its end (nasr_get_step_results): loss, the fault word as it stands after the
   // forward pass, and the greedy decode are copied to pinned memory right behind the CTC forward kernels; the fault
   // word at the END of a step is copied behind its Adam launch (nasr_settle_step).  Two slots each: the host may be
   // one step ahead of the device.
-  struct StepRes { void* host = nullptr; size_t cap = 0; uint32_t* stamp = nullptr; uint32_t seq = 0; bool valid = false; int B = 0, Bp = 0, Tp = 0; bool logits = false, greedy = false;
-                   hipEvent_t ev_lg = nullptr; };   // ev_lg: the step's logits have landed in host memory (stream d2h)
+  struct StepRes { Pinned<void> host; size_t cap = 0; Pinned<uint32_t> stamp; uint32_t seq = 0; bool valid = false; int B = 0, Bp = 0, Tp = 0; bool logits = false, greedy = false;
+                   Event ev_lg; };   // ev_lg: the step's logits have landed in host memory (stream d2h)
   StepRes res[2];
   int res_cur = 0;
-  struct StepEnd { float* host = nullptr; uint32_t* stamp = nullptr; uint32_t seq = 0; bool valid = false; int64_t token = 0; };
+  struct StepEnd { Pinned<float> host; uint32_t* stamp = nullptr; uint32_t seq = 0; bool valid = false; int64_t token = 0; };   // stamp: inside host
   static constexpr int NEND = 4;             // steps whose end the host may still ask about (nasr_settle_token)
   StepEnd endw[NEND];
   int end_cur = 0;
@@ -252,9 +305,9 @@ struct nasr_ctx {
   std::vector<int32_t> h_seq;
   BatchSlot slots[NSLOT];
   BatchSlot* cur = nullptr;                  // the resident batch
-  hipStream_t cst = nullptr;                 // copy stream of nasr_stage_batch
-  hipStream_t d2h = nullptr;                 // the step's logits leave on this one, from a snapshot (ctc_forward)
-  hipEvent_t ev_snap = nullptr;
+  Stream cst;                                // copy stream of nasr_stage_batch
+  Stream d2h;                                // the step's logits leave on this one, from a snapshot (ctc_forward)
+  Event ev_snap;
   DevBuf logits_snap;
   std::mutex slot_mu;                        // slot states (nasr_stage_batch may run on a loader thread)
   int slot_rr = 0;
@@ -277,9 +330,10 @@ struct nasr_ctx {
   // from its own copies of everything the main stream rewrites meanwhile (dG^T planes, column scales, partial column sums,
   // slabs: index l & 1), and is joined before layer l's gradients are released / Adam.
   bool wg_overlap = false;
-  hipStream_t wst = nullptr;
-  hipEvent_t ev_dx = nullptr;
-  std::vector<hipEvent_t> ev_wg;             // per layer: its weight gradients are complete
+  bool bwd_lean = false;                     // the side stream exists: persistent BPTT launches leave it room (launch_lstm_persist_bwd)
+  Stream wst;
+  Event ev_dx;
+  std::vector<Event> ev_wg;                  // per layer: its weight gradients are complete
   std::vector<char> wg_pending;              // ... and the main stream has not waited for that yet
   DevBuf GTTP2, csws2, slabs2;
   SV sc_gc2;
@@ -300,11 +354,11 @@ struct nasr_ctx {
 
   // profiling
   bool profiling = false;
-  std::vector<hipEvent_t> ev_pool;
+  std::vector<Event> ev_pool;
   size_t ev_used = 0;
   struct Span { int ph; hipEvent_t a, b; };
   std::vector<Span> spans;
-  hipEvent_t ev_total_a = nullptr, ev_total_b = nullptr;
+  Event ev_total_a, ev_total_b;
   bool window_open = false, total_valid = false;   // timing window [upload|compute_grads .. apply_adam]
   int n_fwd_launch = 0, n_bwd_launch = 0;
   nasr_phase_times last_times;
@@ -387,7 +441,7 @@ struct PhaseScope {
 
 // ---- nasr_batch.hip
 int ensure_shape(nasr_ctx* h, int B, int T, int Lmax);
-bool pinned_ensure(void** p, size_t* cap, size_t bytes);
+bool pinned_ensure(Pinned<void>& p, size_t* cap, size_t bytes);
 void slot_set_state(nasr_ctx* h, BatchSlot* s, int st);
 int slot_commit(nasr_ctx* h, BatchSlot* s);
 int upload(nasr_ctx* h, const float* feats, const int32_t* seq_len, const int32_t* labels, const int32_t* label_len,

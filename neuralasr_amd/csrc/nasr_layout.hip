@@ -31,9 +31,9 @@ void pl_gemm(GemmTPHDesc g, const float* a_inv, const float* b_inv, hipStream_t 
 int persist_check(nasr_ctx* h) {
   if (!h->persist_used) return NASR_OK;
   h->persist_used = false;
-  const unsigned code = *reinterpret_cast<volatile unsigned*>(h->perr);
+  const unsigned code = *reinterpret_cast<volatile unsigned*>(h->perr.get());
   if (!code) return NASR_OK;
-  *reinterpret_cast<volatile unsigned*>(h->perr) = 0;
+  *reinterpret_cast<volatile unsigned*>(h->perr.get()) = 0;
   h->persist = false;
   h->persist_ok = false;
   h->wide = false;
@@ -68,10 +68,9 @@ bool persist_census(nasr_ctx* h) {
     launch_lstm_persist_fwd(dm, h->Upf, h->rec_f16 ? h->Ucinv : nullptr, g.as<float>(), c.as<float>(), o.as<float>(),
                             sq.as<int>(), h->xchf, h->pctl, h->perr, nullptr, 1.f, h->st);
     launch_lstm_persist_bwd(dm, h->Upb, g.as<float>(), dg.as<float>(), c.as<float>(), o.as<float>(), sq.as<int>(),
-                            h->xchb, h->pctl, h->perr, nullptr, h->st);
+                            h->xchb, h->pctl, h->perr, nullptr, h->st, false, nullptr, nullptr, h->bwd_lean);
     ok = hipStreamSynchronize(h->st) == hipSuccess && hipGetLastError() == hipSuccess && *h->perr == 0;
   }
-  for (DevBuf* b : {&g, &c, &o, &dg, &sq}) b->release();
   *h->perr = 0;
   return ok;
 }
@@ -166,11 +165,7 @@ void drop_graphs(nasr_ctx* h) {
 }
 
 hipEvent_t next_event(nasr_ctx* h) {
-  if (h->ev_used == h->ev_pool.size()) {
-    hipEvent_t e;
-    (void)hipEventCreate(&e);
-    h->ev_pool.push_back(e);
-  }
+  if (h->ev_used == h->ev_pool.size()) (void)hipEventCreate(h->ev_pool.emplace_back().out());
   return h->ev_pool[h->ev_used++];
 }
 // ---- model layout ---------------------------------------------------------------------------

@@ -47,7 +47,7 @@ int run_steps(nasr_ctx* h, int l, bool bwd, int s0, int s1, hipStream_t st) {
       launch_lstm_persist_bwd(dm, h->Upb + k * h->imb, h->gates[l].as<float>(), dg_of(h, l), h->cbuf[l].as<float>(),
                               dout_of(h, l), h->seq_p, h->xchb + (size_t)l * (persist_px_bytes() / 4), h->pctl + 1 + h->L + l,
                               h->perr, h->Gbase, st, true, h->dgmax.as<float>(),
-                              h->dgmax.as<float>() + (size_t)h->D * 32 * h->T * h->Bp);
+                              h->dgmax.as<float>() + (size_t)h->D * 32 * h->T * h->Bp, h->bwd_lean);
       h->dgmax_layer = l;
     }
     h->persist_used = true;
@@ -313,15 +313,15 @@ int ctc_forward(nasr_ctx* h) {
     const size_t ids_bytes = 8 + (size_t)h->Bp * 4 + (size_t)h->B * h->Tp * 4;
     const size_t lg_off = (ids_bytes + 255) / 256 * 256, lg_bytes = h->step_logits ? (size_t)h->Tp * h->Bp * h->Cp * 4 : 0;
     const size_t bytes = lg_off + lg_bytes;
-    if (!pinned_ensure(&r.host, &r.cap, bytes)) return h->fail(NASR_ERR_HIP, "hipHostMalloc of the step results failed");
-    char* hp = static_cast<char*>(r.host);
+    if (!pinned_ensure(r.host, &r.cap, bytes)) return h->fail(NASR_ERR_HIP, "hipHostMalloc of the step results failed");
+    char* hp = static_cast<char*>(r.host.get());
     // the step's logits too (before the CTC gradient overwrites them in place): what tf.nn.ctc_beam_search_decoder reads in
     // the reference's train step (tfnetwork.py:61-64,188-189) - the host decodes them while the device runs on
     // They leave from a snapshot on a stream of their own: the compute stream pays a 1 MB device copy, not the PCIe transfer.
     if (lg_bytes) {
       bool grew = false;
       if (!h->logits_snap.ensure(lg_bytes, &grew)) return h->fail(NASR_ERR_HIP, "hipMalloc of the logits snapshot failed");
-      if (!r.ev_lg) HIPCHK(h, hipEventCreateWithFlags(&r.ev_lg, hipEventDisableTiming));
+      if (!r.ev_lg) HIPCHK(h, hipEventCreateWithFlags(r.ev_lg.out(), hipEventDisableTiming));
       nasr_ctx::StepRes& prev = h->res[h->res_cur ^ 1];
       if (prev.logits && prev.ev_lg) HIPCHK(h, hipStreamWaitEvent(h->st, prev.ev_lg, 0));      // the snapshot's last reader (long done)
       HIPCHK(h, hipMemcpyAsync(h->logits_snap.p, h->logits.p, lg_bytes, hipMemcpyDeviceToDevice, h->st));
@@ -362,11 +362,7 @@ int weight_grads(nasr_ctx* h, int l, hipStream_t ws, bool side) {
   const int* vm = h->cmp_rows ? h->vrow_p : nullptr;
   const int nkb = (rows + 15) / 16;
   // The side instantiation splits K exactly as the main one would: every output element then sums the same k-blocks in
-  // the same order whatever the tile shape - the gradients are bitwise those of the serial order.  (NASR_SIDE_SPLIT=own:
-  // the split its own cost model picks, for the A/B logs.)
-  static const int split_mode = [] { const char* e = getenv("NASR_SIDE_SPLIT"); return !e ? 0 : e[0] == 'o' ? 1 : e[0] == '1' ? 2 : 0; }();
-  const bool side_split = side && split_mode == 1;
-  const bool side_one = side && split_mode == 2;       // (A/B logs: no K split at all on the side stream)
+  // the same order whatever the tile shape - the gradients are bitwise those of the serial order.
   // one pass over dG: its transposed planes + 64-row partial column sums (already there when gemm_dx(l) ran)
   if (h->gttp_layer != l) {
     dg_scales(h, l, R, false, ws);
@@ -396,7 +392,7 @@ int weight_grads(nasr_ctx* h, int l, hipStream_t ws, bool side) {
     g.B = GT; g.C = h->G + h->off_wx[l];
     g.M = h->Ip[l]; g.N = D * N4; g.K = rows; g.nkbA = nkb; g.nkbB = nkb; g.ldc = D * N4;
     g.side = side;
-    g.split_k = side_one ? 1 : gemm_tph_pick_split(g.M, g.N, g.K, 1, side_split);
+    g.split_k = gemm_tph_pick_split(g.M, g.N, g.K);
     g.slabs = slabs_for(g.split_k, g.M, g.N);
     if (g.split_k > 1 && !g.slabs) return h->fail(NASR_ERR_HIP, "slab workspace allocation failed");
     pl_gemm(g, ai.cinv, gc.ip(), ws);
@@ -412,7 +408,7 @@ int weight_grads(nasr_ctx* h, int l, hipStream_t ws, bool side) {
     g.c_bstride = (int64_t)Hp * N4;            // off_u[l*D + 1] - off_u[l*D] (build_layout)
     g.a_kshift1 = vm ? 0 : Bp;
     g.side = side;
-    g.split_k = side_one ? 1 : gemm_tph_pick_split(g.M, g.N, g.K, D, side_split);
+    g.split_k = gemm_tph_pick_split(g.M, g.N, g.K, D);
     g.slabs = slabs_for(g.split_k * D, g.M, g.N);
     if (g.split_k > 1 && !g.slabs) return h->fail(NASR_ERR_HIP, "slab workspace allocation failed");
     pl_gemm(g, ao.cinv, gc.ip(), ws, Hp, N4);

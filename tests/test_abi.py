@@ -55,6 +55,20 @@ def test_product_package_never_imports_the_oracle():
                 assert not c_use.search(open(src_path).read()), f'{f} includes oracle code'
 
 
+def test_environment_is_read_only_at_create_and_by_the_test_hooks():
+    """getenv under csrc/ appears only in nasr_create (the create-time switches of README) and in test_hook(): no switch
+    is read at a kernel launch, where it would apply to the whole process and ignore later handles."""
+    csrc = os.path.join(ROOT, 'neuralasr_amd', 'csrc')
+    call = re.compile(r'\bgetenv\s*\(')
+    allowed = {'nasr_api.hip': 'int nasr_create(', 'optim.hip': 'const char* test_hook('}
+    for f in sorted(os.listdir(csrc)):
+        src = re.sub(r'//[^\n]*', '', open(os.path.join(csrc, f)).read())
+        if f in allowed:
+            a = src.index(allowed[f])
+            src = src[:a] + src[src.index('\n}', a):]   # the function's body ends at the first brace in column 0
+        assert not call.search(src), f'{f} reads the environment outside nasr_create / test_hook'
+
+
 def test_bench_touches_the_oracle_only_in_its_cpu_baseline_leg():
     """bench.py builds its workload, synthetic batch and weights itself; `oracle` appears only inside cpu_baseline()
     and the Workload.oracle_spec() helper that leg calls."""

@@ -358,3 +358,44 @@ def test_ctc_lattice_on_flat_sharp_and_pinned_posteriors():
         np.testing.assert_allclose(nll, nllo, rtol=3e-5, atol=1e-5)
         assert rel(grads, O.flatten(go)) < 1e-4
     e.close()
+
+
+LIFECYCLE = {
+    # kind: (spec, B, T, recurrence mode)
+    'persistent-side-stream': (O.ModelSpec(26, 500, 3, True, 'concat', 29), 4, 20, 'persistent'),
+    'per-step': (O.ModelSpec(26, 500, 3, True, 'concat', 29), 4, 20, 'per-step'),
+    'wide': (O.ModelSpec(10, 2048, 1, True, 'concat', 5), 3, 7, 'wide-persistent'),
+    'deepspeech': (O.ModelSpec(14, 20, 1, True, 'concat', 6, pre=(24, 24, 40), post=24, relu_clip=2.0,
+                                dropout=(0.1, 0.1, 0.1, 0.1)), 4, 12, 'persistent'),
+}
+
+
+@pytest.mark.parametrize('kind', list(LIFECYCLE))
+def test_destroy_returns_the_device_memory_of_create_and_a_step(kind, monkeypatch):
+    """nasr_destroy releases every buffer, stream and event nasr_create and a training step made: after one warm-up cycle
+    (code objects, runtime pools), three more create -> train step -> destroy cycles leave the free device memory where it
+    was, within 16 MiB."""
+    import torch
+    from neuralasr_amd.engine import Engine
+    spec, B, T, mode = LIFECYCLE[kind]
+    monkeypatch.setenv('NASR_PERSIST', '0' if kind == 'per-step' else '1')
+    monkeypatch.delenv('NASR_WGRAD_OVERLAP', raising=False)
+    feats, seq_len, labels, label_len = O.synth_batch(spec, B, T, seed=5, var_len=True, Lmin=1, Lmax=3)
+
+    def cycle():
+        e = Engine(spec.feature_size, spec.hidden, spec.num_layers, spec.bidirectional, spec.merge, spec.num_classes,
+                   learning_rate=1e-3, pre=spec.pre, post=spec.post, relu_clip=spec.relu_clip, dropout=spec.dropout)
+        assert e.recurrence_mode == mode
+        assert e.wgrad_overlap == (kind == 'persistent-side-stream')
+        rs = np.random.default_rng(1)
+        e.set_params(rs.standard_normal(e.param_count, dtype=np.float32) * np.float32(0.03))
+        assert np.isfinite(e.train_step(feats, seq_len, labels, label_len))
+        e.close()
+
+    cycle()
+    torch.cuda.synchronize()
+    free0 = torch.cuda.mem_get_info()[0]
+    for _ in range(3):
+        cycle()
+    torch.cuda.synchronize()
+    assert abs(torch.cuda.mem_get_info()[0] - free0) <= 16 << 20
