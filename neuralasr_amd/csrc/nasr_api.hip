@@ -1,6 +1,6 @@
 // nasr_api.hip — the C ABI of include/nasr.h: every entry point names the reference interface it replaces there.  The work
-// behind them lives in nasr_layout.hip (parameters, operand images), nasr_batch.hip (batches), nasr_pass.hip (the step) and
-// nasr_comm.hip (RCCL); the shared handle is nasr_ctx.h.
+// behind them lives in nasr_layout.hip (parameters, operand images), nasr_rec.hip (the recurrence, nasr_*_recurrence_mode),
+// nasr_batch.hip (batches), nasr_pass.hip (the step) and nasr_comm.hip (RCCL); the shared handle is nasr_ctx.h.
 #include "nasr_ctx.h"
 
 using namespace nasr;
@@ -12,7 +12,7 @@ int settle_end(nasr_ctx* h, nasr_ctx::StepEnd& e, int* void_out) {
   if (!wait_stamp(e.stamp, e.seq, 60.0)) return h->fail(NASR_ERR_HIP, "nasr_settle_step: the step did not end within 60 s");
   if (*e.host != 0.f) {
     *void_out = 1;
-    (void)persist_check(h);   // a local abort: this handle continues on the per-step kernels (message in last_error)
+    (void)rec_check(h);   // a local abort: this handle continues on the per-step kernels (message in last_error)
   }
   return NASR_OK;
 }
@@ -183,59 +183,9 @@ int nasr_create(const nasr_model_cfg* cfg, int device_id, void* stream, nasr_han
   (void)hipMemsetAsync(h->Ub, 0, ub, h->st);
   {
     const char* e = getenv("NASR_PERSIST");
-    h->persist = !(e && e[0] == '0') && persist_supported(h->Hp) && prop.multiProcessorCount == 256;
-    if (h->persist) {
-      h->imf = persist_image_floats(h->Hp, false);
-      h->imb = persist_image_floats(h->Hp, true);
-      const size_t nk = (size_t)h->L * h->D;
-      if (persist_prepare() != hipSuccess || hipMalloc(h->Upf.out(), nk * h->imf * 4) != hipSuccess ||
-          hipMalloc(h->Upb.out(), nk * h->imb * 4) != hipSuccess ||
-          hipMalloc(h->xchf.out(), (size_t)h->L * persist_hx_bytes(h->Hp)) != hipSuccess ||
-          hipMalloc(h->xchb.out(), (size_t)h->L * persist_px_bytes()) != hipSuccess ||
-          hipMalloc(h->pctl.out(), (size_t)(1 + 2 * h->L) * sizeof(PersistCtl)) != hipSuccess ||   // [0] census, then one per layer pass
-          hipHostMalloc(h->perr.out(), 64, hipHostMallocMapped) != hipSuccess)
-        return bail(NASR_ERR_HIP, "allocation of the persistent-recurrence buffers failed");
-      *h->perr = 0;
-      const char* er = getenv("NASR_REC");
-      h->rec_f16 = !(er && std::string(er) == "f32");
-      if (h->rec_f16) {
-        bool g2 = false;
-        size_t wsf = 0;
-        for (size_t k = 0; k < nk; ++k) wsf += tph_scale_ws_floats(h->Hp, h->N4);
-        if (hipMalloc(h->Ucs.out(), nk * h->N4 * 4) != hipSuccess || hipMalloc(h->Ucinv.out(), nk * h->N4 * 4) != hipSuccess ||
-            !h->scws.ensure(wsf * 4, &g2))
-          return bail(NASR_ERR_HIP, "allocation of the recurrent-weight scales failed");
-        (void)hipMemsetAsync(h->Ucs, 0, nk * h->N4 * 4, h->st);
-        (void)hipMemsetAsync(h->Ucinv, 0, nk * h->N4 * 4, h->st);
-      }
-      (void)hipMemsetAsync(h->Upf, 0, nk * h->imf * 4, h->st);
-      (void)hipMemsetAsync(h->Upb, 0, nk * h->imb * 4, h->st);
-    }
-  }
-  {
-    const char* e = getenv("NASR_PERSIST");
-    const char* ew = getenv("NASR_WIDE");
-    h->wide = !h->persist && !(e && e[0] == '0') && !(ew && ew[0] == '0') && wide_supported(h->Hp, 16) &&
-              prop.multiProcessorCount == 256;
-    if (h->wide) {
-      const size_t nk = (size_t)h->L * h->D;
-      bool g2 = false;
-      size_t wsf = 0;
-      for (size_t k = 0; k < nk; ++k) wsf += tph_scale_ws_floats(h->Hp, h->N4);
-      if (wide_prepare() != hipSuccess || hipMalloc(h->Uw.out(), nk * wide_image_bytes(h->Hp)) != hipSuccess ||
-          hipMalloc(h->whx.out(), wide_hx_bytes(64)) != hipSuccess || hipMalloc(h->wpart.out(), wide_part_bytes(64)) != hipSuccess ||
-          hipMalloc(h->wctl.out(), sizeof(WideCtl)) != hipSuccess || hipMalloc(h->Uwb.out(), nk * wide_image_bytes(h->Hp)) != hipSuccess ||
-          hipMalloc(h->wpx.out(), wide_px_bytes(64)) != hipSuccess || hipMalloc(h->Urs.out(), nk * h->Hp * 4) != hipSuccess ||
-          hipMalloc(h->Urinv.out(), nk * h->Hp * 4) != hipSuccess || hipMalloc(h->wsrow.out(), 2 * 64 * 4) != hipSuccess ||
-          hipMalloc(h->Ucs.out(), nk * h->N4 * 4) != hipSuccess ||
-          hipMalloc(h->Ucinv.out(), nk * h->N4 * 4) != hipSuccess || !h->scws.ensure(wsf * 4, &g2) ||
-          (!h->perr && hipHostMalloc(h->perr.out(), 64, hipHostMallocMapped) != hipSuccess))
-        return bail(NASR_ERR_HIP, "allocation of the wide persistent-recurrence buffers failed");
-      *h->perr = 0;
-      (void)hipMemsetAsync(h->whx, 0, wide_hx_bytes(64), h->st);
-      (void)hipMemsetAsync(h->wpx, 0, wide_px_bytes(64), h->st);
-      h->wide_wanted = true;
-    }
+    const char* er = getenv("NASR_REC");
+    if (rec_setup(h, !(e && e[0] == '0') && prop.multiProcessorCount == 256, er && std::string(er) == "f32") != NASR_OK)
+      return bail(NASR_ERR_HIP, t_err);
   }
   h->gates.resize(h->L);
   h->OTT.resize(h->L);
@@ -250,7 +200,7 @@ int nasr_create(const nasr_model_cfg* cfg, int device_id, void* stream, nasr_han
     return bail(NASR_ERR_HIP, "hipStreamCreate (results stream) failed");
   {
     const char* eo = getenv("NASR_WGRAD_OVERLAP");
-    const bool eligible = h->persist && h->Hp == 512 && h->L > 1;
+    const bool eligible = h->rec_kind == RecKind::Persist && h->Hp == 512 && h->L > 1;
     h->wg_overlap = eligible && !(eo && eo[0] == '0');          // on unless NASR_WGRAD_OVERLAP=0 (nasr_set_wgrad_overlap)
     h->ev_wg.resize(h->L);
     h->wg_pending.assign(h->L, 0);
@@ -285,17 +235,15 @@ int nasr_create(const nasr_model_cfg* cfg, int device_id, void* stream, nasr_han
   (void)hipEventCreate(h->ev_total_b.out());
   memset(&h->last_times, 0, sizeof(h->last_times));
   if (hipStreamSynchronize(h->st) != hipSuccess) return bail(NASR_ERR_HIP, "stream synchronize failed in create");
-  if (h->persist || h->wide) {
+  if (h->rec_kind != RecKind::Step) {
     const char* er = getenv("NASR_PERSIST_REARM");
     h->rearm_after = er && *er ? std::max<long long>(0, atoll(er)) : 200;
   }
-  if (h->persist) {
-    if (!persist_census(h)) h->persist = false;
-    h->persist_ok = h->persist;
-    h->persist_wanted = h->persist;
+  if (h->rec_kind == RecKind::Persist) {
     const char* eb = getenv("NASR_BUCKET_DEFER");
     h->bucket_defer = !(eb && eb[0] == '0');
   }
+  rec_start(h);   // the census, after the weight-gradient side stream that its BPTT launch makes room for
   *out = h;
   return NASR_OK;
 }
@@ -455,7 +403,7 @@ int nasr_compute_grads(nasr_handle h) {
     h->window_open = true;
     h->total_valid = false;
   }
-  persist_rearm(h);
+  rec_rearm(h);
   int rc = forward(h);   // clears the step's fault word
   if (rc) return rc;
   rc = ctc_forward(h);
@@ -592,7 +540,7 @@ int nasr_step_void(nasr_handle h, int* void_out) {
   float fault = 0.f;
   HIPCHK(h, hipMemcpyAsync(&fault, h->Gbase, 4, hipMemcpyDeviceToHost, h->st));
   HIPCHK(h, hipStreamSynchronize(h->st));
-  (void)persist_check(h);   // a local abort: switch this handle to the per-step kernels (the message stays in last_error)
+  (void)rec_check(h);   // a local abort: switch this handle to the per-step kernels (the message stays in last_error)
   *void_out = fault != 0.f ? 1 : 0;
   return NASR_OK;
 }
@@ -812,24 +760,6 @@ int nasr_get_dropout_state(nasr_handle h, uint32_t* seed, uint32_t* counter) {
   if (seed) *seed = h->drop_seed;
   if (counter) *counter = h->drop_counter;
   return NASR_OK;
-}
-
-int nasr_get_recurrence_mode(nasr_handle h) { return !h ? 0 : h->persist ? 1 : h->wide ? 2 : 0; }
-
-int nasr_set_recurrence_mode(nasr_handle h, int persistent) {
-  if (!h) return NASR_ERR_ARG;
-  if (h->Uw) {   // a wide layer: the wide forward kernel on / off
-    HIPCHK(h, hipStreamSynchronize(h->st));
-    h->wide = persistent != 0;
-    h->wide_wanted = h->wide;
-    return repack(h);
-  }
-  if (persistent && !h->persist_ok)
-    return h->fail(NASR_ERR_STATE, "the persistent recurrence is not available on this device / hidden size");
-  HIPCHK(h, hipStreamSynchronize(h->st));
-  h->persist = persistent != 0;
-  h->persist_wanted = h->persist;
-  return repack(h);
 }
 
 int nasr_set_wgrad_overlap(nasr_handle h, int enabled) {

@@ -24,7 +24,7 @@ int ensure_shape(nasr_ctx* h, int B, int T, int Lmax) {
   ok &= h->partial.ensure((size_t)2 * D * (Hp / 32) * Bp * Hp * 4, &grew);
   ok &= h->dcstate.ensure((size_t)2 * D * Bp * Hp * 4, &grew);
   ok &= h->dgbuf.ensure(R * D * N4 * 4, &grew);
-  if (h->Upf) ok &= h->dgmax.ensure(persist_dgmax_floats(T, Bp, Hp, D) * 4, &grew);
+  if (h->rec_kind == RecKind::Persist) ok &= h->dgmax.ensure(persist_dgmax_floats(T, Bp, Hp, D) * 4, &grew);
   {
     int ipmax = h->Fp, wmax = D * N4;
     for (int l = 0; l < h->L; ++l) ipmax = std::max(ipmax, h->Ip[l]);

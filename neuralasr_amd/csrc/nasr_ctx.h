@@ -1,6 +1,7 @@
 // nasr_ctx.h — what the translation units behind include/nasr.h share: the handle (struct nasr_ctx: model layout, HBM buffers,
 // batch slots, streams / events, recurrence mode), small helpers, and the functions they call in each other (internal, C++).
-//   nasr_layout.hip  parameter layout, TF <-> internal maps, operand images (repack), persistent-mode management
+//   nasr_layout.hip  parameter layout, TF <-> internal maps, operand images (repack)
+//   nasr_rec.hip     the recurrence's kind: create-time set-up and census, resident launches, abort check, re-arming
 //   nasr_batch.hip   batch buffers and slots: upload, stage / commit
 //   nasr_pass.hip    forward, CTC, backward: the orchestration of one step on the handle's streams
 //   nasr_api.hip     the C ABI entry points
@@ -164,6 +165,9 @@ struct BatchSlot {
   int32_t* meta_d() const { return dmeta.as<int32_t>(); }
 };
 
+// the kinds of kernels that run the recurrence; the values are the codes of nasr_get_recurrence_mode
+enum class RecKind { Step = 0, Persist = 1, Wide = 2 };
+
 }  // namespace nasr_impl
 
 // (internal header: the translation units behind the ABI use both namespaces unqualified)
@@ -180,33 +184,32 @@ struct nasr_ctx {
   DevPtr<unsigned char> WfTP;          // per layer planes of Wx^T [D*N4][Ip]: B operand of the input GEMM
   DevPtr<unsigned char> WbTP;          // per layer (l >= 1) planes of Wx [Ip][D*N4]: B operand of the input-gradient GEMM
   std::vector<size_t> off_wftp, off_wbtp;
-  // Persistent recurrence (lstm_persist.hip): one launch per layer pass instead of T step launches.  Needs the full
-  // 8 XCD x 32 CU chip and Hp <= 512; NASR_PERSIST=0 keeps the per-step kernels.
-  bool persist = false;
-  bool persist_ok = false;             // the device passed the census at create time
-  bool persist_used = false;           // a persistent launch is in flight since the last check of *perr
-  // re-arming the persistent recurrence after an abort (persist_check): the per-step kernels serve `rearm_after` clean
-  // steps, then the census of nasr_create runs again and, if it passes, the persistent kernels come back; every further
-  // abort doubles the wait.  NASR_PERSIST_REARM sets the first wait (0 = never re-arm).
-  bool persist_wanted = false;         // the persistent mode is what this handle should run when the device allows it
+  // The recurrence (nasr_rec.hip): the per-step kernels (lstm.hip, one launch per timestep), the persistent kernels for
+  // Hp <= 512 (lstm_persist.hip, one launch per layer pass) or the wide ones for Hp = 2048 (lstm_wide.hip, one launch per
+  // direction and pass).  The resident kinds need the full 8 XCD x 32 CU chip; NASR_PERSIST=0 keeps the per-step kernels.
+  RecKind rec_kind = RecKind::Step;    // kind: the resident kind set up at create (Step: none, or the census failed)
+  RecKind rec_use = RecKind::Step;     // in use: Step or the kind (nasr_get_recurrence_mode)
+  bool rec_wanted = false;             // wanted: the kind is what this handle should run when the device allows it
+  bool rec_inflight = false;           // inflight: a resident launch has run since *perr was last checked
+  bool rec_refused = false;            // refused until re-armed: an abort sets it; the persistent kind refuses set(1) meanwhile
+  // re-arming after an abort (rec_check): `rearm_after` clean steps on the per-step kernels, then back to the kind (rec_rearm);
+  // every further abort doubles the wait.  NASR_PERSIST_REARM sets the first wait (0 = never re-arm).
   int64_t rearm_after = 0, rearm_wait = 0, clean_steps = 0;
   int persist_aborts = 0, persist_rearms = 0;
-  DevPtr<float> Upf, Upb;              // [L][D] operand images
-  // forward recurrence on fp16 planes of U (v_mfma_f32_4x4x4_16B_f16, lstm_persist.hip): column scales / inverse scales of
-  // every (layer, direction) matrix, [L*D][N4] each, measured after every optimiser step.  NASR_REC=f32 keeps fp32 MFMAs.
+  Pinned<unsigned> perr;               // host-mapped sticky error word of the resident launches
+  DevPtr<float> Ucs, Ucinv;            // [L*D][N4] column scales / inverse scales of every (layer, direction) recurrent matrix
+  // the persistent kind: [L][D] operand images; the forward recurrence on fp16 planes of U (v_mfma_f32_4x4x4_16B_f16)
+  // under the column scales Ucs, measured after every optimiser step.  NASR_REC=f32 keeps fp32 MFMAs.
   bool rec_f16 = false;
-  DevPtr<float> Ucs, Ucinv;
+  DevPtr<float> Upf, Upb;
   size_t imf = 0, imb = 0;             // floats per (layer, direction) image
   // the hand-offs validate themselves by epoch bits (lstm_persist.hip) and start from cleared buffers: one buffer per
   // layer pass, all of a pass cleared in one go
   DevPtr<float> xchf;                  // [L] h exchange buffers of the forward launches (persist_hx_bytes each)
   DevPtr<float> xchb;                  // [L] partial-sum exchange buffers of the BPTT launches (persist_px_bytes each)
   DevPtr<PersistCtl> pctl;
-  // Wide persistent FORWARD recurrence (lstm_wide.hip): Hp = 2048 (DeepSpeech's cell count), one launch per direction
-  // with U resident in the registers of all 256 CUs; the BPTT of such a layer stays on the per-step kernels.  NASR_WIDE=0
-  // (or NASR_PERSIST=0) keeps the per-step forward kernels.  Shares the abort / re-arm bookkeeping above.
-  bool wide = false, wide_wanted = false;
-  DevPtr<unsigned char> Uw;            // [L][D] forward operand images (wide_image_bytes each)
+  // the wide kind: U resident in the registers of all 256 CUs, forward and BPTT
+  DevPtr<unsigned char> Uw;            // [L][D] forward operand images (wide_image_bytes each) under the column scales Ucs
   DevPtr<unsigned char> Uwb;           // [L][D] BPTT operand images (U^T fragments under per-row scales)
   DevPtr<float> Urs, Urinv;            // [L*D][Hp] row scales of every recurrent matrix and their inverses
   DevPtr<float> wsrow;                 // [D][64] dG scale per (direction, utterance) of the running BPTT pass
@@ -214,7 +217,6 @@ struct nasr_ctx {
   DevPtr<float> wpart;                 // cross-XCD inboxes: partial sums (forward) / dG planes (BPTT)
   DevPtr<void> wpx;                    // BPTT: partial dh through the XCD's L2
   DevPtr<WideCtl> wctl;
-  Pinned<unsigned> perr;               // host-mapped sticky error word
   // in-library gradient exchange (nasr_comm_*): one RCCL rank per handle, collectives on a side stream
   void* comm = nullptr;                  // ncclComm_t
   // nasr_comm_mean's own communicator (ncclCommSplit of `comm`, same ranks) and stream: the two host floats of a step do
@@ -409,9 +411,6 @@ int build_layout(nasr_ctx* h);
 int repack(nasr_ctx* h);
 int scatter_to_device(nasr_ctx* h, const float* tf_flat, float* dev);
 int gather_from_device(nasr_ctx* h, const float* dev, float* tf_flat);
-int persist_check(nasr_ctx* h);
-bool persist_census(nasr_ctx* h);
-void persist_rearm(nasr_ctx* h);
 // a word in host-mapped pinned memory written in stream order (and, with f0_dst, a device float copied beside it)
 void launch_stamp(unsigned* dst, unsigned value, float* f0_dst, const float* f0_src, hipStream_t st);
 void launch_publish_results(const float* loss, const float* fault, const int* lens, int Bp, const int* ids, int n_ids, void* host,
@@ -438,6 +437,15 @@ struct PhaseScope {
     }
   }
 };
+
+// ---- nasr_rec.hip
+int rec_setup(nasr_ctx* h, bool allowed, bool f32);   // allowed: NASR_PERSIST is not 0 and the chip is whole; f32: NASR_REC=f32
+void rec_start(nasr_ctx* h);                          // the census, once the handle's streams exist
+int rec_launch(nasr_ctx* h, int l, bool bwd, hipStream_t st, int* launches);
+int rec_check(nasr_ctx* h);
+void rec_rearm(nasr_ctx* h);
+std::vector<TphScaleJob> rec_scale_jobs(const nasr_ctx* h);   // repack: scale jobs, then images of the recurrent matrices
+void rec_images(nasr_ctx* h);
 
 // ---- nasr_batch.hip
 int ensure_shape(nasr_ctx* h, int B, int T, int Lmax);

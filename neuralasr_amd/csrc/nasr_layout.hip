@@ -1,6 +1,6 @@
 // nasr_layout.hip — parameter layout of a handle (TF variable order <-> the padded internal buffers), the operand images the
-// kernels keep of the weights (repack), host <-> device parameter copies, and the management of the persistent recurrence
-// mode (abort handling, census, re-arming).  See include/nasr.h and DESIGN.md §3.
+// kernels keep of the weights (repack; the recurrent matrices' images are nasr_rec.hip's), host <-> device parameter
+// copies.  See include/nasr.h and DESIGN.md §3.
 #include "nasr_ctx.h"
 
 using namespace nasr;
@@ -27,83 +27,6 @@ void pl_split(const float* src, unsigned char* tpN, unsigned char* tpT, int rows
 void pl_gemm(GemmTPHDesc g, const float* a_inv, const float* b_inv, hipStream_t st, int64_t ainv_bstride, int64_t binv_bstride) {
   g.a_inv = a_inv; g.b_inv = b_inv; g.ainv_bstride = ainv_bstride; g.binv_bstride = binv_bstride;
   launch_gemm_tph(g, st);
-}
-int persist_check(nasr_ctx* h) {
-  if (!h->persist_used) return NASR_OK;
-  h->persist_used = false;
-  const unsigned code = *reinterpret_cast<volatile unsigned*>(h->perr.get());
-  if (!code) return NASR_OK;
-  *reinterpret_cast<volatile unsigned*>(h->perr.get()) = 0;
-  h->persist = false;
-  h->persist_ok = false;
-  h->wide = false;
-  h->persist_aborts += 1;
-  h->clean_steps = 0;
-  h->rearm_wait = h->persist_aborts <= 1 ? h->rearm_after : std::min<int64_t>(h->rearm_wait * 2, (int64_t)1 << 20);
-  (void)repack(h);   // operand images of the per-step kernels
-  return h->fail(NASR_ERR_HIP, "persistent recurrence aborted (code " + std::to_string(code) +
-                                   ": 1 = hand-off timeout, 2 = workgroup placement, 4 = dG beyond its fp16 planes); the results of this step are "
-                                   "invalid, later steps use the per-step kernels" +
-                                   (h->rearm_wait > 0 ? " (the persistent kernels are tried again after " +
-                                                            std::to_string(h->rearm_wait) + " clean steps)"
-                                                      : ""));
-}
-
-// Census: two steps of both persistent kernels on a zero layer.  A chip that does not place 32 workgroups on each of
-// its 8 XCDs (partition modes, masked CUs, a co-tenant) is detected here and served by the per-step kernels.
-// Synchronises the stream.
-bool persist_census(nasr_ctx* h) {
-  const int Bp = 16, T = 2;
-  const size_t R = (size_t)T * Bp;
-  DevBuf g, c, o, dg, sq;
-  bool grew = false;
-  bool ok = g.ensure(R * h->D * h->N4 * 4, &grew) && c.ensure(R * h->D * h->Hp * 4, &grew) &&
-            o.ensure(R * h->D * h->Hp * 4, &grew) && dg.ensure(R * h->D * h->N4 * 4, &grew) && sq.ensure(Bp * 4, &grew);
-  if (ok) {
-    (void)hipMemsetAsync(g.p, 0, R * h->D * h->N4 * 4, h->st);
-    (void)hipMemsetAsync(o.p, 0, R * h->D * h->Hp * 4, h->st);
-    std::vector<int32_t> two((size_t)Bp, T);
-    (void)hipMemcpyAsync(sq.p, two.data(), Bp * 4, hipMemcpyHostToDevice, h->st);
-    const LstmDims dm{T, Bp, Bp, h->H, h->Hp, h->D};
-    launch_lstm_persist_fwd(dm, h->Upf, h->rec_f16 ? h->Ucinv : nullptr, g.as<float>(), c.as<float>(), o.as<float>(),
-                            sq.as<int>(), h->xchf, h->pctl, h->perr, nullptr, 1.f, h->st);
-    launch_lstm_persist_bwd(dm, h->Upb, g.as<float>(), dg.as<float>(), c.as<float>(), o.as<float>(), sq.as<int>(),
-                            h->xchb, h->pctl, h->perr, nullptr, h->st, false, nullptr, nullptr, h->bwd_lean);
-    ok = hipStreamSynchronize(h->st) == hipSuccess && hipGetLastError() == hipSuccess && *h->perr == 0;
-  }
-  *h->perr = 0;
-  return ok;
-}
-
-// After `rearm_wait` clean steps on the per-step kernels: run the census again and go back to the persistent kernels
-// (called at the start of a step, before anything of it is enqueued).
-void persist_rearm(nasr_ctx* h) {
-  if (h->wide_wanted && !h->wide && h->persist_aborts > 0 && h->rearm_wait > 0) {
-    // the wide forward kernel has no census launch of its own: its next launch is the census (a second abort voids that
-    // step, which the caller repeats on the per-step kernels, and doubles the wait)
-    if (++h->clean_steps <= h->rearm_wait) return;
-    h->clean_steps = 0;
-    if (hipStreamSynchronize(h->st) != hipSuccess) return;
-    h->wide = true;
-    if (repack(h) != NASR_OK) { h->wide = false; return; }
-    h->persist_rearms += 1;
-    return;
-  }
-  if (h->persist || !h->persist_wanted || h->persist_aborts == 0 || h->rearm_wait <= 0 || !h->Upf) return;
-  if (++h->clean_steps <= h->rearm_wait) return;   // `rearm_wait` whole steps ran on the per-step kernels since the abort
-  h->clean_steps = 0;
-  if (hipStreamSynchronize(h->st) != hipSuccess) return;
-  // the operand images of the persistent kernels are stale (repack() only maintains the mode in use): rebuild first
-  h->persist = true;
-  if (repack(h) != NASR_OK || !persist_census(h)) {
-    h->persist = false;
-    h->rearm_wait = std::min<int64_t>(h->rearm_wait * 2, (int64_t)1 << 20);
-    (void)repack(h);
-    return;
-  }
-  h->persist_ok = true;
-  h->persist_rearms += 1;
-  drop_graphs(h);
 }
 // A word in host-mapped pinned memory, written by a one-thread kernel in stream order (system-scope store): the host
 // learns that everything enqueued before it has happened by READING MEMORY - no runtime call, no event.  (Waiting on a HIP
@@ -156,7 +79,7 @@ bool wait_stamp(const uint32_t* w, uint32_t want, double timeout_s) {
 
 int sync_checked(nasr_ctx* h) {
   HIPCHK(h, hipStreamSynchronize(h->st));
-  return persist_check(h);
+  return rec_check(h);
 }
 
 void drop_graphs(nasr_ctx* h) {
@@ -323,17 +246,10 @@ int build_layout(nasr_ctx* h) {
 }
 
 int repack(nasr_ctx* h) {
-  // only the operand images of the kernels in use (a mode switch calls repack again)
+  // only the operand images of the kernels in use (a switch of the recurrence's kind calls repack again)
   // scales of every matrix that needs them - recurrent matrices of the persistent / wide kernels, input and dense
   // weights of the plane GEMMs - in ONE batch (two launches), then the images
-  std::vector<TphScaleJob> jobs;
-  if (h->persist && h->rec_f16)
-    for (size_t k = 0; k < h->off_u.size(); ++k)
-      jobs.push_back({h->P + h->off_u[k], h->Hp, h->N4, h->N4, nullptr, nullptr, h->Ucs + k * h->N4, h->Ucinv + k * h->N4});
-  if (!h->persist && h->wide)
-    for (size_t k = 0; k < h->off_u.size(); ++k)
-      jobs.push_back({h->P + h->off_u[k], h->Hp, h->N4, h->N4, h->Urs + k * h->Hp, h->Urinv + k * h->Hp,
-                      h->Ucs + k * h->N4, h->Ucinv + k * h->N4});
+  std::vector<TphScaleJob> jobs = rec_scale_jobs(h);
   for (int l = 0; l < h->L; ++l) {
     const bool back = l > 0 || h->npre > 0;
     jobs.push_back({h->P + h->off_wx[l], h->Ip[l], h->D * h->N4, h->D * h->N4, back ? h->sc_wr[l].sp() : nullptr,
@@ -350,23 +266,7 @@ int repack(nasr_ctx* h) {
       return h->fail(NASR_ERR_HIP, "allocation of the scale workspace failed");
   }
   launch_tph_scales_batch(jobs.data(), (int)jobs.size(), h->scws.as<float>(), h->st);
-  if (h->persist) {
-    launch_repack_persist(h->P, h->off_u.data(), (int)h->off_u.size(), h->Upf, h->Upb, h->Hp,
-                          h->rec_f16 ? h->Ucs : nullptr, h->st);
-  } else {
-    if (!h->wide)   // (a fall-back from the wide kernels calls repack again: persist_check)
-      for (int l = 0; l < h->L; ++l)
-        for (int d = 0; d < h->D; ++d) {
-          const size_t k = (size_t)l * h->D + d;
-          const size_t o = k * (size_t)h->Hp * h->N4;
-          launch_repack_u(h->P + h->off_u[k], h->Uf + o, h->Ub + o, h->Hp, h->st);
-        }
-    if (h->wide)    // the fp16-plane images of the wide kernels
-      for (size_t k = 0; k < h->off_u.size(); ++k) {
-        launch_repack_wide(h->P + h->off_u[k], h->Ucs + k * h->N4, h->Uw + k * wide_image_bytes(h->Hp), h->Hp, h->st);
-        launch_repack_wide_bwd(h->P + h->off_u[k], h->Urs + k * h->Hp, h->Uwb + k * wide_image_bytes(h->Hp), h->Hp, h->st);
-      }
-  }
+  rec_images(h);
   for (int l = 0; l < h->L; ++l) {
     // forward operand = planes of Wx^T, input-gradient operand = planes of Wx: one pass where both are needed
     const bool back = l > 0 || h->npre > 0;

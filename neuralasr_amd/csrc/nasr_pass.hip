@@ -9,51 +9,12 @@ using namespace nasr_impl;
 
 namespace nasr_impl {
 
-// ---- the per-timestep loops over steps [s0, s1), optionally replayed from a hipGraph -----------
-int run_steps(nasr_ctx* h, int l, bool bwd, int s0, int s1, hipStream_t st) {
+// ---- one layer pass of the recurrence: the whole pass in the resident kind in use (nasr_rec.hip), or the per-timestep
+// loops over steps [s0, s1), optionally replayed from a hipGraph.  *launches += the recurrence launches it enqueued.
+int run_steps(nasr_ctx* h, int l, bool bwd, int s0, int s1, hipStream_t st, int* launches) {
+  if (h->rec_use != RecKind::Step && s0 == 0 && s1 == h->T) return rec_launch(h, l, bwd, st, launches);
+  *launches += s1 - s0;
   const LstmDims dm{h->T, h->B, h->Bp, h->H, h->Hp, h->D};
-  if (!bwd && h->wide && s0 == 0 && s1 == h->T && wide_supported(h->Hp, h->Bp)) {
-    for (int d = 0; d < h->D; ++d) {
-      const size_t k = (size_t)l * h->D + d;
-      launch_lstm_wide_fwd(dm, d, h->Uw + k * wide_image_bytes(h->Hp), h->Ucinv + k * h->N4, h->gates[l].as<float>(),
-                           h->cbuf[l].as<float>(), h->outb[l].as<float>(), h->seq_p, h->whx, h->wpart, h->wctl, h->perr,
-                           h->Gbase, h->cfg.forget_bias, st);
-    }
-    h->persist_used = true;
-    HIPCHK(h, hipGetLastError());
-    return NASR_OK;
-  }
-  if (bwd && h->wide && s0 == 0 && s1 == h->T && wide_supported(h->Hp, h->Bp)) {
-    launch_wide_row_scales(dm, dout_of(h, l), h->seq_p, h->wsrow, st);
-    for (int d = 0; d < h->D; ++d) {
-      const size_t k = (size_t)l * h->D + d;
-      launch_lstm_wide_bwd(dm, d, h->Uwb + k * wide_image_bytes(h->Hp), h->Urinv + k * h->Hp, h->wsrow,
-                           h->gates[l].as<float>(), dg_of(h, l), h->cbuf[l].as<float>(), dout_of(h, l), h->seq_p, h->wpart,
-                           h->wpx, h->wctl, h->perr, h->Gbase, st);
-    }
-    h->persist_used = true;
-    HIPCHK(h, hipGetLastError());
-    return NASR_OK;
-  }
-  if (h->persist && s0 == 0 && s1 == h->T) {
-    const size_t k = (size_t)l * h->D;
-    if (!bwd)
-      launch_lstm_persist_fwd(dm, h->Upf + k * h->imf, h->rec_f16 ? h->Ucinv + k * h->N4 : nullptr,
-                              h->gates[l].as<float>(), h->cbuf[l].as<float>(),
-                              h->outb[l].as<float>(), h->seq_p, h->xchf + (size_t)l * (persist_hx_bytes(h->Hp) / 4),
-                              h->pctl + 1 + l, h->perr, h->Gbase, h->cfg.forget_bias, st, true);
-    else
-    {
-      launch_lstm_persist_bwd(dm, h->Upb + k * h->imb, h->gates[l].as<float>(), dg_of(h, l), h->cbuf[l].as<float>(),
-                              dout_of(h, l), h->seq_p, h->xchb + (size_t)l * (persist_px_bytes() / 4), h->pctl + 1 + h->L + l,
-                              h->perr, h->Gbase, st, true, h->dgmax.as<float>(),
-                              h->dgmax.as<float>() + (size_t)h->D * 32 * h->T * h->Bp, h->bwd_lean);
-      h->dgmax_layer = l;
-    }
-    h->persist_used = true;
-    HIPCHK(h, hipGetLastError());
-    return NASR_OK;
-  }
   const size_t sU = (size_t)l * h->D * h->Hp * h->N4;
   const size_t hs = (size_t)h->D * h->Bp * h->Hp;   // one h-state image
   const size_t ps = (size_t)h->D * lstm_bwd_partials(h->Hp) * h->Bp * h->Hp;   // one partial-sum image
@@ -238,7 +199,7 @@ int forward(nasr_ctx* h) {
   // said is gone with it
   HIPCHK(h, hipMemsetAsync(h->Gbase, 0, GRAD_HEAD * 4, h->st));
   // the control blocks of this pass's persistent launches, cleared in one go (one per layer: run_steps)
-  if (h->persist) {
+  if (h->rec_use == RecKind::Persist) {
     HIPCHK(h, hipMemsetAsync(h->pctl + 1, 0, (size_t)h->L * sizeof(PersistCtl), h->st));
     HIPCHK(h, hipMemsetAsync(h->xchf, 0, (size_t)h->L * persist_hx_bytes(h->Hp), h->st));   // epoch 0 everywhere (lstm_persist.hip)
   }
@@ -254,9 +215,8 @@ int forward(nasr_ctx* h) {
       HIPCHK(h, hipGetLastError());
     }
     PhaseScope ps(h, PH_RECF);
-    int rc = run_steps(h, l, false, 0, T, h->st);
+    int rc = run_steps(h, l, false, 0, T, h->st, &h->n_fwd_launch);
     if (rc) return rc;
-    h->n_fwd_launch += h->persist ? 1 : (h->wide && wide_supported(h->Hp, h->Bp)) ? D : T;
   }
   if (h->has_post) {
     PhaseScope ps(h, PH_XPROJ);
@@ -430,7 +390,7 @@ int backward(nasr_ctx* h) {
   const int Bp = h->Bp, T = h->T, D = h->D, Hp = h->Hp;
   const int R = T * Bp, Rp = h->Tp * Bp;
   const bool sr = h->cfg.merge == NASR_MERGE_STACK_RESHAPE && D == 2;
-  if (h->persist) {
+  if (h->rec_use == RecKind::Persist) {
     HIPCHK(h, hipMemsetAsync(h->pctl + 1 + h->L, 0, (size_t)h->L * sizeof(PersistCtl), h->st));
     HIPCHK(h, hipMemsetAsync(h->xchb, 0, (size_t)h->L * persist_px_bytes(), h->st));   // epoch 0 everywhere (lstm_persist.hip)
   }
@@ -476,12 +436,11 @@ int backward(nasr_ctx* h) {
   h->n_bwd_launch = 0;
   h->dgmax_layer = -1;
   for (int l = h->L - 1; l >= 0; --l) {
-    const bool defer = (h->persist || h->wide) && h->bucket_defer;
+    const bool defer = h->rec_use != RecKind::Step && h->bucket_defer;
     {
       PhaseScope ps(h, PH_RECB);
-      int rc = run_steps(h, l, true, 0, T, h->st);
+      int rc = run_steps(h, l, true, 0, T, h->st, &h->n_bwd_launch);
       if (rc) return rc;
-      h->n_bwd_launch += h->persist ? 1 : (h->wide && wide_supported(h->Hp, h->Bp)) ? D : T;
     }
     if (defer && l + 1 < h->L && h->bucket_of_layer[l + 1] >= 0) {   // the layer above's bucket, held back over this launch
       if (int rc = wg_join(h, l + 1)) return rc;
@@ -494,7 +453,7 @@ int backward(nasr_ctx* h) {
     if (l > 0 || h->npre > 0) gemm_dx(h, l, R, h->st);   // critical path first
     // layer l's weight gradients feed nothing before Adam: with the overlap on they leave the main stream here and run
     // beside the persistent BPTT launch of layer l-1 (tfnetwork.py:120-128: the gradients are a set, nothing orders them)
-    const bool side = h->wg_overlap && h->persist && l > 0 && h->gttp_layer == l;
+    const bool side = h->wg_overlap && h->rec_use == RecKind::Persist && l > 0 && h->gttp_layer == l;
     if (side) {
       HIPCHK(h, hipEventRecord(h->ev_dx, h->st));
       HIPCHK(h, hipStreamWaitEvent(h->wst, h->ev_dx, 0));

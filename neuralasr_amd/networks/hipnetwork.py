@@ -169,7 +169,7 @@ class HipNetwork(Network):
 
     def _retry_aborted(self, fn):
         """Run fn(); if this rank's persistent recurrence gave up in it (the handle has then switched to the per-step
-        kernels, nasr_api.hip persist_check), run it once more.  Forward-only calls have no collective inside, so a
+        kernels, nasr_rec.hip rec_check), run it once more.  Forward-only calls have no collective inside, so a
         local repeat keeps multi-rank runs in step."""
         from .._lib import NasrError
         try:

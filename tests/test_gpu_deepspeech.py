@@ -130,7 +130,7 @@ def test_reference_shape_constructs_and_steps():
     feats, seq_len, labels, label_len = O.synth_batch(spec, B, T, seed=1, Lmin=2, Lmax=4)
     rs = np.random.RandomState(0)
     runs = {}
-    wide_on = os.environ.get('NASR_PERSIST', '1')[:1] != '0' and os.environ.get('NASR_WIDE', '1')[:1] != '0'
+    wide_on = os.environ.get('NASR_PERSIST', '1')[:1] != '0'
     for mode in (('wide-persistent', 'per-step') if wide_on else ('per-step',)):
         e = make_engine(spec, lr=1e-4)
         assert e.recurrence_mode == ('wide-persistent' if wide_on else 'per-step')
@@ -261,8 +261,8 @@ def test_reference_widths_over_128_timesteps_match_the_c_restatement(mode):
     every gradient tensor against oracle/cref, once through the wide persistent kernels (fp16-plane BPTT with its
     per-utterance dG scale, lstm_wide.hip) and once through the per-step kernels at Hp = 2048 (lstm.hip) - each pinned to a
     CPU restatement instead of to the other."""
-    if mode == 'wide-persistent' and (os.environ.get('NASR_PERSIST', '1')[:1] == '0' or os.environ.get('NASR_WIDE', '1')[:1] == '0'):
-        pytest.skip('NASR_PERSIST=0 / NASR_WIDE=0 force the per-step kernels')
+    if mode == 'wide-persistent' and os.environ.get('NASR_PERSIST', '1')[:1] == '0':
+        pytest.skip('NASR_PERSIST=0 forces the per-step kernels')
     c = _long_case()
     spec, (feats, seq_len, labels, label_len), (seed, counter) = c['spec'], c['batch'], c['drop']
     lo, nllo, go, lgo = c['ref']

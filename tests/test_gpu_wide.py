@@ -11,8 +11,8 @@ import pytest
 from oracle import nasr_oracle as O
 
 pytestmark = [pytest.mark.gpu,
-              pytest.mark.skipif(os.environ.get('NASR_PERSIST', '1')[:1] == '0' or os.environ.get('NASR_WIDE', '1')[:1] == '0',
-                                 reason='NASR_PERSIST=0 / NASR_WIDE=0 force the per-step kernels: nothing wide to test')]
+              pytest.mark.skipif(os.environ.get('NASR_PERSIST', '1')[:1] == '0',
+                                 reason='NASR_PERSIST=0 forces the per-step kernels: nothing wide to test')]
 
 
 def make_engine(spec, lr=1e-3):
