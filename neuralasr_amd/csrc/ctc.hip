@@ -120,16 +120,14 @@ void launch_ctc_logz(const CtcDims& d, const float* logits, const int* seq_len, 
 // ulp is 1.2e-4 and alpha+beta-logp (the posterior exponent) loses 3 digits; rescaled columns stay O(10).
 // The time loop runs in branch-free groups of 4 frames (loads clamped, updates selected) so the emission
 // gathers of the NEXT group are in flight behind counted waits while this group computes.
-#ifndef NASR_CTC_GROUP
-#define NASR_CTC_GROUP 4   // 8 (twice the prefetch distance, rescale every 8 frames): same time - the lattice is not waiting for its emissions
-#endif
 template <int KS>
 __device__ __forceinline__ void ctc_ab_log(
     const float* __restrict__ logits, const float* __restrict__ logz, const int* __restrict__ labels,
     const int* __restrict__ label_len, const int* __restrict__ seq_len, float* __restrict__ alpha,
     float* __restrict__ beta, double* __restrict__ aoff, double* __restrict__ boff, float* __restrict__ nll,
     double* __restrict__ logp_out, int Bp, int Cp, int C, int Lmax, int Tws, float* fin) {
-  constexpr int G = NASR_CTC_GROUP;          // frames per branch-free group = prefetch distance of the emissions
+  constexpr int G = 4;   // frames per branch-free group = prefetch distance of the emissions
+                         // (8, rescaling every 8 frames: same time - the lattice is not waiting for its emissions)
   const int b = blockIdx.x;
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int L = label_len[b], Tb = seq_len[b], S = 2 * L + 1;

@@ -15,10 +15,7 @@ namespace nasr {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
-#ifndef NASR_GEMM_BK
-#define NASR_GEMM_BK 16
-#endif
-constexpr int BM = 128, BN = 128, BK = NASR_GEMM_BK, LDT = 132;
+constexpr int BM = 128, BN = 128, BK = 16, LDT = 132;
 
 struct GemmParams {
   const float* A;

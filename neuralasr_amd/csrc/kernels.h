@@ -154,7 +154,6 @@ struct WideCtl {               // device words, zeroed before every launch
   unsigned error;              // bit 0: a bounded spin gave up, bit 1: placement is not 32 workgroups on each of 8 XCDs,
                                // bit 2 (BPTT): dG left the fp16 range of its planes
   unsigned pad[23];
-  unsigned hflag[8 * 32];      // [XCD x][member]: timesteps whose h this workgroup has published
   unsigned stamps[160];        // diagnostic build (NASR_WSTAMP, tools/widebench): phase cycles of two workgroups' waves
 };
 struct WideGeom {

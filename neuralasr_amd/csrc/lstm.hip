@@ -7,7 +7,7 @@
 // hoisted out of the loop into one MFMA GEMM (gemm.hip); what remains per step is the
 // [Bp,Hp]x[Hp,4Hp] recurrent product fused with the cell update.
 //
-// One launch = one timestep of BOTH directions (blockIdx.y).  Measured on MI355X (tools/stepbench.hip):
+// One launch = one timestep of BOTH directions (blockIdx.y).  Measured on MI355X (with a per-step microbenchmark since removed):
 // a dependent launch costs 1.55 us whatever its shape, and a CU pulls only ~35-70 GB/s from the Infinity
 // Cache / its XCD's L2 (PMC: every launch re-fetches the matrices through the fabric, the L2s do not keep
 // them across a kernel boundary), so a step is priced by BYTES PER CU, not by chip bandwidth.  Both kernels
@@ -24,41 +24,9 @@
 // MFMA 16x16x4 f32 fragment maps: A[row = l&15][k = l>>4], B[k = l>>4][col = l&15],
 // C/D col = l&15, row = 4*(l>>4) + reg.
 #include "kernels.h"
-
-#ifndef NASR_NT
-#define NASR_NT 0    // 1: non-temporal loads for the recurrent weights (tools/stepbench.hip experiment)
-#endif
-#ifndef NASR_NTST
-#define NASR_NTST 0  // 1: non-temporal stores for the state handed to the next launch (experiment)
-#endif
-#ifndef NASR_ABL
-#define NASR_ABL 0   // tools/stepbench.hip ablation mask: 1 no U loads, 2 no h loads, 4 no MFMA, 8 no cell I/O
-#endif
+#include "lstm_device.h"
 
 namespace nasr {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ float4 ldw(const float4* p) {
-#if NASR_NT
-  typedef float v4f __attribute__((ext_vector_type(4)));
-  const v4f v = __builtin_nontemporal_load(reinterpret_cast<const v4f*>(p));
-  return make_float4(v.x, v.y, v.z, v.w);
-#else
-  return *p;
-#endif
-}
-__device__ __forceinline__ void st_state(float* p, float v) {
-#if NASR_NTST
-  __builtin_nontemporal_store(v, p);
-#else
-  *p = v;
-#endif
-}
-// bare v_exp_f32, as in lstm_persist.hip (saturation makes the denormal scaling of __expf pointless here)
-__device__ __forceinline__ float exp_(float x) { return __builtin_amdgcn_exp2f(x * 1.44269504088896341f); }
-__device__ __forceinline__ float sigmoidf_(float x) { return __builtin_amdgcn_rcpf(1.f + exp_(-x)); }
-__device__ __forceinline__ float tanhf_(float x) { return 1.f - 2.f * __builtin_amdgcn_rcpf(1.f + exp_(2.f * x)); }
 
 // Element (row b16, unit k) of M-tile mt inside the swizzled h-state image (contraction length Kd).
 // Lane l of 16-byte group q holds, in component i, the value the MFMA k-step 4q+i wants from lane l:
@@ -165,7 +133,6 @@ __global__ __launch_bounds__(256) void lstm_fwd_step_kernel(
   __shared__ __attribute__((aligned(16))) float red[4][MT][64][4];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int tile = blockIdx.x, d = blockIdx.y;
-  if ((NASR_ABL & 64) && s != 123456) return;
   const int N4 = 4 * Hp, DH = D * Hp, DN = D * N4;
   const int nq = NQ > 0 ? NQ : (Hp >> 6);   // float4 groups per wave (K quarter)
   const int q0 = w * nq;
@@ -175,7 +142,7 @@ __global__ __launch_bounds__(256) void lstm_fwd_step_kernel(
   const int cmt = tid >> 6, cl = tid & 63;
   const int b16 = cl & 15, u = cl >> 4;
   const int b = cmt * 16 + b16;
-  const int len_ld = (NASR_ABL & 16) ? T : seq_len[b < Bp ? b : 0];
+  const int len_ld = seq_len[b < Bp ? b : 0];
 
   // ---- recurrent product: acc[mt] (16 x 16) over this wave's K quarter.  Loads are issued in
   // consumption order (h, U, h, U, ...) ahead of everything else.
@@ -183,12 +150,13 @@ __global__ __launch_bounds__(256) void lstm_fwd_step_kernel(
   const float4* ha = reinterpret_cast<const float4*>(hin) + ((size_t)d * MT * (Hp >> 4) + q0) * 64 + lane;
   float4 bu[CH];
   float4 av[MT][CH];
+  // (the h operands of the first chunk are loaded as temporaries: a plain assignment gives hipcc a different schedule)
 #pragma unroll
   for (int x = 0; x < CH; ++x) {
 #pragma unroll
     for (int m = 0; m < MT; ++m)
-      av[m][x] = (NASR_ABL & 2) ? make_float4(1e-3f, 2e-3f, 3e-3f, 4e-3f) : ha[((size_t)m * (Hp >> 4) + x) * 64];
-    bu[x] = (NASR_ABL & 1) ? make_float4(1e-3f, 2e-3f, 3e-3f, 4e-3f) : ldw(ub + (size_t)x * 64);
+      av[m][x] = float4(ha[((size_t)m * (Hp >> 4) + x) * 64]);
+    bu[x] = ub[(size_t)x * 64];
   }
 
   // ---- cell threads: issue the loads the cell update needs
@@ -205,10 +173,8 @@ __global__ __launch_bounds__(256) void lstm_fwd_step_kernel(
     if (valid) {
       const int tb = d ? (len - 1 - s) : s;
       r = tb * Bp + b;
-      if (!(NASR_ABL & 8)) {
-        xg = *reinterpret_cast<const float4*>(gates + (size_t)r * DN + d * N4 + 4 * j);
-        if (s > 0) cprev = cbuf[(size_t)(d ? r + Bp : r - Bp) * DH + d * Hp + j];
-      }
+      xg = *reinterpret_cast<const float4*>(gates + (size_t)r * DN + d * N4 + 4 * j);
+      if (s > 0) cprev = cbuf[(size_t)(d ? r + Bp : r - Bp) * DH + d * Hp + j];
     }
   }
 
@@ -224,18 +190,14 @@ __global__ __launch_bounds__(256) void lstm_fwd_step_kernel(
       for (int x = 0; x < CH; ++x) {
 #pragma unroll
         for (int m = 0; m < MT; ++m)
-          if (!(NASR_ABL & 2)) av[m][x] = ha[((size_t)m * (Hp >> 4) + qc + x) * 64];
-        if (!(NASR_ABL & 1)) bu[x] = ldw(ub + (size_t)(qc + x) * 64);
+          av[m][x] = ha[((size_t)m * (Hp >> 4) + qc + x) * 64];
+        bu[x] = ub[(size_t)(qc + x) * 64];
       }
     }
 #pragma unroll
     for (int x = 0; x < CH; ++x) {
 #pragma unroll
       for (int m = 0; m < MT; ++m) {
-        if (NASR_ABL & 4) {
-          acc[m][0][0] += av[m][x].x * bu[x].x + av[m][x].y * bu[x].y + av[m][x].z * bu[x].z + av[m][x].w * bu[x].w;
-          continue;
-        }
         acc[m][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[m][x].x, bu[x].x, acc[m][0], 0, 0, 0);
         acc[m][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[m][x].y, bu[x].y, acc[m][1], 0, 0, 0);
         acc[m][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[m][x].z, bu[x].z, acc[m][0], 0, 0, 0);
@@ -265,12 +227,10 @@ __global__ __launch_bounds__(256) void lstm_fwd_step_kernel(
       const float so = sigmoidf_(xg.w + g[3]);
       const float c = cprev * sf + si * tj;
       const float h = tanhf_(c) * so;
-      if (!(NASR_ABL & 8)) {
-        *reinterpret_cast<float4*>(gates + (size_t)r * DN + d * N4 + 4 * j) = make_float4(si, tj, sf, so);
-        cbuf[(size_t)r * DH + d * Hp + j] = c;
-        out[(size_t)r * DH + d * Hp + j] = h;
-      }
-      if (!(NASR_ABL & 32) || h == 123.456f) st_state(hdst, h);
+      *reinterpret_cast<float4*>(gates + (size_t)r * DN + d * N4 + 4 * j) = make_float4(si, tj, sf, so);
+      cbuf[(size_t)r * DH + d * Hp + j] = c;
+      out[(size_t)r * DH + d * Hp + j] = h;
+      *hdst = h;
     } else {
       // frame s of row b is past seq_len for both directions: zero output (A.2); state is dead
       if (s < T) out[((size_t)s * Bp + b) * DH + d * Hp + j] = 0.f;
@@ -355,7 +315,7 @@ __global__ __launch_bounds__(256) void lstm_bwd_step_kernel(
 #pragma unroll
   for (int nt = 0; nt < 4; ++nt)
 #pragma unroll
-    for (int q2 = 0; q2 < 2; ++q2) bu[nt][q2] = ldw(ub + (size_t)(nt * 2 + q2) * 64);
+    for (int q2 = 0; q2 < 2; ++q2) bu[nt][q2] = ub[(size_t)(nt * 2 + q2) * 64];
 
   // ---- P stage: 2*MT cells per thread, processed in pairs: every load of a pair is issued before any
   // of its arithmetic so the two latency chains overlap.
@@ -483,7 +443,10 @@ __global__ __launch_bounds__(256) void lstm_bwd_step_kernel(
     const int jo = 64 * jt + 16 * w + (lane & 15);
     const int b0 = 16 * m + 4 * (lane >> 4);
 #pragma unroll
-    for (int rg = 0; rg < 4; ++rg) st_state(&po[(size_t)(b0 + rg) * Hp + jo], v[rg]);
+    for (int rg = 0; rg < 4; ++rg) {   // (address before value: the other order gives hipcc a different schedule)
+      float* p = &po[(size_t)(b0 + rg) * Hp + jo];
+      *p = v[rg];
+    }
   }
 }
 
@@ -528,23 +491,21 @@ __global__ __launch_bounds__(256) void lstm_bwd_cell_kernel(const float* __restr
 }
 
 // partial sums a BPTT step hands on: Hp/32 of them per output, Hp/128 for the wide-layer form
-#ifndef NASR_BWD_KSL
-#define NASR_BWD_KSL 4   // K slices a block of the wide form walks (tools/stepbench.hip A/B: 2, 4, 8)
-#endif
-static bool bwd_wide_form(int Hp) { return Hp > 512 && Hp % (32 * NASR_BWD_KSL) == 0; }
-int lstm_bwd_partials(int Hp) { return bwd_wide_form(Hp) ? Hp / (32 * NASR_BWD_KSL) : Hp / 32; }
+constexpr int BWD_KSL = 4;   // K slices a block of the wide form walks (A/B: 2, 4, 8)
+static bool bwd_wide_form(int Hp) { return Hp > 512 && Hp % (32 * BWD_KSL) == 0; }
+int lstm_bwd_partials(int Hp) { return bwd_wide_form(Hp) ? Hp / (32 * BWD_KSL) : Hp / 32; }
 
 void launch_lstm_bwd_step(const LstmDims& dm, int s, const float* Ub, const float* pin, float* pout,
                           const float* gates, float* dgbuf, const float* cbuf, const float* dout, const float* dcin,
                           float* dcout, const int* seq_len, hipStream_t st) {
   const int MT = dm.Bp / 16, ksp = dm.Hp / 32;
   if (bwd_wide_form(dm.Hp)) {     // wide layer: cell arithmetic once, then the product (see the kernel's header)
-    const int np = dm.Hp / (32 * NASR_BWD_KSL);
+    const int np = dm.Hp / (32 * BWD_KSL);
     hipLaunchKernelGGL(lstm_bwd_cell_kernel, dim3((dm.Bp * dm.Hp + 255) / 256, dm.D), dim3(256), 0, st, pin, np, gates, dgbuf,
                        cbuf, dout, dcin, dcout, seq_len, s, dm.Bp, dm.Hp, dm.D);
     dim3 gridw((dm.Hp / 64) * np, dm.D);
 #define NASR_BWDW(MTV)                                                                                              \
-  hipLaunchKernelGGL((lstm_bwd_step_kernel<MTV, 0, true, NASR_BWD_KSL>), gridw, dim3(256), 0, st, Ub, pin, pout, gates, dgbuf, cbuf, \
+  hipLaunchKernelGGL((lstm_bwd_step_kernel<MTV, 0, true, BWD_KSL>), gridw, dim3(256), 0, st, Ub, pin, pout, gates, dgbuf, cbuf, \
                      dout, dcin, dcout, seq_len, s, dm.T, dm.Bp, dm.Hp, dm.D)
     switch (MT) {
       case 1: NASR_BWDW(1); break;

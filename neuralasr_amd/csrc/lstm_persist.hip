@@ -32,26 +32,12 @@
 // spin is bounded; a timeout or an unexpected placement (not 32 workgroups on each of 8 XCDs) raises
 // PersistCtl::error, the launch drains, and the host falls back to the per-step kernels of lstm.hip for good.
 #include "kernels.h"
+#include "lstm_device.h"
 
 #include <cstdlib>
-#include <type_traits>
-#include <utility>
 
 #ifndef NASR_PSTAMP
 #define NASR_PSTAMP 0   // 1: wave 0 of one workgroup accumulates s_memtime deltas per phase into PersistCtl::pad (tools/persistbench)
-#endif
-
-#ifndef NASR_FWD_EPOCH
-#define NASR_FWD_EPOCH 1   // forward hand-off: h words carry an epoch bit, consumers poll the payload itself (0: flag, then payload)
-#endif
-#ifndef NASR_BWD_EPOCH
-#define NASR_BWD_EPOCH 1   // BPTT hand-off: every partial sum carries an epoch bit in its last mantissa bit, consumers poll the sums
-#endif
-#ifndef NASR_BWD_NACC
-#define NASR_BWD_NACC 4    // accumulator chains per output group of the BPTT product (2 or 4)
-#endif
-#ifndef NASR_EP_DELAY
-#define NASR_EP_DELAY 0    // s_sleep units between "this CU has published" and the first load of the others' h
 #endif
 
 namespace nasr {
@@ -86,38 +72,6 @@ struct Stamps {
 #endif
   }
 };
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(1))) unsigned gu32;
-typedef volatile __attribute__((address_space(3))) unsigned lds_vu32;   // a volatile access through a GENERIC pointer to LDS
-                                                                        // compiles to flat_store sc0 sc1 + vmcnt(0)
-
-// The bare v_exp_f32 (2^x), without the denormal scaling __expf can wrap around it: an exponential that overflows to inf
-// or flushes to 0 gives the saturated value of the sigmoid / tanh either way, and in the normal range the two are the
-// same instruction on the same input (results bitwise equal; measured time equal too - the cell wave's chain is latency,
-// not issue).
-__device__ __forceinline__ float pexp(float x) { return __builtin_amdgcn_exp2f(x * 1.44269504088896341f); }
-__device__ __forceinline__ float psig(float x) { return __builtin_amdgcn_rcpf(1.f + pexp(-x)); }
-__device__ __forceinline__ float ptanh(float x) { return 1.f - 2.f * __builtin_amdgcn_rcpf(1.f + pexp(2.f * x)); }
-
-template <int I, int N, class F>
-__device__ __forceinline__ void static_for(F&& f) {
-  if constexpr (I < N) {
-    f(std::integral_constant<int, I>{});
-    static_for<I + 1, N>(f);
-  }
-}
-
-constexpr unsigned SPIN_BUDGET = 1u << 21;   // polls before a wave gives up (~0.5 s)
-
-// wait until every active lane's word is >= want (monotonic step counters; wrap-safe compare)
-__device__ __forceinline__ bool poll_ge(gu32* p, bool active, unsigned want) {
-  for (unsigned n = 0; n < SPIN_BUDGET; ++n) {
-    const unsigned v = active ? __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : want;
-    if (__all((int)(v - want) >= 0)) return true;
-  }
-  return false;
-}
 
 // (xcc id, ticket within the XCD) of this workgroup; false when the placement is not 32-per-XCD-of-8
 __device__ __forceinline__ void raise_error(PersistCtl* ctl, unsigned* sticky, float* fault, unsigned code) {
@@ -273,6 +227,8 @@ constexpr int LDS_RED = 0, LDS_ADG = 2 * 4 * 4 * 64, LDS_SIDE = LDS_ADG + 2 * 25
 // packed in the 4 bytes the fp32 value took), three MFMAs per chunk of 4 units
 // (h1 U1 + h1 U2 + h2 U1) instead of four fp32 ones: 96 instead of 128 MFMAs of the same duration per wave and step,
 // the same accuracy class as the fp16-plane GEMMs.  cinv [D][N4]: 1 / column scale.
+// The F16 hand-off is validated by epoch bits in the published words themselves; the fp32 form (NASR_REC=f32) polls the
+// producers' flags, then loads h.
 template <int NU, bool F16>
 __global__ __launch_bounds__(320, 1) void lstm_persist_fwd_kernel(
     const float* __restrict__ Upf,   // [D] images
@@ -283,7 +239,7 @@ __global__ __launch_bounds__(320, 1) void lstm_persist_fwd_kernel(
   constexpr int KW = 8 * NU;                 // units (= MFMAs) per wave
   constexpr int NCH = 2 * NU;                // 16-byte chunks (4 units x 1 utterance) per wave and utterance
   constexpr int NJ = (NCH + 15) / 16;        // 16-byte loads per lane
-  constexpr bool EP = F16 && NASR_FWD_EPOCH;  // hand-off validated by the payload's own epoch bits
+  constexpr bool EP = F16;                   // hand-off validated by the payload's own epoch bits
   float* red = lds + LDS_RED;
   float* side = lds + LDS_SIDE;
   float* xgb = lds + LDS_XGB;
@@ -391,7 +347,6 @@ __global__ __launch_bounds__(320, 1) void lstm_persist_fwd_kernel(
               const unsigned want = tagbase + (unsigned)s;
               for (unsigned n = 0; n < (1u << 26) && (int)(*(lds_vu32*)(info + 5) - want) < 0; ++n) __builtin_amdgcn_s_sleep(1);
             }
-            if (NASR_EP_DELAY) __builtin_amdgcn_s_sleep(NASR_EP_DELAY);
             const float* src = ghx + (size_t)((s - 1) & 1) * Hp * 4 + ((size_t)w * KW * 4 + (size_t)lane * 4);
             const unsigned eexp = epoch_of(rd, s - 1) << 30;
             const bool has0 = NCH >= 16 || lane < 4 * NCH, has1 = NJ == 2 && lane < 4 * (NCH - 16);
@@ -459,7 +414,7 @@ __global__ __launch_bounds__(320, 1) void lstm_persist_fwd_kernel(
               const u2 lo = {__builtin_amdgcn_perm(d1, d0, 0x05040100u), __builtin_amdgcn_perm(d3, d2, 0x05040100u)};
               const u2 hi = {__builtin_amdgcn_perm(d1, d0, 0x07060302u), __builtin_amdgcn_perm(d3, d2, 0x07060302u)};
               a1[i] = __builtin_bit_cast(h4, lo);
-              a2[i] = __builtin_bit_cast(h4, EP ? (u2){hi[0] & 0xBFFFBFFFu, hi[1] & 0xBFFFBFFFu} : hi);
+              a2[i] = __builtin_bit_cast(h4, (u2){hi[0] & 0xBFFFBFFFu, hi[1] & 0xBFFFBFFFu});   // without the epoch bits
             }
             static_for<0, NCH>([&](auto bbc) {
               constexpr int bb = decltype(bbc)::value;
@@ -520,25 +475,25 @@ __global__ __launch_bounds__(320, 1) void lstm_persist_fwd_kernel(
           const f32x4 xg = *reinterpret_cast<const f32x4*>(xgb + (par * 64 + lane) * 4);
           const f32x4 pre = xg + ((g0 + g1) + (g2 + g3));
           f32x4 act;
-          act.x = psig(pre.x);
-          act.y = ptanh(pre.y);
-          act.z = psig(pre.z + fb);
-          act.w = psig(pre.w);
+          act.x = sigmoidf_(pre.x);
+          act.y = tanhf_(pre.y);
+          act.z = sigmoidf_(pre.z + fb);
+          act.w = sigmoidf_(pre.w);
           if (valid) {
             c = c * act.z + act.x * act.y;
-            h = ptanh(c) * act.w;
+            h = tanhf_(c) * act.w;
           }
           if constexpr (F16) {
             // split h (|h| < 1) into its two fp16 parts of h * 2^14 HERE, once, instead of in every consumer wave of the
             // group (32 CUs x 4 waves redid these five operations per value on their MFMA chain): same arithmetic, same bits
             const float v = h * 16384.f;
             const _Float16 h1 = (_Float16)v;
-            // EP: the low part as (v - h1) / 8: |v - h1| <= 4, so its fp16 exponent field stays below 16 and bit 14 of the
+            // the low part as (v - h1) / 8: |v - h1| <= 4, so its fp16 exponent field stays below 16 and bit 14 of the
             // half - bit 30 of the word - is free for the epoch of this use of the buffer (the consumers multiply the
             // h2 U1 product by 8; both scalings are exact)
-            const _Float16 h2 = (_Float16)(EP ? (v - (float)h1) * 0.125f : (v - (float)h1));
+            const _Float16 h2 = (_Float16)((v - (float)h1) * 0.125f);
             const unsigned pk = (unsigned)__builtin_bit_cast(unsigned short, h1) |
-                                ((unsigned)__builtin_bit_cast(unsigned short, h2) << 16) | (EP ? epoch_of(rd, s) << 30 : 0u);
+                                ((unsigned)__builtin_bit_cast(unsigned short, h2) << 16) | (epoch_of(rd, s) << 30);
             ghx[(size_t)par * Hp * 4 + hidx] = __uint_as_float(pk);
           } else {
             ghx[(size_t)par * Hp * 4 + hidx] = h;          // plain store: lands in this XCD's L2
@@ -611,7 +566,6 @@ __global__ __launch_bounds__(320, 1) void lstm_persist_bwd_kernel(
   bool aborted = false;
   Stamps stp;
   stp.start(w == 0);
-  constexpr bool EP = NASR_BWD_EPOCH != 0;
   f32x4 cmax = (f32x4){0.f, 0.f, 0.f, 0.f};   // memory wave: running column maxima of this lane's (unit, utterance slot)
   // epoch of the use of exchange buffer (k & 1) that step k of round rd is (uses alternate 1, 0, 1, ... from a cleared buffer)
   // (the rounds a group runs come first - b0 grows with rd - so rd counts its uses.  The buffer is CLEARED before every
@@ -679,9 +633,10 @@ __global__ __launch_bounds__(320, 1) void lstm_persist_bwd_kernel(
       const int s = T - 1 - k, par = k & 1;
       stp.mark(0);
       if (w == 0) {
-        // 1. every wave of every producer has published its partial sums of step k-1
+        // 1. the partial sums of step k-1 (below) validate themselves; the flags are only the barrier between the rounds,
+        // which reuse the buffers
         bool ok = false;
-        if (!EP || (k == 0 && rd > 0)) {   // (EP: the flags are only the barrier between rounds, which reuse the buffers)
+        if (k == 0 && rd > 0) {   // every wave of every producer has published its partial sums of the last round
           const unsigned want = tagbase + (unsigned)k;
           for (unsigned n = 0; n < SPIN_BUDGET && !ok; ++n) {
             const unsigned v0 = __hip_atomic_load(gflag + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -713,13 +668,13 @@ __global__ __launch_bounds__(320, 1) void lstm_persist_bwd_kernel(
         "=&v"(pv[g8 + 5]), "=&v"(pv[g8 + 6]), "=&v"(pv[g8 + 7])                                                    \
       : "v"(src + (size_t)(g8) * 64)                                                                               \
       : "memory")
-          // EP: the sums themselves say whether they are those of step k-1 - bit 0 of every word is the epoch of this use
+          // the sums themselves say whether they are those of step k-1 - bit 0 of every word is the epoch of this use
           // of the buffer; a lane that finds a stale word loads its 32 again (one round trip when everybody is on time,
           // and no acknowledgement wait or flag on the producers' side)
           const unsigned eexp = epoch_of(rd, k - 1);
           bool need = lane_ok;
           bool got = false;
-          for (unsigned n = 0; n < (EP ? SPIN_BUDGET : 1u); ++n) {
+          for (unsigned n = 0; n < SPIN_BUDGET; ++n) {
             if (need) { NASR_LD8(0); NASR_LD8(8); NASR_LD8(16); NASR_LD8(24); }
             // one wait for all 32 loads; naming every destination keeps hipcc from touching them before it
             asm volatile("s_waitcnt vmcnt(0)"
@@ -734,27 +689,23 @@ __global__ __launch_bounds__(320, 1) void lstm_persist_bwd_kernel(
                            "+v"(pv[30]), "+v"(pv[31])
                          :
                          : "memory");
-            if constexpr (EP) {
-              unsigned bad;                   // bit 0: some word of this lane is not of epoch eexp (wave-uniform branch)
-              if (eexp) {
-                unsigned a_ = 1u;
+            unsigned bad;                     // bit 0: some word of this lane is not of epoch eexp (wave-uniform branch)
+            if (eexp) {
+              unsigned a_ = 1u;
 #pragma unroll
-                for (int p = 0; p < 32; ++p) a_ &= __float_as_uint(pv[p]);
-                bad = ~a_;
-              } else {
-                unsigned o_ = 0u;
-#pragma unroll
-                for (int p = 0; p < 32; ++p) o_ |= __float_as_uint(pv[p]);
-                bad = o_;
-              }
-              need = lane_ok && (bad & 1u) != 0;
-              if (!__any(need)) { got = true; break; }
-#if NASR_PSTAMP
-              if (stp.on) stp.acc[11] += 1;      // extra attempts
-#endif
+              for (int p = 0; p < 32; ++p) a_ &= __float_as_uint(pv[p]);
+              bad = ~a_;
             } else {
-              got = true;
+              unsigned o_ = 0u;
+#pragma unroll
+              for (int p = 0; p < 32; ++p) o_ |= __float_as_uint(pv[p]);
+              bad = o_;
             }
+            need = lane_ok && (bad & 1u) != 0;
+            if (!__any(need)) { got = true; break; }
+#if NASR_PSTAMP
+            if (stp.on) stp.acc[11] += 1;        // extra attempts
+#endif
           }
 #undef NASR_LD8
           if (!got) ok = false;
@@ -770,7 +721,7 @@ __global__ __launch_bounds__(320, 1) void lstm_persist_bwd_kernel(
         f32x4 dg = (f32x4){0.f, 0.f, 0.f, 0.f};
         float dcn = 0.f;
         if (valid) {
-          const float tc = ptanh(o.x);
+          const float tc = tanhf_(o.x);
           const float dct = dc + dhs * a.w * (1.f - tc * tc);
           dg.x = dct * a.y * a.x * (1.f - a.x);
           dg.y = dct * a.x * (1.f - a.y * a.y);
@@ -804,7 +755,7 @@ __global__ __launch_bounds__(320, 1) void lstm_persist_bwd_kernel(
       for (int v = 0; v < NV; ++v) av[v] = (64 * v + lane < 4 * NC) ? adg[par * 256 + 64 * v + lane] : 0.f;
       // NACC independent accumulator chains per output group: with NOG * NACC = 8 chains in flight the wave always has an
       // MFMA ready to issue (it runs at priority 3: beside another kernel's MFMA waves it keeps the pipe for its phase)
-      constexpr int NACC = NASR_BWD_NACC;
+      constexpr int NACC = 4;
       f32x4 acc[NOG][NACC];
 #pragma unroll
       for (int og = 0; og < NOG; ++og)
@@ -821,12 +772,9 @@ __global__ __launch_bounds__(320, 1) void lstm_persist_bwd_kernel(
       const unsigned eb = epoch_of(rd, k);
 #pragma unroll
       for (int og = 0; og < NOG; ++og) {
-        f32x4 sum = acc[og][0] + acc[og][1];
-        if constexpr (NACC == 4) sum = sum + (acc[og][2] + acc[og][3]);
-        if constexpr (EP) {   // the last mantissa bit of every sum = the epoch of this use of the buffer
+        f32x4 sum = (acc[og][0] + acc[og][1]) + (acc[og][2] + acc[og][3]);
 #pragma unroll
-          for (int i = 0; i < 4; ++i) sum[i] = __uint_as_float((__float_as_uint(sum[i]) & ~1u) | eb);
-        }
+        for (int i = 0; i < 4; ++i) sum[i] = __uint_as_float((__float_as_uint(sum[i]) & ~1u) | eb);   // last mantissa bit = epoch
         const int kl = og * 64 + lane;
         if (kl < KW) {
           const int kk = w * KW + kl;
@@ -835,9 +783,8 @@ __global__ __launch_bounds__(320, 1) void lstm_persist_bwd_kernel(
         }
       }
       stp.mark(5);
-      if constexpr (!EP) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       stp.mark(6);
-      if (lane == 0) *(ctl->flags + xcc * 128 + member * 4 + w) = tagbase + (unsigned)k + 1u;
+      if (lane == 0) *(ctl->flags + xcc * 128 + member * 4 + w) = tagbase + (unsigned)k + 1u;   // the round barrier only
       if (abort_word) { aborted = true; break; }
     }
     if (aborted) break;
@@ -913,7 +860,7 @@ void launch_lstm_persist_fwd(const LstmDims& dm, const float* Upf, const float* 
   gm.fault = fault;
   if (!ctl_zeroed) (void)hipMemsetAsync(ctl, 0, sizeof(PersistCtl), st);
   // epoch-validated hand-off: the exchange buffers start from epoch 0 (ctl_zeroed: the caller cleared them with *ctl)
-  if (NASR_FWD_EPOCH && cinv && !ctl_zeroed) (void)hipMemsetAsync(xch, 0, persist_hx_bytes(dm.Hp), st);
+  if (cinv && !ctl_zeroed) (void)hipMemsetAsync(xch, 0, persist_hx_bytes(dm.Hp), st);
   dim3 grid(256), block(320);
 #define NASR_PF(NUV)                                                                                                  \
   if (cinv)                                                                                                           \
@@ -940,9 +887,11 @@ void launch_lstm_persist_bwd(const LstmDims& dm, const float* Upb, const float* 
                              float* fault, hipStream_t st, bool ctl_zeroed, float* rowpart, float* colpart, bool lean) {
   PersistGeom gm = make_geom(dm, true);
   gm.fault = fault;
-  if (!ctl_zeroed) (void)hipMemsetAsync(ctl, 0, sizeof(PersistCtl), st);
   // epoch-validated hand-off: the exchange buffer starts from epoch 0 (ctl_zeroed: the caller cleared it with *ctl)
-  if (NASR_BWD_EPOCH && !ctl_zeroed) (void)hipMemsetAsync(xch, 0, persist_px_bytes(), st);
+  if (!ctl_zeroed) {
+    (void)hipMemsetAsync(ctl, 0, sizeof(PersistCtl), st);
+    (void)hipMemsetAsync(xch, 0, persist_px_bytes(), st);
+  }
   dim3 grid(256), block(320);
   // (lean only at Hp = 512, where the kernel's 5 x 220 VGPRs alone keep it at one workgroup per CU)
   const int bwd_lds = (lean && dm.Hp == 512) ? PERSIST_LDS_LEAN : PERSIST_LDS_BYTES;

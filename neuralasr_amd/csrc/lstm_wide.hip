@@ -13,24 +13,18 @@
 //     slice.  Wave w of a workgroup holds the columns that belong to slice x' = w.
 //   * per timestep two hand-offs: (1) h_{s-1} of the XCD's own row slice through the XCD's L2 (32 producers x 1 KB,
 //     plain stores + sc1 loads, as lstm_persist.hip); (2) the 8 partial sums of every unit cross the XCDs: wave w
-//     sends its 16*MT x 32 partial pre-activations to workgroup (w, nb) (sc1 write-through stores + flag), which sums
+//     sends its 16*MT x 32 partial pre-activations to workgroup (w, nb) (sc1 write-through stores, no flag), which sums
 //     the 8 in fixed order, does the cell update of its 8 units (c in a register for all T) and publishes h.
-//   * products on v_mfma_f32_16x16x32_f16: h*2^14 split into two fp16 parts by its producer, three products per tile.
+//   * products on v_mfma_f32_16x16x32_f16: 2h split into two fp16 parts by its producer, three products per tile.  The
+//     parts carry the epoch of their buffer's use, so the loads of hand-off (1) validate themselves.
 //
 // Placement is read from HW_REG_XCC_ID with a ticket per XCD; every spin is bounded; a timeout or an unexpected placement
 // raises WideCtl::error (+ the sticky host word and the fault float) and the launch drains.
 #include "kernels.h"
+#include "lstm_device.h"
 
 #include <cstdlib>
-#include <type_traits>
-#include <utility>
 
-#ifndef WIDE_PF
-#define WIDE_PF 2        // k-tiles of A fragments read ahead of the MFMAs (tools/widebench A/B: 1, 2, 3)
-#endif
-#ifndef NASR_WIDE_EPOCH
-#define NASR_WIDE_EPOCH 1   // forward: the h all-gather is validated by epoch bits in the payload (0: flag, then payload)
-#endif
 #ifndef NASR_WSTAMP
 #define NASR_WSTAMP 0   // 1: s_memtime deltas per phase -> WideCtl::stamps (tools/widebench)
 #endif
@@ -54,32 +48,10 @@ namespace nasr {
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef _Float16 h8 __attribute__((ext_vector_type(8)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(1))) unsigned gu32;
 
-__device__ __forceinline__ float wexp(float x) { return __builtin_amdgcn_exp2f(x * 1.44269504088896341f); }
-__device__ __forceinline__ float wsig(float x) { return __builtin_amdgcn_rcpf(1.f + wexp(-x)); }
-__device__ __forceinline__ float wtanh(float x) { return 1.f - 2.f * __builtin_amdgcn_rcpf(1.f + wexp(2.f * x)); }
-
-template <int I, int N, class F>
-__device__ __forceinline__ void wstatic_for(F&& f) {
-  if constexpr (I < N) {
-    f(std::integral_constant<int, I>{});
-    wstatic_for<I + 1, N>(f);
-  }
-}
-
-constexpr unsigned WIDE_SPIN = 1u << 21;
-
-__device__ __forceinline__ bool wpoll_ge(gu32* p, bool active, unsigned want) {
-  for (unsigned n = 0; n < WIDE_SPIN; ++n) {
-    const unsigned v = active ? __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : want;
-    if (__all((int)(v - want) >= 0)) return true;
-  }
-  return false;
-}
+constexpr int PF = 2;   // k-tiles of A fragments read ahead of the MFMAs (widebench A/B: 1, 2, 3)
 
 __device__ __forceinline__ u32x4 ld16_sc1(const void* p) {
   u32x4 v;
@@ -157,13 +129,12 @@ template <int MT>
 __global__ __launch_bounds__(512, 1) void lstm_wide_fwd_kernel(
     const u32x4* __restrict__ Uw,       // this direction's image
     float* gates, float* cbuf, float* out, const int* __restrict__ seq_len,
-    u32x4* hx,                           // [2 parity][8 x][32 nb][2 plane][16*MT rows]: 8 halfs of h*2^14 per unit
+    u32x4* hx,                           // [2 parity][8 x][32 nb][2 plane][16*MT rows]: 8 halfs of 2h per unit
     float* part,                         // [2 parity][256 dest][8 src][MT][2 h2][64 lane][4]
     WideCtl* ctl, unsigned* sticky, WideGeom gm, float fb, const float* __restrict__ cinv) {
   extern __shared__ __attribute__((aligned(16))) u32x4 wlds[];
   using L = WideLds<MT>;
   constexpr int ROWS = 16 * MT;
-  constexpr bool EP = NASR_WIDE_EPOCH != 0;
   constexpr int NCW = (8 * ROWS + 63) / 64;      // waves with cell threads
   u32x4* Alds = wlds + L::A;
   f32x4* Plds = reinterpret_cast<f32x4*>(wlds + L::P);
@@ -203,9 +174,7 @@ __global__ __launch_bounds__(512, 1) void lstm_wide_fwd_kernel(
   float osc[2];
 #pragma unroll
   for (int h2 = 0; h2 < 2; ++h2)
-    osc[h2] = cinv[4 * (KS * w + 8 * nb + 4 * h2 + ((lane & 15) >> 2)) + (lane & 3)] * (EP ? 0.5f : 1.f / 16384.f);
-
-  gu32* hflag = (gu32*)(ctl->hflag + x * 32);
+    osc[h2] = cinv[4 * (KS * w + 8 * nb + 4 * h2 + ((lane & 15) >> 2)) + (lane & 3)] * 0.5f;   // h travels as 2h
 
   // ---- cell threads: tid < 128*MT: (row b, unit i of this workgroup's 8)
   const bool cell = tid < 8 * ROWS;
@@ -232,73 +201,52 @@ __global__ __launch_bounds__(512, 1) void lstm_wide_fwd_kernel(
       // 1. h_{s-1} of this XCD's row slice: wave w fetches k-tile w = the 8 units of producers 4w .. 4w+3
       const u32x4* src = hx + ((size_t)(((s - 1) & 1) * 8 + x) * 32 + 4 * w + (lane >> 4)) * 2 * ROWS + (lane & 15);
       u32x4 v[MT][2];
-      if constexpr (EP) {
-        // ONE round trip, as in lstm_persist.hip: every half of the two planes carries the epoch of this use of the buffer in
-        // bit 14 (plane 0 = fp16(2h), plane 1 = fp16((2h - plane 0) * 2^10): both stay below 2, their exponent fields below
-        // 16), so the loads themselves say whether the four producers have published; a lane with a stale granule loads
-        // again.  Waves without cell threads first wait (in LDS) until this workgroup's own cell waves have published.
-        ok = !(s == gm.inject && me == 0);
-        if (ok) {
-          const unsigned want = (unsigned)s * (unsigned)NCW;
-          for (unsigned n = 0; n < (1u << 24) && (int)(*(volatile __attribute__((address_space(3))) unsigned*)(info + 3) - want) < 0; ++n)
-            __builtin_amdgcn_s_sleep(1);
-        }
-        WMARK(1);
-        if (ok) {
-          const unsigned em = ((((unsigned)(s - 1) >> 1) + 1u) & 1u) ? 0x40004000u : 0u;
-          bool need = true;
-          ok = false;
-          for (unsigned n = 0; n < WIDE_SPIN; ++n) {
-            if (need) {
-#pragma unroll
-              for (int m = 0; m < MT; ++m)
-#pragma unroll
-                for (int p = 0; p < 2; ++p) v[m][p] = ld16_sc1(src + p * ROWS + 16 * m);
-            }
-            unsigned bad = 0;
+      // ONE round trip, as in lstm_persist.hip: every half of the two planes carries the epoch of this use of the buffer in
+      // bit 14 (plane 0 = fp16(2h), plane 1 = fp16((2h - plane 0) * 2^10): both stay below 2, their exponent fields below
+      // 16), so the loads themselves say whether the four producers have published; a lane with a stale granule loads
+      // again.  Waves without cell threads first wait (in LDS) until this workgroup's own cell waves have published.
+      ok = !(s == gm.inject && me == 0);
+      if (ok) {
+        const unsigned want = (unsigned)s * (unsigned)NCW;
+        for (unsigned n = 0; n < (1u << 24) && (int)(*(lds_vu32*)(info + 3) - want) < 0; ++n)
+          __builtin_amdgcn_s_sleep(1);
+      }
+      WMARK(1);
+      if (ok) {
+        const unsigned em = ((((unsigned)(s - 1) >> 1) + 1u) & 1u) ? 0x40004000u : 0u;
+        bool need = true;
+        ok = false;
+        for (unsigned n = 0; n < SPIN_BUDGET; ++n) {
+          if (need) {
 #pragma unroll
             for (int m = 0; m < MT; ++m)
 #pragma unroll
-              for (int p = 0; p < 2; ++p) {
-                wait_vm0(v[m][p]);
-                const u32x4 t = v[m][p];
-                bad |= (t.x ^ em) | (t.y ^ em) | (t.z ^ em) | (t.w ^ em);
-              }
-            need = (bad & 0x40004000u) != 0;
-            if (!__any(need)) { ok = true; break; }
+              for (int p = 0; p < 2; ++p) v[m][p] = ld16_sc1(src + p * ROWS + 16 * m);
           }
-        }
-        if (ok) {
+          unsigned bad = 0;
 #pragma unroll
           for (int m = 0; m < MT; ++m)
 #pragma unroll
             for (int p = 0; p < 2; ++p) {
-              u32x4 t = v[m][p];
-              t.x &= 0xBFFFBFFFu; t.y &= 0xBFFFBFFFu; t.z &= 0xBFFFBFFFu; t.w &= 0xBFFFBFFFu;
-              Alds[((w * MT + m) * 2 + p) * 64 + lane] = t;
+              wait_vm0(v[m][p]);
+              const u32x4 t = v[m][p];
+              bad |= (t.x ^ em) | (t.y ^ em) | (t.z ^ em) | (t.w ^ em);
             }
-        } else {
-          info[2] = 1;
+          need = (bad & 0x40004000u) != 0;
+          if (!__any(need)) { ok = true; break; }
         }
-      } else {
-      ok = wpoll_ge(hflag + 4 * w + (lane & 3), lane < 4, (unsigned)s) && !(s == gm.inject && me == 0);
-      WMARK(1);
+      }
       if (ok) {
 #pragma unroll
         for (int m = 0; m < MT; ++m)
 #pragma unroll
-          for (int p = 0; p < 2; ++p) v[m][p] = ld16_sc1(src + p * ROWS + 16 * m);
-#pragma unroll
-        for (int m = 0; m < MT; ++m)
-#pragma unroll
-          for (int p = 0; p < 2; ++p) wait_vm0(v[m][p]);
-#pragma unroll
-        for (int m = 0; m < MT; ++m)
-#pragma unroll
-          for (int p = 0; p < 2; ++p) Alds[((w * MT + m) * 2 + p) * 64 + lane] = v[m][p];
+          for (int p = 0; p < 2; ++p) {
+            u32x4 t = v[m][p];
+            t.x &= 0xBFFFBFFFu; t.y &= 0xBFFFBFFFu; t.z &= 0xBFFFBFFFu; t.w &= 0xBFFFBFFFu;
+            Alds[((w * MT + m) * 2 + p) * 64 + lane] = t;
+          }
       } else {
         info[2] = 1;
-      }
       }
     }
     WMARK(2);
@@ -313,44 +261,36 @@ __global__ __launch_bounds__(512, 1) void lstm_wide_fwd_kernel(
       //  below and later overwrites a slot this wave reset finds the reset already in memory)
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       WMARK(5);
-      wstatic_for<0, MT>([&](auto mc) {
+      static_for<0, MT>([&](auto mc) {
         constexpr int m = decltype(mc)::value;
         // both 16 x 16 tiles of this M tile together; the A fragments of k-tile kt+1 are read while kt multiplies (the
         // scheduling barriers keep the compiler from hoisting every read to the top, which costs 64 registers per M tile)
         f32x4 t0 = (f32x4){0.f, 0.f, 0.f, 0.f}, t1 = (f32x4){0.f, 0.f, 0.f, 0.f};
-        f32x4 t0b = (f32x4){0.f, 0.f, 0.f, 0.f}, t1b = (f32x4){0.f, 0.f, 0.f, 0.f};   // EP: the plane-1 products (scale 2^11 instead of 2)
+        f32x4 t0b = (f32x4){0.f, 0.f, 0.f, 0.f}, t1b = (f32x4){0.f, 0.f, 0.f, 0.f};   // the plane-1 products (scale 2^11 instead of 2)
         // fragments of k-tiles kt+1 and kt+2 are in flight while kt multiplies (PF = prefetch distance)
-        constexpr int PF = WIDE_PF;
         h8 q0[PF + 1], q1[PF + 1];
 #pragma unroll
         for (int j = 0; j < PF; ++j) {
           q0[j] = __builtin_bit_cast(h8, Alds[((j * MT + m) * 2 + 0) * 64 + lane]);
           q1[j] = __builtin_bit_cast(h8, Alds[((j * MT + m) * 2 + 1) * 64 + lane]);
         }
-        wstatic_for<0, 8>([&](auto ktc) {
+        static_for<0, 8>([&](auto ktc) {
           constexpr int kt = decltype(ktc)::value;
           if constexpr (kt + PF < 8) {
             q0[(kt + PF) % (PF + 1)] = __builtin_bit_cast(h8, Alds[(((kt + PF) * MT + m) * 2 + 0) * 64 + lane]);
             q1[(kt + PF) % (PF + 1)] = __builtin_bit_cast(h8, Alds[(((kt + PF) * MT + m) * 2 + 1) * 64 + lane]);
           }
           const h8 c0 = q0[kt % (PF + 1)], c1 = q1[kt % (PF + 1)];
-          if constexpr (EP) {
-            t0b = __builtin_amdgcn_mfma_f32_16x16x32_f16(c1, ur[kt][0][0], t0b, 0, 0, 0);
-            t1b = __builtin_amdgcn_mfma_f32_16x16x32_f16(c1, ur[kt][1][0], t1b, 0, 0, 0);
-          } else {
-            t0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(c1, ur[kt][0][0], t0, 0, 0, 0);
-            t1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(c1, ur[kt][1][0], t1, 0, 0, 0);
-          }
+          t0b = __builtin_amdgcn_mfma_f32_16x16x32_f16(c1, ur[kt][0][0], t0b, 0, 0, 0);
+          t1b = __builtin_amdgcn_mfma_f32_16x16x32_f16(c1, ur[kt][1][0], t1b, 0, 0, 0);
           t0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(c0, ur[kt][0][1], t0, 0, 0, 0);
           t1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(c0, ur[kt][1][1], t1, 0, 0, 0);
           t0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(c0, ur[kt][0][0], t0, 0, 0, 0);
           t1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(c0, ur[kt][1][0], t1, 0, 0, 0);
           __builtin_amdgcn_sched_barrier(0);
         });
-        if constexpr (EP) {
-          t0 = t0 + t0b * (1.f / 1024.f);
-          t1 = t1 + t1b * (1.f / 1024.f);
-        }
+        t0 = t0 + t0b * (1.f / 1024.f);
+        t1 = t1 + t1b * (1.f / 1024.f);
         t0 *= osc[0];
         t1 *= osc[1];
         if (w != x) {
@@ -369,7 +309,7 @@ __global__ __launch_bounds__(512, 1) void lstm_wide_fwd_kernel(
         float* src = part + ((((size_t)par * 256 + me) * 8 + w) * MT * 2) * 256 + lane * 4;
         u32x4 v[MT][2];
         ok = false;
-        for (unsigned n = 0; n < WIDE_SPIN; ++n) {
+        for (unsigned n = 0; n < SPIN_BUDGET; ++n) {
           // the tile stored last first: when it is there the others mostly are
           v[MT - 1][1] = ld16_sc1(src + ((MT - 1) * 2 + 1) * 256);
           wait_vm0(v[MT - 1][1]);
@@ -426,30 +366,24 @@ __global__ __launch_bounds__(512, 1) void lstm_wide_fwd_kernel(
       }
       const f32x4 pre = xg + g;
       f32x4 act;
-      act.x = wsig(pre.x);
-      act.y = wtanh(pre.y);
-      act.z = wsig(pre.z + fb);
-      act.w = wsig(pre.w);
+      act.x = sigmoidf_(pre.x);
+      act.y = tanhf_(pre.y);
+      act.z = sigmoidf_(pre.z + fb);
+      act.w = sigmoidf_(pre.w);
       float h = 0.f;
       if (valid) {
         c = c * act.z + act.x * act.y;
-        h = wtanh(c) * act.w;
+        h = tanhf_(c) * act.w;
       }
-      // (EP: |2h| is kept below 2 - tanh and the sigmoid saturate to exactly 1 - so that plane 0's exponent field stays below 16;
+      // (|2h| is kept below 2 - tanh and the sigmoid saturate to exactly 1 - so that plane 0's exponent field stays below 16;
       //  the residual of that clamp, 2^-10, is exact in plane 1)
-      const float hv = EP ? fminf(fmaxf(h * 2.f, -1.9990234375f), 1.9990234375f) : h * 16384.f;
-      const float hres = (EP ? h * 2.f : hv) - 0.f;
+      const float hv = fminf(fmaxf(h * 2.f, -1.9990234375f), 1.9990234375f);
       const _Float16 h1 = (_Float16)hv;
-      const _Float16 h2v = (_Float16)(EP ? (hres - (float)h1) * 1024.f : (hv - (float)h1));
-      if constexpr (EP) {
-        // bit 14 of every half = the epoch of this use of the buffer (uses alternate 1, 0, 1, ... from a cleared buffer)
-        const unsigned short eb = ((((unsigned)s >> 1) + 1u) & 1u) ? 0x4000u : 0u;
-        reinterpret_cast<unsigned short*>(hp)[(0 * ROWS + cb) * 8 + ci] = __builtin_bit_cast(unsigned short, h1) | eb;
-        reinterpret_cast<unsigned short*>(hp)[(1 * ROWS + cb) * 8 + ci] = __builtin_bit_cast(unsigned short, h2v) | eb;
-      } else {
-        hp[(0 * ROWS + cb) * 8 + ci] = h1;
-        hp[(1 * ROWS + cb) * 8 + ci] = h2v;
-      }
+      const _Float16 h2v = (_Float16)((h * 2.f - (float)h1) * 1024.f);
+      // bit 14 of every half = the epoch of this use of the buffer (uses alternate 1, 0, 1, ... from a cleared buffer)
+      const unsigned short eb = ((((unsigned)s >> 1) + 1u) & 1u) ? 0x4000u : 0u;
+      reinterpret_cast<unsigned short*>(hp)[(0 * ROWS + cb) * 8 + ci] = __builtin_bit_cast(unsigned short, h1) | eb;
+      reinterpret_cast<unsigned short*>(hp)[(1 * ROWS + cb) * 8 + ci] = __builtin_bit_cast(unsigned short, h2v) | eb;
       __builtin_amdgcn_wave_barrier();
       // the row's 8 halfs were written by 8 consecutive lanes of this wave: LDS operations of one wave complete in order
       if (ci == 0) {
@@ -457,13 +391,9 @@ __global__ __launch_bounds__(512, 1) void lstm_wide_fwd_kernel(
         dst[0] = *reinterpret_cast<const u32x4*>(hp + (0 * ROWS + cb) * 8);     // plain stores: land in this XCD's L2
         dst[ROWS] = *reinterpret_cast<const u32x4*>(hp + (1 * ROWS + cb) * 8);
       }
-      if constexpr (EP) {
-        // no acknowledgement to wait for and no flag: the granules validate themselves.  The workgroup's other waves learn
-        // from an LDS counter that this cell wave has published.
-        if (lane == 0) atomicAdd(info + 3, 1u);
-      } else {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // acknowledged before the flag goes out
-      }
+      // no acknowledgement to wait for and no flag: the granules validate themselves.  The workgroup's other waves learn
+      // from an LDS counter that this cell wave has published.
+      if (lane == 0) atomicAdd(info + 3, 1u);
       // per-frame results for the BPTT / the layer above
       if (rowok) {
         if (valid) {
@@ -477,13 +407,7 @@ __global__ __launch_bounds__(512, 1) void lstm_wide_fwd_kernel(
         }
       }
     }
-    if constexpr (!EP) {
-      __syncthreads();                                      // #3: every cell wave's h is acknowledged
-      WMARK(9);
-      if (tid == 0) hflag[nb] = (unsigned)s + 1u;
-    } else {
-      WMARK(9);
-    }
+    WMARK(9);
     if (abort_word) { aborted = true; break; }
   }
   WSTAMP_FLUSH;
@@ -673,7 +597,7 @@ __global__ __launch_bounds__(512, 1) void lstm_wide_bwd_kernel(
         u32x4* src = inbox + ((((size_t)((k - 1) & 1) * 256 + me) * 8 + w) * MT * 2) * 64 + lane;
         u32x4 v[MT][2];
         ok = false;
-        for (unsigned n = 0; n < WIDE_SPIN; ++n) {
+        for (unsigned n = 0; n < SPIN_BUDGET; ++n) {
           v[MT - 1][1] = ld16_sc1(src + ((MT - 1) * 2 + 1) * 64);
           wait_vm0(v[MT - 1][1]);
           const u32x4 q = v[MT - 1][1];
@@ -719,20 +643,19 @@ __global__ __launch_bounds__(512, 1) void lstm_wide_bwd_kernel(
       // (the sentinels this wave wrote as a READER one step ago are acknowledged before it writes as a source again: whoever
       //  sees the partial sums below and later refills a block this wave reset finds the reset in the L2 already)
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      wstatic_for<0, MT>([&](auto mc) {
+      static_for<0, MT>([&](auto mc) {
         constexpr int m = decltype(mc)::value;
         // both 16 x 16 tiles of this M tile together; the A fragments of k-tile kt+1 are read while kt multiplies (the
         // scheduling barriers keep the compiler from hoisting every read to the top, which costs 64 registers per M tile)
         f32x4 t0 = (f32x4){0.f, 0.f, 0.f, 0.f}, t1 = (f32x4){0.f, 0.f, 0.f, 0.f};
         // fragments of k-tiles kt+1 and kt+2 are in flight while kt multiplies (PF = prefetch distance)
-        constexpr int PF = WIDE_PF;
         h8 q0[PF + 1], q1[PF + 1];
 #pragma unroll
         for (int j = 0; j < PF; ++j) {
           q0[j] = __builtin_bit_cast(h8, Alds[((j * MT + m) * 2 + 0) * 64 + lane]);
           q1[j] = __builtin_bit_cast(h8, Alds[((j * MT + m) * 2 + 1) * 64 + lane]);
         }
-        wstatic_for<0, 8>([&](auto ktc) {
+        static_for<0, 8>([&](auto ktc) {
           constexpr int kt = decltype(ktc)::value;
           if constexpr (kt + PF < 8) {
             q0[(kt + PF) % (PF + 1)] = __builtin_bit_cast(h8, Alds[(((kt + PF) * MT + m) * 2 + 0) * 64 + lane]);
@@ -766,7 +689,7 @@ __global__ __launch_bounds__(512, 1) void lstm_wide_bwd_kernel(
         constexpr int NL = (4 * PU + 63) / 64;               // 16-byte loads per lane for 4 sources
         u32x4 v[NL];
         ok = false;
-        for (unsigned n = 0; n < WIDE_SPIN; ++n) {
+        for (unsigned n = 0; n < SPIN_BUDGET; ++n) {
           bool all = true;
 #pragma unroll
           for (int j = 0; j < NL; ++j)
@@ -811,7 +734,7 @@ __global__ __launch_bounds__(512, 1) void lstm_wide_bwd_kernel(
       float dcn = 0.f;
       if (valid) {
         if (s == 0) cpv = 0.f;
-        const float tc = wtanh(cc);
+        const float tc = tanhf_(cc);
         const float dct = dc + dhs * act.w * (1.f - tc * tc);
         dg.x = dct * act.y * act.x * (1.f - act.x);
         dg.y = dct * act.x * (1.f - act.y * act.y);
@@ -921,7 +844,7 @@ void launch_lstm_wide_fwd(const LstmDims& dm, int d, const void* Uw, const float
                           float* fault, float forget_bias, hipStream_t st) {
   (void)hipMemsetAsync(ctl, 0, sizeof(WideCtl), st);
   (void)hipMemsetAsync(part, 0xff, wide_part_bytes(dm.Bp), st);   // every inbox word = the sentinel
-  if (NASR_WIDE_EPOCH) (void)hipMemsetAsync(hx, 0, wide_hx_bytes(dm.Bp), st);   // the h buffers start from epoch 0
+  (void)hipMemsetAsync(hx, 0, wide_hx_bytes(dm.Bp), st);   // the h buffers start from epoch 0
   WideGeom gm{dm.T, dm.Bp, dm.Hp, dm.D, d, -1, 0, fault};
   if (const char* e = test_hook("NASR_WIDE_FAULT")) gm.inject = atoi(e);
   const int MT = dm.Bp / 16;

@@ -69,6 +69,15 @@ def test_environment_is_read_only_at_create_and_by_the_test_hooks():
         assert not call.search(src), f'{f} reads the environment outside nasr_create / test_hook'
 
 
+def test_no_compile_time_variants_besides_the_stamp_builds():
+    """The only `#ifndef X / #define X <default>` blocks under csrc/ are the diagnostic stamp builds: a variant that was
+    measured and lost is deleted, not kept behind a macro the product build never sets."""
+    csrc = os.path.join(ROOT, 'neuralasr_amd', 'csrc')
+    default = re.compile(r'^[ \t]*#[ \t]*ifndef[ \t]+(\w+)[ \t]*\n[ \t]*#[ \t]*define[ \t]+\1\b', re.M)
+    found = {(f, m) for f in sorted(os.listdir(csrc)) for m in default.findall(open(os.path.join(csrc, f)).read())}
+    assert found == {('lstm_persist.hip', 'NASR_PSTAMP'), ('lstm_wide.hip', 'NASR_WSTAMP')}, sorted(found)
+
+
 def test_bench_touches_the_oracle_only_in_its_cpu_baseline_leg():
     """bench.py builds its workload, synthetic batch and weights itself; `oracle` appears only inside cpu_baseline()
     and the Workload.oracle_spec() helper that leg calls."""

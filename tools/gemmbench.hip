@@ -1,5 +1,5 @@
 // gemmbench.hip — times the GEMM shapes of the training step (B 16, T 500, H 500, F 546).
-// hipcc --offload-arch=gfx950 -O3 -std=c++17 [-DNASR_GEMM_BK=..] tools/gemmbench.hip -o tools/sb_gemm
+// hipcc --offload-arch=gfx950 -O3 -std=c++17 tools/gemmbench.hip -o tools/sb_gemm
 #include "../neuralasr_amd/csrc/gemm.hip"
 #include "../neuralasr_amd/csrc/gemm_tph.hip"
 #include "../neuralasr_amd/csrc/optim.hip"

@@ -26,7 +26,7 @@ if [ -x tools/sb_st ]; then
   timeout -k 5 60 tools/sb_st 500 16 500 2 0 > "$OUT/${TAG}_persist_stamps.log" 2>&1
   python3 tools/stamps_to_json.py bilstm3x500 "$OUT/${TAG}_persist_stamps.log" "$OUT/persist_stamps.json" > /dev/null
 fi
-if [ -x tools/sb_wide_st ]; then   # wide persistent kernels (Hp 2048): hipcc ... -DNASR_WSTAMP=1 tools/widebench.hip lstm.hip lstm_wide.hip
+if [ -x tools/sb_wide_st ]; then   # wide persistent kernels (Hp 2048): hipcc ... -DNASR_WSTAMP=1 tools/widebench.hip lstm.hip lstm_wide.hip optim.hip
   WIDE_STAMPS=1 timeout -k 5 120 tools/sb_wide_st 500 32 0 > "$OUT/${TAG}_wide_stamps.log" 2>&1
   python3 tools/stamps_to_json.py --wide deepspeech "$OUT/${TAG}_wide_stamps.log" "$OUT/persist_stamps.json" > /dev/null
 fi

@@ -3,7 +3,7 @@
 timestep, median over the 256 workgroups of the last repetition) into profiles/persist_stamps.json, which bench.py quotes
 as roofline.latency.phase_cycles.
     hipcc --offload-arch=gfx950 -O3 -std=c++17 -DNASR_PSTAMP=1 tools/persistbench.hip neuralasr_amd/csrc/lstm.hip \
-          neuralasr_amd/csrc/lstm_persist.hip -o tools/sb_st && tools/sb_st 500 16 500 2 0 > log
+          neuralasr_amd/csrc/lstm_persist.hip neuralasr_amd/csrc/optim.hip -o tools/sb_st && tools/sb_st 500 16 500 2 0 > log
     python tools/stamps_to_json.py <workload key> log [profiles/persist_stamps.json]
     python tools/stamps_to_json.py --wide deepspeech widebench.log [profiles/persist_stamps.json]"""
 import json

@@ -1,7 +1,7 @@
 // widebench.hip — development check + timing of the wide persistent forward recurrence (lstm_wide.hip) against the
 // per-timestep kernels (lstm.hip) at DeepSpeech's width: Hp 2048, both directions, random U / gate pre-activations.
 // Build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -I neuralasr_amd/csrc tools/widebench.hip neuralasr_amd/csrc/lstm.hip \
-//        neuralasr_amd/csrc/lstm_wide.hip -o tools/sb_wide
+//        neuralasr_amd/csrc/lstm_wide.hip neuralasr_amd/csrc/optim.hip -o tools/sb_wide
 // Run:   tools/sb_wide [T=64] [B=32] [check=1]
 #include "kernels.h"
 #include <cmath>
