@@ -309,6 +309,51 @@ int nasr_set_recurrence_mode(nasr_handle h, int persistent);
  * that sits on the per-step kernels slows every rank of a data-parallel job: bench.py reports these per rank). */
 int nasr_get_persist_stats(nasr_handle h, int* aborts, int* rearms);
 
+/* ---- the WaveNet CTC network (networks/wavenet.py) ------------------------------------------
+ * front/conv_in (1x1 conv F->dim, batch norm, tanh); num_blocks x num_rates residual blocks of a gated dilated
+ * convolution (kernel_size taps at rates[r], filter tanh(BN) times gate sigmoid(BN)), a 1x1 conv with BN and tanh, the
+ * residual sum and the skip sum; logit/conv_1 (1x1, BN, tanh) over the skip sum; logit/conv_2 (1x1 to the classes, no BN).
+ * Every convolution is bias-free.  The reference has num_blocks 3, rates (1,2,4,8,16), dim 128, kernel_size 7: only
+ * dim 128 and kernel_size 7 are implemented.  Batch norm is tf.contrib.layers.batch_norm(decay, epsilon, center, scale,
+ * zero_debias_moving_mean): gradient passes (nasr_compute_grads, nasr_loss_and_grads, nasr_train_step) normalise with the
+ * batch statistics over all T x B frames (padding frames past seq_len included) and update the moving statistics;
+ * nasr_forward, nasr_loss and the decoders use the moving statistics.  Flat parameter order = TF variable creation order:
+ * front/conv_in/W [F,dim], .../BatchNorm/beta, gamma; per block block_<i>_<r>/conv_filterblock_<i>_<r>/W [k*dim,dim] (row
+ * tap*dim + in channel), beta, gamma, conv_gate... likewise, conv_out... [dim,dim], beta, gamma; logit/conv_1/W, beta,
+ * gamma; logit/conv_2/W [dim,C].  nasr_create_wavenet returns an ordinary handle: every call above that is not about the
+ * recurrence works on it; nasr_*_recurrence_mode, nasr_set_wgrad_overlap, nasr_set_row_compaction and
+ * nasr_*_dropout_state return NASR_ERR_STATE. */
+typedef struct {
+  int32_t feature_size;  /* F */
+  int32_t num_classes;   /* C; blank = C-1 */
+  int32_t dim;           /* 128 */
+  int32_t kernel_size;   /* 7 */
+  int32_t num_blocks;    /* 3 */
+  int32_t num_rates;     /* 5 (<= 8) */
+  int32_t rates[8];      /* 1, 2, 4, 8, 16 */
+  float bn_epsilon;      /* 1e-3 (contrib batch_norm's default) */
+  float bn_decay;        /* 0.99 */
+  float learning_rate;
+  float beta1, beta2, epsilon; /* Adam: 0.9, 0.999, 1e-8 */
+} nasr_wavenet_cfg;
+int nasr_create_wavenet(const nasr_wavenet_cfg* cfg, int device_id, void* stream, nasr_handle* out);
+/* Batch-norm state: S = 2 + 3*num_blocks*num_rates sites in variable creation order (conv_in; per block filter, gate,
+ * conv_out; conv_1), dim channels each: nasr_wavenet_bn_count = S*dim floats per array.  moving_mean, moving_variance, the
+ * zero-debias accumulator `biased` and the update count (TF's local_step) - what a checkpoint carries besides the
+ * trainable variables. */
+int64_t nasr_wavenet_bn_count(nasr_handle h);
+int nasr_wavenet_get_bn_state(nasr_handle h, float* moving_mean, float* moving_var, float* biased, int64_t n,
+                              int64_t* updates);
+int nasr_wavenet_set_bn_state(nasr_handle h, const float* moving_mean, const float* moving_var, const float* biased,
+                              int64_t n, int64_t updates);
+/* Data parallelism (make_parallel: every tower applies its own update).  hold = 1: gradient passes leave the moving
+ * statistics alone; nasr_wavenet_get_batch_stats returns the last gradient pass's per-site batch mean and the variance its
+ * update would use (N/(N-1) x the batch variance at the 1x1 sites, the batch variance at the dilated ones), [S][dim];
+ * nasr_wavenet_apply_bn_stats applies `count` such updates in order ([count][S][dim] each). */
+int nasr_wavenet_set_bn_hold(nasr_handle h, int hold);
+int nasr_wavenet_get_batch_stats(nasr_handle h, float* mean, float* var, int64_t n);
+int nasr_wavenet_apply_bn_stats(nasr_handle h, const float* mean, const float* var, int64_t n, int count);
+
 #ifdef __cplusplus
 }
 #endif

@@ -32,6 +32,8 @@ SYMBOLS = [
     'nasr_comm_allreduce_grads', 'nasr_comm_mean', 'nasr_comm_destroy', 'nasr_get_step_results', 'nasr_settle_step',
     'nasr_step_token', 'nasr_settle_token', 'nasr_diag_bucket_traffic', 'nasr_get_step_logits',
     'nasr_set_wgrad_overlap', 'nasr_get_wgrad_overlap', 'nasr_set_row_compaction', 'nasr_resident_rows',
+    'nasr_create_wavenet', 'nasr_wavenet_bn_count', 'nasr_wavenet_get_bn_state', 'nasr_wavenet_set_bn_state',
+    'nasr_wavenet_set_bn_hold', 'nasr_wavenet_get_batch_stats', 'nasr_wavenet_apply_bn_stats',
 ]
 
 
@@ -41,6 +43,13 @@ class ModelCfg(Structure):
                 ('beta1', c_float), ('beta2', c_float), ('epsilon', c_float),
                 ('num_pre', c_int32), ('pre_width', c_int32 * 3), ('post_width', c_int32), ('relu_clip', c_float),
                 ('dropout', c_float * 4)]
+
+
+class WaveNetCfg(Structure):
+    _fields_ = [('feature_size', c_int32), ('num_classes', c_int32), ('dim', c_int32), ('kernel_size', c_int32),
+                ('num_blocks', c_int32), ('num_rates', c_int32), ('rates', c_int32 * 8), ('bn_epsilon', c_float),
+                ('bn_decay', c_float), ('learning_rate', c_float), ('beta1', c_float), ('beta2', c_float),
+                ('epsilon', c_float)]
 
 
 class PhaseTimes(Structure):
@@ -143,6 +152,13 @@ def load():
         'nasr_get_step_logits': (c_int, [H, fp]),
         'nasr_set_wgrad_overlap': (c_int, [H, c_int]),
         'nasr_get_wgrad_overlap': (c_int, [H]),
+        'nasr_create_wavenet': (c_int, [POINTER(WaveNetCfg), c_int, c_void_p, POINTER(H)]),
+        'nasr_wavenet_bn_count': (c_int64, [H]),
+        'nasr_wavenet_get_bn_state': (c_int, [H, fp, fp, fp, c_int64, POINTER(c_int64)]),
+        'nasr_wavenet_set_bn_state': (c_int, [H, fp, fp, fp, c_int64, c_int64]),
+        'nasr_wavenet_set_bn_hold': (c_int, [H, c_int]),
+        'nasr_wavenet_get_batch_stats': (c_int, [H, fp, fp, c_int64]),
+        'nasr_wavenet_apply_bn_stats': (c_int, [H, fp, fp, c_int64, c_int]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

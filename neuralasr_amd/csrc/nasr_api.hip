@@ -403,6 +403,11 @@ int nasr_compute_grads(nasr_handle h) {
     h->window_open = true;
     h->total_valid = false;
   }
+  if (h->wn) {           // a gradient pass: training-mode batch norm
+    int rc = wn_forward(h, true);
+    if (!rc) rc = ctc_forward(h);
+    return rc ? rc : backward(h);
+  }
   rec_rearm(h);
   int rc = forward(h);   // clears the step's fault word
   if (rc) return rc;
@@ -595,6 +600,7 @@ int nasr_resident_frames(nasr_handle h, int64_t* frames) {
 
 int nasr_set_row_compaction(nasr_handle h, int enabled) {
   if (!h) return NASR_ERR_ARG;
+  if (h->wn) return h->fail(NASR_ERR_STATE, "nasr_set_row_compaction: a WaveNet handle has no recurrence to compact rows for");
   // what the resident batch's plane buffers hold depends on it: takes effect with the next uploaded / committed batch
   h->compactable = enabled && h->ndense == 0;
   return NASR_OK;
@@ -750,6 +756,7 @@ int nasr_set_graph_mode(nasr_handle h, int enabled) {
 
 int nasr_set_dropout_state(nasr_handle h, uint32_t seed, uint32_t counter) {
   if (!h) return NASR_ERR_ARG;
+  if (h->wn) return h->fail(NASR_ERR_STATE, "nasr_set_dropout_state: a WaveNet handle has no dropout");
   h->drop_seed = seed;
   h->drop_counter = counter;
   return NASR_OK;
@@ -757,6 +764,7 @@ int nasr_set_dropout_state(nasr_handle h, uint32_t seed, uint32_t counter) {
 
 int nasr_get_dropout_state(nasr_handle h, uint32_t* seed, uint32_t* counter) {
   if (!h) return NASR_ERR_ARG;
+  if (h->wn) return h->fail(NASR_ERR_STATE, "nasr_get_dropout_state: a WaveNet handle has no dropout");
   if (seed) *seed = h->drop_seed;
   if (counter) *counter = h->drop_counter;
   return NASR_OK;
@@ -764,6 +772,7 @@ int nasr_get_dropout_state(nasr_handle h, uint32_t* seed, uint32_t* counter) {
 
 int nasr_set_wgrad_overlap(nasr_handle h, int enabled) {
   if (!h) return NASR_ERR_ARG;
+  if (h->wn) return h->fail(NASR_ERR_STATE, "nasr_set_wgrad_overlap: a WaveNet handle has no recurrence");
   if (enabled && !h->wst) return h->fail(NASR_ERR_STATE, "the weight-gradient side stream was not set up for this handle "
                                                          "(needs the persistent recurrence at Hp = 512 and more than one layer)");
   HIPCHK(h, hipStreamSynchronize(h->st));

@@ -9,6 +9,7 @@ using namespace nasr_impl;
 namespace nasr_impl {
 
 int ensure_shape(nasr_ctx* h, int B, int T, int Lmax) {
+  if (h->wn) return wn_ensure_shape(h, B, T, Lmax);
   const int Bp = rup(B, 16);
   const int Tp = nasr_logit_frames(h, T);
   const size_t R = (size_t)T * Bp;
@@ -315,11 +316,12 @@ int slot_commit(nasr_ctx* h, BatchSlot* s) {
                             h->X0.as<float>(), B, Bp, T, s->ctx, s->ncep, h->Fp, h->st);
     else
       launch_pack_feats(s->dfeats.as<float>(), h->X0.as<float>(), B, Bp, T, h->F, h->Fp, h->st);
-    pl_scales(h, h->X0.as<float>(), T * Bp, h->Fp, h->Fp, &h->sc_x0r, &h->sc_x0c, h->st);
+    if (!h->wn)         // (the WaveNet's GEMMs read the fp32 features as they are)
+      pl_scales(h, h->X0.as<float>(), T * Bp, h->Fp, h->Fp, &h->sc_x0r, &h->sc_x0c, h->st);
     if (h->cmp_rows)    // the feature rows' scales in the compacted order (layer 0's input GEMM)
       launch_gather_rows(h->sc_cx.sp(), h->sc_x0r.sp(), h->vrow_p, h->cmp_rows_p, 1.f, h->st),
       launch_gather_rows(h->sc_cx.ip(), h->sc_x0r.ip(), h->vrow_p, h->cmp_rows_p, 1.f, h->st);
-    if (s->has_labels && h->npre == 0)   // layer-0 input with the frame index as contraction index, for dWx = X^T dG
+    if (s->has_labels && h->npre == 0 && !h->wn)   // layer-0 input with the frame index as contraction index, for dWx = X^T dG
       launch_tph_split2(h->X0.as<float>(), nullptr, h->X0TTP.as<unsigned char>(), h->cmp_rows ? h->cmp_rows : T * Bp, h->Fp, h->Fp,
                         nullptr, 1.f, h->sc_x0c.sp(), 1.f, nullptr, h->st, h->cmp_rows ? h->vrow_p : nullptr);
     HIPCHK(h, hipGetLastError());

@@ -6,6 +6,7 @@
 //   nasr_pass.hip    forward, CTC, backward: the orchestration of one step on the handle's streams
 //   nasr_api.hip     the C ABI entry points
 //   nasr_comm.hip    RCCL bound with dlopen: nasr_comm_*
+//   nasr_wavenet.hip the WaveNet handle (nasr_create_wavenet): its layout, buffers, BN state and pass
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -21,6 +22,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -168,6 +170,10 @@ struct BatchSlot {
 // the kinds of kernels that run the recurrence; the values are the codes of nasr_get_recurrence_mode
 enum class RecKind { Step = 0, Persist = 1, Wide = 2 };
 
+// What a WaveNet handle holds beyond the common parts (nasr_wavenet.hip); NULL on every other handle.
+struct WnState;
+struct WnStateDelete { void operator()(WnState* w) const; };
+
 }  // namespace nasr_impl
 
 // (internal header: the translation units behind the ABI use both namespaces unqualified)
@@ -177,6 +183,7 @@ using namespace nasr_impl;
 struct nasr_ctx {
 
   nasr_model_cfg cfg;
+  std::unique_ptr<WnState, WnStateDelete> wn;   // a WaveNet handle (nasr_create_wavenet); the LSTM members stay unused
   int device = 0;
   Stream st;
   // Bulk GEMMs (input projections, input / weight gradients, dense stages): fp32 products from two fp16 planes per
@@ -479,5 +486,10 @@ CtcDims ctc_dims(nasr_ctx* h);
 int ctc_forward(nasr_ctx* h);
 int backward(nasr_ctx* h);
 int fetch_logits(nasr_ctx* h, float* logits_out);
+
+// ---- nasr_wavenet.hip (the WaveNet handle's side of ensure_shape, forward and backward)
+int wn_ensure_shape(nasr_ctx* h, int B, int T, int Lmax);
+int wn_forward(nasr_ctx* h, bool training);
+int wn_backward(nasr_ctx* h);
 
 }  // namespace nasr_impl

@@ -458,7 +458,10 @@ class Engine:
     def recurrence_mode(self):
         """'persistent' (one launch per layer pass, lstm_persist.hip), 'wide-persistent' (Hp = 2048: one persistent launch per
         direction and pass, lstm_wide.hip) or 'per-step' (lstm.hip)."""
-        return ('per-step', 'persistent', 'wide-persistent')[int(self.lib.nasr_get_recurrence_mode(self.h))]
+        m = int(self.lib.nasr_get_recurrence_mode(self.h))
+        if m < 0:
+            self._ck(m)
+        return ('per-step', 'persistent', 'wide-persistent')[m]
 
     def persist_stats(self):
         """(aborts, re-arms) of the persistent recurrence on this handle (include/nasr.h, nasr_get_persist_stats)."""
@@ -474,3 +477,64 @@ class Engine:
         pt = _lib.PhaseTimes()
         self._ck(self.lib.nasr_get_phase_times(self.h, byref(pt)))
         return pt.as_dict()
+
+
+class WaveNetEngine(Engine):
+    """An Engine over a WaveNet handle (include/nasr.h: nasr_create_wavenet): the same step, parameter, batch, decoder and
+    gradient-exchange calls, plus the batch-norm state.  Only dim 128 and kernel size 7 are implemented."""
+
+    def __init__(self, feature_size, num_classes, num_blocks=3, rates=(1, 2, 4, 8, 16), dim=128, kernel_size=7,
+                 bn_epsilon=1e-3, bn_decay=0.99, learning_rate=1e-4, beta1=0.9, beta2=0.999, epsilon=1e-8, device_id=0,
+                 stream=None):
+        self.lib = _lib.load()
+        rates = tuple(int(r) for r in rates)
+        if len(rates) > 8:
+            raise ValueError('at most 8 dilation rates')
+        self.cfg = _lib.WaveNetCfg(int(feature_size), int(num_classes), int(dim), int(kernel_size), int(num_blocks),
+                                   len(rates), (c_int32 * 8)(*(rates + (0,) * (8 - len(rates)))), float(bn_epsilon),
+                                   float(bn_decay), float(learning_rate), float(beta1), float(beta2), float(epsilon))
+        if stream is not None and int(stream) == 0:
+            raise ValueError('stream 0 (the legacy default stream) cannot carry the engine')
+        self.h = c_void_p()
+        rc = self.lib.nasr_create_wavenet(byref(self.cfg), int(device_id), c_void_p(stream) if stream else None,
+                                          byref(self.h))
+        if rc != 0:
+            msg = self.lib.nasr_last_error(None)
+            self.h = None
+            raise _lib.NasrError(rc, msg.decode() if msg else 'nasr_create_wavenet failed')
+        self.num_classes = int(num_classes)
+        self.param_count = int(self.lib.nasr_param_count(self.h))
+        self.bn_count = int(self.lib.nasr_wavenet_bn_count(self.h))
+
+    def bn_state(self):
+        """(moving_mean, moving_variance, biased, updates): [S, dim] arrays in site order and the update count."""
+        n = self.bn_count
+        mm, mv, bs = (np.empty(n, np.float32) for _ in range(3))
+        cnt = c_int64()
+        self._ck(self.lib.nasr_wavenet_get_bn_state(self.h, _fp(mm), _fp(mv), _fp(bs), n, byref(cnt)))
+        d = self.cfg.dim
+        return mm.reshape(-1, d), mv.reshape(-1, d), bs.reshape(-1, d), cnt.value
+
+    def set_bn_state(self, moving_mean, moving_var, biased, updates):
+        mm, mv, bs = (_f32(a).ravel() for a in (moving_mean, moving_var, biased))
+        self._ck(self.lib.nasr_wavenet_set_bn_state(self.h, _fp(mm), _fp(mv), _fp(bs), mm.size, int(updates)))
+
+    def set_bn_hold(self, hold):
+        self._ck(self.lib.nasr_wavenet_set_bn_hold(self.h, int(bool(hold))))
+
+    def batch_stats(self):
+        """(mean, variance of the update) of the last gradient pass, [S, dim] each."""
+        n = self.bn_count
+        m, v = np.empty(n, np.float32), np.empty(n, np.float32)
+        self._ck(self.lib.nasr_wavenet_get_batch_stats(self.h, _fp(m), _fp(v), n))
+        d = self.cfg.dim
+        return m.reshape(-1, d), v.reshape(-1, d)
+
+    def apply_bn_stats(self, means, variances):
+        """Apply len(means) moving-statistics updates in order (means / variances: sequences of [S, dim] arrays)."""
+        k = len(means)
+        if k == 0:
+            return
+        m = _f32(np.stack([np.asarray(x).ravel() for x in means]))
+        v = _f32(np.stack([np.asarray(x).ravel() for x in variances]))
+        self._ck(self.lib.nasr_wavenet_apply_bn_stats(self.h, _fp(m), _fp(v), self.bn_count, k))

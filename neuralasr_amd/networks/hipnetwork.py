@@ -102,6 +102,18 @@ class HipNetwork(Network):
     def initial_params(self, tensors, seed):
         return _glorot_init(tensors, seed)
 
+    # model families with state beyond the trainable variables (WaveNet's batch norm) override these three
+    def model_state(self):
+        """Extra arrays a checkpoint carries (name -> array); none for the LSTM families."""
+        return {}
+
+    def restore_model_state(self, npz):
+        pass
+
+    def after_compute_grads(self):
+        """Called on every rank of a multi-process step right after compute_grads has been enqueued."""
+        pass
+
     # ------------------------------------------------------------------ per-model hook
     def create_network(self, features, labels, seq_len, labels_len, num_classes, is_training):
         """(logits [T',B,C], loss, decoded ids per utterance, None, mean LER) for a batch
@@ -126,6 +138,7 @@ class HipNetwork(Network):
             with np.load(files[-1]) as z:
                 self.engine.set_params(z['params'])
                 self.engine.set_adam_state(z['adam_m'], z['adam_v'], int(z['step']))
+                self.restore_model_state(z)
             self.logger.info('Done Restoring checkpoint: ' + files[-1])
         elif self.coll.rank == 0:
             if os.path.exists(model_dir):
@@ -148,7 +161,8 @@ class HipNetwork(Network):
         np.savez(path, params=self.engine.get_params(), adam_m=m, adam_v=v, step=np.int64(step),
                  meta=json.dumps({'hidden': self.num_hidden, 'layers': self.num_layers,
                                   'bidirectional': self.bidirectional, 'merge': self.merge,
-                                  'classes': self.num_classes, 'feature_size': self.config.feature_size}))
+                                  'classes': self.num_classes, 'feature_size': self.config.feature_size}),
+                 **self.model_state())
         for old in self._ckpt_files(self.config.model_dir)[:-self.keep_checkpoints]:
             os.remove(old)
 
@@ -266,6 +280,7 @@ class HipNetwork(Network):
         self.engine.set_step_decode(True, logits=beam, greedy=not beam)     # (the beam search reads the logits; no greedy pass then)
         self.engine.compute_grads()
         if self.coll.world > 1:
+            self.after_compute_grads()
             if self._grad_tensor is None:
                 self._grad_tensor = self.engine.grad_tensor()
                 self._reducer = self.coll.bucketed(self.engine, self._grad_tensor) if self.bucketed_allreduce else None
