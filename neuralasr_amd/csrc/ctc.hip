@@ -194,7 +194,7 @@ __device__ __forceinline__ void ctc_ab_log(
 #pragma unroll
     for (int i = 0; i < KS; ++i) {
       const int s = lane * KS + i;
-      const int e2 = (s >= 2 && (s & 1)) ? lab[(s >> 1) - 1] : blank;   // l'_{s-2}
+      const int e2 = (act[i] && s >= 2 && (s & 1)) ? lab[(s >> 1) - 1] : blank;   // l'_{s-2} (past S, beyond the label row)
       skip[i] = act[i] && s >= 2 && ext[i] != blank && ext[i] != e2;
     }
     float a[KS], e[G][KS];
@@ -377,7 +377,7 @@ __device__ __forceinline__ void ctc_fast_walk(const int* __restrict__ labels, co
     const bool act = s < S;
     ext[i] = act ? ((s & 1) ? lab[s >> 1] : blank) : 31;      // column 31 of an emission row is NEG
     if (fwd) {
-      const int e2 = (s >= 2 && (s & 1)) ? lab[(s >> 1) - 1] : blank;   // l'_{s-2}
+      const int e2 = (act && s >= 2 && (s & 1)) ? lab[(s >> 1) - 1] : blank;   // l'_{s-2} (past S, beyond the label row)
       skip[i] = act && s >= 2 && ext[i] != blank && ext[i] != e2;
     } else {
       const int e2 = (s + 2 < S && (s & 1)) ? lab[(s >> 1) + 1] : blank;   // l'_{s+2}

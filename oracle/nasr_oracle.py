@@ -793,3 +793,13 @@ def synth_batch(spec: ModelSpec, B, T, seed=1234, var_len=False, Lmin=None, Lmax
     for b in range(B):
         labels[b, :label_len[b]] = rs.randint(1, max(C - 1, 2), size=label_len[b])
     return feats, seq_len, labels, label_len
+
+
+def pinned_label(rs, L, rep, C):
+    """L label ids in [0, C-2] with exactly `rep` adjacent repeats: in L + rep frames (TF's least, ctc_feasible) every frame of
+    the one alignment is forced."""
+    at = set(rs.choice(np.arange(1, L), rep, replace=False).tolist()) if rep else set()
+    lab = [int(rs.randint(0, C - 1))]
+    for i in range(1, L):
+        lab.append(lab[-1] if i in at else int((lab[-1] + 1 + rs.randint(0, C - 2)) % (C - 1)))
+    return lab

@@ -54,6 +54,42 @@ def test_ctc_matches_torch():
     np.testing.assert_allclose(grad, lt.grad.numpy(), atol=1e-10)
 
 
+@pytest.mark.parametrize("scale", [1.0, 60.0], ids=['flat', 'sharp'])
+def test_ctc_matches_torch_at_the_lattice_limit(scale):
+    """The shapes tests/test_gpu_ctc_lattice.py takes its reference at: 511 labels in 1100 frames (the longest label the
+    lattice kernel takes), a pinned label (L + adjacent repeats = seq_len: one alignment's worth of paths), a label far
+    below the width of the label array (whose padding holds class ids, not zeros), an empty label; flat posteriors and
+    posteriors as sharp as the GPU test's projection scaled by 60."""
+    rs = np.random.RandomState(511)
+    Tp, B, C, Lmax = 1100, 4, 29, 511
+    logits = rs.randn(Tp, B, C) * scale
+    labels = rs.randint(0, C - 1, size=(B, Lmax))
+    pin = O.pinned_label(rs, 300, 120, C)
+    labels[1, :300] = pin
+    assert sum(a == b for a, b in zip(pin[:-1], pin[1:])) == 120
+    seq_len = np.array([1100, 420, 977, 350])
+    label_len = np.array([511, 300, 90, 0])
+    assert O.ctc_feasible(labels[0], 1100) and not O.ctc_feasible(pin, 419)
+    nll, grad = O.ctc_loss_and_grad(logits, labels, label_len, seq_len)
+    lt = torch.tensor(logits, requires_grad=True)
+    tl = torch.nn.functional.ctc_loss(torch.log_softmax(lt, -1), torch.tensor(labels), torch.tensor(seq_len),
+                                      torch.tensor(label_len), blank=C - 1, reduction='none', zero_infinity=False)
+    tl.sum().backward()
+    np.testing.assert_allclose(nll, tl.detach().numpy(), rtol=1e-10)
+    # the posteriors are exp(alpha + beta - log p) of log-domain values as large as the nll: fp64 rounds them to ~1e-16 of
+    # that (measured 2e-12 flat, 1.5e-10 sharp at nll 8e4)
+    np.testing.assert_allclose(grad, lt.grad.numpy(), atol=1e-14 * nll.max())
+    # the pinned label has one alignment: its nll is the sum of the forced emissions
+    lp = O.log_softmax(logits[:420, 1])
+    forced = []
+    for i, k in enumerate(pin):
+        if i and k == pin[i - 1]:
+            forced.append(C - 1)
+        forced.append(k)
+    assert len(forced) == 420
+    assert nll[1] == pytest.approx(-lp[np.arange(420), forced].sum(), rel=1e-12)
+
+
 # ----------------------------------------------------------------- LSTM single step by hand
 def test_lstm_single_step_hand_computed():
     # I=1, H=1, one frame: g = x*k_x + 0*k_h + bias; i,j,f,o order
