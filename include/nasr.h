@@ -354,6 +354,37 @@ int nasr_wavenet_set_bn_hold(nasr_handle h, int hold);
 int nasr_wavenet_get_batch_stats(nasr_handle h, float* mean, float* var, int64_t n);
 int nasr_wavenet_apply_bn_stats(nasr_handle h, const float* mean, const float* var, int64_t n, int count);
 
+/* ---- the MFCC front end (utils.py:24-31: convert_to_mfcc) --------------------------------------
+ * python_speech_features 0.6's mfcc(audio, samplerate, numcep=numcep, nfilt=128) on float32 audio: pre-emphasis in
+ * float32 (two roundings), frames of round_half_up(winlen*sr) samples every round_half_up(winstep*sr), zero-padded tail,
+ * rectangular window, then in float64 |rfft(frame, nfft)|^2 / nfft (frames longer than nfft truncated), frame energy, the triangular mel
+ * filterbank over [0, sr/2], log (exact zeros -> float64 eps), DCT-II (ortho), the lifter, c0 <- log(energy); then
+ * include_context (utils.py:8-21) and the whole-utterance (X - mean(X)) / std(X) of utils.py:29, in float64.
+ * nasr_create_featurizer returns an ordinary handle: nasr_last_error, nasr_synchronize and nasr_destroy work on it and
+ * every model call returns NASR_ERR_STATE.  Only nfft = 512 (psf 0.6's default) is implemented; 1 <= nfilt <= 128. */
+typedef struct {
+  int32_t samplerate, numcep, numcontext; /* config.samplerate, numcep, numcontext; 1 <= numcep <= nfilt */
+  int32_t nfilt, nfft;                    /* 128, 512 (utils.py:26) */
+  double winlen, winstep;                 /* 0.025, 0.01 s */
+  float preemph;                          /* 0.97 */
+  int32_t ceplifter, append_energy;       /* 22, 1 */
+} nasr_mfcc_cfg;
+int nasr_create_featurizer(const nasr_mfcc_cfg* cfg, int device_id, void* stream, nasr_handle* out);
+/* Host only (no device needed): the frame count of an utterance of num_samples >= 1 samples (psf framesig: 1 if
+ * num_samples <= frame_len, else 1 + ceil((num_samples - frame_len) / frame_step)); < 0 on a bad cfg or length. */
+int64_t nasr_mfcc_frames(const nasr_mfcc_cfg* cfg, int64_t num_samples);
+/* Host only: the filterbank the kernels use (psf get_filterbanks), bin edges [nfilt+2] and weights [nfilt][nfft/2+1]
+ * (float32 copies of the kernels' float64 table); either may be NULL. */
+int nasr_mfcc_filterbank(const nasr_mfcc_cfg* cfg, int32_t* bins, float* weights);
+/* The features of n utterances: utterance i is audio[offsets[i] .. offsets[i+1]) (float32, at least one sample each).
+ * out [out_rows][(2*numcontext+1)*numcep] receives the utterances' normalised rows one after another; out_rows must be
+ * the sum of their nasr_mfcc_frames.  mean_std (nullable) [n][2]: each utterance's mean and std (ddof 0) over its
+ * stacked matrix, zero pads included.  Returns when out is written (utils.py:24-31 for every utterance). */
+int nasr_featurize(nasr_handle h, const float* audio, const int64_t* offsets, int n, float* out, int64_t out_rows,
+                   double* mean_std);
+/* The last nasr_featurize's device-timed phases: host-to-device copies, kernels, device-to-host copies (ms). */
+int nasr_featurize_times(nasr_handle h, float* h2d_ms, float* kernel_ms, float* d2h_ms);
+
 #ifdef __cplusplus
 }
 #endif

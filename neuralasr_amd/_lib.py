@@ -2,7 +2,7 @@
 missing or no gfx950 device is usable, everything here raises."""
 import ctypes
 import os
-from ctypes import POINTER, Structure, byref, c_char, c_char_p, c_float, c_int, c_int32, c_int64, c_uint32, c_void_p
+from ctypes import POINTER, Structure, byref, c_char, c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_uint32, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, 'libnasr.so')
@@ -34,6 +34,7 @@ SYMBOLS = [
     'nasr_set_wgrad_overlap', 'nasr_get_wgrad_overlap', 'nasr_set_row_compaction', 'nasr_resident_rows',
     'nasr_create_wavenet', 'nasr_wavenet_bn_count', 'nasr_wavenet_get_bn_state', 'nasr_wavenet_set_bn_state',
     'nasr_wavenet_set_bn_hold', 'nasr_wavenet_get_batch_stats', 'nasr_wavenet_apply_bn_stats',
+    'nasr_create_featurizer', 'nasr_mfcc_frames', 'nasr_mfcc_filterbank', 'nasr_featurize', 'nasr_featurize_times',
 ]
 
 
@@ -50,6 +51,12 @@ class WaveNetCfg(Structure):
                 ('num_blocks', c_int32), ('num_rates', c_int32), ('rates', c_int32 * 8), ('bn_epsilon', c_float),
                 ('bn_decay', c_float), ('learning_rate', c_float), ('beta1', c_float), ('beta2', c_float),
                 ('epsilon', c_float)]
+
+
+class MfccCfg(Structure):
+    _fields_ = [('samplerate', c_int32), ('numcep', c_int32), ('numcontext', c_int32), ('nfilt', c_int32),
+                ('nfft', c_int32), ('winlen', c_double), ('winstep', c_double), ('preemph', c_float),
+                ('ceplifter', c_int32), ('append_energy', c_int32)]
 
 
 class PhaseTimes(Structure):
@@ -159,6 +166,11 @@ def load():
         'nasr_wavenet_set_bn_hold': (c_int, [H, c_int]),
         'nasr_wavenet_get_batch_stats': (c_int, [H, fp, fp, c_int64]),
         'nasr_wavenet_apply_bn_stats': (c_int, [H, fp, fp, c_int64, c_int]),
+        'nasr_create_featurizer': (c_int, [POINTER(MfccCfg), c_int, c_void_p, POINTER(H)]),
+        'nasr_mfcc_frames': (c_int64, [POINTER(MfccCfg), c_int64]),
+        'nasr_mfcc_filterbank': (c_int, [POINTER(MfccCfg), ip, fp]),
+        'nasr_featurize': (c_int, [H, fp, POINTER(c_int64), c_int, fp, c_int64, POINTER(c_double)]),
+        'nasr_featurize_times': (c_int, [H, fp, fp, fp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

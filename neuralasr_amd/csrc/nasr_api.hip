@@ -270,10 +270,17 @@ int nasr_synchronize(nasr_handle h) {
   return sync_checked(h);
 }
 
-int64_t nasr_param_count(nasr_handle h) { return h ? h->np_tf : -1; }
-int nasr_num_tensors(nasr_handle h) { return h ? (int)h->tensors.size() : -1; }
+int64_t nasr_param_count(nasr_handle h) {
+  MODEL_CALL(h);
+  return h ? h->np_tf : -1;
+}
+int nasr_num_tensors(nasr_handle h) {
+  MODEL_CALL(h);
+  return h ? (int)h->tensors.size() : -1;
+}
 
 int nasr_tensor_info(nasr_handle h, int idx, char name[64], int64_t* offset, int64_t* rows, int64_t* cols) {
+  MODEL_CALL(h);
   if (!h) return NASR_ERR_ARG;
   if (idx < 0 || idx >= (int)h->tensors.size()) return h->fail(NASR_ERR_ARG, "tensor index out of range");
   const TensorInfo& t = h->tensors[idx];
@@ -288,6 +295,7 @@ int nasr_tensor_info(nasr_handle h, int idx, char name[64], int64_t* offset, int
 }
 
 int nasr_set_params(nasr_handle h, const float* flat, int64_t n) {
+  MODEL_CALL(h);
   if (!h || !flat) return NASR_ERR_ARG;
   if (n != h->np_tf) return h->fail(NASR_ERR_ARG, "nasr_set_params: expected " + std::to_string(h->np_tf) + " floats");
   HIPCHK(h, hipSetDevice(h->device));
@@ -300,6 +308,7 @@ int nasr_set_params(nasr_handle h, const float* flat, int64_t n) {
 }
 
 int nasr_get_params(nasr_handle h, float* flat, int64_t n) {
+  MODEL_CALL(h);
   if (!h || !flat) return NASR_ERR_ARG;
   if (n != h->np_tf) return h->fail(NASR_ERR_ARG, "nasr_get_params: wrong length");
   HIPCHK(h, hipSetDevice(h->device));
@@ -307,6 +316,7 @@ int nasr_get_params(nasr_handle h, float* flat, int64_t n) {
 }
 
 int nasr_set_adam_state(nasr_handle h, const float* m, const float* v, int64_t n, int64_t step) {
+  MODEL_CALL(h);
   if (!h || !m || !v) return NASR_ERR_ARG;
   if (n != h->np_tf || step < 0) return h->fail(NASR_ERR_ARG, "nasr_set_adam_state: wrong length or negative step");
   HIPCHK(h, hipSetDevice(h->device));
@@ -321,6 +331,7 @@ int nasr_set_adam_state(nasr_handle h, const float* m, const float* v, int64_t n
 }
 
 int nasr_get_adam_state(nasr_handle h, float* m, float* v, int64_t n, int64_t* step) {
+  MODEL_CALL(h);
   if (!h) return NASR_ERR_ARG;
   if (n != h->np_tf) return h->fail(NASR_ERR_ARG, "nasr_get_adam_state: wrong length");
   HIPCHK(h, hipSetDevice(h->device));
@@ -337,18 +348,21 @@ int nasr_get_adam_state(nasr_handle h, float* m, float* v, int64_t n, int64_t* s
 }
 
 int nasr_set_learning_rate(nasr_handle h, float lr) {
+  MODEL_CALL(h);
   if (!h) return NASR_ERR_ARG;
   h->lr = lr;
   return NASR_OK;
 }
 
 int nasr_logit_frames(nasr_handle h, int T) {
+  MODEL_CALL(h);
   if (!h) return NASR_ERR_ARG;
   return (h->cfg.bidirectional && h->cfg.merge == NASR_MERGE_STACK_RESHAPE) ? 2 * T : T;
 }
 
 int nasr_upload_batch(nasr_handle h, const float* feats, const int32_t* seq_len, const int32_t* labels,
                       const int32_t* label_len, int B, int T, int Lmax) {
+  MODEL_CALL(h);
   if (!h) return NASR_ERR_ARG;
   return upload(h, feats, seq_len, labels, label_len, B, T, Lmax);
 }
@@ -356,6 +370,7 @@ int nasr_upload_batch(nasr_handle h, const float* feats, const int32_t* seq_len,
 int nasr_upload_batch_context(nasr_handle h, const float* centre, const float* pad_value, int numcontext, int numcep,
                               const int32_t* seq_len, const int32_t* labels, const int32_t* label_len, int B, int T,
                               int Lmax) {
+  MODEL_CALL(h);
   if (!h) return NASR_ERR_ARG;
   if (!centre) return h->fail(NASR_ERR_ARG, "null input buffer");
   return upload(h, nullptr, seq_len, labels, label_len, B, T, Lmax, centre, pad_value, numcontext, numcep);
@@ -363,6 +378,7 @@ int nasr_upload_batch_context(nasr_handle h, const float* centre, const float* p
 
 int nasr_stage_batch(nasr_handle h, const float* feats, const int32_t* seq_len, const int32_t* labels,
                      const int32_t* label_len, int B, int T, int Lmax, int* ticket) {
+  MODEL_CALL(h);
   if (!h) return NASR_ERR_ARG;
   return stage(h, feats, seq_len, labels, label_len, B, T, Lmax, nullptr, nullptr, 0, 0, ticket);
 }
@@ -370,12 +386,14 @@ int nasr_stage_batch(nasr_handle h, const float* feats, const int32_t* seq_len, 
 int nasr_stage_batch_context(nasr_handle h, const float* centre, const float* pad_value, int numcontext, int numcep,
                              const int32_t* seq_len, const int32_t* labels, const int32_t* label_len, int B, int T,
                              int Lmax, int* ticket) {
+  MODEL_CALL(h);
   if (!h) return NASR_ERR_ARG;
   if (!centre) return h->fail(NASR_ERR_ARG, "null input buffer");
   return stage(h, nullptr, seq_len, labels, label_len, B, T, Lmax, centre, pad_value, numcontext, numcep, ticket);
 }
 
 int nasr_commit_batch(nasr_handle h, int ticket) {
+  MODEL_CALL(h);
   if (!h) return NASR_ERR_ARG;
   BatchSlot* s = slot_of_ticket(h, ticket);
   if (!s) return h->fail(NASR_ERR_STATE, "nasr_commit_batch: no staged batch behind this ticket");
@@ -385,6 +403,7 @@ int nasr_commit_batch(nasr_handle h, int ticket) {
 }
 
 int nasr_discard_batch(nasr_handle h, int ticket) {
+  MODEL_CALL(h);
   if (!h) return NASR_ERR_ARG;
   BatchSlot* s = slot_of_ticket(h, ticket);
   if (!s) return h->fail(NASR_ERR_STATE, "nasr_discard_batch: no staged batch behind this ticket");
@@ -393,6 +412,7 @@ int nasr_discard_batch(nasr_handle h, int ticket) {
 }
 
 int nasr_compute_grads(nasr_handle h) {
+  MODEL_CALL(h);
   if (!h) return NASR_ERR_ARG;
   if (!h->resident) return h->fail(NASR_ERR_STATE, "no resident batch");
   HIPCHK(h, hipSetDevice(h->device));
@@ -416,12 +436,19 @@ int nasr_compute_grads(nasr_handle h) {
   return backward(h);
 }
 
-void* nasr_grad_device_ptr(nasr_handle h) { return h ? h->Gbase : nullptr; }
-int64_t nasr_grad_device_count(nasr_handle h) { return h ? h->np_int + GRAD_HEAD : -1; }
+void* nasr_grad_device_ptr(nasr_handle h) { return h && !h->fz ? h->Gbase : nullptr; }
+int64_t nasr_grad_device_count(nasr_handle h) {
+  MODEL_CALL(h);
+  return h ? h->np_int + GRAD_HEAD : -1;
+}
 
-int nasr_grad_bucket_count(nasr_handle h) { return h ? (int)h->buckets.size() : NASR_ERR_ARG; }
+int nasr_grad_bucket_count(nasr_handle h) {
+  MODEL_CALL(h);
+  return h ? (int)h->buckets.size() : NASR_ERR_ARG;
+}
 
 int nasr_grad_bucket(nasr_handle h, int i, int64_t* offset, int64_t* count) {
+  MODEL_CALL(h);
   if (!h) return NASR_ERR_ARG;
   if (i < 0 || i >= (int)h->buckets.size() || !offset || !count) return h->fail(NASR_ERR_ARG, "nasr_grad_bucket: bad index");
   *offset = h->buckets[i].first;
@@ -430,6 +457,7 @@ int nasr_grad_bucket(nasr_handle h, int i, int64_t* offset, int64_t* count) {
 }
 
 int nasr_grad_bucket_wait(nasr_handle h, int i, void* hip_stream) {
+  MODEL_CALL(h);
   if (!h) return NASR_ERR_ARG;
   if (i < 0 || i >= (int)h->buckets.size()) return h->fail(NASR_ERR_ARG, "nasr_grad_bucket_wait: bad index");
   HIPCHK(h, hipStreamWaitEvent((hipStream_t)hip_stream, h->ev_bucket[i], 0));
@@ -437,6 +465,7 @@ int nasr_grad_bucket_wait(nasr_handle h, int i, void* hip_stream) {
 }
 
 int nasr_diag_bucket_traffic(nasr_handle h, int i, void* hip_stream, int nblocks, int passes) {
+  MODEL_CALL(h);
   if (!h) return NASR_ERR_ARG;
   if (i < 0 || i >= (int)h->buckets.size() || nblocks < 1 || nblocks > 1024 || passes < 1)
     return h->fail(NASR_ERR_ARG, "nasr_diag_bucket_traffic: bad bucket index, nblocks (1..1024) or passes");
@@ -448,6 +477,7 @@ int nasr_diag_bucket_traffic(nasr_handle h, int i, void* hip_stream, int nblocks
 }
 
 int nasr_apply_adam(nasr_handle h, float grad_scale) {
+  MODEL_CALL(h);
   if (!h) return NASR_ERR_ARG;
   if (!h->have_grads) return h->fail(NASR_ERR_STATE, "nasr_apply_adam without gradients");
   HIPCHK(h, hipSetDevice(h->device));
@@ -475,6 +505,7 @@ int nasr_apply_adam(nasr_handle h, float grad_scale) {
 }
 
 int nasr_get_grads(nasr_handle h, float* flat, int64_t n) {
+  MODEL_CALL(h);
   if (!h || !flat) return NASR_ERR_ARG;
   if (n != h->np_tf) return h->fail(NASR_ERR_ARG, "nasr_get_grads: wrong length");
   if (!h->have_grads) return h->fail(NASR_ERR_STATE, "nasr_get_grads without gradients");
@@ -483,6 +514,7 @@ int nasr_get_grads(nasr_handle h, float* flat, int64_t n) {
 }
 
 int nasr_set_grads(nasr_handle h, const float* flat, int64_t n) {
+  MODEL_CALL(h);
   if (!h || !flat) return NASR_ERR_ARG;
   if (n != h->np_tf) return h->fail(NASR_ERR_ARG, "nasr_set_grads: wrong length");
   HIPCHK(h, hipSetDevice(h->device));
@@ -525,6 +557,7 @@ int nasr_label_error_rate(const int32_t* hyp_ids, const int32_t* hyp_lens, int h
 }
 
 int nasr_get_loss(nasr_handle h, float* loss_out) {
+  MODEL_CALL(h);
   if (!h || !loss_out) return NASR_ERR_ARG;
   // the step's fault word travels with the gradients through the all-reduce: non-zero = some rank's persistent
   // recurrence gave up, every rank's Adam launch of that step was a no-op (optim.hip) and the step is void everywhere
@@ -541,6 +574,7 @@ int nasr_get_loss(nasr_handle h, float* loss_out) {
 }
 
 int nasr_step_void(nasr_handle h, int* void_out) {
+  MODEL_CALL(h);
   if (!h || !void_out) return NASR_ERR_ARG;
   float fault = 0.f;
   HIPCHK(h, hipMemcpyAsync(&fault, h->Gbase, 4, hipMemcpyDeviceToHost, h->st));
@@ -551,6 +585,7 @@ int nasr_step_void(nasr_handle h, int* void_out) {
 }
 
 int nasr_get_step_results(nasr_handle h, float* loss_out, int* fault_out, int32_t* ids_out, int32_t* lens_out) {
+  MODEL_CALL(h);
   if (!h) return NASR_ERR_ARG;
   nasr_ctx::StepRes& r = h->res[h->res_cur];
   if (!r.valid) return h->fail(NASR_ERR_STATE, "nasr_get_step_results: no step with nasr_set_step_decode(1) has been enqueued");
@@ -573,6 +608,7 @@ int nasr_get_step_results(nasr_handle h, float* loss_out, int* fault_out, int32_
 
 
 int nasr_settle_step(nasr_handle h, int previous, int* void_out) {
+  MODEL_CALL(h);
   if (!h || !void_out) return NASR_ERR_ARG;
   *void_out = 0;
   nasr_ctx::StepEnd& e = h->endw[previous ? (h->end_cur + nasr_ctx::NEND - 1) % nasr_ctx::NEND : h->end_cur];
@@ -580,9 +616,13 @@ int nasr_settle_step(nasr_handle h, int previous, int* void_out) {
   return settle_end(h, e, void_out);
 }
 
-int64_t nasr_step_token(nasr_handle h) { return h ? h->step_token : -1; }
+int64_t nasr_step_token(nasr_handle h) {
+  MODEL_CALL(h);
+  return h ? h->step_token : -1;
+}
 
 int nasr_settle_token(nasr_handle h, int64_t token, int* void_out) {
+  MODEL_CALL(h);
   if (!h || !void_out) return NASR_ERR_ARG;
   *void_out = 0;
   if (token <= 0 || token > h->step_token) return h->fail(NASR_ERR_ARG, "nasr_settle_token: no such step");
@@ -593,12 +633,14 @@ int nasr_settle_token(nasr_handle h, int64_t token, int* void_out) {
 }
 
 int nasr_resident_frames(nasr_handle h, int64_t* frames) {
+  MODEL_CALL(h);
   if (!h || !frames) return NASR_ERR_ARG;
   *frames = h->resident ? h->frames : 0;
   return NASR_OK;
 }
 
 int nasr_set_row_compaction(nasr_handle h, int enabled) {
+  MODEL_CALL(h);
   if (!h) return NASR_ERR_ARG;
   if (h->wn) return h->fail(NASR_ERR_STATE, "nasr_set_row_compaction: a WaveNet handle has no recurrence to compact rows for");
   // what the resident batch's plane buffers hold depends on it: takes effect with the next uploaded / committed batch
@@ -607,6 +649,7 @@ int nasr_set_row_compaction(nasr_handle h, int enabled) {
 }
 
 int nasr_resident_rows(nasr_handle h, int64_t* rows) {
+  MODEL_CALL(h);
   if (!h || !rows) return NASR_ERR_ARG;
   *rows = !h->resident ? 0 : h->cmp_rows ? h->cmp_rows : (int64_t)h->T * h->Bp;
   return NASR_OK;
@@ -614,6 +657,7 @@ int nasr_resident_rows(nasr_handle h, int64_t* rows) {
 
 int nasr_train_step(nasr_handle h, const float* feats, const int32_t* seq_len, const int32_t* labels,
                     const int32_t* label_len, int B, int T, int Lmax, float* loss_out) {
+  MODEL_CALL(h);
   if (!h) return NASR_ERR_ARG;
   if (!labels) return h->fail(NASR_ERR_ARG, "nasr_train_step needs labels");
   int rc = upload(h, feats, seq_len, labels, label_len, B, T, Lmax);
@@ -627,6 +671,7 @@ int nasr_train_step(nasr_handle h, const float* feats, const int32_t* seq_len, c
 }
 
 int nasr_forward(nasr_handle h, const float* feats, const int32_t* seq_len, int B, int T, float* logits_out) {
+  MODEL_CALL(h);
   if (!h) return NASR_ERR_ARG;
   int rc = upload(h, feats, seq_len, nullptr, nullptr, B, T, 0);
   if (rc) return rc;
@@ -638,6 +683,7 @@ int nasr_forward(nasr_handle h, const float* feats, const int32_t* seq_len, int 
 
 int nasr_loss(nasr_handle h, const float* feats, const int32_t* seq_len, const int32_t* labels,
               const int32_t* label_len, int B, int T, int Lmax, float* loss_out, float* nll_out) {
+  MODEL_CALL(h);
   if (!h) return NASR_ERR_ARG;
   if (!labels) return h->fail(NASR_ERR_ARG, "nasr_loss needs labels");
   int rc = upload(h, feats, seq_len, labels, label_len, B, T, Lmax);
@@ -654,6 +700,7 @@ int nasr_loss(nasr_handle h, const float* feats, const int32_t* seq_len, const i
 int nasr_loss_and_grads(nasr_handle h, const float* feats, const int32_t* seq_len, const int32_t* labels,
                         const int32_t* label_len, int B, int T, int Lmax, float* loss_out, float* nll_out,
                         float* flat_grads_out) {
+  MODEL_CALL(h);
   if (!h) return NASR_ERR_ARG;
   if (!labels) return h->fail(NASR_ERR_ARG, "nasr_loss_and_grads needs labels");
   int rc = upload(h, feats, seq_len, labels, label_len, B, T, Lmax);
@@ -671,6 +718,7 @@ int nasr_loss_and_grads(nasr_handle h, const float* feats, const int32_t* seq_le
 
 int nasr_greedy_decode(nasr_handle h, const float* feats, const int32_t* seq_len, int B, int T, int32_t* ids_out,
                        int32_t* lens_out) {
+  MODEL_CALL(h);
   if (!h || !ids_out || !lens_out) return NASR_ERR_ARG;
   int rc = upload(h, feats, seq_len, nullptr, nullptr, B, T, 0);
   if (rc) return rc;
@@ -686,6 +734,7 @@ int nasr_greedy_decode(nasr_handle h, const float* feats, const int32_t* seq_len
 }
 
 int nasr_set_step_decode(nasr_handle h, int enabled) {
+  MODEL_CALL(h);
   if (!h) return NASR_ERR_ARG;
   h->step_decode = enabled != 0;
   h->step_greedy = (enabled & 1) != 0;
@@ -694,6 +743,7 @@ int nasr_set_step_decode(nasr_handle h, int enabled) {
 }
 
 int nasr_get_step_logits(nasr_handle h, float* logits_out) {
+  MODEL_CALL(h);
   if (!h || !logits_out) return NASR_ERR_ARG;
   nasr_ctx::StepRes& r = h->res[h->res_cur];
   if (!r.valid || !r.logits)
@@ -709,6 +759,7 @@ int nasr_get_step_logits(nasr_handle h, float* logits_out) {
 }
 
 int nasr_get_decoded(nasr_handle h, int32_t* ids_out, int32_t* lens_out) {
+  MODEL_CALL(h);
   if (!h || !ids_out || !lens_out) return NASR_ERR_ARG;
   if (!h->have_decoded) return h->fail(NASR_ERR_STATE, "nasr_get_decoded: no decoded step (enable nasr_set_step_decode)");
   HIPCHK(h, hipMemcpyAsync(lens_out, h->lens.p, (size_t)h->B * 4, hipMemcpyDeviceToHost, h->st));
@@ -717,6 +768,7 @@ int nasr_get_decoded(nasr_handle h, int32_t* ids_out, int32_t* lens_out) {
 }
 
 int nasr_set_profiling(nasr_handle h, int enabled) {
+  MODEL_CALL(h);
   if (!h) return NASR_ERR_ARG;
   h->profiling = enabled != 0;
   h->ev_used = 0;
@@ -727,6 +779,7 @@ int nasr_set_profiling(nasr_handle h, int enabled) {
 }
 
 int nasr_get_phase_times(nasr_handle h, nasr_phase_times* out) {
+  MODEL_CALL(h);
   if (!h || !out) return NASR_ERR_ARG;
   HIPCHK(h, hipStreamSynchronize(h->st));
   float acc[PH_COUNT] = {0};
@@ -748,6 +801,7 @@ int nasr_get_phase_times(nasr_handle h, nasr_phase_times* out) {
 }
 
 int nasr_set_graph_mode(nasr_handle h, int enabled) {
+  MODEL_CALL(h);
   if (!h) return NASR_ERR_ARG;
   h->graph_mode = enabled != 0;
   if (!h->graph_mode) drop_graphs(h);
@@ -755,6 +809,7 @@ int nasr_set_graph_mode(nasr_handle h, int enabled) {
 }
 
 int nasr_set_dropout_state(nasr_handle h, uint32_t seed, uint32_t counter) {
+  MODEL_CALL(h);
   if (!h) return NASR_ERR_ARG;
   if (h->wn) return h->fail(NASR_ERR_STATE, "nasr_set_dropout_state: a WaveNet handle has no dropout");
   h->drop_seed = seed;
@@ -763,6 +818,7 @@ int nasr_set_dropout_state(nasr_handle h, uint32_t seed, uint32_t counter) {
 }
 
 int nasr_get_dropout_state(nasr_handle h, uint32_t* seed, uint32_t* counter) {
+  MODEL_CALL(h);
   if (!h) return NASR_ERR_ARG;
   if (h->wn) return h->fail(NASR_ERR_STATE, "nasr_get_dropout_state: a WaveNet handle has no dropout");
   if (seed) *seed = h->drop_seed;
@@ -771,6 +827,7 @@ int nasr_get_dropout_state(nasr_handle h, uint32_t* seed, uint32_t* counter) {
 }
 
 int nasr_set_wgrad_overlap(nasr_handle h, int enabled) {
+  MODEL_CALL(h);
   if (!h) return NASR_ERR_ARG;
   if (h->wn) return h->fail(NASR_ERR_STATE, "nasr_set_wgrad_overlap: a WaveNet handle has no recurrence");
   if (enabled && !h->wst) return h->fail(NASR_ERR_STATE, "the weight-gradient side stream was not set up for this handle "
@@ -781,15 +838,20 @@ int nasr_set_wgrad_overlap(nasr_handle h, int enabled) {
   return NASR_OK;
 }
 
-int nasr_get_wgrad_overlap(nasr_handle h) { return h && h->wg_overlap ? 1 : 0; }
+int nasr_get_wgrad_overlap(nasr_handle h) {
+  MODEL_CALL(h);
+  return h && h->wg_overlap ? 1 : 0;
+}
 
 int nasr_set_bucket_defer(nasr_handle h, int defer) {
+  MODEL_CALL(h);
   if (!h) return NASR_ERR_ARG;
   h->bucket_defer = defer != 0;
   return NASR_OK;
 }
 
 int nasr_get_persist_stats(nasr_handle h, int* aborts, int* rearms) {
+  MODEL_CALL(h);
   if (!h) return NASR_ERR_ARG;
   if (aborts) *aborts = h->persist_aborts;
   if (rearms) *rearms = h->persist_rearms;

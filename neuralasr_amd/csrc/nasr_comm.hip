@@ -71,6 +71,7 @@ int nasr_comm_unique_id(void* id128) {
 }
 
 int nasr_comm_init(nasr_handle h, const void* id128, int rank, int nranks) {
+  MODEL_CALL(h);
   if (!h || !id128) return NASR_ERR_ARG;
   if (nranks < 1 || rank < 0 || rank >= nranks) return h->fail(NASR_ERR_ARG, "nasr_comm_init: bad rank / nranks");
   if (h->comm) return h->fail(NASR_ERR_STATE, "nasr_comm_init: this handle already has a communicator");
@@ -98,9 +99,13 @@ int nasr_comm_init(nasr_handle h, const void* id128, int rank, int nranks) {
   return NASR_OK;
 }
 
-int nasr_comm_size(nasr_handle h) { return h ? (h->comm ? h->comm_n : 1) : NASR_ERR_ARG; }
+int nasr_comm_size(nasr_handle h) {
+  MODEL_CALL(h);
+  return h ? (h->comm ? h->comm_n : 1) : NASR_ERR_ARG;
+}
 
 int nasr_comm_allreduce_grads(nasr_handle h) {
+  MODEL_CALL(h);
   if (!h) return NASR_ERR_ARG;
   if (!h->comm) return h->fail(NASR_ERR_STATE, "nasr_comm_allreduce_grads: call nasr_comm_init first");
   if (!h->have_grads) return h->fail(NASR_ERR_STATE, "nasr_comm_allreduce_grads without gradients");
@@ -120,6 +125,7 @@ int nasr_comm_allreduce_grads(nasr_handle h) {
 }
 
 int nasr_comm_mean(nasr_handle h, float* vals, int n) {
+  MODEL_CALL(h);
   if (!h || !vals) return NASR_ERR_ARG;
   if (n < 1 || n > 64) return h->fail(NASR_ERR_ARG, "nasr_comm_mean: 1..64 values");
   if (!h->comm) return NASR_OK;                   // one rank: the mean is the value

@@ -7,6 +7,7 @@
 //   nasr_api.hip     the C ABI entry points
 //   nasr_comm.hip    RCCL bound with dlopen: nasr_comm_*
 //   nasr_wavenet.hip the WaveNet handle (nasr_create_wavenet): its layout, buffers, BN state and pass
+//   mfcc.hip         the featurizer handle (nasr_create_featurizer): the MFCC front end's tables, buffers and kernels
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -173,6 +174,9 @@ enum class RecKind { Step = 0, Persist = 1, Wide = 2 };
 // What a WaveNet handle holds beyond the common parts (nasr_wavenet.hip); NULL on every other handle.
 struct WnState;
 struct WnStateDelete { void operator()(WnState* w) const; };
+// What a featurizer handle holds (mfcc.hip); NULL on every model handle.
+struct FzState;
+struct FzStateDelete { void operator()(FzState* f) const; };
 
 }  // namespace nasr_impl
 
@@ -184,6 +188,7 @@ struct nasr_ctx {
 
   nasr_model_cfg cfg;
   std::unique_ptr<WnState, WnStateDelete> wn;   // a WaveNet handle (nasr_create_wavenet); the LSTM members stay unused
+  std::unique_ptr<FzState, FzStateDelete> fz;   // a featurizer handle (nasr_create_featurizer): no model at all
   int device = 0;
   Stream st;
   // Bulk GEMMs (input projections, input / weight gradients, dense stages): fp32 products from two fp16 planes per
@@ -386,6 +391,11 @@ namespace nasr_impl {
     hipError_t e_ = (expr);                                                                               \
     if (e_ != hipSuccess)                                                                                 \
       return (h)->fail(NASR_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));                  \
+  } while (0)
+// the first statement of every model call: a featurizer handle answers NASR_ERR_STATE
+#define MODEL_CALL(h)                                                                                     \
+  do {                                                                                                    \
+    if ((h) && (h)->fz) return (h)->fail(NASR_ERR_STATE, std::string(__func__) + ": a featurizer handle has no model"); \
   } while (0)
 // ---- tiled fp16 planes (gemm_tph.hip) ---------------------------------------------------------------------------
 inline size_t pl_rb_bytes(int nkb) { return (size_t)nkb * 2 * 1024; }   // one 32-row block: nkb k-blocks x 2 parts x 1 KiB

@@ -1,0 +1,182 @@
+"""The MFCC front end (reference: utils.py:24-31, convert_to_mfcc): WAV reading and the GPU featurizer.
+
+read_wav returns what librosa.load(path, sr, mono=True) returns for a file already at `sr`: float32 samples scaled the
+way libsndfile scales them, channels averaged in float32.  Resampling is not done: a file at another rate is an error.
+Featurizer runs python_speech_features 0.6's mfcc(nfilt=128), include_context and the whole-utterance normalisation on
+the GPU (neuralasr_amd/csrc/mfcc.hip), a batch of utterances per call."""
+import ctypes
+import struct
+
+import numpy as np
+
+from . import _lib
+
+WAVE_FORMAT_PCM = 0x0001
+WAVE_FORMAT_IEEE_FLOAT = 0x0003
+WAVE_FORMAT_EXTENSIBLE = 0xFFFE
+
+
+def _chunks(data):
+    pos = 12
+    while pos + 8 <= len(data):
+        cid, size = struct.unpack_from('<4sI', data, pos)
+        body = data[pos + 8:pos + 8 + size]
+        yield cid, body
+        pos += 8 + size + (size & 1)
+
+
+def read_wav(path, samplerate):
+    """float32 [n] of a RIFF/WAVE file: PCM 8/16/24/32-bit, IEEE float 32/64-bit, or WAVE_FORMAT_EXTENSIBLE with a PCM
+    or float subformat.  Integers are scaled as libsndfile does (x/32768, x/2^23, x/2^31, (x-128)/128); several
+    channels become their float32 mean.  A file whose rate is not `samplerate` raises ValueError."""
+    with open(path, 'rb') as fh:
+        data = fh.read()
+    if len(data) < 12 or data[:4] != b'RIFF' or data[8:12] != b'WAVE':
+        raise ValueError('%s: not a RIFF/WAVE file' % path)
+    fmt = pcm = None
+    for cid, body in _chunks(data):
+        if cid == b'fmt ' and fmt is None:
+            if len(body) < 16:
+                raise ValueError('%s: short fmt chunk' % path)
+            fmt = body
+        elif cid == b'data' and pcm is None:
+            pcm = body
+    if fmt is None or pcm is None:
+        raise ValueError('%s: no fmt or data chunk' % path)
+    tag, channels, rate, _, block_align, bits = struct.unpack_from('<HHIIHH', fmt, 0)
+    if tag == WAVE_FORMAT_EXTENSIBLE:
+        if len(fmt) < 40:
+            raise ValueError('%s: short WAVE_FORMAT_EXTENSIBLE fmt chunk' % path)
+        tag = struct.unpack_from('<H', fmt, 24)[0]     # the first two bytes of the subformat GUID
+    if rate != samplerate:
+        raise ValueError('%s: sample rate %d Hz, expected %d Hz (resampling is not supported)' % (path, rate, samplerate))
+    if channels < 1:
+        raise ValueError('%s: no channels' % path)
+    width = bits // 8
+    if tag == WAVE_FORMAT_PCM and bits in (8, 16, 24, 32):
+        n = len(pcm) // (width * channels) * channels
+        raw = np.frombuffer(pcm, dtype=np.uint8, count=n * width)
+        if bits == 8:
+            y = (raw.astype(np.float32) - 128.0) / 128.0
+        elif bits == 16:
+            y = raw.view('<i2').astype(np.float32) / np.float32(32768.0)
+        elif bits == 24:
+            b = raw.reshape(-1, 3).astype(np.int32)
+            v = b[:, 0] | (b[:, 1] << 8) | (b[:, 2] << 16)
+            v = np.where(v >= 1 << 23, v - (1 << 24), v)
+            y = v.astype(np.float32) / np.float32(1 << 23)
+        else:
+            y = (raw.view('<i4').astype(np.float64) / 2.0 ** 31).astype(np.float32)
+    elif tag == WAVE_FORMAT_IEEE_FLOAT and bits in (32, 64):
+        n = len(pcm) // (width * channels) * channels
+        y = np.frombuffer(pcm, dtype='<f4' if bits == 32 else '<f8', count=n).astype(np.float32)
+    else:
+        raise ValueError('%s: unsupported WAV encoding (format tag 0x%04x, %d bits); supported are PCM 8/16/24/32-bit '
+                         'and IEEE float 32/64-bit' % (path, tag, bits))
+    y = y.astype(np.float32, copy=False)
+    if channels > 1:
+        y = np.mean(y.reshape(-1, channels).T, axis=0)     # librosa.to_mono on float32 [channels, n]
+    return np.ascontiguousarray(y, dtype=np.float32)
+
+
+def _cfg(samplerate, numcep, numcontext, nfilt, nfft):
+    return _lib.MfccCfg(samplerate=samplerate, numcep=numcep, numcontext=numcontext, nfilt=nfilt, nfft=nfft,
+                        winlen=0.025, winstep=0.01, preemph=0.97, ceplifter=22, append_energy=1)
+
+
+def num_frames(num_samples, samplerate, numcep=13, nfilt=128, nfft=512):
+    """psf's frame count of an utterance (computed by the library, no GPU needed)."""
+    lib = _lib.load()
+    cfg = _cfg(samplerate, numcep, 0, nfilt, nfft)
+    n = lib.nasr_mfcc_frames(ctypes.byref(cfg), int(num_samples))
+    if n < 0:
+        raise ValueError('no frame count for %d samples at %d Hz' % (num_samples, samplerate))
+    return int(n)
+
+
+def filterbank(samplerate, nfilt=128, nfft=512):
+    """(bins int32 [nfilt+2], weights float32 [nfilt, nfft/2+1]): the filterbank the kernels use."""
+    lib = _lib.load()
+    cfg = _cfg(samplerate, 1, 0, nfilt, nfft)
+    bins = np.zeros(nfilt + 2, dtype=np.int32)
+    w = np.zeros((nfilt, nfft // 2 + 1), dtype=np.float32)
+    rc = lib.nasr_mfcc_filterbank(ctypes.byref(cfg), bins.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+                                  w.ctypes.data_as(ctypes.POINTER(ctypes.c_float)))
+    if rc != _lib.NASR_OK:
+        raise ValueError('bad filterbank configuration')
+    return bins, w
+
+
+class Featurizer:
+    """The normalised MFCC features of utils.convert_to_mfcc for a list of float32 utterances, on the GPU.  compute()
+    packs consecutive utterances into calls of at most `max_samples` samples (a longer utterance goes alone)."""
+
+    def __init__(self, samplerate, numcep, numcontext, nfilt=128, nfft=512, device_id=0, max_samples=1 << 23):
+        self.lib = _lib.load()
+        self.samplerate, self.numcep, self.numcontext = int(samplerate), int(numcep), int(numcontext)
+        self.width = (2 * self.numcontext + 1) * self.numcep
+        self.max_samples = int(max_samples)
+        self.cfg = _cfg(self.samplerate, self.numcep, self.numcontext, nfilt, nfft)
+        h = ctypes.c_void_p()
+        rc = self.lib.nasr_create_featurizer(ctypes.byref(self.cfg), device_id, None, ctypes.byref(h))
+        _lib.check(self.lib, None, rc)
+        self.h = h
+
+    def frames(self, num_samples):
+        n = self.lib.nasr_mfcc_frames(ctypes.byref(self.cfg), int(num_samples))
+        if n < 0:
+            raise ValueError('an utterance needs at least one sample')
+        return int(n)
+
+    def compute(self, audios, return_stats=False):
+        """list of float32 [n_i] -> list of float32 [T_i, (2*numcontext+1)*numcep] (and [(mean, std)] if asked)."""
+        audios = [np.ascontiguousarray(a, dtype=np.float32).reshape(-1) for a in audios]
+        for i, a in enumerate(audios):
+            if a.size == 0:
+                raise ValueError('utterance %d has no samples' % i)
+        feats, stats = [], []
+        i = 0
+        while i < len(audios):
+            j, total = i, 0
+            while j < len(audios) and (j == i or total + audios[j].size <= self.max_samples):
+                total += audios[j].size
+                j += 1
+            f, s = self._call(audios[i:j])
+            feats += f
+            stats += s
+            i = j
+        return (feats, stats) if return_stats else feats
+
+    def _call(self, audios):
+        n = len(audios)
+        offsets = np.zeros(n + 1, dtype=np.int64)
+        offsets[1:] = np.cumsum([a.size for a in audios])
+        flat = np.concatenate(audios) if n > 1 else audios[0]
+        frames = [self.frames(a.size) for a in audios]
+        rows = int(sum(frames))
+        out = np.empty((rows, self.width), dtype=np.float32)
+        ms = np.empty((n, 2), dtype=np.float64)
+        rc = self.lib.nasr_featurize(self.h, flat.ctypes.data_as(ctypes.POINTER(ctypes.c_float)),
+                                     offsets.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), n,
+                                     out.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), rows,
+                                     ms.ctypes.data_as(ctypes.POINTER(ctypes.c_double)))
+        _lib.check(self.lib, self.h, rc)
+        cut = np.cumsum([0] + frames)
+        return [out[cut[k]:cut[k + 1]] for k in range(n)], [tuple(ms[k]) for k in range(n)]
+
+    def times(self):
+        """(h2d_ms, kernel_ms, d2h_ms) of the last library call."""
+        t = [ctypes.c_float() for _ in range(3)]
+        _lib.check(self.lib, self.h, self.lib.nasr_featurize_times(self.h, *[ctypes.byref(x) for x in t]))
+        return tuple(x.value for x in t)
+
+    def close(self):
+        if getattr(self, 'h', None):
+            self.lib.nasr_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

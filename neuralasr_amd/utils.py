@@ -1,5 +1,8 @@
-"""Pure-NumPy helpers of the reference's utils.py that sit next to the hot path (the audio front end —
-librosa / python_speech_features — is out of scope)."""
+"""The reference's utils.py: include_context, read_label_text, sparse_tuple_from, and
+compute_mfcc_and_read_transcription on the GPU front end of features.py (librosa and python_speech_features are not
+needed)."""
+import re
+
 import numpy as np
 
 
@@ -30,3 +33,39 @@ def sparse_tuple_from(sequences, output_lengths):
     values = np.asarray(vals, dtype=np.int32)
     shape = np.asarray([len(sequences), indices[:, 1].max() + 1], dtype=np.int64)
     return indices, values, shape
+
+
+def read_label_text(txtfile, punc_regex):
+    """The cleaned transcription of a text file (reference: utils.py:34-41): newlines dropped, stripped, lowercased,
+    punc_regex removed, one pass of '  ' -> ' ', then ' ' -> '_'."""
+    with open(txtfile, 'r') as f:
+        transcription = f.read().replace('\n', '').replace('\r', '')
+    transcription = transcription.strip().lower()
+    clean_transcription = re.sub(punc_regex, '', transcription)
+    return clean_transcription.replace('  ', ' ').replace(' ', '_')
+
+
+_featurizers = {}
+
+
+def featurizer(sr, numcontext, numcep):
+    """One GPU featurizer per (sr, numcontext, numcep) for the process."""
+    key = (int(sr), int(numcontext), int(numcep))
+    if key not in _featurizers:
+        from .features import Featurizer
+        _featurizers[key] = Featurizer(sr, numcep, numcontext)
+    return _featurizers[key]
+
+
+def convert_to_mfcc(wavfile, sr, numcontext, numcep):
+    """float32 [T, (2*numcontext+1)*numcep] normalised MFCC features of a WAV file (reference: utils.py:24-31)."""
+    from .features import read_wav
+    return featurizer(sr, numcontext, numcep).compute([read_wav(wavfile, sr)])[0]
+
+
+def compute_mfcc_and_read_transcription(wavfile, sr, numcontext, numcep, punc_regex=None, txtfile=None):
+    """(reference: utils.py:61-68) the features, and the cleaned transcription when txtfile is given."""
+    audio_mfcc = convert_to_mfcc(wavfile, sr, numcontext, numcep)
+    if txtfile:
+        return audio_mfcc, read_label_text(txtfile, punc_regex)
+    return audio_mfcc

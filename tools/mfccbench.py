@@ -1,0 +1,73 @@
+"""MFCC front-end throughput and error: a batch of synthetic int16 utterances (default 64 x 10 s at 16 kHz, the
+16000sr_26mfcc config: numcep 26, numcontext 10) through nasr_featurize, split into host-to-device copies, kernels and
+device-to-host copies (device events), and through the fp64 NumPy restatement of tests/mfcc_ref.py on the same batch.
+Prints one JSON line.   python tools/mfccbench.py [--utts 64 --seconds 10 --sr 16000 --numcep 26 --numcontext 10]"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), '..')
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, 'tests'))
+import mfcc_ref as R                                # noqa: E402
+from neuralasr_amd.features import Featurizer       # noqa: E402
+
+
+def synth(n, sr, seed):
+    """int16-quantised harmonics of a wandering pitch, syllable-rate envelope, noise."""
+    rng = np.random.default_rng(seed)
+    t = np.arange(n) / sr
+    f0 = 110 + 40 * np.sin(2 * np.pi * 0.7 * t + rng.uniform(0, 6))
+    phase = 2 * np.pi * np.cumsum(f0) / sr
+    x = sum(np.sin(h * phase + rng.uniform(0, 6)) / h ** 1.2 for h in range(1, 30) if h * 160 <= sr / 2)
+    x = x * (0.55 + 0.45 * np.sin(2 * np.pi * 4.0 * t)) / 3 + 0.05 * rng.standard_normal(n)
+    return (np.clip(np.round(x * 0.3 * 32767), -32768, 32767).astype(np.int16).astype(np.float32) / np.float32(32768))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--utts', type=int, default=64)
+    ap.add_argument('--seconds', type=float, default=10.0)
+    ap.add_argument('--sr', type=int, default=16000)
+    ap.add_argument('--numcep', type=int, default=26)
+    ap.add_argument('--numcontext', type=int, default=10)
+    ap.add_argument('--reps', type=int, default=10)
+    ap.add_argument('--ref-utts', type=int, default=8, help='utterances the fp64 restatement is timed and checked on')
+    a = ap.parse_args()
+    n = int(a.seconds * a.sr)
+    audios = [synth(n, a.sr, s) for s in range(a.utts)]
+    fz = Featurizer(a.sr, a.numcep, a.numcontext, max_samples=n * a.utts)
+    feats = fz.compute(audios)                            # warm-up: code objects, buffers
+    t_h2d = t_k = t_d2h = wall = 0.0
+    for _ in range(a.reps):
+        t0 = time.perf_counter()
+        feats = fz.compute(audios)
+        wall += time.perf_counter() - t0
+        h2d, k, d2h = fz.times()
+        t_h2d += h2d; t_k += k; t_d2h += d2h
+    frames = sum(f.shape[0] for f in feats)
+    audio_s = a.utts * a.seconds
+    m = a.reps
+    nref = min(a.ref_utts, a.utts)
+    t0 = time.perf_counter()
+    ref = [R.features(x, a.sr, a.numcontext, a.numcep)[0] for x in audios[:nref]]
+    t_ref = (time.perf_counter() - t0) * a.utts / nref
+    err = np.concatenate([np.abs(f.astype(np.float64) - r).ravel() for f, r in zip(feats, ref)])
+    fz.close()
+    print(json.dumps({
+        'utts': a.utts, 'seconds_each': a.seconds, 'sr': a.sr, 'numcep': a.numcep, 'numcontext': a.numcontext,
+        'frames': frames, 'out_mb': round(frames * feats[0].shape[1] * 4 / 2 ** 20, 1),
+        'h2d_ms': round(t_h2d / m, 3), 'kernel_ms': round(t_k / m, 3), 'd2h_ms': round(t_d2h / m, 3),
+        'call_ms': round(wall / m * 1e3, 3),
+        'audio_s_per_s_call': round(audio_s / (wall / m)), 'audio_s_per_s_kernels': round(audio_s / (t_k / m * 1e-3)),
+        'frames_per_s_call': round(frames / (wall / m)), 'frames_per_s_kernels': round(frames / (t_k / m * 1e-3)),
+        'ref_fp64_s_batch': round(t_ref, 3), 'ref_checked_utts': nref,
+        'max_abs_err': float(err.max()), 'mean_abs_err': float(err.mean())}))
+
+
+if __name__ == '__main__':
+    main()
