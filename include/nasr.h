@@ -354,6 +354,48 @@ int nasr_wavenet_set_bn_hold(nasr_handle h, int hold);
 int nasr_wavenet_get_batch_stats(nasr_handle h, float* mean, float* var, int64_t n);
 int nasr_wavenet_apply_bn_stats(nasr_handle h, const float* mean, const float* var, int64_t n, int count);
 
+/* ---- the LAS network (networks/las.py: Listen, Attend and Spell) ------------------------------
+ * A 4-layer pyramidal BiLSTM encoder (250 units per direction; an odd length gets one zero frame, both directions run over
+ * every padded frame whatever seq_len says, frame pairs are concatenated between layers) and an attention decoder
+ * (BasicLSTMCell(500) in an AttentionWrapper: Bahdanau attention with 500 units over the top layer's output, no memory mask,
+ * attention layer 250, projection to the classes).  Training decodes U = Lmax steps; step t is fed labels[:, t] (the
+ * reference's literal input, not labels[:, t-1]) and, from step 1 on, with probability p a sample from softmax(logits_{t-1})
+ * (ScheduledEmbeddingTrainingHelper).  The loss is sequence_loss: sum of w*CE / (sum w + 1e-12), w = t < label_len[b].
+ * Labels are dense [B][Lmax] ids in [0, num_classes-1]; every entry, padding included, must be a valid id (it is fed).
+ * The common calls work on the handle: parameters (TF variable order, nasr_tensor_info), Adam, batches, nasr_compute_grads,
+ * nasr_loss (nll_out: per-utterance sum of w*CE), nasr_loss_and_grads, nasr_train_step, gradient buffer and buckets, the
+ * fault word, step tokens, nasr_comm_*.  The CTC-only calls (nasr_forward, nasr_greedy_decode, nasr_set_step_decode with
+ * a greedy pass, nasr_logit_frames) return NASR_ERR_STATE.
+ * Variables: per layer l = 0..3: bidirectional_rnn/fw/fw_l/kernel [I+250, 1000] (I = F for l = 0, else 1000), .../bias,
+ * bidirectional_rnn/bw/bw_l/kernel, .../bias; memory_layer/kernel [500,500]; decoder_lstm/kernel [C+250+500, 2000] (rows:
+ * one-hot input, previous attention, h), decoder_lstm/bias; query_layer/kernel [500,500]; attention_v [500];
+ * attention_layer/kernel [1000,250] (rows: h, context); projection_layer/kernel [250,C], projection_layer/bias [C].
+ * Scheduled sampling is defined by a counter-based hash (neuralasr_amd/csrc/las.hip, first comment): every sampling pass
+ * (nasr_compute_grads, nasr_loss, nasr_las_forward with sample = 1) uses the current counter and then increments it. */
+typedef struct {
+  int32_t feature_size;
+  int32_t num_classes;
+  int32_t num_hidden;          /* 250 (the reference's) */
+  int32_t num_layers;          /* 4 */
+  float sampling_probability;  /* 0.1 */
+  uint32_t seed;               /* of the sampling hash */
+  float learning_rate;
+  float beta1, beta2, epsilon;
+} nasr_las_cfg;
+int nasr_create_las(const nasr_las_cfg* cfg, int device_id, void* stream, nasr_handle* out);
+/* sampling probability, hash seed, pass counter and tower index (a checkpoint carries them; towers key their own draws) */
+int nasr_las_set_sampling(nasr_handle h, float p, uint32_t seed, uint32_t counter, int tower);
+int nasr_las_get_sampling(nasr_handle h, float* p, uint32_t* seed, uint32_t* counter, int* tower);
+/* a forward pass of the decoder over labels [B][U] (sample = 0: every step fed its label; 1: scheduled sampling), its
+ * logits [B][U][C] (or NULL); the loss is left for nasr_get_loss */
+int nasr_las_forward(nasr_handle h, const float* feats, const int32_t* seq_len, const int32_t* labels, const int32_t* label_len,
+                     int B, int T, int U, int sample, float* logits_out);
+/* of the last decoder pass: logits [B][U][C], the ids fed to each step [B][U] */
+int nasr_las_get_logits(nasr_handle h, float* logits_out);
+int nasr_las_get_fed_ids(nasr_handle h, int32_t* ids_out);
+/* of the last decoder pass: 1 where the step's input was a scheduled sample, else 0 [B][U] (step 0 is never sampled) */
+int nasr_las_get_sampled(nasr_handle h, int32_t* sampled_out);
+
 /* ---- the MFCC front end (utils.py:24-31: convert_to_mfcc) --------------------------------------
  * python_speech_features 0.6's mfcc(audio, samplerate, numcep=numcep, nfilt=128) on float32 audio: pre-emphasis in
  * float32 (two roundings), frames of round_half_up(winlen*sr) samples every round_half_up(winstep*sr), zero-padded tail,

@@ -34,6 +34,8 @@ SYMBOLS = [
     'nasr_set_wgrad_overlap', 'nasr_get_wgrad_overlap', 'nasr_set_row_compaction', 'nasr_resident_rows',
     'nasr_create_wavenet', 'nasr_wavenet_bn_count', 'nasr_wavenet_get_bn_state', 'nasr_wavenet_set_bn_state',
     'nasr_wavenet_set_bn_hold', 'nasr_wavenet_get_batch_stats', 'nasr_wavenet_apply_bn_stats',
+    'nasr_create_las', 'nasr_las_set_sampling', 'nasr_las_get_sampling', 'nasr_las_forward', 'nasr_las_get_logits',
+    'nasr_las_get_fed_ids', 'nasr_las_get_sampled',
     'nasr_create_featurizer', 'nasr_mfcc_frames', 'nasr_mfcc_filterbank', 'nasr_featurize', 'nasr_featurize_times',
 ]
 
@@ -51,6 +53,12 @@ class WaveNetCfg(Structure):
                 ('num_blocks', c_int32), ('num_rates', c_int32), ('rates', c_int32 * 8), ('bn_epsilon', c_float),
                 ('bn_decay', c_float), ('learning_rate', c_float), ('beta1', c_float), ('beta2', c_float),
                 ('epsilon', c_float)]
+
+
+class LasCfg(Structure):
+    _fields_ = [('feature_size', c_int32), ('num_classes', c_int32), ('num_hidden', c_int32), ('num_layers', c_int32),
+                ('sampling_probability', c_float), ('seed', c_uint32), ('learning_rate', c_float), ('beta1', c_float),
+                ('beta2', c_float), ('epsilon', c_float)]
 
 
 class MfccCfg(Structure):
@@ -166,6 +174,13 @@ def load():
         'nasr_wavenet_set_bn_hold': (c_int, [H, c_int]),
         'nasr_wavenet_get_batch_stats': (c_int, [H, fp, fp, c_int64]),
         'nasr_wavenet_apply_bn_stats': (c_int, [H, fp, fp, c_int64, c_int]),
+        'nasr_create_las': (c_int, [POINTER(LasCfg), c_int, c_void_p, POINTER(H)]),
+        'nasr_las_set_sampling': (c_int, [H, c_float, c_uint32, c_uint32, c_int]),
+        'nasr_las_get_sampling': (c_int, [H, POINTER(c_float), POINTER(c_uint32), POINTER(c_uint32), POINTER(c_int)]),
+        'nasr_las_forward': (c_int, [H, fp, ip, ip, ip, c_int, c_int, c_int, c_int, fp]),
+        'nasr_las_get_logits': (c_int, [H, fp]),
+        'nasr_las_get_fed_ids': (c_int, [H, ip]),
+        'nasr_las_get_sampled': (c_int, [H, ip]),
         'nasr_create_featurizer': (c_int, [POINTER(MfccCfg), c_int, c_void_p, POINTER(H)]),
         'nasr_mfcc_frames': (c_int64, [POINTER(MfccCfg), c_int64]),
         'nasr_mfcc_filterbank': (c_int, [POINTER(MfccCfg), ip, fp]),

@@ -357,6 +357,7 @@ int nasr_set_learning_rate(nasr_handle h, float lr) {
 int nasr_logit_frames(nasr_handle h, int T) {
   MODEL_CALL(h);
   if (!h) return NASR_ERR_ARG;
+  if (h->las) return h->fail(NASR_ERR_STATE, "nasr_logit_frames: a LAS handle has no CTC logit frames");
   return (h->cfg.bidirectional && h->cfg.merge == NASR_MERGE_STACK_RESHAPE) ? 2 * T : T;
 }
 
@@ -422,6 +423,10 @@ int nasr_compute_grads(nasr_handle h) {
     (void)hipEventRecord(h->ev_total_a, h->st);
     h->window_open = true;
     h->total_valid = false;
+  }
+  if (h->las) {          // a gradient pass: scheduled sampling on; the sequence loss is part of the forward pass
+    int rc = las_forward(h, true);
+    return rc ? rc : backward(h);
   }
   if (h->wn) {           // a gradient pass: training-mode batch norm
     int rc = wn_forward(h, true);
@@ -642,7 +647,7 @@ int nasr_resident_frames(nasr_handle h, int64_t* frames) {
 int nasr_set_row_compaction(nasr_handle h, int enabled) {
   MODEL_CALL(h);
   if (!h) return NASR_ERR_ARG;
-  if (h->wn) return h->fail(NASR_ERR_STATE, "nasr_set_row_compaction: a WaveNet handle has no recurrence to compact rows for");
+  if (h->wn || h->las) return h->fail(NASR_ERR_STATE, "nasr_set_row_compaction: a WaveNet or LAS handle has no recurrence to compact rows for");
   // what the resident batch's plane buffers hold depends on it: takes effect with the next uploaded / committed batch
   h->compactable = enabled && h->ndense == 0;
   return NASR_OK;
@@ -688,9 +693,9 @@ int nasr_loss(nasr_handle h, const float* feats, const int32_t* seq_len, const i
   if (!labels) return h->fail(NASR_ERR_ARG, "nasr_loss needs labels");
   int rc = upload(h, feats, seq_len, labels, label_len, B, T, Lmax);
   if (rc) return rc;
-  rc = forward(h);
+  rc = h->las ? las_forward(h, true) : forward(h);
   if (rc) return rc;
-  rc = ctc_forward(h);
+  if (!h->las) rc = ctc_forward(h);
   if (rc) return rc;
   if (nll_out) HIPCHK(h, hipMemcpyAsync(nll_out, h->nll.p, (size_t)B * 4, hipMemcpyDeviceToHost, h->st));
   if (loss_out) return nasr_get_loss(h, loss_out);
@@ -720,6 +725,7 @@ int nasr_greedy_decode(nasr_handle h, const float* feats, const int32_t* seq_len
                        int32_t* lens_out) {
   MODEL_CALL(h);
   if (!h || !ids_out || !lens_out) return NASR_ERR_ARG;
+  if (h->las) return h->fail(NASR_ERR_STATE, "nasr_greedy_decode: a LAS handle has no CTC decoder");
   int rc = upload(h, feats, seq_len, nullptr, nullptr, B, T, 0);
   if (rc) return rc;
   rc = forward(h);
@@ -736,6 +742,7 @@ int nasr_greedy_decode(nasr_handle h, const float* feats, const int32_t* seq_len
 int nasr_set_step_decode(nasr_handle h, int enabled) {
   MODEL_CALL(h);
   if (!h) return NASR_ERR_ARG;
+  if (h->las && (enabled & 1)) return h->fail(NASR_ERR_STATE, "nasr_set_step_decode: a LAS handle has no greedy CTC pass");
   h->step_decode = enabled != 0;
   h->step_greedy = (enabled & 1) != 0;
   h->step_logits = (enabled & 2) != 0;
@@ -811,7 +818,7 @@ int nasr_set_graph_mode(nasr_handle h, int enabled) {
 int nasr_set_dropout_state(nasr_handle h, uint32_t seed, uint32_t counter) {
   MODEL_CALL(h);
   if (!h) return NASR_ERR_ARG;
-  if (h->wn) return h->fail(NASR_ERR_STATE, "nasr_set_dropout_state: a WaveNet handle has no dropout");
+  if (h->wn || h->las) return h->fail(NASR_ERR_STATE, "nasr_set_dropout_state: a WaveNet or LAS handle has no dropout");
   h->drop_seed = seed;
   h->drop_counter = counter;
   return NASR_OK;
@@ -820,7 +827,7 @@ int nasr_set_dropout_state(nasr_handle h, uint32_t seed, uint32_t counter) {
 int nasr_get_dropout_state(nasr_handle h, uint32_t* seed, uint32_t* counter) {
   MODEL_CALL(h);
   if (!h) return NASR_ERR_ARG;
-  if (h->wn) return h->fail(NASR_ERR_STATE, "nasr_get_dropout_state: a WaveNet handle has no dropout");
+  if (h->wn || h->las) return h->fail(NASR_ERR_STATE, "nasr_get_dropout_state: a WaveNet or LAS handle has no dropout");
   if (seed) *seed = h->drop_seed;
   if (counter) *counter = h->drop_counter;
   return NASR_OK;
@@ -829,7 +836,7 @@ int nasr_get_dropout_state(nasr_handle h, uint32_t* seed, uint32_t* counter) {
 int nasr_set_wgrad_overlap(nasr_handle h, int enabled) {
   MODEL_CALL(h);
   if (!h) return NASR_ERR_ARG;
-  if (h->wn) return h->fail(NASR_ERR_STATE, "nasr_set_wgrad_overlap: a WaveNet handle has no recurrence");
+  if (h->wn || h->las) return h->fail(NASR_ERR_STATE, "nasr_set_wgrad_overlap: a WaveNet or LAS handle has no recurrence");
   if (enabled && !h->wst) return h->fail(NASR_ERR_STATE, "the weight-gradient side stream was not set up for this handle "
                                                          "(needs the persistent recurrence at Hp = 512 and more than one layer)");
   HIPCHK(h, hipStreamSynchronize(h->st));

@@ -10,6 +10,7 @@ namespace nasr_impl {
 
 int ensure_shape(nasr_ctx* h, int B, int T, int Lmax) {
   if (h->wn) return wn_ensure_shape(h, B, T, Lmax);
+  if (h->las) return las_ensure_shape(h, B, T, Lmax);
   const int Bp = rup(B, 16);
   const int Tp = nasr_logit_frames(h, T);
   const size_t R = (size_t)T * Bp;
@@ -104,6 +105,15 @@ int validate_batch(nasr_ctx* h, const int32_t* seq_len, const int32_t* labels, c
     if (seq_len[b] < 1 || seq_len[b] > T)
       return h->fail(NASR_ERR_ARG, "seq_len[" + std::to_string(b) + "] out of [1,T]");
     if (!labels) continue;
+    if (h->las) {   // dense labels: every entry is fed to the decoder, any class is a label, no CTC feasibility
+      if (label_len[b] < 0 || label_len[b] > Lmax)
+        return h->fail(NASR_ERR_ARG, "label_len[" + std::to_string(b) + "] out of [0,Lmax]");
+      for (int i = 0; i < Lmax; ++i) {
+        const int v = labels[(size_t)b * Lmax + i];
+        if (v < 0 || v >= h->C) return h->fail(NASR_ERR_ARG, "label id out of [0, num_classes-1]");
+      }
+      continue;
+    }
     const int L = label_len[b];
     if (L < 0 || L > Lmax) return h->fail(NASR_ERR_ARG, "label_len[" + std::to_string(b) + "] out of [0,Lmax]");
     int rep = 0;
@@ -169,7 +179,7 @@ int slot_fill(nasr_ctx* h, BatchSlot* s, const float* feats, const int32_t* seq_
   int rc = validate_batch(h, seq_len, labels, label_len, B, T, Lmax);
   if (rc) return rc;
   HIPCHK(h, hipSetDevice(h->device));
-  const int Bp = rup(B, 16), Tp = nasr_logit_frames(h, T), C = h->C, Lm = std::max(labels ? Lmax : 0, 1);
+  const int Bp = rup(B, 16), Tp = h->las ? T : nasr_logit_frames(h, T), C = h->C, Lm = std::max(labels ? Lmax : 0, 1);
   const bool sr = h->cfg.merge == NASR_MERGE_STACK_RESHAPE && h->D == 2;
   // meta layout (int32): seq [Bp] | lablen [Bp] | labels [B*Lm] | cstart [B*(C+1)] | cpos [B*Lm] | rowmap [Tp*Bp]
   s->o_seq = 0;
@@ -316,12 +326,12 @@ int slot_commit(nasr_ctx* h, BatchSlot* s) {
                             h->X0.as<float>(), B, Bp, T, s->ctx, s->ncep, h->Fp, h->st);
     else
       launch_pack_feats(s->dfeats.as<float>(), h->X0.as<float>(), B, Bp, T, h->F, h->Fp, h->st);
-    if (!h->wn)         // (the WaveNet's GEMMs read the fp32 features as they are)
+    if (!h->wn && !h->las)   // (the WaveNet's and LAS's GEMMs read the fp32 features as they are)
       pl_scales(h, h->X0.as<float>(), T * Bp, h->Fp, h->Fp, &h->sc_x0r, &h->sc_x0c, h->st);
     if (h->cmp_rows)    // the feature rows' scales in the compacted order (layer 0's input GEMM)
       launch_gather_rows(h->sc_cx.sp(), h->sc_x0r.sp(), h->vrow_p, h->cmp_rows_p, 1.f, h->st),
       launch_gather_rows(h->sc_cx.ip(), h->sc_x0r.ip(), h->vrow_p, h->cmp_rows_p, 1.f, h->st);
-    if (s->has_labels && h->npre == 0 && !h->wn)   // layer-0 input with the frame index as contraction index, for dWx = X^T dG
+    if (s->has_labels && h->npre == 0 && !h->wn && !h->las)   // layer-0 input with the frame index as contraction index, for dWx = X^T dG
       launch_tph_split2(h->X0.as<float>(), nullptr, h->X0TTP.as<unsigned char>(), h->cmp_rows ? h->cmp_rows : T * Bp, h->Fp, h->Fp,
                         nullptr, 1.f, h->sc_x0c.sp(), 1.f, nullptr, h->st, h->cmp_rows ? h->vrow_p : nullptr);
     HIPCHK(h, hipGetLastError());

@@ -7,6 +7,7 @@
 //   nasr_api.hip     the C ABI entry points
 //   nasr_comm.hip    RCCL bound with dlopen: nasr_comm_*
 //   nasr_wavenet.hip the WaveNet handle (nasr_create_wavenet): its layout, buffers, BN state and pass
+//   nasr_las.hip     the LAS handle (nasr_create_las): its layout, buffers, sampling state and pass
 //   mfcc.hip         the featurizer handle (nasr_create_featurizer): the MFCC front end's tables, buffers and kernels
 #pragma once
 #include <hip/hip_runtime.h>
@@ -177,6 +178,9 @@ struct WnStateDelete { void operator()(WnState* w) const; };
 // What a featurizer handle holds (mfcc.hip); NULL on every model handle.
 struct FzState;
 struct FzStateDelete { void operator()(FzState* f) const; };
+// What a LAS handle holds beyond the common parts (nasr_las.hip); NULL on every other handle.
+struct LasState;
+struct LasStateDelete { void operator()(LasState* s) const; };
 
 }  // namespace nasr_impl
 
@@ -189,6 +193,7 @@ struct nasr_ctx {
   nasr_model_cfg cfg;
   std::unique_ptr<WnState, WnStateDelete> wn;   // a WaveNet handle (nasr_create_wavenet); the LSTM members stay unused
   std::unique_ptr<FzState, FzStateDelete> fz;   // a featurizer handle (nasr_create_featurizer): no model at all
+  std::unique_ptr<LasState, LasStateDelete> las;   // a LAS handle (nasr_create_las); the LSTM members stay unused
   int device = 0;
   Stream st;
   // Bulk GEMMs (input projections, input / weight gradients, dense stages): fp32 products from two fp16 planes per
@@ -501,5 +506,12 @@ int fetch_logits(nasr_ctx* h, float* logits_out);
 int wn_ensure_shape(nasr_ctx* h, int B, int T, int Lmax);
 int wn_forward(nasr_ctx* h, bool training);
 int wn_backward(nasr_ctx* h);
+// the common tail of nasr_create_wavenet / nasr_create_las (streams, events, stamps; one gradient bucket)
+int single_bucket_handle_setup(nasr_ctx* h, std::string* err);
+
+// ---- nasr_las.hip (the LAS handle's side of ensure_shape, forward and backward; its loss is part of its forward pass)
+int las_ensure_shape(nasr_ctx* h, int B, int T, int Lmax);
+int las_forward(nasr_ctx* h, bool sample);
+int las_backward(nasr_ctx* h);
 
 }  // namespace nasr_impl

@@ -1,0 +1,532 @@
+// nasr_las.hip — the LAS network of the reference (networks/las.py: Listen, Attend and Spell): a 4-layer pyramidal BiLSTM
+// encoder (250 units per direction, odd lengths padded by one zero frame, frame pairs concatenated between layers, both
+// directions over every padded frame) and an attention decoder (BasicLSTMCell(500) in an AttentionWrapper with
+// unnormalised Bahdanau attention over the top layer's output, attention layer 250, projection to the classes), trained
+// with scheduled sampling and sequence_loss.  This file holds the handle's create call, parameter layout, buffers and the
+// forward / backward pass; the kernels are in las.hip and gemm.hip.  Batches, Adam, gradient exchange and checkpoints are
+// the common code.  DESIGN.md §10.
+#include "nasr_ctx.h"
+#include "las.h"
+
+#include <functional>
+
+using namespace nasr;
+using namespace nasr_impl;
+
+namespace nasr_impl {
+
+struct LasState {
+  nasr_las_cfg cfg;
+  static constexpr int NL = 4;
+  // internal parameter layout (floats from P): per layer Wx [Ip][2*G4E] (fw | bw gate columns), Wh fw / bw [LAS_HE][G4E],
+  // bias [2*G4E]; memory_layer [512][512]; the decoder kernel's one-hot rows E [C][G4D], its [a; h] rows Wah [768][G4D],
+  // its bias; query_layer [512][512]; attention_v [512]; attention_layer [1024][256]; projection [256][Cp], bias [Cp]
+  int Ip[NL];
+  int64_t off_wx[NL], off_whf[NL], off_whb[NL], off_b[NL];
+  int64_t off_wmem = 0, off_e = 0, off_wah = 0, off_bd = 0, off_wq = 0, off_v = 0, off_watt = 0, off_wp = 0, off_bp = 0;
+  // scheduled sampling: probability, hash seed, pass counter, tower (las.hip)
+  float p = 0.1f;
+  uint32_t seed = 1u, counter = 0u;
+  int tower = 0;
+  // shape of the resident batch
+  int Lr[NL] = {0, 0, 0, 0};   // frames each layer runs over
+  int U = 0;
+  bool have_pass = false;
+  // encoder activations per layer, rows Lr[l] * Bp
+  DevBuf X[NL], xp[NL], act[NL], c[NL], out[NL];
+  DevBuf dGe, dX, dout, dhc, dcc, whT;   // whT: [2][G4E][LAS_HE] the layer's recurrent matrices transposed (BPTT)
+  // attention and decoder
+  DevBuf keys, dkeys, dmem, tmpm;
+  DevBuf S, cinit, dc, dact, gp, Q, alpha, HC, logits, ids, sampled;
+  DevBuf dL, wce, w, tmpA, dA, dHC, dQ, dhq, dGd, dS, dcd, dvpart, csws;
+};
+
+namespace {
+inline float* fp(const DevBuf& b, size_t off = 0) { return b.as<float>() + off; }
+
+int las_gemm(nasr_ctx* h, const float* A, const float* B, float* C, int M, int N, int K, int lda, int ldb, int ldc, bool a_col,
+             bool b_col, const float* bias = nullptr, int a_shift = 0, int a_rows = -1) {
+  GemmDesc g{};
+  g.A = A; g.B = B; g.C = C;
+  g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldc = ldc;
+  g.a_col = a_col; g.b_col = b_col;
+  g.a_shift = a_shift;
+  g.a_rows = a_rows >= 0 ? a_rows : (a_col ? K : M);
+  g.bias = bias;
+  g.split_k = bias ? 1 : gemm_pick_split(M, N, K);
+  if (g.split_k > 1) {
+    bool grew = false;
+    if (!h->slabs.ensure((size_t)g.split_k * M * N * 4, &grew)) return h->fail(NASR_ERR_HIP, "slab workspace allocation failed");
+    g.slabs = h->slabs.as<float>();
+  }
+  launch_gemm(g, h->st);
+  return NASR_OK;
+}
+}  // namespace
+
+int las_layout(nasr_ctx* h) {
+  LasState& s = *h->las;
+  const int C = s.cfg.num_classes;
+  h->F = s.cfg.feature_size;
+  h->C = C;
+  h->Fp = rup(h->F, 32);
+  h->Cp = rup(C, 32);
+  h->H = h->Hp = h->N4 = h->D = h->L = 0;
+  h->Pin = h->Pinp = 0;
+  int64_t off = 0;
+  for (int l = 0; l < LasState::NL; ++l) {
+    s.Ip[l] = l == 0 ? h->Fp : 4 * LAS_HE;
+    s.off_wx[l] = off; off += (int64_t)s.Ip[l] * 2 * LAS_G4E;
+    s.off_whf[l] = off; off += (int64_t)LAS_HE * LAS_G4E;
+    s.off_whb[l] = off; off += (int64_t)LAS_HE * LAS_G4E;
+    s.off_b[l] = off; off += 2 * LAS_G4E;
+  }
+  s.off_wmem = off; off += (int64_t)LAS_HD * LAS_HD;
+  s.off_e = off; off += (int64_t)C * LAS_G4D;
+  s.off_wah = off; off += (int64_t)LAS_SW * LAS_G4D;
+  s.off_bd = off; off += LAS_G4D;
+  s.off_wq = off; off += (int64_t)LAS_HD * LAS_HD;
+  s.off_v = off; off += LAS_HD;
+  s.off_watt = off; off += (int64_t)2 * LAS_HD * LAS_HE;
+  s.off_wp = off; off += (int64_t)LAS_HE * h->Cp;
+  s.off_bp = off; off += h->Cp;
+  h->np_int = off;
+
+  h->tensors.clear();
+  h->tf2int.clear();
+  int64_t tf = 0;
+  // rows x cols in TF order; where(r, c) = the internal index of element (r, c)
+  auto add = [&](const std::string& name, int64_t rows, int64_t cols, const std::function<int64_t(int64_t, int64_t)>& where) {
+    h->tensors.push_back({name, tf, rows, cols});
+    for (int64_t r = 0; r < rows; ++r)
+      for (int64_t c = 0; c < cols; ++c) h->tf2int.push_back((int32_t)where(r, c));
+    tf += rows * cols;
+  };
+  for (int l = 0; l < LasState::NL; ++l) {
+    const int I = l == 0 ? h->F : 4 * LAS_H;
+    auto in_row = [l](int64_t r) -> int64_t {   // TF input row -> internal row of Wx (layers >= 1: the pair layout)
+      if (l == 0) return r;
+      const int64_t p = r / (2 * LAS_H), q = r % (2 * LAS_H);
+      return p * 2 * LAS_HE + las_memcol((int)q);
+    };
+    for (int d = 0; d < 2; ++d) {
+      const std::string dn = d == 0 ? "fw" : "bw";
+      const std::string scope = "bidirectional_rnn/" + dn + "/" + dn + "_" + std::to_string(l);
+      const int64_t whoff = d == 0 ? s.off_whf[l] : s.off_whb[l];
+      add(scope + "/kernel", I + LAS_H, LAS_G4E, [&](int64_t r, int64_t c) {
+        return r < I ? s.off_wx[l] + in_row(r) * 2 * LAS_G4E + d * LAS_G4E + c : whoff + (r - I) * LAS_G4E + c;
+      });
+      add(scope + "/bias", LAS_G4E, 1, [&](int64_t r, int64_t) { return s.off_b[l] + d * LAS_G4E + r; });
+    }
+  }
+  add("memory_layer/kernel", 2 * LAS_H, 2 * LAS_H,
+      [&](int64_t r, int64_t c) { return s.off_wmem + (int64_t)las_memcol((int)r) * LAS_HD + c; });
+  add("decoder_lstm/kernel", C + LAS_H + 2 * LAS_H, LAS_G4D, [&](int64_t r, int64_t c) {
+    if (r < C) return s.off_e + r * LAS_G4D + c;
+    if (r < C + LAS_H) return s.off_wah + (r - C) * LAS_G4D + c;
+    return s.off_wah + (LAS_HE + r - C - LAS_H) * LAS_G4D + c;
+  });
+  add("decoder_lstm/bias", LAS_G4D, 1, [&](int64_t r, int64_t) { return s.off_bd + r; });
+  add("query_layer/kernel", 2 * LAS_H, 2 * LAS_H, [&](int64_t r, int64_t c) { return s.off_wq + r * LAS_HD + c; });
+  add("attention_v", 2 * LAS_H, 1, [&](int64_t r, int64_t) { return s.off_v + r; });
+  add("attention_layer/kernel", 4 * LAS_H, LAS_H, [&](int64_t r, int64_t c) {
+    const int64_t row = r < 2 * LAS_H ? r : LAS_HD + las_memcol((int)(r - 2 * LAS_H));
+    return s.off_watt + row * LAS_HE + c;
+  });
+  add("projection_layer/kernel", LAS_H, C, [&](int64_t r, int64_t c) { return s.off_wp + r * h->Cp + c; });
+  add("projection_layer/bias", C, 1, [&](int64_t r, int64_t) { return s.off_bp + r; });
+  h->np_tf = tf;
+  return NASR_OK;
+}
+
+// L1 = T + T%2, L(i+1) = L(i)/2 + (L(i)/2)%2
+void las_lengths(int T, int* Lr) {
+  int L = T + T % 2;
+  for (int l = 0; l < LasState::NL; ++l) {
+    Lr[l] = L;
+    L = L / 2 + (L / 2) % 2;
+  }
+}
+
+int las_ensure_shape(nasr_ctx* h, int B, int T, int Lmax) {
+  LasState& s = *h->las;
+  const int Bp = rup(B, 16);
+  int Lr[LasState::NL];
+  las_lengths(T, Lr);
+  const int U = std::max(Lmax, 1), L4 = Lr[LasState::NL - 1];
+  const size_t R0 = (size_t)Lr[0] * Bp, UB = (size_t)U * Bp, MB = (size_t)L4 * Bp;
+  bool grew = false, ok = true;
+  ok &= h->X0.ensure((size_t)T * Bp * h->Fp * 4, &grew);
+  ok &= h->seqbuf.ensure((size_t)Bp * 4, &grew);
+  ok &= h->loss.ensure(16, &grew);
+  ok &= h->nll.ensure((size_t)Bp * 4, &grew);
+  for (int l = 0; l < LasState::NL; ++l) {
+    const size_t R = (size_t)Lr[l] * Bp;
+    if (l > 0) ok &= s.X[l].ensure(R * 4 * LAS_HE * 4, &grew);
+    ok &= s.xp[l].ensure(R * 2 * LAS_G4E * 4, &grew);
+    ok &= s.act[l].ensure(R * 2 * LAS_G4E * 4, &grew);
+    ok &= s.c[l].ensure(R * 2 * LAS_H * 4, &grew);
+    ok &= s.out[l].ensure(R * 2 * LAS_HE * 4, &grew);
+  }
+  ok &= s.dGe.ensure(R0 * 2 * LAS_G4E * 4, &grew);
+  ok &= s.dX.ensure(R0 * 4 * LAS_HE * 4, &grew);
+  ok &= s.dout.ensure(R0 * 2 * LAS_HE * 4, &grew);
+  ok &= s.whT.ensure((size_t)2 * LAS_G4E * LAS_HE * 4, &grew);
+  ok &= s.dhc.ensure((size_t)2 * Bp * LAS_HE * 4, &grew) && s.dcc.ensure((size_t)2 * Bp * LAS_HE * 4, &grew);
+  for (DevBuf* m : {&s.keys, &s.dkeys, &s.dmem, &s.tmpm}) ok &= m->ensure(MB * LAS_HD * 4, &grew);
+  ok &= s.S.ensure((UB + Bp) * LAS_SW * 4, &grew);
+  ok &= s.cinit.ensure((size_t)Bp * LAS_HD * 4, &grew);
+  ok &= s.dc.ensure(UB * LAS_HD * 4, &grew);
+  ok &= s.dact.ensure(UB * LAS_G4D * 4, &grew);
+  ok &= s.gp.ensure((size_t)Bp * LAS_G4D * 4, &grew);
+  ok &= s.Q.ensure(UB * LAS_HD * 4, &grew);
+  ok &= s.alpha.ensure(UB * L4 * 4, &grew);
+  ok &= s.HC.ensure(UB * 2 * LAS_HD * 4, &grew);
+  ok &= s.logits.ensure(UB * h->Cp * 4, &grew);
+  ok &= s.ids.ensure(UB * 4, &grew) && s.sampled.ensure(UB * 4, &grew);
+  ok &= s.dL.ensure(UB * h->Cp * 4, &grew);
+  ok &= s.wce.ensure(UB * 4, &grew) && s.w.ensure(UB * 4, &grew);
+  ok &= s.tmpA.ensure((size_t)Bp * LAS_HE * 4, &grew);
+  ok &= s.dA.ensure(UB * LAS_HE * 4, &grew);
+  ok &= s.dHC.ensure((size_t)Bp * 2 * LAS_HD * 4, &grew);
+  ok &= s.dQ.ensure(UB * LAS_HD * 4, &grew);
+  ok &= s.dhq.ensure((size_t)Bp * LAS_HD * 4, &grew);
+  ok &= s.dGd.ensure(UB * LAS_G4D * 4, &grew);
+  ok &= s.dS.ensure((size_t)Bp * LAS_SW * 4, &grew);
+  ok &= s.dcd.ensure((size_t)Bp * LAS_HD * 4, &grew);
+  ok &= s.dvpart.ensure(UB * LAS_HD * 4, &grew);
+  ok &= s.csws.ensure((size_t)32 * 2 * LAS_G4E * 4, &grew);
+  if (!ok) return h->fail(NASR_ERR_HIP, "hipMalloc failed while sizing batch buffers");
+  h->B = B; h->Bp = Bp; h->T = T; h->Lmax = Lmax; h->Tp = U; h->KS = 1;
+  for (int l = 0; l < LasState::NL; ++l) s.Lr[l] = Lr[l];
+  s.U = U;
+  return NASR_OK;
+}
+
+// The encoder and the decoder chain of the resident batch.  sample: scheduled sampling with the handle's probability (one
+// counter value per such pass); otherwise every step is fed its label.
+int las_forward(nasr_ctx* h, bool sample) {
+  if (!h->resident) return h->fail(NASR_ERR_STATE, "no resident batch: call nasr_upload_batch first");
+  if (h->Lmax < 1) return h->fail(NASR_ERR_ARG, "the LAS decoder needs labels (U = labels.shape[1] >= 1)");
+  LasState& s = *h->las;
+  const int B = h->B, Bp = h->Bp, U = s.U, C = h->C, Cp = h->Cp;
+  const float* P = h->P;
+  hipStream_t st = h->st;
+  HIPCHK(h, hipMemsetAsync(h->Gbase, 0, GRAD_HEAD * 4, st));   // the step's fault word (nothing here raises it)
+  {
+    PhaseScope ps(h, PH_RECF);
+    for (int l = 0; l < LasState::NL; ++l) {
+      const int L = s.Lr[l];
+      const float* Xin = l == 0 ? h->X0.as<float>() : fp(s.X[l]);
+      // rows past the input's frames (the odd-length padding) read as zero
+      const int in_rows = (l == 0 ? h->T : s.Lr[l - 1] / 2) * Bp;
+      if (l > 0) launch_las_pyr_pack(fp(s.out[l - 1]), fp(s.X[l]), s.Lr[l - 1] / 2, Bp, st);
+      if (int rc = las_gemm(h, Xin, P + s.off_wx[l], fp(s.xp[l]), L * Bp, 2 * LAS_G4E, s.Ip[l], s.Ip[l], 2 * LAS_G4E,
+                            2 * LAS_G4E, false, false, P + s.off_b[l], 0, in_rows))
+        return rc;
+      for (int t = 0; t < L; ++t)
+        launch_las_enc_fwd_step(fp(s.xp[l]), P + s.off_whf[l], P + s.off_whb[l], fp(s.act[l]), fp(s.c[l]), fp(s.out[l]), t, L,
+                                B, Bp, st);
+    }
+  }
+  PhaseScope ps(h, PH_PROJCTC);
+  const int L4 = s.Lr[LasState::NL - 1];
+  const float* mem = fp(s.out[LasState::NL - 1]);
+  if (int rc = las_gemm(h, mem, P + s.off_wmem, fp(s.keys), L4 * Bp, LAS_HD, LAS_HD, LAS_HD, LAS_HD, LAS_HD, false, false))
+    return rc;
+  launch_las_dec_init(mem, fp(s.c[LasState::NL - 1]), h->labels_p, h->Lmax, L4, B, Bp, fp(s.S), fp(s.cinit), s.ids.as<int32_t>(),
+                      st);
+  LasSample smp{};
+  if (sample && s.p > 0.f) {
+    smp.on = 1;
+    smp.p = s.p;
+    smp.thr = s.p >= 1.f ? (1u << 24) : (uint32_t)std::floor((double)s.p * 16777216.0);
+    smp.key = s.seed + 0x9E3779B9u * (uint32_t)(s.tower + 1) + 0x85EBCA6Bu * s.counter;
+  }
+  if (sample) s.counter += 1;
+  HIPCHK(h, hipMemsetAsync(s.sampled.p, 0, (size_t)Bp * 4, st));
+  for (int t = 0; t < U; ++t) {
+    float* St = fp(s.S, (size_t)t * Bp * LAS_SW);
+    float* Sn = St + (size_t)Bp * LAS_SW;
+    float* HCt = fp(s.HC, (size_t)t * Bp * 2 * LAS_HD);
+    float* Qt = fp(s.Q, (size_t)t * Bp * LAS_HD);
+    float* lg = fp(s.logits, (size_t)t * Bp * Cp);
+    if (int rc = las_gemm(h, St, P + s.off_wah, fp(s.gp), Bp, LAS_G4D, LAS_SW, LAS_SW, LAS_G4D, LAS_G4D, false, false)) return rc;
+    launch_las_dec_cell(fp(s.gp), P + s.off_e, P + s.off_bd, s.ids.as<int32_t>() + (size_t)t * Bp,
+                        t == 0 ? fp(s.cinit) : fp(s.dc, (size_t)(t - 1) * Bp * LAS_HD), fp(s.dact, (size_t)t * Bp * LAS_G4D),
+                        fp(s.dc, (size_t)t * Bp * LAS_HD), Sn, HCt, Bp, st);
+    if (int rc = las_gemm(h, Sn + LAS_HE, P + s.off_wq, Qt, Bp, LAS_HD, LAS_HD, LAS_SW, LAS_HD, LAS_HD, false, false)) return rc;
+    launch_las_attend(fp(s.keys), mem, Qt, P + s.off_v, fp(s.alpha, (size_t)t * Bp * L4), HCt, L4, Bp, st);
+    if (int rc = las_gemm(h, HCt, P + s.off_watt, Sn, Bp, LAS_HE, 2 * LAS_HD, 2 * LAS_HD, LAS_HE, LAS_SW, false, false)) return rc;
+    if (int rc = las_gemm(h, Sn, P + s.off_wp, lg, Bp, Cp, LAS_HE, LAS_SW, Cp, Cp, false, false, P + s.off_bp)) return rc;
+    if (t + 1 < U)
+      launch_las_sample(lg, Cp, C, h->labels_p, h->Lmax, t, B, Bp, smp, s.ids.as<int32_t>() + (size_t)(t + 1) * Bp,
+                        s.sampled.as<int32_t>() + (size_t)(t + 1) * Bp, st);
+  }
+  launch_las_ce(fp(s.logits), h->labels_p, h->lablen_p, h->Lmax, U, B, Bp, C, Cp, fp(s.dL), fp(s.wce), fp(s.w), st);
+  launch_las_loss(fp(s.wce), fp(s.w), U, B, Bp, h->loss.as<float>(), h->nll.as<float>(), fp(s.dL), Cp, st);
+  HIPCHK(h, hipGetLastError());
+  s.have_pass = true;
+  h->have_fwd = true;
+  return NASR_OK;
+}
+
+int las_backward(nasr_ctx* h) {
+  LasState& s = *h->las;
+  const int B = h->B, Bp = h->Bp, U = s.U, C = h->C, Cp = h->Cp;
+  const int L4 = s.Lr[LasState::NL - 1];
+  const int UB = U * Bp;
+  const float* P = h->P;
+  float* G = h->G;
+  hipStream_t st = h->st;
+  const float* mem = fp(s.out[LasState::NL - 1]);
+  {
+    PhaseScope ps(h, PH_PROJB);
+    for (int t = U - 1; t >= 0; --t) {
+      const bool last = t == U - 1;
+      const float* dLt = fp(s.dL, (size_t)t * Bp * Cp);
+      float* dAt = fp(s.dA, (size_t)t * Bp * LAS_HE);
+      float* dQt = fp(s.dQ, (size_t)t * Bp * LAS_HD);
+      // da_t = dlogits W_p^T (+ the next step's gate input)
+      if (int rc = las_gemm(h, dLt, P + s.off_wp, last ? dAt : fp(s.tmpA), Bp, LAS_HE, Cp, Cp, Cp, LAS_HE, false, true)) return rc;
+      if (!last) launch_las_add(fp(s.tmpA), LAS_HE, fp(s.dS), LAS_SW, dAt, LAS_HE, Bp, LAS_HE, st);
+      if (int rc = las_gemm(h, dAt, P + s.off_watt, fp(s.dHC), Bp, 2 * LAS_HD, LAS_HE, LAS_HE, LAS_HE, 2 * LAS_HD, false, true))
+        return rc;
+      launch_las_attend_bwd(fp(s.keys), mem, fp(s.Q, (size_t)t * Bp * LAS_HD), P + s.off_v, fp(s.alpha, (size_t)t * Bp * L4),
+                            fp(s.dHC), dQt, fp(s.dkeys), fp(s.dmem), fp(s.dvpart, (size_t)t * Bp * LAS_HD), L4, Bp, last, st);
+      if (int rc = las_gemm(h, dQt, P + s.off_wq, fp(s.dhq), Bp, LAS_HD, LAS_HD, LAS_HD, LAS_HD, LAS_HD, false, true)) return rc;
+      float* dGt = fp(s.dGd, (size_t)t * Bp * LAS_G4D);
+      launch_las_dec_cell_bwd(fp(s.dact, (size_t)t * Bp * LAS_G4D), fp(s.dc, (size_t)t * Bp * LAS_HD),
+                              t == 0 ? fp(s.cinit) : fp(s.dc, (size_t)(t - 1) * Bp * LAS_HD), fp(s.dHC), fp(s.dhq), fp(s.dS),
+                              fp(s.dcd), dGt, Bp, last, st);
+      if (int rc = las_gemm(h, dGt, P + s.off_wah, fp(s.dS), Bp, LAS_SW, LAS_G4D, LAS_G4D, LAS_G4D, LAS_SW, false, true)) return rc;
+    }
+    launch_las_dec_init_bwd(fp(s.dS), fp(s.dcd), fp(s.dhc), fp(s.dcc), B, Bp, st);
+    HIPCHK(h, hipGetLastError());
+  }
+  {
+    PhaseScope ps(h, PH_WGRAD);
+    const float* Snext = fp(s.S, (size_t)Bp * LAS_SW);   // rows of steps 1..U: [a_t | h_t]
+    if (int rc = las_gemm(h, Snext, fp(s.dL), G + s.off_wp, LAS_HE, Cp, UB, LAS_SW, Cp, Cp, true, false)) return rc;
+    launch_colsum(fp(s.dL), UB, Cp, Cp, G + s.off_bp, fp(s.csws), st);
+    if (int rc = las_gemm(h, fp(s.HC), fp(s.dA), G + s.off_watt, 2 * LAS_HD, LAS_HE, UB, 2 * LAS_HD, LAS_HE, LAS_HE, true, false))
+      return rc;
+    if (int rc = las_gemm(h, Snext + LAS_HE, fp(s.dQ), G + s.off_wq, LAS_HD, LAS_HD, UB, LAS_SW, LAS_HD, LAS_HD, true, false))
+      return rc;
+    launch_colsum(fp(s.dvpart), UB, LAS_HD, LAS_HD, G + s.off_v, fp(s.csws), st);
+    if (int rc = las_gemm(h, fp(s.S), fp(s.dGd), G + s.off_wah, LAS_SW, LAS_G4D, UB, LAS_SW, LAS_G4D, LAS_G4D, true, false))
+      return rc;
+    launch_colsum(fp(s.dGd), UB, LAS_G4D, LAS_G4D, G + s.off_bd, fp(s.csws), st);
+    launch_las_embed_grad(fp(s.dGd), s.ids.as<int32_t>(), U, B, Bp, C, G + s.off_e, st);
+    if (int rc = las_gemm(h, mem, fp(s.dkeys), G + s.off_wmem, LAS_HD, LAS_HD, L4 * Bp, LAS_HD, LAS_HD, LAS_HD, true, false))
+      return rc;
+    // the memory's gradient: the context's share plus the keys' share, into the top layer's output gradient
+    if (int rc = las_gemm(h, fp(s.dkeys), P + s.off_wmem, fp(s.tmpm), L4 * Bp, LAS_HD, LAS_HD, LAS_HD, LAS_HD, LAS_HD, false, true))
+      return rc;
+    launch_las_add(fp(s.dmem), LAS_HD, fp(s.tmpm), LAS_HD, fp(s.dout), LAS_HD, L4 * Bp, LAS_HD, st);
+    HIPCHK(h, hipGetLastError());
+  }
+  for (int l = LasState::NL - 1; l >= 0; --l) {
+    const int L = s.Lr[l];
+    const int R = L * Bp;
+    {
+      PhaseScope ps(h, PH_RECB);
+      if (l < LasState::NL - 1) {
+        HIPCHK(h, hipMemsetAsync(s.dhc.p, 0, (size_t)2 * Bp * LAS_HE * 4, st));
+        HIPCHK(h, hipMemsetAsync(s.dcc.p, 0, (size_t)2 * Bp * LAS_HE * 4, st));
+      }
+      launch_las_transpose_wh(P + s.off_whf[l], fp(s.whT), st);
+      launch_las_transpose_wh(P + s.off_whb[l], fp(s.whT, (size_t)LAS_G4E * LAS_HE), st);
+      for (int t = L - 1; t >= 0; --t)
+        launch_las_enc_bwd_step(fp(s.dout), fp(s.whT), fp(s.whT, (size_t)LAS_G4E * LAS_HE), fp(s.act[l]), fp(s.c[l]), fp(s.dGe), fp(s.dhc),
+                                fp(s.dcc), t, L, B, Bp, st);
+    }
+    PhaseScope ps(h, PH_WGRAD);
+    const float* Xin = l == 0 ? h->X0.as<float>() : fp(s.X[l]);
+    const int in_rows = (l == 0 ? h->T : s.Lr[l - 1] / 2) * Bp;
+    if (int rc = las_gemm(h, Xin, fp(s.dGe), G + s.off_wx[l], s.Ip[l], 2 * LAS_G4E, R, s.Ip[l], 2 * LAS_G4E, 2 * LAS_G4E, true,
+                          false, nullptr, 0, in_rows))
+      return rc;
+    launch_colsum(fp(s.dGe), R, 2 * LAS_G4E, 2 * LAS_G4E, G + s.off_b[l], fp(s.csws), st);
+    // recurrent weights: h of the frame before (fw) / after (bw), zero outside the layer's frames
+    const float* o = fp(s.out[l]);
+    if (int rc = las_gemm(h, o, fp(s.dGe), G + s.off_whf[l], LAS_HE, LAS_G4E, R, 2 * LAS_HE, 2 * LAS_G4E, LAS_G4E, true, false,
+                          nullptr, -Bp, R))
+      return rc;
+    if (int rc = las_gemm(h, o + LAS_HE, fp(s.dGe) + LAS_G4E, G + s.off_whb[l], LAS_HE, LAS_G4E, R, 2 * LAS_HE, 2 * LAS_G4E,
+                          LAS_G4E, true, false, nullptr, Bp, R))
+      return rc;
+    if (l > 0) {
+      if (int rc = las_gemm(h, fp(s.dGe), P + s.off_wx[l], fp(s.dX), R, 4 * LAS_HE, 2 * LAS_G4E, 2 * LAS_G4E, 2 * LAS_G4E,
+                            4 * LAS_HE, false, true))
+        return rc;
+      launch_las_pyr_unpack(fp(s.dX), fp(s.dout), s.Lr[l - 1] / 2, Bp, st);
+    }
+    HIPCHK(h, hipGetLastError());
+  }
+  HIPCHK(h, hipEventRecord(h->ev_bucket.back(), st));   // one bucket: the whole gradient with the fault word
+  h->have_grads = true;
+  return NASR_OK;
+}
+
+}  // namespace nasr_impl
+
+void nasr_impl::LasStateDelete::operator()(LasState* s) const { delete s; }
+
+namespace {
+LasState* las_of(nasr_handle h) { return h ? h->las.get() : nullptr; }
+
+// [U][Bp][cols] (element size esz) read back and reordered to [B][U][cols]
+int las_read_bu(nasr_ctx* h, const DevBuf& src, int cols, int ld, size_t esz, void* dst) {
+  LasState& s = *h->las;
+  const int B = h->B, Bp = h->Bp, U = s.U;
+  std::vector<char> tmp((size_t)U * Bp * ld * esz);
+  HIPCHK(h, hipMemcpyAsync(tmp.data(), src.p, tmp.size(), hipMemcpyDeviceToHost, h->st));
+  if (int rc = sync_checked(h)) return rc;
+  char* d = static_cast<char*>(dst);
+  for (int b = 0; b < B; ++b)
+    for (int t = 0; t < U; ++t)
+      memcpy(d + ((size_t)b * U + t) * cols * esz, tmp.data() + ((size_t)t * Bp + b) * ld * esz, (size_t)cols * esz);
+  return NASR_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int nasr_create_las(const nasr_las_cfg* cfg, int device_id, void* stream, nasr_handle* out) {
+  if (!cfg || !out) {
+    g_create_error = "nasr_create_las: null argument";
+    return NASR_ERR_ARG;
+  }
+  *out = nullptr;
+  if (cfg->feature_size < 1 || cfg->num_classes < 2) {
+    g_create_error = "nasr_create_las: feature_size must be >= 1 and num_classes >= 2";
+    return NASR_ERR_ARG;
+  }
+  if (cfg->num_hidden != LAS_H || cfg->num_layers != LasState::NL) {
+    g_create_error = "nasr_create_las: only num_hidden = 250 and num_layers = 4 (the reference's) are implemented";
+    return NASR_ERR_ARG;
+  }
+  if (!(cfg->sampling_probability >= 0.f && cfg->sampling_probability <= 1.f)) {
+    g_create_error = "nasr_create_las: sampling_probability must be in [0,1]";
+    return NASR_ERR_ARG;
+  }
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) {
+    g_create_error = "nasr_create_las: no HIP device visible (libnasr has no CPU fallback)";
+    return NASR_ERR_HIP;
+  }
+  if (device_id < 0 || device_id >= ndev) {
+    g_create_error = "nasr_create_las: device_id out of range";
+    return NASR_ERR_ARG;
+  }
+  hipDeviceProp_t prop;
+  if (hipGetDeviceProperties(&prop, device_id) != hipSuccess) {
+    g_create_error = "nasr_create_las: hipGetDeviceProperties failed";
+    return NASR_ERR_HIP;
+  }
+  if (std::string(prop.gcnArchName).find("gfx950") == std::string::npos) {
+    g_create_error = std::string("nasr_create_las: device is ") + prop.gcnArchName + ", libnasr is built for gfx950 only";
+    return NASR_ERR_HIP;
+  }
+  nasr_ctx* h = new nasr_ctx();
+  auto bail = [&](int code, const std::string& m) {
+    g_create_error = m;
+    nasr_destroy(h);
+    return code;
+  };
+  memset(&h->cfg, 0, sizeof(h->cfg));
+  h->cfg.feature_size = cfg->feature_size;
+  h->cfg.num_classes = cfg->num_classes;
+  h->cfg.merge = NASR_MERGE_NONE;
+  h->cfg.learning_rate = cfg->learning_rate;
+  h->cfg.beta1 = cfg->beta1; h->cfg.beta2 = cfg->beta2; h->cfg.epsilon = cfg->epsilon;
+  h->device = device_id;
+  h->lr = cfg->learning_rate;
+  h->graph_mode = false;
+  h->las.reset(new LasState());
+  LasState& s = *h->las;
+  s.cfg = *cfg;
+  s.p = cfg->sampling_probability;
+  s.seed = cfg->seed;
+  if (hipSetDevice(device_id) != hipSuccess) return bail(NASR_ERR_HIP, "hipSetDevice failed");
+  if (stream)
+    h->st.borrow(reinterpret_cast<hipStream_t>(stream));
+  else if (hipStreamCreateWithFlags(h->st.out(), hipStreamNonBlocking) != hipSuccess)
+    return bail(NASR_ERR_HIP, "hipStreamCreate failed");
+  las_layout(h);
+  const size_t nb = (size_t)h->np_int * 4, gb = nb + GRAD_HEAD * 4;
+  if (hipMalloc(h->P.out(), nb) != hipSuccess || hipMalloc(h->M.out(), nb) != hipSuccess || hipMalloc(h->V.out(), nb) != hipSuccess ||
+      hipMalloc(h->Gbase.out(), gb) != hipSuccess || hipMalloc(h->adam_dev.out(), sizeof(AdamDev)) != hipSuccess)
+    return bail(NASR_ERR_HIP, "hipMalloc of parameter buffers failed");
+  (void)hipMemsetAsync(h->adam_dev, 0, sizeof(AdamDev), h->st);
+  (void)hipMemsetAsync(h->P, 0, nb, h->st);
+  (void)hipMemsetAsync(h->M, 0, nb, h->st);
+  (void)hipMemsetAsync(h->V, 0, nb, h->st);
+  (void)hipMemsetAsync(h->Gbase, 0, gb, h->st);
+  h->G = h->Gbase + GRAD_HEAD;
+  if (int rc = single_bucket_handle_setup(h, &g_create_error)) {
+    const std::string m = g_create_error;
+    return bail(rc, m);
+  }
+  *out = h;
+  return NASR_OK;
+}
+
+int nasr_las_set_sampling(nasr_handle h, float p, uint32_t seed, uint32_t counter, int tower) {
+  LasState* s = las_of(h);
+  if (!s) return h ? h->fail(NASR_ERR_STATE, "nasr_las_set_sampling: not a LAS handle") : NASR_ERR_ARG;
+  if (!(p >= 0.f && p <= 1.f) || tower < 0) return h->fail(NASR_ERR_ARG, "nasr_las_set_sampling: p must be in [0,1], tower >= 0");
+  s->p = p; s->seed = seed; s->counter = counter; s->tower = tower;
+  return NASR_OK;
+}
+
+int nasr_las_get_sampling(nasr_handle h, float* p, uint32_t* seed, uint32_t* counter, int* tower) {
+  LasState* s = las_of(h);
+  if (!s) return h ? h->fail(NASR_ERR_STATE, "nasr_las_get_sampling: not a LAS handle") : NASR_ERR_ARG;
+  if (p) *p = s->p;
+  if (seed) *seed = s->seed;
+  if (counter) *counter = s->counter;
+  if (tower) *tower = s->tower;
+  return NASR_OK;
+}
+
+int nasr_las_forward(nasr_handle h, const float* feats, const int32_t* seq_len, const int32_t* labels, const int32_t* label_len,
+                     int B, int T, int U, int sample, float* logits_out) {
+  LasState* s = las_of(h);
+  if (!s) return h ? h->fail(NASR_ERR_STATE, "nasr_las_forward: not a LAS handle") : NASR_ERR_ARG;
+  if (!labels || !label_len) return h->fail(NASR_ERR_ARG, "nasr_las_forward needs labels");
+  HIPCHK(h, hipSetDevice(h->device));
+  int rc = upload(h, feats, seq_len, labels, label_len, B, T, U);
+  if (rc) return rc;
+  rc = las_forward(h, sample != 0);
+  if (rc) return rc;
+  if (logits_out) return nasr_las_get_logits(h, logits_out);
+  return sync_checked(h);
+}
+
+int nasr_las_get_logits(nasr_handle h, float* logits_out) {
+  LasState* s = las_of(h);
+  if (!s) return h ? h->fail(NASR_ERR_STATE, "nasr_las_get_logits: not a LAS handle") : NASR_ERR_ARG;
+  if (!logits_out) return h->fail(NASR_ERR_ARG, "nasr_las_get_logits: null output");
+  if (!s->have_pass) return h->fail(NASR_ERR_STATE, "nasr_las_get_logits: no decoder pass has run");
+  return las_read_bu(h, s->logits, h->C, h->Cp, 4, logits_out);
+}
+
+int nasr_las_get_fed_ids(nasr_handle h, int32_t* ids_out) {
+  LasState* s = las_of(h);
+  if (!s) return h ? h->fail(NASR_ERR_STATE, "nasr_las_get_fed_ids: not a LAS handle") : NASR_ERR_ARG;
+  if (!ids_out) return h->fail(NASR_ERR_ARG, "nasr_las_get_fed_ids: null output");
+  if (!s->have_pass) return h->fail(NASR_ERR_STATE, "nasr_las_get_fed_ids: no decoder pass has run");
+  return las_read_bu(h, s->ids, 1, 1, 4, ids_out);
+}
+
+int nasr_las_get_sampled(nasr_handle h, int32_t* sampled_out) {
+  LasState* s = las_of(h);
+  if (!s) return h ? h->fail(NASR_ERR_STATE, "nasr_las_get_sampled: not a LAS handle") : NASR_ERR_ARG;
+  if (!sampled_out) return h->fail(NASR_ERR_ARG, "nasr_las_get_sampled: null output");
+  if (!s->have_pass) return h->fail(NASR_ERR_STATE, "nasr_las_get_sampled: no decoder pass has run");
+  return las_read_bu(h, s->sampled, 1, 1, 4, sampled_out);
+}
+
+}  // extern "C"

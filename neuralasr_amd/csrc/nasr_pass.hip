@@ -192,6 +192,7 @@ int dense_backward(nasr_ctx* h, int i, const float* X, float* dX) {
 int forward(nasr_ctx* h) {
   if (!h->resident) return h->fail(NASR_ERR_STATE, "no resident batch: call nasr_upload_batch first");
   if (h->wn) return wn_forward(h, false);   // forward-only calls: inference-mode batch norm
+  if (h->las) return h->fail(NASR_ERR_STATE, "a LAS handle has no CTC logits: use nasr_las_forward");
   const int Bp = h->Bp, T = h->T, D = h->D, Hp = h->Hp;
   const int R = T * Bp;
   h->n_fwd_launch = 0;
@@ -389,6 +390,7 @@ int wg_join(nasr_ctx* h, int l) {
 
 int backward(nasr_ctx* h) {
   if (h->wn) return wn_backward(h);
+  if (h->las) return las_backward(h);
   const int Bp = h->Bp, T = h->T, D = h->D, Hp = h->Hp;
   const int R = T * Bp, Rp = h->Tp * Bp;
   const bool sr = h->cfg.merge == NASR_MERGE_STACK_RESHAPE && D == 2;

@@ -299,6 +299,44 @@ int wn_backward(nasr_ctx* h) {
   return NASR_OK;
 }
 
+
+// The set-up the WaveNet and LAS handles share once their parameter buffers exist: one gradient bucket (the whole array,
+// completed at the end of the backward pass) with its event, the copy and logits streams, the batch slots' events, the
+// step-result stamps and step-end words, the timing events; then a synchronise.  A failure leaves its message in *err.
+int single_bucket_handle_setup(nasr_ctx* h, std::string* err) {
+  auto bail = [&](int code, const char* m) { *err = m; return code; };
+  h->buckets.push_back({0, GRAD_HEAD + h->np_int});
+  h->ev_bucket.resize(1);
+  if (hipEventCreateWithFlags(h->ev_bucket[0].out(), hipEventDisableTiming) != hipSuccess)
+    return bail(NASR_ERR_HIP, "hipEventCreate failed");
+  if (hipStreamCreateWithFlags(h->cst.out(), hipStreamNonBlocking) != hipSuccess ||
+      hipStreamCreateWithFlags(h->d2h.out(), hipStreamNonBlocking) != hipSuccess ||
+      hipEventCreateWithFlags(h->ev_snap.out(), hipEventDisableTiming) != hipSuccess)
+    return bail(NASR_ERR_HIP, "hipStreamCreate failed");
+  for (BatchSlot& bs : h->slots)
+    if (hipEventCreateWithFlags(bs.ev_copy.out(), hipEventDisableTiming) != hipSuccess ||
+        hipEventCreateWithFlags(bs.ev_released.out(), hipEventDisableTiming) != hipSuccess)
+      return bail(NASR_ERR_HIP, "hipEventCreate failed");
+  for (auto& r : h->res) {
+    if (hipHostMalloc(r.stamp.out(), 64, hipHostMallocMapped) != hipSuccess)
+      return bail(NASR_ERR_HIP, "set-up of the step-result stamps failed");
+    *r.stamp = 0;
+  }
+  for (auto& e : h->endw) {
+    if (hipHostMalloc(e.host.out(), 64, hipHostMallocMapped) != hipSuccess)
+      return bail(NASR_ERR_HIP, "set-up of the step-end words failed");
+    e.stamp = reinterpret_cast<uint32_t*>(e.host.get()) + 8;
+    *e.host = 0.f;
+    *e.stamp = 0;
+  }
+  (void)hipEventCreate(h->ev_total_a.out());
+  (void)hipEventCreate(h->ev_total_b.out());
+  memset(&h->last_times, 0, sizeof(h->last_times));
+  if (hipGetLastError() != hipSuccess || hipStreamSynchronize(h->st) != hipSuccess)
+    return bail(NASR_ERR_HIP, "stream synchronize failed in create");
+  return NASR_OK;
+}
+
 }  // namespace nasr_impl
 
 void nasr_impl::WnStateDelete::operator()(WnState* w) const { delete w; }
@@ -403,36 +441,10 @@ int nasr_create_wavenet(const nasr_wavenet_cfg* cfg, int device_id, void* stream
   (void)hipMemsetAsync(w.mm, 0, sb, h->st);
   (void)hipMemsetAsync(w.biased, 0, sb, h->st);
   launch_fill(w.mv, 1.f, w.S * w.D, h->st);
-  // one gradient bucket: the whole array, completed at the end of the backward pass
-  h->buckets.push_back({0, GRAD_HEAD + h->np_int});
-  h->ev_bucket.resize(1);
-  if (hipEventCreateWithFlags(h->ev_bucket[0].out(), hipEventDisableTiming) != hipSuccess)
-    return bail(NASR_ERR_HIP, "hipEventCreate failed");
-  if (hipStreamCreateWithFlags(h->cst.out(), hipStreamNonBlocking) != hipSuccess ||
-      hipStreamCreateWithFlags(h->d2h.out(), hipStreamNonBlocking) != hipSuccess ||
-      hipEventCreateWithFlags(h->ev_snap.out(), hipEventDisableTiming) != hipSuccess)
-    return bail(NASR_ERR_HIP, "hipStreamCreate failed");
-  for (BatchSlot& bs : h->slots)
-    if (hipEventCreateWithFlags(bs.ev_copy.out(), hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(bs.ev_released.out(), hipEventDisableTiming) != hipSuccess)
-      return bail(NASR_ERR_HIP, "hipEventCreate failed");
-  for (auto& r : h->res) {
-    if (hipHostMalloc(r.stamp.out(), 64, hipHostMallocMapped) != hipSuccess)
-      return bail(NASR_ERR_HIP, "set-up of the step-result stamps failed");
-    *r.stamp = 0;
+  if (int rc = single_bucket_handle_setup(h, &g_create_error)) {
+    const std::string m = g_create_error;
+    return bail(rc, m);
   }
-  for (auto& e : h->endw) {
-    if (hipHostMalloc(e.host.out(), 64, hipHostMallocMapped) != hipSuccess)
-      return bail(NASR_ERR_HIP, "set-up of the step-end words failed");
-    e.stamp = reinterpret_cast<uint32_t*>(e.host.get()) + 8;
-    *e.host = 0.f;
-    *e.stamp = 0;
-  }
-  (void)hipEventCreate(h->ev_total_a.out());
-  (void)hipEventCreate(h->ev_total_b.out());
-  memset(&h->last_times, 0, sizeof(h->last_times));
-  if (hipGetLastError() != hipSuccess || hipStreamSynchronize(h->st) != hipSuccess)
-    return bail(NASR_ERR_HIP, "stream synchronize failed in create");
   *out = h;
   return NASR_OK;
 }

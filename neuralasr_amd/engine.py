@@ -538,3 +538,84 @@ class WaveNetEngine(Engine):
         m = _f32(np.stack([np.asarray(x).ravel() for x in means]))
         v = _f32(np.stack([np.asarray(x).ravel() for x in variances]))
         self._ck(self.lib.nasr_wavenet_apply_bn_stats(self.h, _fp(m), _fp(v), self.bn_count, k))
+
+
+class LasEngine(Engine):
+    """An Engine over a LAS handle (include/nasr.h: nasr_create_las): the common parameter, batch, gradient, Adam and
+    exchange calls, plus the decoder's logits, the ids fed to its steps and the scheduled-sampling state.  Labels are
+    dense [B, U]; the loss is sequence_loss."""
+
+    def __init__(self, feature_size, num_classes, num_hidden=250, num_layers=4, sampling_probability=0.1, seed=1,
+                 learning_rate=1e-4, beta1=0.9, beta2=0.999, epsilon=1e-8, device_id=0, stream=None):
+        self.lib = _lib.load()
+        self.cfg = _lib.LasCfg(int(feature_size), int(num_classes), int(num_hidden), int(num_layers),
+                               float(sampling_probability), int(seed) & 0xFFFFFFFF, float(learning_rate), float(beta1),
+                               float(beta2), float(epsilon))
+        if stream is not None and int(stream) == 0:
+            raise ValueError('stream 0 (the legacy default stream) cannot carry the engine')
+        self.h = c_void_p()
+        rc = self.lib.nasr_create_las(byref(self.cfg), int(device_id), c_void_p(stream) if stream else None, byref(self.h))
+        if rc != 0:
+            msg = self.lib.nasr_last_error(None)
+            self.h = None
+            raise _lib.NasrError(rc, msg.decode() if msg else 'nasr_create_las failed')
+        self.num_classes = int(num_classes)
+        self.param_count = int(self.lib.nasr_param_count(self.h))
+        self._BU = (0, 0)
+
+    def set_step_decode(self, on, logits=False, greedy=True):
+        """The LAS step has no CTC step results: its loss and logits are read after the pass (get_loss, logits)."""
+
+    def upload_batch(self, feats, seq_len, labels, label_len):
+        feats, seq, labels, ll, B, T, U = self._batch(feats, seq_len, labels, label_len)
+        self._BU = (B, U)
+        self._ck(self.lib.nasr_upload_batch(self.h, _fp(feats), _ip(seq), _ip(labels), _ip(ll), B, T, U))
+
+    def las_forward(self, feats, seq_len, labels, label_len, sample=False):
+        """logits [B, U, C] of a decoder pass (sample: scheduled sampling at the handle's probability); loss via get_loss."""
+        feats, seq, labels, ll, B, T, U = self._batch(feats, seq_len, labels, label_len)
+        self._BU = (B, U)
+        out = np.empty((B, U, self.num_classes), np.float32)
+        self._ck(self.lib.nasr_las_forward(self.h, _fp(feats), _ip(seq), _ip(labels), _ip(ll), B, T, U, int(bool(sample)),
+                                           _fp(out)))
+        return out
+
+    def loss(self, feats, seq_len, labels, label_len):
+        _, _, labels, _, B, _, U = self._batch(feats, seq_len, labels, label_len)
+        self._BU = (B, U)
+        return Engine.loss(self, feats, seq_len, labels, label_len)
+
+    def loss_and_grads(self, feats, seq_len, labels, label_len):
+        _, _, labels, _, B, _, U = self._batch(feats, seq_len, labels, label_len)
+        self._BU = (B, U)
+        return Engine.loss_and_grads(self, feats, seq_len, labels, label_len)
+
+    def logits(self):
+        """logits [B, U, C] of the last decoder pass"""
+        B, U = self._BU
+        out = np.empty((B, U, self.num_classes), np.float32)
+        self._ck(self.lib.nasr_las_get_logits(self.h, _fp(out)))
+        return out
+
+    def fed_ids(self):
+        """the ids the last decoder pass fed to its steps [B, U] (labels, or scheduled samples)"""
+        B, U = self._BU
+        out = np.empty((B, U), np.int32)
+        self._ck(self.lib.nasr_las_get_fed_ids(self.h, _ip(out)))
+        return out
+
+    def sampled(self):
+        """1 where the last decoder pass fed a scheduled sample instead of the label [B, U]"""
+        B, U = self._BU
+        out = np.empty((B, U), np.int32)
+        self._ck(self.lib.nasr_las_get_sampled(self.h, _ip(out)))
+        return out
+
+    def sampling_state(self):
+        p, seed, counter, tower = c_float(), c_uint32(), c_uint32(), ctypes.c_int()
+        self._ck(self.lib.nasr_las_get_sampling(self.h, byref(p), byref(seed), byref(counter), byref(tower)))
+        return float(p.value), int(seed.value), int(counter.value), int(tower.value)
+
+    def set_sampling_state(self, p, seed, counter, tower=0):
+        self._ck(self.lib.nasr_las_set_sampling(self.h, float(p), int(seed) & 0xFFFFFFFF, int(counter) & 0xFFFFFFFF,
+                                                int(tower)))
