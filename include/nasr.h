@@ -395,6 +395,28 @@ int nasr_las_get_logits(nasr_handle h, float* logits_out);
 int nasr_las_get_fed_ids(nasr_handle h, int32_t* ids_out);
 /* of the last decoder pass: 1 where the step's input was a scheduled sample, else 0 [B][U] (step 0 is never sampled) */
 int nasr_las_get_sampled(nasr_handle h, int32_t* sampled_out);
+/* Beam-search decoding (the reference's inference graph: BeamSearchDecoder of TF 1.15 with length penalty, then
+ * gather_tree).  The encoder runs over feats [B][T][F] (B in [1,64], seq_len in [1,T]); every utterance's memory and final
+ * (c, h) are tiled to beam_width beams (in [1,1024]); beam 0 starts with log-prob 0 and beams 1.. start finished with
+ * -inf; every step feeds the chosen ids (start_id first).  A step scores total / ((5 + len)^p / 6^p) and keeps the exact
+ * top beam_width of each utterance's beam_width * C candidates (score descending, equal scores by index beam*C + id
+ * ascending).  The search stops after the step at which every beam is finished (or after max_steps, in [1,1000]);
+ * *steps_out = T_dec, the steps run.  start_id / end_id in [0, num_classes-1], length_penalty finite and >= 0.
+ * A search has buffers of its own: it does not replace the uploaded batch and leaves the parameters, the Adam state, the
+ * gradient buffer, the sampling state and the last decoder pass's loss, logits and ids as they were (it is not a sampling
+ * pass).  With nasr_set_profiling on, the search records its device-timed phases (nasr_las_beam_get_times). */
+int nasr_las_beam_search(nasr_handle h, const float* feats, const int32_t* seq_len, int B, int T, int beam_width, int max_steps,
+                         int start_id, int end_id, float length_penalty, int32_t* steps_out);
+/* of the last search: the gathered ids (gather_tree) [B][T_dec][W] */
+int nasr_las_beam_get_ids(nasr_handle h, int32_t* ids_out);
+/* of the last search, any output may be NULL: every step's top-W scores, chosen word ids and parent beams [B][T_dec][W] */
+int nasr_las_beam_get_trace(nasr_handle h, float* scores_out, int32_t* word_out, int32_t* parent_out);
+/* of the last search, any output may be NULL: the final log-probs, lengths and finished flags (0 / 1) [B][W] */
+int nasr_las_beam_get_final(nasr_handle h, float* log_probs_out, int32_t* lengths_out, int32_t* finished_out);
+/* of the last search when it ran with profiling on (else NASR_ERR_STATE): device-timed ms of 7 phases: encoder (with the
+ * feature copy, keys and initial state), decoder GEMMs, decoder cell, attention, selection (scores, top-W, update),
+ * gather_tree, and the host's waits between chunks of steps */
+int nasr_las_beam_get_times(nasr_handle h, float* ms_out);
 
 /* ---- the MFCC front end (utils.py:24-31: convert_to_mfcc) --------------------------------------
  * python_speech_features 0.6's mfcc(audio, samplerate, numcep=numcep, nfilt=128) on float32 audio: pre-emphasis in

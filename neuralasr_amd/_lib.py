@@ -35,7 +35,8 @@ SYMBOLS = [
     'nasr_create_wavenet', 'nasr_wavenet_bn_count', 'nasr_wavenet_get_bn_state', 'nasr_wavenet_set_bn_state',
     'nasr_wavenet_set_bn_hold', 'nasr_wavenet_get_batch_stats', 'nasr_wavenet_apply_bn_stats',
     'nasr_create_las', 'nasr_las_set_sampling', 'nasr_las_get_sampling', 'nasr_las_forward', 'nasr_las_get_logits',
-    'nasr_las_get_fed_ids', 'nasr_las_get_sampled',
+    'nasr_las_get_fed_ids', 'nasr_las_get_sampled', 'nasr_las_beam_search', 'nasr_las_beam_get_ids',
+    'nasr_las_beam_get_trace', 'nasr_las_beam_get_final', 'nasr_las_beam_get_times',
     'nasr_create_featurizer', 'nasr_mfcc_frames', 'nasr_mfcc_filterbank', 'nasr_featurize', 'nasr_featurize_times',
 ]
 
@@ -181,6 +182,11 @@ def load():
         'nasr_las_get_logits': (c_int, [H, fp]),
         'nasr_las_get_fed_ids': (c_int, [H, ip]),
         'nasr_las_get_sampled': (c_int, [H, ip]),
+        'nasr_las_beam_search': (c_int, [H, fp, ip, c_int, c_int, c_int, c_int, c_int, c_int, c_float, ip]),
+        'nasr_las_beam_get_ids': (c_int, [H, ip]),
+        'nasr_las_beam_get_trace': (c_int, [H, fp, ip, ip]),
+        'nasr_las_beam_get_final': (c_int, [H, fp, ip, ip]),
+        'nasr_las_beam_get_times': (c_int, [H, fp]),
         'nasr_create_featurizer': (c_int, [POINTER(MfccCfg), c_int, c_void_p, POINTER(H)]),
         'nasr_mfcc_frames': (c_int64, [POINTER(MfccCfg), c_int64]),
         'nasr_mfcc_filterbank': (c_int, [POINTER(MfccCfg), ip, fp]),

@@ -7,6 +7,7 @@
 // the common code.  DESIGN.md §10.
 #include "nasr_ctx.h"
 #include "las.h"
+#include "las_beam.h"
 
 #include <functional>
 
@@ -14,6 +15,26 @@ using namespace nasr;
 using namespace nasr_impl;
 
 namespace nasr_impl {
+
+// The beam search's own buffers (nasr_las_beam_search), made on the first search and apart from the training pass's: a
+// search leaves the resident batch, the last pass's logits and loss, the gradient and the sampling state as they are.
+// Beam rows r = b*W + k, R = rup(B*W, 16); the encoder's rows t*Bp + b as in training.
+struct LasBeam {
+  static constexpr int NL = 4;
+  int B = 0, Bp = 0, T = 0, W = 0, R = 0, max_steps = 0, Tdec = 0, end_id = 0;
+  int Lr[NL] = {0, 0, 0, 0};
+  bool have = false, timed = false;
+  DevBuf feats, X0, X[NL], xp[NL], act[NL], c[NL], out[NL], keys;
+  // decoder rows: S / c the beams' state, Sx / cx the step's outputs before the gather by parent
+  DevBuf S, cs, Sx, cx, gp, dact, HC, Q, logits, ids;
+  DevBuf logp[2], len[2], fin[2];                  // ping-pong by step parity: step t reads [t & 1], writes the other
+  DevBuf scores, totals, sel_idx, sel_score, pen, flags;
+  DevBuf tr_score, tr_word, tr_parent, gathered;   // [max_steps][B*W]
+  std::vector<float> hpen;
+  std::vector<Event> ev;                           // phase marks of a timed search
+  std::vector<std::pair<int, size_t>> marks;
+  float times[7] = {0, 0, 0, 0, 0, 0, 0};
+};
 
 struct LasState {
   nasr_las_cfg cfg;
@@ -39,6 +60,7 @@ struct LasState {
   DevBuf keys, dkeys, dmem, tmpm;
   DevBuf S, cinit, dc, dact, gp, Q, alpha, HC, logits, ids, sampled;
   DevBuf dL, wce, w, tmpA, dA, dHC, dQ, dhq, dGd, dS, dcd, dvpart, csws;
+  std::unique_ptr<LasBeam> beam;   // the beam search's buffers (first search)
 };
 
 namespace {
@@ -203,6 +225,28 @@ int las_ensure_shape(nasr_ctx* h, int B, int T, int Lmax) {
   return NASR_OK;
 }
 
+// The pyramidal encoder over X0 [T*Bp][Fp] (rows t*Bp + b) into the given per-layer buffers, Lr: las_lengths(T).  The
+// training pass and the beam search share it.
+int las_encode(nasr_ctx* h, const float* X0, int T, int B, int Bp, const int* Lr, DevBuf* X, DevBuf* xp, DevBuf* act, DevBuf* c,
+               DevBuf* out) {
+  LasState& s = *h->las;
+  const float* P = h->P;
+  hipStream_t st = h->st;
+  for (int l = 0; l < LasState::NL; ++l) {
+    const int L = Lr[l];
+    const float* Xin = l == 0 ? X0 : fp(X[l]);
+    // rows past the input's frames (the odd-length padding) read as zero
+    const int in_rows = (l == 0 ? T : Lr[l - 1] / 2) * Bp;
+    if (l > 0) launch_las_pyr_pack(fp(out[l - 1]), fp(X[l]), Lr[l - 1] / 2, Bp, st);
+    if (int rc = las_gemm(h, Xin, P + s.off_wx[l], fp(xp[l]), L * Bp, 2 * LAS_G4E, s.Ip[l], s.Ip[l], 2 * LAS_G4E, 2 * LAS_G4E,
+                          false, false, P + s.off_b[l], 0, in_rows))
+      return rc;
+    for (int t = 0; t < L; ++t)
+      launch_las_enc_fwd_step(fp(xp[l]), P + s.off_whf[l], P + s.off_whb[l], fp(act[l]), fp(c[l]), fp(out[l]), t, L, B, Bp, st);
+  }
+  return NASR_OK;
+}
+
 // The encoder and the decoder chain of the resident batch.  sample: scheduled sampling with the handle's probability (one
 // counter value per such pass); otherwise every step is fed its label.
 int las_forward(nasr_ctx* h, bool sample) {
@@ -215,19 +259,7 @@ int las_forward(nasr_ctx* h, bool sample) {
   HIPCHK(h, hipMemsetAsync(h->Gbase, 0, GRAD_HEAD * 4, st));   // the step's fault word (nothing here raises it)
   {
     PhaseScope ps(h, PH_RECF);
-    for (int l = 0; l < LasState::NL; ++l) {
-      const int L = s.Lr[l];
-      const float* Xin = l == 0 ? h->X0.as<float>() : fp(s.X[l]);
-      // rows past the input's frames (the odd-length padding) read as zero
-      const int in_rows = (l == 0 ? h->T : s.Lr[l - 1] / 2) * Bp;
-      if (l > 0) launch_las_pyr_pack(fp(s.out[l - 1]), fp(s.X[l]), s.Lr[l - 1] / 2, Bp, st);
-      if (int rc = las_gemm(h, Xin, P + s.off_wx[l], fp(s.xp[l]), L * Bp, 2 * LAS_G4E, s.Ip[l], s.Ip[l], 2 * LAS_G4E,
-                            2 * LAS_G4E, false, false, P + s.off_b[l], 0, in_rows))
-        return rc;
-      for (int t = 0; t < L; ++t)
-        launch_las_enc_fwd_step(fp(s.xp[l]), P + s.off_whf[l], P + s.off_whb[l], fp(s.act[l]), fp(s.c[l]), fp(s.out[l]), t, L,
-                                B, Bp, st);
-    }
+    if (int rc = las_encode(h, h->X0.as<float>(), h->T, B, Bp, s.Lr, s.X, s.xp, s.act, s.c, s.out)) return rc;
   }
   PhaseScope ps(h, PH_PROJCTC);
   const int L4 = s.Lr[LasState::NL - 1];
@@ -366,6 +398,144 @@ int las_backward(nasr_ctx* h) {
   }
   HIPCHK(h, hipEventRecord(h->ev_bucket.back(), st));   // one bucket: the whole gradient with the fault word
   h->have_grads = true;
+  return NASR_OK;
+}
+
+
+// ------------------------------------------------------------------ beam search
+enum { LB_ENC = 0, LB_GEMM, LB_CELL, LB_ATTN, LB_SEL, LB_TREE, LB_WAIT, LB_COUNT };
+
+int las_beam_ensure(nasr_ctx* h, LasBeam& m, int B, int T, int W, int max_steps) {
+  const int Bp = rup(B, 16), nrows = B * W, R = rup(nrows, 16), C = h->C;
+  int Lr[LasBeam::NL];
+  las_lengths(T, Lr);
+  const size_t L4B = (size_t)Lr[LasBeam::NL - 1] * Bp, MR = (size_t)max_steps * nrows;
+  bool grew = false, ok = true;
+  ok &= m.feats.ensure((size_t)B * T * h->F * 4, &grew);
+  ok &= m.X0.ensure((size_t)T * Bp * h->Fp * 4, &grew);
+  for (int l = 0; l < LasBeam::NL; ++l) {
+    const size_t Rl = (size_t)Lr[l] * Bp;
+    if (l > 0) ok &= m.X[l].ensure(Rl * 4 * LAS_HE * 4, &grew);
+    ok &= m.xp[l].ensure(Rl * 2 * LAS_G4E * 4, &grew);
+    ok &= m.act[l].ensure(Rl * 2 * LAS_G4E * 4, &grew);
+    ok &= m.c[l].ensure(Rl * 2 * LAS_H * 4, &grew);
+    ok &= m.out[l].ensure(Rl * 2 * LAS_HE * 4, &grew);
+  }
+  ok &= m.keys.ensure(L4B * LAS_HD * 4, &grew);
+  ok &= m.S.ensure((size_t)R * LAS_SW * 4, &grew) && m.Sx.ensure((size_t)R * LAS_SW * 4, &grew);
+  ok &= m.cs.ensure((size_t)R * LAS_HD * 4, &grew) && m.cx.ensure((size_t)R * LAS_HD * 4, &grew);
+  ok &= m.gp.ensure((size_t)R * LAS_G4D * 4, &grew) && m.dact.ensure((size_t)R * LAS_G4D * 4, &grew);
+  ok &= m.HC.ensure((size_t)R * 2 * LAS_HD * 4, &grew) && m.Q.ensure((size_t)R * LAS_HD * 4, &grew);
+  ok &= m.logits.ensure((size_t)R * h->Cp * 4, &grew) && m.ids.ensure((size_t)R * 4, &grew);
+  for (int i = 0; i < 2; ++i)
+    ok &= m.logp[i].ensure((size_t)R * 4, &grew) && m.len[i].ensure((size_t)R * 4, &grew) && m.fin[i].ensure((size_t)R * 4, &grew);
+  ok &= m.scores.ensure((size_t)nrows * C * 4, &grew) && m.totals.ensure((size_t)nrows * C * 4, &grew);
+  ok &= m.sel_idx.ensure((size_t)nrows * 4, &grew) && m.sel_score.ensure((size_t)nrows * 4, &grew);
+  ok &= m.pen.ensure((size_t)(max_steps + 1) * 4, &grew) && m.flags.ensure(8, &grew);
+  ok &= m.tr_score.ensure(MR * 4, &grew) && m.tr_word.ensure(MR * 4, &grew) && m.tr_parent.ensure(MR * 4, &grew);
+  ok &= m.gathered.ensure(MR * 4, &grew);
+  if (!ok) return h->fail(NASR_ERR_HIP, "hipMalloc failed while sizing beam-search buffers");
+  m.B = B; m.Bp = Bp; m.T = T; m.W = W; m.R = R; m.max_steps = max_steps;
+  for (int l = 0; l < LasBeam::NL; ++l) m.Lr[l] = Lr[l];
+  return NASR_OK;
+}
+
+// The inference graph of the reference: the encoder, the tiled initial state, then per step the decoder
+// cell and attention over all beam rows, the scores and the exact top-W, the update by parent; gather_tree at the end.
+// Steps are enqueued in chunks; the host reads the device's done word once per chunk.
+int las_beam_search(nasr_ctx* h, const float* feats, int B, int T, int W, int max_steps, int start_id, int end_id, float lp) {
+  LasState& s = *h->las;
+  if (!s.beam) s.beam.reset(new LasBeam());
+  LasBeam& m = *s.beam;
+  m.have = false;
+  if (int rc = las_beam_ensure(h, m, B, T, W, max_steps)) return rc;
+  const int Bp = m.Bp, R = m.R, nrows = B * W, C = h->C, Cp = h->Cp;
+  const int L4 = m.Lr[LasBeam::NL - 1];
+  const float* P = h->P;
+  hipStream_t st = h->st;
+  const bool timed = h->profiling;
+  m.marks.clear();
+  size_t nev = 0;
+  auto mark = [&](int ph) {
+    if (!timed) return;
+    if (nev == m.ev.size()) (void)hipEventCreate(m.ev.emplace_back().out());
+    (void)hipEventRecord(m.ev[nev], st);
+    m.marks.push_back({ph, nev++});
+  };
+  // (5 + n)^lp / 6^lp in fp32 for every length a step can see (TF: 1 when lp is 0)
+  m.hpen.assign((size_t)max_steps + 1, 1.f);
+  if (lp != 0.f)
+    for (int n = 0; n <= max_steps; ++n) m.hpen[n] = powf(5.f + (float)n, lp) / powf(6.f, lp);
+  mark(-1);
+  HIPCHK(h, hipMemcpyAsync(m.pen.p, m.hpen.data(), m.hpen.size() * 4, hipMemcpyHostToDevice, st));
+  HIPCHK(h, hipMemsetAsync(m.flags.p, 0, 8, st));
+  HIPCHK(h, hipMemcpyAsync(m.feats.p, feats, (size_t)B * T * h->F * 4, hipMemcpyHostToDevice, st));
+  launch_pack_feats(m.feats.as<float>(), m.X0.as<float>(), B, Bp, T, h->F, h->Fp, st);
+  if (int rc = las_encode(h, m.X0.as<float>(), T, B, Bp, m.Lr, m.X, m.xp, m.act, m.c, m.out)) return rc;
+  const float* mem = fp(m.out[LasBeam::NL - 1]);
+  if (int rc = las_gemm(h, mem, P + s.off_wmem, fp(m.keys), L4 * Bp, LAS_HD, LAS_HD, LAS_HD, LAS_HD, LAS_HD, false, false))
+    return rc;
+  launch_las_beam_init(mem, fp(m.c[LasBeam::NL - 1]), L4, Bp, W, nrows, R, start_id, fp(m.S), fp(m.cs), m.ids.as<int32_t>(),
+                       fp(m.logp[0]), m.len[0].as<int32_t>(), m.fin[0].as<int32_t>(), st);
+  HIPCHK(h, hipGetLastError());
+  mark(LB_ENC);
+  const int32_t* done = m.flags.as<int32_t>();
+  int32_t hf[2] = {0, 0};
+  constexpr int CHUNK = 8;
+  for (int t = 0; t < max_steps;) {
+    for (const int end = std::min(max_steps, t + CHUNK); t < end; ++t) {
+      const int i = t & 1, o = i ^ 1;
+      const size_t tr = (size_t)t * nrows;
+      if (int rc = las_gemm(h, fp(m.S), P + s.off_wah, fp(m.gp), R, LAS_G4D, LAS_SW, LAS_SW, LAS_G4D, LAS_G4D, false, false))
+        return rc;
+      mark(LB_GEMM);
+      launch_las_dec_cell(fp(m.gp), P + s.off_e, P + s.off_bd, m.ids.as<int32_t>(), fp(m.cs), fp(m.dact), fp(m.cx), fp(m.Sx),
+                          fp(m.HC), R, st);
+      mark(LB_CELL);
+      if (int rc = las_gemm(h, fp(m.Sx) + LAS_HE, P + s.off_wq, fp(m.Q), R, LAS_HD, LAS_HD, LAS_SW, LAS_HD, LAS_HD, false, false))
+        return rc;
+      mark(LB_GEMM);
+      launch_las_beam_attend(fp(m.keys), mem, fp(m.Q), P + s.off_v, fp(m.HC), L4, Bp, W, nrows, R, done, st);
+      mark(LB_ATTN);
+      if (int rc = las_gemm(h, fp(m.HC), P + s.off_watt, fp(m.Sx), R, LAS_HE, 2 * LAS_HD, 2 * LAS_HD, LAS_HE, LAS_SW, false, false))
+        return rc;
+      if (int rc = las_gemm(h, fp(m.Sx), P + s.off_wp, fp(m.logits), R, Cp, LAS_HE, LAS_SW, Cp, Cp, false, false, P + s.off_bp))
+        return rc;
+      mark(LB_GEMM);
+      launch_las_beam_score(fp(m.logits), Cp, C, fp(m.logp[i]), m.len[i].as<int32_t>(), m.fin[i].as<int32_t>(), fp(m.pen), end_id,
+                            nrows, fp(m.scores), fp(m.totals), done, st);
+      launch_las_beam_select(fp(m.scores), B, W, C, m.sel_idx.as<int32_t>(), fp(m.sel_score), done, st);
+      launch_las_beam_update(m.sel_idx.as<int32_t>(), fp(m.sel_score), fp(m.totals), W, C, end_id, nrows, fp(m.Sx), fp(m.cx),
+                             m.len[i].as<int32_t>(), m.fin[i].as<int32_t>(), fp(m.S), fp(m.cs), m.ids.as<int32_t>(),
+                             fp(m.logp[o]), m.len[o].as<int32_t>(), m.fin[o].as<int32_t>(), fp(m.tr_score) + tr,
+                             m.tr_word.as<int32_t>() + tr, m.tr_parent.as<int32_t>() + tr, done, st);
+      launch_las_beam_finish(m.fin[o].as<int32_t>(), nrows, t, max_steps, m.flags.as<int32_t>(), st);
+      HIPCHK(h, hipGetLastError());
+      mark(LB_SEL);
+    }
+    HIPCHK(h, hipMemcpyAsync(hf, m.flags.p, 8, hipMemcpyDeviceToHost, st));
+    if (int rc = sync_checked(h)) return rc;
+    mark(LB_WAIT);
+    if (hf[0]) break;
+  }
+  m.Tdec = hf[1];
+  m.end_id = end_id;
+  if (m.Tdec < 1 || m.Tdec > max_steps) return h->fail(NASR_ERR_HIP, "las beam search: the device's step count is out of range");
+  launch_las_beam_gather_tree(m.tr_word.as<int32_t>(), m.tr_parent.as<int32_t>(), m.len[m.Tdec & 1].as<int32_t>(), m.Tdec, B, W,
+                              end_id, m.gathered.as<int32_t>(), st);
+  HIPCHK(h, hipGetLastError());
+  mark(LB_TREE);
+  if (int rc = sync_checked(h)) return rc;
+  m.timed = timed;
+  if (timed) {
+    for (float& x : m.times) x = 0.f;
+    for (size_t k = 1; k < m.marks.size(); ++k) {
+      float ms = 0.f;
+      HIPCHK(h, hipEventElapsedTime(&ms, m.ev[m.marks[k - 1].second], m.ev[m.marks[k].second]));
+      m.times[m.marks[k].first] += ms;
+    }
+  }
+  m.have = true;
   return NASR_OK;
 }
 
@@ -527,6 +697,93 @@ int nasr_las_get_sampled(nasr_handle h, int32_t* sampled_out) {
   if (!sampled_out) return h->fail(NASR_ERR_ARG, "nasr_las_get_sampled: null output");
   if (!s->have_pass) return h->fail(NASR_ERR_STATE, "nasr_las_get_sampled: no decoder pass has run");
   return las_read_bu(h, s->sampled, 1, 1, 4, sampled_out);
+}
+
+int nasr_las_beam_search(nasr_handle h, const float* feats, const int32_t* seq_len, int B, int T, int beam_width, int max_steps,
+                         int start_id, int end_id, float length_penalty, int32_t* steps_out) {
+  LasState* s = las_of(h);
+  if (!s) return h ? h->fail(NASR_ERR_STATE, "nasr_las_beam_search: not a LAS handle") : NASR_ERR_ARG;
+  if (!feats || !seq_len) return h->fail(NASR_ERR_ARG, "nasr_las_beam_search: null input buffer");
+  if (B < 1 || B > 64 || T < 1) return h->fail(NASR_ERR_ARG, "nasr_las_beam_search: B must be in [1,64] and T >= 1");
+  for (int b = 0; b < B; ++b)
+    if (seq_len[b] < 1 || seq_len[b] > T)
+      return h->fail(NASR_ERR_ARG, "nasr_las_beam_search: seq_len[" + std::to_string(b) + "] out of [1,T]");
+  if (beam_width < 1 || beam_width > 1024) return h->fail(NASR_ERR_ARG, "nasr_las_beam_search: beam_width must be in [1,1024]");
+  if (max_steps < 1 || max_steps > 1000) return h->fail(NASR_ERR_ARG, "nasr_las_beam_search: max_steps must be in [1,1000]");
+  if (start_id < 0 || start_id >= h->C || end_id < 0 || end_id >= h->C)
+    return h->fail(NASR_ERR_ARG, "nasr_las_beam_search: start_id and end_id must be in [0, num_classes-1]");
+  if (!(length_penalty >= 0.f) || !std::isfinite(length_penalty))
+    return h->fail(NASR_ERR_ARG, "nasr_las_beam_search: length_penalty must be finite and >= 0");
+  HIPCHK(h, hipSetDevice(h->device));
+  const int rc = las_beam_search(h, feats, B, T, beam_width, max_steps, start_id, end_id, length_penalty);
+  if (rc) return rc;
+  if (steps_out) *steps_out = s->beam->Tdec;
+  return NASR_OK;
+}
+
+namespace {
+LasBeam* beam_of(nasr_handle h, const char* fn, int* rc) {
+  LasState* s = las_of(h);
+  *rc = NASR_OK;
+  if (!s) *rc = h ? h->fail(NASR_ERR_STATE, std::string(fn) + ": not a LAS handle") : NASR_ERR_ARG;
+  else if (!s->beam || !s->beam->have) *rc = h->fail(NASR_ERR_STATE, std::string(fn) + ": no beam search has run");
+  return *rc ? nullptr : s->beam.get();
+}
+// [Tdec][B*W] read back and reordered to [B][Tdec][W]
+int beam_read_tbw(nasr_ctx* h, const LasBeam& m, const DevBuf& src, void* dst) {
+  const int B = m.B, W = m.W, Td = m.Tdec, n = B * W;
+  std::vector<int32_t> tmp((size_t)Td * n);
+  HIPCHK(h, hipMemcpyAsync(tmp.data(), src.p, tmp.size() * 4, hipMemcpyDeviceToHost, h->st));
+  if (int rc = sync_checked(h)) return rc;
+  int32_t* d = static_cast<int32_t*>(dst);
+  for (int b = 0; b < B; ++b)
+    for (int t = 0; t < Td; ++t) memcpy(d + ((size_t)b * Td + t) * W, tmp.data() + (size_t)t * n + (size_t)b * W, (size_t)W * 4);
+  return NASR_OK;
+}
+int beam_read(nasr_ctx* h, const DevBuf& src, size_t n, void* dst) {
+  HIPCHK(h, hipMemcpyAsync(dst, src.p, n * 4, hipMemcpyDeviceToHost, h->st));
+  return sync_checked(h);
+}
+}  // namespace
+
+int nasr_las_beam_get_ids(nasr_handle h, int32_t* ids_out) {
+  int rc;
+  LasBeam* m = beam_of(h, "nasr_las_beam_get_ids", &rc);
+  if (!m) return rc;
+  if (!ids_out) return h->fail(NASR_ERR_ARG, "nasr_las_beam_get_ids: null output");
+  return beam_read_tbw(h, *m, m->gathered, ids_out);
+}
+
+int nasr_las_beam_get_trace(nasr_handle h, float* scores_out, int32_t* word_out, int32_t* parent_out) {
+  int rc;
+  LasBeam* m = beam_of(h, "nasr_las_beam_get_trace", &rc);
+  if (!m) return rc;
+  if (scores_out && (rc = beam_read_tbw(h, *m, m->tr_score, scores_out))) return rc;
+  if (word_out && (rc = beam_read_tbw(h, *m, m->tr_word, word_out))) return rc;
+  if (parent_out && (rc = beam_read_tbw(h, *m, m->tr_parent, parent_out))) return rc;
+  return NASR_OK;
+}
+
+int nasr_las_beam_get_final(nasr_handle h, float* log_probs_out, int32_t* lengths_out, int32_t* finished_out) {
+  int rc;
+  LasBeam* m = beam_of(h, "nasr_las_beam_get_final", &rc);
+  if (!m) return rc;
+  const int f = m->Tdec & 1;
+  const size_t n = (size_t)m->B * m->W;
+  if (log_probs_out && (rc = beam_read(h, m->logp[f], n, log_probs_out))) return rc;
+  if (lengths_out && (rc = beam_read(h, m->len[f], n, lengths_out))) return rc;
+  if (finished_out && (rc = beam_read(h, m->fin[f], n, finished_out))) return rc;
+  return NASR_OK;
+}
+
+int nasr_las_beam_get_times(nasr_handle h, float* ms_out) {
+  int rc;
+  LasBeam* m = beam_of(h, "nasr_las_beam_get_times", &rc);
+  if (!m) return rc;
+  if (!ms_out) return h->fail(NASR_ERR_ARG, "nasr_las_beam_get_times: null output");
+  if (!m->timed) return h->fail(NASR_ERR_STATE, "nasr_las_beam_get_times: the last search ran with profiling off");
+  memcpy(ms_out, m->times, sizeof(m->times));
+  return NASR_OK;
 }
 
 }  // extern "C"

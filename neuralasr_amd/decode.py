@@ -25,7 +25,7 @@ def decode(dataTest, config):
         spent += time.time() - t0
         loss_sum += loss
         ler_sum += ler
-        logger.info('Decoded: ' + config.symbols.convert_to_str(np.asarray(output)))
+        logger.info('Decoded: ' + config.symbols.convert_to_str(np.asarray(output).ravel()))
         logger.info('Original: ' + config.symbols.convert_to_str(np.asarray(labels[0])))
     logger.info('Finished Decoding!!!')
     logger.info('Decoded Time = %.4fs, avg_loss = %.4f, avg_ler = %.4f' % (spent, loss_sum / steps, ler_sum / steps))

@@ -619,3 +619,37 @@ class LasEngine(Engine):
     def set_sampling_state(self, p, seed, counter, tower=0):
         self._ck(self.lib.nasr_las_set_sampling(self.h, float(p), int(seed) & 0xFFFFFFFF, int(counter) & 0xFFFFFFFF,
                                                 int(tower)))
+
+    def beam_search(self, feats, seq_len, beam_width, max_steps, start_id, end_id, length_penalty=0.5, trace=False):
+        """The reference's inference graph (include/nasr.h: nasr_las_beam_search): {'steps': T_dec, 'predicted_ids':
+        gather_tree's ids [B, T_dec, W]}, and with trace also every step's 'scores', 'word_ids', 'parent_ids'
+        [B, T_dec, W] and the final 'log_probs', 'lengths', 'finished' [B, W]."""
+        feats, seq, _, _, B, T, _ = self._batch(feats, seq_len)
+        if feats.shape[2] != self.cfg.feature_size:
+            raise ValueError(f'feature size {feats.shape[2]} != configured {self.cfg.feature_size}')
+        W = int(beam_width)
+        steps = c_int32()
+        self._ck(self.lib.nasr_las_beam_search(self.h, _fp(feats), _ip(seq), B, T, W, int(max_steps), int(start_id),
+                                               int(end_id), float(length_penalty), byref(steps)))
+        Td = steps.value
+        out = {'steps': Td, 'predicted_ids': np.empty((B, Td, W), np.int32)}
+        self._ck(self.lib.nasr_las_beam_get_ids(self.h, _ip(out['predicted_ids'])))
+        if trace:
+            out['scores'] = np.empty((B, Td, W), np.float32)
+            out['word_ids'] = np.empty((B, Td, W), np.int32)
+            out['parent_ids'] = np.empty((B, Td, W), np.int32)
+            self._ck(self.lib.nasr_las_beam_get_trace(self.h, _fp(out['scores']), _ip(out['word_ids']),
+                                                      _ip(out['parent_ids'])))
+            out['log_probs'] = np.empty((B, W), np.float32)
+            out['lengths'] = np.empty((B, W), np.int32)
+            fin = np.empty((B, W), np.int32)
+            self._ck(self.lib.nasr_las_beam_get_final(self.h, _fp(out['log_probs']), _ip(out['lengths']), _ip(fin)))
+            out['finished'] = fin != 0
+        return out
+
+    def beam_times(self):
+        """device-timed ms of the last search's phases (it must have run with profiling on: set_profiling(True))"""
+        ms = (c_float * 7)()
+        self._ck(self.lib.nasr_las_beam_get_times(self.h, ms))
+        names = ('encoder', 'decoder_gemm', 'decoder_cell', 'attention', 'selection', 'gather_tree', 'host_wait')
+        return dict(zip(names, (float(x) for x in ms)))

@@ -9,8 +9,13 @@ train() / validate() run the training graph (sampling on, as the reference's val
 sequence_mask against the labels, both with id 0 dropped (dense_to_sparse).  With num_gpus > 1 every tower computes its own
 sequence_loss and the gradients are averaged (time-sliced in one process, or one process per GPU); every tower of a step
 draws with the step's sampling counter and keys its samples by its tower index, and the counter advances once per step,
-so both layouts feed the same inputs and end with the same counter.  Checkpoints carry the sampling state (las_sampling) beside the variables.  The beam-search decoder of the
-reference's inference graph is not implemented yet: decode() and evaluate() raise."""
+so both layouts feed the same inputs and end with the same counter.  Checkpoints carry the sampling state (las_sampling) beside the variables.
+
+decode() / evaluate() run the reference's inference graph on the GPU (LasEngine.beam_search): BeamSearchDecoder of TF 1.15
+with beam_width 1000, maximum_iterations 100 and length_penalty_weight 0.5, starting from start_marker and ending at
+end_marker, then gather_tree; the model is beam 0 of the gathered ids [B, T_dec].  evaluate()'s loss is the reference's
+sequence_loss over the step scores [B, T_dec, W] taken as logits; its graph cannot build unless T_dec == U, so here it is
+NaN then (beam_sequence_loss)."""
 import numpy as np
 
 from ..engine import LasEngine
@@ -69,6 +74,26 @@ def label_error_rate(model, labels):
     return float(np.mean(lers))
 
 
+def beam_sequence_loss(scores, labels, labels_len):
+    """sequence_loss(scores, labels, sequence_mask(labels_len, U)) of the reference's evaluate graph, with the step scores
+    [B, T_dec, W] as logits over W classes, evaluated literally in float32 (inf and NaN as they come): per entry
+    logsumexp(scores) - scores[label], times the mask, summed / (sum of the mask + 1e-12).  TF's graph only builds when
+    T_dec == U, and a label id must be a class (< W): NaN otherwise."""
+    scores = np.asarray(scores, np.float32)
+    labels = np.asarray(labels, np.int64)
+    B, Td, W = scores.shape
+    U = labels.shape[1]
+    if Td != U or (labels.size and (labels.min() < 0 or labels.max() >= W)):
+        return np.float32(np.nan)
+    w = (np.arange(U)[None, :] < np.asarray(labels_len)[:, None]).astype(np.float32)
+    with np.errstate(all='ignore'):
+        m = scores.max(axis=2, keepdims=True)
+        lse = (np.log(np.exp(scores - m).sum(axis=2, dtype=np.float32)) + m[:, :, 0]).astype(np.float32)
+        picked = np.take_along_axis(scores, labels[:, :, None], axis=2)[:, :, 0]
+        ce = (lse - picked) * w
+        return np.float32(ce.sum(dtype=np.float32) / np.float32(w.sum(dtype=np.float32) + np.float32(1e-12)))
+
+
 def model_ids(logits, labels_len):
     """argmax(logits) x sequence_mask(labels_len, U)"""
     U = logits.shape[1]
@@ -83,6 +108,10 @@ class LAS(HipNetwork):
     merge = 'none'
     sampling_probability = 0.1
     sampling_seed = 1
+    # the inference graph (networks/las.py, fortraining=False)
+    beam_width = 1000
+    max_decode_steps = 100
+    length_penalty_weight = 0.5
 
     def make_engine(self, config, device, stream):
         e = LasEngine(config.feature_size, self.num_classes, num_hidden=self.num_hidden, num_layers=self.num_layers,
@@ -201,10 +230,20 @@ class LAS(HipNetwork):
                              '(preprocess_mfcc writes them into the labels)')
         return self.config.symbols.get_id(start), self.config.symbols.get_id(end)
 
+    def _beam_search(self, mfccs, seq_len, trace):
+        start, end = self._markers()
+        return self.engine.beam_search(mfccs, seq_len, self.beam_width, self.max_decode_steps, start, end,
+                                       self.length_penalty_weight, trace=trace)
+
     def evaluate(self, mfccs, labels, seq_len, labels_len):
-        self._markers()
-        raise NotImplementedError('LAS: the beam-search decoder of the inference graph is not implemented yet')
+        """[model [B, T_dec], loss, ler]: beam 0 of the gathered ids, beam_sequence_loss of the step scores, and the LER of
+        the model against the labels (id 0 dropped from both; the end marker stays in the hypothesis)"""
+        out = self._beam_search(mfccs, seq_len, True)
+        model = out['predicted_ids'][:, :, 0].astype(np.int64)
+        loss = beam_sequence_loss(out['scores'], labels, labels_len)
+        return [model, np.float32(loss), np.float32(label_error_rate(model, labels))]
 
     def decode(self, mfccs, seq_len):
-        self._markers()
-        raise NotImplementedError('LAS: the beam-search decoder of the inference graph is not implemented yet')
+        """the first utterance's model: beam 0 of the gathered ids [T_dec]"""
+        out = self._beam_search(mfccs, seq_len, False)
+        return out['predicted_ids'][0, :, 0].astype(np.int64)
