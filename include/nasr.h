@@ -446,8 +446,32 @@ int nasr_mfcc_filterbank(const nasr_mfcc_cfg* cfg, int32_t* bins, float* weights
  * stacked matrix, zero pads included.  Returns when out is written (utils.py:24-31 for every utterance). */
 int nasr_featurize(nasr_handle h, const float* audio, const int64_t* offsets, int n, float* out, int64_t out_rows,
                    double* mean_std);
-/* The last nasr_featurize's device-timed phases: host-to-device copies, kernels, device-to-host copies (ms). */
+/* The last nasr_featurize's, nasr_featurize_rates' or nasr_resample's device-timed phases: host-to-device copies,
+ * kernels (the resampling kernel included), device-to-host copies (ms). */
 int nasr_featurize_times(nasr_handle h, float* h2d_ms, float* kernel_ms, float* d2h_ms);
+
+/* ---- resampling to the config rate (utils.py:25: librosa.load(wavfile, mono=True, sr=sr)) -------
+ * librosa 0.6-0.9's resample(y, rate, sr, res_type='kaiser_best'): resampy 0.2 then fix_length.  ratio = sr / rate
+ * in float64; resampy makes int(n * ratio) samples (none: it raises) by band-limited sinc interpolation (64 zero
+ * crossings, 512 table entries per crossing, Kaiser window, the table scaled by ratio when ratio < 1) on its
+ * sequential float64 time register, summing each output in float32 after every tap; librosa zero-pads them to
+ * ceil(n * ratio).  An utterance already at sr is left as it is. */
+/* Host only (utils.py:25): resampy's kaiser_best half window, float64 [len], len = 32769. */
+int nasr_resample_filter(double* table, int64_t len);
+/* Host only (utils.py:25): librosa's length ceil(n * ratio) of n >= 1 samples at in_rate resampled to out_rate, and
+ * resampy's filtered length int(n * ratio) in *filtered (nullable); < 0 on a rate <= 0, n < 1, or when resampy would
+ * raise (int(n * ratio) < 1). */
+int64_t nasr_resample_length(int32_t in_rate, int32_t out_rate, int64_t n, int64_t* filtered);
+/* (utils.py:25) Utterance i, audio[offsets[i] .. offsets[i+1]) at rates[i] Hz, resampled to the featurizer's
+ * samplerate; out [out_len] receives the utterances' nasr_resample_length samples one after another.  NASR_ERR_ARG,
+ * naming the utterance, on a rate <= 0 or an utterance too short; NASR_ERR_STATE on a model handle. */
+int nasr_resample(nasr_handle h, const float* audio, const int64_t* offsets, const int32_t* rates, int n, float* out,
+                  int64_t out_len);
+/* (utils.py:24-31 after utils.py:25's resampling) nasr_featurize of the utterances resampled as nasr_resample does,
+ * on the device: the resampled samples never leave it.  out_rows is the sum of the nasr_mfcc_frames of their
+ * resampled lengths.  Utterances at the samplerate give bitwise what nasr_featurize gives them. */
+int nasr_featurize_rates(nasr_handle h, const float* audio, const int64_t* offsets, const int32_t* rates, int n,
+                         float* out, int64_t out_rows, double* mean_std);
 
 #ifdef __cplusplus
 }

@@ -38,6 +38,7 @@ SYMBOLS = [
     'nasr_las_get_fed_ids', 'nasr_las_get_sampled', 'nasr_las_beam_search', 'nasr_las_beam_get_ids',
     'nasr_las_beam_get_trace', 'nasr_las_beam_get_final', 'nasr_las_beam_get_times',
     'nasr_create_featurizer', 'nasr_mfcc_frames', 'nasr_mfcc_filterbank', 'nasr_featurize', 'nasr_featurize_times',
+    'nasr_resample_filter', 'nasr_resample_length', 'nasr_resample', 'nasr_featurize_rates',
 ]
 
 
@@ -192,6 +193,10 @@ def load():
         'nasr_mfcc_filterbank': (c_int, [POINTER(MfccCfg), ip, fp]),
         'nasr_featurize': (c_int, [H, fp, POINTER(c_int64), c_int, fp, c_int64, POINTER(c_double)]),
         'nasr_featurize_times': (c_int, [H, fp, fp, fp]),
+        'nasr_resample_filter': (c_int, [POINTER(c_double), c_int64]),
+        'nasr_resample_length': (c_int64, [c_int32, c_int32, c_int64, POINTER(c_int64)]),
+        'nasr_resample': (c_int, [H, fp, POINTER(c_int64), ip, c_int, fp, c_int64]),
+        'nasr_featurize_rates': (c_int, [H, fp, POINTER(c_int64), ip, c_int, fp, c_int64, POINTER(c_double)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

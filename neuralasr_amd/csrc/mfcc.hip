@@ -9,7 +9,10 @@
 //                         frames (each counted once per window that holds it, the zero pads as a count), then the
 //                         normalised rows written straight into the stacked layout
 // Tables (twiddles, filter weights, the DCT x lifter matrix) are built once per handle on the host in double.
+// nasr_featurize_rates first resamples utterances at other rates to the config rate (resample.hip) into a device
+// buffer, which the same two kernels then read.
 #include "nasr_ctx.h"
+#include "resample.h"
 
 using namespace nasr;
 using namespace nasr_impl;
@@ -271,6 +274,9 @@ struct FzState {
   DevPtr<double> fb_w, dct;
   DevBuf audio, meta, cep, out, mstd;
   std::vector<char> hmeta;
+  DevPtr<double2> rs_tab;              // the resampling filter's (table[k], table[k+1]) pairs, made at the first use
+  DevBuf raud, rmeta;                  // resampled audio; the resampling plan (RsUtt [n], then RsWave [waves])
+  std::vector<char> hrmeta;
   Event ev[4];
   float times[3] = {0.f, 0.f, 0.f};
 };
@@ -278,6 +284,115 @@ struct FzState {
 }  // namespace nasr_impl
 
 void nasr_impl::FzStateDelete::operator()(FzState* f) const { delete f; }
+
+namespace {
+
+const RsWave* rs_waves(FzState& z, int n) {
+  return reinterpret_cast<const RsWave*>(z.rmeta.as<char>() + (size_t)n * sizeof(RsUtt));
+}
+
+// the filter table (once per handle), the plan's host image and the device buffers of a resampling launch
+int resample_prepare(nasr_ctx* h, FzState& z, const ResamplePlan& plan, int64_t in_samples) {
+  if (!z.rs_tab) {
+    const std::vector<double2> pairs = resample_table_pairs();
+    HIPCHK(h, hipMalloc(z.rs_tab.out(), pairs.size() * sizeof(double2)));
+    HIPCHK(h, hipMemcpy(z.rs_tab.get(), pairs.data(), pairs.size() * sizeof(double2), hipMemcpyHostToDevice));
+  }
+  const size_t ub = plan.utt.size() * sizeof(RsUtt), wb = plan.waves.size() * sizeof(RsWave);
+  z.hrmeta.resize(ub + wb);
+  memcpy(z.hrmeta.data(), plan.utt.data(), ub);
+  memcpy(z.hrmeta.data() + ub, plan.waves.data(), wb);
+  if (!z.audio.ensure((size_t)in_samples * 4, nullptr) || !z.raud.ensure((size_t)plan.total * 4, nullptr) ||
+      !z.rmeta.ensure(z.hrmeta.size(), nullptr))
+    return h->fail(NASR_ERR_HIP, "resampling: device buffers for " + std::to_string(in_samples) + " + " +
+                                     std::to_string(plan.total) + " samples could not be allocated");
+  return NASR_OK;
+}
+
+// wait for the stream; the device-timed phases between the four events
+int finish(nasr_ctx* h, FzState& z) {
+  if (int rc = sync_checked(h)) return rc;
+  for (int i = 0; i < 3; ++i)
+    if (hipEventElapsedTime(&z.times[i], z.ev[i], z.ev[i + 1]) != hipSuccess) z.times[i] = 0.f;
+  return NASR_OK;
+}
+
+// The features of n utterances.  rates == nullptr (nasr_featurize): every utterance is at the config rate.  Otherwise
+// an utterance at another rate is resampled to it first, into z.raud, which the MFCC kernels then read.
+int featurize(nasr_handle h, const std::string& fn, const float* audio, const int64_t* offsets, const int32_t* rates,
+              int n, float* out, int64_t out_rows, double* mean_std) {
+  if (!h) return NASR_ERR_ARG;
+  FzState* zp = h->fz.get();
+  if (!zp) return h->fail(NASR_ERR_STATE, fn + ": not a featurizer handle");
+  FzState& z = *zp;
+  if (!audio || !offsets || !out || n < 1) return h->fail(NASR_ERR_ARG, fn + ": null buffer or n < 1");
+  ResamplePlan plan;
+  bool rs = false;
+  if (rates) {
+    std::string why;
+    if (!resample_plan(offsets, rates, n, z.cfg.samplerate, &plan, &why)) return h->fail(NASR_ERR_ARG, fn + ": " + why);
+    for (const RsUtt& u : plan.utt) rs = rs || u.step != 0;
+  }
+  // frame offsets and the frame -> utterance map, on the host
+  const size_t mb = (size_t)(n + 1) * 8;
+  std::vector<int64_t> uoff(n + 1), foff(n + 1);
+  foff[0] = 0;
+  for (int i = 0; i < n; ++i) {
+    const int64_t len = rs ? plan.utt[i].n_samples : offsets[i + 1] - offsets[i];
+    if (len < 1) return h->fail(NASR_ERR_ARG, fn + ": utterance " + std::to_string(i) + " has no samples");
+    uoff[i] = rs ? plan.utt[i].out_off : offsets[i] - offsets[0];
+    foff[i + 1] = foff[i] + frames_of(z.d.frame_len, z.d.frame_step, len);
+  }
+  const int64_t S_in = offsets[n] - offsets[0];
+  uoff[n] = rs ? plan.total : S_in;
+  const int64_t F = foff[n], S = uoff[n];
+  if (out_rows != F)
+    return h->fail(NASR_ERR_ARG, fn + ": out_rows is " + std::to_string(out_rows) + ", the utterances have " +
+                                     std::to_string(F) + " frames");
+  z.hmeta.resize(2 * mb + (size_t)F * 4);
+  memcpy(z.hmeta.data(), uoff.data(), mb);
+  memcpy(z.hmeta.data() + mb, foff.data(), mb);
+  int* fmap = reinterpret_cast<int*>(z.hmeta.data() + 2 * mb);
+  for (int i = 0; i < n; ++i)
+    for (int64_t f = foff[i]; f < foff[i + 1]; ++f) fmap[f] = i;
+  const size_t rowlen = (size_t)z.W * z.d.numcep;
+  HIPCHK(h, hipSetDevice(h->device));
+  if (rs) {
+    if (int rc = resample_prepare(h, z, plan, S_in)) return rc;
+  }
+  if (!z.audio.ensure((size_t)S_in * 4, nullptr) || !z.meta.ensure(z.hmeta.size(), nullptr) ||
+      !z.cep.ensure((size_t)F * z.d.numcep * 8, nullptr) || !z.out.ensure((size_t)F * rowlen * 4, nullptr) ||
+      !z.mstd.ensure((size_t)n * 16, nullptr))
+    return h->fail(NASR_ERR_HIP, fn + ": device buffers for " + std::to_string(S) + " samples could not be allocated");
+  const int64_t* d_uoff = z.meta.as<int64_t>();
+  const int64_t* d_foff = d_uoff + (n + 1);
+  const int* d_fmap = reinterpret_cast<const int*>(z.meta.as<char>() + 2 * mb);
+  HIPCHK(h, hipEventRecord(z.ev[0], h->st));
+  HIPCHK(h, hipMemcpyAsync(z.audio.p, audio + offsets[0], (size_t)S_in * 4, hipMemcpyHostToDevice, h->st));
+  HIPCHK(h, hipMemcpyAsync(z.meta.p, z.hmeta.data(), z.hmeta.size(), hipMemcpyHostToDevice, h->st));
+  if (rs) HIPCHK(h, hipMemcpyAsync(z.rmeta.p, z.hrmeta.data(), z.hrmeta.size(), hipMemcpyHostToDevice, h->st));
+  HIPCHK(h, hipEventRecord(z.ev[1], h->st));
+  if (rs) {
+    launch_resample(z.audio.as<float>(), z.rmeta.as<RsUtt>(), rs_waves(z, n), (int64_t)plan.waves.size(), z.rs_tab,
+                    z.raud.as<float>(), h->st);
+    HIPCHK(h, hipGetLastError());
+  }
+  const int64_t nblk = (F + SPEC_WAVES - 1) / SPEC_WAVES;
+  mfcc_spectral_kernel<<<dim3((unsigned)nblk), dim3(64 * SPEC_WAVES), 0, h->st>>>(
+      rs ? z.raud.as<float>() : z.audio.as<float>(), d_uoff, d_foff, d_fmap, F, z.tw, z.tw2, z.fb_lo, z.fb_n,
+      z.fb_off, z.fb_w, z.dct, z.d, z.cep.as<double>());
+  HIPCHK(h, hipGetLastError());
+  mfcc_norm_kernel<<<dim3(n), dim3(NORM_THREADS), 0, h->st>>>(z.cep.as<double>(), d_foff, z.d.numcep, z.d.nc,
+                                                             z.out.as<float>(), z.mstd.as<double>());
+  HIPCHK(h, hipGetLastError());
+  HIPCHK(h, hipEventRecord(z.ev[2], h->st));
+  HIPCHK(h, hipMemcpyAsync(out, z.out.p, (size_t)F * rowlen * 4, hipMemcpyDeviceToHost, h->st));
+  if (mean_std) HIPCHK(h, hipMemcpyAsync(mean_std, z.mstd.p, (size_t)n * 16, hipMemcpyDeviceToHost, h->st));
+  HIPCHK(h, hipEventRecord(z.ev[3], h->st));
+  return finish(h, z);
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -396,61 +511,42 @@ int nasr_create_featurizer(const nasr_mfcc_cfg* cfg, int device_id, void* stream
 
 int nasr_featurize(nasr_handle h, const float* audio, const int64_t* offsets, int n, float* out, int64_t out_rows,
                    double* mean_std) {
+  return featurize(h, "nasr_featurize", audio, offsets, nullptr, n, out, out_rows, mean_std);
+}
+
+int nasr_featurize_rates(nasr_handle h, const float* audio, const int64_t* offsets, const int32_t* rates, int n,
+                         float* out, int64_t out_rows, double* mean_std) {
+  if (h && h->fz && !rates) return h->fail(NASR_ERR_ARG, "nasr_featurize_rates: null rates");
+  return featurize(h, "nasr_featurize_rates", audio, offsets, rates, n, out, out_rows, mean_std);
+}
+
+int nasr_resample(nasr_handle h, const float* audio, const int64_t* offsets, const int32_t* rates, int n, float* out,
+                  int64_t out_len) {
   if (!h) return NASR_ERR_ARG;
   FzState* zp = h->fz.get();
-  if (!zp) return h->fail(NASR_ERR_STATE, "nasr_featurize: not a featurizer handle");
+  if (!zp) return h->fail(NASR_ERR_STATE, "nasr_resample: not a featurizer handle");
   FzState& z = *zp;
-  if (!audio || !offsets || !out || n < 1) return h->fail(NASR_ERR_ARG, "nasr_featurize: null buffer or n < 1");
-  // frame offsets and the frame -> utterance map, on the host
-  const size_t mb = (size_t)(n + 1) * 8;
-  std::vector<int64_t> uoff(n + 1), foff(n + 1);
-  foff[0] = 0;
-  for (int i = 0; i < n; ++i) {
-    const int64_t len = offsets[i + 1] - offsets[i];
-    if (len < 1) return h->fail(NASR_ERR_ARG, "nasr_featurize: utterance " + std::to_string(i) + " has no samples");
-    uoff[i] = offsets[i] - offsets[0];
-    foff[i + 1] = foff[i] + frames_of(z.d.frame_len, z.d.frame_step, len);
-  }
-  uoff[n] = offsets[n] - offsets[0];
-  const int64_t F = foff[n], S = uoff[n];
-  if (out_rows != F)
-    return h->fail(NASR_ERR_ARG, "nasr_featurize: out_rows is " + std::to_string(out_rows) + ", the utterances have " +
-                                     std::to_string(F) + " frames");
-  z.hmeta.resize(2 * mb + (size_t)F * 4);
-  memcpy(z.hmeta.data(), uoff.data(), mb);
-  memcpy(z.hmeta.data() + mb, foff.data(), mb);
-  int* fmap = reinterpret_cast<int*>(z.hmeta.data() + 2 * mb);
-  for (int i = 0; i < n; ++i)
-    for (int64_t f = foff[i]; f < foff[i + 1]; ++f) fmap[f] = i;
-  const size_t rowlen = (size_t)z.W * z.d.numcep;
+  if (!audio || !offsets || !rates || !out || n < 1) return h->fail(NASR_ERR_ARG, "nasr_resample: null buffer or n < 1");
+  ResamplePlan plan;
+  std::string why;
+  if (!resample_plan(offsets, rates, n, z.cfg.samplerate, &plan, &why)) return h->fail(NASR_ERR_ARG, "nasr_resample: " + why);
+  if (out_len != plan.total)
+    return h->fail(NASR_ERR_ARG, "nasr_resample: out_len is " + std::to_string(out_len) + ", the utterances resample to " +
+                                     std::to_string(plan.total) + " samples");
+  const int64_t S = offsets[n] - offsets[0];
   HIPCHK(h, hipSetDevice(h->device));
-  if (!z.audio.ensure((size_t)S * 4, nullptr) || !z.meta.ensure(z.hmeta.size(), nullptr) ||
-      !z.cep.ensure((size_t)F * z.d.numcep * 8, nullptr) || !z.out.ensure((size_t)F * rowlen * 4, nullptr) ||
-      !z.mstd.ensure((size_t)n * 16, nullptr))
-    return h->fail(NASR_ERR_HIP, "nasr_featurize: device buffers for " + std::to_string(S) + " samples could not be allocated");
-  const int64_t* d_uoff = z.meta.as<int64_t>();
-  const int64_t* d_foff = d_uoff + (n + 1);
-  const int* d_fmap = reinterpret_cast<const int*>(z.meta.as<char>() + 2 * mb);
+  if (int rc = resample_prepare(h, z, plan, S)) return rc;
   HIPCHK(h, hipEventRecord(z.ev[0], h->st));
   HIPCHK(h, hipMemcpyAsync(z.audio.p, audio + offsets[0], (size_t)S * 4, hipMemcpyHostToDevice, h->st));
-  HIPCHK(h, hipMemcpyAsync(z.meta.p, z.hmeta.data(), z.hmeta.size(), hipMemcpyHostToDevice, h->st));
+  HIPCHK(h, hipMemcpyAsync(z.rmeta.p, z.hrmeta.data(), z.hrmeta.size(), hipMemcpyHostToDevice, h->st));
   HIPCHK(h, hipEventRecord(z.ev[1], h->st));
-  const int64_t nblk = (F + SPEC_WAVES - 1) / SPEC_WAVES;
-  mfcc_spectral_kernel<<<dim3((unsigned)nblk), dim3(64 * SPEC_WAVES), 0, h->st>>>(
-      z.audio.as<float>(), d_uoff, d_foff, d_fmap, F, z.tw, z.tw2, z.fb_lo, z.fb_n, z.fb_off, z.fb_w, z.dct, z.d,
-      z.cep.as<double>());
-  HIPCHK(h, hipGetLastError());
-  mfcc_norm_kernel<<<dim3(n), dim3(NORM_THREADS), 0, h->st>>>(z.cep.as<double>(), d_foff, z.d.numcep, z.d.nc,
-                                                             z.out.as<float>(), z.mstd.as<double>());
+  launch_resample(z.audio.as<float>(), z.rmeta.as<RsUtt>(), rs_waves(z, n), (int64_t)plan.waves.size(), z.rs_tab,
+                  z.raud.as<float>(), h->st);
   HIPCHK(h, hipGetLastError());
   HIPCHK(h, hipEventRecord(z.ev[2], h->st));
-  HIPCHK(h, hipMemcpyAsync(out, z.out.p, (size_t)F * rowlen * 4, hipMemcpyDeviceToHost, h->st));
-  if (mean_std) HIPCHK(h, hipMemcpyAsync(mean_std, z.mstd.p, (size_t)n * 16, hipMemcpyDeviceToHost, h->st));
+  HIPCHK(h, hipMemcpyAsync(out, z.raud.p, (size_t)plan.total * 4, hipMemcpyDeviceToHost, h->st));
   HIPCHK(h, hipEventRecord(z.ev[3], h->st));
-  if (int rc = sync_checked(h)) return rc;
-  for (int i = 0; i < 3; ++i)
-    if (hipEventElapsedTime(&z.times[i], z.ev[i], z.ev[i + 1]) != hipSuccess) z.times[i] = 0.f;
-  return NASR_OK;
+  return finish(h, z);
 }
 
 int nasr_featurize_times(nasr_handle h, float* h2d_ms, float* kernel_ms, float* d2h_ms) {

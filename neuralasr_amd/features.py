@@ -1,9 +1,13 @@
 """The MFCC front end (reference: utils.py:24-31, convert_to_mfcc): WAV reading and the GPU featurizer.
 
 read_wav returns what librosa.load(path, sr, mono=True) returns for a file already at `sr`: float32 samples scaled the
-way libsndfile scales them, channels averaged in float32.  Resampling is not done: a file at another rate is an error.
+way libsndfile scales them, channels averaged in float32; a file at another rate is an error there.  read_wav_native
+returns the same samples and the file's own rate, and Featurizer resamples them on the GPU
+(neuralasr_amd/csrc/resample.hip) as librosa 0.6-0.9's resample(res_type='kaiser_best') does: resampy 0.2's sinc
+interpolation, then fix_length to ceil(n * sr / rate) samples.
 Featurizer runs python_speech_features 0.6's mfcc(nfilt=128), include_context and the whole-utterance normalisation on
-the GPU (neuralasr_amd/csrc/mfcc.hip), a batch of utterances per call."""
+the GPU (neuralasr_amd/csrc/mfcc.hip), a batch of utterances per call; with `rates`, utterances at another rate are
+resampled first and the resampled samples stay on the device."""
 import ctypes
 import struct
 
@@ -25,10 +29,8 @@ def _chunks(data):
         pos += 8 + size + (size & 1)
 
 
-def read_wav(path, samplerate):
-    """float32 [n] of a RIFF/WAVE file: PCM 8/16/24/32-bit, IEEE float 32/64-bit, or WAVE_FORMAT_EXTENSIBLE with a PCM
-    or float subformat.  Integers are scaled as libsndfile does (x/32768, x/2^23, x/2^31, (x-128)/128); several
-    channels become their float32 mean.  A file whose rate is not `samplerate` raises ValueError."""
+def _parse(path):
+    """(format tag, channels, rate, bits, data chunk) of a RIFF/WAVE file."""
     with open(path, 'rb') as fh:
         data = fh.read()
     if len(data) < 12 or data[:4] != b'RIFF' or data[8:12] != b'WAVE':
@@ -48,8 +50,11 @@ def read_wav(path, samplerate):
         if len(fmt) < 40:
             raise ValueError('%s: short WAVE_FORMAT_EXTENSIBLE fmt chunk' % path)
         tag = struct.unpack_from('<H', fmt, 24)[0]     # the first two bytes of the subformat GUID
-    if rate != samplerate:
-        raise ValueError('%s: sample rate %d Hz, expected %d Hz (resampling is not supported)' % (path, rate, samplerate))
+    return tag, channels, rate, bits, pcm
+
+
+def _decode(path, tag, channels, bits, pcm):
+    """float32 mono samples of a data chunk."""
     if channels < 1:
         raise ValueError('%s: no channels' % path)
     width = bits // 8
@@ -77,6 +82,41 @@ def read_wav(path, samplerate):
     if channels > 1:
         y = np.mean(y.reshape(-1, channels).T, axis=0)     # librosa.to_mono on float32 [channels, n]
     return np.ascontiguousarray(y, dtype=np.float32)
+
+
+def read_wav(path, samplerate):
+    """float32 [n] of a RIFF/WAVE file: PCM 8/16/24/32-bit, IEEE float 32/64-bit, or WAVE_FORMAT_EXTENSIBLE with a PCM
+    or float subformat.  Integers are scaled as libsndfile does (x/32768, x/2^23, x/2^31, (x-128)/128); several
+    channels become their float32 mean.  A file whose rate is not `samplerate` raises ValueError."""
+    tag, channels, rate, bits, pcm = _parse(path)
+    if rate != samplerate:
+        raise ValueError('%s: sample rate %d Hz, expected %d Hz (resampling is not supported)' % (path, rate, samplerate))
+    return _decode(path, tag, channels, bits, pcm)
+
+
+def read_wav_native(path):
+    """(float32 [n], rate): read_wav's samples of a file at its own rate, for Featurizer's `rates`."""
+    tag, channels, rate, bits, pcm = _parse(path)
+    return _decode(path, tag, channels, bits, pcm), int(rate)
+
+
+def resample_length(num_samples, rate, samplerate):
+    """(librosa's ceil(n * ratio), resampy's int(n * ratio)) of n samples at `rate` resampled to `samplerate` (computed
+    by the library, no GPU needed).  ValueError when resampy would raise: a rate <= 0 or no resampled sample."""
+    lib = _lib.load()
+    filtered = ctypes.c_int64()
+    n = lib.nasr_resample_length(int(rate), int(samplerate), int(num_samples), ctypes.byref(filtered))
+    if n < 0:
+        raise ValueError('%d samples at %d Hz give no sample at %d Hz' % (num_samples, rate, samplerate))
+    return int(n), int(filtered.value)
+
+
+def resample_filter():
+    """float64 [32769]: resampy's kaiser_best half window, as the library builds it."""
+    lib = _lib.load()
+    t = np.empty(32769, dtype=np.float64)
+    _lib.check(lib, None, lib.nasr_resample_filter(t.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), t.size))
+    return t
 
 
 def _cfg(samplerate, numcep, numcontext, nfilt, nfft):
@@ -109,7 +149,8 @@ def filterbank(samplerate, nfilt=128, nfft=512):
 
 class Featurizer:
     """The normalised MFCC features of utils.convert_to_mfcc for a list of float32 utterances, on the GPU.  compute()
-    packs consecutive utterances into calls of at most `max_samples` samples (a longer utterance goes alone)."""
+    packs consecutive utterances into calls of at most `max_samples` samples, native and resampled ones counted (a
+    longer utterance goes alone)."""
 
     def __init__(self, samplerate, numcep, numcontext, nfilt=128, nfft=512, device_id=0, max_samples=1 << 23):
         self.lib = _lib.load()
@@ -128,38 +169,92 @@ class Featurizer:
             raise ValueError('an utterance needs at least one sample')
         return int(n)
 
-    def compute(self, audios, return_stats=False):
-        """list of float32 [n_i] -> list of float32 [T_i, (2*numcontext+1)*numcep] (and [(mean, std)] if asked)."""
-        audios = [np.ascontiguousarray(a, dtype=np.float32).reshape(-1) for a in audios]
-        for i, a in enumerate(audios):
-            if a.size == 0:
-                raise ValueError('utterance %d has no samples' % i)
+    def compute(self, audios, return_stats=False, *, rates=None):
+        """list of float32 [n_i] -> list of float32 [T_i, (2*numcontext+1)*numcep] (and [(mean, std)] if asked).
+        rates: each utterance's sample rate; one at another rate than `samplerate` is resampled first (librosa.load)."""
+        audios = self._utterances(audios)
+        sizes = self._sizes(audios, rates)
         feats, stats = [], []
         i = 0
         while i < len(audios):
             j, total = i, 0
-            while j < len(audios) and (j == i or total + audios[j].size <= self.max_samples):
-                total += audios[j].size
+            while j < len(audios) and (j == i or total + sizes[j] <= self.max_samples):
+                total += sizes[j]
                 j += 1
-            f, s = self._call(audios[i:j])
+            f, s = self._call(audios[i:j], None if rates is None else rates[i:j])
             feats += f
             stats += s
             i = j
         return (feats, stats) if return_stats else feats
 
-    def _call(self, audios):
+    def resample(self, audios, rates):
+        """list of float32 [n_i] at rates[i] Hz -> list of float32 [ceil(n_i * samplerate / rates[i])]: librosa's
+        resample(y, rates[i], samplerate) (res_type 'kaiser_best'); an utterance at `samplerate` comes back as it is."""
+        audios = self._utterances(audios)
+        lens = [n for n, _ in self._lengths(audios, rates)]
         n = len(audios)
         offsets = np.zeros(n + 1, dtype=np.int64)
         offsets[1:] = np.cumsum([a.size for a in audios])
         flat = np.concatenate(audios) if n > 1 else audios[0]
-        frames = [self.frames(a.size) for a in audios]
+        r = np.ascontiguousarray(rates, dtype=np.int32)
+        out = np.empty(int(sum(lens)), dtype=np.float32)
+        rc = self.lib.nasr_resample(self.h, flat.ctypes.data_as(ctypes.POINTER(ctypes.c_float)),
+                                    offsets.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)),
+                                    r.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), n,
+                                    out.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), out.size)
+        _lib.check(self.lib, self.h, rc)
+        cut = np.cumsum([0] + lens)
+        return [out[cut[k]:cut[k + 1]] for k in range(n)]
+
+    @staticmethod
+    def _utterances(audios):
+        audios = [np.ascontiguousarray(a, dtype=np.float32).reshape(-1) for a in audios]
+        for i, a in enumerate(audios):
+            if a.size == 0:
+                raise ValueError('utterance %d has no samples' % i)
+        return audios
+
+    def _lengths(self, audios, rates):
+        """[(resampled length, filtered length)] of every utterance; ValueError naming the first that has none."""
+        if len(rates) != len(audios):
+            raise ValueError('%d rates for %d utterances' % (len(rates), len(audios)))
+        out = []
+        for i, (a, r) in enumerate(zip(audios, rates)):
+            try:
+                out.append(resample_length(a.size, r, self.samplerate))
+            except ValueError as e:
+                raise ValueError('utterance %d: %s' % (i, e)) from None
+        return out
+
+    def _sizes(self, audios, rates):
+        """the samples an utterance takes on the device: native, plus resampled when its rate is not `samplerate`."""
+        if rates is None:
+            return [a.size for a in audios]
+        return [a.size + (n if int(r) != self.samplerate else 0)
+                for a, r, (n, _) in zip(audios, rates, self._lengths(audios, rates))]
+
+    def _call(self, audios, rates=None):
+        n = len(audios)
+        offsets = np.zeros(n + 1, dtype=np.int64)
+        offsets[1:] = np.cumsum([a.size for a in audios])
+        flat = np.concatenate(audios) if n > 1 else audios[0]
+        if rates is None:
+            frames = [self.frames(a.size) for a in audios]
+        else:
+            frames = [self.frames(m) for m, _ in self._lengths(audios, rates)]
         rows = int(sum(frames))
         out = np.empty((rows, self.width), dtype=np.float32)
         ms = np.empty((n, 2), dtype=np.float64)
-        rc = self.lib.nasr_featurize(self.h, flat.ctypes.data_as(ctypes.POINTER(ctypes.c_float)),
-                                     offsets.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), n,
-                                     out.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), rows,
-                                     ms.ctypes.data_as(ctypes.POINTER(ctypes.c_double)))
+        args = (out.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), rows,
+                ms.ctypes.data_as(ctypes.POINTER(ctypes.c_double)))
+        audio_p = flat.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
+        off_p = offsets.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))
+        if rates is None:
+            rc = self.lib.nasr_featurize(self.h, audio_p, off_p, n, *args)
+        else:
+            r = np.ascontiguousarray(rates, dtype=np.int32)
+            rc = self.lib.nasr_featurize_rates(self.h, audio_p, off_p, r.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+                                               n, *args)
         _lib.check(self.lib, self.h, rc)
         cut = np.cumsum([0] + frames)
         return [out[cut[k]:cut[k + 1]] for k in range(n)], [tuple(ms[k]) for k in range(n)]

@@ -75,14 +75,15 @@ def sort_rows(rows):
 
 
 def gpu_featurize(config):
-    """paths -> features, the WAVs read on a few host threads and featurised on the GPU in one call."""
-    from .features import read_wav
+    """paths -> features, the WAVs read on a few host threads and featurised on the GPU in one call (files at another
+    rate than the config's resampled to it there)."""
+    from .features import read_wav_native
     fz = featurizer(config.samplerate, config.numcontext, config.numcep)
 
     def run(paths):
         with ThreadPoolExecutor(max_workers=READ_THREADS) as ex:
-            audios = list(ex.map(lambda p: read_wav(p, config.samplerate), paths))
-        return fz.compute(audios)
+            audios, rates = zip(*ex.map(read_wav_native, paths))
+        return fz.compute(list(audios), rates=list(rates))
     return run
 
 

@@ -58,9 +58,11 @@ def featurizer(sr, numcontext, numcep):
 
 
 def convert_to_mfcc(wavfile, sr, numcontext, numcep):
-    """float32 [T, (2*numcontext+1)*numcep] normalised MFCC features of a WAV file (reference: utils.py:24-31)."""
-    from .features import read_wav
-    return featurizer(sr, numcontext, numcep).compute([read_wav(wavfile, sr)])[0]
+    """float32 [T, (2*numcontext+1)*numcep] normalised MFCC features of a WAV file (reference: utils.py:24-31); a file
+    at another rate than sr is resampled to it on the GPU, as librosa.load(wavfile, mono=True, sr=sr) does."""
+    from .features import read_wav_native
+    audio, rate = read_wav_native(wavfile)
+    return featurizer(sr, numcontext, numcep).compute([audio], rates=[rate])[0]
 
 
 def compute_mfcc_and_read_transcription(wavfile, sr, numcontext, numcep, punc_regex=None, txtfile=None):

@@ -1,7 +1,10 @@
 """MFCC front-end throughput and error: a batch of synthetic int16 utterances (default 64 x 10 s at 16 kHz, the
 16000sr_26mfcc config: numcep 26, numcontext 10) through nasr_featurize, split into host-to-device copies, kernels and
 device-to-host copies (device events), and through the fp64 NumPy restatement of tests/mfcc_ref.py on the same batch.
-Prints one JSON line.   python tools/mfccbench.py [--utts 64 --seconds 10 --sr 16000 --numcep 26 --numcontext 10]"""
+Prints one JSON line.   python tools/mfccbench.py [--utts 64 --seconds 10 --sr 16000 --numcep 26 --numcontext 10]
+With --native-sr R the utterances are made at R Hz and resampled to --sr on the GPU first (nasr_featurize_rates); the
+line then also carries a "resample" field: nasr_resample's phases alone, and the fp64 restatement of
+tests/resample_ref.py timed on a few utterances and scaled to the batch."""
 import argparse
 import json
 import os
@@ -14,6 +17,7 @@ ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), '..')
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, 'tests'))
 import mfcc_ref as R                                # noqa: E402
+import resample_ref as RR                           # noqa: E402
 from neuralasr_amd.features import Featurizer       # noqa: E402
 
 
@@ -37,15 +41,18 @@ def main():
     ap.add_argument('--numcontext', type=int, default=10)
     ap.add_argument('--reps', type=int, default=10)
     ap.add_argument('--ref-utts', type=int, default=8, help='utterances the fp64 restatement is timed and checked on')
+    ap.add_argument('--native-sr', type=int, default=None, help='make the audio at this rate and resample it to --sr')
     a = ap.parse_args()
-    n = int(a.seconds * a.sr)
-    audios = [synth(n, a.sr, s) for s in range(a.utts)]
-    fz = Featurizer(a.sr, a.numcep, a.numcontext, max_samples=n * a.utts)
-    feats = fz.compute(audios)                            # warm-up: code objects, buffers
+    native = a.native_sr or a.sr
+    n = int(a.seconds * native)
+    audios = [synth(n, native, s) for s in range(a.utts)]
+    rates = None if a.native_sr is None else [native] * a.utts
+    fz = Featurizer(a.sr, a.numcep, a.numcontext, max_samples=(n if rates is None else n + int(a.seconds * a.sr) + 1) * a.utts)
+    feats = fz.compute(audios, rates=rates)               # warm-up: code objects, buffers
     t_h2d = t_k = t_d2h = wall = 0.0
     for _ in range(a.reps):
         t0 = time.perf_counter()
-        feats = fz.compute(audios)
+        feats = fz.compute(audios, rates=rates)
         wall += time.perf_counter() - t0
         h2d, k, d2h = fz.times()
         t_h2d += h2d; t_k += k; t_d2h += d2h
@@ -53,8 +60,29 @@ def main():
     audio_s = a.utts * a.seconds
     m = a.reps
     nref = min(a.ref_utts, a.utts)
+    resample = None
+    at_sr = audios
+    if rates is not None:
+        fz.resample(audios, rates)                        # warm-up
+        r_h2d = r_k = r_d2h = r_wall = 0.0
+        for _ in range(a.reps):
+            t0 = time.perf_counter()
+            at_sr = fz.resample(audios, rates)
+            r_wall += time.perf_counter() - t0
+            h2d, k, d2h = fz.times()
+            r_h2d += h2d; r_k += k; r_d2h += d2h
+        nrs = min(2, a.utts)
+        table = RR.table()
+        t0 = time.perf_counter()
+        restated = [RR.resample(x, native, a.sr, win=table) for x in audios[:nrs]]
+        t_rs = (time.perf_counter() - t0) * a.utts / nrs
+        resample = {'native_sr': native, 'h2d_ms': round(r_h2d / m, 3), 'kernel_ms': round(r_k / m, 3),
+                    'd2h_ms': round(r_d2h / m, 3), 'call_ms': round(r_wall / m * 1e3, 3),
+                    'outputs': int(sum(x.size for x in at_sr)),
+                    'ref_fp64_s_batch': round(t_rs, 3), 'ref_checked_utts': nrs,
+                    'bitwise_vs_ref': all(x.tobytes() == y.tobytes() for x, y in zip(at_sr, restated))}
     t0 = time.perf_counter()
-    ref = [R.features(x, a.sr, a.numcontext, a.numcep)[0] for x in audios[:nref]]
+    ref = [R.features(x, a.sr, a.numcontext, a.numcep)[0] for x in at_sr[:nref]]
     t_ref = (time.perf_counter() - t0) * a.utts / nref
     err = np.concatenate([np.abs(f.astype(np.float64) - r).ravel() for f, r in zip(feats, ref)])
     fz.close()
@@ -66,7 +94,8 @@ def main():
         'audio_s_per_s_call': round(audio_s / (wall / m)), 'audio_s_per_s_kernels': round(audio_s / (t_k / m * 1e-3)),
         'frames_per_s_call': round(frames / (wall / m)), 'frames_per_s_kernels': round(frames / (t_k / m * 1e-3)),
         'ref_fp64_s_batch': round(t_ref, 3), 'ref_checked_utts': nref,
-        'max_abs_err': float(err.max()), 'mean_abs_err': float(err.mean())}))
+        'max_abs_err': float(err.max()), 'mean_abs_err': float(err.mean()),
+        **({} if resample is None else {'resample': resample})}))
 
 
 if __name__ == '__main__':
