@@ -432,45 +432,16 @@ int nasr_create_featurizer(const nasr_mfcc_cfg* cfg, int device_id, void* stream
     g_create_error = "nasr_create_featurizer: winlen * samplerate and winstep * samplerate must round to >= 1 sample";
     return NASR_ERR_ARG;
   }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) {
-    g_create_error = "nasr_create_featurizer: no HIP device visible (libnasr has no CPU fallback)";
-    return NASR_ERR_HIP;
-  }
-  if (device_id < 0 || device_id >= ndev) {
-    g_create_error = "nasr_create_featurizer: device_id out of range";
-    return NASR_ERR_ARG;
-  }
-  hipDeviceProp_t prop;
-  if (hipGetDeviceProperties(&prop, device_id) != hipSuccess) {
-    g_create_error = "nasr_create_featurizer: hipGetDeviceProperties failed";
-    return NASR_ERR_HIP;
-  }
-  if (std::string(prop.gcnArchName).find("gfx950") == std::string::npos) {
-    g_create_error = std::string("nasr_create_featurizer: device is ") + prop.gcnArchName + ", libnasr is built for gfx950 only";
-    return NASR_ERR_HIP;
-  }
-  nasr_ctx* h = new nasr_ctx();
-  auto bail = [&](int code, const std::string& m) {
-    g_create_error = m;
-    nasr_destroy(h);
-    return code;
-  };
-  memset(&h->cfg, 0, sizeof(h->cfg));
-  h->device = device_id;
+  nasr_ctx* h = nullptr;
+  if (int rc = handle_open("nasr_create_featurizer", Family::Featurizer, device_id, stream, &h, nullptr)) return rc;
   h->graph_mode = false;
   h->fz.reset(new FzState());
   FzState& z = *h->fz;
   z.cfg = *cfg;
   z.d = FzDims{(int)flen, (int)fstep, cfg->numcep, cfg->nfilt, cfg->numcontext, cfg->append_energy ? 1 : 0, cfg->preemph};
   z.W = 2 * cfg->numcontext + 1;
-  if (hipSetDevice(device_id) != hipSuccess) return bail(NASR_ERR_HIP, "hipSetDevice failed");
-  if (stream)
-    h->st.borrow(reinterpret_cast<hipStream_t>(stream));
-  else if (hipStreamCreateWithFlags(h->st.out(), hipStreamNonBlocking) != hipSuccess)
-    return bail(NASR_ERR_HIP, "hipStreamCreate failed");
   for (Event& e : z.ev)
-    if (hipEventCreate(e.out()) != hipSuccess) return bail(NASR_ERR_HIP, "hipEventCreate failed");
+    if (hipEventCreate(e.out()) != hipSuccess) return create_fail(h, NASR_ERR_HIP, "hipEventCreate failed");
 
   const double pi = 3.14159265358979323846;
   std::vector<double2> tw(FFT_N), tw2(NBIN);
@@ -504,7 +475,7 @@ int nasr_create_featurizer(const nasr_mfcc_cfg* cfg, int device_id, void* stream
   };
   if (!put(z.tw, tw) || !put(z.tw2, tw2) || !put(z.fb_lo, lo) || !put(z.fb_n, cnt) || !put(z.fb_off, off) ||
       !put(z.fb_w, w) || !put(z.dct, dct))
-    return bail(NASR_ERR_HIP, "nasr_create_featurizer: upload of the tables failed");
+    return create_fail(h, NASR_ERR_HIP, "nasr_create_featurizer: upload of the tables failed");
   *out = h;
   return NASR_OK;
 }

@@ -1,4 +1,5 @@
-// nasr_api.hip — the C ABI of include/nasr.h: every entry point names the reference interface it replaces there.  The work
+// nasr_api.hip — the C ABI of include/nasr.h: every entry point names the reference interface it replaces there, and what
+// the create calls of all handle kinds share (handle_open, alloc_param_buffers, handle_finish).  The work
 // behind them lives in nasr_layout.hip (parameters, operand images), nasr_rec.hip (the recurrence, nasr_*_recurrence_mode),
 // nasr_batch.hip (batches), nasr_pass.hip (the step) and nasr_comm.hip (RCCL); the shared handle is nasr_ctx.h.
 #include "nasr_ctx.h"
@@ -17,6 +18,89 @@ int settle_end(nasr_ctx* h, nasr_ctx::StepEnd& e, int* void_out) {
   return NASR_OK;
 }
 }  // namespace
+
+namespace nasr_impl {
+
+int create_fail(nasr_ctx* h, int code, const std::string& m) {
+  g_create_error = m;
+  nasr_destroy(h);
+  return code;
+}
+
+int handle_open(const char* fn, Family family, int device_id, void* stream, nasr_ctx** out, hipDeviceProp_t* prop) {
+  auto refuse = [fn](int code, const std::string& m) {
+    g_create_error = std::string(fn) + ": " + m;
+    return code;
+  };
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return refuse(NASR_ERR_HIP, "no HIP device visible (libnasr has no CPU fallback)");
+  if (device_id < 0 || device_id >= ndev) return refuse(NASR_ERR_ARG, "device_id out of range");
+  hipDeviceProp_t p;
+  if (hipGetDeviceProperties(&p, device_id) != hipSuccess) return refuse(NASR_ERR_HIP, "hipGetDeviceProperties failed");
+  if (std::string(p.gcnArchName).find("gfx950") == std::string::npos)
+    return refuse(NASR_ERR_HIP, std::string("device is ") + p.gcnArchName + ", libnasr is built for gfx950 only");
+  if (prop) *prop = p;
+  nasr_ctx* h = new nasr_ctx();
+  memset(&h->cfg, 0, sizeof(h->cfg));
+  h->family = family;
+  h->device = device_id;
+  if (hipSetDevice(device_id) != hipSuccess) return create_fail(h, NASR_ERR_HIP, "hipSetDevice failed");
+  if (stream)
+    h->st.borrow(reinterpret_cast<hipStream_t>(stream));
+  else if (hipStreamCreateWithFlags(h->st.out(), hipStreamNonBlocking) != hipSuccess)
+    return create_fail(h, NASR_ERR_HIP, "hipStreamCreate failed");
+  *out = h;
+  return NASR_OK;
+}
+
+bool alloc_param_buffers(nasr_ctx* h) {
+  const size_t nb = (size_t)h->np_int * 4;
+  const size_t gb = nb + GRAD_HEAD * 4;   // the gradient buffer starts with the fault word (+ padding): see nasr_grad_device_count
+  if (hipMalloc(h->P.out(), nb) != hipSuccess || hipMalloc(h->M.out(), nb) != hipSuccess || hipMalloc(h->V.out(), nb) != hipSuccess ||
+      hipMalloc(h->Gbase.out(), gb) != hipSuccess || hipMalloc(h->adam_dev.out(), sizeof(AdamDev)) != hipSuccess)
+    return false;
+  (void)hipMemsetAsync(h->adam_dev, 0, sizeof(AdamDev), h->st);
+  (void)hipMemsetAsync(h->P, 0, nb, h->st);
+  (void)hipMemsetAsync(h->M, 0, nb, h->st);
+  (void)hipMemsetAsync(h->V, 0, nb, h->st);
+  (void)hipMemsetAsync(h->Gbase, 0, gb, h->st);
+  h->G = h->Gbase + GRAD_HEAD;
+  return true;
+}
+
+int handle_finish(nasr_ctx* h) {
+  h->ev_bucket.resize(h->buckets.size());
+  for (Event& e : h->ev_bucket)
+    if (hipEventCreateWithFlags(e.out(), hipEventDisableTiming) != hipSuccess) return create_fail(h, NASR_ERR_HIP, "hipEventCreate failed");
+  if (hipStreamCreateWithFlags(h->cst.out(), hipStreamNonBlocking) != hipSuccess ||
+      hipStreamCreateWithFlags(h->d2h.out(), hipStreamNonBlocking) != hipSuccess ||
+      hipEventCreateWithFlags(h->ev_snap.out(), hipEventDisableTiming) != hipSuccess)
+    return create_fail(h, NASR_ERR_HIP, "hipStreamCreate failed");
+  for (BatchSlot& bs : h->slots)
+    if (hipEventCreateWithFlags(bs.ev_copy.out(), hipEventDisableTiming) != hipSuccess ||
+        hipEventCreateWithFlags(bs.ev_released.out(), hipEventDisableTiming) != hipSuccess)
+      return create_fail(h, NASR_ERR_HIP, "hipEventCreate failed");
+  for (auto& r : h->res) {
+    if (hipHostMalloc(r.stamp.out(), 64, hipHostMallocMapped) != hipSuccess)
+      return create_fail(h, NASR_ERR_HIP, "set-up of the step-result stamps failed");
+    *r.stamp = 0;
+  }
+  for (auto& e : h->endw) {
+    if (hipHostMalloc(e.host.out(), 64, hipHostMallocMapped) != hipSuccess)
+      return create_fail(h, NASR_ERR_HIP, "set-up of the step-end words failed");
+    e.stamp = reinterpret_cast<uint32_t*>(e.host.get()) + 8;
+    *e.host = 0.f;
+    *e.stamp = 0;
+  }
+  (void)hipEventCreate(h->ev_total_a.out());
+  (void)hipEventCreate(h->ev_total_b.out());
+  memset(&h->last_times, 0, sizeof(h->last_times));
+  if (hipGetLastError() != hipSuccess || hipStreamSynchronize(h->st) != hipSuccess)
+    return create_fail(h, NASR_ERR_HIP, "stream synchronize failed in create");
+  return NASR_OK;
+}
+
+}  // namespace nasr_impl
 
 // =============================================================================== C ABI
 extern "C" {
@@ -61,40 +145,13 @@ int nasr_create(const nasr_model_cfg* cfg, int device_id, void* stream, nasr_han
     g_create_error = "nasr_create: STACK_RESHAPE is the literal 1-layer BiLstmCTCNet; use CONCAT for stacks";
     return NASR_ERR_ARG;
   }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) {
-    g_create_error = "nasr_create: no HIP device visible (libnasr has no CPU fallback)";
-    return NASR_ERR_HIP;
-  }
-  if (device_id < 0 || device_id >= ndev) {
-    g_create_error = "nasr_create: device_id out of range";
-    return NASR_ERR_ARG;
-  }
+  nasr_ctx* h = nullptr;
   hipDeviceProp_t prop;
-  if (hipGetDeviceProperties(&prop, device_id) != hipSuccess) {
-    g_create_error = "nasr_create: hipGetDeviceProperties failed";
-    return NASR_ERR_HIP;
-  }
-  if (std::string(prop.gcnArchName).find("gfx950") == std::string::npos) {
-    g_create_error = std::string("nasr_create: device is ") + prop.gcnArchName + ", libnasr is built for gfx950 only";
-    return NASR_ERR_HIP;
-  }
-  nasr_ctx* h = new nasr_ctx();
+  if (int rc = handle_open("nasr_create", Family::Lstm, device_id, stream, &h, &prop)) return rc;
   h->cfg = *cfg;
   if (!cfg->bidirectional) h->cfg.merge = NASR_MERGE_NONE;
-  h->device = device_id;
   h->lr = cfg->learning_rate;
-  auto bail = [&](int code, const std::string& m) {
-    g_create_error = m;
-    nasr_destroy(h);
-    return code;
-  };
-  if (hipSetDevice(device_id) != hipSuccess) return bail(NASR_ERR_HIP, "hipSetDevice failed");
-  if (stream)
-    h->st.borrow(reinterpret_cast<hipStream_t>(stream));
-  else if (hipStreamCreateWithFlags(h->st.out(), hipStreamNonBlocking) != hipSuccess)
-    return bail(NASR_ERR_HIP, "hipStreamCreate failed");
-  if (build_layout(h) != NASR_OK) return bail(NASR_ERR_ARG, t_err);
+  if (build_layout(h) != NASR_OK) return create_fail(h, NASR_ERR_ARG, t_err);
   {
     const char* ec = getenv("NASR_COMPACT");
     h->compactable = h->ndense == 0 && !(ec && ec[0] == '0');
@@ -117,7 +174,7 @@ int nasr_create(const nasr_model_cfg* cfg, int device_id, void* stream, nasr_han
       for (int l = 0; l < h->L; ++l) wsf += tph_scale_ws_floats(h->Ip[l], h->D * h->N4);
       for (int i = 0; i < h->ndense; ++i) wsf += tph_scale_ws_floats(h->dIp[i], h->dWp[i]);
       ok = ok && h->scws.ensure(std::max(wsf, tph_scale_ws_floats(rmax, cmax)) * 4, &g2);
-      if (!ok) return bail(NASR_ERR_HIP, "set-up of the fp16-plane GEMMs failed");
+      if (!ok) return create_fail(h, NASR_ERR_HIP, "set-up of the fp16-plane GEMMs failed");
     }
     {
       size_t of = 0, ob = 0;
@@ -136,22 +193,12 @@ int nasr_create(const nasr_model_cfg* cfg, int device_id, void* stream, nasr_han
           hipMalloc(h->WbTP.out(), std::max<size_t>(ob, 1024)) != hipSuccess ||
           hipMalloc(h->DfTP.out(), std::max<size_t>(df, 1024)) != hipSuccess ||
           hipMalloc(h->DbTP.out(), std::max<size_t>(db, 1024)) != hipSuccess)
-        return bail(NASR_ERR_HIP, "hipMalloc of the tiled weight planes failed");
+        return create_fail(h, NASR_ERR_HIP, "hipMalloc of the tiled weight planes failed");
     }
   }
-  const size_t nb = (size_t)h->np_int * 4;
-  const size_t gb = nb + GRAD_HEAD * 4;   // the gradient buffer starts with the fault word (+ padding): see nasr_grad_device_count
   const size_t ub = (size_t)h->L * h->D * h->Hp * h->N4 * 4;
-  if (hipMalloc(h->P.out(), nb) != hipSuccess || hipMalloc(h->M.out(), nb) != hipSuccess || hipMalloc(h->V.out(), nb) != hipSuccess ||
-      hipMalloc(h->Gbase.out(), gb) != hipSuccess || hipMalloc(h->Uf.out(), ub) != hipSuccess || hipMalloc(h->Ub.out(), ub) != hipSuccess)
-    return bail(NASR_ERR_HIP, "hipMalloc of parameter buffers failed");
-  if (hipMalloc(h->adam_dev.out(), sizeof(AdamDev)) != hipSuccess) return bail(NASR_ERR_HIP, "hipMalloc of the Adam state failed");
-  (void)hipMemsetAsync(h->adam_dev, 0, sizeof(AdamDev), h->st);
-  (void)hipMemsetAsync(h->P, 0, nb, h->st);
-  (void)hipMemsetAsync(h->M, 0, nb, h->st);
-  (void)hipMemsetAsync(h->V, 0, nb, h->st);
-  h->G = h->Gbase + GRAD_HEAD;
-  (void)hipMemsetAsync(h->Gbase, 0, gb, h->st);
+  if (!alloc_param_buffers(h) || hipMalloc(h->Uf.out(), ub) != hipSuccess || hipMalloc(h->Ub.out(), ub) != hipSuccess)
+    return create_fail(h, NASR_ERR_HIP, "hipMalloc of parameter buffers failed");
   {
     // Buckets for an all-reduce that overlaps the rest of the backward pass (nasr_grad_bucket*): the internal layout
     // is [head | dense stages | layer 0 | ... | layer L-1 | W | b] and backward() finishes W, b first, then the layers
@@ -175,9 +222,6 @@ int nasr_create(const nasr_model_cfg* cfg, int device_id, void* stream, nasr_han
     } else {
       h->buckets.push_back({0, GRAD_HEAD + h->np_int});
     }
-    h->ev_bucket.resize(h->buckets.size());
-    for (auto& e2 : h->ev_bucket)
-      if (hipEventCreateWithFlags(e2.out(), hipEventDisableTiming) != hipSuccess) return bail(NASR_ERR_HIP, "hipEventCreate failed");
   }
   (void)hipMemsetAsync(h->Uf, 0, ub, h->st);
   (void)hipMemsetAsync(h->Ub, 0, ub, h->st);
@@ -185,7 +229,7 @@ int nasr_create(const nasr_model_cfg* cfg, int device_id, void* stream, nasr_han
     const char* e = getenv("NASR_PERSIST");
     const char* er = getenv("NASR_REC");
     if (rec_setup(h, !(e && e[0] == '0') && prop.multiProcessorCount == 256, er && std::string(er) == "f32") != NASR_OK)
-      return bail(NASR_ERR_HIP, t_err);
+      return create_fail(h, NASR_ERR_HIP, t_err);
   }
   h->gates.resize(h->L);
   h->OTT.resize(h->L);
@@ -194,10 +238,7 @@ int nasr_create(const nasr_model_cfg* cfg, int device_id, void* stream, nasr_han
   h->cbuf.resize(h->L);
   h->Ybuf.resize(h->ndense);
   h->dYbuf.resize(h->ndense);
-  if (hipStreamCreateWithFlags(h->cst.out(), hipStreamNonBlocking) != hipSuccess) return bail(NASR_ERR_HIP, "hipStreamCreate (copy stream) failed");
-  if (hipStreamCreateWithFlags(h->d2h.out(), hipStreamNonBlocking) != hipSuccess ||
-      hipEventCreateWithFlags(h->ev_snap.out(), hipEventDisableTiming) != hipSuccess)
-    return bail(NASR_ERR_HIP, "hipStreamCreate (results stream) failed");
+  if (int rc = handle_finish(h)) return rc;
   {
     const char* eo = getenv("NASR_WGRAD_OVERLAP");
     const bool eligible = h->rec_kind == RecKind::Persist && h->Hp == 512 && h->L > 1;
@@ -209,32 +250,12 @@ int nasr_create(const nasr_model_cfg* cfg, int device_id, void* stream, nasr_han
       (void)hipDeviceGetStreamPriorityRange(&lo, &hi);          // lo = lowest priority (largest number)
       if (hipStreamCreateWithPriority(h->wst.out(), hipStreamNonBlocking, lo) != hipSuccess ||
           hipEventCreateWithFlags(h->ev_dx.out(), hipEventDisableTiming) != hipSuccess)
-        return bail(NASR_ERR_HIP, "set-up of the weight-gradient side stream failed");
+        return create_fail(h, NASR_ERR_HIP, "set-up of the weight-gradient side stream failed");
       for (auto& e : h->ev_wg)
-        if (hipEventCreateWithFlags(e.out(), hipEventDisableTiming) != hipSuccess) return bail(NASR_ERR_HIP, "hipEventCreate failed");
+        if (hipEventCreateWithFlags(e.out(), hipEventDisableTiming) != hipSuccess) return create_fail(h, NASR_ERR_HIP, "hipEventCreate failed");
       h->bwd_lean = true;
     }
   }
-  for (BatchSlot& bs : h->slots)
-    if (hipEventCreateWithFlags(bs.ev_copy.out(), hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(bs.ev_released.out(), hipEventDisableTiming) != hipSuccess)
-      return bail(NASR_ERR_HIP, "hipEventCreate failed");
-  for (auto& r : h->res) {
-    if (hipHostMalloc(r.stamp.out(), 64, hipHostMallocMapped) != hipSuccess)
-      return bail(NASR_ERR_HIP, "set-up of the step-result stamps failed");
-    *r.stamp = 0;
-  }
-  for (auto& e : h->endw) {
-    if (hipHostMalloc(e.host.out(), 64, hipHostMallocMapped) != hipSuccess)
-      return bail(NASR_ERR_HIP, "set-up of the step-end words failed");
-    e.stamp = reinterpret_cast<uint32_t*>(e.host.get()) + 8;
-    *e.host = 0.f;
-    *e.stamp = 0;
-  }
-  (void)hipEventCreate(h->ev_total_a.out());
-  (void)hipEventCreate(h->ev_total_b.out());
-  memset(&h->last_times, 0, sizeof(h->last_times));
-  if (hipStreamSynchronize(h->st) != hipSuccess) return bail(NASR_ERR_HIP, "stream synchronize failed in create");
   if (h->rec_kind != RecKind::Step) {
     const char* er = getenv("NASR_PERSIST_REARM");
     h->rearm_after = er && *er ? std::max<long long>(0, atoll(er)) : 200;
@@ -357,7 +378,7 @@ int nasr_set_learning_rate(nasr_handle h, float lr) {
 int nasr_logit_frames(nasr_handle h, int T) {
   MODEL_CALL(h);
   if (!h) return NASR_ERR_ARG;
-  if (h->las) return h->fail(NASR_ERR_STATE, "nasr_logit_frames: a LAS handle has no CTC logit frames");
+  if (h->family == Family::Las) return h->fail(NASR_ERR_STATE, "nasr_logit_frames: a LAS handle has no CTC logit frames");
   return (h->cfg.bidirectional && h->cfg.merge == NASR_MERGE_STACK_RESHAPE) ? 2 * T : T;
 }
 
@@ -424,24 +445,12 @@ int nasr_compute_grads(nasr_handle h) {
     h->window_open = true;
     h->total_valid = false;
   }
-  if (h->las) {          // a gradient pass: scheduled sampling on; the sequence loss is part of the forward pass
-    int rc = las_forward(h, true);
-    return rc ? rc : backward(h);
-  }
-  if (h->wn) {           // a gradient pass: training-mode batch norm
-    int rc = wn_forward(h, true);
-    if (!rc) rc = ctc_forward(h);
-    return rc ? rc : backward(h);
-  }
-  rec_rearm(h);
-  int rc = forward(h);   // clears the step's fault word
-  if (rc) return rc;
-  rc = ctc_forward(h);
-  if (rc) return rc;
-  return backward(h);
+  rec_rearm(h);                        // (nothing to re-arm on a handle without a resident recurrence)
+  const int rc = loss_pass(h, true);   // a gradient pass: training-mode batch norm, scheduled sampling
+  return rc ? rc : backward(h);
 }
 
-void* nasr_grad_device_ptr(nasr_handle h) { return h && !h->fz ? h->Gbase : nullptr; }
+void* nasr_grad_device_ptr(nasr_handle h) { return h && h->family != Family::Featurizer ? h->Gbase : nullptr; }
 int64_t nasr_grad_device_count(nasr_handle h) {
   MODEL_CALL(h);
   return h ? h->np_int + GRAD_HEAD : -1;
@@ -647,7 +656,7 @@ int nasr_resident_frames(nasr_handle h, int64_t* frames) {
 int nasr_set_row_compaction(nasr_handle h, int enabled) {
   MODEL_CALL(h);
   if (!h) return NASR_ERR_ARG;
-  if (h->wn || h->las) return h->fail(NASR_ERR_STATE, "nasr_set_row_compaction: a WaveNet or LAS handle has no recurrence to compact rows for");
+  LSTM_CALL(h, "has no recurrence to compact rows for");
   // what the resident batch's plane buffers hold depends on it: takes effect with the next uploaded / committed batch
   h->compactable = enabled && h->ndense == 0;
   return NASR_OK;
@@ -693,9 +702,7 @@ int nasr_loss(nasr_handle h, const float* feats, const int32_t* seq_len, const i
   if (!labels) return h->fail(NASR_ERR_ARG, "nasr_loss needs labels");
   int rc = upload(h, feats, seq_len, labels, label_len, B, T, Lmax);
   if (rc) return rc;
-  rc = h->las ? las_forward(h, true) : forward(h);
-  if (rc) return rc;
-  if (!h->las) rc = ctc_forward(h);
+  rc = loss_pass(h, false);   // inference-mode batch norm
   if (rc) return rc;
   if (nll_out) HIPCHK(h, hipMemcpyAsync(nll_out, h->nll.p, (size_t)B * 4, hipMemcpyDeviceToHost, h->st));
   if (loss_out) return nasr_get_loss(h, loss_out);
@@ -725,7 +732,7 @@ int nasr_greedy_decode(nasr_handle h, const float* feats, const int32_t* seq_len
                        int32_t* lens_out) {
   MODEL_CALL(h);
   if (!h || !ids_out || !lens_out) return NASR_ERR_ARG;
-  if (h->las) return h->fail(NASR_ERR_STATE, "nasr_greedy_decode: a LAS handle has no CTC decoder");
+  if (h->family == Family::Las) return h->fail(NASR_ERR_STATE, "nasr_greedy_decode: a LAS handle has no CTC decoder");
   int rc = upload(h, feats, seq_len, nullptr, nullptr, B, T, 0);
   if (rc) return rc;
   rc = forward(h);
@@ -742,7 +749,7 @@ int nasr_greedy_decode(nasr_handle h, const float* feats, const int32_t* seq_len
 int nasr_set_step_decode(nasr_handle h, int enabled) {
   MODEL_CALL(h);
   if (!h) return NASR_ERR_ARG;
-  if (h->las && (enabled & 1)) return h->fail(NASR_ERR_STATE, "nasr_set_step_decode: a LAS handle has no greedy CTC pass");
+  if (h->family == Family::Las && (enabled & 1)) return h->fail(NASR_ERR_STATE, "nasr_set_step_decode: a LAS handle has no greedy CTC pass");
   h->step_decode = enabled != 0;
   h->step_greedy = (enabled & 1) != 0;
   h->step_logits = (enabled & 2) != 0;
@@ -818,7 +825,7 @@ int nasr_set_graph_mode(nasr_handle h, int enabled) {
 int nasr_set_dropout_state(nasr_handle h, uint32_t seed, uint32_t counter) {
   MODEL_CALL(h);
   if (!h) return NASR_ERR_ARG;
-  if (h->wn || h->las) return h->fail(NASR_ERR_STATE, "nasr_set_dropout_state: a WaveNet or LAS handle has no dropout");
+  LSTM_CALL(h, "has no dropout");
   h->drop_seed = seed;
   h->drop_counter = counter;
   return NASR_OK;
@@ -827,7 +834,7 @@ int nasr_set_dropout_state(nasr_handle h, uint32_t seed, uint32_t counter) {
 int nasr_get_dropout_state(nasr_handle h, uint32_t* seed, uint32_t* counter) {
   MODEL_CALL(h);
   if (!h) return NASR_ERR_ARG;
-  if (h->wn || h->las) return h->fail(NASR_ERR_STATE, "nasr_get_dropout_state: a WaveNet or LAS handle has no dropout");
+  LSTM_CALL(h, "has no dropout");
   if (seed) *seed = h->drop_seed;
   if (counter) *counter = h->drop_counter;
   return NASR_OK;
@@ -836,7 +843,7 @@ int nasr_get_dropout_state(nasr_handle h, uint32_t* seed, uint32_t* counter) {
 int nasr_set_wgrad_overlap(nasr_handle h, int enabled) {
   MODEL_CALL(h);
   if (!h) return NASR_ERR_ARG;
-  if (h->wn || h->las) return h->fail(NASR_ERR_STATE, "nasr_set_wgrad_overlap: a WaveNet or LAS handle has no recurrence");
+  LSTM_CALL(h, "has no recurrence");
   if (enabled && !h->wst) return h->fail(NASR_ERR_STATE, "the weight-gradient side stream was not set up for this handle "
                                                          "(needs the persistent recurrence at Hp = 512 and more than one layer)");
   HIPCHK(h, hipStreamSynchronize(h->st));

@@ -8,17 +8,43 @@ using namespace nasr_impl;
 
 namespace nasr_impl {
 
+int ensure_ctc_buffers(nasr_ctx* h, int B, int Bp, int T, int Tp, int Lmax, bool* grew) {
+  const int KS = std::max(1, (2 * std::max(Lmax, 0) + 1 + 63) / 64);
+  if (KS > 16) return h->fail(NASR_ERR_ARG, "label length > 511 not supported by the CTC lattice kernel");
+  const int KSa = KS <= 1 ? 2 : KS <= 8 ? KS : (KS <= 12 ? 12 : 16);   // kernel instantiations (two states per lane at least: ctc.hip (2b))
+  bool ok = true;
+  ok &= h->logits.ensure((size_t)Tp * Bp * h->Cp * 4, grew);
+  ok &= h->logz.ensure((size_t)Tp * Bp * 4, grew);
+  ok &= h->alpha.ensure((size_t)B * (T + 8) * KSa * 64 * 4, grew);
+  ok &= h->beta.ensure((size_t)B * (T + 8) * KSa * 64 * 4, grew);
+  ok &= h->aoff.ensure((size_t)B * (T + 8) * 8, grew);
+  ok &= h->boff.ensure((size_t)B * (T + 8) * 8, grew);
+  ok &= h->logp.ensure((size_t)Bp * 8, grew);
+  ok &= h->ctcprobs.ensure((size_t)Tp * Bp * h->Cp * 4, grew);              // emission rows of the CTC lattice (ctc.hip (2b))
+  ok &= h->ctckexp.ensure((size_t)B * 2 * ((T + 8) / 4 + 3) * 8, grew);     // its column offsets per group of frames
+  ok &= h->nll.ensure((size_t)Bp * 4, grew);
+  ok &= h->loss.ensure(16, grew);
+  ok &= h->amax.ensure((size_t)Tp * Bp * 4, grew);
+  ok &= h->ids.ensure((size_t)B * Tp * 4, grew);
+  ok &= h->lens.ensure((size_t)Bp * 4, grew);
+  if (!ok) return h->fail(NASR_ERR_HIP, "hipMalloc failed while sizing batch buffers");
+  return KSa;
+}
+
 int ensure_shape(nasr_ctx* h, int B, int T, int Lmax) {
-  if (h->wn) return wn_ensure_shape(h, B, T, Lmax);
-  if (h->las) return las_ensure_shape(h, B, T, Lmax);
+  switch (h->family) {
+    case Family::WaveNet: return wn_ensure_shape(h, B, T, Lmax);
+    case Family::Las: return las_ensure_shape(h, B, T, Lmax);
+    default: break;
+  }
   const int Bp = rup(B, 16);
   const int Tp = nasr_logit_frames(h, T);
   const size_t R = (size_t)T * Bp;
   const int D = h->D, Hp = h->Hp, N4 = h->N4;
-  const int KS = std::max(1, (2 * std::max(Lmax, 0) + 1 + 63) / 64);
-  if (KS > 16) return h->fail(NASR_ERR_ARG, "label length > 511 not supported by the CTC lattice kernel");
   bool grew = false;
   bool ok = true;
+  const int KSa = ensure_ctc_buffers(h, B, Bp, T, Tp, Lmax, &grew);
+  if (KSa < 0) return KSa;
   ok &= h->X0.ensure(R * h->Fp * 4, &grew);
   ok &= h->seqbuf.ensure((size_t)Bp * 4, &grew);
   ok &= h->dout.ensure(R * D * Hp * 4, &grew);
@@ -62,26 +88,11 @@ int ensure_shape(nasr_ctx* h, int B, int T, int Lmax) {
       ok &= h->scws.ensure(tph_scale_ws_floats((int)R, std::max(ipmax, wmax)) * 4, &g2);
     }
   }
-  ok &= h->logits.ensure((size_t)Tp * Bp * h->Cp * 4, &grew);
-  ok &= h->logz.ensure((size_t)Tp * Bp * 4, &grew);
-  const int KSa = KS <= 1 ? 2 : KS <= 8 ? KS : (KS <= 12 ? 12 : 16);   // kernel instantiations (two states per lane at least: ctc.hip (2b))
-  ok &= h->alpha.ensure((size_t)B * (T + 8) * KSa * 64 * 4, &grew);
-  ok &= h->beta.ensure((size_t)B * (T + 8) * KSa * 64 * 4, &grew);
-  ok &= h->aoff.ensure((size_t)B * (T + 8) * 8, &grew);
-  ok &= h->boff.ensure((size_t)B * (T + 8) * 8, &grew);
-  ok &= h->logp.ensure((size_t)Bp * 8, &grew);
-  ok &= h->ctcprobs.ensure((size_t)Tp * Bp * h->Cp * 4, &grew);              // emission rows of the CTC lattice (ctc.hip (2b))
-  ok &= h->ctckexp.ensure((size_t)B * 2 * ((T + 8) / 4 + 3) * 8, &grew);     // its column offsets per group of frames
-  ok &= h->nll.ensure((size_t)Bp * 4, &grew);
-  ok &= h->loss.ensure(16, &grew);
   int csw = std::max(D * N4, h->Cp);
   for (int i = 0; i < h->ndense; ++i) csw = std::max(csw, h->dWp[i]);
   // column-sum partials: 32 rows of launch_colsum, or the 64-row partials of the split pass (tp_split2_parts)
   ok &= h->csws.ensure((size_t)std::max(32, tp_split2_parts((int)R)) * csw * 4, &grew);
   if (h->wg_overlap) ok &= h->csws2.ensure((size_t)std::max(32, tp_split2_parts((int)R)) * csw * 4, &grew);
-  ok &= h->amax.ensure((size_t)Tp * Bp * 4, &grew);
-  ok &= h->ids.ensure((size_t)B * Tp * 4, &grew);
-  ok &= h->lens.ensure((size_t)Bp * 4, &grew);
   for (int i = 0; i < h->ndense; ++i) {
     ok &= h->Ybuf[i].ensure(R * h->dWp[i] * 4, &grew);
     ok &= h->dYbuf[i].ensure(R * h->dWp[i] * 4, &grew);
@@ -105,7 +116,7 @@ int validate_batch(nasr_ctx* h, const int32_t* seq_len, const int32_t* labels, c
     if (seq_len[b] < 1 || seq_len[b] > T)
       return h->fail(NASR_ERR_ARG, "seq_len[" + std::to_string(b) + "] out of [1,T]");
     if (!labels) continue;
-    if (h->las) {   // dense labels: every entry is fed to the decoder, any class is a label, no CTC feasibility
+    if (h->family == Family::Las) {   // dense labels: every entry is fed to the decoder, any class is a label, no CTC feasibility
       if (label_len[b] < 0 || label_len[b] > Lmax)
         return h->fail(NASR_ERR_ARG, "label_len[" + std::to_string(b) + "] out of [0,Lmax]");
       for (int i = 0; i < Lmax; ++i) {
@@ -179,7 +190,7 @@ int slot_fill(nasr_ctx* h, BatchSlot* s, const float* feats, const int32_t* seq_
   int rc = validate_batch(h, seq_len, labels, label_len, B, T, Lmax);
   if (rc) return rc;
   HIPCHK(h, hipSetDevice(h->device));
-  const int Bp = rup(B, 16), Tp = h->las ? T : nasr_logit_frames(h, T), C = h->C, Lm = std::max(labels ? Lmax : 0, 1);
+  const int Bp = rup(B, 16), Tp = h->family == Family::Las ? T : nasr_logit_frames(h, T), C = h->C, Lm = std::max(labels ? Lmax : 0, 1);
   const bool sr = h->cfg.merge == NASR_MERGE_STACK_RESHAPE && h->D == 2;
   // meta layout (int32): seq [Bp] | lablen [Bp] | labels [B*Lm] | cstart [B*(C+1)] | cpos [B*Lm] | rowmap [Tp*Bp]
   s->o_seq = 0;
@@ -326,12 +337,13 @@ int slot_commit(nasr_ctx* h, BatchSlot* s) {
                             h->X0.as<float>(), B, Bp, T, s->ctx, s->ncep, h->Fp, h->st);
     else
       launch_pack_feats(s->dfeats.as<float>(), h->X0.as<float>(), B, Bp, T, h->F, h->Fp, h->st);
-    if (!h->wn && !h->las)   // (the WaveNet's and LAS's GEMMs read the fp32 features as they are)
+    const bool lstm = h->family == Family::Lstm;
+    if (lstm)   // (the WaveNet's and LAS's GEMMs read the fp32 features as they are)
       pl_scales(h, h->X0.as<float>(), T * Bp, h->Fp, h->Fp, &h->sc_x0r, &h->sc_x0c, h->st);
     if (h->cmp_rows)    // the feature rows' scales in the compacted order (layer 0's input GEMM)
       launch_gather_rows(h->sc_cx.sp(), h->sc_x0r.sp(), h->vrow_p, h->cmp_rows_p, 1.f, h->st),
       launch_gather_rows(h->sc_cx.ip(), h->sc_x0r.ip(), h->vrow_p, h->cmp_rows_p, 1.f, h->st);
-    if (s->has_labels && h->npre == 0 && !h->wn && !h->las)   // layer-0 input with the frame index as contraction index, for dWx = X^T dG
+    if (s->has_labels && h->npre == 0 && lstm)   // layer-0 input with the frame index as contraction index, for dWx = X^T dG
       launch_tph_split2(h->X0.as<float>(), nullptr, h->X0TTP.as<unsigned char>(), h->cmp_rows ? h->cmp_rows : T * Bp, h->Fp, h->Fp,
                         nullptr, 1.f, h->sc_x0c.sp(), 1.f, nullptr, h->st, h->cmp_rows ? h->vrow_p : nullptr);
     HIPCHK(h, hipGetLastError());

@@ -4,7 +4,7 @@
 //   nasr_rec.hip     the recurrence's kind: create-time set-up and census, resident launches, abort check, re-arming
 //   nasr_batch.hip   batch buffers and slots: upload, stage / commit
 //   nasr_pass.hip    forward, CTC, backward: the orchestration of one step on the handle's streams
-//   nasr_api.hip     the C ABI entry points
+//   nasr_api.hip     the C ABI entry points; what the create calls share (handle_open, alloc_param_buffers, handle_finish)
 //   nasr_comm.hip    RCCL bound with dlopen: nasr_comm_*
 //   nasr_wavenet.hip the WaveNet handle (nasr_create_wavenet): its layout, buffers, BN state and pass
 //   nasr_las.hip     the LAS handle (nasr_create_las): its layout, buffers, sampling state and pass
@@ -172,6 +172,9 @@ struct BatchSlot {
 // the kinds of kernels that run the recurrence; the values are the codes of nasr_get_recurrence_mode
 enum class RecKind { Step = 0, Persist = 1, Wide = 2 };
 
+// which create call made the handle: what the common calls run on it, and which of the state pointers below it owns
+enum class Family { Lstm, WaveNet, Las, Featurizer };
+
 // What a WaveNet handle holds beyond the common parts (nasr_wavenet.hip); NULL on every other handle.
 struct WnState;
 struct WnStateDelete { void operator()(WnState* w) const; };
@@ -191,6 +194,7 @@ using namespace nasr_impl;
 struct nasr_ctx {
 
   nasr_model_cfg cfg;
+  Family family = Family::Lstm;
   std::unique_ptr<WnState, WnStateDelete> wn;   // a WaveNet handle (nasr_create_wavenet); the LSTM members stay unused
   std::unique_ptr<FzState, FzStateDelete> fz;   // a featurizer handle (nasr_create_featurizer): no model at all
   std::unique_ptr<LasState, LasStateDelete> las;   // a LAS handle (nasr_create_las); the LSTM members stay unused
@@ -400,7 +404,14 @@ namespace nasr_impl {
 // the first statement of every model call: a featurizer handle answers NASR_ERR_STATE
 #define MODEL_CALL(h)                                                                                     \
   do {                                                                                                    \
-    if ((h) && (h)->fz) return (h)->fail(NASR_ERR_STATE, std::string(__func__) + ": a featurizer handle has no model"); \
+    if ((h) && (h)->family == Family::Featurizer)                                                         \
+      return (h)->fail(NASR_ERR_STATE, std::string(__func__) + ": a featurizer handle has no model");     \
+  } while (0)
+// behind it, in the calls that only the (Bi)LSTM families answer: LSTM_CALL(h, "has no dropout")
+#define LSTM_CALL(h, reason)                                                                              \
+  do {                                                                                                    \
+    if ((h) && (h)->family != Family::Lstm)                                                               \
+      return (h)->fail(NASR_ERR_STATE, std::string(__func__) + ": a WaveNet or LAS handle " reason);      \
   } while (0)
 // ---- tiled fp16 planes (gemm_tph.hip) ---------------------------------------------------------------------------
 inline size_t pl_rb_bytes(int nkb) { return (size_t)nkb * 2 * 1024; }   // one 32-row block: nkb k-blocks x 2 parts x 1 KiB
@@ -427,6 +438,16 @@ inline ActScale dense_in_scale(const nasr_ctx* h, int i) {
   if (i < h->npre) return act_y(h, i - 1);
   return act_out(h);                               // the post stage reads the top LSTM layer
 }
+
+// ---- nasr_api.hip: what the create calls share (a failure leaves its message in g_create_error)
+// behind create call fn's own argument checks: a gfx950 device, a new handle on it with the device set and its stream
+// (the caller's, or one of its own) in place; prop: the device's properties, or NULL
+int handle_open(const char* fn, Family family, int device_id, void* stream, nasr_ctx** out, hipDeviceProp_t* prop);
+int create_fail(nasr_ctx* h, int code, const std::string& m);   // destroys the handle
+bool alloc_param_buffers(nasr_ctx* h);   // P, M, V, G behind its head and Adam's state for np_int floats, zeroed
+// once h->buckets is laid out: their events, the copy and logits streams, the batch slots' events, the step-result stamps
+// and step-end words, the timing events; then a synchronise.  A failure destroys the handle.
+int handle_finish(nasr_ctx* h);
 
 // ---- nasr_layout.hip
 int build_layout(nasr_ctx* h);
@@ -471,6 +492,9 @@ void rec_images(nasr_ctx* h);
 
 // ---- nasr_batch.hip
 int ensure_shape(nasr_ctx* h, int B, int T, int Lmax);
+// the logits and what the CTC lattice, its loss and the greedy decoder work in (T frames, Tp logit frames); returns the
+// lattice kernel's instantiation for labels up to Lmax (h->KS), or the code of a failure (< 0)
+int ensure_ctc_buffers(nasr_ctx* h, int B, int Bp, int T, int Tp, int Lmax, bool* grew);
 bool pinned_ensure(Pinned<void>& p, size_t* cap, size_t bytes);
 void slot_set_state(nasr_ctx* h, BatchSlot* s, int st);
 int slot_commit(nasr_ctx* h, BatchSlot* s);
@@ -496,7 +520,12 @@ inline const float* lstm_input(nasr_ctx* h, int l) {
 }
 
 // ---- nasr_pass.hip
+// the fp32 GEMM g (gemm.hip) on the handle's stream; g.split_k > 1 gets the handle's slab workspace, grown to fit
+int gemm_f32(nasr_ctx* h, GemmDesc g);
 int forward(nasr_ctx* h);
+// forward pass and loss of the resident batch.  training: the WaveNet's batch norm on the batch's statistics (a LAS
+// handle samples either way, one counter value per pass)
+int loss_pass(nasr_ctx* h, bool training);
 CtcDims ctc_dims(nasr_ctx* h);
 int ctc_forward(nasr_ctx* h);
 int backward(nasr_ctx* h);
@@ -506,8 +535,6 @@ int fetch_logits(nasr_ctx* h, float* logits_out);
 int wn_ensure_shape(nasr_ctx* h, int B, int T, int Lmax);
 int wn_forward(nasr_ctx* h, bool training);
 int wn_backward(nasr_ctx* h);
-// the common tail of nasr_create_wavenet / nasr_create_las (streams, events, stamps; one gradient bucket)
-int single_bucket_handle_setup(nasr_ctx* h, std::string* err);
 
 // ---- nasr_las.hip (the LAS handle's side of ensure_shape, forward and backward; its loss is part of its forward pass)
 int las_ensure_shape(nasr_ctx* h, int B, int T, int Lmax);

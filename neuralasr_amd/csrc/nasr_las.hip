@@ -3,8 +3,8 @@
 // directions over every padded frame) and an attention decoder (BasicLSTMCell(500) in an AttentionWrapper with
 // unnormalised Bahdanau attention over the top layer's output, attention layer 250, projection to the classes), trained
 // with scheduled sampling and sequence_loss.  This file holds the handle's create call, parameter layout, buffers and the
-// forward / backward pass; the kernels are in las.hip and gemm.hip.  Batches, Adam, gradient exchange and checkpoints are
-// the common code.  DESIGN.md §10.
+// forward / backward pass; the kernels are in las.hip and gemm.hip.  Opening and finishing the handle, batches, Adam, gradient
+// exchange and checkpoints are the common code.  DESIGN.md §10.
 #include "nasr_ctx.h"
 #include "las.h"
 #include "las_beam.h"
@@ -76,13 +76,7 @@ int las_gemm(nasr_ctx* h, const float* A, const float* B, float* C, int M, int N
   g.a_rows = a_rows >= 0 ? a_rows : (a_col ? K : M);
   g.bias = bias;
   g.split_k = bias ? 1 : gemm_pick_split(M, N, K);
-  if (g.split_k > 1) {
-    bool grew = false;
-    if (!h->slabs.ensure((size_t)g.split_k * M * N * 4, &grew)) return h->fail(NASR_ERR_HIP, "slab workspace allocation failed");
-    g.slabs = h->slabs.as<float>();
-  }
-  launch_gemm(g, h->st);
-  return NASR_OK;
+  return gemm_f32(h, g);
 }
 }  // namespace
 
@@ -581,37 +575,13 @@ int nasr_create_las(const nasr_las_cfg* cfg, int device_id, void* stream, nasr_h
     g_create_error = "nasr_create_las: sampling_probability must be in [0,1]";
     return NASR_ERR_ARG;
   }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) {
-    g_create_error = "nasr_create_las: no HIP device visible (libnasr has no CPU fallback)";
-    return NASR_ERR_HIP;
-  }
-  if (device_id < 0 || device_id >= ndev) {
-    g_create_error = "nasr_create_las: device_id out of range";
-    return NASR_ERR_ARG;
-  }
-  hipDeviceProp_t prop;
-  if (hipGetDeviceProperties(&prop, device_id) != hipSuccess) {
-    g_create_error = "nasr_create_las: hipGetDeviceProperties failed";
-    return NASR_ERR_HIP;
-  }
-  if (std::string(prop.gcnArchName).find("gfx950") == std::string::npos) {
-    g_create_error = std::string("nasr_create_las: device is ") + prop.gcnArchName + ", libnasr is built for gfx950 only";
-    return NASR_ERR_HIP;
-  }
-  nasr_ctx* h = new nasr_ctx();
-  auto bail = [&](int code, const std::string& m) {
-    g_create_error = m;
-    nasr_destroy(h);
-    return code;
-  };
-  memset(&h->cfg, 0, sizeof(h->cfg));
+  nasr_ctx* h = nullptr;
+  if (int rc = handle_open("nasr_create_las", Family::Las, device_id, stream, &h, nullptr)) return rc;
   h->cfg.feature_size = cfg->feature_size;
   h->cfg.num_classes = cfg->num_classes;
   h->cfg.merge = NASR_MERGE_NONE;
   h->cfg.learning_rate = cfg->learning_rate;
   h->cfg.beta1 = cfg->beta1; h->cfg.beta2 = cfg->beta2; h->cfg.epsilon = cfg->epsilon;
-  h->device = device_id;
   h->lr = cfg->learning_rate;
   h->graph_mode = false;
   h->las.reset(new LasState());
@@ -619,26 +589,10 @@ int nasr_create_las(const nasr_las_cfg* cfg, int device_id, void* stream, nasr_h
   s.cfg = *cfg;
   s.p = cfg->sampling_probability;
   s.seed = cfg->seed;
-  if (hipSetDevice(device_id) != hipSuccess) return bail(NASR_ERR_HIP, "hipSetDevice failed");
-  if (stream)
-    h->st.borrow(reinterpret_cast<hipStream_t>(stream));
-  else if (hipStreamCreateWithFlags(h->st.out(), hipStreamNonBlocking) != hipSuccess)
-    return bail(NASR_ERR_HIP, "hipStreamCreate failed");
   las_layout(h);
-  const size_t nb = (size_t)h->np_int * 4, gb = nb + GRAD_HEAD * 4;
-  if (hipMalloc(h->P.out(), nb) != hipSuccess || hipMalloc(h->M.out(), nb) != hipSuccess || hipMalloc(h->V.out(), nb) != hipSuccess ||
-      hipMalloc(h->Gbase.out(), gb) != hipSuccess || hipMalloc(h->adam_dev.out(), sizeof(AdamDev)) != hipSuccess)
-    return bail(NASR_ERR_HIP, "hipMalloc of parameter buffers failed");
-  (void)hipMemsetAsync(h->adam_dev, 0, sizeof(AdamDev), h->st);
-  (void)hipMemsetAsync(h->P, 0, nb, h->st);
-  (void)hipMemsetAsync(h->M, 0, nb, h->st);
-  (void)hipMemsetAsync(h->V, 0, nb, h->st);
-  (void)hipMemsetAsync(h->Gbase, 0, gb, h->st);
-  h->G = h->Gbase + GRAD_HEAD;
-  if (int rc = single_bucket_handle_setup(h, &g_create_error)) {
-    const std::string m = g_create_error;
-    return bail(rc, m);
-  }
+  if (!alloc_param_buffers(h)) return create_fail(h, NASR_ERR_HIP, "hipMalloc of parameter buffers failed");
+  h->buckets.push_back({0, GRAD_HEAD + h->np_int});   // one bucket: the whole gradient, complete at the end of the backward pass
+  if (int rc = handle_finish(h)) return rc;
   *out = h;
   return NASR_OK;
 }

@@ -70,6 +70,14 @@ float* ensure_slabs(nasr_ctx* h, int split, int M, int N) {
   return h->slabs.as<float>();
 }
 
+int gemm_f32(nasr_ctx* h, GemmDesc g) {
+  g.slabs = ensure_slabs(h, g.split_k, g.M, g.N);
+  if (g.split_k > 1 && !g.slabs) return h->fail(NASR_ERR_HIP, "slab workspace allocation failed");
+  launch_gemm(g, h->st);
+  HIPCHK(h, hipGetLastError());
+  return NASR_OK;
+}
+
 // operand scales of layer l's dG (rows = frames: sc_gr, optional; columns = gates: sc_gc): from the maxima the persistent
 // BPTT kernel took while it stored dG, or by a pass over dG
 void dg_scales(nasr_ctx* h, int l, int R, bool rows, hipStream_t st) {
@@ -191,8 +199,11 @@ int dense_backward(nasr_ctx* h, int i, const float* X, float* dX) {
 
 int forward(nasr_ctx* h) {
   if (!h->resident) return h->fail(NASR_ERR_STATE, "no resident batch: call nasr_upload_batch first");
-  if (h->wn) return wn_forward(h, false);   // forward-only calls: inference-mode batch norm
-  if (h->las) return h->fail(NASR_ERR_STATE, "a LAS handle has no CTC logits: use nasr_las_forward");
+  switch (h->family) {
+    case Family::WaveNet: return wn_forward(h, false);   // forward-only calls: inference-mode batch norm
+    case Family::Las: return h->fail(NASR_ERR_STATE, "a LAS handle has no CTC logits: use nasr_las_forward");
+    default: break;
+  }
   const int Bp = h->Bp, T = h->T, D = h->D, Hp = h->Hp;
   const int R = T * Bp;
   h->n_fwd_launch = 0;
@@ -240,10 +251,7 @@ int forward(nasr_ctx* h) {
     g.bias = h->P + h->off_b;
     // N = Cp (32 for the 29 classes) gives the 128-row tiles of gemm.hip one block column: split K to fill the chip
     g.split_k = gemm_pick_split(g.M, g.N, g.K);
-    g.slabs = ensure_slabs(h, g.split_k, g.M, g.N);
-    if (g.split_k > 1 && !g.slabs) g.split_k = 1;
-    launch_gemm(g, h->st);
-    HIPCHK(h, hipGetLastError());
+    if (int rc = gemm_f32(h, g)) return rc;
   }
   h->have_fwd = true;
   return NASR_OK;
@@ -302,6 +310,16 @@ int ctc_forward(nasr_ctx* h) {
   }
   HIPCHK(h, hipGetLastError());
   return NASR_OK;
+}
+
+int loss_pass(nasr_ctx* h, bool training) {
+  int rc;
+  switch (h->family) {
+    case Family::Las: return las_forward(h, true);   // the sequence loss is part of its forward pass
+    case Family::WaveNet: rc = wn_forward(h, training); break;
+    default: rc = forward(h); break;                 // clears the step's fault word
+  }
+  return rc ? rc : ctc_forward(h);
 }
 
 // weight / bias gradients of layer l from its complete dG, on stream ws: the main stream, or (side = true) the side stream
@@ -389,8 +407,11 @@ int wg_join(nasr_ctx* h, int l) {
 }
 
 int backward(nasr_ctx* h) {
-  if (h->wn) return wn_backward(h);
-  if (h->las) return las_backward(h);
+  switch (h->family) {
+    case Family::WaveNet: return wn_backward(h);
+    case Family::Las: return las_backward(h);
+    default: break;
+  }
   const int Bp = h->Bp, T = h->T, D = h->D, Hp = h->Hp;
   const int R = T * Bp, Rp = h->Tp * Bp;
   const bool sr = h->cfg.merge == NASR_MERGE_STACK_RESHAPE && D == 2;
@@ -417,9 +438,7 @@ int backward(nasr_ctx* h) {
     g.lda = sr ? Hp : h->Pinp; g.ldb = h->Cp; g.ldc = h->Cp;
     g.a_col = true; g.a_map = sr ? h->rowmap_p : nullptr; g.a_rows = sr ? 2 * R : R;
     g.split_k = gemm_pick_split(g.M, g.N, g.K);
-    g.slabs = ensure_slabs(h, g.split_k, g.M, g.N);
-    if (g.split_k > 1 && !g.slabs) return h->fail(NASR_ERR_HIP, "slab workspace allocation failed");
-    launch_gemm(g, h->st);
+    if (int rc = gemm_f32(h, g)) return rc;
     launch_colsum(h->logits.as<float>(), Rp, h->Cp, h->Cp, h->G + h->off_b, h->csws.as<float>(), h->st);
     // dOut_last = scatter(dlogits W^T)
     GemmDesc x{};
@@ -429,8 +448,7 @@ int backward(nasr_ctx* h) {
     x.M = Rp; x.N = h->Pinp; x.K = h->Cp;
     x.lda = h->Cp; x.ldb = h->Cp; x.ldc = sr ? Hp : h->Pinp;
     x.b_col = true; x.a_rows = Rp; x.c_map = sr ? h->rowmap_p : nullptr; x.split_k = 1;
-    launch_gemm(x, h->st);
-    HIPCHK(h, hipGetLastError());
+    if (int rc = gemm_f32(h, x)) return rc;
   }
   if (h->has_post) {
     PhaseScope ps(h, PH_WGRAD);

@@ -187,14 +187,14 @@ void rec_images(nasr_ctx* h) {
 
 extern "C" int nasr_get_recurrence_mode(nasr_handle h) {
   MODEL_CALL(h);
-  if (h && (h->wn || h->las)) return h->fail(NASR_ERR_STATE, "nasr_get_recurrence_mode: a WaveNet or LAS handle has no recurrence");
+  LSTM_CALL(h, "has no recurrence");
   return h ? (int)h->rec_use : 0;
 }
 
 extern "C" int nasr_set_recurrence_mode(nasr_handle h, int persistent) {
   MODEL_CALL(h);
   if (!h) return NASR_ERR_ARG;
-  if (h->wn || h->las) return h->fail(NASR_ERR_STATE, "nasr_set_recurrence_mode: a WaveNet or LAS handle has no recurrence");
+  LSTM_CALL(h, "has no recurrence");
   if (persistent && h->rec_kind != RecKind::Wide && (h->rec_kind == RecKind::Step || h->rec_refused))
     return h->fail(NASR_ERR_STATE, "the persistent recurrence is not available on this device / hidden size");
   HIPCHK(h, hipStreamSynchronize(h->st));

@@ -3,7 +3,7 @@
 // 1x1 convolution with batch norm and tanh, residual and skip outputs), a 1x1 convolution with batch norm and tanh over the
 // skip sum and a last 1x1 convolution to the classes.  Every convolution is bias-free.  This file holds the handle's
 // create call, parameter layout, buffers, batch-norm state and the forward / backward pass; the kernels are in wavenet.hip
-// and gemm.hip.  Everything else of the step (batches, CTC, decoders, Adam, gradient exchange) is the common code.
+// and gemm.hip.  Everything else (opening and finishing the handle, batches, CTC, decoders, Adam, gradient exchange) is the common code.
 #include "nasr_ctx.h"
 #include "wavenet.h"
 
@@ -45,14 +45,7 @@ int wn_gemm(nasr_ctx* h, const float* A, const float* B, float* C, int M, int N,
   g.a_col = a_col; g.b_col = b_col;
   g.a_rows = a_col ? K : M;
   g.split_k = gemm_pick_split(M, N, K);
-  if (g.split_k > 1) {
-    bool grew = false;
-    if (!h->slabs.ensure((size_t)g.split_k * M * N * 4, &grew)) return h->fail(NASR_ERR_HIP, "slab workspace allocation failed");
-    g.slabs = h->slabs.as<float>();
-  }
-  launch_gemm(g, h->st);
-  HIPCHK(h, hipGetLastError());
-  return NASR_OK;
+  return gemm_f32(h, g);
 }
 
 // Parameter names, TF order, and the map into the internal layout (nasr_tensor_info, nasr_get/set_params).
@@ -127,27 +120,12 @@ int wn_ensure_shape(nasr_ctx* h, int B, int T, int Lmax) {
   const int Bp = rup(B, 16);
   const size_t R = (size_t)T * Bp;
   const int D = w.D;
-  const int KS = std::max(1, (2 * std::max(Lmax, 0) + 1 + 63) / 64);
-  if (KS > 16) return h->fail(NASR_ERR_ARG, "label length > 511 not supported by the CTC lattice kernel");
   bool grew = false, ok = true;
-  // the common parts: features and the CTC lattice's buffers (as for the LSTM handles)
+  // the common parts: the CTC lattice's buffers (as for the LSTM handles) and the features
+  const int KSa = ensure_ctc_buffers(h, B, Bp, T, T, Lmax, &grew);
+  if (KSa < 0) return KSa;
   ok &= h->X0.ensure(R * h->Fp * 4, &grew);
   ok &= h->seqbuf.ensure((size_t)Bp * 4, &grew);
-  ok &= h->logits.ensure(R * h->Cp * 4, &grew);
-  ok &= h->logz.ensure(R * 4, &grew);
-  const int KSa = KS <= 1 ? 2 : KS <= 8 ? KS : (KS <= 12 ? 12 : 16);
-  ok &= h->alpha.ensure((size_t)B * (T + 8) * KSa * 64 * 4, &grew);
-  ok &= h->beta.ensure((size_t)B * (T + 8) * KSa * 64 * 4, &grew);
-  ok &= h->aoff.ensure((size_t)B * (T + 8) * 8, &grew);
-  ok &= h->boff.ensure((size_t)B * (T + 8) * 8, &grew);
-  ok &= h->logp.ensure((size_t)Bp * 8, &grew);
-  ok &= h->ctcprobs.ensure(R * h->Cp * 4, &grew);
-  ok &= h->ctckexp.ensure((size_t)B * 2 * ((T + 8) / 4 + 3) * 8, &grew);
-  ok &= h->nll.ensure((size_t)Bp * 4, &grew);
-  ok &= h->loss.ensure(16, &grew);
-  ok &= h->amax.ensure(R * 4, &grew);
-  ok &= h->ids.ensure((size_t)B * T * 4, &grew);
-  ok &= h->lens.ensure((size_t)Bp * 4, &grew);
   // the WaveNet's activations (kept for the backward pass) and scratch
   const size_t a = R * D * 4, nb = (size_t)std::max(w.nblk, 1);
   ok &= w.Y0.ensure(a, &grew) && w.Z.ensure((nb + 1) * a, &grew);
@@ -299,44 +277,6 @@ int wn_backward(nasr_ctx* h) {
   return NASR_OK;
 }
 
-
-// The set-up the WaveNet and LAS handles share once their parameter buffers exist: one gradient bucket (the whole array,
-// completed at the end of the backward pass) with its event, the copy and logits streams, the batch slots' events, the
-// step-result stamps and step-end words, the timing events; then a synchronise.  A failure leaves its message in *err.
-int single_bucket_handle_setup(nasr_ctx* h, std::string* err) {
-  auto bail = [&](int code, const char* m) { *err = m; return code; };
-  h->buckets.push_back({0, GRAD_HEAD + h->np_int});
-  h->ev_bucket.resize(1);
-  if (hipEventCreateWithFlags(h->ev_bucket[0].out(), hipEventDisableTiming) != hipSuccess)
-    return bail(NASR_ERR_HIP, "hipEventCreate failed");
-  if (hipStreamCreateWithFlags(h->cst.out(), hipStreamNonBlocking) != hipSuccess ||
-      hipStreamCreateWithFlags(h->d2h.out(), hipStreamNonBlocking) != hipSuccess ||
-      hipEventCreateWithFlags(h->ev_snap.out(), hipEventDisableTiming) != hipSuccess)
-    return bail(NASR_ERR_HIP, "hipStreamCreate failed");
-  for (BatchSlot& bs : h->slots)
-    if (hipEventCreateWithFlags(bs.ev_copy.out(), hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(bs.ev_released.out(), hipEventDisableTiming) != hipSuccess)
-      return bail(NASR_ERR_HIP, "hipEventCreate failed");
-  for (auto& r : h->res) {
-    if (hipHostMalloc(r.stamp.out(), 64, hipHostMallocMapped) != hipSuccess)
-      return bail(NASR_ERR_HIP, "set-up of the step-result stamps failed");
-    *r.stamp = 0;
-  }
-  for (auto& e : h->endw) {
-    if (hipHostMalloc(e.host.out(), 64, hipHostMallocMapped) != hipSuccess)
-      return bail(NASR_ERR_HIP, "set-up of the step-end words failed");
-    e.stamp = reinterpret_cast<uint32_t*>(e.host.get()) + 8;
-    *e.host = 0.f;
-    *e.stamp = 0;
-  }
-  (void)hipEventCreate(h->ev_total_a.out());
-  (void)hipEventCreate(h->ev_total_b.out());
-  memset(&h->last_times, 0, sizeof(h->last_times));
-  if (hipGetLastError() != hipSuccess || hipStreamSynchronize(h->st) != hipSuccess)
-    return bail(NASR_ERR_HIP, "stream synchronize failed in create");
-  return NASR_OK;
-}
-
 }  // namespace nasr_impl
 
 void nasr_impl::WnStateDelete::operator()(WnState* w) const { delete w; }
@@ -374,37 +314,13 @@ int nasr_create_wavenet(const nasr_wavenet_cfg* cfg, int device_id, void* stream
     g_create_error = "nasr_create_wavenet: bn_epsilon must be > 0 and bn_decay in [0,1)";
     return NASR_ERR_ARG;
   }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) {
-    g_create_error = "nasr_create_wavenet: no HIP device visible (libnasr has no CPU fallback)";
-    return NASR_ERR_HIP;
-  }
-  if (device_id < 0 || device_id >= ndev) {
-    g_create_error = "nasr_create_wavenet: device_id out of range";
-    return NASR_ERR_ARG;
-  }
-  hipDeviceProp_t prop;
-  if (hipGetDeviceProperties(&prop, device_id) != hipSuccess) {
-    g_create_error = "nasr_create_wavenet: hipGetDeviceProperties failed";
-    return NASR_ERR_HIP;
-  }
-  if (std::string(prop.gcnArchName).find("gfx950") == std::string::npos) {
-    g_create_error = std::string("nasr_create_wavenet: device is ") + prop.gcnArchName + ", libnasr is built for gfx950 only";
-    return NASR_ERR_HIP;
-  }
-  nasr_ctx* h = new nasr_ctx();
-  auto bail = [&](int code, const std::string& m) {
-    g_create_error = m;
-    nasr_destroy(h);
-    return code;
-  };
-  memset(&h->cfg, 0, sizeof(h->cfg));
+  nasr_ctx* h = nullptr;
+  if (int rc = handle_open("nasr_create_wavenet", Family::WaveNet, device_id, stream, &h, nullptr)) return rc;
   h->cfg.feature_size = cfg->feature_size;
   h->cfg.num_classes = cfg->num_classes;
   h->cfg.merge = NASR_MERGE_NONE;
   h->cfg.learning_rate = cfg->learning_rate;
   h->cfg.beta1 = cfg->beta1; h->cfg.beta2 = cfg->beta2; h->cfg.epsilon = cfg->epsilon;
-  h->device = device_id;
   h->lr = cfg->learning_rate;
   h->graph_mode = false;
   h->wn.reset(new WnState());
@@ -416,35 +332,20 @@ int nasr_create_wavenet(const nasr_wavenet_cfg* cfg, int device_id, void* stream
     for (int r = 0; r < cfg->num_rates; ++r) w.rate.push_back(cfg->rates[r]);
   w.eps = cfg->bn_epsilon;
   w.omd = (float)(1.0 - (double)cfg->bn_decay);
-  if (hipSetDevice(device_id) != hipSuccess) return bail(NASR_ERR_HIP, "hipSetDevice failed");
-  if (stream)
-    h->st.borrow(reinterpret_cast<hipStream_t>(stream));
-  else if (hipStreamCreateWithFlags(h->st.out(), hipStreamNonBlocking) != hipSuccess)
-    return bail(NASR_ERR_HIP, "hipStreamCreate failed");
   wn_layout(h);
-  const size_t nb = (size_t)h->np_int * 4, gb = nb + GRAD_HEAD * 4, sb = (size_t)w.S * w.D * 4;
-  if (hipMalloc(h->P.out(), nb) != hipSuccess || hipMalloc(h->M.out(), nb) != hipSuccess || hipMalloc(h->V.out(), nb) != hipSuccess ||
-      hipMalloc(h->Gbase.out(), gb) != hipSuccess || hipMalloc(h->adam_dev.out(), sizeof(AdamDev)) != hipSuccess)
-    return bail(NASR_ERR_HIP, "hipMalloc of parameter buffers failed");
+  const size_t sb = (size_t)w.S * w.D * 4;
+  if (!alloc_param_buffers(h)) return create_fail(h, NASR_ERR_HIP, "hipMalloc of parameter buffers failed");
   if (hipMalloc(w.mm.out(), sb) != hipSuccess || hipMalloc(w.mv.out(), sb) != hipSuccess ||
       hipMalloc(w.biased.out(), sb) != hipSuccess || hipMalloc(w.bmean.out(), sb) != hipSuccess ||
       hipMalloc(w.bvar.out(), sb) != hipSuccess || hipMalloc(w.bvup.out(), sb) != hipSuccess ||
       hipMalloc(w.ws.out(), (size_t)WN_STAT_WS * 4) != hipSuccess)
-    return bail(NASR_ERR_HIP, "hipMalloc of the batch-norm state failed");
-  (void)hipMemsetAsync(h->adam_dev, 0, sizeof(AdamDev), h->st);
-  (void)hipMemsetAsync(h->P, 0, nb, h->st);
-  (void)hipMemsetAsync(h->M, 0, nb, h->st);
-  (void)hipMemsetAsync(h->V, 0, nb, h->st);
-  (void)hipMemsetAsync(h->Gbase, 0, gb, h->st);
-  h->G = h->Gbase + GRAD_HEAD;
+    return create_fail(h, NASR_ERR_HIP, "hipMalloc of the batch-norm state failed");
   // moving mean 0, moving variance 1 (contrib batch_norm's initialisers), zero-debias accumulator 0
   (void)hipMemsetAsync(w.mm, 0, sb, h->st);
   (void)hipMemsetAsync(w.biased, 0, sb, h->st);
   launch_fill(w.mv, 1.f, w.S * w.D, h->st);
-  if (int rc = single_bucket_handle_setup(h, &g_create_error)) {
-    const std::string m = g_create_error;
-    return bail(rc, m);
-  }
+  h->buckets.push_back({0, GRAD_HEAD + h->np_int});   // one bucket: the whole gradient, complete at the end of the backward pass
+  if (int rc = handle_finish(h)) return rc;
   *out = h;
   return NASR_OK;
 }

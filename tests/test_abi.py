@@ -31,14 +31,40 @@ def test_structs_match_header_layout():
     assert ctypes.sizeof(_lib.PhaseTimes) == 9 * 4 + 2 * 4
 
 
-def test_no_cpu_fallback_without_gpu():
+def _create_calls():
+    """name -> (C function, a valid create call, [(a create call with bad arguments of the family's own, its message)])"""
+    from neuralasr_amd.engine import Engine, LasEngine, WaveNetEngine
+    from neuralasr_amd.features import Featurizer
+    return {
+        'Engine': ('nasr_create', lambda: Engine(8, 16, 1, True, 'stack_reshape', 5),
+                   [(lambda: Engine(8, 16, 1, True, 'stack_reshape', 1), 'num_classes >= 2')]),
+        'WaveNetEngine': ('nasr_create_wavenet', lambda: WaveNetEngine(39, 29),
+                          [(lambda: WaveNetEngine(39, 29, dim=64), 'dim = 128'),
+                           (lambda: WaveNetEngine(39, 29, kernel_size=5), 'kernel_size = 7')]),
+        'LasEngine': ('nasr_create_las', lambda: LasEngine(39, 29),
+                      [(lambda: LasEngine(39, 29, num_hidden=128), 'num_hidden = 250')]),
+        'Featurizer': ('nasr_create_featurizer', lambda: Featurizer(16000, 13, 2),
+                       [(lambda: Featurizer(16000, 0, 2), 'nasr_create_featurizer: ')]),
+    }
+
+
+@pytest.mark.parametrize('name', ['Engine', 'WaveNetEngine', 'LasEngine', 'Featurizer'])
+def test_no_cpu_fallback_without_gpu(name):
+    """Every create call refuses a machine without a device in the same words, after its own argument checks."""
     import torch
     if torch.cuda.is_available():
         pytest.skip('GPU present')
     from neuralasr_amd import _lib
-    from neuralasr_amd.engine import Engine
-    with pytest.raises(_lib.NasrError, match='no HIP device|no CPU fallback'):
-        Engine(8, 16, 1, True, 'stack_reshape', 5)
+    fn, create, bad_calls = _create_calls()[name]
+    with pytest.raises(_lib.NasrError) as e:
+        create()
+    assert e.value.code == _lib.NASR_ERR_HIP
+    assert str(e.value) == f'libnasr error {_lib.NASR_ERR_HIP}: {fn}: no HIP device visible (libnasr has no CPU fallback)'
+    for bad, text in bad_calls:
+        with pytest.raises(_lib.NasrError) as e:
+            bad()
+        assert e.value.code == _lib.NASR_ERR_ARG and str(e.value).startswith(f'libnasr error {_lib.NASR_ERR_ARG}: {fn}: ')
+        assert text in str(e.value) and 'no HIP device' not in str(e.value)
 
 
 def test_product_package_never_imports_the_oracle():
