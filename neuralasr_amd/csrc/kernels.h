@@ -111,10 +111,16 @@ void launch_lstm_bwd_step(const LstmDims& dm, int s, const float* Ub, const floa
                           float* dcout, const int* seq_len, hipStream_t st);
 
 // ---- persistent recurrence (lstm_persist.hip): one launch per layer pass, one XCD per (direction, utterance slice) ----
-struct PersistCtl {            // device words, zeroed before every launch
-  unsigned xcc_count[8];       // ticket per XCD: member index of a workgroup inside its group
-  unsigned error;              // bit 0: a bounded spin gave up, bit 1: placement is not 32 workgroups on each of 8 XCDs
-  unsigned pad[23];
+// the head of every resident kernel's control block (the first bytes of PersistCtl and WideCtl): placement and abort,
+// served by join_xcd() / raise_error() of lstm_device.h
+struct XcdCtl {                // device words, zeroed before every launch
+  unsigned xcc_count[8];       // ticket per XCD: member index of a workgroup inside its XCD
+  unsigned error;              // bit 0: a bounded spin gave up, bit 1: placement is not 32 workgroups on each of 8 XCDs,
+                               // bit 2 (wide BPTT): dG left the fp16 range of its planes
+  unsigned pad[23];            // (diagnostic build of tools/persistbench: the phase cycles of workgroup (0,0)'s wave 0)
+};
+static_assert(sizeof(XcdCtl) == 32 * sizeof(unsigned), "the control blocks' head is 32 words");
+struct PersistCtl : XcdCtl {
   unsigned flags[8 * 128];     // per group: forward 32 words (one per member), BPTT 128 (member*4 + wave)
 #if defined(NASR_PSTAMP) && NASR_PSTAMP
   unsigned stamps[256][12];    // diagnostic build only (tools/persistbench): wave 0's phase cycles of EVERY workgroup
@@ -149,11 +155,7 @@ void launch_lstm_persist_bwd(const LstmDims& dm, const float* Upb, const float* 
 size_t persist_dgmax_floats(int T, int Bp, int Hp, int D);
 
 // ---- wide persistent forward recurrence (lstm_wide.hip): Hp = 2048, one launch per direction over all 256 CUs ----
-struct WideCtl {               // device words, zeroed before every launch
-  unsigned xcc_count[8];
-  unsigned error;              // bit 0: a bounded spin gave up, bit 1: placement is not 32 workgroups on each of 8 XCDs,
-                               // bit 2 (BPTT): dG left the fp16 range of its planes
-  unsigned pad[23];
+struct WideCtl : XcdCtl {
   unsigned stamps[160];        // diagnostic build (NASR_WSTAMP, tools/widebench): phase cycles of two workgroups' waves
 };
 struct WideGeom {

@@ -221,13 +221,10 @@ __global__ __launch_bounds__(256) void lstm_fwd_step_kernel(
 #pragma unroll
       for (int gi = 0; gi < 4; ++gi)
         g[gi] = red[0][cmt][ls + gi][rg] + red[1][cmt][ls + gi][rg] + red[2][cmt][ls + gi][rg] + red[3][cmt][ls + gi][rg];
-      const float si = sigmoidf_(xg.x + g[0]);
-      const float tj = tanhf_(xg.y + g[1]);
-      const float sf = sigmoidf_(xg.z + g[2] + fb);
-      const float so = sigmoidf_(xg.w + g[3]);
-      const float c = cprev * sf + si * tj;
-      const float h = tanhf_(c) * so;
-      *reinterpret_cast<float4*>(gates + (size_t)r * DN + d * N4 + 4 * j) = make_float4(si, tj, sf, so);
+      const f32x4 act = lstm_gates((f32x4){xg.x + g[0], xg.y + g[1], xg.z + g[2], xg.w + g[3]}, fb);
+      float c = cprev;
+      const float h = lstm_state(act, c);
+      *reinterpret_cast<float4*>(gates + (size_t)r * DN + d * N4 + 4 * j) = to_float4(act);
       cbuf[(size_t)r * DH + d * Hp + j] = c;
       out[(size_t)r * DH + d * Hp + j] = h;
       *hdst = h;
@@ -239,30 +236,17 @@ __global__ __launch_bounds__(256) void lstm_fwd_step_kernel(
   }
 }
 
+using StepMT = std::integer_sequence<int, 1, 2, 3, 4>;   // MT = Bp/16 M tiles of the step kernels
+
 void launch_lstm_fwd_step(const LstmDims& dm, int s, const float* Uf, const float* hin, float* hout, float* gates,
                           float* cbuf, float* out, const int* seq_len, float forget_bias, hipStream_t st) {
   dim3 grid(dm.Hp / 4, dm.D), block(256);
-  const int MT = dm.Bp / 16, nq = dm.Hp / 64;
-#define NASR_FWD(MTV, NQV)                                                                                     \
-  hipLaunchKernelGGL((lstm_fwd_step_kernel<MTV, NQV>), grid, block, 0, st, Uf, hin, hout, gates, cbuf, out, \
-                     seq_len, s, dm.T, dm.Bp, dm.Hp, dm.D, forget_bias)
-#define NASR_FWD_NQ(MTV)                                  \
-  switch (nq) {                                           \
-    case 1: NASR_FWD(MTV, 1); break;                      \
-    case 2: NASR_FWD(MTV, 2); break;                      \
-    case 4: NASR_FWD(MTV, 4); break;                      \
-    case 8: NASR_FWD(MTV, 8); break;                      \
-    case 16: NASR_FWD(MTV, 16); break;                    \
-    default: NASR_FWD(MTV, 0); break;                     \
-  }
-  switch (MT) {
-    case 1: NASR_FWD_NQ(1); break;
-    case 2: NASR_FWD_NQ(2); break;
-    case 3: NASR_FWD_NQ(3); break;
-    default: NASR_FWD_NQ(4); break;
-  }
-#undef NASR_FWD_NQ
-#undef NASR_FWD
+  dispatch_int(StepMT{}, dm.Bp / 16, [&](auto mt) {
+    dispatch_int(std::integer_sequence<int, 1, 2, 4, 8, 16, 0>{}, dm.Hp / 64, [&](auto nq) {   // NQ = Hp/64, 0 = the generic form
+      hipLaunchKernelGGL((lstm_fwd_step_kernel<mt(), nq()>), grid, block, 0, st, Uf, hin, hout, gates, cbuf, out, seq_len, s,
+                         dm.T, dm.Bp, dm.Hp, dm.D, forget_bias);
+    });
+  });
 }
 
 // ------------------------------------------------------------------ BPTT step
@@ -360,7 +344,6 @@ __global__ __launch_bounds__(256) void lstm_bwd_step_kernel(
       a[e] = *reinterpret_cast<const float4*>(gates + (size_t)r * DN + d * N4 + 4 * j);  // si,tj,sf,so
       cc[e] = cbuf[(size_t)r * DH + d * Hp + j];
       cpv[e] = cbuf[(size_t)(val[e] ? rp : r) * DH + d * Hp + j];
-      if (s == 0) cpv[e] = 0.f;
       dh[e] = dout[(size_t)r * DH + d * Hp + j];
       dci[e] = dcin[((size_t)d * Bp + b) * Hp + j];
       const float* pp = pbase + (size_t)b * Hp + j;
@@ -385,13 +368,7 @@ __global__ __launch_bounds__(256) void lstm_bwd_step_kernel(
         float dhs = dh[e];
 #pragma unroll
         for (int k = 0; k < KV; ++k) dhs += pv[e][k];
-        const float tc = tanhf_(cc[e]);
-        const float dct = dci[e] + dhs * a[e].w * (1.f - tc * tc);
-        dg.x = dct * a[e].y * a[e].x * (1.f - a[e].x);
-        dg.y = dct * a[e].x * (1.f - a[e].y * a[e].y);
-        dg.z = dct * cpv[e] * a[e].z * (1.f - a[e].z);
-        dg.w = dhs * tc * a[e].w * (1.f - a[e].w);
-        dcn = dct * a[e].z;
+        dg = to_float4(lstm_cell_bwd(to_f32x4(a[e]), cc[e], cpv[e], s == 0, dhs, dci[e], dcn));
       }
       if (jt == 0) {   // the frame of a masked step is frame s itself (past seq_len in both directions): dG = 0 there
         const size_t row = val[e] ? (size_t)rr[e] : (size_t)s * Bp + b;
@@ -477,14 +454,8 @@ __global__ __launch_bounds__(256) void lstm_bwd_cell_kernel(const float* __restr
     dhs += s0 + s1;
     const float4 a = *reinterpret_cast<const float4*>(gates + r * DN + d * N4 + 4 * j);
     const float cc = cbuf[r * DH + d * Hp + j];
-    const float cpv = s > 0 ? cbuf[(d ? r + Bp : r - Bp) * DH + d * Hp + j] : 0.f;
-    const float tc = tanhf_(cc);
-    const float dct = dcin[((size_t)d * Bp + b) * Hp + j] + dhs * a.w * (1.f - tc * tc);
-    dg.x = dct * a.y * a.x * (1.f - a.x);
-    dg.y = dct * a.x * (1.f - a.y * a.y);
-    dg.z = dct * cpv * a.z * (1.f - a.z);
-    dg.w = dhs * tc * a.w * (1.f - a.w);
-    dcn = dct * a.z;
+    const float cpv = s > 0 ? cbuf[(d ? r + Bp : r - Bp) * DH + d * Hp + j] : 0.f;   // (no frame before the first one to read)
+    dg = to_float4(lstm_cell_bwd(to_f32x4(a), cc, cpv, s == 0, dhs, dcin[((size_t)d * Bp + b) * Hp + j], dcn));
   }
   *reinterpret_cast<float4*>(dgbuf + r * DN + d * N4 + 4 * j) = dg;
   dcout[((size_t)d * Bp + b) * Hp + j] = dcn;
@@ -498,44 +469,24 @@ int lstm_bwd_partials(int Hp) { return bwd_wide_form(Hp) ? Hp / (32 * BWD_KSL) :
 void launch_lstm_bwd_step(const LstmDims& dm, int s, const float* Ub, const float* pin, float* pout,
                           const float* gates, float* dgbuf, const float* cbuf, const float* dout, const float* dcin,
                           float* dcout, const int* seq_len, hipStream_t st) {
-  const int MT = dm.Bp / 16, ksp = dm.Hp / 32;
   if (bwd_wide_form(dm.Hp)) {     // wide layer: cell arithmetic once, then the product (see the kernel's header)
     const int np = dm.Hp / (32 * BWD_KSL);
     hipLaunchKernelGGL(lstm_bwd_cell_kernel, dim3((dm.Bp * dm.Hp + 255) / 256, dm.D), dim3(256), 0, st, pin, np, gates, dgbuf,
                        cbuf, dout, dcin, dcout, seq_len, s, dm.Bp, dm.Hp, dm.D);
     dim3 gridw((dm.Hp / 64) * np, dm.D);
-#define NASR_BWDW(MTV)                                                                                              \
-  hipLaunchKernelGGL((lstm_bwd_step_kernel<MTV, 0, true, BWD_KSL>), gridw, dim3(256), 0, st, Ub, pin, pout, gates, dgbuf, cbuf, \
-                     dout, dcin, dcout, seq_len, s, dm.T, dm.Bp, dm.Hp, dm.D)
-    switch (MT) {
-      case 1: NASR_BWDW(1); break;
-      case 2: NASR_BWDW(2); break;
-      case 3: NASR_BWDW(3); break;
-      default: NASR_BWDW(4); break;
-    }
-#undef NASR_BWDW
+    dispatch_int(StepMT{}, dm.Bp / 16, [&](auto mt) {
+      hipLaunchKernelGGL((lstm_bwd_step_kernel<mt(), 0, true, BWD_KSL>), gridw, dim3(256), 0, st, Ub, pin, pout, gates, dgbuf,
+                         cbuf, dout, dcin, dcout, seq_len, s, dm.T, dm.Bp, dm.Hp, dm.D);
+    });
     return;
   }
   dim3 grid((dm.Hp / 64) * (dm.Hp / 32), dm.D), block(256);
-#define NASR_BWD(MTV, KV)                                                                                        \
-  hipLaunchKernelGGL((lstm_bwd_step_kernel<MTV, KV>), grid, block, 0, st, Ub, pin, pout, gates, dgbuf, cbuf, \
-                     dout, dcin, dcout, seq_len, s, dm.T, dm.Bp, dm.Hp, dm.D)
-#define NASR_BWD_K(MTV)                                   \
-  switch (ksp) {                                          \
-    case 2: NASR_BWD(MTV, 2); break;                      \
-    case 4: NASR_BWD(MTV, 4); break;                      \
-    case 8: NASR_BWD(MTV, 8); break;                      \
-    case 16: NASR_BWD(MTV, 16); break;                    \
-    default: NASR_BWD(MTV, 0); break;                     \
-  }
-  switch (MT) {
-    case 1: NASR_BWD_K(1); break;
-    case 2: NASR_BWD_K(2); break;
-    case 3: NASR_BWD_K(3); break;
-    default: NASR_BWD_K(4); break;
-  }
-#undef NASR_BWD_K
-#undef NASR_BWD
+  dispatch_int(StepMT{}, dm.Bp / 16, [&](auto mt) {
+    dispatch_int(std::integer_sequence<int, 2, 4, 8, 16, 0>{}, dm.Hp / 32, [&](auto ksp) {   // KSP = Hp/32, 0 = the generic form
+      hipLaunchKernelGGL((lstm_bwd_step_kernel<mt(), ksp()>), grid, block, 0, st, Ub, pin, pout, gates, dgbuf, cbuf, dout,
+                         dcin, dcout, seq_len, s, dm.T, dm.Bp, dm.Hp, dm.D);
+    });
+  });
 }
 
 }  // namespace nasr

@@ -37,68 +37,21 @@
 #include <cstdlib>
 
 #ifndef NASR_PSTAMP
-#define NASR_PSTAMP 0   // 1: wave 0 of one workgroup accumulates s_memtime deltas per phase into PersistCtl::pad (tools/persistbench)
+#define NASR_PSTAMP 0   // 1: wave 0 of every workgroup accumulates s_memtime deltas per phase into PersistCtl::stamps (tools/persistbench)
 #endif
 
 namespace nasr {
 
 namespace {
 
-struct Stamps {
-  unsigned long long last;
-  unsigned acc[12];
-  bool on;
-  __device__ __forceinline__ void start(bool enable) {
-    on = enable;
-    for (int i = 0; i < 12; ++i) acc[i] = 0;
-    last = NASR_PSTAMP ? __builtin_amdgcn_s_memtime() : 0ull;
-  }
-  __device__ __forceinline__ void mark(int i) {
-#if NASR_PSTAMP
-    if (on) {
-      const unsigned long long t = __builtin_amdgcn_s_memtime();
-      acc[i] += (unsigned)(t - last);
-      last = t;
-    }
-#endif
-  }
-  __device__ __forceinline__ void flush(PersistCtl* ctl, unsigned slot, bool first) {
-#if NASR_PSTAMP
-    if (on && (threadIdx.x & 63) == 0) {
-      for (int i = 0; i < 12; ++i) ctl->stamps[slot & 255][i] = acc[i];
-      if (first)
-        for (int i = 0; i < 12; ++i) ctl->pad[i] = acc[i];
-    }
-#endif
-  }
-};
+using PStamps = Stamps<12, NASR_PSTAMP != 0>;
 
-// (xcc id, ticket within the XCD) of this workgroup; false when the placement is not 32-per-XCD-of-8
-__device__ __forceinline__ void raise_error(PersistCtl* ctl, unsigned* sticky, float* fault, unsigned code) {
-  atomicOr(&ctl->error, code);
-  if (fault) *fault = 1.f;   // sits behind the gradients: all-reduced with them, makes Adam a no-op on every rank
-  if (sticky) __hip_atomic_store(sticky, code, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);   // host-visible, never cleared by a launch
-}
-
-__device__ __forceinline__ bool join_group(PersistCtl* ctl, unsigned* sticky, float* fault, unsigned* info, unsigned& xcc,
-                                           unsigned& member) {
-  if (threadIdx.x == 0) {
-    const unsigned x = __builtin_amdgcn_s_getreg((3 << 11) | 20) & 15u;   // HW_REG_XCC_ID[3:0]
-    info[0] = x;
-    info[1] = x < 8 ? atomicAdd(&ctl->xcc_count[x], 1u) : 0xffffu;
-    info[2] = 0;
-    info[3] = 0;
-    info[4] = 0;
-    info[5] = 0;
-  }
-  __syncthreads();
-  xcc = info[0];
-  member = info[1];
-  if (xcc >= 8 || member >= 32) {
-    if (threadIdx.x == 0) raise_error(ctl, sticky, fault, 2u);
-    return false;
-  }
-  return true;
+// wave 0's phase sums of EVERY workgroup; those of workgroup (0,0) also where a plain build's PersistCtl has room
+__device__ __forceinline__ void flush_stamps(PStamps& stp, PersistCtl* ctl, unsigned slot) {
+#if NASR_PSTAMP
+  stp.flush(ctl->stamps[slot & 255]);
+  if (slot == 0) stp.flush(ctl->pad);
+#endif
 }
 
 }  // namespace
@@ -116,17 +69,13 @@ struct RepackOffs { long long o[PERSIST_MAX_MATS]; };
 //   Upf as 8-byte units [32 m][4 w][KW/4 bb][2 planes][64 lane]: the 4 halfs are units k = w*KW + 4*bb + 0..3 of the
 //   lane's column; plane 0 = fp16(U*s), plane 1 = fp16(U*s - plane 0).
 __global__ __launch_bounds__(256) void repack_persist_kernel(const float* __restrict__ P, RepackOffs off,
-                                                             float* __restrict__ Upf0, float* __restrict__ Upb0,
-                                                             long long imf, long long imb, int Hp,
+                                                             float* __restrict__ Upf0, long long imf, int Hp,
                                                              const float* __restrict__ cs0) {
   const float* __restrict__ U = P + off.o[blockIdx.y];
   float* __restrict__ Upf = Upf0 + (size_t)blockIdx.y * imf;
-  float* __restrict__ Upb = Upb0 + (size_t)blockIdx.y * imb;
   const int NU = Hp / 32, KW = 8 * NU, N4 = 4 * Hp;
-  const int NOG = (KW + 63) / 64, KB = NOG * 4 * NU;
-  const int64_t nf = (int64_t)32 * 4 * KW * 64, nb = (int64_t)32 * 4 * KB * 64;
+  const int64_t nf = (int64_t)32 * 4 * KW * 64;
   const int64_t nfe = cs0 ? nf / 4 : nf;      // fp16 image: one work item per (chunk of 4 units, lane)
-  (void)nb; (void)Upb; (void)KB;
   for (int64_t e0 = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e0 < nfe; e0 += (int64_t)gridDim.x * blockDim.x) {
     {
       const int lane = e0 & 63;
@@ -145,9 +94,10 @@ __global__ __launch_bounds__(256) void repack_persist_kernel(const float* __rest
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const float v = bp < NU ? U[(size_t)(w * KW + idx + r) * N4 + col] * sc : 0.f;
-          const _Float16 h1 = (_Float16)v;
+          _Float16 h1, h2;
+          split_f16x2(v, h1, h2);
           p1[r] = h1;
-          p2[r] = (_Float16)(v - (float)h1);
+          p2[r] = h2;
         }
         h4* dst = reinterpret_cast<h4*>(Upf) + ((((size_t)m * 4 + w) * (KW / 4) + idx / 4) * 2) * 64 + lane;
         dst[0] = p1;
@@ -190,8 +140,8 @@ void launch_repack_persist(const float* P, const int64_t* offs, int n, float* Up
     const int m = n - k0 < PERSIST_MAX_MATS ? n - k0 : PERSIST_MAX_MATS;
     RepackOffs off{};
     for (int k = 0; k < m; ++k) off.o[k] = offs[k0 + k];
-    hipLaunchKernelGGL(repack_persist_kernel, dim3(512, m), dim3(256), 0, st, P, off, Upf + (size_t)k0 * imf,
-                       Upb + (size_t)k0 * imb, imf, imb, Hp, col_scale ? col_scale + (size_t)k0 * 4 * Hp : nullptr);
+    hipLaunchKernelGGL(repack_persist_kernel, dim3(512, m), dim3(256), 0, st, P, off, Upf + (size_t)k0 * imf, imf, Hp,
+                       col_scale ? col_scale + (size_t)k0 * 4 * Hp : nullptr);
     const int NU = Hp / 32, NOG = (8 * NU + 63) / 64;
     hipLaunchKernelGGL(repack_persist_bwd_kernel, dim3(32 * 4 * NOG, m), dim3(256), 0, st, P, off, Upb + (size_t)k0 * imb, imb, Hp);
   }
@@ -246,7 +196,7 @@ __global__ __launch_bounds__(320, 1) void lstm_persist_fwd_kernel(
   unsigned* info = reinterpret_cast<unsigned*>(lds + LDS_INFO);
   const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
   unsigned xcc, member;
-  if (!join_group(ctl, sticky, gm.fault, info, xcc, member)) return;
+  if (!join_xcd(ctl, sticky, gm.fault, info, 4, xcc, member)) return;
   const int T = gm.T, Bp = gm.Bp, Hp = gm.Hp, D = gm.D;
   const int NGD = 8 / D, d = (int)xcc / NGD, grp = (int)xcc % NGD;
   const int N4 = 4 * Hp, DH = D * Hp, DN = D * N4;
@@ -281,10 +231,8 @@ __global__ __launch_bounds__(320, 1) void lstm_persist_fwd_kernel(
   const int jcl = j < Hp ? j : Hp - 1;
   const int hidx = (j >> 2) * 16 + q * 4 + (j & 3);
   bool aborted = false;
-  Stamps stp;
+  PStamps stp;
   stp.start(w == 0);
-  // epoch of the use of exchange buffer (s & 1) that step s of round rd is: uses alternate 1, 0, 1, ... from a cleared buffer
-  auto epoch_of = [&](int rd, int s) -> unsigned { return (unsigned)(rd * ((T + 1 - (s & 1)) >> 1) + (s >> 1) + 1) & 1u; };
 
   for (int rd = 0; rd < gm.rounds; ++rd) {
     const int b0 = (rd * NGD + grp) * gm.ub;
@@ -348,7 +296,7 @@ __global__ __launch_bounds__(320, 1) void lstm_persist_fwd_kernel(
               for (unsigned n = 0; n < (1u << 26) && (int)(*(lds_vu32*)(info + 5) - want) < 0; ++n) __builtin_amdgcn_s_sleep(1);
             }
             const float* src = ghx + (size_t)((s - 1) & 1) * Hp * 4 + ((size_t)w * KW * 4 + (size_t)lane * 4);
-            const unsigned eexp = epoch_of(rd, s - 1) << 30;
+            const unsigned eexp = use_epoch(rd, T, s - 1) << 30;
             const bool has0 = NCH >= 16 || lane < 4 * NCH, has1 = NJ == 2 && lane < 4 * (NCH - 16);
             bool need = true;
             ok = false;
@@ -370,8 +318,8 @@ __global__ __launch_bounds__(320, 1) void lstm_persist_fwd_kernel(
                          (__float_as_uint(P[NJ - 1][2]) ^ eexp) | (__float_as_uint(P[NJ - 1][3]) ^ eexp);
               need = (bad & 0x40000000u) != 0;
               if (!__any(need)) { ok = true; break; }
-#if NASR_PSTAMP
-              if (stp.on) stp.acc[11] += 1;      // extra attempts of wave 0
+#if NASR_PSTAMP   // (not even an empty call here: it changes how hipcc lays out the spin loop)
+              stp.add(11, 1);                    // extra attempts of wave 0
 #endif
             }
           }
@@ -457,7 +405,7 @@ __global__ __launch_bounds__(320, 1) void lstm_persist_fwd_kernel(
       __syncthreads();
       stp.mark(4);
 #if NASR_PSTAMP
-      if (stp.on) for (int i = 1; i < 5; ++i) stp.acc[6 + i] += info[8 + i] - info[8];   // arrival of wave i after wave 0 (mod 2^32)
+      for (int i = 1; i < 5; ++i) stp.add(6 + i, info[8 + i] - info[8]);   // arrival of wave i after wave 0 (mod 2^32)
 #endif
       // (the abort word is tested at the END of the iteration: tested here, its LDS round trip sat in front of the cell
       //  update's own reads on the cell wave's chain; an aborted step publishes garbage, which nobody uses)
@@ -474,15 +422,8 @@ __global__ __launch_bounds__(320, 1) void lstm_persist_fwd_kernel(
           const f32x4 g3 = *reinterpret_cast<const f32x4*>(rr + 768);
           const f32x4 xg = *reinterpret_cast<const f32x4*>(xgb + (par * 64 + lane) * 4);
           const f32x4 pre = xg + ((g0 + g1) + (g2 + g3));
-          f32x4 act;
-          act.x = sigmoidf_(pre.x);
-          act.y = tanhf_(pre.y);
-          act.z = sigmoidf_(pre.z + fb);
-          act.w = sigmoidf_(pre.w);
-          if (valid) {
-            c = c * act.z + act.x * act.y;
-            h = tanhf_(c) * act.w;
-          }
+          const f32x4 act = lstm_gates(pre, fb);
+          if (valid) h = lstm_state(act, c);
           if constexpr (F16) {
             // split h (|h| < 1) into its two fp16 parts of h * 2^14 HERE, once, instead of in every consumer wave of the
             // group (32 CUs x 4 waves redid these five operations per value on their MFMA chain): same arithmetic, same bits
@@ -493,7 +434,7 @@ __global__ __launch_bounds__(320, 1) void lstm_persist_fwd_kernel(
             // h2 U1 product by 8; both scalings are exact)
             const _Float16 h2 = (_Float16)((v - (float)h1) * 0.125f);
             const unsigned pk = (unsigned)__builtin_bit_cast(unsigned short, h1) |
-                                ((unsigned)__builtin_bit_cast(unsigned short, h2) << 16) | (epoch_of(rd, s) << 30);
+                                ((unsigned)__builtin_bit_cast(unsigned short, h2) << 16) | (use_epoch(rd, T, s) << 30);
             ghx[(size_t)par * Hp * 4 + hidx] = __uint_as_float(pk);
           } else {
             ghx[(size_t)par * Hp * 4 + hidx] = h;          // plain store: lands in this XCD's L2
@@ -518,7 +459,7 @@ __global__ __launch_bounds__(320, 1) void lstm_persist_fwd_kernel(
     __syncthreads();                  // the last cell update's results are in LDS
     if (w == 4) store_side(T - 1);
   }
-  stp.flush(ctl, xcc * 32 + member, xcc == 0 && member == 0);
+  flush_stamps(stp, ctl, xcc * 32 + member);
   if (aborted && tid == 0) raise_error(ctl, sticky, gm.fault, 1u);
 }
 
@@ -543,7 +484,7 @@ __global__ __launch_bounds__(320, 1) void lstm_persist_bwd_kernel(
   unsigned* info = reinterpret_cast<unsigned*>(lds + LDS_INFO);
   const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
   unsigned xcc, member;
-  if (!join_group(ctl, sticky, gm.fault, info, xcc, member)) return;
+  if (!join_xcd(ctl, sticky, gm.fault, info, 4, xcc, member)) return;
   const int T = gm.T, Bp = gm.Bp, Hp = gm.Hp, D = gm.D;
   const int NGD = 8 / D, d = (int)xcc / NGD, grp = (int)xcc % NGD;
   const int N4 = 4 * Hp, DH = D * Hp, DN = D * N4;
@@ -564,14 +505,10 @@ __global__ __launch_bounds__(320, 1) void lstm_persist_bwd_kernel(
   const int j = NU * (int)member + u;
   const int jcl = j < Hp ? j : Hp - 1;
   bool aborted = false;
-  Stamps stp;
+  PStamps stp;
   stp.start(w == 0);
   f32x4 cmax = (f32x4){0.f, 0.f, 0.f, 0.f};   // memory wave: running column maxima of this lane's (unit, utterance slot)
-  // epoch of the use of exchange buffer (k & 1) that step k of round rd is (uses alternate 1, 0, 1, ... from a cleared buffer)
-  // (the rounds a group runs come first - b0 grows with rd - so rd counts its uses.  The buffer is CLEARED before every
-  //  launch: the bit pattern the sums carry is then a function of the launch's shape alone, and two runs of the same
-  //  step give the same bits)
-  auto epoch_of = [&](int rd, int k) -> unsigned { return (unsigned)(rd * ((T + 1 - (k & 1)) >> 1) + (k >> 1) + 1) & 1u; };
+  // (use_epoch: the rounds a group runs come first - b0 grows with rd - so rd counts the uses of its exchange buffers)
 
   for (int rd = 0; rd < gm.rounds; ++rd) {
     const int b0 = (rd * NGD + grp) * gm.ub;
@@ -671,7 +608,7 @@ __global__ __launch_bounds__(320, 1) void lstm_persist_bwd_kernel(
           // the sums themselves say whether they are those of step k-1 - bit 0 of every word is the epoch of this use
           // of the buffer; a lane that finds a stale word loads its 32 again (one round trip when everybody is on time,
           // and no acknowledgement wait or flag on the producers' side)
-          const unsigned eexp = epoch_of(rd, k - 1);
+          const unsigned eexp = use_epoch(rd, T, k - 1);
           bool need = lane_ok;
           bool got = false;
           for (unsigned n = 0; n < SPIN_BUDGET; ++n) {
@@ -703,8 +640,8 @@ __global__ __launch_bounds__(320, 1) void lstm_persist_bwd_kernel(
             }
             need = lane_ok && (bad & 1u) != 0;
             if (!__any(need)) { got = true; break; }
-#if NASR_PSTAMP
-            if (stp.on) stp.acc[11] += 1;        // extra attempts
+#if NASR_PSTAMP   // (not even an empty call here: it changes how hipcc lays out the spin loop)
+            stp.add(11, 1);                      // extra attempts
 #endif
           }
 #undef NASR_LD8
@@ -720,15 +657,7 @@ __global__ __launch_bounds__(320, 1) void lstm_persist_bwd_kernel(
         // 2. gate derivatives of this CU's cells
         f32x4 dg = (f32x4){0.f, 0.f, 0.f, 0.f};
         float dcn = 0.f;
-        if (valid) {
-          const float tc = tanhf_(o.x);
-          const float dct = dc + dhs * a.w * (1.f - tc * tc);
-          dg.x = dct * a.y * a.x * (1.f - a.x);
-          dg.y = dct * a.x * (1.f - a.y * a.y);
-          dg.z = dct * (s > 0 ? o.y : 0.f) * a.z * (1.f - a.z);
-          dg.w = dhs * tc * a.w * (1.f - a.w);
-          dcn = dct * a.z;
-        }
+        if (valid) dg = lstm_cell_bwd(a, o.x, o.y, s == 0, dhs, dc, dcn);
         dc = dcn;
         if (lane_ok) {   // A image: adg[par][c = 4u+g][utterance q]
           float* ad = adg + par * 256 + 16 * u + q;
@@ -769,7 +698,7 @@ __global__ __launch_bounds__(320, 1) void lstm_persist_bwd_kernel(
         });
       });
       // 4. hand the partial rows to their consumers: unit k' -> consumer k'/NU, row element 4*(k'%NU) + utt
-      const unsigned eb = epoch_of(rd, k);
+      const unsigned eb = use_epoch(rd, T, k);
 #pragma unroll
       for (int og = 0; og < NOG; ++og) {
         f32x4 sum = (acc[og][0] + acc[og][1]) + (acc[og][2] + acc[og][3]);
@@ -800,7 +729,7 @@ __global__ __launch_bounds__(320, 1) void lstm_persist_bwd_kernel(
     }
     if (q == 0 && lane_ok) *reinterpret_cast<f32x4*>(colpart + ((size_t)grp * DN + (size_t)(d * N4 + 4 * j))) = cmax;
   }
-  stp.flush(ctl, xcc * 32 + member, xcc == 0 && member == 0);
+  flush_stamps(stp, ctl, xcc * 32 + member);
   if (aborted && tid == 0) raise_error(ctl, sticky, gm.fault, 1u);
 }
 
@@ -836,20 +765,19 @@ size_t persist_xch_floats(int Hp) {
   return f > b ? f : b;
 }
 
+using PersistNU = std::integer_sequence<int, 2, 4, 6, 8, 10, 12, 14, 16>;   // NU = Hp/32 the kernels are built for
+
 hipError_t persist_prepare() {
   hipError_t e = hipSuccess;
-#define NASR_PATTR(NUV)                                                                                             \
-  if (e == hipSuccess)                                                                                              \
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(&lstm_persist_fwd_kernel<NUV, false>),                    \
-                            hipFuncAttributeMaxDynamicSharedMemorySize, PERSIST_LDS_BYTES);                         \
-  if (e == hipSuccess)                                                                                              \
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(&lstm_persist_fwd_kernel<NUV, true>),                     \
-                            hipFuncAttributeMaxDynamicSharedMemorySize, PERSIST_LDS_BYTES);                         \
-  if (e == hipSuccess)                                                                                              \
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(&lstm_persist_bwd_kernel<NUV>),                           \
-                            hipFuncAttributeMaxDynamicSharedMemorySize, PERSIST_LDS_BYTES);
-  NASR_PATTR(2) NASR_PATTR(4) NASR_PATTR(6) NASR_PATTR(8) NASR_PATTR(10) NASR_PATTR(12) NASR_PATTR(14) NASR_PATTR(16)
-#undef NASR_PATTR
+  auto raise = [&](auto* kernel) {
+    if (e == hipSuccess)
+      e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, PERSIST_LDS_BYTES);
+  };
+  for_each_int(PersistNU{}, [&](auto nu) {
+    raise(&lstm_persist_fwd_kernel<nu(), false>);
+    raise(&lstm_persist_fwd_kernel<nu(), true>);
+    raise(&lstm_persist_bwd_kernel<nu()>);
+  });
   return e;
 }
 
@@ -862,24 +790,14 @@ void launch_lstm_persist_fwd(const LstmDims& dm, const float* Upf, const float* 
   // epoch-validated hand-off: the exchange buffers start from epoch 0 (ctl_zeroed: the caller cleared them with *ctl)
   if (cinv && !ctl_zeroed) (void)hipMemsetAsync(xch, 0, persist_hx_bytes(dm.Hp), st);
   dim3 grid(256), block(320);
-#define NASR_PF(NUV)                                                                                                  \
-  if (cinv)                                                                                                           \
-    hipLaunchKernelGGL((lstm_persist_fwd_kernel<NUV, true>), grid, block, PERSIST_LDS_BYTES, st, Upf, gates, cbuf, out,   \
-                       seq_len, xch, ctl, sticky, gm, forget_bias, cinv);                                               \
-  else                                                                                                                \
-    hipLaunchKernelGGL((lstm_persist_fwd_kernel<NUV, false>), grid, block, PERSIST_LDS_BYTES, st, Upf, gates, cbuf, out,  \
-                       seq_len, xch, ctl, sticky, gm, forget_bias, cinv)
-  switch (dm.Hp / 32) {
-    case 2: NASR_PF(2); break;
-    case 4: NASR_PF(4); break;
-    case 6: NASR_PF(6); break;
-    case 8: NASR_PF(8); break;
-    case 10: NASR_PF(10); break;
-    case 12: NASR_PF(12); break;
-    case 14: NASR_PF(14); break;
-    default: NASR_PF(16); break;
-  }
-#undef NASR_PF
+  dispatch_int(PersistNU{}, dm.Hp / 32, [&](auto nu) {
+    if (cinv)
+      hipLaunchKernelGGL((lstm_persist_fwd_kernel<nu(), true>), grid, block, PERSIST_LDS_BYTES, st, Upf, gates, cbuf, out, seq_len,
+                         xch, ctl, sticky, gm, forget_bias, cinv);
+    else
+      hipLaunchKernelGGL((lstm_persist_fwd_kernel<nu(), false>), grid, block, PERSIST_LDS_BYTES, st, Upf, gates, cbuf, out, seq_len,
+                         xch, ctl, sticky, gm, forget_bias, cinv);
+  });
 }
 
 void launch_lstm_persist_bwd(const LstmDims& dm, const float* Upb, const float* gates, float* dgbuf, const float* cbuf,
@@ -895,20 +813,10 @@ void launch_lstm_persist_bwd(const LstmDims& dm, const float* Upb, const float* 
   dim3 grid(256), block(320);
   // (lean only at Hp = 512, where the kernel's 5 x 220 VGPRs alone keep it at one workgroup per CU)
   const int bwd_lds = (lean && dm.Hp == 512) ? PERSIST_LDS_LEAN : PERSIST_LDS_BYTES;
-#define NASR_PB(NUV)                                                                                                   \
-  hipLaunchKernelGGL((lstm_persist_bwd_kernel<NUV>), grid, block, bwd_lds, st, Upb, gates, dgbuf, cbuf, dout, \
-                     seq_len, xch, ctl, sticky, gm, rowpart, colpart)
-  switch (dm.Hp / 32) {
-    case 2: NASR_PB(2); break;
-    case 4: NASR_PB(4); break;
-    case 6: NASR_PB(6); break;
-    case 8: NASR_PB(8); break;
-    case 10: NASR_PB(10); break;
-    case 12: NASR_PB(12); break;
-    case 14: NASR_PB(14); break;
-    default: NASR_PB(16); break;
-  }
-#undef NASR_PB
+  dispatch_int(PersistNU{}, dm.Hp / 32, [&](auto nu) {
+    hipLaunchKernelGGL((lstm_persist_bwd_kernel<nu()>), grid, block, bwd_lds, st, Upb, gates, dgbuf, cbuf, dout, seq_len, xch, ctl,
+                       sticky, gm, rowpart, colpart);
+  });
 }
 
 }  // namespace nasr

@@ -29,21 +29,6 @@
 #define NASR_WSTAMP 0   // 1: s_memtime deltas per phase -> WideCtl::stamps (tools/widebench)
 #endif
 
-// phase stamps (diagnostic build): every wave of workgroups (0,0) and (7,31) accumulates s_memtime deltas per phase
-#if NASR_WSTAMP
-#define WSTAMP_DECL unsigned long long tl = __builtin_amdgcn_s_memtime(); unsigned tacc[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0}
-#define WMARK(i) do { const unsigned long long t_ = __builtin_amdgcn_s_memtime(); tacc[i] += (unsigned)(t_ - tl); tl = t_; } while (0)
-#define WSTAMP_FLUSH                                                                                        \
-  do {                                                                                                      \
-    if (lane == 0 && (me == 0 || me == 255))                                                                \
-      for (int i = 0; i < 10; ++i) ctl->stamps[((me ? 8 : 0) + w) * 10 + i] = tacc[i]; \
-  } while (0)
-#else
-#define WSTAMP_DECL do { } while (0)
-#define WMARK(i) do { } while (0)
-#define WSTAMP_FLUSH do { } while (0)
-#endif
-
 namespace nasr {
 
 namespace {
@@ -66,13 +51,40 @@ __device__ __forceinline__ void st16_sc1(void* p, f32x4 v) {
 // wait for the asm loads above; the loaded value passes through the statement so that no copy of it is scheduled earlier
 __device__ __forceinline__ void wait_vm0(u32x4& v) { asm volatile("s_waitcnt vmcnt(0)" : "+v"(v) : : "memory"); }
 
-__device__ __forceinline__ void wide_raise(WideCtl* ctl, unsigned* sticky, float* fault, unsigned code) {
-  atomicOr(&ctl->error, code);
-  if (fault) *fault = 1.f;
-  // the FIRST cause stays in the host word (the timeouts it triggers in the other workgroups come half a second later)
-  if (sticky && __hip_atomic_load(sticky, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) == 0)
-    __hip_atomic_store(sticky, code, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+// Sentinel-polled inboxes: a block with ONE reader holds the sentinel (all ones, a NaN no arithmetic produces) until the data
+// land, so its words are polled themselves - no flag - and reset by the reader for the step after next.
+constexpr unsigned SENTINEL = 0xffffffffu;
+// every word of this 16-byte granule differs from the sentinel
+__device__ __forceinline__ bool landed(u32x4 t) { return t.x != SENTINEL && t.y != SENTINEL && t.z != SENTINEL && t.w != SENTINEL; }
+// loads the [MT][2] granules per lane at src (64 apart) until every word of every lane has landed; the granule stored last
+// first: when it is there the others mostly are.  false: the spin budget ran out.
+template <int MT>
+__device__ __forceinline__ bool poll_landed(const u32x4* src, u32x4 (&v)[MT][2]) {
+  for (unsigned n = 0; n < SPIN_BUDGET; ++n) {
+    v[MT - 1][1] = ld16_sc1(src + ((MT - 1) * 2 + 1) * 64);
+    wait_vm0(v[MT - 1][1]);
+    if (!__all(landed(v[MT - 1][1]))) continue;
+    bool all = true;
+#pragma unroll
+    for (int m = 0; m < MT; ++m)
+#pragma unroll
+      for (int p = 0; p < 2; ++p)
+        if (m != MT - 1 || p != 1) v[m][p] = ld16_sc1(src + (m * 2 + p) * 64);
+#pragma unroll
+    for (int m = 0; m < MT; ++m)
+#pragma unroll
+      for (int p = 0; p < 2; ++p)
+        if (m != MT - 1 || p != 1) {
+          wait_vm0(v[m][p]);
+          all = all && landed(v[m][p]);
+        }
+    if (__all(all)) return true;
+  }
+  return false;
 }
+
+// every wave of workgroups (0,0) and (7,31) stamps its phases -> WideCtl::stamps [16 waves][10]
+using WStamps = Stamps<10, NASR_WSTAMP != 0>;
 
 }  // namespace
 
@@ -99,9 +111,10 @@ __global__ __launch_bounds__(256) void repack_wide_kernel(const float* __restric
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       const float v = U[(size_t)(k0 + j) * N4 + col] * sc;
-      const _Float16 a = (_Float16)v;
+      _Float16 a, b;
+      split_f16x2(v, a, b);
       p1[j] = a;
-      p2[j] = (_Float16)(v - (float)a);
+      p2[j] = b;
     }
     u32x4* dst = Uw + (e >> 6) * 128 + l;
     dst[0] = __builtin_bit_cast(u32x4, p1);
@@ -143,19 +156,9 @@ __global__ __launch_bounds__(512, 1) void lstm_wide_fwd_kernel(
   const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
 
   // ---- placement: XCD id = row slice x, ticket = member nb
-  if (tid == 0) {
-    const unsigned xi = __builtin_amdgcn_s_getreg((3 << 11) | 20) & 15u;   // HW_REG_XCC_ID[3:0]
-    info[0] = xi;
-    info[1] = xi < 8 ? atomicAdd(&ctl->xcc_count[xi], 1u) : 0xffffu;
-    info[2] = 0;
-    info[3] = 0;
-  }
-  __syncthreads();
-  const int x = (int)info[0], nb = (int)info[1];
-  if (x >= 8 || nb >= 32) {
-    if (tid == 0) wide_raise(ctl, sticky, gm.fault, 2u);
-    return;
-  }
+  unsigned xcc, member;
+  if (!join_xcd(ctl, sticky, gm.fault, info, 2, xcc, member)) return;
+  const int x = (int)xcc, nb = (int)member;
   const int T = gm.T, Bp = gm.Bp, Hp = gm.Hp, D = gm.D, d = gm.d;
   const int KS = Hp / 8, N4 = 4 * Hp, DH = D * Hp, DN = D * N4;
   const int me = x * 32 + nb;
@@ -187,12 +190,13 @@ __global__ __launch_bounds__(512, 1) void lstm_wide_fwd_kernel(
   const unsigned xoff = (unsigned)(rowok ? cb : 0) * (unsigned)DN + (unsigned)(d * N4 + 4 * u);
   auto frame_of = [&](int s) { return (rowok && s < len) ? (d ? len - 1 - s : s) : 0; };
   bool aborted = false;
-  WSTAMP_DECL;
+  WStamps stp;
+  stp.start(me == 0 || me == 255);
 
   for (int s = 0; s < T; ++s) {
     const int par = s & 1;
     bool ok = true;
-    WMARK(0);
+    stp.mark(0);
     // gate pre-activations of this step's frame (x W + b, from the hoisted GEMM): in flight during the whole product phase
     f32x4 xg = (f32x4){0.f, 0.f, 0.f, 0.f};
     if (cell) xg = *reinterpret_cast<const f32x4*>(gates + (xoff + (unsigned)frame_of(s) * xstep));
@@ -211,9 +215,9 @@ __global__ __launch_bounds__(512, 1) void lstm_wide_fwd_kernel(
         for (unsigned n = 0; n < (1u << 24) && (int)(*(lds_vu32*)(info + 3) - want) < 0; ++n)
           __builtin_amdgcn_s_sleep(1);
       }
-      WMARK(1);
+      stp.mark(1);
       if (ok) {
-        const unsigned em = ((((unsigned)(s - 1) >> 1) + 1u) & 1u) ? 0x40004000u : 0u;
+        const unsigned em = use_epoch(0, T, s - 1) ? 0x40004000u : 0u;
         bool need = true;
         ok = false;
         for (unsigned n = 0; n < SPIN_BUDGET; ++n) {
@@ -249,9 +253,9 @@ __global__ __launch_bounds__(512, 1) void lstm_wide_fwd_kernel(
         info[2] = 1;
       }
     }
-    WMARK(2);
+    stp.mark(2);
     __syncthreads();                                        // #1: the A operand is in LDS
-    WMARK(3);
+    stp.mark(3);
     if (s > 0 && !info[2]) {
       // 2. + 3. partial pre-activations of destination slice w over this XCD's 256 contraction rows, one 16 x 16 tile
       // at a time; each tile leaves for workgroup (w, nb) as soon as it is complete (its write-through acknowledgement
@@ -260,7 +264,7 @@ __global__ __launch_bounds__(512, 1) void lstm_wide_fwd_kernel(
       // (the sentinel stores this wave made as a CONSUMER one step ago are acknowledged: whoever sees the partial sums
       //  below and later overwrites a slot this wave reset finds the reset already in memory)
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      WMARK(5);
+      stp.mark(5);
       static_for<0, MT>([&](auto mc) {
         constexpr int m = decltype(mc)::value;
         // both 16 x 16 tiles of this M tile together; the A fragments of k-tile kt+1 are read while kt multiplies (the
@@ -301,55 +305,31 @@ __global__ __launch_bounds__(512, 1) void lstm_wide_fwd_kernel(
           Plds[((x * MT + m) * 2 + 1) * 64 + lane] = t1;
         }
       });
-      WMARK(4);
-      // 4. the 7 partial sums of the own units that other XCDs computed: wave w fetches source slice w.  No flag: the
-      // inbox holds a sentinel (all ones, a NaN no arithmetic produces) until the data land; the words are polled
-      // themselves, then reset for the step after next (this parity's next use).
+      stp.mark(4);
+      // 4. the 7 partial sums of the own units that other XCDs computed: wave w fetches source slice w from its
+      // sentinel-polled inbox, then resets it for the step after next (this parity's next use).
       if (w != x) {
-        float* src = part + ((((size_t)par * 256 + me) * 8 + w) * MT * 2) * 256 + lane * 4;
+        u32x4* src = reinterpret_cast<u32x4*>(part) + ((((size_t)par * 256 + me) * 8 + w) * MT * 2) * 64 + lane;
         u32x4 v[MT][2];
-        ok = false;
-        for (unsigned n = 0; n < SPIN_BUDGET; ++n) {
-          // the tile stored last first: when it is there the others mostly are
-          v[MT - 1][1] = ld16_sc1(src + ((MT - 1) * 2 + 1) * 256);
-          wait_vm0(v[MT - 1][1]);
-          const u32x4 q = v[MT - 1][1];
-          if (!__all(q.x != 0xffffffffu && q.y != 0xffffffffu && q.z != 0xffffffffu && q.w != 0xffffffffu)) continue;
-          bool all = true;
-#pragma unroll
-          for (int m = 0; m < MT; ++m)
-#pragma unroll
-            for (int h2 = 0; h2 < 2; ++h2)
-              if (m != MT - 1 || h2 != 1) v[m][h2] = ld16_sc1(src + (m * 2 + h2) * 256);
-#pragma unroll
-          for (int m = 0; m < MT; ++m)
-#pragma unroll
-            for (int h2 = 0; h2 < 2; ++h2)
-              if (m != MT - 1 || h2 != 1) {
-                wait_vm0(v[m][h2]);
-                const u32x4 t = v[m][h2];
-                all = all && t.x != 0xffffffffu && t.y != 0xffffffffu && t.z != 0xffffffffu && t.w != 0xffffffffu;
-              }
-          if (__all(all)) { ok = true; break; }
-        }
-        WMARK(6);
+        ok = poll_landed<MT>(src, v);
+        stp.mark(6);
         if (ok) {
-          const f32x4 sent = __builtin_bit_cast(f32x4, (u32x4){0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu});
+          const f32x4 sent = __builtin_bit_cast(f32x4, (u32x4){SENTINEL, SENTINEL, SENTINEL, SENTINEL});
 #pragma unroll
           for (int m = 0; m < MT; ++m)
 #pragma unroll
             for (int h2 = 0; h2 < 2; ++h2) {
               Plds[((w * MT + m) * 2 + h2) * 64 + lane] = __builtin_bit_cast(f32x4, v[m][h2]);
-              st16_sc1(src + (m * 2 + h2) * 256, sent);
+              st16_sc1(src + (m * 2 + h2) * 64, sent);
             }
         } else {
           info[2] = 1;
         }
       }
     }
-    WMARK(7);
+    stp.mark(7);
     __syncthreads();                                        // #2: the 8 partial sums are in LDS
-    WMARK(8);
+    stp.mark(8);
     const unsigned abort_word = info[2];
     // 5. cell update of (row cb, unit ci): sum of the 8 sources in fixed order
     if (cell) {
@@ -365,23 +345,16 @@ __global__ __launch_bounds__(512, 1) void lstm_wide_fwd_kernel(
         }
       }
       const f32x4 pre = xg + g;
-      f32x4 act;
-      act.x = sigmoidf_(pre.x);
-      act.y = tanhf_(pre.y);
-      act.z = sigmoidf_(pre.z + fb);
-      act.w = sigmoidf_(pre.w);
+      const f32x4 act = lstm_gates(pre, fb);
       float h = 0.f;
-      if (valid) {
-        c = c * act.z + act.x * act.y;
-        h = tanhf_(c) * act.w;
-      }
+      if (valid) h = lstm_state(act, c);
       // (|2h| is kept below 2 - tanh and the sigmoid saturate to exactly 1 - so that plane 0's exponent field stays below 16;
       //  the residual of that clamp, 2^-10, is exact in plane 1)
       const float hv = fminf(fmaxf(h * 2.f, -1.9990234375f), 1.9990234375f);
       const _Float16 h1 = (_Float16)hv;
       const _Float16 h2v = (_Float16)((h * 2.f - (float)h1) * 1024.f);
-      // bit 14 of every half = the epoch of this use of the buffer (uses alternate 1, 0, 1, ... from a cleared buffer)
-      const unsigned short eb = ((((unsigned)s >> 1) + 1u) & 1u) ? 0x4000u : 0u;
+      // bit 14 of every half = the epoch of this use of the buffer
+      const unsigned short eb = use_epoch(0, T, s) ? 0x4000u : 0u;
       reinterpret_cast<unsigned short*>(hp)[(0 * ROWS + cb) * 8 + ci] = __builtin_bit_cast(unsigned short, h1) | eb;
       reinterpret_cast<unsigned short*>(hp)[(1 * ROWS + cb) * 8 + ci] = __builtin_bit_cast(unsigned short, h2v) | eb;
       __builtin_amdgcn_wave_barrier();
@@ -407,11 +380,11 @@ __global__ __launch_bounds__(512, 1) void lstm_wide_fwd_kernel(
         }
       }
     }
-    WMARK(9);
+    stp.mark(9);
     if (abort_word) { aborted = true; break; }
   }
-  WSTAMP_FLUSH;
-  if (aborted && tid == 0) wide_raise(ctl, sticky, gm.fault, 1u);
+  stp.flush(ctl->stamps + ((me ? 8 : 0) + w) * 10);
+  if (aborted && tid == 0) raise_error(ctl, sticky, gm.fault, 1u);
 }
 
 // ------------------------------------------------------------------ BPTT
@@ -448,9 +421,10 @@ __global__ __launch_bounds__(256) void repack_wide_bwd_kernel(const float* __res
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       const float v = src[j] * sc;
-      const _Float16 a = (_Float16)v;
+      _Float16 a, b;
+      split_f16x2(v, a, b);
       p1[j] = a;
-      p2[j] = (_Float16)(v - (float)a);
+      p2[j] = b;
     }
     u32x4* dst = Uwb + (e >> 6) * 128 + l;
     dst[0] = __builtin_bit_cast(u32x4, p1);
@@ -522,19 +496,9 @@ __global__ __launch_bounds__(512, 1) void lstm_wide_bwd_kernel(
   f32x4* PBlds = reinterpret_cast<f32x4*>(wlds + L::PB);
   unsigned* info = reinterpret_cast<unsigned*>(wlds + L::INFO);
   const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
-  if (tid == 0) {
-    const unsigned xi = __builtin_amdgcn_s_getreg((3 << 11) | 20) & 15u;   // HW_REG_XCC_ID[3:0]
-    info[0] = xi;
-    info[1] = xi < 8 ? atomicAdd(&ctl->xcc_count[xi], 1u) : 0xffffu;
-    info[2] = 0;
-    info[3] = 0;
-  }
-  __syncthreads();
-  const int x = (int)info[0], nb = (int)info[1];
-  if (x >= 8 || nb >= 32) {
-    if (tid == 0) wide_raise(ctl, sticky, gm.fault, 2u);
-    return;
-  }
+  unsigned xcc, member;
+  if (!join_xcd(ctl, sticky, gm.fault, info, 2, xcc, member)) return;
+  const int x = (int)xcc, nb = (int)member;
   const int T = gm.T, Bp = gm.Bp, Hp = gm.Hp, D = gm.D, d = gm.d;
   const int KS = Hp / 8, N4 = 4 * Hp, DH = D * Hp, DN = D * N4;
   const int me = x * 32 + nb;
@@ -567,13 +531,14 @@ __global__ __launch_bounds__(512, 1) void lstm_wide_bwd_kernel(
   const float sb = rowok ? wide_scale_of(smax[cb], gm.scale_shift) : 1.f;
   float dc = 0.f;
   bool aborted = false;
-  WSTAMP_DECL;
-  const f32x4 sent = __builtin_bit_cast(f32x4, (u32x4){0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu});
+  WStamps stp;
+  stp.start(me == 0 || me == 255);
+  const f32x4 sent = __builtin_bit_cast(f32x4, (u32x4){SENTINEL, SENTINEL, SENTINEL, SENTINEL});
 
   for (int k = 0; k < T; ++k) {
     const int s = T - 1 - k, par = k & 1;
     bool ok = true;
-    WMARK(0);
+    stp.mark(0);
     // per-frame operands of the cell backward: in flight during the gather / product phases.  Unconditional loads
     // (a masked cell reads frame 0 of its row and is zeroed below).
     const bool valid = rowok && s < len;
@@ -596,31 +561,9 @@ __global__ __launch_bounds__(512, 1) void lstm_wide_bwd_kernel(
       if (w != x) {
         u32x4* src = inbox + ((((size_t)((k - 1) & 1) * 256 + me) * 8 + w) * MT * 2) * 64 + lane;
         u32x4 v[MT][2];
-        ok = false;
-        for (unsigned n = 0; n < SPIN_BUDGET; ++n) {
-          v[MT - 1][1] = ld16_sc1(src + ((MT - 1) * 2 + 1) * 64);
-          wait_vm0(v[MT - 1][1]);
-          const u32x4 q = v[MT - 1][1];
-          if (!__all(q.x != 0xffffffffu && q.y != 0xffffffffu && q.z != 0xffffffffu && q.w != 0xffffffffu)) continue;
-          bool all = true;
-#pragma unroll
-          for (int m = 0; m < MT; ++m)
-#pragma unroll
-            for (int p = 0; p < 2; ++p)
-              if (m != MT - 1 || p != 1) v[m][p] = ld16_sc1(src + (m * 2 + p) * 64);
-#pragma unroll
-          for (int m = 0; m < MT; ++m)
-#pragma unroll
-            for (int p = 0; p < 2; ++p)
-              if (m != MT - 1 || p != 1) {
-                wait_vm0(v[m][p]);
-                const u32x4 t = v[m][p];
-                all = all && t.x != 0xffffffffu && t.y != 0xffffffffu && t.z != 0xffffffffu && t.w != 0xffffffffu;
-              }
-          if (__all(all)) { ok = true; break; }
-        }
+        ok = poll_landed<MT>(src, v);
         if (s == gm.inject && me == 0) ok = false;
-        WMARK(1);
+        stp.mark(1);
         if (ok) {
 #pragma unroll
           for (int m = 0; m < MT; ++m)
@@ -634,9 +577,9 @@ __global__ __launch_bounds__(512, 1) void lstm_wide_bwd_kernel(
         }
       }
     }
-    WMARK(2);
+    stp.mark(2);
     __syncthreads();                                        // #1: dG of step k-1 is in LDS (all 8 column groups)
-    WMARK(3);
+    stp.mark(3);
     if (k > 0 && !info[2]) {
       // 2. partial dh of units [32w, 32w+32) of the slice; each 16 x 16 tile goes to the XCD's exchange buffer at once
       f32x4* pdst = px + (((size_t)(par * 8 + x) * 32) * 32 + nb) * PU;        // + dest * 32 * PU
@@ -679,9 +622,9 @@ __global__ __launch_bounds__(512, 1) void lstm_wide_bwd_kernel(
         pd[0] = t0;
         pd[(size_t)2 * 32 * PU] = t1;
       });
-      WMARK(4);
+      stp.mark(4);
       load_cell();                                           // in flight under the gather below
-      WMARK(5);
+      stp.mark(5);
       // 3. the 32 partial sums of the own 8 units: wave w fetches sources 4w .. 4w+3.  No flag, as across the XCDs: every
       // (destination, source) block has ONE reader, so its words are polled against the sentinel and reset after the read
       {
@@ -698,12 +641,11 @@ __global__ __launch_bounds__(512, 1) void lstm_wide_bwd_kernel(
           for (int j = 0; j < NL; ++j)
             if (lane + 64 * j < 4 * PU) {
               wait_vm0(v[j]);
-              const u32x4 q = v[j];
-              all = all && q.x != 0xffffffffu && q.y != 0xffffffffu && q.z != 0xffffffffu && q.w != 0xffffffffu;
+              all = all && landed(v[j]);
             }
           if (__all(all)) { ok = true; break; }
         }
-        WMARK(6);
+        stp.mark(6);
         if (ok) {
 #pragma unroll
           for (int j = 0; j < NL; ++j)
@@ -716,9 +658,9 @@ __global__ __launch_bounds__(512, 1) void lstm_wide_bwd_kernel(
         }
       }
     }
-    WMARK(7);
+    stp.mark(7);
     __syncthreads();                                        // #2: the 32 partial sums are in LDS
-    WMARK(8);
+    stp.mark(8);
     const unsigned abort_word = info[2];
     // 4. cell backward of (row cb, unit ci)
     if (cell) {
@@ -732,16 +674,7 @@ __global__ __launch_bounds__(512, 1) void lstm_wide_bwd_kernel(
       }
       f32x4 dg = (f32x4){0.f, 0.f, 0.f, 0.f};
       float dcn = 0.f;
-      if (valid) {
-        if (s == 0) cpv = 0.f;
-        const float tc = tanhf_(cc);
-        const float dct = dc + dhs * act.w * (1.f - tc * tc);
-        dg.x = dct * act.y * act.x * (1.f - act.x);
-        dg.y = dct * act.x * (1.f - act.y * act.y);
-        dg.z = dct * cpv * act.z * (1.f - act.z);
-        dg.w = dhs * tc * act.w * (1.f - act.w);
-        dcn = dct * act.z;
-      }
+      if (valid) dg = lstm_cell_bwd(act, cc, cpv, s == 0, dhs, dc, dcn);
       dc = dcn;
       // the planes of dG * S_row in A-fragment order: (row cb, columns 4ci .. 4ci+3) of the 32 = unit (cb&15) + 16*(ci>>1) of
       // M tile cb>>4, halfs 4*(ci&1) ..
@@ -751,9 +684,10 @@ __global__ __launch_bounds__(512, 1) void lstm_wide_bwd_kernel(
       h4 p1, p2;
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        const _Float16 a = (_Float16)sv[j];
+        _Float16 a, b;
+        split_f16x2(sv[j], a, b);
         p1[j] = a;
-        p2[j] = (_Float16)(sv[j] - (float)a);
+        p2[j] = b;
       }
       // own column group (kt = x) of the next step's A operand: straight into LDS
       h4* ap = reinterpret_cast<h4*>(Alds + ((x * MT + (cb >> 4)) * 2) * 64 + (cb & 15) + 16 * (ci >> 1)) + (ci & 1);
@@ -766,7 +700,7 @@ __global__ __launch_bounds__(512, 1) void lstm_wide_bwd_kernel(
       }
     }
     __syncthreads();                                        // #3: the own dG tile is complete in LDS
-    if (info[3]) { if (tid == 0) wide_raise(ctl, sticky, gm.fault, 4u); aborted = true; }
+    if (info[3]) { if (tid == 0) raise_error(ctl, sticky, gm.fault, 4u); aborted = true; }
     // 5. publish the tile to the 7 other workgroups that hold these units' columns (wave w -> XCD w)
     if (w != x && k + 1 < T && !aborted) {
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // (the sentinel stores of this wave's gather are acknowledged)
@@ -777,33 +711,22 @@ __global__ __launch_bounds__(512, 1) void lstm_wide_bwd_kernel(
         for (int p = 0; p < 2; ++p)
           st16_sc1(dst + (m * 2 + p) * 64, __builtin_bit_cast(f32x4, Alds[((x * MT + m) * 2 + p) * 64 + lane]));
     }
-    WMARK(9);
+    stp.mark(9);
     if (abort_word || aborted) { aborted = true; break; }
   }
-  WSTAMP_FLUSH;
-  if (aborted && tid == 0) wide_raise(ctl, sticky, gm.fault, 1u);
+  stp.flush(ctl->stamps + ((me ? 8 : 0) + w) * 10);
+  if (aborted && tid == 0) raise_error(ctl, sticky, gm.fault, 1u);
 }
+
+using WideMT = std::integer_sequence<int, 1, 2, 3, 4>;   // MT = Bp/16 the kernels are built for
 
 hipError_t wide_prepare() {
   hipError_t e = hipSuccess;
-#define NASR_WIDE_ATTR(MTV)                                                                                         \
-  if (e == hipSuccess)                                                                                              \
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(&lstm_wide_fwd_kernel<MTV>),                              \
-                            hipFuncAttributeMaxDynamicSharedMemorySize, WideLds<MTV>::END * 16)
-  NASR_WIDE_ATTR(1);
-  NASR_WIDE_ATTR(2);
-  NASR_WIDE_ATTR(3);
-  NASR_WIDE_ATTR(4);
-#undef NASR_WIDE_ATTR
-#define NASR_WIDE_ATTR(MTV)                                                                                         \
-  if (e == hipSuccess)                                                                                              \
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(&lstm_wide_bwd_kernel<MTV>),                              \
-                            hipFuncAttributeMaxDynamicSharedMemorySize, WideLdsB<MTV>::END * 16)
-  NASR_WIDE_ATTR(1);
-  NASR_WIDE_ATTR(2);
-  NASR_WIDE_ATTR(3);
-  NASR_WIDE_ATTR(4);
-#undef NASR_WIDE_ATTR
+  auto raise = [&](auto* kernel, int bytes) {
+    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+  };
+  for_each_int(WideMT{}, [&](auto mt) { raise(&lstm_wide_fwd_kernel<mt()>, WideLds<mt()>::END * 16); });
+  for_each_int(WideMT{}, [&](auto mt) { raise(&lstm_wide_bwd_kernel<mt()>, WideLdsB<mt()>::END * 16); });
   return e;
 }
 
@@ -824,19 +747,11 @@ void launch_lstm_wide_bwd(const LstmDims& dm, int d, const void* Uwb, const floa
   WideGeom gm{dm.T, dm.Bp, dm.Hp, dm.D, d, -1, 0, fault};
   if (const char* e = test_hook("NASR_WIDE_FAULT_BWD")) gm.inject = atoi(e);
   if (const char* e = test_hook("NASR_WIDE_SCALE_SHIFT")) gm.scale_shift = atoi(e);   // test hook: > 10 drives dG * S out of the fp16 range
-  const int MT = dm.Bp / 16;
-#define NASR_WIDE(MTV)                                                                                               \
-  hipLaunchKernelGGL((lstm_wide_bwd_kernel<MTV>), dim3(256), dim3(512), WideLdsB<MTV>::END * 16, st,                 \
-                     reinterpret_cast<const u32x4*>(Uwb), gates, dgbuf, cbuf, dout, seq_len,                           \
-                     reinterpret_cast<u32x4*>(inbox), reinterpret_cast<f32x4*>(px), ctl, sticky, gm, rinv,                    \
-                     reinterpret_cast<const unsigned*>(srow) + (size_t)d * dm.Bp)
-  switch (MT) {
-    case 1: NASR_WIDE(1); break;
-    case 2: NASR_WIDE(2); break;
-    case 3: NASR_WIDE(3); break;
-    default: NASR_WIDE(4); break;
-  }
-#undef NASR_WIDE
+  dispatch_int(WideMT{}, dm.Bp / 16, [&](auto mt) {
+    hipLaunchKernelGGL((lstm_wide_bwd_kernel<mt()>), dim3(256), dim3(512), WideLdsB<mt()>::END * 16, st,
+                       reinterpret_cast<const u32x4*>(Uwb), gates, dgbuf, cbuf, dout, seq_len, reinterpret_cast<u32x4*>(inbox),
+                       reinterpret_cast<f32x4*>(px), ctl, sticky, gm, rinv, reinterpret_cast<const unsigned*>(srow) + (size_t)d * dm.Bp);
+  });
 }
 
 void launch_lstm_wide_fwd(const LstmDims& dm, int d, const void* Uw, const float* cinv, float* gates, float* cbuf,
@@ -847,18 +762,11 @@ void launch_lstm_wide_fwd(const LstmDims& dm, int d, const void* Uw, const float
   (void)hipMemsetAsync(hx, 0, wide_hx_bytes(dm.Bp), st);   // the h buffers start from epoch 0
   WideGeom gm{dm.T, dm.Bp, dm.Hp, dm.D, d, -1, 0, fault};
   if (const char* e = test_hook("NASR_WIDE_FAULT")) gm.inject = atoi(e);
-  const int MT = dm.Bp / 16;
-#define NASR_WIDE(MTV)                                                                                               \
-  hipLaunchKernelGGL((lstm_wide_fwd_kernel<MTV>), dim3(256), dim3(512), WideLds<MTV>::END * 16, st,                  \
-                     reinterpret_cast<const u32x4*>(Uw), gates, cbuf, out, seq_len, reinterpret_cast<u32x4*>(hx), part, \
-                     ctl, sticky, gm, forget_bias, cinv)
-  switch (MT) {
-    case 1: NASR_WIDE(1); break;
-    case 2: NASR_WIDE(2); break;
-    case 3: NASR_WIDE(3); break;
-    default: NASR_WIDE(4); break;
-  }
-#undef NASR_WIDE
+  dispatch_int(WideMT{}, dm.Bp / 16, [&](auto mt) {
+    hipLaunchKernelGGL((lstm_wide_fwd_kernel<mt()>), dim3(256), dim3(512), WideLds<mt()>::END * 16, st,
+                       reinterpret_cast<const u32x4*>(Uw), gates, cbuf, out, seq_len, reinterpret_cast<u32x4*>(hx), part, ctl, sticky,
+                       gm, forget_bias, cinv);
+  });
 }
 
 }  // namespace nasr

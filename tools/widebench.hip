@@ -105,9 +105,9 @@ int main(int argc, char** argv) {
     CK(hipEventElapsedTime(&msB, a, b));
   }
   if (getenv("WIDE_STAMPS")) {
-    std::vector<unsigned> hc(sizeof(WideCtl) / 4);
-    CK(hipMemcpy(hc.data(), ctl, sizeof(WideCtl), hipMemcpyDeviceToHost));
-    const unsigned* st_ = hc.data() + (offsetof(WideCtl, stamps) / 4);
+    WideCtl hc;
+    CK(hipMemcpy(&hc, ctl, sizeof(WideCtl), hipMemcpyDeviceToHost));
+    const unsigned* st_ = hc.stamps;
     const char* names[10] = {"loop-top", "h-poll", "h-load+lds", "barrier1", "mfma", "part-store+ack", "part-poll", "part-load+lds", "barrier2", "cell..barrier3"};
     printf("cycles per step (100 MHz s_memtime ticks x 24 ~ core cycles at 2.4 GHz):\n");
     for (int i = 0; i < 10; ++i) {
@@ -238,9 +238,9 @@ int main(int argc, char** argv) {
       CK(hipEventElapsedTime(&msD, a, b));
     }
     if (getenv("WIDE_STAMPS")) {
-      std::vector<unsigned> hc(sizeof(WideCtl) / 4);
-      CK(hipMemcpy(hc.data(), ctl, sizeof(WideCtl), hipMemcpyDeviceToHost));
-      const unsigned* st_ = hc.data() + (offsetof(WideCtl, stamps) / 4);
+      WideCtl hc;
+      CK(hipMemcpy(&hc, ctl, sizeof(WideCtl), hipMemcpyDeviceToHost));
+      const unsigned* st_ = hc.stamps;
       const char* names[10] = {"loop-top", "dG-poll+load", "dG-lds", "barrier1", "mfma+stores", "ack+flag", "px-poll", "px-load+lds", "barrier2", "cell..publish"};
       printf("BPTT cycles per step:\n");
       for (int i = 0; i < 10; ++i) {
