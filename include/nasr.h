@@ -171,8 +171,33 @@ int nasr_stage_batch(nasr_handle h, const float* feats, const int32_t* seq_len, 
 int nasr_stage_batch_context(nasr_handle h, const float* centre, const float* pad_value, int numcontext, int numcep,
                              const int32_t* seq_len, const int32_t* labels, const int32_t* label_len, int B, int T,
                              int Lmax, int* ticket);
+/* (utils.py:24-31 feeding dataset.py:33-40) A batch straight from audio: the utterances audio[offsets[b] ..
+ * offsets[b+1]) at rates[b] Hz (NULL: all at the featurizer's samplerate) go through `featurizer`'s front end - resampler,
+ * MFCC, whole-utterance normalisation - on the device, and its last kernel writes the normalised centre frames
+ * [B,T,numcep] (zeros past an utterance's end) and the pad values straight into `model`'s batch slot, in the layout of
+ * nasr_upload_batch_context: no feature crosses PCIe in either direction.  T = the longest utterance's nasr_mfcc_frames,
+ * seq_len_out[b] = utterance b's; both are computed on the host and written before anything is launched.  The slot holds
+ * the same bits as nasr_featurize_rates + zero-padding to T + nasr_upload_batch_context give it.  Staging runs copies
+ * and kernels on the model's copy stream; a later nasr_featurize* / nasr_resample on the featurizer handle is ordered
+ * behind them by an event (no host wait).  One thread at a time per featurizer handle.  nasr_commit_batch,
+ * nasr_discard_batch and the two-ahead limit apply.  NASR_ERR_STATE: `featurizer` is not a featurizer handle, `model` is
+ * one, or they sit on different devices; NASR_ERR_ARG: feature_size != (2*numcontext+1)*numcep, a bad rate or a
+ * too-short utterance (named), and what nasr_upload_batch refuses, with the computed seq_len. */
+int nasr_upload_batch_audio(nasr_handle model, nasr_handle featurizer, const float* audio, const int64_t* offsets,
+                            const int32_t* rates, const int32_t* labels, const int32_t* label_len, int B, int Lmax,
+                            int32_t* seq_len_out, int* T_out);
+/* (utils.py:24-31 feeding dataset.py:33-40) the same as the staging half of a step: see nasr_stage_batch */
+int nasr_stage_batch_audio(nasr_handle model, nasr_handle featurizer, const float* audio, const int64_t* offsets,
+                           const int32_t* rates, const int32_t* labels, const int32_t* label_len, int B, int Lmax,
+                           int32_t* seq_len_out, int* T_out, int* ticket);
 int nasr_commit_batch(nasr_handle h, int ticket);
 int nasr_discard_batch(nasr_handle h, int ticket);   /* give a staged batch's slot back unused */
+/* nasr_forward / nasr_loss / nasr_greedy_decode on the batch that is resident already (nasr_upload_batch*,
+ * nasr_commit_batch): what validation and decoding from audio run after nasr_upload_batch_audio.  NASR_ERR_STATE
+ * without a resident batch (nasr_loss_resident: without labels in it). */
+int nasr_forward_resident(nasr_handle h, float* logits_out);
+int nasr_loss_resident(nasr_handle h, float* loss_out, float* nll_out);
+int nasr_greedy_decode_resident(nasr_handle h, int32_t* ids_out, int32_t* lens_out);
 int nasr_compute_grads(nasr_handle h);          /* forward+CTC+backward on the resident batch (async) */
 /* ---- in-library gradient exchange: average_gradients (tfnetwork.py:72-86) for hosts without torch.distributed ------
  * One RCCL rank per handle (one process per GPU, or one host thread per handle).  librccl.so is bound with dlopen when

@@ -39,6 +39,8 @@ SYMBOLS = [
     'nasr_las_beam_get_trace', 'nasr_las_beam_get_final', 'nasr_las_beam_get_times',
     'nasr_create_featurizer', 'nasr_mfcc_frames', 'nasr_mfcc_filterbank', 'nasr_featurize', 'nasr_featurize_times',
     'nasr_resample_filter', 'nasr_resample_length', 'nasr_resample', 'nasr_featurize_rates',
+    'nasr_upload_batch_audio', 'nasr_stage_batch_audio', 'nasr_forward_resident', 'nasr_loss_resident',
+    'nasr_greedy_decode_resident',
 ]
 
 
@@ -152,6 +154,12 @@ def load():
         'nasr_get_persist_stats': (c_int, [H, POINTER(c_int), POINTER(c_int)]),
         'nasr_stage_batch': (c_int, [H, fp, ip, ip, ip, c_int, c_int, c_int, POINTER(c_int)]),
         'nasr_stage_batch_context': (c_int, [H, fp, fp, c_int, c_int, ip, ip, ip, c_int, c_int, c_int, POINTER(c_int)]),
+        'nasr_upload_batch_audio': (c_int, [H, H, fp, POINTER(c_int64), ip, ip, ip, c_int, c_int, ip, POINTER(c_int)]),
+        'nasr_stage_batch_audio': (c_int, [H, H, fp, POINTER(c_int64), ip, ip, ip, c_int, c_int, ip, POINTER(c_int),
+                                           POINTER(c_int)]),
+        'nasr_forward_resident': (c_int, [H, fp]),
+        'nasr_loss_resident': (c_int, [H, fp, fp]),
+        'nasr_greedy_decode_resident': (c_int, [H, ip, ip]),
         'nasr_commit_batch': (c_int, [H, c_int]),
         'nasr_discard_batch': (c_int, [H, c_int]),
         'nasr_set_bucket_defer': (c_int, [H, c_int]),

@@ -8,6 +8,9 @@
 //   mfcc_norm_kernel      one workgroup per utterance: the float64 mean and std of the stacked matrix from the centre
 //                         frames (each counted once per window that holds it, the zero pads as a count), then the
 //                         normalised rows written straight into the stacked layout
+//   mfcc_norm_slot_kernel the same statistics, written as a model handle's batch slot takes them (nasr_batch.hip):
+//                         the normalised centre frames [B][T][numcep] of a whole batch, zeros past each utterance's
+//                         end, and one pad value (0 - mean) / std per utterance; nasr_upload_batch_audio
 // Tables (twiddles, filter weights, the DCT x lifter matrix) are built once per handle on the host in double.
 // nasr_featurize_rates first resamples utterances at other rates to the config rate (resample.hip) into a device
 // buffer, which the same two kernels then read.
@@ -156,18 +159,14 @@ __global__ __launch_bounds__(64 * SPEC_WAVES) void mfcc_spectral_kernel(
   }
 }
 
-// One workgroup per utterance u of T frames: the stacked matrix [T][W*C] (W = 2 nc + 1) holds centre frame t in
+// One workgroup per utterance of T frames: the stacked matrix [T][W*C] (W = 2 nc + 1) holds centre frame t in
 // cnt_t = min(t,nc) + min(T-1-t,nc) + 1 windows, zeros elsewhere.  Two float64 passes (numpy's mean, then the mean
-// squared deviation), fixed-order sums; then out[t][w*C + c] = (cep[t+w-nc][c] - mean) / std (0 outside the utterance).
-__global__ __launch_bounds__(NORM_THREADS) void mfcc_norm_kernel(const double* __restrict__ cep,
-                                                                 const int64_t* __restrict__ foff, int numcep, int nc,
-                                                                 float* __restrict__ out, double* __restrict__ mstd) {
-  __shared__ double red[NORM_THREADS];
-  const int u = blockIdx.x, tid = threadIdx.x;
-  const int64_t f0 = foff[u], T = foff[u + 1] - f0;
+// squared deviation), fixed-order sums.  Every thread of the workgroup calls it and gets the same (mean, std).
+__device__ __forceinline__ void utt_mean_std(const double* __restrict__ src, int64_t T, int numcep, int nc, double* red,
+                                             double* mean_out, double* sd_out) {
+  const int tid = threadIdx.x;
   const int W = 2 * nc + 1;
   const int64_t ne = T * numcep;
-  const double* src = cep + f0 * numcep;
   auto cnt = [&](int64_t t) { return (double)((t < nc ? t : nc) + (T - 1 - t < nc ? T - 1 - t : nc) + 1); };
   auto block_sum = [&](double v) {
     red[tid] = v;
@@ -195,20 +194,55 @@ __global__ __launch_bounds__(NORM_THREADS) void mfcc_norm_kernel(const double* _
     q += cnt(e / numcep) * dv * dv;
   }
   const double var = (block_sum(q) + zeros * mean * mean) / N;
-  const double sd = sqrt(var);
+  *mean_out = mean;
+  *sd_out = sqrt(var);
+}
+
+// the one expression both writers round through: a stacked element, a centre frame's, a pad value (v = 0)
+__device__ __forceinline__ float norm_value(double v, double mean, double sd) { return (float)((v - mean) / sd); }
+
+// The stacked form: out[t][w*C + c] = (cep[t+w-nc][c] - mean) / std (0 outside the utterance), utterance after utterance.
+__global__ __launch_bounds__(NORM_THREADS) void mfcc_norm_kernel(const double* __restrict__ cep,
+                                                                 const int64_t* __restrict__ foff, int numcep, int nc,
+                                                                 float* __restrict__ out, double* __restrict__ mstd) {
+  __shared__ double red[NORM_THREADS];
+  const int u = blockIdx.x, tid = threadIdx.x;
+  const int64_t f0 = foff[u], T = foff[u + 1] - f0;
+  const double* src = cep + f0 * numcep;
+  double mean, sd;
+  utt_mean_std(src, T, numcep, nc, red, &mean, &sd);
   if (mstd && tid == 0) {
     mstd[2 * u] = mean;
     mstd[2 * u + 1] = sd;
   }
-  const int rowlen = W * numcep;
+  const int rowlen = (2 * nc + 1) * numcep;
   float* dst = out + f0 * rowlen;
   for (int64_t e = tid; e < T * rowlen; e += NORM_THREADS) {
     const int64_t t = e / rowlen;
     const int r = (int)(e - t * rowlen);
     const int64_t ts = t + r / numcep - nc;
     const double v = (ts >= 0 && ts < T) ? src[ts * numcep + r % numcep] : 0.0;
-    dst[e] = (float)((v - mean) / sd);
+    dst[e] = norm_value(v, mean, sd);
   }
+}
+
+// The batch-slot form (the `centre` layout of nasr_upload_batch_context): centre [B][Tb][numcep] gets utterance u's
+// normalised frames and exact zeros for t >= its T frames, pad[u] the value of an out-of-utterance context frame.
+// Consecutive threads write consecutive floats of the utterance's [Tb][numcep] block.
+__global__ __launch_bounds__(NORM_THREADS) void mfcc_norm_slot_kernel(const double* __restrict__ cep,
+                                                                      const int64_t* __restrict__ foff, int numcep, int nc,
+                                                                      int Tb, float* __restrict__ centre,
+                                                                      float* __restrict__ pad) {
+  __shared__ double red[NORM_THREADS];
+  const int u = blockIdx.x, tid = threadIdx.x;
+  const int64_t f0 = foff[u], T = foff[u + 1] - f0;
+  const double* src = cep + f0 * numcep;
+  double mean, sd;
+  utt_mean_std(src, T, numcep, nc, red, &mean, &sd);
+  if (tid == 0) pad[u] = norm_value(0.0, mean, sd);
+  const int64_t ne = T * numcep, nb = (int64_t)Tb * numcep;
+  float* dst = centre + (int64_t)u * nb;
+  for (int64_t e = tid; e < nb; e += NORM_THREADS) dst[e] = e < ne ? norm_value(src[e], mean, sd) : 0.f;
 }
 
 // --------------------------------------------------------------------------------------------------- host tables
@@ -279,6 +313,11 @@ struct FzState {
   std::vector<char> hrmeta;
   Event ev[4];
   float times[3] = {0.f, 0.f, 0.f};
+  bool times_pending = false;          // ev[0..2] were recorded by a batch-slot call and not read yet (nasr_featurize_times)
+  // A batch-slot call (nasr_upload_batch_audio, nasr_stage_batch_audio) runs the front end on a MODEL handle's stream and
+  // returns with the kernels still in flight: ev_busy marks the point behind which the scratch buffers above are free.
+  Event ev_busy;
+  bool busy_valid = false;
 };
 
 }  // namespace nasr_impl
@@ -286,6 +325,18 @@ struct FzState {
 void nasr_impl::FzStateDelete::operator()(FzState* f) const { delete f; }
 
 namespace {
+
+// Grows scratch buffer b to `bytes`.  A batch-slot call may still read the old allocation on a model's stream (ev_busy):
+// the host waits for that event before the buffer is freed, so the free never races the kernels and does not lean on
+// hipFree's own device-wide synchronisation.  Only a call LARGER than every one before it pays this wait; buffers that
+// are big enough are ordered by scratch_acquire's stream wait alone.
+bool scratch_ensure(FzState& z, DevBuf& b, size_t bytes) {
+  if (bytes > b.cap && z.busy_valid) {
+    (void)hipEventSynchronize(z.ev_busy);
+    z.busy_valid = false;
+  }
+  return b.ensure(bytes, nullptr);
+}
 
 const RsWave* rs_waves(FzState& z, int n) {
   return reinterpret_cast<const RsWave*>(z.rmeta.as<char>() + (size_t)n * sizeof(RsUtt));
@@ -302,8 +353,8 @@ int resample_prepare(nasr_ctx* h, FzState& z, const ResamplePlan& plan, int64_t 
   z.hrmeta.resize(ub + wb);
   memcpy(z.hrmeta.data(), plan.utt.data(), ub);
   memcpy(z.hrmeta.data() + ub, plan.waves.data(), wb);
-  if (!z.audio.ensure((size_t)in_samples * 4, nullptr) || !z.raud.ensure((size_t)plan.total * 4, nullptr) ||
-      !z.rmeta.ensure(z.hrmeta.size(), nullptr))
+  if (!scratch_ensure(z, z.audio, (size_t)in_samples * 4) || !scratch_ensure(z, z.raud, (size_t)plan.total * 4) ||
+      !scratch_ensure(z, z.rmeta, z.hrmeta.size()))
     return h->fail(NASR_ERR_HIP, "resampling: device buffers for " + std::to_string(in_samples) + " + " +
                                      std::to_string(plan.total) + " samples could not be allocated");
   return NASR_OK;
@@ -314,8 +365,133 @@ int finish(nasr_ctx* h, FzState& z) {
   if (int rc = sync_checked(h)) return rc;
   for (int i = 0; i < 3; ++i)
     if (hipEventElapsedTime(&z.times[i], z.ev[i], z.ev[i + 1]) != hipSuccess) z.times[i] = 0.f;
+  z.times_pending = false;
   return NASR_OK;
 }
+
+// `st` is about to use the scratch buffers: behind whatever batch-slot call still reads them on another stream
+int scratch_acquire(nasr_ctx* eh, FzState& z, hipStream_t st) {
+  if (!z.busy_valid) return NASR_OK;
+  // The event was recorded on a model handle's stream, and that handle may be gone by now.  nasr_destroy waits for its
+  // streams first, so the event of a destroyed handle has completed: a completed event is dropped here, and a wait is
+  // only ever queued on one whose stream still has the work in flight.
+  if (hipEventQuery(z.ev_busy) == hipSuccess) {
+    z.busy_valid = false;
+    return NASR_OK;
+  }
+  HIPCHK(eh, hipStreamWaitEvent(st, z.ev_busy, 0));
+  return NASR_OK;
+}
+
+}  // namespace
+
+namespace nasr_impl {
+
+// What a front-end call works out on the host before anything is launched: the resampling plan, every utterance's
+// sample and frame offsets.  Errors go to handle eh (the featurizer itself, or the model handle of a batch-slot call).
+int fz_plan(nasr_ctx* eh, FzState& z, const std::string& fn, const int64_t* offsets, const int32_t* rates, int n, FzPlan* p) {
+  p->rs = false;
+  if (rates) {
+    std::string why;
+    if (!resample_plan(offsets, rates, n, z.cfg.samplerate, &p->rp, &why)) return eh->fail(NASR_ERR_ARG, fn + ": " + why);
+    for (const RsUtt& u : p->rp.utt) p->rs = p->rs || u.step != 0;
+  }
+  p->n = n;
+  p->uoff.assign(n + 1, 0);
+  p->foff.assign(n + 1, 0);
+  for (int i = 0; i < n; ++i) {
+    const int64_t len = p->rs ? p->rp.utt[i].n_samples : offsets[i + 1] - offsets[i];
+    if (len < 1) return eh->fail(NASR_ERR_ARG, fn + ": utterance " + std::to_string(i) + " has no samples");
+    p->uoff[i] = p->rs ? p->rp.utt[i].out_off : offsets[i] - offsets[0];
+    p->foff[i + 1] = p->foff[i] + frames_of(z.d.frame_len, z.d.frame_step, len);
+  }
+  p->S_in = offsets[n] - offsets[0];
+  p->uoff[n] = p->rs ? p->rp.total : p->S_in;
+  p->mb = (size_t)(n + 1) * 8;
+  p->meta_bytes = 2 * p->mb + (size_t)p->foff[n] * 4;
+  p->rmeta_bytes = p->rs ? p->rp.utt.size() * sizeof(RsUtt) + p->rp.waves.size() * sizeof(RsWave) : 0;
+  return NASR_OK;
+}
+
+size_t fz_stage_bytes(const FzPlan& p) { return ((size_t)p.S_in * 4 + 7) / 8 * 8 + p.meta_bytes + p.rmeta_bytes; }
+
+// The copies, the resampler and mfcc_spectral_kernel of plan p on stream st: z.cep holds the cepstra afterwards, z.meta
+// the offsets.  audio: the first utterance's first sample.  pinned (nullable): fz_stage_bytes of pinned memory the
+// host-to-device copies go through, so that they are plain DMAs that return at once.
+int fz_front(nasr_ctx* eh, FzState& z, const std::string& fn, const FzPlan& p, const float* audio, void* pinned, hipStream_t st) {
+  const int n = p.n;
+  const int64_t F = p.foff[n];
+  z.hmeta.resize(p.meta_bytes);
+  memcpy(z.hmeta.data(), p.uoff.data(), p.mb);
+  memcpy(z.hmeta.data() + p.mb, p.foff.data(), p.mb);
+  int* fmap = reinterpret_cast<int*>(z.hmeta.data() + 2 * p.mb);
+  for (int i = 0; i < n; ++i)
+    for (int64_t f = p.foff[i]; f < p.foff[i + 1]; ++f) fmap[f] = i;
+  if (int rc = scratch_acquire(eh, z, st)) return rc;
+  if (p.rs) {
+    if (int rc = resample_prepare(eh, z, p.rp, p.S_in)) return rc;
+  }
+  if (!scratch_ensure(z, z.audio, (size_t)p.S_in * 4) || !scratch_ensure(z, z.meta, z.hmeta.size()) ||
+      !scratch_ensure(z, z.cep, (size_t)F * z.d.numcep * 8) || !scratch_ensure(z, z.mstd, (size_t)n * 16))
+    return eh->fail(NASR_ERR_HIP, fn + ": device buffers for " + std::to_string(p.uoff[n]) + " samples could not be allocated");
+  const void *src_audio = audio, *src_meta = z.hmeta.data(), *src_rmeta = p.rs ? z.hrmeta.data() : nullptr;
+  if (pinned) {
+    char* pa = static_cast<char*>(pinned);
+    char* pm = pa + ((size_t)p.S_in * 4 + 7) / 8 * 8;
+    memcpy(pa, audio, (size_t)p.S_in * 4);
+    memcpy(pm, z.hmeta.data(), p.meta_bytes);
+    if (p.rs) memcpy(pm + p.meta_bytes, z.hrmeta.data(), p.rmeta_bytes);
+    src_audio = pa; src_meta = pm; src_rmeta = pm + p.meta_bytes;
+  }
+  HIPCHK(eh, hipEventRecord(z.ev[0], st));
+  HIPCHK(eh, hipMemcpyAsync(z.audio.p, src_audio, (size_t)p.S_in * 4, hipMemcpyHostToDevice, st));
+  HIPCHK(eh, hipMemcpyAsync(z.meta.p, src_meta, p.meta_bytes, hipMemcpyHostToDevice, st));
+  if (p.rs) HIPCHK(eh, hipMemcpyAsync(z.rmeta.p, src_rmeta, p.rmeta_bytes, hipMemcpyHostToDevice, st));
+  HIPCHK(eh, hipEventRecord(z.ev[1], st));
+  if (p.rs) {
+    launch_resample(z.audio.as<float>(), z.rmeta.as<RsUtt>(), rs_waves(z, n), (int64_t)p.rp.waves.size(), z.rs_tab,
+                    z.raud.as<float>(), st);
+    HIPCHK(eh, hipGetLastError());
+  }
+  const int64_t nblk = (F + SPEC_WAVES - 1) / SPEC_WAVES;
+  mfcc_spectral_kernel<<<dim3((unsigned)nblk), dim3(64 * SPEC_WAVES), 0, st>>>(
+      p.rs ? z.raud.as<float>() : z.audio.as<float>(), z.meta.as<int64_t>(), z.meta.as<int64_t>() + (n + 1),
+      reinterpret_cast<const int*>(z.meta.as<char>() + 2 * p.mb), F, z.tw, z.tw2, z.fb_lo, z.fb_n, z.fb_off, z.fb_w, z.dct,
+      z.d, z.cep.as<double>());
+  HIPCHK(eh, hipGetLastError());
+  return NASR_OK;
+}
+
+// The device producer of a batch slot's centre frames (nasr_batch.hip slot_fill): the front end of plan p on the slot's
+// stream, then mfcc_norm_slot_kernel straight into the slot.  The featurizer's scratch buffers are busy until ev_busy.
+int fz_produce_slot(nasr_ctx* eh, nasr_ctx* fzh, const FzPlan& p, const float* audio, int Tb, float* dcentre, float* dpad,
+                    void* pinned, hipStream_t st) {
+  FzState& z = *fzh->fz;
+  const std::string fn = "audio batch";
+  int rc = fz_front(eh, z, fn, p, audio, pinned, st);
+  if (!rc) {
+    mfcc_norm_slot_kernel<<<dim3(p.n), dim3(NORM_THREADS), 0, st>>>(z.cep.as<double>(), z.meta.as<int64_t>() + (p.n + 1),
+                                                                    z.d.numcep, z.d.nc, Tb, dcentre, dpad);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) rc = eh->fail(NASR_ERR_HIP, fn + ": " + hipGetErrorString(e));
+  }
+  // also when something failed part-way: whatever was queued on st still reads the scratch buffers
+  (void)hipEventRecord(z.ev[2], st);
+  if (hipEventRecord(z.ev_busy, st) == hipSuccess) z.busy_valid = true;
+  z.times_pending = rc == NASR_OK;
+  return rc;
+}
+
+int fz_feature_width(const nasr_ctx* fzh, int* numcontext, int* numcep) {
+  const FzState& z = *fzh->fz;
+  *numcontext = z.d.nc;
+  *numcep = z.d.numcep;
+  return z.W * z.d.numcep;
+}
+
+}  // namespace nasr_impl
+
+namespace {
 
 // The features of n utterances.  rates == nullptr (nasr_featurize): every utterance is at the config rate.  Otherwise
 // an utterance at another rate is resampled to it first, into z.raud, which the MFCC kernels then read.
@@ -326,64 +502,20 @@ int featurize(nasr_handle h, const std::string& fn, const float* audio, const in
   if (!zp) return h->fail(NASR_ERR_STATE, fn + ": not a featurizer handle");
   FzState& z = *zp;
   if (!audio || !offsets || !out || n < 1) return h->fail(NASR_ERR_ARG, fn + ": null buffer or n < 1");
-  ResamplePlan plan;
-  bool rs = false;
-  if (rates) {
-    std::string why;
-    if (!resample_plan(offsets, rates, n, z.cfg.samplerate, &plan, &why)) return h->fail(NASR_ERR_ARG, fn + ": " + why);
-    for (const RsUtt& u : plan.utt) rs = rs || u.step != 0;
-  }
-  // frame offsets and the frame -> utterance map, on the host
-  const size_t mb = (size_t)(n + 1) * 8;
-  std::vector<int64_t> uoff(n + 1), foff(n + 1);
-  foff[0] = 0;
-  for (int i = 0; i < n; ++i) {
-    const int64_t len = rs ? plan.utt[i].n_samples : offsets[i + 1] - offsets[i];
-    if (len < 1) return h->fail(NASR_ERR_ARG, fn + ": utterance " + std::to_string(i) + " has no samples");
-    uoff[i] = rs ? plan.utt[i].out_off : offsets[i] - offsets[0];
-    foff[i + 1] = foff[i] + frames_of(z.d.frame_len, z.d.frame_step, len);
-  }
-  const int64_t S_in = offsets[n] - offsets[0];
-  uoff[n] = rs ? plan.total : S_in;
-  const int64_t F = foff[n], S = uoff[n];
+  FzPlan p;
+  if (int rc = fz_plan(h, z, fn, offsets, rates, n, &p)) return rc;
+  const int64_t F = p.foff[n];
   if (out_rows != F)
     return h->fail(NASR_ERR_ARG, fn + ": out_rows is " + std::to_string(out_rows) + ", the utterances have " +
                                      std::to_string(F) + " frames");
-  z.hmeta.resize(2 * mb + (size_t)F * 4);
-  memcpy(z.hmeta.data(), uoff.data(), mb);
-  memcpy(z.hmeta.data() + mb, foff.data(), mb);
-  int* fmap = reinterpret_cast<int*>(z.hmeta.data() + 2 * mb);
-  for (int i = 0; i < n; ++i)
-    for (int64_t f = foff[i]; f < foff[i + 1]; ++f) fmap[f] = i;
   const size_t rowlen = (size_t)z.W * z.d.numcep;
   HIPCHK(h, hipSetDevice(h->device));
-  if (rs) {
-    if (int rc = resample_prepare(h, z, plan, S_in)) return rc;
-  }
-  if (!z.audio.ensure((size_t)S_in * 4, nullptr) || !z.meta.ensure(z.hmeta.size(), nullptr) ||
-      !z.cep.ensure((size_t)F * z.d.numcep * 8, nullptr) || !z.out.ensure((size_t)F * rowlen * 4, nullptr) ||
-      !z.mstd.ensure((size_t)n * 16, nullptr))
-    return h->fail(NASR_ERR_HIP, fn + ": device buffers for " + std::to_string(S) + " samples could not be allocated");
-  const int64_t* d_uoff = z.meta.as<int64_t>();
-  const int64_t* d_foff = d_uoff + (n + 1);
-  const int* d_fmap = reinterpret_cast<const int*>(z.meta.as<char>() + 2 * mb);
-  HIPCHK(h, hipEventRecord(z.ev[0], h->st));
-  HIPCHK(h, hipMemcpyAsync(z.audio.p, audio + offsets[0], (size_t)S_in * 4, hipMemcpyHostToDevice, h->st));
-  HIPCHK(h, hipMemcpyAsync(z.meta.p, z.hmeta.data(), z.hmeta.size(), hipMemcpyHostToDevice, h->st));
-  if (rs) HIPCHK(h, hipMemcpyAsync(z.rmeta.p, z.hrmeta.data(), z.hrmeta.size(), hipMemcpyHostToDevice, h->st));
-  HIPCHK(h, hipEventRecord(z.ev[1], h->st));
-  if (rs) {
-    launch_resample(z.audio.as<float>(), z.rmeta.as<RsUtt>(), rs_waves(z, n), (int64_t)plan.waves.size(), z.rs_tab,
-                    z.raud.as<float>(), h->st);
-    HIPCHK(h, hipGetLastError());
-  }
-  const int64_t nblk = (F + SPEC_WAVES - 1) / SPEC_WAVES;
-  mfcc_spectral_kernel<<<dim3((unsigned)nblk), dim3(64 * SPEC_WAVES), 0, h->st>>>(
-      rs ? z.raud.as<float>() : z.audio.as<float>(), d_uoff, d_foff, d_fmap, F, z.tw, z.tw2, z.fb_lo, z.fb_n,
-      z.fb_off, z.fb_w, z.dct, z.d, z.cep.as<double>());
-  HIPCHK(h, hipGetLastError());
-  mfcc_norm_kernel<<<dim3(n), dim3(NORM_THREADS), 0, h->st>>>(z.cep.as<double>(), d_foff, z.d.numcep, z.d.nc,
-                                                             z.out.as<float>(), z.mstd.as<double>());
+  if (int rc = scratch_acquire(h, z, h->st)) return rc;
+  if (!z.out.ensure((size_t)F * rowlen * 4, nullptr))
+    return h->fail(NASR_ERR_HIP, fn + ": device buffers for " + std::to_string(p.uoff[n]) + " samples could not be allocated");
+  if (int rc = fz_front(h, z, fn, p, audio + offsets[0], nullptr, h->st)) return rc;
+  mfcc_norm_kernel<<<dim3(n), dim3(NORM_THREADS), 0, h->st>>>(z.cep.as<double>(), z.meta.as<int64_t>() + (n + 1), z.d.numcep,
+                                                             z.d.nc, z.out.as<float>(), z.mstd.as<double>());
   HIPCHK(h, hipGetLastError());
   HIPCHK(h, hipEventRecord(z.ev[2], h->st));
   HIPCHK(h, hipMemcpyAsync(out, z.out.p, (size_t)F * rowlen * 4, hipMemcpyDeviceToHost, h->st));
@@ -442,6 +574,8 @@ int nasr_create_featurizer(const nasr_mfcc_cfg* cfg, int device_id, void* stream
   z.W = 2 * cfg->numcontext + 1;
   for (Event& e : z.ev)
     if (hipEventCreate(e.out()) != hipSuccess) return create_fail(h, NASR_ERR_HIP, "hipEventCreate failed");
+  if (hipEventCreateWithFlags(z.ev_busy.out(), hipEventDisableTiming) != hipSuccess)
+    return create_fail(h, NASR_ERR_HIP, "hipEventCreate failed");
 
   const double pi = 3.14159265358979323846;
   std::vector<double2> tw(FFT_N), tw2(NBIN);
@@ -506,6 +640,7 @@ int nasr_resample(nasr_handle h, const float* audio, const int64_t* offsets, con
                                      std::to_string(plan.total) + " samples");
   const int64_t S = offsets[n] - offsets[0];
   HIPCHK(h, hipSetDevice(h->device));
+  if (int rc = scratch_acquire(h, z, h->st)) return rc;
   if (int rc = resample_prepare(h, z, plan, S)) return rc;
   HIPCHK(h, hipEventRecord(z.ev[0], h->st));
   HIPCHK(h, hipMemcpyAsync(z.audio.p, audio + offsets[0], (size_t)S * 4, hipMemcpyHostToDevice, h->st));
@@ -523,6 +658,14 @@ int nasr_resample(nasr_handle h, const float* audio, const int64_t* offsets, con
 int nasr_featurize_times(nasr_handle h, float* h2d_ms, float* kernel_ms, float* d2h_ms) {
   if (!h) return NASR_ERR_ARG;
   if (!h->fz) return h->fail(NASR_ERR_STATE, "nasr_featurize_times: not a featurizer handle");
+  if (h->fz->times_pending) {           // a batch-slot call: copies and kernels on the model's stream, nothing comes back
+    FzState& z = *h->fz;
+    HIPCHK(h, hipEventSynchronize(z.ev[2]));
+    for (int i = 0; i < 2; ++i)
+      if (hipEventElapsedTime(&z.times[i], z.ev[i], z.ev[i + 1]) != hipSuccess) z.times[i] = 0.f;
+    z.times[2] = 0.f;
+    z.times_pending = false;
+  }
   if (h2d_ms) *h2d_ms = h->fz->times[0];
   if (kernel_ms) *kernel_ms = h->fz->times[1];
   if (d2h_ms) *d2h_ms = h->fz->times[2];

@@ -414,6 +414,59 @@ int nasr_stage_batch_context(nasr_handle h, const float* centre, const float* pa
   return stage(h, nullptr, seq_len, labels, label_len, B, T, Lmax, centre, pad_value, numcontext, numcep, ticket);
 }
 
+// The common part of nasr_upload_batch_audio / nasr_stage_batch_audio (utils.py:24-31 feeding dataset.py:33-40): the
+// checks, the host-side plan (seq_len, T), and the front end as the producer of the slot's centre frames.
+static int audio_batch(nasr_ctx* h, nasr_ctx* fzh, const std::string& fn, const float* audio, const int64_t* offsets,
+                       const int32_t* rates, const int32_t* labels, const int32_t* label_len, int B, int Lmax,
+                       int32_t* seq_len_out, int* T_out, int* ticket) {
+  if (!fzh || !fzh->fz) return h->fail(NASR_ERR_STATE, fn + ": `featurizer` is not a featurizer handle");
+  if (fzh->device != h->device)
+    return h->fail(NASR_ERR_STATE, fn + ": the model is on device " + std::to_string(h->device) + ", the featurizer on device " +
+                                       std::to_string(fzh->device));
+  if (!audio || !offsets || !seq_len_out || !T_out) return h->fail(NASR_ERR_ARG, fn + ": null buffer");
+  if (B < 1 || B > 64) return validate_batch(h, nullptr, nullptr, nullptr, B, 1, 0);
+  int ctx = 0, ncep = 0;
+  if (fz_feature_width(fzh, &ctx, &ncep) != h->F)
+    return h->fail(NASR_ERR_ARG, fn + ": feature_size " + std::to_string(h->F) + " must equal (2*numcontext+1)*numcep = (2*" +
+                                     std::to_string(ctx) + "+1)*" + std::to_string(ncep) + " of the featurizer");
+  FzPlan plan;
+  if (int rc = fz_plan(h, *fzh->fz, fn, offsets, rates, B, &plan)) return rc;
+  int64_t Tmax = 0;
+  for (int b = 0; b < B; ++b) Tmax = std::max(Tmax, plan.foff[b + 1] - plan.foff[b]);
+  if (Tmax > (1 << 24)) return h->fail(NASR_ERR_ARG, fn + ": an utterance of " + std::to_string(Tmax) + " frames");
+  const int T = (int)Tmax;
+  for (int b = 0; b < B; ++b) seq_len_out[b] = (int32_t)(plan.foff[b + 1] - plan.foff[b]);
+  *T_out = T;
+  CentreProducer prod;
+  prod.stage_bytes = fz_stage_bytes(plan);
+  const float* first = audio + offsets[0];
+  prod.run = [&](float* dcentre, float* dpad, void* pinned, hipStream_t cs) {
+    return fz_produce_slot(h, fzh, plan, first, T, dcentre, dpad, pinned, cs);
+  };
+  if (ticket) return stage(h, nullptr, seq_len_out, labels, label_len, B, T, Lmax, nullptr, nullptr, ctx, ncep, ticket, &prod);
+  return upload(h, nullptr, seq_len_out, labels, label_len, B, T, Lmax, nullptr, nullptr, ctx, ncep, &prod);
+}
+
+int nasr_upload_batch_audio(nasr_handle model, nasr_handle featurizer, const float* audio, const int64_t* offsets,
+                            const int32_t* rates, const int32_t* labels, const int32_t* label_len, int B, int Lmax,
+                            int32_t* seq_len_out, int* T_out) {
+  MODEL_CALL(model);
+  if (!model) return NASR_ERR_ARG;
+  return audio_batch(model, featurizer, "nasr_upload_batch_audio", audio, offsets, rates, labels, label_len, B, Lmax,
+                     seq_len_out, T_out, nullptr);
+}
+
+int nasr_stage_batch_audio(nasr_handle model, nasr_handle featurizer, const float* audio, const int64_t* offsets,
+                           const int32_t* rates, const int32_t* labels, const int32_t* label_len, int B, int Lmax,
+                           int32_t* seq_len_out, int* T_out, int* ticket) {
+  MODEL_CALL(model);
+  if (!model) return NASR_ERR_ARG;
+  if (!ticket) return model->fail(NASR_ERR_ARG, "null ticket");
+  *ticket = -1;
+  return audio_batch(model, featurizer, "nasr_stage_batch_audio", audio, offsets, rates, labels, label_len, B, Lmax,
+                     seq_len_out, T_out, ticket);
+}
+
 int nasr_commit_batch(nasr_handle h, int ticket) {
   MODEL_CALL(h);
   if (!h) return NASR_ERR_ARG;
@@ -684,15 +737,22 @@ int nasr_train_step(nasr_handle h, const float* feats, const int32_t* seq_len, c
   return NASR_OK;
 }
 
-int nasr_forward(nasr_handle h, const float* feats, const int32_t* seq_len, int B, int T, float* logits_out) {
+int nasr_forward_resident(nasr_handle h, float* logits_out) {
   MODEL_CALL(h);
   if (!h) return NASR_ERR_ARG;
-  int rc = upload(h, feats, seq_len, nullptr, nullptr, B, T, 0);
-  if (rc) return rc;
-  rc = forward(h);
+  if (!h->resident) return h->fail(NASR_ERR_STATE, "no resident batch");
+  const int rc = forward(h);
   if (rc) return rc;
   if (logits_out) return fetch_logits(h, logits_out);
   return nasr_synchronize(h);
+}
+
+int nasr_forward(nasr_handle h, const float* feats, const int32_t* seq_len, int B, int T, float* logits_out) {
+  MODEL_CALL(h);
+  if (!h) return NASR_ERR_ARG;
+  const int rc = upload(h, feats, seq_len, nullptr, nullptr, B, T, 0);
+  if (rc) return rc;
+  return nasr_forward_resident(h, logits_out);
 }
 
 int nasr_loss(nasr_handle h, const float* feats, const int32_t* seq_len, const int32_t* labels,
@@ -700,11 +760,18 @@ int nasr_loss(nasr_handle h, const float* feats, const int32_t* seq_len, const i
   MODEL_CALL(h);
   if (!h) return NASR_ERR_ARG;
   if (!labels) return h->fail(NASR_ERR_ARG, "nasr_loss needs labels");
-  int rc = upload(h, feats, seq_len, labels, label_len, B, T, Lmax);
+  const int rc = upload(h, feats, seq_len, labels, label_len, B, T, Lmax);
   if (rc) return rc;
-  rc = loss_pass(h, false);   // inference-mode batch norm
+  return nasr_loss_resident(h, loss_out, nll_out);
+}
+
+int nasr_loss_resident(nasr_handle h, float* loss_out, float* nll_out) {
+  MODEL_CALL(h);
+  if (!h) return NASR_ERR_ARG;
+  if (!h->resident || !h->cur || !h->cur->has_labels) return h->fail(NASR_ERR_STATE, "no resident batch with labels");
+  const int rc = loss_pass(h, false);   // inference-mode batch norm
   if (rc) return rc;
-  if (nll_out) HIPCHK(h, hipMemcpyAsync(nll_out, h->nll.p, (size_t)B * 4, hipMemcpyDeviceToHost, h->st));
+  if (nll_out) HIPCHK(h, hipMemcpyAsync(nll_out, h->nll.p, (size_t)h->B * 4, hipMemcpyDeviceToHost, h->st));
   if (loss_out) return nasr_get_loss(h, loss_out);
   return nasr_synchronize(h);
 }
@@ -733,16 +800,24 @@ int nasr_greedy_decode(nasr_handle h, const float* feats, const int32_t* seq_len
   MODEL_CALL(h);
   if (!h || !ids_out || !lens_out) return NASR_ERR_ARG;
   if (h->family == Family::Las) return h->fail(NASR_ERR_STATE, "nasr_greedy_decode: a LAS handle has no CTC decoder");
-  int rc = upload(h, feats, seq_len, nullptr, nullptr, B, T, 0);
+  const int rc = upload(h, feats, seq_len, nullptr, nullptr, B, T, 0);
   if (rc) return rc;
-  rc = forward(h);
+  return nasr_greedy_decode_resident(h, ids_out, lens_out);
+}
+
+int nasr_greedy_decode_resident(nasr_handle h, int32_t* ids_out, int32_t* lens_out) {
+  MODEL_CALL(h);
+  if (!h || !ids_out || !lens_out) return NASR_ERR_ARG;
+  if (h->family == Family::Las) return h->fail(NASR_ERR_STATE, "nasr_greedy_decode: a LAS handle has no CTC decoder");
+  if (!h->resident) return h->fail(NASR_ERR_STATE, "no resident batch");
+  const int rc = forward(h);
   if (rc) return rc;
   const CtcDims d = ctc_dims(h);
   launch_greedy(d, h->logits.as<float>(), h->seq_p, h->amax.as<int>(), h->ids.as<int>(), h->lens.as<int>(),
                 h->st);
   HIPCHK(h, hipGetLastError());
-  HIPCHK(h, hipMemcpyAsync(lens_out, h->lens.p, (size_t)B * 4, hipMemcpyDeviceToHost, h->st));
-  HIPCHK(h, hipMemcpyAsync(ids_out, h->ids.p, (size_t)B * h->Tp * 4, hipMemcpyDeviceToHost, h->st));
+  HIPCHK(h, hipMemcpyAsync(lens_out, h->lens.p, (size_t)h->B * 4, hipMemcpyDeviceToHost, h->st));
+  HIPCHK(h, hipMemcpyAsync(ids_out, h->ids.p, (size_t)h->B * h->Tp * 4, hipMemcpyDeviceToHost, h->st));
   return sync_checked(h);
 }
 

@@ -179,12 +179,16 @@ void slot_set_state(nasr_ctx* h, BatchSlot* s, int st) {
 // Copies one batch into slot s: the integer arrays through the slot's pinned meta buffer, the features from the caller's
 // memory (`pinned_feats` false: hipMemcpyAsync from pageable memory, which returns when the source may be reused) or
 // through the slot's pinned feature buffer (true: the H2D is a plain DMA that overlaps whatever the compute stream runs).
-// All device copies go to stream cs and end with the slot's ev_copy.
+// The centre form (centre frames [B][T][ncep] + one pad value per utterance) comes from host memory (`centre`,
+// `pad_value`) or from a device producer, whose kernels write it into the slot on stream cs: that is the only difference
+// between the two, the meta block and everything slot_commit does are the same.
+// All device copies (and a producer's kernels) go to stream cs and end with the slot's ev_copy.
 int slot_fill(nasr_ctx* h, BatchSlot* s, const float* feats, const int32_t* seq_len, const int32_t* labels,
               const int32_t* label_len, int B, int T, int Lmax, const float* centre, const float* pad_value, int ctx,
-              int ncep, hipStream_t cs, bool pinned_feats) {
-  if ((!feats && !centre) || !seq_len) return h->fail(NASR_ERR_ARG, "null input buffer");
-  if (centre && (!pad_value || ctx < 0 || ncep < 1 || (2 * ctx + 1) * ncep != h->F))
+              int ncep, hipStream_t cs, bool pinned_feats, const CentreProducer* producer) {
+  const bool centre_form = centre || producer;
+  if ((!feats && !centre_form) || !seq_len) return h->fail(NASR_ERR_ARG, "null input buffer");
+  if (centre_form && ((centre && !pad_value) || ctx < 0 || ncep < 1 || (2 * ctx + 1) * ncep != h->F))
     return h->fail(NASR_ERR_ARG, "context upload: feature_size must equal (2*numcontext+1)*numcep");
   if (labels && !label_len) return h->fail(NASR_ERR_ARG, "labels without label_len");
   int rc = validate_batch(h, seq_len, labels, label_len, B, T, Lmax);
@@ -210,11 +214,11 @@ int slot_fill(nasr_ctx* h, BatchSlot* s, const float* feats, const int32_t* seq_
   s->o_vprev = s->o_vrow + s->Rvp;
   s->o_vnext = s->o_vprev + s->Rvp;
   const size_t nmeta = s->o_vnext + s->Rvp;
-  const size_t nfeat = centre ? (size_t)B * T * ncep + B : (size_t)B * T * h->F;
+  const size_t nfeat = centre_form ? (size_t)B * T * ncep + B : (size_t)B * T * h->F;
   bool grew = false;
   if (!s->dmeta.ensure(nmeta * 4, &grew) || !s->dfeats.ensure(nfeat * 4, &grew) ||
       !pinned_ensure(s->hmeta, &s->hmeta_cap, nmeta * 4) ||
-      (pinned_feats && !pinned_ensure(s->hfeats, &s->hfeats_cap, nfeat * 4)))
+      (pinned_feats && !pinned_ensure(s->hfeats, &s->hfeats_cap, producer ? producer->stage_bytes : nfeat * 4)))
     return h->fail(NASR_ERR_HIP, "allocation of a batch slot failed");
   if (s->copy_valid) HIPCHK(h, hipEventSynchronize(s->ev_copy));          // the pinned mirrors are free to overwrite
   if (s->released_valid && cs != h->st) HIPCHK(h, hipStreamWaitEvent(cs, s->ev_released, 0));   // and the device side unread
@@ -266,7 +270,14 @@ int slot_fill(nasr_ctx* h, BatchSlot* s, const float* feats, const int32_t* seq_
         }
     for (; i < s->Rvp; ++i) vr[i] = vp[i] = vn[i] = -1;
   }
-  if (centre) {
+  if (producer) {
+    rc = producer->run(s->dfeats.as<float>(), s->dfeats.as<float>() + (size_t)B * T * ncep,
+                       pinned_feats ? s->hfeats.get() : nullptr, cs);
+    if (rc) {   // what the producer queued before it failed may still read the slot's pinned buffer: the next fill waits for it
+      if (hipEventRecord(s->ev_copy, cs) == hipSuccess) s->copy_valid = true;
+      return rc;
+    }
+  } else if (centre) {
     const size_t nc = (size_t)B * T * ncep;
     if (pinned_feats) {
       memcpy(s->hfeats, centre, nc * 4);
@@ -287,7 +298,7 @@ int slot_fill(nasr_ctx* h, BatchSlot* s, const float* feats, const int32_t* seq_
   s->copy_valid = true;
   s->B = B; s->T = T; s->Lmax = labels ? Lmax : 0; s->Bp = Bp; s->Tp = Tp; s->ctx = ctx; s->ncep = ncep;
   s->has_labels = labels != nullptr;
-  s->centre = centre != nullptr;
+  s->centre = centre_form;
   return NASR_OK;
 }
 
@@ -357,10 +368,12 @@ int slot_commit(nasr_ctx* h, BatchSlot* s) {
 
 // the synchronous upload of nasr_upload_batch / nasr_train_step / ...: fill on the compute stream, commit
 int upload(nasr_ctx* h, const float* feats, const int32_t* seq_len, const int32_t* labels, const int32_t* label_len,
-           int B, int T, int Lmax, const float* centre, const float* pad_value, int ctx, int ncep) {
+           int B, int T, int Lmax, const float* centre, const float* pad_value, int ctx, int ncep,
+           const CentreProducer* producer) {
   BatchSlot* s = slot_acquire(h, false);
   if (!s) return h->fail(NASR_ERR_STATE, "every batch slot holds a staged batch: commit or discard one first");
-  int rc = slot_fill(h, s, feats, seq_len, labels, label_len, B, T, Lmax, centre, pad_value, ctx, ncep, h->st, false);
+  int rc = slot_fill(h, s, feats, seq_len, labels, label_len, B, T, Lmax, centre, pad_value, ctx, ncep, h->st, false,
+                     producer);
   if (!rc) rc = slot_commit(h, s);
   if (rc && h->cur != s) slot_set_state(h, s, SLOT_FREE);
   return rc;
@@ -374,12 +387,14 @@ BatchSlot* slot_of_ticket(nasr_ctx* h, int ticket) {
 }
 
 int stage(nasr_ctx* h, const float* feats, const int32_t* seq_len, const int32_t* labels, const int32_t* label_len, int B,
-          int T, int Lmax, const float* centre, const float* pad_value, int ctx, int ncep, int* ticket) {
+          int T, int Lmax, const float* centre, const float* pad_value, int ctx, int ncep, int* ticket,
+          const CentreProducer* producer) {
   if (!ticket) return h->fail(NASR_ERR_ARG, "null ticket");
   *ticket = -1;
   BatchSlot* s = slot_acquire(h, true);
   if (!s) return h->fail(NASR_ERR_STATE, "no free batch slot: commit or discard a staged batch first");
-  const int rc = slot_fill(h, s, feats, seq_len, labels, label_len, B, T, Lmax, centre, pad_value, ctx, ncep, h->cst, true);
+  const int rc = slot_fill(h, s, feats, seq_len, labels, label_len, B, T, Lmax, centre, pad_value, ctx, ncep, h->cst, true,
+                           producer);
   if (rc) {
     slot_set_state(h, s, SLOT_FREE);
     return rc;

@@ -23,6 +23,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -31,6 +32,7 @@
 
 #include "../../include/nasr.h"
 #include "kernels.h"
+#include "resample.h"
 
 namespace nasr_impl {
 using namespace nasr;
@@ -495,15 +497,39 @@ int ensure_shape(nasr_ctx* h, int B, int T, int Lmax);
 // the logits and what the CTC lattice, its loss and the greedy decoder work in (T frames, Tp logit frames); returns the
 // lattice kernel's instantiation for labels up to Lmax (h->KS), or the code of a failure (< 0)
 int ensure_ctc_buffers(nasr_ctx* h, int B, int Bp, int T, int Tp, int Lmax, bool* grew);
+int validate_batch(nasr_ctx* h, const int32_t* seq_len, const int32_t* labels, const int32_t* label_len, int B, int T, int Lmax);
 bool pinned_ensure(Pinned<void>& p, size_t* cap, size_t bytes);
 void slot_set_state(nasr_ctx* h, BatchSlot* s, int st);
 int slot_commit(nasr_ctx* h, BatchSlot* s);
+// Where a slot's centre frames and pad values come from when not from host memory: run() enqueues on stream cs whatever
+// writes dcentre [B][T][ncep] and dpad [B]; pinned is stage_bytes of the slot's pinned buffer (NULL on a synchronous upload).
+struct CentreProducer {
+  size_t stage_bytes = 0;
+  std::function<int(float* dcentre, float* dpad, void* pinned, hipStream_t cs)> run;
+};
 int upload(nasr_ctx* h, const float* feats, const int32_t* seq_len, const int32_t* labels, const int32_t* label_len,
            int B, int T, int Lmax, const float* centre = nullptr, const float* pad_value = nullptr, int ctx = 0,
-           int ncep = 0);
+           int ncep = 0, const CentreProducer* producer = nullptr);
 BatchSlot* slot_of_ticket(nasr_ctx* h, int ticket);
 int stage(nasr_ctx* h, const float* feats, const int32_t* seq_len, const int32_t* labels, const int32_t* label_len, int B,
-          int T, int Lmax, const float* centre, const float* pad_value, int ctx, int ncep, int* ticket);
+          int T, int Lmax, const float* centre, const float* pad_value, int ctx, int ncep, int* ticket,
+          const CentreProducer* producer = nullptr);
+
+// ---- mfcc.hip: the front end as the device producer of a batch slot (nasr_upload_batch_audio, nasr_stage_batch_audio)
+// what a front-end call works out on the host before anything is launched
+struct FzPlan {
+  ResamplePlan rp;
+  bool rs = false;                     // some utterance is resampled: the kernels read the resampled buffer
+  int n = 0;
+  std::vector<int64_t> uoff, foff;     // [n+1] sample offsets (in the buffer the kernels read) and frame offsets
+  int64_t S_in = 0;                    // native samples
+  size_t mb = 0, meta_bytes = 0, rmeta_bytes = 0;
+};
+int fz_plan(nasr_ctx* eh, FzState& z, const std::string& fn, const int64_t* offsets, const int32_t* rates, int n, FzPlan* p);
+size_t fz_stage_bytes(const FzPlan& p);
+int fz_produce_slot(nasr_ctx* eh, nasr_ctx* fzh, const FzPlan& p, const float* audio, int Tb, float* dcentre, float* dpad,
+                    void* pinned, hipStream_t st);
+int fz_feature_width(const nasr_ctx* fzh, int* numcontext, int* numcep);   // (2*numcontext+1)*numcep
 
 inline float* dout_of(nasr_ctx* h, int) { return h->dout.as<float>(); }
 inline float* dg_of(nasr_ctx* h, int) { return h->dgbuf.as<float>(); }

@@ -231,6 +231,81 @@ class Engine:
         self._ck(rc)
         return int(ticket.value)
 
+    # ------------------------------------------------------------------ batches straight from audio (nasr_upload_batch_audio)
+    @staticmethod
+    def _audio(audios, labels, label_len, rates):
+        audios = [np.ascontiguousarray(a, dtype=np.float32).reshape(-1) for a in audios]
+        B = len(audios)
+        offsets = np.zeros(B + 1, dtype=np.int64)
+        offsets[1:] = np.cumsum([a.size for a in audios])
+        flat = np.concatenate(audios) if B > 1 else (audios[0] if B else np.zeros(1, np.float32))
+        r = None if rates is None else _i32(np.asarray([int(x) for x in rates])).ravel()
+        if r is not None and r.size != B:
+            raise ValueError('%d rates for %d utterances' % (r.size, B))
+        Lmax = 0
+        if labels is not None:
+            labels = _i32(labels)
+            labels = labels.reshape(B, -1) if B else labels
+            label_len = _i32(np.asarray([int(x) for x in label_len])).ravel()
+            assert label_len.size == B
+            Lmax = labels.shape[1] if B else 0
+        else:
+            label_len = None
+        return flat, offsets, r, labels, label_len, B, Lmax
+
+    def _audio_call(self, fn, featurizer, audios, labels, label_len, rates, *tail):
+        from ctypes import c_int
+        flat, offsets, r, labels, ll, B, Lmax = self._audio(audios, labels, label_len, rates)
+        seq = np.zeros(max(B, 1), np.int32)
+        T = c_int(0)
+        fz = getattr(featurizer, 'h', featurizer)
+        rc = fn(self.h, fz, _fp(flat), offsets.ctypes.data_as(POINTER(c_int64)), None if r is None else _ip(r),
+                None if labels is None else _ip(labels), None if ll is None else _ip(ll), B, Lmax, _ip(seq), byref(T),
+                *tail)
+        return rc, seq[:B], int(T.value)
+
+    def upload_batch_audio(self, featurizer, audios, labels, label_len, rates=None):
+        """A batch from audio: `featurizer` (features.Featurizer, same device) makes the MFCC features of the float32
+        utterances `audios` (at `rates` Hz, None: all at its samplerate) on the device and writes them into this handle's
+        batch slot; the batch is resident afterwards, as after upload_batch.  Returns (seq_len int32 [B], T)."""
+        rc, seq, T = self._audio_call(self.lib.nasr_upload_batch_audio, featurizer, audios, labels, label_len, rates)
+        self._ck(rc)
+        return seq, T
+
+    def stage_batch_audio(self, featurizer, audios, labels, label_len, rates=None):
+        """upload_batch_audio's staging half (stage_batch): copies and front-end kernels on the copy stream while the
+        current step runs.  Returns (seq_len, T, ticket); ticket is None when no staging slot is free."""
+        from ctypes import c_int
+        ticket = c_int(-1)
+        rc, seq, T = self._audio_call(self.lib.nasr_stage_batch_audio, featurizer, audios, labels, label_len, rates,
+                                      byref(ticket))
+        if rc == _lib.NASR_ERR_STATE and ticket.value < 0:
+            msg = self.lib.nasr_last_error(self.h)
+            if msg and b'no free batch slot' in msg:
+                return seq, T, None
+        self._ck(rc)
+        return seq, T, int(ticket.value)
+
+    def forward_resident(self, B, T):
+        """logits [T',B,C] of the resident batch (forward() without its upload)"""
+        out = np.empty((self.logit_frames(T), B, self.num_classes), np.float32)
+        self._ck(self.lib.nasr_forward_resident(self.h, _fp(out)))
+        return out
+
+    def loss_resident(self, B):
+        """(loss, nll [B]) of the resident batch (loss() without its upload; inference-mode pass)"""
+        loss = c_float()
+        nll = np.empty(B, np.float32)
+        self._ck(self.lib.nasr_loss_resident(self.h, byref(loss), _fp(nll)))
+        return float(loss.value), nll
+
+    def greedy_decode_resident(self, B, T):
+        Tp = self.logit_frames(T)
+        ids = np.zeros((B, Tp), np.int32)
+        lens = np.zeros(B, np.int32)
+        self._ck(self.lib.nasr_greedy_decode_resident(self.h, _ip(ids), _ip(lens)))
+        return [ids[b, :lens[b]].tolist() for b in range(B)]
+
     def commit_batch(self, ticket):
         self._ck(self.lib.nasr_commit_batch(self.h, int(ticket)))
 
@@ -570,6 +645,10 @@ class LasEngine(Engine):
         feats, seq, labels, ll, B, T, U = self._batch(feats, seq_len, labels, label_len)
         self._BU = (B, U)
         self._ck(self.lib.nasr_upload_batch(self.h, _fp(feats), _ip(seq), _ip(labels), _ip(ll), B, T, U))
+
+    def upload_batch_audio(self, featurizer, audios, labels, label_len, rates=None):
+        self._BU = (len(audios), np.asarray(labels).reshape(len(audios), -1).shape[1])
+        return Engine.upload_batch_audio(self, featurizer, audios, labels, label_len, rates)
 
     def las_forward(self, feats, seq_len, labels, label_len, sample=False):
         """logits [B, U, C] of a decoder pass (sample: scheduled sampling at the handle's probability); loss via get_loss."""

@@ -100,6 +100,46 @@ def read_wav_native(path):
     return _decode(path, tag, channels, bits, pcm), int(rate)
 
 
+def wav_info(path):
+    """(mono samples, rate) of a RIFF/WAVE file from its chunk headers alone: what read_wav_native would return the
+    length and rate of, without reading or decoding the data chunk."""
+    with open(path, 'rb') as fh:
+        head = fh.read(12)
+        if len(head) < 12 or head[:4] != b'RIFF' or head[8:12] != b'WAVE':
+            raise ValueError('%s: not a RIFF/WAVE file' % path)
+        fmt = nbytes = None
+        while fmt is None or nbytes is None:
+            hdr = fh.read(8)
+            if len(hdr) < 8:
+                break
+            cid, size = struct.unpack('<4sI', hdr)
+            if cid == b'fmt ' and fmt is None:
+                fmt = fh.read(size)
+                fh.seek(size & 1, 1)
+            else:
+                if cid == b'data' and nbytes is None:
+                    here = fh.tell()
+                    fh.seek(0, 2)
+                    nbytes = min(size, fh.tell() - here)          # _chunks slices a truncated data chunk the same way
+                    fh.seek(here)
+                fh.seek(size + (size & 1), 1)
+    if fmt is None or nbytes is None or len(fmt) < 16:
+        raise ValueError('%s: no fmt or data chunk' % path)
+    _, channels, rate, _, _, bits = struct.unpack_from('<HHIIHH', fmt, 0)
+    if channels < 1 or bits < 8:
+        raise ValueError('%s: no channels' % path)
+    return nbytes // (bits // 8 * channels), int(rate)
+
+
+def write_wav16(path, audio, rate):
+    """float samples in [-1, 1) as a mono 16-bit PCM RIFF/WAVE file (tools and tests make their corpora with it)"""
+    pcm = np.round(np.asarray(audio) * 32768).astype('<i2').tobytes()
+    fmt = struct.pack('<HHIIHH', WAVE_FORMAT_PCM, 1, rate, rate * 2, 2, 16)
+    body = b'WAVE' + b'fmt ' + struct.pack('<I', 16) + fmt + b'data' + struct.pack('<I', len(pcm)) + pcm
+    with open(path, 'wb') as fh:
+        fh.write(b'RIFF' + struct.pack('<I', len(body)) + body)
+
+
 def resample_length(num_samples, rate, samplerate):
     """(librosa's ceil(n * ratio), resampy's int(n * ratio)) of n samples at `rate` resampled to `samplerate` (computed
     by the library, no GPU needed).  ValueError when resampy would raise: a rate <= 0 or no resampled sample."""
@@ -145,6 +185,39 @@ def filterbank(samplerate, nfilt=128, nfft=512):
     if rc != _lib.NASR_OK:
         raise ValueError('bad filterbank configuration')
     return bins, w
+
+
+class AudioBatch:
+    """A batch as audio: what HipNetwork's *_audio calls and AudioDataSet hand to the step machinery in the place of the
+    padded feature array.  The features are made on the device when the batch is uploaded (Engine.upload_batch_audio);
+    the frame counts - seq_len and the padded length T - are the library's host-side arithmetic.  `shape` is the shape
+    the padded feature array would have."""
+
+    def __init__(self, samplerate, audios, rates=None, width=0):
+        self.samplerate = int(samplerate)
+        self.audios = Featurizer._utterances(audios)
+        self.rates = None if rates is None else [int(r) for r in rates]
+        if self.rates is not None and len(self.rates) != len(self.audios):
+            raise ValueError('%d rates for %d utterances' % (len(self.rates), len(self.audios)))
+        frames = []
+        for i, a in enumerate(self.audios):
+            n = a.size
+            if self.rates is not None and self.rates[i] != self.samplerate:
+                try:
+                    n = resample_length(n, self.rates[i], self.samplerate)[0]
+                except ValueError as e:
+                    raise ValueError('utterance %d: %s' % (i, e)) from None
+            frames.append(num_frames(n, self.samplerate))
+        self.seq_len = [np.asarray(t, dtype=np.int32) for t in frames]
+        self.shape = (len(self.audios), max(frames), int(width))
+
+    def __len__(self):
+        return len(self.audios)
+
+    def shard(self, lo, hi):
+        """utterances [lo, hi) as a batch of their own, padded to ITS longest utterance"""
+        return AudioBatch(self.samplerate, self.audios[lo:hi], None if self.rates is None else self.rates[lo:hi],
+                          self.shape[2])
 
 
 class Featurizer:

@@ -22,7 +22,9 @@ import weakref
 import numpy as np
 
 from ..engine import Engine
-from ..parallel import Collective, take_shard
+from ..features import AudioBatch
+from ..parallel import Collective, shard_bounds
+from ..parallel import take_shard as _take_feature_shard
 from .network import Network
 
 
@@ -43,6 +45,18 @@ def _glorot_init(tensors, seed):
     return np.concatenate(chunks).astype(np.float32)
 
 
+def take_shard(mfccs, labels, seq_len, labels_len, world, rank):
+    """parallel.take_shard; a batch given as audio (features.AudioBatch) is split by utterance"""
+    if not isinstance(mfccs, AudioBatch):
+        return _take_feature_shard(mfccs, labels, seq_len, labels_len, world, rank)
+    if world == 1:
+        return mfccs, np.asarray(labels), list(seq_len), list(labels_len) if labels_len is not None else None
+    lo, hi = shard_bounds(len(seq_len), world, rank)
+    labels = np.asarray(labels)
+    return (mfccs.shard(lo, hi), labels[lo:hi] if labels.ndim else labels, list(seq_len[lo:hi]),
+            list(labels_len[lo:hi]) if labels_len is not None else None)
+
+
 class HipNetwork(Network):
     # model shape; subclasses override (the reference hard-codes these as locals of create_network)
     num_hidden = 500
@@ -60,6 +74,7 @@ class HipNetwork(Network):
     # A void step (rare: a persistent-recurrence abort on some rank) is noticed one call later and repeated then.
     # False: train() additionally waits for the END of its step (and repeats it there if it was void) - same code path.
     async_step = True
+    takes_audio = True                       # train_audio / validate_audio / evaluate_audio / decode_audio work on this network
 
     def __init__(self, config, fortraining=False):
         Network.__init__(self)
@@ -78,6 +93,8 @@ class HipNetwork(Network):
             torch.cuda.set_stream(self._torch_stream)
             stream = self._torch_stream.cuda_stream
         self.logger.info('Initializing network for %s.' % ('training' if fortraining else 'inference'))
+        self._device = device
+        self._featurizer = None                 # the front end of the *_audio calls, made at the first of them
         self.engine = self.make_engine(config, device, stream)
         self.engine.set_step_decode(True)
         self.engine.set_params(self.initial_params(self.engine.tensors(), seed=1))
@@ -194,16 +211,60 @@ class HipNetwork(Network):
             self.logger.warning('persistent recurrence aborted in a forward-only call: repeating it on the per-step kernels')
             return fn()
 
+    # ------------------------------------------------------------------ batches given as audio
+    def featurizer(self):
+        """The MFCC front end of the *_audio calls: on this network's device, shaped by the config."""
+        if self._featurizer is None:
+            from ..features import Featurizer
+            self._featurizer = Featurizer(self.config.samplerate, self.config.numcep, self.config.numcontext,
+                                          device_id=self._device)
+        return self._featurizer
+
+    def audio_batch(self, audios, rates=None):
+        """The batch `audios` (float32 utterances at `rates` Hz, None: all at config.samplerate) as train / validate /
+        evaluate / decode / stage_batch take it in the place of the padded features; its .seq_len is their seq_len."""
+        n, _ = self._towers()
+        if n > 1 and self.merge == 'stack_reshape' and self.bidirectional:
+            raise ValueError('batches from audio are padded per tower; the stack_reshape merge is a function of the padded '
+                             'length of the WHOLE batch: use features with num_gpus > 1 on this network')
+        return AudioBatch(self.config.samplerate, audios, rates, self.config.feature_size)
+
+    def _upload_audio(self, b, labels=None, labels_len=None):
+        self.engine.upload_batch_audio(self.featurizer(), b.audios, labels, labels_len, b.rates)
+
+    def _forward(self, mfccs, seq_len):
+        if isinstance(mfccs, AudioBatch):
+            self._upload_audio(mfccs)
+            return self.engine.forward_resident(len(mfccs), mfccs.shape[1])
+        return self.engine.forward(mfccs, seq_len)
+
+    def _upload(self, f, l, s, ll):
+        """the synchronous upload of one tower's shard"""
+        if isinstance(f, AudioBatch):
+            self._upload_audio(f, l, ll)
+        elif not (self._use_device_context() and
+                  self.engine.upload_batch_context(f, s, l, ll, self.config.numcontext, self.config.numcep)):
+            self.engine.upload_batch(f, s, l, ll)
+
     def _decode(self, mfccs, seq_len, which):
         if which == 'beam':
-            logits = self._retry_aborted(lambda: self.engine.forward(mfccs, seq_len))
+            logits = self._retry_aborted(lambda: self._forward(mfccs, seq_len))
             return self.engine.beam_search(logits, seq_len, self.beam_width, merge_repeated=True)[0]
+        if isinstance(mfccs, AudioBatch):
+            def run():
+                self._upload_audio(mfccs)
+                return self.engine.greedy_decode_resident(len(mfccs), mfccs.shape[1])
+            return self._retry_aborted(run)
         return self._retry_aborted(lambda: self.engine.greedy_decode(mfccs, seq_len))
 
     def _loss_ler_one(self, mfccs, labels, seq_len, labels_len):
         def run():
-            loss, _ = self.engine.loss(mfccs, seq_len, labels, labels_len)
-            hyps = None if self.decoder == 'beam' else self.engine.get_decoded(len(seq_len), np.asarray(mfccs).shape[1])
+            if isinstance(mfccs, AudioBatch):
+                self._upload_audio(mfccs, labels, labels_len)
+                loss, _ = self.engine.loss_resident(len(mfccs))
+            else:
+                loss, _ = self.engine.loss(mfccs, seq_len, labels, labels_len)
+            hyps = None if self.decoder == 'beam' else self.engine.get_decoded(len(seq_len), np.shape(mfccs)[1])
             return loss, hyps
         loss, hyps = self._retry_aborted(run)
         if hyps is None:
@@ -273,9 +334,8 @@ class HipNetwork(Network):
         ticket = self._take_staged(mfccs)
         if ticket is not None:
             self.engine.commit_batch(ticket)
-        elif not (self._use_device_context() and
-                  self.engine.upload_batch_context(f, s, l, ll, self.config.numcontext, self.config.numcep)):
-            self.engine.upload_batch(f, s, l, ll)
+        else:
+            self._upload(f, l, s, ll)
         beam = self.train_ler_decoder == 'beam'
         self.engine.set_step_decode(True, logits=beam, greedy=not beam)     # (the beam search reads the logits; no greedy pass then)
         self.engine.compute_grads()
@@ -382,8 +442,11 @@ class HipNetwork(Network):
         if len(mine) != 1:
             return False                        # towers time-sliced on one GPU: each upload replaces the resident batch
         f, l, s, ll = take_shard(mfccs, labels, seq_len, labels_len, n, mine[0])
-        ctx = self.config.numcontext if self._use_device_context() else 0
-        ticket = self.engine.stage_batch(f, s, l, ll, ctx, getattr(self.config, 'numcep', 0))
+        if isinstance(f, AudioBatch):
+            ticket = self.engine.stage_batch_audio(self.featurizer(), f.audios, l, ll, f.rates)[2]
+        else:
+            ctx = self.config.numcontext if self._use_device_context() else 0
+            ticket = self.engine.stage_batch(f, s, l, ll, ctx, getattr(self.config, 'numcep', 0))
         if ticket is None:
             return False
         with self._staged_lock:
@@ -422,9 +485,7 @@ class HipNetwork(Network):
             losses, lers, gsum, void = [], [], None, False
             for k in mine:
                 f, l, s, ll = take_shard(mfccs, labels, seq_len, labels_len, n, k)
-                if not (self._use_device_context() and
-                        self.engine.upload_batch_context(f, s, l, ll, self.config.numcontext, self.config.numcep)):
-                    self.engine.upload_batch(f, s, l, ll)
+                self._upload(f, l, s, ll)
                 beam = self.train_ler_decoder == 'beam'
                 self.engine.set_step_decode(True, logits=beam, greedy=not beam)
                 self.engine.compute_grads()
@@ -463,3 +524,21 @@ class HipNetwork(Network):
         self._settle()
         hyps = self._decode(mfccs, seq_len, self.decoder)
         return np.asarray([i for h in hyps for i in h], dtype=np.int64)
+
+    # ------------------------------------------------------------------ the same four calls on audio
+    # (utils.py:24-31 made on the device per batch instead of pickled ahead: the features never reach the host)
+    def train_audio(self, audios, rates, labels, labels_len):
+        b = self.audio_batch(audios, rates)
+        return self.train(b, labels, b.seq_len, labels_len)
+
+    def validate_audio(self, audios, rates, labels, labels_len):
+        b = self.audio_batch(audios, rates)
+        return self.validate(b, labels, b.seq_len, labels_len)
+
+    def evaluate_audio(self, audios, rates, labels, labels_len):
+        b = self.audio_batch(audios, rates)
+        return self.evaluate(b, labels, b.seq_len, labels_len)
+
+    def decode_audio(self, audios, rates=None):
+        b = self.audio_batch(audios, rates)
+        return self.decode(b, b.seq_len)

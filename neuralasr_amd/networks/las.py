@@ -112,6 +112,7 @@ class LAS(HipNetwork):
     beam_width = 1000
     max_decode_steps = 100
     length_penalty_weight = 0.5
+    takes_audio = False                      # the beam search reads host features (nasr_las_beam_search)
 
     def make_engine(self, config, device, stream):
         e = LasEngine(config.feature_size, self.num_classes, num_hidden=self.num_hidden, num_layers=self.num_layers,
@@ -203,6 +204,10 @@ class LAS(HipNetwork):
 
     def stage_batch(self, mfccs, labels, seq_len, labels_len):
         return False
+
+    def audio_batch(self, audios, rates=None):
+        raise NotImplementedError('LAS takes features: its beam search reads them from the host (nasr_las_beam_search), and '
+                                  'its step uploads per tower; LasEngine.upload_batch_audio is the audio path of a LAS handle')
 
     def _settle(self):
         pass

@@ -2,6 +2,7 @@
 one validation batch every report_step, same log-line formats.
 
   python -m neuralasr_amd.train <config>
+  python -m neuralasr_amd.train <config> --from-audio     # from the [MFCC Featurizer] input CSV: features made on the GPU per batch
   python -m torch.distributed.run --nproc-per-node N -m neuralasr_amd.train <config>   # num_gpus = N"""
 import argparse
 import os
@@ -105,6 +106,9 @@ def train_model(dataTrain, datavalid, config, prefetch=2):
 def main(argv=None):
     ap = argparse.ArgumentParser(description='Train speech recognizer on featurized mfcc files.')
     ap.add_argument('config', help='Configuration file.')
+    ap.add_argument('--from-audio', action='store_true',
+                    help='read WAV files and transcripts from the [MFCC Featurizer] input CSV instead of pickled features; '
+                         'the features are made on the GPU for every batch (needs rand_shift=0)')
     args = ap.parse_args(argv)
     if int(os.environ.get('WORLD_SIZE', '1')) > 1:
         import torch
@@ -112,13 +116,36 @@ def main(argv=None):
         torch.cuda.set_device(int(os.environ.get('LOCAL_RANK', '0')))
         dist.init_process_group('nccl')
     config = Config(args.config, isTraining=True)
-    dataTrain = DataSet(config.train_input, config)
+    if args.from_audio:
+        dataTrain, dataValid = audio_datasets(args.config, config)
+    else:
+        dataTrain = DataSet(config.train_input, config)
+        dataValid = None
+        if config.test_input:
+            config_test = Config(args.config, isTraining=True)
+            config_test.epochs = None
+            dataValid = DataSet(config_test.test_input, config_test)
+    return train_model(dataTrain, dataValid, config)
+
+
+def audio_datasets(configfile, config):
+    """--from-audio: the training and the validation set of the [MFCC Featurizer] input CSV as train_model reads them.
+    The batches hold audio (features.AudioBatch); HipNetwork stages and uploads them through the GPU front end."""
+    from .audio_dataset import AudioDataSet, AudioFeed
+    if config.rand_shift > 0:
+        raise ValueError('--from-audio cannot be combined with rand_shift > 0 (rand_shift=%d): the roll-and-crop leaves real '
+                         'neighbour frames where the context pads were, and a batch from audio is rebuilt from centre frames '
+                         'and pad values; set rand_shift=0 or train from the pickled features' % config.rand_shift)
+    if not config.mfcc_input:
+        raise ValueError("--from-audio needs 'input' in the [MFCC Featurizer] section of " + configfile)
+    dataTrain = AudioFeed(AudioDataSet(config.mfcc_input, config, 'train'))     # (writes the symbol table when there is none)
     dataValid = None
     if config.test_input:
-        config_test = Config(args.config, isTraining=True)
+        config_test = Config(configfile, isTraining=True)
         config_test.epochs = None
-        dataValid = DataSet(config_test.test_input, config_test)
-    train_model(dataTrain, dataValid, config)
+        valid = AudioDataSet(config_test.mfcc_input, config_test, 'test')
+        dataValid = AudioFeed(valid) if valid.get_num_of_sample() else None
+    return dataTrain, dataValid
 
 
 if __name__ == '__main__':

@@ -4,7 +4,11 @@ device-to-host copies (device events), and through the fp64 NumPy restatement of
 Prints one JSON line.   python tools/mfccbench.py [--utts 64 --seconds 10 --sr 16000 --numcep 26 --numcontext 10]
 With --native-sr R the utterances are made at R Hz and resampled to --sr on the GPU first (nasr_featurize_rates); the
 line then also carries a "resample" field: nasr_resample's phases alone, and the fp64 restatement of
-tests/resample_ref.py timed on a few utterances and scaled to the batch."""
+tests/resample_ref.py timed on a few utterances and scaled to the batch.
+With --to-batch the line also carries a "to_batch" field: the same batch made resident on a BiLSTM handle by
+Engine.upload_batch_audio (features written into the batch slot on the device) and, in the same run, by the route through
+the host (Featurizer.compute, zero-pad, Engine.upload_batch_context): wall time of each up to the end of the upload's
+device work, and the audio call's device-timed copies and kernels."""
 import argparse
 import json
 import os
@@ -32,6 +36,45 @@ def synth(n, sr, seed):
     return (np.clip(np.round(x * 0.3 * 32767), -32768, 32767).astype(np.int16).astype(np.float32) / np.float32(32768))
 
 
+def batch_routes(a, fz, audios, rates):
+    """the batch made resident on a model handle: through the host, and straight from audio"""
+    from neuralasr_amd.engine import Engine
+    e = Engine(fz.width, 128, 1, True, 'stack_reshape', 30)
+    labels, ll = np.ones((len(audios), 1), np.int32), [1] * len(audios)
+
+    def host_route():
+        feats = fz.compute(audios, rates=rates)
+        T = max(f.shape[0] for f in feats)
+        x = np.zeros((len(feats), T, fz.width), np.float32)
+        for b, f in enumerate(feats):
+            x[b, :f.shape[0]] = f
+        seq = [f.shape[0] for f in feats]
+        if not e.upload_batch_context(x, seq, labels, ll, fz.numcontext, fz.numcep):
+            e.upload_batch(x, seq, labels, ll)
+        e.synchronize()
+
+    def audio_route():
+        e.upload_batch_audio(fz, audios, labels, ll, rates)
+        e.synchronize()
+    out = {}
+    for name, fn in (('host_route', host_route), ('audio_route', audio_route)):
+        fn()                                              # warm-up: slot buffers
+        wall = h2d = k = 0.0
+        for _ in range(a.reps):
+            t0 = time.perf_counter()
+            fn()
+            wall += time.perf_counter() - t0
+            if name == 'audio_route':
+                t = fz.times()
+                h2d += t[0]; k += t[1]
+        out[name + '_ms'] = round(wall / a.reps * 1e3, 3)
+        if name == 'audio_route':
+            out['audio_h2d_ms'] = round(h2d / a.reps, 3)
+            out['audio_kernel_ms'] = round(k / a.reps, 3)
+    e.close()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--utts', type=int, default=64)
@@ -42,6 +85,7 @@ def main():
     ap.add_argument('--reps', type=int, default=10)
     ap.add_argument('--ref-utts', type=int, default=8, help='utterances the fp64 restatement is timed and checked on')
     ap.add_argument('--native-sr', type=int, default=None, help='make the audio at this rate and resample it to --sr')
+    ap.add_argument('--to-batch', action='store_true', help='also time the batch into a model handle, both routes')
     a = ap.parse_args()
     native = a.native_sr or a.sr
     n = int(a.seconds * native)
@@ -81,6 +125,7 @@ def main():
                     'outputs': int(sum(x.size for x in at_sr)),
                     'ref_fp64_s_batch': round(t_rs, 3), 'ref_checked_utts': nrs,
                     'bitwise_vs_ref': all(x.tobytes() == y.tobytes() for x, y in zip(at_sr, restated))}
+    to_batch = batch_routes(a, fz, audios, rates) if a.to_batch else None
     t0 = time.perf_counter()
     ref = [R.features(x, a.sr, a.numcontext, a.numcep)[0] for x in at_sr[:nref]]
     t_ref = (time.perf_counter() - t0) * a.utts / nref
@@ -95,7 +140,8 @@ def main():
         'frames_per_s_call': round(frames / (wall / m)), 'frames_per_s_kernels': round(frames / (t_k / m * 1e-3)),
         'ref_fp64_s_batch': round(t_ref, 3), 'ref_checked_utts': nref,
         'max_abs_err': float(err.max()), 'mean_abs_err': float(err.mean()),
-        **({} if resample is None else {'resample': resample})}))
+        **({} if resample is None else {'resample': resample}),
+        **({} if to_batch is None else {'to_batch': to_batch})}))
 
 
 if __name__ == '__main__':
