@@ -70,6 +70,12 @@ struct GemmTPHDesc {
   const unsigned char* B;   // TPH of [>= N rows][K_B]
   float* C;
   int M, N, K;              // M, N multiples of 4 (row blocks past M / N read as zero), K = contraction length
+  // K and the operands' k extents.  A step of the kernel is TWO k-blocks, so the sum runs over k in [0, Kc), Kc =
+  // 32 * ceil(K / 32): whatever an operand holds in [K, Kc) (A: after its shift) ENTERS the product - the rest of a ragged
+  // k-block and, when ceil(K/16) is odd, the whole k-block ceil(K/16) if it is < nkbA / nkbB.  Nothing from Kc on is read.
+  // So either K covers the operand's extent (nkbA, nkbB <= ceil(K/16): every caller - the planes are written by
+  // launch_tph_split2 for exactly K, which zero-fills the ragged tail) or the operand holds zeros in [K, Kc).
+  // (tests/test_gpu_gemm_kernels.py: test_tph_contraction_runs_over_whole_steps)
   int nkbA, nkbB;           // k-blocks per row block in A / B: ceil(K_A/16), ceil(K_B/16)
   int ldc;
   int a_kshift;             // multiple of 16: A is read at k + a_kshift, zero outside [0, K_A)
@@ -87,7 +93,8 @@ struct GemmTPHDesc {
   int64_t c_bstride, ainv_bstride, binv_bstride;
   int a_kshift1;
   bool side;                // the 3-wave 128 x 192 instantiation that fits beside a persistent-recurrence workgroup
-  const int* c_map;         // (or NULL) output row m goes to row c_map[m] of C (-1: dropped); nbatch == 1 only
+  const int* c_map;         // (or NULL) output row m goes to row c_map[m] of C (-1: dropped); nbatch == 1 only.  `side` has no
+                            // scattering epilogue: with split_k == 1 it ignores c_map (row m -> row m); its reduction scatters
 };
 hipError_t gemm_tph_prepare();
 int gemm_tph_pick_split(int M, int N, int K, int nbatch = 1);

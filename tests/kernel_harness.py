@@ -1,0 +1,246 @@
+"""ctypes side of tests/kernel_harness/harness.hip (neuralasr_amd/libnasr_kt.so, built by neuralasr_amd/build.py): the
+GEMM-layer launchers of csrc/kernels.h, callable with NumPy arrays.  Every call raises on a HIP error or a refused
+argument; outputs come back as fresh arrays whose untouched bytes still hold FILL."""
+import ctypes
+import os
+from ctypes import POINTER, Structure, c_float, c_int, c_longlong, c_ubyte, c_ulonglong, c_void_p
+
+import numpy as np
+
+import gemm_ref as R
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+KT_PATH = os.path.join(ROOT, 'neuralasr_amd', 'libnasr_kt.so')
+SYMBOLS = ['kt_gemm_pick_split', 'kt_gemm_tp_tile_rows', 'kt_gemm_tph_pick_split', 'kt_tp_split2_parts', 'kt_tph_bytes',
+           'kt_gemm_f32', 'kt_tph_scales', 'kt_tph_scales_batch', 'kt_tph_scales_from_parts', 'kt_tph_split2', 'kt_gemm_tph',
+           'kt_colsum', 'kt_colsum_parts', 'kt_reduce_slabs', 'kt_reduce_slabs_rows']
+
+FILL = 0xCD                                   # pre-fill byte of every output buffer
+FILL_F32 = np.frombuffer(bytes([FILL] * 4), dtype=np.float32)[0]
+
+
+class KtGemm(Structure):
+    _fields_ = [(n, c_int) for n in ('M', 'N', 'K', 'lda', 'ldb', 'ldc', 'a_col', 'b_col', 'a_shift', 'a_rows', 'split_k')]
+
+
+class KtScaleJob(Structure):
+    _fields_ = [('src', c_void_p), ('src_floats', c_longlong), ('rows', c_int), ('K', c_int), ('ld', c_int), ('pad', c_int),
+                ('row_scale', c_void_p), ('row_inv', c_void_p), ('col_scale', c_void_p), ('col_inv', c_void_p)]
+
+
+class KtTph(Structure):
+    _fields_ = ([(n, c_int) for n in ('M', 'N', 'K', 'KA', 'KB', 'ldc', 'a_kshift', 'a_kshift1', 'split_k', 'tile_rows',
+                                      'nbatch', 'side')] +
+                [(n, c_longlong) for n in ('a_bstride', 'b_bstride', 'c_bstride', 'ainv_bstride', 'binv_bstride')] +
+                [('a_rows', c_int), ('b_rows', c_int)])
+
+
+_lib = None
+
+
+def lib():
+    global _lib
+    if _lib is None:
+        if not os.path.exists(KT_PATH):
+            raise ImportError(f'{KT_PATH} is missing: run `python -m neuralasr_amd.build`')
+        _lib = ctypes.CDLL(KT_PATH)
+        _lib.kt_tph_bytes.restype = c_ulonglong
+    return _lib
+
+
+def _f(a):
+    return None if a is None else a.ctypes.data_as(POINTER(c_float))
+
+
+def _i(a):
+    return None if a is None else a.ctypes.data_as(POINTER(c_int))
+
+
+def _b(a):
+    return None if a is None else a.ctypes.data_as(POINTER(c_ubyte))
+
+
+def _f32(a):
+    return None if a is None else np.ascontiguousarray(a, dtype=np.float32)
+
+
+def _i32(a):
+    return None if a is None else np.ascontiguousarray(a, dtype=np.int32)
+
+
+def _check(rc, what):
+    if rc != 0:
+        raise RuntimeError(f'{what}: ' + ('arguments refused by the harness' if rc == -1 else f'HIP error {rc}'))
+
+
+def _out(n):
+    return np.zeros(n, dtype=np.float32)
+
+
+def gemm_f32(c):
+    """Runs a gemm_ref.GemmCase; returns the whole C buffer [c_rows][ldc]."""
+    A, B = _f32(c.A), _f32(c.B)
+    d = KtGemm(c.M, c.N, c.K, A.shape[1], B.shape[1], c.ldc, int(c.a_col), int(c.b_col), c.a_shift, c.a_rows, c.split_k)
+    C = _out(c.c_rows * c.ldc)
+    a_map, c_map, bias = _i32(c.a_map), _i32(c.c_map), _f32(c.bias)
+    rc = lib().kt_gemm_f32(ctypes.byref(d), _f(A), c_longlong(A.size), _f(B), c_longlong(B.size), _f(C), c_longlong(C.size),
+                           _i(a_map), 0 if a_map is None else a_map.size, _i(c_map), _f(bias), FILL)
+    _check(rc, 'kt_gemm_f32')
+    return C.reshape(c.c_rows, c.ldc)
+
+
+def tph_planes(c, poison=False, gap=(0, 0, 0, 0, 0)):
+    """Planes, inverse scales and strides of a gemm_ref.TphCase, built with the Python encoder and scale model.  poison: NaN
+    in the plane rows [M, rup32(M)) / [N, rup32(N)) (needs operands of exactly M / N rows).  gap: extra (A row blocks, B row
+    blocks, C floats, a_inv floats, b_inv floats) between the two batches, so that all five strides differ."""
+    nb = 2 if c.nbatch > 1 else 1
+    planes, invs = [[], []], [[], []]
+    for o, mats in enumerate((c.A, c.B)):
+        for b in range(nb):
+            x = np.asarray(mats[b], dtype=np.float32)
+            s, inv = R.scale_model(R.line_max(x, 1))
+            h1, h2 = R.split_parts(x * s[:, None])
+            if poison:
+                pad = (-x.shape[0]) % 32
+                h1 = np.vstack([h1, np.full((pad, x.shape[1]), np.nan, np.float16)])
+                h2 = np.vstack([h2, np.full((pad, x.shape[1]), np.nan, np.float16)])
+            planes[o].append(R.tph_encode_parts(h1, h2))
+            invs[o].append(inv)
+    out = {}
+    for o, key in enumerate('ab'):
+        nkb = (np.asarray((c.A, c.B)[o][0]).shape[1] + 15) // 16
+        stride = planes[o][0].size + gap[o] * nkb * 2048
+        buf = np.full(stride * (nb - 1) + planes[o][nb - 1].size, 0xFF, dtype=np.uint8)      # the gap: NaN halves
+        istride = invs[o][0].size + gap[3 + o]
+        ibuf = np.full(istride * (nb - 1) + invs[o][nb - 1].size, np.nan, dtype=np.float32)
+        for b in range(nb):
+            buf[b * stride:b * stride + planes[o][b].size] = planes[o][b]
+            ibuf[b * istride:b * istride + invs[o][b].size] = invs[o][b]
+        out[key] = (buf, stride, ibuf, istride)
+    out['c_bstride'] = c.c_rows * c.ldc + gap[2]
+    return out
+
+
+def gemm_tph(c, planes=None, fp32=False):
+    """Runs a gemm_ref.TphCase: from planes (tph_planes(c) unless given) or, fp32=True, from the fp32 operands through
+    launch_tph_scales + launch_tph_split2.  Returns the C buffer(s) [nbatch][c_rows][ldc] (nbatch == 2 with split_k > 1:
+    c_bstride = M * N as GemmTPHDesc demands)."""
+    nb = 2 if c.nbatch > 1 else 1
+    KA, KB = np.asarray(c.A[0]).shape[1], np.asarray(c.B[0]).shape[1]
+    d = KtTph(M=c.M, N=c.N, K=c.K, KA=KA, KB=KB, ldc=c.ldc, a_kshift=c.a_kshift, a_kshift1=c.a_kshift1, split_k=c.split_k,
+              tile_rows=c.tile_rows, nbatch=c.nbatch, side=int(c.side))
+    bias, c_map = _f32(c.bias), _i32(c.c_map)
+    if fp32:
+        assert nb == 1
+        A, B = _f32(c.A[0]), _f32(c.B[0])
+        d.a_rows, d.b_rows = A.shape[0], B.shape[0]
+        c_bstride = c.c_rows * c.ldc
+        C = _out(c_bstride)
+        rc = lib().kt_gemm_tph(ctypes.byref(d), _f(A), _f(B), None, c_longlong(0), None, c_longlong(0), None, None, _f(C),
+                               c_longlong(C.size), _f(bias), _i(c_map), FILL)
+    else:
+        p = planes or tph_planes(c)
+        (ab, d.a_bstride, ai, d.ainv_bstride), (bb, d.b_bstride, bi, d.binv_bstride) = p['a'], p['b']
+        c_bstride = d.c_bstride = p['c_bstride']
+        d.a_rows, d.b_rows = ai.size, bi.size
+        C = _out(c_bstride * (nb - 1) + c.c_rows * c.ldc)
+        rc = lib().kt_gemm_tph(ctypes.byref(d), None, None, _b(ab), c_longlong(ab.size), _b(bb), c_longlong(bb.size), _f(ai),
+                               _f(bi), _f(C), c_longlong(C.size), _f(bias), _i(c_map), FILL)
+    _check(rc, 'kt_gemm_tph')
+    return C, c_bstride
+
+
+def tph_scales(src, rows, K, want_rows=True, want_cols=True):
+    src = _f32(src)
+    rs, ri, cs, ci = (_out(rows) if want_rows else None, _out(rows) if want_rows else None,
+                      _out(K) if want_cols else None, _out(K) if want_cols else None)
+    rc = lib().kt_tph_scales(_f(src), c_longlong(src.size), rows, K, src.shape[1], _f(rs), _f(ri), _f(cs), _f(ci), FILL)
+    _check(rc, 'kt_tph_scales')
+    return rs, ri, cs, ci
+
+
+def tph_scales_batch(jobs):
+    """jobs: [(src 2-D, rows, K, want_rows)] -> [(rs, ri, cs, ci)]"""
+    arr = (KtScaleJob * len(jobs))()
+    keep, outs = [], []
+    for j, (src, rows, K, want_rows) in enumerate(jobs):
+        src = _f32(src)
+        o = (_out(rows) if want_rows else None, _out(rows) if want_rows else None, _out(K), _out(K))
+        keep.append(src)
+        outs.append(o)
+        arr[j] = KtScaleJob(src.ctypes.data, src.size, rows, K, src.shape[1], 0, *[None if a is None else a.ctypes.data for a in o])
+    _check(lib().kt_tph_scales_batch(arr, len(jobs), FILL), 'kt_tph_scales_batch')
+    return outs
+
+
+def tph_scales_from_parts(rowpart, colpart):
+    rowpart, colpart = _f32(rowpart), _f32(colpart)
+    nrp, rows = rowpart.shape if rowpart is not None else (0, 0)
+    ncp, K = colpart.shape if colpart is not None else (0, 0)
+    rs, ri, cs, ci = (_out(rows) if rows else None, _out(rows) if rows else None, _out(K) if K else None, _out(K) if K else None)
+    rc = lib().kt_tph_scales_from_parts(_f(rowpart), nrp, rows, _f(rs), _f(ri), _f(colpart), ncp, K, _f(cs), _f(ci), FILL)
+    _check(rc, 'kt_tph_scales_from_parts')
+    return rs, ri, cs, ci
+
+
+def tph_split2(src, rows, K, row_scale=None, rs=1.0, col_scale=None, cs=1.0, rowmap=None, rowmap2=None, col2=0):
+    """-> (tpN bytes, tpT bytes, colpart [parts][K])"""
+    src = _f32(src)
+    tpN = np.zeros(R.tph_bytes(rows, K), dtype=np.uint8)
+    tpT = np.zeros(R.tph_bytes(K, rows), dtype=np.uint8)
+    parts = lib().kt_tp_split2_parts(rows)
+    colpart = _out(parts * K)
+    row_scale, col_scale, rowmap, rowmap2 = _f32(row_scale), _f32(col_scale), _i32(rowmap), _i32(rowmap2)
+    rc = lib().kt_tph_split2(_f(src), src.shape[0], rows, K, src.shape[1], _f(row_scale), c_float(rs), _f(col_scale), c_float(cs),
+                             _b(tpN), _b(tpT), _f(colpart), _i(rowmap), _i(rowmap2), col2, FILL)
+    _check(rc, 'kt_tph_split2')
+    return tpN, tpT, colpart.reshape(parts, K)
+
+
+def colsum(M, R_, N, pad=4):
+    M = _f32(M)
+    out = _out(N + pad)
+    _check(lib().kt_colsum(_f(M), R_, N, M.shape[1], _f(out), out.size, FILL), 'kt_colsum')
+    return out
+
+
+def colsum_parts(part, N, pad=4):
+    part = _f32(part)
+    out = _out(N + pad)
+    _check(lib().kt_colsum_parts(_f(part), part.shape[0], N, _f(out), out.size, FILL), 'kt_colsum_parts')
+    return out
+
+
+def reduce_slabs(slabs, pad=4):
+    slabs = _f32(slabs)
+    S, n = slabs.shape[0], slabs[0].size
+    out = _out(n + pad)
+    _check(lib().kt_reduce_slabs(_f(slabs), S, c_longlong(n), _f(out), c_longlong(out.size), FILL), 'kt_reduce_slabs')
+    return out
+
+
+def reduce_slabs_rows(slabs, ldc, rowmap, out_rows):
+    slabs, rowmap = _f32(slabs), _i32(rowmap)
+    S, M, N = slabs.shape
+    out = _out(out_rows * ldc)
+    rc = lib().kt_reduce_slabs_rows(_f(slabs), S, M, N, ldc, _i(rowmap), _f(out), c_longlong(out.size), FILL)
+    _check(rc, 'kt_reduce_slabs_rows')
+    return out.reshape(out_rows, ldc)
+
+
+# ------------------------------------------------------------------ checks shared by the GPU tests
+def untouched(buf):
+    """Mask of the floats that still hold the pre-fill pattern."""
+    return np.asarray(buf, dtype=np.float32).view(np.uint32) == np.uint32(int.from_bytes(bytes([FILL] * 4), 'little'))
+
+
+def expected_buffer(C64, rows, c_rows, ldc):
+    """(expected [c_rows][ldc] fp64, written mask) of a result scattered by rows[]."""
+    exp = np.zeros((c_rows, ldc))
+    mask = np.zeros((c_rows, ldc), dtype=bool)
+    N = C64.shape[1]
+    for m, r in enumerate(rows):
+        if r >= 0:
+            exp[r, :N] = C64[m]
+            mask[r, :N] = True
+    return exp, mask
