@@ -36,7 +36,8 @@ SYMBOLS = [
     'nasr_wavenet_set_bn_hold', 'nasr_wavenet_get_batch_stats', 'nasr_wavenet_apply_bn_stats',
     'nasr_create_las', 'nasr_las_set_sampling', 'nasr_las_get_sampling', 'nasr_las_forward', 'nasr_las_get_logits',
     'nasr_las_get_fed_ids', 'nasr_las_get_sampled', 'nasr_las_beam_search', 'nasr_las_beam_get_ids',
-    'nasr_las_beam_get_trace', 'nasr_las_beam_get_final', 'nasr_las_beam_get_times',
+    'nasr_las_beam_get_trace', 'nasr_las_beam_get_final', 'nasr_las_beam_get_times', 'nasr_las_forward_resident',
+    'nasr_las_beam_search_resident',
     'nasr_create_featurizer', 'nasr_mfcc_frames', 'nasr_mfcc_filterbank', 'nasr_featurize', 'nasr_featurize_times',
     'nasr_resample_filter', 'nasr_resample_length', 'nasr_resample', 'nasr_featurize_rates',
     'nasr_upload_batch_audio', 'nasr_stage_batch_audio', 'nasr_forward_resident', 'nasr_loss_resident',
@@ -188,10 +189,12 @@ def load():
         'nasr_las_set_sampling': (c_int, [H, c_float, c_uint32, c_uint32, c_int]),
         'nasr_las_get_sampling': (c_int, [H, POINTER(c_float), POINTER(c_uint32), POINTER(c_uint32), POINTER(c_int)]),
         'nasr_las_forward': (c_int, [H, fp, ip, ip, ip, c_int, c_int, c_int, c_int, fp]),
+        'nasr_las_forward_resident': (c_int, [H, c_int, fp]),
         'nasr_las_get_logits': (c_int, [H, fp]),
         'nasr_las_get_fed_ids': (c_int, [H, ip]),
         'nasr_las_get_sampled': (c_int, [H, ip]),
         'nasr_las_beam_search': (c_int, [H, fp, ip, c_int, c_int, c_int, c_int, c_int, c_int, c_float, ip]),
+        'nasr_las_beam_search_resident': (c_int, [H, c_int, c_int, c_int, c_int, c_float, ip]),
         'nasr_las_beam_get_ids': (c_int, [H, ip]),
         'nasr_las_beam_get_trace': (c_int, [H, fp, ip, ip]),
         'nasr_las_beam_get_final': (c_int, [H, fp, ip, ip]),

@@ -14,6 +14,23 @@ log = get_logger()
 _INT_KEYS = ('samplerate', 'numcep', 'batch_size', 'epochs', 'start_step', 'report_step', 'num_gpus', 'label_context')
 
 
+def network_class(name):
+    """the class a config's `network=` names, not yet constructed"""
+    parts = name.split('.')
+    modname, classname = '.'.join(parts[:-1]), parts[-1]
+    module = None
+    for candidate in (modname, 'neuralasr_amd.' + modname):
+        try:
+            module = importlib.import_module(candidate)
+            getattr(module, classname)
+            break
+        except (ImportError, AttributeError):
+            module = None
+    if module is None:
+        raise ImportError('cannot load network class ' + name)
+    return getattr(module, classname)
+
+
 class Config(object):
     def __init__(self, configfile, isTraining=False):
         self.isTraining = isTraining
@@ -47,19 +64,7 @@ class Config(object):
             raise ValueError("Missing 'test_input' in configuration file: " + configfile)
 
     def load_network(self, fortraining=False):
-        parts = self.network.split('.')
-        modname, classname = '.'.join(parts[:-1]), parts[-1]
-        module = None
-        for candidate in (modname, 'neuralasr_amd.' + modname):
-            try:
-                module = importlib.import_module(candidate)
-                getattr(module, classname)
-                break
-            except (ImportError, AttributeError):
-                module = None
-        if module is None:
-            raise ImportError('cannot load network class ' + self.network)
-        return getattr(module, classname)(self, fortraining=fortraining)
+        return network_class(self.network)(self, fortraining=fortraining)
 
     def print_config(self):
         names = ['samplerate', 'numcep', 'numcontext', 'rand_shift', 'batch_size', 'epochs', 'learningrate',

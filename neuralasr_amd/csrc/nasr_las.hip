@@ -399,14 +399,17 @@ int las_backward(nasr_ctx* h) {
 // ------------------------------------------------------------------ beam search
 enum { LB_ENC = 0, LB_GEMM, LB_CELL, LB_ATTN, LB_SEL, LB_TREE, LB_WAIT, LB_COUNT };
 
-int las_beam_ensure(nasr_ctx* h, LasBeam& m, int B, int T, int W, int max_steps) {
+// host_feats: the search packs features of its own (m.feats, m.X0); otherwise it reads the resident batch's X0
+int las_beam_ensure(nasr_ctx* h, LasBeam& m, int B, int T, int W, int max_steps, bool host_feats) {
   const int Bp = rup(B, 16), nrows = B * W, R = rup(nrows, 16), C = h->C;
   int Lr[LasBeam::NL];
   las_lengths(T, Lr);
   const size_t L4B = (size_t)Lr[LasBeam::NL - 1] * Bp, MR = (size_t)max_steps * nrows;
   bool grew = false, ok = true;
-  ok &= m.feats.ensure((size_t)B * T * h->F * 4, &grew);
-  ok &= m.X0.ensure((size_t)T * Bp * h->Fp * 4, &grew);
+  if (host_feats) {
+    ok &= m.feats.ensure((size_t)B * T * h->F * 4, &grew);
+    ok &= m.X0.ensure((size_t)T * Bp * h->Fp * 4, &grew);
+  }
   for (int l = 0; l < LasBeam::NL; ++l) {
     const size_t Rl = (size_t)Lr[l] * Bp;
     if (l > 0) ok &= m.X[l].ensure(Rl * 4 * LAS_HE * 4, &grew);
@@ -437,12 +440,14 @@ int las_beam_ensure(nasr_ctx* h, LasBeam& m, int B, int T, int W, int max_steps)
 // The inference graph of the reference: the encoder, the tiled initial state, then per step the decoder
 // cell and attention over all beam rows, the scores and the exact top-W, the update by parent; gather_tree at the end.
 // Steps are enqueued in chunks; the host reads the device's done word once per chunk.
+// feats: host features [B][T][F], copied and packed into the search's own X0; nullptr: the encoder reads the resident
+// batch's time-major X0 (B, T: the resident batch's), which the search only reads.
 int las_beam_search(nasr_ctx* h, const float* feats, int B, int T, int W, int max_steps, int start_id, int end_id, float lp) {
   LasState& s = *h->las;
   if (!s.beam) s.beam.reset(new LasBeam());
   LasBeam& m = *s.beam;
   m.have = false;
-  if (int rc = las_beam_ensure(h, m, B, T, W, max_steps)) return rc;
+  if (int rc = las_beam_ensure(h, m, B, T, W, max_steps, feats != nullptr)) return rc;
   const int Bp = m.Bp, R = m.R, nrows = B * W, C = h->C, Cp = h->Cp;
   const int L4 = m.Lr[LasBeam::NL - 1];
   const float* P = h->P;
@@ -463,9 +468,12 @@ int las_beam_search(nasr_ctx* h, const float* feats, int B, int T, int W, int ma
   mark(-1);
   HIPCHK(h, hipMemcpyAsync(m.pen.p, m.hpen.data(), m.hpen.size() * 4, hipMemcpyHostToDevice, st));
   HIPCHK(h, hipMemsetAsync(m.flags.p, 0, 8, st));
-  HIPCHK(h, hipMemcpyAsync(m.feats.p, feats, (size_t)B * T * h->F * 4, hipMemcpyHostToDevice, st));
-  launch_pack_feats(m.feats.as<float>(), m.X0.as<float>(), B, Bp, T, h->F, h->Fp, st);
-  if (int rc = las_encode(h, m.X0.as<float>(), T, B, Bp, m.Lr, m.X, m.xp, m.act, m.c, m.out)) return rc;
+  if (feats) {
+    HIPCHK(h, hipMemcpyAsync(m.feats.p, feats, (size_t)B * T * h->F * 4, hipMemcpyHostToDevice, st));
+    launch_pack_feats(m.feats.as<float>(), m.X0.as<float>(), B, Bp, T, h->F, h->Fp, st);
+  }
+  const float* X0 = feats ? m.X0.as<float>() : h->X0.as<float>();
+  if (int rc = las_encode(h, X0, T, B, Bp, m.Lr, m.X, m.xp, m.act, m.c, m.out)) return rc;
   const float* mem = fp(m.out[LasBeam::NL - 1]);
   if (int rc = las_gemm(h, mem, P + s.off_wmem, fp(m.keys), L4 * Bp, LAS_HD, LAS_HD, LAS_HD, LAS_HD, LAS_HD, false, false))
     return rc;
@@ -615,18 +623,31 @@ int nasr_las_get_sampling(nasr_handle h, float* p, uint32_t* seed, uint32_t* cou
   return NASR_OK;
 }
 
+namespace {
+// the decoder pass of nasr_las_forward / nasr_las_forward_resident on the resident batch
+int las_forward_out(nasr_ctx* h, int sample, float* logits_out) {
+  if (int rc = las_forward(h, sample != 0)) return rc;
+  if (logits_out) return nasr_las_get_logits(h, logits_out);
+  return sync_checked(h);
+}
+}  // namespace
+
 int nasr_las_forward(nasr_handle h, const float* feats, const int32_t* seq_len, const int32_t* labels, const int32_t* label_len,
                      int B, int T, int U, int sample, float* logits_out) {
   LasState* s = las_of(h);
   if (!s) return h ? h->fail(NASR_ERR_STATE, "nasr_las_forward: not a LAS handle") : NASR_ERR_ARG;
   if (!labels || !label_len) return h->fail(NASR_ERR_ARG, "nasr_las_forward needs labels");
   HIPCHK(h, hipSetDevice(h->device));
-  int rc = upload(h, feats, seq_len, labels, label_len, B, T, U);
-  if (rc) return rc;
-  rc = las_forward(h, sample != 0);
-  if (rc) return rc;
-  if (logits_out) return nasr_las_get_logits(h, logits_out);
-  return sync_checked(h);
+  if (int rc = upload(h, feats, seq_len, labels, label_len, B, T, U)) return rc;
+  return las_forward_out(h, sample, logits_out);
+}
+
+int nasr_las_forward_resident(nasr_handle h, int sample, float* logits_out) {
+  LasState* s = las_of(h);
+  if (!s) return h ? h->fail(NASR_ERR_STATE, "nasr_las_forward_resident: not a LAS handle") : NASR_ERR_ARG;
+  if (!h->resident) return h->fail(NASR_ERR_STATE, "nasr_las_forward_resident: no resident batch");
+  HIPCHK(h, hipSetDevice(h->device));
+  return las_forward_out(h, sample, logits_out);
 }
 
 int nasr_las_get_logits(nasr_handle h, float* logits_out) {
@@ -653,26 +674,41 @@ int nasr_las_get_sampled(nasr_handle h, int32_t* sampled_out) {
   return las_read_bu(h, s->sampled, 1, 1, 4, sampled_out);
 }
 
+namespace {
+// The argument ranges of a search and the search itself.  feats: host features, or nullptr for the resident batch's X0;
+// seq_len: the host's copy of the batch's lengths.
+int las_beam_call(nasr_ctx* h, const std::string& fn, const float* feats, const int32_t* seq_len, int B, int T, int beam_width,
+                  int max_steps, int start_id, int end_id, float length_penalty, int32_t* steps_out) {
+  if (B < 1 || B > 64 || T < 1) return h->fail(NASR_ERR_ARG, fn + ": B must be in [1,64] and T >= 1");
+  for (int b = 0; b < B; ++b)
+    if (seq_len[b] < 1 || seq_len[b] > T) return h->fail(NASR_ERR_ARG, fn + ": seq_len[" + std::to_string(b) + "] out of [1,T]");
+  if (beam_width < 1 || beam_width > 1024) return h->fail(NASR_ERR_ARG, fn + ": beam_width must be in [1,1024]");
+  if (max_steps < 1 || max_steps > 1000) return h->fail(NASR_ERR_ARG, fn + ": max_steps must be in [1,1000]");
+  if (start_id < 0 || start_id >= h->C || end_id < 0 || end_id >= h->C)
+    return h->fail(NASR_ERR_ARG, fn + ": start_id and end_id must be in [0, num_classes-1]");
+  if (!(length_penalty >= 0.f) || !std::isfinite(length_penalty))
+    return h->fail(NASR_ERR_ARG, fn + ": length_penalty must be finite and >= 0");
+  HIPCHK(h, hipSetDevice(h->device));
+  if (int rc = las_beam_search(h, feats, B, T, beam_width, max_steps, start_id, end_id, length_penalty)) return rc;
+  if (steps_out) *steps_out = h->las->beam->Tdec;
+  return NASR_OK;
+}
+}  // namespace
+
 int nasr_las_beam_search(nasr_handle h, const float* feats, const int32_t* seq_len, int B, int T, int beam_width, int max_steps,
                          int start_id, int end_id, float length_penalty, int32_t* steps_out) {
-  LasState* s = las_of(h);
-  if (!s) return h ? h->fail(NASR_ERR_STATE, "nasr_las_beam_search: not a LAS handle") : NASR_ERR_ARG;
+  if (!las_of(h)) return h ? h->fail(NASR_ERR_STATE, "nasr_las_beam_search: not a LAS handle") : NASR_ERR_ARG;
   if (!feats || !seq_len) return h->fail(NASR_ERR_ARG, "nasr_las_beam_search: null input buffer");
-  if (B < 1 || B > 64 || T < 1) return h->fail(NASR_ERR_ARG, "nasr_las_beam_search: B must be in [1,64] and T >= 1");
-  for (int b = 0; b < B; ++b)
-    if (seq_len[b] < 1 || seq_len[b] > T)
-      return h->fail(NASR_ERR_ARG, "nasr_las_beam_search: seq_len[" + std::to_string(b) + "] out of [1,T]");
-  if (beam_width < 1 || beam_width > 1024) return h->fail(NASR_ERR_ARG, "nasr_las_beam_search: beam_width must be in [1,1024]");
-  if (max_steps < 1 || max_steps > 1000) return h->fail(NASR_ERR_ARG, "nasr_las_beam_search: max_steps must be in [1,1000]");
-  if (start_id < 0 || start_id >= h->C || end_id < 0 || end_id >= h->C)
-    return h->fail(NASR_ERR_ARG, "nasr_las_beam_search: start_id and end_id must be in [0, num_classes-1]");
-  if (!(length_penalty >= 0.f) || !std::isfinite(length_penalty))
-    return h->fail(NASR_ERR_ARG, "nasr_las_beam_search: length_penalty must be finite and >= 0");
-  HIPCHK(h, hipSetDevice(h->device));
-  const int rc = las_beam_search(h, feats, B, T, beam_width, max_steps, start_id, end_id, length_penalty);
-  if (rc) return rc;
-  if (steps_out) *steps_out = s->beam->Tdec;
-  return NASR_OK;
+  return las_beam_call(h, "nasr_las_beam_search", feats, seq_len, B, T, beam_width, max_steps, start_id, end_id, length_penalty,
+                       steps_out);
+}
+
+int nasr_las_beam_search_resident(nasr_handle h, int beam_width, int max_steps, int start_id, int end_id, float length_penalty,
+                                  int32_t* steps_out) {
+  if (!las_of(h)) return h ? h->fail(NASR_ERR_STATE, "nasr_las_beam_search_resident: not a LAS handle") : NASR_ERR_ARG;
+  if (!h->resident) return h->fail(NASR_ERR_STATE, "nasr_las_beam_search_resident: no resident batch");
+  return las_beam_call(h, "nasr_las_beam_search_resident", nullptr, h->h_seq.data(), h->B, h->T, beam_width, max_steps, start_id,
+                       end_id, length_penalty, steps_out);
 }
 
 namespace {

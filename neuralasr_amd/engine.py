@@ -647,7 +647,7 @@ class LasEngine(Engine):
         self._ck(self.lib.nasr_upload_batch(self.h, _fp(feats), _ip(seq), _ip(labels), _ip(ll), B, T, U))
 
     def upload_batch_audio(self, featurizer, audios, labels, label_len, rates=None):
-        self._BU = (len(audios), np.asarray(labels).reshape(len(audios), -1).shape[1])
+        self._BU = (len(audios), 0 if labels is None else np.asarray(labels).reshape(len(audios), -1).shape[1])
         return Engine.upload_batch_audio(self, featurizer, audios, labels, label_len, rates)
 
     def las_forward(self, feats, seq_len, labels, label_len, sample=False):
@@ -657,6 +657,13 @@ class LasEngine(Engine):
         out = np.empty((B, U, self.num_classes), np.float32)
         self._ck(self.lib.nasr_las_forward(self.h, _fp(feats), _ip(seq), _ip(labels), _ip(ll), B, T, U, int(bool(sample)),
                                            _fp(out)))
+        return out
+
+    def las_forward_resident(self, sample=False):
+        """las_forward on the batch that is resident already (upload_batch, upload_batch_audio): logits [B, U, C]"""
+        B, U = self._BU
+        out = np.empty((B, U, self.num_classes), np.float32)
+        self._ck(self.lib.nasr_las_forward_resident(self.h, int(bool(sample)), _fp(out)))
         return out
 
     def loss(self, feats, seq_len, labels, label_len):
@@ -706,11 +713,20 @@ class LasEngine(Engine):
         feats, seq, _, _, B, T, _ = self._batch(feats, seq_len)
         if feats.shape[2] != self.cfg.feature_size:
             raise ValueError(f'feature size {feats.shape[2]} != configured {self.cfg.feature_size}')
-        W = int(beam_width)
         steps = c_int32()
-        self._ck(self.lib.nasr_las_beam_search(self.h, _fp(feats), _ip(seq), B, T, W, int(max_steps), int(start_id),
-                                               int(end_id), float(length_penalty), byref(steps)))
-        Td = steps.value
+        self._ck(self.lib.nasr_las_beam_search(self.h, _fp(feats), _ip(seq), B, T, int(beam_width), int(max_steps),
+                                               int(start_id), int(end_id), float(length_penalty), byref(steps)))
+        return self._beam_results(B, int(beam_width), steps.value, trace)
+
+    def beam_search_resident(self, beam_width, max_steps, start_id, end_id, length_penalty=0.5, trace=False):
+        """beam_search over the batch that is resident already (include/nasr.h: nasr_las_beam_search_resident): no feature
+        leaves the host, and the batch stays as it is for the passes that follow."""
+        steps = c_int32()
+        self._ck(self.lib.nasr_las_beam_search_resident(self.h, int(beam_width), int(max_steps), int(start_id),
+                                                        int(end_id), float(length_penalty), byref(steps)))
+        return self._beam_results(self._BU[0], int(beam_width), steps.value, trace)
+
+    def _beam_results(self, B, W, Td, trace):
         out = {'steps': Td, 'predicted_ids': np.empty((B, Td, W), np.int32)}
         self._ck(self.lib.nasr_las_beam_get_ids(self.h, _ip(out['predicted_ids'])))
         if trace:

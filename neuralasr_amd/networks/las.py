@@ -15,12 +15,16 @@ decode() / evaluate() run the reference's inference graph on the GPU (LasEngine.
 with beam_width 1000, maximum_iterations 100 and length_penalty_weight 0.5, starting from start_marker and ending at
 end_marker, then gather_tree; the model is beam 0 of the gathered ids [B, T_dec].  evaluate()'s loss is the reference's
 sequence_loss over the step scores [B, T_dec, W] taken as logits; its graph cannot build unless T_dec == U, so here it is
-NaN then (beam_sequence_loss)."""
+NaN then (beam_sequence_loss).
+
+Every call takes a features.AudioBatch in the place of the padded features (audio_batch, the *_audio calls): a tower's
+shard goes through the GPU front end into the handle's batch slot (LasEngine.upload_batch_audio) and the passes and the
+beam search run on that resident batch, so no feature crosses to the host or back."""
 import numpy as np
 
 from ..engine import LasEngine
-from ..parallel import take_shard
-from .hipnetwork import HipNetwork
+from ..features import AudioBatch
+from .hipnetwork import HipNetwork, take_shard
 
 
 def pyramid_lengths(T, layers=4):
@@ -112,7 +116,6 @@ class LAS(HipNetwork):
     beam_width = 1000
     max_decode_steps = 100
     length_penalty_weight = 0.5
-    takes_audio = False                      # the beam search reads host features (nasr_las_beam_search)
 
     def make_engine(self, config, device, stream):
         e = LasEngine(config.feature_size, self.num_classes, num_hidden=self.num_hidden, num_layers=self.num_layers,
@@ -154,11 +157,11 @@ class LAS(HipNetwork):
         samples), so time-sliced towers and one process per tower feed the same inputs"""
         p, seed, _, _ = self.engine.sampling_state()
         self.engine.set_sampling_state(p, seed, counter, tower)
-        self.engine.upload_batch(f, s, l, ll)
+        self._upload(f, l, s, ll)
         if grads:
             self.engine.compute_grads()
         else:
-            self.engine.las_forward(f, s, l, ll, sample=True)
+            self.engine.las_forward_resident(sample=True)
         loss = self.engine.get_loss()
         ler = label_error_rate(model_ids(self.engine.logits(), ll), l)
         return loss, ler
@@ -205,9 +208,12 @@ class LAS(HipNetwork):
     def stage_batch(self, mfccs, labels, seq_len, labels_len):
         return False
 
-    def audio_batch(self, audios, rates=None):
-        raise NotImplementedError('LAS takes features: its beam search reads them from the host (nasr_las_beam_search), and '
-                                  'its step uploads per tower; LasEngine.upload_batch_audio is the audio path of a LAS handle')
+    def _upload(self, f, l, s, ll):
+        """one tower's shard into the handle's batch slot: audio through the GPU front end, features as they are"""
+        if isinstance(f, AudioBatch):
+            self._upload_audio(f, l, ll)
+        else:
+            self.engine.upload_batch(f, s, l, ll)
 
     def _settle(self):
         pass
@@ -237,8 +243,11 @@ class LAS(HipNetwork):
 
     def _beam_search(self, mfccs, seq_len, trace):
         start, end = self._markers()
-        return self.engine.beam_search(mfccs, seq_len, self.beam_width, self.max_decode_steps, start, end,
-                                       self.length_penalty_weight, trace=trace)
+        args = (self.beam_width, self.max_decode_steps, start, end, self.length_penalty_weight)
+        if isinstance(mfccs, AudioBatch):
+            self._upload_audio(mfccs)             # the front end once; the search reads the resident batch
+            return self.engine.beam_search_resident(*args, trace=trace)
+        return self.engine.beam_search(mfccs, seq_len, *args, trace=trace)
 
     def evaluate(self, mfccs, labels, seq_len, labels_len):
         """[model [B, T_dec], loss, ler]: beam 0 of the gathered ids, beam_sequence_loss of the step scores, and the LER of

@@ -3,7 +3,12 @@ T 400, C 32, beam width 1000, at most 100 steps, length penalty 0.5.  One decode
 gather_tree, ending in a device synchronise) plus the read-back of the gathered ids.  Then one profiled search for its
 device-timed phases: encoder, decoder GEMMs, decoder cell, attention, selection (scores, top-W, update), gather_tree,
 host waits between chunks of steps; the read-back is host-timed.  Prints one JSON line.
-   python tools/lasbeambench.py [--steps 10 --warmup 3]"""
+   python tools/lasbeambench.py [--steps 10 --warmup 3]
+--from-audio times one LAS.evaluate of that batch shape given as audio (one utterance at 16 kHz whose 400 frames give
+T 400) two ways, alternating in one process: the host route (Featurizer.compute, zero-pad, evaluate: the features come to
+the host and go back) and evaluate_audio (the features stay in the handle's batch slot).  Host clock around each call;
+both end in the read-back of the search's results.  Prints one JSON line with both medians and their spreads.
+   python tools/lasbeambench.py --from-audio [--steps 10 --warmup 3]"""
 import argparse
 import ctypes
 import json
@@ -18,6 +23,55 @@ from neuralasr_amd.engine import LasEngine      # noqa: E402
 from neuralasr_amd.networks.las import LAS      # noqa: E402
 
 
+def evaluate_from_audio(a):
+    """one evaluate() per route and repetition, alternating; ms per call"""
+    import tempfile
+    from neuralasr_amd.config import Config
+    sr, numcep, numcontext, C, T = 16000, 40, 10, 32, a.frames
+    syms = ['<padding>', '^', '$'] + [chr(ord('a') + i) for i in range(26)] + ['_', "'", '<blank>']
+    assert len(syms) == C
+    with tempfile.TemporaryDirectory() as d:
+        with open(os.path.join(d, 'symbols'), 'w') as fh:
+            fh.write(''.join('%s %d\n' % (s, i) for i, s in enumerate(syms)))
+        cfg = os.path.join(d, 'las.config')
+        with open(cfg, 'w') as fh:
+            fh.write('[Parameters]\nsamplerate=%d\nnumcep=%d\nnumcontext=%d\nlabel_context=0\nbatch_size=1\nepochs=1\n'
+                     'learningrate=0.0001\nmodel_dir=%s\nstart_step=0\nreport_step=1\nnum_gpus=1\npunc_regex=[^a-z ]\n'
+                     'sym_file=%s\nnetwork=networks.las.LAS\n[Train]\ninput=%s\n[Test]\n'
+                     '[MFCC Featurizer]\nstart_marker=^\nend_marker=$$\n'
+                     % (sr, numcep, numcontext, os.path.join(d, 'model'), os.path.join(d, 'symbols'), os.path.join(d, 'none')))
+        net = Config(cfg, True).load_network(fortraining=True)
+    net.beam_width, net.max_decode_steps = a.width, a.max_steps
+    rs = np.random.RandomState(1)
+    audio = (0.1 * rs.randn(400 + (T - 1) * 160)).astype(np.float32)      # 25 ms frames every 10 ms: T frames
+    labels = rs.randint(3, C - 1, size=(1, 20)).astype(np.int32)
+    f = net.featurizer()
+
+    def host_route():
+        feats = f.compute([audio], rates=[sr])
+        padded = np.zeros((1, max(x.shape[0] for x in feats), f.width), np.float32)
+        padded[0, :feats[0].shape[0]] = feats[0]
+        return net.evaluate(padded, labels, [np.asarray(feats[0].shape[0], np.int32)], [20])
+
+    def audio_route():
+        return net.evaluate_audio([audio], [sr], labels, [20])
+    ms = {'host_route': [], 'evaluate_audio': []}
+    for i in range(a.warmup + a.steps):
+        for name, fn in (('host_route', host_route), ('evaluate_audio', audio_route)):
+            t0 = time.perf_counter()
+            out = fn()
+            if i >= a.warmup:
+                ms[name].append((time.perf_counter() - t0) * 1e3)
+    ids = {name: fn()[0] for name, fn in (('host_route', host_route), ('evaluate_audio', audio_route))}
+    res = {'workload': 'las_evaluate_from_audio', 'B': 1, 'T': T, 'F': f.width, 'C': C, 'W': a.width, 'max_steps': a.max_steps,
+           'T_dec': int(out[0].shape[1]), 'repetitions': a.steps, 'warmup': a.warmup,
+           'same_ids': bool(np.array_equal(ids['host_route'], ids['evaluate_audio']))}
+    for name, v in ms.items():
+        res[name + '_ms'] = {'median': round(float(np.median(v)), 3), 'min': round(min(v), 3), 'max': round(max(v), 3)}
+    print(json.dumps(res))
+    net.engine.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--steps', type=int, default=10)
@@ -25,7 +79,10 @@ def main():
     ap.add_argument('--frames', type=int, default=400)
     ap.add_argument('--width', type=int, default=1000)
     ap.add_argument('--max-steps', type=int, default=100)
+    ap.add_argument('--from-audio', action='store_true', help='time LAS.evaluate through the host route and evaluate_audio')
     a = ap.parse_args()
+    if a.from_audio:
+        return evaluate_from_audio(a)
     F, C, B, T, W, S = 840, 32, 1, a.frames, a.width, a.max_steps
     start_id, end_id = 1, 2
     rs = np.random.RandomState(1)
