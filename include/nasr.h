@@ -154,7 +154,8 @@ int nasr_upload_batch(nasr_handle h, const float* feats, const int32_t* seq_len,
  * un-stacked [B,T,numcep] slice (for features made by preprocess_mfcc.py: columns [numcontext*numcep,
  * (numcontext+1)*numcep) of the stacked array), pad_value[b] the value the stacked array holds in the
  * out-of-utterance context frames of utterance b (its element [b,0,0]).  Needs feature_size ==
- * (2*numcontext+1)*numcep.  Moves 1/(2*numcontext+1) of the bytes over PCIe. */
+ * (2*numcontext+1)*numcep.  Moves 1/(2*numcontext+1) of the bytes over PCIe.  `numcep` here is the width of one
+ * un-stacked frame: nasr_mfcc_width of the features' config (the static columns and their deltas). */
 int nasr_upload_batch_context(nasr_handle h, const float* centre, const float* pad_value, int numcontext, int numcep,
                               const int32_t* seq_len, const int32_t* labels, const int32_t* label_len, int B, int T,
                               int Lmax);
@@ -173,15 +174,15 @@ int nasr_stage_batch_context(nasr_handle h, const float* centre, const float* pa
                              int Lmax, int* ticket);
 /* (utils.py:24-31 feeding dataset.py:33-40) A batch straight from audio: the utterances audio[offsets[b] ..
  * offsets[b+1]) at rates[b] Hz (NULL: all at the featurizer's samplerate) go through `featurizer`'s front end - resampler,
- * MFCC, whole-utterance normalisation - on the device, and its last kernel writes the normalised centre frames
- * [B,T,numcep] (zeros past an utterance's end) and the pad values straight into `model`'s batch slot, in the layout of
+ * features, whole-utterance normalisation - on the device, and its last kernel writes the normalised centre frames
+ * [B,T,D] (D = nasr_mfcc_width of the featurizer's config; zeros past an utterance's end) and the pad values straight into `model`'s batch slot, in the layout of
  * nasr_upload_batch_context: no feature crosses PCIe in either direction.  T = the longest utterance's nasr_mfcc_frames,
  * seq_len_out[b] = utterance b's; both are computed on the host and written before anything is launched.  The slot holds
  * the same bits as nasr_featurize_rates + zero-padding to T + nasr_upload_batch_context give it.  Staging runs copies
  * and kernels on the model's copy stream; a later nasr_featurize* / nasr_resample on the featurizer handle is ordered
  * behind them by an event (no host wait).  One thread at a time per featurizer handle.  nasr_commit_batch,
  * nasr_discard_batch and the two-ahead limit apply.  NASR_ERR_STATE: `featurizer` is not a featurizer handle, `model` is
- * one, or they sit on different devices; NASR_ERR_ARG: feature_size != (2*numcontext+1)*numcep, a bad rate or a
+ * one, or they sit on different devices; NASR_ERR_ARG: feature_size != (2*numcontext+1)*D, a bad rate or a
  * too-short utterance (named), and what nasr_upload_batch refuses, with the computed seq_len. */
 int nasr_upload_batch_audio(nasr_handle model, nasr_handle featurizer, const float* audio, const int64_t* offsets,
                             const int32_t* rates, const int32_t* labels, const int32_t* label_len, int B, int Lmax,
@@ -457,12 +458,21 @@ int nasr_las_beam_get_final(nasr_handle h, float* log_probs_out, int32_t* length
  * gather_tree, and the host's waits between chunks of steps */
 int nasr_las_beam_get_times(nasr_handle h, float* ms_out);
 
-/* ---- the MFCC front end (utils.py:24-31: convert_to_mfcc) --------------------------------------
+/* ---- the feature front end (utils.py:24-31: convert_to_mfcc) ------------------------------------
  * python_speech_features 0.6's mfcc(audio, samplerate, numcep=numcep, nfilt=128) on float32 audio: pre-emphasis in
  * float32 (two roundings), frames of round_half_up(winlen*sr) samples every round_half_up(winstep*sr), zero-padded tail,
  * rectangular window, then in float64 |rfft(frame, nfft)|^2 / nfft (frames longer than nfft truncated), frame energy, the triangular mel
  * filterbank over [0, sr/2], log (exact zeros -> float64 eps), DCT-II (ortho), the lifter, c0 <- log(energy); then
  * include_context (utils.py:8-21) and the whole-utterance (X - mean(X)) / std(X) of utils.py:29, in float64.
+ * kind = 1 stops after the log: psf 0.6's logfbank(audio, samplerate, nfilt=numcep), the log filterbank energies
+ * themselves (no DCT, no lifter, no energy column).
+ * deltas = 1 or 2 appends psf 0.6's delta(feat, N=2) of the static columns, and for 2 also delta(delta(feat, 2), 2):
+ * delta[t] = ((p[t+1] - p[t-1]) + 2 (p[t+2] - p[t-2])) / 10 in float64, p the array edge-replicated by 2 frames inside
+ * its own utterance; the second level replicates the edges of the delta array (it does not look at deltas that the
+ * first level would have beyond the edge).  A frame is then D = numcep * (1 + deltas) wide, [static | delta |
+ * delta-delta], and include_context and the normalisation work on D-wide frames (one mean and one std over the stacked
+ * matrix, zero pads included).  Both restate psf's documented procedure; neither is pinned against the package, nor is
+ * the summation order against numpy.dot's inside psf's delta.
  * nasr_create_featurizer returns an ordinary handle: nasr_last_error, nasr_synchronize and nasr_destroy work on it and
  * every model call returns NASR_ERR_STATE.  Only nfft = 512 (psf 0.6's default) is implemented; 1 <= nfilt <= 128. */
 typedef struct {
@@ -471,16 +481,21 @@ typedef struct {
   double winlen, winstep;                 /* 0.025, 0.01 s */
   float preemph;                          /* 0.97 */
   int32_t ceplifter, append_energy;       /* 22, 1 */
+  int32_t kind;                           /* 0: MFCC; 1: log-mel filterbank, numcep filters: numcep must equal nfilt,
+                                             ceplifter and append_energy are ignored */
+  int32_t deltas;                         /* 0, 1 (+ delta) or 2 (+ delta and delta-delta) */
 } nasr_mfcc_cfg;
 int nasr_create_featurizer(const nasr_mfcc_cfg* cfg, int device_id, void* stream, nasr_handle* out);
 /* Host only (no device needed): the frame count of an utterance of num_samples >= 1 samples (psf framesig: 1 if
  * num_samples <= frame_len, else 1 + ceil((num_samples - frame_len) / frame_step)); < 0 on a bad cfg or length. */
 int64_t nasr_mfcc_frames(const nasr_mfcc_cfg* cfg, int64_t num_samples);
+/* Host only: the width D = numcep * (1 + deltas) of one un-stacked frame; < 0 on a bad cfg. */
+int nasr_mfcc_width(const nasr_mfcc_cfg* cfg);
 /* Host only: the filterbank the kernels use (psf get_filterbanks), bin edges [nfilt+2] and weights [nfilt][nfft/2+1]
  * (float32 copies of the kernels' float64 table); either may be NULL. */
 int nasr_mfcc_filterbank(const nasr_mfcc_cfg* cfg, int32_t* bins, float* weights);
 /* The features of n utterances: utterance i is audio[offsets[i] .. offsets[i+1]) (float32, at least one sample each).
- * out [out_rows][(2*numcontext+1)*numcep] receives the utterances' normalised rows one after another; out_rows must be
+ * out [out_rows][(2*numcontext+1)*D] (D = nasr_mfcc_width) receives the utterances' normalised rows one after another; out_rows must be
  * the sum of their nasr_mfcc_frames.  mean_std (nullable) [n][2]: each utterance's mean and std (ddof 0) over its
  * stacked matrix, zero pads included.  Returns when out is written (utils.py:24-31 for every utterance). */
 int nasr_featurize(nasr_handle h, const float* audio, const int64_t* offsets, int n, float* out, int64_t out_rows,

@@ -38,7 +38,7 @@ SYMBOLS = [
     'nasr_las_get_fed_ids', 'nasr_las_get_sampled', 'nasr_las_beam_search', 'nasr_las_beam_get_ids',
     'nasr_las_beam_get_trace', 'nasr_las_beam_get_final', 'nasr_las_beam_get_times', 'nasr_las_forward_resident',
     'nasr_las_beam_search_resident',
-    'nasr_create_featurizer', 'nasr_mfcc_frames', 'nasr_mfcc_filterbank', 'nasr_featurize', 'nasr_featurize_times',
+    'nasr_create_featurizer', 'nasr_mfcc_frames', 'nasr_mfcc_width', 'nasr_mfcc_filterbank', 'nasr_featurize', 'nasr_featurize_times',
     'nasr_resample_filter', 'nasr_resample_length', 'nasr_resample', 'nasr_featurize_rates',
     'nasr_upload_batch_audio', 'nasr_stage_batch_audio', 'nasr_forward_resident', 'nasr_loss_resident',
     'nasr_greedy_decode_resident',
@@ -69,7 +69,7 @@ class LasCfg(Structure):
 class MfccCfg(Structure):
     _fields_ = [('samplerate', c_int32), ('numcep', c_int32), ('numcontext', c_int32), ('nfilt', c_int32),
                 ('nfft', c_int32), ('winlen', c_double), ('winstep', c_double), ('preemph', c_float),
-                ('ceplifter', c_int32), ('append_energy', c_int32)]
+                ('ceplifter', c_int32), ('append_energy', c_int32), ('kind', c_int32), ('deltas', c_int32)]
 
 
 class PhaseTimes(Structure):
@@ -201,6 +201,7 @@ def load():
         'nasr_las_beam_get_times': (c_int, [H, fp]),
         'nasr_create_featurizer': (c_int, [POINTER(MfccCfg), c_int, c_void_p, POINTER(H)]),
         'nasr_mfcc_frames': (c_int64, [POINTER(MfccCfg), c_int64]),
+        'nasr_mfcc_width': (c_int, [POINTER(MfccCfg)]),
         'nasr_mfcc_filterbank': (c_int, [POINTER(MfccCfg), ip, fp]),
         'nasr_featurize': (c_int, [H, fp, POINTER(c_int64), c_int, fp, c_int64, POINTER(c_double)]),
         'nasr_featurize_times': (c_int, [H, fp, fp, fp]),

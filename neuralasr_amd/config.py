@@ -1,7 +1,9 @@
 """Run configuration (reference: config.py:11-113): the same INI files (ExtendedInterpolation,
 sections Parameters / Train / Test / MFCC Featurizer), the same derived fields
 (feature_size = (2*numcontext+1)*numcep, batch_size multiplied by num_gpus) and the same dotted-name
-network loader.  `network=networks.bilstm_ctc_net.BiLstmCTCNet` resolves to the HIP implementation in
+network loader.  Two optional [Parameters] keys choose the features the GPU front end makes: features=mfcc|logfbank
+(default mfcc) and deltas=0|1|2 (default 0); a frame is frame_width = numcep*(1+deltas) wide and feature_size is
+(2*numcontext+1)*frame_width.  `network=networks.bilstm_ctc_net.BiLstmCTCNet` resolves to the HIP implementation in
 neuralasr_amd.networks when the reference's TensorFlow package of that name is not importable."""
 import importlib
 from configparser import ConfigParser, ExtendedInterpolation
@@ -48,7 +50,15 @@ class Config(object):
         self.punc_regex = par['punc_regex']
         self.network = par['network']
         self.sym_file = par['sym_file'] if 'sym_file' in par else None
-        self.feature_size = (2 * self.numcontext + 1) * self.numcep
+        self.features = par['features'].strip() if 'features' in par else 'mfcc'
+        if self.features not in ('mfcc', 'logfbank'):
+            raise ValueError("'features' must be mfcc or logfbank, not %r, in %s" % (self.features, configfile))
+        deltas = par['deltas'].strip() if 'deltas' in par else '0'
+        if deltas not in ('0', '1', '2'):
+            raise ValueError("'deltas' must be 0, 1 or 2, not %r, in %s" % (deltas, configfile))
+        self.deltas = int(deltas)
+        self.frame_width = self.numcep * (1 + self.deltas)
+        self.feature_size = (2 * self.numcontext + 1) * self.frame_width
         # the configured batch is per GPU (reference: config.py:35-36)
         self.batch_size *= self.num_gpus if self.num_gpus > 0 else 1
         self.symbols = Symbols(self.label_context, self.sym_file) if isTraining else Symbols(self.label_context)
@@ -67,7 +77,7 @@ class Config(object):
         return network_class(self.network)(self, fortraining=fortraining)
 
     def print_config(self):
-        names = ['samplerate', 'numcep', 'numcontext', 'rand_shift', 'batch_size', 'epochs', 'learningrate',
+        names = ['samplerate', 'numcep', 'numcontext', 'features', 'deltas', 'rand_shift', 'batch_size', 'epochs', 'learningrate',
                  'model_dir', 'start_step', 'report_step', 'num_gpus', 'label_context', 'punc_regex', 'network',
                  'sym_file', 'train_input', 'test_input', 'mfcc_input', 'mfcc_output', 'start_marker', 'end_marker']
         lines = ['']

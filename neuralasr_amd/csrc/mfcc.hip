@@ -1,15 +1,21 @@
-// mfcc.hip — the MFCC front end (reference utils.py:24-31, convert_to_mfcc): python_speech_features 0.6's
-// mfcc(nfilt=128) on float32 audio, include_context and the whole-utterance normalisation, for a batch of utterances.
+// mfcc.hip — the feature front end (reference utils.py:24-31, convert_to_mfcc): python_speech_features 0.6's
+// mfcc(nfilt=128) on float32 audio, include_context and the whole-utterance normalisation, for a batch of utterances;
+// or psf's logfbank in the place of mfcc (cfg.kind = 1), and psf's delta(feat, 2) columns appended (cfg.deltas).
 //   mfcc_spectral_kernel  one wave per frame, every frame of the batch in one launch: pre-emphasis (float32, as the
 //                         reference), then in float64 the 512-point real FFT (a 256-point complex FFT over the packed
 //                         even / odd samples, radix-4 Stockham in LDS), power, energy, the sparse triangular filterbank,
-//                         log, DCT-II with the lifter folded in, c0 <- log(energy).  float64 so that narrow filters over
-//                         near-zero bins keep their precision (at 8 kHz filter 0 is the DC bin alone)
+//                         log, DCT-II with the lifter folded in, c0 <- log(energy); kind 1 writes the log filterbank
+//                         energies themselves.  float64 so that narrow filters over near-zero bins keep their precision
+//                         (at 8 kHz filter 0 is the DC bin alone).  Rows of the cep buffer are D =
+//                         numcep (1 + deltas) wide, [static | delta | delta-delta]; this kernel writes the static part
+//   mfcc_delta_kernel     one thread per (frame, static column) of the batch: one level of psf's delta(feat, 2) from
+//                         one block of columns into the next, clamped to the frame's own utterance; launched once per
+//                         level, so the delta-delta reads deltas that an earlier launch finished
 //   mfcc_norm_kernel      one workgroup per utterance: the float64 mean and std of the stacked matrix from the centre
 //                         frames (each counted once per window that holds it, the zero pads as a count), then the
 //                         normalised rows written straight into the stacked layout
 //   mfcc_norm_slot_kernel the same statistics, written as a model handle's batch slot takes them (nasr_batch.hip):
-//                         the normalised centre frames [B][T][numcep] of a whole batch, zeros past each utterance's
+//                         the normalised centre frames [B][T][D] of a whole batch, zeros past each utterance's
 //                         end, and one pad value (0 - mean) / std per utterance; nasr_upload_batch_audio
 // Tables (twiddles, filter weights, the DCT x lifter matrix) are built once per handle on the host in double.
 // nasr_featurize_rates first resamples utterances at other rates to the config rate (resample.hip) into a device
@@ -33,6 +39,7 @@ struct FzDims {
   int frame_len, frame_step, numcep, nfilt, nc;
   int append_energy;
   float preemph;
+  int kind, width;                      // cfg.kind; D = numcep (1 + deltas), the row stride of the cep buffer
 };
 
 // ---------------------------------------------------------------------------------------------------------- kernels
@@ -148,20 +155,46 @@ __global__ __launch_bounds__(64 * SPEC_WAVES) void mfcc_spectral_kernel(
   }
   __syncthreads();
 
-  // DCT-II (ortho) x lifter; c0 <- log(energy)
+  // DCT-II (ortho) x lifter; c0 <- log(energy).  kind 1 (numcep == nfilt): the log filterbank energies as they are
   if (valid) {
-    const double lg_en = log(en == 0.0 ? F64_EPS : en);
-    for (int c = lane; c < d.numcep; c += 64) {
-      double acc = 0.0;
-      for (int j = 0; j < d.nfilt; ++j) acc += dct[j * d.numcep + c] * logmel[wv][j];
-      cep[f * d.numcep + c] = (c == 0 && d.append_energy) ? lg_en : acc;
+    double* row = cep + f * d.width;
+    if (d.kind == 1) {
+      for (int j = lane; j < d.numcep; j += 64) row[j] = logmel[wv][j];
+    } else {
+      const double lg_en = log(en == 0.0 ? F64_EPS : en);
+      for (int c = lane; c < d.numcep; c += 64) {
+        double acc = 0.0;
+        for (int j = 0; j < d.nfilt; ++j) acc += dct[j * d.numcep + c] * logmel[wv][j];
+        row[c] = (c == 0 && d.append_energy) ? lg_en : acc;
+      }
     }
   }
+}
+
+// One level of psf 0.6's delta(feat, N=2) over the packed frames [F][width] of the batch: columns [src, src + numcep)
+// of every frame give columns [dst, dst + numcep).  p is the source edge-replicated inside the frame's own utterance
+// (t clamped to [foff[u], foff[u+1])), and the sum is taken in this order:
+//   delta[t] = ((p[t+1] - p[t-1]) + 2 (p[t+2] - p[t-2])) / 10
+// Consecutive threads take consecutive columns of a frame.  A launch reads only columns that an earlier launch wrote:
+// the delta-delta is a second launch with src = the delta columns, so its edges replicate the DELTA array.
+__global__ __launch_bounds__(NORM_THREADS) void mfcc_delta_kernel(double* cep, const int64_t* __restrict__ foff,
+                                                                  const int* __restrict__ fmap, int64_t nframes, int numcep,
+                                                                  int width, int src, int dst) {
+  const int64_t e = (int64_t)blockIdx.x * NORM_THREADS + threadIdx.x;
+  if (e >= nframes * numcep) return;
+  const int64_t f = e / numcep;
+  const int c = (int)(e - f * numcep);
+  const int u = fmap[f];
+  const int64_t lo = foff[u], hi = foff[u + 1] - 1;
+  auto p = [&](int64_t t) { return cep[(t < lo ? lo : t > hi ? hi : t) * width + src + c]; };
+  const double d1 = p(f + 1) - p(f - 1), d2 = p(f + 2) - p(f - 2);
+  cep[f * width + dst + c] = (d1 + 2.0 * d2) / 10.0;
 }
 
 // One workgroup per utterance of T frames: the stacked matrix [T][W*C] (W = 2 nc + 1) holds centre frame t in
 // cnt_t = min(t,nc) + min(T-1-t,nc) + 1 windows, zeros elsewhere.  Two float64 passes (numpy's mean, then the mean
 // squared deviation), fixed-order sums.  Every thread of the workgroup calls it and gets the same (mean, std).
+// `numcep`, here and in the two kernels below, is the width of a frame of the cep buffer: D = numcep (1 + deltas).
 __device__ __forceinline__ void utt_mean_std(const double* __restrict__ src, int64_t T, int numcep, int nc, double* red,
                                              double* mean_out, double* sd_out) {
   const int tid = threadIdx.x;
@@ -252,9 +285,13 @@ bool cfg_ok(const nasr_mfcc_cfg* c, std::string* why) {
   if (c->nfft != 2 * FFT_N) return *why = "only nfft = 512 (python_speech_features 0.6's default) is implemented", false;
   if (c->nfilt < 1 || c->nfilt > MAX_FILT) return *why = "nfilt must be in [1,128]", false;
   if (c->numcep < 1 || c->numcep > c->nfilt) return *why = "numcep must be in [1,nfilt]", false;
+  if (c->kind != 0 && c->kind != 1) return *why = "kind must be 0 (MFCC) or 1 (log-mel filterbank)", false;
+  if (c->deltas < 0 || c->deltas > 2) return *why = "deltas must be 0, 1 or 2", false;
+  if (c->kind == 1 && c->numcep != c->nfilt)
+    return *why = "kind 1 (log-mel filterbank): numcep is the number of filters and must equal nfilt", false;
   if (c->numcontext < 0) return *why = "numcontext must be >= 0", false;
   if (!(c->winlen > 0.0) || !(c->winstep > 0.0)) return *why = "winlen and winstep must be > 0", false;
-  if (c->ceplifter < 0) return *why = "ceplifter must be >= 0", false;
+  if (c->kind == 0 && c->ceplifter < 0) return *why = "ceplifter must be >= 0", false;
   return true;
 }
 
@@ -415,8 +452,8 @@ int fz_plan(nasr_ctx* eh, FzState& z, const std::string& fn, const int64_t* offs
 
 size_t fz_stage_bytes(const FzPlan& p) { return ((size_t)p.S_in * 4 + 7) / 8 * 8 + p.meta_bytes + p.rmeta_bytes; }
 
-// The copies, the resampler and mfcc_spectral_kernel of plan p on stream st: z.cep holds the cepstra afterwards, z.meta
-// the offsets.  audio: the first utterance's first sample.  pinned (nullable): fz_stage_bytes of pinned memory the
+// The copies, the resampler, mfcc_spectral_kernel and the delta launches of plan p on stream st: z.cep holds the frames
+// [F][D] afterwards, z.meta the offsets.  audio: the first utterance's first sample.  pinned (nullable): fz_stage_bytes of pinned memory the
 // host-to-device copies go through, so that they are plain DMAs that return at once.
 int fz_front(nasr_ctx* eh, FzState& z, const std::string& fn, const FzPlan& p, const float* audio, void* pinned, hipStream_t st) {
   const int n = p.n;
@@ -432,7 +469,7 @@ int fz_front(nasr_ctx* eh, FzState& z, const std::string& fn, const FzPlan& p, c
     if (int rc = resample_prepare(eh, z, p.rp, p.S_in)) return rc;
   }
   if (!scratch_ensure(z, z.audio, (size_t)p.S_in * 4) || !scratch_ensure(z, z.meta, z.hmeta.size()) ||
-      !scratch_ensure(z, z.cep, (size_t)F * z.d.numcep * 8) || !scratch_ensure(z, z.mstd, (size_t)n * 16))
+      !scratch_ensure(z, z.cep, (size_t)F * z.d.width * 8) || !scratch_ensure(z, z.mstd, (size_t)n * 16))
     return eh->fail(NASR_ERR_HIP, fn + ": device buffers for " + std::to_string(p.uoff[n]) + " samples could not be allocated");
   const void *src_audio = audio, *src_meta = z.hmeta.data(), *src_rmeta = p.rs ? z.hrmeta.data() : nullptr;
   if (pinned) {
@@ -459,6 +496,13 @@ int fz_front(nasr_ctx* eh, FzState& z, const std::string& fn, const FzPlan& p, c
       reinterpret_cast<const int*>(z.meta.as<char>() + 2 * p.mb), F, z.tw, z.tw2, z.fb_lo, z.fb_n, z.fb_off, z.fb_w, z.dct,
       z.d, z.cep.as<double>());
   HIPCHK(eh, hipGetLastError());
+  const int64_t dblk = (F * z.d.numcep + NORM_THREADS - 1) / NORM_THREADS;
+  for (int lv = 1; lv <= z.cfg.deltas; ++lv) {
+    mfcc_delta_kernel<<<dim3((unsigned)dblk), dim3(NORM_THREADS), 0, st>>>(
+        z.cep.as<double>(), z.meta.as<int64_t>() + (n + 1), reinterpret_cast<const int*>(z.meta.as<char>() + 2 * p.mb), F,
+        z.d.numcep, z.d.width, (lv - 1) * z.d.numcep, lv * z.d.numcep);
+    HIPCHK(eh, hipGetLastError());
+  }
   return NASR_OK;
 }
 
@@ -471,7 +515,7 @@ int fz_produce_slot(nasr_ctx* eh, nasr_ctx* fzh, const FzPlan& p, const float* a
   int rc = fz_front(eh, z, fn, p, audio, pinned, st);
   if (!rc) {
     mfcc_norm_slot_kernel<<<dim3(p.n), dim3(NORM_THREADS), 0, st>>>(z.cep.as<double>(), z.meta.as<int64_t>() + (p.n + 1),
-                                                                    z.d.numcep, z.d.nc, Tb, dcentre, dpad);
+                                                                    z.d.width, z.d.nc, Tb, dcentre, dpad);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) rc = eh->fail(NASR_ERR_HIP, fn + ": " + hipGetErrorString(e));
   }
@@ -482,11 +526,11 @@ int fz_produce_slot(nasr_ctx* eh, nasr_ctx* fzh, const FzPlan& p, const float* a
   return rc;
 }
 
-int fz_feature_width(const nasr_ctx* fzh, int* numcontext, int* numcep) {
+int fz_feature_width(const nasr_ctx* fzh, int* numcontext, int* frame_width) {
   const FzState& z = *fzh->fz;
   *numcontext = z.d.nc;
-  *numcep = z.d.numcep;
-  return z.W * z.d.numcep;
+  *frame_width = z.d.width;
+  return z.W * z.d.width;
 }
 
 }  // namespace nasr_impl
@@ -508,13 +552,13 @@ int featurize(nasr_handle h, const std::string& fn, const float* audio, const in
   if (out_rows != F)
     return h->fail(NASR_ERR_ARG, fn + ": out_rows is " + std::to_string(out_rows) + ", the utterances have " +
                                      std::to_string(F) + " frames");
-  const size_t rowlen = (size_t)z.W * z.d.numcep;
+  const size_t rowlen = (size_t)z.W * z.d.width;
   HIPCHK(h, hipSetDevice(h->device));
   if (int rc = scratch_acquire(h, z, h->st)) return rc;
   if (!z.out.ensure((size_t)F * rowlen * 4, nullptr))
     return h->fail(NASR_ERR_HIP, fn + ": device buffers for " + std::to_string(p.uoff[n]) + " samples could not be allocated");
   if (int rc = fz_front(h, z, fn, p, audio + offsets[0], nullptr, h->st)) return rc;
-  mfcc_norm_kernel<<<dim3(n), dim3(NORM_THREADS), 0, h->st>>>(z.cep.as<double>(), z.meta.as<int64_t>() + (n + 1), z.d.numcep,
+  mfcc_norm_kernel<<<dim3(n), dim3(NORM_THREADS), 0, h->st>>>(z.cep.as<double>(), z.meta.as<int64_t>() + (n + 1), z.d.width,
                                                              z.d.nc, z.out.as<float>(), z.mstd.as<double>());
   HIPCHK(h, hipGetLastError());
   HIPCHK(h, hipEventRecord(z.ev[2], h->st));
@@ -533,6 +577,12 @@ int64_t nasr_mfcc_frames(const nasr_mfcc_cfg* cfg, int64_t num_samples) {
   if (!cfg_ok(cfg, &why) || num_samples < 1) return NASR_ERR_ARG;
   return frames_of(round_half_up(cfg->winlen * cfg->samplerate), std::max<int64_t>(1, round_half_up(cfg->winstep * cfg->samplerate)),
                    num_samples);
+}
+
+int nasr_mfcc_width(const nasr_mfcc_cfg* cfg) {
+  std::string why;
+  if (!cfg_ok(cfg, &why)) return NASR_ERR_ARG;
+  return cfg->numcep * (1 + cfg->deltas);
 }
 
 int nasr_mfcc_filterbank(const nasr_mfcc_cfg* cfg, int32_t* bins, float* weights) {
@@ -570,7 +620,8 @@ int nasr_create_featurizer(const nasr_mfcc_cfg* cfg, int device_id, void* stream
   h->fz.reset(new FzState());
   FzState& z = *h->fz;
   z.cfg = *cfg;
-  z.d = FzDims{(int)flen, (int)fstep, cfg->numcep, cfg->nfilt, cfg->numcontext, cfg->append_energy ? 1 : 0, cfg->preemph};
+  z.d = FzDims{(int)flen, (int)fstep, cfg->numcep, cfg->nfilt, cfg->numcontext, cfg->append_energy ? 1 : 0, cfg->preemph,
+                 cfg->kind, cfg->numcep * (1 + cfg->deltas)};
   z.W = 2 * cfg->numcontext + 1;
   for (Event& e : z.ev)
     if (hipEventCreate(e.out()) != hipSuccess) return create_fail(h, NASR_ERR_HIP, "hipEventCreate failed");

@@ -425,9 +425,9 @@ static int audio_batch(nasr_ctx* h, nasr_ctx* fzh, const std::string& fn, const 
                                        std::to_string(fzh->device));
   if (!audio || !offsets || !seq_len_out || !T_out) return h->fail(NASR_ERR_ARG, fn + ": null buffer");
   if (B < 1 || B > 64) return validate_batch(h, nullptr, nullptr, nullptr, B, 1, 0);
-  int ctx = 0, ncep = 0;
+  int ctx = 0, ncep = 0;                 // ncep: the featurizer's frame width, numcep*(1+deltas)
   if (fz_feature_width(fzh, &ctx, &ncep) != h->F)
-    return h->fail(NASR_ERR_ARG, fn + ": feature_size " + std::to_string(h->F) + " must equal (2*numcontext+1)*numcep = (2*" +
+    return h->fail(NASR_ERR_ARG, fn + ": feature_size " + std::to_string(h->F) + " must equal (2*numcontext+1)*numcep*(1+deltas) = (2*" +
                                      std::to_string(ctx) + "+1)*" + std::to_string(ncep) + " of the featurizer");
   FzPlan plan;
   if (int rc = fz_plan(h, *fzh->fz, fn, offsets, rates, B, &plan)) return rc;

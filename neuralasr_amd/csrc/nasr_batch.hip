@@ -179,7 +179,8 @@ void slot_set_state(nasr_ctx* h, BatchSlot* s, int st) {
 // Copies one batch into slot s: the integer arrays through the slot's pinned meta buffer, the features from the caller's
 // memory (`pinned_feats` false: hipMemcpyAsync from pageable memory, which returns when the source may be reused) or
 // through the slot's pinned feature buffer (true: the H2D is a plain DMA that overlaps whatever the compute stream runs).
-// The centre form (centre frames [B][T][ncep] + one pad value per utterance) comes from host memory (`centre`,
+// The centre form (centre frames [B][T][ncep], ncep the width of one un-stacked frame: numcep*(1+deltas) of the features'
+// config, + one pad value per utterance) comes from host memory (`centre`,
 // `pad_value`) or from a device producer, whose kernels write it into the slot on stream cs: that is the only difference
 // between the two, the meta block and everything slot_commit does are the same.
 // All device copies (and a producer's kernels) go to stream cs and end with the slot's ev_copy.

@@ -529,7 +529,7 @@ int fz_plan(nasr_ctx* eh, FzState& z, const std::string& fn, const int64_t* offs
 size_t fz_stage_bytes(const FzPlan& p);
 int fz_produce_slot(nasr_ctx* eh, nasr_ctx* fzh, const FzPlan& p, const float* audio, int Tb, float* dcentre, float* dpad,
                     void* pinned, hipStream_t st);
-int fz_feature_width(const nasr_ctx* fzh, int* numcontext, int* numcep);   // (2*numcontext+1)*numcep
+int fz_feature_width(const nasr_ctx* fzh, int* numcontext, int* frame_width);   // (2*numcontext+1)*frame_width
 
 inline float* dout_of(nasr_ctx* h, int) { return h->dout.as<float>(); }
 inline float* dg_of(nasr_ctx* h, int) { return h->dgbuf.as<float>(); }

@@ -35,7 +35,8 @@ def main(argv=None):
         from .features import read_wav_native
         audio, rate = read_wav_native(args.input)
         return report(config, network.decode_audio([audio], [rate]))
-    mfcc = compute_mfcc_and_read_transcription(args.input, config.samplerate, config.numcontext, config.numcep)
+    mfcc = compute_mfcc_and_read_transcription(args.input, config.samplerate, config.numcontext, config.numcep,
+                                               kind=config.features, deltas=config.deltas)
     mfcc = np.expand_dims(mfcc, axis=0)
     seq_len = np.asarray(mfcc.shape[1], dtype=np.int32)
     return decode(config, mfcc, [seq_len], network)

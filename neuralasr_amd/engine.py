@@ -179,7 +179,8 @@ class Engine:
         per utterance produce, so that the centre slice + the pad value determine it.  The first / last numcontext frames
         of EVERY utterance are checked exactly: that is where an array that went through rand_shift's roll-and-crop
         (dataset.py:23-31) differs (real neighbours instead of the pad value, and a pad read from a real sample); the
-        interior is spot-checked."""
+        interior is spot-checked.  `numcep` is the width of one un-stacked frame: config.frame_width, the static columns
+        and their deltas."""
         B = feats.shape[0]
         w = 2 * numcontext + 1
         if numcontext < 1 or feats.shape[2] != w * numcep:

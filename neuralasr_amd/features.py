@@ -1,4 +1,4 @@
-"""The MFCC front end (reference: utils.py:24-31, convert_to_mfcc): WAV reading and the GPU featurizer.
+"""The feature front end (reference: utils.py:24-31, convert_to_mfcc): WAV reading and the GPU featurizer.
 
 read_wav returns what librosa.load(path, sr, mono=True) returns for a file already at `sr`: float32 samples scaled the
 way libsndfile scales them, channels averaged in float32; a file at another rate is an error there.  read_wav_native
@@ -7,7 +7,9 @@ returns the same samples and the file's own rate, and Featurizer resamples them 
 interpolation, then fix_length to ceil(n * sr / rate) samples.
 Featurizer runs python_speech_features 0.6's mfcc(nfilt=128), include_context and the whole-utterance normalisation on
 the GPU (neuralasr_amd/csrc/mfcc.hip), a batch of utterances per call; with `rates`, utterances at another rate are
-resampled first and the resampled samples stay on the device."""
+resampled first and the resampled samples stay on the device.  kind='logfbank' makes psf's logfbank (numcep log-mel
+filterbank energies) in the place of the MFCC, and deltas=1|2 appends psf's delta(feat, 2) columns (and their deltas)
+to every frame before the context stacking and the normalisation."""
 import ctypes
 import struct
 
@@ -159,9 +161,17 @@ def resample_filter():
     return t
 
 
-def _cfg(samplerate, numcep, numcontext, nfilt, nfft):
+KINDS = {'mfcc': 0, 'logfbank': 1}
+
+
+def _cfg(samplerate, numcep, numcontext, nfilt, nfft, kind='mfcc', deltas=0):
+    if kind not in KINDS:
+        raise ValueError("kind must be 'mfcc' or 'logfbank', not %r" % (kind,))
+    if kind == 'logfbank':
+        nfilt = numcep                                     # psf logfbank(nfilt=numcep): one column per filter
     return _lib.MfccCfg(samplerate=samplerate, numcep=numcep, numcontext=numcontext, nfilt=nfilt, nfft=nfft,
-                        winlen=0.025, winstep=0.01, preemph=0.97, ceplifter=22, append_energy=1)
+                        winlen=0.025, winstep=0.01, preemph=0.97, ceplifter=22, append_energy=1,
+                        kind=KINDS[kind], deltas=int(deltas))
 
 
 def num_frames(num_samples, samplerate, numcep=13, nfilt=128, nfft=512):
@@ -223,14 +233,21 @@ class AudioBatch:
 class Featurizer:
     """The normalised MFCC features of utils.convert_to_mfcc for a list of float32 utterances, on the GPU.  compute()
     packs consecutive utterances into calls of at most `max_samples` samples, native and resampled ones counted (a
-    longer utterance goes alone)."""
+    longer utterance goes alone).  kind='logfbank': numcep log-mel filterbank energies per frame (nfilt = numcep);
+    deltas=1|2: every frame is [static | delta | delta-delta], frame_width = numcep*(1+deltas) wide.  `width` is the
+    width of a row that compute() returns: (2*numcontext+1)*frame_width."""
 
-    def __init__(self, samplerate, numcep, numcontext, nfilt=128, nfft=512, device_id=0, max_samples=1 << 23):
+    def __init__(self, samplerate, numcep, numcontext, nfilt=128, nfft=512, device_id=0, max_samples=1 << 23,
+                 kind='mfcc', deltas=0):
         self.lib = _lib.load()
         self.samplerate, self.numcep, self.numcontext = int(samplerate), int(numcep), int(numcontext)
-        self.width = (2 * self.numcontext + 1) * self.numcep
+        self.kind, self.deltas = kind, int(deltas)
         self.max_samples = int(max_samples)
-        self.cfg = _cfg(self.samplerate, self.numcep, self.numcontext, nfilt, nfft)
+        self.cfg = _cfg(self.samplerate, self.numcep, self.numcontext, nfilt, nfft, kind, self.deltas)
+        self.frame_width = self.lib.nasr_mfcc_width(ctypes.byref(self.cfg))
+        if self.frame_width < 0:                           # nasr_create_featurizer names what is wrong with the cfg
+            self.frame_width = self.numcep * (1 + self.deltas)
+        self.width = (2 * self.numcontext + 1) * self.frame_width
         h = ctypes.c_void_p()
         rc = self.lib.nasr_create_featurizer(ctypes.byref(self.cfg), device_id, None, ctypes.byref(h))
         _lib.check(self.lib, None, rc)
@@ -243,7 +260,7 @@ class Featurizer:
         return int(n)
 
     def compute(self, audios, return_stats=False, *, rates=None):
-        """list of float32 [n_i] -> list of float32 [T_i, (2*numcontext+1)*numcep] (and [(mean, std)] if asked).
+        """list of float32 [n_i] -> list of float32 [T_i, self.width] (and [(mean, std)] if asked).
         rates: each utterance's sample rate; one at another rate than `samplerate` is resampled first (librosa.load)."""
         audios = self._utterances(audios)
         sizes = self._sizes(audios, rates)

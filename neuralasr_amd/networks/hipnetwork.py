@@ -211,13 +211,19 @@ class HipNetwork(Network):
             self.logger.warning('persistent recurrence aborted in a forward-only call: repeating it on the per-step kernels')
             return fn()
 
+    def _frame_width(self):
+        """the width of one un-stacked frame of the pickled features: numcep*(1+deltas); 0 without a numcep"""
+        numcep = getattr(self.config, 'numcep', 0)
+        return getattr(self.config, 'frame_width', numcep)
+
     # ------------------------------------------------------------------ batches given as audio
     def featurizer(self):
-        """The MFCC front end of the *_audio calls: on this network's device, shaped by the config."""
+        """The feature front end of the *_audio calls: on this network's device, shaped by the config."""
         if self._featurizer is None:
             from ..features import Featurizer
             self._featurizer = Featurizer(self.config.samplerate, self.config.numcep, self.config.numcontext,
-                                          device_id=self._device)
+                                          device_id=self._device, kind=getattr(self.config, 'features', 'mfcc'),
+                                          deltas=getattr(self.config, 'deltas', 0))
         return self._featurizer
 
     def audio_batch(self, audios, rates=None):
@@ -243,7 +249,7 @@ class HipNetwork(Network):
         if isinstance(f, AudioBatch):
             self._upload_audio(f, l, ll)
         elif not (self._use_device_context() and
-                  self.engine.upload_batch_context(f, s, l, ll, self.config.numcontext, self.config.numcep)):
+                  self.engine.upload_batch_context(f, s, l, ll, self.config.numcontext, self._frame_width())):
             self.engine.upload_batch(f, s, l, ll)
 
     def _decode(self, mfccs, seq_len, which):
@@ -446,7 +452,7 @@ class HipNetwork(Network):
             ticket = self.engine.stage_batch_audio(self.featurizer(), f.audios, l, ll, f.rates)[2]
         else:
             ctx = self.config.numcontext if self._use_device_context() else 0
-            ticket = self.engine.stage_batch(f, s, l, ll, ctx, getattr(self.config, 'numcep', 0))
+            ticket = self.engine.stage_batch(f, s, l, ll, ctx, self._frame_width())
         if ticket is None:
             return False
         with self._staged_lock:

@@ -78,7 +78,7 @@ def gpu_featurize(config):
     """paths -> features, the WAVs read on a few host threads and featurised on the GPU in one call (files at another
     rate than the config's resampled to it there)."""
     from .features import read_wav_native
-    fz = featurizer(config.samplerate, config.numcontext, config.numcep)
+    fz = featurizer(config.samplerate, config.numcontext, config.numcep, config.features, config.deltas)
 
     def run(paths):
         with ThreadPoolExecutor(max_workers=READ_THREADS) as ex:

@@ -48,26 +48,28 @@ def read_label_text(txtfile, punc_regex):
 _featurizers = {}
 
 
-def featurizer(sr, numcontext, numcep):
-    """One GPU featurizer per (sr, numcontext, numcep) for the process."""
-    key = (int(sr), int(numcontext), int(numcep))
+def featurizer(sr, numcontext, numcep, kind='mfcc', deltas=0):
+    """One GPU featurizer per (sr, numcontext, numcep, kind, deltas) for the process."""
+    key = (int(sr), int(numcontext), int(numcep), kind, int(deltas))
     if key not in _featurizers:
         from .features import Featurizer
-        _featurizers[key] = Featurizer(sr, numcep, numcontext)
+        _featurizers[key] = Featurizer(sr, numcep, numcontext, kind=kind, deltas=deltas)
     return _featurizers[key]
 
 
-def convert_to_mfcc(wavfile, sr, numcontext, numcep):
-    """float32 [T, (2*numcontext+1)*numcep] normalised MFCC features of a WAV file (reference: utils.py:24-31); a file
-    at another rate than sr is resampled to it on the GPU, as librosa.load(wavfile, mono=True, sr=sr) does."""
+def convert_to_mfcc(wavfile, sr, numcontext, numcep, kind='mfcc', deltas=0):
+    """float32 [T, (2*numcontext+1)*numcep*(1+deltas)] normalised features of a WAV file (reference: utils.py:24-31; MFCC,
+    or the log-mel filterbank for kind='logfbank', with `deltas` levels of delta columns); a file at another rate than
+    sr is resampled to it on the GPU, as librosa.load(wavfile, mono=True, sr=sr) does."""
     from .features import read_wav_native
     audio, rate = read_wav_native(wavfile)
-    return featurizer(sr, numcontext, numcep).compute([audio], rates=[rate])[0]
+    return featurizer(sr, numcontext, numcep, kind, deltas).compute([audio], rates=[rate])[0]
 
 
-def compute_mfcc_and_read_transcription(wavfile, sr, numcontext, numcep, punc_regex=None, txtfile=None):
+def compute_mfcc_and_read_transcription(wavfile, sr, numcontext, numcep, punc_regex=None, txtfile=None, kind='mfcc',
+                                        deltas=0):
     """(reference: utils.py:61-68) the features, and the cleaned transcription when txtfile is given."""
-    audio_mfcc = convert_to_mfcc(wavfile, sr, numcontext, numcep)
+    audio_mfcc = convert_to_mfcc(wavfile, sr, numcontext, numcep, kind, deltas)
     if txtfile:
         return audio_mfcc, read_label_text(txtfile, punc_regex)
     return audio_mfcc

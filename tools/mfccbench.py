@@ -2,6 +2,8 @@
 16000sr_26mfcc config: numcep 26, numcontext 10) through nasr_featurize, split into host-to-device copies, kernels and
 device-to-host copies (device events), and through the fp64 NumPy restatement of tests/mfcc_ref.py on the same batch.
 Prints one JSON line.   python tools/mfccbench.py [--utts 64 --seconds 10 --sr 16000 --numcep 26 --numcontext 10]
+With --features logfbank and --deltas 1|2 the batch goes through the log-mel filterbank and the delta kernels instead
+(the restatement is then tests/feat_ref.py); the line carries "features", "deltas" and "frame_width".
 With --native-sr R the utterances are made at R Hz and resampled to --sr on the GPU first (nasr_featurize_rates); the
 line then also carries a "resample" field: nasr_resample's phases alone, and the fp64 restatement of
 tests/resample_ref.py timed on a few utterances and scaled to the batch.
@@ -20,7 +22,7 @@ import numpy as np
 ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), '..')
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, 'tests'))
-import mfcc_ref as R                                # noqa: E402
+import feat_ref as FR                               # noqa: E402
 import resample_ref as RR                           # noqa: E402
 from neuralasr_amd.features import Featurizer       # noqa: E402
 
@@ -49,7 +51,7 @@ def batch_routes(a, fz, audios, rates):
         for b, f in enumerate(feats):
             x[b, :f.shape[0]] = f
         seq = [f.shape[0] for f in feats]
-        if not e.upload_batch_context(x, seq, labels, ll, fz.numcontext, fz.numcep):
+        if not e.upload_batch_context(x, seq, labels, ll, fz.numcontext, fz.frame_width):
             e.upload_batch(x, seq, labels, ll)
         e.synchronize()
 
@@ -82,6 +84,8 @@ def main():
     ap.add_argument('--sr', type=int, default=16000)
     ap.add_argument('--numcep', type=int, default=26)
     ap.add_argument('--numcontext', type=int, default=10)
+    ap.add_argument('--features', choices=('mfcc', 'logfbank'), default='mfcc', help='logfbank: --numcep log-mel filters')
+    ap.add_argument('--deltas', type=int, choices=(0, 1, 2), default=0, help='append delta (and delta-delta) columns')
     ap.add_argument('--reps', type=int, default=10)
     ap.add_argument('--ref-utts', type=int, default=8, help='utterances the fp64 restatement is timed and checked on')
     ap.add_argument('--native-sr', type=int, default=None, help='make the audio at this rate and resample it to --sr')
@@ -91,7 +95,8 @@ def main():
     n = int(a.seconds * native)
     audios = [synth(n, native, s) for s in range(a.utts)]
     rates = None if a.native_sr is None else [native] * a.utts
-    fz = Featurizer(a.sr, a.numcep, a.numcontext, max_samples=(n if rates is None else n + int(a.seconds * a.sr) + 1) * a.utts)
+    fz = Featurizer(a.sr, a.numcep, a.numcontext, max_samples=(n if rates is None else n + int(a.seconds * a.sr) + 1) * a.utts,
+                    kind=a.features, deltas=a.deltas)
     feats = fz.compute(audios, rates=rates)               # warm-up: code objects, buffers
     t_h2d = t_k = t_d2h = wall = 0.0
     for _ in range(a.reps):
@@ -127,12 +132,13 @@ def main():
                     'bitwise_vs_ref': all(x.tobytes() == y.tobytes() for x, y in zip(at_sr, restated))}
     to_batch = batch_routes(a, fz, audios, rates) if a.to_batch else None
     t0 = time.perf_counter()
-    ref = [R.features(x, a.sr, a.numcontext, a.numcep)[0] for x in at_sr[:nref]]
+    ref = [FR.features(x, a.sr, a.numcontext, a.numcep, a.features, a.deltas)[0] for x in at_sr[:nref]]
     t_ref = (time.perf_counter() - t0) * a.utts / nref
     err = np.concatenate([np.abs(f.astype(np.float64) - r).ravel() for f, r in zip(feats, ref)])
     fz.close()
     print(json.dumps({
         'utts': a.utts, 'seconds_each': a.seconds, 'sr': a.sr, 'numcep': a.numcep, 'numcontext': a.numcontext,
+        'features': a.features, 'deltas': a.deltas, 'frame_width': fz.frame_width,
         'frames': frames, 'out_mb': round(frames * feats[0].shape[1] * 4 / 2 ** 20, 1),
         'h2d_ms': round(t_h2d / m, 3), 'kernel_ms': round(t_k / m, 3), 'd2h_ms': round(t_d2h / m, 3),
         'call_ms': round(wall / m * 1e3, 3),
