@@ -300,6 +300,21 @@ int nasr_get_decoded(nasr_handle h, int32_t* ids_out /*[B,T']*/, int32_t* lens_o
  * Host code (one thread per utterance), no GPU work. */
 int nasr_ctc_beam_search(const float* logits, const int32_t* seq_len, int B, int Tp, int C, int beam_width,
                          int merge_repeated, int32_t* ids_out, int32_t* lens_out, float* logp_out);
+/* The same search fused with a dense n-gram model over the label ids (not part of the reference).
+ * lm_logp [K][C] float32 log-probabilities, K = C^(order-1), order in [1,4], K*C <= 2^24; row ctx is the history
+ * id(t-1), ..., id(t-order+1) with the most recent id as the lowest digit in base C, histories before the start filled with
+ * bos_id (in [0,C-1]); lm_eos [K]: the log-probability that the sequence ends after the history.  Every beam entry carries
+ * the context of its prefix; wherever mass flows from an entry to its extension by label c, that contribution gets
+ * weight * lm_logp[ctx(entry)][c] + bonus added (blank and repeat updates of an entry itself get nothing), pruning uses the
+ * fused totals, and the top path is the one with the largest total + weight * lm_eos[ctx], which logp_out receives.  The
+ * score of a labelling y is therefore log P_ctc(y) + sum_i (weight * lm(y_i | y_<i) + bonus) + weight * eos(ctx(y)).
+ * merge_repeated collapses the output only: contexts are those of the unmerged prefix.  Every entry of lm_logp and lm_eos
+ * must be finite (not checked here: the call would read the whole table every time; a forbidden symbol is a large negative
+ * value, not -inf, since 0 * -inf is NaN and weight 0 would no longer be the plain search).  lm_logp == NULL: exactly
+ * nasr_ctc_beam_search (the remaining LM arguments are not read). */
+int nasr_ctc_beam_search_lm(const float* logits, const int32_t* seq_len, int B, int Tp, int C, int beam_width,
+                            int merge_repeated, const float* lm_logp, const float* lm_eos, int order, int bos_id,
+                            float weight, float bonus, int32_t* ids_out, int32_t* lens_out, float* logp_out);
 
 /* create_metric (networks/tfnetwork.py:66-70): mean over the batch of Levenshtein(hyp, truth)/len(truth)
  * (tf.edit_distance normalize=True, Appendix A.7).  Host code, no GPU work.  hyp_ids [B,hyp_stride],
@@ -453,6 +468,18 @@ int nasr_las_beam_get_ids(nasr_handle h, int32_t* ids_out);
 int nasr_las_beam_get_trace(nasr_handle h, float* scores_out, int32_t* word_out, int32_t* parent_out);
 /* of the last search, any output may be NULL: the final log-probs, lengths and finished flags (0 / 1) [B][W] */
 int nasr_las_beam_get_final(nasr_handle h, float* log_probs_out, int32_t* lengths_out, int32_t* finished_out);
+/* n-gram fusion inside the search (not part of the reference).  logp [K][C] float32, C = the handle's
+ * num_classes, K = C^(order-1), order in [1,4], K*C <= 2^24, weight and every entry finite (checked: NASR_ERR_ARG, and
+ * the table set before stays): copied to the device once, owned by the handle
+ * and used by every later nasr_las_beam_search / _resident.  Every beam row carries the context of its hypothesis (the last
+ * order-1 ids, the most recent as the lowest digit in base C, start_id in every digit at the start); an unfinished row's
+ * step log-probs become ((l - max) - lse) + (weight * logp[ctx][w]) in float32, product and sum rounded separately; a
+ * finished row's are unchanged; a row's next context is its parent's when the parent was finished, else
+ * (ctx[parent]*C + word) mod K.  The end marker is an ordinary class of the table.  logp == NULL removes the table: the
+ * search is then bit for bit the plain one.  NASR_ERR_STATE: not a LAS handle. */
+int nasr_las_beam_set_lm(nasr_handle h, const float* logp, int order, float weight);
+/* of the last search: the final context index of every beam [B][W] (all 0 when no table was set) */
+int nasr_las_beam_get_lm_context(nasr_handle h, int32_t* ctx_out);
 /* of the last search when it ran with profiling on (else NASR_ERR_STATE): device-timed ms of 7 phases: encoder (with the
  * feature copy, keys and initial state), decoder GEMMs, decoder cell, attention, selection (scores, top-W, update),
  * gather_tree, and the host's waits between chunks of steps */

@@ -24,7 +24,7 @@ SYMBOLS = [
     'nasr_loss', 'nasr_loss_and_grads', 'nasr_greedy_decode', 'nasr_upload_batch', 'nasr_compute_grads',
     'nasr_grad_device_ptr', 'nasr_grad_device_count', 'nasr_grad_bucket_count', 'nasr_grad_bucket',
     'nasr_grad_bucket_wait', 'nasr_apply_adam', 'nasr_get_grads', 'nasr_set_grads',
-    'nasr_upload_batch_context', 'nasr_label_error_rate', 'nasr_set_step_decode', 'nasr_get_decoded', 'nasr_ctc_beam_search', 'nasr_get_loss', 'nasr_resident_frames',
+    'nasr_upload_batch_context', 'nasr_label_error_rate', 'nasr_set_step_decode', 'nasr_get_decoded', 'nasr_ctc_beam_search', 'nasr_ctc_beam_search_lm', 'nasr_get_loss', 'nasr_resident_frames',
     'nasr_set_profiling', 'nasr_get_phase_times', 'nasr_set_graph_mode',
     'nasr_get_recurrence_mode', 'nasr_set_recurrence_mode', 'nasr_set_dropout_state', 'nasr_get_dropout_state',
     'nasr_step_void', 'nasr_get_persist_stats', 'nasr_stage_batch', 'nasr_stage_batch_context', 'nasr_commit_batch',
@@ -37,7 +37,7 @@ SYMBOLS = [
     'nasr_create_las', 'nasr_las_set_sampling', 'nasr_las_get_sampling', 'nasr_las_forward', 'nasr_las_get_logits',
     'nasr_las_get_fed_ids', 'nasr_las_get_sampled', 'nasr_las_beam_search', 'nasr_las_beam_get_ids',
     'nasr_las_beam_get_trace', 'nasr_las_beam_get_final', 'nasr_las_beam_get_times', 'nasr_las_forward_resident',
-    'nasr_las_beam_search_resident',
+    'nasr_las_beam_search_resident', 'nasr_las_beam_set_lm', 'nasr_las_beam_get_lm_context',
     'nasr_create_featurizer', 'nasr_mfcc_frames', 'nasr_mfcc_width', 'nasr_mfcc_filterbank', 'nasr_featurize', 'nasr_featurize_times',
     'nasr_resample_filter', 'nasr_resample_length', 'nasr_resample', 'nasr_featurize_rates',
     'nasr_upload_batch_audio', 'nasr_stage_batch_audio', 'nasr_forward_resident', 'nasr_loss_resident',
@@ -140,6 +140,8 @@ def load():
         'nasr_set_step_decode': (c_int, [H, c_int]),
         'nasr_get_decoded': (c_int, [H, ip, ip]),
         'nasr_ctc_beam_search': (c_int, [fp, ip, c_int, c_int, c_int, c_int, c_int, ip, ip, fp]),
+        'nasr_ctc_beam_search_lm': (c_int, [fp, ip, c_int, c_int, c_int, c_int, c_int, fp, fp, c_int, c_int, c_float, c_float,
+                                            ip, ip, fp]),
         'nasr_get_loss': (c_int, [H, fp]),
         'nasr_resident_frames': (c_int, [H, POINTER(c_int64)]),
         'nasr_resident_rows': (c_int, [H, POINTER(c_int64)]),
@@ -199,6 +201,8 @@ def load():
         'nasr_las_beam_get_trace': (c_int, [H, fp, ip, ip]),
         'nasr_las_beam_get_final': (c_int, [H, fp, ip, ip]),
         'nasr_las_beam_get_times': (c_int, [H, fp]),
+        'nasr_las_beam_set_lm': (c_int, [H, fp, c_int, c_float]),
+        'nasr_las_beam_get_lm_context': (c_int, [H, ip]),
         'nasr_create_featurizer': (c_int, [POINTER(MfccCfg), c_int, c_void_p, POINTER(H)]),
         'nasr_mfcc_frames': (c_int64, [POINTER(MfccCfg), c_int64]),
         'nasr_mfcc_width': (c_int, [POINTER(MfccCfg)]),

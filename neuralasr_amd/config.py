@@ -4,7 +4,9 @@ sections Parameters / Train / Test / MFCC Featurizer), the same derived fields
 network loader.  Two optional [Parameters] keys choose the features the GPU front end makes: features=mfcc|logfbank
 (default mfcc) and deltas=0|1|2 (default 0); a frame is frame_width = numcep*(1+deltas) wide and feature_size is
 (2*numcontext+1)*frame_width.  `network=networks.bilstm_ctc_net.BiLstmCTCNet` resolves to the HIP implementation in
-neuralasr_amd.networks when the reference's TensorFlow package of that name is not importable."""
+neuralasr_amd.networks when the reference's TensorFlow package of that name is not importable.  Three more optional
+[Parameters] keys fuse an n-gram model into the beam searches of evaluate / decode (lm.py): lm_file, lm_weight (default 0)
+and lm_bonus (per emitted symbol, CTC only, default 0); without lm_file nothing changes, and training never reads them."""
 import importlib
 from configparser import ConfigParser, ExtendedInterpolation
 
@@ -59,6 +61,9 @@ class Config(object):
         self.deltas = int(deltas)
         self.frame_width = self.numcep * (1 + self.deltas)
         self.feature_size = (2 * self.numcontext + 1) * self.frame_width
+        self.lm_file = par['lm_file'].strip() if 'lm_file' in par else None
+        self.lm_weight = float(par['lm_weight']) if 'lm_weight' in par else 0.0
+        self.lm_bonus = float(par['lm_bonus']) if 'lm_bonus' in par else 0.0
         # the configured batch is per GPU (reference: config.py:35-36)
         self.batch_size *= self.num_gpus if self.num_gpus > 0 else 1
         self.symbols = Symbols(self.label_context, self.sym_file) if isTraining else Symbols(self.label_context)

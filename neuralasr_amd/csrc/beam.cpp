@@ -5,6 +5,11 @@
 // even when a blank separated them (TF's documented quirk).  One thread per utterance.
 // Parity status: restated from TF 1.x's documented algorithm; unpinned (no TF here), cross-checked against an
 // independent Python restatement (oracle/nasr_oracle.py: ctc_beam_search) in tests/test_beam.py.
+//
+// nasr_ctc_beam_search_lm fuses a dense n-gram table over the label ids: every entry carries the context
+// index of its prefix, and wherever mass flows from an entry to its extension by label c that contribution gets
+// weight * logp[ctx(parent)][c] + bonus; the top path is chosen by total + weight * eos[ctx].  The plain call is the same
+// code with no table.
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
@@ -37,16 +42,31 @@ struct Prob {
 struct Entry {
   Entry* parent = nullptr;
   int label = -1;
+  int ctx = 0;   // the n-gram context index of this prefix (Lm)
   Prob oldp, newp;
   Entry** kids = nullptr;
   bool active() const { return newp.total != kLogZero; }
 };
 
+// The n-gram table of a fused search: logp [K][C], eos [K], K = C^(order-1); a context is the last order-1 ids with the
+// most recent as the lowest digit.  No table (logp == nullptr): every term below is skipped, not added as zero.
+struct Lm {
+  const float* logp = nullptr;
+  const float* eos = nullptr;
+  int C = 0, K = 1, root = 0;
+  float weight = 0.f, bonus = 0.f;
+  // what an extension of a prefix with context ctx by label c adds to the mass it carries over
+  float step(int ctx, int c) const { return weight * logp[(size_t)ctx * C + c] + bonus; }
+  int next(int ctx, int c) const { return (int)(((int64_t)ctx * C + c) % K); }
+  float final_score(const Entry* e) const { return logp ? e->newp.total + weight * eos[e->ctx] : e->newp.total; }
+};
+
 struct Arena {
   int C;
+  const Lm& lm;
   std::deque<Entry> entries;
   std::deque<std::vector<Entry*>> kid_arrays;
-  explicit Arena(int c) : C(c) {}
+  Arena(int c, const Lm& l) : C(c), lm(l) {}
   Entry* child(Entry* p, int lab) {
     if (!p->kids) {
       kid_arrays.emplace_back((size_t)C, nullptr);
@@ -58,6 +78,7 @@ struct Arena {
       slot = &entries.back();
       slot->parent = p;
       slot->label = lab;
+      if (lm.logp) slot->ctx = lm.next(p->ctx, lab);
     }
     return slot;
   }
@@ -85,11 +106,12 @@ struct Leaves {
   }
 };
 
-void decode_one(const float* logits, size_t frame_stride, int T, int C, int beam_width, bool merge_repeated,
+void decode_one(const float* logits, size_t frame_stride, int T, int C, int beam_width, bool merge_repeated, const Lm& lm,
                 int32_t* ids_out, int32_t* len_out, float* logp_out) {
   const int blank = C - 1;
-  Arena arena(C);
+  Arena arena(C, lm);
   Entry root;
+  root.ctx = lm.root;
   root.newp.total = 0.f;
   root.newp.blank = 0.f;
   Leaves leaves((size_t)beam_width);
@@ -111,7 +133,8 @@ void decode_one(const float* logits, size_t frame_stride, int T, int C, int beam
     for (Entry* b : branches) {   // extensions that keep the prefix
       if (b->parent) {
         if (b->parent->active()) {
-          const float prev = (b->label == b->parent->label) ? b->parent->oldp.blank : b->parent->oldp.total;
+          float prev = (b->label == b->parent->label) ? b->parent->oldp.blank : b->parent->oldp.total;
+          if (lm.logp) prev += lm.step(b->parent->ctx, b->label);
           b->newp.label = lse(b->newp.label, prev);
         }
         b->newp.label += lp[b->label];
@@ -129,7 +152,8 @@ void decode_one(const float* logits, size_t frame_stride, int T, int C, int beam
         if (lab == blank) continue;
         // the extension's score needs nothing of the child: test it against the beam's bottom BEFORE the child is looked up
         // or created (an inactive child that fails the test is left as it is: nothing reads it until it becomes a leaf)
-        const float prev = (lab == b->label) ? b->oldp.blank : b->oldp.total;
+        float prev = (lab == b->label) ? b->oldp.blank : b->oldp.total;
+        if (lm.logp) prev += lm.step(b->ctx, lab);
         Prob np;
         np.blank = kLogZero;
         np.label = lp[lab] + prev;
@@ -150,7 +174,7 @@ void decode_one(const float* logits, size_t frame_stride, int T, int C, int beam
     }
   }
   Entry* best = *std::max_element(leaves.v.begin(), leaves.v.end(),
-                                  [](const Entry* a, const Entry* b) { return a->newp.total < b->newp.total; });
+                                  [&](const Entry* a, const Entry* b) { return lm.final_score(a) < lm.final_score(b); });
   std::vector<int> seq;
   int prev_label = -1;
   for (const Entry* c = best; c->parent; c = c->parent) {
@@ -160,13 +184,11 @@ void decode_one(const float* logits, size_t frame_stride, int T, int C, int beam
   std::reverse(seq.begin(), seq.end());
   *len_out = (int32_t)seq.size();
   for (size_t i = 0; i < seq.size(); ++i) ids_out[i] = seq[i];
-  if (logp_out) *logp_out = best->newp.total;
+  if (logp_out) *logp_out = lm.final_score(best);
 }
 
-}  // namespace
-
-extern "C" int nasr_ctc_beam_search(const float* logits, const int32_t* seq_len, int B, int Tp, int C, int beam_width,
-                                    int merge_repeated, int32_t* ids_out, int32_t* lens_out, float* logp_out) {
+int beam_search(const float* logits, const int32_t* seq_len, int B, int Tp, int C, int beam_width, int merge_repeated,
+                const Lm& lm, int32_t* ids_out, int32_t* lens_out, float* logp_out) {
   if (!logits || !seq_len || !ids_out || !lens_out || B < 1 || Tp < 1 || C < 2 || beam_width < 1) return NASR_ERR_ARG;
   for (int b = 0; b < B; ++b)
     if (seq_len[b] < 0 || seq_len[b] > Tp) return NASR_ERR_ARG;
@@ -174,11 +196,33 @@ extern "C" int nasr_ctc_beam_search(const float* logits, const int32_t* seq_len,
   const int nthr = (int)std::min<unsigned>(hw, (unsigned)B);
   std::vector<std::thread> pool;
   for (int w = 0; w < nthr; ++w)
-    pool.emplace_back([=]() {
+    pool.emplace_back([=, &lm]() {
       for (int b = w; b < B; b += nthr)
-        decode_one(logits + (size_t)b * C, (size_t)B * C, seq_len[b], C, beam_width, merge_repeated != 0,
+        decode_one(logits + (size_t)b * C, (size_t)B * C, seq_len[b], C, beam_width, merge_repeated != 0, lm,
                    ids_out + (size_t)b * Tp, lens_out + b, logp_out ? logp_out + b : nullptr);
     });
   for (auto& t : pool) t.join();
   return NASR_OK;
+}
+
+}  // namespace
+
+extern "C" int nasr_ctc_beam_search(const float* logits, const int32_t* seq_len, int B, int Tp, int C, int beam_width,
+                                    int merge_repeated, int32_t* ids_out, int32_t* lens_out, float* logp_out) {
+  return beam_search(logits, seq_len, B, Tp, C, beam_width, merge_repeated, Lm(), ids_out, lens_out, logp_out);
+}
+
+extern "C" int nasr_ctc_beam_search_lm(const float* logits, const int32_t* seq_len, int B, int Tp, int C, int beam_width,
+                                       int merge_repeated, const float* lm_logp, const float* lm_eos, int order, int bos_id,
+                                       float weight, float bonus, int32_t* ids_out, int32_t* lens_out, float* logp_out) {
+  Lm lm;
+  if (lm_logp) {
+    if (!lm_eos || C < 2 || order < 1 || order > 4 || bos_id < 0 || bos_id >= C) return NASR_ERR_ARG;
+    int64_t K = 1;   // C^(order-1); the table's K * C entries may not exceed 2^24
+    for (int i = 1; i < order && K * C <= ((int64_t)1 << 24); ++i) K *= C;
+    if (K * C > ((int64_t)1 << 24)) return NASR_ERR_ARG;
+    lm.logp = lm_logp; lm.eos = lm_eos; lm.C = C; lm.K = (int)K; lm.weight = weight; lm.bonus = bonus;
+    for (int i = 1; i < order; ++i) lm.root = lm.root * C + bos_id;
+  }
+  return beam_search(logits, seq_len, B, Tp, C, beam_width, merge_repeated, lm, ids_out, lens_out, logp_out);
 }

@@ -6,6 +6,10 @@
 // Beam rows r = b*W + k (utterance b, beam k), R = rup(B*W, 16) rows; rows >= B*W are padding that no selection reads.
 // Every kernel of a step after the one that finished every beam returns at once: *done (set by las_beam_finish) is read
 // at the top, so the host enqueues steps without waiting and reads the word once per chunk of steps.
+//
+// n-gram fusion: every beam row carries the context index of its hypothesis (the last order-1 ids, the
+// most recent as the lowest digit, K = C^(order-1) contexts; 0 and K = 1 without a table); the score kernel adds
+// weight * table[ctx][w] to an unfinished row's log-probs, the update derives the row's next context from its parent's.
 #include "las_beam.h"
 
 #include <cfloat>
@@ -30,15 +34,22 @@ __device__ __forceinline__ uint32_t ord_key(float f) {
 __device__ __forceinline__ float ord_val(uint32_t k) {
   return __uint_as_float((k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k);
 }
+// lp + weight * t as a rounded product and a rounded sum (no fused multiply-add: tests/las_beam_lm_ref.py follows it
+// operation by operation)
+__device__ __forceinline__ float lm_fuse(float lp, float weight, float t) {
+#pragma clang fp contract(off)
+  const float p = weight * t;
+  return lp + p;
+}
 }  // namespace
 
 // S [R][LAS_SW] = [a = 0 | h = (h_fw final; h_bw final) of utterance r / W], c [R][LAS_HD], ids = start_id, log_probs =
-// (0, -inf, -inf, ...), finished = (0, 1, 1, ...), lengths = 0 (block r, 512 threads)
+// (0, -inf, -inf, ...), finished = (0, 1, 1, ...), lengths = 0, ctx = ctx0 (start_id in every digit) (block r, 512 threads)
 __global__ __launch_bounds__(512) void las_beam_init_kernel(const float* __restrict__ out4, const float* __restrict__ c4, int L4,
                                                             int Bp, int W, int nrows, int start_id, float* __restrict__ S,
                                                             float* __restrict__ c, int32_t* __restrict__ ids,
                                                             float* __restrict__ logp, int32_t* __restrict__ len,
-                                                            int32_t* __restrict__ fin) {
+                                                            int32_t* __restrict__ fin, int32_t* __restrict__ ctx, int ctx0) {
   const int r = blockIdx.x, k = threadIdx.x;
   float h = 0.f, cv = 0.f;
   if (r < nrows && k < 2 * LAS_H) {
@@ -56,13 +67,15 @@ __global__ __launch_bounds__(512) void las_beam_init_kernel(const float* __restr
     logp[r] = kb == 0 ? 0.f : -INFINITY;
     len[r] = 0;
     fin[r] = kb != 0;
+    ctx[r] = ctx0;
   }
 }
 
 void launch_las_beam_init(const float* out4, const float* c4, int L4, int Bp, int W, int nrows, int R, int start_id, float* S,
-                          float* c, int32_t* ids, float* logp, int32_t* len, int32_t* fin, hipStream_t st) {
+                          float* c, int32_t* ids, float* logp, int32_t* len, int32_t* fin, int32_t* ctx, int ctx0,
+                          hipStream_t st) {
   hipLaunchKernelGGL(las_beam_init_kernel, dim3(R), dim3(LAS_HD), 0, st, out4, c4, L4, Bp, W, nrows, start_id, S, c, ids, logp,
-                     len, fin);
+                     len, fin, ctx, ctx0);
 }
 
 // Bahdanau attention of beam row r over the memory of utterance r / W (block r, 4 waves): the arithmetic of
@@ -113,11 +126,15 @@ void launch_las_beam_attend(const float* keys, const float* mem, const float* q,
 // One wave per beam row: lp = (l - max) - log(sum exp(l - max)) (the sum: lane-strided partials, then a fixed butterfly);
 // a finished row's lp is 0 at end_id and FLT_LOWEST elsewhere; total = log_probs + lp; score = total / pen[len_s],
 // len_s = lengths + (!finished && w != end_id).  scores / totals [B*W][C]: utterance b's flat candidate k*C + w.
+// table != nullptr (the same for every wave of the launch): an unfinished row's lp gets weight * table[ctx[r]][w] added, the
+// row's C contiguous floats of the [K][C] table read lane-strided like the logits.
 __global__ __launch_bounds__(256) void las_beam_score_kernel(const float* __restrict__ logits, int Cp, int C,
                                                              const float* __restrict__ logp, const int32_t* __restrict__ len,
                                                              const int32_t* __restrict__ fin, const float* __restrict__ pen,
-                                                             int end_id, int nrows, float* __restrict__ scores,
-                                                             float* __restrict__ totals, const int32_t* __restrict__ done) {
+                                                             int end_id, int nrows, const float* __restrict__ table,
+                                                             const int32_t* __restrict__ ctx, float weight,
+                                                             float* __restrict__ scores, float* __restrict__ totals,
+                                                             const int32_t* __restrict__ done) {
   if (*done) return;
   const int r = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (r >= nrows) return;
@@ -132,10 +149,12 @@ __global__ __launch_bounds__(256) void las_beam_score_kernel(const float* __rest
   const bool f = fin[r] != 0;
   const float lp0 = logp[r];
   const int n0 = len[r];
+  const float* trow = (table && !f) ? table + (size_t)ctx[r] * C : nullptr;
   float* sc = scores + (size_t)r * C;
   float* to = totals + (size_t)r * C;
   for (int w = lane; w < C; w += 64) {
-    const float lp = f ? (w == end_id ? 0.f : -FLT_MAX) : (l[w] - m) - lse;
+    float lp = f ? (w == end_id ? 0.f : -FLT_MAX) : (l[w] - m) - lse;
+    if (trow) lp = lm_fuse(lp, weight, trow[w]);
     const float t = lp0 + lp;
     const int ls = n0 + ((!f && w != end_id) ? 1 : 0);
     to[w] = t;
@@ -144,10 +163,10 @@ __global__ __launch_bounds__(256) void las_beam_score_kernel(const float* __rest
 }
 
 void launch_las_beam_score(const float* logits, int Cp, int C, const float* logp, const int32_t* len, const int32_t* fin,
-                           const float* pen, int end_id, int nrows, float* scores, float* totals, const int32_t* done,
-                           hipStream_t st) {
+                           const float* pen, int end_id, int nrows, const float* table, const int32_t* ctx, float weight,
+                           float* scores, float* totals, const int32_t* done, hipStream_t st) {
   hipLaunchKernelGGL(las_beam_score_kernel, dim3((nrows + 3) / 4), dim3(256), 0, st, logits, Cp, C, logp, len, fin, pen, end_id,
-                     nrows, scores, totals, done);
+                     nrows, table, ctx, weight, scores, totals, done);
 }
 
 // The exact top-W of utterance b's N = W*C scores (block b, 1024 threads), in tf.nn.top_k's order: score descending, equal
@@ -244,11 +263,12 @@ void launch_las_beam_select(const float* scores, int B, int W, int C, int32_t* s
 
 // Beam row r = b*W + k takes candidate sel_idx[r] = parent*C + word: [a | h] and c gathered from the parent's row of the
 // step's outputs (Sx, cx) into S, c; log_probs = total, finished = finished[parent] || word == end_id, lengths =
-// lengths[parent] + !finished[parent]; the next input id; the trace row of the step (block r, 256 threads).
+// lengths[parent] + !finished[parent]; ctx = finished[parent] ? ctx[parent] : (ctx[parent]*C + word) mod K (ctx_in: the
+// step's input copy, as len_in / fin_in); the next input id; the trace row of the step (block r, 256 threads).
 __global__ __launch_bounds__(256) void las_beam_update_kernel(
     const int32_t* __restrict__ sel_idx, const float* __restrict__ sel_score, const float* __restrict__ totals, int W, int C,
-    int end_id, const float* __restrict__ Sx, const float* __restrict__ cx, const int32_t* __restrict__ len_in, const int32_t* __restrict__ fin_in, float* __restrict__ S, float* __restrict__ c,
-    int32_t* __restrict__ ids, float* __restrict__ logp_out, int32_t* __restrict__ len_out, int32_t* __restrict__ fin_out,
+    int end_id, const float* __restrict__ Sx, const float* __restrict__ cx, const int32_t* __restrict__ len_in, const int32_t* __restrict__ fin_in, const int32_t* __restrict__ ctx_in, int K, float* __restrict__ S, float* __restrict__ c,
+    int32_t* __restrict__ ids, float* __restrict__ logp_out, int32_t* __restrict__ len_out, int32_t* __restrict__ fin_out, int32_t* __restrict__ ctx_out,
     float* __restrict__ tr_score, int32_t* __restrict__ tr_word, int32_t* __restrict__ tr_parent,
     const int32_t* __restrict__ done) {
   if (*done) return;
@@ -265,6 +285,8 @@ __global__ __launch_bounds__(256) void las_beam_update_kernel(
     logp_out[r] = totals[(size_t)b * W * C + idx];
     fin_out[r] = pf || word == end_id;
     len_out[r] = len_in[pr] + (pf ? 0 : 1);
+    const int pc = ctx_in[pr];   // < K, and K * C <= 2^24: no overflow below
+    ctx_out[r] = pf ? pc : (pc * C + word) % K;
     ids[r] = word;
     tr_score[r] = sel_score[r];
     tr_word[r] = word;
@@ -274,11 +296,12 @@ __global__ __launch_bounds__(256) void las_beam_update_kernel(
 
 void launch_las_beam_update(const int32_t* sel_idx, const float* sel_score, const float* totals, int W, int C, int end_id,
                             int nrows, const float* Sx, const float* cx, const int32_t* len_in,
-                            const int32_t* fin_in, float* S, float* c, int32_t* ids, float* logp_out, int32_t* len_out,
-                            int32_t* fin_out, float* tr_score, int32_t* tr_word, int32_t* tr_parent, const int32_t* done,
-                            hipStream_t st) {
+                            const int32_t* fin_in, const int32_t* ctx_in, int K, float* S, float* c, int32_t* ids,
+                            float* logp_out, int32_t* len_out, int32_t* fin_out, int32_t* ctx_out, float* tr_score,
+                            int32_t* tr_word, int32_t* tr_parent, const int32_t* done, hipStream_t st) {
   hipLaunchKernelGGL(las_beam_update_kernel, dim3(nrows), dim3(256), 0, st, sel_idx, sel_score, totals, W, C, end_id, Sx, cx,
-                     len_in, fin_in, S, c, ids, logp_out, len_out, fin_out, tr_score, tr_word, tr_parent, done);
+                     len_in, fin_in, ctx_in, K, S, c, ids, logp_out, len_out, fin_out, ctx_out, tr_score, tr_word, tr_parent,
+                     done);
 }
 
 // after step t: flags[1] = t + 1 (steps run); flags[0] = 1 once every beam is finished or t + 1 == max_steps (one block)

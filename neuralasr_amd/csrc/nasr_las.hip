@@ -27,7 +27,7 @@ struct LasBeam {
   DevBuf feats, X0, X[NL], xp[NL], act[NL], c[NL], out[NL], keys;
   // decoder rows: S / c the beams' state, Sx / cx the step's outputs before the gather by parent
   DevBuf S, cs, Sx, cx, gp, dact, HC, Q, logits, ids;
-  DevBuf logp[2], len[2], fin[2];                  // ping-pong by step parity: step t reads [t & 1], writes the other
+  DevBuf logp[2], len[2], fin[2], ctx[2];          // ping-pong by step parity: step t reads [t & 1], writes the other
   DevBuf scores, totals, sel_idx, sel_score, pen, flags;
   DevBuf tr_score, tr_word, tr_parent, gathered;   // [max_steps][B*W]
   std::vector<float> hpen;
@@ -61,6 +61,10 @@ struct LasState {
   DevBuf S, cinit, dc, dact, gp, Q, alpha, HC, logits, ids, sampled;
   DevBuf dL, wce, w, tmpA, dA, dHC, dQ, dhq, dGd, dS, dcd, dvpart, csws;
   std::unique_ptr<LasBeam> beam;   // the beam search's buffers (first search)
+  // n-gram fusion of the search (nasr_las_beam_set_lm): the dense table [lm_K][C] on the device, lm_K = C^(order-1)
+  DevBuf lm;
+  int lm_order = 0, lm_K = 1;
+  float lm_weight = 0.f;
 };
 
 namespace {
@@ -425,7 +429,8 @@ int las_beam_ensure(nasr_ctx* h, LasBeam& m, int B, int T, int W, int max_steps,
   ok &= m.HC.ensure((size_t)R * 2 * LAS_HD * 4, &grew) && m.Q.ensure((size_t)R * LAS_HD * 4, &grew);
   ok &= m.logits.ensure((size_t)R * h->Cp * 4, &grew) && m.ids.ensure((size_t)R * 4, &grew);
   for (int i = 0; i < 2; ++i)
-    ok &= m.logp[i].ensure((size_t)R * 4, &grew) && m.len[i].ensure((size_t)R * 4, &grew) && m.fin[i].ensure((size_t)R * 4, &grew);
+    ok &= m.logp[i].ensure((size_t)R * 4, &grew) && m.len[i].ensure((size_t)R * 4, &grew) && m.fin[i].ensure((size_t)R * 4, &grew) &&
+          m.ctx[i].ensure((size_t)R * 4, &grew);
   ok &= m.scores.ensure((size_t)nrows * C * 4, &grew) && m.totals.ensure((size_t)nrows * C * 4, &grew);
   ok &= m.sel_idx.ensure((size_t)nrows * 4, &grew) && m.sel_score.ensure((size_t)nrows * 4, &grew);
   ok &= m.pen.ensure((size_t)(max_steps + 1) * 4, &grew) && m.flags.ensure(8, &grew);
@@ -474,11 +479,16 @@ int las_beam_search(nasr_ctx* h, const float* feats, int B, int T, int W, int ma
   }
   const float* X0 = feats ? m.X0.as<float>() : h->X0.as<float>();
   if (int rc = las_encode(h, X0, T, B, Bp, m.Lr, m.X, m.xp, m.act, m.c, m.out)) return rc;
+  // the n-gram table, if one is set: every row's context starts as start_id in every digit
+  const float* table = s.lm_order ? fp(s.lm) : nullptr;
+  const int K = s.lm_order ? s.lm_K : 1;
+  int ctx0 = 0;
+  for (int d = 1; d < s.lm_order; ++d) ctx0 = ctx0 * C + start_id;
   const float* mem = fp(m.out[LasBeam::NL - 1]);
   if (int rc = las_gemm(h, mem, P + s.off_wmem, fp(m.keys), L4 * Bp, LAS_HD, LAS_HD, LAS_HD, LAS_HD, LAS_HD, false, false))
     return rc;
   launch_las_beam_init(mem, fp(m.c[LasBeam::NL - 1]), L4, Bp, W, nrows, R, start_id, fp(m.S), fp(m.cs), m.ids.as<int32_t>(),
-                       fp(m.logp[0]), m.len[0].as<int32_t>(), m.fin[0].as<int32_t>(), st);
+                       fp(m.logp[0]), m.len[0].as<int32_t>(), m.fin[0].as<int32_t>(), m.ctx[0].as<int32_t>(), ctx0, st);
   HIPCHK(h, hipGetLastError());
   mark(LB_ENC);
   const int32_t* done = m.flags.as<int32_t>();
@@ -505,11 +515,12 @@ int las_beam_search(nasr_ctx* h, const float* feats, int B, int T, int W, int ma
         return rc;
       mark(LB_GEMM);
       launch_las_beam_score(fp(m.logits), Cp, C, fp(m.logp[i]), m.len[i].as<int32_t>(), m.fin[i].as<int32_t>(), fp(m.pen), end_id,
-                            nrows, fp(m.scores), fp(m.totals), done, st);
+                            nrows, table, m.ctx[i].as<int32_t>(), s.lm_weight, fp(m.scores), fp(m.totals), done, st);
       launch_las_beam_select(fp(m.scores), B, W, C, m.sel_idx.as<int32_t>(), fp(m.sel_score), done, st);
       launch_las_beam_update(m.sel_idx.as<int32_t>(), fp(m.sel_score), fp(m.totals), W, C, end_id, nrows, fp(m.Sx), fp(m.cx),
-                             m.len[i].as<int32_t>(), m.fin[i].as<int32_t>(), fp(m.S), fp(m.cs), m.ids.as<int32_t>(),
-                             fp(m.logp[o]), m.len[o].as<int32_t>(), m.fin[o].as<int32_t>(), fp(m.tr_score) + tr,
+                             m.len[i].as<int32_t>(), m.fin[i].as<int32_t>(), m.ctx[i].as<int32_t>(), K, fp(m.S), fp(m.cs),
+                             m.ids.as<int32_t>(), fp(m.logp[o]), m.len[o].as<int32_t>(), m.fin[o].as<int32_t>(),
+                             m.ctx[o].as<int32_t>(), fp(m.tr_score) + tr,
                              m.tr_word.as<int32_t>() + tr, m.tr_parent.as<int32_t>() + tr, done, st);
       launch_las_beam_finish(m.fin[o].as<int32_t>(), nrows, t, max_steps, m.flags.as<int32_t>(), st);
       HIPCHK(h, hipGetLastError());
@@ -764,6 +775,43 @@ int nasr_las_beam_get_final(nasr_handle h, float* log_probs_out, int32_t* length
   if (lengths_out && (rc = beam_read(h, m->len[f], n, lengths_out))) return rc;
   if (finished_out && (rc = beam_read(h, m->fin[f], n, finished_out))) return rc;
   return NASR_OK;
+}
+
+int nasr_las_beam_set_lm(nasr_handle h, const float* logp, int order, float weight) {
+  LasState* s = las_of(h);
+  if (!s) return h ? h->fail(NASR_ERR_STATE, "nasr_las_beam_set_lm: not a LAS handle") : NASR_ERR_ARG;
+  if (logp) {
+    if (order < 1 || order > 4) return h->fail(NASR_ERR_ARG, "nasr_las_beam_set_lm: order must be in [1,4]");
+    if (!std::isfinite(weight)) return h->fail(NASR_ERR_ARG, "nasr_las_beam_set_lm: weight must be finite");
+  }
+  const int64_t C = h->C, lim = (int64_t)1 << 24;
+  int64_t K = 1;
+  for (int d = 1; logp && d < order && K * C <= lim; ++d) K *= C;
+  if (K * C > lim) return h->fail(NASR_ERR_ARG, "nasr_las_beam_set_lm: a table of num_classes^order entries exceeds 2^24");
+  if (logp)   // (0 * -inf is NaN: a non-finite entry would break "weight 0 is the plain search")
+    for (int64_t i = 0; i < K * C; ++i)
+      if (!std::isfinite(logp[i])) return h->fail(NASR_ERR_ARG, "nasr_las_beam_set_lm: every table entry must be finite");
+  HIPCHK(h, hipSetDevice(h->device));
+  if (int rc = sync_checked(h)) return rc;   // (a search in flight may still read the table this call replaces or frees)
+  // the handle is on the plain search from here until the new table is whole on the device
+  s->lm_order = 0; s->lm_K = 1; s->lm_weight = 0.f;
+  if (!logp) {
+    s->lm.release();
+    return NASR_OK;
+  }
+  if (!s->lm.ensure((size_t)(K * C) * 4, nullptr)) return h->fail(NASR_ERR_HIP, "nasr_las_beam_set_lm: hipMalloc failed");
+  HIPCHK(h, hipMemcpyAsync(s->lm.p, logp, (size_t)(K * C) * 4, hipMemcpyHostToDevice, h->st));
+  if (int rc = sync_checked(h)) return rc;
+  s->lm_order = order; s->lm_K = (int)K; s->lm_weight = weight;
+  return NASR_OK;
+}
+
+int nasr_las_beam_get_lm_context(nasr_handle h, int32_t* ctx_out) {
+  int rc;
+  LasBeam* m = beam_of(h, "nasr_las_beam_get_lm_context", &rc);
+  if (!m) return rc;
+  if (!ctx_out) return h->fail(NASR_ERR_ARG, "nasr_las_beam_get_lm_context: null output");
+  return beam_read(h, m->ctx[m->Tdec & 1], (size_t)m->B * m->W, ctx_out);
 }
 
 int nasr_las_beam_get_times(nasr_handle h, float* ms_out) {

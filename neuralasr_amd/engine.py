@@ -365,19 +365,28 @@ class Engine:
         self._ck(self.lib.nasr_get_decoded(self.h, _ip(ids), _ip(lens)))
         return [ids[b, :lens[b]].tolist() for b in range(B)]
 
-    def beam_search(self, logits_tm, seq_len, beam_width=100, merge_repeated=True):
+    def beam_search(self, logits_tm, seq_len, beam_width=100, merge_repeated=True, lm=None, lm_weight=0.0, lm_bonus=0.0):
         """tf.nn.ctc_beam_search_decoder defaults (networks/tfnetwork.py:61-64) on host logits [T',B,C].
-        Returns (list of id lists, log-probabilities [B])."""
+        Returns (list of id lists, log-probabilities [B]).  lm (lm.NGramLM): the search fused with that model
+        (include/nasr.h: nasr_ctc_beam_search_lm); the log-probabilities are then the fused scores."""
         lg = _f32(logits_tm)
         Tp, B, C = lg.shape
         seq = _i32(np.asarray([int(x) for x in seq_len]))
         ids = np.zeros((B, Tp), np.int32)
         lens = np.zeros(B, np.int32)
         logp = np.zeros(B, np.float32)
-        rc = self.lib.nasr_ctc_beam_search(_fp(lg), _ip(seq), B, Tp, C, int(beam_width), int(bool(merge_repeated)),
-                                           _ip(ids), _ip(lens), _fp(logp))
+        fn = 'nasr_ctc_beam_search' if lm is None else 'nasr_ctc_beam_search_lm'
+        if lm is not None:
+            if lm.num_classes != C:
+                raise ValueError(f'the language model has num_classes {lm.num_classes} but the logits have {C} classes')
+            rc = self.lib.nasr_ctc_beam_search_lm(_fp(lg), _ip(seq), B, Tp, C, int(beam_width), int(bool(merge_repeated)),
+                                                  _fp(lm.logp), _fp(lm.eos), lm.order, lm.bos_id, float(lm_weight),
+                                                  float(lm_bonus), _ip(ids), _ip(lens), _fp(logp))
+        else:
+            rc = self.lib.nasr_ctc_beam_search(_fp(lg), _ip(seq), B, Tp, C, int(beam_width), int(bool(merge_repeated)),
+                                               _ip(ids), _ip(lens), _fp(logp))
         if rc != 0:
-            raise _lib.NasrError(rc, 'nasr_ctc_beam_search: bad arguments')
+            raise _lib.NasrError(rc, fn + ': bad arguments')
         return [ids[b, :lens[b]].tolist() for b in range(B)], logp
 
     def get_loss(self):
@@ -741,6 +750,26 @@ class LasEngine(Engine):
             fin = np.empty((B, W), np.int32)
             self._ck(self.lib.nasr_las_beam_get_final(self.h, _fp(out['log_probs']), _ip(out['lengths']), _ip(fin)))
             out['finished'] = fin != 0
+        return out
+
+    def set_lm(self, lm, weight=0.0):
+        """Fuse an n-gram model (lm.NGramLM, or a float32 table [K][C] with its order as (table, order)) into every later
+        beam search (include/nasr.h: nasr_las_beam_set_lm); None removes it."""
+        if lm is None:
+            return self._ck(self.lib.nasr_las_beam_set_lm(self.h, None, 0, 0.0))
+        table, order, classes = (lm.logp, lm.order, lm.num_classes) if hasattr(lm, 'logp') else (lm[0], lm[1], None)
+        table = _f32(table)
+        if classes is None:
+            classes = table.shape[-1]
+        if classes != self.num_classes or table.size != self.num_classes ** int(order):
+            raise ValueError(f'an order-{order} table over {self.num_classes} classes has {self.num_classes}^{order} '
+                             f'entries; got num_classes {classes} and {table.size} entries')
+        self._ck(self.lib.nasr_las_beam_set_lm(self.h, _fp(table), int(order), float(weight)))
+
+    def lm_context(self, B, W):
+        """the final n-gram context index of every beam of the last search [B, W]"""
+        out = np.empty((B, W), np.int32)
+        self._ck(self.lib.nasr_las_beam_get_lm_context(self.h, _ip(out)))
         return out
 
     def beam_times(self):

@@ -105,6 +105,7 @@ class HipNetwork(Network):
         self._pending = None                    # the batch of the last fast-path step, until that step is known not to be void
         self._begun = None                      # begin_step() without its finish_step() yet
         self._pool = None                       # host threads that decode the steps' logits (train_ler_decoder = 'beam')
+        self._lm = None                         # config.lm_file's model, loaded at the first evaluate / decode
         self.global_step = self.config.start_step
         self.load_checkpoint(self.global_step if fortraining else 1, self.config.model_dir)
         if fortraining and self.coll.rank == 0:
@@ -252,10 +253,21 @@ class HipNetwork(Network):
                   self.engine.upload_batch_context(f, s, l, ll, self.config.numcontext, self._frame_width())):
             self.engine.upload_batch(f, s, l, ll)
 
-    def _decode(self, mfccs, seq_len, which):
+    def language_model(self):
+        """The n-gram model of config.lm_file (lm.py), or None without the key: evaluate() and decode() fuse it into
+        their beam search with config.lm_weight and config.lm_bonus; train() and validate() never do."""
+        if self._lm is None and getattr(self.config, 'lm_file', None):
+            from ..lm import load_for
+            self._lm = load_for(self.config)
+        return self._lm
+
+    def _decode(self, mfccs, seq_len, which, lm=None):
         if which == 'beam':
             logits = self._retry_aborted(lambda: self._forward(mfccs, seq_len))
-            return self.engine.beam_search(logits, seq_len, self.beam_width, merge_repeated=True)[0]
+            if lm is None:
+                return self.engine.beam_search(logits, seq_len, self.beam_width, merge_repeated=True)[0]
+            return self.engine.beam_search(logits, seq_len, self.beam_width, merge_repeated=True, lm=lm,
+                                           lm_weight=self.config.lm_weight, lm_bonus=self.config.lm_bonus)[0]
         if isinstance(mfccs, AudioBatch):
             def run():
                 self._upload_audio(mfccs)
@@ -263,7 +275,7 @@ class HipNetwork(Network):
             return self._retry_aborted(run)
         return self._retry_aborted(lambda: self.engine.greedy_decode(mfccs, seq_len))
 
-    def _loss_ler_one(self, mfccs, labels, seq_len, labels_len):
+    def _loss_ler_one(self, mfccs, labels, seq_len, labels_len, lm=None):
         def run():
             if isinstance(mfccs, AudioBatch):
                 self._upload_audio(mfccs, labels, labels_len)
@@ -274,20 +286,20 @@ class HipNetwork(Network):
             return loss, hyps
         loss, hyps = self._retry_aborted(run)
         if hyps is None:
-            hyps = self._decode(mfccs, seq_len, 'beam')
+            hyps = self._decode(mfccs, seq_len, 'beam', lm)
         return loss, self.engine.label_error_rate(hyps, labels, labels_len), hyps
 
-    def _loss_ler(self, mfccs, labels, seq_len, labels_len):
+    def _loss_ler(self, mfccs, labels, seq_len, labels_len, lm=None):
         """(loss, mean LER, hypotheses).  A training network evaluates the way its graph was built
         (setup_training_network, tfnetwork.py:115-140): per tower on the tf.split shards - the literal net's
         stack-reshape map is a function of the SHARD's batch size - and the mean of the shard means."""
         n, mine = self._towers()
         if n == 1:
-            return self._loss_ler_one(mfccs, labels, seq_len, labels_len)
+            return self._loss_ler_one(mfccs, labels, seq_len, labels_len, lm)
         losses, lers, hyps = [], [], []
         for k in mine:
             f, l, s, ll = take_shard(mfccs, labels, seq_len, labels_len, n, k)
-            lo, le, hy = self._loss_ler_one(f, l, s, ll)
+            lo, le, hy = self._loss_ler_one(f, l, s, ll, lm)
             losses.append(lo)
             lers.append(le)
             hyps.extend(hy)
@@ -521,14 +533,14 @@ class HipNetwork(Network):
 
     def evaluate(self, mfccs, labels, seq_len, labels_len):
         self._settle()
-        loss, ler, hyps = self._loss_ler(mfccs, labels, seq_len, labels_len)
+        loss, ler, hyps = self._loss_ler(mfccs, labels, seq_len, labels_len, self.language_model())
         # SparseTensorValue.values: every utterance's ids concatenated (tfnetwork.py:176-177)
         flat = np.asarray([i for h in hyps for i in h], dtype=np.int64)
         return flat, np.float32(loss), np.float32(ler)
 
     def decode(self, mfccs, seq_len):
         self._settle()
-        hyps = self._decode(mfccs, seq_len, self.decoder)
+        hyps = self._decode(mfccs, seq_len, self.decoder, self.language_model())
         return np.asarray([i for h in hyps for i in h], dtype=np.int64)
 
     # ------------------------------------------------------------------ the same four calls on audio

@@ -19,7 +19,10 @@ NaN then (beam_sequence_loss).
 
 Every call takes a features.AudioBatch in the place of the padded features (audio_batch, the *_audio calls): a tower's
 shard goes through the GPU front end into the handle's batch slot (LasEngine.upload_batch_audio) and the passes and the
-beam search run on that resident batch, so no feature crosses to the host or back."""
+beam search run on that resident batch, so no feature crosses to the host or back.
+
+With lm_file in the config the beam search of decode() / evaluate() is fused with that n-gram model at lm_weight
+(LasEngine.set_lm); train() and validate() run the training graph and are not touched by it."""
 import numpy as np
 
 from ..engine import LasEngine
@@ -124,6 +127,9 @@ class LAS(HipNetwork):
         if self.coll.world > 1:
             p, seed, counter, _ = e.sampling_state()
             e.set_sampling_state(p, seed, counter, self.coll.rank)
+        if getattr(config, 'lm_file', None):
+            from ..lm import load_for
+            e.set_lm(load_for(config), config.lm_weight)
         return e
 
     def initial_params(self, tensors, seed):

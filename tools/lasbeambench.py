@@ -4,6 +4,10 @@ gather_tree, ending in a device synchronise) plus the read-back of the gathered 
 device-timed phases: encoder, decoder GEMMs, decoder cell, attention, selection (scores, top-W, update), gather_tree,
 host waits between chunks of steps; the read-back is host-timed.  Prints one JSON line.
    python tools/lasbeambench.py [--steps 10 --warmup 3]
+--lm-order N times the same search three ways in one process: plain, fused with an order-N table at weight 0.3
+(nasr_las_beam_set_lm; zero-mean random log-probs, the end id's column lowered by 20 so that both searches run all the
+steps), and plain again, whose distance from the first plain run is the run-to-run spread; each with its profiled phases.
+   python tools/lasbeambench.py --lm-order 4 [--steps 10 --warmup 3]
 --from-audio times one LAS.evaluate of that batch shape given as audio (one utterance at 16 kHz whose 400 frames give
 T 400) two ways, alternating in one process: the host route (Featurizer.compute, zero-pad, evaluate: the features come to
 the host and go back) and evaluate_audio (the features stay in the handle's batch slot).  Host clock around each call;
@@ -80,6 +84,7 @@ def main():
     ap.add_argument('--width', type=int, default=1000)
     ap.add_argument('--max-steps', type=int, default=100)
     ap.add_argument('--from-audio', action='store_true', help='time LAS.evaluate through the host route and evaluate_audio')
+    ap.add_argument('--lm-order', type=int, default=0, help='also time the search fused with an n-gram table of this order')
     a = ap.parse_args()
     if a.from_audio:
         return evaluate_from_audio(a)
@@ -90,27 +95,39 @@ def main():
     feats = rs.randn(B, T, F).astype(np.float32)
     e = LasEngine(F, C)
     e.set_params(LAS.initial_params(LAS.__new__(LAS), e.tensors(), seed=1))
-    for _ in range(a.warmup):
+
+    def timed():
+        for _ in range(a.warmup):
+            out = e.beam_search(feats, seq, W, S, start_id, end_id, 0.5)
+        t0 = time.perf_counter()
+        for _ in range(a.steps):
+            out = e.beam_search(feats, seq, W, S, start_id, end_id, 0.5)
+        dt = (time.perf_counter() - t0) / a.steps
+        e.set_profiling(True)
+        t0 = time.perf_counter()
         out = e.beam_search(feats, seq, W, S, start_id, end_id, 0.5)
-    t0 = time.perf_counter()
-    for _ in range(a.steps):
-        out = e.beam_search(feats, seq, W, S, start_id, end_id, 0.5)
-    dt = (time.perf_counter() - t0) / a.steps
-    e.set_profiling(True)
-    t0 = time.perf_counter()
-    out = e.beam_search(feats, seq, W, S, start_id, end_id, 0.5)
-    t1 = time.perf_counter()
-    ph = e.beam_times()
-    t2 = time.perf_counter()
-    ids = np.empty((B, out['steps'], W), np.int32)
-    e._ck(e.lib.nasr_las_beam_get_ids(e.h, ids.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))))
-    readback = (time.perf_counter() - t2) * 1e3
-    phases = {k + '_ms': v for k, v in ph.items()}
-    phases['readback_ms'] = readback
-    phases['profiled_total_ms'] = (t1 - t0) * 1e3
-    print(json.dumps({'workload': 'las_beam', 'B': B, 'T': T, 'F': F, 'C': C, 'W': W, 'max_steps': S,
-                      'T_dec': out['steps'], 'ms_per_decode': round(dt * 1e3, 3),
-                      'phases': {k: round(v, 3) for k, v in phases.items()}}))
+        t1 = time.perf_counter()
+        ph = e.beam_times()
+        t2 = time.perf_counter()
+        ids = np.empty((B, out['steps'], W), np.int32)
+        e._ck(e.lib.nasr_las_beam_get_ids(e.h, ids.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))))
+        readback = (time.perf_counter() - t2) * 1e3
+        e.set_profiling(False)
+        phases = {k + '_ms': v for k, v in ph.items()}
+        phases['readback_ms'] = readback
+        phases['profiled_total_ms'] = (t1 - t0) * 1e3
+        return {'T_dec': out['steps'], 'ms_per_decode': round(dt * 1e3, 3), 'phases': {k: round(v, 3) for k, v in phases.items()}}
+
+    res = {'workload': 'las_beam', 'B': B, 'T': T, 'F': F, 'C': C, 'W': W, 'max_steps': S}
+    res.update(timed())
+    if a.lm_order:
+        table = rs.randn(C ** (a.lm_order - 1), C).astype(np.float32)
+        table[:, end_id] -= 20.0
+        e.set_lm((table, a.lm_order), 0.3)
+        res['lm'] = dict(timed(), order=a.lm_order, weight=0.3, table_bytes=int(table.nbytes))
+        e.set_lm(None)
+        res['plain_again'] = timed()
+    print(json.dumps(res))
     e.close()
 
 
