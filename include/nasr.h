@@ -280,6 +280,8 @@ int nasr_resident_frames(nasr_handle h, int64_t* frames); /* sum(seq_len) of the
  * the resident batch - sum(seq_len) when compacted, T x (B rounded up to 16) otherwise. */
 int nasr_set_row_compaction(nasr_handle h, int enabled);
 int nasr_resident_rows(nasr_handle h, int64_t* rows);
+/* B and T of the resident batch (0, 0 without one): what the *_resident calls size their outputs by. */
+int nasr_resident_shape(nasr_handle h, int* B, int* T);
 
 /* TensorFlowNetwork.train fetches mean_ler with every step (networks/tfnetwork.py:188-189): with
  * step-decode enabled nasr_compute_grads / nasr_loss also run the greedy decoder on the step's logits
@@ -315,6 +317,34 @@ int nasr_ctc_beam_search(const float* logits, const int32_t* seq_len, int B, int
 int nasr_ctc_beam_search_lm(const float* logits, const int32_t* seq_len, int B, int Tp, int C, int beam_width,
                             int merge_repeated, const float* lm_logp, const float* lm_eos, int order, int bos_id,
                             float weight, float bonus, int32_t* ids_out, int32_t* lens_out, float* logp_out);
+
+/* ---- CTC forced alignment (not part of the reference, which has no aligner) ------------
+ * For utterance b with F = seq_len[b] logit frames (the frames the CTC loss uses) and its label of length L: the path pi over the
+ * S = 2L+1 states of the extended label (blank = C-1 at even states) that starts in {0,1}, ends in {S-1,S-2}, moves by 0, 1 or
+ * (onto a non-blank state that differs from the one two below) 2 states per frame and maximises the sum of the RAW logits
+ * x(t, l'_pi(t)).  Equal predecessors: stay, then s-1, then s-2; equal end states: S-1.  path_out [B][T'] int32: pi(t) for
+ * t < F, -1 from F on; score_out [B] float64: sum_t (x(t, l'_pi(t)) - logZ(t)), the natural-log probability of the path.
+ * All on the device (max-plus walk with 2-bit back-pointers and the way back, one wave per utterance); two calls give the
+ * same bits.  An infeasible label is NASR_ERR_INFEASIBLE before anything is launched, as for the loss.  LAS handles answer
+ * NASR_ERR_STATE; argument errors are NASR_ERR_ARG.  The alignment has workspaces of its own: the resident batch, the
+ * parameters, the last loss pass's results and the gradients stay as they were (the calls on a batch run the forward pass,
+ * as nasr_forward_resident does).
+ * nasr_ctc_align: upload (with labels), forward, align. */
+int nasr_ctc_align(nasr_handle h, const float* feats, const int32_t* seq_len, const int32_t* labels, const int32_t* label_len,
+                   int B, int T, int Lmax, int32_t* path_out /*[B,T']*/, double* score_out /*[B]*/);
+/* The same on the batch that is resident already, by whichever upload (nasr_upload_batch_audio included: an alignment from
+ * audio never sees features on the host).  NASR_ERR_STATE without a resident batch with labels.  No counterpart in the
+ * reference. */
+int nasr_ctc_align_resident(nasr_handle h, int32_t* path_out, double* score_out);
+/* The same kernels on the caller's logits (host, time-major [T',B,C], as nasr_forward returns them; seq_len in logit
+ * frames), on the handle's device and stream: C is the caller's (>= 2), independent of the handle's model; the resident
+ * batch is not touched.  No counterpart in the reference. */
+int nasr_ctc_align_logits(nasr_handle h, const float* logits, const int32_t* seq_len, const int32_t* labels,
+                          const int32_t* label_len, int B, int Tp, int C, int Lmax, int32_t* path_out, double* score_out);
+/* Host only: 1 when a batch whose longest utterance has F frames and whose longest label has L ids keeps its back-pointers
+ * in LDS, 0 when they go through the handle's global workspace (a function of F and L alone); < 0 on F < 1 or L outside
+ * [0,511].  No counterpart in the reference. */
+int nasr_ctc_align_lds(int F, int L);
 
 /* create_metric (networks/tfnetwork.py:66-70): mean over the batch of Levenshtein(hyp, truth)/len(truth)
  * (tf.edit_distance normalize=True, Appendix A.7).  Host code, no GPU work.  hyp_ids [B,hyp_stride],

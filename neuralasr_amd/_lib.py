@@ -42,6 +42,7 @@ SYMBOLS = [
     'nasr_resample_filter', 'nasr_resample_length', 'nasr_resample', 'nasr_featurize_rates',
     'nasr_upload_batch_audio', 'nasr_stage_batch_audio', 'nasr_forward_resident', 'nasr_loss_resident',
     'nasr_greedy_decode_resident',
+    'nasr_ctc_align', 'nasr_ctc_align_resident', 'nasr_ctc_align_logits', 'nasr_ctc_align_lds', 'nasr_resident_shape',
 ]
 
 
@@ -145,6 +146,7 @@ def load():
         'nasr_get_loss': (c_int, [H, fp]),
         'nasr_resident_frames': (c_int, [H, POINTER(c_int64)]),
         'nasr_resident_rows': (c_int, [H, POINTER(c_int64)]),
+        'nasr_resident_shape': (c_int, [H, POINTER(c_int), POINTER(c_int)]),
         'nasr_set_row_compaction': (c_int, [H, c_int]),
         'nasr_set_profiling': (c_int, [H, c_int]),
         'nasr_get_phase_times': (c_int, [H, POINTER(PhaseTimes)]),
@@ -163,6 +165,10 @@ def load():
         'nasr_forward_resident': (c_int, [H, fp]),
         'nasr_loss_resident': (c_int, [H, fp, fp]),
         'nasr_greedy_decode_resident': (c_int, [H, ip, ip]),
+        'nasr_ctc_align': (c_int, [H, fp, ip, ip, ip, c_int, c_int, c_int, ip, POINTER(c_double)]),
+        'nasr_ctc_align_resident': (c_int, [H, ip, POINTER(c_double)]),
+        'nasr_ctc_align_logits': (c_int, [H, fp, ip, ip, ip, c_int, c_int, c_int, c_int, ip, POINTER(c_double)]),
+        'nasr_ctc_align_lds': (c_int, [c_int, c_int]),
         'nasr_commit_batch': (c_int, [H, c_int]),
         'nasr_discard_batch': (c_int, [H, c_int]),
         'nasr_set_bucket_defer': (c_int, [H, c_int]),

@@ -750,4 +750,214 @@ void launch_greedy(const CtcDims& d, const float* logits, const int* seq_len, in
   hipLaunchKernelGGL(collapse_kernel, dim3(d.B), dim3(64), 0, st, argmax_ws, seq_len, ids, lens, d.Tp, d.B, d.Bp, d.C - 1);
 }
 
+// ------------------------------------------------------------------ (4) forced alignment: the best path
+// The lattice of (2) in the (max, +) semiring over the RAW logits (the per-frame log partition is the same for every state of
+// a frame: it does not move the argmax and stays out of the recursion):
+//   v(s,t) = x(t, l'_s) + max(v(s,t-1), v(s-1,t-1), [v(s-2,t-1) if l'_s != blank, != l'_{s-2}]),  v(s,0) = x(0, l'_s) for s < 2;
+// equal predecessors: s, then s-1, then s-2 (strict > in that order); the end state is S-1 unless S-2 is strictly better.
+// One wave per utterance: the column in registers (KS consecutive states per lane, neighbours over the DPP moves of (2)), the
+// raw emissions gathered a block of 2 to 8 groups of 4 frames ahead, the column maximum subtracted every 4 frames (a sum / maximum of logits:
+// integer logits stay integers, every comparison is exact).  A frame's back-pointers are 2 bits per state, packed per lane
+// into 8 / 16 / 32 bits (KS <= 4 / <= 8 / more), a group of 4 frames into 1 / 2 / 4 words per lane: ONE store per group,
+// into LDS when the whole utterance fits (align_bp_in_lds), else into the handle's global workspace.  The same wave then
+// walks back: 64 frames per turn, the state wave-uniform, a frame's step one LDS read (the global route copies the turn's 16
+// groups into LDS first, all lanes at once); lane j keeps the state of the turn's frame j, so path rows leave coalesced and
+// the fp64 score  sum_t x(t, l'_pi(t)) - logZ(t)  is summed per lane, then over a fixed xor tree: no atomics, same bits
+// every run.
+constexpr int ALIGN_G = 4;                      // frames per group: rescaling period, prefetch distance, back-pointer words
+constexpr int ALIGN_LDS_BYTES = 56 * 1024;      // back-pointers kept in LDS up to this (beside 4 KB of the final column)
+constexpr int align_bpf(int KS) { return KS <= 4 ? 8 : KS <= 8 ? 16 : 32; }   // back-pointer bits per lane and frame
+constexpr int align_words(int KS) { return align_bpf(KS) * ALIGN_G / 32; }    // words per lane and group
+static int align_ks(int L) {                                                 // the instantiation for labels up to L (as the loss's)
+  const int KS = std::max(1, (2 * std::max(L, 0) + 1 + 63) / 64);
+  return KS <= 1 ? 2 : KS <= 8 ? KS : (KS <= 12 ? 12 : 16);
+}
+static int align_groups(int F) { return (std::max(F, 1) - 1 + ALIGN_G - 1) / ALIGN_G; }
+
+bool ctc_align_bp_in_lds(int F, int L) { return (size_t)align_groups(F) * 256 * align_words(align_ks(L)) <= (size_t)ALIGN_LDS_BYTES; }
+size_t ctc_align_ws_words(int B, int F, int L) {
+  return ctc_align_bp_in_lds(F, L) ? 0 : (size_t)B * align_groups(F) * 64 * align_words(align_ks(L));
+}
+
+template <int KS, bool LDSBP>
+__global__ __launch_bounds__(64) void ctc_align_kernel(const float* __restrict__ logits, const float* __restrict__ logz,
+                                                       const int* __restrict__ labels, const int* __restrict__ label_len,
+                                                       const int* __restrict__ seq_len, unsigned* __restrict__ bpws,
+                                                       size_t bp_stride, int* __restrict__ path, double* __restrict__ score,
+                                                       int Tp, int Bp, int Cp, int C, int Lmax) {
+  static_assert(KS >= 2 && KS <= 16, "two states per lane at least (the skip never reaches past the neighbour lane), 32 bits of back-pointers at most");
+  constexpr int G = ALIGN_G, BPF = align_bpf(KS), W = align_words(KS);
+  extern __shared__ __attribute__((aligned(16))) unsigned bplds[];   // LDSBP: every group of the utterance; else the 16 groups of a turn
+  __shared__ float fin[64 * KS];
+  const int b = blockIdx.x, lane = threadIdx.x;
+  const int L = label_len[b], F = seq_len[b], S = 2 * L + 1;
+  const int blank = C - 1;
+  const int* lab = labels + (size_t)b * Lmax;
+  int ext[KS];
+  bool act[KS], skip[KS];
+#pragma unroll
+  for (int i = 0; i < KS; ++i) {
+    const int s = lane * KS + i;
+    act[i] = s < S;
+    ext[i] = (act[i] && (s & 1)) ? lab[s >> 1] : blank;
+    const int e2 = (act[i] && s >= 2 && (s & 1)) ? lab[(s >> 1) - 1] : blank;   // l'_{s-2}
+    skip[i] = act[i] && s >= 2 && ext[i] != blank && ext[i] != e2;
+  }
+  const unsigned rstride = (unsigned)Bp * (unsigned)Cp;     // (the launcher checks T' * Bp * Cp * 4 < 2^32)
+  const float* lg = logits + (size_t)b * Cp;
+  auto gather = [&](int t, float (&x)[KS]) {                // t must be a valid frame (callers clamp); ext is always a class id
+#pragma unroll
+    for (int i = 0; i < KS; ++i) x[i] = ldf(lg, ((unsigned)t * rstride + (unsigned)ext[i]) * 4u);
+  };
+  unsigned* bp = LDSBP ? bplds : bpws + (size_t)b * bp_stride;
+  const int ngroups = (F - 1 + G - 1) / G;
+
+  // ---------------- the walk
+  // The emissions are gathered a BLOCK of NB groups ahead: a group of 4 frames is over in a few hundred cycles here, a
+  // fraction of a gather's way to L2 and back (one group ahead, as in (2): the walk waited for memory once per group).
+  constexpr int NB = KS <= 4 ? 8 : KS <= 8 ? 4 : 2, PF = G * NB;
+  float v[KS], e[PF][KS];
+  gather(0, e[0]);
+#pragma unroll
+  for (int i = 0; i < KS; ++i) v[i] = (act[i] && lane * KS + i < 2) ? e[0][i] : NEG;
+#pragma unroll
+  for (int k = 0; k < PF; ++k) gather(min(1 + k, F - 1), e[k]);
+  for (int g0 = 0; g0 < ngroups; g0 += NB) {
+    float vn[PF][KS];
+#pragma unroll
+    for (int k = 0; k < PF; ++k) gather(min(1 + G * g0 + PF + k, F - 1), vn[k]);
+#pragma unroll
+    for (int sub = 0; sub < NB; ++sub) {
+      const int g = g0 + sub;
+      if (g < ngroups) {
+        const int t0 = 1 + G * g;
+        {
+          float m = v[0];
+#pragma unroll
+          for (int i = 1; i < KS; ++i) m = fmaxf(m, v[i]);
+          m = wave_max_dpp(m);
+#pragma unroll
+          for (int i = 0; i < KS; ++i) v[i] = v[i] > 0.5f * NEG ? v[i] - m : NEG;
+        }
+        unsigned w[W];
+#pragma unroll
+        for (int j = 0; j < W; ++j) w[j] = 0u;
+#pragma unroll
+        for (int k = 0; k < G; ++k) {
+          const bool live = t0 + k < F;
+          const float p1 = lane_up1(v[KS - 1], NEG), p2 = lane_up1(v[KS - 2], NEG);
+          float nv[KS];
+          unsigned code = 0u;
+#pragma unroll
+          for (int i = 0; i < KS; ++i) {
+            const float x1 = (i >= 1) ? v[i >= 1 ? i - 1 : 0] : p1;
+            const float x2r = (i >= 2) ? v[i >= 2 ? i - 2 : 0] : (i == 1 ? p1 : p2);
+            const float x2 = skip[i] ? x2r : NEG;
+            float best = v[i];
+            unsigned c = 0u;
+            if (x1 > best) { best = x1; c = 1u; }
+            if (x2 > best) { best = x2; c = 2u; }
+            nv[i] = act[i] ? best + e[sub * G + k][i] : NEG;   // (no path: NEG + x is NEG again, exactly)
+            code |= c << (2 * i);
+          }
+#pragma unroll
+          for (int i = 0; i < KS; ++i) v[i] = live ? nv[i] : v[i];
+          w[(k * BPF) / 32] |= code << ((k * BPF) % 32);       // (frames past the end leave words nobody reads)
+        }
+#pragma unroll
+        for (int j = 0; j < W; ++j) bp[((size_t)g * 64 + lane) * W + j] = w[j];
+      }
+    }
+    asm volatile("" ::: "memory");
+#pragma unroll
+    for (int k = 0; k < PF; ++k)
+#pragma unroll
+      for (int i = 0; i < KS; ++i) {
+        float x = vn[k][i];
+        asm volatile("" : "+v"(x));                     // the next block's gathers enter hipcc's view here, not above the block
+        e[k][i] = x;
+      }
+  }
+#pragma unroll
+  for (int i = 0; i < KS; ++i) fin[lane * KS + i] = v[i];
+  if (!LDSBP) __threadfence();                          // the walk's words, written by other lanes, are read back below
+  __syncthreads();
+
+  // ---------------- the way back
+  int s = (S > 1 && fin[S - 2] > fin[S - 1]) ? S - 2 : S - 1;
+  s = __builtin_amdgcn_readfirstlane(s);
+  int* prow = path + (size_t)b * Tp;
+  const float* lz = logz + b;
+  double acc = 0.0;
+  auto frame_score = [&](int t, int st) {
+    const int cls = (st & 1) ? lab[st >> 1] : blank;
+    return (double)lg[(size_t)t * rstride + cls] - (double)lz[(size_t)t * Bp];
+  };
+  const int nturns = (F - 1 + 63) / 64;                 // frames 1 .. F-1, 64 (= 16 groups) per turn
+  for (int c = nturns - 1; c >= 0; --c) {
+    const int tlo = 64 * c + 1, thi = min(tlo + 63, F - 1);
+    const int g0 = 16 * c;
+    if (!LDSBP) {
+      const int nw = min(16, ngroups - g0) * 64 * W;
+      __syncthreads();                                  // the turn before is done with the staging words
+      for (int j = lane; j < nw; j += 64) bplds[j] = bp[(size_t)g0 * 64 * W + j];
+      __syncthreads();
+    }
+    const int gbase = LDSBP ? 0 : g0;                   // the group bplds starts at
+    int mine = 0;
+    for (int t = thi; t >= tlo; --t) {
+      if (lane == t - tlo) mine = s;
+      const int g = (t - 1) >> 2, k = (t - 1) & 3;
+      const int ls = s / KS, i = s - ls * KS;
+      const unsigned word = bplds[((g - gbase) * 64 + ls) * W + ((k * BPF) >> 5)];
+      s = max(s - (int)((word >> (((k * BPF) & 31) + 2 * i)) & 3u), 0);
+      s = __builtin_amdgcn_readfirstlane(s);
+    }
+    const int t = tlo + lane;
+    if (t <= thi) {
+      prow[t] = mine;
+      acc += frame_score(t, mine);
+    }
+  }
+  if (lane == 0) {
+    prow[0] = s;
+    acc += frame_score(0, s);
+  }
+  for (int t = F + lane; t < Tp; t += 64) prow[t] = -1;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);   // fixed tree
+  if (lane == 0) score[b] = acc;
+}
+
+int launch_ctc_align(const CtcDims& d, int Fmax, const float* logits, const float* logz, const int* labels, const int* label_len,
+                     const int* seq_len, unsigned* bpws, int* path, double* score, hipStream_t st) {
+  if ((size_t)d.Tp * d.Bp * d.Cp * 4 >= ((size_t)1 << 32)) return -1;
+  const int KS = align_ks(d.Lmax);
+  const bool lds = ctc_align_bp_in_lds(Fmax, d.Lmax);
+  const int W = align_words(KS);
+  const size_t stride = (size_t)align_groups(Fmax) * 64 * W;
+  const size_t shm = lds ? std::max<size_t>(stride * 4, 16) : (size_t)16 * 64 * W * 4;
+  if (!lds && !bpws) return -2;
+#define NASR_AL2(K, LD)                                                                                                     \
+  hipLaunchKernelGGL((ctc_align_kernel<K, LD>), dim3(d.B), dim3(64), shm, st, logits, logz, labels, label_len, seq_len, bpws, \
+                     stride, path, score, d.Tp, d.Bp, d.Cp, d.C, d.Lmax)
+#define NASR_AL(K)                                                                                                          \
+  if (lds) NASR_AL2(K, true);                                                                                               \
+  else NASR_AL2(K, false)
+  switch (KS) {
+    case 2: NASR_AL(2); break;
+    case 3: NASR_AL(3); break;
+    case 4: NASR_AL(4); break;
+    case 5: NASR_AL(5); break;
+    case 6: NASR_AL(6); break;
+    case 7: NASR_AL(7); break;
+    case 8: NASR_AL(8); break;
+    case 12: NASR_AL(12); break;
+    default: NASR_AL(16); break;
+  }
+#undef NASR_AL2
+#undef NASR_AL
+  return 0;
+}
+
 }  // namespace nasr

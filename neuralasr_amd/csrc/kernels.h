@@ -221,6 +221,16 @@ void launch_mean(const float* v, int n, float* out, hipStream_t st);
 void launch_greedy(const CtcDims& d, const float* logits, const int* seq_len, int* argmax_ws, int* ids, int* lens,
                    hipStream_t st);
 
+// forced alignment (ctc.hip (4)): the best path of every utterance through its CTC lattice over the raw logits.
+// path [B][T'] = the state of every frame (-1 from seq_len[b] on), score [B] = sum over the path of x - logZ (fp64).
+// Uses d.Tp, B, Bp, C, Cp, Lmax (the stride of `labels`, >= 1); F = the batch's longest seq_len.  Back-pointers stay in LDS when
+// ctc_align_bp_in_lds(F, Lmax); otherwise bpws must hold ctc_align_ws_words(B, F, Lmax) words.  < 0: the logits are too
+// large for 32-bit offsets (-1), or bpws is missing (-2); nothing is launched then.
+bool ctc_align_bp_in_lds(int F, int L);
+size_t ctc_align_ws_words(int B, int F, int L);
+int launch_ctc_align(const CtcDims& d, int F, const float* logits, const float* logz, const int* labels, const int* label_len,
+                     const int* seq_len, unsigned* bpws, int* path, double* score, hipStream_t st);
+
 // ---- optimiser / reductions (optim.hip) ----
 // Adam's step count and the step size derived from it, on the device: a launch whose `fault` word (device float, or NULL)
 // is non-zero is a no-op AND leaves the count alone, so a void step never enters the bias correction.

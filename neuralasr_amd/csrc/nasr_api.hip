@@ -821,6 +821,117 @@ int nasr_greedy_decode_resident(nasr_handle h, int32_t* ids_out, int32_t* lens_o
   return sync_checked(h);
 }
 
+// ---- forced alignment (ctc.hip (4)) ----------------------------------------------------------------
+// logZ of every row, the walk and the way back over logits [Tp*Bp][Cp] on the handle's stream, in workspaces of the
+// alignment's own; path and score to the host.  Lm: the stride of the label rows (>= 1), F: the longest seq_len.
+static int align_run(nasr_ctx* h, const char* fn, const float* logits, const int32_t* seq_d, const int32_t* labels_d,
+                     const int32_t* lablen_d, int B, int Bp, int Tp, int C, int Cp, int Lm, int F, int32_t* path_out,
+                     double* score_out) {
+  if (2 * Lm + 1 > 64 * 16) return h->fail(NASR_ERR_ARG, std::string(fn) + ": label length > 511 not supported by the CTC lattice kernels");
+  if ((size_t)Tp * Bp * Cp * 4 >= ((size_t)1 << 32))
+    return h->fail(NASR_ERR_ARG, std::string(fn) + ": T' x B x C logits beyond the lattice kernels' 32-bit offsets");
+  const size_t wsw = ctc_align_ws_words(B, F, Lm);
+  bool grew = false;
+  if (!h->al_logz.ensure((size_t)Tp * Bp * 4, &grew) || !h->al_path.ensure((size_t)B * Tp * 4, &grew) ||
+      !h->al_score.ensure((size_t)B * 8, &grew) || (wsw && !h->al_bp.ensure(wsw * 4, &grew)))
+    return h->fail(NASR_ERR_HIP, std::string(fn) + ": hipMalloc of the alignment's workspaces failed");
+  CtcDims d;
+  d.Tp = Tp; d.B = B; d.Bp = Bp; d.C = C; d.Cp = Cp; d.Lmax = Lm; d.KS = 0; d.Tws = 0;   // (no lprobs: logZ only)
+  launch_ctc_logz(d, logits, seq_d, h->al_logz.as<float>(), h->st);
+  if (launch_ctc_align(d, F, logits, h->al_logz.as<float>(), labels_d, lablen_d, seq_d, h->al_bp.as<unsigned>(),
+                       h->al_path.as<int>(), h->al_score.as<double>(), h->st) != 0)
+    return h->fail(NASR_ERR_ARG, std::string(fn) + ": the alignment kernel refused the shape");
+  HIPCHK(h, hipGetLastError());
+  HIPCHK(h, hipMemcpyAsync(path_out, h->al_path.p, (size_t)B * Tp * 4, hipMemcpyDeviceToHost, h->st));
+  HIPCHK(h, hipMemcpyAsync(score_out, h->al_score.p, (size_t)B * 8, hipMemcpyDeviceToHost, h->st));
+  return sync_checked(h);
+}
+
+int nasr_ctc_align_lds(int F, int L) {
+  if (F < 1 || L < 0 || L > 511) return NASR_ERR_ARG;
+  return ctc_align_bp_in_lds(F, std::max(L, 1)) ? 1 : 0;
+}
+
+int nasr_ctc_align_resident(nasr_handle h, int32_t* path_out, double* score_out) {
+  MODEL_CALL(h);
+  if (!h) return NASR_ERR_ARG;
+  if (h->family == Family::Las) return h->fail(NASR_ERR_STATE, "nasr_ctc_align_resident: a LAS handle has no CTC lattice");
+  if (!path_out || !score_out) return h->fail(NASR_ERR_ARG, "nasr_ctc_align_resident: null output buffer");
+  if (!h->resident || !h->cur || !h->cur->has_labels)
+    return h->fail(NASR_ERR_STATE, "nasr_ctc_align_resident: no resident batch with labels");
+  const int rc = forward(h);
+  if (rc) return rc;
+  int F = 1;
+  for (int b = 0; b < h->B; ++b) F = std::max(F, (int)h->h_seq[b]);
+  return align_run(h, "nasr_ctc_align_resident", h->logits.as<float>(), h->seq_p, h->labels_p, h->lablen_p, h->B, h->Bp, h->Tp,
+                   h->C, h->Cp, std::max(h->Lmax, 1), F, path_out, score_out);
+}
+
+int nasr_ctc_align(nasr_handle h, const float* feats, const int32_t* seq_len, const int32_t* labels, const int32_t* label_len,
+                   int B, int T, int Lmax, int32_t* path_out, double* score_out) {
+  MODEL_CALL(h);
+  if (!h) return NASR_ERR_ARG;
+  if (h->family == Family::Las) return h->fail(NASR_ERR_STATE, "nasr_ctc_align: a LAS handle has no CTC lattice");
+  if (!labels || !path_out || !score_out) return h->fail(NASR_ERR_ARG, "nasr_ctc_align needs labels and both output buffers");
+  const int rc = upload(h, feats, seq_len, labels, label_len, B, T, Lmax);
+  if (rc) return rc;
+  return nasr_ctc_align_resident(h, path_out, score_out);
+}
+
+int nasr_ctc_align_logits(nasr_handle h, const float* logits, const int32_t* seq_len, const int32_t* labels,
+                          const int32_t* label_len, int B, int Tp, int C, int Lmax, int32_t* path_out, double* score_out) {
+  MODEL_CALL(h);
+  if (!h) return NASR_ERR_ARG;
+  if (h->family == Family::Las) return h->fail(NASR_ERR_STATE, "nasr_ctc_align_logits: a LAS handle has no CTC lattice");
+  if (!logits || !seq_len || !label_len || (Lmax > 0 && !labels) || !path_out || !score_out)
+    return h->fail(NASR_ERR_ARG, "nasr_ctc_align_logits: null buffer");
+  if (C < 2) return h->fail(NASR_ERR_ARG, "nasr_ctc_align_logits: need num_classes >= 2 (a label and the blank)");
+  if (Lmax < 0) return h->fail(NASR_ERR_ARG, "nasr_ctc_align_logits: Lmax < 0");
+  if (Lmax > 511) return h->fail(NASR_ERR_ARG, "nasr_ctc_align_logits: label length > 511 not supported by the CTC lattice kernels");
+  static const int32_t no_label = 0;
+  int rc = validate_batch(h, seq_len, Lmax > 0 ? labels : &no_label, label_len, B, Tp, Lmax, C);   // before anything is launched
+  if (rc) return rc;
+  const int Bp = rup(B, 16), Cp = rup(C, 32), Lm = std::max(Lmax, 1);
+  if ((size_t)Tp * Bp * Cp * 4 >= ((size_t)1 << 32))
+    return h->fail(NASR_ERR_ARG, "nasr_ctc_align_logits: T' x B x C logits beyond the lattice kernels' 32-bit offsets");
+  HIPCHK(h, hipSetDevice(h->device));
+  // the caller's logits in the kernels' layout (rows t*Bp + b of Cp floats), and seq [Bp] | lablen [Bp] | labels [B][Lm]
+  std::vector<float> lg((size_t)Tp * Bp * Cp, 0.f);
+  for (int t = 0; t < Tp; ++t)
+    for (int b = 0; b < B; ++b)
+      memcpy(lg.data() + ((size_t)t * Bp + b) * Cp, logits + ((size_t)t * B + b) * C, (size_t)C * 4);
+  std::vector<int32_t> meta((size_t)2 * Bp + (size_t)B * Lm, 0);
+  int F = 1;
+  for (int b = 0; b < B; ++b) {
+    meta[b] = seq_len[b];
+    meta[Bp + b] = label_len[b];
+    F = std::max(F, (int)seq_len[b]);
+    if (Lmax > 0) memcpy(meta.data() + 2 * Bp + (size_t)b * Lm, labels + (size_t)b * Lmax, (size_t)Lmax * 4);
+  }
+  bool grew = false;
+  if (!h->al_logits.ensure(lg.size() * 4, &grew) || !h->al_meta.ensure(meta.size() * 4, &grew))
+    return h->fail(NASR_ERR_HIP, "nasr_ctc_align_logits: hipMalloc of the alignment's workspaces failed");
+  // from the first copy on every way out passes a stream synchronise: the copies read lg and meta
+  auto run = [&]() -> int {
+    HIPCHK(h, hipMemcpyAsync(h->al_logits.p, lg.data(), lg.size() * 4, hipMemcpyHostToDevice, h->st));
+    HIPCHK(h, hipMemcpyAsync(h->al_meta.p, meta.data(), meta.size() * 4, hipMemcpyHostToDevice, h->st));
+    const int32_t* md = h->al_meta.as<int32_t>();
+    return align_run(h, "nasr_ctc_align_logits", h->al_logits.as<float>(), md, md + 2 * Bp, md + Bp, B, Bp, Tp, C, Cp, Lm, F,
+                     path_out, score_out);
+  };
+  rc = run();
+  if (rc) (void)hipStreamSynchronize(h->st);
+  return rc;
+}
+
+int nasr_resident_shape(nasr_handle h, int* B, int* T) {
+  MODEL_CALL(h);
+  if (!h || !B || !T) return NASR_ERR_ARG;
+  *B = h->resident ? h->B : 0;
+  *T = h->resident ? h->T : 0;
+  return NASR_OK;
+}
+
 int nasr_set_step_decode(nasr_handle h, int enabled) {
   MODEL_CALL(h);
   if (!h) return NASR_ERR_ARG;

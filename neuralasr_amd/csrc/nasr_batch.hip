@@ -109,19 +109,21 @@ int ensure_shape(nasr_ctx* h, int B, int T, int Lmax) {
 }
 
 int validate_batch(nasr_ctx* h, const int32_t* seq_len, const int32_t* labels, const int32_t* label_len, int B, int T,
-                   int Lmax) {
+                   int Lmax, int num_classes) {
+  const bool las = !num_classes && h->family == Family::Las;
+  const int C = num_classes ? num_classes : h->C;
   if (B < 1 || B > 64) return h->fail(NASR_ERR_ARG, "per-GPU batch must be in [1,64]");
   if (T < 1) return h->fail(NASR_ERR_ARG, "T must be >= 1");
   for (int b = 0; b < B; ++b) {
     if (seq_len[b] < 1 || seq_len[b] > T)
       return h->fail(NASR_ERR_ARG, "seq_len[" + std::to_string(b) + "] out of [1,T]");
     if (!labels) continue;
-    if (h->family == Family::Las) {   // dense labels: every entry is fed to the decoder, any class is a label, no CTC feasibility
+    if (las) {   // dense labels: every entry is fed to the decoder, any class is a label, no CTC feasibility
       if (label_len[b] < 0 || label_len[b] > Lmax)
         return h->fail(NASR_ERR_ARG, "label_len[" + std::to_string(b) + "] out of [0,Lmax]");
       for (int i = 0; i < Lmax; ++i) {
         const int v = labels[(size_t)b * Lmax + i];
-        if (v < 0 || v >= h->C) return h->fail(NASR_ERR_ARG, "label id out of [0, num_classes-1]");
+        if (v < 0 || v >= C) return h->fail(NASR_ERR_ARG, "label id out of [0, num_classes-1]");
       }
       continue;
     }
@@ -130,7 +132,7 @@ int validate_batch(nasr_ctx* h, const int32_t* seq_len, const int32_t* labels, c
     int rep = 0;
     for (int i = 0; i < L; ++i) {
       const int v = labels[(size_t)b * Lmax + i];
-      if (v < 0 || v >= h->C - 1)
+      if (v < 0 || v >= C - 1)
         return h->fail(NASR_ERR_ARG, "label id out of [0, num_classes-2] (blank = num_classes-1 is not a label)");
       if (i > 0 && v == labels[(size_t)b * Lmax + i - 1]) ++rep;
     }

@@ -368,6 +368,9 @@ struct nasr_ctx {
   DevBuf ctcprobs, ctckexp;                  // emission rows and column offsets of the CTC lattice (ctc.hip (2b))
   DevBuf seqbuf, X0, logits, logz, alpha, beta, aoff, boff, logp, nll, loss, slabs, csws, amax, ids, lens,
       stage;
+  // forced alignment (nasr_ctc_align*): workspaces of its own, sized at the first call that needs them - its logZ rows, the
+  // back-pointers that do not fit in LDS, path and score; and for nasr_ctc_align_logits the caller's logits and labels
+  DevBuf al_logz, al_bp, al_path, al_score, al_logits, al_meta;
   std::vector<DevBuf> gates, outb, cbuf;
   DevBuf dout, hstate, partial, dcstate, dgbuf;   // shared by the layers (a layer's backward pass is over before the next starts)
 
@@ -497,7 +500,9 @@ int ensure_shape(nasr_ctx* h, int B, int T, int Lmax);
 // the logits and what the CTC lattice, its loss and the greedy decoder work in (T frames, Tp logit frames); returns the
 // lattice kernel's instantiation for labels up to Lmax (h->KS), or the code of a failure (< 0)
 int ensure_ctc_buffers(nasr_ctx* h, int B, int Bp, int T, int Tp, int Lmax, bool* grew);
-int validate_batch(nasr_ctx* h, const int32_t* seq_len, const int32_t* labels, const int32_t* label_len, int B, int T, int Lmax);
+// num_classes: 0 = the handle's (and its family's rules); > 0: CTC labels over that many classes (nasr_ctc_align_logits)
+int validate_batch(nasr_ctx* h, const int32_t* seq_len, const int32_t* labels, const int32_t* label_len, int B, int T, int Lmax,
+                   int num_classes = 0);
 bool pinned_ensure(Pinned<void>& p, size_t* cap, size_t bytes);
 void slot_set_state(nasr_ctx* h, BatchSlot* s, int st);
 int slot_commit(nasr_ctx* h, BatchSlot* s);

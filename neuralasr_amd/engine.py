@@ -2,7 +2,7 @@
 `Network` plugin classes (neuralasr_amd/networks) and bench.py sit on; all arithmetic happens in the HIP
 library behind include/nasr.h."""
 import ctypes
-from ctypes import POINTER, byref, c_char, c_float, c_int32, c_int64, c_uint32, c_void_p
+from ctypes import POINTER, byref, c_char, c_double, c_float, c_int32, c_int64, c_uint32, c_void_p
 
 import numpy as np
 
@@ -306,6 +306,54 @@ class Engine:
         lens = np.zeros(B, np.int32)
         self._ck(self.lib.nasr_greedy_decode_resident(self.h, _ip(ids), _ip(lens)))
         return [ids[b, :lens[b]].tolist() for b in range(B)]
+
+    # ------------------------------------------------------------------ forced alignment
+    def align(self, feats, seq_len, labels, label_len):
+        """(path int32 [B,T'], score float64 [B]): every utterance's best path through the CTC lattice of its label -
+        path[b][t] is the state of the extended label at logit frame t (-1 from seq_len[b] on), score[b] the path's
+        log-probability.  Upload, forward and alignment, all on the device."""
+        feats, seq, labels, ll, B, T, Lmax = self._batch(feats, seq_len, labels, label_len)
+        if feats.shape[2] != self.cfg.feature_size:
+            raise ValueError(f'feature size {feats.shape[2]} != configured {self.cfg.feature_size}')
+        path = np.empty((B, self.logit_frames(T)), np.int32)
+        score = np.empty(B, np.float64)
+        self._ck(self.lib.nasr_ctc_align(self.h, _fp(feats), _ip(seq), _ip(labels), _ip(ll), B, T, Lmax, _ip(path),
+                                         score.ctypes.data_as(POINTER(c_double))))
+        return path, score
+
+    def align_resident(self, B, T):
+        """align() on the resident batch and its labels (whichever upload put them there); B and T must be that batch's"""
+        rb, rt = ctypes.c_int(), ctypes.c_int()
+        self._ck(self.lib.nasr_resident_shape(self.h, byref(rb), byref(rt)))
+        if (rb.value, rt.value) != (int(B), int(T)):
+            raise ValueError('align_resident(B=%d, T=%d): the resident batch has B=%d, T=%d' % (B, T, rb.value, rt.value))
+        path = np.empty((B, self.logit_frames(T)), np.int32)
+        score = np.empty(B, np.float64)
+        self._ck(self.lib.nasr_ctc_align_resident(self.h, _ip(path), score.ctypes.data_as(POINTER(c_double))))
+        return path, score
+
+    def align_logits(self, logits_tm, seq_len, labels, label_len):
+        """The alignment kernels on the caller's logits, time-major [T',B,C] (blank = C-1; seq_len in logit frames),
+        whatever this engine's model is; the resident batch is not touched."""
+        logits = _f32(logits_tm)
+        assert logits.ndim == 3, 'logits must be [T\',B,C]'
+        Tp, B, C = logits.shape
+        seq = _i32(np.asarray([int(x) for x in seq_len])).ravel()
+        ll = _i32(np.asarray([int(x) for x in label_len])).ravel()
+        labels = _i32(labels).reshape(B, -1)
+        assert seq.size == B and ll.size == B
+        path = np.empty((B, Tp), np.int32)
+        score = np.empty(B, np.float64)
+        self._ck(self.lib.nasr_ctc_align_logits(self.h, _fp(logits), _ip(seq), _ip(labels), _ip(ll), B, Tp, C,
+                                                labels.shape[1], _ip(path), score.ctypes.data_as(POINTER(c_double))))
+        return path, score
+
+    def align_in_lds(self, F, L):
+        """True when a batch with F frames and labels up to L ids keeps its back-pointers in LDS (else: global workspace)"""
+        rc = int(self.lib.nasr_ctc_align_lds(int(F), int(L)))
+        if rc < 0:
+            raise ValueError('align_in_lds: F >= 1 and 0 <= L <= 511')
+        return bool(rc)
 
     def commit_batch(self, ticket):
         self._ck(self.lib.nasr_commit_batch(self.h, int(ticket)))
@@ -659,6 +707,11 @@ class LasEngine(Engine):
     def upload_batch_audio(self, featurizer, audios, labels, label_len, rates=None):
         self._BU = (len(audios), 0 if labels is None else np.asarray(labels).reshape(len(audios), -1).shape[1])
         return Engine.upload_batch_audio(self, featurizer, audios, labels, label_len, rates)
+
+    def align(self, *a, **k):
+        raise NotImplementedError('forced alignment walks a CTC lattice; the LAS network has none')
+
+    align_resident = align_logits = align
 
     def las_forward(self, feats, seq_len, labels, label_len, sample=False):
         """logits [B, U, C] of a decoder pass (sample: scheduled sampling at the handle's probability); loss via get_loss."""

@@ -543,6 +543,26 @@ class HipNetwork(Network):
         hyps = self._decode(mfccs, seq_len, self.decoder, self.language_model())
         return np.asarray([i for h in hyps for i in h], dtype=np.int64)
 
+    def align(self, mfccs, labels, seq_len, labels_len):
+        """Forced alignment: for every utterance (score, [(symbol id, first frame, last frame)] in label
+        order) - the log-probability of its best CTC path and the logit frames that path spends on each label (blank
+        frames belong to no symbol).  Walk and traceback run on the GPU."""
+        from ..align import spans
+        self._settle()
+        labels = np.asarray(labels, dtype=np.int32).reshape(len(seq_len), -1)
+
+        def run():
+            if isinstance(mfccs, AudioBatch):
+                self._upload_audio(mfccs, labels, labels_len)
+                return self.engine.align_resident(len(mfccs), mfccs.shape[1])
+            return self.engine.align(mfccs, seq_len, labels, labels_len)
+        path, score = self._retry_aborted(run)
+        return [(float(score[b]), spans(path[b], labels[b, :int(labels_len[b])])) for b in range(len(seq_len))]
+
+    def align_audio(self, audios, rates, labels, labels_len):
+        b = self.audio_batch(audios, rates)
+        return self.align(b, labels, b.seq_len, labels_len)
+
     # ------------------------------------------------------------------ the same four calls on audio
     # (utils.py:24-31 made on the device per batch instead of pickled ahead: the features never reach the host)
     def train_audio(self, audios, rates, labels, labels_len):

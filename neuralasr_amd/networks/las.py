@@ -267,3 +267,10 @@ class LAS(HipNetwork):
         """the first utterance's model: beam 0 of the gathered ids [T_dec]"""
         out = self._beam_search(mfccs, seq_len, False)
         return out['predicted_ids'][0, :, 0].astype(np.int64)
+
+    def align(self, mfccs, labels, seq_len, labels_len):
+        raise NotImplementedError('forced alignment walks the CTC lattice of a label; the LAS network has no CTC output '
+                                  '(its attention weights are not an alignment this package defines)')
+
+    def align_audio(self, audios, rates, labels, labels_len):
+        return self.align(None, labels, None, labels_len)

@@ -27,16 +27,21 @@ BATCH_FILES = 64          # utterances featurised per GPU call
 READ_THREADS = 4
 
 
+def label_ngrams(config, clean_transcription):
+    """The label_context n-grams of a transcription padded with start_marker (or '^'), one per character."""
+    num_context = config.label_context
+    padded_str = (config.start_marker if config.start_marker else '^') * num_context
+    padded_transcript = padded_str + clean_transcription + padded_str
+    return [padded_transcript[i:i + (2 * num_context + 1)] for i in range(len(padded_transcript) - num_context * 2)]
+
+
 def update_symbols(config, clean_transcription):
     """Label ids of a transcription: label_context n-grams over the transcription padded with start_marker (or '^'),
     between the optional start and end markers; new n-grams enter the symbol table (reference: preprocess_mfcc.py:18-30)."""
     sym = config.symbols
     labels = [sym.get_id(config.start_marker)] if config.start_marker else []
-    num_context = config.label_context
-    padded_str = (config.start_marker if config.start_marker else '^') * num_context
-    padded_transcript = padded_str + clean_transcription + padded_str
-    for i in range(len(padded_transcript) - num_context * 2):
-        labels.append(sym.insert_sym(padded_transcript[i:i + (2 * num_context + 1)]))
+    for gram in label_ngrams(config, clean_transcription):
+        labels.append(sym.insert_sym(gram))
     if config.end_marker:
         labels.append(sym.get_id(config.end_marker))
     return np.asarray(labels, dtype=np.int32)
