@@ -191,6 +191,37 @@ int nasr_upload_batch_audio(nasr_handle model, nasr_handle featurizer, const flo
 int nasr_stage_batch_audio(nasr_handle model, nasr_handle featurizer, const float* audio, const int64_t* offsets,
                            const int32_t* rates, const int32_t* labels, const int32_t* label_len, int B, int Lmax,
                            int32_t* seq_len_out, int* T_out, int* ticket);
+/* (No counterpart in the reference: its only augmentation is rand_shift, dataset.py:23-31.)  SpecAugment masks for a
+ * batch in the centre form: utterance b's time mask k zeroes the normalised centre frames [t0, t0 + tw), its frequency
+ * mask k the columns [f0, f0 + fw) of every static_width-wide block of a frame ([static | delta | delta-delta]: column
+ * j of each block derives from filter j).  0 is the utterance's own mean after the whole-utterance normalisation, which
+ * is computed before masking.  The context stacking runs on the masked frames: a masked frame is masked in every window
+ * it appears in, the pad values are never masked.  A mask of width 0 is no mask. */
+#define NASR_AUG_MAX_MASKS 8
+typedef struct {
+  int32_t static_width;      /* width of the frame's static block; must divide the frame width */
+  int32_t n_time, n_freq;    /* masks per utterance, each 0..NASR_AUG_MAX_MASKS */
+  const int32_t* time_mask;  /* [B][n_time][2]: first frame, width (0 = no mask) */
+  const int32_t* freq_mask;  /* [B][n_freq][2]: first static column, width */
+} nasr_batch_aug;
+/* (No counterpart in the reference.)  nasr_upload_batch_context with the masks of `aug` applied on the device, inside the
+ * kernel that stacks the context: the masks travel with the batch's other integer arrays, there is no extra pass, buffer
+ * or launch.  The result is bitwise what nasr_upload_batch gives for the stacked array of the masked centre frames.
+ * aug == NULL, or masks that all have width 0: nasr_upload_batch_context itself.  NASR_ERR_ARG, before anything is
+ * launched and with the resident batch kept, names the utterance and the mask: t0 < 0, tw < 0, t0 + tw > seq_len[b];
+ * f0 < 0, fw < 0, f0 + fw > static_width; a count outside 0..NASR_AUG_MAX_MASKS; static_width not a divisor of numcep. */
+int nasr_upload_batch_context_aug(nasr_handle h, const float* centre, const float* pad_value, int numcontext, int numcep,
+                                  const int32_t* seq_len, const int32_t* labels, const int32_t* label_len, int B, int T,
+                                  int Lmax, const nasr_batch_aug* aug);
+/* (No counterpart in the reference.)  nasr_upload_batch_audio / nasr_stage_batch_audio with the masks of `aug`: the same
+ * rules, checked against the seq_len the call itself computes; static_width must be the featurizer's numcep (the
+ * width of the static block of its frames).  aug == NULL: the plain call. */
+int nasr_upload_batch_audio_aug(nasr_handle model, nasr_handle featurizer, const float* audio, const int64_t* offsets,
+                                const int32_t* rates, const int32_t* labels, const int32_t* label_len, int B, int Lmax,
+                                int32_t* seq_len_out, int* T_out, const nasr_batch_aug* aug);
+int nasr_stage_batch_audio_aug(nasr_handle model, nasr_handle featurizer, const float* audio, const int64_t* offsets,
+                               const int32_t* rates, const int32_t* labels, const int32_t* label_len, int B, int Lmax,
+                               int32_t* seq_len_out, int* T_out, const nasr_batch_aug* aug, int* ticket);
 int nasr_commit_batch(nasr_handle h, int ticket);
 int nasr_discard_batch(nasr_handle h, int ticket);   /* give a staged batch's slot back unused */
 /* nasr_forward / nasr_loss / nasr_greedy_decode on the batch that is resident already (nasr_upload_batch*,

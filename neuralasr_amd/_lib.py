@@ -42,6 +42,7 @@ SYMBOLS = [
     'nasr_resample_filter', 'nasr_resample_length', 'nasr_resample', 'nasr_featurize_rates',
     'nasr_upload_batch_audio', 'nasr_stage_batch_audio', 'nasr_forward_resident', 'nasr_loss_resident',
     'nasr_greedy_decode_resident',
+    'nasr_upload_batch_context_aug', 'nasr_upload_batch_audio_aug', 'nasr_stage_batch_audio_aug',
     'nasr_ctc_align', 'nasr_ctc_align_resident', 'nasr_ctc_align_logits', 'nasr_ctc_align_lds', 'nasr_resident_shape',
 ]
 
@@ -71,6 +72,14 @@ class MfccCfg(Structure):
     _fields_ = [('samplerate', c_int32), ('numcep', c_int32), ('numcontext', c_int32), ('nfilt', c_int32),
                 ('nfft', c_int32), ('winlen', c_double), ('winstep', c_double), ('preemph', c_float),
                 ('ceplifter', c_int32), ('append_energy', c_int32), ('kind', c_int32), ('deltas', c_int32)]
+
+
+AUG_MAX_MASKS = 8      # NASR_AUG_MAX_MASKS
+
+
+class BatchAug(Structure):
+    _fields_ = [('static_width', c_int32), ('n_time', c_int32), ('n_freq', c_int32),
+                ('time_mask', POINTER(c_int32)), ('freq_mask', POINTER(c_int32))]
 
 
 class PhaseTimes(Structure):
@@ -162,6 +171,11 @@ def load():
         'nasr_upload_batch_audio': (c_int, [H, H, fp, POINTER(c_int64), ip, ip, ip, c_int, c_int, ip, POINTER(c_int)]),
         'nasr_stage_batch_audio': (c_int, [H, H, fp, POINTER(c_int64), ip, ip, ip, c_int, c_int, ip, POINTER(c_int),
                                            POINTER(c_int)]),
+        'nasr_upload_batch_context_aug': (c_int, [H, fp, fp, c_int, c_int, ip, ip, ip, c_int, c_int, c_int, POINTER(BatchAug)]),
+        'nasr_upload_batch_audio_aug': (c_int, [H, H, fp, POINTER(c_int64), ip, ip, ip, c_int, c_int, ip, POINTER(c_int),
+                                                POINTER(BatchAug)]),
+        'nasr_stage_batch_audio_aug': (c_int, [H, H, fp, POINTER(c_int64), ip, ip, ip, c_int, c_int, ip, POINTER(c_int),
+                                               POINTER(BatchAug), POINTER(c_int)]),
         'nasr_forward_resident': (c_int, [H, fp]),
         'nasr_loss_resident': (c_int, [H, fp, fp]),
         'nasr_greedy_decode_resident': (c_int, [H, ip, ip]),

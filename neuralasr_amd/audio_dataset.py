@@ -85,8 +85,11 @@ class AudioDataSet:
         self.padding_id = config.symbols.get_padding_id()
         known = config.symbols.counter
         self.X = []                                   # (wav, labels) in DataSet's order
+        self.chars = {}                               # wav -> characters of its cleaned transcription (kept_rows' filter)
+        self.last_chars = []                          # those of the batch get_next_batch returned last
         for wav, _, clean in kept_sets(filename, config)[0 if which == 'train' else 1]:
             self.X.append((wav, update_symbols(config, clean)))
+            self.chars[wav] = len(clean)
         if config.symbols.counter != known:
             raise ValueError('%s holds symbols that %s does not: run preprocess_mfcc, or remove the symbol file to have '
                              'it rebuilt' % (filename, config.sym_file))
@@ -119,6 +122,7 @@ class AudioDataSet:
             self.index += 1
         with ThreadPoolExecutor(max_workers=READ_THREADS) as ex:
             items = list(ex.map(self.load, picks))
+        self.last_chars = [self.chars[wav] for wav, _ in picks]
         max_label = max(n for _, _, _, n in items)
         labels = np.full((len(items), max_label), self.padding_id, dtype=np.int32)
         for i, (_, _, l, n) in enumerate(items):
@@ -136,10 +140,15 @@ class AudioDataSet:
 
 
 class AudioFeed:
-    """An AudioDataSet as train_model reads a DataSet: every batch as (features.AudioBatch, labels, seq_len, labels_len)."""
+    """An AudioDataSet as train_model reads a DataSet: every batch as (features.AudioBatch, labels, seq_len, labels_len).
+    With an `augmenter` (augment.Augmenter; the training feed of `train --from-audio` only) every batch is drawn speed
+    factors and SpecAugment masks under the counter of the global step it will train: config.start_step + the number of
+    batches handed out, this one included."""
 
-    def __init__(self, dataset):
+    def __init__(self, dataset, augmenter=None):
         self.dataset = dataset
+        self.augmenter = augmenter
+        self.handed_out = 0
 
     def __getattr__(self, name):
         return getattr(self.dataset, name)
@@ -148,5 +157,9 @@ class AudioFeed:
         from .features import AudioBatch
         audios, rates, labels, labels_len = self.dataset.get_next_batch()
         cfg = self.dataset.config
-        b = AudioBatch(cfg.samplerate, audios, rates, cfg.feature_size)
+        self.handed_out += 1
+        if self.augmenter is not None:
+            b = self.augmenter.batch(cfg.start_step + self.handed_out, audios, rates, self.dataset.last_chars)
+        else:
+            b = AudioBatch(cfg.samplerate, audios, rates, cfg.feature_size)
         return b, labels, b.seq_len, labels_len

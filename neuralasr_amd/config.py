@@ -6,7 +6,12 @@ network loader.  Two optional [Parameters] keys choose the features the GPU fron
 (2*numcontext+1)*frame_width.  `network=networks.bilstm_ctc_net.BiLstmCTCNet` resolves to the HIP implementation in
 neuralasr_amd.networks when the reference's TensorFlow package of that name is not importable.  Three more optional
 [Parameters] keys fuse an n-gram model into the beam searches of evaluate / decode (lm.py): lm_file, lm_weight (default 0)
-and lm_bonus (per emitted symbol, CTC only, default 0); without lm_file nothing changes, and training never reads them."""
+and lm_bonus (per emitted symbol, CTC only, default 0); without lm_file nothing changes, and training never reads them.
+Seven more optional [Parameters] keys switch on the augmentation of `train --from-audio` (augment.py; the
+reference has none but rand_shift): spec_time_masks / spec_freq_masks (masks per utterance, 0..8, default 0),
+spec_time_width / spec_freq_width (largest width in frames / static columns, default 0), spec_time_ratio (largest time
+mask as a share of the utterance, default 1.0), speed_perturb (comma-separated factors, each in (0.5, 2.0), default none)
+and augment_seed (default 0); without them nothing changes."""
 import importlib
 from configparser import ConfigParser, ExtendedInterpolation
 
@@ -64,6 +69,7 @@ class Config(object):
         self.lm_file = par['lm_file'].strip() if 'lm_file' in par else None
         self.lm_weight = float(par['lm_weight']) if 'lm_weight' in par else 0.0
         self.lm_bonus = float(par['lm_bonus']) if 'lm_bonus' in par else 0.0
+        self._read_augment(par, configfile)
         # the configured batch is per GPU (reference: config.py:35-36)
         self.batch_size *= self.num_gpus if self.num_gpus > 0 else 1
         self.symbols = Symbols(self.label_context, self.sym_file) if isTraining else Symbols(self.label_context)
@@ -77,6 +83,39 @@ class Config(object):
         self.test_input = test['input'] if 'input' in test else None
         if self.test_input is None and not self.train_input:
             raise ValueError("Missing 'test_input' in configuration file: " + configfile)
+
+    def _read_augment(self, par, configfile):
+        def number(key, kind, default, lo, hi, what):
+            if key not in par:
+                return default
+            try:
+                v = kind(par[key].strip())
+            except ValueError:
+                v = None
+            if v is None or not lo <= v <= hi:
+                raise ValueError("'%s' must be %s, not %r, in %s" % (key, what, par[key], configfile))
+            return v
+        big = 1 << 62
+        self.spec_time_masks = number('spec_time_masks', int, 0, 0, 8, 'an integer in [0,8]')
+        self.spec_time_width = number('spec_time_width', int, 0, 0, big, 'an integer >= 0')
+        self.spec_time_ratio = number('spec_time_ratio', float, 1.0, 0.0, 1.0, 'a number in [0,1]')
+        self.spec_freq_masks = number('spec_freq_masks', int, 0, 0, 8, 'an integer in [0,8]')
+        self.spec_freq_width = number('spec_freq_width', int, 0, 0, big, 'an integer >= 0')
+        self.augment_seed = number('augment_seed', int, 0, 0, (1 << 64) - 1, 'an integer in [0, 2^64)')
+        self.speed_perturb = ()
+        if 'speed_perturb' in par:
+            try:
+                self.speed_perturb = tuple(float(x) for x in par['speed_perturb'].split(','))
+            except ValueError:
+                self.speed_perturb = ()
+            if not self.speed_perturb or not all(0.5 < f < 2.0 for f in self.speed_perturb):
+                raise ValueError("'speed_perturb' must be comma-separated factors, each in (0.5, 2.0), not %r, in %s"
+                                 % (par['speed_perturb'], configfile))
+
+    @property
+    def augment_on(self):
+        """some augmentation key is switched on"""
+        return self.spec_time_masks > 0 or self.spec_freq_masks > 0 or len(self.speed_perturb) > 0
 
     def load_network(self, fortraining=False):
         return network_class(self.network)(self, fortraining=fortraining)

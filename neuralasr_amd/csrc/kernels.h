@@ -107,6 +107,13 @@ struct LstmDims {
 void launch_pack_feats(const float* feats_bm, float* X0, int B, int Bp, int T, int F, int Fp, hipStream_t st);
 void launch_expand_context(const float* centre, const float* pad, const int* seq_len, float* X0, int B, int Bp, int T,
                            int ctx, int ncep, int Fp, hipStream_t st);
+// The same with SpecAugment masks on the centre frames (no counterpart in the reference): masks [B][nm] of
+// {t0, tw, f0, fw}, utterance b's k-th time mask over frames [t0, t0 + tw) and its k-th frequency mask over columns
+// [f0, f0 + fw) of each static_width-wide block of a frame; width 0 = no mask.  Masked centre values are 0, pads stay.
+// Uses 2*ctx+1 + ncep bytes of dynamic LDS.
+void launch_expand_context_masked(const float* centre, const float* pad, const int* seq_len, const int* masks, int nm,
+                                  int static_width, float* X0, int B, int Bp, int T, int ctx, int ncep, int Fp,
+                                  hipStream_t st);
 // repack canonical U [Hp][N4] of every (layer,dir) into the forward / backward MFMA B-operand images
 void launch_repack_u(const float* U, float* Uf, float* Ub, int Hp, hipStream_t st);
 void launch_lstm_fwd_step(const LstmDims& dm, int s, const float* Uf, const float* hin, float* hout, float* gates,

@@ -85,6 +85,60 @@ void launch_expand_context(const float* centre, const float* pad, const int* seq
                      ncep, Fp);
 }
 
+// expand_context_kernel with SpecAugment masks (the reference has no augmentation but rand_shift): the
+// masks are applied to the utterance's normalised centre frames - 0 is their mean - and include_context runs on the
+// result, so a masked frame is masked in every window it appears in and the pads stay what they were.  masks [B][nm]:
+// {t0, tw, f0, fw}, validated on the host to lie inside the utterance and the static block.  The row's workgroup
+// decides one flag per window and one per column (the mask list is walked nw + ncep times, not once per element) and
+// keeps them in LDS: flag [nw] windows | [ncep] columns.
+__global__ __launch_bounds__(256) void expand_context_masked_kernel(const float* __restrict__ centre,
+                                                                    const float* __restrict__ pad,
+                                                                    const int* __restrict__ seq_len,
+                                                                    const int4* __restrict__ masks, int nm, int sw,
+                                                                    float* __restrict__ x, int B, int Bp, int T, int ctx,
+                                                                    int ncep, int Fp) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char flag[];
+  const int r = blockIdx.x;  // t*Bp + b
+  const int t = r / Bp, b = r % Bp;
+  float* dst = x + (size_t)r * Fp;
+  const int len = b < B ? seq_len[b] : 0;
+  if (t >= len) {            // (the whole workgroup: no barrier is skipped by a part of it)
+    for (int i = threadIdx.x; i < Fp; i += blockDim.x) dst[i] = 0.f;
+    return;
+  }
+  const int nw = 2 * ctx + 1, F = nw * ncep;
+  const int4* mk = masks + (size_t)b * nm;
+  for (int j = threadIdx.x; j < nw + ncep; j += blockDim.x) {
+    bool hit = false;
+    if (j < nw) {
+      const int ts = t + j - ctx;     // outside [0, len): a pad, and no mask reaches there
+      for (int k = 0; k < nm; ++k) hit |= ts >= mk[k].x && ts < mk[k].x + mk[k].y;
+    } else {
+      const int c = (j - nw) % sw;
+      for (int k = 0; k < nm; ++k) hit |= c >= mk[k].z && c < mk[k].z + mk[k].w;
+    }
+    flag[j] = hit;
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < Fp; i += blockDim.x) {
+    float v = 0.f;
+    if (i < F) {
+      const int wdw = i / ncep, c = i - wdw * ncep;
+      const int ts = t + wdw - ctx;
+      if (ts < 0 || ts >= len) v = pad[b];
+      else if (!(flag[wdw] | flag[nw + c])) v = centre[((size_t)b * T + ts) * ncep + c];
+    }
+    dst[i] = v;
+  }
+}
+
+void launch_expand_context_masked(const float* centre, const float* pad, const int* seq_len, const int* masks, int nm,
+                                  int static_width, float* X0, int B, int Bp, int T, int ctx, int ncep, int Fp,
+                                  hipStream_t st) {
+  hipLaunchKernelGGL(expand_context_masked_kernel, dim3(T * Bp), dim3(256), (size_t)(2 * ctx + 1 + ncep), st, centre, pad,
+                     seq_len, reinterpret_cast<const int4*>(masks), nm, static_width, X0, B, Bp, T, ctx, ncep, Fp);
+}
+
 // ------------------------------------------------------------------ recurrent weight repack
 // U [Hp][N4] (row k = h unit, col n = 4*j+g) ->
 //   Uf [N4/16 tiles][Hp/16][64][4] : Uf[tile][q][l][i] = U[16q + 4*(l>>4) + i][16*tile + (l&15)]

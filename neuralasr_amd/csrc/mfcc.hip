@@ -533,6 +533,8 @@ int fz_feature_width(const nasr_ctx* fzh, int* numcontext, int* frame_width) {
   return z.W * z.d.width;
 }
 
+int fz_static_width(const nasr_ctx* fzh) { return fzh->fz->d.numcep; }
+
 }  // namespace nasr_impl
 
 namespace {

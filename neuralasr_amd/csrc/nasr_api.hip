@@ -398,6 +398,15 @@ int nasr_upload_batch_context(nasr_handle h, const float* centre, const float* p
   return upload(h, nullptr, seq_len, labels, label_len, B, T, Lmax, centre, pad_value, numcontext, numcep);
 }
 
+int nasr_upload_batch_context_aug(nasr_handle h, const float* centre, const float* pad_value, int numcontext, int numcep,
+                                  const int32_t* seq_len, const int32_t* labels, const int32_t* label_len, int B, int T,
+                                  int Lmax, const nasr_batch_aug* aug) {
+  MODEL_CALL(h);
+  if (!h) return NASR_ERR_ARG;
+  if (!centre) return h->fail(NASR_ERR_ARG, "null input buffer");
+  return upload(h, nullptr, seq_len, labels, label_len, B, T, Lmax, centre, pad_value, numcontext, numcep, nullptr, aug);
+}
+
 int nasr_stage_batch(nasr_handle h, const float* feats, const int32_t* seq_len, const int32_t* labels,
                      const int32_t* label_len, int B, int T, int Lmax, int* ticket) {
   MODEL_CALL(h);
@@ -418,7 +427,7 @@ int nasr_stage_batch_context(nasr_handle h, const float* centre, const float* pa
 // checks, the host-side plan (seq_len, T), and the front end as the producer of the slot's centre frames.
 static int audio_batch(nasr_ctx* h, nasr_ctx* fzh, const std::string& fn, const float* audio, const int64_t* offsets,
                        const int32_t* rates, const int32_t* labels, const int32_t* label_len, int B, int Lmax,
-                       int32_t* seq_len_out, int* T_out, int* ticket) {
+                       int32_t* seq_len_out, int* T_out, int* ticket, const nasr_batch_aug* aug = nullptr) {
   if (!fzh || !fzh->fz) return h->fail(NASR_ERR_STATE, fn + ": `featurizer` is not a featurizer handle");
   if (fzh->device != h->device)
     return h->fail(NASR_ERR_STATE, fn + ": the model is on device " + std::to_string(h->device) + ", the featurizer on device " +
@@ -429,6 +438,9 @@ static int audio_batch(nasr_ctx* h, nasr_ctx* fzh, const std::string& fn, const 
   if (fz_feature_width(fzh, &ctx, &ncep) != h->F)
     return h->fail(NASR_ERR_ARG, fn + ": feature_size " + std::to_string(h->F) + " must equal (2*numcontext+1)*numcep*(1+deltas) = (2*" +
                                      std::to_string(ctx) + "+1)*" + std::to_string(ncep) + " of the featurizer");
+  if (aug && aug->static_width != fz_static_width(fzh))
+    return h->fail(NASR_ERR_ARG, fn + ": augmentation: static_width " + std::to_string(aug->static_width) +
+                                     " is not the featurizer's numcep " + std::to_string(fz_static_width(fzh)));
   FzPlan plan;
   if (int rc = fz_plan(h, *fzh->fz, fn, offsets, rates, B, &plan)) return rc;
   int64_t Tmax = 0;
@@ -443,8 +455,8 @@ static int audio_batch(nasr_ctx* h, nasr_ctx* fzh, const std::string& fn, const 
   prod.run = [&](float* dcentre, float* dpad, void* pinned, hipStream_t cs) {
     return fz_produce_slot(h, fzh, plan, first, T, dcentre, dpad, pinned, cs);
   };
-  if (ticket) return stage(h, nullptr, seq_len_out, labels, label_len, B, T, Lmax, nullptr, nullptr, ctx, ncep, ticket, &prod);
-  return upload(h, nullptr, seq_len_out, labels, label_len, B, T, Lmax, nullptr, nullptr, ctx, ncep, &prod);
+  if (ticket) return stage(h, nullptr, seq_len_out, labels, label_len, B, T, Lmax, nullptr, nullptr, ctx, ncep, ticket, &prod, aug);
+  return upload(h, nullptr, seq_len_out, labels, label_len, B, T, Lmax, nullptr, nullptr, ctx, ncep, &prod, aug);
 }
 
 int nasr_upload_batch_audio(nasr_handle model, nasr_handle featurizer, const float* audio, const int64_t* offsets,
@@ -465,6 +477,26 @@ int nasr_stage_batch_audio(nasr_handle model, nasr_handle featurizer, const floa
   *ticket = -1;
   return audio_batch(model, featurizer, "nasr_stage_batch_audio", audio, offsets, rates, labels, label_len, B, Lmax,
                      seq_len_out, T_out, ticket);
+}
+
+int nasr_upload_batch_audio_aug(nasr_handle model, nasr_handle featurizer, const float* audio, const int64_t* offsets,
+                                const int32_t* rates, const int32_t* labels, const int32_t* label_len, int B, int Lmax,
+                                int32_t* seq_len_out, int* T_out, const nasr_batch_aug* aug) {
+  MODEL_CALL(model);
+  if (!model) return NASR_ERR_ARG;
+  return audio_batch(model, featurizer, "nasr_upload_batch_audio_aug", audio, offsets, rates, labels, label_len, B, Lmax,
+                     seq_len_out, T_out, nullptr, aug);
+}
+
+int nasr_stage_batch_audio_aug(nasr_handle model, nasr_handle featurizer, const float* audio, const int64_t* offsets,
+                               const int32_t* rates, const int32_t* labels, const int32_t* label_len, int B, int Lmax,
+                               int32_t* seq_len_out, int* T_out, const nasr_batch_aug* aug, int* ticket) {
+  MODEL_CALL(model);
+  if (!model) return NASR_ERR_ARG;
+  if (!ticket) return model->fail(NASR_ERR_ARG, "null ticket");
+  *ticket = -1;
+  return audio_batch(model, featurizer, "nasr_stage_batch_audio_aug", audio, offsets, rates, labels, label_len, B, Lmax,
+                     seq_len_out, T_out, ticket, aug);
 }
 
 int nasr_commit_batch(nasr_handle h, int ticket) {

@@ -144,6 +144,38 @@ int validate_batch(nasr_ctx* h, const int32_t* seq_len, const int32_t* labels, c
   return NASR_OK;
 }
 
+// The checks of nasr_batch_aug (include/nasr.h) against the batch's own seq_len; *masked: some mask has a non-zero width.
+static int validate_aug(nasr_ctx* h, const nasr_batch_aug* a, const int32_t* seq_len, int B, int ctx, int ncep, bool* masked) {
+  *masked = false;
+  if (a->n_time < 0 || a->n_time > NASR_AUG_MAX_MASKS || a->n_freq < 0 || a->n_freq > NASR_AUG_MAX_MASKS)
+    return h->fail(NASR_ERR_ARG, "augmentation: n_time = " + std::to_string(a->n_time) + ", n_freq = " + std::to_string(a->n_freq) +
+                                     ": each must be in [0," + std::to_string(NASR_AUG_MAX_MASKS) + "]");
+  if (a->static_width < 1 || ncep % a->static_width)
+    return h->fail(NASR_ERR_ARG, "augmentation: static_width " + std::to_string(a->static_width) + " does not divide the frame width " +
+                                     std::to_string(ncep));
+  if ((a->n_time && !a->time_mask) || (a->n_freq && !a->freq_mask)) return h->fail(NASR_ERR_ARG, "augmentation: null mask array");
+  if (2 * (int64_t)ctx + 1 + ncep > 32768) return h->fail(NASR_ERR_ARG, "augmentation: 2*numcontext+1 + frame width > 32768");
+  for (int b = 0; b < B; ++b) {
+    for (int k = 0; k < a->n_time; ++k) {
+      const int64_t t0 = a->time_mask[((size_t)b * a->n_time + k) * 2], tw = a->time_mask[((size_t)b * a->n_time + k) * 2 + 1];
+      if (t0 < 0 || tw < 0 || t0 + tw > seq_len[b])
+        return h->fail(NASR_ERR_ARG, "augmentation: time mask " + std::to_string(k) + " of utterance " + std::to_string(b) + " [" +
+                                         std::to_string(t0) + ", " + std::to_string(t0 + tw) + ") is not inside its " +
+                                         std::to_string(seq_len[b]) + " frames");
+      *masked |= tw > 0;
+    }
+    for (int k = 0; k < a->n_freq; ++k) {
+      const int64_t f0 = a->freq_mask[((size_t)b * a->n_freq + k) * 2], fw = a->freq_mask[((size_t)b * a->n_freq + k) * 2 + 1];
+      if (f0 < 0 || fw < 0 || f0 + fw > a->static_width)
+        return h->fail(NASR_ERR_ARG, "augmentation: frequency mask " + std::to_string(k) + " of utterance " + std::to_string(b) + " [" +
+                                         std::to_string(f0) + ", " + std::to_string(f0 + fw) + ") is not inside the static block of " +
+                                         std::to_string(a->static_width) + " columns");
+      *masked |= fw > 0;
+    }
+  }
+  return NASR_OK;
+}
+
 bool pinned_ensure(Pinned<void>& p, size_t* cap, size_t bytes) {
   if (bytes <= *cap) return true;
   *cap = 0;
@@ -186,9 +218,11 @@ void slot_set_state(nasr_ctx* h, BatchSlot* s, int st) {
 // `pad_value`) or from a device producer, whose kernels write it into the slot on stream cs: that is the only difference
 // between the two, the meta block and everything slot_commit does are the same.
 // All device copies (and a producer's kernels) go to stream cs and end with the slot's ev_copy.
+// aug (nullable, centre form only): SpecAugment masks, checked here against seq_len and written behind the rest of the
+// meta block; without a mask of non-zero width the slot is what it is without aug.
 int slot_fill(nasr_ctx* h, BatchSlot* s, const float* feats, const int32_t* seq_len, const int32_t* labels,
               const int32_t* label_len, int B, int T, int Lmax, const float* centre, const float* pad_value, int ctx,
-              int ncep, hipStream_t cs, bool pinned_feats, const CentreProducer* producer) {
+              int ncep, hipStream_t cs, bool pinned_feats, const CentreProducer* producer, const nasr_batch_aug* aug) {
   const bool centre_form = centre || producer;
   if ((!feats && !centre_form) || !seq_len) return h->fail(NASR_ERR_ARG, "null input buffer");
   if (centre_form && ((centre && !pad_value) || ctx < 0 || ncep < 1 || (2 * ctx + 1) * ncep != h->F))
@@ -196,6 +230,13 @@ int slot_fill(nasr_ctx* h, BatchSlot* s, const float* feats, const int32_t* seq_
   if (labels && !label_len) return h->fail(NASR_ERR_ARG, "labels without label_len");
   int rc = validate_batch(h, seq_len, labels, label_len, B, T, Lmax);
   if (rc) return rc;
+  bool masked = false;
+  if (aug) {
+    if (!centre_form) return h->fail(NASR_ERR_ARG, "augmentation masks need a batch in the centre form");
+    rc = validate_aug(h, aug, seq_len, B, ctx, ncep, &masked);
+    if (rc) return rc;
+  }
+  const int nm = masked ? std::max(aug->n_time, aug->n_freq) : 0;
   HIPCHK(h, hipSetDevice(h->device));
   const int Bp = rup(B, 16), Tp = h->family == Family::Las ? T : nasr_logit_frames(h, T), C = h->C, Lm = std::max(labels ? Lmax : 0, 1);
   const bool sr = h->cfg.merge == NASR_MERGE_STACK_RESHAPE && h->D == 2;
@@ -216,7 +257,8 @@ int slot_fill(nasr_ctx* h, BatchSlot* s, const float* feats, const int32_t* seq_
   s->o_vrow = s->o_rowmap + (sr ? (size_t)Tp * Bp : 0);
   s->o_vprev = s->o_vrow + s->Rvp;
   s->o_vnext = s->o_vprev + s->Rvp;
-  const size_t nmeta = s->o_vnext + s->Rvp;
+  s->o_aug = (s->o_vnext + s->Rvp + 3) / 4 * 4;      // (the kernel reads a mask as one int4)
+  const size_t nmeta = masked ? s->o_aug + (size_t)B * nm * 4 : s->o_vnext + s->Rvp;
   const size_t nfeat = centre_form ? (size_t)B * T * ncep + B : (size_t)B * T * h->F;
   bool grew = false;
   if (!s->dmeta.ensure(nmeta * 4, &grew) || !s->dfeats.ensure(nfeat * 4, &grew) ||
@@ -273,6 +315,13 @@ int slot_fill(nasr_ctx* h, BatchSlot* s, const float* feats, const int32_t* seq_
         }
     for (; i < s->Rvp; ++i) vr[i] = vp[i] = vn[i] = -1;
   }
+  if (masked)
+    for (int b = 0; b < B; ++b)
+      for (int k = 0; k < nm; ++k) {
+        int32_t* q = m + s->o_aug + ((size_t)b * nm + k) * 4;
+        if (k < aug->n_time) { q[0] = aug->time_mask[((size_t)b * aug->n_time + k) * 2]; q[1] = aug->time_mask[((size_t)b * aug->n_time + k) * 2 + 1]; }
+        if (k < aug->n_freq) { q[2] = aug->freq_mask[((size_t)b * aug->n_freq + k) * 2]; q[3] = aug->freq_mask[((size_t)b * aug->n_freq + k) * 2 + 1]; }
+      }
   if (producer) {
     rc = producer->run(s->dfeats.as<float>(), s->dfeats.as<float>() + (size_t)B * T * ncep,
                        pinned_feats ? s->hfeats.get() : nullptr, cs);
@@ -302,6 +351,7 @@ int slot_fill(nasr_ctx* h, BatchSlot* s, const float* feats, const int32_t* seq_
   s->B = B; s->T = T; s->Lmax = labels ? Lmax : 0; s->Bp = Bp; s->Tp = Tp; s->ctx = ctx; s->ncep = ncep;
   s->has_labels = labels != nullptr;
   s->centre = centre_form;
+  s->masked = masked; s->aug_nm = nm; s->aug_sw = masked ? aug->static_width : 0;
   return NASR_OK;
 }
 
@@ -346,7 +396,11 @@ int slot_commit(nasr_ctx* h, BatchSlot* s) {
   h->frames = s->frames;
   {
     PhaseScope ps(h, PH_PACK);
-    if (s->centre)
+    if (s->centre && s->masked)
+      launch_expand_context_masked(s->dfeats.as<float>(), s->dfeats.as<float>() + (size_t)B * T * s->ncep, h->seq_p,
+                                   md + s->o_aug, s->aug_nm, s->aug_sw, h->X0.as<float>(), B, Bp, T, s->ctx, s->ncep,
+                                   h->Fp, h->st);
+    else if (s->centre)
       launch_expand_context(s->dfeats.as<float>(), s->dfeats.as<float>() + (size_t)B * T * s->ncep, h->seq_p,
                             h->X0.as<float>(), B, Bp, T, s->ctx, s->ncep, h->Fp, h->st);
     else
@@ -372,11 +426,11 @@ int slot_commit(nasr_ctx* h, BatchSlot* s) {
 // the synchronous upload of nasr_upload_batch / nasr_train_step / ...: fill on the compute stream, commit
 int upload(nasr_ctx* h, const float* feats, const int32_t* seq_len, const int32_t* labels, const int32_t* label_len,
            int B, int T, int Lmax, const float* centre, const float* pad_value, int ctx, int ncep,
-           const CentreProducer* producer) {
+           const CentreProducer* producer, const nasr_batch_aug* aug) {
   BatchSlot* s = slot_acquire(h, false);
   if (!s) return h->fail(NASR_ERR_STATE, "every batch slot holds a staged batch: commit or discard one first");
   int rc = slot_fill(h, s, feats, seq_len, labels, label_len, B, T, Lmax, centre, pad_value, ctx, ncep, h->st, false,
-                     producer);
+                     producer, aug);
   if (!rc) rc = slot_commit(h, s);
   if (rc && h->cur != s) slot_set_state(h, s, SLOT_FREE);
   return rc;
@@ -391,13 +445,13 @@ BatchSlot* slot_of_ticket(nasr_ctx* h, int ticket) {
 
 int stage(nasr_ctx* h, const float* feats, const int32_t* seq_len, const int32_t* labels, const int32_t* label_len, int B,
           int T, int Lmax, const float* centre, const float* pad_value, int ctx, int ncep, int* ticket,
-          const CentreProducer* producer) {
+          const CentreProducer* producer, const nasr_batch_aug* aug) {
   if (!ticket) return h->fail(NASR_ERR_ARG, "null ticket");
   *ticket = -1;
   BatchSlot* s = slot_acquire(h, true);
   if (!s) return h->fail(NASR_ERR_STATE, "no free batch slot: commit or discard a staged batch first");
   const int rc = slot_fill(h, s, feats, seq_len, labels, label_len, B, T, Lmax, centre, pad_value, ctx, ncep, h->cst, true,
-                           producer);
+                           producer, aug);
   if (rc) {
     slot_set_state(h, s, SLOT_FREE);
     return rc;

@@ -168,6 +168,10 @@ struct BatchSlot {
   size_t o_vrow = 0, o_vprev = 0, o_vnext = 0;   // compacted rows of a ragged batch (Rv of them, padded to Rvp with -1), or unused
   int Rv = 0, Rvp = 0;
   bool cmp = false;
+  // SpecAugment masks of a centre-form batch (nasr_batch_aug): [B][aug_nm] of {t0, tw, f0, fw} at o_aug, or none
+  size_t o_aug = 0;
+  int aug_nm = 0, aug_sw = 0;
+  bool masked = false;
   int32_t* meta_d() const { return dmeta.as<int32_t>(); }
 };
 
@@ -514,11 +518,11 @@ struct CentreProducer {
 };
 int upload(nasr_ctx* h, const float* feats, const int32_t* seq_len, const int32_t* labels, const int32_t* label_len,
            int B, int T, int Lmax, const float* centre = nullptr, const float* pad_value = nullptr, int ctx = 0,
-           int ncep = 0, const CentreProducer* producer = nullptr);
+           int ncep = 0, const CentreProducer* producer = nullptr, const nasr_batch_aug* aug = nullptr);
 BatchSlot* slot_of_ticket(nasr_ctx* h, int ticket);
 int stage(nasr_ctx* h, const float* feats, const int32_t* seq_len, const int32_t* labels, const int32_t* label_len, int B,
           int T, int Lmax, const float* centre, const float* pad_value, int ctx, int ncep, int* ticket,
-          const CentreProducer* producer = nullptr);
+          const CentreProducer* producer = nullptr, const nasr_batch_aug* aug = nullptr);
 
 // ---- mfcc.hip: the front end as the device producer of a batch slot (nasr_upload_batch_audio, nasr_stage_batch_audio)
 // what a front-end call works out on the host before anything is launched
@@ -535,6 +539,7 @@ size_t fz_stage_bytes(const FzPlan& p);
 int fz_produce_slot(nasr_ctx* eh, nasr_ctx* fzh, const FzPlan& p, const float* audio, int Tb, float* dcentre, float* dpad,
                     void* pinned, hipStream_t st);
 int fz_feature_width(const nasr_ctx* fzh, int* numcontext, int* frame_width);   // (2*numcontext+1)*frame_width
+int fz_static_width(const nasr_ctx* fzh);                                        // the featurizer's numcep
 
 inline float* dout_of(nasr_ctx* h, int) { return h->dout.as<float>(); }
 inline float* dg_of(nasr_ctx* h, int) { return h->dgbuf.as<float>(); }

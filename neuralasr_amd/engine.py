@@ -1,6 +1,7 @@
 """Engine: NumPy-in / NumPy-out wrapper over one libnasr handle (= one GPU).  This is the thin layer the
 `Network` plugin classes (neuralasr_amd/networks) and bench.py sit on; all arithmetic happens in the HIP
 library behind include/nasr.h."""
+import collections
 import ctypes
 from ctypes import POINTER, byref, c_char, c_double, c_float, c_int32, c_int64, c_uint32, c_void_p
 
@@ -23,6 +24,24 @@ def _fp(a):
 
 def _ip(a):
     return a.ctypes.data_as(POINTER(c_int32))
+
+
+class BatchAug(collections.namedtuple('BatchAug', 'static_width time_masks freq_masks')):
+    """SpecAugment masks of one batch (nasr_batch_aug, include/nasr.h): time_masks int32 [B, nt, 2] of (first frame, width),
+    freq_masks int32 [B, nf, 2] of (first static column, width), either may be None; static_width is the width of the
+    static block of a frame (the config's numcep).  The library checks them; a mask of width 0 is no mask."""
+    __slots__ = ()
+
+    def struct(self, B):
+        """(_lib.BatchAug, the arrays it points into - to be kept alive over the call)"""
+        arrs = []
+        for m in (self.time_masks, self.freq_masks):
+            m = np.zeros((B, 0, 2), np.int32) if m is None else _i32(m)
+            if m.ndim != 3 or m.shape[0] != B or m.shape[2] != 2:
+                raise ValueError('masks must be [B=%d, n, 2], not %s' % (B, m.shape))
+            arrs.append(m)
+        tm, fm = arrs
+        return _lib.BatchAug(int(self.static_width), tm.shape[1], fm.shape[1], _ip(tm), _ip(fm)), arrs
 
 
 class Engine:
@@ -199,15 +218,22 @@ class Engine:
                 return False
         return True
 
-    def upload_batch_context(self, feats, seq_len, labels, label_len, numcontext, numcep):
+    def upload_batch_context(self, feats, seq_len, labels, label_len, numcontext, numcep, aug=None):
         """Upload context-stacked features [B,T,(2*numcontext+1)*numcep] as their centre slice and rebuild the
         stacking on the device (include_context, utils.py:8-21).  Returns False (nothing uploaded) when the
-        array does not have that structure (e.g. rand_shift cropped it), so the caller can upload it whole."""
+        array does not have that structure (e.g. rand_shift cropped it), so the caller can upload it whole.
+        `aug` (BatchAug): the kernel that stacks masks the centre frames first (nasr_upload_batch_context_aug)."""
         feats, seq, labels, ll, B, T, Lmax = self._batch(feats, seq_len, labels, label_len)
-        if not self.context_structure_ok(feats, seq, numcontext, numcep):
+        bare = aug is not None and numcontext == 0 and feats.shape[2] == numcep      # un-stacked frames: masked as they are
+        if not bare and not self.context_structure_ok(feats, seq, numcontext, numcep):
             return False
         pad = np.ascontiguousarray(feats[:, 0, 0])
         centre = np.ascontiguousarray(feats[:, :, numcontext * numcep:(numcontext + 1) * numcep])
+        if aug is not None:
+            st, keep = aug.struct(B)
+            self._ck(self.lib.nasr_upload_batch_context_aug(self.h, _fp(centre), _fp(pad), int(numcontext), int(numcep),
+                                                            _ip(seq), _ip(labels), _ip(ll), B, T, Lmax, byref(st)))
+            return True
         self._ck(self.lib.nasr_upload_batch_context(self.h, _fp(centre), _fp(pad), int(numcontext), int(numcep),
                                                     _ip(seq), _ip(labels), _ip(ll), B, T, Lmax))
         return True
@@ -265,21 +291,33 @@ class Engine:
                 *tail)
         return rc, seq[:B], int(T.value)
 
-    def upload_batch_audio(self, featurizer, audios, labels, label_len, rates=None):
+    def upload_batch_audio(self, featurizer, audios, labels, label_len, rates=None, aug=None):
         """A batch from audio: `featurizer` (features.Featurizer, same device) makes the MFCC features of the float32
         utterances `audios` (at `rates` Hz, None: all at its samplerate) on the device and writes them into this handle's
-        batch slot; the batch is resident afterwards, as after upload_batch.  Returns (seq_len int32 [B], T)."""
+        batch slot; the batch is resident afterwards, as after upload_batch.  Returns (seq_len int32 [B], T).
+        `aug` (BatchAug): SpecAugment masks on the normalised frames (nasr_upload_batch_audio_aug)."""
+        if aug is not None:
+            st, keep = aug.struct(len(audios))
+            rc, seq, T = self._audio_call(self.lib.nasr_upload_batch_audio_aug, featurizer, audios, labels, label_len, rates,
+                                          byref(st))
+            self._ck(rc)
+            return seq, T
         rc, seq, T = self._audio_call(self.lib.nasr_upload_batch_audio, featurizer, audios, labels, label_len, rates)
         self._ck(rc)
         return seq, T
 
-    def stage_batch_audio(self, featurizer, audios, labels, label_len, rates=None):
+    def stage_batch_audio(self, featurizer, audios, labels, label_len, rates=None, aug=None):
         """upload_batch_audio's staging half (stage_batch): copies and front-end kernels on the copy stream while the
         current step runs.  Returns (seq_len, T, ticket); ticket is None when no staging slot is free."""
         from ctypes import c_int
         ticket = c_int(-1)
-        rc, seq, T = self._audio_call(self.lib.nasr_stage_batch_audio, featurizer, audios, labels, label_len, rates,
-                                      byref(ticket))
+        if aug is not None:
+            st, keep = aug.struct(len(audios))
+            rc, seq, T = self._audio_call(self.lib.nasr_stage_batch_audio_aug, featurizer, audios, labels, label_len, rates,
+                                          byref(st), byref(ticket))
+        else:
+            rc, seq, T = self._audio_call(self.lib.nasr_stage_batch_audio, featurizer, audios, labels, label_len, rates,
+                                          byref(ticket))
         if rc == _lib.NASR_ERR_STATE and ticket.value < 0:
             msg = self.lib.nasr_last_error(self.h)
             if msg and b'no free batch slot' in msg:
@@ -704,9 +742,9 @@ class LasEngine(Engine):
         self._BU = (B, U)
         self._ck(self.lib.nasr_upload_batch(self.h, _fp(feats), _ip(seq), _ip(labels), _ip(ll), B, T, U))
 
-    def upload_batch_audio(self, featurizer, audios, labels, label_len, rates=None):
+    def upload_batch_audio(self, featurizer, audios, labels, label_len, rates=None, aug=None):
         self._BU = (len(audios), 0 if labels is None else np.asarray(labels).reshape(len(audios), -1).shape[1])
-        return Engine.upload_batch_audio(self, featurizer, audios, labels, label_len, rates)
+        return Engine.upload_batch_audio(self, featurizer, audios, labels, label_len, rates, aug)
 
     def align(self, *a, **k):
         raise NotImplementedError('forced alignment walks a CTC lattice; the LAS network has none')

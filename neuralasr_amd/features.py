@@ -201,9 +201,11 @@ class AudioBatch:
     """A batch as audio: what HipNetwork's *_audio calls and AudioDataSet hand to the step machinery in the place of the
     padded feature array.  The features are made on the device when the batch is uploaded (Engine.upload_batch_audio);
     the frame counts - seq_len and the padded length T - are the library's host-side arithmetic.  `shape` is the shape
-    the padded feature array would have."""
+    the padded feature array would have.  time_masks [B, nt, 2] / freq_masks [B, nf, 2] (int32, optional): the
+    SpecAugment masks a TRAINING step applies to the normalised frames on the device (augment.py, DESIGN.md §13);
+    validate / evaluate / decode / align ignore them."""
 
-    def __init__(self, samplerate, audios, rates=None, width=0):
+    def __init__(self, samplerate, audios, rates=None, width=0, time_masks=None, freq_masks=None):
         self.samplerate = int(samplerate)
         self.audios = Featurizer._utterances(audios)
         self.rates = None if rates is None else [int(r) for r in rates]
@@ -220,6 +222,23 @@ class AudioBatch:
             frames.append(num_frames(n, self.samplerate))
         self.seq_len = [np.asarray(t, dtype=np.int32) for t in frames]
         self.shape = (len(self.audios), max(frames), int(width))
+        self.time_masks = self._masks(time_masks, 'time_masks')
+        self.freq_masks = self._masks(freq_masks, 'freq_masks')
+
+    def _masks(self, m, name):
+        if m is None:
+            return None
+        m = np.ascontiguousarray(m, dtype=np.int32)
+        if m.ndim != 3 or m.shape[0] != len(self.audios) or m.shape[2] != 2:
+            raise ValueError('%s must be [%d, n, 2], not %s' % (name, len(self.audios), m.shape))
+        return m
+
+    def aug(self, static_width):
+        """the masks as the engine's upload calls take them (engine.BatchAug), or None without masks"""
+        if self.time_masks is None and self.freq_masks is None:
+            return None
+        from .engine import BatchAug
+        return BatchAug(int(static_width), self.time_masks, self.freq_masks)
 
     def __len__(self):
         return len(self.audios)
@@ -227,7 +246,8 @@ class AudioBatch:
     def shard(self, lo, hi):
         """utterances [lo, hi) as a batch of their own, padded to ITS longest utterance"""
         return AudioBatch(self.samplerate, self.audios[lo:hi], None if self.rates is None else self.rates[lo:hi],
-                          self.shape[2])
+                          self.shape[2], None if self.time_masks is None else self.time_masks[lo:hi],
+                          None if self.freq_masks is None else self.freq_masks[lo:hi])
 
 
 class Featurizer:

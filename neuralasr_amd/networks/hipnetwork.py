@@ -236,8 +236,10 @@ class HipNetwork(Network):
                              'length of the WHOLE batch: use features with num_gpus > 1 on this network')
         return AudioBatch(self.config.samplerate, audios, rates, self.config.feature_size)
 
-    def _upload_audio(self, b, labels=None, labels_len=None):
-        self.engine.upload_batch_audio(self.featurizer(), b.audios, labels, labels_len, b.rates)
+    def _upload_audio(self, b, labels=None, labels_len=None, masked=False):
+        """masked: a training step's upload, with the batch's SpecAugment masks when it carries any"""
+        aug = b.aug(self.config.numcep) if masked else None
+        self.engine.upload_batch_audio(self.featurizer(), b.audios, labels, labels_len, b.rates, aug)
 
     def _forward(self, mfccs, seq_len):
         if isinstance(mfccs, AudioBatch):
@@ -246,9 +248,9 @@ class HipNetwork(Network):
         return self.engine.forward(mfccs, seq_len)
 
     def _upload(self, f, l, s, ll):
-        """the synchronous upload of one tower's shard"""
+        """the synchronous upload of one tower's shard for a training step"""
         if isinstance(f, AudioBatch):
-            self._upload_audio(f, l, ll)
+            self._upload_audio(f, l, ll, masked=True)
         elif not (self._use_device_context() and
                   self.engine.upload_batch_context(f, s, l, ll, self.config.numcontext, self._frame_width())):
             self.engine.upload_batch(f, s, l, ll)
@@ -461,7 +463,7 @@ class HipNetwork(Network):
             return False                        # towers time-sliced on one GPU: each upload replaces the resident batch
         f, l, s, ll = take_shard(mfccs, labels, seq_len, labels_len, n, mine[0])
         if isinstance(f, AudioBatch):
-            ticket = self.engine.stage_batch_audio(self.featurizer(), f.audios, l, ll, f.rates)[2]
+            ticket = self.engine.stage_batch_audio(self.featurizer(), f.audios, l, ll, f.rates, f.aug(self.config.numcep))[2]
         else:
             ctx = self.config.numcontext if self._use_device_context() else 0
             ticket = self.engine.stage_batch(f, s, l, ll, ctx, self._frame_width())

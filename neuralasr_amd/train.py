@@ -119,6 +119,10 @@ def main(argv=None):
     if args.from_audio:
         dataTrain, dataValid = audio_datasets(args.config, config)
     else:
+        if config.augment_on:
+            raise ValueError('the augmentation keys (spec_time_masks, spec_freq_masks, speed_perturb) need --from-audio: the '
+                             'masks and the perturbed rates are applied where the GPU makes the features; pickled features '
+                             'are not masked')
         dataTrain = DataSet(config.train_input, config)
         dataValid = None
         if config.test_input:
@@ -130,7 +134,8 @@ def main(argv=None):
 
 def audio_datasets(configfile, config):
     """--from-audio: the training and the validation set of the [MFCC Featurizer] input CSV as train_model reads them.
-    The batches hold audio (features.AudioBatch); HipNetwork stages and uploads them through the GPU front end."""
+    The batches hold audio (features.AudioBatch); HipNetwork stages and uploads them through the GPU front end.  With an
+    augmentation key switched on the training feed draws speed factors and SpecAugment masks (augment.py)."""
     from .audio_dataset import AudioDataSet, AudioFeed
     if config.rand_shift > 0:
         raise ValueError('--from-audio cannot be combined with rand_shift > 0 (rand_shift=%d): the roll-and-crop leaves real '
@@ -138,7 +143,12 @@ def audio_datasets(configfile, config):
                          'and pad values; set rand_shift=0 or train from the pickled features' % config.rand_shift)
     if not config.mfcc_input:
         raise ValueError("--from-audio needs 'input' in the [MFCC Featurizer] section of " + configfile)
-    dataTrain = AudioFeed(AudioDataSet(config.mfcc_input, config, 'train'))     # (writes the symbol table when there is none)
+    augmenter = None
+    if config.augment_on:       # the training feed only: validation and decode never augment
+        import torch.distributed as dist
+        from .augment import Augmenter
+        augmenter = Augmenter(config, rank=dist.get_rank() if dist.is_available() and dist.is_initialized() else 0)
+    dataTrain = AudioFeed(AudioDataSet(config.mfcc_input, config, 'train'), augmenter)     # (writes the symbol table when there is none)
     dataValid = None
     if config.test_input:
         config_test = Config(configfile, isTraining=True)

@@ -3,7 +3,10 @@
 AudioDataSet -> features made on the GPU per batch) against the pickled loop (preprocess_mfcc -> DataSet) on the same
 utterances: synthetic WAVs at 16 kHz, numcep 26, numcontext 10, the 3x500 bidirectional net, one GPU.
 
-    python tools/e2e_audio.py [utterances=64] [epochs=4] [seconds=5] [batch=16]"""
+    python tools/e2e_audio.py [utterances=64] [epochs=4] [seconds=5] [batch=16] [augment=0]
+
+augment=1: the loop from audio without and with the augmentation keys (2 time masks up to 40 frames, 2 frequency masks up
+to 7 columns, speed_perturb=0.9,1.0,1.1) in the place of the pickled loop."""
 import os
 import shutil
 import sys
@@ -35,7 +38,7 @@ model_dir=%(out)s/model
 start_step=0
 report_step=1000000
 num_gpus=1
-punc_regex=[^a-z0-9 ]
+%(keys)spunc_regex=[^a-z0-9 ]
 sym_file=${MFCC Featurizer:output}/symbols
 network=networks.bilstm_ctc_net.BiLstm3x500CTCNet
 
@@ -48,6 +51,8 @@ input=${MFCC Featurizer:output}/train.scp
 input=%(out)s/data.csv
 output=%(out)s/mfcc
 """
+KEYS = ('spec_time_masks=2\nspec_time_width=40\nspec_freq_masks=2\nspec_freq_width=7\nspeed_perturb=0.9,1.0,1.1\n'
+        'augment_seed=1\n')
 
 
 def main():
@@ -55,6 +60,7 @@ def main():
     epochs = int(sys.argv[2]) if len(sys.argv) > 2 else 4
     seconds = float(sys.argv[3]) if len(sys.argv) > 3 else 5.0
     batch = int(sys.argv[4]) if len(sys.argv) > 4 else 16
+    augment = len(sys.argv) > 5 and int(sys.argv[5]) != 0
     out = tempfile.mkdtemp(prefix='nasr_e2e_audio_')
     try:
         rs = np.random.RandomState(7)
@@ -68,14 +74,21 @@ def main():
             rows.append('%s,%s,%d' % (wav, txt, os.path.getsize(wav)))
         with open(os.path.join(out, 'data.csv'), 'w') as fh:
             fh.write('\n'.join(rows) + '\n')
-        cfgp = os.path.join(out, 'e2e.config')
+        cfgp, cfga = os.path.join(out, 'e2e.config'), os.path.join(out, 'e2e_aug.config')
         with open(cfgp, 'w') as fh:
-            fh.write(CONFIG % dict(out=out, epochs=epochs, batch=batch))
+            fh.write(CONFIG % dict(out=out, epochs=epochs, batch=batch, keys=''))
+        with open(cfga, 'w') as fh:
+            fh.write(CONFIG % dict(out=out, epochs=epochs, batch=batch, keys=KEYS))
         preprocess_mfcc.main([cfgp])
-        for label, audio in (('pickled features (DataSet)', False), ('from audio (AudioDataSet)', True),
-                             ('pickled features, again', False), ('from audio, again', True)):
-            cfg = Config(cfgp, True)
-            data = train_mod.audio_datasets(cfgp, cfg)[0] if audio else DataSet(cfg.train_input, cfg)
+        legs = (('pickled features (DataSet)', False), ('from audio (AudioDataSet)', True),
+                ('pickled features, again', False), ('from audio, again', True))
+        if augment:
+            legs = (('from audio (AudioDataSet)', True), ('from audio, augmented', cfga),
+                    ('from audio, again', True), ('from audio, augmented, again', cfga))
+        for label, audio in legs:
+            path = audio if isinstance(audio, str) else cfgp
+            cfg = Config(path, True)
+            data = train_mod.audio_datasets(path, cfg)[0] if audio else DataSet(cfg.train_input, cfg)
             steps_per_epoch = (data.get_num_of_sample() + batch - 1) // batch
             stamps = []
             orig = cfg.load_network.__func__
