@@ -386,7 +386,7 @@ int nasr_upload_batch(nasr_handle h, const float* feats, const int32_t* seq_len,
                       const int32_t* label_len, int B, int T, int Lmax) {
   MODEL_CALL(h);
   if (!h) return NASR_ERR_ARG;
-  return upload(h, feats, seq_len, labels, label_len, B, T, Lmax);
+  return upload(h, stacked_batch(feats, seq_len, labels, label_len, B, T, Lmax));
 }
 
 int nasr_upload_batch_context(nasr_handle h, const float* centre, const float* pad_value, int numcontext, int numcep,
@@ -395,7 +395,7 @@ int nasr_upload_batch_context(nasr_handle h, const float* centre, const float* p
   MODEL_CALL(h);
   if (!h) return NASR_ERR_ARG;
   if (!centre) return h->fail(NASR_ERR_ARG, "null input buffer");
-  return upload(h, nullptr, seq_len, labels, label_len, B, T, Lmax, centre, pad_value, numcontext, numcep);
+  return upload(h, centre_batch(centre, pad_value, numcontext, numcep, seq_len, labels, label_len, B, T, Lmax, nullptr));
 }
 
 int nasr_upload_batch_context_aug(nasr_handle h, const float* centre, const float* pad_value, int numcontext, int numcep,
@@ -404,14 +404,14 @@ int nasr_upload_batch_context_aug(nasr_handle h, const float* centre, const floa
   MODEL_CALL(h);
   if (!h) return NASR_ERR_ARG;
   if (!centre) return h->fail(NASR_ERR_ARG, "null input buffer");
-  return upload(h, nullptr, seq_len, labels, label_len, B, T, Lmax, centre, pad_value, numcontext, numcep, nullptr, aug);
+  return upload(h, centre_batch(centre, pad_value, numcontext, numcep, seq_len, labels, label_len, B, T, Lmax, aug));
 }
 
 int nasr_stage_batch(nasr_handle h, const float* feats, const int32_t* seq_len, const int32_t* labels,
                      const int32_t* label_len, int B, int T, int Lmax, int* ticket) {
   MODEL_CALL(h);
   if (!h) return NASR_ERR_ARG;
-  return stage(h, feats, seq_len, labels, label_len, B, T, Lmax, nullptr, nullptr, 0, 0, ticket);
+  return stage(h, stacked_batch(feats, seq_len, labels, label_len, B, T, Lmax), ticket);
 }
 
 int nasr_stage_batch_context(nasr_handle h, const float* centre, const float* pad_value, int numcontext, int numcep,
@@ -420,14 +420,20 @@ int nasr_stage_batch_context(nasr_handle h, const float* centre, const float* pa
   MODEL_CALL(h);
   if (!h) return NASR_ERR_ARG;
   if (!centre) return h->fail(NASR_ERR_ARG, "null input buffer");
-  return stage(h, nullptr, seq_len, labels, label_len, B, T, Lmax, centre, pad_value, numcontext, numcep, ticket);
+  return stage(h, centre_batch(centre, pad_value, numcontext, numcep, seq_len, labels, label_len, B, T, Lmax, nullptr), ticket);
 }
 
-// The common part of nasr_upload_batch_audio / nasr_stage_batch_audio (utils.py:24-31 feeding dataset.py:33-40): the
-// checks, the host-side plan (seq_len, T), and the front end as the producer of the slot's centre frames.
-static int audio_batch(nasr_ctx* h, nasr_ctx* fzh, const std::string& fn, const float* audio, const int64_t* offsets,
+// The four nasr_*_batch_audio* calls (utils.py:24-31 feeding dataset.py:33-40), fn the one that was called: the checks, the
+// host-side plan (seq_len, T), and the front end as the producer of the slot's centre frames.  staged: into *ticket.
+static int audio_batch(const std::string& fn, nasr_ctx* h, nasr_ctx* fzh, const float* audio, const int64_t* offsets,
                        const int32_t* rates, const int32_t* labels, const int32_t* label_len, int B, int Lmax,
-                       int32_t* seq_len_out, int* T_out, int* ticket, const nasr_batch_aug* aug = nullptr) {
+                       int32_t* seq_len_out, int* T_out, const nasr_batch_aug* aug, bool staged, int* ticket) {
+  if (!h) return NASR_ERR_ARG;
+  if (h->family == Family::Featurizer) return h->fail(NASR_ERR_STATE, fn + ": a featurizer handle has no model");   // MODEL_CALL
+  if (staged) {
+    if (!ticket) return h->fail(NASR_ERR_ARG, "null ticket");
+    *ticket = -1;
+  }
   if (!fzh || !fzh->fz) return h->fail(NASR_ERR_STATE, fn + ": `featurizer` is not a featurizer handle");
   if (fzh->device != h->device)
     return h->fail(NASR_ERR_STATE, fn + ": the model is on device " + std::to_string(h->device) + ", the featurizer on device " +
@@ -455,48 +461,36 @@ static int audio_batch(nasr_ctx* h, nasr_ctx* fzh, const std::string& fn, const 
   prod.run = [&](float* dcentre, float* dpad, void* pinned, hipStream_t cs) {
     return fz_produce_slot(h, fzh, plan, first, T, dcentre, dpad, pinned, cs);
   };
-  if (ticket) return stage(h, nullptr, seq_len_out, labels, label_len, B, T, Lmax, nullptr, nullptr, ctx, ncep, ticket, &prod, aug);
-  return upload(h, nullptr, seq_len_out, labels, label_len, B, T, Lmax, nullptr, nullptr, ctx, ncep, &prod, aug);
+  const BatchSrc src = produced_batch(&prod, ctx, ncep, seq_len_out, labels, label_len, B, T, Lmax, aug);
+  return staged ? stage(h, src, ticket) : upload(h, src);
 }
 
 int nasr_upload_batch_audio(nasr_handle model, nasr_handle featurizer, const float* audio, const int64_t* offsets,
                             const int32_t* rates, const int32_t* labels, const int32_t* label_len, int B, int Lmax,
                             int32_t* seq_len_out, int* T_out) {
-  MODEL_CALL(model);
-  if (!model) return NASR_ERR_ARG;
-  return audio_batch(model, featurizer, "nasr_upload_batch_audio", audio, offsets, rates, labels, label_len, B, Lmax,
-                     seq_len_out, T_out, nullptr);
+  return audio_batch(__func__, model, featurizer, audio, offsets, rates, labels, label_len, B, Lmax, seq_len_out, T_out, nullptr,
+                     false, nullptr);
 }
 
 int nasr_stage_batch_audio(nasr_handle model, nasr_handle featurizer, const float* audio, const int64_t* offsets,
                            const int32_t* rates, const int32_t* labels, const int32_t* label_len, int B, int Lmax,
                            int32_t* seq_len_out, int* T_out, int* ticket) {
-  MODEL_CALL(model);
-  if (!model) return NASR_ERR_ARG;
-  if (!ticket) return model->fail(NASR_ERR_ARG, "null ticket");
-  *ticket = -1;
-  return audio_batch(model, featurizer, "nasr_stage_batch_audio", audio, offsets, rates, labels, label_len, B, Lmax,
-                     seq_len_out, T_out, ticket);
+  return audio_batch(__func__, model, featurizer, audio, offsets, rates, labels, label_len, B, Lmax, seq_len_out, T_out, nullptr,
+                     true, ticket);
 }
 
 int nasr_upload_batch_audio_aug(nasr_handle model, nasr_handle featurizer, const float* audio, const int64_t* offsets,
                                 const int32_t* rates, const int32_t* labels, const int32_t* label_len, int B, int Lmax,
                                 int32_t* seq_len_out, int* T_out, const nasr_batch_aug* aug) {
-  MODEL_CALL(model);
-  if (!model) return NASR_ERR_ARG;
-  return audio_batch(model, featurizer, "nasr_upload_batch_audio_aug", audio, offsets, rates, labels, label_len, B, Lmax,
-                     seq_len_out, T_out, nullptr, aug);
+  return audio_batch(__func__, model, featurizer, audio, offsets, rates, labels, label_len, B, Lmax, seq_len_out, T_out, aug,
+                     false, nullptr);
 }
 
 int nasr_stage_batch_audio_aug(nasr_handle model, nasr_handle featurizer, const float* audio, const int64_t* offsets,
                                const int32_t* rates, const int32_t* labels, const int32_t* label_len, int B, int Lmax,
                                int32_t* seq_len_out, int* T_out, const nasr_batch_aug* aug, int* ticket) {
-  MODEL_CALL(model);
-  if (!model) return NASR_ERR_ARG;
-  if (!ticket) return model->fail(NASR_ERR_ARG, "null ticket");
-  *ticket = -1;
-  return audio_batch(model, featurizer, "nasr_stage_batch_audio_aug", audio, offsets, rates, labels, label_len, B, Lmax,
-                     seq_len_out, T_out, ticket, aug);
+  return audio_batch(__func__, model, featurizer, audio, offsets, rates, labels, label_len, B, Lmax, seq_len_out, T_out, aug,
+                     true, ticket);
 }
 
 int nasr_commit_batch(nasr_handle h, int ticket) {
@@ -759,7 +753,7 @@ int nasr_train_step(nasr_handle h, const float* feats, const int32_t* seq_len, c
   MODEL_CALL(h);
   if (!h) return NASR_ERR_ARG;
   if (!labels) return h->fail(NASR_ERR_ARG, "nasr_train_step needs labels");
-  int rc = upload(h, feats, seq_len, labels, label_len, B, T, Lmax);
+  int rc = upload(h, stacked_batch(feats, seq_len, labels, label_len, B, T, Lmax));
   if (rc) return rc;
   rc = nasr_compute_grads(h);
   if (rc) return rc;
@@ -782,7 +776,7 @@ int nasr_forward_resident(nasr_handle h, float* logits_out) {
 int nasr_forward(nasr_handle h, const float* feats, const int32_t* seq_len, int B, int T, float* logits_out) {
   MODEL_CALL(h);
   if (!h) return NASR_ERR_ARG;
-  const int rc = upload(h, feats, seq_len, nullptr, nullptr, B, T, 0);
+  const int rc = upload(h, stacked_batch(feats, seq_len, nullptr, nullptr, B, T, 0));
   if (rc) return rc;
   return nasr_forward_resident(h, logits_out);
 }
@@ -792,7 +786,7 @@ int nasr_loss(nasr_handle h, const float* feats, const int32_t* seq_len, const i
   MODEL_CALL(h);
   if (!h) return NASR_ERR_ARG;
   if (!labels) return h->fail(NASR_ERR_ARG, "nasr_loss needs labels");
-  const int rc = upload(h, feats, seq_len, labels, label_len, B, T, Lmax);
+  const int rc = upload(h, stacked_batch(feats, seq_len, labels, label_len, B, T, Lmax));
   if (rc) return rc;
   return nasr_loss_resident(h, loss_out, nll_out);
 }
@@ -814,7 +808,7 @@ int nasr_loss_and_grads(nasr_handle h, const float* feats, const int32_t* seq_le
   MODEL_CALL(h);
   if (!h) return NASR_ERR_ARG;
   if (!labels) return h->fail(NASR_ERR_ARG, "nasr_loss_and_grads needs labels");
-  int rc = upload(h, feats, seq_len, labels, label_len, B, T, Lmax);
+  int rc = upload(h, stacked_batch(feats, seq_len, labels, label_len, B, T, Lmax));
   if (rc) return rc;
   rc = nasr_compute_grads(h);
   if (rc) return rc;
@@ -832,7 +826,7 @@ int nasr_greedy_decode(nasr_handle h, const float* feats, const int32_t* seq_len
   MODEL_CALL(h);
   if (!h || !ids_out || !lens_out) return NASR_ERR_ARG;
   if (h->family == Family::Las) return h->fail(NASR_ERR_STATE, "nasr_greedy_decode: a LAS handle has no CTC decoder");
-  const int rc = upload(h, feats, seq_len, nullptr, nullptr, B, T, 0);
+  const int rc = upload(h, stacked_batch(feats, seq_len, nullptr, nullptr, B, T, 0));
   if (rc) return rc;
   return nasr_greedy_decode_resident(h, ids_out, lens_out);
 }
@@ -905,7 +899,7 @@ int nasr_ctc_align(nasr_handle h, const float* feats, const int32_t* seq_len, co
   if (!h) return NASR_ERR_ARG;
   if (h->family == Family::Las) return h->fail(NASR_ERR_STATE, "nasr_ctc_align: a LAS handle has no CTC lattice");
   if (!labels || !path_out || !score_out) return h->fail(NASR_ERR_ARG, "nasr_ctc_align needs labels and both output buffers");
-  const int rc = upload(h, feats, seq_len, labels, label_len, B, T, Lmax);
+  const int rc = upload(h, stacked_batch(feats, seq_len, labels, label_len, B, T, Lmax));
   if (rc) return rc;
   return nasr_ctc_align_resident(h, path_out, score_out);
 }

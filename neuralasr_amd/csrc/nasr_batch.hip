@@ -210,72 +210,66 @@ void slot_set_state(nasr_ctx* h, BatchSlot* s, int st) {
   s->state = st;
 }
 
-// Copies one batch into slot s: the integer arrays through the slot's pinned meta buffer, the features from the caller's
-// memory (`pinned_feats` false: hipMemcpyAsync from pageable memory, which returns when the source may be reused) or
-// through the slot's pinned feature buffer (true: the H2D is a plain DMA that overlaps whatever the compute stream runs).
-// The centre form (centre frames [B][T][ncep], ncep the width of one un-stacked frame: numcep*(1+deltas) of the features'
-// config, + one pad value per utterance) comes from host memory (`centre`,
-// `pad_value`) or from a device producer, whose kernels write it into the slot on stream cs: that is the only difference
-// between the two, the meta block and everything slot_commit does are the same.
-// All device copies (and a producer's kernels) go to stream cs and end with the slot's ev_copy.
-// aug (nullable, centre form only): SpecAugment masks, checked here against seq_len and written behind the rest of the
-// meta block; without a mask of non-zero width the slot is what it is without aug.
-int slot_fill(nasr_ctx* h, BatchSlot* s, const float* feats, const int32_t* seq_len, const int32_t* labels,
-              const int32_t* label_len, int B, int T, int Lmax, const float* centre, const float* pad_value, int ctx,
-              int ncep, hipStream_t cs, bool pinned_feats, const CentreProducer* producer, const nasr_batch_aug* aug) {
-  const bool centre_form = centre || producer;
-  if ((!feats && !centre_form) || !seq_len) return h->fail(NASR_ERR_ARG, "null input buffer");
-  if (centre_form && ((centre && !pad_value) || ctx < 0 || ncep < 1 || (2 * ctx + 1) * ncep != h->F))
+static bool stack_reshape(const nasr_ctx* h) { return h->cfg.merge == NASR_MERGE_STACK_RESHAPE && h->D == 2; }
+
+// slot_fill (1): the argument checks, in this order; *masked: aug has a mask of non-zero width
+static int check_batch(nasr_ctx* h, const BatchSrc& b, bool* masked) {
+  *masked = false;
+  if ((b.feats != nullptr) + (b.centre != nullptr) + (b.producer != nullptr) != 1 || !b.seq_len)
+    return h->fail(NASR_ERR_ARG, "null input buffer");
+  if (b.centre_form() && ((b.centre && !b.pad_value) || b.ctx < 0 || b.ncep < 1 || (2 * b.ctx + 1) * b.ncep != h->F))
     return h->fail(NASR_ERR_ARG, "context upload: feature_size must equal (2*numcontext+1)*numcep");
-  if (labels && !label_len) return h->fail(NASR_ERR_ARG, "labels without label_len");
-  int rc = validate_batch(h, seq_len, labels, label_len, B, T, Lmax);
-  if (rc) return rc;
-  bool masked = false;
-  if (aug) {
-    if (!centre_form) return h->fail(NASR_ERR_ARG, "augmentation masks need a batch in the centre form");
-    rc = validate_aug(h, aug, seq_len, B, ctx, ncep, &masked);
-    if (rc) return rc;
-  }
-  const int nm = masked ? std::max(aug->n_time, aug->n_freq) : 0;
-  HIPCHK(h, hipSetDevice(h->device));
-  const int Bp = rup(B, 16), Tp = h->family == Family::Las ? T : nasr_logit_frames(h, T), C = h->C, Lm = std::max(labels ? Lmax : 0, 1);
-  const bool sr = h->cfg.merge == NASR_MERGE_STACK_RESHAPE && h->D == 2;
-  // meta layout (int32): seq [Bp] | lablen [Bp] | labels [B*Lm] | cstart [B*(C+1)] | cpos [B*Lm] | rowmap [Tp*Bp]
+  if (b.labels && !b.label_len) return h->fail(NASR_ERR_ARG, "labels without label_len");
+  if (int rc = validate_batch(h, b.seq_len, b.labels, b.label_len, b.B, b.T, b.Lmax)) return rc;
+  if (!b.aug) return NASR_OK;
+  if (!b.centre_form()) return h->fail(NASR_ERR_ARG, "augmentation masks need a batch in the centre form");
+  return validate_aug(h, b.aug, b.seq_len, b.B, b.ctx, b.ncep, masked);
+}
+
+// slot_fill (2): the slot's shape and the layout of its meta block (int32): seq [Bp] | lablen [Bp] | labels [B*Lm] |
+// cstart [B*(C+1)] | cpos [B*Lm] | rowmap [Tp*Bp] | vrow, vprev, vnext [Rvp] | masks [B*nm] of int4.  No HIP call.
+static void meta_layout(nasr_ctx* h, BatchSlot* s, const BatchSrc& b, bool masked) {
+  const int B = b.B, T = b.T;
+  s->B = B; s->T = T; s->Lmax = b.labels ? b.Lmax : 0; s->ctx = b.ctx; s->ncep = b.ncep;
+  s->Bp = rup(B, 16);
+  s->Tp = h->family == Family::Las ? T : nasr_logit_frames(h, T);
+  s->has_labels = b.labels != nullptr;
+  s->centre = b.centre_form();
+  s->masked = masked;
+  s->aug_nm = masked ? std::max(b.aug->n_time, b.aug->n_freq) : 0;
+  s->aug_sw = masked ? b.aug->static_width : 0;
+  s->frames = 0;
+  for (int i = 0; i < B; ++i) s->frames += b.seq_len[i];
+  const size_t BLm = (size_t)B * std::max(s->Lmax, 1);
   s->o_seq = 0;
-  s->o_lablen = s->o_seq + Bp;
-  s->o_labels = s->o_lablen + Bp;
-  s->o_cstart = s->o_labels + (size_t)B * Lm;
-  s->o_cpos = s->o_cstart + (labels ? (size_t)B * (C + 1) : 0);
-  s->o_rowmap = s->o_cpos + (size_t)B * Lm;
+  s->o_lablen = s->o_seq + s->Bp;
+  s->o_labels = s->o_lablen + s->Bp;
+  s->o_cstart = s->o_labels + BLm;
+  s->o_cpos = s->o_cstart + (b.labels ? (size_t)B * (h->C + 1) : 0);
+  s->o_rowmap = s->o_cpos + BLm;
   // compacted rows: worth it when at least 15 % of the T x Bp rows are padding (profiles/r03_row_compaction_ab.log: even at
   // 10 %), and only for training batches
-  int64_t rv = 0;
-  for (int b = 0; b < B; ++b) rv += seq_len[b];
-  s->cmp = h->compactable && labels && rv * 20 <= (int64_t)T * Bp * 17;
-  s->Rv = s->cmp ? (int)rv : 0;
-  s->Rvp = s->cmp ? rup((int)rv, 64) : 0;
-  s->o_vrow = s->o_rowmap + (sr ? (size_t)Tp * Bp : 0);
+  s->cmp = h->compactable && b.labels && s->frames * 20 <= (int64_t)T * s->Bp * 17;
+  s->Rv = s->cmp ? (int)s->frames : 0;
+  s->Rvp = s->cmp ? rup(s->Rv, 64) : 0;
+  s->o_vrow = s->o_rowmap + (stack_reshape(h) ? (size_t)s->Tp * s->Bp : 0);
   s->o_vprev = s->o_vrow + s->Rvp;
   s->o_vnext = s->o_vprev + s->Rvp;
   s->o_aug = (s->o_vnext + s->Rvp + 3) / 4 * 4;      // (the kernel reads a mask as one int4)
-  const size_t nmeta = masked ? s->o_aug + (size_t)B * nm * 4 : s->o_vnext + s->Rvp;
-  const size_t nfeat = centre_form ? (size_t)B * T * ncep + B : (size_t)B * T * h->F;
-  bool grew = false;
-  if (!s->dmeta.ensure(nmeta * 4, &grew) || !s->dfeats.ensure(nfeat * 4, &grew) ||
-      !pinned_ensure(s->hmeta, &s->hmeta_cap, nmeta * 4) ||
-      (pinned_feats && !pinned_ensure(s->hfeats, &s->hfeats_cap, producer ? producer->stage_bytes : nfeat * 4)))
-    return h->fail(NASR_ERR_HIP, "allocation of a batch slot failed");
-  if (s->copy_valid) HIPCHK(h, hipEventSynchronize(s->ev_copy));          // the pinned mirrors are free to overwrite
-  if (s->released_valid && cs != h->st) HIPCHK(h, hipStreamWaitEvent(cs, s->ev_released, 0));   // and the device side unread
+  s->nmeta = masked ? s->o_aug + (size_t)B * s->aug_nm * 4 : s->o_vnext + s->Rvp;
+  s->nfeat = s->centre ? (size_t)B * T * b.ncep + B : (size_t)B * T * h->F;
+}
+
+// slot_fill (3): the meta block, as laid out, into the slot's pinned mirror
+static void write_meta(const nasr_ctx* h, BatchSlot* s, const BatchSrc& src) {
+  const int B = src.B, T = src.T, Bp = s->Bp, Tp = s->Tp, C = h->C, Lmax = src.Lmax, Lm = std::max(s->Lmax, 1), nm = s->aug_nm;
+  const int32_t *seq_len = src.seq_len, *labels = src.labels, *label_len = src.label_len;
+  const nasr_batch_aug* aug = src.aug;
   int32_t* m = static_cast<int32_t*>(s->hmeta.get());
-  memset(m, 0, nmeta * 4);
-  s->frames = 0;
-  for (int b = 0; b < B; ++b) {
-    m[s->o_seq + b] = seq_len[b];
-    s->frames += seq_len[b];
-  }
+  memset(m, 0, s->nmeta * 4);
+  memcpy(m + s->o_seq, seq_len, (size_t)B * 4);
   if (labels) {
-    for (int b = 0; b < B; ++b) m[s->o_lablen + b] = label_len[b];
+    memcpy(m + s->o_lablen, label_len, (size_t)B * 4);
     if (Lmax > 0) memcpy(m + s->o_labels, labels, (size_t)B * Lmax * 4);
     // the label positions of every utterance sorted by class (counting sort): the fixed summation order of ctc_grad
     std::vector<int32_t> fill((size_t)C);
@@ -288,7 +282,7 @@ int slot_fill(nasr_ctx* h, BatchSlot* s, const float* feats, const int32_t* seq_
       for (int i = 0; i < label_len[b]; ++i) m[s->o_cpos + (size_t)b * Lm + fill[lb[i]]++] = i;
     }
   }
-  if (sr) {
+  if (stack_reshape(h)) {
     // logits[t',b'] <- flat row q = b'*2T + t' of O = stack(fw,bw) [2,B,T,H];
     // physical row index in the [(t*Bp+b)*2 + d][Hp] view of the last layer's output.
     int32_t* map = m + s->o_rowmap;
@@ -315,43 +309,63 @@ int slot_fill(nasr_ctx* h, BatchSlot* s, const float* feats, const int32_t* seq_
         }
     for (; i < s->Rvp; ++i) vr[i] = vp[i] = vn[i] = -1;
   }
-  if (masked)
+  if (s->masked)
     for (int b = 0; b < B; ++b)
       for (int k = 0; k < nm; ++k) {
         int32_t* q = m + s->o_aug + ((size_t)b * nm + k) * 4;
         if (k < aug->n_time) { q[0] = aug->time_mask[((size_t)b * aug->n_time + k) * 2]; q[1] = aug->time_mask[((size_t)b * aug->n_time + k) * 2 + 1]; }
         if (k < aug->n_freq) { q[2] = aug->freq_mask[((size_t)b * aug->n_freq + k) * 2]; q[3] = aug->freq_mask[((size_t)b * aug->n_freq + k) * 2 + 1]; }
       }
-  if (producer) {
-    rc = producer->run(s->dfeats.as<float>(), s->dfeats.as<float>() + (size_t)B * T * ncep,
-                       pinned_feats ? s->hfeats.get() : nullptr, cs);
-    if (rc) {   // what the producer queued before it failed may still read the slot's pinned buffer: the next fill waits for it
-      if (hipEventRecord(s->ev_copy, cs) == hipSuccess) s->copy_valid = true;
-      return rc;
-    }
-  } else if (centre) {
-    const size_t nc = (size_t)B * T * ncep;
-    if (pinned_feats) {
-      memcpy(s->hfeats, centre, nc * 4);
-      memcpy(static_cast<float*>(s->hfeats.get()) + nc, pad_value, (size_t)B * 4);
-      HIPCHK(h, hipMemcpyAsync(s->dfeats.p, s->hfeats, (nc + B) * 4, hipMemcpyHostToDevice, cs));
-    } else {
-      HIPCHK(h, hipMemcpyAsync(s->dfeats.p, centre, nc * 4, hipMemcpyHostToDevice, cs));
-      HIPCHK(h, hipMemcpyAsync(s->dfeats.as<float>() + nc, pad_value, (size_t)B * 4, hipMemcpyHostToDevice, cs));
-    }
-  } else if (pinned_feats) {
-    memcpy(s->hfeats, feats, nfeat * 4);
-    HIPCHK(h, hipMemcpyAsync(s->dfeats.p, s->hfeats, nfeat * 4, hipMemcpyHostToDevice, cs));
-  } else {
-    HIPCHK(h, hipMemcpyAsync(s->dfeats.p, feats, nfeat * 4, hipMemcpyHostToDevice, cs));
+}
+
+// slot_fill (4): the features into s->dfeats on stream cs.  `pinned_feats` false: hipMemcpyAsync from the caller's pageable
+// memory, which returns when the source may be reused; true: through the slot's pinned feature buffer, a plain DMA that
+// overlaps whatever the compute stream runs.  A producer's kernels write the centre frames and pad values themselves.
+static int copy_feats(nasr_ctx* h, BatchSlot* s, const BatchSrc& b, hipStream_t cs, bool pinned_feats) {
+  const size_t nc = s->nfeat - b.B;        // centre form: the centre frames, then one pad value per utterance
+  float* d = s->dfeats.as<float>();
+  if (b.producer) {
+    const int rc = b.producer->run(d, d + nc, pinned_feats ? s->hfeats.get() : nullptr, cs);
+    // what the producer queued before it failed may still read the slot's pinned buffer: the next fill waits for it
+    if (rc && hipEventRecord(s->ev_copy, cs) == hipSuccess) s->copy_valid = true;
+    return rc;
   }
-  HIPCHK(h, hipMemcpyAsync(s->dmeta.p, s->hmeta, nmeta * 4, hipMemcpyHostToDevice, cs));
+  if (pinned_feats) {
+    float* p = static_cast<float*>(s->hfeats.get());
+    memcpy(p, b.centre ? b.centre : b.feats, (b.centre ? nc : s->nfeat) * 4);
+    if (b.centre) memcpy(p + nc, b.pad_value, (size_t)b.B * 4);
+    HIPCHK(h, hipMemcpyAsync(d, p, s->nfeat * 4, hipMemcpyHostToDevice, cs));
+  } else if (b.centre) {
+    HIPCHK(h, hipMemcpyAsync(d, b.centre, nc * 4, hipMemcpyHostToDevice, cs));
+    HIPCHK(h, hipMemcpyAsync(d + nc, b.pad_value, (size_t)b.B * 4, hipMemcpyHostToDevice, cs));
+  } else {
+    HIPCHK(h, hipMemcpyAsync(d, b.feats, s->nfeat * 4, hipMemcpyHostToDevice, cs));
+  }
+  return NASR_OK;
+}
+
+// Copies batch b into slot s, in the order the steps above are numbered: the integer arrays through the slot's pinned meta
+// buffer, the features as copy_feats says.  A batch in the centre form differs from a stacked one only in what dfeats
+// holds, and a produced one from a host one only in who writes it: the meta block and everything slot_commit does are the
+// same.  aug: SpecAugment masks behind the rest of the meta block; without a mask of non-zero width the slot is what it
+// is without aug.  All device copies (and a producer's kernels) go to stream cs and end with the slot's ev_copy.
+static int slot_fill(nasr_ctx* h, BatchSlot* s, const BatchSrc& b, hipStream_t cs, bool pinned_feats) {
+  bool masked = false;
+  if (int rc = check_batch(h, b, &masked)) return rc;
+  HIPCHK(h, hipSetDevice(h->device));
+  meta_layout(h, s, b, masked);
+  bool grew = false;
+  if (!s->dmeta.ensure(s->nmeta * 4, &grew) || !s->dfeats.ensure(s->nfeat * 4, &grew) ||
+      !pinned_ensure(s->hmeta, &s->hmeta_cap, s->nmeta * 4) ||
+      (pinned_feats && !pinned_ensure(s->hfeats, &s->hfeats_cap, b.producer ? b.producer->stage_bytes : s->nfeat * 4)))
+    return h->fail(NASR_ERR_HIP, "allocation of a batch slot failed");
+  if (s->copy_valid) HIPCHK(h, hipEventSynchronize(s->ev_copy));          // the pinned mirrors are free to overwrite
+  if (s->released_valid && cs != h->st) HIPCHK(h, hipStreamWaitEvent(cs, s->ev_released, 0));   // and the device side unread
+  write_meta(h, s, b);
+  if (int rc = copy_feats(h, s, b, cs, pinned_feats)) return rc;
+  HIPCHK(h, hipMemcpyAsync(s->dmeta.p, s->hmeta, s->nmeta * 4, hipMemcpyHostToDevice, cs));
   HIPCHK(h, hipEventRecord(s->ev_copy, cs));
   s->copy_valid = true;
-  s->B = B; s->T = T; s->Lmax = labels ? Lmax : 0; s->Bp = Bp; s->Tp = Tp; s->ctx = ctx; s->ncep = ncep;
-  s->has_labels = labels != nullptr;
-  s->centre = centre_form;
-  s->masked = masked; s->aug_nm = nm; s->aug_sw = masked ? aug->static_width : 0;
   return NASR_OK;
 }
 
@@ -423,14 +437,10 @@ int slot_commit(nasr_ctx* h, BatchSlot* s) {
   return NASR_OK;
 }
 
-// the synchronous upload of nasr_upload_batch / nasr_train_step / ...: fill on the compute stream, commit
-int upload(nasr_ctx* h, const float* feats, const int32_t* seq_len, const int32_t* labels, const int32_t* label_len,
-           int B, int T, int Lmax, const float* centre, const float* pad_value, int ctx, int ncep,
-           const CentreProducer* producer, const nasr_batch_aug* aug) {
+int upload(nasr_ctx* h, const BatchSrc& b) {
   BatchSlot* s = slot_acquire(h, false);
   if (!s) return h->fail(NASR_ERR_STATE, "every batch slot holds a staged batch: commit or discard one first");
-  int rc = slot_fill(h, s, feats, seq_len, labels, label_len, B, T, Lmax, centre, pad_value, ctx, ncep, h->st, false,
-                     producer, aug);
+  int rc = slot_fill(h, s, b, h->st, false);
   if (!rc) rc = slot_commit(h, s);
   if (rc && h->cur != s) slot_set_state(h, s, SLOT_FREE);
   return rc;
@@ -443,21 +453,14 @@ BatchSlot* slot_of_ticket(nasr_ctx* h, int ticket) {
   return (s->state == SLOT_STAGED && (int)(s->gen & 0x7fffff) == (ticket >> 8)) ? s : nullptr;
 }
 
-int stage(nasr_ctx* h, const float* feats, const int32_t* seq_len, const int32_t* labels, const int32_t* label_len, int B,
-          int T, int Lmax, const float* centre, const float* pad_value, int ctx, int ncep, int* ticket,
-          const CentreProducer* producer, const nasr_batch_aug* aug) {
+int stage(nasr_ctx* h, const BatchSrc& b, int* ticket) {
   if (!ticket) return h->fail(NASR_ERR_ARG, "null ticket");
   *ticket = -1;
   BatchSlot* s = slot_acquire(h, true);
   if (!s) return h->fail(NASR_ERR_STATE, "no free batch slot: commit or discard a staged batch first");
-  const int rc = slot_fill(h, s, feats, seq_len, labels, label_len, B, T, Lmax, centre, pad_value, ctx, ncep, h->cst, true,
-                           producer, aug);
-  if (rc) {
-    slot_set_state(h, s, SLOT_FREE);
-    return rc;
-  }
-  slot_set_state(h, s, SLOT_STAGED);
-  *ticket = (int)(s - h->slots) | (int)((s->gen & 0x7fffff) << 8);
-  return NASR_OK;
+  const int rc = slot_fill(h, s, b, h->cst, true);
+  slot_set_state(h, s, rc ? SLOT_FREE : SLOT_STAGED);
+  if (!rc) *ticket = (int)(s - h->slots) | (int)((s->gen & 0x7fffff) << 8);
+  return rc;
 }
 }  // namespace nasr_impl

@@ -168,6 +168,7 @@ struct BatchSlot {
   size_t o_vrow = 0, o_vprev = 0, o_vnext = 0;   // compacted rows of a ragged batch (Rv of them, padded to Rvp with -1), or unused
   int Rv = 0, Rvp = 0;
   bool cmp = false;
+  size_t nmeta = 0, nfeat = 0;                   // int32s of meta, floats of dfeats
   // SpecAugment masks of a centre-form batch (nasr_batch_aug): [B][aug_nm] of {t0, tw, f0, fw} at o_aug, or none
   size_t o_aug = 0;
   int aug_nm = 0, aug_sw = 0;
@@ -516,13 +517,44 @@ struct CentreProducer {
   size_t stage_bytes = 0;
   std::function<int(float* dcentre, float* dpad, void* pinned, hipStream_t cs)> run;
 };
-int upload(nasr_ctx* h, const float* feats, const int32_t* seq_len, const int32_t* labels, const int32_t* label_len,
-           int B, int T, int Lmax, const float* centre = nullptr, const float* pad_value = nullptr, int ctx = 0,
-           int ncep = 0, const CentreProducer* producer = nullptr, const nasr_batch_aug* aug = nullptr);
+// What a batch is, from the ABI entry point to its slot.  Exactly one source: feats (stacked [B][T][F]), centre + pad_value
+// (the centre form in host memory: centre frames [B][T][ncep] and one pad value per utterance) or producer (the centre
+// form, written on the device).  ctx and ncep (numcontext; the width of one un-stacked frame) mean something in the two
+// centre forms only.  labels, label_len and aug are nullable; aug needs a centre form.  Made by the three functions below.
+struct BatchSrc {
+  const float *feats = nullptr, *centre = nullptr, *pad_value = nullptr;
+  const CentreProducer* producer = nullptr;
+  int ctx = 0, ncep = 0;
+  const int32_t *seq_len = nullptr, *labels = nullptr, *label_len = nullptr;
+  int B = 0, T = 0, Lmax = 0;
+  const nasr_batch_aug* aug = nullptr;
+  bool centre_form() const { return centre || producer; }
+};
+inline BatchSrc stacked_batch(const float* feats, const int32_t* seq_len, const int32_t* labels, const int32_t* label_len, int B,
+                              int T, int Lmax) {
+  BatchSrc b;
+  b.feats = feats; b.seq_len = seq_len; b.labels = labels; b.label_len = label_len; b.B = B; b.T = T; b.Lmax = Lmax;
+  return b;
+}
+inline BatchSrc centre_batch(const float* centre, const float* pad_value, int ctx, int ncep, const int32_t* seq_len,
+                             const int32_t* labels, const int32_t* label_len, int B, int T, int Lmax,
+                             const nasr_batch_aug* aug) {
+  BatchSrc b = stacked_batch(nullptr, seq_len, labels, label_len, B, T, Lmax);
+  b.centre = centre; b.pad_value = pad_value; b.ctx = ctx; b.ncep = ncep; b.aug = aug;
+  return b;
+}
+inline BatchSrc produced_batch(const CentreProducer* producer, int ctx, int ncep, const int32_t* seq_len, const int32_t* labels,
+                               const int32_t* label_len, int B, int T, int Lmax, const nasr_batch_aug* aug) {
+  BatchSrc b = centre_batch(nullptr, nullptr, ctx, ncep, seq_len, labels, label_len, B, T, Lmax, aug);
+  b.producer = producer;
+  return b;
+}
+// A batch into a slot (slot_fill: check, lay out the meta block, size the buffers, wait for the slot, write the meta block,
+// copy the features, copy the meta block, record ev_copy), then: upload commits it on the compute stream (the synchronous
+// upload of nasr_upload_batch / nasr_train_step / ...), stage leaves it STAGED on the copy stream behind *ticket.
+int upload(nasr_ctx* h, const BatchSrc& b);
 BatchSlot* slot_of_ticket(nasr_ctx* h, int ticket);
-int stage(nasr_ctx* h, const float* feats, const int32_t* seq_len, const int32_t* labels, const int32_t* label_len, int B,
-          int T, int Lmax, const float* centre, const float* pad_value, int ctx, int ncep, int* ticket,
-          const CentreProducer* producer = nullptr, const nasr_batch_aug* aug = nullptr);
+int stage(nasr_ctx* h, const BatchSrc& b, int* ticket);
 
 // ---- mfcc.hip: the front end as the device producer of a batch slot (nasr_upload_batch_audio, nasr_stage_batch_audio)
 // what a front-end call works out on the host before anything is launched

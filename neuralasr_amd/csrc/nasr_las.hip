@@ -649,7 +649,7 @@ int nasr_las_forward(nasr_handle h, const float* feats, const int32_t* seq_len, 
   if (!s) return h ? h->fail(NASR_ERR_STATE, "nasr_las_forward: not a LAS handle") : NASR_ERR_ARG;
   if (!labels || !label_len) return h->fail(NASR_ERR_ARG, "nasr_las_forward needs labels");
   HIPCHK(h, hipSetDevice(h->device));
-  if (int rc = upload(h, feats, seq_len, labels, label_len, B, T, U)) return rc;
+  if (int rc = upload(h, stacked_batch(feats, seq_len, labels, label_len, B, T, U))) return rc;
   return las_forward_out(h, sample, logits_out);
 }
 

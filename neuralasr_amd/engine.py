@@ -3,7 +3,7 @@
 library behind include/nasr.h."""
 import collections
 import ctypes
-from ctypes import POINTER, byref, c_char, c_double, c_float, c_int32, c_int64, c_uint32, c_void_p
+from ctypes import POINTER, byref, c_char, c_double, c_float, c_int, c_int32, c_int64, c_uint32, c_void_p
 
 import numpy as np
 
@@ -23,7 +23,7 @@ def _fp(a):
 
 
 def _ip(a):
-    return a.ctypes.data_as(POINTER(c_int32))
+    return None if a is None else a.ctypes.data_as(POINTER(c_int32))
 
 
 class BatchAug(collections.namedtuple('BatchAug', 'static_width time_masks freq_masks')):
@@ -56,24 +56,29 @@ class Engine:
         pre, dropout = tuple(int(w) for w in pre), tuple(float(p) for p in dropout)
         if len(pre) > 3 or len(dropout) > 4:
             raise ValueError('at most 3 dense stages before the LSTM stack and one behind it')
-        self.cfg = _lib.ModelCfg(int(feature_size), int(hidden), int(num_layers), int(bool(bidirectional)), merge_id,
-                                 int(num_classes), float(forget_bias), float(learning_rate), float(beta1),
-                                 float(beta2), float(epsilon), len(pre), (c_int32 * 3)(*(pre + (0,) * (3 - len(pre)))),
-                                 int(post), float(relu_clip),
-                                 (c_float * 4)(*[dropout[i] if i < len(dropout) else 0.0 for i in range(4)]))
+        cfg = _lib.ModelCfg(int(feature_size), int(hidden), int(num_layers), int(bool(bidirectional)), merge_id,
+                            int(num_classes), float(forget_bias), float(learning_rate), float(beta1),
+                            float(beta2), float(epsilon), len(pre), (c_int32 * 3)(*(pre + (0,) * (3 - len(pre)))),
+                            int(post), float(relu_clip),
+                            (c_float * 4)(*[dropout[i] if i < len(dropout) else 0.0 for i in range(4)]))
+        self._open(self.lib.nasr_create, cfg, device_id, stream)
+
+    # ------------------------------------------------------------------ lifetime
+    def _open(self, create_fn, cfg, device_id, stream):
+        """What the three engine constructors share: the handle for `cfg` from the family's create call."""
         if stream is not None and int(stream) == 0:
             raise ValueError('stream 0 (the legacy default stream) cannot carry the engine: pass a created stream '
                              '(e.g. torch.cuda.Stream().cuda_stream) or None for an engine-owned one')
+        self.cfg = cfg
         self.h = c_void_p()
-        rc = self.lib.nasr_create(byref(self.cfg), int(device_id), c_void_p(stream) if stream else None, byref(self.h))
+        rc = create_fn(byref(cfg), int(device_id), c_void_p(stream) if stream else None, byref(self.h))
         if rc != 0:
             msg = self.lib.nasr_last_error(None)
             self.h = None
-            raise _lib.NasrError(rc, msg.decode() if msg else 'nasr_create failed')
-        self.num_classes = int(num_classes)
+            raise _lib.NasrError(rc, msg.decode() if msg else create_fn.__name__ + ' failed')
+        self.num_classes = int(cfg.num_classes)
         self.param_count = int(self.lib.nasr_param_count(self.h))
 
-    # ------------------------------------------------------------------ lifetime
     def close(self):
         if getattr(self, 'h', None):
             self.lib.nasr_destroy(self.h)
@@ -129,11 +134,14 @@ class Engine:
         self._ck(self.lib.nasr_set_learning_rate(self.h, float(lr)))
 
     # ------------------------------------------------------------------ host-buffer entry points
-    @staticmethod
-    def _batch(feats, seq_len, labels=None, label_len=None):
+    def _batch(self, feats, seq_len, labels=None, label_len=None):
+        """The arrays of a batch as the library takes them.  The library reads B*T*feature_size floats behind a bare
+        pointer: features of any other width are refused here, before any call."""
         feats = _f32(feats)
         assert feats.ndim == 3, 'features must be [B,T,F]'
-        B, T, _ = feats.shape
+        B, T, F = feats.shape
+        if F != self.cfg.feature_size:
+            raise ValueError(f'feature size {F} != configured {self.cfg.feature_size}')
         seq = _i32(np.asarray([int(x) for x in seq_len])).ravel()
         assert seq.size == B
         if labels is None:
@@ -150,8 +158,6 @@ class Engine:
 
     def forward(self, feats, seq_len):
         feats, seq, _, _, B, T, _ = self._batch(feats, seq_len)
-        if feats.shape[2] != self.cfg.feature_size:
-            raise ValueError(f'feature size {feats.shape[2]} != configured {self.cfg.feature_size}')
         out = np.empty((self.logit_frames(T), B, self.num_classes), np.float32)
         self._ck(self.lib.nasr_forward(self.h, _fp(feats), _ip(seq), B, T, _fp(out)))
         return out
@@ -218,6 +224,32 @@ class Engine:
                 return False
         return True
 
+    @classmethod
+    def _centre_form(cls, feats, seq, numcontext, numcep, bare=False):
+        """(centre frames [B,T,numcep], pad value [B]) that determine the stacked feats, or None when they do not have
+        include_context's structure (context_structure_ok); bare: un-stacked frames, taken as they are"""
+        if not bare and not cls.context_structure_ok(feats, seq, numcontext, numcep):
+            return None
+        return (np.ascontiguousarray(feats[:, :, numcontext * numcep:(numcontext + 1) * numcep]),
+                np.ascontiguousarray(feats[:, 0, 0]))
+
+    def _with_aug(self, name, aug, B):
+        """(entry point, its arguments behind the plain ones, what those point into - to be kept alive over the call):
+        `name` itself without masks, its _aug sibling with the BatchAug's struct with them"""
+        if aug is None:
+            return getattr(self.lib, name), (), None
+        st, keep = aug.struct(B)
+        return getattr(self.lib, name + '_aug'), (byref(st),), (st, keep)
+
+    def _ticket(self, rc, ticket):
+        """What a stage call returns: its ticket, or None when no staging slot was free; any other failure raises"""
+        if rc == _lib.NASR_ERR_STATE and ticket.value < 0:
+            msg = self.lib.nasr_last_error(self.h)
+            if msg and b'no free batch slot' in msg:
+                return None
+        self._ck(rc)
+        return int(ticket.value)
+
     def upload_batch_context(self, feats, seq_len, labels, label_len, numcontext, numcep, aug=None):
         """Upload context-stacked features [B,T,(2*numcontext+1)*numcep] as their centre slice and rebuild the
         stacking on the device (include_context, utils.py:8-21).  Returns False (nothing uploaded) when the
@@ -225,17 +257,12 @@ class Engine:
         `aug` (BatchAug): the kernel that stacks masks the centre frames first (nasr_upload_batch_context_aug)."""
         feats, seq, labels, ll, B, T, Lmax = self._batch(feats, seq_len, labels, label_len)
         bare = aug is not None and numcontext == 0 and feats.shape[2] == numcep      # un-stacked frames: masked as they are
-        if not bare and not self.context_structure_ok(feats, seq, numcontext, numcep):
+        form = self._centre_form(feats, seq, numcontext, numcep, bare)
+        if form is None:
             return False
-        pad = np.ascontiguousarray(feats[:, 0, 0])
-        centre = np.ascontiguousarray(feats[:, :, numcontext * numcep:(numcontext + 1) * numcep])
-        if aug is not None:
-            st, keep = aug.struct(B)
-            self._ck(self.lib.nasr_upload_batch_context_aug(self.h, _fp(centre), _fp(pad), int(numcontext), int(numcep),
-                                                            _ip(seq), _ip(labels), _ip(ll), B, T, Lmax, byref(st)))
-            return True
-        self._ck(self.lib.nasr_upload_batch_context(self.h, _fp(centre), _fp(pad), int(numcontext), int(numcep),
-                                                    _ip(seq), _ip(labels), _ip(ll), B, T, Lmax))
+        fn, tail, keep = self._with_aug('nasr_upload_batch_context', aug, B)
+        self._ck(fn(self.h, _fp(form[0]), _fp(form[1]), int(numcontext), int(numcep), _ip(seq), _ip(labels), _ip(ll), B, T,
+                    Lmax, *tail))
         return True
 
     def stage_batch(self, feats, seq_len, labels, label_len, numcontext=0, numcep=0):
@@ -243,20 +270,15 @@ class Engine:
         include/nasr.h nasr_stage_batch); may be called from a loader thread.  With numcontext > 0 and features that have
         include_context's structure only the centre slice crosses PCIe.  Returns a ticket for commit_batch(), or None
         when no staging slot is free (upload the batch the synchronous way then)."""
-        from ctypes import c_int
         feats, seq, labels, ll, B, T, Lmax = self._batch(feats, seq_len, labels, label_len)
         ticket = c_int(-1)
-        if numcontext > 0 and self.context_structure_ok(feats, seq, numcontext, numcep):
-            pad = np.ascontiguousarray(feats[:, 0, 0])
-            centre = np.ascontiguousarray(feats[:, :, numcontext * numcep:(numcontext + 1) * numcep])
-            rc = self.lib.nasr_stage_batch_context(self.h, _fp(centre), _fp(pad), int(numcontext), int(numcep), _ip(seq),
-                                                   _ip(labels), _ip(ll), B, T, Lmax, byref(ticket))
+        form = self._centre_form(feats, seq, numcontext, numcep)
+        if form is not None:
+            rc = self.lib.nasr_stage_batch_context(self.h, _fp(form[0]), _fp(form[1]), int(numcontext), int(numcep),
+                                                   _ip(seq), _ip(labels), _ip(ll), B, T, Lmax, byref(ticket))
         else:
             rc = self.lib.nasr_stage_batch(self.h, _fp(feats), _ip(seq), _ip(labels), _ip(ll), B, T, Lmax, byref(ticket))
-        if rc == _lib.NASR_ERR_STATE:
-            return None
-        self._ck(rc)
-        return int(ticket.value)
+        return self._ticket(rc, ticket)
 
     # ------------------------------------------------------------------ batches straight from audio (nasr_upload_batch_audio)
     @staticmethod
@@ -281,14 +303,12 @@ class Engine:
         return flat, offsets, r, labels, label_len, B, Lmax
 
     def _audio_call(self, fn, featurizer, audios, labels, label_len, rates, *tail):
-        from ctypes import c_int
         flat, offsets, r, labels, ll, B, Lmax = self._audio(audios, labels, label_len, rates)
         seq = np.zeros(max(B, 1), np.int32)
         T = c_int(0)
         fz = getattr(featurizer, 'h', featurizer)
-        rc = fn(self.h, fz, _fp(flat), offsets.ctypes.data_as(POINTER(c_int64)), None if r is None else _ip(r),
-                None if labels is None else _ip(labels), None if ll is None else _ip(ll), B, Lmax, _ip(seq), byref(T),
-                *tail)
+        rc = fn(self.h, fz, _fp(flat), offsets.ctypes.data_as(POINTER(c_int64)), _ip(r), _ip(labels), _ip(ll), B, Lmax,
+                _ip(seq), byref(T), *tail)
         return rc, seq[:B], int(T.value)
 
     def upload_batch_audio(self, featurizer, audios, labels, label_len, rates=None, aug=None):
@@ -296,34 +316,18 @@ class Engine:
         utterances `audios` (at `rates` Hz, None: all at its samplerate) on the device and writes them into this handle's
         batch slot; the batch is resident afterwards, as after upload_batch.  Returns (seq_len int32 [B], T).
         `aug` (BatchAug): SpecAugment masks on the normalised frames (nasr_upload_batch_audio_aug)."""
-        if aug is not None:
-            st, keep = aug.struct(len(audios))
-            rc, seq, T = self._audio_call(self.lib.nasr_upload_batch_audio_aug, featurizer, audios, labels, label_len, rates,
-                                          byref(st))
-            self._ck(rc)
-            return seq, T
-        rc, seq, T = self._audio_call(self.lib.nasr_upload_batch_audio, featurizer, audios, labels, label_len, rates)
+        fn, tail, keep = self._with_aug('nasr_upload_batch_audio', aug, len(audios))
+        rc, seq, T = self._audio_call(fn, featurizer, audios, labels, label_len, rates, *tail)
         self._ck(rc)
         return seq, T
 
     def stage_batch_audio(self, featurizer, audios, labels, label_len, rates=None, aug=None):
         """upload_batch_audio's staging half (stage_batch): copies and front-end kernels on the copy stream while the
         current step runs.  Returns (seq_len, T, ticket); ticket is None when no staging slot is free."""
-        from ctypes import c_int
         ticket = c_int(-1)
-        if aug is not None:
-            st, keep = aug.struct(len(audios))
-            rc, seq, T = self._audio_call(self.lib.nasr_stage_batch_audio_aug, featurizer, audios, labels, label_len, rates,
-                                          byref(st), byref(ticket))
-        else:
-            rc, seq, T = self._audio_call(self.lib.nasr_stage_batch_audio, featurizer, audios, labels, label_len, rates,
-                                          byref(ticket))
-        if rc == _lib.NASR_ERR_STATE and ticket.value < 0:
-            msg = self.lib.nasr_last_error(self.h)
-            if msg and b'no free batch slot' in msg:
-                return seq, T, None
-        self._ck(rc)
-        return seq, T, int(ticket.value)
+        fn, tail, keep = self._with_aug('nasr_stage_batch_audio', aug, len(audios))
+        rc, seq, T = self._audio_call(fn, featurizer, audios, labels, label_len, rates, *tail, byref(ticket))
+        return seq, T, self._ticket(rc, ticket)
 
     def forward_resident(self, B, T):
         """logits [T',B,C] of the resident batch (forward() without its upload)"""
@@ -351,8 +355,6 @@ class Engine:
         path[b][t] is the state of the extended label at logit frame t (-1 from seq_len[b] on), score[b] the path's
         log-probability.  Upload, forward and alignment, all on the device."""
         feats, seq, labels, ll, B, T, Lmax = self._batch(feats, seq_len, labels, label_len)
-        if feats.shape[2] != self.cfg.feature_size:
-            raise ValueError(f'feature size {feats.shape[2]} != configured {self.cfg.feature_size}')
         path = np.empty((B, self.logit_frames(T)), np.int32)
         score = np.empty(B, np.float64)
         self._ck(self.lib.nasr_ctc_align(self.h, _fp(feats), _ip(seq), _ip(labels), _ip(ll), B, T, Lmax, _ip(path),
@@ -661,20 +663,10 @@ class WaveNetEngine(Engine):
         rates = tuple(int(r) for r in rates)
         if len(rates) > 8:
             raise ValueError('at most 8 dilation rates')
-        self.cfg = _lib.WaveNetCfg(int(feature_size), int(num_classes), int(dim), int(kernel_size), int(num_blocks),
-                                   len(rates), (c_int32 * 8)(*(rates + (0,) * (8 - len(rates)))), float(bn_epsilon),
-                                   float(bn_decay), float(learning_rate), float(beta1), float(beta2), float(epsilon))
-        if stream is not None and int(stream) == 0:
-            raise ValueError('stream 0 (the legacy default stream) cannot carry the engine')
-        self.h = c_void_p()
-        rc = self.lib.nasr_create_wavenet(byref(self.cfg), int(device_id), c_void_p(stream) if stream else None,
-                                          byref(self.h))
-        if rc != 0:
-            msg = self.lib.nasr_last_error(None)
-            self.h = None
-            raise _lib.NasrError(rc, msg.decode() if msg else 'nasr_create_wavenet failed')
-        self.num_classes = int(num_classes)
-        self.param_count = int(self.lib.nasr_param_count(self.h))
+        cfg = _lib.WaveNetCfg(int(feature_size), int(num_classes), int(dim), int(kernel_size), int(num_blocks),
+                              len(rates), (c_int32 * 8)(*(rates + (0,) * (8 - len(rates)))), float(bn_epsilon),
+                              float(bn_decay), float(learning_rate), float(beta1), float(beta2), float(epsilon))
+        self._open(self.lib.nasr_create_wavenet, cfg, device_id, stream)
         self.bn_count = int(self.lib.nasr_wavenet_bn_count(self.h))
 
     def bn_state(self):
@@ -719,19 +711,10 @@ class LasEngine(Engine):
     def __init__(self, feature_size, num_classes, num_hidden=250, num_layers=4, sampling_probability=0.1, seed=1,
                  learning_rate=1e-4, beta1=0.9, beta2=0.999, epsilon=1e-8, device_id=0, stream=None):
         self.lib = _lib.load()
-        self.cfg = _lib.LasCfg(int(feature_size), int(num_classes), int(num_hidden), int(num_layers),
-                               float(sampling_probability), int(seed) & 0xFFFFFFFF, float(learning_rate), float(beta1),
-                               float(beta2), float(epsilon))
-        if stream is not None and int(stream) == 0:
-            raise ValueError('stream 0 (the legacy default stream) cannot carry the engine')
-        self.h = c_void_p()
-        rc = self.lib.nasr_create_las(byref(self.cfg), int(device_id), c_void_p(stream) if stream else None, byref(self.h))
-        if rc != 0:
-            msg = self.lib.nasr_last_error(None)
-            self.h = None
-            raise _lib.NasrError(rc, msg.decode() if msg else 'nasr_create_las failed')
-        self.num_classes = int(num_classes)
-        self.param_count = int(self.lib.nasr_param_count(self.h))
+        cfg = _lib.LasCfg(int(feature_size), int(num_classes), int(num_hidden), int(num_layers),
+                          float(sampling_probability), int(seed) & 0xFFFFFFFF, float(learning_rate), float(beta1),
+                          float(beta2), float(epsilon))
+        self._open(self.lib.nasr_create_las, cfg, device_id, stream)
         self._BU = (0, 0)
 
     def set_step_decode(self, on, logits=False, greedy=True):
@@ -812,8 +795,6 @@ class LasEngine(Engine):
         gather_tree's ids [B, T_dec, W]}, and with trace also every step's 'scores', 'word_ids', 'parent_ids'
         [B, T_dec, W] and the final 'log_probs', 'lengths', 'finished' [B, W]."""
         feats, seq, _, _, B, T, _ = self._batch(feats, seq_len)
-        if feats.shape[2] != self.cfg.feature_size:
-            raise ValueError(f'feature size {feats.shape[2]} != configured {self.cfg.feature_size}')
         steps = c_int32()
         self._ck(self.lib.nasr_las_beam_search(self.h, _fp(feats), _ip(seq), B, T, int(beam_width), int(max_steps),
                                                int(start_id), int(end_id), float(length_penalty), byref(steps)))

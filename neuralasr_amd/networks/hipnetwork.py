@@ -236,24 +236,23 @@ class HipNetwork(Network):
                              'length of the WHOLE batch: use features with num_gpus > 1 on this network')
         return AudioBatch(self.config.samplerate, audios, rates, self.config.feature_size)
 
-    def _upload_audio(self, b, labels=None, labels_len=None, masked=False):
-        """masked: a training step's upload, with the batch's SpecAugment masks when it carries any"""
-        aug = b.aug(self.config.numcep) if masked else None
+    def _upload_audio(self, b, labels=None, labels_len=None, aug=None):
         self.engine.upload_batch_audio(self.featurizer(), b.audios, labels, labels_len, b.rates, aug)
 
-    def _forward(self, mfccs, seq_len):
-        if isinstance(mfccs, AudioBatch):
-            self._upload_audio(mfccs)
-            return self.engine.forward_resident(len(mfccs), mfccs.shape[1])
-        return self.engine.forward(mfccs, seq_len)
-
-    def _upload(self, f, l, s, ll):
-        """the synchronous upload of one tower's shard for a training step"""
+    def _upload(self, f, l, s, ll, training=True):
+        """One tower's shard made the resident batch, the synchronous way; the only place that knows the kinds of batch.
+        Audio goes through the GPU front end, features cross as they are.  training: a training step's upload - audio with
+        the batch's SpecAugment masks when it carries any, features as their centre slice where _context() allows it
+        (inference uploads the whole stacked array, as engine.forward / loss / greedy_decode / align do)."""
+        ctx = self._context() if training else 0
         if isinstance(f, AudioBatch):
-            self._upload_audio(f, l, ll, masked=True)
-        elif not (self._use_device_context() and
-                  self.engine.upload_batch_context(f, s, l, ll, self.config.numcontext, self._frame_width())):
+            self._upload_audio(f, l, ll, f.aug(self.config.numcep) if training else None)
+        elif not (ctx and self.engine.upload_batch_context(f, s, l, ll, ctx, self._frame_width())):
             self.engine.upload_batch(f, s, l, ll)
+
+    def _forward(self, mfccs, seq_len):
+        self._upload(mfccs, None, seq_len, None, training=False)
+        return self.engine.forward_resident(len(seq_len), np.shape(mfccs)[1])
 
     def language_model(self):
         """The n-gram model of config.lm_file (lm.py), or None without the key: evaluate() and decode() fuse it into
@@ -270,20 +269,16 @@ class HipNetwork(Network):
                 return self.engine.beam_search(logits, seq_len, self.beam_width, merge_repeated=True)[0]
             return self.engine.beam_search(logits, seq_len, self.beam_width, merge_repeated=True, lm=lm,
                                            lm_weight=self.config.lm_weight, lm_bonus=self.config.lm_bonus)[0]
-        if isinstance(mfccs, AudioBatch):
-            def run():
-                self._upload_audio(mfccs)
-                return self.engine.greedy_decode_resident(len(mfccs), mfccs.shape[1])
-            return self._retry_aborted(run)
-        return self._retry_aborted(lambda: self.engine.greedy_decode(mfccs, seq_len))
+
+        def run():
+            self._upload(mfccs, None, seq_len, None, training=False)
+            return self.engine.greedy_decode_resident(len(seq_len), np.shape(mfccs)[1])
+        return self._retry_aborted(run)
 
     def _loss_ler_one(self, mfccs, labels, seq_len, labels_len, lm=None):
         def run():
-            if isinstance(mfccs, AudioBatch):
-                self._upload_audio(mfccs, labels, labels_len)
-                loss, _ = self.engine.loss_resident(len(mfccs))
-            else:
-                loss, _ = self.engine.loss(mfccs, seq_len, labels, labels_len)
+            self._upload(mfccs, labels, seq_len, labels_len, training=False)
+            loss, _ = self.engine.loss_resident(len(seq_len))
             hyps = None if self.decoder == 'beam' else self.engine.get_decoded(len(seq_len), np.shape(mfccs)[1])
             return loss, hyps
         loss, hyps = self._retry_aborted(run)
@@ -446,11 +441,12 @@ class HipNetwork(Network):
             loss, ler = self.coll.mean_scalars([loss, ler])
         return np.float32(loss), np.float32(ler)
 
-    def _use_device_context(self):
+    def _context(self):
+        """numcontext when training batches of features go to the GPU as their centre slice, else 0"""
         # rand_shift's roll-and-crop (dataset.py:23-31) leaves real neighbour frames where include_context put its pad
         # in the first / last numcontext frames: such batches are uploaded whole
-        return (self.device_context and getattr(self.config, 'numcontext', 0) > 0 and
-                not getattr(self.config, 'rand_shift', 0) > 0)
+        ctx = getattr(self.config, 'numcontext', 0)
+        return ctx if self.device_context and ctx > 0 and not getattr(self.config, 'rand_shift', 0) > 0 else 0
 
     # ------------------------------------------------------------------ input pipeline (SURVEY.md §8f row 2)
     def stage_batch(self, mfccs, labels, seq_len, labels_len):
@@ -465,8 +461,7 @@ class HipNetwork(Network):
         if isinstance(f, AudioBatch):
             ticket = self.engine.stage_batch_audio(self.featurizer(), f.audios, l, ll, f.rates, f.aug(self.config.numcep))[2]
         else:
-            ctx = self.config.numcontext if self._use_device_context() else 0
-            ticket = self.engine.stage_batch(f, s, l, ll, ctx, self._frame_width())
+            ticket = self.engine.stage_batch(f, s, l, ll, self._context(), self._frame_width())
         if ticket is None:
             return False
         with self._staged_lock:
@@ -554,10 +549,8 @@ class HipNetwork(Network):
         labels = np.asarray(labels, dtype=np.int32).reshape(len(seq_len), -1)
 
         def run():
-            if isinstance(mfccs, AudioBatch):
-                self._upload_audio(mfccs, labels, labels_len)
-                return self.engine.align_resident(len(mfccs), mfccs.shape[1])
-            return self.engine.align(mfccs, seq_len, labels, labels_len)
+            self._upload(mfccs, labels, seq_len, labels_len, training=False)
+            return self.engine.align_resident(len(seq_len), np.shape(mfccs)[1])
         path, score = self._retry_aborted(run)
         return [(float(score[b]), spans(path[b], labels[b, :int(labels_len[b])])) for b in range(len(seq_len))]
 

@@ -113,6 +113,7 @@ class LAS(HipNetwork):
     num_layers = 4
     bidirectional = True
     merge = 'none'
+    device_context = False                   # features are uploaded whole
     sampling_probability = 0.1
     sampling_seed = 1
     # the inference graph (networks/las.py, fortraining=False)
@@ -163,7 +164,7 @@ class LAS(HipNetwork):
         samples), so time-sliced towers and one process per tower feed the same inputs"""
         p, seed, _, _ = self.engine.sampling_state()
         self.engine.set_sampling_state(p, seed, counter, tower)
-        self._upload(f, l, s, ll, masked=grads)      # (validate runs the training graph on unmasked features)
+        self._upload(f, l, s, ll, training=grads)      # (validate runs the training graph on unmasked features)
         if grads:
             self.engine.compute_grads()
         else:
@@ -213,14 +214,6 @@ class LAS(HipNetwork):
 
     def stage_batch(self, mfccs, labels, seq_len, labels_len):
         return False
-
-    def _upload(self, f, l, s, ll, masked=False):
-        """one tower's shard into the handle's batch slot: audio through the GPU front end, features as they are;
-        masked: a training step's upload, with the batch's SpecAugment masks when it carries any"""
-        if isinstance(f, AudioBatch):
-            self._upload_audio(f, l, ll, masked=masked)
-        else:
-            self.engine.upload_batch(f, s, l, ll)
 
     def _settle(self):
         pass
