@@ -262,6 +262,29 @@ int nasr_grad_bucket_count(nasr_handle h);
 int nasr_grad_bucket(nasr_handle h, int i, int64_t* offset, int64_t* count);
 int nasr_grad_bucket_wait(nasr_handle h, int i, void* hip_stream);
 int nasr_apply_adam(nasr_handle h, float grad_scale);
+/* Global-norm gradient clipping with a non-finite guard (not part of the reference, whose optimiser step
+ * - tfnetwork.py:116-139, average_gradients then apply_gradients - clips nothing and checks nothing).  With max_norm > 0
+ * nasr_apply_adam (and nasr_train_step through it) first measures norm = |grad_scale| * sqrt(sum g_i^2) of the gradient
+ * buffer as it stands then, i.e. after an all-reduce, in fp64 and in a fixed order (the same bits on every run and every
+ * rank), and decides on the device, without a host round trip:
+ *   - fault word set: the step is void as ever; nothing is measured, scaled or counted;
+ *   - norm not finite: the step is SKIPPED - parameters, moments and Adam's step count stay as they were, `skipped`
+ *     counts it; the fault word stays 0, so the step is not void, is not repeated and nasr_settle_* report nothing;
+ *   - otherwise coef = norm > max_norm ? max_norm / norm : 1 (tf.clip_by_global_norm's rule; in double, rounded to fp32)
+ *     and Adam runs on g * (grad_scale * coef), one fp32 product per element: with coef == 1 bit for bit the step
+ *     without clipping.  max_norm = +inf measures and guards but never scales.
+ * 0 = off (the default): nasr_apply_adam launches exactly what it launched before.  Negative or NaN: NASR_ERR_ARG.
+ * nasr_get_grad_clip_stats synchronises: norm and coefficient of the last step that was not void, the largest finite norm and the
+ * numbers of applied (steps), scaled (clipped) and skipped steps since the window was last cleared (reset != 0 clears
+ * it behind the read). */
+typedef struct {
+  double last_norm, window_max_norm;
+  float last_coef;
+  int64_t steps, clipped, skipped;
+} nasr_clip_stats;
+int nasr_set_grad_clip(nasr_handle h, float max_norm);
+int nasr_get_grad_clip(nasr_handle h, float* max_norm);
+int nasr_get_grad_clip_stats(nasr_handle h, nasr_clip_stats* out, int reset);
 /* Diagnostics - what ONE GPU can show of a collective that co-runs with the step (average_gradients moved under the
  * backward pass, tfnetwork.py:72-86): waits on `hip_stream` for bucket i like nasr_grad_bucket_wait, then launches there a
  * kernel shaped like a ring all-reduce step over that bucket - nblocks workgroups of 256 threads, each sweeping its slice

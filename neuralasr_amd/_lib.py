@@ -44,6 +44,7 @@ SYMBOLS = [
     'nasr_greedy_decode_resident',
     'nasr_upload_batch_context_aug', 'nasr_upload_batch_audio_aug', 'nasr_stage_batch_audio_aug',
     'nasr_ctc_align', 'nasr_ctc_align_resident', 'nasr_ctc_align_logits', 'nasr_ctc_align_lds', 'nasr_resident_shape',
+    'nasr_set_grad_clip', 'nasr_get_grad_clip', 'nasr_get_grad_clip_stats',
 ]
 
 
@@ -86,6 +87,14 @@ class PhaseTimes(Structure):
     _fields_ = [('pack_ms', c_float), ('xproj_ms', c_float), ('rec_fwd_ms', c_float), ('proj_ctc_ms', c_float),
                 ('proj_bwd_ms', c_float), ('rec_bwd_ms', c_float), ('wgrad_ms', c_float), ('adam_ms', c_float),
                 ('total_ms', c_float), ('rec_fwd_launches', c_int32), ('rec_bwd_launches', c_int32)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+class ClipStats(Structure):
+    _fields_ = [('last_norm', c_double), ('window_max_norm', c_double), ('last_coef', c_float), ('steps', c_int64),
+                ('clipped', c_int64), ('skipped', c_int64)]
 
     def as_dict(self):
         return {n: getattr(self, n) for n, _ in self._fields_}
@@ -144,6 +153,9 @@ def load():
         'nasr_grad_bucket': (c_int, [H, c_int, POINTER(c_int64), POINTER(c_int64)]),
         'nasr_grad_bucket_wait': (c_int, [H, c_int, c_void_p]),
         'nasr_apply_adam': (c_int, [H, c_float]),
+        'nasr_set_grad_clip': (c_int, [H, c_float]),
+        'nasr_get_grad_clip': (c_int, [H, fp]),
+        'nasr_get_grad_clip_stats': (c_int, [H, POINTER(ClipStats), c_int]),
         'nasr_get_grads': (c_int, [H, fp, c_int64]),
         'nasr_set_grads': (c_int, [H, fp, c_int64]),
         'nasr_label_error_rate': (c_int, [ip, ip, c_int, ip, ip, c_int, c_int, fp]),

@@ -11,7 +11,10 @@ Seven more optional [Parameters] keys switch on the augmentation of `train --fro
 reference has none but rand_shift): spec_time_masks / spec_freq_masks (masks per utterance, 0..8, default 0),
 spec_time_width / spec_freq_width (largest width in frames / static columns, default 0), spec_time_ratio (largest time
 mask as a share of the utterance, default 1.0), speed_perturb (comma-separated factors, each in (0.5, 2.0), default none)
-and augment_seed (default 0); without them nothing changes."""
+and augment_seed (default 0); without them nothing changes.  One more optional [Parameters] key, max_grad_norm, switches
+on global-norm gradient clipping with a non-finite guard in the optimiser step (the reference clips
+nothing): absent or 0 = off, a positive number = tf.clip_by_global_norm's threshold, inf = measure and guard only; only
+training reads it."""
 import importlib
 from configparser import ConfigParser, ExtendedInterpolation
 
@@ -70,6 +73,7 @@ class Config(object):
         self.lm_weight = float(par['lm_weight']) if 'lm_weight' in par else 0.0
         self.lm_bonus = float(par['lm_bonus']) if 'lm_bonus' in par else 0.0
         self._read_augment(par, configfile)
+        self.max_grad_norm = self._read_max_grad_norm(par, configfile)
         # the configured batch is per GPU (reference: config.py:35-36)
         self.batch_size *= self.num_gpus if self.num_gpus > 0 else 1
         self.symbols = Symbols(self.label_context, self.sym_file) if isTraining else Symbols(self.label_context)
@@ -111,6 +115,19 @@ class Config(object):
             if not self.speed_perturb or not all(0.5 < f < 2.0 for f in self.speed_perturb):
                 raise ValueError("'speed_perturb' must be comma-separated factors, each in (0.5, 2.0), not %r, in %s"
                                  % (par['speed_perturb'], configfile))
+
+    @staticmethod
+    def _read_max_grad_norm(par, configfile):
+        if 'max_grad_norm' not in par:
+            return 0.0
+        try:
+            v = float(par['max_grad_norm'].strip())
+        except ValueError:
+            v = -1.0
+        if not v >= 0.0:        # negative, NaN, or not a number at all
+            raise ValueError("'max_grad_norm' must be 0 (off), a positive number or inf, not %r, in %s"
+                             % (par['max_grad_norm'], configfile))
+        return v
 
     @property
     def augment_on(self):

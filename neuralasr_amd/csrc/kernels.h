@@ -244,6 +244,16 @@ int launch_ctc_align(const CtcDims& d, int F, const float* logits, const float* 
 struct AdamDev { long long step; float lr_t; int applied; };
 void launch_adam(float* p, float* m, float* v, const float* g, int64_t n, AdamDev* state, float lr, float beta1, float beta2,
                  float eps, float gscale, const float* fault, hipStream_t st);
+// Global-norm clipping (nasr_set_grad_clip): what the second stage of the norm decides for the step, on the device.  s is
+// the multiplier the Adam pass reads (grad_scale * coef); skip = 1: the norm was not finite, the step touches nothing.
+// window_max_norm .. skipped are the window nasr_get_grad_clip_stats(reset) clears.
+struct ClipDev { double last_norm; float last_coef, s; int skip, pad; double window_max_norm; long long steps, clipped, skipped; };
+constexpr int GRAD_SUMSQ_MAX_BLOCKS = 1024;
+int grad_sumsq_blocks(int64_t n);   // workgroups (= partial sums) of the norm's first stage: a function of n alone
+// launch_adam behind the norm of g: `part` holds GRAD_SUMSQ_MAX_BLOCKS doubles.  max_norm > 0 or +inf.
+void launch_adam_clipped(float* p, float* m, float* v, const float* g, int64_t n, AdamDev* state, ClipDev* clip, double* part,
+                         float lr, float beta1, float beta2, float eps, float gscale, float max_norm, const float* fault,
+                         hipStream_t st);
 // out[n] = sum_r M[r*ld + n], deterministic two-stage; ws holds 32*N floats
 void launch_colsum(const float* M, int R, int N, int ld, float* out, float* ws, hipStream_t st);
 void launch_colsum_parts(const float* part, int nparts, int N, float* out, hipStream_t st);   // out[n] = sum_k part[k][n]

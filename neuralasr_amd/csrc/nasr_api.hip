@@ -59,7 +59,13 @@ bool alloc_param_buffers(nasr_ctx* h) {
   if (hipMalloc(h->P.out(), nb) != hipSuccess || hipMalloc(h->M.out(), nb) != hipSuccess || hipMalloc(h->V.out(), nb) != hipSuccess ||
       hipMalloc(h->Gbase.out(), gb) != hipSuccess || hipMalloc(h->adam_dev.out(), sizeof(AdamDev)) != hipSuccess)
     return false;
+  if (hipMalloc(h->clip_dev.out(), sizeof(ClipDev)) != hipSuccess ||
+      hipMalloc(h->clip_part.out(), GRAD_SUMSQ_MAX_BLOCKS * sizeof(double)) != hipSuccess)
+    return false;
   (void)hipMemsetAsync(h->adam_dev, 0, sizeof(AdamDev), h->st);
+  static const ClipDev clip0{0.0, 1.f, 1.f, 0, 0, 0.0, 0, 0, 0};   // nothing measured yet: coef 1
+  (void)hipMemcpyAsync(h->clip_dev, &clip0, sizeof(ClipDev), hipMemcpyHostToDevice, h->st);
+  (void)hipMemsetAsync(h->clip_part, 0, GRAD_SUMSQ_MAX_BLOCKS * sizeof(double), h->st);
   (void)hipMemsetAsync(h->P, 0, nb, h->st);
   (void)hipMemsetAsync(h->M, 0, nb, h->st);
   (void)hipMemsetAsync(h->V, 0, nb, h->st);
@@ -576,8 +582,12 @@ int nasr_apply_adam(nasr_handle h, float grad_scale) {
   HIPCHK(h, hipSetDevice(h->device));
   {
     PhaseScope ps(h, PH_ADAM);
-    launch_adam(h->P, h->M, h->V, h->G, h->np_int, h->adam_dev, h->lr, h->cfg.beta1, h->cfg.beta2, h->cfg.epsilon, grad_scale,
-                h->Gbase, h->st);
+    if (h->max_grad_norm > 0.f)   // the norm of the (all-reduced) gradient first; its second stage decides the step on the device
+      launch_adam_clipped(h->P, h->M, h->V, h->G, h->np_int, h->adam_dev, h->clip_dev, h->clip_part, h->lr, h->cfg.beta1,
+                          h->cfg.beta2, h->cfg.epsilon, grad_scale, h->max_grad_norm, h->Gbase, h->st);
+    else
+      launch_adam(h->P, h->M, h->V, h->G, h->np_int, h->adam_dev, h->lr, h->cfg.beta1, h->cfg.beta2, h->cfg.epsilon, grad_scale,
+                  h->Gbase, h->st);
     int rc = repack(h);
     if (rc) return rc;
     // the step's fault word as it stands now (all-reduced with the gradients): read later, without a stream sync
@@ -594,6 +604,41 @@ int nasr_apply_adam(nasr_handle h, float grad_scale) {
     h->total_valid = true;
   }
   h->have_grads = false;
+  return NASR_OK;
+}
+
+int nasr_set_grad_clip(nasr_handle h, float max_norm) {
+  MODEL_CALL(h);
+  if (!h) return NASR_ERR_ARG;
+  if (!(max_norm >= 0.f)) return h->fail(NASR_ERR_ARG, "nasr_set_grad_clip: max_norm must be 0 (off), positive or +inf");
+  h->max_grad_norm = max_norm;
+  return NASR_OK;
+}
+
+int nasr_get_grad_clip(nasr_handle h, float* max_norm) {
+  MODEL_CALL(h);
+  if (!h || !max_norm) return NASR_ERR_ARG;
+  *max_norm = h->max_grad_norm;
+  return NASR_OK;
+}
+
+int nasr_get_grad_clip_stats(nasr_handle h, nasr_clip_stats* out, int reset) {
+  MODEL_CALL(h);
+  if (!h || !out) return NASR_ERR_ARG;
+  HIPCHK(h, hipSetDevice(h->device));
+  ClipDev d{};
+  HIPCHK(h, hipMemcpyAsync(&d, h->clip_dev, sizeof(d), hipMemcpyDeviceToHost, h->st));
+  if (reset) {   // the window: its largest norm and the three counters, the tail of ClipDev
+    constexpr size_t off = offsetof(ClipDev, window_max_norm);
+    HIPCHK(h, hipMemsetAsync(reinterpret_cast<char*>(h->clip_dev.get()) + off, 0, sizeof(ClipDev) - off, h->st));
+  }
+  if (int rc = sync_checked(h)) return rc;
+  out->last_norm = d.last_norm;
+  out->window_max_norm = d.window_max_norm;
+  out->last_coef = d.last_coef;
+  out->steps = d.steps;
+  out->clipped = d.clipped;
+  out->skipped = d.skipped;
   return NASR_OK;
 }
 

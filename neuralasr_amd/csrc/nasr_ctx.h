@@ -313,6 +313,11 @@ struct nasr_ctx {
   // it alone, so a void step never enters the bias correction - whenever the host learns about it.
   DevPtr<AdamDev> adam_dev;
   float lr;
+  // Global-norm gradient clipping (nasr_set_grad_clip; 0 = off, the default: nasr_apply_adam then launches what it always
+  // did).  The norm, the decision and the counters live on the device beside AdamDev, so the step stays asynchronous.
+  float max_grad_norm = 0.f;
+  DevPtr<ClipDev> clip_dev;
+  DevPtr<double> clip_part;                  // GRAD_SUMSQ_MAX_BLOCKS partial sums of squares
   // Results of a step without waiting for its end (nasr_get_step_results): loss, the fault word as it stands after the
   // forward pass, and the greedy decode are copied to pinned memory right behind the CTC forward kernels; the fault
   // word at the END of a step is copied behind its Adam launch (nasr_settle_step).  Two slots each: the host may be
@@ -454,7 +459,7 @@ inline ActScale dense_in_scale(const nasr_ctx* h, int i) {
 // (the caller's, or one of its own) in place; prop: the device's properties, or NULL
 int handle_open(const char* fn, Family family, int device_id, void* stream, nasr_ctx** out, hipDeviceProp_t* prop);
 int create_fail(nasr_ctx* h, int code, const std::string& m);   // destroys the handle
-bool alloc_param_buffers(nasr_ctx* h);   // P, M, V, G behind its head and Adam's state for np_int floats, zeroed
+bool alloc_param_buffers(nasr_ctx* h);   // P, M, V, G behind its head, Adam's and the clipping state for np_int floats, zeroed
 // once h->buckets is laid out: their events, the copy and logits streams, the batch slots' events, the step-result stamps
 // and step-end words, the timing events; then a synchronise.  A failure destroys the handle.
 int handle_finish(nasr_ctx* h);

@@ -6,6 +6,10 @@
 //   p <- p - lr_t * m / (sqrt(v) + eps)          (eps NOT bias-corrected)
 // `gscale` folds average_gradients' 1/num_towers (networks/tfnetwork.py:72-86) into the same pass.
 // One pass reads g,m,v,p and writes m,v,p with 16-byte accesses: 28 B/param, HBM-bound.
+//
+// Global-norm gradient clipping with a non-finite guard (nasr_set_grad_clip; the reference has neither): a deterministic
+// two-stage fp64 sum of squares of the gradient buffer, whose second stage decides the step on the device and leaves the
+// multiplier for the Adam pass in device memory (ClipDev).  With clipping off none of it is launched.
 #include "kernels.h"
 
 #include <cstdlib>
@@ -20,17 +24,42 @@ const char* test_hook(const char* name) {
   return enabled ? getenv(name) : nullptr;
 }
 
-// t <- t + 1 and lr_t = lr*sqrt(1-b2^t)/(1-b1^t) in double, by one thread, unless the step is void
-__global__ void adam_prepare_kernel(AdamDev* st, const float* __restrict__ fault, float lr, float b1, float b2) {
-  if (fault && *fault != 0.f) {
-    st->applied = 0;
-    return;
-  }
+// t <- t + 1 and lr_t = lr*sqrt(1-b2^t)/(1-b1^t) in double, by one thread
+__device__ __forceinline__ void adam_advance(AdamDev* st, float lr, float b1, float b2) {
   const long long t = st->step + 1;
   st->step = t;
   st->lr_t = (float)((double)lr * sqrt(1.0 - pow((double)b2, (double)t)) / (1.0 - pow((double)b1, (double)t)));
   st->applied = 1;
 }
+
+// ... unless the step is void
+__global__ void adam_prepare_kernel(AdamDev* st, const float* __restrict__ fault, float lr, float b1, float b2) {
+  if (fault && *fault != 0.f) {
+    st->applied = 0;
+    return;
+  }
+  adam_advance(st, lr, b1, b2);
+}
+
+// the sweep of both Adam kernels, behind their void-step check; `gscale` is the step's multiplier and `lr_t` its step size
+#define NASR_ADAM_SWEEP                                                                                                   \
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {       \
+    float4 gg = reinterpret_cast<const float4*>(g)[i];                                                                    \
+    float4 mm = reinterpret_cast<float4*>(m)[i];                                                                          \
+    float4 vv = reinterpret_cast<float4*>(v)[i];                                                                          \
+    float4 pp = reinterpret_cast<float4*>(p)[i];                                                                          \
+    NASR_ADAM1(x) NASR_ADAM1(y) NASR_ADAM1(z) NASR_ADAM1(w)                                                               \
+    reinterpret_cast<float4*>(m)[i] = mm;                                                                                 \
+    reinterpret_cast<float4*>(v)[i] = vv;                                                                                 \
+    reinterpret_cast<float4*>(p)[i] = pp;                                                                                 \
+  }
+#define NASR_ADAM1(c)                                   \
+  {                                                     \
+    const float gc = gg.c * gscale;                     \
+    mm.c = b1 * mm.c + (1.f - b1) * gc;                 \
+    vv.c = b2 * vv.c + (1.f - b2) * gc * gc;            \
+    pp.c = pp.c - lr_t * mm.c / (sqrtf(vv.c) + eps);    \
+  }
 
 __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, float* __restrict__ m, float* __restrict__ v,
                                                    const float* __restrict__ g, int64_t n4, const AdamDev* __restrict__ st,
@@ -40,24 +69,94 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, float*
   // gradients, so every rank sees it): such a step must not touch the parameters, on any rank.
   if (fault && *fault != 0.f) return;
   const float lr_t = st->lr_t;
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
-    float4 gg = reinterpret_cast<const float4*>(g)[i];
-    float4 mm = reinterpret_cast<float4*>(m)[i];
-    float4 vv = reinterpret_cast<float4*>(v)[i];
-    float4 pp = reinterpret_cast<float4*>(p)[i];
-#define NASR_ADAM1(c)                                   \
-  {                                                     \
-    const float gc = gg.c * gscale;                     \
-    mm.c = b1 * mm.c + (1.f - b1) * gc;                 \
-    vv.c = b2 * vv.c + (1.f - b2) * gc * gc;            \
-    pp.c = pp.c - lr_t * mm.c / (sqrtf(vv.c) + eps);    \
-  }
-    NASR_ADAM1(x) NASR_ADAM1(y) NASR_ADAM1(z) NASR_ADAM1(w)
+  NASR_ADAM_SWEEP
+}
+
+// the same with the multiplier of this step read from ClipDev: grad_scale * coef, or nothing at all for a skipped step
+__global__ __launch_bounds__(256) void adam_clip_kernel(float* __restrict__ p, float* __restrict__ m, float* __restrict__ v,
+                                                        const float* __restrict__ g, int64_t n4,
+                                                        const AdamDev* __restrict__ st, const ClipDev* __restrict__ clip,
+                                                        float b1, float b2, float eps, const float* __restrict__ fault) {
+  if (fault && *fault != 0.f) return;
+  if (clip->skip) return;
+  const float lr_t = st->lr_t;
+  const float gscale = clip->s;
+  NASR_ADAM_SWEEP
+}
 #undef NASR_ADAM1
-    reinterpret_cast<float4*>(m)[i] = mm;
-    reinterpret_cast<float4*>(v)[i] = vv;
-    reinterpret_cast<float4*>(p)[i] = pp;
+#undef NASR_ADAM_SWEEP
+
+// ---- the global norm: n2 = sum_i (double)g_i * (double)g_i, the same bits on every run ----------------------------------
+// The square of an fp32 value is exact in fp64 and every partial sum is rounded once, in an order that depends on the
+// element count alone: lane j of workgroup b adds the float4s lo_b + j, lo_b + j + 256, ... of b's contiguous share
+// (one accumulator per component, combined (x+y)+(z+w)), the 64 lanes of a wave fold by halves (32, 16, ... 1), the four
+// waves combine through LDS as (0+1)+(2+3).  No atomics.
+__device__ __forceinline__ double block_sum_fixed(double a, double* sm) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) a += __shfl_down(a, off, 64);
+  if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = a;
+  __syncthreads();
+  return (sm[0] + sm[1]) + (sm[2] + sm[3]);
+}
+
+int grad_sumsq_blocks(int64_t n) {
+  const int64_t b = (n / 4 + 255) / 256;    // a share is at least one 16-byte load per lane
+  return b < 1 ? 1 : b > GRAD_SUMSQ_MAX_BLOCKS ? GRAD_SUMSQ_MAX_BLOCKS : (int)b;
+}
+
+__global__ __launch_bounds__(256) void grad_sumsq_part_kernel(const float* __restrict__ g, int64_t n,
+                                                              double* __restrict__ part, const float* __restrict__ fault) {
+  __shared__ double sm[4];
+  if (fault && *fault != 0.f) return;   // a void step: nothing is measured (grad_clip_final_kernel returns as well)
+  const int64_t n4 = n / 4;
+  const int64_t per = (n4 + gridDim.x - 1) / gridDim.x;
+  const int64_t lo = per * blockIdx.x, hi = lo + per < n4 ? lo + per : n4;
+  double ax = 0.0, ay = 0.0, az = 0.0, aw = 0.0;
+#pragma unroll 4
+  for (int64_t i = lo + threadIdx.x; i < hi; i += 256) {
+    const float4 v = reinterpret_cast<const float4*>(g)[i];
+    ax += (double)v.x * (double)v.x;
+    ay += (double)v.y * (double)v.y;
+    az += (double)v.z * (double)v.z;
+    aw += (double)v.w * (double)v.w;
   }
+  if (blockIdx.x == 0 && threadIdx.x == 0)
+    for (int64_t i = n4 * 4; i < n; ++i) ax += (double)g[i] * (double)g[i];   // (every layout here is a multiple of 4)
+  const double s = block_sum_fixed((ax + ay) + (az + aw), sm);
+  if (threadIdx.x == 0) part[blockIdx.x] = s;
+}
+
+// One workgroup: thread j adds the partials j, j + 256, ... in index order, then the same fixed fold; thread 0 decides the
+// step.  A void step (fault word set) leaves everything alone, as adam_prepare_kernel does, whose work this kernel takes
+// over: a step that is applied advances Adam's count, a skipped one (non-finite norm) does not.
+__global__ __launch_bounds__(256) void grad_clip_final_kernel(const double* __restrict__ part, int nparts, ClipDev* clip,
+                                                              AdamDev* st, const float* __restrict__ fault, float gscale,
+                                                              float max_norm, float lr, float b1, float b2) {
+  __shared__ double sm[4];
+  if (fault && *fault != 0.f) {
+    if (threadIdx.x == 0) st->applied = 0;
+    return;
+  }
+  double a = 0.0;
+  for (int k = threadIdx.x; k < nparts; k += 256) a += part[k];
+  const double n2 = block_sum_fixed(a, sm);
+  if (threadIdx.x != 0) return;
+  const double norm = fabs((double)gscale) * sqrt(n2);
+  clip->last_norm = norm;
+  if (!isfinite(norm)) {            // an inf or a NaN somewhere in the gradient: P, M, V and t stay as they are
+    clip->skip = 1;
+    clip->skipped += 1;
+    st->applied = 0;
+    return;
+  }
+  const float coef = (float)(norm > (double)max_norm ? (double)max_norm / norm : 1.0);   // tf.clip_by_global_norm
+  clip->skip = 0;
+  clip->s = gscale * coef;          // == gscale exactly when coef == 1
+  clip->last_coef = coef;
+  clip->steps += 1;
+  if (coef < 1.f) clip->clipped += 1;
+  if (norm > clip->window_max_norm) clip->window_max_norm = norm;
+  adam_advance(st, lr, b1, b2);
 }
 
 void launch_adam(float* p, float* m, float* v, const float* g, int64_t n, AdamDev* state, float lr, float beta1, float beta2,
@@ -67,6 +166,19 @@ void launch_adam(float* p, float* m, float* v, const float* g, int64_t n, AdamDe
   if (blocks > 2048) blocks = 2048;
   hipLaunchKernelGGL(adam_prepare_kernel, dim3(1), dim3(1), 0, st, state, fault, lr, beta1, beta2);
   hipLaunchKernelGGL(adam_kernel, dim3(blocks), dim3(256), 0, st, p, m, v, g, n4, state, beta1, beta2, eps, gscale, fault);
+}
+
+void launch_adam_clipped(float* p, float* m, float* v, const float* g, int64_t n, AdamDev* state, ClipDev* clip, double* part,
+                         float lr, float beta1, float beta2, float eps, float gscale, float max_norm, const float* fault,
+                         hipStream_t st) {
+  const int64_t n4 = n / 4;
+  int blocks = (int)((n4 + 255) / 256);
+  if (blocks > 2048) blocks = 2048;
+  const int nparts = grad_sumsq_blocks(n);
+  hipLaunchKernelGGL(grad_sumsq_part_kernel, dim3(nparts), dim3(256), 0, st, g, n, part, fault);
+  hipLaunchKernelGGL(grad_clip_final_kernel, dim3(1), dim3(256), 0, st, part, nparts, clip, state, fault, gscale, max_norm, lr,
+                     beta1, beta2);
+  hipLaunchKernelGGL(adam_clip_kernel, dim3(blocks), dim3(256), 0, st, p, m, v, g, n4, state, clip, beta1, beta2, eps, fault);
 }
 
 // ---- column sums: stage 1 writes part[rs][n] for 32 row slices, stage 2 adds them in order

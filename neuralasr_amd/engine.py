@@ -407,6 +407,25 @@ class Engine:
     def apply_adam(self, grad_scale=1.0):
         self._ck(self.lib.nasr_apply_adam(self.h, float(grad_scale)))
 
+    def set_grad_clip(self, max_norm):
+        """Global-norm clipping of every apply_adam() from here on (include/nasr.h, nasr_set_grad_clip): 0 = off, a positive
+        number = tf.clip_by_global_norm's threshold, inf = measure the norm and skip non-finite gradients, never scale."""
+        self._ck(self.lib.nasr_set_grad_clip(self.h, float(max_norm)))
+
+    @property
+    def grad_clip(self):
+        """the threshold set_grad_clip() set; 0.0 = clipping is off"""
+        v = c_float()
+        self._ck(self.lib.nasr_get_grad_clip(self.h, byref(v)))
+        return float(v.value)
+
+    def grad_clip_stats(self, reset=False):
+        """dict of last_norm, window_max_norm, last_coef, steps, clipped, skipped (nasr_clip_stats); synchronises.
+        reset=True clears the window (its largest norm and the three counters) behind the read."""
+        st = _lib.ClipStats()
+        self._ck(self.lib.nasr_get_grad_clip_stats(self.h, byref(st), int(bool(reset))))
+        return st.as_dict()
+
     def get_grads(self):
         g = np.empty(self.param_count, np.float32)
         self._ck(self.lib.nasr_get_grads(self.h, _fp(g), g.size))

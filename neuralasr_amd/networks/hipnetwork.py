@@ -96,6 +96,8 @@ class HipNetwork(Network):
         self._device = device
         self._featurizer = None                 # the front end of the *_audio calls, made at the first of them
         self.engine = self.make_engine(config, device, stream)
+        if fortraining and getattr(config, 'max_grad_norm', 0.0) > 0:
+            self.engine.set_grad_clip(config.max_grad_norm)     # every apply_adam of every step path clips from here on
         self.engine.set_step_decode(True)
         self.engine.set_params(self.initial_params(self.engine.tensors(), seed=1))
         self._grad_tensor = None

@@ -1,5 +1,6 @@
 """Training loop (reference: train.py:14-63): epochs x batches, cumulative wall time, checkpoint + log +
-one validation batch every report_step, same log-line formats.
+one validation batch every report_step, same log-line formats (plus one "Grad:" line behind every "Step:" line when the
+config's max_grad_norm switches gradient clipping on).
 
   python -m neuralasr_amd.train <config>
   python -m neuralasr_amd.train <config> --from-audio     # from the [MFCC Featurizer] input CSV: features made on the GPU per batch
@@ -54,6 +55,15 @@ def train_model(dataTrain, datavalid, config, prefetch=2):
                         ', ler = %.4f' % (ler_sum / den) + ', time = %.4f' % spent)
             loss_sum = ler_sum = 0.0
             counted = 0
+            if getattr(config, 'max_grad_norm', 0.0) > 0:
+                # max_grad_norm: the optimiser steps since the last log line, read where save_checkpoint has
+                # just waited for the device anyway
+                gc = network.engine.grad_clip_stats(reset=True)
+                logger.info('Grad: norm = %.4f' % gc['last_norm'] + ', max = %.4f' % gc['window_max_norm'] +
+                            ', clipped %d of %d' % (gc['clipped'], gc['steps']) + ', skipped %d' % gc['skipped'])
+                if gc['skipped'] > 0:
+                    logger.warning('%d optimiser step(s) skipped: their gradient had a non-finite norm (parameters and Adam '
+                                   'state were left as they were)' % gc['skipped'])
             if datavalid:
                 if not datavalid.has_more_batches():
                     datavalid.reset_epoch()
