@@ -372,6 +372,68 @@ int nasr_ctc_beam_search_lm(const float* logits, const int32_t* seq_len, int B, 
                             int merge_repeated, const float* lm_logp, const float* lm_eos, int order, int bos_id,
                             float weight, float bonus, int32_t* ids_out, int32_t* lens_out, float* logp_out);
 
+/* ---- streaming recognition -----------------------------------------------------
+ * A causal network (networks/lstm_ctc_net.py: unidirectional LSTM cells) fed chunk by chunk: a stream session keeps, per
+ * LSTM layer and stream slot, the cell's (c, h) in fp32 on the device, and a feed is a forward pass over one chunk that
+ * starts every slot from its saved state and saves the state at the slot's last frame.  The logits of an utterance fed in
+ * chunks are those of nasr_forward on the whole utterance up to summation order (the bulk GEMMs split their sums by the
+ * row count), not bit for bit; the same sequence of feeds gives the same bits.  Feeds run the per-timestep recurrence
+ * kernels whatever nasr_get_recurrence_mode says, leave that mode and nasr_get_persist_stats alone, and change nothing
+ * of the parameters, Adam's state, the gradient buffer, the dropout state or the clip statistics.  Batch calls
+ * between feeds are allowed and do not touch the stream state; parameters may change between feeds (nasr_set_params, a
+ * training step): the state is simply carried. */
+/* (No counterpart in the reference: tfnetwork.py:179-181 decodes whole utterances.)  Opens the handle's stream session with
+ * S slots (concurrent streams), 1 <= S <= 64 (else NASR_ERR_ARG), all state zero.  NASR_ERR_STATE, with the reason in
+ * nasr_last_error: a second open; a bidirectional config; a dropout probability > 0 (the reference applies dropout in
+ * every graph, keyed by the pass counter); a WaveNet, LAS or featurizer handle. */
+int nasr_stream_open(nasr_handle h, int S);
+/* (No counterpart in the reference: tfnetwork.py:179-181 decodes whole utterances.)  Ends the session and frees its
+ * state.  NASR_ERR_STATE without one, as for every call below. */
+int nasr_stream_close(nasr_handle h);
+/* (No counterpart in the reference: tfnetwork.py:179-181 decodes whole utterances.)  Zeroes the state and the frame count
+ * of the n slots listed (slots == NULL: of every slot): a new utterance starts there.  A slot outside [0,S-1]:
+ * NASR_ERR_ARG, nothing reset. */
+int nasr_stream_reset(nasr_handle h, const int32_t* slots, int n);
+/* (No counterpart in the reference: tfnetwork.py:179-181 decodes whole utterances.)  One chunk: feats [S][Tc][F], n_frames
+ * [S] with n_frames[b] in [0,Tc] frames of slot b (0: the slot is idle in this chunk and keeps its state).  logits_out
+ * time-major [Tc][S][C] as nasr_forward returns them; rows t >= n_frames[b] are unspecified.  Synchronises.  The chunk
+ * replaces the resident batch as nasr_forward does, and is itself none for the *_resident calls: they answer NASR_ERR_STATE
+ * until the next upload.  NASR_ERR_ARG, with the resident batch kept: Tc < 1, an n_frames outside [0,Tc], a null
+ * buffer. */
+int nasr_stream_feed(nasr_handle h, const float* feats, const int32_t* n_frames, int Tc, float* logits_out);
+/* (No counterpart in the reference: tfnetwork.py:179-181 decodes whole utterances.)  frames_out [S]: the frames each slot
+ * has consumed since its reset. */
+int nasr_stream_frames(nasr_handle h, int64_t* frames_out);
+/* (No counterpart in the reference: tfnetwork.py:179-181 decodes whole utterances.)  The session's state, [L][S][2][H]
+ * float32: per layer and slot the cell's c, then its h, as of the slot's last frame; n must be L*S*2*H.  Synchronises. */
+int nasr_stream_get_state(nasr_handle h, float* state, int64_t n);
+/* (No counterpart in the reference: tfnetwork.py:179-181 decodes whole utterances.)  Replaces the session's state (the
+ * layout of nasr_stream_get_state; the frame counts stay): continuing on another handle with the same parameters gives
+ * the first handle's logits bit for bit. */
+int nasr_stream_set_state(nasr_handle h, const float* state, int64_t n);
+
+/* The CTC beam search as a state that lives between calls - host only, the procedure and arithmetic of
+ * nasr_ctc_beam_search(_lm), which is open + one feed + best + close on this very code: feeding an utterance's frames in
+ * any split gives its ids and log-probability bit for bit.  One handle per thread. */
+typedef struct nasr_beam* nasr_beam_handle;
+/* (No counterpart in the reference: tfnetwork.py:179-181 decodes whole utterances.)  A search over C classes (blank = C-1)
+ * before its first frame.  lm_logp == NULL: the plain search (the remaining LM arguments are not read); else the fused
+ * one with the arguments and rules of nasr_ctc_beam_search_lm.  The tables are borrowed: they must outlive the handle.
+ * NASR_ERR_ARG: C < 2, beam_width < 1, out == NULL, bad LM arguments. */
+int nasr_ctc_beam_open(int C, int beam_width, int merge_repeated, const float* lm_logp, const float* lm_eos, int order,
+                       int bos_id, float weight, float bonus, nasr_beam_handle* out);
+/* (No counterpart in the reference: tfnetwork.py:179-181 decodes whole utterances.)  The next n_frames frames: frame t at
+ * logits + t * frame_stride (C raw logits each; frame_stride >= C floats, S*C for slot b's column of a [Tc][S][C] array).
+ * n_frames = 0 is allowed. */
+int nasr_ctc_beam_feed(nasr_beam_handle s, const float* logits, int64_t frame_stride, int n_frames);
+/* (No counterpart in the reference: tfnetwork.py:179-181 decodes whole utterances.)  The top path of the frames fed so far
+ * (the empty one before the first), at any time and without disturbing the search: *len_out ids into ids_out [cap],
+ * logp_out (may be NULL) as nasr_ctc_beam_search(_lm) reports it.  cap smaller than the hypothesis: NASR_ERR_ARG, with
+ * *len_out set and ids_out untouched. */
+int nasr_ctc_beam_best(nasr_beam_handle s, int32_t* ids_out, int cap, int32_t* len_out, float* logp_out);
+/* (No counterpart in the reference: tfnetwork.py:179-181 decodes whole utterances.)  Frees the search (NULL: nothing). */
+int nasr_ctc_beam_close(nasr_beam_handle s);
+
 /* ---- CTC forced alignment (not part of the reference, which has no aligner) ------------
  * For utterance b with F = seq_len[b] logit frames (the frames the CTC loss uses) and its label of length L: the path pi over the
  * S = 2L+1 states of the extended label (blank = C-1 at even states) that starts in {0,1}, ends in {S-1,S-2}, moves by 0, 1 or

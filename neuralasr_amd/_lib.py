@@ -45,6 +45,9 @@ SYMBOLS = [
     'nasr_upload_batch_context_aug', 'nasr_upload_batch_audio_aug', 'nasr_stage_batch_audio_aug',
     'nasr_ctc_align', 'nasr_ctc_align_resident', 'nasr_ctc_align_logits', 'nasr_ctc_align_lds', 'nasr_resident_shape',
     'nasr_set_grad_clip', 'nasr_get_grad_clip', 'nasr_get_grad_clip_stats',
+    'nasr_stream_open', 'nasr_stream_close', 'nasr_stream_reset', 'nasr_stream_feed', 'nasr_stream_frames',
+    'nasr_stream_get_state', 'nasr_stream_set_state',
+    'nasr_ctc_beam_open', 'nasr_ctc_beam_feed', 'nasr_ctc_beam_best', 'nasr_ctc_beam_close',
 ]
 
 
@@ -245,6 +248,17 @@ def load():
         'nasr_resample_length': (c_int64, [c_int32, c_int32, c_int64, POINTER(c_int64)]),
         'nasr_resample': (c_int, [H, fp, POINTER(c_int64), ip, c_int, fp, c_int64]),
         'nasr_featurize_rates': (c_int, [H, fp, POINTER(c_int64), ip, c_int, fp, c_int64, POINTER(c_double)]),
+        'nasr_stream_open': (c_int, [H, c_int]),
+        'nasr_stream_close': (c_int, [H]),
+        'nasr_stream_reset': (c_int, [H, ip, c_int]),
+        'nasr_stream_feed': (c_int, [H, fp, ip, c_int, fp]),
+        'nasr_stream_frames': (c_int, [H, POINTER(c_int64)]),
+        'nasr_stream_get_state': (c_int, [H, fp, c_int64]),
+        'nasr_stream_set_state': (c_int, [H, fp, c_int64]),
+        'nasr_ctc_beam_open': (c_int, [c_int, c_int, c_int, fp, fp, c_int, c_int, c_float, c_float, POINTER(c_void_p)]),
+        'nasr_ctc_beam_feed': (c_int, [c_void_p, fp, c_int64, c_int]),
+        'nasr_ctc_beam_best': (c_int, [c_void_p, ip, c_int, ip, fp]),
+        'nasr_ctc_beam_close': (c_int, [c_void_p]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

@@ -14,7 +14,7 @@ KT_LIB = os.path.join(HERE, 'libnasr_kt.so')
 KT_SRC = os.path.join(HERE, '..', 'tests', 'kernel_harness', 'harness.hip')
 KT_OBJS = ['gemm.o', 'gemm_tph.o', 'optim.o']       # the objects of libnasr.so the kernel tests link against
 SOURCES = ['gemm.hip', 'gemm_tph.hip', 'lstm.hip', 'lstm_persist.hip', 'lstm_wide.hip', 'ctc.hip', 'dense.hip', 'optim.hip', 'nasr_layout.hip',
-           'nasr_rec.hip', 'nasr_batch.hip', 'nasr_pass.hip', 'nasr_api.hip', 'nasr_comm.hip', 'beam.cpp',
+           'nasr_rec.hip', 'nasr_batch.hip', 'nasr_pass.hip', 'nasr_stream.hip', 'nasr_api.hip', 'nasr_comm.hip', 'beam.cpp',
            'wavenet.hip', 'nasr_wavenet.hip', 'las.hip', 'las_beam.hip', 'nasr_las.hip', 'mfcc.hip', 'resample.hip']
 HEADERS = [os.path.join(CSRC, 'kernels.h'), os.path.join(CSRC, 'lstm_device.h'), os.path.join(CSRC, 'nasr_ctx.h'), os.path.join(CSRC, 'wavenet.h'), os.path.join(CSRC, 'las.h'), os.path.join(CSRC, 'las_beam.h'), os.path.join(CSRC, 'resample.h'),
            os.path.join(HERE, '..', 'include', 'nasr.h')]

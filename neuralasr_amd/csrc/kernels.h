@@ -118,6 +118,15 @@ void launch_expand_context_masked(const float* centre, const float* pad, const i
 void launch_repack_u(const float* U, float* Uf, float* Ub, int Hp, hipStream_t st);
 void launch_lstm_fwd_step(const LstmDims& dm, int s, const float* Uf, const float* hin, float* hout, float* gates,
                           float* cbuf, float* out, const int* seq_len, float forget_bias, hipStream_t st);
+// step 0 of a stream feed (nasr_stream.hip): the same kernel, continuing from hin = the saved h (operand image) and
+// c0 = the saved c [D][Bp][Hp] instead of starting a sequence
+void launch_lstm_fwd_step_carry(const LstmDims& dm, const float* Uf, const float* hin, float* hout, float* gates, float* cbuf,
+                                float* out, const int* seq_len, float forget_bias, const float* c0, hipStream_t st);
+// one layer's stream state [S][2][H] (c, then h; unidirectional) -> the h operand image of step 0 [Bp*Hp] and c [Bp][Hp],
+// zeros in padded units and slots; and back from row n_frames[b]-1 of out / cbuf [Tc*Bp][Hp] (n_frames[b] = 0: untouched)
+void launch_stream_load_state(const float* state, float* himg, float* cimg, int S, int H, int Bp, int Hp, hipStream_t st);
+void launch_stream_save_state(const float* out, const float* cbuf, const int* n_frames, float* state, int S, int H, int Bp,
+                              int Hp, hipStream_t st);
 // BPTT step: pin/pout = [D][lstm_bwd_partials(Hp)][Bp][Hp] partial sums handed launch to launch, dcin/dcout = [D][Bp][Hp]
 int lstm_bwd_partials(int Hp);
 void launch_lstm_bwd_step(const LstmDims& dm, int s, const float* Ub, const float* pin, float* pout,

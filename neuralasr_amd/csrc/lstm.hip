@@ -178,12 +178,15 @@ void launch_repack_u(const float* U, float* Uf, float* Ub, int Hp, hipStream_t s
 // NQ = Hp/64 (16-byte operand groups per wave) as a template constant keeps the load/MFMA stream
 // straight-line, so hipcc emits counted vmcnt waits and the MFMA chain starts when the first pair lands;
 // NQ = 0 is the generic (runtime) form.
-template <int MT, int NQ>
+// CARRY: the state-carrying form of a stream feed (nasr_stream.hip).  Step 0 continues a sequence instead of starting
+// one: hin is the saved h, written in the layout of sw_index by stream_load_state_kernel, and c_{-1} is c0 [D][Bp][Hp]
+// instead of 0.  Everything else, and every step s > 0, is the batch form, which never reads c0.
+template <int MT, int NQ, bool CARRY = false>
 __global__ __launch_bounds__(256) void lstm_fwd_step_kernel(
     const float* __restrict__ Uf,    // [D][Hp/4][Hp/16][64][4]
     const float* __restrict__ hin,   // [D][MT][Hp/16][64][4]
     float* __restrict__ hout, float* __restrict__ gates, float* __restrict__ cbuf, float* __restrict__ out,
-    const int* __restrict__ seq_len, int s, int T, int Bp, int Hp, int D, float fb) {
+    const int* __restrict__ seq_len, int s, int T, int Bp, int Hp, int D, float fb, const float* __restrict__ c0) {
   __shared__ __attribute__((aligned(16))) float red[4][MT][64][4];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int tile = blockIdx.x, d = blockIdx.y;
@@ -229,6 +232,7 @@ __global__ __launch_bounds__(256) void lstm_fwd_step_kernel(
       r = tb * Bp + b;
       xg = *reinterpret_cast<const float4*>(gates + (size_t)r * DN + d * N4 + 4 * j);
       if (s > 0) cprev = cbuf[(size_t)(d ? r + Bp : r - Bp) * DH + d * Hp + j];
+      else if (CARRY) cprev = c0[((size_t)d * Bp + b) * Hp + j];
     }
   }
 
@@ -298,9 +302,61 @@ void launch_lstm_fwd_step(const LstmDims& dm, int s, const float* Uf, const floa
   dispatch_int(StepMT{}, dm.Bp / 16, [&](auto mt) {
     dispatch_int(std::integer_sequence<int, 1, 2, 4, 8, 16, 0>{}, dm.Hp / 64, [&](auto nq) {   // NQ = Hp/64, 0 = the generic form
       hipLaunchKernelGGL((lstm_fwd_step_kernel<mt(), nq()>), grid, block, 0, st, Uf, hin, hout, gates, cbuf, out, seq_len, s,
-                         dm.T, dm.Bp, dm.Hp, dm.D, forget_bias);
+                         dm.T, dm.Bp, dm.Hp, dm.D, forget_bias, static_cast<const float*>(nullptr));
     });
   });
+}
+
+// the first step of a stream feed: hin = the saved h as an operand image, c0 = the saved c [D][Bp][Hp]
+void launch_lstm_fwd_step_carry(const LstmDims& dm, const float* Uf, const float* hin, float* hout, float* gates, float* cbuf,
+                                float* out, const int* seq_len, float forget_bias, const float* c0, hipStream_t st) {
+  dim3 grid(dm.Hp / 4, dm.D), block(256);
+  dispatch_int(StepMT{}, dm.Bp / 16, [&](auto mt) {
+    dispatch_int(std::integer_sequence<int, 1, 2, 4, 8, 16, 0>{}, dm.Hp / 64, [&](auto nq) {
+      hipLaunchKernelGGL((lstm_fwd_step_kernel<mt(), nq(), true>), grid, block, 0, st, Uf, hin, hout, gates, cbuf, out, seq_len,
+                         0, dm.T, dm.Bp, dm.Hp, dm.D, forget_bias, c0);
+    });
+  });
+}
+
+// ------------------------------------------------------------------ stream state (nasr_stream.hip)
+// One layer's saved state, natural layout [S][2][H] (c, then h), into what step 0 of a feed reads: the h operand image
+// [Bp/16][Hp/16][64][4] in the layout of sw_index and c [Bp][Hp].  Padded units and padded slots: zeros.
+__global__ __launch_bounds__(256) void stream_load_state_kernel(const float* __restrict__ state, float* __restrict__ himg,
+                                                                float* __restrict__ cimg, int S, int H, int Bp, int Hp) {
+  const int e = blockIdx.x * 256 + threadIdx.x;
+  if (e >= Bp * Hp) return;
+  const int b = e / Hp, j = e - b * Hp;
+  float c = 0.f, hv = 0.f;
+  if (b < S && j < H) {
+    c = state[((size_t)b * 2 + 0) * H + j];
+    hv = state[((size_t)b * 2 + 1) * H + j];
+  }
+  cimg[e] = c;
+  himg[sw_index(Hp, b >> 4, b & 15, j)] = hv;
+}
+
+// ... and back: every slot's state as of its last frame of the chunk, row (n_frames[b] - 1) * Bp + b of cbuf / out
+// [Tc * Bp][Hp].  A slot without a frame in this chunk keeps what it had.
+__global__ __launch_bounds__(256) void stream_save_state_kernel(const float* __restrict__ out, const float* __restrict__ cbuf,
+                                                                const int* __restrict__ n_frames, float* __restrict__ state,
+                                                                int S, int H, int Bp, int Hp) {
+  const int e = blockIdx.x * 256 + threadIdx.x;
+  if (e >= S * H) return;
+  const int b = e / H, j = e - b * H;
+  const int n = n_frames[b];
+  if (n < 1) return;
+  const size_t r = (size_t)(n - 1) * Bp + b;
+  state[((size_t)b * 2 + 0) * H + j] = cbuf[r * Hp + j];
+  state[((size_t)b * 2 + 1) * H + j] = out[r * Hp + j];
+}
+
+void launch_stream_load_state(const float* state, float* himg, float* cimg, int S, int H, int Bp, int Hp, hipStream_t st) {
+  hipLaunchKernelGGL(stream_load_state_kernel, dim3((Bp * Hp + 255) / 256), dim3(256), 0, st, state, himg, cimg, S, H, Bp, Hp);
+}
+void launch_stream_save_state(const float* out, const float* cbuf, const int* n_frames, float* state, int S, int H, int Bp,
+                              int Hp, hipStream_t st) {
+  hipLaunchKernelGGL(stream_save_state_kernel, dim3((S * H + 255) / 256), dim3(256), 0, st, out, cbuf, n_frames, state, S, H, Bp, Hp);
 }
 
 // ------------------------------------------------------------------ BPTT step

@@ -144,6 +144,15 @@ int validate_batch(nasr_ctx* h, const int32_t* seq_len, const int32_t* labels, c
   return NASR_OK;
 }
 
+int validate_chunk(nasr_ctx* h, const int32_t* n_frames, int S, int Tc) {
+  if (Tc < 1) return h->fail(NASR_ERR_ARG, "a stream chunk needs Tc >= 1");
+  for (int b = 0; b < S; ++b)
+    if (n_frames[b] < 0 || n_frames[b] > Tc)
+      return h->fail(NASR_ERR_ARG, "n_frames[" + std::to_string(b) + "] = " + std::to_string(n_frames[b]) + " out of [0,Tc = " +
+                                       std::to_string(Tc) + "]");
+  return NASR_OK;
+}
+
 // The checks of nasr_batch_aug (include/nasr.h) against the batch's own seq_len; *masked: some mask has a non-zero width.
 static int validate_aug(nasr_ctx* h, const nasr_batch_aug* a, const int32_t* seq_len, int B, int ctx, int ncep, bool* masked) {
   *masked = false;
@@ -220,6 +229,7 @@ static int check_batch(nasr_ctx* h, const BatchSrc& b, bool* masked) {
   if (b.centre_form() && ((b.centre && !b.pad_value) || b.ctx < 0 || b.ncep < 1 || (2 * b.ctx + 1) * b.ncep != h->F))
     return h->fail(NASR_ERR_ARG, "context upload: feature_size must equal (2*numcontext+1)*numcep");
   if (b.labels && !b.label_len) return h->fail(NASR_ERR_ARG, "labels without label_len");
+  if (b.chunk) return validate_chunk(h, b.seq_len, b.B, b.T);
   if (int rc = validate_batch(h, b.seq_len, b.labels, b.label_len, b.B, b.T, b.Lmax)) return rc;
   if (!b.aug) return NASR_OK;
   if (!b.centre_form()) return h->fail(NASR_ERR_ARG, "augmentation masks need a batch in the centre form");

@@ -4,6 +4,7 @@
 //   nasr_rec.hip     the recurrence's kind: create-time set-up and census, resident launches, abort check, re-arming
 //   nasr_batch.hip   batch buffers and slots: upload, stage / commit
 //   nasr_pass.hip    forward, CTC, backward: the orchestration of one step on the handle's streams
+//   nasr_stream.hip  streaming sessions (nasr_stream_*): recurrent state that survives between chunks
 //   nasr_api.hip     the C ABI entry points; what the create calls share (handle_open, alloc_param_buffers, handle_finish)
 //   nasr_comm.hip    RCCL bound with dlopen: nasr_comm_*
 //   nasr_wavenet.hip the WaveNet handle (nasr_create_wavenet): its layout, buffers, BN state and pass
@@ -192,6 +193,15 @@ struct FzStateDelete { void operator()(FzState* f) const; };
 struct LasState;
 struct LasStateDelete { void operator()(LasState* s) const; };
 
+// A stream session (nasr_stream.hip): S concurrent streams on a unidirectional LSTM-family handle.
+struct StreamState {
+  int S = 0;
+  DevBuf state;                      // [L][S][2][H] fp32: c, then h, as of each slot's last frame; zero after open / reset
+  DevBuf cimg;                       // [Bp][Hp]: the layer's saved c as step 0 of a feed reads it
+  std::vector<int64_t> frames;       // [S] frames consumed since the slot's reset
+  uint64_t uf_seq = ~0ull;           // repack_seq of the per-step operand images the session built itself (see stream_feed)
+};
+
 }  // namespace nasr_impl
 
 // (internal header: the translation units behind the ABI use both namespaces unqualified)
@@ -224,6 +234,8 @@ struct nasr_ctx {
   // every further abort doubles the wait.  NASR_PERSIST_REARM sets the first wait (0 = never re-arm).
   int64_t rearm_after = 0, rearm_wait = 0, clean_steps = 0;
   int persist_aborts = 0, persist_rearms = 0;
+  uint64_t repack_seq = 0;             // counts repack(): the parameters' operand images changed
+  std::unique_ptr<StreamState> stream; // the open stream session, or none
   Pinned<unsigned> perr;               // host-mapped sticky error word of the resident launches
   DevPtr<float> Ucs, Ucinv;            // [L*D][N4] column scales / inverse scales of every (layer, direction) recurrent matrix
   // the persistent kind: [L][D] operand images; the forward recurrence on fp16 planes of U (v_mfma_f32_4x4x4_16B_f16)
@@ -513,6 +525,8 @@ int ensure_ctc_buffers(nasr_ctx* h, int B, int Bp, int T, int Tp, int Lmax, bool
 // num_classes: 0 = the handle's (and its family's rules); > 0: CTC labels over that many classes (nasr_ctc_align_logits)
 int validate_batch(nasr_ctx* h, const int32_t* seq_len, const int32_t* labels, const int32_t* label_len, int B, int T, int Lmax,
                    int num_classes = 0);
+// a chunk of a stream session: S slots, Tc frames, n_frames[b] in [0, Tc] (0 = the slot is idle in this chunk)
+int validate_chunk(nasr_ctx* h, const int32_t* n_frames, int S, int Tc);
 bool pinned_ensure(Pinned<void>& p, size_t* cap, size_t bytes);
 void slot_set_state(nasr_ctx* h, BatchSlot* s, int st);
 int slot_commit(nasr_ctx* h, BatchSlot* s);
@@ -533,6 +547,7 @@ struct BatchSrc {
   const int32_t *seq_len = nullptr, *labels = nullptr, *label_len = nullptr;
   int B = 0, T = 0, Lmax = 0;
   const nasr_batch_aug* aug = nullptr;
+  bool chunk = false;   // a chunk of a stream session: seq_len[b] = 0 is an idle slot (validate_chunk instead of validate_batch)
   bool centre_form() const { return centre || producer; }
 };
 inline BatchSrc stacked_batch(const float* feats, const int32_t* seq_len, const int32_t* labels, const int32_t* label_len, int B,
@@ -595,7 +610,9 @@ inline const float* lstm_input(nasr_ctx* h, int l) {
 // ---- nasr_pass.hip
 // the fp32 GEMM g (gemm.hip) on the handle's stream; g.split_k > 1 gets the handle's slab workspace, grown to fit
 int gemm_f32(nasr_ctx* h, GemmDesc g);
-int forward(nasr_ctx* h);
+// chunk: the resident batch is a chunk of the open stream session - the recurrence continues from the session's state on
+// the per-step kernels and saves it again; the fault word, the resident kinds' control blocks and the dropout counter stay
+int forward(nasr_ctx* h, bool chunk = false);
 // forward pass and loss of the resident batch.  training: the WaveNet's batch norm on the batch's statistics (a LAS
 // handle samples either way, one counter value per pass)
 int loss_pass(nasr_ctx* h, bool training);

@@ -247,6 +247,7 @@ int build_layout(nasr_ctx* h) {
 
 int repack(nasr_ctx* h) {
   if (h->family != Family::Lstm) return NASR_OK;   // the WaveNet's and LAS's GEMMs read the fp32 parameters directly: no operand images
+  h->repack_seq += 1;
   // only the operand images of the kernels in use (a switch of the recurrence's kind calls repack again)
   // scales of every matrix that needs them - recurrent matrices of the persistent / wide kernels, input and dense
   // weights of the plane GEMMs - in ONE batch (two launches), then the images

@@ -197,7 +197,27 @@ int dense_backward(nasr_ctx* h, int i, const float* X, float* dX) {
   return NASR_OK;
 }
 
-int forward(nasr_ctx* h) {
+// One layer of a stream chunk: the recurrence over the chunk's T steps on the per-step kernels, whatever kind the handle's
+// batches run on, from the session's saved (c, h) of layer l, which it then replaces by every slot's state at its last
+// frame.  No graph: step 0 is another kernel than the rest, and a chunk is a few dozen launches.
+static int run_chunk_steps(nasr_ctx* h, int l, hipStream_t st) {
+  StreamState& ss = *h->stream;
+  const LstmDims dm{h->T, h->B, h->Bp, h->H, h->Hp, h->D};
+  const size_t sU = (size_t)l * h->Hp * h->N4, hs = (size_t)h->Bp * h->Hp;
+  float* hst = h->hstate.as<float>();
+  float* state = ss.state.as<float>() + (size_t)l * ss.S * 2 * h->H;
+  float *g = h->gates[l].as<float>(), *c = h->cbuf[l].as<float>(), *o = h->outb[l].as<float>();
+  launch_stream_load_state(state, hst, ss.cimg.as<float>(), ss.S, h->H, h->Bp, h->Hp, st);
+  launch_lstm_fwd_step_carry(dm, h->Uf + sU, hst, hst + hs, g, c, o, h->seq_p, h->cfg.forget_bias, ss.cimg.as<float>(), st);
+  for (int s = 1; s < h->T; ++s)
+    launch_lstm_fwd_step(dm, s, h->Uf + sU, hst + (s & 1) * hs, hst + ((s + 1) & 1) * hs, g, c, o, h->seq_p, h->cfg.forget_bias, st);
+  launch_stream_save_state(o, c, h->seq_p, state, ss.S, h->H, h->Bp, h->Hp, st);
+  h->n_fwd_launch += h->T;
+  HIPCHK(h, hipGetLastError());
+  return NASR_OK;
+}
+
+int forward(nasr_ctx* h, bool chunk) {
   if (!h->resident) return h->fail(NASR_ERR_STATE, "no resident batch: call nasr_upload_batch first");
   switch (h->family) {
     case Family::WaveNet: return wn_forward(h, false);   // forward-only calls: inference-mode batch norm
@@ -210,9 +230,9 @@ int forward(nasr_ctx* h) {
   std::fill(h->ott_valid.begin(), h->ott_valid.end(), 0);
   // the fault word of the pass that starts here (a training step or a forward-only call); what an unread earlier word
   // said is gone with it
-  HIPCHK(h, hipMemsetAsync(h->Gbase, 0, GRAD_HEAD * 4, h->st));
+  if (!chunk) HIPCHK(h, hipMemsetAsync(h->Gbase, 0, GRAD_HEAD * 4, h->st));
   // the control blocks of this pass's persistent launches, cleared in one go (one per layer: run_steps)
-  if (h->rec_use == RecKind::Persist) {
+  if (h->rec_use == RecKind::Persist && !chunk) {
     HIPCHK(h, hipMemsetAsync(h->pctl + 1, 0, (size_t)h->L * sizeof(PersistCtl), h->st));
     HIPCHK(h, hipMemsetAsync(h->xchf, 0, (size_t)h->L * persist_hx_bytes(h->Hp), h->st));   // epoch 0 everywhere (lstm_persist.hip)
   }
@@ -228,7 +248,7 @@ int forward(nasr_ctx* h) {
       HIPCHK(h, hipGetLastError());
     }
     PhaseScope ps(h, PH_RECF);
-    int rc = run_steps(h, l, false, 0, T, h->st, &h->n_fwd_launch);
+    int rc = chunk ? run_chunk_steps(h, l, h->st) : run_steps(h, l, false, 0, T, h->st, &h->n_fwd_launch);
     if (rc) return rc;
   }
   if (h->has_post) {
@@ -236,7 +256,7 @@ int forward(nasr_ctx* h) {
     int rc = dense_forward(h, h->npre, h->outb[h->L - 1].as<float>());
     if (rc) return rc;
   }
-  if (h->ndense) h->drop_counter += 1;   // one counter value per forward pass
+  if (h->ndense && !chunk) h->drop_counter += 1;   // one counter value per forward pass (a chunk: no dropout, no count)
   {
     PhaseScope ps(h, PH_PROJCTC);
     const bool sr = h->cfg.merge == NASR_MERGE_STACK_RESHAPE && D == 2;
@@ -253,7 +273,7 @@ int forward(nasr_ctx* h) {
     g.split_k = gemm_pick_split(g.M, g.N, g.K);
     if (int rc = gemm_f32(h, g)) return rc;
   }
-  h->have_fwd = true;
+  h->have_fwd = !chunk;
   return NASR_OK;
 }
 

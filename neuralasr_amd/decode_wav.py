@@ -1,7 +1,10 @@
 """Transcribe one WAV file with a trained model (reference: decode_wav.py:12-32).
 `python -m neuralasr_amd.decode_wav CONFIG WAV`: the features of utils.compute_mfcc_and_read_transcription, the
 configured network's decoder, and a 'Decoded: ...' log line.  A network that takes audio (HipNetwork.takes_audio) gets the samples:
-its features are made on the GPU and stay there.  Every other network class takes features, so every one works."""
+its features are made on the GPU and stay there.  Every other network class takes features, so every one works.
+`--stream [--chunk-frames N]`: a causal network (LstmCTCNet) is fed the file's frames N at a time (default 50 = 0.5 s), with a
+'Partial: ...' line after every chunk whose hypothesis changed.  The features are computed over the whole file first: the
+reference normalises by whole-utterance mean and std (utils.py:29), so frames a trained model understands exist only then."""
 import argparse
 
 import numpy as np
@@ -24,13 +27,57 @@ def decode(config, mfcc, seq_len, network=None):
     return report(config, network.decode(mfcc, seq_len))
 
 
-def main(argv=None):
+def features_of(config, network, path):
+    """The file's normalised, context-stacked frames [T, feature_size] on the host, from the network's GPU front end when it
+    has one"""
+    if getattr(network, 'takes_audio', False):
+        from .features import read_wav_native
+        audio, rate = read_wav_native(path)
+        return np.asarray(network.featurizer().compute([audio], rates=[rate])[0], dtype=np.float32)
+    return np.asarray(compute_mfcc_and_read_transcription(path, config.samplerate, config.numcontext, config.numcep,
+                                                          kind=config.features, deltas=config.deltas), dtype=np.float32)
+
+
+def decode_stream(config, network, feats, chunk_frames):
+    """Feed feats [T, F] to network.stream() chunk_frames at a time: a 'Partial:' line after every chunk whose hypothesis
+    changed, then the usual 'Decoded:' line.  Returns the final text."""
+    if chunk_frames < 1:
+        raise ValueError('--chunk-frames must be >= 1')
+    rec = network.stream(1)
+    try:
+        last = None
+        for t in range(0, len(feats), chunk_frames):
+            ids = rec.feed([feats[t:t + chunk_frames]])[0]
+            if ids != last:
+                logger.info('Partial: ' + config.symbols.convert_to_str(np.asarray(ids, dtype=np.int64)))
+                last = ids
+        ids, _ = rec.finish(0)
+    finally:
+        rec.close()
+    return report(config, np.asarray(ids, dtype=np.int64))
+
+
+def parse_args(argv=None):
     parser = argparse.ArgumentParser(description='Convert a given audio file into text using trained model.')
     parser.add_argument('config', help='Configuration file.')
     parser.add_argument('input', help='Audio file path')
+    parser.add_argument('--stream', action='store_true',
+                        help='feed the frames in chunks to a causal network and log partial hypotheses')
+    parser.add_argument('--chunk-frames', type=int, default=50, help='frames per chunk with --stream (default 50 = 0.5 s)')
     args = parser.parse_args(argv)
+    if args.chunk_frames < 1:
+        parser.error('--chunk-frames must be >= 1')
+    return args
+
+
+def main(argv=None):
+    args = parse_args(argv)
     config = Config(args.config, True)
     network = config.load_network(fortraining=False)
+    if args.stream:
+        if not hasattr(network, 'stream'):
+            raise SystemExit('--stream: network %s cannot stream' % type(network).__name__)
+        return decode_stream(config, network, features_of(config, network, args.input), args.chunk_frames)
     if getattr(network, 'takes_audio', False):
         from .features import read_wav_native
         audio, rate = read_wav_native(args.input)

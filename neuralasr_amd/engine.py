@@ -496,6 +496,47 @@ class Engine:
             raise _lib.NasrError(rc, fn + ': bad arguments')
         return [ids[b, :lens[b]].tolist() for b in range(B)], logp
 
+    # ------------------------------------------------------------------ streaming (nasr_stream_*)
+    def stream_open(self, slots=1):
+        """Open the stream session: `slots` concurrent streams, each layer's (c, h) per slot kept on the device between
+        feeds.  Raises the library's message for a network that cannot stream."""
+        self._ck(self.lib.nasr_stream_open(self.h, int(slots)))
+        self._stream_slots = int(slots)
+
+    def stream_close(self):
+        self._ck(self.lib.nasr_stream_close(self.h))
+
+    def stream_reset(self, slots=None):
+        """A new utterance starts in `slots` (None: in every slot): state and frame count zero."""
+        if slots is None:
+            self._ck(self.lib.nasr_stream_reset(self.h, None, 0))
+        else:
+            sl = _i32(np.asarray([int(x) for x in slots])).ravel()
+            self._ck(self.lib.nasr_stream_reset(self.h, _ip(sl), sl.size))
+
+    def stream_feed(self, feats, n_frames):
+        """One chunk: feats [S,Tc,F], n_frames [S] in [0,Tc] (0: the slot is idle).  Returns the logits [Tc,S,C]; rows
+        t >= n_frames[b] of slot b are unspecified."""
+        feats, n, _, _, S, Tc, _ = self._batch(feats, n_frames)
+        out = np.empty((Tc, S, self.num_classes), np.float32)
+        self._ck(self.lib.nasr_stream_feed(self.h, _fp(feats), _ip(n), Tc, _fp(out)))
+        return out
+
+    def stream_frames(self):
+        out = np.zeros(getattr(self, '_stream_slots', 0), np.int64)
+        self._ck(self.lib.nasr_stream_frames(self.h, out.ctypes.data_as(POINTER(c_int64))))
+        return out
+
+    def stream_state(self):
+        """The session's state [L,S,2,H] float32: per layer and slot the cell's c, then its h."""
+        out = np.empty((int(self.cfg.num_layers), getattr(self, '_stream_slots', 0), 2, int(self.cfg.hidden)), np.float32)
+        self._ck(self.lib.nasr_stream_get_state(self.h, _fp(out), out.size))
+        return out
+
+    def set_stream_state(self, state):
+        state = _f32(state)
+        self._ck(self.lib.nasr_stream_set_state(self.h, _fp(state), state.size))
+
     def get_loss(self):
         loss = c_float()
         self._ck(self.lib.nasr_get_loss(self.h, byref(loss)))
@@ -669,6 +710,76 @@ class Engine:
         pt = _lib.PhaseTimes()
         self._ck(self.lib.nasr_get_phase_times(self.h, byref(pt)))
         return pt.as_dict()
+
+
+class BeamStream:
+    """The CTC beam search of Engine.beam_search as a state that lives between calls (nasr_ctc_beam_open / feed / best /
+    close; host only): feed() frames as they arrive, best() at any time.  Feeding an utterance in any split gives the
+    ids and log-probability of the whole-utterance search bit for bit.  lm (lm.NGramLM): the fused search; its arrays
+    are kept alive here, the library only borrows them.  One object per thread."""
+
+    def __init__(self, num_classes, beam_width=100, merge_repeated=True, lm=None, lm_weight=0.0, lm_bonus=0.0):
+        self.lib = _lib.load()
+        self.C = int(num_classes)
+        if lm is not None and lm.num_classes != self.C:
+            raise ValueError(f'the language model has num_classes {lm.num_classes} but the search has {self.C} classes')
+        self._args = (self.C, int(beam_width), int(bool(merge_repeated)))
+        self._lm = None if lm is None else (_f32(lm.logp), _f32(lm.eos), int(lm.order), int(lm.bos_id), float(lm_weight),
+                                            float(lm_bonus))
+        self.h = None
+        self.frames = 0
+        self.reset()
+
+    def reset(self):
+        """A new search before its first frame."""
+        self.close()
+        h = c_void_p()
+        lm = self._lm
+        tail = (None, None, 1, 0, 0.0, 0.0) if lm is None else (_fp(lm[0]), _fp(lm[1])) + lm[2:]
+        rc = self.lib.nasr_ctc_beam_open(*self._args, *tail, byref(h))
+        if rc != 0:
+            raise _lib.NasrError(rc, 'nasr_ctc_beam_open: bad arguments')
+        self.h = h
+        self.frames = 0
+
+    def feed(self, logits, slot=None):
+        """The next frames: logits [n,C], or column `slot` of a time-major [n,S,C] array (read in place)."""
+        lg = _f32(logits)
+        if lg.ndim == 3:
+            n, S, C = lg.shape
+            if not 0 <= int(slot) < S:
+                raise ValueError(f'slot {slot} of {S}')
+            offset, stride = int(slot) * C, S * C
+        else:
+            (n, C), offset, stride = lg.shape, 0, lg.shape[1]
+        if C != self.C:
+            raise ValueError(f'{C} classes fed to a search over {self.C}')
+        if n:
+            ptr = ctypes.cast(lg.ctypes.data + 4 * offset, POINTER(c_float))
+            rc = self.lib.nasr_ctc_beam_feed(self.h, ptr, stride, n)
+            if rc != 0:
+                raise _lib.NasrError(rc, 'nasr_ctc_beam_feed: bad arguments')
+        self.frames += n
+
+    def best(self):
+        """(ids, log-probability) of the top path of the frames fed so far; does not disturb the search."""
+        ids = np.zeros(max(self.frames, 1), np.int32)
+        n, logp = c_int32(), c_float()
+        rc = self.lib.nasr_ctc_beam_best(self.h, _ip(ids), ids.size, byref(n), byref(logp))
+        if rc != 0:
+            raise _lib.NasrError(rc, 'nasr_ctc_beam_best: bad arguments')
+        return ids[:n.value].tolist(), float(logp.value)
+
+    def close(self):
+        if getattr(self, 'h', None):
+            self.lib.nasr_ctc_beam_close(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class WaveNetEngine(Engine):

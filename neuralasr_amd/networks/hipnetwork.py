@@ -542,6 +542,13 @@ class HipNetwork(Network):
         hyps = self._decode(mfccs, seq_len, self.decoder, self.language_model())
         return np.asarray([i for h in hyps for i in h], dtype=np.int64)
 
+    def stream(self, slots=1):
+        """A stream.StreamingRecognizer on this network: `slots` concurrent streams fed chunk by chunk, the LSTM state
+        carried on the GPU, the hypothesis available after every chunk.  Raises the library's message for
+        a network that cannot stream (bidirectional layers, dropout, WaveNet, LAS)."""
+        from ..stream import StreamingRecognizer
+        return StreamingRecognizer(self, slots)
+
     def align(self, mfccs, labels, seq_len, labels_len):
         """Forced alignment: for every utterance (score, [(symbol id, first frame, last frame)] in label
         order) - the log-probability of its best CTC path and the logit frames that path spends on each label (blank
