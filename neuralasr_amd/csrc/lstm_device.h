@@ -50,9 +50,10 @@ __device__ __forceinline__ float lstm_state(f32x4 act, float& c) {
 // BPTT of one cell: dG (i, j, f, o) and dc_out, the dc handed to the step before, from the saved activations, this step's
 // c, the c the forward step started from (first: the sequence's first step started from 0, c_prev is not looked at), dh
 // and the dc handed back by the step after.  A masked step does not call this: its dG and dc_out are 0.
-__device__ __forceinline__ f32x4 lstm_cell_bwd(f32x4 act, float c, float c_prev, bool first, float dh, float dc_in,
-                                               float& dc_out) {
-  const float tc = tanhf_(c);
+// lstm_cell_bwd_tc takes tc = tanhf_(c) in place of c (nothing else reads c): a caller that has c early - the persistent
+// BPTT kernel's memory wave - takes the tanh off the chain of the wave that does the cell.
+__device__ __forceinline__ f32x4 lstm_cell_bwd_tc(f32x4 act, float tc, float c_prev, bool first, float dh, float dc_in,
+                                                  float& dc_out) {
   const float dct = dc_in + dh * act.w * (1.f - tc * tc);
   f32x4 dg;
   dg.x = dct * act.y * act.x * (1.f - act.x);
@@ -61,6 +62,10 @@ __device__ __forceinline__ f32x4 lstm_cell_bwd(f32x4 act, float c, float c_prev,
   dg.w = dh * tc * act.w * (1.f - act.w);
   dc_out = dct * act.z;
   return dg;
+}
+__device__ __forceinline__ f32x4 lstm_cell_bwd(f32x4 act, float c, float c_prev, bool first, float dh, float dc_in,
+                                               float& dc_out) {
+  return lstm_cell_bwd_tc(act, tanhf_(c), c_prev, first, dh, dc_in, dc_out);
 }
 
 // v as two fp16 planes: h1 = fp16(v), h2 = fp16(v - h1)

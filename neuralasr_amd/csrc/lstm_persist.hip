@@ -500,7 +500,9 @@ __global__ __launch_bounds__(320, 1) void lstm_persist_bwd_kernel(
   float* gpx = px + (size_t)xcc * 2 * 32 * 32 * 64;
   gu32* gflag = (gu32*)(ctl->flags + xcc * 128);
 
-  const int q = lane & 3, u = lane >> 2;        // cell decomposition: lane = 4*u + q, the order of an exchange row
+  // cell decomposition, the same in every wave and the forward kernel's: lane = 16*q + u -> utterance slot q, unit
+  // NU*member + u.  A 16-lane row is then one utterance slot, and lane (q, u) reads 16-byte pieces of the exchange rows
+  const int q = lane >> 4, u = lane & 15;
   const bool lane_ok = u < NU;
   const int j = NU * (int)member + u;
   const int jcl = j < Hp ? j : Hp - 1;
@@ -534,10 +536,13 @@ __global__ __launch_bounds__(320, 1) void lstm_persist_bwd_kernel(
       pb.y = cbuf[rp * (unsigned)DH + cj];
       pb.z = dout[r * (unsigned)DH + cj];
     };
-    auto hand_over = [&](int k) {   // operands of step k -> LDS, read by the cell wave after the next barrier
+    // operands of step k -> LDS, read by the cell wave after the next barrier.  c travels as tanh(c), all the cell update
+    // wants of it (lstm_cell_bwd_tc): five dependent instructions that the cell wave had at the head of its chain, here in
+    // a wave that waits for the barrier anyway (the same function on the same input: the same bits)
+    auto hand_over = [&](int k) {
       float* dst = pfb + ((k & 1) * 64 + lane) * 8;
       *reinterpret_cast<f32x4*>(dst) = pa;
-      *reinterpret_cast<f32x4*>(dst + 4) = pb;
+      *reinterpret_cast<f32x4*>(dst + 4) = (f32x4){tanhf_(pb.x), pb.y, pb.z, pb.w};
     };
     auto store_dg = [&](int k) {    // memory wave: frame-indexed dG of step k (zero at masked frames) from the A image
       float m = 0.f;
@@ -552,12 +557,12 @@ __global__ __launch_bounds__(320, 1) void lstm_persist_bwd_kernel(
         cmax = (f32x4){fmaxf(cmax.x, ab.x), fmaxf(cmax.y, ab.y), fmaxf(cmax.z, ab.z), fmaxf(cmax.w, ab.w)};
         m = fmaxf(fmaxf(ab.x, ab.y), fmaxf(ab.z, ab.w));
       }
-      if (rowpart) {   // max over the CU's units of this utterance slot: lanes 4u + q, u = 0..15 (order-independent: exact)
+      if (rowpart) {   // max over the CU's units of this utterance slot: the 16 lanes of row q (order-independent: exact)
+        m = fmaxf(m, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, m), 0x121, 0xf, 0xf, false)));   // row_ror:1
+        m = fmaxf(m, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, m), 0x122, 0xf, 0xf, false)));   // row_ror:2
         m = fmaxf(m, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, m), 0x124, 0xf, 0xf, false)));   // row_ror:4
         m = fmaxf(m, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, m), 0x128, 0xf, 0xf, false)));   // row_ror:8
-        m = fmaxf(m, __shfl_xor(m, 16));
-        m = fmaxf(m, __shfl_xor(m, 32));
-        if (lane < 4 && rowok) rowpart[(size_t)(d * 32 + (int)member) * ((size_t)T * Bp) + row] = m;
+        if (u == 0 && rowok) rowpart[(size_t)(d * 32 + (int)member) * ((size_t)T * Bp) + row] = m;
       }
     };
     if (w == 4) {
@@ -591,73 +596,79 @@ __global__ __launch_bounds__(320, 1) void lstm_persist_bwd_kernel(
         const f32x4 o = *reinterpret_cast<const f32x4*>(pf + 4);
         float dhs = o.z;
         if (k > 0 && ok) {
-          const float* src = gpx + ((size_t)(((k - 1) & 1) * 32 + member) * 32) * 64 + lane;
-          float pv[32];
+          // the 32 producers' rows [consumer = member][producer p][16 units][4 utterances] of step k-1 are contiguous: lane
+          // 16g + u reads the 16 bytes of unit u (its four utterances) of producers p = 4i + g, i = 0..7 - one wave
+          // instruction is 1 KB of contiguous memory, and the 8 KB arrive in 8 instructions (the producers stored them
+          // 16 bytes at a time too)
+          const float* src = gpx + ((size_t)(((k - 1) & 1) * 32 + member) * 32) * 64 + 4 * lane;
+          f32x4 P[8];
 #pragma unroll
-          for (int p = 0; p < 32; ++p) pv[p] = 0.f;
-#define NASR_LD8(g8)                                                                                               \
-  asm volatile(                                                                                                    \
-      "global_load_dword %0, %8, off sc1\n\tglobal_load_dword %1, %8, off offset:256 sc1\n\t"                       \
-      "global_load_dword %2, %8, off offset:512 sc1\n\tglobal_load_dword %3, %8, off offset:768 sc1\n\t"            \
-      "global_load_dword %4, %8, off offset:1024 sc1\n\tglobal_load_dword %5, %8, off offset:1280 sc1\n\t"          \
-      "global_load_dword %6, %8, off offset:1536 sc1\n\tglobal_load_dword %7, %8, off offset:1792 sc1"              \
-      : "=&v"(pv[g8 + 0]), "=&v"(pv[g8 + 1]), "=&v"(pv[g8 + 2]), "=&v"(pv[g8 + 3]), "=&v"(pv[g8 + 4]),             \
-        "=&v"(pv[g8 + 5]), "=&v"(pv[g8 + 6]), "=&v"(pv[g8 + 7])                                                    \
-      : "v"(src + (size_t)(g8) * 64)                                                                               \
-      : "memory")
+          for (int i = 0; i < 8; ++i) P[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
           // the sums themselves say whether they are those of step k-1 - bit 0 of every word is the epoch of this use
-          // of the buffer; a lane that finds a stale word loads its 32 again (one round trip when everybody is on time,
-          // and no acknowledgement wait or flag on the producers' side)
+          // of the buffer; a lane that finds a stale word loads its 8 x 16 bytes again (one round trip when everybody is on
+          // time, and no acknowledgement wait or flag on the producers' side).
+          // One attempt is ONE asm statement: the loads of the lanes in `mask` (exec narrowed around them: the other lanes
+          // keep their words in place) and one wait for all of them.  Nothing hipcc emits can then come between a load and
+          // the wait - with the loads under a C++ branch it merged the two cases by copying the 16-byte destinations while
+          // the loads were in flight.
           const unsigned eexp = use_epoch(rd, T, k - 1);
-          bool need = lane_ok;
+          unsigned long long mask = __ballot(lane_ok);
           bool got = false;
           for (unsigned n = 0; n < SPIN_BUDGET; ++n) {
-            if (need) { NASR_LD8(0); NASR_LD8(8); NASR_LD8(16); NASR_LD8(24); }
-            // one wait for all 32 loads; naming every destination keeps hipcc from touching them before it
-            asm volatile("s_waitcnt vmcnt(0)"
-                         : "+v"(pv[0]), "+v"(pv[1]), "+v"(pv[2]), "+v"(pv[3]), "+v"(pv[4]), "+v"(pv[5]), "+v"(pv[6]),
-                           "+v"(pv[7]), "+v"(pv[8]), "+v"(pv[9]), "+v"(pv[10]), "+v"(pv[11]), "+v"(pv[12]), "+v"(pv[13]),
-                           "+v"(pv[14]), "+v"(pv[15])
-                         :
-                         : "memory");
-            asm volatile(""
-                         : "+v"(pv[16]), "+v"(pv[17]), "+v"(pv[18]), "+v"(pv[19]), "+v"(pv[20]), "+v"(pv[21]), "+v"(pv[22]),
-                           "+v"(pv[23]), "+v"(pv[24]), "+v"(pv[25]), "+v"(pv[26]), "+v"(pv[27]), "+v"(pv[28]), "+v"(pv[29]),
-                           "+v"(pv[30]), "+v"(pv[31])
-                         :
-                         : "memory");
+            unsigned long long saved;
+            asm volatile(
+                "s_and_saveexec_b64 %[sv], %[m]\n\t"
+                "global_load_dwordx4 %0, %[a0], off sc1\n\tglobal_load_dwordx4 %1, %[a0], off offset:1024 sc1\n\t"
+                "global_load_dwordx4 %2, %[a0], off offset:2048 sc1\n\tglobal_load_dwordx4 %3, %[a0], off offset:3072 sc1\n\t"
+                "global_load_dwordx4 %4, %[a1], off sc1\n\tglobal_load_dwordx4 %5, %[a1], off offset:1024 sc1\n\t"
+                "global_load_dwordx4 %6, %[a1], off offset:2048 sc1\n\tglobal_load_dwordx4 %7, %[a1], off offset:3072 sc1\n\t"
+                "s_mov_b64 exec, %[sv]\n\t"
+                "s_waitcnt vmcnt(0)"
+                : "+v"(P[0]), "+v"(P[1]), "+v"(P[2]), "+v"(P[3]), "+v"(P[4]), "+v"(P[5]), "+v"(P[6]), "+v"(P[7]),
+                  [sv] "=&s"(saved)
+                : [m] "s"(mask), [a0] "v"(src), [a1] "v"(src + 1024)
+                : "memory", "scc");
             unsigned bad;                     // bit 0: some word of this lane is not of epoch eexp (wave-uniform branch)
             if (eexp) {
               unsigned a_ = 1u;
 #pragma unroll
-              for (int p = 0; p < 32; ++p) a_ &= __float_as_uint(pv[p]);
+              for (int i = 0; i < 8; ++i)
+                a_ &= (__float_as_uint(P[i][0]) & __float_as_uint(P[i][1])) & (__float_as_uint(P[i][2]) & __float_as_uint(P[i][3]));
               bad = ~a_;
             } else {
               unsigned o_ = 0u;
 #pragma unroll
-              for (int p = 0; p < 32; ++p) o_ |= __float_as_uint(pv[p]);
+              for (int i = 0; i < 8; ++i)
+                o_ |= (__float_as_uint(P[i][0]) | __float_as_uint(P[i][1])) | (__float_as_uint(P[i][2]) | __float_as_uint(P[i][3]));
               bad = o_;
             }
-            need = lane_ok && (bad & 1u) != 0;
-            if (!__any(need)) { got = true; break; }
+            mask = __ballot(lane_ok && (bad & 1u) != 0);
+            if (mask == 0) { got = true; break; }
 #if NASR_PSTAMP   // (not even an empty call here: it changes how hipcc lays out the spin loop)
             stp.add(11, 1);                      // extra attempts
 #endif
           }
-#undef NASR_LD8
           if (!got) ok = false;
-          if (lane_ok) {
-            float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
+          // The sum keeps the order it had when a lane read one word of each of the 32 rows: s_g = the producers g, g + 4,
+          // ... from zero, then (s0 + s1) + (s2 + s3).  Component q of lane group g's accumulator IS s_g of cell (u, q).
+          // One v_permlane16_swap pairs the groups for two components at once (rows 0 / 2 end up with s_g + s_g+1 of
+          // component 0 resp. 2, rows 1 / 3 with that of component 1 resp. 3: operand order s0 + s1 in every row), one
+          // v_permlane32_swap the pairs: lane (g, u) holds the total of component q = g.  (Lanes u >= NU hold zeros.)
+          f32x4 sg = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-            for (int p = 0; p < 32; p += 4) { s0 += pv[p]; s1 += pv[p + 1]; s2 += pv[p + 2]; s3 += pv[p + 3]; }
-            dhs += (s0 + s1) + (s2 + s3);
-          }
+          for (int i = 0; i < 8; ++i) sg += P[i];
+          const auto r01 = __builtin_amdgcn_permlane16_swap(__float_as_uint(sg[0]), __float_as_uint(sg[1]), false, false);
+          const auto r23 = __builtin_amdgcn_permlane16_swap(__float_as_uint(sg[2]), __float_as_uint(sg[3]), false, false);
+          const float p01 = __uint_as_float(r01[0]) + __uint_as_float(r01[1]);   // rows 0, 1: s0 + s1; rows 2, 3: s2 + s3
+          const float p23 = __uint_as_float(r23[0]) + __uint_as_float(r23[1]);
+          const auto rt = __builtin_amdgcn_permlane32_swap(__float_as_uint(p01), __float_as_uint(p23), false, false);
+          dhs += __uint_as_float(rt[0]) + __uint_as_float(rt[1]);               // (s0 + s1) + (s2 + s3) of component q
         }
         stp.mark(2);
         // 2. gate derivatives of this CU's cells
         f32x4 dg = (f32x4){0.f, 0.f, 0.f, 0.f};
         float dcn = 0.f;
-        if (valid) dg = lstm_cell_bwd(a, o.x, o.y, s == 0, dhs, dc, dcn);
+        if (valid) dg = lstm_cell_bwd_tc(a, o.x, o.y, s == 0, dhs, dc, dcn);   // o.x: tanh(c) from the memory wave
         dc = dcn;
         if (lane_ok) {   // A image: adg[par][c = 4u+g][utterance q]
           float* ad = adg + par * 256 + 16 * u + q;
@@ -719,13 +730,14 @@ __global__ __launch_bounds__(320, 1) void lstm_persist_bwd_kernel(
     if (aborted) break;
     __syncthreads();                  // pfb / adg are reused by the next round
   }
-  if (w == 4 && colpart) {   // column maxima of this group's utterances: over the 4 utterance slots (lanes 4u + q), then out
+  if (w == 4 && colpart) {   // column maxima of this group's utterances: over the 4 utterance slots (the rows 16q + u), then out
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-      float v = cmax[i];
-      v = fmaxf(v, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xf, 0xf, false)));   // quad_perm [1,0,3,2]
-      v = fmaxf(v, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x4E, 0xf, 0xf, false)));   // quad_perm [2,3,0,1]
-      cmax[i] = v;
+      // swapping a value with itself leaves every lane with its own and its partner row's (resp. half's) value
+      const auto r16 = __builtin_amdgcn_permlane16_swap(__float_as_uint(cmax[i]), __float_as_uint(cmax[i]), false, false);
+      const float v = fmaxf(__uint_as_float(r16[0]), __uint_as_float(r16[1]));
+      const auto r32 = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
+      cmax[i] = fmaxf(__uint_as_float(r32[0]), __uint_as_float(r32[1]));
     }
     if (q == 0 && lane_ok) *reinterpret_cast<f32x4*>(colpart + ((size_t)grp * DN + (size_t)(d * N4 + 4 * j))) = cmax;
   }
