@@ -20,6 +20,27 @@ constexpr int LAS_SW = LAS_HE + LAS_HD;   // decoder step-input row: [a (256) | 
 // memory feature q (TF order [fw 250; bw 250]) -> internal column
 __host__ __device__ inline int las_memcol(int q) { return (q / LAS_H) * LAS_HE + q % LAS_H; }
 
+// sum over a wave of 64 lanes in a fixed butterfly order (every lane gets the same result)
+__device__ __forceinline__ float wave_sum(float v) {
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+// Thread k (of 512) of a decoder row's initial state: Srow [LAS_SW] = [a = 0 | h = (h_fw final; h_bw final)], crow [LAS_HD] =
+// (c_fw final; c_bw final) of utterance b's top encoder layer (fw: frame L4-1, bw: frame 0); live = false: a zero row
+__device__ __forceinline__ void las_final_state(const float* __restrict__ out4, const float* __restrict__ c4, int L4, int Bp, int b,
+                                                bool live, int k, float* __restrict__ Srow, float* __restrict__ crow) {
+  float h = 0.f, cv = 0.f;
+  if (live && k < 2 * LAS_H) {
+    const int d = k / LAS_H, j = k % LAS_H;
+    const size_t row = (size_t)(d == 0 ? L4 - 1 : 0) * Bp + b;
+    h = out4[row * (2 * LAS_HE) + d * LAS_HE + j];
+    cv = c4[(row * 2 + d) * LAS_H + j];
+  }
+  if (k < LAS_HE) Srow[k] = 0.f;
+  Srow[LAS_HE + k] = h;
+  crow[k] = cv;
+}
+
 // encoder
 void launch_las_enc_fwd_step(const float* xp, const float* WhF, const float* WhB, float* act, float* c, float* out, int s,
                              int L, int B, int Bp, hipStream_t st);
@@ -34,8 +55,10 @@ void launch_las_dec_init(const float* out4, const float* c4, const int32_t* labe
                          float* S0, float* c0, int32_t* ids0, hipStream_t st);
 void launch_las_dec_cell(const float* gp, const float* E, const float* bias, const int32_t* ids, const float* cprev,
                          float* act, float* c, float* Snext, float* HC, int Bp, hipStream_t st);
+// attention of `rows` decoder rows, row r over the memory of utterance r / W; rows >= nrows get a zero context.  alpha
+// [rows][L4] or nullptr; done: nullptr, or a word that makes the launch return at once when it is set
 void launch_las_attend(const float* keys, const float* mem, const float* q, const float* v, float* alpha, float* HC, int L4,
-                       int Bp, hipStream_t st);
+                       int Bp, int W, int nrows, int rows, const int32_t* done, hipStream_t st);
 struct LasSample { float p; uint32_t thr, key; int on; };
 void launch_las_sample(const float* logits, int Cp, int C, const int32_t* labels, int Lmax, int t, int B, int Bp,
                        LasSample smp, int32_t* ids_next, int32_t* sampled, hipStream_t st);

@@ -2,6 +2,8 @@
 // frame-pair packing between its layers, and the attention decoder's per-step cell, Bahdanau attention, scheduled
 // sampling, sequence loss and their gradients.  The bulk products (input projections, keys, query, attention layer,
 // projection, every weight gradient) run on gemm.hip's fp32 MFMA GEMM; nasr_las.hip orchestrates.  Layouts: las.h.
+// The decoder cell and the attention kernel serve the training pass and the beam search (las_beam.hip) alike: a launch is
+// over decoder rows, the training pass's utterances or the search's beams.
 //
 // Scheduled sampling (ScheduledEmbeddingTrainingHelper, sampling_probability p) is defined by a counter-based hash that an
 // oracle can recompute (tests/test_las_host.py):
@@ -21,11 +23,6 @@ __device__ __forceinline__ float sigm(float x) { return 1.f / (1.f + expf(-x)); 
 __device__ __forceinline__ uint32_t lowbias32(uint32_t x) {
   x ^= x >> 16; x *= 0x7FEB352Du; x ^= x >> 15; x *= 0x846CA68Bu; x ^= x >> 16;
   return x;
-}
-// sum over a wave of 64 lanes in a fixed butterfly order (every lane gets the same result)
-__device__ __forceinline__ float wave_sum(float v) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
 }
 }  // namespace
 
@@ -185,16 +182,7 @@ __global__ __launch_bounds__(512) void las_dec_init_kernel(const float* __restri
                                                            int Bp, float* __restrict__ S0, float* __restrict__ c0,
                                                            int32_t* __restrict__ ids0) {
   const int b = blockIdx.x, k = threadIdx.x;
-  float h = 0.f, cv = 0.f;
-  if (b < B && k < 2 * LAS_H) {
-    const int d = k / LAS_H, j = k % LAS_H;
-    const size_t row = (size_t)(d == 0 ? L4 - 1 : 0) * Bp + b;
-    h = out4[row * (2 * LAS_HE) + d * LAS_HE + j];
-    cv = c4[(row * 2 + d) * LAS_H + j];
-  }
-  if (k < LAS_HE) S0[(size_t)b * LAS_SW + k] = 0.f;
-  S0[(size_t)b * LAS_SW + LAS_HE + k] = h;
-  c0[(size_t)b * LAS_HD + k] = cv;
+  las_final_state(out4, c4, L4, Bp, b, b < B, k, S0 + (size_t)b * LAS_SW, c0 + (size_t)b * LAS_HD);
   if (k == 0) ids0[b] = b < B ? labels[(size_t)b * Lmax] : 0;
 }
 
@@ -236,14 +224,24 @@ void launch_las_dec_cell(const float* gp, const float* E, const float* bias, con
   hipLaunchKernelGGL(las_dec_cell_kernel, dim3(Bp), dim3(LAS_HD), 0, st, gp, E, bias, ids, cprev, act, c, Snext, HC);
 }
 
-// Bahdanau attention of utterance b (block b, 4 waves): score_l = v . tanh(keys_l + q), alpha = softmax over all L4
-// frames (no memory mask), context = sum_l alpha_l mem_l into HC[b][512..].  alpha [Bp][L4].
+// Bahdanau attention of decoder row r over the memory of utterance b = r / W (block r, 4 waves): score_l = v . tanh(keys_l
+// + q), alpha = softmax over all L4 frames (no memory mask), context = sum_l alpha_l mem_l into HC[r][512..].  Rows >=
+// nrows get a zero context.  alpha [rows][L4] is stored unless it is nullptr; a set *done (nullptr: none) ends the launch
+// at once.  Training: W = 1 and nrows = Bp (every padded row runs the body); the beam search: its W, nrows = B*W.
 __global__ __launch_bounds__(256) void las_attend_kernel(const float* __restrict__ keys, const float* __restrict__ mem,
                                                          const float* __restrict__ q, const float* __restrict__ v,
-                                                         float* __restrict__ alpha, float* __restrict__ HC, int L4, int Bp) {
+                                                         float* __restrict__ alpha, float* __restrict__ HC, int L4, int Bp,
+                                                         int W, int nrows, const int32_t* __restrict__ done) {
   extern __shared__ float sc[];
-  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const float* qb = q + (size_t)b * LAS_HD;
+  if (done && *done) return;
+  const int r = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  float* ctx = HC + (size_t)r * 2 * LAS_HD + LAS_HD;
+  if (r >= nrows) {
+    for (int k = tid; k < LAS_HD; k += blockDim.x) ctx[k] = 0.f;
+    return;
+  }
+  const int b = r / W;
+  const float* qb = q + (size_t)r * LAS_HD;
   for (int l = w; l < L4; l += 4) {
     const float* kr = keys + ((size_t)l * Bp + b) * LAS_HD;
     float s = 0.f;
@@ -260,17 +258,19 @@ __global__ __launch_bounds__(256) void las_attend_kernel(const float* __restrict
     for (int l = 0; l < L4; ++l) sc[l] = sc[l] / z;
   }
   __syncthreads();
-  for (int l = tid; l < L4; l += blockDim.x) alpha[(size_t)b * L4 + l] = sc[l];
+  if (alpha)
+    for (int l = tid; l < L4; l += blockDim.x) alpha[(size_t)r * L4 + l] = sc[l];
   for (int k = tid; k < LAS_HD; k += blockDim.x) {
     float s = 0.f;
     for (int l = 0; l < L4; ++l) s = fmaf(sc[l], mem[((size_t)l * Bp + b) * LAS_HD + k], s);
-    HC[(size_t)b * 2 * LAS_HD + LAS_HD + k] = s;
+    ctx[k] = s;
   }
 }
 
 void launch_las_attend(const float* keys, const float* mem, const float* q, const float* v, float* alpha, float* HC, int L4,
-                       int Bp, hipStream_t st) {
-  hipLaunchKernelGGL(las_attend_kernel, dim3(Bp), dim3(256), (size_t)L4 * 4, st, keys, mem, q, v, alpha, HC, L4, Bp);
+                       int Bp, int W, int nrows, int rows, const int32_t* done, hipStream_t st) {
+  hipLaunchKernelGGL(las_attend_kernel, dim3(rows), dim3(256), (size_t)L4 * 4, st, keys, mem, q, v, alpha, HC, L4, Bp, W, nrows,
+                     done);
 }
 
 // the input of step t+1: labels[:, t+1], or with probability p a sample from softmax(logits_t) (one thread per utterance)

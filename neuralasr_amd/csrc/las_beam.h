@@ -11,8 +11,6 @@ namespace nasr {
 void launch_las_beam_init(const float* out4, const float* c4, int L4, int Bp, int W, int nrows, int R, int start_id, float* S,
                           float* c, int32_t* ids, float* logp, int32_t* len, int32_t* fin, int32_t* ctx, int ctx0,
                           hipStream_t st);
-void launch_las_beam_attend(const float* keys, const float* mem, const float* q, const float* v, float* HC, int L4, int Bp,
-                            int W, int nrows, int R, const int32_t* done, hipStream_t st);
 void launch_las_beam_score(const float* logits, int Cp, int C, const float* logp, const int32_t* len, const int32_t* fin,
                            const float* pen, int end_id, int nrows, const float* table, const int32_t* ctx, float weight,
                            float* scores, float* totals, const int32_t* done, hipStream_t st);

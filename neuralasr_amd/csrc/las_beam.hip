@@ -1,7 +1,7 @@
 // las_beam.hip — the kernels of the LAS inference graph's beam search (tf.contrib.seq2seq.BeamSearchDecoder of TF 1.15,
-// DESIGN.md §10): the tiled initial state, attention of beam rows over their utterance's memory, the step's scores, an
-// exact per-utterance top-W, the state update by parent and gather_tree.  nasr_las.hip orchestrates; the decoder cell and
-// every product are the training path's (las.hip, gemm.hip).
+// DESIGN.md §10): the tiled initial state, the step's scores, an exact per-utterance top-W, the state update by parent and
+// gather_tree.  nasr_las.hip orchestrates; the decoder step itself (cell, attention of a beam row over its utterance's
+// memory, every product) is the training path's (las.hip, gemm.hip), as are wave_sum and the final-state gather (las.h).
 //
 // Beam rows r = b*W + k (utterance b, beam k), R = rup(B*W, 16) rows; rows >= B*W are padding that no selection reads.
 // Every kernel of a step after the one that finished every beam returns at once: *done (set by las_beam_finish) is read
@@ -18,10 +18,6 @@
 namespace nasr {
 
 namespace {
-__device__ __forceinline__ float wave_sum_b(float v) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
 __device__ __forceinline__ float wave_max_b(float v) {
   for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
   return v;
@@ -51,16 +47,7 @@ __global__ __launch_bounds__(512) void las_beam_init_kernel(const float* __restr
                                                             float* __restrict__ logp, int32_t* __restrict__ len,
                                                             int32_t* __restrict__ fin, int32_t* __restrict__ ctx, int ctx0) {
   const int r = blockIdx.x, k = threadIdx.x;
-  float h = 0.f, cv = 0.f;
-  if (r < nrows && k < 2 * LAS_H) {
-    const int b = r / W, d = k / LAS_H, j = k % LAS_H;
-    const size_t row = (size_t)(d == 0 ? L4 - 1 : 0) * Bp + b;
-    h = out4[row * (2 * LAS_HE) + d * LAS_HE + j];
-    cv = c4[(row * 2 + d) * LAS_H + j];
-  }
-  if (k < LAS_HE) S[(size_t)r * LAS_SW + k] = 0.f;
-  S[(size_t)r * LAS_SW + LAS_HE + k] = h;
-  c[(size_t)r * LAS_HD + k] = cv;
+  las_final_state(out4, c4, L4, Bp, r / W, r < nrows, k, S + (size_t)r * LAS_SW, c + (size_t)r * LAS_HD);
   if (k == 0) {
     const int kb = r < nrows ? r % W : 1;
     ids[r] = start_id;
@@ -76,51 +63,6 @@ void launch_las_beam_init(const float* out4, const float* c4, int L4, int Bp, in
                           hipStream_t st) {
   hipLaunchKernelGGL(las_beam_init_kernel, dim3(R), dim3(LAS_HD), 0, st, out4, c4, L4, Bp, W, nrows, start_id, S, c, ids, logp,
                      len, fin, ctx, ctx0);
-}
-
-// Bahdanau attention of beam row r over the memory of utterance r / W (block r, 4 waves): the arithmetic of
-// las_attend_kernel; the context goes to HC[r][512..].  Padding rows get a zero context.
-__global__ __launch_bounds__(256) void las_beam_attend_kernel(const float* __restrict__ keys, const float* __restrict__ mem,
-                                                              const float* __restrict__ q, const float* __restrict__ v,
-                                                              float* __restrict__ HC, int L4, int Bp, int W, int nrows,
-                                                              const int32_t* __restrict__ done) {
-  extern __shared__ float sc[];
-  if (*done) return;
-  const int r = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  float* ctx = HC + (size_t)r * 2 * LAS_HD + LAS_HD;
-  if (r >= nrows) {
-    for (int k = tid; k < LAS_HD; k += blockDim.x) ctx[k] = 0.f;
-    return;
-  }
-  const int b = r / W;
-  const float* qb = q + (size_t)r * LAS_HD;
-  for (int l = w; l < L4; l += 4) {
-    const float* kr = keys + ((size_t)l * Bp + b) * LAS_HD;
-    float s = 0.f;
-    for (int k = lane; k < LAS_HD; k += 64) s = fmaf(v[k], tanhf(kr[k] + qb[k]), s);
-    s = wave_sum_b(s);
-    if (lane == 0) sc[l] = s;
-  }
-  __syncthreads();
-  if (tid == 0) {
-    float m = sc[0];
-    for (int l = 1; l < L4; ++l) m = fmaxf(m, sc[l]);
-    float z = 0.f;
-    for (int l = 0; l < L4; ++l) { sc[l] = expf(sc[l] - m); z += sc[l]; }
-    for (int l = 0; l < L4; ++l) sc[l] = sc[l] / z;
-  }
-  __syncthreads();
-  for (int k = tid; k < LAS_HD; k += blockDim.x) {
-    float s = 0.f;
-    for (int l = 0; l < L4; ++l) s = fmaf(sc[l], mem[((size_t)l * Bp + b) * LAS_HD + k], s);
-    ctx[k] = s;
-  }
-}
-
-void launch_las_beam_attend(const float* keys, const float* mem, const float* q, const float* v, float* HC, int L4, int Bp,
-                            int W, int nrows, int R, const int32_t* done, hipStream_t st) {
-  hipLaunchKernelGGL(las_beam_attend_kernel, dim3(R), dim3(256), (size_t)L4 * 4, st, keys, mem, q, v, HC, L4, Bp, W, nrows,
-                     done);
 }
 
 // One wave per beam row: lp = (l - max) - log(sum exp(l - max)) (the sum: lane-strided partials, then a fixed butterfly);
@@ -144,7 +86,7 @@ __global__ __launch_bounds__(256) void las_beam_score_kernel(const float* __rest
   m = wave_max_b(m);
   float z = 0.f;
   for (int w = lane; w < C; w += 64) z += expf(l[w] - m);
-  z = wave_sum_b(z);
+  z = wave_sum(z);
   const float lse = logf(z);
   const bool f = fin[r] != 0;
   const float lp0 = logp[r];

@@ -440,6 +440,15 @@ namespace nasr_impl {
     if ((h) && (h)->family != Family::Lstm)                                                               \
       return (h)->fail(NASR_ERR_STATE, std::string(__func__) + ": a WaveNet or LAS handle " reason);      \
   } while (0)
+// the first statement of a call that only one family answers: a null handle is NASR_ERR_ARG, a handle of another family
+// NASR_ERR_STATE with "<function>: not a LAS handle" / "... not a WaveNet handle"
+#define FAMILY_CALL(h, state, text)                                                                       \
+  do {                                                                                                    \
+    if (!(h)) return NASR_ERR_ARG;                                                                        \
+    if (!(h)->state) return (h)->fail(NASR_ERR_STATE, std::string(__func__) + ": " text);                 \
+  } while (0)
+#define LAS_CALL(h) FAMILY_CALL(h, las, "not a LAS handle")
+#define WAVENET_CALL(h) FAMILY_CALL(h, wn, "not a WaveNet handle")
 // ---- tiled fp16 planes (gemm_tph.hip) ---------------------------------------------------------------------------
 inline size_t pl_rb_bytes(int nkb) { return (size_t)nkb * 2 * 1024; }   // one 32-row block: nkb k-blocks x 2 parts x 1 KiB
 // scales of src [rows][K]: per row into `row`, per column into `col` (either may be NULL)
@@ -610,6 +619,12 @@ inline const float* lstm_input(nasr_ctx* h, int l) {
 // ---- nasr_pass.hip
 // the fp32 GEMM g (gemm.hip) on the handle's stream; g.split_k > 1 gets the handle's slab workspace, grown to fit
 int gemm_f32(nasr_ctx* h, GemmDesc g);
+// C [M][N] = op(A) op(B) (+ bias per column) as one gemm_f32 call; a_col / b_col: the operand is stored transposed.
+// a_shift / a_rows: rows of A are read a_shift rows further on, and rows outside [0, a_rows) read as zero (a_rows < 0: all
+// of A, K rows when a_col and M otherwise).  With a bias the product is not split along K.
+int gemm_dense(nasr_ctx* h, const float* A, const float* B, float* C, int M, int N, int K, int lda, int ldb, int ldc, bool a_col,
+               bool b_col, const float* bias = nullptr, int a_shift = 0, int a_rows = -1);
+inline float* fp(const DevBuf& b, size_t off = 0) { return b.as<float>() + off; }
 // chunk: the resident batch is a chunk of the open stream session - the recurrence continues from the session's state on
 // the per-step kernels and saves it again; the fault word, the resident kinds' control blocks and the dropout counter stay
 int forward(nasr_ctx* h, bool chunk = false);

@@ -3,8 +3,10 @@
 // directions over every padded frame) and an attention decoder (BasicLSTMCell(500) in an AttentionWrapper with
 // unnormalised Bahdanau attention over the top layer's output, attention layer 250, projection to the classes), trained
 // with scheduled sampling and sequence_loss.  This file holds the handle's create call, parameter layout, buffers and the
-// forward / backward pass; the kernels are in las.hip and gemm.hip.  Opening and finishing the handle, batches, Adam, gradient
-// exchange and checkpoints are the common code.  DESIGN.md §10.
+// forward / backward pass, and the beam search; the kernels are in las.hip, las_beam.hip and gemm.hip.  The
+// training pass and the search run the same encoder loop (las_encode, each over a LasEnc of its own) and the same decoder
+// step (las_decoder_step).  Opening and finishing the handle, batches, Adam, gradient exchange and checkpoints are the
+// common code.  DESIGN.md §10.
 #include "nasr_ctx.h"
 #include "las.h"
 #include "las_beam.h"
@@ -16,15 +18,35 @@ using namespace nasr_impl;
 
 namespace nasr_impl {
 
+// One set of encoder activations, rows Lr[l] * Bp per layer: the training pass has one, the beam search another
+struct LasEnc {
+  static constexpr int NL = 4;
+  int Lr[NL] = {0, 0, 0, 0};   // frames each layer runs over: L1 = T + T%2, L(i+1) = L(i)/2 + (L(i)/2)%2
+  DevBuf X[NL], xp[NL], act[NL], c[NL], out[NL];
+  // sizes the buffers for T frames of Bp rows and sets Lr; false: an allocation failed
+  bool ensure(int T, int Bp, bool* grew) {
+    bool ok = true;
+    for (int l = 0, L = T + T % 2; l < NL; ++l, L = L / 2 + (L / 2) % 2) {
+      const size_t R = (size_t)L * Bp;
+      Lr[l] = L;
+      if (l > 0) ok &= X[l].ensure(R * 4 * LAS_HE * 4, grew);
+      ok &= xp[l].ensure(R * 2 * LAS_G4E * 4, grew);
+      ok &= act[l].ensure(R * 2 * LAS_G4E * 4, grew);
+      ok &= c[l].ensure(R * 2 * LAS_H * 4, grew);
+      ok &= out[l].ensure(R * 2 * LAS_HE * 4, grew);
+    }
+    return ok;
+  }
+};
+
 // The beam search's own buffers (nasr_las_beam_search), made on the first search and apart from the training pass's: a
 // search leaves the resident batch, the last pass's logits and loss, the gradient and the sampling state as they are.
 // Beam rows r = b*W + k, R = rup(B*W, 16); the encoder's rows t*Bp + b as in training.
 struct LasBeam {
-  static constexpr int NL = 4;
   int B = 0, Bp = 0, T = 0, W = 0, R = 0, max_steps = 0, Tdec = 0, end_id = 0;
-  int Lr[NL] = {0, 0, 0, 0};
   bool have = false, timed = false;
-  DevBuf feats, X0, X[NL], xp[NL], act[NL], c[NL], out[NL], keys;
+  LasEnc enc;
+  DevBuf feats, X0, keys;
   // decoder rows: S / c the beams' state, Sx / cx the step's outputs before the gather by parent
   DevBuf S, cs, Sx, cx, gp, dact, HC, Q, logits, ids;
   DevBuf logp[2], len[2], fin[2], ctx[2];          // ping-pong by step parity: step t reads [t & 1], writes the other
@@ -38,23 +60,20 @@ struct LasBeam {
 
 struct LasState {
   nasr_las_cfg cfg;
-  static constexpr int NL = 4;
   // internal parameter layout (floats from P): per layer Wx [Ip][2*G4E] (fw | bw gate columns), Wh fw / bw [LAS_HE][G4E],
   // bias [2*G4E]; memory_layer [512][512]; the decoder kernel's one-hot rows E [C][G4D], its [a; h] rows Wah [768][G4D],
   // its bias; query_layer [512][512]; attention_v [512]; attention_layer [1024][256]; projection [256][Cp], bias [Cp]
-  int Ip[NL];
-  int64_t off_wx[NL], off_whf[NL], off_whb[NL], off_b[NL];
+  int Ip[LasEnc::NL];
+  int64_t off_wx[LasEnc::NL], off_whf[LasEnc::NL], off_whb[LasEnc::NL], off_b[LasEnc::NL];
   int64_t off_wmem = 0, off_e = 0, off_wah = 0, off_bd = 0, off_wq = 0, off_v = 0, off_watt = 0, off_wp = 0, off_bp = 0;
   // scheduled sampling: probability, hash seed, pass counter, tower (las.hip)
   float p = 0.1f;
   uint32_t seed = 1u, counter = 0u;
   int tower = 0;
-  // shape of the resident batch
-  int Lr[NL] = {0, 0, 0, 0};   // frames each layer runs over
+  // shape of the resident batch and its encoder activations
   int U = 0;
   bool have_pass = false;
-  // encoder activations per layer, rows Lr[l] * Bp
-  DevBuf X[NL], xp[NL], act[NL], c[NL], out[NL];
+  LasEnc enc;
   DevBuf dGe, dX, dout, dhc, dcc, whT;   // whT: [2][G4E][LAS_HE] the layer's recurrent matrices transposed (BPTT)
   // attention and decoder
   DevBuf keys, dkeys, dmem, tmpm;
@@ -67,23 +86,6 @@ struct LasState {
   float lm_weight = 0.f;
 };
 
-namespace {
-inline float* fp(const DevBuf& b, size_t off = 0) { return b.as<float>() + off; }
-
-int las_gemm(nasr_ctx* h, const float* A, const float* B, float* C, int M, int N, int K, int lda, int ldb, int ldc, bool a_col,
-             bool b_col, const float* bias = nullptr, int a_shift = 0, int a_rows = -1) {
-  GemmDesc g{};
-  g.A = A; g.B = B; g.C = C;
-  g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldc = ldc;
-  g.a_col = a_col; g.b_col = b_col;
-  g.a_shift = a_shift;
-  g.a_rows = a_rows >= 0 ? a_rows : (a_col ? K : M);
-  g.bias = bias;
-  g.split_k = bias ? 1 : gemm_pick_split(M, N, K);
-  return gemm_f32(h, g);
-}
-}  // namespace
-
 int las_layout(nasr_ctx* h) {
   LasState& s = *h->las;
   const int C = s.cfg.num_classes;
@@ -94,7 +96,7 @@ int las_layout(nasr_ctx* h) {
   h->H = h->Hp = h->N4 = h->D = h->L = 0;
   h->Pin = h->Pinp = 0;
   int64_t off = 0;
-  for (int l = 0; l < LasState::NL; ++l) {
+  for (int l = 0; l < LasEnc::NL; ++l) {
     s.Ip[l] = l == 0 ? h->Fp : 4 * LAS_HE;
     s.off_wx[l] = off; off += (int64_t)s.Ip[l] * 2 * LAS_G4E;
     s.off_whf[l] = off; off += (int64_t)LAS_HE * LAS_G4E;
@@ -122,7 +124,7 @@ int las_layout(nasr_ctx* h) {
       for (int64_t c = 0; c < cols; ++c) h->tf2int.push_back((int32_t)where(r, c));
     tf += rows * cols;
   };
-  for (int l = 0; l < LasState::NL; ++l) {
+  for (int l = 0; l < LasEnc::NL; ++l) {
     const int I = l == 0 ? h->F : 4 * LAS_H;
     auto in_row = [l](int64_t r) -> int64_t {   // TF input row -> internal row of Wx (layers >= 1: the pair layout)
       if (l == 0) return r;
@@ -159,35 +161,16 @@ int las_layout(nasr_ctx* h) {
   return NASR_OK;
 }
 
-// L1 = T + T%2, L(i+1) = L(i)/2 + (L(i)/2)%2
-void las_lengths(int T, int* Lr) {
-  int L = T + T % 2;
-  for (int l = 0; l < LasState::NL; ++l) {
-    Lr[l] = L;
-    L = L / 2 + (L / 2) % 2;
-  }
-}
-
 int las_ensure_shape(nasr_ctx* h, int B, int T, int Lmax) {
   LasState& s = *h->las;
   const int Bp = rup(B, 16);
-  int Lr[LasState::NL];
-  las_lengths(T, Lr);
-  const int U = std::max(Lmax, 1), L4 = Lr[LasState::NL - 1];
-  const size_t R0 = (size_t)Lr[0] * Bp, UB = (size_t)U * Bp, MB = (size_t)L4 * Bp;
-  bool grew = false, ok = true;
+  bool grew = false, ok = s.enc.ensure(T, Bp, &grew);
+  const int U = std::max(Lmax, 1), L4 = s.enc.Lr[LasEnc::NL - 1];
+  const size_t R0 = (size_t)s.enc.Lr[0] * Bp, UB = (size_t)U * Bp, MB = (size_t)L4 * Bp;
   ok &= h->X0.ensure((size_t)T * Bp * h->Fp * 4, &grew);
   ok &= h->seqbuf.ensure((size_t)Bp * 4, &grew);
   ok &= h->loss.ensure(16, &grew);
   ok &= h->nll.ensure((size_t)Bp * 4, &grew);
-  for (int l = 0; l < LasState::NL; ++l) {
-    const size_t R = (size_t)Lr[l] * Bp;
-    if (l > 0) ok &= s.X[l].ensure(R * 4 * LAS_HE * 4, &grew);
-    ok &= s.xp[l].ensure(R * 2 * LAS_G4E * 4, &grew);
-    ok &= s.act[l].ensure(R * 2 * LAS_G4E * 4, &grew);
-    ok &= s.c[l].ensure(R * 2 * LAS_H * 4, &grew);
-    ok &= s.out[l].ensure(R * 2 * LAS_HE * 4, &grew);
-  }
   ok &= s.dGe.ensure(R0 * 2 * LAS_G4E * 4, &grew);
   ok &= s.dX.ensure(R0 * 4 * LAS_HE * 4, &grew);
   ok &= s.dout.ensure(R0 * 2 * LAS_HE * 4, &grew);
@@ -218,30 +201,73 @@ int las_ensure_shape(nasr_ctx* h, int B, int T, int Lmax) {
   ok &= s.csws.ensure((size_t)32 * 2 * LAS_G4E * 4, &grew);
   if (!ok) return h->fail(NASR_ERR_HIP, "hipMalloc failed while sizing batch buffers");
   h->B = B; h->Bp = Bp; h->T = T; h->Lmax = Lmax; h->Tp = U; h->KS = 1;
-  for (int l = 0; l < LasState::NL; ++l) s.Lr[l] = Lr[l];
   s.U = U;
   return NASR_OK;
 }
 
-// The pyramidal encoder over X0 [T*Bp][Fp] (rows t*Bp + b) into the given per-layer buffers, Lr: las_lengths(T).  The
+// The pyramidal encoder over X0 [T*Bp][Fp] (rows t*Bp + b, Bp = rup(B, 16)) into e, sized by e.ensure(T, Bp).  The
 // training pass and the beam search share it.
-int las_encode(nasr_ctx* h, const float* X0, int T, int B, int Bp, const int* Lr, DevBuf* X, DevBuf* xp, DevBuf* act, DevBuf* c,
-               DevBuf* out) {
+int las_encode(nasr_ctx* h, const float* X0, int T, int B, LasEnc& e) {
   LasState& s = *h->las;
+  const int Bp = rup(B, 16);
   const float* P = h->P;
   hipStream_t st = h->st;
-  for (int l = 0; l < LasState::NL; ++l) {
-    const int L = Lr[l];
-    const float* Xin = l == 0 ? X0 : fp(X[l]);
+  for (int l = 0; l < LasEnc::NL; ++l) {
+    const int L = e.Lr[l];
+    const float* Xin = l == 0 ? X0 : fp(e.X[l]);
     // rows past the input's frames (the odd-length padding) read as zero
-    const int in_rows = (l == 0 ? T : Lr[l - 1] / 2) * Bp;
-    if (l > 0) launch_las_pyr_pack(fp(out[l - 1]), fp(X[l]), Lr[l - 1] / 2, Bp, st);
-    if (int rc = las_gemm(h, Xin, P + s.off_wx[l], fp(xp[l]), L * Bp, 2 * LAS_G4E, s.Ip[l], s.Ip[l], 2 * LAS_G4E, 2 * LAS_G4E,
-                          false, false, P + s.off_b[l], 0, in_rows))
+    const int in_rows = (l == 0 ? T : e.Lr[l - 1] / 2) * Bp;
+    if (l > 0) launch_las_pyr_pack(fp(e.out[l - 1]), fp(e.X[l]), e.Lr[l - 1] / 2, Bp, st);
+    if (int rc = gemm_dense(h, Xin, P + s.off_wx[l], fp(e.xp[l]), L * Bp, 2 * LAS_G4E, s.Ip[l], s.Ip[l], 2 * LAS_G4E,
+                            2 * LAS_G4E, false, false, P + s.off_b[l], 0, in_rows))
       return rc;
     for (int t = 0; t < L; ++t)
-      launch_las_enc_fwd_step(fp(xp[l]), P + s.off_whf[l], P + s.off_whb[l], fp(act[l]), fp(c[l]), fp(out[l]), t, L, B, Bp, st);
+      launch_las_enc_fwd_step(fp(e.xp[l]), P + s.off_whf[l], P + s.off_whb[l], fp(e.act[l]), fp(e.c[l]), fp(e.out[l]), t, L, B,
+                              Bp, st);
   }
+  return NASR_OK;
+}
+
+// phases of a timed beam search (nasr_las_beam_get_times)
+enum { LB_ENC = 0, LB_GEMM, LB_CELL, LB_ATTN, LB_SEL, LB_TREE, LB_WAIT, LB_COUNT };
+
+// One decoder step over `rows` decoder rows (the training pass's utterances, the search's beams).
+struct LasStep {
+  const float* S;         // the step's input rows [a | h] [rows][LAS_SW]
+  const int32_t* ids;     // the ids fed to the step
+  const float* cprev;     // the cell state before it
+  float *gp, *act, *c;    // the gate product (scratch), the gate activations and the cell state after it
+  float* Snext;           // [a | h] of the next step
+  float *HC, *Q, *logits;
+  // attention: the keys and the memory [L4*Bp][LAS_HD], W rows per utterance, rows >= nrows padding, alpha [rows][L4] or
+  // nullptr, the search's done word or nullptr
+  const float *keys, *mem;
+  int L4, Bp, W, nrows;
+  float* alpha;
+  const int32_t* done;
+};
+
+// Enqueues the step: gate GEMM on [a | h] W_ah, the cell, the query GEMM, attention, the attention-layer and projection
+// GEMMs.  mark (may be empty): called with the phase just enqueued (LB_GEMM, LB_CELL, LB_GEMM, LB_ATTN, LB_GEMM).
+int las_decoder_step(nasr_ctx* h, int rows, const LasStep& k, const std::function<void(int)>& mark) {
+  const LasState& s = *h->las;
+  const float* P = h->P;
+  const int Cp = h->Cp;
+  hipStream_t st = h->st;
+  if (int rc = gemm_dense(h, k.S, P + s.off_wah, k.gp, rows, LAS_G4D, LAS_SW, LAS_SW, LAS_G4D, LAS_G4D, false, false)) return rc;
+  if (mark) mark(LB_GEMM);
+  launch_las_dec_cell(k.gp, P + s.off_e, P + s.off_bd, k.ids, k.cprev, k.act, k.c, k.Snext, k.HC, rows, st);
+  if (mark) mark(LB_CELL);
+  if (int rc = gemm_dense(h, k.Snext + LAS_HE, P + s.off_wq, k.Q, rows, LAS_HD, LAS_HD, LAS_SW, LAS_HD, LAS_HD, false, false))
+    return rc;
+  if (mark) mark(LB_GEMM);
+  launch_las_attend(k.keys, k.mem, k.Q, P + s.off_v, k.alpha, k.HC, k.L4, k.Bp, k.W, k.nrows, rows, k.done, st);
+  if (mark) mark(LB_ATTN);
+  if (int rc = gemm_dense(h, k.HC, P + s.off_watt, k.Snext, rows, LAS_HE, 2 * LAS_HD, 2 * LAS_HD, LAS_HE, LAS_SW, false, false))
+    return rc;
+  if (int rc = gemm_dense(h, k.Snext, P + s.off_wp, k.logits, rows, Cp, LAS_HE, LAS_SW, Cp, Cp, false, false, P + s.off_bp))
+    return rc;
+  if (mark) mark(LB_GEMM);
   return NASR_OK;
 }
 
@@ -257,14 +283,14 @@ int las_forward(nasr_ctx* h, bool sample) {
   HIPCHK(h, hipMemsetAsync(h->Gbase, 0, GRAD_HEAD * 4, st));   // the step's fault word (nothing here raises it)
   {
     PhaseScope ps(h, PH_RECF);
-    if (int rc = las_encode(h, h->X0.as<float>(), h->T, B, Bp, s.Lr, s.X, s.xp, s.act, s.c, s.out)) return rc;
+    if (int rc = las_encode(h, h->X0.as<float>(), h->T, B, s.enc)) return rc;
   }
   PhaseScope ps(h, PH_PROJCTC);
-  const int L4 = s.Lr[LasState::NL - 1];
-  const float* mem = fp(s.out[LasState::NL - 1]);
-  if (int rc = las_gemm(h, mem, P + s.off_wmem, fp(s.keys), L4 * Bp, LAS_HD, LAS_HD, LAS_HD, LAS_HD, LAS_HD, false, false))
+  const int L4 = s.enc.Lr[LasEnc::NL - 1];
+  const float* mem = fp(s.enc.out[LasEnc::NL - 1]);
+  if (int rc = gemm_dense(h, mem, P + s.off_wmem, fp(s.keys), L4 * Bp, LAS_HD, LAS_HD, LAS_HD, LAS_HD, LAS_HD, false, false))
     return rc;
-  launch_las_dec_init(mem, fp(s.c[LasState::NL - 1]), h->labels_p, h->Lmax, L4, B, Bp, fp(s.S), fp(s.cinit), s.ids.as<int32_t>(),
+  launch_las_dec_init(mem, fp(s.enc.c[LasEnc::NL - 1]), h->labels_p, h->Lmax, L4, B, Bp, fp(s.S), fp(s.cinit), s.ids.as<int32_t>(),
                       st);
   LasSample smp{};
   if (sample && s.p > 0.f) {
@@ -277,18 +303,17 @@ int las_forward(nasr_ctx* h, bool sample) {
   HIPCHK(h, hipMemsetAsync(s.sampled.p, 0, (size_t)Bp * 4, st));
   for (int t = 0; t < U; ++t) {
     float* St = fp(s.S, (size_t)t * Bp * LAS_SW);
-    float* Sn = St + (size_t)Bp * LAS_SW;
-    float* HCt = fp(s.HC, (size_t)t * Bp * 2 * LAS_HD);
-    float* Qt = fp(s.Q, (size_t)t * Bp * LAS_HD);
     float* lg = fp(s.logits, (size_t)t * Bp * Cp);
-    if (int rc = las_gemm(h, St, P + s.off_wah, fp(s.gp), Bp, LAS_G4D, LAS_SW, LAS_SW, LAS_G4D, LAS_G4D, false, false)) return rc;
-    launch_las_dec_cell(fp(s.gp), P + s.off_e, P + s.off_bd, s.ids.as<int32_t>() + (size_t)t * Bp,
-                        t == 0 ? fp(s.cinit) : fp(s.dc, (size_t)(t - 1) * Bp * LAS_HD), fp(s.dact, (size_t)t * Bp * LAS_G4D),
-                        fp(s.dc, (size_t)t * Bp * LAS_HD), Sn, HCt, Bp, st);
-    if (int rc = las_gemm(h, Sn + LAS_HE, P + s.off_wq, Qt, Bp, LAS_HD, LAS_HD, LAS_SW, LAS_HD, LAS_HD, false, false)) return rc;
-    launch_las_attend(fp(s.keys), mem, Qt, P + s.off_v, fp(s.alpha, (size_t)t * Bp * L4), HCt, L4, Bp, st);
-    if (int rc = las_gemm(h, HCt, P + s.off_watt, Sn, Bp, LAS_HE, 2 * LAS_HD, 2 * LAS_HD, LAS_HE, LAS_SW, false, false)) return rc;
-    if (int rc = las_gemm(h, Sn, P + s.off_wp, lg, Bp, Cp, LAS_HE, LAS_SW, Cp, Cp, false, false, P + s.off_bp)) return rc;
+    LasStep k{};
+    k.S = St; k.ids = s.ids.as<int32_t>() + (size_t)t * Bp;
+    k.cprev = t == 0 ? fp(s.cinit) : fp(s.dc, (size_t)(t - 1) * Bp * LAS_HD);
+    k.gp = fp(s.gp); k.act = fp(s.dact, (size_t)t * Bp * LAS_G4D); k.c = fp(s.dc, (size_t)t * Bp * LAS_HD);
+    k.Snext = St + (size_t)Bp * LAS_SW;
+    k.HC = fp(s.HC, (size_t)t * Bp * 2 * LAS_HD); k.Q = fp(s.Q, (size_t)t * Bp * LAS_HD); k.logits = lg;
+    k.keys = fp(s.keys); k.mem = mem; k.L4 = L4; k.Bp = Bp;
+    k.W = 1; k.nrows = Bp;   // every row, the padded ones too, runs the attention body
+    k.alpha = fp(s.alpha, (size_t)t * Bp * L4);
+    if (int rc = las_decoder_step(h, Bp, k, nullptr)) return rc;
     if (t + 1 < U)
       launch_las_sample(lg, Cp, C, h->labels_p, h->Lmax, t, B, Bp, smp, s.ids.as<int32_t>() + (size_t)(t + 1) * Bp,
                         s.sampled.as<int32_t>() + (size_t)(t + 1) * Bp, st);
@@ -304,12 +329,12 @@ int las_forward(nasr_ctx* h, bool sample) {
 int las_backward(nasr_ctx* h) {
   LasState& s = *h->las;
   const int B = h->B, Bp = h->Bp, U = s.U, C = h->C, Cp = h->Cp;
-  const int L4 = s.Lr[LasState::NL - 1];
+  const int L4 = s.enc.Lr[LasEnc::NL - 1];
   const int UB = U * Bp;
   const float* P = h->P;
   float* G = h->G;
   hipStream_t st = h->st;
-  const float* mem = fp(s.out[LasState::NL - 1]);
+  const float* mem = fp(s.enc.out[LasEnc::NL - 1]);
   {
     PhaseScope ps(h, PH_PROJB);
     for (int t = U - 1; t >= 0; --t) {
@@ -318,18 +343,18 @@ int las_backward(nasr_ctx* h) {
       float* dAt = fp(s.dA, (size_t)t * Bp * LAS_HE);
       float* dQt = fp(s.dQ, (size_t)t * Bp * LAS_HD);
       // da_t = dlogits W_p^T (+ the next step's gate input)
-      if (int rc = las_gemm(h, dLt, P + s.off_wp, last ? dAt : fp(s.tmpA), Bp, LAS_HE, Cp, Cp, Cp, LAS_HE, false, true)) return rc;
+      if (int rc = gemm_dense(h, dLt, P + s.off_wp, last ? dAt : fp(s.tmpA), Bp, LAS_HE, Cp, Cp, Cp, LAS_HE, false, true)) return rc;
       if (!last) launch_las_add(fp(s.tmpA), LAS_HE, fp(s.dS), LAS_SW, dAt, LAS_HE, Bp, LAS_HE, st);
-      if (int rc = las_gemm(h, dAt, P + s.off_watt, fp(s.dHC), Bp, 2 * LAS_HD, LAS_HE, LAS_HE, LAS_HE, 2 * LAS_HD, false, true))
+      if (int rc = gemm_dense(h, dAt, P + s.off_watt, fp(s.dHC), Bp, 2 * LAS_HD, LAS_HE, LAS_HE, LAS_HE, 2 * LAS_HD, false, true))
         return rc;
       launch_las_attend_bwd(fp(s.keys), mem, fp(s.Q, (size_t)t * Bp * LAS_HD), P + s.off_v, fp(s.alpha, (size_t)t * Bp * L4),
                             fp(s.dHC), dQt, fp(s.dkeys), fp(s.dmem), fp(s.dvpart, (size_t)t * Bp * LAS_HD), L4, Bp, last, st);
-      if (int rc = las_gemm(h, dQt, P + s.off_wq, fp(s.dhq), Bp, LAS_HD, LAS_HD, LAS_HD, LAS_HD, LAS_HD, false, true)) return rc;
+      if (int rc = gemm_dense(h, dQt, P + s.off_wq, fp(s.dhq), Bp, LAS_HD, LAS_HD, LAS_HD, LAS_HD, LAS_HD, false, true)) return rc;
       float* dGt = fp(s.dGd, (size_t)t * Bp * LAS_G4D);
       launch_las_dec_cell_bwd(fp(s.dact, (size_t)t * Bp * LAS_G4D), fp(s.dc, (size_t)t * Bp * LAS_HD),
                               t == 0 ? fp(s.cinit) : fp(s.dc, (size_t)(t - 1) * Bp * LAS_HD), fp(s.dHC), fp(s.dhq), fp(s.dS),
                               fp(s.dcd), dGt, Bp, last, st);
-      if (int rc = las_gemm(h, dGt, P + s.off_wah, fp(s.dS), Bp, LAS_SW, LAS_G4D, LAS_G4D, LAS_G4D, LAS_SW, false, true)) return rc;
+      if (int rc = gemm_dense(h, dGt, P + s.off_wah, fp(s.dS), Bp, LAS_SW, LAS_G4D, LAS_G4D, LAS_G4D, LAS_SW, false, true)) return rc;
     }
     launch_las_dec_init_bwd(fp(s.dS), fp(s.dcd), fp(s.dhc), fp(s.dcc), B, Bp, st);
     HIPCHK(h, hipGetLastError());
@@ -337,60 +362,60 @@ int las_backward(nasr_ctx* h) {
   {
     PhaseScope ps(h, PH_WGRAD);
     const float* Snext = fp(s.S, (size_t)Bp * LAS_SW);   // rows of steps 1..U: [a_t | h_t]
-    if (int rc = las_gemm(h, Snext, fp(s.dL), G + s.off_wp, LAS_HE, Cp, UB, LAS_SW, Cp, Cp, true, false)) return rc;
+    if (int rc = gemm_dense(h, Snext, fp(s.dL), G + s.off_wp, LAS_HE, Cp, UB, LAS_SW, Cp, Cp, true, false)) return rc;
     launch_colsum(fp(s.dL), UB, Cp, Cp, G + s.off_bp, fp(s.csws), st);
-    if (int rc = las_gemm(h, fp(s.HC), fp(s.dA), G + s.off_watt, 2 * LAS_HD, LAS_HE, UB, 2 * LAS_HD, LAS_HE, LAS_HE, true, false))
+    if (int rc = gemm_dense(h, fp(s.HC), fp(s.dA), G + s.off_watt, 2 * LAS_HD, LAS_HE, UB, 2 * LAS_HD, LAS_HE, LAS_HE, true, false))
       return rc;
-    if (int rc = las_gemm(h, Snext + LAS_HE, fp(s.dQ), G + s.off_wq, LAS_HD, LAS_HD, UB, LAS_SW, LAS_HD, LAS_HD, true, false))
+    if (int rc = gemm_dense(h, Snext + LAS_HE, fp(s.dQ), G + s.off_wq, LAS_HD, LAS_HD, UB, LAS_SW, LAS_HD, LAS_HD, true, false))
       return rc;
     launch_colsum(fp(s.dvpart), UB, LAS_HD, LAS_HD, G + s.off_v, fp(s.csws), st);
-    if (int rc = las_gemm(h, fp(s.S), fp(s.dGd), G + s.off_wah, LAS_SW, LAS_G4D, UB, LAS_SW, LAS_G4D, LAS_G4D, true, false))
+    if (int rc = gemm_dense(h, fp(s.S), fp(s.dGd), G + s.off_wah, LAS_SW, LAS_G4D, UB, LAS_SW, LAS_G4D, LAS_G4D, true, false))
       return rc;
     launch_colsum(fp(s.dGd), UB, LAS_G4D, LAS_G4D, G + s.off_bd, fp(s.csws), st);
     launch_las_embed_grad(fp(s.dGd), s.ids.as<int32_t>(), U, B, Bp, C, G + s.off_e, st);
-    if (int rc = las_gemm(h, mem, fp(s.dkeys), G + s.off_wmem, LAS_HD, LAS_HD, L4 * Bp, LAS_HD, LAS_HD, LAS_HD, true, false))
+    if (int rc = gemm_dense(h, mem, fp(s.dkeys), G + s.off_wmem, LAS_HD, LAS_HD, L4 * Bp, LAS_HD, LAS_HD, LAS_HD, true, false))
       return rc;
     // the memory's gradient: the context's share plus the keys' share, into the top layer's output gradient
-    if (int rc = las_gemm(h, fp(s.dkeys), P + s.off_wmem, fp(s.tmpm), L4 * Bp, LAS_HD, LAS_HD, LAS_HD, LAS_HD, LAS_HD, false, true))
+    if (int rc = gemm_dense(h, fp(s.dkeys), P + s.off_wmem, fp(s.tmpm), L4 * Bp, LAS_HD, LAS_HD, LAS_HD, LAS_HD, LAS_HD, false, true))
       return rc;
     launch_las_add(fp(s.dmem), LAS_HD, fp(s.tmpm), LAS_HD, fp(s.dout), LAS_HD, L4 * Bp, LAS_HD, st);
     HIPCHK(h, hipGetLastError());
   }
-  for (int l = LasState::NL - 1; l >= 0; --l) {
-    const int L = s.Lr[l];
+  for (int l = LasEnc::NL - 1; l >= 0; --l) {
+    const int L = s.enc.Lr[l];
     const int R = L * Bp;
     {
       PhaseScope ps(h, PH_RECB);
-      if (l < LasState::NL - 1) {
+      if (l < LasEnc::NL - 1) {
         HIPCHK(h, hipMemsetAsync(s.dhc.p, 0, (size_t)2 * Bp * LAS_HE * 4, st));
         HIPCHK(h, hipMemsetAsync(s.dcc.p, 0, (size_t)2 * Bp * LAS_HE * 4, st));
       }
       launch_las_transpose_wh(P + s.off_whf[l], fp(s.whT), st);
       launch_las_transpose_wh(P + s.off_whb[l], fp(s.whT, (size_t)LAS_G4E * LAS_HE), st);
       for (int t = L - 1; t >= 0; --t)
-        launch_las_enc_bwd_step(fp(s.dout), fp(s.whT), fp(s.whT, (size_t)LAS_G4E * LAS_HE), fp(s.act[l]), fp(s.c[l]), fp(s.dGe), fp(s.dhc),
+        launch_las_enc_bwd_step(fp(s.dout), fp(s.whT), fp(s.whT, (size_t)LAS_G4E * LAS_HE), fp(s.enc.act[l]), fp(s.enc.c[l]), fp(s.dGe), fp(s.dhc),
                                 fp(s.dcc), t, L, B, Bp, st);
     }
     PhaseScope ps(h, PH_WGRAD);
-    const float* Xin = l == 0 ? h->X0.as<float>() : fp(s.X[l]);
-    const int in_rows = (l == 0 ? h->T : s.Lr[l - 1] / 2) * Bp;
-    if (int rc = las_gemm(h, Xin, fp(s.dGe), G + s.off_wx[l], s.Ip[l], 2 * LAS_G4E, R, s.Ip[l], 2 * LAS_G4E, 2 * LAS_G4E, true,
+    const float* Xin = l == 0 ? h->X0.as<float>() : fp(s.enc.X[l]);
+    const int in_rows = (l == 0 ? h->T : s.enc.Lr[l - 1] / 2) * Bp;
+    if (int rc = gemm_dense(h, Xin, fp(s.dGe), G + s.off_wx[l], s.Ip[l], 2 * LAS_G4E, R, s.Ip[l], 2 * LAS_G4E, 2 * LAS_G4E, true,
                           false, nullptr, 0, in_rows))
       return rc;
     launch_colsum(fp(s.dGe), R, 2 * LAS_G4E, 2 * LAS_G4E, G + s.off_b[l], fp(s.csws), st);
     // recurrent weights: h of the frame before (fw) / after (bw), zero outside the layer's frames
-    const float* o = fp(s.out[l]);
-    if (int rc = las_gemm(h, o, fp(s.dGe), G + s.off_whf[l], LAS_HE, LAS_G4E, R, 2 * LAS_HE, 2 * LAS_G4E, LAS_G4E, true, false,
+    const float* o = fp(s.enc.out[l]);
+    if (int rc = gemm_dense(h, o, fp(s.dGe), G + s.off_whf[l], LAS_HE, LAS_G4E, R, 2 * LAS_HE, 2 * LAS_G4E, LAS_G4E, true, false,
                           nullptr, -Bp, R))
       return rc;
-    if (int rc = las_gemm(h, o + LAS_HE, fp(s.dGe) + LAS_G4E, G + s.off_whb[l], LAS_HE, LAS_G4E, R, 2 * LAS_HE, 2 * LAS_G4E,
+    if (int rc = gemm_dense(h, o + LAS_HE, fp(s.dGe) + LAS_G4E, G + s.off_whb[l], LAS_HE, LAS_G4E, R, 2 * LAS_HE, 2 * LAS_G4E,
                           LAS_G4E, true, false, nullptr, Bp, R))
       return rc;
     if (l > 0) {
-      if (int rc = las_gemm(h, fp(s.dGe), P + s.off_wx[l], fp(s.dX), R, 4 * LAS_HE, 2 * LAS_G4E, 2 * LAS_G4E, 2 * LAS_G4E,
+      if (int rc = gemm_dense(h, fp(s.dGe), P + s.off_wx[l], fp(s.dX), R, 4 * LAS_HE, 2 * LAS_G4E, 2 * LAS_G4E, 2 * LAS_G4E,
                             4 * LAS_HE, false, true))
         return rc;
-      launch_las_pyr_unpack(fp(s.dX), fp(s.dout), s.Lr[l - 1] / 2, Bp, st);
+      launch_las_pyr_unpack(fp(s.dX), fp(s.dout), s.enc.Lr[l - 1] / 2, Bp, st);
     }
     HIPCHK(h, hipGetLastError());
   }
@@ -401,26 +426,14 @@ int las_backward(nasr_ctx* h) {
 
 
 // ------------------------------------------------------------------ beam search
-enum { LB_ENC = 0, LB_GEMM, LB_CELL, LB_ATTN, LB_SEL, LB_TREE, LB_WAIT, LB_COUNT };
-
 // host_feats: the search packs features of its own (m.feats, m.X0); otherwise it reads the resident batch's X0
 int las_beam_ensure(nasr_ctx* h, LasBeam& m, int B, int T, int W, int max_steps, bool host_feats) {
   const int Bp = rup(B, 16), nrows = B * W, R = rup(nrows, 16), C = h->C;
-  int Lr[LasBeam::NL];
-  las_lengths(T, Lr);
-  const size_t L4B = (size_t)Lr[LasBeam::NL - 1] * Bp, MR = (size_t)max_steps * nrows;
-  bool grew = false, ok = true;
+  bool grew = false, ok = m.enc.ensure(T, Bp, &grew);
+  const size_t L4B = (size_t)m.enc.Lr[LasEnc::NL - 1] * Bp, MR = (size_t)max_steps * nrows;
   if (host_feats) {
     ok &= m.feats.ensure((size_t)B * T * h->F * 4, &grew);
     ok &= m.X0.ensure((size_t)T * Bp * h->Fp * 4, &grew);
-  }
-  for (int l = 0; l < LasBeam::NL; ++l) {
-    const size_t Rl = (size_t)Lr[l] * Bp;
-    if (l > 0) ok &= m.X[l].ensure(Rl * 4 * LAS_HE * 4, &grew);
-    ok &= m.xp[l].ensure(Rl * 2 * LAS_G4E * 4, &grew);
-    ok &= m.act[l].ensure(Rl * 2 * LAS_G4E * 4, &grew);
-    ok &= m.c[l].ensure(Rl * 2 * LAS_H * 4, &grew);
-    ok &= m.out[l].ensure(Rl * 2 * LAS_HE * 4, &grew);
   }
   ok &= m.keys.ensure(L4B * LAS_HD * 4, &grew);
   ok &= m.S.ensure((size_t)R * LAS_SW * 4, &grew) && m.Sx.ensure((size_t)R * LAS_SW * 4, &grew);
@@ -438,7 +451,6 @@ int las_beam_ensure(nasr_ctx* h, LasBeam& m, int B, int T, int W, int max_steps,
   ok &= m.gathered.ensure(MR * 4, &grew);
   if (!ok) return h->fail(NASR_ERR_HIP, "hipMalloc failed while sizing beam-search buffers");
   m.B = B; m.Bp = Bp; m.T = T; m.W = W; m.R = R; m.max_steps = max_steps;
-  for (int l = 0; l < LasBeam::NL; ++l) m.Lr[l] = Lr[l];
   return NASR_OK;
 }
 
@@ -454,13 +466,13 @@ int las_beam_search(nasr_ctx* h, const float* feats, int B, int T, int W, int ma
   m.have = false;
   if (int rc = las_beam_ensure(h, m, B, T, W, max_steps, feats != nullptr)) return rc;
   const int Bp = m.Bp, R = m.R, nrows = B * W, C = h->C, Cp = h->Cp;
-  const int L4 = m.Lr[LasBeam::NL - 1];
+  const int L4 = m.enc.Lr[LasEnc::NL - 1];
   const float* P = h->P;
   hipStream_t st = h->st;
   const bool timed = h->profiling;
   m.marks.clear();
   size_t nev = 0;
-  auto mark = [&](int ph) {
+  const std::function<void(int)> mark = [&](int ph) {
     if (!timed) return;
     if (nev == m.ev.size()) (void)hipEventCreate(m.ev.emplace_back().out());
     (void)hipEventRecord(m.ev[nev], st);
@@ -478,42 +490,34 @@ int las_beam_search(nasr_ctx* h, const float* feats, int B, int T, int W, int ma
     launch_pack_feats(m.feats.as<float>(), m.X0.as<float>(), B, Bp, T, h->F, h->Fp, st);
   }
   const float* X0 = feats ? m.X0.as<float>() : h->X0.as<float>();
-  if (int rc = las_encode(h, X0, T, B, Bp, m.Lr, m.X, m.xp, m.act, m.c, m.out)) return rc;
+  if (int rc = las_encode(h, X0, T, B, m.enc)) return rc;
   // the n-gram table, if one is set: every row's context starts as start_id in every digit
   const float* table = s.lm_order ? fp(s.lm) : nullptr;
   const int K = s.lm_order ? s.lm_K : 1;
   int ctx0 = 0;
   for (int d = 1; d < s.lm_order; ++d) ctx0 = ctx0 * C + start_id;
-  const float* mem = fp(m.out[LasBeam::NL - 1]);
-  if (int rc = las_gemm(h, mem, P + s.off_wmem, fp(m.keys), L4 * Bp, LAS_HD, LAS_HD, LAS_HD, LAS_HD, LAS_HD, false, false))
+  const float* mem = fp(m.enc.out[LasEnc::NL - 1]);
+  if (int rc = gemm_dense(h, mem, P + s.off_wmem, fp(m.keys), L4 * Bp, LAS_HD, LAS_HD, LAS_HD, LAS_HD, LAS_HD, false, false))
     return rc;
-  launch_las_beam_init(mem, fp(m.c[LasBeam::NL - 1]), L4, Bp, W, nrows, R, start_id, fp(m.S), fp(m.cs), m.ids.as<int32_t>(),
+  launch_las_beam_init(mem, fp(m.enc.c[LasEnc::NL - 1]), L4, Bp, W, nrows, R, start_id, fp(m.S), fp(m.cs), m.ids.as<int32_t>(),
                        fp(m.logp[0]), m.len[0].as<int32_t>(), m.fin[0].as<int32_t>(), m.ctx[0].as<int32_t>(), ctx0, st);
   HIPCHK(h, hipGetLastError());
   mark(LB_ENC);
   const int32_t* done = m.flags.as<int32_t>();
   int32_t hf[2] = {0, 0};
   constexpr int CHUNK = 8;
+  // every step reads the beams' S / cs and writes Sx / cx, which the update gathers by parent back into S / cs
+  LasStep step{};
+  step.S = fp(m.S); step.ids = m.ids.as<int32_t>(); step.cprev = fp(m.cs);
+  step.gp = fp(m.gp); step.act = fp(m.dact); step.c = fp(m.cx); step.Snext = fp(m.Sx);
+  step.HC = fp(m.HC); step.Q = fp(m.Q); step.logits = fp(m.logits);
+  step.keys = fp(m.keys); step.mem = mem; step.L4 = L4; step.Bp = Bp; step.W = W; step.nrows = nrows;
+  step.done = done;
   for (int t = 0; t < max_steps;) {
     for (const int end = std::min(max_steps, t + CHUNK); t < end; ++t) {
       const int i = t & 1, o = i ^ 1;
       const size_t tr = (size_t)t * nrows;
-      if (int rc = las_gemm(h, fp(m.S), P + s.off_wah, fp(m.gp), R, LAS_G4D, LAS_SW, LAS_SW, LAS_G4D, LAS_G4D, false, false))
-        return rc;
-      mark(LB_GEMM);
-      launch_las_dec_cell(fp(m.gp), P + s.off_e, P + s.off_bd, m.ids.as<int32_t>(), fp(m.cs), fp(m.dact), fp(m.cx), fp(m.Sx),
-                          fp(m.HC), R, st);
-      mark(LB_CELL);
-      if (int rc = las_gemm(h, fp(m.Sx) + LAS_HE, P + s.off_wq, fp(m.Q), R, LAS_HD, LAS_HD, LAS_SW, LAS_HD, LAS_HD, false, false))
-        return rc;
-      mark(LB_GEMM);
-      launch_las_beam_attend(fp(m.keys), mem, fp(m.Q), P + s.off_v, fp(m.HC), L4, Bp, W, nrows, R, done, st);
-      mark(LB_ATTN);
-      if (int rc = las_gemm(h, fp(m.HC), P + s.off_watt, fp(m.Sx), R, LAS_HE, 2 * LAS_HD, 2 * LAS_HD, LAS_HE, LAS_SW, false, false))
-        return rc;
-      if (int rc = las_gemm(h, fp(m.Sx), P + s.off_wp, fp(m.logits), R, Cp, LAS_HE, LAS_SW, Cp, Cp, false, false, P + s.off_bp))
-        return rc;
-      mark(LB_GEMM);
+      if (int rc = las_decoder_step(h, R, step, mark)) return rc;
       launch_las_beam_score(fp(m.logits), Cp, C, fp(m.logp[i]), m.len[i].as<int32_t>(), m.fin[i].as<int32_t>(), fp(m.pen), end_id,
                             nrows, table, m.ctx[i].as<int32_t>(), s.lm_weight, fp(m.scores), fp(m.totals), done, st);
       launch_las_beam_select(fp(m.scores), B, W, C, m.sel_idx.as<int32_t>(), fp(m.sel_score), done, st);
@@ -557,8 +561,6 @@ int las_beam_search(nasr_ctx* h, const float* feats, int B, int T, int W, int ma
 void nasr_impl::LasStateDelete::operator()(LasState* s) const { delete s; }
 
 namespace {
-LasState* las_of(nasr_handle h) { return h ? h->las.get() : nullptr; }
-
 // [U][Bp][cols] (element size esz) read back and reordered to [B][U][cols]
 int las_read_bu(nasr_ctx* h, const DevBuf& src, int cols, int ld, size_t esz, void* dst) {
   LasState& s = *h->las;
@@ -586,7 +588,7 @@ int nasr_create_las(const nasr_las_cfg* cfg, int device_id, void* stream, nasr_h
     g_create_error = "nasr_create_las: feature_size must be >= 1 and num_classes >= 2";
     return NASR_ERR_ARG;
   }
-  if (cfg->num_hidden != LAS_H || cfg->num_layers != LasState::NL) {
+  if (cfg->num_hidden != LAS_H || cfg->num_layers != LasEnc::NL) {
     g_create_error = "nasr_create_las: only num_hidden = 250 and num_layers = 4 (the reference's) are implemented";
     return NASR_ERR_ARG;
   }
@@ -617,16 +619,16 @@ int nasr_create_las(const nasr_las_cfg* cfg, int device_id, void* stream, nasr_h
 }
 
 int nasr_las_set_sampling(nasr_handle h, float p, uint32_t seed, uint32_t counter, int tower) {
-  LasState* s = las_of(h);
-  if (!s) return h ? h->fail(NASR_ERR_STATE, "nasr_las_set_sampling: not a LAS handle") : NASR_ERR_ARG;
+  LAS_CALL(h);
+  LasState* s = h->las.get();
   if (!(p >= 0.f && p <= 1.f) || tower < 0) return h->fail(NASR_ERR_ARG, "nasr_las_set_sampling: p must be in [0,1], tower >= 0");
   s->p = p; s->seed = seed; s->counter = counter; s->tower = tower;
   return NASR_OK;
 }
 
 int nasr_las_get_sampling(nasr_handle h, float* p, uint32_t* seed, uint32_t* counter, int* tower) {
-  LasState* s = las_of(h);
-  if (!s) return h ? h->fail(NASR_ERR_STATE, "nasr_las_get_sampling: not a LAS handle") : NASR_ERR_ARG;
+  LAS_CALL(h);
+  LasState* s = h->las.get();
   if (p) *p = s->p;
   if (seed) *seed = s->seed;
   if (counter) *counter = s->counter;
@@ -645,8 +647,7 @@ int las_forward_out(nasr_ctx* h, int sample, float* logits_out) {
 
 int nasr_las_forward(nasr_handle h, const float* feats, const int32_t* seq_len, const int32_t* labels, const int32_t* label_len,
                      int B, int T, int U, int sample, float* logits_out) {
-  LasState* s = las_of(h);
-  if (!s) return h ? h->fail(NASR_ERR_STATE, "nasr_las_forward: not a LAS handle") : NASR_ERR_ARG;
+  LAS_CALL(h);
   if (!labels || !label_len) return h->fail(NASR_ERR_ARG, "nasr_las_forward needs labels");
   HIPCHK(h, hipSetDevice(h->device));
   if (int rc = upload(h, stacked_batch(feats, seq_len, labels, label_len, B, T, U))) return rc;
@@ -654,32 +655,31 @@ int nasr_las_forward(nasr_handle h, const float* feats, const int32_t* seq_len, 
 }
 
 int nasr_las_forward_resident(nasr_handle h, int sample, float* logits_out) {
-  LasState* s = las_of(h);
-  if (!s) return h ? h->fail(NASR_ERR_STATE, "nasr_las_forward_resident: not a LAS handle") : NASR_ERR_ARG;
+  LAS_CALL(h);
   if (!h->resident) return h->fail(NASR_ERR_STATE, "nasr_las_forward_resident: no resident batch");
   HIPCHK(h, hipSetDevice(h->device));
   return las_forward_out(h, sample, logits_out);
 }
 
 int nasr_las_get_logits(nasr_handle h, float* logits_out) {
-  LasState* s = las_of(h);
-  if (!s) return h ? h->fail(NASR_ERR_STATE, "nasr_las_get_logits: not a LAS handle") : NASR_ERR_ARG;
+  LAS_CALL(h);
+  LasState* s = h->las.get();
   if (!logits_out) return h->fail(NASR_ERR_ARG, "nasr_las_get_logits: null output");
   if (!s->have_pass) return h->fail(NASR_ERR_STATE, "nasr_las_get_logits: no decoder pass has run");
   return las_read_bu(h, s->logits, h->C, h->Cp, 4, logits_out);
 }
 
 int nasr_las_get_fed_ids(nasr_handle h, int32_t* ids_out) {
-  LasState* s = las_of(h);
-  if (!s) return h ? h->fail(NASR_ERR_STATE, "nasr_las_get_fed_ids: not a LAS handle") : NASR_ERR_ARG;
+  LAS_CALL(h);
+  LasState* s = h->las.get();
   if (!ids_out) return h->fail(NASR_ERR_ARG, "nasr_las_get_fed_ids: null output");
   if (!s->have_pass) return h->fail(NASR_ERR_STATE, "nasr_las_get_fed_ids: no decoder pass has run");
   return las_read_bu(h, s->ids, 1, 1, 4, ids_out);
 }
 
 int nasr_las_get_sampled(nasr_handle h, int32_t* sampled_out) {
-  LasState* s = las_of(h);
-  if (!s) return h ? h->fail(NASR_ERR_STATE, "nasr_las_get_sampled: not a LAS handle") : NASR_ERR_ARG;
+  LAS_CALL(h);
+  LasState* s = h->las.get();
   if (!sampled_out) return h->fail(NASR_ERR_ARG, "nasr_las_get_sampled: null output");
   if (!s->have_pass) return h->fail(NASR_ERR_STATE, "nasr_las_get_sampled: no decoder pass has run");
   return las_read_bu(h, s->sampled, 1, 1, 4, sampled_out);
@@ -708,7 +708,7 @@ int las_beam_call(nasr_ctx* h, const std::string& fn, const float* feats, const 
 
 int nasr_las_beam_search(nasr_handle h, const float* feats, const int32_t* seq_len, int B, int T, int beam_width, int max_steps,
                          int start_id, int end_id, float length_penalty, int32_t* steps_out) {
-  if (!las_of(h)) return h ? h->fail(NASR_ERR_STATE, "nasr_las_beam_search: not a LAS handle") : NASR_ERR_ARG;
+  LAS_CALL(h);
   if (!feats || !seq_len) return h->fail(NASR_ERR_ARG, "nasr_las_beam_search: null input buffer");
   return las_beam_call(h, "nasr_las_beam_search", feats, seq_len, B, T, beam_width, max_steps, start_id, end_id, length_penalty,
                        steps_out);
@@ -716,19 +716,18 @@ int nasr_las_beam_search(nasr_handle h, const float* feats, const int32_t* seq_l
 
 int nasr_las_beam_search_resident(nasr_handle h, int beam_width, int max_steps, int start_id, int end_id, float length_penalty,
                                   int32_t* steps_out) {
-  if (!las_of(h)) return h ? h->fail(NASR_ERR_STATE, "nasr_las_beam_search_resident: not a LAS handle") : NASR_ERR_ARG;
+  LAS_CALL(h);
   if (!h->resident) return h->fail(NASR_ERR_STATE, "nasr_las_beam_search_resident: no resident batch");
   return las_beam_call(h, "nasr_las_beam_search_resident", nullptr, h->h_seq.data(), h->B, h->T, beam_width, max_steps, start_id,
                        end_id, length_penalty, steps_out);
 }
 
 namespace {
+// the last search's buffers of a LAS handle (after LAS_CALL), or nullptr with *rc set
 LasBeam* beam_of(nasr_handle h, const char* fn, int* rc) {
-  LasState* s = las_of(h);
-  *rc = NASR_OK;
-  if (!s) *rc = h ? h->fail(NASR_ERR_STATE, std::string(fn) + ": not a LAS handle") : NASR_ERR_ARG;
-  else if (!s->beam || !s->beam->have) *rc = h->fail(NASR_ERR_STATE, std::string(fn) + ": no beam search has run");
-  return *rc ? nullptr : s->beam.get();
+  LasBeam* m = h->las->beam.get();
+  *rc = m && m->have ? NASR_OK : h->fail(NASR_ERR_STATE, std::string(fn) + ": no beam search has run");
+  return *rc ? nullptr : m;
 }
 // [Tdec][B*W] read back and reordered to [B][Tdec][W]
 int beam_read_tbw(nasr_ctx* h, const LasBeam& m, const DevBuf& src, void* dst) {
@@ -748,16 +747,18 @@ int beam_read(nasr_ctx* h, const DevBuf& src, size_t n, void* dst) {
 }  // namespace
 
 int nasr_las_beam_get_ids(nasr_handle h, int32_t* ids_out) {
+  LAS_CALL(h);
   int rc;
-  LasBeam* m = beam_of(h, "nasr_las_beam_get_ids", &rc);
+  LasBeam* m = beam_of(h, __func__, &rc);
   if (!m) return rc;
   if (!ids_out) return h->fail(NASR_ERR_ARG, "nasr_las_beam_get_ids: null output");
   return beam_read_tbw(h, *m, m->gathered, ids_out);
 }
 
 int nasr_las_beam_get_trace(nasr_handle h, float* scores_out, int32_t* word_out, int32_t* parent_out) {
+  LAS_CALL(h);
   int rc;
-  LasBeam* m = beam_of(h, "nasr_las_beam_get_trace", &rc);
+  LasBeam* m = beam_of(h, __func__, &rc);
   if (!m) return rc;
   if (scores_out && (rc = beam_read_tbw(h, *m, m->tr_score, scores_out))) return rc;
   if (word_out && (rc = beam_read_tbw(h, *m, m->tr_word, word_out))) return rc;
@@ -766,8 +767,9 @@ int nasr_las_beam_get_trace(nasr_handle h, float* scores_out, int32_t* word_out,
 }
 
 int nasr_las_beam_get_final(nasr_handle h, float* log_probs_out, int32_t* lengths_out, int32_t* finished_out) {
+  LAS_CALL(h);
   int rc;
-  LasBeam* m = beam_of(h, "nasr_las_beam_get_final", &rc);
+  LasBeam* m = beam_of(h, __func__, &rc);
   if (!m) return rc;
   const int f = m->Tdec & 1;
   const size_t n = (size_t)m->B * m->W;
@@ -778,8 +780,8 @@ int nasr_las_beam_get_final(nasr_handle h, float* log_probs_out, int32_t* length
 }
 
 int nasr_las_beam_set_lm(nasr_handle h, const float* logp, int order, float weight) {
-  LasState* s = las_of(h);
-  if (!s) return h ? h->fail(NASR_ERR_STATE, "nasr_las_beam_set_lm: not a LAS handle") : NASR_ERR_ARG;
+  LAS_CALL(h);
+  LasState* s = h->las.get();
   if (logp) {
     if (order < 1 || order > 4) return h->fail(NASR_ERR_ARG, "nasr_las_beam_set_lm: order must be in [1,4]");
     if (!std::isfinite(weight)) return h->fail(NASR_ERR_ARG, "nasr_las_beam_set_lm: weight must be finite");
@@ -807,16 +809,18 @@ int nasr_las_beam_set_lm(nasr_handle h, const float* logp, int order, float weig
 }
 
 int nasr_las_beam_get_lm_context(nasr_handle h, int32_t* ctx_out) {
+  LAS_CALL(h);
   int rc;
-  LasBeam* m = beam_of(h, "nasr_las_beam_get_lm_context", &rc);
+  LasBeam* m = beam_of(h, __func__, &rc);
   if (!m) return rc;
   if (!ctx_out) return h->fail(NASR_ERR_ARG, "nasr_las_beam_get_lm_context: null output");
   return beam_read(h, m->ctx[m->Tdec & 1], (size_t)m->B * m->W, ctx_out);
 }
 
 int nasr_las_beam_get_times(nasr_handle h, float* ms_out) {
+  LAS_CALL(h);
   int rc;
-  LasBeam* m = beam_of(h, "nasr_las_beam_get_times", &rc);
+  LasBeam* m = beam_of(h, __func__, &rc);
   if (!m) return rc;
   if (!ms_out) return h->fail(NASR_ERR_ARG, "nasr_las_beam_get_times: null output");
   if (!m->timed) return h->fail(NASR_ERR_STATE, "nasr_las_beam_get_times: the last search ran with profiling off");

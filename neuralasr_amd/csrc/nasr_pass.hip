@@ -78,6 +78,19 @@ int gemm_f32(nasr_ctx* h, GemmDesc g) {
   return NASR_OK;
 }
 
+int gemm_dense(nasr_ctx* h, const float* A, const float* B, float* C, int M, int N, int K, int lda, int ldb, int ldc, bool a_col,
+               bool b_col, const float* bias, int a_shift, int a_rows) {
+  GemmDesc g{};
+  g.A = A; g.B = B; g.C = C;
+  g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldc = ldc;
+  g.a_col = a_col; g.b_col = b_col;
+  g.a_shift = a_shift;
+  g.a_rows = a_rows >= 0 ? a_rows : (a_col ? K : M);
+  g.bias = bias;
+  g.split_k = bias ? 1 : gemm_pick_split(M, N, K);
+  return gemm_f32(h, g);
+}
+
 // operand scales of layer l's dG (rows = frames: sc_gr, optional; columns = gates: sc_gc): from the maxima the persistent
 // BPTT kernel took while it stored dG, or by a pass over dG
 void dg_scales(nasr_ctx* h, int l, int R, bool rows, hipStream_t st) {

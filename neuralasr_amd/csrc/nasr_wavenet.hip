@@ -37,17 +37,6 @@ struct WnState {
   int site_out(int j) const { return 3 + 3 * j; }
 };
 
-int wn_gemm(nasr_ctx* h, const float* A, const float* B, float* C, int M, int N, int K, int lda, int ldb, int ldc, bool a_col,
-            bool b_col) {
-  GemmDesc g{};
-  g.A = A; g.B = B; g.C = C;
-  g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldc = ldc;
-  g.a_col = a_col; g.b_col = b_col;
-  g.a_rows = a_col ? K : M;
-  g.split_k = gemm_pick_split(M, N, K);
-  return gemm_f32(h, g);
-}
-
 // Parameter names, TF order, and the map into the internal layout (nasr_tensor_info, nasr_get/set_params).
 int wn_layout(nasr_ctx* h) {
   WnState& w = *h->wn;
@@ -139,10 +128,6 @@ int wn_ensure_shape(nasr_ctx* h, int B, int T, int Lmax) {
   return NASR_OK;
 }
 
-namespace {
-inline float* fp(const DevBuf& b, size_t off = 0) { return b.as<float>() + off; }
-}  // namespace
-
 int wn_forward(nasr_ctx* h, bool training) {
   if (!h->resident) return h->fail(NASR_ERR_STATE, "no resident batch: call nasr_upload_batch first");
   WnState& w = *h->wn;
@@ -169,7 +154,7 @@ int wn_forward(nasr_ctx* h, bool training) {
   const float *mean, *var;
   PhaseScope ps(h, PH_XPROJ);
   // front/conv_in: z0 = tanh(BN(X0 W))
-  if (int rc = wn_gemm(h, h->X0.as<float>(), P + w.off_win, fp(w.Y0), R, D, h->Fp, h->Fp, D, D, false, false)) return rc;
+  if (int rc = gemm_dense(h, h->X0.as<float>(), P + w.off_win, fp(w.Y0), R, D, h->Fp, h->Fp, D, D, false, false)) return rc;
   stats(0, fp(w.Y0), D, &mean, &var);
   launch_wn_bn_tanh(fp(w.Y0), mean, var, P + w.off_gamma[0], P + w.off_beta[0], eps, fp(w.Z), nullptr, nullptr, nullptr,
                     false, rw, D, st);
@@ -181,12 +166,12 @@ int wn_forward(nasr_ctx* h, bool training) {
     float* yo = fp(w.Yo, j * a);
     // filter | gate: one GEMM of N = 2D over the K = KS*D (tap, channel) columns of the shifted rows
     launch_wn_im2col(z, fp(w.col), rw, D, KS, w.rate[j], st);
-    if (int rc = wn_gemm(h, fp(w.col), P + w.off_wfg[j], yfg, R, 2 * D, KS * D, KS * D, 2 * D, 2 * D, false, false)) return rc;
+    if (int rc = gemm_dense(h, fp(w.col), P + w.off_wfg[j], yfg, R, 2 * D, KS * D, KS * D, 2 * D, 2 * D, false, false)) return rc;
     const int sf = w.site_filter(j);
     stats(sf, yfg, 2 * D, &mean, &var);
     launch_wn_bn_gate(yfg, mean, var, P + w.off_gamma[sf], P + w.off_beta[sf], eps, fg, pm, rw, D, st);
     // conv_out, residual and skip
-    if (int rc = wn_gemm(h, pm, P + w.off_wo[j], yo, R, D, D, D, D, D, false, false)) return rc;
+    if (int rc = gemm_dense(h, pm, P + w.off_wo[j], yo, R, D, D, D, D, D, false, false)) return rc;
     const int so = w.site_out(j);
     stats(so, yo, D, &mean, &var);
     launch_wn_bn_tanh(yo, mean, var, P + w.off_gamma[so], P + w.off_beta[so], eps, fp(w.O, j * a), z, fp(w.Z, (j + 1) * a),
@@ -194,11 +179,11 @@ int wn_forward(nasr_ctx* h, bool training) {
   }
   if (w.nblk == 0) HIPCHK(h, hipMemsetAsync(w.skip.p, 0, a * 4, st));
   // logit/conv_1 and conv_2 (no BN, no bias)
-  if (int rc = wn_gemm(h, fp(w.skip), P + w.off_w1, fp(w.Y1), R, D, D, D, D, D, false, false)) return rc;
+  if (int rc = gemm_dense(h, fp(w.skip), P + w.off_w1, fp(w.Y1), R, D, D, D, D, D, false, false)) return rc;
   stats(w.S - 1, fp(w.Y1), D, &mean, &var);
   launch_wn_bn_tanh(fp(w.Y1), mean, var, P + w.off_gamma[w.S - 1], P + w.off_beta[w.S - 1], eps, fp(w.S2), nullptr, nullptr,
                     nullptr, false, rw, D, st);
-  if (int rc = wn_gemm(h, fp(w.S2), P + w.off_w2, h->logits.as<float>(), R, h->Cp, D, D, h->Cp, h->Cp, false, false)) return rc;
+  if (int rc = gemm_dense(h, fp(w.S2), P + w.off_w2, h->logits.as<float>(), R, h->Cp, D, D, h->Cp, h->Cp, false, false)) return rc;
   if (training) {
     w.have_stats = true;
     if (!w.hold) {
@@ -241,13 +226,13 @@ int wn_backward(nasr_ctx* h) {
   const float* dlog = h->logits.as<float>();
   float* dy = fp(w.dy);
   // conv_2: dW2 = S2^T dlogits, dS2 = dlogits W2^T
-  if (int rc = wn_gemm(h, fp(w.S2), dlog, G + w.off_w2, D, h->Cp, R, D, h->Cp, h->Cp, true, false)) return rc;
-  if (int rc = wn_gemm(h, dlog, P + w.off_w2, fp(w.dp), R, D, h->Cp, h->Cp, h->Cp, D, false, true)) return rc;
+  if (int rc = gemm_dense(h, fp(w.S2), dlog, G + w.off_w2, D, h->Cp, R, D, h->Cp, h->Cp, true, false)) return rc;
+  if (int rc = gemm_dense(h, dlog, P + w.off_w2, fp(w.dp), R, D, h->Cp, h->Cp, h->Cp, D, false, true)) return rc;
   // conv_1
   launch_wn_dtanh(dy, fp(w.dp), nullptr, fp(w.S2), rw, D, st);
   bn_bwd(w.S - 1, fp(w.Y1), dy, D);
-  if (int rc = wn_gemm(h, fp(w.skip), dy, G + w.off_w1, D, D, R, D, D, D, true, false)) return rc;
-  if (int rc = wn_gemm(h, dy, P + w.off_w1, fp(w.dskip), R, D, D, D, D, D, false, true)) return rc;
+  if (int rc = gemm_dense(h, fp(w.skip), dy, G + w.off_w1, D, D, R, D, D, D, true, false)) return rc;
+  if (int rc = gemm_dense(h, dy, P + w.off_w1, fp(w.dskip), R, D, D, D, D, D, false, true)) return rc;
   HIPCHK(h, hipMemsetAsync(w.dz.p, 0, a * 4, st));   // the last block's residual output feeds nothing
   for (int j = w.nblk - 1; j >= 0; --j) {
     const float* z = fp(w.Z, j * a);
@@ -256,21 +241,21 @@ int wn_backward(nasr_ctx* h) {
     // conv_out: its output went to the residual (dz) and to the skip sum (dskip)
     launch_wn_dtanh(dy, fp(w.dz), fp(w.dskip), fp(w.O, j * a), rw, D, st);
     bn_bwd(w.site_out(j), fp(w.Yo, j * a), dy, D);
-    if (int rc = wn_gemm(h, pm, dy, G + w.off_wo[j], D, D, R, D, D, D, true, false)) return rc;
-    if (int rc = wn_gemm(h, dy, P + w.off_wo[j], fp(w.dp), R, D, D, D, D, D, false, true)) return rc;
+    if (int rc = gemm_dense(h, pm, dy, G + w.off_wo[j], D, D, R, D, D, D, true, false)) return rc;
+    if (int rc = gemm_dense(h, dy, P + w.off_wo[j], fp(w.dp), R, D, D, D, D, D, false, true)) return rc;
     // the gate, then batch norm of filter and gate together (2D channels)
     launch_wn_dgate(dy, fp(w.dp), fp(w.FG, 2 * j * a), rw, D, st);
     bn_bwd(w.site_filter(j), yfg, dy, 2 * D);
     launch_wn_im2col(z, fp(w.col), rw, D, KS, w.rate[j], st);
-    if (int rc = wn_gemm(h, fp(w.col), dy, G + w.off_wfg[j], KS * D, 2 * D, R, KS * D, 2 * D, 2 * D, true, false)) return rc;
+    if (int rc = gemm_dense(h, fp(w.col), dy, G + w.off_wfg[j], KS * D, 2 * D, R, KS * D, 2 * D, 2 * D, true, false)) return rc;
     // data gradient: the shifted-tap products, then each tap's rows moved back (the taps reversed) onto the residual's
-    if (int rc = wn_gemm(h, dy, P + w.off_wfg[j], fp(w.dcol), R, KS * D, 2 * D, 2 * D, 2 * D, KS * D, false, true)) return rc;
+    if (int rc = gemm_dense(h, dy, P + w.off_wfg[j], fp(w.dcol), R, KS * D, 2 * D, 2 * D, 2 * D, KS * D, false, true)) return rc;
     launch_wn_col2im_add(fp(w.dcol), fp(w.dz), rw, D, KS, w.rate[j], st);
   }
   // front/conv_in
   launch_wn_dtanh(dy, fp(w.dz), w.nblk == 0 ? fp(w.dskip) : nullptr, fp(w.Z), rw, D, st);
   bn_bwd(0, fp(w.Y0), dy, D);
-  if (int rc = wn_gemm(h, h->X0.as<float>(), dy, G + w.off_win, h->Fp, D, R, h->Fp, D, D, true, false)) return rc;
+  if (int rc = gemm_dense(h, h->X0.as<float>(), dy, G + w.off_win, h->Fp, D, R, h->Fp, D, D, true, false)) return rc;
   HIPCHK(h, hipGetLastError());
   HIPCHK(h, hipEventRecord(h->ev_bucket.back(), st));   // one bucket: the whole gradient with the fault word
   h->have_grads = true;
@@ -280,10 +265,6 @@ int wn_backward(nasr_ctx* h) {
 }  // namespace nasr_impl
 
 void nasr_impl::WnStateDelete::operator()(WnState* w) const { delete w; }
-
-namespace {
-WnState* wn_of(nasr_handle h) { return h ? h->wn.get() : nullptr; }
-}  // namespace
 
 extern "C" {
 
@@ -351,15 +332,15 @@ int nasr_create_wavenet(const nasr_wavenet_cfg* cfg, int device_id, void* stream
 }
 
 int64_t nasr_wavenet_bn_count(nasr_handle h) {
-  WnState* w = wn_of(h);
-  if (!w) return h ? h->fail(NASR_ERR_STATE, "nasr_wavenet_bn_count: not a WaveNet handle") : NASR_ERR_ARG;
+  WAVENET_CALL(h);
+  WnState* w = h->wn.get();
   return (int64_t)w->S * w->D;
 }
 
 int nasr_wavenet_get_bn_state(nasr_handle h, float* moving_mean, float* moving_var, float* biased, int64_t n,
                               int64_t* updates) {
-  WnState* w = wn_of(h);
-  if (!w) return h ? h->fail(NASR_ERR_STATE, "nasr_wavenet_get_bn_state: not a WaveNet handle") : NASR_ERR_ARG;
+  WAVENET_CALL(h);
+  WnState* w = h->wn.get();
   if (n != (int64_t)w->S * w->D) return h->fail(NASR_ERR_ARG, "nasr_wavenet_get_bn_state: wrong length");
   HIPCHK(h, hipSetDevice(h->device));
   const size_t sb = (size_t)n * 4;
@@ -373,8 +354,8 @@ int nasr_wavenet_get_bn_state(nasr_handle h, float* moving_mean, float* moving_v
 
 int nasr_wavenet_set_bn_state(nasr_handle h, const float* moving_mean, const float* moving_var, const float* biased,
                               int64_t n, int64_t updates) {
-  WnState* w = wn_of(h);
-  if (!w) return h ? h->fail(NASR_ERR_STATE, "nasr_wavenet_set_bn_state: not a WaveNet handle") : NASR_ERR_ARG;
+  WAVENET_CALL(h);
+  WnState* w = h->wn.get();
   if (n != (int64_t)w->S * w->D || updates < 0 || !moving_mean || !moving_var || !biased)
     return h->fail(NASR_ERR_ARG, "nasr_wavenet_set_bn_state: wrong length, null array or negative update count");
   HIPCHK(h, hipSetDevice(h->device));
@@ -388,15 +369,15 @@ int nasr_wavenet_set_bn_state(nasr_handle h, const float* moving_mean, const flo
 }
 
 int nasr_wavenet_set_bn_hold(nasr_handle h, int hold) {
-  WnState* w = wn_of(h);
-  if (!w) return h ? h->fail(NASR_ERR_STATE, "nasr_wavenet_set_bn_hold: not a WaveNet handle") : NASR_ERR_ARG;
+  WAVENET_CALL(h);
+  WnState* w = h->wn.get();
   w->hold = hold != 0;
   return NASR_OK;
 }
 
 int nasr_wavenet_get_batch_stats(nasr_handle h, float* mean, float* var, int64_t n) {
-  WnState* w = wn_of(h);
-  if (!w) return h ? h->fail(NASR_ERR_STATE, "nasr_wavenet_get_batch_stats: not a WaveNet handle") : NASR_ERR_ARG;
+  WAVENET_CALL(h);
+  WnState* w = h->wn.get();
   if (n != (int64_t)w->S * w->D || !mean || !var) return h->fail(NASR_ERR_ARG, "nasr_wavenet_get_batch_stats: wrong length");
   if (!w->have_stats) return h->fail(NASR_ERR_STATE, "nasr_wavenet_get_batch_stats: no training pass has run");
   HIPCHK(h, hipSetDevice(h->device));
@@ -406,8 +387,8 @@ int nasr_wavenet_get_batch_stats(nasr_handle h, float* mean, float* var, int64_t
 }
 
 int nasr_wavenet_apply_bn_stats(nasr_handle h, const float* mean, const float* var, int64_t n, int count) {
-  WnState* w = wn_of(h);
-  if (!w) return h ? h->fail(NASR_ERR_STATE, "nasr_wavenet_apply_bn_stats: not a WaveNet handle") : NASR_ERR_ARG;
+  WAVENET_CALL(h);
+  WnState* w = h->wn.get();
   if (n != (int64_t)w->S * w->D || count < 0 || (count > 0 && (!mean || !var)))
     return h->fail(NASR_ERR_ARG, "nasr_wavenet_apply_bn_stats: wrong length or count");
   if (count == 0) return NASR_OK;
