@@ -174,7 +174,8 @@ int nasr_stage_batch_context(nasr_handle h, const float* centre, const float* pa
                              int Lmax, int* ticket);
 /* (utils.py:24-31 feeding dataset.py:33-40) A batch straight from audio: the utterances audio[offsets[b] ..
  * offsets[b+1]) at rates[b] Hz (NULL: all at the featurizer's samplerate) go through `featurizer`'s front end - resampler,
- * features, whole-utterance normalisation - on the device, and its last kernel writes the normalised centre frames
+ * features, whole-utterance normalisation (or the causal rule, nasr_mfcc_cfg.norm = 1: every pad value is then 0) - on
+ * the device, and its last kernel writes the normalised centre frames
  * [B,T,D] (D = nasr_mfcc_width of the featurizer's config; zeros past an utterance's end) and the pad values straight into `model`'s batch slot, in the layout of
  * nasr_upload_batch_context: no feature crosses PCIe in either direction.  T = the longest utterance's nasr_mfcc_frames,
  * seq_len_out[b] = utterance b's; both are computed on the host and written before anything is launched.  The slot holds
@@ -194,8 +195,8 @@ int nasr_stage_batch_audio(nasr_handle model, nasr_handle featurizer, const floa
 /* (No counterpart in the reference: its only augmentation is rand_shift, dataset.py:23-31.)  SpecAugment masks for a
  * batch in the centre form: utterance b's time mask k zeroes the normalised centre frames [t0, t0 + tw), its frequency
  * mask k the columns [f0, f0 + fw) of every static_width-wide block of a frame ([static | delta | delta-delta]: column
- * j of each block derives from filter j).  0 is the utterance's own mean after the whole-utterance normalisation, which
- * is computed before masking.  The context stacking runs on the masked frames: a masked frame is masked in every window
+ * j of each block derives from filter j).  0 is the utterance's own mean after the whole-utterance normalisation (the
+ * running mean under the causal rule), which is computed before masking.  The context stacking runs on the masked frames: a masked frame is masked in every window
  * it appears in, the pad values are never masked.  A mask of width 0 is no mask. */
 #define NASR_AUG_MAX_MASKS 8
 typedef struct {
@@ -391,7 +392,8 @@ int nasr_stream_open(nasr_handle h, int S);
  * state.  NASR_ERR_STATE without one, as for every call below. */
 int nasr_stream_close(nasr_handle h);
 /* (No counterpart in the reference: tfnetwork.py:179-181 decodes whole utterances.)  Zeroes the state and the frame count
- * of the n slots listed (slots == NULL: of every slot): a new utterance starts there.  A slot outside [0,S-1]:
+ * of the n slots listed (slots == NULL: of every slot), and their front-end state when the session takes samples
+ * (nasr_stream_attach_audio): a new utterance starts there.  A slot outside [0,S-1]:
  * NASR_ERR_ARG, nothing reset. */
 int nasr_stream_reset(nasr_handle h, const int32_t* slots, int n);
 /* (No counterpart in the reference: tfnetwork.py:179-181 decodes whole utterances.)  One chunk: feats [S][Tc][F], n_frames
@@ -411,6 +413,39 @@ int nasr_stream_get_state(nasr_handle h, float* state, int64_t n);
  * layout of nasr_stream_get_state; the frame counts stay): continuing on another handle with the same parameters gives
  * the first handle's logits bit for bit. */
 int nasr_stream_set_state(nasr_handle h, const float* state, int64_t n);
+/* (No counterpart in the reference: tfnetwork.py:179-181 decodes whole utterances, utils.py:29 normalises them whole.)  The
+ * session takes SAMPLES from now on: `featurizer`, a featurizer handle with norm = 1 (the causal rule at nasr_mfcc_cfg), turns
+ * each slot's samples into the chunk's stacked rows on the device.  Called once, after nasr_stream_open;
+ * the featurizer must outlive the session, its scratch buffers are shared with its other calls (ordered by an event, as
+ * for nasr_upload_batch_audio; one thread at a time per featurizer handle).  Per slot the device keeps the un-framed tail
+ * of the samples with the one sample in front of it that pre-emphasis reads, the running sums S1, S2, the raw frames that
+ * wait for the norm_min_frames-th (at most that many) and a ring of the last 2*numcontext normalised frames: nothing
+ * grows with the utterance.  NASR_ERR_STATE: `featurizer` is not a featurizer handle, sits on another device, has
+ * norm != 1, or samples are attached already; NASR_ERR_ARG: feature_size != (2*numcontext+1)*D. */
+int nasr_stream_attach_audio(nasr_handle model, nasr_handle featurizer);
+/* (No counterpart in the reference: tfnetwork.py:179-181 decodes whole utterances.)  Host only: what a
+ * nasr_stream_feed_audio of n_samples [S] new samples per slot, with last [S] (nullable), would emit now: rows_out [S] and
+ * *Tc_out = their maximum, which sizes logits_out.  With n samples of an utterance received, Fc = 0 if n < frame_len else
+ * 1 + (n - frame_len) / frame_step frames are complete, and the rows that exist are nasr_mfcc_frames(n) once the utterance
+ * is declared finished, else 0 while Fc < norm_min_frames, else max(0, Fc - numcontext); a feed emits the difference.  The
+ * errors are those of the feed; nothing changes. */
+int nasr_stream_audio_rows(nasr_handle model, const int64_t* n_samples, const uint8_t* last, int32_t* rows_out, int* Tc_out);
+/* (No counterpart in the reference: tfnetwork.py:179-181 decodes whole utterances.)  One feed of samples at the
+ * featurizer's rate (no resampling in a session): slot b's new samples are audio[offsets[b] .. offsets[b+1]), none is
+ * allowed (the slot is idle, or finishing); last[b] != 0 (last nullable) declares slot b's utterance complete: only then is
+ * a zero-padded final frame made.  On the handle's stream: the samples are appended to each slot's tail, the spectral
+ * kernel of nasr_featurize runs on the newly complete frames, the running sums advance frame by frame, every frame u
+ * whose n_u = max(u+1, norm_min_frames) frames (capped by the utterance's own at `last`) exist is normalised with exactly
+ * S[n_u] - whenever its samples happen to arrive - and a kernel writes the chunk's stacked rows [S][Tc][F] into the chunk's
+ * batch slot; then the forward pass of nasr_stream_feed.  rows_out [S] and *Tc_out as nasr_stream_audio_rows gives them;
+ * logits_out [Tc][S][C] (logits_rows >= Tc rows of it), rows t >= rows_out[b] of slot b unspecified.  The logits are, bit
+ * for bit, those of nasr_stream_feed given the rows of nasr_featurize (norm = 1) of the whole utterance.  Tc = 0: no
+ * forward pass runs and the resident batch is kept.  After a feed with last[b] the slot waits for nasr_stream_reset, which
+ * also clears its front-end state; until then any sample or `last` for it is NASR_ERR_STATE.  NASR_ERR_ARG, nothing
+ * changed: `last` on a slot that has received no sample at all (named), offsets that decrease, logits_rows < Tc, more
+ * than 2^28 samples; NASR_ERR_STATE: no samples attached. */
+int nasr_stream_feed_audio(nasr_handle model, const float* audio, const int64_t* offsets, const uint8_t* last, int32_t* rows_out,
+                           int* Tc_out, float* logits_out, int64_t logits_rows);
 
 /* The CTC beam search as a state that lives between calls - host only, the procedure and arithmetic of
  * nasr_ctc_beam_search(_lm), which is open + one feed + best + close on this very code: feeding an utterance's frames in
@@ -646,6 +681,17 @@ int nasr_las_beam_get_times(nasr_handle h, float* ms_out);
  * delta-delta], and include_context and the normalisation work on D-wide frames (one mean and one std over the stacked
  * matrix, zero pads included).  Both restate psf's documented procedure; neither is pinned against the package, nor is
  * the summation order against numpy.dot's inside psf's delta.
+ * norm = 1 (no counterpart in the reference) replaces the whole-utterance normalisation by a causal rule
+ * that can be computed while the audio arrives.  x[u] is un-normalised frame u of an utterance of T frames (D columns),
+ * M = norm_min_frames.  In float64, without fused multiply-adds: p1[u] = sum_k x[u][k] and p2[u] = sum_k x[u][k]^2 with
+ * the columns in ascending order; S1[n] = S1[n-1] + p1[n-1] and likewise S2, S[0] = 0, strictly in frame order (no
+ * parallel scan: a chunked and a whole-utterance run must agree bit for bit).  Frame u is normalised once, with the first
+ * n_u = min(T, max(u+1, M)) frames: N = n_u D, mean = S1[n_u] / N, var = S2[n_u] / N - mean mean, sd = sqrt(var) if
+ * var > 0, else 1 (digital silence must not put NaNs into a carried LSTM state), y[u][k] = (float)((x[u][k] - mean) / sd).
+ * Every frame counts once.  Row t of the output is y[t-numcontext .. t+numcontext], an out-of-utterance context frame is
+ * exact 0.0f (the running mean), so the pad value of every utterance in the batch-slot form is 0.  mean_std reports
+ * (mean, sd) at n = T.  norm = 1 with deltas > 0 is refused: psf's delta looks 2 (or 4) frames ahead and replicates the end of
+ * the array, which needs a look-ahead rule of its own.  A zeroed norm / norm_min_frames is the whole-utterance rule.
  * nasr_create_featurizer returns an ordinary handle: nasr_last_error, nasr_synchronize and nasr_destroy work on it and
  * every model call returns NASR_ERR_STATE.  Only nfft = 512 (psf 0.6's default) is implemented; 1 <= nfilt <= 128. */
 typedef struct {
@@ -657,6 +703,8 @@ typedef struct {
   int32_t kind;                           /* 0: MFCC; 1: log-mel filterbank, numcep filters: numcep must equal nfilt,
                                              ceplifter and append_energy are ignored */
   int32_t deltas;                         /* 0, 1 (+ delta) or 2 (+ delta and delta-delta) */
+  int32_t norm;                           /* 0: whole-utterance normalisation (utils.py:29); 1: the causal rule above */
+  int32_t norm_min_frames;                /* M of the causal rule, in [1,1000]; read only when norm = 1 */
 } nasr_mfcc_cfg;
 int nasr_create_featurizer(const nasr_mfcc_cfg* cfg, int device_id, void* stream, nasr_handle* out);
 /* Host only (no device needed): the frame count of an utterance of num_samples >= 1 samples (psf framesig: 1 if

@@ -2,7 +2,7 @@
 missing or no gfx950 device is usable, everything here raises."""
 import ctypes
 import os
-from ctypes import POINTER, Structure, byref, c_char, c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_uint32, c_void_p
+from ctypes import POINTER, Structure, byref, c_char, c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_uint8, c_uint32, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, 'libnasr.so')
@@ -47,6 +47,7 @@ SYMBOLS = [
     'nasr_set_grad_clip', 'nasr_get_grad_clip', 'nasr_get_grad_clip_stats',
     'nasr_stream_open', 'nasr_stream_close', 'nasr_stream_reset', 'nasr_stream_feed', 'nasr_stream_frames',
     'nasr_stream_get_state', 'nasr_stream_set_state',
+    'nasr_stream_attach_audio', 'nasr_stream_audio_rows', 'nasr_stream_feed_audio',
     'nasr_ctc_beam_open', 'nasr_ctc_beam_feed', 'nasr_ctc_beam_best', 'nasr_ctc_beam_close',
 ]
 
@@ -75,7 +76,8 @@ class LasCfg(Structure):
 class MfccCfg(Structure):
     _fields_ = [('samplerate', c_int32), ('numcep', c_int32), ('numcontext', c_int32), ('nfilt', c_int32),
                 ('nfft', c_int32), ('winlen', c_double), ('winstep', c_double), ('preemph', c_float),
-                ('ceplifter', c_int32), ('append_energy', c_int32), ('kind', c_int32), ('deltas', c_int32)]
+                ('ceplifter', c_int32), ('append_energy', c_int32), ('kind', c_int32), ('deltas', c_int32),
+                ('norm', c_int32), ('norm_min_frames', c_int32)]
 
 
 AUG_MAX_MASKS = 8      # NASR_AUG_MAX_MASKS
@@ -255,6 +257,9 @@ def load():
         'nasr_stream_frames': (c_int, [H, POINTER(c_int64)]),
         'nasr_stream_get_state': (c_int, [H, fp, c_int64]),
         'nasr_stream_set_state': (c_int, [H, fp, c_int64]),
+        'nasr_stream_attach_audio': (c_int, [H, H]),
+        'nasr_stream_audio_rows': (c_int, [H, POINTER(c_int64), POINTER(c_uint8), ip, POINTER(c_int)]),
+        'nasr_stream_feed_audio': (c_int, [H, fp, POINTER(c_int64), POINTER(c_uint8), ip, POINTER(c_int), fp, c_int64]),
         'nasr_ctc_beam_open': (c_int, [c_int, c_int, c_int, fp, fp, c_int, c_int, c_float, c_float, POINTER(c_void_p)]),
         'nasr_ctc_beam_feed': (c_int, [c_void_p, fp, c_int64, c_int]),
         'nasr_ctc_beam_best': (c_int, [c_void_p, ip, c_int, ip, fp]),

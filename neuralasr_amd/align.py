@@ -14,7 +14,7 @@ import numpy as np
 from .config import Config
 from .logger import get_logger
 from .preprocess_mfcc import label_ngrams
-from .utils import compute_mfcc_and_read_transcription, read_label_text
+from .utils import compute_mfcc_and_read_transcription, normalization_of, read_label_text
 
 logger = get_logger()
 
@@ -92,7 +92,8 @@ def main(argv=None):
             (score, sp), = network.align_audio([audio], [rate], labels, [ids.size])
         else:
             mfcc = compute_mfcc_and_read_transcription(args.input, config.samplerate, config.numcontext, config.numcep,
-                                                       kind=config.features, deltas=config.deltas)
+                                                       kind=config.features, deltas=config.deltas,
+                                                       **normalization_of(config))
             (score, sp), = network.align(np.expand_dims(mfcc, axis=0), labels, [mfcc.shape[0]], [ids.size])
     finally:
         engine = getattr(network, 'engine', None)        # the handle goes with the call, not with the collector

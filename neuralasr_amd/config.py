@@ -14,7 +14,10 @@ mask as a share of the utterance, default 1.0), speed_perturb (comma-separated f
 and augment_seed (default 0); without them nothing changes.  One more optional [Parameters] key, max_grad_norm, switches
 on global-norm gradient clipping with a non-finite guard in the optimiser step (the reference clips
 nothing): absent or 0 = off, a positive number = tf.clip_by_global_norm's threshold, inf = measure and guard only; only
-training reads it."""
+training reads it.  Two more optional [Parameters] keys choose how the GPU front end normalises (the
+reference has only the whole-utterance rule of utils.py:29): normalization=utterance|causal (default utterance) and, with
+causal only, norm_min_frames (the frames the running statistics wait for, 1..1000, default 50 = 0.5 s); training,
+preprocessing and decoding all read them, so that a model is decoded with the normalisation it was trained with."""
 import importlib
 from configparser import ConfigParser, ExtendedInterpolation
 
@@ -67,6 +70,7 @@ class Config(object):
         if deltas not in ('0', '1', '2'):
             raise ValueError("'deltas' must be 0, 1 or 2, not %r, in %s" % (deltas, configfile))
         self.deltas = int(deltas)
+        self._read_normalization(par, configfile)
         self.frame_width = self.numcep * (1 + self.deltas)
         self.feature_size = (2 * self.numcontext + 1) * self.frame_width
         self.lm_file = par['lm_file'].strip() if 'lm_file' in par else None
@@ -87,6 +91,28 @@ class Config(object):
         self.test_input = test['input'] if 'input' in test else None
         if self.test_input is None and not self.train_input:
             raise ValueError("Missing 'test_input' in configuration file: " + configfile)
+
+    def _read_normalization(self, par, configfile):
+        """normalization and norm_min_frames (None under the whole-utterance rule, which has no such number)"""
+        self.normalization = par['normalization'].strip() if 'normalization' in par else 'utterance'
+        if self.normalization not in ('utterance', 'causal'):
+            raise ValueError("'normalization' must be utterance or causal, not %r, in %s" % (self.normalization, configfile))
+        self.norm_min_frames = None
+        if 'norm_min_frames' in par:
+            if self.normalization != 'causal':
+                raise ValueError("'norm_min_frames' needs normalization=causal, in %s" % configfile)
+            try:
+                self.norm_min_frames = int(par['norm_min_frames'].strip())
+            except ValueError:
+                self.norm_min_frames = 0
+            if not 1 <= self.norm_min_frames <= 1000:
+                raise ValueError("'norm_min_frames' must be an integer in [1,1000], not %r, in %s"
+                                 % (par['norm_min_frames'], configfile))
+        elif self.normalization == 'causal':
+            self.norm_min_frames = 50
+        if self.normalization == 'causal' and self.deltas:
+            raise ValueError("'normalization=causal' needs deltas=0 (the delta columns look ahead; DESIGN.md §16), in %s"
+                             % configfile)
 
     def _read_augment(self, par, configfile):
         def number(key, kind, default, lo, hi, what):
@@ -138,7 +164,7 @@ class Config(object):
         return network_class(self.network)(self, fortraining=fortraining)
 
     def print_config(self):
-        names = ['samplerate', 'numcep', 'numcontext', 'features', 'deltas', 'rand_shift', 'batch_size', 'epochs', 'learningrate',
+        names = ['samplerate', 'numcep', 'numcontext', 'features', 'deltas', 'normalization', 'norm_min_frames', 'rand_shift', 'batch_size', 'epochs', 'learningrate',
                  'model_dir', 'start_step', 'report_step', 'num_gpus', 'label_context', 'punc_regex', 'network',
                  'sym_file', 'train_input', 'test_input', 'mfcc_input', 'mfcc_output', 'start_marker', 'end_marker']
         lines = ['']

@@ -17,6 +17,17 @@
 //   mfcc_norm_slot_kernel the same statistics, written as a model handle's batch slot takes them (nasr_batch.hip):
 //                         the normalised centre frames [B][T][D] of a whole batch, zeros past each utterance's
 //                         end, and one pad value (0 - mean) / std per utterance; nasr_upload_batch_audio
+//   mfcc_causal_norm_kernel, mfcc_causal_slot_kernel
+//                         cfg.norm = 1 (the reference has no causal front end): the same two output forms
+//                         under the causal rule.  One workgroup per utterance: the per-frame sums p1, p2 in parallel over
+//                         frames, their prefix sums S1, S2 by ONE lane each in frame order, then frame u normalised with
+//                         the statistics of its first n_u = min(T, max(u+1, M)) frames; context frames outside the
+//                         utterance are exact zeros
+//   mfcc_stream_*_kernel  a stream session that takes samples (nasr_stream_feed_audio): per slot the carried sample tail and
+//                         the new samples become one segment (assemble), mfcc_spectral_kernel runs on the newly complete
+//                         frames, the prefix continues from the carried sums and the frames that have become normalisable
+//                         are normalised (norm), the chunk's stacked rows go straight into the batch slot (stack), and the
+//                         ring of the last 2 nc normalised frames and the tail are left for the next feed (carry)
 // Tables (twiddles, filter weights, the DCT x lifter matrix) are built once per handle on the host in double.
 // nasr_featurize_rates first resamples utterances at other rates to the config rate (resample.hip) into a device
 // buffer, which the same two kernels then read.
@@ -46,10 +57,12 @@ struct FzDims {
 // tw [256] = exp(-2 pi i t / 256), tw2 [257] = exp(-2 pi i k / 512); fb_lo/fb_n [nfilt]: a filter's first bin and bin
 // count, fb_off [nfilt]: where its weights start in fb_w; dct [nfilt][numcep]: ortho DCT-II x lifter, c fastest.
 // meta: uoff [n+1] (int64 sample offsets), foff [n+1] (int64 frame offsets), fmap [F] (int32 frame -> utterance).
+// ulead (NULL: zeros) [n]: the samples of utterance u in front of its first frame of this launch: a stream session hands
+// over the one sample that pre-emphasis reads before the frame (sample 0 of the BUFFER is the utterance's first only then).
 __global__ __launch_bounds__(64 * SPEC_WAVES) void mfcc_spectral_kernel(
     const float* __restrict__ audio, const int64_t* __restrict__ uoff, const int64_t* __restrict__ foff,
-    const int* __restrict__ fmap, int64_t nframes, const double2* __restrict__ tw, const double2* __restrict__ tw2,
-    const int* __restrict__ fb_lo, const int* __restrict__ fb_n, const int* __restrict__ fb_off,
+    const int* __restrict__ fmap, const int64_t* __restrict__ ulead, int64_t nframes, const double2* __restrict__ tw,
+    const double2* __restrict__ tw2, const int* __restrict__ fb_lo, const int* __restrict__ fb_n, const int* __restrict__ fb_off,
     const double* __restrict__ fb_w, const double* __restrict__ dct, FzDims d, double* __restrict__ cep) {
   __shared__ double2 buf[SPEC_WAVES][2][FFT_N];
   __shared__ double logmel[SPEC_WAVES][MAX_FILT];
@@ -65,7 +78,7 @@ __global__ __launch_bounds__(64 * SPEC_WAVES) void mfcc_spectral_kernel(
     const int u = fmap[f];
     base = uoff[u];
     len = uoff[u + 1] - base;
-    t0 = (f - foff[u]) * (int64_t)d.frame_step;
+    t0 = (f - foff[u]) * (int64_t)d.frame_step + (ulead ? ulead[u] : 0);
   }
   const int nval = min(d.frame_len, 2 * FFT_N);   // frames longer than nfft are truncated (rfft(frame, nfft))
 #pragma unroll
@@ -278,6 +291,224 @@ __global__ __launch_bounds__(NORM_THREADS) void mfcc_norm_slot_kernel(const doub
   for (int64_t e = tid; e < nb; e += NORM_THREADS) dst[e] = e < ne ? norm_value(src[e], mean, sd) : 0.f;
 }
 
+// ------------------------------------------------------------------------------------------ the causal rule (§16)
+// (mean, sd) of the first n frames from their sums S1 = sum x, S2 = sum x^2: the one expression every user of the rule
+// rounds through.  No FMA: mean * mean is rounded before it is subtracted.  A variance that is not > 0 (digital silence,
+// or a NaN) gives sd = 1, so that 0 / 0 becomes 0.
+__device__ __forceinline__ void causal_mean_sd(double S1, double S2, int64_t n, int D, double* mean, double* sd) {
+#pragma clang fp contract(off)
+  const double N = (double)(n * D);
+  const double m = S1 / N;
+  const double var = S2 / N - m * m;
+  *mean = m;
+  *sd = var > 0.0 ? sqrt(var) : 1.0;
+}
+
+// the frames whose statistics normalise frame u of T: every frame waits for the first M, none looks past its own
+__device__ __forceinline__ int64_t causal_count(int64_t u, int64_t T, int M) {
+  const int64_t n = u + 1 > M ? u + 1 : M;
+  return n < T ? n : T;
+}
+
+// One workgroup walks T frames [T][D] at src; every thread calls it.  pfx [T][2] receives (S1, S2) after each frame.
+// Frames are taken NORM_THREADS at a time: each thread sums the columns of its frame in ascending order (product rounded,
+// then added), lane 0 of wave 0 then walks the chunk's p1 and lane 0 of wave 1 its p2 in frame order, each carrying its
+// running sum from chunk to chunk: the association order is that of a sequential loop over the utterance, whatever T is
+// and wherever a stream session cuts it.  carry: the sum so far (thread 0: S1, thread 64: S2; 0 at the utterance's
+// start); returned to those two threads as it stands after the T frames.  Every value has one writer.
+__device__ __forceinline__ double causal_prefix(const double* __restrict__ src, int64_t T, int D, double carry, double* pfx,
+                                                double (*sh)[NORM_THREADS]) {
+  const int tid = threadIdx.x;
+  for (int64_t base = 0; base < T; base += NORM_THREADS) {
+    const int64_t u = base + tid;
+    if (u < T) {
+#pragma clang fp contract(off)
+      const double* row = src + u * D;
+      double a = 0.0, b = 0.0;
+      for (int k = 0; k < D; ++k) {
+        const double v = row[k];
+        a += v;
+        b += v * v;
+      }
+      sh[0][tid] = a;
+      sh[1][tid] = b;
+    }
+    __syncthreads();
+    if (tid == 0 || tid == 64) {
+      double* q = sh[tid >> 6];
+      const int cnt = (int)(T - base < NORM_THREADS ? T - base : NORM_THREADS);
+      for (int i = 0; i < cnt; ++i) {
+        carry += q[i];
+        q[i] = carry;
+      }
+    }
+    __syncthreads();
+    if (u < T) {
+      pfx[2 * u] = sh[0][tid];
+      pfx[2 * u + 1] = sh[1][tid];
+    }
+  }
+  __syncthreads();
+  return carry;
+}
+
+// One workgroup per utterance of T frames: pfx [T][2] as above, ms [T][2] the (mean, sd) frame u is normalised with.
+__device__ __forceinline__ void causal_utt_stats(const double* __restrict__ src, int64_t T, int D, int M, double* pfx,
+                                                 double* ms, double (*sh)[NORM_THREADS]) {
+  causal_prefix(src, T, D, 0.0, pfx, sh);
+  for (int64_t u = threadIdx.x; u < T; u += NORM_THREADS) {
+    const int64_t n = causal_count(u, T, M);
+    double mean, sd;
+    causal_mean_sd(pfx[2 * (n - 1)], pfx[2 * (n - 1) + 1], n, D, &mean, &sd);
+    ms[2 * u] = mean;
+    ms[2 * u + 1] = sd;
+  }
+  __syncthreads();
+}
+
+// The stacked form under the causal rule: out[t][w*D + c] = y[t+w-nc][c], exact 0 outside the utterance; mstd (nullable)
+// gets (mean, sd) of all T frames.  pfx and ms are [F][2] scratch, indexed like the frames.
+__global__ __launch_bounds__(NORM_THREADS) void mfcc_causal_norm_kernel(const double* __restrict__ cep,
+                                                                        const int64_t* __restrict__ foff, int D, int nc, int M,
+                                                                        double* pfx, double* ms, float* __restrict__ out,
+                                                                        double* __restrict__ mstd) {
+  __shared__ double sh[2][NORM_THREADS];
+  const int u = blockIdx.x, tid = threadIdx.x;
+  const int64_t f0 = foff[u], T = foff[u + 1] - f0;
+  const double* src = cep + f0 * D;
+  const double* m = ms + 2 * f0;
+  causal_utt_stats(src, T, D, M, pfx + 2 * f0, ms + 2 * f0, sh);
+  if (mstd && tid == 0) {                 // frame T-1 is normalised with all T frames
+    mstd[2 * u] = m[2 * (T - 1)];
+    mstd[2 * u + 1] = m[2 * (T - 1) + 1];
+  }
+  const int rowlen = (2 * nc + 1) * D;
+  float* dst = out + f0 * rowlen;
+  for (int64_t e = tid; e < T * rowlen; e += NORM_THREADS) {
+    const int64_t t = e / rowlen;
+    const int r = (int)(e - t * rowlen);
+    const int64_t ts = t + r / D - nc;
+    dst[e] = (ts >= 0 && ts < T) ? norm_value(src[ts * D + r % D], m[2 * ts], m[2 * ts + 1]) : 0.f;
+  }
+}
+
+// The batch-slot form under the causal rule: the normalised centre frames, zeros past the utterance's end, pad value 0.
+__global__ __launch_bounds__(NORM_THREADS) void mfcc_causal_slot_kernel(const double* __restrict__ cep,
+                                                                        const int64_t* __restrict__ foff, int D, int M, int Tb,
+                                                                        double* pfx, double* ms, float* __restrict__ centre,
+                                                                        float* __restrict__ pad) {
+  __shared__ double sh[2][NORM_THREADS];
+  const int u = blockIdx.x, tid = threadIdx.x;
+  const int64_t f0 = foff[u], T = foff[u + 1] - f0;
+  const double* src = cep + f0 * D;
+  const double* m = ms + 2 * f0;
+  causal_utt_stats(src, T, D, M, pfx + 2 * f0, ms + 2 * f0, sh);
+  if (tid == 0) pad[u] = 0.f;
+  const int64_t ne = T * D, nb = (int64_t)Tb * D;
+  float* dst = centre + (int64_t)u * nb;
+  for (int64_t e = tid; e < nb; e += NORM_THREADS) {
+    const int64_t t = e / D;
+    dst[e] = e < ne ? norm_value(src[e], m[2 * t], m[2 * t + 1]) : 0.f;
+  }
+}
+
+// ---------------------------------------------------------------------- a stream session that takes samples (§16)
+// One feed, slot by slot (FzFeedSlot, worked out on the host): the slot's segment of the work buffer is its carried tail
+// followed by its new samples.  grid (x, S).
+__global__ __launch_bounds__(NORM_THREADS) void mfcc_stream_assemble_kernel(const FzFeedSlot* __restrict__ desc,
+                                                                            const float* __restrict__ tail, int tail_cap,
+                                                                            const float* __restrict__ in, float* __restrict__ seg) {
+  const int b = blockIdx.y;
+  const FzFeedSlot d = desc[b];
+  const int64_t n = d.ntail + d.nnew;
+  for (int64_t i = (int64_t)blockIdx.x * NORM_THREADS + threadIdx.x; i < n; i += (int64_t)gridDim.x * NORM_THREADS)
+    seg[d.seg_off + i] = i < d.ntail ? tail[(int64_t)b * tail_cap + i] : in[d.in_off + i - d.ntail];
+}
+
+// One workgroup per slot, behind the spectral kernel: the sequential update of the slot's running sums over its new frames
+// (causal_prefix, continued from sums [S][2]), then every frame that this feed makes normalisable - frames [nnorm, upto),
+// the waiting ones of earlier feeds from pend [S][M][D] and the new ones from cep - through causal_mean_sd and norm_value
+// with exactly S[n_u], n_u = max(u+1, M) capped by T when the feed completes the utterance; frames that still wait for
+// the M-th go to pend.  ynew [.][D] receives the normalised frames in frame order.
+__global__ __launch_bounds__(NORM_THREADS) void mfcc_stream_norm_kernel(const double* __restrict__ cep,
+                                                                        const FzFeedSlot* __restrict__ desc, int D, int M,
+                                                                        double* sums, double* pend, double* pfx,
+                                                                        float* __restrict__ ynew) {
+  __shared__ double sh[2][NORM_THREADS];
+  __shared__ double s0[2];
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const FzFeedSlot d = desc[b];
+  const int64_t nnew = d.want - d.nfb;
+  const double* src = cep + d.f_off * D;
+  double* px = pfx + 2 * d.f_off;
+  double* pd = pend + (int64_t)b * M * D;
+  const bool chain = tid == 0 || tid == 64;
+  double c = 0.0;
+  if (chain) {
+    if (d.nfb > 0) c = sums[2 * b + (tid >> 6)];
+    s0[tid >> 6] = c;                     // S[nfb]
+  }
+  c = causal_prefix(src, nnew, D, c, px, sh);
+  if (chain) sums[2 * b + (tid >> 6)] = c;
+  const int64_t ne = (d.upto - d.nnorm) * D;
+  float* y = ynew + d.y_off * D;
+  for (int64_t e = tid; e < ne; e += NORM_THREADS) {
+    const int64_t j = e / D, u = d.nnorm + j;
+    const int k = (int)(e - j * D);
+    int64_t n = u + 1 > M ? u + 1 : M;
+    if (d.T >= 0 && n > d.T) n = d.T;
+    const double S1 = n > d.nfb ? px[2 * (n - d.nfb - 1)] : s0[0];
+    const double S2 = n > d.nfb ? px[2 * (n - d.nfb - 1) + 1] : s0[1];
+    double mean, sd;
+    causal_mean_sd(S1, S2, n, D, &mean, &sd);
+    const double x = u >= d.nfb ? src[(u - d.nfb) * D + k] : pd[u * D + k];
+    y[e] = norm_value(x, mean, sd);
+  }
+  if (d.upto == 0)                        // fewer than M frames so far (want < M): they wait, at their own index
+    for (int64_t e = tid; e < nnew * D; e += NORM_THREADS) pd[d.nfb * D + e] = src[e];
+}
+
+// The chunk's stacked rows [S][Tc][(2 nc + 1) D] straight into the batch slot, one thread per element: row t of slot b is
+// row rows0 + t of its utterance, context frame s from this feed's ynew or, older, from the slot's ring yring [S][R][D]
+// (frame s at s mod R); exact zeros outside the utterance and behind the slot's nrows.
+__global__ __launch_bounds__(NORM_THREADS) void mfcc_stream_stack_kernel(const FzFeedSlot* __restrict__ desc, int S, int Tc, int D,
+                                                                         int nc, int R, const float* __restrict__ ynew,
+                                                                         const float* __restrict__ yring, float* __restrict__ out) {
+  const int F = (2 * nc + 1) * D;
+  const int64_t e = (int64_t)blockIdx.x * NORM_THREADS + threadIdx.x;
+  if (e >= (int64_t)S * Tc * F) return;
+  const int b = (int)(e / ((int64_t)Tc * F));
+  const int64_t r = e - (int64_t)b * Tc * F;
+  const int t = (int)(r / F), q = (int)(r - (int64_t)t * F);
+  const int w = q / D, k = q - w * D;
+  const FzFeedSlot d = desc[b];
+  float v = 0.f;
+  if (t < d.nrows) {
+    const int64_t fs = d.rows0 + t + w - nc;
+    if (fs >= 0 && fs < d.upto)
+      v = fs >= d.nnorm ? ynew[(d.y_off + fs - d.nnorm) * D + k] : yring[((int64_t)b * R + fs % R) * D + k];
+  }
+  out[e] = v;
+}
+
+// One workgroup per slot, behind the stacking kernel (which reads the ring as the feed found it): the last 2 nc normalised
+// frames into the ring, the un-framed samples (with the one in front of them) into the tail.
+__global__ __launch_bounds__(NORM_THREADS) void mfcc_stream_carry_kernel(const FzFeedSlot* __restrict__ desc, int D, int nc, int R,
+                                                                         const float* __restrict__ ynew, float* __restrict__ yring,
+                                                                         const float* __restrict__ seg, float* __restrict__ tail,
+                                                                         int tail_cap) {
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const FzFeedSlot d = desc[b];
+  int64_t u0 = d.upto - 2 * nc;
+  if (u0 < d.nnorm) u0 = d.nnorm;
+  for (int64_t e = tid; e < (d.upto - u0) * D; e += NORM_THREADS) {
+    const int64_t u = u0 + e / D;
+    const int k = (int)(e % D);
+    yring[((int64_t)b * R + u % R) * D + k] = ynew[(d.y_off + u - d.nnorm) * D + k];
+  }
+  for (int64_t i = tid; i < d.nkeep; i += NORM_THREADS) tail[(int64_t)b * tail_cap + i] = seg[d.seg_off + d.keep_off + i];
+}
+
 // --------------------------------------------------------------------------------------------------- host tables
 bool cfg_ok(const nasr_mfcc_cfg* c, std::string* why) {
   if (!c) return *why = "null cfg", false;
@@ -292,6 +523,13 @@ bool cfg_ok(const nasr_mfcc_cfg* c, std::string* why) {
   if (c->numcontext < 0) return *why = "numcontext must be >= 0", false;
   if (!(c->winlen > 0.0) || !(c->winstep > 0.0)) return *why = "winlen and winstep must be > 0", false;
   if (c->kind == 0 && c->ceplifter < 0) return *why = "ceplifter must be >= 0", false;
+  if (c->norm != 0 && c->norm != 1) return *why = "norm must be 0 (whole utterance) or 1 (causal)", false;
+  if (c->norm == 1 && (c->norm_min_frames < 1 || c->norm_min_frames > 1000))
+    return *why = "norm_min_frames must be in [1,1000] when norm = 1", false;
+  if (c->norm == 1 && c->deltas > 0)
+    return *why = "norm = 1 (causal) needs deltas = 0: psf's delta looks 2 frames ahead (4 for the delta-delta) and replicates "
+                  "the end of the array, which needs a look-ahead rule of its own",
+           false;
   return true;
 }
 
@@ -344,6 +582,8 @@ struct FzState {
   DevPtr<int> fb_lo, fb_n, fb_off;
   DevPtr<double> fb_w, dct;
   DevBuf audio, meta, cep, out, mstd;
+  DevBuf pfx, fms;                     // norm = 1: the prefix sums (S1, S2) and the (mean, sd) of every frame, [F][2] each
+  DevBuf sin, ynew;                    // a stream session's feed: the new samples as they came, the frames it normalises
   std::vector<char> hmeta;
   DevPtr<double2> rs_tab;              // the resampling filter's (table[k], table[k+1]) pairs, made at the first use
   DevBuf raud, rmeta;                  // resampled audio; the resampling plan (RsUtt [n], then RsWave [waves])
@@ -469,7 +709,8 @@ int fz_front(nasr_ctx* eh, FzState& z, const std::string& fn, const FzPlan& p, c
     if (int rc = resample_prepare(eh, z, p.rp, p.S_in)) return rc;
   }
   if (!scratch_ensure(z, z.audio, (size_t)p.S_in * 4) || !scratch_ensure(z, z.meta, z.hmeta.size()) ||
-      !scratch_ensure(z, z.cep, (size_t)F * z.d.width * 8) || !scratch_ensure(z, z.mstd, (size_t)n * 16))
+      !scratch_ensure(z, z.cep, (size_t)F * z.d.width * 8) || !scratch_ensure(z, z.mstd, (size_t)n * 16) ||
+      (z.cfg.norm == 1 && (!scratch_ensure(z, z.pfx, (size_t)F * 16) || !scratch_ensure(z, z.fms, (size_t)F * 16))))
     return eh->fail(NASR_ERR_HIP, fn + ": device buffers for " + std::to_string(p.uoff[n]) + " samples could not be allocated");
   const void *src_audio = audio, *src_meta = z.hmeta.data(), *src_rmeta = p.rs ? z.hrmeta.data() : nullptr;
   if (pinned) {
@@ -493,7 +734,7 @@ int fz_front(nasr_ctx* eh, FzState& z, const std::string& fn, const FzPlan& p, c
   const int64_t nblk = (F + SPEC_WAVES - 1) / SPEC_WAVES;
   mfcc_spectral_kernel<<<dim3((unsigned)nblk), dim3(64 * SPEC_WAVES), 0, st>>>(
       p.rs ? z.raud.as<float>() : z.audio.as<float>(), z.meta.as<int64_t>(), z.meta.as<int64_t>() + (n + 1),
-      reinterpret_cast<const int*>(z.meta.as<char>() + 2 * p.mb), F, z.tw, z.tw2, z.fb_lo, z.fb_n, z.fb_off, z.fb_w, z.dct,
+      reinterpret_cast<const int*>(z.meta.as<char>() + 2 * p.mb), nullptr, F, z.tw, z.tw2, z.fb_lo, z.fb_n, z.fb_off, z.fb_w, z.dct,
       z.d, z.cep.as<double>());
   HIPCHK(eh, hipGetLastError());
   const int64_t dblk = (F * z.d.numcep + NORM_THREADS - 1) / NORM_THREADS;
@@ -514,8 +755,13 @@ int fz_produce_slot(nasr_ctx* eh, nasr_ctx* fzh, const FzPlan& p, const float* a
   const std::string fn = "audio batch";
   int rc = fz_front(eh, z, fn, p, audio, pinned, st);
   if (!rc) {
-    mfcc_norm_slot_kernel<<<dim3(p.n), dim3(NORM_THREADS), 0, st>>>(z.cep.as<double>(), z.meta.as<int64_t>() + (p.n + 1),
-                                                                    z.d.width, z.d.nc, Tb, dcentre, dpad);
+    if (z.cfg.norm == 1)
+      mfcc_causal_slot_kernel<<<dim3(p.n), dim3(NORM_THREADS), 0, st>>>(z.cep.as<double>(), z.meta.as<int64_t>() + (p.n + 1),
+                                                                        z.d.width, z.cfg.norm_min_frames, Tb, z.pfx.as<double>(),
+                                                                        z.fms.as<double>(), dcentre, dpad);
+    else
+      mfcc_norm_slot_kernel<<<dim3(p.n), dim3(NORM_THREADS), 0, st>>>(z.cep.as<double>(), z.meta.as<int64_t>() + (p.n + 1),
+                                                                      z.d.width, z.d.nc, Tb, dcentre, dpad);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) rc = eh->fail(NASR_ERR_HIP, fn + ": " + hipGetErrorString(e));
   }
@@ -534,6 +780,188 @@ int fz_feature_width(const nasr_ctx* fzh, int* numcontext, int* frame_width) {
 }
 
 int fz_static_width(const nasr_ctx* fzh) { return fzh->fz->d.numcep; }
+
+// What a stream session that takes samples keeps (nasr_stream_attach_audio): on the device, per slot, the sample tail
+// (capacity frame_len + 1), the running sums, the frames that wait for the M-th, and the ring of the last 2 nc normalised
+// frames; on the host the counts that decide what a feed does.  Nothing in it grows with the utterance.
+struct FzStream {
+  nasr_ctx* fzh = nullptr;             // the featurizer: its tables, and its scratch buffers under the ev_busy protocol
+  int S = 0, tail_cap = 0, R = 1;
+  DevBuf tail, sums, pend, yring;
+  struct Slot {
+    int64_t n = 0, nframes = 0, nnorm = 0, rows = 0;   // samples received, frames made, frames normalised, rows emitted
+    bool finished = false;
+  };
+  std::vector<Slot> slot;
+};
+
+void FzStreamDelete::operator()(FzStream* f) const { delete f; }
+
+int fz_stream_attach(nasr_ctx* eh, nasr_ctx* fzh, int S, std::unique_ptr<FzStream, FzStreamDelete>* out) {
+  const std::string fn = "nasr_stream_attach_audio";
+  if (!fzh || !fzh->fz) return eh->fail(NASR_ERR_STATE, fn + ": `featurizer` is not a featurizer handle");
+  if (fzh->device != eh->device)
+    return eh->fail(NASR_ERR_STATE, fn + ": the model is on device " + std::to_string(eh->device) + ", the featurizer on device " +
+                                        std::to_string(fzh->device));
+  const FzState& z = *fzh->fz;
+  if (z.cfg.norm != 1)
+    return eh->fail(NASR_ERR_STATE, fn + ": the featurizer's norm is " + std::to_string(z.cfg.norm) +
+                                        ": only the causal normalisation (norm = 1) can be computed while the audio arrives");
+  if (z.W * z.d.width != eh->F)
+    return eh->fail(NASR_ERR_ARG, fn + ": feature_size " + std::to_string(eh->F) + " must equal (2*numcontext+1)*numcep = (2*" +
+                                      std::to_string(z.d.nc) + "+1)*" + std::to_string(z.d.width) + " of the featurizer");
+  if (z.d.frame_step > z.d.frame_len)
+    return eh->fail(NASR_ERR_ARG, fn + ": frames that leave samples out (winstep > winlen) are not implemented");
+  std::unique_ptr<FzStream, FzStreamDelete> a(new FzStream());
+  a->fzh = fzh;
+  a->S = S;
+  a->tail_cap = z.d.frame_len + 1;
+  a->R = std::max(1, 2 * z.d.nc);
+  a->slot.assign((size_t)S, FzStream::Slot());
+  const size_t D = (size_t)z.d.width;
+  if (!a->tail.ensure((size_t)S * a->tail_cap * 4, nullptr) || !a->sums.ensure((size_t)S * 16, nullptr) ||
+      !a->pend.ensure((size_t)S * z.cfg.norm_min_frames * D * 8, nullptr) || !a->yring.ensure((size_t)S * a->R * D * 4, nullptr))
+    return eh->fail(NASR_ERR_HIP, fn + ": hipMalloc of the slots' front-end state failed");
+  *out = std::move(a);
+  return NASR_OK;
+}
+
+void fz_stream_reset(FzStream& a, int slot) {
+  // the counts alone: a slot with no frame reads none of its device state
+  for (int b = 0; b < a.S; ++b)
+    if (slot < 0 || slot == b) a.slot[(size_t)b] = FzStream::Slot();
+}
+
+int fz_stream_plan(nasr_ctx* eh, const FzStream& a, const std::string& fn, const int64_t* nnew, const uint8_t* last, FzFeedPlan* p) {
+  const FzState& z = *a.fzh->fz;
+  const int64_t flen = z.d.frame_len, fstep = z.d.frame_step, M = z.cfg.norm_min_frames, nc = z.d.nc;
+  p->slot.assign((size_t)a.S, FzFeedSlot());
+  p->seg_total = p->in_total = p->f_total = p->y_total = 0;
+  p->Tc = 0;
+  for (int b = 0; b < a.S; ++b) {
+    const FzStream::Slot& s = a.slot[(size_t)b];
+    const bool fin = last && last[b];
+    if (nnew[b] < 0) return eh->fail(NASR_ERR_ARG, fn + ": slot " + std::to_string(b) + " has a negative sample count");
+    if (s.finished && (nnew[b] > 0 || fin))
+      return eh->fail(NASR_ERR_STATE, fn + ": slot " + std::to_string(b) + " holds a finished utterance: nasr_stream_reset it first");
+    if (fin && s.n + nnew[b] < 1)
+      return eh->fail(NASR_ERR_ARG, fn + ": `last` on slot " + std::to_string(b) + ", which has received no sample");
+    FzFeedSlot& d = p->slot[(size_t)b];
+    const int64_t n2 = s.n + nnew[b];
+    const int64_t full = n2 < flen ? 0 : 1 + (n2 - flen) / fstep;
+    const int64_t a0 = std::max<int64_t>(0, s.nframes * fstep - 1);
+    d.nfb = s.nframes;
+    d.want = s.finished ? s.nframes : fin ? frames_of(flen, fstep, n2) : full;
+    d.T = fin ? d.want : -1;
+    d.nnorm = s.nnorm;
+    d.upto = s.finished ? s.nnorm : (fin || d.want >= M) ? d.want : 0;
+    d.rows0 = s.rows;
+    d.nrows = (s.finished ? s.rows : fin ? d.want : std::max<int64_t>(0, d.upto - nc)) - s.rows;
+    d.ntail = s.finished ? 0 : s.n - a0;
+    d.nnew = nnew[b];
+    d.lead = s.nframes > 0 ? 1 : 0;
+    const int64_t a1 = std::max<int64_t>(0, d.want * fstep - 1);
+    d.keep_off = a1 - a0;
+    d.nkeep = (fin || s.finished) ? 0 : std::max<int64_t>(0, n2 - a1);
+    d.n_after = n2;
+    d.seg_off = p->seg_total; d.in_off = p->in_total; d.f_off = p->f_total; d.y_off = p->y_total;
+    if (d.nkeep > a.tail_cap || d.ntail > a.tail_cap || d.nrows < 0 || d.upto < d.nnorm || d.want < d.nfb)
+      return eh->fail(NASR_ERR_STATE, fn + ": slot " + std::to_string(b) + ": inconsistent front-end state");
+    p->seg_total += d.ntail + d.nnew;
+    p->in_total += d.nnew;
+    p->f_total += d.want - d.nfb;
+    p->y_total += d.upto - d.nnorm;
+    if (d.nrows > (1 << 24)) return eh->fail(NASR_ERR_ARG, fn + ": slot " + std::to_string(b) + " would emit " + std::to_string(d.nrows) + " rows in one feed");
+    p->Tc = std::max(p->Tc, (int)d.nrows);
+  }
+  if (p->in_total > ((int64_t)1 << 28))
+    return eh->fail(NASR_ERR_ARG, fn + ": " + std::to_string(p->in_total) + " samples in one feed: at most 2^28");
+  return NASR_OK;
+}
+
+void fz_stream_advance(FzStream& a, const FzFeedPlan& p, const uint8_t* last) {
+  for (int b = 0; b < a.S; ++b) {
+    FzStream::Slot& s = a.slot[(size_t)b];
+    const FzFeedSlot& d = p.slot[(size_t)b];
+    s.n = d.n_after;
+    s.nframes = d.want;
+    s.nnorm = d.upto;
+    s.rows = d.rows0 + d.nrows;
+    s.finished = s.finished || (last && last[b]);
+  }
+}
+
+int fz_stream_run(nasr_ctx* eh, FzStream& a, const FzFeedPlan& p, const float* audio, float* dfeats, hipStream_t st) {
+  FzState& z = *a.fzh->fz;
+  const std::string fn = "nasr_stream_feed_audio";
+  const int S = a.S, D = z.d.width;
+  const int64_t F = p.f_total;
+  // the meta block: the slots' descriptors, then what the spectral kernel reads: uoff [S+1], foff [S+1], lead [S], fmap [F]
+  const size_t db = (size_t)S * sizeof(FzFeedSlot), ob = (size_t)(S + 1) * 8;
+  z.hmeta.resize(db + 2 * ob + (size_t)S * 8 + (size_t)F * 4);
+  memcpy(z.hmeta.data(), p.slot.data(), db);
+  int64_t* uoff = reinterpret_cast<int64_t*>(z.hmeta.data() + db);
+  int64_t* foff = uoff + (S + 1);
+  int64_t* lead = foff + (S + 1);
+  int* fmap = reinterpret_cast<int*>(lead + S);
+  for (int b = 0; b < S; ++b) {
+    const FzFeedSlot& d = p.slot[(size_t)b];
+    uoff[b] = d.seg_off;
+    foff[b] = d.f_off;
+    lead[b] = d.lead;
+    for (int64_t f = 0; f < d.want - d.nfb; ++f) fmap[d.f_off + f] = b;
+  }
+  uoff[S] = p.seg_total;
+  foff[S] = F;
+  int rc = scratch_acquire(eh, z, st);
+  if (rc) return rc;
+  if (!scratch_ensure(z, z.sin, (size_t)std::max<int64_t>(p.in_total, 1) * 4) ||
+      !scratch_ensure(z, z.audio, (size_t)std::max<int64_t>(p.seg_total, 1) * 4) || !scratch_ensure(z, z.meta, z.hmeta.size()) ||
+      !scratch_ensure(z, z.cep, (size_t)std::max<int64_t>(F, 1) * D * 8) || !scratch_ensure(z, z.pfx, (size_t)std::max<int64_t>(F, 1) * 16) ||
+      !scratch_ensure(z, z.ynew, (size_t)std::max<int64_t>(p.y_total, 1) * D * 4))
+    return eh->fail(NASR_ERR_HIP, fn + ": device buffers for " + std::to_string(p.seg_total) + " samples could not be allocated");
+  const FzFeedSlot* desc = z.meta.as<FzFeedSlot>();
+  const int64_t* d_uoff = reinterpret_cast<const int64_t*>(z.meta.as<char>() + db);
+  auto queue = [&]() -> int {
+    HIPCHK(eh, hipEventRecord(z.ev[0], st));
+    if (p.in_total > 0) HIPCHK(eh, hipMemcpyAsync(z.sin.p, audio, (size_t)p.in_total * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(eh, hipMemcpyAsync(z.meta.p, z.hmeta.data(), z.hmeta.size(), hipMemcpyHostToDevice, st));
+    HIPCHK(eh, hipEventRecord(z.ev[1], st));
+    int64_t longest = 1;
+    for (const FzFeedSlot& d : p.slot) longest = std::max(longest, d.ntail + d.nnew);
+    const unsigned gx = (unsigned)std::min<int64_t>(64, (longest + NORM_THREADS - 1) / NORM_THREADS);
+    mfcc_stream_assemble_kernel<<<dim3(gx, S), dim3(NORM_THREADS), 0, st>>>(desc, a.tail.as<float>(), a.tail_cap,
+                                                                             z.sin.as<float>(), z.audio.as<float>());
+    HIPCHK(eh, hipGetLastError());
+    if (F > 0) {
+      const int64_t nblk = (F + SPEC_WAVES - 1) / SPEC_WAVES;
+      mfcc_spectral_kernel<<<dim3((unsigned)nblk), dim3(64 * SPEC_WAVES), 0, st>>>(
+          z.audio.as<float>(), d_uoff, d_uoff + (S + 1), reinterpret_cast<const int*>(d_uoff + 3 * S + 2), d_uoff + 2 * (S + 1), F,
+          z.tw, z.tw2, z.fb_lo, z.fb_n, z.fb_off, z.fb_w, z.dct, z.d, z.cep.as<double>());
+      HIPCHK(eh, hipGetLastError());
+    }
+    mfcc_stream_norm_kernel<<<dim3(S), dim3(NORM_THREADS), 0, st>>>(z.cep.as<double>(), desc, D, z.cfg.norm_min_frames,
+                                                                    a.sums.as<double>(), a.pend.as<double>(), z.pfx.as<double>(),
+                                                                    z.ynew.as<float>());
+    HIPCHK(eh, hipGetLastError());
+    if (dfeats) {
+      const int64_t ne = (int64_t)S * p.Tc * z.W * D;
+      mfcc_stream_stack_kernel<<<dim3((unsigned)((ne + NORM_THREADS - 1) / NORM_THREADS)), dim3(NORM_THREADS), 0, st>>>(
+          desc, S, p.Tc, D, z.d.nc, a.R, z.ynew.as<float>(), a.yring.as<float>(), dfeats);
+      HIPCHK(eh, hipGetLastError());
+    }
+    mfcc_stream_carry_kernel<<<dim3(S), dim3(NORM_THREADS), 0, st>>>(desc, D, z.d.nc, a.R, z.ynew.as<float>(), a.yring.as<float>(),
+                                                                     z.audio.as<float>(), a.tail.as<float>(), a.tail_cap);
+    HIPCHK(eh, hipGetLastError());
+    return NASR_OK;
+  };
+  rc = queue();
+  // also when something failed part-way: whatever was queued on st still reads the scratch buffers
+  (void)hipEventRecord(z.ev[2], st);
+  if (hipEventRecord(z.ev_busy, st) == hipSuccess) z.busy_valid = true;
+  z.times_pending = rc == NASR_OK;       // nasr_featurize_times: this feed's copies and front-end kernels
+  return rc;
+}
 
 }  // namespace nasr_impl
 
@@ -560,8 +988,14 @@ int featurize(nasr_handle h, const std::string& fn, const float* audio, const in
   if (!z.out.ensure((size_t)F * rowlen * 4, nullptr))
     return h->fail(NASR_ERR_HIP, fn + ": device buffers for " + std::to_string(p.uoff[n]) + " samples could not be allocated");
   if (int rc = fz_front(h, z, fn, p, audio + offsets[0], nullptr, h->st)) return rc;
-  mfcc_norm_kernel<<<dim3(n), dim3(NORM_THREADS), 0, h->st>>>(z.cep.as<double>(), z.meta.as<int64_t>() + (n + 1), z.d.width,
-                                                             z.d.nc, z.out.as<float>(), z.mstd.as<double>());
+  if (z.cfg.norm == 1)
+    mfcc_causal_norm_kernel<<<dim3(n), dim3(NORM_THREADS), 0, h->st>>>(z.cep.as<double>(), z.meta.as<int64_t>() + (n + 1),
+                                                                      z.d.width, z.d.nc, z.cfg.norm_min_frames,
+                                                                      z.pfx.as<double>(), z.fms.as<double>(),
+                                                                      z.out.as<float>(), z.mstd.as<double>());
+  else
+    mfcc_norm_kernel<<<dim3(n), dim3(NORM_THREADS), 0, h->st>>>(z.cep.as<double>(), z.meta.as<int64_t>() + (n + 1), z.d.width,
+                                                               z.d.nc, z.out.as<float>(), z.mstd.as<double>());
   HIPCHK(h, hipGetLastError());
   HIPCHK(h, hipEventRecord(z.ev[2], h->st));
   HIPCHK(h, hipMemcpyAsync(out, z.out.p, (size_t)F * rowlen * 4, hipMemcpyDeviceToHost, h->st));

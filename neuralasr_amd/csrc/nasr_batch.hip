@@ -224,7 +224,7 @@ static bool stack_reshape(const nasr_ctx* h) { return h->cfg.merge == NASR_MERGE
 // slot_fill (1): the argument checks, in this order; *masked: aug has a mask of non-zero width
 static int check_batch(nasr_ctx* h, const BatchSrc& b, bool* masked) {
   *masked = false;
-  if ((b.feats != nullptr) + (b.centre != nullptr) + (b.producer != nullptr) != 1 || !b.seq_len)
+  if ((b.feats != nullptr) + (b.centre != nullptr) + (b.producer != nullptr) + (b.stacked != nullptr) != 1 || !b.seq_len)
     return h->fail(NASR_ERR_ARG, "null input buffer");
   if (b.centre_form() && ((b.centre && !b.pad_value) || b.ctx < 0 || b.ncep < 1 || (2 * b.ctx + 1) * b.ncep != h->F))
     return h->fail(NASR_ERR_ARG, "context upload: feature_size must equal (2*numcontext+1)*numcep");
@@ -330,12 +330,13 @@ static void write_meta(const nasr_ctx* h, BatchSlot* s, const BatchSrc& src) {
 
 // slot_fill (4): the features into s->dfeats on stream cs.  `pinned_feats` false: hipMemcpyAsync from the caller's pageable
 // memory, which returns when the source may be reused; true: through the slot's pinned feature buffer, a plain DMA that
-// overlaps whatever the compute stream runs.  A producer's kernels write the centre frames and pad values themselves.
+// overlaps whatever the compute stream runs.  A producer's kernels write the centre frames and pad values (or, `stacked`,
+// the stacked rows) themselves.
 static int copy_feats(nasr_ctx* h, BatchSlot* s, const BatchSrc& b, hipStream_t cs, bool pinned_feats) {
   const size_t nc = s->nfeat - b.B;        // centre form: the centre frames, then one pad value per utterance
   float* d = s->dfeats.as<float>();
-  if (b.producer) {
-    const int rc = b.producer->run(d, d + nc, pinned_feats ? s->hfeats.get() : nullptr, cs);
+  if (b.producer || b.stacked) {
+    const int rc = b.stacked ? b.stacked->run(d, cs) : b.producer->run(d, d + nc, pinned_feats ? s->hfeats.get() : nullptr, cs);
     // what the producer queued before it failed may still read the slot's pinned buffer: the next fill waits for it
     if (rc && hipEventRecord(s->ev_copy, cs) == hipSuccess) s->copy_valid = true;
     return rc;
@@ -367,7 +368,8 @@ static int slot_fill(nasr_ctx* h, BatchSlot* s, const BatchSrc& b, hipStream_t c
   bool grew = false;
   if (!s->dmeta.ensure(s->nmeta * 4, &grew) || !s->dfeats.ensure(s->nfeat * 4, &grew) ||
       !pinned_ensure(s->hmeta, &s->hmeta_cap, s->nmeta * 4) ||
-      (pinned_feats && !pinned_ensure(s->hfeats, &s->hfeats_cap, b.producer ? b.producer->stage_bytes : s->nfeat * 4)))
+      (pinned_feats && !b.stacked &&
+       !pinned_ensure(s->hfeats, &s->hfeats_cap, b.producer ? b.producer->stage_bytes : s->nfeat * 4)))
     return h->fail(NASR_ERR_HIP, "allocation of a batch slot failed");
   if (s->copy_valid) HIPCHK(h, hipEventSynchronize(s->ev_copy));          // the pinned mirrors are free to overwrite
   if (s->released_valid && cs != h->st) HIPCHK(h, hipStreamWaitEvent(cs, s->ev_released, 0));   // and the device side unread

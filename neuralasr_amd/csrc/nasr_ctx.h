@@ -193,9 +193,15 @@ struct FzStateDelete { void operator()(FzState* f) const; };
 struct LasState;
 struct LasStateDelete { void operator()(LasState* s) const; };
 
+// The front end of a stream session that takes samples (mfcc.hip: nasr_stream_attach_audio); NULL while the session is
+// fed finished frames.
+struct FzStream;
+struct FzStreamDelete { void operator()(FzStream* f) const; };
+
 // A stream session (nasr_stream.hip): S concurrent streams on a unidirectional LSTM-family handle.
 struct StreamState {
   int S = 0;
+  std::unique_ptr<FzStream, FzStreamDelete> audio;   // per slot: sample tail, running sums, waiting and recent frames
   DevBuf state;                      // [L][S][2][H] fp32: c, then h, as of each slot's last frame; zero after open / reset
   DevBuf cimg;                       // [Bp][Hp]: the layer's saved c as step 0 of a feed reads it
   std::vector<int64_t> frames;       // [S] frames consumed since the slot's reset
@@ -545,13 +551,19 @@ struct CentreProducer {
   size_t stage_bytes = 0;
   std::function<int(float* dcentre, float* dpad, void* pinned, hipStream_t cs)> run;
 };
+// The counterpart for stacked rows: run() enqueues on stream cs whatever writes dfeats [B][T][F], every element of it (a
+// stream session's front end: nasr_stream_feed_audio).
+struct StackedProducer {
+  std::function<int(float* dfeats, hipStream_t cs)> run;
+};
 // What a batch is, from the ABI entry point to its slot.  Exactly one source: feats (stacked [B][T][F]), centre + pad_value
-// (the centre form in host memory: centre frames [B][T][ncep] and one pad value per utterance) or producer (the centre
-// form, written on the device).  ctx and ncep (numcontext; the width of one un-stacked frame) mean something in the two
+// (the centre form in host memory: centre frames [B][T][ncep] and one pad value per utterance), producer (the centre
+// form, written on the device) or stacked (stacked rows, written on the device).  ctx and ncep (numcontext; the width of one un-stacked frame) mean something in the two
 // centre forms only.  labels, label_len and aug are nullable; aug needs a centre form.  Made by the three functions below.
 struct BatchSrc {
   const float *feats = nullptr, *centre = nullptr, *pad_value = nullptr;
   const CentreProducer* producer = nullptr;
+  const StackedProducer* stacked = nullptr;
   int ctx = 0, ncep = 0;
   const int32_t *seq_len = nullptr, *labels = nullptr, *label_len = nullptr;
   int B = 0, T = 0, Lmax = 0;
@@ -601,6 +613,33 @@ int fz_produce_slot(nasr_ctx* eh, nasr_ctx* fzh, const FzPlan& p, const float* a
                     void* pinned, hipStream_t st);
 int fz_feature_width(const nasr_ctx* fzh, int* numcontext, int* frame_width);   // (2*numcontext+1)*frame_width
 int fz_static_width(const nasr_ctx* fzh);                                        // the featurizer's numcep
+
+// ---- mfcc.hip: the front end of a stream session that takes samples (nasr_stream_attach_audio / _audio_rows / _feed_audio)
+// What one feed does to every slot, worked out on the host from the sample counts alone; nothing is launched or changed.
+struct FzFeedSlot {
+  // (int64 throughout: the kernels read an array of these as it is)
+  int64_t seg_off, ntail, in_off, nnew;   // the slot's segment of the work buffer: ntail carried samples, then nnew new ones
+  int64_t keep_off, nkeep;                // the part of the segment that is the next feed's tail
+  int64_t lead;                           // samples of the segment in front of the first new frame (0 or 1)
+  int64_t f_off, nfb, want;               // first new frame in the work buffers; frames before and after the feed
+  int64_t nnorm, upto, y_off;             // frames normalised before and after; first of them in the work buffer
+  int64_t T;                              // the utterance's frames when this feed completes it, else -1
+  int64_t rows0, nrows;                   // rows emitted before, and by this feed
+  int64_t n_after;                        // samples received after the feed
+};
+struct FzFeedPlan {
+  std::vector<FzFeedSlot> slot;
+  int64_t seg_total = 0, in_total = 0, f_total = 0, y_total = 0;
+  int Tc = 0;
+};
+// fzh must be a causal featurizer on device `device` whose rows are F wide: NASR_ERR_STATE / NASR_ERR_ARG as the header says
+int fz_stream_attach(nasr_ctx* eh, nasr_ctx* fzh, int S, std::unique_ptr<FzStream, FzStreamDelete>* out);
+int fz_stream_plan(nasr_ctx* eh, const FzStream& a, const std::string& fn, const int64_t* nnew, const uint8_t* last, FzFeedPlan* p);
+// the feed's kernels on stream st; dfeats [S][Tc][F] (NULL with Tc = 0: nothing is emitted) gets the stacked rows, zeros
+// behind each slot's
+int fz_stream_run(nasr_ctx* eh, FzStream& a, const FzFeedPlan& p, const float* audio, float* dfeats, hipStream_t st);
+void fz_stream_advance(FzStream& a, const FzFeedPlan& p, const uint8_t* last);   // the host's counts, once the kernels are queued
+void fz_stream_reset(FzStream& a, int slot);                                     // slot < 0: every slot
 
 inline float* dout_of(nasr_ctx* h, int) { return h->dout.as<float>(); }
 inline float* dg_of(nasr_ctx* h, int) { return h->dgbuf.as<float>(); }

@@ -3,15 +3,18 @@
 configured network's decoder, and a 'Decoded: ...' log line.  A network that takes audio (HipNetwork.takes_audio) gets the samples:
 its features are made on the GPU and stay there.  Every other network class takes features, so every one works.
 `--stream [--chunk-frames N]`: a causal network (LstmCTCNet) is fed the file's frames N at a time (default 50 = 0.5 s), with a
-'Partial: ...' line after every chunk whose hypothesis changed.  The features are computed over the whole file first: the
-reference normalises by whole-utterance mean and std (utils.py:29), so frames a trained model understands exist only then."""
+'Partial: ...' line after every chunk whose hypothesis changed.  With normalization=utterance (the default) the features
+are computed over the whole file first: the reference normalises by whole-utterance mean and std (utils.py:29), so frames a
+model trained that way understands exist only then.  With normalization=causal the SAMPLES are fed,
+N * frame_step per feed, and the session's front end normalises as they arrive; a file at another rate than the config's
+is resampled whole on the GPU first and then chunked."""
 import argparse
 
 import numpy as np
 
 from .config import Config
 from .logger import get_logger
-from .utils import compute_mfcc_and_read_transcription
+from .utils import compute_mfcc_and_read_transcription, normalization_of
 
 logger = get_logger()
 
@@ -35,7 +38,8 @@ def features_of(config, network, path):
         audio, rate = read_wav_native(path)
         return np.asarray(network.featurizer().compute([audio], rates=[rate])[0], dtype=np.float32)
     return np.asarray(compute_mfcc_and_read_transcription(path, config.samplerate, config.numcontext, config.numcep,
-                                                          kind=config.features, deltas=config.deltas), dtype=np.float32)
+                                                          kind=config.features, deltas=config.deltas,
+                                                          **normalization_of(config)), dtype=np.float32)
 
 
 def decode_stream(config, network, feats, chunk_frames):
@@ -57,13 +61,39 @@ def decode_stream(config, network, feats, chunk_frames):
     return report(config, np.asarray(ids, dtype=np.int64))
 
 
+def decode_stream_audio(config, network, audio, rate, chunk_frames):
+    """Feed the file's SAMPLES to network.stream(), chunk_frames * frame_step at a time (normalization=causal): the same
+    'Partial:' and 'Decoded:' lines as decode_stream.  A file at another rate is resampled whole first."""
+    if chunk_frames < 1:
+        raise ValueError('--chunk-frames must be >= 1')
+    fz = network.featurizer()
+    if rate != config.samplerate:
+        audio = fz.resample([audio], [rate])[0]
+    step = chunk_frames * fz.frame_params()[1]
+    rec = network.stream(1)
+    try:
+        prev = None
+        for t in range(0, len(audio), step):
+            ids = rec.feed_audio([audio[t:t + step]], [t + step >= len(audio)])[0]
+            if ids != prev:
+                logger.info('Partial: ' + config.symbols.convert_to_str(np.asarray(ids, dtype=np.int64)))
+                prev = ids
+        ids, _ = rec.finish(0)
+    finally:
+        rec.close()
+    return report(config, np.asarray(ids, dtype=np.int64))
+
+
 def parse_args(argv=None):
     parser = argparse.ArgumentParser(description='Convert a given audio file into text using trained model.')
     parser.add_argument('config', help='Configuration file.')
     parser.add_argument('input', help='Audio file path')
     parser.add_argument('--stream', action='store_true',
-                        help='feed the frames in chunks to a causal network and log partial hypotheses')
-    parser.add_argument('--chunk-frames', type=int, default=50, help='frames per chunk with --stream (default 50 = 0.5 s)')
+                        help='feed the file in chunks to a causal network and log partial hypotheses: its samples when the '
+                             'config says normalization=causal (a file at another rate is resampled whole on the GPU '
+                             'first and then chunked), else the frames of the features computed over the whole file')
+    parser.add_argument('--chunk-frames', type=int, default=50,
+                        help='frames per chunk with --stream (default 50 = 0.5 s); samples are fed chunk-frames * frame_step at a time')
     args = parser.parse_args(argv)
     if args.chunk_frames < 1:
         parser.error('--chunk-frames must be >= 1')
@@ -77,13 +107,17 @@ def main(argv=None):
     if args.stream:
         if not hasattr(network, 'stream'):
             raise SystemExit('--stream: network %s cannot stream' % type(network).__name__)
+        if getattr(config, 'normalization', 'utterance') == 'causal':
+            from .features import read_wav_native
+            audio, rate = read_wav_native(args.input)
+            return decode_stream_audio(config, network, audio, rate, args.chunk_frames)
         return decode_stream(config, network, features_of(config, network, args.input), args.chunk_frames)
     if getattr(network, 'takes_audio', False):
         from .features import read_wav_native
         audio, rate = read_wav_native(args.input)
         return report(config, network.decode_audio([audio], [rate]))
     mfcc = compute_mfcc_and_read_transcription(args.input, config.samplerate, config.numcontext, config.numcep,
-                                               kind=config.features, deltas=config.deltas)
+                                               kind=config.features, deltas=config.deltas, **normalization_of(config))
     mfcc = np.expand_dims(mfcc, axis=0)
     seq_len = np.asarray(mfcc.shape[1], dtype=np.int32)
     return decode(config, mfcc, [seq_len], network)

@@ -3,7 +3,7 @@
 library behind include/nasr.h."""
 import collections
 import ctypes
-from ctypes import POINTER, byref, c_char, c_double, c_float, c_int, c_int32, c_int64, c_uint32, c_void_p
+from ctypes import POINTER, byref, c_char, c_double, c_float, c_int, c_int32, c_int64, c_uint8, c_uint32, c_void_p
 
 import numpy as np
 
@@ -521,6 +521,54 @@ class Engine:
         out = np.empty((Tc, S, self.num_classes), np.float32)
         self._ck(self.lib.nasr_stream_feed(self.h, _fp(feats), _ip(n), Tc, _fp(out)))
         return out
+
+    # ---- a session that takes samples
+    def stream_attach_audio(self, featurizer):
+        """The open session takes SAMPLES from now on: `featurizer` (features.Featurizer with normalization='causal', same
+        device) turns them into the chunks' rows on the device.  It must stay open as long as the session."""
+        self._ck(self.lib.nasr_stream_attach_audio(self.h, getattr(featurizer, 'h', featurizer)))
+        self._stream_featurizer = featurizer
+        self._stream_max_samples = int(getattr(featurizer, 'max_samples', 1 << 23))
+
+    def _stream_audio_args(self, n_or_chunks, last):
+        S = getattr(self, '_stream_slots', 0)
+        if len(n_or_chunks) != S:
+            raise ValueError('%d entries for %d slots' % (len(n_or_chunks), S))
+        if last is None:
+            return S, None, None
+        fin = np.ascontiguousarray([1 if x else 0 for x in last], dtype=np.uint8)
+        if fin.size != S:
+            raise ValueError('%d `last` flags for %d slots' % (fin.size, S))
+        return S, fin, fin.ctypes.data_as(POINTER(c_uint8))
+
+    def stream_audio_rows(self, n_samples, last=None):
+        """(rows int32 [S], Tc): what a stream_feed_audio of n_samples[b] new samples per slot would emit now (host only)."""
+        S, fin, fin_p = self._stream_audio_args(n_samples, last)
+        n = np.ascontiguousarray([int(x) for x in n_samples], dtype=np.int64)
+        rows, Tc = np.zeros(S, np.int32), c_int(0)
+        self._ck(self.lib.nasr_stream_audio_rows(self.h, n.ctypes.data_as(POINTER(c_int64)), fin_p, _ip(rows), byref(Tc)))
+        return rows, int(Tc.value)
+
+    def stream_feed_audio(self, chunks, last=None):
+        """One feed of samples: chunks[b] float32 [n_b] at the featurizer's rate, or None / empty (slot b is idle, or only
+        finishing); last[b] true declares slot b's utterance complete.  Returns (logits [Tc,S,C], rows int32 [S]): slot b's
+        rows_b new rows are logits[:rows_b, b]; Tc = 0 when the feed emitted nothing.  At most the featurizer's
+        max_samples per feed."""
+        S, fin, fin_p = self._stream_audio_args(chunks, last)
+        arrs = [np.zeros(0, np.float32) if c is None else np.ascontiguousarray(c, dtype=np.float32).reshape(-1) for c in chunks]
+        offsets = np.zeros(S + 1, dtype=np.int64)
+        offsets[1:] = np.cumsum([a.size for a in arrs])
+        most = getattr(self, '_stream_max_samples', 1 << 23)
+        if offsets[S] > most:
+            raise ValueError('%d samples in one feed: the featurizer takes at most max_samples = %d' % (offsets[S], most))
+        rows, Tc = self.stream_audio_rows([a.size for a in arrs], last)
+        flat = np.concatenate(arrs) if offsets[S] else np.zeros(1, np.float32)
+        out = np.empty((Tc, S, self.num_classes), np.float32)
+        got, Tc2 = np.zeros(S, np.int32), c_int(0)
+        self._ck(self.lib.nasr_stream_feed_audio(self.h, _fp(flat), offsets.ctypes.data_as(POINTER(c_int64)), fin_p, _ip(got),
+                                                 byref(Tc2), _fp(out), Tc))
+        assert Tc2.value == Tc and np.array_equal(got, rows)
+        return out, got
 
     def stream_frames(self):
         out = np.zeros(getattr(self, '_stream_slots', 0), np.int64)

@@ -5,12 +5,14 @@ way libsndfile scales them, channels averaged in float32; a file at another rate
 returns the same samples and the file's own rate, and Featurizer resamples them on the GPU
 (neuralasr_amd/csrc/resample.hip) as librosa 0.6-0.9's resample(res_type='kaiser_best') does: resampy 0.2's sinc
 interpolation, then fix_length to ceil(n * sr / rate) samples.
-Featurizer runs python_speech_features 0.6's mfcc(nfilt=128), include_context and the whole-utterance normalisation on
+Featurizer runs python_speech_features 0.6's mfcc(nfilt=128), include_context and the whole-utterance normalisation (or,
+with normalization='causal', this project's running normalisation: DESIGN.md §16) on
 the GPU (neuralasr_amd/csrc/mfcc.hip), a batch of utterances per call; with `rates`, utterances at another rate are
 resampled first and the resampled samples stay on the device.  kind='logfbank' makes psf's logfbank (numcep log-mel
 filterbank energies) in the place of the MFCC, and deltas=1|2 appends psf's delta(feat, 2) columns (and their deltas)
 to every frame before the context stacking and the normalisation."""
 import ctypes
+import math
 import struct
 
 import numpy as np
@@ -162,16 +164,28 @@ def resample_filter():
 
 
 KINDS = {'mfcc': 0, 'logfbank': 1}
+NORMS = {'utterance': 0, 'causal': 1}
+NORM_MIN_FRAMES = 50                                       # the default M of the causal rule: 0.5 s of frames
 
 
-def _cfg(samplerate, numcep, numcontext, nfilt, nfft, kind='mfcc', deltas=0):
+def _cfg(samplerate, numcep, numcontext, nfilt, nfft, kind='mfcc', deltas=0, normalization='utterance',
+         norm_min_frames=None):
     if kind not in KINDS:
         raise ValueError("kind must be 'mfcc' or 'logfbank', not %r" % (kind,))
+    if normalization not in NORMS:
+        raise ValueError("normalization must be 'utterance' or 'causal', not %r" % (normalization,))
+    if normalization == 'utterance':
+        if norm_min_frames is not None:
+            raise ValueError("norm_min_frames belongs to normalization='causal'")
+        norm_min_frames = 0                                # not read: the struct stays what it was without the fields
+    elif norm_min_frames is None:
+        norm_min_frames = NORM_MIN_FRAMES
     if kind == 'logfbank':
         nfilt = numcep                                     # psf logfbank(nfilt=numcep): one column per filter
     return _lib.MfccCfg(samplerate=samplerate, numcep=numcep, numcontext=numcontext, nfilt=nfilt, nfft=nfft,
                         winlen=0.025, winstep=0.01, preemph=0.97, ceplifter=22, append_energy=1,
-                        kind=KINDS[kind], deltas=int(deltas))
+                        kind=KINDS[kind], deltas=int(deltas), norm=NORMS[normalization],
+                        norm_min_frames=int(norm_min_frames))
 
 
 def num_frames(num_samples, samplerate, numcep=13, nfilt=128, nfft=512):
@@ -255,15 +269,20 @@ class Featurizer:
     packs consecutive utterances into calls of at most `max_samples` samples, native and resampled ones counted (a
     longer utterance goes alone).  kind='logfbank': numcep log-mel filterbank energies per frame (nfilt = numcep);
     deltas=1|2: every frame is [static | delta | delta-delta], frame_width = numcep*(1+deltas) wide.  `width` is the
-    width of a row that compute() returns: (2*numcontext+1)*frame_width."""
+    width of a row that compute() returns: (2*numcontext+1)*frame_width.  normalization='causal'  replaces
+    the whole-utterance mean and std by running ones: frame u is normalised with the statistics of its first
+    max(u+1, norm_min_frames) frames (default 50; at most the utterance's), context frames outside the utterance are
+    exact zeros, and the (mean, std) that compute(return_stats=True) reports are those of all frames."""
 
     def __init__(self, samplerate, numcep, numcontext, nfilt=128, nfft=512, device_id=0, max_samples=1 << 23,
-                 kind='mfcc', deltas=0):
+                 kind='mfcc', deltas=0, normalization='utterance', norm_min_frames=None):
         self.lib = _lib.load()
         self.samplerate, self.numcep, self.numcontext = int(samplerate), int(numcep), int(numcontext)
         self.kind, self.deltas = kind, int(deltas)
         self.max_samples = int(max_samples)
-        self.cfg = _cfg(self.samplerate, self.numcep, self.numcontext, nfilt, nfft, kind, self.deltas)
+        self.cfg = _cfg(self.samplerate, self.numcep, self.numcontext, nfilt, nfft, kind, self.deltas, normalization,
+                        norm_min_frames)
+        self.normalization, self.norm_min_frames = normalization, int(self.cfg.norm_min_frames)
         self.frame_width = self.lib.nasr_mfcc_width(ctypes.byref(self.cfg))
         if self.frame_width < 0:                           # nasr_create_featurizer names what is wrong with the cfg
             self.frame_width = self.numcep * (1 + self.deltas)
@@ -272,6 +291,12 @@ class Featurizer:
         rc = self.lib.nasr_create_featurizer(ctypes.byref(self.cfg), device_id, None, ctypes.byref(h))
         _lib.check(self.lib, None, rc)
         self.h = h
+
+    def frame_params(self):
+        """(frame_len, frame_step) in samples: psf's round_half_up of winlen and winstep times the rate"""
+        def half_up(x):
+            return int(math.floor(x)) + (1 if x - math.floor(x) >= 0.5 else 0)
+        return half_up(self.cfg.winlen * self.samplerate), max(1, half_up(self.cfg.winstep * self.samplerate))
 
     def frames(self, num_samples):
         n = self.lib.nasr_mfcc_frames(ctypes.byref(self.cfg), int(num_samples))

@@ -25,6 +25,7 @@ from ..engine import Engine
 from ..features import AudioBatch
 from ..parallel import Collective, shard_bounds
 from ..parallel import take_shard as _take_feature_shard
+from ..utils import normalization_of
 from .network import Network
 
 
@@ -226,7 +227,7 @@ class HipNetwork(Network):
             from ..features import Featurizer
             self._featurizer = Featurizer(self.config.samplerate, self.config.numcep, self.config.numcontext,
                                           device_id=self._device, kind=getattr(self.config, 'features', 'mfcc'),
-                                          deltas=getattr(self.config, 'deltas', 0))
+                                          deltas=getattr(self.config, 'deltas', 0), **normalization_of(self.config))
         return self._featurizer
 
     def audio_batch(self, audios, rates=None):

@@ -18,7 +18,7 @@ import numpy as np
 from .audiosample import AudioSample
 from .config import Config
 from .logger import get_logger
-from .utils import featurizer, read_label_text
+from .utils import featurizer, normalization_of, read_label_text
 
 logger = get_logger()
 
@@ -83,7 +83,8 @@ def gpu_featurize(config):
     """paths -> features, the WAVs read on a few host threads and featurised on the GPU in one call (files at another
     rate than the config's resampled to it there)."""
     from .features import read_wav_native
-    fz = featurizer(config.samplerate, config.numcontext, config.numcep, config.features, config.deltas)
+    fz = featurizer(config.samplerate, config.numcontext, config.numcep, config.features, config.deltas,
+                    **normalization_of(config))
 
     def run(paths):
         with ThreadPoolExecutor(max_workers=READ_THREADS) as ex:

@@ -3,9 +3,11 @@ networks/tfnetwork.py:179-181).  StreamingRecognizer feeds chunks of feature fra
 carries every LSTM layer's (c, h) per slot on the GPU, and each slot's logits to that slot's own incremental CTC beam
 search on the host; the current hypothesis is there after every chunk.
 
-The features are the caller's: the reference normalises by whole-utterance mean and std (utils.py:29), so frames that
-match a trained model exist only once the utterance is complete (`decode_wav --stream` therefore featurizes the whole
-file first and chunks the normalised frames)."""
+feed() takes the caller's features: the reference normalises by whole-utterance mean and std (utils.py:29), so frames that
+match a model trained that way exist only once the utterance is complete (`decode_wav --stream` then featurizes the whole
+file first and chunks the normalised frames).  feed_audio() takes SAMPLES: with normalization=causal in the config
+ the network's featurizer normalises as the audio arrives, the session's front end keeps each slot's sample
+tail and running statistics on the GPU, and the rows a feed makes go straight into the chunk."""
 import numpy as np
 
 from .engine import BeamStream
@@ -30,6 +32,8 @@ class StreamingRecognizer:
         width = network.beam_width if getattr(network, 'decoder', 'beam') == 'beam' else 1
         kw = {} if lm is None else dict(lm=lm, lm_weight=network.config.lm_weight, lm_bonus=network.config.lm_bonus)
         self.beams = [BeamStream(network.num_classes, width, True, **kw) for _ in range(self.slots)]
+        self._audio = False                      # feed_audio attached the network's featurizer to the session
+        self._open_audio = [False] * self.slots  # the slot holds audio that no `last` has completed yet
 
     def feed(self, chunks):
         """chunks: one entry per slot, float32 [n_b, F] (the slot's next frames) or None (the slot is idle).  Pads to the
@@ -54,12 +58,36 @@ class StreamingRecognizer:
                     self.beams[b].feed(logits[:n[b]], slot=b)
         return [beam.best()[0] for beam in self.beams]
 
+    def feed_audio(self, chunks, last=None):
+        """chunks: one entry per slot, float32 [n_b] samples at config.samplerate (the slot's next samples) or None (the
+        slot is idle); last: per slot, true when the slot's utterance ends with these samples.  The session's front end
+        makes the rows that the samples so far allow (none while fewer than norm_min_frames frames are complete, and
+        numcontext frames are held back for their right context until `last`), the network runs over them, and every
+        slot's beam is fed with its own.  Returns the current hypothesis of every slot.  Needs normalization=causal."""
+        if len(chunks) != self.slots:
+            raise ValueError('%d chunks for %d slots' % (len(chunks), self.slots))
+        if not self._audio:
+            self.engine.stream_attach_audio(self.network.featurizer())
+            self._audio = True
+        logits, rows = self.engine.stream_feed_audio(chunks, last)
+        for b in range(self.slots):
+            if rows[b]:
+                self.beams[b].feed(logits[:rows[b]], slot=b)
+            if last is not None and last[b]:
+                self._open_audio[b] = False
+            elif chunks[b] is not None and np.size(chunks[b]):
+                self._open_audio[b] = True
+        return [beam.best()[0] for beam in self.beams]
+
     def hypothesis(self, slot=0):
         """(ids, log-probability) of `slot` as it stands."""
         return self.beams[slot].best()
 
     def finish(self, slot=0):
-        """The final (ids, log-probability) of `slot`; the slot's device state and beam then start a new utterance."""
+        """The final (ids, log-probability) of `slot`; the slot's device state and beam then start a new utterance.  A
+        slot whose audio (feed_audio) no `last` has completed is completed first, with an empty feed."""
+        if self._open_audio[slot]:
+            self.feed_audio([None] * self.slots, [b == slot for b in range(self.slots)])
         out = self.beams[slot].best()
         self.engine.stream_reset([slot])
         self.beams[slot].reset()

@@ -48,28 +48,38 @@ def read_label_text(txtfile, punc_regex):
 _featurizers = {}
 
 
-def featurizer(sr, numcontext, numcep, kind='mfcc', deltas=0):
-    """One GPU featurizer per (sr, numcontext, numcep, kind, deltas) for the process."""
-    key = (int(sr), int(numcontext), int(numcep), kind, int(deltas))
+def normalization_of(config):
+    """the front end's normalisation keywords of a config (Config.normalization, norm_min_frames); the whole-utterance
+    rule for a config object without them"""
+    return dict(normalization=getattr(config, 'normalization', 'utterance'),
+                norm_min_frames=getattr(config, 'norm_min_frames', None))
+
+
+def featurizer(sr, numcontext, numcep, kind='mfcc', deltas=0, normalization='utterance', norm_min_frames=None):
+    """One GPU featurizer per (sr, numcontext, numcep, kind, deltas, normalization, norm_min_frames) for the process."""
+    key = (int(sr), int(numcontext), int(numcep), kind, int(deltas), normalization, norm_min_frames)
     if key not in _featurizers:
         from .features import Featurizer
-        _featurizers[key] = Featurizer(sr, numcep, numcontext, kind=kind, deltas=deltas)
+        _featurizers[key] = Featurizer(sr, numcep, numcontext, kind=kind, deltas=deltas, normalization=normalization,
+                                       norm_min_frames=norm_min_frames)
     return _featurizers[key]
 
 
-def convert_to_mfcc(wavfile, sr, numcontext, numcep, kind='mfcc', deltas=0):
+def convert_to_mfcc(wavfile, sr, numcontext, numcep, kind='mfcc', deltas=0, normalization='utterance',
+                    norm_min_frames=None):
     """float32 [T, (2*numcontext+1)*numcep*(1+deltas)] normalised features of a WAV file (reference: utils.py:24-31; MFCC,
     or the log-mel filterbank for kind='logfbank', with `deltas` levels of delta columns); a file at another rate than
-    sr is resampled to it on the GPU, as librosa.load(wavfile, mono=True, sr=sr) does."""
+    sr is resampled to it on the GPU, as librosa.load(wavfile, mono=True, sr=sr) does.  normalization='causal': the running
+    normalisation of DESIGN.md §16 in the place of the whole-utterance one."""
     from .features import read_wav_native
     audio, rate = read_wav_native(wavfile)
-    return featurizer(sr, numcontext, numcep, kind, deltas).compute([audio], rates=[rate])[0]
+    return featurizer(sr, numcontext, numcep, kind, deltas, normalization, norm_min_frames).compute([audio], rates=[rate])[0]
 
 
 def compute_mfcc_and_read_transcription(wavfile, sr, numcontext, numcep, punc_regex=None, txtfile=None, kind='mfcc',
-                                        deltas=0):
+                                        deltas=0, normalization='utterance', norm_min_frames=None):
     """(reference: utils.py:61-68) the features, and the cleaned transcription when txtfile is given."""
-    audio_mfcc = convert_to_mfcc(wavfile, sr, numcontext, numcep, kind, deltas)
+    audio_mfcc = convert_to_mfcc(wavfile, sr, numcontext, numcep, kind, deltas, normalization, norm_min_frames)
     if txtfile:
         return audio_mfcc, read_label_text(txtfile, punc_regex)
     return audio_mfcc

@@ -10,7 +10,11 @@ tests/resample_ref.py timed on a few utterances and scaled to the batch.
 With --to-batch the line also carries a "to_batch" field: the same batch made resident on a BiLSTM handle by
 Engine.upload_batch_audio (features written into the batch slot on the device) and, in the same run, by the route through
 the host (Featurizer.compute, zero-pad, Engine.upload_batch_context): wall time of each up to the end of the upload's
-device work, and the audio call's device-timed copies and kernels."""
+device work, and the audio call's device-timed copies and kernels.
+With --normalization causal [--norm-min-frames M] the batch goes through the causal normaliser (the
+restatement is then tests/causal_ref.py) and the line carries a "normalization" field: the kernels' time of the causal and
+of the whole-utterance front end on the same batch, rep by rep in turn in the same run - the spectral kernel is the same
+launch in both, so their difference is the normalisers'."""
 import argparse
 import json
 import os
@@ -22,6 +26,7 @@ import numpy as np
 ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), '..')
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, 'tests'))
+import causal_ref as CR                             # noqa: E402
 import feat_ref as FR                               # noqa: E402
 import resample_ref as RR                           # noqa: E402
 from neuralasr_amd.features import Featurizer       # noqa: E402
@@ -86,6 +91,8 @@ def main():
     ap.add_argument('--numcontext', type=int, default=10)
     ap.add_argument('--features', choices=('mfcc', 'logfbank'), default='mfcc', help='logfbank: --numcep log-mel filters')
     ap.add_argument('--deltas', type=int, choices=(0, 1, 2), default=0, help='append delta (and delta-delta) columns')
+    ap.add_argument('--normalization', choices=('utterance', 'causal'), default='utterance')
+    ap.add_argument('--norm-min-frames', type=int, default=50, help='M of the causal rule')
     ap.add_argument('--reps', type=int, default=10)
     ap.add_argument('--ref-utts', type=int, default=8, help='utterances the fp64 restatement is timed and checked on')
     ap.add_argument('--native-sr', type=int, default=None, help='make the audio at this rate and resample it to --sr')
@@ -96,8 +103,24 @@ def main():
     audios = [synth(n, native, s) for s in range(a.utts)]
     rates = None if a.native_sr is None else [native] * a.utts
     fz = Featurizer(a.sr, a.numcep, a.numcontext, max_samples=(n if rates is None else n + int(a.seconds * a.sr) + 1) * a.utts,
-                    kind=a.features, deltas=a.deltas)
+                    kind=a.features, deltas=a.deltas, normalization=a.normalization,
+                    norm_min_frames=a.norm_min_frames if a.normalization == 'causal' else None)
     feats = fz.compute(audios, rates=rates)               # warm-up: code objects, buffers
+    normalization = None
+    if a.normalization == 'causal':
+        whole = Featurizer(a.sr, a.numcep, a.numcontext, max_samples=fz.max_samples, kind=a.features)
+        whole.compute(audios, rates=rates)
+        k_causal, k_whole = [], []
+        for _ in range(a.reps):
+            fz.compute(audios, rates=rates)
+            k_causal.append(fz.times()[1])
+            whole.compute(audios, rates=rates)
+            k_whole.append(whole.times()[1])
+        whole.close()
+        normalization = {'norm_min_frames': a.norm_min_frames, 'frames_per_utt': fz.frames(int(a.seconds * a.sr)),
+                         'causal_kernel_ms': round(float(np.median(k_causal)), 4),
+                         'utterance_kernel_ms': round(float(np.median(k_whole)), 4),
+                         'causal_minus_utterance_ms': round(float(np.median(k_causal) - np.median(k_whole)), 4)}
     t_h2d = t_k = t_d2h = wall = 0.0
     for _ in range(a.reps):
         t0 = time.perf_counter()
@@ -132,7 +155,10 @@ def main():
                     'bitwise_vs_ref': all(x.tobytes() == y.tobytes() for x, y in zip(at_sr, restated))}
     to_batch = batch_routes(a, fz, audios, rates) if a.to_batch else None
     t0 = time.perf_counter()
-    ref = [FR.features(x, a.sr, a.numcontext, a.numcep, a.features, a.deltas)[0] for x in at_sr[:nref]]
+    if a.normalization == 'causal':
+        ref = [CR.features(x, a.sr, a.numcontext, a.numcep, a.norm_min_frames, a.features)[0] for x in at_sr[:nref]]
+    else:
+        ref = [FR.features(x, a.sr, a.numcontext, a.numcep, a.features, a.deltas)[0] for x in at_sr[:nref]]
     t_ref = (time.perf_counter() - t0) * a.utts / nref
     err = np.concatenate([np.abs(f.astype(np.float64) - r).ravel() for f, r in zip(feats, ref)])
     fz.close()
@@ -146,6 +172,7 @@ def main():
         'frames_per_s_call': round(frames / (wall / m)), 'frames_per_s_kernels': round(frames / (t_k / m * 1e-3)),
         'ref_fp64_s_batch': round(t_ref, 3), 'ref_checked_utts': nref,
         'max_abs_err': float(err.max()), 'mean_abs_err': float(err.mean()),
+        **({} if normalization is None else {'normalization': normalization}),
         **({} if resample is None else {'resample': resample}),
         **({} if to_batch is None else {'to_batch': to_batch})}))
 

@@ -11,7 +11,11 @@
   rt_factor   host_ms (and device_ms) over the audio the chunk covers (Tc frames of 10 ms): below 1 the stream keeps up
 and, for orientation only, `forward` of the same frames as one batch (B = S, T = Tc, zero initial state) on the per-step
 kernels (set_recurrence_mode(0)) on the same box: what the state hand-over adds to a forward pass of that shape.
-   python tools/streambench.py [--steps 100 --warmup 10] [--out profiles/stream_bench.json]"""
+   python tools/streambench.py [--steps 100 --warmup 10] [--out profiles/stream_bench.json]
+With --from-audio every shape also carries "from_audio" (DESIGN.md §16): the same session shape fed SAMPLES
+(Engine.stream_feed_audio; 16 kHz, 26 cepstra, numcontext 9, norm_min_frames 50; Tc * 160 samples per slot and feed, which
+emit Tc rows each once the first 50 frames are in), measured in the same child as stream_feed of as many rows: host_ms as
+above, the front end's device-timed copies and kernels (nasr_featurize_times) and the forward pass's phases."""
 import argparse
 import csv
 import glob
@@ -60,6 +64,9 @@ def worker(a):
             dev.append([pt['pack_ms'], pt['xproj_ms'], pt['rec_fwd_ms'], pt['proj_ctc_ms']])
         e.set_profiling(False)
     e.stream_close()
+    audio = None
+    if a.from_audio and not a.profiled:
+        audio = from_audio(a, e, S, Tc)
     if not a.profiled:      # (kept out of the profiled child: its kernel statistics are the feeds' alone)
         e.set_recurrence_mode(False)
         for i in range(a.warmup + a.steps):
@@ -71,6 +78,8 @@ def worker(a):
     res = {'S': S, 'Tc': Tc, 'feeds': a.warmup + a.steps, 'recurrence_mode_of_the_handle': mode,
            'host_ms': {k: {'median': round(float(np.median(v)), 3), 'min': round(min(v), 3), 'max': round(max(v), 3)}
                        for k, v in ms.items() if v}}
+    if audio:
+        res['from_audio'] = audio
     if dev:
         dev = np.asarray(dev)
         res['device_ms_per_feed'] = round(float(np.median(dev.sum(1))), 4)
@@ -78,6 +87,47 @@ def worker(a):
                                              (round(float(x), 4) for x in np.median(dev, 0))))
     print('STREAMBENCH ' + json.dumps(res), flush=True)
     e.close()
+
+
+def from_audio(a, e, S, Tc):
+    """the session fed samples: host clock, then with the profiler on the front end's and the forward pass's device time"""
+    from neuralasr_amd.features import Featurizer
+    sr, numcep, nc, M = 16000, 26, 9, 50
+    fz = Featurizer(sr, numcep, nc, normalization='causal', norm_min_frames=M)
+    assert fz.width == F
+    step = fz.frame_params()[1]
+    rs = np.random.RandomState(8)
+    feeds = a.warmup + 2 * a.steps
+    audio = (0.1 * rs.randn(S, fz.frame_params()[0] + (M + nc) * step + feeds * Tc * step)).astype(np.float32)
+    e.stream_open(S)
+    e.stream_attach_audio(fz)
+    pos = fz.frame_params()[0] + (M + nc - 1) * step          # the first M + nc frames: from here on Tc * step samples emit Tc rows
+    e.stream_feed_audio([audio[b, :pos] for b in range(S)])
+    host, front, dev = [], [], []
+    for i in range(feeds):
+        if i == a.warmup + a.steps:
+            e.set_profiling(True)
+        chunk = [audio[b, pos:pos + Tc * step] for b in range(S)]
+        pos += Tc * step
+        t0 = time.perf_counter()
+        out, rows = e.stream_feed_audio(chunk)
+        dt = (time.perf_counter() - t0) * 1e3
+        assert rows.tolist() == [Tc] * S and np.isfinite(out).all()
+        if a.warmup <= i < a.warmup + a.steps:
+            host.append(dt)
+        elif i >= a.warmup + a.steps:
+            pt = e.phase_times()
+            t = fz.times()
+            front.append([t[0], t[1]])
+            dev.append(pt['pack_ms'] + pt['xproj_ms'] + pt['rec_fwd_ms'] + pt['proj_ctc_ms'])
+    e.set_profiling(False)
+    e.stream_close()
+    fz.close()
+    front = np.median(np.asarray(front), 0)
+    return {'samples_per_slot_and_feed': Tc * step, 'norm_min_frames': M,
+            'host_ms': {'median': round(float(np.median(host)), 3), 'min': round(min(host), 3), 'max': round(max(host), 3)},
+            'front_end_copies_ms': round(float(front[0]), 4), 'front_end_kernels_ms': round(float(front[1]), 4),
+            'forward_device_ms': round(float(np.median(dev)), 4)}
 
 
 def kernel_ns(d):
@@ -95,6 +145,8 @@ def kernel_ns(d):
 
 def child(shape, a, profiled, d=None):
     cmd = [sys.executable, os.path.abspath(__file__), '--worker', '%dx%d' % shape, '--steps', str(a.steps), '--warmup', str(a.warmup)]
+    if a.from_audio and not profiled:
+        cmd.append('--from-audio')
     if profiled:
         cmd = ['rocprofv3', '--kernel-trace', '--stats', '--output-format', 'csv', '-d', d, '--'] + cmd + ['--profiled']
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=400)
@@ -109,6 +161,7 @@ def main():
     ap.add_argument('--steps', type=int, default=100)
     ap.add_argument('--warmup', type=int, default=10)
     ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'stream_bench.json'))
+    ap.add_argument('--from-audio', action='store_true', help='also feed the session samples (stream_feed_audio)')
     ap.add_argument('--worker', help='(internal) SxTc: the measured process of one shape')
     ap.add_argument('--profiled', action='store_true', help='(internal) the child runs under the profiler')
     a = ap.parse_args()
@@ -129,6 +182,8 @@ def main():
         res['audio_ms_per_chunk'] = audio_ms
         res['rt_factor_host'] = round(res['host_ms']['stream_feed']['median'] / audio_ms, 4)
         res['rt_factor_device'] = round(res['device_ms_per_feed'] / audio_ms, 4)
+        if 'from_audio' in res:
+            res['from_audio']['feed_audio_over_feed_host'] = round(res['from_audio']['host_ms']['median'] / res['host_ms']['stream_feed']['median'], 3)
         res['feed_over_forward_host'] = round(res['host_ms']['stream_feed']['median'] / res['host_ms']['forward_per_step']['median'], 3)
         doc['shapes'].append(res)
         print(json.dumps(res), flush=True)
