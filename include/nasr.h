@@ -223,6 +223,35 @@ int nasr_upload_batch_audio_aug(nasr_handle model, nasr_handle featurizer, const
 int nasr_stage_batch_audio_aug(nasr_handle model, nasr_handle featurizer, const float* audio, const int64_t* offsets,
                                const int32_t* rates, const int32_t* labels, const int32_t* label_len, int B, int Lmax,
                                int32_t* seq_len_out, int* T_out, const nasr_batch_aug* aug, int* ticket);
+/* (No counterpart in the reference: its only augmentation is rand_shift, dataset.py:23-31.)  Waveform augmentation of a
+ * batch that is given as audio, on the samples at the featurizer's rate, behind the resampler: every
+ * array is [B].  rir[b] (rir NULL: none) is an index into the featurizer's RIR bank (nasr_featurizer_set_rirs) or -1:
+ * utterance x [N] with the RIR h [K] becomes y[t] = sum_{k=0..min(K-1,t)} h[k] x[t-k], t in [0,N) (the tail is dropped:
+ * seq_len never changes), accumulated in float32 in an order that depends on (N, K, t) alone; -1: y is x, bit for bit.
+ * noise[b] (noise NULL: none) is an index into the noise bank (nasr_featurizer_set_noise) or -1: with the clip c [L] and
+ * noise_off[b] = o in [0,L), n[t] = c[(o+t) mod L], Ps = sum y^2 and Pn = sum n^2 over [0,N) in float64 in a fixed order,
+ * g = float32(sqrt(Ps/Pn) 10^(-snr_db[b]/20)) (0 when Ps or Pn is 0) and z[t] = y[t] + g n[t] in float32 (two roundings);
+ * -1: z is y, bit for bit.  noise_off and snr_db are read for the utterances with noise[b] >= 0 only. */
+#define NASR_AUG_MAX_RIR_TAPS 8192
+typedef struct {
+  const int32_t* rir;        /* [B] index into the RIR bank, -1: none; NULL: none for the whole batch */
+  const int32_t* noise;      /* [B] index into the noise bank, -1: none; NULL: none for the whole batch */
+  const int64_t* noise_off;  /* [B] first sample of the clip, in [0, its length) */
+  const float* snr_db;       /* [B] finite */
+} nasr_wave_aug;
+/* (No counterpart in the reference.)  nasr_upload_batch_audio_aug / nasr_stage_batch_audio_aug with the waveform
+ * augmentation `wave` between the resampler and the spectral kernel: everything downstream runs on z unchanged, and the
+ * result is bitwise that of the plain call on nasr_augment_audio's output.  wave == NULL (or both of its index arrays
+ * NULL): the _aug call itself, no further launch and no further buffer.  NASR_ERR_ARG, before anything is launched and
+ * with the resident batch kept, names the utterance: an index outside its bank (or no bank set), noise_off outside the
+ * clip, a non-finite snr_db, noise without noise_off or snr_db. */
+int nasr_upload_batch_audio_wave(nasr_handle model, nasr_handle featurizer, const float* audio, const int64_t* offsets,
+                                 const int32_t* rates, const int32_t* labels, const int32_t* label_len, int B, int Lmax,
+                                 int32_t* seq_len_out, int* T_out, const nasr_batch_aug* aug, const nasr_wave_aug* wave);
+int nasr_stage_batch_audio_wave(nasr_handle model, nasr_handle featurizer, const float* audio, const int64_t* offsets,
+                                const int32_t* rates, const int32_t* labels, const int32_t* label_len, int B, int Lmax,
+                                int32_t* seq_len_out, int* T_out, const nasr_batch_aug* aug, const nasr_wave_aug* wave,
+                                int* ticket);
 int nasr_commit_batch(nasr_handle h, int ticket);
 int nasr_discard_batch(nasr_handle h, int ticket);   /* give a staged batch's slot back unused */
 /* nasr_forward / nasr_loss / nasr_greedy_decode on the batch that is resident already (nasr_upload_batch*,
@@ -721,7 +750,7 @@ int nasr_mfcc_filterbank(const nasr_mfcc_cfg* cfg, int32_t* bins, float* weights
  * stacked matrix, zero pads included.  Returns when out is written (utils.py:24-31 for every utterance). */
 int nasr_featurize(nasr_handle h, const float* audio, const int64_t* offsets, int n, float* out, int64_t out_rows,
                    double* mean_std);
-/* The last nasr_featurize's, nasr_featurize_rates' or nasr_resample's device-timed phases: host-to-device copies,
+/* The last nasr_featurize's, nasr_featurize_rates', nasr_resample's or nasr_augment_audio's device-timed phases: host-to-device copies,
  * kernels (the resampling kernel included), device-to-host copies (ms). */
 int nasr_featurize_times(nasr_handle h, float* h2d_ms, float* kernel_ms, float* d2h_ms);
 
@@ -747,6 +776,27 @@ int nasr_resample(nasr_handle h, const float* audio, const int64_t* offsets, con
  * resampled lengths.  Utterances at the samplerate give bitwise what nasr_featurize gives them. */
 int nasr_featurize_rates(nasr_handle h, const float* audio, const int64_t* offsets, const int32_t* rates, int n,
                          float* out, int64_t out_rows, double* mean_std);
+
+/* ---- waveform augmentation banks (the rules are at nasr_wave_aug) -----------------
+ * (No counterpart in the reference: its only augmentation is rand_shift, dataset.py:23-31.)  The featurizer's noise
+ * bank: clip i is samples[offsets[i] .. offsets[i+1]) (float32, at the featurizer's samplerate), offsets [n_clips+1]
+ * ascending from offsets[0] >= 0.  Uploaded once; it lives on the handle until it is replaced or the handle is destroyed.
+ * n_clips = 0 (samples and offsets may be NULL) frees the bank.  Replacing it waits for the batch-slot call that may
+ * still read the old one.  NASR_ERR_ARG, naming the clip: an empty clip, a non-finite sample; NASR_ERR_STATE on a model
+ * handle. */
+int nasr_featurizer_set_noise(nasr_handle fz, const float* samples, const int64_t* offsets, int n_clips);
+/* (No counterpart in the reference.)  The featurizer's bank of room impulse responses, in the same form: RIR i is
+ * taps[offsets[i] .. offsets[i+1]), 1 to NASR_AUG_MAX_RIR_TAPS taps, used as they are (augment.prepare_rir makes the
+ * direct path tap 0 and the energy 1).  n_rirs = 0 frees the bank.  NASR_ERR_ARG, naming the RIR: no tap, more than
+ * NASR_AUG_MAX_RIR_TAPS, a non-finite tap; NASR_ERR_STATE on a model handle. */
+int nasr_featurizer_set_rirs(nasr_handle fz, const float* taps, const int64_t* offsets, int n_rirs);
+/* (No counterpart in the reference.)  nasr_resample followed by the waveform augmentation `wave` (nullable): the
+ * resampler and the three kernels that nasr_upload_batch_audio_wave runs, and the waveform z comes back: out [out_len],
+ * out_len the sum of the utterances' nasr_resample_length.  rates == NULL: every utterance is at the samplerate.
+ * nasr_featurize_times covers it (kernels: the resampler and the augmentation).  The refusals of nasr_resample and of
+ * nasr_upload_batch_audio_wave. */
+int nasr_augment_audio(nasr_handle fz, const float* audio, const int64_t* offsets, const int32_t* rates, int n,
+                       const nasr_wave_aug* wave, float* out, int64_t out_len);
 
 #ifdef __cplusplus
 }

@@ -49,6 +49,8 @@ SYMBOLS = [
     'nasr_stream_get_state', 'nasr_stream_set_state',
     'nasr_stream_attach_audio', 'nasr_stream_audio_rows', 'nasr_stream_feed_audio',
     'nasr_ctc_beam_open', 'nasr_ctc_beam_feed', 'nasr_ctc_beam_best', 'nasr_ctc_beam_close',
+    'nasr_featurizer_set_noise', 'nasr_featurizer_set_rirs', 'nasr_upload_batch_audio_wave', 'nasr_stage_batch_audio_wave',
+    'nasr_augment_audio',
 ]
 
 
@@ -86,6 +88,14 @@ AUG_MAX_MASKS = 8      # NASR_AUG_MAX_MASKS
 class BatchAug(Structure):
     _fields_ = [('static_width', c_int32), ('n_time', c_int32), ('n_freq', c_int32),
                 ('time_mask', POINTER(c_int32)), ('freq_mask', POINTER(c_int32))]
+
+
+AUG_MAX_RIR_TAPS = 8192      # NASR_AUG_MAX_RIR_TAPS
+
+
+class WaveAug(Structure):
+    _fields_ = [('rir', POINTER(c_int32)), ('noise', POINTER(c_int32)), ('noise_off', POINTER(c_int64)),
+                ('snr_db', POINTER(c_float))]
 
 
 class PhaseTimes(Structure):
@@ -193,6 +203,13 @@ def load():
                                                 POINTER(BatchAug)]),
         'nasr_stage_batch_audio_aug': (c_int, [H, H, fp, POINTER(c_int64), ip, ip, ip, c_int, c_int, ip, POINTER(c_int),
                                                POINTER(BatchAug), POINTER(c_int)]),
+        'nasr_upload_batch_audio_wave': (c_int, [H, H, fp, POINTER(c_int64), ip, ip, ip, c_int, c_int, ip, POINTER(c_int),
+                                                 POINTER(BatchAug), POINTER(WaveAug)]),
+        'nasr_stage_batch_audio_wave': (c_int, [H, H, fp, POINTER(c_int64), ip, ip, ip, c_int, c_int, ip, POINTER(c_int),
+                                                POINTER(BatchAug), POINTER(WaveAug), POINTER(c_int)]),
+        'nasr_featurizer_set_noise': (c_int, [H, fp, POINTER(c_int64), c_int]),
+        'nasr_featurizer_set_rirs': (c_int, [H, fp, POINTER(c_int64), c_int]),
+        'nasr_augment_audio': (c_int, [H, fp, POINTER(c_int64), ip, c_int, POINTER(WaveAug), fp, c_int64]),
         'nasr_forward_resident': (c_int, [H, fp]),
         'nasr_loss_resident': (c_int, [H, fp, fp]),
         'nasr_greedy_decode_resident': (c_int, [H, ip, ip]),

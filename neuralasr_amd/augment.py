@@ -15,14 +15,77 @@ index) and of nothing else - not of the order of the draws, the tower split or n
 kind 0 (speed): the factor is speed_perturb[r0 % len(speed_perturb)].  kind 1 (time mask k): width r0 % (wmax + 1) with
 wmax = min(spec_time_width, floor(spec_time_ratio * len)), first frame r1 % (len - width + 1).  kind 2 (frequency mask
 k): width r0 % (min(spec_freq_width, numcep) + 1), first column r1 % (numcep - width + 1).  The counter is the global
-step the batch trains, so a resumed run draws what the uninterrupted one drew."""
+step the batch trains, so a resumed run draws what the uninterrupted one drew.
+
+The waveform augmentation (nasr_wave_aug in include/nasr.h has the rules the GPU applies): with
+u(r) = (r >> 11) * 2^-53, kind 3 (reverberation): applied iff u(r0) < rir_prob, with RIR r1 % n_rirs of rir_list.  kind 4
+(noise): applied iff u(r0) < noise_prob, with clip r1 % n_clips of noise_list.  kind 5 (placement of the noise): the
+clip's first sample is r0 % L (L its length at the config rate), the SNR noise_snr[0] + (noise_snr[1] - noise_snr[0]) *
+u(r1) dB.  The banks themselves are read once (load_banks) and live on the featurizer."""
 import math
+import os
 
 import numpy as np
 
-from .features import AudioBatch, num_frames, resample_length
+from .features import AudioBatch, num_frames, read_wav_native, resample_length, wav_info
 
-KIND_SPEED, KIND_TIME, KIND_FREQ = 0, 1, 2
+KIND_SPEED, KIND_TIME, KIND_FREQ, KIND_RIR, KIND_NOISE, KIND_PLACE = 0, 1, 2, 3, 4, 5
+MAX_RIR_TAPS = 8192          # NASR_AUG_MAX_RIR_TAPS
+
+
+def unit(r):
+    """u(r): the 64-bit draw r as a float64 in [0, 1)"""
+    return (r >> 11) * 2.0 ** -53
+
+
+def read_list(list_file):
+    """the WAV paths of a list file: one per line, blank lines and lines that start with # skipped; a relative path is
+    relative to the list file's directory"""
+    here = os.path.dirname(os.path.abspath(list_file))
+    with open(list_file) as fh:
+        lines = [ln.strip() for ln in fh]
+    paths = [ln if os.path.isabs(ln) else os.path.join(here, ln) for ln in lines if ln and not ln.startswith('#')]
+    if not paths:
+        raise ValueError('%s lists no WAV file' % list_file)
+    return paths
+
+
+def clip_length(path, samplerate):
+    """samples of a WAV file once it is at `samplerate` (from its header alone; load_bank's arithmetic)"""
+    n, rate = wav_info(path)
+    if n < 1:
+        raise ValueError('%s holds no sample' % path)
+    return n if rate == samplerate else resample_length(n, rate, samplerate)[0]
+
+
+def prepare_rir(h):
+    """A measured room impulse response as the FIR convolves it: everything before the tap of largest |h| (the direct
+    path) dropped, so that the reverberated speech stays where the transcription and an alignment expect it; at most 8192
+    taps; unit energy (computed in float64); float32."""
+    h = np.asarray(h, dtype=np.float64).reshape(-1)
+    if h.size == 0 or not np.all(np.isfinite(h)) or not np.any(h):
+        raise ValueError('a room impulse response needs a finite, non-zero tap')
+    h = h[int(np.argmax(np.abs(h))):][:MAX_RIR_TAPS]
+    return (h / math.sqrt(float(np.sum(h * h)))).astype(np.float32)
+
+
+def load_bank(list_file, featurizer):
+    """float32 mono clips of the WAV files of a list file (read_wav_native: several channels become their mean) at the
+    featurizer's samplerate; a file at another rate is resampled on the GPU (Featurizer.resample)"""
+    out = []
+    for path in read_list(list_file):
+        a, rate = read_wav_native(path)
+        if a.size == 0:
+            raise ValueError('%s holds no sample' % path)
+        out.append(a if rate == featurizer.samplerate else np.array(featurizer.resample([a], [rate])[0]))
+    return out
+
+
+def load_banks(config, featurizer):
+    """(noise clips, prepared RIRs) of config.noise_list / config.rir_list; an empty list for a key that is off"""
+    noise = load_bank(config.noise_list, featurizer) if getattr(config, 'noise_list', None) else []
+    rirs = [prepare_rir(h) for h in load_bank(config.rir_list, featurizer)] if getattr(config, 'rir_list', None) else []
+    return noise, rirs
 
 
 class Augmenter:
@@ -38,6 +101,12 @@ class Augmenter:
         self.speeds = tuple(float(f) for f in getattr(config, 'speed_perturb', ()))
         self.seed = int(getattr(config, 'augment_seed', 0))
         self.rank = int(rank)
+        self.noise_prob = float(getattr(config, 'noise_prob', 0.0)) if getattr(config, 'noise_list', None) else 0.0
+        self.rir_prob = float(getattr(config, 'rir_prob', 0.0)) if getattr(config, 'rir_list', None) else 0.0
+        self.snr = tuple(float(v) for v in getattr(config, 'noise_snr', (10.0, 20.0)))
+        # host only: the banks' sizes from the list files and the WAV headers
+        self.clip_len = [clip_length(p, self.samplerate) for p in read_list(config.noise_list)] if self.noise_prob > 0 else []
+        self.n_rirs = len(read_list(config.rir_list)) if self.rir_prob > 0 else 0
 
     def raw(self, counter, utt, kind, k=0):
         """(r0, r1): the two 64-bit values behind the draw (counter, utt, kind, k)"""
@@ -93,10 +162,32 @@ class Augmenter:
                 fm[i, k] = (r1 % (self.numcep - w + 1), w)
         return tm, fm
 
+    def wave(self, counter, B):
+        """(rir int32 [B], noise int32 [B], noise_off int64 [B], snr_db float32 [B]) of step `counter` as nasr_wave_aug
+        takes them, -1 where an utterance gets none; None in the place of the arrays of a kind that is switched off"""
+        rir = np.full(B, -1, np.int32) if self.rir_prob > 0 else None
+        noise = np.full(B, -1, np.int32) if self.noise_prob > 0 else None
+        off = np.zeros(B, np.int64) if noise is not None else None
+        snr = np.zeros(B, np.float32) if noise is not None else None
+        for i in range(B):
+            if rir is not None:
+                r0, r1 = self.raw(counter, i, KIND_RIR)
+                if unit(r0) < self.rir_prob:
+                    rir[i] = r1 % self.n_rirs
+            if noise is not None:
+                r0, r1 = self.raw(counter, i, KIND_NOISE)
+                if unit(r0) < self.noise_prob:
+                    noise[i] = r1 % len(self.clip_len)
+                    r0, r1 = self.raw(counter, i, KIND_PLACE)
+                    off[i] = r0 % self.clip_len[noise[i]]
+                    snr[i] = self.snr[0] + (self.snr[1] - self.snr[0]) * unit(r1)
+        return rir, noise, off, snr
+
     def batch(self, counter, audios, rates, chars=None):
         """The AudioBatch of step `counter`: speed first, then the time masks from the resulting seq_len, then the
-        frequency masks."""
+        frequency masks; the waveform augmentation's draws depend on the batch's size alone."""
         new_rates, _ = self.speed(counter, [np.asarray(a).size for a in audios], rates, chars)
-        b = AudioBatch(self.samplerate, audios, new_rates, self.width)
+        rir, noise, off, snr = self.wave(counter, len(audios))
+        b = AudioBatch(self.samplerate, audios, new_rates, self.width, rir=rir, noise=noise, noise_off=off, snr_db=snr)
         b.time_masks, b.freq_masks = self.masks(counter, b.seq_len)
         return b

@@ -17,8 +17,13 @@ nothing): absent or 0 = off, a positive number = tf.clip_by_global_norm's thresh
 training reads it.  Two more optional [Parameters] keys choose how the GPU front end normalises (the
 reference has only the whole-utterance rule of utils.py:29): normalization=utterance|causal (default utterance) and, with
 causal only, norm_min_frames (the frames the running statistics wait for, 1..1000, default 50 = 0.5 s); training,
-preprocessing and decoding all read them, so that a model is decoded with the normalisation it was trained with."""
+preprocessing and decoding all read them, so that a model is decoded with the normalisation it was trained with.  Five
+more optional [Parameters] keys switch on the waveform augmentation of `train --from-audio` (augment.py; the
+reference has none): noise_list / rir_list (a file that lists WAV paths, one per line: noise clips, room impulse
+responses), noise_prob / rir_prob (the share of utterances that get one, in [0,1], default 1 when the list is given) and
+noise_snr=lo,hi (dB, lo <= hi, default 10,20); without them nothing changes, and only the training feed reads them."""
 import importlib
+import math
 from configparser import ConfigParser, ExtendedInterpolation
 
 from .logger import get_logger
@@ -141,6 +146,26 @@ class Config(object):
             if not self.speed_perturb or not all(0.5 < f < 2.0 for f in self.speed_perturb):
                 raise ValueError("'speed_perturb' must be comma-separated factors, each in (0.5, 2.0), not %r, in %s"
                                  % (par['speed_perturb'], configfile))
+        # waveform augmentation: list files of WAV paths, one per line
+        self.noise_list = par['noise_list'].strip() if 'noise_list' in par else None
+        self.rir_list = par['rir_list'].strip() if 'rir_list' in par else None
+        for key, lst in (('noise_list', self.noise_list), ('rir_list', self.rir_list)):
+            if lst is not None and not lst:
+                raise ValueError("'%s' must name a file that lists WAV paths, in %s" % (key, configfile))
+        for key, lst in (('noise_prob', 'noise_list'), ('noise_snr', 'noise_list'), ('rir_prob', 'rir_list')):
+            if key in par and getattr(self, lst) is None:
+                raise ValueError("'%s' needs '%s', in %s" % (key, lst, configfile))
+        self.noise_prob = number('noise_prob', float, 1.0 if self.noise_list else 0.0, 0.0, 1.0, 'a number in [0,1]')
+        self.rir_prob = number('rir_prob', float, 1.0 if self.rir_list else 0.0, 0.0, 1.0, 'a number in [0,1]')
+        self.noise_snr = (10.0, 20.0)
+        if 'noise_snr' in par:
+            try:
+                snr = tuple(float(x) for x in par['noise_snr'].split(','))
+            except ValueError:
+                snr = ()
+            if len(snr) != 2 or not all(math.isfinite(v) for v in snr) or not snr[0] <= snr[1]:
+                raise ValueError("'noise_snr' must be lo,hi in dB with lo <= hi, not %r, in %s" % (par['noise_snr'], configfile))
+            self.noise_snr = snr
 
     @staticmethod
     def _read_max_grad_norm(par, configfile):
@@ -158,7 +183,12 @@ class Config(object):
     @property
     def augment_on(self):
         """some augmentation key is switched on"""
-        return self.spec_time_masks > 0 or self.spec_freq_masks > 0 or len(self.speed_perturb) > 0
+        return self.spec_time_masks > 0 or self.spec_freq_masks > 0 or len(self.speed_perturb) > 0 or self.wave_on
+
+    @property
+    def wave_on(self):
+        """the waveform augmentation (noise, reverberation) is switched on"""
+        return (self.noise_list is not None and self.noise_prob > 0) or (self.rir_list is not None and self.rir_prob > 0)
 
     def load_network(self, fortraining=False):
         return network_class(self.network)(self, fortraining=fortraining)

@@ -30,7 +30,8 @@
 //                         ring of the last 2 nc normalised frames and the tail are left for the next feed (carry)
 // Tables (twiddles, filter weights, the DCT x lifter matrix) are built once per handle on the host in double.
 // nasr_featurize_rates first resamples utterances at other rates to the config rate (resample.hip) into a device
-// buffer, which the same two kernels then read.
+// buffer, which the same two kernels then read.  A call with waveform augmentation runs wave_aug.hip's
+// three kernels behind the resampler, and the spectral kernel reads their output.
 #include "nasr_ctx.h"
 #include "resample.h"
 
@@ -588,6 +589,13 @@ struct FzState {
   DevPtr<double2> rs_tab;              // the resampling filter's (table[k], table[k+1]) pairs, made at the first use
   DevBuf raud, rmeta;                  // resampled audio; the resampling plan (RsUtt [n], then RsWave [waves])
   std::vector<char> hrmeta;
+  // waveform augmentation: the banks (set once, offsets [n+1] from 0 on the host), and a call's augmented
+  // samples, its plan (WvUtt [n], then WvTile [tiles]), the tiles' powers [tiles][2] and the gains [n]; none of them exists
+  // until a call asks for it
+  DevBuf noise_bank, rir_bank;
+  std::vector<int64_t> noise_off, rir_off;
+  DevBuf wav, wmeta, wpart, gain;
+  std::vector<char> hwmeta;
   Event ev[4];
   float times[3] = {0.f, 0.f, 0.f};
   bool times_pending = false;          // ev[0..2] were recorded by a batch-slot call and not read yet (nasr_featurize_times)
@@ -690,12 +698,66 @@ int fz_plan(nasr_ctx* eh, FzState& z, const std::string& fn, const int64_t* offs
   return NASR_OK;
 }
 
-size_t fz_stage_bytes(const FzPlan& p) { return ((size_t)p.S_in * 4 + 7) / 8 * 8 + p.meta_bytes + p.rmeta_bytes; }
+size_t fz_stage_bytes(const FzPlan& p) {
+  return ((size_t)p.S_in * 4 + 7) / 8 * 8 + p.meta_bytes + p.rmeta_bytes + (p.wave ? p.wp.bytes() : 0);
+}
+
+// The checks of nasr_wave_aug (include/nasr.h) against the banks, and the kernels' parameters: utterance i's samples are
+// [p->uoff[i], p->uoff[i+1]) of the buffer at the featurizer's rate.
+int fz_wave_plan(nasr_ctx* eh, FzState& z, const std::string& fn, const nasr_wave_aug* wave, FzPlan* p) {
+  p->wave = false;
+  if (!wave || (!wave->rir && !wave->noise)) return NASR_OK;
+  const int n = p->n;
+  const std::string pre = fn + ": waveform augmentation: utterance ";
+  p->wp.utt.assign(n, WvUtt{});
+  for (int i = 0; i < n; ++i) {
+    WvUtt& u = p->wp.utt[i];
+    u.off = p->uoff[i];
+    u.n = p->uoff[i + 1] - p->uoff[i];
+    u.c_len = 1;
+    u.noise = -1;
+    const int r = wave->rir ? wave->rir[i] : -1, c = wave->noise ? wave->noise[i] : -1;
+    const int nr = (int)z.rir_off.size() - 1, ncl = (int)z.noise_off.size() - 1;
+    if (r >= 0 || r < -1) {
+      if (nr < 1) return eh->fail(NASR_ERR_ARG, pre + std::to_string(i) + " asks for RIR " + std::to_string(r) +
+                                                    ", the featurizer has no RIR bank (nasr_featurizer_set_rirs)");
+      if (r < 0 || r >= nr)
+        return eh->fail(NASR_ERR_ARG, pre + std::to_string(i) + ": RIR index " + std::to_string(r) + " is outside the bank's [0," +
+                                          std::to_string(nr - 1) + "] (-1: none)");
+      u.h_off = z.rir_off[r];
+      u.K = (int32_t)(z.rir_off[r + 1] - z.rir_off[r]);
+    }
+    if (c >= 0 || c < -1) {
+      if (ncl < 1) return eh->fail(NASR_ERR_ARG, pre + std::to_string(i) + " asks for noise clip " + std::to_string(c) +
+                                                     ", the featurizer has no noise bank (nasr_featurizer_set_noise)");
+      if (c < 0 || c >= ncl)
+        return eh->fail(NASR_ERR_ARG, pre + std::to_string(i) + ": noise index " + std::to_string(c) + " is outside the bank's [0," +
+                                          std::to_string(ncl - 1) + "] (-1: none)");
+      if (!wave->noise_off || !wave->snr_db)
+        return eh->fail(NASR_ERR_ARG, pre + std::to_string(i) + " has noise, but noise_off or snr_db is null");
+      u.c_off = z.noise_off[c];
+      u.c_len = z.noise_off[c + 1] - z.noise_off[c];
+      u.c_pos = wave->noise_off[i];
+      if (u.c_pos < 0 || u.c_pos >= u.c_len)
+        return eh->fail(NASR_ERR_ARG, pre + std::to_string(i) + ": noise_off " + std::to_string(u.c_pos) + " is outside clip " +
+                                          std::to_string(c) + "'s [0," + std::to_string(u.c_len - 1) + "]");
+      if (!std::isfinite(wave->snr_db[i])) return eh->fail(NASR_ERR_ARG, pre + std::to_string(i) + ": snr_db is not finite");
+      u.scale = std::pow(10.0, -(double)wave->snr_db[i] / 20.0);
+      u.noise = c;
+    }
+  }
+  wave_tiles(&p->wp);
+  p->wave = true;
+  return NASR_OK;
+}
 
 // The copies, the resampler, mfcc_spectral_kernel and the delta launches of plan p on stream st: z.cep holds the frames
 // [F][D] afterwards, z.meta the offsets.  audio: the first utterance's first sample.  pinned (nullable): fz_stage_bytes of pinned memory the
 // host-to-device copies go through, so that they are plain DMAs that return at once.
-int fz_front(nasr_ctx* eh, FzState& z, const std::string& fn, const FzPlan& p, const float* audio, void* pinned, hipStream_t st) {
+// samples_out (nullable): the call wants the samples at the featurizer's rate, augmented when the plan says so, and no
+// features: it returns behind the last kernel that writes them, with ev[2] still to be recorded by the caller.
+int fz_front(nasr_ctx* eh, FzState& z, const std::string& fn, const FzPlan& p, const float* audio, void* pinned, hipStream_t st,
+             const float** samples_out = nullptr) {
   const int n = p.n;
   const int64_t F = p.foff[n];
   z.hmeta.resize(p.meta_bytes);
@@ -708,32 +770,58 @@ int fz_front(nasr_ctx* eh, FzState& z, const std::string& fn, const FzPlan& p, c
   if (p.rs) {
     if (int rc = resample_prepare(eh, z, p.rp, p.S_in)) return rc;
   }
-  if (!scratch_ensure(z, z.audio, (size_t)p.S_in * 4) || !scratch_ensure(z, z.meta, z.hmeta.size()) ||
-      !scratch_ensure(z, z.cep, (size_t)F * z.d.width * 8) || !scratch_ensure(z, z.mstd, (size_t)n * 16) ||
-      (z.cfg.norm == 1 && (!scratch_ensure(z, z.pfx, (size_t)F * 16) || !scratch_ensure(z, z.fms, (size_t)F * 16))))
+  const bool feats = !samples_out;
+  if (!scratch_ensure(z, z.audio, (size_t)p.S_in * 4) ||
+      (feats && (!scratch_ensure(z, z.meta, z.hmeta.size()) || !scratch_ensure(z, z.cep, (size_t)F * z.d.width * 8) ||
+                 !scratch_ensure(z, z.mstd, (size_t)n * 16))) ||
+      (feats && z.cfg.norm == 1 && (!scratch_ensure(z, z.pfx, (size_t)F * 16) || !scratch_ensure(z, z.fms, (size_t)F * 16))))
     return eh->fail(NASR_ERR_HIP, fn + ": device buffers for " + std::to_string(p.uoff[n]) + " samples could not be allocated");
+  const size_t wub = p.wave ? p.wp.utt.size() * sizeof(WvUtt) : 0, wb = p.wave ? p.wp.bytes() : 0;
+  if (p.wave) {
+    z.hwmeta.resize(wb);
+    memcpy(z.hwmeta.data(), p.wp.utt.data(), wub);
+    memcpy(z.hwmeta.data() + wub, p.wp.tiles.data(), wb - wub);
+    if (!scratch_ensure(z, z.wav, (size_t)p.uoff[n] * 4) || !scratch_ensure(z, z.wmeta, wb) ||
+        !scratch_ensure(z, z.wpart, p.wp.tiles.size() * 16) || !scratch_ensure(z, z.gain, (size_t)n * 4))
+      return eh->fail(NASR_ERR_HIP, fn + ": device buffers for " + std::to_string(p.uoff[n]) + " augmented samples could not be allocated");
+  }
   const void *src_audio = audio, *src_meta = z.hmeta.data(), *src_rmeta = p.rs ? z.hrmeta.data() : nullptr;
+  const void* src_wmeta = p.wave ? z.hwmeta.data() : nullptr;
   if (pinned) {
     char* pa = static_cast<char*>(pinned);
     char* pm = pa + ((size_t)p.S_in * 4 + 7) / 8 * 8;
     memcpy(pa, audio, (size_t)p.S_in * 4);
     memcpy(pm, z.hmeta.data(), p.meta_bytes);
     if (p.rs) memcpy(pm + p.meta_bytes, z.hrmeta.data(), p.rmeta_bytes);
-    src_audio = pa; src_meta = pm; src_rmeta = pm + p.meta_bytes;
+    if (p.wave) memcpy(pm + p.meta_bytes + p.rmeta_bytes, z.hwmeta.data(), wb);
+    src_audio = pa; src_meta = pm; src_rmeta = pm + p.meta_bytes; src_wmeta = pm + p.meta_bytes + p.rmeta_bytes;
   }
   HIPCHK(eh, hipEventRecord(z.ev[0], st));
   HIPCHK(eh, hipMemcpyAsync(z.audio.p, src_audio, (size_t)p.S_in * 4, hipMemcpyHostToDevice, st));
-  HIPCHK(eh, hipMemcpyAsync(z.meta.p, src_meta, p.meta_bytes, hipMemcpyHostToDevice, st));
+  if (feats) HIPCHK(eh, hipMemcpyAsync(z.meta.p, src_meta, p.meta_bytes, hipMemcpyHostToDevice, st));
   if (p.rs) HIPCHK(eh, hipMemcpyAsync(z.rmeta.p, src_rmeta, p.rmeta_bytes, hipMemcpyHostToDevice, st));
+  if (p.wave) HIPCHK(eh, hipMemcpyAsync(z.wmeta.p, src_wmeta, wb, hipMemcpyHostToDevice, st));
   HIPCHK(eh, hipEventRecord(z.ev[1], st));
   if (p.rs) {
     launch_resample(z.audio.as<float>(), z.rmeta.as<RsUtt>(), rs_waves(z, n), (int64_t)p.rp.waves.size(), z.rs_tab,
                     z.raud.as<float>(), st);
     HIPCHK(eh, hipGetLastError());
   }
+  const float* samples = p.rs ? z.raud.as<float>() : z.audio.as<float>();
+  if (p.wave) {
+    launch_wave_aug(samples, z.wav.as<float>(), z.wmeta.as<WvUtt>(), n, reinterpret_cast<const WvTile*>(z.wmeta.as<char>() + wub),
+                    (int64_t)p.wp.tiles.size(), z.rir_bank.as<float>(), z.noise_bank.as<float>(), z.wpart.as<double>(),
+                    z.gain.as<float>(), st);
+    HIPCHK(eh, hipGetLastError());
+    samples = z.wav.as<float>();
+  }
+  if (samples_out) {
+    *samples_out = samples;
+    return NASR_OK;
+  }
   const int64_t nblk = (F + SPEC_WAVES - 1) / SPEC_WAVES;
   mfcc_spectral_kernel<<<dim3((unsigned)nblk), dim3(64 * SPEC_WAVES), 0, st>>>(
-      p.rs ? z.raud.as<float>() : z.audio.as<float>(), z.meta.as<int64_t>(), z.meta.as<int64_t>() + (n + 1),
+      samples, z.meta.as<int64_t>(), z.meta.as<int64_t>() + (n + 1),
       reinterpret_cast<const int*>(z.meta.as<char>() + 2 * p.mb), nullptr, F, z.tw, z.tw2, z.fb_lo, z.fb_n, z.fb_off, z.fb_w, z.dct,
       z.d, z.cep.as<double>());
   HIPCHK(eh, hipGetLastError());
@@ -1140,6 +1228,73 @@ int nasr_resample(nasr_handle h, const float* audio, const int64_t* offsets, con
   HIPCHK(h, hipMemcpyAsync(out, z.raud.p, (size_t)plan.total * 4, hipMemcpyDeviceToHost, h->st));
   HIPCHK(h, hipEventRecord(z.ev[3], h->st));
   return finish(h, z);
+}
+
+int nasr_augment_audio(nasr_handle h, const float* audio, const int64_t* offsets, const int32_t* rates, int n,
+                       const nasr_wave_aug* wave, float* out, int64_t out_len) {
+  const std::string fn = "nasr_augment_audio";
+  if (!h) return NASR_ERR_ARG;
+  FzState* zp = h->fz.get();
+  if (!zp) return h->fail(NASR_ERR_STATE, fn + ": not a featurizer handle");
+  FzState& z = *zp;
+  if (!audio || !offsets || !out || n < 1) return h->fail(NASR_ERR_ARG, fn + ": null buffer or n < 1");
+  FzPlan p;
+  if (int rc = fz_plan(h, z, fn, offsets, rates, n, &p)) return rc;
+  if (int rc = fz_wave_plan(h, z, fn, wave, &p)) return rc;
+  if (out_len != p.uoff[n])
+    return h->fail(NASR_ERR_ARG, fn + ": out_len is " + std::to_string(out_len) + ", the utterances have " + std::to_string(p.uoff[n]) +
+                                     " samples at the featurizer's rate");
+  HIPCHK(h, hipSetDevice(h->device));
+  const float* samples = nullptr;
+  if (int rc = fz_front(h, z, fn, p, audio + offsets[0], nullptr, h->st, &samples)) return rc;
+  HIPCHK(h, hipEventRecord(z.ev[2], h->st));
+  HIPCHK(h, hipMemcpyAsync(out, samples, (size_t)out_len * 4, hipMemcpyDeviceToHost, h->st));
+  HIPCHK(h, hipEventRecord(z.ev[3], h->st));
+  return finish(h, z);
+}
+
+// A bank of the featurizer (noise clips, RIRs): the checks, then the upload; `what` names an entry in the messages.
+static int set_bank(nasr_ctx* h, const std::string& fn, const char* what, const float* data, const int64_t* offsets, int n,
+                    int64_t max_len, DevBuf FzState::*bank, std::vector<int64_t> FzState::*off) {
+  if (!h) return NASR_ERR_ARG;
+  FzState* zp = h->fz.get();
+  if (!zp) return h->fail(NASR_ERR_STATE, fn + ": not a featurizer handle");
+  FzState& z = *zp;
+  if (n < 0 || (n > 0 && (!data || !offsets))) return h->fail(NASR_ERR_ARG, fn + ": null buffer or a negative count");
+  std::vector<int64_t> o(n > 0 ? n + 1 : 0, 0);
+  for (int i = 0; i < n; ++i) {
+    const int64_t len = offsets[i + 1] - offsets[i];
+    if (offsets[0] < 0 || len < 1) return h->fail(NASR_ERR_ARG, fn + ": " + what + " " + std::to_string(i) + " is empty");
+    if (max_len > 0 && len > max_len)
+      return h->fail(NASR_ERR_ARG, fn + ": " + what + " " + std::to_string(i) + " has " + std::to_string(len) + " taps, at most " +
+                                       std::to_string(max_len) + " (NASR_AUG_MAX_RIR_TAPS) are taken");
+    for (int64_t k = offsets[i]; k < offsets[i + 1]; ++k)
+      if (!std::isfinite(data[k]))
+        return h->fail(NASR_ERR_ARG, fn + ": " + what + " " + std::to_string(i) + " holds a value that is not finite (at " +
+                                         std::to_string(k - offsets[i]) + ")");
+    o[i + 1] = offsets[i + 1] - offsets[0];
+  }
+  HIPCHK(h, hipSetDevice(h->device));
+  if (z.busy_valid) {                    // a batch-slot call may still read the old bank on a model's stream
+    (void)hipEventSynchronize(z.ev_busy);
+    z.busy_valid = false;
+  }
+  (z.*bank).release();
+  (z.*off).clear();
+  if (n == 0) return NASR_OK;
+  const size_t bytes = (size_t)o[n] * 4;
+  if (!(z.*bank).ensure(bytes, nullptr)) return h->fail(NASR_ERR_HIP, fn + ": the bank's " + std::to_string(bytes) + " bytes could not be allocated");
+  HIPCHK(h, hipMemcpy((z.*bank).p, data + offsets[0], bytes, hipMemcpyHostToDevice));
+  (z.*off) = std::move(o);
+  return NASR_OK;
+}
+
+int nasr_featurizer_set_noise(nasr_handle h, const float* samples, const int64_t* offsets, int n_clips) {
+  return set_bank(h, __func__, "noise clip", samples, offsets, n_clips, 0, &FzState::noise_bank, &FzState::noise_off);
+}
+
+int nasr_featurizer_set_rirs(nasr_handle h, const float* taps, const int64_t* offsets, int n_rirs) {
+  return set_bank(h, __func__, "RIR", taps, offsets, n_rirs, WV_MAX_TAPS, &FzState::rir_bank, &FzState::rir_off);
 }
 
 int nasr_featurize_times(nasr_handle h, float* h2d_ms, float* kernel_ms, float* d2h_ms) {

@@ -429,11 +429,12 @@ int nasr_stage_batch_context(nasr_handle h, const float* centre, const float* pa
   return stage(h, centre_batch(centre, pad_value, numcontext, numcep, seq_len, labels, label_len, B, T, Lmax, nullptr), ticket);
 }
 
-// The four nasr_*_batch_audio* calls (utils.py:24-31 feeding dataset.py:33-40), fn the one that was called: the checks, the
+// The six nasr_*_batch_audio* calls (utils.py:24-31 feeding dataset.py:33-40), fn the one that was called: the checks, the
 // host-side plan (seq_len, T), and the front end as the producer of the slot's centre frames.  staged: into *ticket.
 static int audio_batch(const std::string& fn, nasr_ctx* h, nasr_ctx* fzh, const float* audio, const int64_t* offsets,
                        const int32_t* rates, const int32_t* labels, const int32_t* label_len, int B, int Lmax,
-                       int32_t* seq_len_out, int* T_out, const nasr_batch_aug* aug, bool staged, int* ticket) {
+                       int32_t* seq_len_out, int* T_out, const nasr_batch_aug* aug, const nasr_wave_aug* wave, bool staged,
+                       int* ticket) {
   if (!h) return NASR_ERR_ARG;
   if (h->family == Family::Featurizer) return h->fail(NASR_ERR_STATE, fn + ": a featurizer handle has no model");   // MODEL_CALL
   if (staged) {
@@ -455,6 +456,7 @@ static int audio_batch(const std::string& fn, nasr_ctx* h, nasr_ctx* fzh, const 
                                      " is not the featurizer's numcep " + std::to_string(fz_static_width(fzh)));
   FzPlan plan;
   if (int rc = fz_plan(h, *fzh->fz, fn, offsets, rates, B, &plan)) return rc;
+  if (int rc = fz_wave_plan(h, *fzh->fz, fn, wave, &plan)) return rc;
   int64_t Tmax = 0;
   for (int b = 0; b < B; ++b) Tmax = std::max(Tmax, plan.foff[b + 1] - plan.foff[b]);
   if (Tmax > (1 << 24)) return h->fail(NASR_ERR_ARG, fn + ": an utterance of " + std::to_string(Tmax) + " frames");
@@ -475,28 +477,43 @@ int nasr_upload_batch_audio(nasr_handle model, nasr_handle featurizer, const flo
                             const int32_t* rates, const int32_t* labels, const int32_t* label_len, int B, int Lmax,
                             int32_t* seq_len_out, int* T_out) {
   return audio_batch(__func__, model, featurizer, audio, offsets, rates, labels, label_len, B, Lmax, seq_len_out, T_out, nullptr,
-                     false, nullptr);
+                     nullptr, false, nullptr);
 }
 
 int nasr_stage_batch_audio(nasr_handle model, nasr_handle featurizer, const float* audio, const int64_t* offsets,
                            const int32_t* rates, const int32_t* labels, const int32_t* label_len, int B, int Lmax,
                            int32_t* seq_len_out, int* T_out, int* ticket) {
   return audio_batch(__func__, model, featurizer, audio, offsets, rates, labels, label_len, B, Lmax, seq_len_out, T_out, nullptr,
-                     true, ticket);
+                     nullptr, true, ticket);
 }
 
 int nasr_upload_batch_audio_aug(nasr_handle model, nasr_handle featurizer, const float* audio, const int64_t* offsets,
                                 const int32_t* rates, const int32_t* labels, const int32_t* label_len, int B, int Lmax,
                                 int32_t* seq_len_out, int* T_out, const nasr_batch_aug* aug) {
   return audio_batch(__func__, model, featurizer, audio, offsets, rates, labels, label_len, B, Lmax, seq_len_out, T_out, aug,
-                     false, nullptr);
+                     nullptr, false, nullptr);
 }
 
 int nasr_stage_batch_audio_aug(nasr_handle model, nasr_handle featurizer, const float* audio, const int64_t* offsets,
                                const int32_t* rates, const int32_t* labels, const int32_t* label_len, int B, int Lmax,
                                int32_t* seq_len_out, int* T_out, const nasr_batch_aug* aug, int* ticket) {
   return audio_batch(__func__, model, featurizer, audio, offsets, rates, labels, label_len, B, Lmax, seq_len_out, T_out, aug,
-                     true, ticket);
+                     nullptr, true, ticket);
+}
+
+int nasr_upload_batch_audio_wave(nasr_handle model, nasr_handle featurizer, const float* audio, const int64_t* offsets,
+                                 const int32_t* rates, const int32_t* labels, const int32_t* label_len, int B, int Lmax,
+                                 int32_t* seq_len_out, int* T_out, const nasr_batch_aug* aug, const nasr_wave_aug* wave) {
+  return audio_batch(__func__, model, featurizer, audio, offsets, rates, labels, label_len, B, Lmax, seq_len_out, T_out, aug,
+                     wave, false, nullptr);
+}
+
+int nasr_stage_batch_audio_wave(nasr_handle model, nasr_handle featurizer, const float* audio, const int64_t* offsets,
+                                const int32_t* rates, const int32_t* labels, const int32_t* label_len, int B, int Lmax,
+                                int32_t* seq_len_out, int* T_out, const nasr_batch_aug* aug, const nasr_wave_aug* wave,
+                                int* ticket) {
+  return audio_batch(__func__, model, featurizer, audio, offsets, rates, labels, label_len, B, Lmax, seq_len_out, T_out, aug,
+                     wave, true, ticket);
 }
 
 int nasr_commit_batch(nasr_handle h, int ticket) {

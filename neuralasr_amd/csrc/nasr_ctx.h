@@ -34,6 +34,7 @@
 #include "../../include/nasr.h"
 #include "kernels.h"
 #include "resample.h"
+#include "wave_aug.h"
 
 namespace nasr_impl {
 using namespace nasr;
@@ -606,8 +607,12 @@ struct FzPlan {
   std::vector<int64_t> uoff, foff;     // [n+1] sample offsets (in the buffer the kernels read) and frame offsets
   int64_t S_in = 0;                    // native samples
   size_t mb = 0, meta_bytes = 0, rmeta_bytes = 0;
+  bool wave = false;                   // waveform augmentation: wp is filled, the kernels read its output
+  WavePlan wp;
 };
 int fz_plan(nasr_ctx* eh, FzState& z, const std::string& fn, const int64_t* offsets, const int32_t* rates, int n, FzPlan* p);
+// behind fz_plan: the checks of `wave` (nullable) against the featurizer's banks and its parameters into p; nothing is launched
+int fz_wave_plan(nasr_ctx* eh, FzState& z, const std::string& fn, const nasr_wave_aug* wave, FzPlan* p);
 size_t fz_stage_bytes(const FzPlan& p);
 int fz_produce_slot(nasr_ctx* eh, nasr_ctx* fzh, const FzPlan& p, const float* audio, int Tb, float* dcentre, float* dpad,
                     void* pinned, hipStream_t st);

@@ -44,6 +44,28 @@ class BatchAug(collections.namedtuple('BatchAug', 'static_width time_masks freq_
         return _lib.BatchAug(int(self.static_width), tm.shape[1], fm.shape[1], _ip(tm), _ip(fm)), arrs
 
 
+class WaveAug(collections.namedtuple('WaveAug', 'rir noise noise_off snr_db')):
+    """Waveform augmentation of one batch given as audio (nasr_wave_aug, include/nasr.h): rir int32 [B] (an
+    index into the featurizer's RIR bank, -1: none), noise int32 [B] (into its noise bank, -1: none), noise_off int64 [B]
+    (the clip's first sample) and snr_db float32 [B]; rir or noise may be None (none for the whole batch), noise_off and
+    snr_db only without noise.  The library checks them against the banks."""
+    __slots__ = ()
+
+    def struct(self, B):
+        """(_lib.WaveAug, the arrays it points into - to be kept alive over the call)"""
+        def arr(a, dtype, name):
+            if a is None:
+                return None
+            a = np.ascontiguousarray(a, dtype=dtype).ravel()
+            if a.size != B:
+                raise ValueError('%s must be [B=%d], not %d values' % (name, B, a.size))
+            return a
+        keep = [arr(self.rir, np.int32, 'rir'), arr(self.noise, np.int32, 'noise'), arr(self.noise_off, np.int64, 'noise_off'),
+                arr(self.snr_db, np.float32, 'snr_db')]
+        ptr = [None if a is None else a.ctypes.data_as(POINTER(t)) for a, t in zip(keep, (c_int32, c_int32, c_int64, c_float))]
+        return _lib.WaveAug(*ptr), keep
+
+
 class Engine:
     def __init__(self, feature_size, hidden, num_layers, bidirectional, merge, num_classes, forget_bias=1.0,
                  learning_rate=1e-4, beta1=0.9, beta2=0.999, epsilon=1e-8, device_id=0, stream=None,
@@ -233,13 +255,17 @@ class Engine:
         return (np.ascontiguousarray(feats[:, :, numcontext * numcep:(numcontext + 1) * numcep]),
                 np.ascontiguousarray(feats[:, 0, 0]))
 
-    def _with_aug(self, name, aug, B):
+    def _with_aug(self, name, aug, B, wave=None):
         """(entry point, its arguments behind the plain ones, what those point into - to be kept alive over the call):
-        `name` itself without masks, its _aug sibling with the BatchAug's struct with them"""
-        if aug is None:
+        `name` itself without masks, its _aug sibling with the BatchAug's struct with them, its _wave sibling with a
+        WaveAug (an audio call's waveform augmentation) as well"""
+        if aug is None and wave is None:
             return getattr(self.lib, name), (), None
-        st, keep = aug.struct(B)
-        return getattr(self.lib, name + '_aug'), (byref(st),), (st, keep)
+        st, keep = aug.struct(B) if aug is not None else (None, None)
+        if wave is None:
+            return getattr(self.lib, name + '_aug'), (byref(st),), (st, keep)
+        wst, wkeep = wave.struct(B)
+        return getattr(self.lib, name + '_wave'), (None if st is None else byref(st), byref(wst)), (st, keep, wst, wkeep)
 
     def _ticket(self, rc, ticket):
         """What a stage call returns: its ticket, or None when no staging slot was free; any other failure raises"""
@@ -311,21 +337,23 @@ class Engine:
                 _ip(seq), byref(T), *tail)
         return rc, seq[:B], int(T.value)
 
-    def upload_batch_audio(self, featurizer, audios, labels, label_len, rates=None, aug=None):
+    def upload_batch_audio(self, featurizer, audios, labels, label_len, rates=None, aug=None, wave=None):
         """A batch from audio: `featurizer` (features.Featurizer, same device) makes the MFCC features of the float32
         utterances `audios` (at `rates` Hz, None: all at its samplerate) on the device and writes them into this handle's
         batch slot; the batch is resident afterwards, as after upload_batch.  Returns (seq_len int32 [B], T).
-        `aug` (BatchAug): SpecAugment masks on the normalised frames (nasr_upload_batch_audio_aug)."""
-        fn, tail, keep = self._with_aug('nasr_upload_batch_audio', aug, len(audios))
+        `aug` (BatchAug): SpecAugment masks on the normalised frames (nasr_upload_batch_audio_aug).  `wave` (WaveAug):
+        reverberation and noise from the featurizer's banks on the samples, before the features are made
+        (nasr_upload_batch_audio_wave)."""
+        fn, tail, keep = self._with_aug('nasr_upload_batch_audio', aug, len(audios), wave)
         rc, seq, T = self._audio_call(fn, featurizer, audios, labels, label_len, rates, *tail)
         self._ck(rc)
         return seq, T
 
-    def stage_batch_audio(self, featurizer, audios, labels, label_len, rates=None, aug=None):
+    def stage_batch_audio(self, featurizer, audios, labels, label_len, rates=None, aug=None, wave=None):
         """upload_batch_audio's staging half (stage_batch): copies and front-end kernels on the copy stream while the
         current step runs.  Returns (seq_len, T, ticket); ticket is None when no staging slot is free."""
         ticket = c_int(-1)
-        fn, tail, keep = self._with_aug('nasr_stage_batch_audio', aug, len(audios))
+        fn, tail, keep = self._with_aug('nasr_stage_batch_audio', aug, len(audios), wave)
         rc, seq, T = self._audio_call(fn, featurizer, audios, labels, label_len, rates, *tail, byref(ticket))
         return seq, T, self._ticket(rc, ticket)
 
@@ -903,9 +931,9 @@ class LasEngine(Engine):
         self._BU = (B, U)
         self._ck(self.lib.nasr_upload_batch(self.h, _fp(feats), _ip(seq), _ip(labels), _ip(ll), B, T, U))
 
-    def upload_batch_audio(self, featurizer, audios, labels, label_len, rates=None, aug=None):
+    def upload_batch_audio(self, featurizer, audios, labels, label_len, rates=None, aug=None, wave=None):
         self._BU = (len(audios), 0 if labels is None else np.asarray(labels).reshape(len(audios), -1).shape[1])
-        return Engine.upload_batch_audio(self, featurizer, audios, labels, label_len, rates, aug)
+        return Engine.upload_batch_audio(self, featurizer, audios, labels, label_len, rates, aug, wave)
 
     def align(self, *a, **k):
         raise NotImplementedError('forced alignment walks a CTC lattice; the LAS network has none')

@@ -217,9 +217,12 @@ class AudioBatch:
     the frame counts - seq_len and the padded length T - are the library's host-side arithmetic.  `shape` is the shape
     the padded feature array would have.  time_masks [B, nt, 2] / freq_masks [B, nf, 2] (int32, optional): the
     SpecAugment masks a TRAINING step applies to the normalised frames on the device (augment.py, DESIGN.md §13);
-    validate / evaluate / decode / align ignore them."""
+    validate / evaluate / decode / align ignore them.  rir / noise (int32 [B], -1: none), noise_off (int64 [B]) and
+    snr_db (float32 [B]), all optional: the waveform augmentation of a TRAINING step (nasr_wave_aug), indices
+    into the banks that the network's featurizer holds; ignored like the masks everywhere else."""
 
-    def __init__(self, samplerate, audios, rates=None, width=0, time_masks=None, freq_masks=None):
+    def __init__(self, samplerate, audios, rates=None, width=0, time_masks=None, freq_masks=None, rir=None, noise=None,
+                 noise_off=None, snr_db=None):
         self.samplerate = int(samplerate)
         self.audios = Featurizer._utterances(audios)
         self.rates = None if rates is None else [int(r) for r in rates]
@@ -238,6 +241,20 @@ class AudioBatch:
         self.shape = (len(self.audios), max(frames), int(width))
         self.time_masks = self._masks(time_masks, 'time_masks')
         self.freq_masks = self._masks(freq_masks, 'freq_masks')
+        self.rir = self._per_utt(rir, np.int32, 'rir')
+        self.noise = self._per_utt(noise, np.int32, 'noise')
+        self.noise_off = self._per_utt(noise_off, np.int64, 'noise_off')
+        self.snr_db = self._per_utt(snr_db, np.float32, 'snr_db')
+        if self.noise is not None and (self.noise_off is None or self.snr_db is None):
+            raise ValueError('noise needs noise_off and snr_db')
+
+    def _per_utt(self, a, dtype, name):
+        if a is None:
+            return None
+        a = np.ascontiguousarray(a, dtype=dtype).ravel()
+        if a.size != len(self.audios):
+            raise ValueError('%s must hold %d values, not %d' % (name, len(self.audios), a.size))
+        return a
 
     def _masks(self, m, name):
         if m is None:
@@ -254,14 +271,22 @@ class AudioBatch:
         from .engine import BatchAug
         return BatchAug(int(static_width), self.time_masks, self.freq_masks)
 
+    def wave(self):
+        """the waveform augmentation as the engine's audio calls take it (engine.WaveAug), or None without any"""
+        if self.rir is None and self.noise is None:
+            return None
+        from .engine import WaveAug
+        return WaveAug(self.rir, self.noise, self.noise_off, self.snr_db)
+
     def __len__(self):
         return len(self.audios)
 
     def shard(self, lo, hi):
         """utterances [lo, hi) as a batch of their own, padded to ITS longest utterance"""
-        return AudioBatch(self.samplerate, self.audios[lo:hi], None if self.rates is None else self.rates[lo:hi],
-                          self.shape[2], None if self.time_masks is None else self.time_masks[lo:hi],
-                          None if self.freq_masks is None else self.freq_masks[lo:hi])
+        def cut(a):
+            return None if a is None else a[lo:hi]
+        return AudioBatch(self.samplerate, self.audios[lo:hi], cut(self.rates), self.shape[2], cut(self.time_masks),
+                          cut(self.freq_masks), cut(self.rir), cut(self.noise), cut(self.noise_off), cut(self.snr_db))
 
 
 class Featurizer:
@@ -337,6 +362,48 @@ class Featurizer:
                                     offsets.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)),
                                     r.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), n,
                                     out.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), out.size)
+        _lib.check(self.lib, self.h, rc)
+        cut = np.cumsum([0] + lens)
+        return [out[cut[k]:cut[k + 1]] for k in range(n)]
+
+    def _set_bank(self, fn, arrays):
+        arrays = [np.ascontiguousarray(a, dtype=np.float32).reshape(-1) for a in arrays]
+        n = len(arrays)
+        offsets = np.zeros(n + 1, dtype=np.int64)
+        offsets[1:] = np.cumsum([a.size for a in arrays])
+        flat = np.concatenate(arrays) if n else np.zeros(1, np.float32)
+        _lib.check(self.lib, self.h, fn(self.h, flat.ctypes.data_as(ctypes.POINTER(ctypes.c_float)),
+                                        offsets.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), n))
+
+    def set_noise(self, clips):
+        """The noise bank of the waveform augmentation: float32 clips at `samplerate`, uploaded once; an
+        empty list frees it."""
+        self._set_bank(self.lib.nasr_featurizer_set_noise, clips)
+        self.n_clips = len(clips)
+
+    def set_rirs(self, rirs):
+        """The bank of room impulse responses, as they are convolved (augment.prepare_rir makes them): at most 8192 taps
+        each; an empty list frees it."""
+        self._set_bank(self.lib.nasr_featurizer_set_rirs, rirs)
+        self.n_rirs = len(rirs)
+
+    def augment_audio(self, audios, rates=None, wave=None):
+        """resample() followed by the waveform augmentation `wave` (engine.WaveAug or None) on the device: the list of
+        float32 waveforms at `samplerate` that the spectral kernel of an upload_batch_audio(..., wave=wave) reads."""
+        audios = self._utterances(audios)
+        n = len(audios)
+        lens = [a.size for a in audios] if rates is None else [m for m, _ in self._lengths(audios, rates)]
+        offsets = np.zeros(n + 1, dtype=np.int64)
+        offsets[1:] = np.cumsum([a.size for a in audios])
+        flat = np.concatenate(audios) if n > 1 else audios[0]
+        r = None if rates is None else np.ascontiguousarray(rates, dtype=np.int32)
+        st, keep = wave.struct(n) if wave is not None else (None, None)
+        out = np.empty(int(sum(lens)), dtype=np.float32)
+        rc = self.lib.nasr_augment_audio(self.h, flat.ctypes.data_as(ctypes.POINTER(ctypes.c_float)),
+                                         offsets.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)),
+                                         None if r is None else r.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), n,
+                                         None if st is None else ctypes.byref(st),
+                                         out.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), out.size)
         _lib.check(self.lib, self.h, rc)
         cut = np.cumsum([0] + lens)
         return [out[cut[k]:cut[k + 1]] for k in range(n)]

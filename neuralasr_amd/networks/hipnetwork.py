@@ -105,6 +105,8 @@ class HipNetwork(Network):
         self._reducer = None
         self._staged = {}                       # id(mfccs) -> (ticket, weakref to mfccs): batches stage_batch() sent ahead
         self._staged_lock = threading.Lock()
+        self._banks_lock = threading.Lock()     # the featurizer's noise and RIR banks are set once (_wave)
+        self._banks_set = False
         self._pending = None                    # the batch of the last fast-path step, until that step is known not to be void
         self._begun = None                      # begin_step() without its finish_step() yet
         self._pool = None                       # host threads that decode the steps' logits (train_ler_decoder = 'beam')
@@ -239,17 +241,32 @@ class HipNetwork(Network):
                              'length of the WHOLE batch: use features with num_gpus > 1 on this network')
         return AudioBatch(self.config.samplerate, audios, rates, self.config.feature_size)
 
-    def _upload_audio(self, b, labels=None, labels_len=None, aug=None):
-        self.engine.upload_batch_audio(self.featurizer(), b.audios, labels, labels_len, b.rates, aug)
+    def _wave(self, b):
+        """The waveform augmentation that a TRAINING batch carries (engine.WaveAug), or None; the
+        featurizer gets the banks of config.noise_list / config.rir_list before the first such batch."""
+        wave = b.wave()
+        if wave is not None:
+            with self._banks_lock:
+                if not self._banks_set:
+                    from ..augment import load_banks
+                    fz = self.featurizer()
+                    noise, rirs = load_banks(self.config, fz)
+                    fz.set_noise(noise)
+                    fz.set_rirs(rirs)
+                    self._banks_set = True
+        return wave
+
+    def _upload_audio(self, b, labels=None, labels_len=None, aug=None, wave=None):
+        self.engine.upload_batch_audio(self.featurizer(), b.audios, labels, labels_len, b.rates, aug, wave)
 
     def _upload(self, f, l, s, ll, training=True):
         """One tower's shard made the resident batch, the synchronous way; the only place that knows the kinds of batch.
         Audio goes through the GPU front end, features cross as they are.  training: a training step's upload - audio with
-        the batch's SpecAugment masks when it carries any, features as their centre slice where _context() allows it
+        the batch's SpecAugment masks and waveform augmentation when it carries any, features as their centre slice where _context() allows it
         (inference uploads the whole stacked array, as engine.forward / loss / greedy_decode / align do)."""
         ctx = self._context() if training else 0
         if isinstance(f, AudioBatch):
-            self._upload_audio(f, l, ll, f.aug(self.config.numcep) if training else None)
+            self._upload_audio(f, l, ll, f.aug(self.config.numcep) if training else None, self._wave(f) if training else None)
         elif not (ctx and self.engine.upload_batch_context(f, s, l, ll, ctx, self._frame_width())):
             self.engine.upload_batch(f, s, l, ll)
 
@@ -462,7 +479,8 @@ class HipNetwork(Network):
             return False                        # towers time-sliced on one GPU: each upload replaces the resident batch
         f, l, s, ll = take_shard(mfccs, labels, seq_len, labels_len, n, mine[0])
         if isinstance(f, AudioBatch):
-            ticket = self.engine.stage_batch_audio(self.featurizer(), f.audios, l, ll, f.rates, f.aug(self.config.numcep))[2]
+            ticket = self.engine.stage_batch_audio(self.featurizer(), f.audios, l, ll, f.rates, f.aug(self.config.numcep),
+                                                   self._wave(f))[2]
         else:
             ticket = self.engine.stage_batch(f, s, l, ll, self._context(), self._frame_width())
         if ticket is None:

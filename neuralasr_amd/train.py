@@ -130,9 +130,9 @@ def main(argv=None):
         dataTrain, dataValid = audio_datasets(args.config, config)
     else:
         if config.augment_on:
-            raise ValueError('the augmentation keys (spec_time_masks, spec_freq_masks, speed_perturb) need --from-audio: the '
-                             'masks and the perturbed rates are applied where the GPU makes the features; pickled features '
-                             'are not masked')
+            raise ValueError('the augmentation keys (spec_time_masks, spec_freq_masks, speed_perturb, noise_list, rir_list) need '
+                             '--from-audio: the masks, the perturbed rates, the noise and the reverberation are applied where the '
+                             'GPU makes the features; pickled features are not masked')
         dataTrain = DataSet(config.train_input, config)
         dataValid = None
         if config.test_input:
@@ -145,7 +145,8 @@ def main(argv=None):
 def audio_datasets(configfile, config):
     """--from-audio: the training and the validation set of the [MFCC Featurizer] input CSV as train_model reads them.
     The batches hold audio (features.AudioBatch); HipNetwork stages and uploads them through the GPU front end.  With an
-    augmentation key switched on the training feed draws speed factors and SpecAugment masks (augment.py)."""
+    augmentation key switched on the training feed draws speed factors, SpecAugment masks, noise clips and room impulse
+    responses (augment.py)."""
     from .audio_dataset import AudioDataSet, AudioFeed
     if config.rand_shift > 0:
         raise ValueError('--from-audio cannot be combined with rand_shift > 0 (rand_shift=%d): the roll-and-crop leaves real '

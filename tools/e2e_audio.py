@@ -6,7 +6,9 @@ utterances: synthetic WAVs at 16 kHz, numcep 26, numcontext 10, the 3x500 bidire
     python tools/e2e_audio.py [utterances=64] [epochs=4] [seconds=5] [batch=16] [augment=0]
 
 augment=1: the loop from audio without and with the augmentation keys (2 time masks up to 40 frames, 2 frequency masks up
-to 7 columns, speed_perturb=0.9,1.0,1.1) in the place of the pickled loop."""
+to 7 columns, speed_perturb=0.9,1.0,1.1) in the place of the pickled loop.  augment=2: without and with
+the waveform keys (three noise clips at 0 to 20 dB and three 4000-tap RIRs, every utterance gets both).
+Every leg also prints the persistent recurrence's (aborts, re-arms) of its handle (nasr_get_persist_stats)."""
 import os
 import shutil
 import sys
@@ -60,7 +62,7 @@ def main():
     epochs = int(sys.argv[2]) if len(sys.argv) > 2 else 4
     seconds = float(sys.argv[3]) if len(sys.argv) > 3 else 5.0
     batch = int(sys.argv[4]) if len(sys.argv) > 4 else 16
-    augment = len(sys.argv) > 5 and int(sys.argv[5]) != 0
+    augment = int(sys.argv[5]) if len(sys.argv) > 5 else 0
     out = tempfile.mkdtemp(prefix='nasr_e2e_audio_')
     try:
         rs = np.random.RandomState(7)
@@ -82,6 +84,21 @@ def main():
         preprocess_mfcc.main([cfgp])
         legs = (('pickled features (DataSet)', False), ('from audio (AudioDataSet)', True),
                 ('pickled features, again', False), ('from audio, again', True))
+        if augment == 2:
+            from neuralasr_amd.augment import prepare_rir
+            for kind in ('noise', 'rir'):
+                names = []
+                for i in range(3):
+                    a = 0.1 * rs.randn(3 * 16000 + 1000 * i)
+                    if kind == 'rir':
+                        a = 0.9 * prepare_rir(rs.randn(4000) * np.exp(-np.arange(4000) / 800.0))
+                    names.append(os.path.join(out, '%s%d.wav' % (kind, i)))
+                    write_wav16(names[-1], a, 16000)
+                with open(os.path.join(out, kind + '.lst'), 'w') as fh:
+                    fh.write('\n'.join(names) + '\n')
+            with open(cfga, 'w') as fh:
+                keys = 'noise_list=%s/noise.lst\nnoise_snr=0,20\nrir_list=%s/rir.lst\naugment_seed=1\n' % (out, out)
+                fh.write(CONFIG % dict(out=out, epochs=epochs, batch=batch, keys=keys))
         if augment:
             legs = (('from audio (AudioDataSet)', True), ('from audio, augmented', cfga),
                     ('from audio, again', True), ('from audio, augmented, again', cfga))
@@ -105,11 +122,13 @@ def main():
                 return net
             cfg.load_network = load.__get__(cfg)
             net = train_mod.train_model(data, None, cfg)
+            persist = net.engine.persist_stats()
             net.engine.close()
             gaps = np.diff(np.asarray(stamps)) * 1e3
-            print('%-34s median %.3f ms, mean %.3f ms per step over %d steps after the first epoch (%d x %.1f s per batch)'
+            print('%-34s median %.3f ms, mean %.3f ms per step over %d steps after the first epoch (%d x %.1f s per batch); '
+                  'persistent recurrence (aborts, re-arms) %r'
                   % (label, float(np.median(gaps[steps_per_epoch:])), float(gaps[steps_per_epoch:].mean()),
-                     len(gaps) - steps_per_epoch, batch, seconds), flush=True)
+                     len(gaps) - steps_per_epoch, batch, seconds, persist), flush=True)
     finally:
         shutil.rmtree(out, ignore_errors=True)
 
