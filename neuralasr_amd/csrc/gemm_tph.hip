@@ -20,6 +20,7 @@
 #include "kernels.h"
 
 #include <cstdlib>
+#include <type_traits>
 
 namespace nasr {
 
@@ -73,6 +74,22 @@ __device__ __forceinline__ void emit_h2(const float (&x)[8], float s, unsigned c
   }
   *reinterpret_cast<f16x8*>(dst) = p1;
   *reinterpret_cast<f16x8*>(dst + HTB) = p2;
+}
+
+// Pins the issue order of one scheduling region that holds NMF MFMAs and NRD < NMF LDS reads: one MFMA, one read, ...
+// until the reads are out, then the remaining MFMAs.  The reads lead because hipcc waits for ALL of them (lgkmcnt(0)) in
+// front of the first MFMA that uses one, whichever fragment that is: with NMF - NRD MFMAs (twelve 32-cycle ones for a
+// 128-row wave tile) between the last read and that wait, it finds them retired.  Compile time only:
+// sched_group_barrier tells hipcc's scheduler what to emit next, it is no instruction.
+template <int NMF, int NRD, int R = 0>
+__device__ __forceinline__ void pin_reads_among_mfmas() {
+  if constexpr (R < NRD) {
+    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);             // MFMA
+    __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);             // DS read
+    pin_reads_among_mfmas<NMF, NRD, R + 1>();
+  } else {
+    __builtin_amdgcn_sched_group_barrier(0x008, NMF - NRD, 0);
+  }
 }
 
 }  // namespace
@@ -453,59 +470,138 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN + 3) / 4) void gemm_tph_kern
     return c;
   };
 
+  // The k-loop.  Two fragment sets live in registers: the 2 TMW + 4 ds_read_b128 of a step's SECOND k-block are issued among
+  // the 6 TMW MFMAs of its first, one read behind each of the first MFMAs (pin_reads_among_mfmas), so the one LDS wait the
+  // second k-block keeps is 4 TMW - 4 MFMAs behind its last read.  With one fragment set hipcc read six fragments, waited,
+  // and fed each later group of six MFMAs from two reads with an lgkmcnt(0) directly behind them: four bare LDS waits per
+  // k-block, at the same moment in both waves of a SIMD.  What stays exposed is the first k-block's reads behind the
+  // step barrier.  Per accumulator the products stay x1 y0, x0 y1, x0 y0 over ascending k-blocks: not a bit changes.
+  // The synchronisation is the old one: vmcnt(0) + barrier in front of a step's reads, the next step's DMA behind it.
+  // (Also built and measured, not kept: the barrier moved between the two k-blocks, the next step's first reads under the
+  // second k-block's MFMAs.  1-3 % faster per launch, about 1 % SLOWER per training step - DESIGN.md 4.2.)
+  struct Frag { f16x8 a[TMW][2], b[2][2]; };
+  auto load_frag = [&](Frag& f, int buf, int kk) {         // in the order mfma_block takes them
+    const unsigned char* base = lds + buf * BUFB + kk * (NRB * 2 * HTB) + foff;
+#pragma unroll
+    for (int i = 0; i < TMW; ++i) {
+#pragma unroll
+      for (int q = 0; q < 2; ++q) f.a[i][q] = *reinterpret_cast<const f16x8*>(base + ((wm * TMW + i) * 2 + q) * HTB);
+      if (i == 0) {
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+          for (int q = 0; q < 2; ++q) f.b[j][q] = *reinterpret_cast<const f16x8*>(base + ((NA + wn * 2 + j) * 2 + q) * HTB);
+      }
+    }
+  };
+  auto mfma_block = [&](const Frag& f) {
+#pragma unroll
+    for (int i = 0; i < TMW; ++i)
+#pragma unroll
+      for (int j = 0; j < 2; ++j) acc[i][j] = chain3(acc[i][j], f.a[i], f.b[j]);
+  };
   if (kb0 < kb1) issue(kb0, 0);
   for (int kb = kb0; kb < kb1; kb += 2) {
     const int buf = ((kb - kb0) >> 1) & 1;
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
-    if (kb + 2 < kb1) issue(kb + 2, buf ^ 1);   // (issued after the first fragment reads instead: 2 % slower)
-#pragma unroll
-    for (int kk = 0; kk < 2; ++kk) {
-      f16x8 a[TMW][2], b[2][2];
-      const unsigned char* base = lds + buf * BUFB + kk * (NRB * 2 * HTB) + foff;
-#pragma unroll
-      for (int i = 0; i < TMW; ++i)
-#pragma unroll
-        for (int q = 0; q < 2; ++q) a[i][q] = *reinterpret_cast<const f16x8*>(base + ((wm * TMW + i) * 2 + q) * HTB);
-#pragma unroll
-      for (int j = 0; j < 2; ++j)
-#pragma unroll
-        for (int q = 0; q < 2; ++q) b[j][q] = *reinterpret_cast<const f16x8*>(base + ((NA + wn * 2 + j) * 2 + q) * HTB);
-#pragma unroll
-      for (int i = 0; i < TMW; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) acc[i][j] = chain3(acc[i][j], a[i], b[j]);
-    }
+    if (kb + 2 < kb1) issue(kb + 2, buf ^ 1);
+    Frag f0, f1;
+    load_frag(f0, buf, 0);
+    __builtin_amdgcn_sched_barrier(0);         // these reads stay in front: the first MFMAs need them
+    load_frag(f1, buf, 1);
+    mfma_block(f0);
+    pin_reads_among_mfmas<6 * TMW, 2 * TMW + 4>();
+    mfma_block(f1);
   }
 
   const int li = lane & 31, lh = lane >> 5;
   const float* ainv = p.a_inv + (bz ? p.ainv_bstride : 0);
   const float* binv = p.b_inv + (bz ? p.binv_bstride : 0);
+  if constexpr (NWV == 3) {
+    // <4,1,3> keeps the plain epilogue: the one below takes it from 272 to 376 registers, and beside a 224-register wave of
+    // the persistent BPTT a SIMD has 288 left.  Its stores are under the BPTT launch, off the step's critical path.
 #pragma unroll
-  for (int mi = 0; mi < TMW; ++mi)
+    for (int mi = 0; mi < TMW; ++mi)
 #pragma unroll
-    for (int ni = 0; ni < 2; ++ni) {
-      const int col = n0 + wn * 64 + 32 * ni + li;
-      if (col >= p.N) continue;
-      const float bv = (p.bias && p.split_k == 1) ? p.bias[col] : 0.f;
-      const float sb = binv[col];
+      for (int ni = 0; ni < 2; ++ni) {
+        const int col = n0 + wn * 64 + 32 * ni + li;
+        if (col >= p.N) continue;
+        const float bv = (p.bias && p.split_k == 1) ? p.bias[col] : 0.f;
+        const float sb = binv[col];
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const int row = m0 + wm * (32 * TMW) + 32 * mi + (r & 3) + 8 * (r >> 2) + 4 * lh;
+          if (row >= p.M) continue;
+          const float v = acc[mi][ni][r] * (ainv[row] * sb);        // powers of two: exact
+          if (p.split_k > 1) p.slabs[((size_t)bzz * p.M + row) * p.N + col] = v;
+          else p.C[(size_t)bz * p.c_bstride + (size_t)row * p.ldc + col] = v + bv;
+        }
+      }
+    return;
+  }
+  // The epilogue: C (or this slice's slab) = acc * (1/s_row * 1/s_col) (+ bias).  A wave tile that lies wholly inside M x N -
+  // all but the last row and column of tiles - takes a straight-line copy (FULL): no bounds test per row, so hipcc counts its
+  // waits and the stores leave back to back.  In the general copy every row sits behind its own exec branch, where hipcc
+  // falls back to vmcnt(0): each store waits for its row's scale AND for the store before it to be acknowledged.  The
+  // split-K / plain choice is made once per copy, not per element.  What a 32-row block's stores need (the inverse scales of
+  // this lane's 16 rows, CMAP: their target rows) is loaded one block ahead of them; the compiler fences keep hipcc from
+  // hoisting all 16 TMW loads and their addresses to the top, which spills.
+  float sbv[2], bvv[2];
+#pragma unroll
+  for (int ni = 0; ni < 2; ++ni) {
+    const int col = min(n0 + wn * 64 + 32 * ni + li, p.N - 1);
+    sbv[ni] = binv[col];
+    bvv[ni] = (p.bias && p.split_k == 1) ? p.bias[col] : 0.f;
+  }
+  const int row0 = m0 + wm * (32 * TMW) + 4 * lh, col0 = n0 + wn * 64 + li;
+  auto store_tile = [&](auto split_c, auto full_c) {
+    constexpr bool SPLIT = decltype(split_c)::value, FULL = decltype(full_c)::value;
+    float* const out = SPLIT ? p.slabs + (size_t)bzz * p.M * p.N : p.C + (size_t)bz * p.c_bstride;
+    const size_t ld = SPLIT ? (size_t)p.N : (size_t)p.ldc;
+    float sa[TMW][16];
+    int orow[TMW][16];
+    auto load_rows = [&](int mi) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int row = m0 + wm * (32 * TMW) + 32 * mi + (r & 3) + 8 * (r >> 2) + 4 * lh;
-        if (row >= p.M) continue;
-        const float v = acc[mi][ni][r] * (ainv[row] * sb);        // powers of two: exact
-        if (p.split_k > 1) {
-          p.slabs[((size_t)bzz * p.M + row) * p.N + col] = v;
-        } else {
-          if constexpr (CMAP) {
-            const int orow = p.c_map[row];
-            if (orow >= 0) p.C[(size_t)bz * p.c_bstride + (size_t)orow * p.ldc + col] = v + bv;
+        const int row = row0 + 32 * mi + (r & 3) + 8 * (r >> 2);
+        const int rc = FULL ? row : min(row, p.M - 1);
+        sa[mi][r] = ainv[rc];
+        if constexpr (CMAP && !SPLIT) orow[mi][r] = p.c_map[rc];
+      }
+    };
+    load_rows(0);
+#pragma unroll
+    for (int mi = 0; mi < TMW; ++mi) {
+      if (mi + 1 < TMW) load_rows(mi + 1);
+      asm volatile("" ::: "memory");
+#pragma unroll
+      for (int ni = 0; ni < 2; ++ni) {
+        const int col = col0 + 32 * ni;
+        if (!FULL && col >= p.N) continue;
+        const float bv = bvv[ni], sb = sbv[ni];
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const int row = row0 + 32 * mi + (r & 3) + 8 * (r >> 2);
+          if (!FULL && row >= p.M) continue;
+          const float v = acc[mi][ni][r] * (sa[mi][r] * sb);        // powers of two: exact
+          if constexpr (SPLIT) {
+            out[(size_t)row * ld + col] = v;
+          } else if constexpr (CMAP) {
+            if (orow[mi][r] >= 0) out[(size_t)orow[mi][r] * ld + col] = v + bv;
           } else {
-            p.C[(size_t)bz * p.c_bstride + (size_t)row * p.ldc + col] = v + bv;
+            out[(size_t)row * ld + col] = v + bv;
           }
         }
       }
+      asm volatile("" ::: "memory");
     }
+  };
+  const bool full = m0 + (wm + 1) * (32 * TMW) <= p.M && n0 + (wn + 1) * 64 <= p.N;      // wave-uniform
+  using T = std::true_type;
+  using F = std::false_type;
+  if (p.split_k > 1) { if (full) store_tile(T{}, T{}); else store_tile(T{}, F{}); }
+  else { if (full) store_tile(F{}, T{}); else store_tile(F{}, F{}); }
 }
 
 constexpr int TPH_LDS_SIDE = 2 * 40 * HTB;     // <4,1,3>: (4 + 6) row blocks x 2 k-blocks x 2 parts, two buffers
@@ -528,6 +624,8 @@ int gemm_tph_pick_split(int M, int N, int K, int nbatch) {
   const int tm = gemm_tp_tile_rows(M), tn = 256;
   const int tiles = ((M + tm - 1) / tm) * ((N + tn - 1) / tn) * (nbatch > 1 ? 2 : 1);
   const int kbs = (K + 15) / 16;
+  // (kstep was measured on the kernel before its fragment prefetch and its straight-line epilogue; it is KEPT, not
+  // re-measured: another constant picks other splits, and a split is a summation order - the gradients' bits)
   const double kstep = 1.3e-6 * tm / 256.0;     // one step = two k-blocks of one block
   const double slab = (double)(nbatch > 1 ? 2 : 1) * M * N * 8.0 / 4e12 / kstep;
   int best = 1;

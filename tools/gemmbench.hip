@@ -1,12 +1,34 @@
 // gemmbench.hip — times the GEMM shapes of the training step (B 16, T 500, H 500, F 546).
-// hipcc --offload-arch=gfx950 -O3 -std=c++17 tools/gemmbench.hip -o tools/sb_gemm
-#include "../neuralasr_amd/csrc/gemm.hip"
-#include "../neuralasr_amd/csrc/gemm_tph.hip"
+// hipcc --offload-arch=gfx950 -O3 -std=c++17 tools/gemmbench.hip -o tools/sb_gemm -ldl
+//
+// `sb_gemm --ab [reps] name=lib.so ...`: the plane GEMM (gemm_tph.hip) of this tree against other builds of it, ALTERNATING
+// in one process on one device - the only way two kernels compare (devices differ by up to 12 % on MFMA-dense loops).
+// A build to compare against is this file compiled as a library around another copy of gemm_tph.hip, e.g. the parent's:
+//   git show HEAD~1:neuralasr_amd/csrc/gemm_tph.hip > /tmp/parent/gemm_tph.hip
+//   hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -shared -Wl,-Bsymbolic -DGEMMBENCH_LIB \
+//         -DGEMM_TPH_SRC='"/tmp/parent/gemm_tph.hip"' -Ineuralasr_amd/csrc tools/gemmbench.hip -o tools/sb_gemm_parent.so
+//   tools/sb_gemm --ab 5 parent=tools/sb_gemm_parent.so
+// Shapes: the flagship step's (xproj, dx, dWx, the two-direction dU with its shifts, the side form of the weight gradients)
+// and DeepSpeech's (B 32, 2048 wide); operand planes hold random halves of the magnitudes real planes have.
+#ifndef GEMM_TPH_SRC
+#define GEMM_TPH_SRC "../neuralasr_amd/csrc/gemm_tph.hip"
+#endif
+#ifdef GEMMBENCH_LIB
+#include GEMM_TPH_SRC
 #include "../neuralasr_amd/csrc/optim.hip"
+extern "C" int gb_prepare() { return (int)nasr::gemm_tph_prepare(); }
+extern "C" void gb_launch(const nasr::GemmTPHDesc* g, hipStream_t st) { nasr::launch_gemm_tph(*g, st); }
+#else
+#include "../neuralasr_amd/csrc/gemm.hip"
+#include GEMM_TPH_SRC
+#include "../neuralasr_amd/csrc/optim.hip"
+#include <dlfcn.h>
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <string>
 #include <vector>
 using namespace nasr;
 #define CK(x) do { hipError_t e = (x); if (e != hipSuccess) { printf("%s: %s\n", #x, hipGetErrorString(e)); exit(1);} } while (0)
@@ -16,7 +38,102 @@ static float* dev_rand(size_t n) {
   float* d; CK(hipMalloc(&d, n * 4)); CK(hipMemcpy(d, h.data(), n * 4, hipMemcpyHostToDevice));
   return d;
 }
-int main() {
+
+// ---- --ab: this tree's launch_gemm_tph and the libraries' gb_launch, alternating
+// plane halves: part 0 tiles uniform in +-2^15 (a row's maximum lands in [2^14, 2^15)), part 1 tiles 2^-11 of that
+__global__ void fill_planes_kernel(_Float16* p, size_t n) {
+  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+    unsigned x = (unsigned)i * 2654435761u ^ (unsigned)(i >> 32) * 40503u;
+    x ^= x >> 15; x *= 2246822519u; x ^= x >> 13; x *= 3266489917u; x ^= x >> 16;
+    const float u = (int)(x & 0xffff) - 32768;
+    p[i] = (_Float16)(((i >> 9) & 1) ? u * (1.f / 2048.f) : u * 0.999f);
+  }
+}
+static void gb_local(const GemmTPHDesc* g, hipStream_t st) { launch_gemm_tph(*g, st); }
+static int run_ab(int argc, char** argv) {
+  typedef void (*launch_fn)(const GemmTPHDesc*, hipStream_t);
+  struct Impl { std::string name; launch_fn launch; };
+  std::vector<Impl> impls = {{"tree", gb_local}};
+  int reps = 5;
+  for (int i = 2; i < argc; ++i) {
+    const char* eq = strchr(argv[i], '=');
+    if (!eq) { reps = atoi(argv[i]); continue; }
+    void* so = dlopen(eq + 1, RTLD_NOW | RTLD_LOCAL);
+    if (!so) { printf("%s\n", dlerror()); return 1; }
+    auto prep = (int (*)())dlsym(so, "gb_prepare");
+    auto fn = (launch_fn)dlsym(so, "gb_launch");
+    if (!prep || !fn || prep() != 0) { printf("%s: no gb_prepare / gb_launch\n", eq + 1); return 1; }
+    impls.push_back({std::string(argv[i], eq - argv[i]), fn});
+  }
+  CK(gemm_tph_prepare());
+  struct Case { const char* name; int M, N, K, nbatch, side; };
+  const Case cases[] = {
+      {"xproj 8000x4096x576", 8000, 4096, 576, 1, 0},       {"xproj 8000x4096x1024", 8000, 4096, 1024, 1, 0},
+      {"dx 8000x1024x4096", 8000, 1024, 4096, 1, 0},        {"dWx 1024x4096x8000", 1024, 4096, 8000, 1, 0},
+      {"dWx 576x4096x8000", 576, 4096, 8000, 1, 0},         {"dU 2x512x2048x8000", 512, 2048, 8000, 2, 0},
+      {"side dWx 1024x4096x8000", 1024, 4096, 8000, 1, 1},  {"side dU 2x512x2048x8000", 512, 2048, 8000, 2, 1},
+      {"ds xproj 16000x16384x2048", 16000, 16384, 2048, 1, 0}, {"ds dx 16000x2048x16384", 16000, 2048, 16384, 1, 0},
+      {"ds dWx 2048x16384x16000", 2048, 16384, 16000, 1, 0},   {"ds dU 2x2048x8192x16000", 2048, 8192, 16000, 2, 0},
+  };
+  const size_t plane_bytes = tph_bytes(16384, 16384), c_floats = (size_t)16000 * 16384, slab_floats = (size_t)1 << 28;
+  unsigned char *PA, *PB;
+  float *C, *slabs, *ones;
+  CK(hipMalloc(&PA, plane_bytes)); CK(hipMalloc(&PB, plane_bytes)); CK(hipMalloc(&C, c_floats * 4)); CK(hipMalloc(&slabs, slab_floats * 4));
+  CK(hipMalloc(&ones, 16384 * 4));
+  hipStream_t st; CK(hipStreamCreate(&st));
+  hipLaunchKernelGGL(fill_planes_kernel, dim3(4096), dim3(256), 0, st, (_Float16*)PA, plane_bytes / 2);
+  hipLaunchKernelGGL(fill_planes_kernel, dim3(4096), dim3(256), 0, st, (_Float16*)PB + 512, plane_bytes / 2 - 512);
+  launch_fill(ones, 1.f, 16384, st);
+  CK(hipStreamSynchronize(st)); CK(hipGetLastError());
+  hipEvent_t a, b; CK(hipEventCreate(&a)); CK(hipEventCreate(&b));
+  const int nl = 10;
+  const char* only = getenv("GEMMBENCH_ONLY");         // substring of the case names to run
+  for (const Case& c : cases) {
+    if (only && !strstr(c.name, only)) continue;
+    GemmTPHDesc g{};
+    const int nkb = (c.K + 15) / 16;
+    g.A = PA; g.B = PB; g.C = C; g.M = c.M; g.N = c.N; g.K = c.K; g.nkbA = nkb; g.nkbB = nkb; g.ldc = c.N;
+    g.a_inv = ones; g.b_inv = ones; g.side = c.side != 0; g.nbatch = c.nbatch;
+    if (c.nbatch == 2) {
+      g.a_kshift = -16; g.a_kshift1 = 16;
+      g.a_bstride = (size_t)(c.M / 32) * nkb * 2048; g.b_bstride = (size_t)(c.N / 32) * nkb * 2048;
+      g.c_bstride = (int64_t)c.M * c.N; g.ainv_bstride = c.M; g.binv_bstride = c.N;
+    }
+    g.split_k = gemm_tph_pick_split(c.M, c.N, c.K, c.nbatch); g.slabs = slabs;
+    if ((size_t)g.split_k * c.nbatch * c.M * c.N > slab_floats) { printf("%s: slabs too small\n", c.name); continue; }
+    std::vector<std::vector<float>> us(impls.size());
+    std::vector<float> first;
+    for (int i = 0; i < 2 * nl; ++i)           // clocks settle on the shape before anything is timed
+      for (auto& im : impls) im.launch(&g, st);
+    for (int r = 0; r < reps; ++r)
+      for (size_t k = 0; k < impls.size(); ++k) {
+        for (int i = 0; i < 2; ++i) impls[k].launch(&g, st);
+        CK(hipEventRecord(a, st));
+        for (int i = 0; i < nl; ++i) impls[k].launch(&g, st);
+        CK(hipEventRecord(b, st)); CK(hipEventSynchronize(b)); CK(hipGetLastError());
+        float ms; CK(hipEventElapsedTime(&ms, a, b));
+        us[k].push_back(ms * 1000.f / nl);
+        if (r == 0) {          // every build must give the same bits
+          std::vector<float> h((size_t)c.nbatch * c.M * c.N);
+          CK(hipMemcpy(h.data(), C, h.size() * 4, hipMemcpyDeviceToHost));
+          if (k == 0) first = h;
+          else if (memcmp(first.data(), h.data(), h.size() * 4) != 0) printf("%s: %s DIFFERS from %s\n", c.name, impls[k].name.c_str(), impls[0].name.c_str());
+        }
+      }
+    for (size_t k = 0; k < impls.size(); ++k) {
+      const float lo = *std::min_element(us[k].begin(), us[k].end()), hi = *std::max_element(us[k].begin(), us[k].end());
+      printf("%-26s split %2d  %-8s us/launch min %8.1f max %8.1f  %6.1f TF-equiv  runs:", c.name, g.split_k, impls[k].name.c_str(), lo, hi,
+             2.0 * c.nbatch * c.M * c.N * c.K / lo / 1e6);
+      for (float v : us[k]) printf(" %.1f", v);
+      printf("\n");
+    }
+    fflush(stdout);
+  }
+  return 0;
+}
+
+int main(int argc, char** argv) {
+  if (argc > 1 && !strcmp(argv[1], "--ab")) return run_ab(argc, argv);
   const int R = 8000;
   float* X = dev_rand((size_t)R * 1024);
   float* G = dev_rand((size_t)R * 4096);
@@ -166,3 +283,4 @@ int main() {
   }
   return 0;
 }
+#endif
