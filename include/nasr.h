@@ -476,6 +476,45 @@ int nasr_stream_audio_rows(nasr_handle model, const int64_t* n_samples, const ui
 int nasr_stream_feed_audio(nasr_handle model, const float* audio, const int64_t* offsets, const uint8_t* last, int32_t* rows_out,
                            int* Tc_out, float* logits_out, int64_t logits_rows);
 
+/* ---- streaming the bidirectional networks with a bounded look-ahead -------------------------------
+ * The latency-controlled BiLSTM: a look-ahead session of S slots and R look-ahead frames keeps, per slot, the FORWARD
+ * direction's (c, h) per layer (the layout of nasr_stream_get_state) and up to R held feature rows.  A feed gives slot b
+ * n[b] >= 0 new rows and an optional last[b]; with P = held[b] + n[b] pending rows it emits E = P rows with last[b], else
+ * E = max(0, P - R), and the last P - E rows stay held.  A slot with E = 0 runs nothing; if every slot has E = 0 no pass
+ * runs and the resident batch is kept.  A slot with E > 0 runs its WINDOW, all P pending rows, through the whole network:
+ * dense stages row by row, every layer's forward direction from the saved state (saved again as of row E - 1), every
+ * layer's backward direction from zero at row P - 1 down to row 0; logits are returned for rows 0 .. E-1, and the P - E
+ * look-ahead rows are computed again as the head of the next window.  THE RESULT DEPENDS ON HOW THE INPUT WAS SPLIT INTO
+ * FEEDS: a frame's backward context is between R and R + E - 1 frames.  It is the whole-utterance network (to fp32
+ * tolerance) when one window covers the utterance.  The same feeds give the same bits.  What nasr_stream_open's comment
+ * says about the per-step kernels, the handle's parameters and batch calls between feeds holds here too.
+ * On such a session nasr_stream_reset (the held rows go too), _close, _frames (rows EMITTED) and _get_state (the forward
+ * state) work; nasr_stream_set_state only while no slot holds rows (else NASR_ERR_STATE); nasr_stream_feed is
+ * NASR_ERR_STATE, as nasr_stream_feed_lookahead and nasr_stream_lookahead_rows are on a session of nasr_stream_open.
+ * nasr_stream_attach_audio / _feed_audio / _audio_rows work: the rows the causal front end makes for a feed join the
+ * slot's pending rows on the device, the window rule applies to them, `last` completes the front end's hold-back and
+ * the look-ahead, and rows_out / Tc_out count the rows emitted after both. */
+/* (No counterpart in the reference: tfnetwork.py:179-181 decodes whole utterances.)  Opens a look-ahead session: 1 <= S <= 64
+ * slots, 1 <= R <= 1024 look-ahead frames (else NASR_ERR_ARG), all state zero, nothing held.  NASR_ERR_STATE, with the
+ * reason in nasr_last_error: a unidirectional config (use nasr_stream_open); NASR_MERGE_STACK_RESHAPE (its logits mix frames of
+ * the whole padded batch: no chunk of it is a point in time); a dropout probability > 0; a WaveNet, LAS or featurizer
+ * handle; a second session. */
+int nasr_stream_open_lookahead(nasr_handle h, int S, int R);
+/* (No counterpart in the reference: tfnetwork.py:179-181 decodes whole utterances.)  Host only: what a
+ * nasr_stream_feed_lookahead of n_frames [S] new rows per slot, with last [S] (nullable), would emit now: rows_out [S] = the
+ * E of every slot, *Te_out = their maximum, which sizes logits_out.  NASR_ERR_ARG: an n_frames < 0; NASR_ERR_STATE: a row
+ * or `last` for a slot that has had `last` and no reset.  Nothing changes. */
+int nasr_stream_lookahead_rows(nasr_handle h, const int32_t* n_frames, const uint8_t* last, int32_t* rows_out, int* Te_out);
+/* (No counterpart in the reference: tfnetwork.py:179-181 decodes whole utterances.)  One feed of finished feature rows: feats
+ * [S][Tc][F] (nullable when no slot has a new row), n_frames [S] in [0,Tc], last [S] nullable.  rows_out [S] and *Te_out as
+ * nasr_stream_lookahead_rows gives them; logits_out time-major [Te][S][C] (logits_rows >= Te rows of it), rows
+ * t >= rows_out[b] of slot b unspecified.  Synchronises when a pass runs; the window then replaces the resident batch as a
+ * chunk of nasr_stream_feed does.  After a feed with last[b] the slot waits for nasr_stream_reset.  Refused with nothing
+ * changed - NASR_ERR_ARG: an n_frames[b] outside [0,Tc], logits_rows < Te, a null buffer; NASR_ERR_STATE: a row or `last`
+ * for a slot that has had `last` and no reset, a session that takes samples, a session without look-ahead. */
+int nasr_stream_feed_lookahead(nasr_handle h, const float* feats, const int32_t* n_frames, const uint8_t* last, int Tc,
+                               int32_t* rows_out, int* Te_out, float* logits_out, int64_t logits_rows);
+
 /* The CTC beam search as a state that lives between calls - host only, the procedure and arithmetic of
  * nasr_ctc_beam_search(_lm), which is open + one feed + best + close on this very code: feeding an utterance's frames in
  * any split gives its ids and log-probability bit for bit.  One handle per thread. */

@@ -21,7 +21,10 @@ preprocessing and decoding all read them, so that a model is decoded with the no
 more optional [Parameters] keys switch on the waveform augmentation of `train --from-audio` (augment.py; the
 reference has none): noise_list / rir_list (a file that lists WAV paths, one per line: noise clips, room impulse
 responses), noise_prob / rir_prob (the share of utterances that get one, in [0,1], default 1 when the list is given) and
-noise_snr=lo,hi (dB, lo <= hi, default 10,20); without them nothing changes, and only the training feed reads them."""
+noise_snr=lo,hi (dB, lo <= hi, default 10,20); without them nothing changes, and only the training feed reads them.  One
+more optional [Parameters] key, stream_lookahead (frames, 0..1024, default 0 = off), is the look-ahead with which a
+bidirectional network streams (HipNetwork.stream, decode_wav --stream; the reference decodes whole
+utterances); unidirectional networks ignore it."""
 import importlib
 import math
 from configparser import ConfigParser, ExtendedInterpolation
@@ -76,6 +79,15 @@ class Config(object):
             raise ValueError("'deltas' must be 0, 1 or 2, not %r, in %s" % (deltas, configfile))
         self.deltas = int(deltas)
         self._read_normalization(par, configfile)
+        # frames of look-ahead with which a bidirectional network streams (the reference decodes whole
+        # utterances): 0 = off, unidirectional networks ignore it
+        try:
+            self.stream_lookahead = int(par['stream_lookahead'].strip()) if 'stream_lookahead' in par else 0
+        except ValueError:
+            self.stream_lookahead = -1
+        if not 0 <= self.stream_lookahead <= 1024:
+            raise ValueError("'stream_lookahead' must be an integer in [0,1024], not %r, in %s"
+                             % (par['stream_lookahead'], configfile))
         self.frame_width = self.numcep * (1 + self.deltas)
         self.feature_size = (2 * self.numcontext + 1) * self.frame_width
         self.lm_file = par['lm_file'].strip() if 'lm_file' in par else None
@@ -194,7 +206,7 @@ class Config(object):
         return network_class(self.network)(self, fortraining=fortraining)
 
     def print_config(self):
-        names = ['samplerate', 'numcep', 'numcontext', 'features', 'deltas', 'normalization', 'norm_min_frames', 'rand_shift', 'batch_size', 'epochs', 'learningrate',
+        names = ['samplerate', 'numcep', 'numcontext', 'features', 'deltas', 'normalization', 'norm_min_frames', 'stream_lookahead', 'rand_shift', 'batch_size', 'epochs', 'learningrate',
                  'model_dir', 'start_step', 'report_step', 'num_gpus', 'label_context', 'punc_regex', 'network',
                  'sym_file', 'train_input', 'test_input', 'mfcc_input', 'mfcc_output', 'start_marker', 'end_marker']
         lines = ['']

@@ -359,6 +359,71 @@ void launch_stream_save_state(const float* out, const float* cbuf, const int* n_
   hipLaunchKernelGGL(stream_save_state_kernel, dim3((S * H + 255) / 256), dim3(256), 0, st, out, cbuf, n_frames, state, S, H, Bp, Hp);
 }
 
+// ------------------------------------------------------------------ look-ahead session (nasr_stream.hip)
+// Every slot's window = its held rows, then its new rows; block (t, b) moves pending row t of slot b.  An emitting slot's
+// window goes into the chunk's stacked rows win [S][T][F] (zeros behind it, and in the whole of a slot that emits
+// nothing: its seq_len is 0), and the rows that stay held, pending rows [emit, P), into the OTHER hold buffer: shifted
+// in place they would overlap whenever fewer rows arrive than are held.  win == NULL: no slot emits, the rows only move.
+__global__ __launch_bounds__(256) void la_window_kernel(const float* __restrict__ hold_in, const float* __restrict__ fresh,
+                                                        LaSlots sl, float* __restrict__ win, float* __restrict__ hold_out,
+                                                        int R, int Tc, int T, int F) {
+  const int t = blockIdx.x, b = blockIdx.y;
+  const int held = sl.held[b], P = held + sl.n[b], E = sl.emit[b];
+  const float* src = t < held ? hold_in + ((size_t)b * R + t) * F : t < P ? fresh + ((size_t)b * Tc + (t - held)) * F : nullptr;
+  float* wdst = (win && t < T) ? win + ((size_t)b * T + t) * F : nullptr;
+  float* hdst = (src && t >= E) ? hold_out + ((size_t)b * R + (t - E)) * F : nullptr;   // t - E < P - E <= R
+  for (int i = threadIdx.x; i < F; i += blockDim.x) {
+    const float v = src ? src[i] : 0.f;
+    if (wdst) wdst[i] = E > 0 ? v : 0.f;
+    if (hdst) hdst[i] = v;
+  }
+}
+
+void launch_la_window(const float* hold_in, const float* fresh, const LaSlots& sl, float* win, float* hold_out, int S, int R,
+                      int Tc, int T, int rows, int F, hipStream_t st) {
+  hipLaunchKernelGGL(la_window_kernel, dim3(rows, S), dim3(256), 0, st, hold_in, fresh, sl, win, hold_out, R, Tc, T, F);
+}
+
+// One layer's saved forward state [S][2][H] into what step 0 of a window reads, for both directions (blockIdx.y): the
+// forward direction's h operand image and c as stream_load_state_kernel writes them, zeros for the backward direction -
+// it starts every window anew - and for padded units and padded slots.  Every element is written on every launch.
+__global__ __launch_bounds__(256) void la_load_state_kernel(const float* __restrict__ state, float* __restrict__ himg,
+                                                            float* __restrict__ cimg, int S, int H, int Bp, int Hp) {
+  const int e = blockIdx.x * 256 + threadIdx.x, d = blockIdx.y;
+  if (e >= Bp * Hp) return;
+  const int b = e / Hp, j = e - b * Hp;
+  float c = 0.f, hv = 0.f;
+  if (d == 0 && b < S && j < H) {
+    c = state[((size_t)b * 2 + 0) * H + j];
+    hv = state[((size_t)b * 2 + 1) * H + j];
+  }
+  cimg[(size_t)d * Bp * Hp + e] = c;
+  himg[(size_t)d * Bp * Hp + sw_index(Hp, b >> 4, b & 15, j)] = hv;
+}
+
+// ... and back: the forward direction's state after the last EMITTED row, the forward half of row (emit[b] - 1) * Bp + b
+// of cbuf / out [T * Bp][2 * Hp]; the look-ahead rows behind it are run again by the next window.  A slot that emits
+// nothing keeps what it had.
+__global__ __launch_bounds__(256) void la_save_state_kernel(const float* __restrict__ out, const float* __restrict__ cbuf,
+                                                            LaSlots sl, float* __restrict__ state, int S, int H, int Bp, int DH) {
+  const int e = blockIdx.x * 256 + threadIdx.x;
+  if (e >= S * H) return;
+  const int b = e / H, j = e - b * H;
+  const int E = sl.emit[b];
+  if (E < 1) return;
+  const size_t r = (size_t)(E - 1) * Bp + b;
+  state[((size_t)b * 2 + 0) * H + j] = cbuf[r * DH + j];
+  state[((size_t)b * 2 + 1) * H + j] = out[r * DH + j];
+}
+
+void launch_la_load_state(const float* state, float* himg, float* cimg, int S, int H, int Bp, int Hp, hipStream_t st) {
+  hipLaunchKernelGGL(la_load_state_kernel, dim3((Bp * Hp + 255) / 256, 2), dim3(256), 0, st, state, himg, cimg, S, H, Bp, Hp);
+}
+void launch_la_save_state(const float* out, const float* cbuf, const LaSlots& sl, float* state, int S, int H, int Bp, int Hp,
+                          hipStream_t st) {
+  hipLaunchKernelGGL(la_save_state_kernel, dim3((S * H + 255) / 256), dim3(256), 0, st, out, cbuf, sl, state, S, H, Bp, 2 * Hp);
+}
+
 // ------------------------------------------------------------------ BPTT step
 // grid.x = (Hp/64 output tiles jt) x (Hp/32 K slices ks), blockIdx.x = jt*KSPLIT + ks so the blocks that
 // rebuild the same dG slice share an XCD (ids equal mod 8).  Per block and step:

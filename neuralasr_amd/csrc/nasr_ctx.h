@@ -199,12 +199,25 @@ struct LasStateDelete { void operator()(LasState* s) const; };
 struct FzStream;
 struct FzStreamDelete { void operator()(FzStream* f) const; };
 
-// A stream session (nasr_stream.hip): S concurrent streams on a unidirectional LSTM-family handle.
+// What a look-ahead session keeps beyond the forward state (nasr_stream_open_lookahead).
+struct Lookahead {
+  int R = 0;                         // look-ahead frames
+  DevBuf hold[2];                    // [S][R][F] held feature rows; a feed reads hold[cur] and writes the other one
+  int cur = 0;
+  DevBuf fresh;                      // [S][Tc][F] the feed's new rows: uploaded, or made by the front end
+  std::vector<int32_t> held;         // [S] rows held
+  std::vector<uint8_t> done;         // [S] the slot has had `last` and no reset
+  LaSlots sl{};                      // the feed that is running (run_chunk_steps: which row's state to save)
+};
+
+// A stream session (nasr_stream.hip): S concurrent streams on a unidirectional LSTM-family handle, or (la) on a
+// bidirectional one whose backward direction restarts in every window.
 struct StreamState {
+  std::unique_ptr<Lookahead> la;
   int S = 0;
   std::unique_ptr<FzStream, FzStreamDelete> audio;   // per slot: sample tail, running sums, waiting and recent frames
-  DevBuf state;                      // [L][S][2][H] fp32: c, then h, as of each slot's last frame; zero after open / reset
-  DevBuf cimg;                       // [Bp][Hp]: the layer's saved c as step 0 of a feed reads it
+  DevBuf state;                      // [L][S][2][H] fp32: c, then h, as of each slot's last (emitted) frame; zero after open / reset
+  DevBuf cimg;                       // [D][Bp][Hp]: the layer's saved c as step 0 of a feed reads it
   std::vector<int64_t> frames;       // [S] frames consumed since the slot's reset
   uint64_t uf_seq = ~0ull;           // repack_seq of the per-step operand images the session built itself (see stream_feed)
 };
@@ -678,7 +691,8 @@ int loss_pass(nasr_ctx* h, bool training);
 CtcDims ctc_dims(nasr_ctx* h);
 int ctc_forward(nasr_ctx* h);
 int backward(nasr_ctx* h);
-int fetch_logits(nasr_ctx* h, float* logits_out);
+// rows >= 0: the first `rows` logit frames only
+int fetch_logits(nasr_ctx* h, float* logits_out, int rows = -1);
 
 // ---- nasr_wavenet.hip (the WaveNet handle's side of ensure_shape, forward and backward)
 int wn_ensure_shape(nasr_ctx* h, int B, int T, int Lmax);

@@ -213,18 +213,22 @@ int dense_backward(nasr_ctx* h, int i, const float* X, float* dX) {
 // One layer of a stream chunk: the recurrence over the chunk's T steps on the per-step kernels, whatever kind the handle's
 // batches run on, from the session's saved (c, h) of layer l, which it then replaces by every slot's state at its last
 // frame.  No graph: step 0 is another kernel than the rest, and a chunk is a few dozen launches.
+// A look-ahead session (ss.la): both directions over the window's T steps, the forward one from the saved state, the backward
+// one from zero at each slot's last pending row (seq_len[b] = its window); saved is the forward state after the last emitted row.
 static int run_chunk_steps(nasr_ctx* h, int l, hipStream_t st) {
   StreamState& ss = *h->stream;
   const LstmDims dm{h->T, h->B, h->Bp, h->H, h->Hp, h->D};
-  const size_t sU = (size_t)l * h->Hp * h->N4, hs = (size_t)h->Bp * h->Hp;
+  const size_t sU = (size_t)l * h->D * h->Hp * h->N4, hs = (size_t)h->D * h->Bp * h->Hp;
   float* hst = h->hstate.as<float>();
   float* state = ss.state.as<float>() + (size_t)l * ss.S * 2 * h->H;
   float *g = h->gates[l].as<float>(), *c = h->cbuf[l].as<float>(), *o = h->outb[l].as<float>();
-  launch_stream_load_state(state, hst, ss.cimg.as<float>(), ss.S, h->H, h->Bp, h->Hp, st);
+  if (ss.la) launch_la_load_state(state, hst, ss.cimg.as<float>(), ss.S, h->H, h->Bp, h->Hp, st);
+  else launch_stream_load_state(state, hst, ss.cimg.as<float>(), ss.S, h->H, h->Bp, h->Hp, st);
   launch_lstm_fwd_step_carry(dm, h->Uf + sU, hst, hst + hs, g, c, o, h->seq_p, h->cfg.forget_bias, ss.cimg.as<float>(), st);
   for (int s = 1; s < h->T; ++s)
     launch_lstm_fwd_step(dm, s, h->Uf + sU, hst + (s & 1) * hs, hst + ((s + 1) & 1) * hs, g, c, o, h->seq_p, h->cfg.forget_bias, st);
-  launch_stream_save_state(o, c, h->seq_p, state, ss.S, h->H, h->Bp, h->Hp, st);
+  if (ss.la) launch_la_save_state(o, c, ss.la->sl, state, ss.S, h->H, h->Bp, h->Hp, st);
+  else launch_stream_save_state(o, c, h->seq_p, state, ss.S, h->H, h->Bp, h->Hp, st);
   h->n_fwd_launch += h->T;
   HIPCHK(h, hipGetLastError());
   return NASR_OK;
@@ -538,12 +542,13 @@ int backward(nasr_ctx* h) {
   return NASR_OK;
 }
 
-int fetch_logits(nasr_ctx* h, float* logits_out) {
-  const size_t n = (size_t)h->Tp * h->Bp * h->Cp;
+int fetch_logits(nasr_ctx* h, float* logits_out, int rows) {
+  const int Tr = rows >= 0 ? std::min(rows, h->Tp) : h->Tp;
+  const size_t n = (size_t)Tr * h->Bp * h->Cp;
   std::vector<float> host(n);
   HIPCHK(h, hipMemcpyAsync(host.data(), h->logits.p, n * 4, hipMemcpyDeviceToHost, h->st));
   if (int rc = sync_checked(h)) return rc;
-  for (int t = 0; t < h->Tp; ++t)
+  for (int t = 0; t < Tr; ++t)
     for (int b = 0; b < h->B; ++b)
       memcpy(logits_out + ((size_t)t * h->B + b) * h->C, host.data() + ((size_t)t * h->Bp + b) * h->Cp,
              (size_t)h->C * 4);

@@ -7,7 +7,10 @@ its features are made on the GPU and stay there.  Every other network class take
 are computed over the whole file first: the reference normalises by whole-utterance mean and std (utils.py:29), so frames a
 model trained that way understands exist only then.  With normalization=causal the SAMPLES are fed,
 N * frame_step per feed, and the session's front end normalises as they arrive; a file at another rate than the config's
-is resampled whole on the GPU first and then chunked."""
+is resampled whole on the GPU first and then chunked.
+`--lookahead-frames R`: a bidirectional network (BiLstmConcatCTCNet, BiLstm3x500CTCNet, DeepSpeech without dropout) streams
+with R frames of look-ahead (default: the config key stream_lookahead) on either route; its partial
+hypotheses trail the audio by the chunk plus R frames, and the text depends on the chunking."""
 import argparse
 
 import numpy as np
@@ -42,12 +45,13 @@ def features_of(config, network, path):
                                                           **normalization_of(config)), dtype=np.float32)
 
 
-def decode_stream(config, network, feats, chunk_frames):
+def decode_stream(config, network, feats, chunk_frames, lookahead=None):
     """Feed feats [T, F] to network.stream() chunk_frames at a time: a 'Partial:' line after every chunk whose hypothesis
-    changed, then the usual 'Decoded:' line.  Returns the final text."""
+    changed, then the usual 'Decoded:' line.  Returns the final text.  lookahead: the look-ahead frames of a bidirectional
+    network (None: the config's stream_lookahead)."""
     if chunk_frames < 1:
         raise ValueError('--chunk-frames must be >= 1')
-    rec = network.stream(1)
+    rec = network.stream(1) if lookahead is None else network.stream(1, lookahead=lookahead)
     try:
         last = None
         for t in range(0, len(feats), chunk_frames):
@@ -61,7 +65,7 @@ def decode_stream(config, network, feats, chunk_frames):
     return report(config, np.asarray(ids, dtype=np.int64))
 
 
-def decode_stream_audio(config, network, audio, rate, chunk_frames):
+def decode_stream_audio(config, network, audio, rate, chunk_frames, lookahead=None):
     """Feed the file's SAMPLES to network.stream(), chunk_frames * frame_step at a time (normalization=causal): the same
     'Partial:' and 'Decoded:' lines as decode_stream.  A file at another rate is resampled whole first."""
     if chunk_frames < 1:
@@ -70,7 +74,7 @@ def decode_stream_audio(config, network, audio, rate, chunk_frames):
     if rate != config.samplerate:
         audio = fz.resample([audio], [rate])[0]
     step = chunk_frames * fz.frame_params()[1]
-    rec = network.stream(1)
+    rec = network.stream(1) if lookahead is None else network.stream(1, lookahead=lookahead)
     try:
         prev = None
         for t in range(0, len(audio), step):
@@ -94,9 +98,14 @@ def parse_args(argv=None):
                              'first and then chunked), else the frames of the features computed over the whole file')
     parser.add_argument('--chunk-frames', type=int, default=50,
                         help='frames per chunk with --stream (default 50 = 0.5 s); samples are fed chunk-frames * frame_step at a time')
+    parser.add_argument('--lookahead-frames', type=int, default=None,
+                        help='with --stream on a bidirectional network: frames of right context the backward direction gets '
+                             'beyond the frames a feed emits (overrides the config key stream_lookahead)')
     args = parser.parse_args(argv)
     if args.chunk_frames < 1:
         parser.error('--chunk-frames must be >= 1')
+    if args.lookahead_frames is not None and args.lookahead_frames < 1:
+        parser.error('--lookahead-frames must be >= 1')
     return args
 
 
@@ -110,8 +119,8 @@ def main(argv=None):
         if getattr(config, 'normalization', 'utterance') == 'causal':
             from .features import read_wav_native
             audio, rate = read_wav_native(args.input)
-            return decode_stream_audio(config, network, audio, rate, args.chunk_frames)
-        return decode_stream(config, network, features_of(config, network, args.input), args.chunk_frames)
+            return decode_stream_audio(config, network, audio, rate, args.chunk_frames, args.lookahead_frames)
+        return decode_stream(config, network, features_of(config, network, args.input), args.chunk_frames, args.lookahead_frames)
     if getattr(network, 'takes_audio', False):
         from .features import read_wav_native
         audio, rate = read_wav_native(args.input)

@@ -598,6 +598,42 @@ class Engine:
         assert Tc2.value == Tc and np.array_equal(got, rows)
         return out, got
 
+    # ---- a look-ahead session on a bidirectional network
+    def stream_open_lookahead(self, slots=1, lookahead=1):
+        """Open a look-ahead session: `slots` concurrent streams on a bidirectional (concat) network, the forward
+        direction's (c, h) carried, the backward direction restarted in every feed `lookahead` frames to the right of the
+        rows the feed emits.  Raises the library's message for a network that cannot stream this way."""
+        self._ck(self.lib.nasr_stream_open_lookahead(self.h, int(slots), int(lookahead)))
+        self._stream_slots = int(slots)
+
+    def stream_lookahead_rows(self, n_frames, last=None):
+        """(rows int32 [S], Te): what a stream_feed_lookahead of n_frames[b] new rows per slot would emit now (host only)."""
+        S, fin, fin_p = self._stream_audio_args(n_frames, last)
+        n = _i32(np.asarray([int(x) for x in n_frames])).ravel()
+        rows, Te = np.zeros(S, np.int32), c_int(0)
+        self._ck(self.lib.nasr_stream_lookahead_rows(self.h, _ip(n), fin_p, _ip(rows), byref(Te)))
+        return rows, int(Te.value)
+
+    def stream_feed_lookahead(self, feats, n_frames, last=None):
+        """One feed: feats [S,Tc,F] (Tc may be 0), n_frames [S] in [0,Tc], last[b] true declares slot b's utterance
+        complete.  Returns (logits [Te,S,C], rows int32 [S]): slot b's rows_b emitted rows are logits[:rows_b, b]; Te = 0
+        when the feed emitted nothing."""
+        S, fin, fin_p = self._stream_audio_args(n_frames, last)
+        feats = _f32(feats)
+        F = int(self.cfg.feature_size)
+        if feats.ndim != 3 or feats.shape[0] != S or feats.shape[2] != F:
+            raise ValueError('feats must be [%d, Tc, %d], not %s' % (S, F, feats.shape))
+        Tc = int(feats.shape[1])
+        n = _i32(np.asarray([int(x) for x in n_frames])).ravel()
+        # (the library refuses these too; here they must not size the output array first)
+        rows, Te = self.stream_lookahead_rows(np.clip(n, 0, None), last)
+        out = np.empty((Te, S, self.num_classes), np.float32)
+        got, Te2 = np.zeros(S, np.int32), c_int(0)
+        self._ck(self.lib.nasr_stream_feed_lookahead(self.h, _fp(feats) if feats.size else None, _ip(n), fin_p, Tc, _ip(got),
+                                                     byref(Te2), _fp(out) if out.size else None, Te))
+        assert Te2.value == Te and np.array_equal(got, rows)
+        return out, got
+
     def stream_frames(self):
         out = np.zeros(getattr(self, '_stream_slots', 0), np.int64)
         self._ck(self.lib.nasr_stream_frames(self.h, out.ctypes.data_as(POINTER(c_int64))))

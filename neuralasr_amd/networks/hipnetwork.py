@@ -561,12 +561,21 @@ class HipNetwork(Network):
         hyps = self._decode(mfccs, seq_len, self.decoder, self.language_model())
         return np.asarray([i for h in hyps for i in h], dtype=np.int64)
 
-    def stream(self, slots=1):
+    def stream(self, slots=1, lookahead=None):
         """A stream.StreamingRecognizer on this network: `slots` concurrent streams fed chunk by chunk, the LSTM state
-        carried on the GPU, the hypothesis available after every chunk.  Raises the library's message for
-        a network that cannot stream (bidirectional layers, dropout, WaveNet, LAS)."""
+        carried on the GPU, the hypothesis available after every chunk.  A bidirectional network streams
+        with `lookahead` frames of right context (None: the config's stream_lookahead), a unidirectional
+        one ignores both.  Raises the library's message for a network that cannot stream (stack-reshape merge, dropout,
+        WaveNet, LAS)."""
         from ..stream import StreamingRecognizer
-        return StreamingRecognizer(self, slots)
+        if not int(getattr(getattr(self.engine, 'cfg', None), 'bidirectional', 0)):
+            return StreamingRecognizer(self, slots)
+        if lookahead is None:
+            lookahead = int(getattr(self.config, 'stream_lookahead', 0))
+        if lookahead < 1:
+            raise ValueError('a bidirectional network streams only with a look-ahead: set stream_lookahead (frames, >= 1) '
+                             'under [Parameters] or pass lookahead=')
+        return StreamingRecognizer(self, slots, lookahead=lookahead)
 
     def align(self, mfccs, labels, seq_len, labels_len):
         """Forced alignment: for every utterance (score, [(symbol id, first frame, last frame)] in label

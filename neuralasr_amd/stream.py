@@ -7,7 +7,11 @@ feed() takes the caller's features: the reference normalises by whole-utterance 
 match a model trained that way exist only once the utterance is complete (`decode_wav --stream` then featurizes the whole
 file first and chunks the normalised frames).  feed_audio() takes SAMPLES: with normalization=causal in the config
  the network's featurizer normalises as the audio arrives, the session's front end keeps each slot's sample
-tail and running statistics on the GPU, and the rows a feed makes go straight into the chunk."""
+tail and running statistics on the GPU, and the rows a feed makes go straight into the chunk.
+
+A bidirectional (concat) network streams with a look-ahead: StreamingRecognizer(network, slots, lookahead=R)
+opens a look-ahead session, whose feeds hold each slot's last R rows back for their right context; the beams get the rows a
+feed emits, and finish() flushes the rest.  The hypothesis then depends on how the input was split into feeds."""
 import numpy as np
 
 from .engine import BeamStream
@@ -15,19 +19,24 @@ from .engine import BeamStream
 
 class StreamingRecognizer:
     """`slots` concurrent streams on `network` (a HipNetwork whose engine can stream: unidirectional LSTM layers, no
-    dropout; any other raises the library's message here).  The decoder is the network's, as in decode(): beam_width,
+    dropout - or, with lookahead = R frames, bidirectional concat layers; any other raises the library's message here).  The decoder is the network's, as in decode(): beam_width,
     merge_repeated as TF's default, and language_model() fused with config.lm_weight / lm_bonus when the config names
     one; decoder = 'greedy' streams with a beam of width 1."""
 
-    def __init__(self, network, slots=1):
+    def __init__(self, network, slots=1, lookahead=None):
         self.network = network
         self.engine = network.engine
         self.slots = int(slots)
+        self.lookahead = None if lookahead is None else int(lookahead)
         self.feature_size = int(network.config.feature_size)
         settle = getattr(network, '_settle', None)
         if settle:
             settle()
-        self.engine.stream_open(self.slots)
+        if self.lookahead is None:
+            self.engine.stream_open(self.slots)
+        else:
+            self.engine.stream_open_lookahead(self.slots, self.lookahead)
+        self._open_rows = [False] * self.slots   # look-ahead: the slot has rows that no `last` has flushed yet
         lm = network.language_model()
         width = network.beam_width if getattr(network, 'decoder', 'beam') == 'beam' else 1
         kw = {} if lm is None else dict(lm=lm, lm_weight=network.config.lm_weight, lm_bonus=network.config.lm_bonus)
@@ -35,10 +44,11 @@ class StreamingRecognizer:
         self._audio = False                      # feed_audio attached the network's featurizer to the session
         self._open_audio = [False] * self.slots  # the slot holds audio that no `last` has completed yet
 
-    def feed(self, chunks):
+    def feed(self, chunks, last=None):
         """chunks: one entry per slot, float32 [n_b, F] (the slot's next frames) or None (the slot is idle).  Pads to the
         longest, runs the chunk on the GPU, feeds every slot's beam with its own frames.  Returns the current hypothesis
-        (list of ids) of every slot."""
+        (list of ids) of every slot.  With a look-ahead the last `lookahead` frames of a slot wait for their right
+        context: the beam gets the rows the feed emitted, and last[b] true (look-ahead only) flushes slot b."""
         if len(chunks) != self.slots:
             raise ValueError('%d chunks for %d slots' % (len(chunks), self.slots))
         arrs = [None if c is None else np.asarray(c, dtype=np.float32) for c in chunks]
@@ -47,6 +57,22 @@ class StreamingRecognizer:
                 raise ValueError('a chunk must be [n, %d], not %s' % (self.feature_size, a.shape))
         n = np.asarray([0 if a is None else a.shape[0] for a in arrs], dtype=np.int32)
         Tc = int(n.max())
+        if self.lookahead is not None:
+            feats = np.zeros((self.slots, Tc, self.feature_size), np.float32)
+            for b, a in enumerate(arrs):
+                if n[b]:
+                    feats[b, :n[b]] = a
+            logits, rows = self.engine.stream_feed_lookahead(feats, n, last)
+            for b in range(self.slots):
+                if rows[b]:
+                    self.beams[b].feed(logits[:rows[b]], slot=b)
+                if last is not None and last[b]:
+                    self._open_rows[b] = False
+                elif n[b]:
+                    self._open_rows[b] = True
+            return [beam.best()[0] for beam in self.beams]
+        if last is not None and any(last):
+            raise ValueError('`last` means something only with a look-ahead')
         if Tc > 0:
             feats = np.zeros((self.slots, Tc, self.feature_size), np.float32)
             for b, a in enumerate(arrs):
@@ -88,6 +114,8 @@ class StreamingRecognizer:
         slot whose audio (feed_audio) no `last` has completed is completed first, with an empty feed."""
         if self._open_audio[slot]:
             self.feed_audio([None] * self.slots, [b == slot for b in range(self.slots)])
+        elif self._open_rows[slot]:
+            self.feed([None] * self.slots, [b == slot for b in range(self.slots)])
         out = self.beams[slot].best()
         self.engine.stream_reset([slot])
         self.beams[slot].reset()

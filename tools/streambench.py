@@ -15,7 +15,13 @@ kernels (set_recurrence_mode(0)) on the same box: what the state hand-over adds 
 With --from-audio every shape also carries "from_audio" (DESIGN.md §16): the same session shape fed SAMPLES
 (Engine.stream_feed_audio; 16 kHz, 26 cepstra, numcontext 9, norm_min_frames 50; Tc * 160 samples per slot and feed, which
 emit Tc rows each once the first 50 frames are in), measured in the same child as stream_feed of as many rows: host_ms as
-above, the front end's device-timed copies and kernels (nasr_featurize_times) and the forward pass's phases."""
+above, the front end's device-timed copies and kernels (nasr_featurize_times) and the forward pass's phases.
+With --lookahead R (repeatable) the tool measures look-ahead sessions instead: the 3x500 BIDIRECTIONAL concat
+network (F 494, C 29), S in {1, 16}, Tc in {10, 50}, every feed Tc new rows per slot behind R held ones, so that each feed
+runs a window of Tc + R rows and emits Tc.  Per shape: host_ms and device_ms of Engine.stream_feed_lookahead as above (one
+child, no profiler child), and `forward` of Tc + R frames as one batch on the per-step kernels in the same process: a feed
+recomputes its R look-ahead rows, so that forward pass is what it is expected to cost.
+   python tools/streambench.py --lookahead 20 --lookahead 50 [--out profiles/stream_lookahead_bench.json]"""
 import argparse
 import csv
 import glob
@@ -89,6 +95,60 @@ def worker(a):
     e.close()
 
 
+def worker_lookahead(a):
+    """one look-ahead shape SxTcxR in steady state: every feed a window of Tc + R rows"""
+    from neuralasr_amd.engine import Engine
+    from neuralasr_amd.networks.hipnetwork import _glorot_init
+    S, Tc, R = (int(x) for x in a.worker.split('x'))
+    e = Engine(F, H, L, True, 'concat', C)
+    e.set_params(_glorot_init(e.tensors(), 1))
+    mode = e.recurrence_mode
+    rs = np.random.RandomState(7)
+    chunks = [rs.randn(S, Tc, F).astype(np.float32) for _ in range(4)]
+    n = [Tc] * S
+    e.stream_open_lookahead(S, R)
+    fill = rs.randn(S, R, F).astype(np.float32)
+    assert e.stream_feed_lookahead(fill, [R] * S)[1].tolist() == [0] * S          # R rows held: from here on a feed emits Tc
+    host, dev = [], []
+    for i in range(a.warmup + 2 * a.steps):
+        if i == a.warmup + a.steps:
+            e.set_profiling(True)
+        t0 = time.perf_counter()
+        out, rows = e.stream_feed_lookahead(chunks[i % 4], n)
+        dt = (time.perf_counter() - t0) * 1e3
+        assert rows.tolist() == n
+        if a.warmup <= i < a.warmup + a.steps:
+            host.append(dt)
+        elif i >= a.warmup + a.steps:
+            pt = e.phase_times()
+            dev.append([pt['pack_ms'], pt['xproj_ms'], pt['rec_fwd_ms'], pt['proj_ctc_ms']])
+    e.set_profiling(False)
+    assert np.isfinite(out).all() and e.stream_frames().tolist() == [(a.warmup + 2 * a.steps) * Tc] * S
+    e.stream_close()
+    e.set_recurrence_mode(False)
+    win = [rs.randn(S, Tc + R, F).astype(np.float32) for _ in range(4)]
+    fwd = []
+    for i in range(a.warmup + a.steps):
+        t0 = time.perf_counter()
+        e.forward(win[i % 4], [Tc + R] * S)
+        if i >= a.warmup:
+            fwd.append((time.perf_counter() - t0) * 1e3)
+    dev = np.asarray(dev)
+
+    def stat(v):
+        return {'median': round(float(np.median(v)), 3), 'min': round(min(v), 3), 'max': round(max(v), 3)}
+    res = {'S': S, 'Tc': Tc, 'R': R, 'window_rows': Tc + R, 'feeds': a.warmup + 2 * a.steps, 'recurrence_mode_of_the_handle': mode,
+           'host_ms': {'stream_feed_lookahead': stat(host), 'forward_per_step_of_the_window': stat(fwd)},
+           'device_ms_per_feed': round(float(np.median(dev.sum(1))), 4),
+           'device_ms_by_phase': dict(zip(('pack', 'input_gemms', 'recurrence', 'projection'),
+                                          (round(float(x), 4) for x in np.median(dev, 0)))),
+           'audio_ms_per_chunk': Tc * FRAME_MS, 'latency_ms_of_the_rule': (Tc + R) * FRAME_MS}
+    res['rt_factor_host'] = round(res['host_ms']['stream_feed_lookahead']['median'] / (Tc * FRAME_MS), 4)
+    res['feed_over_forward_host'] = round(res['host_ms']['stream_feed_lookahead']['median'] / res['host_ms']['forward_per_step_of_the_window']['median'], 3)
+    print('STREAMBENCH ' + json.dumps(res), flush=True)
+    e.close()
+
+
 def from_audio(a, e, S, Tc):
     """the session fed samples: host clock, then with the profiler on the front end's and the forward pass's device time"""
     from neuralasr_amd.features import Featurizer
@@ -144,7 +204,8 @@ def kernel_ns(d):
 
 
 def child(shape, a, profiled, d=None):
-    cmd = [sys.executable, os.path.abspath(__file__), '--worker', '%dx%d' % shape, '--steps', str(a.steps), '--warmup', str(a.warmup)]
+    cmd = [sys.executable, os.path.abspath(__file__), '--worker', 'x'.join(str(x) for x in shape), '--steps', str(a.steps),
+           '--warmup', str(a.warmup)]
     if a.from_audio and not profiled:
         cmd.append('--from-audio')
     if profiled:
@@ -152,7 +213,7 @@ def child(shape, a, profiled, d=None):
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=400)
     line = [l for l in r.stdout.splitlines() if l.startswith('STREAMBENCH ')]
     if r.returncode != 0 or not line:
-        raise SystemExit('the %dx%d child failed (%d):\n%s\n%s' % (shape + (r.returncode, r.stdout[-2000:], r.stderr[-2000:])))
+        raise SystemExit('the %s child failed (%d):\n%s\n%s' % ('x'.join(str(x) for x in shape), r.returncode, r.stdout[-2000:], r.stderr[-2000:]))
     return json.loads(line[0][len('STREAMBENCH '):])
 
 
@@ -164,9 +225,25 @@ def main():
     ap.add_argument('--from-audio', action='store_true', help='also feed the session samples (stream_feed_audio)')
     ap.add_argument('--worker', help='(internal) SxTc: the measured process of one shape')
     ap.add_argument('--profiled', action='store_true', help='(internal) the child runs under the profiler')
+    ap.add_argument('--lookahead', type=int, action='append', metavar='R',
+                    help='measure look-ahead sessions of the bidirectional 3x500 network with R look-ahead frames (repeatable)')
     a = ap.parse_args()
     if a.worker:
-        return worker(a)
+        return worker_lookahead(a) if a.worker.count('x') == 2 else worker(a)
+    if a.lookahead:
+        doc = {'tool': 'tools/streambench.py --lookahead', 'network': 'bilstm 3x500 concat, F %d, C %d' % (F, C),
+               'method': 'host clock and HIP events (nasr_set_profiling) in one child per shape; every feed runs a window of Tc + R rows',
+               'shapes': []}
+        for S, Tc in SHAPES:
+            for R in a.lookahead:
+                res = child((S, Tc, R), a, False)
+                doc['shapes'].append(res)
+                print(json.dumps(res), flush=True)
+        out = a.out if a.out != ap.get_default('out') else os.path.join(ROOT, 'profiles', 'stream_lookahead_bench.json')
+        with open(out, 'w') as fh:
+            json.dump(doc, fh, indent=1)
+            fh.write('\n')
+        return
     doc = {'tool': 'tools/streambench.py', 'network': 'lstm_ctc_net 3x500 uni, F %d, C %d' % (F, C),
            'method': 'host clock and HIP events in one child per shape; kernel durations from a second child under rocprofv3 --kernel-trace --stats',
            'shapes': []}
