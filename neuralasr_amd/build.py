@@ -1,7 +1,8 @@
 """Builds neuralasr_amd/libnasr.so (the HIP kernels + C ABI of include/nasr.h) for gfx950 with hipcc.
 In-tree, explicit `hipcc -shared -fPIC`; cross-compiles without a GPU.  `python -m neuralasr_amd.build`.
-Also neuralasr_amd/libnasr_kt.so: the kernel tests' entry points (tests/kernel_harness/harness.hip) over the very
-gemm.o / gemm_tph.o / optim.o objects of libnasr.so."""
+Also neuralasr_amd/libnasr_kt.so: the kernel tests' entry points (tests/kernel_harness/harness.hip for the GEMM layer,
+rec_harness.hip for the recurrence) over the very gemm.o / gemm_tph.o / optim.o / lstm.o / lstm_persist.o / lstm_wide.o
+objects of libnasr.so."""
 import os
 import subprocess
 import sys
@@ -11,8 +12,11 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 LIB = os.path.join(HERE, 'libnasr.so')
 KT_LIB = os.path.join(HERE, 'libnasr_kt.so')
-KT_SRC = os.path.join(HERE, '..', 'tests', 'kernel_harness', 'harness.hip')
-KT_OBJS = ['gemm.o', 'gemm_tph.o', 'optim.o']       # the objects of libnasr.so the kernel tests link against
+KT_DIR = os.path.join(HERE, '..', 'tests', 'kernel_harness')
+KT_SRCS = ['harness.hip', 'rec_harness.hip']
+KT_HEADERS = [os.path.join(KT_DIR, 'arena.h')]
+# the objects of libnasr.so the kernel tests link against (optim.o also holds test_hook(), which the recurrence launchers call)
+KT_OBJS = ['gemm.o', 'gemm_tph.o', 'optim.o', 'lstm.o', 'lstm_persist.o', 'lstm_wide.o']
 SOURCES = ['gemm.hip', 'gemm_tph.hip', 'lstm.hip', 'lstm_persist.hip', 'lstm_wide.hip', 'ctc.hip', 'dense.hip', 'optim.hip', 'nasr_layout.hip',
            'nasr_rec.hip', 'nasr_batch.hip', 'nasr_pass.hip', 'nasr_stream.hip', 'nasr_api.hip', 'nasr_comm.hip', 'beam.cpp',
            'wavenet.hip', 'nasr_wavenet.hip', 'las.hip', 'las_beam.hip', 'nasr_las.hip', 'mfcc.hip', 'resample.hip', 'wave_aug.hip']
@@ -60,15 +64,19 @@ def build(force=False, verbose=False):
         if verbose and r.stderr.strip():
             print(r.stderr)
 
-    kt_obj = os.path.join(bdir, 'kt_harness.o')
-    if force or _stale(kt_obj, [KT_SRC] + HEADERS):
-        jobs.append([hipcc] + FLAGS + ['-c', KT_SRC, '-o', kt_obj])
+    kt_objs = []
+    for s in KT_SRCS:
+        src = os.path.join(KT_DIR, s)
+        obj = os.path.join(bdir, 'kt_' + os.path.splitext(s)[0] + '.o')
+        kt_objs.append(obj)
+        if force or _stale(obj, [src] + KT_HEADERS + HEADERS):
+            jobs.append([hipcc] + FLAGS + ['-c', src, '-o', obj])
 
     with ThreadPoolExecutor(max_workers=min(4, max(1, len(jobs)))) as ex:
         list(ex.map(run, jobs))
     if force or jobs or _stale(LIB, objs):
         run([hipcc, '--offload-arch=gfx950', '-shared', '-fPIC', '-o', LIB] + objs + ['-lpthread'])
-    kt_objs = [kt_obj] + [os.path.join(bdir, o) for o in KT_OBJS]
+    kt_objs += [os.path.join(bdir, o) for o in KT_OBJS]
     if force or jobs or _stale(KT_LIB, kt_objs):
         run([hipcc, '--offload-arch=gfx950', '-shared', '-fPIC', '-o', KT_LIB] + kt_objs)
     return LIB

@@ -114,6 +114,22 @@ void launch_expand_context(const float* centre, const float* pad, const int* seq
 void launch_expand_context_masked(const float* centre, const float* pad, const int* seq_len, const int* masks, int nm,
                                   int static_width, float* X0, int B, int Bp, int T, int ctx, int ncep, int Fp,
                                   hipStream_t st);
+// Contract of every recurrence launcher below and in the two sections that follow, on what is not computed
+// (tests/test_gpu_rec_kernels.py holds each of them to it):
+//   seq_len   Bp entries, 0 in the rows b >= B.  Frame t of row b is computed iff t < seq_len[b].  A row b < B may have
+//             length 0 too (a stream slot without frames in a chunk: validate_chunk admits it, validate_batch does not):
+//             every kernel treats it like a padded row, whatever state it carries.
+//   forward   gates and cbuf of a frame that is not computed are neither written nor allowed into a result (gates may
+//             hold anything there: the ragged input GEMM leaves them alone); out is +0 there, for every row b < Bp.
+//   BPTT      gates, cbuf and dOut of such a frame may be loaded (unconditional loads) but never enter a result; dG is +0
+//             there, for every row b < Bp.
+//   units     j in [H, Hp): U's padded rows and columns and the padded gate columns of the input must be 0; c and out
+//             are then exactly 0 there.  dOut must be 0 there too (it is: the layer above has zero weights for them);
+//             dG is then exactly 0 there - except in the persistent BPTT, whose partial sums carry their epoch in the
+//             last mantissa bit, so a zero partial sum can be the subnormal 2^-149: |dG| <= 32 T 2^-149 in those units.
+//             These columns of dG also enter the weight- and bias-gradient GEMMs of the padded parameters.  Whether the
+//             optimiser then keeps the padded parameters at exactly 0 (Adam divides a gradient of that size by eps) has
+//             NOT been checked; the requirement above that U's padding is 0 rests on it.
 // repack canonical U [Hp][N4] of every (layer,dir) into the forward / backward MFMA B-operand images
 void launch_repack_u(const float* U, float* Uf, float* Ub, int Hp, hipStream_t st);
 void launch_lstm_fwd_step(const LstmDims& dm, int s, const float* Uf, const float* hin, float* hout, float* gates,

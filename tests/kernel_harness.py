@@ -1,5 +1,5 @@
-"""ctypes side of tests/kernel_harness/harness.hip (neuralasr_amd/libnasr_kt.so, built by neuralasr_amd/build.py): the
-GEMM-layer launchers of csrc/kernels.h, callable with NumPy arrays.  Every call raises on a HIP error or a refused
+"""ctypes side of tests/kernel_harness/harness.hip and rec_harness.hip (neuralasr_amd/libnasr_kt.so, built by
+neuralasr_amd/build.py): the GEMM-layer and recurrence launchers of csrc/kernels.h, callable with NumPy arrays.  Every call raises on a HIP error or a refused
 argument; outputs come back as fresh arrays whose untouched bytes still hold FILL."""
 import ctypes
 import os
@@ -13,7 +13,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 KT_PATH = os.path.join(ROOT, 'neuralasr_amd', 'libnasr_kt.so')
 SYMBOLS = ['kt_gemm_pick_split', 'kt_gemm_tp_tile_rows', 'kt_gemm_tph_pick_split', 'kt_tp_split2_parts', 'kt_tph_bytes',
            'kt_gemm_f32', 'kt_tph_scales', 'kt_tph_scales_batch', 'kt_tph_scales_from_parts', 'kt_tph_split2', 'kt_gemm_tph',
-           'kt_colsum', 'kt_colsum_parts', 'kt_reduce_slabs', 'kt_reduce_slabs_rows']
+           'kt_colsum', 'kt_colsum_parts', 'kt_reduce_slabs', 'kt_reduce_slabs_rows',
+           'kt_persist_dgmax_floats', 'kt_lstm_step_fwd', 'kt_lstm_step_bwd',
+           'kt_lstm_persist_fwd', 'kt_lstm_persist_bwd', 'kt_lstm_wide_fwd', 'kt_lstm_wide_bwd']
 
 FILL = 0xCD                                   # pre-fill byte of every output buffer
 FILL_F32 = np.frombuffer(bytes([FILL] * 4), dtype=np.float32)[0]
@@ -35,6 +37,11 @@ class KtTph(Structure):
                 [('a_rows', c_int), ('b_rows', c_int)])
 
 
+class KtRec(Structure):
+    _fields_ = ([(n, c_int) for n in ('T', 'B', 'Bp', 'H', 'Hp', 'D')] + [('forget_bias', c_float)] +
+                [(n, c_int) for n in ('f16', 'lean', 'parts', 'fill')])
+
+
 _lib = None
 
 
@@ -45,6 +52,7 @@ def lib():
             raise ImportError(f'{KT_PATH} is missing: run `python -m neuralasr_amd.build`')
         _lib = ctypes.CDLL(KT_PATH)
         _lib.kt_tph_bytes.restype = c_ulonglong
+        _lib.kt_persist_dgmax_floats.restype = c_ulonglong
     return _lib
 
 
@@ -226,6 +234,76 @@ def reduce_slabs_rows(slabs, ldc, rowmap, out_rows):
     rc = lib().kt_reduce_slabs_rows(_f(slabs), S, M, N, ldc, _i(rowmap), _f(out), c_longlong(out.size), FILL)
     _check(rc, 'kt_reduce_slabs_rows')
     return out.reshape(out_rows, ldc)
+
+
+# ------------------------------------------------------------------ the recurrence (rec_harness.hip)
+class RecurrenceAbort(RuntimeError):
+    """A resident kernel reported through XcdCtl::error, the sticky word or the fault float."""
+
+
+def _rec_desc(inp, pre, **kw):
+    T, Bp, D, Hp = pre.shape[:4]
+    return KtRec(T=T, B=inp['B'], Bp=Bp, H=inp['H'], Hp=Hp, D=D, forget_bias=inp['fb'], fill=FILL, **kw)
+
+
+def _rec_status(status, what):
+    if status.any():
+        raise RecurrenceAbort(f'{what}: error word {status[0]:#x}, sticky word {status[1]:#x}, fault {status[2]}')
+
+
+def lstm_forward(path, inp):
+    """Runs a forward path of rec_ref.KINDS on rec_ref.make_inputs buffers -> (gates, c, out), frame-indexed
+    [T][Bp][D][Hp](4) float32; gates = the caller's pre-activations with the activations written over them."""
+    pre = inp['pre']
+    T, Bp, D, Hp = pre.shape[:4]
+    U = _f32(inp['U'])
+    g = np.array(pre, dtype=np.float32, order='C')
+    c, o = _out(T * Bp * D * Hp), _out(T * Bp * D * Hp)
+    sq = _i32(inp['seq_len'])
+    if path in ('step_fwd', 'step_carry'):
+        d = _rec_desc(inp, pre)
+        st = _f32(inp['state']) if path == 'step_carry' else None
+        _check(lib().kt_lstm_step_fwd(ctypes.byref(d), _f(U), _f(g), _f(c), _f(o), _i(sq), _f(st)), 'kt_lstm_step_fwd')
+    else:
+        d = _rec_desc(inp, pre, f16=int(path == 'persist_fwd16'))
+        status = np.full(3, 0xFFFFFFFF, dtype=np.uint32)
+        name = 'kt_lstm_wide_fwd' if path == 'wide_fwd' else 'kt_lstm_persist_fwd'
+        rc = getattr(lib(), name)(ctypes.byref(d), _f(U), _f(g), _f(c), _f(o), _i(sq), status.ctypes.data_as(c_void_p))
+        _check(rc, name)
+        _rec_status(status, name)
+    return g, c.reshape(T, Bp, D, Hp), o.reshape(T, Bp, D, Hp)
+
+
+def lstm_backward(path, inp, lean=False, parts=False):
+    """Runs a BPTT path -> (dG [T][Bp][D][Hp][4], rowpart [D*32][T*Bp] or None, colpart [8/D][D*4Hp] or None)."""
+    act = inp['act']
+    T, Bp, D, Hp = act.shape[:4]
+    U, a, c, do = _f32(inp['U']), _f32(act), _f32(inp['c']), _f32(inp['dout'])
+    dg = _out(act.size)
+    sq = _i32(inp['seq_len'])
+    rp = cp = None
+    if path == 'step_bwd':
+        d = _rec_desc(inp, act)
+        _check(lib().kt_lstm_step_bwd(ctypes.byref(d), _f(U), _f(a), _f(c), _f(do), _f(dg), _i(sq)), 'kt_lstm_step_bwd')
+    elif path == 'wide_bwd':
+        d = _rec_desc(inp, act)
+        status = np.full(3, 0xFFFFFFFF, dtype=np.uint32)
+        rc = lib().kt_lstm_wide_bwd(ctypes.byref(d), _f(U), _f(a), _f(c), _f(do), _f(dg), _i(sq), status.ctypes.data_as(c_void_p))
+        _check(rc, 'kt_lstm_wide_bwd')
+        _rec_status(status, 'kt_lstm_wide_bwd')
+    else:
+        d = _rec_desc(inp, act, lean=int(lean), parts=int(parts))
+        if parts:
+            rp, cp = _out(D * 32 * T * Bp), _out((8 // D) * D * 4 * Hp)
+            assert rp.size + cp.size == lib().kt_persist_dgmax_floats(T, Bp, Hp, D), 'rowpart / colpart are not what the library allocates'
+        status = np.full(3, 0xFFFFFFFF, dtype=np.uint32)
+        rc = lib().kt_lstm_persist_bwd(ctypes.byref(d), _f(U), _f(a), _f(c), _f(do), _f(dg), _f(rp), _f(cp), _i(sq),
+                                       status.ctypes.data_as(c_void_p))
+        _check(rc, 'kt_lstm_persist_bwd')
+        _rec_status(status, 'kt_lstm_persist_bwd')
+        if parts:
+            rp, cp = rp.reshape(D * 32, T * Bp), cp.reshape(8 // D, D * 4 * Hp)
+    return dg.reshape(act.shape), rp, cp
 
 
 # ------------------------------------------------------------------ checks shared by the GPU tests
