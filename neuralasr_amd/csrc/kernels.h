@@ -138,25 +138,22 @@ void launch_lstm_fwd_step(const LstmDims& dm, int s, const float* Uf, const floa
 // c0 = the saved c [D][Bp][Hp] instead of starting a sequence
 void launch_lstm_fwd_step_carry(const LstmDims& dm, const float* Uf, const float* hin, float* hout, float* gates, float* cbuf,
                                 float* out, const int* seq_len, float forget_bias, const float* c0, hipStream_t st);
-// one layer's stream state [S][2][H] (c, then h; unidirectional) -> the h operand image of step 0 [Bp*Hp] and c [Bp][Hp],
-// zeros in padded units and slots; and back from row n_frames[b]-1 of out / cbuf [Tc*Bp][Hp] (n_frames[b] = 0: untouched)
-void launch_stream_load_state(const float* state, float* himg, float* cimg, int S, int H, int Bp, int Hp, hipStream_t st);
-void launch_stream_save_state(const float* out, const float* cbuf, const int* n_frames, float* state, int S, int H, int Bp,
-                              int Hp, hipStream_t st);
-// A look-ahead session's feed as the kernels see it (nasr_stream.hip), per slot: rows held before the feed,
-// new rows, rows the feed emits.  Passed by value: a feed needs no upload of its own for them.
+// A stream session's feed as the kernels see it (nasr_stream.hip), per slot: rows held before the feed,
+// new rows, rows the feed emits (without a look-ahead: 0, n, n).  Passed by value: a feed needs no upload of its own for them.
 constexpr int LA_MAX_SLOTS = 64;
 struct LaSlots { int held[LA_MAX_SLOTS], n[LA_MAX_SLOTS], emit[LA_MAX_SLOTS]; };
+// one layer's forward stream state [S][2][H] (c, then h) -> step 0's h operand images [D][Bp*Hp] and c [D][Bp][Hp]:
+// direction 0 from the state, the others, padded units and padded slots zero; and back from the first Hp of row
+// (emit[b]-1)*Bp+b of out / cbuf [T*Bp][DH], DH = D*Hp (emit[b] = 0: untouched).  D = 1 loads one direction from a state:
+// the kernel tests call it so, once per direction at an offset.
+void launch_stream_load_state(const float* state, float* himg, float* cimg, int S, int H, int Bp, int Hp, hipStream_t st, int D = 1);
+void launch_stream_save_state(const float* out, const float* cbuf, const LaSlots& sl, float* state, int S, int H, int Bp, int DH,
+                              hipStream_t st);
 // Window assembly: pending row t of slot b is hold_in [S][R][F] row t (t < held) or fresh [S][Tc][F] row t - held; rows
 // [0, P) of an emitting slot go to win [S][T][F] (zeros elsewhere; win NULL: nothing emits), rows [emit, P) to hold_out
 // [S][R][F], which must not be hold_in.  rows = the largest P, >= 1.
 void launch_la_window(const float* hold_in, const float* fresh, const LaSlots& sl, float* win, float* hold_out, int S, int R,
                       int Tc, int T, int rows, int F, hipStream_t st);
-// one layer's forward state [S][2][H] -> step 0's h operand images [2][Bp*Hp] and c [2][Bp][Hp]: the backward direction,
-// padded units and padded slots zero; and back from the forward half of row (emit[b]-1)*Bp+b of out / cbuf [T*Bp][2*Hp]
-void launch_la_load_state(const float* state, float* himg, float* cimg, int S, int H, int Bp, int Hp, hipStream_t st);
-void launch_la_save_state(const float* out, const float* cbuf, const LaSlots& sl, float* state, int S, int H, int Bp, int Hp,
-                          hipStream_t st);
 // BPTT step: pin/pout = [D][lstm_bwd_partials(Hp)][Bp][Hp] partial sums handed launch to launch, dcin/dcout = [D][Bp][Hp]
 int lstm_bwd_partials(int Hp);
 void launch_lstm_bwd_step(const LstmDims& dm, int s, const float* Ub, const float* pin, float* pout,

@@ -320,43 +320,45 @@ void launch_lstm_fwd_step_carry(const LstmDims& dm, const float* Uf, const float
 }
 
 // ------------------------------------------------------------------ stream state (nasr_stream.hip)
-// One layer's saved state, natural layout [S][2][H] (c, then h), into what step 0 of a feed reads: the h operand image
-// [Bp/16][Hp/16][64][4] in the layout of sw_index and c [Bp][Hp].  Padded units and padded slots: zeros.
+// One layer's saved forward state, natural layout [S][2][H] (c, then h), into what step 0 of a feed reads, for every
+// direction (blockIdx.y): the h operand image [Bp/16][Hp/16][64][4] in the layout of sw_index and c [Bp][Hp].  Direction 0
+// comes from the saved state; a backward direction starts every window anew, from zeros.  Padded units and padded slots:
+// zeros.  Every element is written on every launch.
 __global__ __launch_bounds__(256) void stream_load_state_kernel(const float* __restrict__ state, float* __restrict__ himg,
                                                                 float* __restrict__ cimg, int S, int H, int Bp, int Hp) {
-  const int e = blockIdx.x * 256 + threadIdx.x;
+  const int e = blockIdx.x * 256 + threadIdx.x, d = blockIdx.y;
   if (e >= Bp * Hp) return;
   const int b = e / Hp, j = e - b * Hp;
   float c = 0.f, hv = 0.f;
-  if (b < S && j < H) {
+  if (d == 0 && b < S && j < H) {
     c = state[((size_t)b * 2 + 0) * H + j];
     hv = state[((size_t)b * 2 + 1) * H + j];
   }
-  cimg[e] = c;
-  himg[sw_index(Hp, b >> 4, b & 15, j)] = hv;
+  cimg[(size_t)d * Bp * Hp + e] = c;
+  himg[(size_t)d * Bp * Hp + sw_index(Hp, b >> 4, b & 15, j)] = hv;
 }
 
-// ... and back: every slot's state as of its last frame of the chunk, row (n_frames[b] - 1) * Bp + b of cbuf / out
-// [Tc * Bp][Hp].  A slot without a frame in this chunk keeps what it had.
+// ... and back: the forward direction's state after every slot's last EMITTED row, the first Hp of row
+// (emit[b] - 1) * Bp + b of cbuf / out [T * Bp][DH]; the look-ahead rows behind it are run again by the next window.  A
+// slot that emits nothing keeps what it had.
 __global__ __launch_bounds__(256) void stream_save_state_kernel(const float* __restrict__ out, const float* __restrict__ cbuf,
-                                                                const int* __restrict__ n_frames, float* __restrict__ state,
-                                                                int S, int H, int Bp, int Hp) {
+                                                                LaSlots sl, float* __restrict__ state, int S, int H, int Bp, int DH) {
   const int e = blockIdx.x * 256 + threadIdx.x;
   if (e >= S * H) return;
   const int b = e / H, j = e - b * H;
-  const int n = n_frames[b];
-  if (n < 1) return;
-  const size_t r = (size_t)(n - 1) * Bp + b;
-  state[((size_t)b * 2 + 0) * H + j] = cbuf[r * Hp + j];
-  state[((size_t)b * 2 + 1) * H + j] = out[r * Hp + j];
+  const int E = sl.emit[b];
+  if (E < 1) return;
+  const size_t r = (size_t)(E - 1) * Bp + b;
+  state[((size_t)b * 2 + 0) * H + j] = cbuf[r * DH + j];
+  state[((size_t)b * 2 + 1) * H + j] = out[r * DH + j];
 }
 
-void launch_stream_load_state(const float* state, float* himg, float* cimg, int S, int H, int Bp, int Hp, hipStream_t st) {
-  hipLaunchKernelGGL(stream_load_state_kernel, dim3((Bp * Hp + 255) / 256), dim3(256), 0, st, state, himg, cimg, S, H, Bp, Hp);
+void launch_stream_load_state(const float* state, float* himg, float* cimg, int S, int H, int Bp, int Hp, hipStream_t st, int D) {
+  hipLaunchKernelGGL(stream_load_state_kernel, dim3((Bp * Hp + 255) / 256, D), dim3(256), 0, st, state, himg, cimg, S, H, Bp, Hp);
 }
-void launch_stream_save_state(const float* out, const float* cbuf, const int* n_frames, float* state, int S, int H, int Bp,
-                              int Hp, hipStream_t st) {
-  hipLaunchKernelGGL(stream_save_state_kernel, dim3((S * H + 255) / 256), dim3(256), 0, st, out, cbuf, n_frames, state, S, H, Bp, Hp);
+void launch_stream_save_state(const float* out, const float* cbuf, const LaSlots& sl, float* state, int S, int H, int Bp, int DH,
+                              hipStream_t st) {
+  hipLaunchKernelGGL(stream_save_state_kernel, dim3((S * H + 255) / 256), dim3(256), 0, st, out, cbuf, sl, state, S, H, Bp, DH);
 }
 
 // ------------------------------------------------------------------ look-ahead session (nasr_stream.hip)
@@ -382,46 +384,6 @@ __global__ __launch_bounds__(256) void la_window_kernel(const float* __restrict_
 void launch_la_window(const float* hold_in, const float* fresh, const LaSlots& sl, float* win, float* hold_out, int S, int R,
                       int Tc, int T, int rows, int F, hipStream_t st) {
   hipLaunchKernelGGL(la_window_kernel, dim3(rows, S), dim3(256), 0, st, hold_in, fresh, sl, win, hold_out, R, Tc, T, F);
-}
-
-// One layer's saved forward state [S][2][H] into what step 0 of a window reads, for both directions (blockIdx.y): the
-// forward direction's h operand image and c as stream_load_state_kernel writes them, zeros for the backward direction -
-// it starts every window anew - and for padded units and padded slots.  Every element is written on every launch.
-__global__ __launch_bounds__(256) void la_load_state_kernel(const float* __restrict__ state, float* __restrict__ himg,
-                                                            float* __restrict__ cimg, int S, int H, int Bp, int Hp) {
-  const int e = blockIdx.x * 256 + threadIdx.x, d = blockIdx.y;
-  if (e >= Bp * Hp) return;
-  const int b = e / Hp, j = e - b * Hp;
-  float c = 0.f, hv = 0.f;
-  if (d == 0 && b < S && j < H) {
-    c = state[((size_t)b * 2 + 0) * H + j];
-    hv = state[((size_t)b * 2 + 1) * H + j];
-  }
-  cimg[(size_t)d * Bp * Hp + e] = c;
-  himg[(size_t)d * Bp * Hp + sw_index(Hp, b >> 4, b & 15, j)] = hv;
-}
-
-// ... and back: the forward direction's state after the last EMITTED row, the forward half of row (emit[b] - 1) * Bp + b
-// of cbuf / out [T * Bp][2 * Hp]; the look-ahead rows behind it are run again by the next window.  A slot that emits
-// nothing keeps what it had.
-__global__ __launch_bounds__(256) void la_save_state_kernel(const float* __restrict__ out, const float* __restrict__ cbuf,
-                                                            LaSlots sl, float* __restrict__ state, int S, int H, int Bp, int DH) {
-  const int e = blockIdx.x * 256 + threadIdx.x;
-  if (e >= S * H) return;
-  const int b = e / H, j = e - b * H;
-  const int E = sl.emit[b];
-  if (E < 1) return;
-  const size_t r = (size_t)(E - 1) * Bp + b;
-  state[((size_t)b * 2 + 0) * H + j] = cbuf[r * DH + j];
-  state[((size_t)b * 2 + 1) * H + j] = out[r * DH + j];
-}
-
-void launch_la_load_state(const float* state, float* himg, float* cimg, int S, int H, int Bp, int Hp, hipStream_t st) {
-  hipLaunchKernelGGL(la_load_state_kernel, dim3((Bp * Hp + 255) / 256, 2), dim3(256), 0, st, state, himg, cimg, S, H, Bp, Hp);
-}
-void launch_la_save_state(const float* out, const float* cbuf, const LaSlots& sl, float* state, int S, int H, int Bp, int Hp,
-                          hipStream_t st) {
-  hipLaunchKernelGGL(la_save_state_kernel, dim3((S * H + 255) / 256), dim3(256), 0, st, out, cbuf, sl, state, S, H, Bp, 2 * Hp);
 }
 
 // ------------------------------------------------------------------ BPTT step

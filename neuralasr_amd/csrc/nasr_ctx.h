@@ -199,26 +199,22 @@ struct LasStateDelete { void operator()(LasState* s) const; };
 struct FzStream;
 struct FzStreamDelete { void operator()(FzStream* f) const; };
 
-// What a look-ahead session keeps beyond the forward state (nasr_stream_open_lookahead).
-struct Lookahead {
-  int R = 0;                         // look-ahead frames
-  DevBuf hold[2];                    // [S][R][F] held feature rows; a feed reads hold[cur] and writes the other one
-  int cur = 0;
-  DevBuf fresh;                      // [S][Tc][F] the feed's new rows: uploaded, or made by the front end
-  std::vector<int32_t> held;         // [S] rows held
-  std::vector<uint8_t> done;         // [S] the slot has had `last` and no reset
-  LaSlots sl{};                      // the feed that is running (run_chunk_steps: which row's state to save)
-};
-
-// A stream session (nasr_stream.hip): S concurrent streams on a unidirectional LSTM-family handle, or (la) on a
-// bidirectional one whose backward direction restarts in every window.
+// A stream session (nasr_stream.hip): S concurrent streams with a look-ahead of R frames.  R = 0 on a unidirectional
+// LSTM-family handle (nasr_stream_open: nothing is ever held), R >= 1 on a bidirectional one whose backward direction
+// restarts in every window (nasr_stream_open_lookahead).
 struct StreamState {
-  std::unique_ptr<Lookahead> la;
   int S = 0;
+  int R = 0;                         // look-ahead frames
   std::unique_ptr<FzStream, FzStreamDelete> audio;   // per slot: sample tail, running sums, waiting and recent frames
   DevBuf state;                      // [L][S][2][H] fp32: c, then h, as of each slot's last (emitted) frame; zero after open / reset
   DevBuf cimg;                       // [D][Bp][Hp]: the layer's saved c as step 0 of a feed reads it
-  std::vector<int64_t> frames;       // [S] frames consumed since the slot's reset
+  DevBuf hold[2];                    // R > 0: [S][R][F] held feature rows; a feed reads hold[cur] and writes the other one
+  int cur = 0;
+  DevBuf fresh;                      // R > 0: [S][Tc][F] the feed's new rows: uploaded, or made by the front end
+  std::vector<int32_t> held;         // [S] rows held
+  std::vector<uint8_t> done;         // [S] the slot has had `last` and no reset
+  LaSlots sl{};                      // the feed that is running (run_chunk_steps: which row's state to save)
+  std::vector<int64_t> frames;       // [S] frames emitted since the slot's reset
   uint64_t uf_seq = ~0ull;           // repack_seq of the per-step operand images the session built itself (see stream_feed)
 };
 

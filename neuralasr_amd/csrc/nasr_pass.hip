@@ -211,10 +211,10 @@ int dense_backward(nasr_ctx* h, int i, const float* X, float* dX) {
 }
 
 // One layer of a stream chunk: the recurrence over the chunk's T steps on the per-step kernels, whatever kind the handle's
-// batches run on, from the session's saved (c, h) of layer l, which it then replaces by every slot's state at its last
-// frame.  No graph: step 0 is another kernel than the rest, and a chunk is a few dozen launches.
-// A look-ahead session (ss.la): both directions over the window's T steps, the forward one from the saved state, the backward
-// one from zero at each slot's last pending row (seq_len[b] = its window); saved is the forward state after the last emitted row.
+// batches run on: the forward direction from the session's saved (c, h) of layer l, a backward direction (a look-ahead
+// session's) from zero at each slot's last pending row (seq_len[b] = its window).  Saved again is the forward state after
+// every slot's last emitted row; without a look-ahead that is its last frame.  No graph: step 0 is another kernel than
+// the rest, and a chunk is a few dozen launches.
 static int run_chunk_steps(nasr_ctx* h, int l, hipStream_t st) {
   StreamState& ss = *h->stream;
   const LstmDims dm{h->T, h->B, h->Bp, h->H, h->Hp, h->D};
@@ -222,13 +222,11 @@ static int run_chunk_steps(nasr_ctx* h, int l, hipStream_t st) {
   float* hst = h->hstate.as<float>();
   float* state = ss.state.as<float>() + (size_t)l * ss.S * 2 * h->H;
   float *g = h->gates[l].as<float>(), *c = h->cbuf[l].as<float>(), *o = h->outb[l].as<float>();
-  if (ss.la) launch_la_load_state(state, hst, ss.cimg.as<float>(), ss.S, h->H, h->Bp, h->Hp, st);
-  else launch_stream_load_state(state, hst, ss.cimg.as<float>(), ss.S, h->H, h->Bp, h->Hp, st);
+  launch_stream_load_state(state, hst, ss.cimg.as<float>(), ss.S, h->H, h->Bp, h->Hp, st, h->D);
   launch_lstm_fwd_step_carry(dm, h->Uf + sU, hst, hst + hs, g, c, o, h->seq_p, h->cfg.forget_bias, ss.cimg.as<float>(), st);
   for (int s = 1; s < h->T; ++s)
     launch_lstm_fwd_step(dm, s, h->Uf + sU, hst + (s & 1) * hs, hst + ((s + 1) & 1) * hs, g, c, o, h->seq_p, h->cfg.forget_bias, st);
-  if (ss.la) launch_la_save_state(o, c, ss.la->sl, state, ss.S, h->H, h->Bp, h->Hp, st);
-  else launch_stream_save_state(o, c, h->seq_p, state, ss.S, h->H, h->Bp, h->Hp, st);
+  launch_stream_save_state(o, c, ss.sl, state, ss.S, h->H, h->Bp, h->D * h->Hp, st);
   h->n_fwd_launch += h->T;
   HIPCHK(h, hipGetLastError());
   return NASR_OK;

@@ -558,45 +558,54 @@ class Engine:
         self._stream_featurizer = featurizer
         self._stream_max_samples = int(getattr(featurizer, 'max_samples', 1 << 23))
 
-    def _stream_audio_args(self, n_or_chunks, last):
+    def _stream_slots_and_last(self, per_slot, last):
+        """(S, the `last` flags as the library takes them, or None): per_slot and last must have one entry per slot"""
         S = getattr(self, '_stream_slots', 0)
-        if len(n_or_chunks) != S:
-            raise ValueError('%d entries for %d slots' % (len(n_or_chunks), S))
+        if len(per_slot) != S:
+            raise ValueError('%d entries for %d slots' % (len(per_slot), S))
         if last is None:
-            return S, None, None
+            return S, None
         fin = np.ascontiguousarray([1 if x else 0 for x in last], dtype=np.uint8)
         if fin.size != S:
             raise ValueError('%d `last` flags for %d slots' % (fin.size, S))
-        return S, fin, fin.ctypes.data_as(POINTER(c_uint8))
+        return S, fin.ctypes.data_as(POINTER(c_uint8))
+
+    def _stream_rows_then_feed(self, rows_fn, n, last, feed=None):
+        """The library's `rows_fn` on n (an int array, one count per slot): (rows int32 [S], the most of them), host only.
+        With `feed`, the feed those rows size: feed(last, rows out, most out, logits out, its rows) fills logits
+        [most,S,C] and must report what rows_fn said; (logits, rows) then."""
+        S, fin_p = self._stream_slots_and_last(n, last)
+        rows, most = np.zeros(S, np.int32), c_int(0)
+        self._ck(rows_fn(self.h, n.ctypes.data_as(POINTER(np.ctypeslib.as_ctypes_type(n.dtype))), fin_p, _ip(rows), byref(most)))
+        if feed is None:
+            return rows, int(most.value)
+        out = np.empty((most.value, S, self.num_classes), np.float32)
+        got, most2 = np.zeros(S, np.int32), c_int(0)
+        self._ck(feed(fin_p, _ip(got), byref(most2), _fp(out) if out.size else None, most.value))
+        assert most2.value == most.value and np.array_equal(got, rows)
+        return out, got
 
     def stream_audio_rows(self, n_samples, last=None):
         """(rows int32 [S], Tc): what a stream_feed_audio of n_samples[b] new samples per slot would emit now (host only)."""
-        S, fin, fin_p = self._stream_audio_args(n_samples, last)
-        n = np.ascontiguousarray([int(x) for x in n_samples], dtype=np.int64)
-        rows, Tc = np.zeros(S, np.int32), c_int(0)
-        self._ck(self.lib.nasr_stream_audio_rows(self.h, n.ctypes.data_as(POINTER(c_int64)), fin_p, _ip(rows), byref(Tc)))
-        return rows, int(Tc.value)
+        return self._stream_rows_then_feed(self.lib.nasr_stream_audio_rows, np.asarray([int(x) for x in n_samples], np.int64), last)
 
     def stream_feed_audio(self, chunks, last=None):
         """One feed of samples: chunks[b] float32 [n_b] at the featurizer's rate, or None / empty (slot b is idle, or only
         finishing); last[b] true declares slot b's utterance complete.  Returns (logits [Tc,S,C], rows int32 [S]): slot b's
         rows_b new rows are logits[:rows_b, b]; Tc = 0 when the feed emitted nothing.  At most the featurizer's
         max_samples per feed."""
-        S, fin, fin_p = self._stream_audio_args(chunks, last)
+        S, _ = self._stream_slots_and_last(chunks, last)
         arrs = [np.zeros(0, np.float32) if c is None else np.ascontiguousarray(c, dtype=np.float32).reshape(-1) for c in chunks]
         offsets = np.zeros(S + 1, dtype=np.int64)
         offsets[1:] = np.cumsum([a.size for a in arrs])
         most = getattr(self, '_stream_max_samples', 1 << 23)
         if offsets[S] > most:
             raise ValueError('%d samples in one feed: the featurizer takes at most max_samples = %d' % (offsets[S], most))
-        rows, Tc = self.stream_audio_rows([a.size for a in arrs], last)
         flat = np.concatenate(arrs) if offsets[S] else np.zeros(1, np.float32)
-        out = np.empty((Tc, S, self.num_classes), np.float32)
-        got, Tc2 = np.zeros(S, np.int32), c_int(0)
-        self._ck(self.lib.nasr_stream_feed_audio(self.h, _fp(flat), offsets.ctypes.data_as(POINTER(c_int64)), fin_p, _ip(got),
-                                                 byref(Tc2), _fp(out), Tc))
-        assert Tc2.value == Tc and np.array_equal(got, rows)
-        return out, got
+        return self._stream_rows_then_feed(
+            self.lib.nasr_stream_audio_rows, np.diff(offsets), last,
+            lambda fin_p, got, Tc2, out, Tc: self.lib.nasr_stream_feed_audio(
+                self.h, _fp(flat), offsets.ctypes.data_as(POINTER(c_int64)), fin_p, got, Tc2, out, Tc))
 
     # ---- a look-ahead session on a bidirectional network (DESIGN.md §18)
     def stream_open_lookahead(self, slots=1, lookahead=1):
@@ -608,31 +617,23 @@ class Engine:
 
     def stream_lookahead_rows(self, n_frames, last=None):
         """(rows int32 [S], Te): what a stream_feed_lookahead of n_frames[b] new rows per slot would emit now (host only)."""
-        S, fin, fin_p = self._stream_audio_args(n_frames, last)
-        n = _i32(np.asarray([int(x) for x in n_frames])).ravel()
-        rows, Te = np.zeros(S, np.int32), c_int(0)
-        self._ck(self.lib.nasr_stream_lookahead_rows(self.h, _ip(n), fin_p, _ip(rows), byref(Te)))
-        return rows, int(Te.value)
+        return self._stream_rows_then_feed(self.lib.nasr_stream_lookahead_rows, _i32(np.asarray([int(x) for x in n_frames])).ravel(), last)
 
     def stream_feed_lookahead(self, feats, n_frames, last=None):
         """One feed: feats [S,Tc,F] (Tc may be 0), n_frames [S] in [0,Tc], last[b] true declares slot b's utterance
         complete.  Returns (logits [Te,S,C], rows int32 [S]): slot b's rows_b emitted rows are logits[:rows_b, b]; Te = 0
         when the feed emitted nothing."""
-        S, fin, fin_p = self._stream_audio_args(n_frames, last)
+        S, _ = self._stream_slots_and_last(n_frames, last)
         feats = _f32(feats)
         F = int(self.cfg.feature_size)
         if feats.ndim != 3 or feats.shape[0] != S or feats.shape[2] != F:
             raise ValueError('feats must be [%d, Tc, %d], not %s' % (S, F, feats.shape))
-        Tc = int(feats.shape[1])
         n = _i32(np.asarray([int(x) for x in n_frames])).ravel()
-        # (the library refuses these too; here they must not size the output array first)
-        rows, Te = self.stream_lookahead_rows(np.clip(n, 0, None), last)
-        out = np.empty((Te, S, self.num_classes), np.float32)
-        got, Te2 = np.zeros(S, np.int32), c_int(0)
-        self._ck(self.lib.nasr_stream_feed_lookahead(self.h, _fp(feats) if feats.size else None, _ip(n), fin_p, Tc, _ip(got),
-                                                     byref(Te2), _fp(out) if out.size else None, Te))
-        assert Te2.value == Te and np.array_equal(got, rows)
-        return out, got
+        # (the library refuses negative counts too; here they must not size the output array first)
+        return self._stream_rows_then_feed(
+            self.lib.nasr_stream_lookahead_rows, np.clip(n, 0, None), last,
+            lambda fin_p, got, Te2, out, Te: self.lib.nasr_stream_feed_lookahead(
+                self.h, _fp(feats) if feats.size else None, _ip(n), fin_p, int(feats.shape[1]), got, Te2, out, Te))
 
     def stream_frames(self):
         out = np.zeros(getattr(self, '_stream_slots', 0), np.int64)

@@ -36,13 +36,34 @@ class StreamingRecognizer:
             self.engine.stream_open(self.slots)
         else:
             self.engine.stream_open_lookahead(self.slots, self.lookahead)
-        self._open_rows = [False] * self.slots   # look-ahead: the slot has rows that no `last` has flushed yet
+        # per slot, what finish() has to complete first: None, 'rows' (look-ahead: rows that no `last` has flushed yet) or
+        # 'audio' (feed_audio: samples that no `last` has completed yet)
+        self._open = [None] * self.slots
         lm = network.language_model()
         width = network.beam_width if getattr(network, 'decoder', 'beam') == 'beam' else 1
         kw = {} if lm is None else dict(lm=lm, lm_weight=network.config.lm_weight, lm_bonus=network.config.lm_bonus)
         self.beams = [BeamStream(network.num_classes, width, True, **kw) for _ in range(self.slots)]
         self._audio = False                      # feed_audio attached the network's featurizer to the session
-        self._open_audio = [False] * self.slots  # the slot holds audio that no `last` has completed yet
+
+    def _padded(self, arrs, n):
+        """the chunk [slots, max n, F]: slot b's n[b] rows, zeros behind them"""
+        feats = np.zeros((self.slots, int(n.max()), self.feature_size), np.float32)
+        for b, a in enumerate(arrs):
+            if n[b]:
+                feats[b, :n[b]] = a
+        return feats
+
+    def _deliver(self, logits, rows, got, last, kind):
+        """Hands every slot's rows[b] emitted rows to its beam and notes what is open: a slot that got input is `kind`
+        until a `last` completes it.  Returns the current hypothesis of every slot."""
+        for b in range(self.slots):
+            if rows[b]:
+                self.beams[b].feed(logits[:rows[b]], slot=b)
+            if last is not None and last[b]:
+                self._open[b] = None
+            elif got[b] and kind:
+                self._open[b] = kind
+        return [beam.best()[0] for beam in self.beams]
 
     def feed(self, chunks, last=None):
         """chunks: one entry per slot, float32 [n_b, F] (the slot's next frames) or None (the slot is idle).  Pads to the
@@ -56,33 +77,14 @@ class StreamingRecognizer:
             if a is not None and (a.ndim != 2 or a.shape[1] != self.feature_size):
                 raise ValueError('a chunk must be [n, %d], not %s' % (self.feature_size, a.shape))
         n = np.asarray([0 if a is None else a.shape[0] for a in arrs], dtype=np.int32)
-        Tc = int(n.max())
         if self.lookahead is not None:
-            feats = np.zeros((self.slots, Tc, self.feature_size), np.float32)
-            for b, a in enumerate(arrs):
-                if n[b]:
-                    feats[b, :n[b]] = a
-            logits, rows = self.engine.stream_feed_lookahead(feats, n, last)
-            for b in range(self.slots):
-                if rows[b]:
-                    self.beams[b].feed(logits[:rows[b]], slot=b)
-                if last is not None and last[b]:
-                    self._open_rows[b] = False
-                elif n[b]:
-                    self._open_rows[b] = True
-            return [beam.best()[0] for beam in self.beams]
+            logits, rows = self.engine.stream_feed_lookahead(self._padded(arrs, n), n, last)
+            return self._deliver(logits, rows, n, last, 'rows')
         if last is not None and any(last):
             raise ValueError('`last` means something only with a look-ahead')
-        if Tc > 0:
-            feats = np.zeros((self.slots, Tc, self.feature_size), np.float32)
-            for b, a in enumerate(arrs):
-                if n[b]:
-                    feats[b, :n[b]] = a
-            logits = self.engine.stream_feed(feats, n)
-            for b in range(self.slots):
-                if n[b]:
-                    self.beams[b].feed(logits[:n[b]], slot=b)
-        return [beam.best()[0] for beam in self.beams]
+        if n.max() == 0:                         # (the library refuses a chunk without rows)
+            return [beam.best()[0] for beam in self.beams]
+        return self._deliver(self.engine.stream_feed(self._padded(arrs, n), n), n, n, None, None)
 
     def feed_audio(self, chunks, last=None):
         """chunks: one entry per slot, float32 [n_b] samples at config.samplerate (the slot's next samples) or None (the
@@ -96,14 +98,7 @@ class StreamingRecognizer:
             self.engine.stream_attach_audio(self.network.featurizer())
             self._audio = True
         logits, rows = self.engine.stream_feed_audio(chunks, last)
-        for b in range(self.slots):
-            if rows[b]:
-                self.beams[b].feed(logits[:rows[b]], slot=b)
-            if last is not None and last[b]:
-                self._open_audio[b] = False
-            elif chunks[b] is not None and np.size(chunks[b]):
-                self._open_audio[b] = True
-        return [beam.best()[0] for beam in self.beams]
+        return self._deliver(logits, rows, [c is not None and np.size(c) for c in chunks], last, 'audio')
 
     def hypothesis(self, slot=0):
         """(ids, log-probability) of `slot` as it stands."""
@@ -112,10 +107,9 @@ class StreamingRecognizer:
     def finish(self, slot=0):
         """The final (ids, log-probability) of `slot`; the slot's device state and beam then start a new utterance.  A
         slot whose audio (feed_audio) no `last` has completed is completed first, with an empty feed."""
-        if self._open_audio[slot]:
-            self.feed_audio([None] * self.slots, [b == slot for b in range(self.slots)])
-        elif self._open_rows[slot]:
-            self.feed([None] * self.slots, [b == slot for b in range(self.slots)])
+        if self._open[slot]:
+            flush = self.feed_audio if self._open[slot] == 'audio' else self.feed
+            flush([None] * self.slots, [b == slot for b in range(self.slots)])
         out = self.beams[slot].best()
         self.engine.stream_reset([slot])
         self.beams[slot].reset()
