@@ -515,6 +515,30 @@ int nasr_stream_lookahead_rows(nasr_handle h, const int32_t* n_frames, const uin
 int nasr_stream_feed_lookahead(nasr_handle h, const float* feats, const int32_t* n_frames, const uint8_t* last, int Tc,
                                int32_t* rows_out, int* Te_out, float* logits_out, int64_t logits_rows);
 
+/* ---- training and evaluating a bidirectional network as a look-ahead session runs it ---------------
+ * (No counterpart in the reference, which trains and decodes whole utterances.)  Latency-controlled training: with chunk
+ * length C >= 1 and look-ahead R >= 1 set, EVERY whole-batch pass of the handle - nasr_forward*, nasr_greedy_decode*,
+ * nasr_loss*, nasr_loss_and_grads, nasr_compute_grads, nasr_train_step, nasr_ctc_align and nasr_ctc_align_resident - runs,
+ * for each utterance of T_b frames on its own, the windows k = 0, 1, ... of rows [kC, min(kC + C + R, T_b)): the first
+ * window that reaches the utterance's end is its last and emits all its rows, every earlier one emits its first C.  In
+ * every layer the forward direction continues from its state after the last row the window before emitted (zero for
+ * window 0), the backward direction starts from zero at the window's last row, and all the window's rows go up to the
+ * next layer.  The utterance's logits are the emitted rows in order; projection, CTC loss, decoding and alignment read
+ * them as ever.  These are the logits a session of nasr_stream_open_lookahead(h, S, R) returns when it is fed C + R rows,
+ * then C rows per feed, then the rest with `last`; with C + R >= T_b it is the whole-utterance network.  Gradients flow
+ * through the carried forward state; two runs give the same bits.  The passes run on the per-step kernels whatever
+ * nasr_get_recurrence_mode says and leave that mode alone; stream sessions, parameters, Adam state, gradient buckets,
+ * clipping and checkpoints are unaffected.  The recurrence's activations take (C + R) / C times the memory.
+ * C = 0 (R ignored) turns it off: the default.  A change drops the resident batch (the next *_resident call or
+ * nasr_compute_grads needs a new upload), and a batch staged before the change is refused at nasr_commit_batch.
+ * NASR_ERR_ARG: C outside [1,4096] (and not 0), R outside [1,1024].  NASR_ERR_STATE, with the reason in nasr_last_error and
+ * nothing changed: a unidirectional config (its graph is causal already); NASR_MERGE_STACK_RESHAPE; dense stages (the
+ * DeepSpeech family, in this version); a dropout probability > 0; a WaveNet, LAS or featurizer handle; an open stream
+ * session.  A batch whose windows need more than 2^22 rows is refused at its upload (NASR_ERR_ARG). */
+int nasr_set_chunking(nasr_handle h, int C, int R);
+/* *C, *R (either nullable) as set; 0, 0 when off. */
+int nasr_get_chunking(nasr_handle h, int* C, int* R);
+
 /* The CTC beam search as a state that lives between calls - host only, the procedure and arithmetic of
  * nasr_ctc_beam_search(_lm), which is open + one feed + best + close on this very code: feeding an utterance's frames in
  * any split gives its ids and log-probability bit for bit.  One handle per thread. */

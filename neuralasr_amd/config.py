@@ -24,7 +24,10 @@ responses), noise_prob / rir_prob (the share of utterances that get one, in [0,1
 noise_snr=lo,hi (dB, lo <= hi, default 10,20); without them nothing changes, and only the training feed reads them.  One
 more optional [Parameters] key, stream_lookahead (frames, 0..1024, default 0 = off), is the look-ahead with which a
 bidirectional network streams (HipNetwork.stream, decode_wav --stream; the reference decodes whole
-utterances); unidirectional networks ignore it."""
+utterances); unidirectional networks ignore it.  One more optional [Parameters] key, chunk_frames (frames, 0..4096, default
+0 = off), trains and evaluates a bidirectional network as a look-ahead session runs it: windows of
+chunk_frames + stream_lookahead rows, the forward state carried from window to window, the backward direction restarted
+in each; it needs stream_lookahead >= 1, and train, validate, evaluate, decode and align all read it."""
 import importlib
 import math
 from configparser import ConfigParser, ExtendedInterpolation
@@ -88,6 +91,16 @@ class Config(object):
         if not 0 <= self.stream_lookahead <= 1024:
             raise ValueError("'stream_lookahead' must be an integer in [0,1024], not %r, in %s"
                              % (par['stream_lookahead'], configfile))
+        # rows a window of latency-controlled training emits: 0 = off, the whole-utterance graph
+        try:
+            self.chunk_frames = int(par['chunk_frames'].strip()) if 'chunk_frames' in par else 0
+        except ValueError:
+            self.chunk_frames = -1
+        if not 0 <= self.chunk_frames <= 4096:
+            raise ValueError("'chunk_frames' must be an integer in [0,4096], not %r, in %s" % (par['chunk_frames'], configfile))
+        if self.chunk_frames > 0 and self.stream_lookahead < 1:
+            raise ValueError("'chunk_frames' needs 'stream_lookahead' >= 1 (the window is chunk_frames + stream_lookahead rows), in %s"
+                             % configfile)
         self.frame_width = self.numcep * (1 + self.deltas)
         self.feature_size = (2 * self.numcontext + 1) * self.frame_width
         self.lm_file = par['lm_file'].strip() if 'lm_file' in par else None
@@ -206,7 +219,7 @@ class Config(object):
         return network_class(self.network)(self, fortraining=fortraining)
 
     def print_config(self):
-        names = ['samplerate', 'numcep', 'numcontext', 'features', 'deltas', 'normalization', 'norm_min_frames', 'stream_lookahead', 'rand_shift', 'batch_size', 'epochs', 'learningrate',
+        names = ['samplerate', 'numcep', 'numcontext', 'features', 'deltas', 'normalization', 'norm_min_frames', 'stream_lookahead', 'chunk_frames', 'rand_shift', 'batch_size', 'epochs', 'learningrate',
                  'model_dir', 'start_step', 'report_step', 'num_gpus', 'label_context', 'punc_regex', 'network',
                  'sym_file', 'train_input', 'test_input', 'mfcc_input', 'mfcc_output', 'start_marker', 'end_marker']
         lines = ['']

@@ -159,6 +159,41 @@ int lstm_bwd_partials(int Hp);
 void launch_lstm_bwd_step(const LstmDims& dm, int s, const float* Ub, const float* pin, float* pout,
                           const float* gates, float* dgbuf, const float* cbuf, const float* dout, const float* dcin,
                           float* dcout, const int* seq_len, hipStream_t st);
+// step 0 of a window's BPTT (below): the same kernels in their carry form - the forward step started from the carried c0
+// [D][Bp][Hp] (zeros for a backward direction) instead of 0.  What the launch leaves in pout and dcout is, as after every
+// step, dG x U^T and dc . f: here the gradient with respect to the carried (h, c).
+void launch_lstm_bwd_step_carry(const LstmDims& dm, const float* Ub, const float* pin, float* pout, const float* gates,
+                                float* dgbuf, const float* cbuf, const float* dout, const float* dcin, float* dcout,
+                                const int* seq_len, const float* c0, hipStream_t st);
+
+// ---- latency-controlled training (lstm.hip): the batch as the windows of a look-ahead session ----
+// Window k of an utterance of len frames holds frames [k*C, min(k*C + W, len)), W = C + R (or the batch's T when that is
+// less: one window then); the first window that reaches
+// the utterance's end is its last and emits all its rows, every earlier one emits its first C.  The windows of a batch lie on
+// a virtual time axis of K windows x W rows: row (k*W + tl)*Bp + b.
+struct LcGeom { int C, W, K, T, Bp; };   // K = lc_last_window(T) + 1 for the batch's T
+__host__ __device__ inline int lc_last_window(int len, int C, int W) { return len <= W ? 0 : (len - W + C - 1) / C; }
+__host__ __device__ inline int lc_window_rows(int len, int k, int C, int W) {
+  if (len < 1 || k > lc_last_window(len, C, W)) return 0;
+  return len - k * C < W ? len - k * C : W;
+}
+// src [T*Bp][F] by frame -> dst [K*W*Bp][F] by window row (zeros where wlen [K][Bp] gives a window no such row)
+void launch_lc_gather(const float* src, const int* wlen, float* dst, const LcGeom& g, int F, hipStream_t st);
+// the emitted rows of outv [K*W*Bp][DH] by frame into top [T*Bp][DH] (zeros from seq_len[b] on), and the transpose: doutv
+// gets dtop's row in every emitted window row and zeros in the look-ahead rows and the rows no window has
+void launch_lc_emit(const float* outv, const int* seq_len, float* top, const LcGeom& g, int DH, hipStream_t st);
+void launch_lc_scatter(const float* dtop, const int* seq_len, const int* wlen, float* doutv, const LcGeom& g, int DH,
+                       hipStream_t st);
+// what step 0 of window k starts from, as launch_stream_load_state writes it: direction 0 from row C-1 of window k-1 of
+// out / cbuf (this layer's, [K*W*Bp][D*Hp]); zeros for window 0, the other directions and utterances without rows in window k
+void launch_lc_load_carry(const float* out, const float* cbuf, const int* wlen, int k, const LcGeom& g, float* himg, float* cimg,
+                          int Hp, int D, hipStream_t st);
+// behind step 0 of window k's BPTT: drow [Bp][DH] (row C-1 of window k-1 of dout) += the sum of direction 0's np partial
+// sums, dcc [Bp][Hp] = its dcout; zeros for utterances without rows in window k (wlen_k [Bp]).  launch_lc_carry_dc adds dcc
+// to the dcin [n = Bp*Hp] that step C-1 of window k-1 reads.
+void launch_lc_carry_out(const float* part, int np, const float* dcs, const int* wlen_k, float* drow, float* dcc, int Bp, int Hp,
+                         int DH, hipStream_t st);
+void launch_lc_carry_dc(float* dcin, const float* dcc, int n, hipStream_t st);
 
 // ---- persistent recurrence (lstm_persist.hip): one launch per layer pass, one XCD per (direction, utterance slice) ----
 // the head of every resident kernel's control block (the first bytes of PersistCtl and WideCtl): placement and abort,

@@ -400,7 +400,11 @@ void launch_la_window(const float* hold_in, const float* fresh, const LaSlots& s
 // and does the cell arithmetic ONCE per cell (writing dG frame-indexed), and this kernel runs with PRE = true: its P
 // stage only copies its dG slice from that buffer, and each block walks KSL = 4 consecutive K slices with the
 // accumulators kept in registers, so 4x fewer partial sums are handed on.
-template <int MT, int KSP, bool PRE = false, int KSL = 1>
+// CARRY: the counterpart of lstm_fwd_step_kernel<.., CARRY> for a window of latency-controlled training,
+// launched for step 0 only.  The forward step started from the carried c0 [D][Bp][Hp] (zeros for a backward direction)
+// instead of 0, so the forget gate's derivative reads it.  Nothing else differs: dcout is dc . f and the partial sums are
+// dG x U^T at every step, which after step 0 are the gradients with respect to the carried (c, h).
+template <int MT, int KSP, bool PRE = false, int KSL = 1, bool CARRY = false>
 __global__ __launch_bounds__(256) void lstm_bwd_step_kernel(
     const float* __restrict__ Ub,     // [D][Hp/64][Hp/32][4][4][2][64][4]
     const float* __restrict__ pin,    // [D][KSPLIT][Bp][Hp] partial sums of dh_rec from the previous launch
@@ -408,7 +412,8 @@ __global__ __launch_bounds__(256) void lstm_bwd_step_kernel(
     const float* __restrict__ gates,  // [R][D*N4] activations si,tj,sf,so
     float* __restrict__ dgbuf,        // [R][D*N4] dG, frame indexed
     const float* __restrict__ cbuf, const float* __restrict__ dout, const float* __restrict__ dcin,
-    float* __restrict__ dcout, const int* __restrict__ seq_len, int s, int T, int Bp, int Hp, int D) {
+    float* __restrict__ dcout, const int* __restrict__ seq_len, int s, int T, int Bp, int Hp, int D,
+    const float* __restrict__ c0) {
   // wide form (PRE): the reduction buffer reuses the dG slice's LDS (32 KB instead of 49 KB at MT = 2), so that the four
   // blocks a CU gets at Hp = 2048 are resident together instead of three and a straggler
   constexpr int AS_FLOATS = MT * 128 * 17, RED_FLOATS = 4 * MT * 4 * 64 * 4;
@@ -480,7 +485,8 @@ __global__ __launch_bounds__(256) void lstm_bwd_step_kernel(
       const int rp = s > 0 ? (d ? r + Bp : r - Bp) : r;
       a[e] = *reinterpret_cast<const float4*>(gates + (size_t)r * DN + d * N4 + 4 * j);  // si,tj,sf,so
       cc[e] = cbuf[(size_t)r * DH + d * Hp + j];
-      cpv[e] = cbuf[(size_t)(val[e] ? rp : r) * DH + d * Hp + j];
+      if constexpr (CARRY) cpv[e] = c0[((size_t)d * Bp + b) * Hp + j];
+      else cpv[e] = cbuf[(size_t)(val[e] ? rp : r) * DH + d * Hp + j];
       dh[e] = dout[(size_t)r * DH + d * Hp + j];
       dci[e] = dcin[((size_t)d * Bp + b) * Hp + j];
       const float* pp = pbase + (size_t)b * Hp + j;
@@ -505,7 +511,7 @@ __global__ __launch_bounds__(256) void lstm_bwd_step_kernel(
         float dhs = dh[e];
 #pragma unroll
         for (int k = 0; k < KV; ++k) dhs += pv[e][k];
-        dg = to_float4(lstm_cell_bwd(to_f32x4(a[e]), cc[e], cpv[e], s == 0, dhs, dci[e], dcn));
+        dg = to_float4(lstm_cell_bwd(to_f32x4(a[e]), cc[e], cpv[e], !CARRY && s == 0, dhs, dci[e], dcn));
       }
       if (jt == 0) {   // the frame of a masked step is frame s itself (past seq_len in both directions): dG = 0 there
         const size_t row = val[e] ? (size_t)rr[e] : (size_t)s * Bp + b;
@@ -598,32 +604,203 @@ __global__ __launch_bounds__(256) void lstm_bwd_cell_kernel(const float* __restr
   dcout[((size_t)d * Bp + b) * Hp + j] = dcn;
 }
 
+// The same for step 0 of a window whose forward step started from the carried c0 [D][Bp][Hp] (the CARRY form of
+// lstm_bwd_step_kernel).  A kernel of its own: sharing the body changes the instruction schedule of the one above.
+__global__ __launch_bounds__(256) void lstm_bwd_cell_carry_kernel(const float* __restrict__ pin, int NP,
+                                                                  const float* __restrict__ gates, float* __restrict__ dgbuf,
+                                                                  const float* __restrict__ cbuf, const float* __restrict__ dout,
+                                                                  const float* __restrict__ dcin, float* __restrict__ dcout,
+                                                                  const int* __restrict__ seq_len, int Bp, int Hp, int D,
+                                                                  const float* __restrict__ c0) {
+  const int c = blockIdx.x * 256 + threadIdx.x, d = blockIdx.y;
+  if (c >= Bp * Hp) return;
+  const int j = c % Hp, b = c / Hp;
+  const int N4 = 4 * Hp, DH = D * Hp, DN = D * N4;
+  const int len = seq_len[b];
+  const bool val = len > 0;
+  const size_t r = (size_t)(val && d ? len - 1 : 0) * Bp + b;
+  float4 dg = make_float4(0.f, 0.f, 0.f, 0.f);
+  float dcn = 0.f;
+  if (val) {
+    const float* pp = pin + (size_t)d * NP * Bp * Hp + (size_t)b * Hp + j;
+    float dhs = dout[r * DH + d * Hp + j];
+    float s0 = 0.f, s1 = 0.f;
+    int k = 0;
+    for (; k + 1 < NP; k += 2) { s0 += pp[(size_t)k * Bp * Hp]; s1 += pp[(size_t)(k + 1) * Bp * Hp]; }
+    if (k < NP) s0 += pp[(size_t)k * Bp * Hp];
+    dhs += s0 + s1;
+    const float4 a = *reinterpret_cast<const float4*>(gates + r * DN + d * N4 + 4 * j);
+    dg = to_float4(lstm_cell_bwd(to_f32x4(a), cbuf[r * DH + d * Hp + j], c0[((size_t)d * Bp + b) * Hp + j], false, dhs,
+                                 dcin[((size_t)d * Bp + b) * Hp + j], dcn));
+  }
+  *reinterpret_cast<float4*>(dgbuf + r * DN + d * N4 + 4 * j) = dg;
+  dcout[((size_t)d * Bp + b) * Hp + j] = dcn;
+}
+
 // partial sums a BPTT step hands on: Hp/32 of them per output, Hp/128 for the wide-layer form
 constexpr int BWD_KSL = 4;   // K slices a block of the wide form walks (A/B: 2, 4, 8)
 static bool bwd_wide_form(int Hp) { return Hp > 512 && Hp % (32 * BWD_KSL) == 0; }
 int lstm_bwd_partials(int Hp) { return bwd_wide_form(Hp) ? Hp / (32 * BWD_KSL) : Hp / 32; }
 
-void launch_lstm_bwd_step(const LstmDims& dm, int s, const float* Ub, const float* pin, float* pout,
-                          const float* gates, float* dgbuf, const float* cbuf, const float* dout, const float* dcin,
-                          float* dcout, const int* seq_len, hipStream_t st) {
+// c0 == NULL: step s of a sequence; c0 != NULL (s = 0): step 0 of a window that continued from the carried c0
+static void bwd_step(const LstmDims& dm, int s, const float* Ub, const float* pin, float* pout, const float* gates, float* dgbuf,
+                     const float* cbuf, const float* dout, const float* dcin, float* dcout, const int* seq_len, const float* c0,
+                     hipStream_t st) {
   if (bwd_wide_form(dm.Hp)) {     // wide layer: cell arithmetic once, then the product (see the kernel's header)
     const int np = dm.Hp / (32 * BWD_KSL);
-    hipLaunchKernelGGL(lstm_bwd_cell_kernel, dim3((dm.Bp * dm.Hp + 255) / 256, dm.D), dim3(256), 0, st, pin, np, gates, dgbuf,
-                       cbuf, dout, dcin, dcout, seq_len, s, dm.Bp, dm.Hp, dm.D);
+    const dim3 gridc((dm.Bp * dm.Hp + 255) / 256, dm.D);
+    if (c0)
+      hipLaunchKernelGGL(lstm_bwd_cell_carry_kernel, gridc, dim3(256), 0, st, pin, np, gates, dgbuf, cbuf, dout, dcin, dcout,
+                         seq_len, dm.Bp, dm.Hp, dm.D, c0);
+    else
+      hipLaunchKernelGGL(lstm_bwd_cell_kernel, gridc, dim3(256), 0, st, pin, np, gates, dgbuf, cbuf, dout, dcin, dcout, seq_len, s,
+                         dm.Bp, dm.Hp, dm.D);
     dim3 gridw((dm.Hp / 64) * np, dm.D);
     dispatch_int(StepMT{}, dm.Bp / 16, [&](auto mt) {
       hipLaunchKernelGGL((lstm_bwd_step_kernel<mt(), 0, true, BWD_KSL>), gridw, dim3(256), 0, st, Ub, pin, pout, gates, dgbuf,
-                         cbuf, dout, dcin, dcout, seq_len, s, dm.T, dm.Bp, dm.Hp, dm.D);
+                         cbuf, dout, dcin, dcout, seq_len, s, dm.T, dm.Bp, dm.Hp, dm.D, static_cast<const float*>(nullptr));
     });
     return;
   }
   dim3 grid((dm.Hp / 64) * (dm.Hp / 32), dm.D), block(256);
   dispatch_int(StepMT{}, dm.Bp / 16, [&](auto mt) {
     dispatch_int(std::integer_sequence<int, 2, 4, 8, 16, 0>{}, dm.Hp / 32, [&](auto ksp) {   // KSP = Hp/32, 0 = the generic form
-      hipLaunchKernelGGL((lstm_bwd_step_kernel<mt(), ksp()>), grid, block, 0, st, Ub, pin, pout, gates, dgbuf, cbuf, dout,
-                         dcin, dcout, seq_len, s, dm.T, dm.Bp, dm.Hp, dm.D);
+      if (c0)
+        hipLaunchKernelGGL((lstm_bwd_step_kernel<mt(), ksp(), false, 1, true>), grid, block, 0, st, Ub, pin, pout, gates, dgbuf,
+                           cbuf, dout, dcin, dcout, seq_len, 0, dm.T, dm.Bp, dm.Hp, dm.D, c0);
+      else
+        hipLaunchKernelGGL((lstm_bwd_step_kernel<mt(), ksp()>), grid, block, 0, st, Ub, pin, pout, gates, dgbuf, cbuf, dout,
+                           dcin, dcout, seq_len, s, dm.T, dm.Bp, dm.Hp, dm.D, static_cast<const float*>(nullptr));
     });
   });
+}
+
+void launch_lstm_bwd_step(const LstmDims& dm, int s, const float* Ub, const float* pin, float* pout,
+                          const float* gates, float* dgbuf, const float* cbuf, const float* dout, const float* dcin,
+                          float* dcout, const int* seq_len, hipStream_t st) {
+  bwd_step(dm, s, Ub, pin, pout, gates, dgbuf, cbuf, dout, dcin, dcout, seq_len, nullptr, st);
+}
+
+// step 0 of a window's BPTT: c0 = the carried c [D][Bp][Hp] its forward step 0 started from
+void launch_lstm_bwd_step_carry(const LstmDims& dm, const float* Ub, const float* pin, float* pout, const float* gates,
+                                float* dgbuf, const float* cbuf, const float* dout, const float* dcin, float* dcout,
+                                const int* seq_len, const float* c0, hipStream_t st) {
+  bwd_step(dm, 0, Ub, pin, pout, gates, dgbuf, cbuf, dout, dcin, dcout, seq_len, c0, st);
+}
+
+// ------------------------------------------------------------------ latency-controlled training (nasr_pass.hip)
+// The windows of every utterance lie one behind the other on a virtual time axis of K windows x W = C + R rows: row
+// (k*W + tl)*Bp + b is row tl of window k of utterance b, which is frame k*C + tl.  wlen [K][Bp] = the rows of each window
+// (lc_window_rows: 0 behind an utterance's last window and in the padded batch rows).
+
+// src [T*Bp][F] by frame -> dst [K*W*Bp][F] by window row, zeros where a window has no row.  One block per window row.
+__global__ __launch_bounds__(256) void lc_gather_kernel(const float* __restrict__ src, const int* __restrict__ wlen,
+                                                        float* __restrict__ dst, LcGeom g, int F) {
+  const int r = blockIdx.x, b = r % g.Bp, vt = r / g.Bp;
+  const int k = vt / g.W, tl = vt - k * g.W;
+  const float* sp = tl < wlen[k * g.Bp + b] ? src + ((size_t)(k * g.C + tl) * g.Bp + b) * F : nullptr;
+  float* dp = dst + (size_t)r * F;
+  for (int i = threadIdx.x; i < F; i += blockDim.x) dp[i] = sp ? sp[i] : 0.f;
+}
+
+// The top layer's EMITTED rows by frame: top [T*Bp][DH] <- outv [K*W*Bp][DH]; frame t of utterance b is row t - k*C of
+// window k = min(t / C, its last window); zeros from seq_len[b] on.  One block per frame row.
+__global__ __launch_bounds__(256) void lc_emit_kernel(const float* __restrict__ outv, const int* __restrict__ seq_len,
+                                                      float* __restrict__ top, LcGeom g, int DH) {
+  const int r = blockIdx.x, b = r % g.Bp, t = r / g.Bp;
+  const int len = seq_len[b];
+  const float* sp = nullptr;
+  if (t < len) {
+    const int k = min(t / g.C, lc_last_window(len, g.C, g.W));
+    sp = outv + ((size_t)(k * g.W + t - k * g.C) * g.Bp + b) * DH;
+  }
+  float* dp = top + (size_t)r * DH;
+  for (int i = threadIdx.x; i < DH; i += blockDim.x) dp[i] = sp ? sp[i] : 0.f;
+}
+
+// ... and its transpose: the gradient of the top layer's window rows from the gradient by frame.  An emitted row gets its
+// frame's gradient, a look-ahead row (tl >= C in a window that is not the utterance's last) and a row no window has get 0.
+// Every window row is written by its own block: no sum, no atomics.
+__global__ __launch_bounds__(256) void lc_scatter_kernel(const float* __restrict__ dtop, const int* __restrict__ seq_len,
+                                                         const int* __restrict__ wlen, float* __restrict__ doutv, LcGeom g,
+                                                         int DH) {
+  const int r = blockIdx.x, b = r % g.Bp, vt = r / g.Bp;
+  const int k = vt / g.W, tl = vt - k * g.W;
+  const int P = wlen[k * g.Bp + b];
+  const int E = k == lc_last_window(seq_len[b], g.C, g.W) ? P : min(P, g.C);
+  const float* sp = tl < E ? dtop + ((size_t)(k * g.C + tl) * g.Bp + b) * DH : nullptr;
+  float* dp = doutv + (size_t)r * DH;
+  for (int i = threadIdx.x; i < DH; i += blockDim.x) dp[i] = sp ? sp[i] : 0.f;
+}
+
+// What step 0 of window k reads, for every direction (blockIdx.y), as stream_load_state_kernel writes it for a feed: the h
+// operand image and c [Bp][Hp].  Direction 0 continues from row C-1 of window k-1 of this layer's out / cbuf [K*W*Bp][DH]
+// (the state after the last row that window emitted); window 0, a backward direction and an utterance without rows in
+// window k start from zeros.  Every element is written.
+__global__ __launch_bounds__(256) void lc_load_carry_kernel(const float* __restrict__ out, const float* __restrict__ cbuf,
+                                                            const int* __restrict__ wlen, int k, LcGeom g,
+                                                            float* __restrict__ himg, float* __restrict__ cimg, int Hp, int DH) {
+  const int e = blockIdx.x * 256 + threadIdx.x, d = blockIdx.y;
+  if (e >= g.Bp * Hp) return;
+  const int b = e / Hp, j = e - b * Hp;
+  float c = 0.f, hv = 0.f;
+  if (d == 0 && k > 0 && wlen[k * g.Bp + b] > 0) {
+    const size_t r = (size_t)((k - 1) * g.W + g.C - 1) * g.Bp + b;
+    c = cbuf[r * DH + j];
+    hv = out[r * DH + j];
+  }
+  cimg[(size_t)d * g.Bp * Hp + e] = c;
+  himg[(size_t)d * g.Bp * Hp + sw_index(Hp, b >> 4, b & 15, j)] = hv;
+}
+
+// Behind step 0 of window k's BPTT (k >= 1): the gradient with respect to the forward direction's carried (h, c) goes to
+// where the state came from.  dh = the NP partial sums that launch left (direction 0: the head of `part`), summed in their
+// order, is ADDED to the forward half of window k-1's row C-1 of dout (drow = that row, [Bp][DH]); dc = its dcout is kept
+// in dcc [Bp][Hp] until window k-1's BPTT reaches that step (lc_carry_dc_kernel).  An utterance without rows in window k
+// hands back zeros.  One thread per (b, j): one writer, fixed order.
+__global__ __launch_bounds__(256) void lc_carry_out_kernel(const float* __restrict__ part, int NP, const float* __restrict__ dcs,
+                                                           const int* __restrict__ wlen_k, float* __restrict__ drow,
+                                                           float* __restrict__ dcc, int Bp, int Hp, int DH) {
+  const int e = blockIdx.x * 256 + threadIdx.x;
+  if (e >= Bp * Hp) return;
+  const int b = e / Hp, j = e - b * Hp;
+  float dc = 0.f;
+  if (wlen_k[b] > 0) {
+    float dh = 0.f;
+    for (int p = 0; p < NP; ++p) dh += part[(size_t)p * Bp * Hp + e];
+    drow[(size_t)b * DH + j] += dh;
+    dc = dcs[e];
+  }
+  dcc[e] = dc;
+}
+
+// ... dc joins the chain: dcin [Bp][Hp] is what the forward direction's BPTT step C-1 of window k-1 is about to read
+__global__ __launch_bounds__(256) void lc_carry_dc_kernel(float* __restrict__ dcin, const float* __restrict__ dcc, int n) {
+  const int e = blockIdx.x * 256 + threadIdx.x;
+  if (e < n) dcin[e] += dcc[e];
+}
+
+void launch_lc_gather(const float* src, const int* wlen, float* dst, const LcGeom& g, int F, hipStream_t st) {
+  hipLaunchKernelGGL(lc_gather_kernel, dim3(g.K * g.W * g.Bp), dim3(256), 0, st, src, wlen, dst, g, F);
+}
+void launch_lc_emit(const float* outv, const int* seq_len, float* top, const LcGeom& g, int DH, hipStream_t st) {
+  hipLaunchKernelGGL(lc_emit_kernel, dim3(g.T * g.Bp), dim3(256), 0, st, outv, seq_len, top, g, DH);
+}
+void launch_lc_scatter(const float* dtop, const int* seq_len, const int* wlen, float* doutv, const LcGeom& g, int DH,
+                       hipStream_t st) {
+  hipLaunchKernelGGL(lc_scatter_kernel, dim3(g.K * g.W * g.Bp), dim3(256), 0, st, dtop, seq_len, wlen, doutv, g, DH);
+}
+void launch_lc_load_carry(const float* out, const float* cbuf, const int* wlen, int k, const LcGeom& g, float* himg, float* cimg,
+                          int Hp, int D, hipStream_t st) {
+  hipLaunchKernelGGL(lc_load_carry_kernel, dim3((g.Bp * Hp + 255) / 256, D), dim3(256), 0, st, out, cbuf, wlen, k, g, himg, cimg,
+                     Hp, D * Hp);
+}
+void launch_lc_carry_out(const float* part, int np, const float* dcs, const int* wlen_k, float* drow, float* dcc, int Bp, int Hp,
+                         int DH, hipStream_t st) {
+  hipLaunchKernelGGL(lc_carry_out_kernel, dim3((Bp * Hp + 255) / 256), dim3(256), 0, st, part, np, dcs, wlen_k, drow, dcc, Bp, Hp, DH);
+}
+void launch_lc_carry_dc(float* dcin, const float* dcc, int n, hipStream_t st) {
+  hipLaunchKernelGGL(lc_carry_dc_kernel, dim3((n + 255) / 256), dim3(256), 0, st, dcin, dcc, n);
 }
 
 }  // namespace nasr

@@ -803,6 +803,46 @@ int nasr_set_row_compaction(nasr_handle h, int enabled) {
   return NASR_OK;
 }
 
+int nasr_set_chunking(nasr_handle h, int C, int R) {
+  MODEL_CALL(h);
+  if (!h) return NASR_ERR_ARG;
+  LSTM_CALL(h, "has no bidirectional recurrence to run in windows");
+  const std::string fn = "nasr_set_chunking";
+  if (h->stream) return h->fail(NASR_ERR_STATE, fn + ": a stream session is open: close it first");
+  if (C != 0) {
+    if (C < 1 || C > 4096) return h->fail(NASR_ERR_ARG, fn + ": C = " + std::to_string(C) + " chunk frames: must be in [1,4096], or 0 = off");
+    if (R < 1 || R > 1024) return h->fail(NASR_ERR_ARG, fn + ": R = " + std::to_string(R) + " look-ahead frames: must be in [1,1024]");
+    if (!h->cfg.bidirectional)
+      return h->fail(NASR_ERR_STATE, fn + ": a unidirectional network needs no look-ahead: its graph is causal already");
+    if (h->cfg.merge != NASR_MERGE_CONCAT)
+      return h->fail(NASR_ERR_STATE, fn + ": NASR_MERGE_STACK_RESHAPE cannot stream: its logits mix frames of the whole padded batch, so "
+                                          "no chunk of it is a point in time");
+    for (int i = 0; i < 4; ++i)
+      if (h->cfg.dropout[i] != 0.f)
+        return h->fail(NASR_ERR_STATE, fn + ": dropout[" + std::to_string(i) + "] = " + std::to_string(h->cfg.dropout[i]) +
+                                           ": a network with dropout cannot stream (the reference applies dropout in every graph, "
+                                           "keyed by the pass counter)");
+    if (h->ndense)
+      return h->fail(NASR_ERR_STATE, fn + ": a network with dense stages (the DeepSpeech family) is not trained in windows yet");
+  }
+  const int Rn = C ? R : 0;
+  if (C == h->lcC && Rn == h->lcR) return NASR_OK;
+  h->lcC = C;
+  h->lcR = Rn;
+  // the resident batch is laid out for the setting it was uploaded under: the next pass needs a new upload
+  h->resident = false;
+  h->have_grads = h->have_fwd = h->have_decoded = false;
+  return NASR_OK;
+}
+
+int nasr_get_chunking(nasr_handle h, int* C, int* R) {
+  MODEL_CALL(h);
+  if (!h) return NASR_ERR_ARG;
+  if (C) *C = h->lcC;
+  if (R) *R = h->lcR;
+  return NASR_OK;
+}
+
 int nasr_resident_rows(nasr_handle h, int64_t* rows) {
   MODEL_CALL(h);
   if (!h || !rows) return NASR_ERR_ARG;
@@ -1122,7 +1162,7 @@ int nasr_set_wgrad_overlap(nasr_handle h, int enabled) {
                                                          "(needs the persistent recurrence at Hp = 512 and more than one layer)");
   HIPCHK(h, hipStreamSynchronize(h->st));
   h->wg_overlap = enabled != 0;
-  if (h->resident) return ensure_shape(h, h->B, h->T, h->Lmax);     // the side stream's own copies of the dG planes
+  if (h->resident) return ensure_shape(h, h->B, h->T, h->Lmax, h->lc_live);     // the side stream's own copies of the dG planes
   return NASR_OK;
 }
 

@@ -31,7 +31,7 @@ int ensure_ctc_buffers(nasr_ctx* h, int B, int Bp, int T, int Tp, int Lmax, bool
   return KSa;
 }
 
-int ensure_shape(nasr_ctx* h, int B, int T, int Lmax) {
+int ensure_shape(nasr_ctx* h, int B, int T, int Lmax, bool chunked) {
   switch (h->family) {
     case Family::WaveNet: return wn_ensure_shape(h, B, T, Lmax);
     case Family::Las: return las_ensure_shape(h, B, T, Lmax);
@@ -39,13 +39,27 @@ int ensure_shape(nasr_ctx* h, int B, int T, int Lmax) {
   }
   const int Bp = rup(B, 16);
   const int Tp = nasr_logit_frames(h, T);
-  const size_t R = (size_t)T * Bp;
+  // the LSTM stack's time axis: the batch's frames, or the rows of its windows
+  LcGeom lg{};
+  if (chunked) {
+    lg.C = h->lcC; lg.W = std::min(h->lcC + h->lcR, T); lg.K = lc_last_window(T, lg.C, lg.W) + 1; lg.T = T; lg.Bp = Bp;
+    if ((int64_t)lg.K * lg.W * Bp > ((int64_t)1 << 22))
+      return h->fail(NASR_ERR_ARG, "chunked batch: " + std::to_string(lg.K) + " windows of " + std::to_string(lg.W) + " rows x " +
+                                       std::to_string(Bp) + " utterances are more than 2^22 rows: use a longer chunk or a shorter look-ahead");
+  }
+  const int Tv = chunked ? lg.K * lg.W : T;
+  const size_t R = (size_t)Tv * Bp;
   const int D = h->D, Hp = h->Hp, N4 = h->N4;
   bool grew = false;
   bool ok = true;
   const int KSa = ensure_ctc_buffers(h, B, Bp, T, Tp, Lmax, &grew);
   if (KSa < 0) return KSa;
   ok &= h->X0.ensure(R * h->Fp * 4, &grew);
+  if (chunked) {
+    ok &= h->lc_x0.ensure((size_t)T * Bp * h->Fp * 4, &grew);
+    ok &= h->lc_top.ensure((size_t)T * Bp * h->Pinp * 4, &grew) && h->lc_dtop.ensure((size_t)T * Bp * h->Pinp * 4, &grew);
+    ok &= h->lc_cimg.ensure((size_t)D * Bp * Hp * 4, &grew) && h->lc_dcc.ensure((size_t)Bp * Hp * 4, &grew);
+  }
   ok &= h->seqbuf.ensure((size_t)Bp * 4, &grew);
   ok &= h->dout.ensure(R * D * Hp * 4, &grew);
   ok &= h->hstate.ensure((size_t)2 * D * Bp * Hp * 4, &grew);
@@ -79,7 +93,7 @@ int ensure_shape(nasr_ctx* h, int B, int T, int Lmax) {
       }
       ok &= h->sc_x0r.ensure(R) && h->sc_x0c.ensure((size_t)h->Fp);
       ok &= h->sc_gr.ensure(R) && h->sc_gc.ensure((size_t)wmax);
-      if (h->compactable) {
+      if (h->compactable || chunked) {
         ok &= h->sc_cr.ensure(R + 64) && h->sc_cx.ensure(R + 64);
         ok &= h->OTS.ensure((h->wg_overlap ? 2 : 1) * tph_bytes(D * Hp, (int)R), &grew);
       }
@@ -105,6 +119,7 @@ int ensure_shape(nasr_ctx* h, int B, int T, int Lmax) {
   if (!ok) return h->fail(NASR_ERR_HIP, "hipMalloc failed while sizing batch buffers");
   if (grew || Bp != h->Bp) drop_graphs(h);
   h->B = B; h->Bp = Bp; h->T = T; h->Lmax = Lmax; h->Tp = Tp; h->KS = KSa;
+  h->Tv = Tv; h->lc_live = chunked; h->lcg = lg;
   return NASR_OK;
 }
 
@@ -261,12 +276,27 @@ static void meta_layout(nasr_ctx* h, BatchSlot* s, const BatchSrc& b, bool maske
   // 10 %), and only for training batches
   s->cmp = h->compactable && b.labels && s->frames * 20 <= (int64_t)T * s->Bp * 17;
   s->Rv = s->cmp ? (int)s->frames : 0;
+  // a batch under nasr_set_chunking: the row lists are those of its windows, always (a stream chunk is no such batch)
+  const bool lc = h->family == Family::Lstm && h->lcC > 0 && !b.chunk;
+  s->chunk = b.chunk;
+  s->lcC = lc ? h->lcC : 0; s->lcR = lc ? h->lcR : 0;
+  s->lcW = lc ? std::min(s->lcC + s->lcR, T) : 0;      // (a window never has more rows than the batch has frames)
+  s->lcK = lc ? lc_last_window(T, s->lcC, s->lcW) + 1 : 0;
+  if (lc) {
+    int64_t rows = 0;
+    for (int i = 0; i < B; ++i)
+      for (int k = 0; k < s->lcK; ++k) rows += lc_window_rows(b.seq_len[i], k, s->lcC, s->lcW);
+    s->cmp = true;
+    s->Rv = (int)std::min<int64_t>(rows, (int64_t)1 << 22);   // (more: ensure_shape refuses the batch at commit)
+  }
   s->Rvp = s->cmp ? rup(s->Rv, 64) : 0;
   s->o_vrow = s->o_rowmap + (stack_reshape(h) ? (size_t)s->Tp * s->Bp : 0);
   s->o_vprev = s->o_vrow + s->Rvp;
   s->o_vnext = s->o_vprev + s->Rvp;
-  s->o_aug = (s->o_vnext + s->Rvp + 3) / 4 * 4;      // (the kernel reads a mask as one int4)
-  s->nmeta = masked ? s->o_aug + (size_t)B * s->aug_nm * 4 : s->o_vnext + s->Rvp;
+  s->o_wlen = s->o_vnext + s->Rvp;
+  const size_t end = s->o_wlen + (size_t)s->lcK * s->Bp;
+  s->o_aug = (end + 3) / 4 * 4;      // (the kernel reads a mask as one int4)
+  s->nmeta = masked ? s->o_aug + (size_t)B * s->aug_nm * 4 : end;
   s->nfeat = s->centre ? (size_t)B * T * b.ncep + B : (size_t)B * T * h->F;
 }
 
@@ -306,7 +336,28 @@ static void write_meta(const nasr_ctx* h, BatchSlot* s, const BatchSrc& src) {
         map[(size_t)tp * Bp + bq] = (t * Bp + b) * 2 + d;
       }
   }
-  if (s->cmp) {
+  if (s->lcC) {
+    // The rows of the windows, window-major: vprev / vnext stay inside a window, except that the row before a window's
+    // first one is the row its forward state was carried from, row C-1 of the window before (the h_{t-1} operand of the
+    // recurrent weight gradient, as everywhere).
+    const int Cc = s->lcC, W = s->lcW;
+    int32_t *vr = m + s->o_vrow, *vp = m + s->o_vprev, *vn = m + s->o_vnext, *wl = m + s->o_wlen;
+    int i = 0;
+    for (int k = 0; k < s->lcK; ++k) {
+      for (int b = 0; b < B; ++b) wl[(size_t)k * Bp + b] = lc_window_rows(seq_len[b], k, Cc, W);
+      for (int tl = 0; tl < W && i < s->Rv; ++tl)
+        for (int b = 0; b < B && i < s->Rv; ++b) {
+          const int P = wl[(size_t)k * Bp + b];
+          if (tl >= P) continue;
+          const int r = (k * W + tl) * Bp + b;
+          vr[i] = r;
+          vp[i] = tl > 0 ? r - Bp : k > 0 ? ((k - 1) * W + Cc - 1) * Bp + b : -1;
+          vn[i] = tl + 1 < P ? r + Bp : -1;
+          ++i;
+        }
+    }
+    for (; i < s->Rvp; ++i) vr[i] = vp[i] = vn[i] = -1;
+  } else if (s->cmp) {
     int32_t *vr = m + s->o_vrow, *vp = m + s->o_vprev, *vn = m + s->o_vnext;
     int i = 0;
     for (int t = 0; t < T; ++t)
@@ -385,7 +436,10 @@ static int slot_fill(nasr_ctx* h, BatchSlot* s, const BatchSrc& b, hipStream_t c
 // released, and the features are laid out for the step (time-major rows, context windows, operand scales).
 int slot_commit(nasr_ctx* h, BatchSlot* s) {
   HIPCHK(h, hipSetDevice(h->device));
-  int rc = ensure_shape(h, s->B, s->T, s->Lmax);
+  // (a slot is laid out for the chunking of the moment it was filled; a stream chunk never is)
+  if (h->family == Family::Lstm && !s->chunk && (s->lcC != h->lcC || s->lcR != (h->lcC ? h->lcR : 0)))
+    return h->fail(NASR_ERR_STATE, "the batch was staged under another nasr_set_chunking than the handle has now: stage it again");
+  int rc = ensure_shape(h, s->B, s->T, s->Lmax, s->lcC > 0);
   if (rc) return rc;
   const int B = s->B, T = s->T, Bp = h->Bp;
   {
@@ -405,7 +459,8 @@ int slot_commit(nasr_ctx* h, BatchSlot* s) {
   HIPCHK(h, hipMemcpyAsync(h->seqbuf.p, md + s->o_seq, (size_t)Bp * 4, hipMemcpyDeviceToDevice, h->st));
   h->seq_p = h->seqbuf.as<int32_t>(); h->lablen_p = md + s->o_lablen; h->labels_p = md + s->o_labels;
   h->cstart_p = md + s->o_cstart; h->cpos_p = md + s->o_cpos; h->rowmap_p = md + s->o_rowmap;
-  const bool cmp = s->cmp && h->compactable;      // (staged with it on, switched off since: the slot's row lists go unused)
+  const bool cmp = s->cmp && (h->compactable || s->lcC);   // (staged with it on, switched off since: the slot's row lists go unused)
+  h->wlen_p = md + s->o_wlen;
   h->cmp_rows = cmp ? s->Rv : 0;
   h->cmp_rows_p = cmp ? s->Rvp : 0;
   h->vrow_p = md + s->o_vrow; h->vprev_p = md + s->o_vprev; h->vnext_p = md + s->o_vnext;
@@ -422,23 +477,25 @@ int slot_commit(nasr_ctx* h, BatchSlot* s) {
   h->frames = s->frames;
   {
     PhaseScope ps(h, PH_PACK);
+    float* x0 = (h->lc_live ? h->lc_x0 : h->X0).as<float>();   // a chunked batch: the rows by frame first
     if (s->centre && s->masked)
       launch_expand_context_masked(s->dfeats.as<float>(), s->dfeats.as<float>() + (size_t)B * T * s->ncep, h->seq_p,
-                                   md + s->o_aug, s->aug_nm, s->aug_sw, h->X0.as<float>(), B, Bp, T, s->ctx, s->ncep,
+                                   md + s->o_aug, s->aug_nm, s->aug_sw, x0, B, Bp, T, s->ctx, s->ncep,
                                    h->Fp, h->st);
     else if (s->centre)
       launch_expand_context(s->dfeats.as<float>(), s->dfeats.as<float>() + (size_t)B * T * s->ncep, h->seq_p,
-                            h->X0.as<float>(), B, Bp, T, s->ctx, s->ncep, h->Fp, h->st);
+                            x0, B, Bp, T, s->ctx, s->ncep, h->Fp, h->st);
     else
-      launch_pack_feats(s->dfeats.as<float>(), h->X0.as<float>(), B, Bp, T, h->F, h->Fp, h->st);
+      launch_pack_feats(s->dfeats.as<float>(), x0, B, Bp, T, h->F, h->Fp, h->st);
+    if (h->lc_live) launch_lc_gather(x0, h->wlen_p, h->X0.as<float>(), h->lcg, h->Fp, h->st);   // ... and into the windows' rows
     const bool lstm = h->family == Family::Lstm;
     if (lstm)   // (the WaveNet's and LAS's GEMMs read the fp32 features as they are)
-      pl_scales(h, h->X0.as<float>(), T * Bp, h->Fp, h->Fp, &h->sc_x0r, &h->sc_x0c, h->st);
+      pl_scales(h, h->X0.as<float>(), h->Tv * Bp, h->Fp, h->Fp, &h->sc_x0r, &h->sc_x0c, h->st);
     if (h->cmp_rows)    // the feature rows' scales in the compacted order (layer 0's input GEMM)
       launch_gather_rows(h->sc_cx.sp(), h->sc_x0r.sp(), h->vrow_p, h->cmp_rows_p, 1.f, h->st),
       launch_gather_rows(h->sc_cx.ip(), h->sc_x0r.ip(), h->vrow_p, h->cmp_rows_p, 1.f, h->st);
     if (s->has_labels && h->npre == 0 && lstm)   // layer-0 input with the frame index as contraction index, for dWx = X^T dG
-      launch_tph_split2(h->X0.as<float>(), nullptr, h->X0TTP.as<unsigned char>(), h->cmp_rows ? h->cmp_rows : T * Bp, h->Fp, h->Fp,
+      launch_tph_split2(h->X0.as<float>(), nullptr, h->X0TTP.as<unsigned char>(), h->cmp_rows ? h->cmp_rows : h->Tv * Bp, h->Fp, h->Fp,
                         nullptr, 1.f, h->sc_x0c.sp(), 1.f, nullptr, h->st, h->cmp_rows ? h->vrow_p : nullptr);
     HIPCHK(h, hipGetLastError());
   }

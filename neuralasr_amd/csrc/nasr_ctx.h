@@ -170,6 +170,11 @@ struct BatchSlot {
   size_t o_vrow = 0, o_vprev = 0, o_vnext = 0;   // compacted rows of a ragged batch (Rv of them, padded to Rvp with -1), or unused
   int Rv = 0, Rvp = 0;
   bool cmp = false;
+  // latency-controlled training (nasr_set_chunking as it stood when the slot was filled; lcC = 0: a whole-utterance batch):
+  // the compacted rows above are then the rows of the utterances' windows, and o_wlen holds wlen [lcK][Bp]
+  int lcC = 0, lcR = 0, lcK = 0, lcW = 0;        // lcW = min(lcC + lcR, T) rows per window, lcK windows
+  bool chunk = false;                            // a chunk of a stream session (BatchSrc::chunk)
+  size_t o_wlen = 0;
   size_t nmeta = 0, nfeat = 0;                   // int32s of meta, floats of dfeats
   // SpecAugment masks of a centre-form batch (nasr_batch_aug): [B][aug_nm] of {t0, tw, f0, fw} at o_aug, or none
   size_t o_aug = 0;
@@ -364,6 +369,20 @@ struct nasr_ctx {
   // resident batch
   bool resident = false, have_grads = false, have_fwd = false;
   int B = 0, Bp = 0, T = 0, Lmax = 0, Tp = 0, KS = 1;
+  // Latency-controlled training (nasr_set_chunking): lcC > 0 = every whole-batch pass runs the utterances'
+  // windows of lcC + lcR rows.  The LSTM stack then works on a virtual time axis of Tv = K*W rows (kernels.h, LcGeom) - its
+  // activations, planes and gradients are sized and indexed by Tv, always through the compacted-row lists (cmp_rows: the
+  // rows the windows have; vprev / vnext stop at a window's edges, vprev of a window's first row is the row the forward
+  // state was carried from) - while the projection and the CTC stay on the T frames: lc_top / lc_dtop hold the top layer's
+  // emitted rows and their gradient by frame.  Tv = T and lc_live = false for every other batch (a stream chunk included).
+  int lcC = 0, lcR = 0;
+  int Tv = 0;
+  bool lc_live = false;                      // the resident batch is laid out in windows
+  LcGeom lcg{};
+  int32_t* wlen_p = nullptr;                 // [K][Bp] rows of every window (inside cur->dmeta)
+  DevBuf lc_x0, lc_top, lc_dtop;             // features by frame [T*Bp][Fp]; top layer's emitted rows / their gradient [T*Bp][Pinp]
+  DevBuf lc_cimg, lc_dcc;                    // the carried c of the window being run [D][Bp][Hp]; carried dc [Bp][Hp]
+  uint64_t lc_uf_seq = ~0ull;                // repack_seq of the per-step operand images the chunked passes built themselves
   int64_t frames = 0;
   std::vector<int32_t> h_seq;
   BatchSlot slots[NSLOT];
@@ -543,7 +562,8 @@ std::vector<TphScaleJob> rec_scale_jobs(const nasr_ctx* h);   // repack: scale j
 void rec_images(nasr_ctx* h);
 
 // ---- nasr_batch.hip
-int ensure_shape(nasr_ctx* h, int B, int T, int Lmax);
+// chunked: the batch is laid out in the windows of nasr_set_chunking (h->lcC, h->lcR)
+int ensure_shape(nasr_ctx* h, int B, int T, int Lmax, bool chunked = false);
 // the logits and what the CTC lattice, its loss and the greedy decoder work in (T frames, Tp logit frames); returns the
 // lattice kernel's instantiation for labels up to Lmax (h->KS), or the code of a failure (< 0)
 int ensure_ctc_buffers(nasr_ctx* h, int B, int Bp, int T, int Tp, int Lmax, bool* grew);
@@ -681,6 +701,10 @@ inline float* fp(const DevBuf& b, size_t off = 0) { return b.as<float>() + off; 
 // chunk: the resident batch is a chunk of the open stream session - the recurrence continues from the session's state on
 // the per-step kernels and saves it again; the fault word, the resident kinds' control blocks and the dropout counter stay
 int forward(nasr_ctx* h, bool chunk = false);
+// One layer pass of the recurrence over the resident batch's windows (h->lc_live), on the per-step kernels whatever kind
+// the handle runs: forward window by window, each from the state carried out of the one before; BPTT in reverse order,
+// the carried state's gradient handed back to the window it came from.
+int lc_run_steps(nasr_ctx* h, int l, bool bwd, hipStream_t st, int* launches);
 // forward pass and loss of the resident batch.  training: the WaveNet's batch norm on the batch's statistics (a LAS
 // handle samples either way, one counter value per pass)
 int loss_pass(nasr_ctx* h, bool training);

@@ -63,6 +63,59 @@ int run_steps(nasr_ctx* h, int l, bool bwd, int s0, int s1, hipStream_t st, int*
   return NASR_OK;
 }
 
+// The same over the windows of a chunked batch (h->lc_live).  Window k of layer l is rows [k*W, (k+1)*W) of
+// the layer's buffers with wlen[k] as its seq_len: to the step kernels a batch of W frames.  No graph, as a stream feed has
+// none: step 0 is another kernel than the rest.
+int lc_run_steps(nasr_ctx* h, int l, bool bwd, hipStream_t st, int* launches) {
+  const LcGeom& g = h->lcg;
+  const int Bp = h->Bp, Hp = h->Hp, D = h->D, W = g.W;
+  const LstmDims dm{W, h->B, Bp, h->H, Hp, D};
+  const int np = lstm_bwd_partials(Hp);
+  const size_t sU = (size_t)l * D * Hp * h->N4, hs = (size_t)D * Bp * Hp, ps = (size_t)D * np * Bp * Hp;
+  const size_t wr = (size_t)W * Bp;                  // rows of a window
+  const int DH = D * Hp, DN = D * h->N4;
+  float *hst = h->hstate.as<float>(), *par = h->partial.as<float>(), *dcs = h->dcstate.as<float>();
+  float *cimg = h->lc_cimg.as<float>(), *dcc = h->lc_dcc.as<float>();
+  float *gt = h->gates[l].as<float>(), *cb = h->cbuf[l].as<float>(), *ob = h->outb[l].as<float>();
+  if (!bwd) {
+    for (int k = 0; k < g.K; ++k) {
+      const int* wl = h->wlen_p + (size_t)k * Bp;
+      float *gk = gt + k * wr * DN, *ck = cb + k * wr * DH, *ok = ob + k * wr * DH;
+      launch_lc_load_carry(ob, cb, h->wlen_p, k, g, hst, cimg, Hp, D, st);
+      launch_lstm_fwd_step_carry(dm, h->Uf + sU, hst, hst + hs, gk, ck, ok, wl, h->cfg.forget_bias, cimg, st);
+      for (int s = 1; s < W; ++s)
+        launch_lstm_fwd_step(dm, s, h->Uf + sU, hst + (s & 1) * hs, hst + ((s + 1) & 1) * hs, gk, ck, ok, wl, h->cfg.forget_bias, st);
+    }
+  } else {
+    float* dov = dout_of(h, l);
+    for (int k = g.K - 1; k >= 0; --k) {
+      const int* wl = h->wlen_p + (size_t)k * Bp;
+      const float *gk = gt + k * wr * DN, *ck = cb + k * wr * DH;
+      float *dgk = dg_of(h, l) + k * wr * DN, *dok = dov + k * wr * DH;
+      (void)hipMemsetAsync(par, 0, ps * 4, st);
+      (void)hipMemsetAsync(dcs, 0, hs * 4, st);
+      for (int s = W - 1; s >= 1; --s) {
+        const int kk = W - 1 - s;
+        // the forward state after row C-1 went on into window k+1: so does its dc come back, into the chain at that step
+        if (s == g.C - 1 && k + 1 < g.K) launch_lc_carry_dc(dcs + (kk & 1) * hs, dcc, Bp * Hp, st);
+        launch_lstm_bwd_step(dm, s, h->Ub + sU, par + (kk & 1) * ps, par + ((kk + 1) & 1) * ps, gk, dgk, ck, dok,
+                             dcs + (kk & 1) * hs, dcs + ((kk + 1) & 1) * hs, wl, st);
+      }
+      const int k0 = W - 1;                            // step 0, in the carry form
+      if (g.C == 1 && k + 1 < g.K) launch_lc_carry_dc(dcs + (k0 & 1) * hs, dcc, Bp * Hp, st);
+      launch_lc_load_carry(ob, cb, h->wlen_p, k, g, hst, cimg, Hp, D, st);   // (hst: free during BPTT; only cimg is read)
+      launch_lstm_bwd_step_carry(dm, h->Ub + sU, par + (k0 & 1) * ps, par + ((k0 + 1) & 1) * ps, gk, dgk, ck, dok,
+                                 dcs + (k0 & 1) * hs, dcs + ((k0 + 1) & 1) * hs, wl, cimg, st);
+      if (k > 0)
+        launch_lc_carry_out(par + ((k0 + 1) & 1) * ps, np, dcs + ((k0 + 1) & 1) * hs, wl,
+                            dov + ((size_t)(k - 1) * W + g.C - 1) * Bp * DH, dcc, Bp, Hp, DH, st);
+    }
+  }
+  *launches += g.K * W;
+  HIPCHK(h, hipGetLastError());
+  return NASR_OK;
+}
+
 float* ensure_slabs(nasr_ctx* h, int split, int M, int N) {
   if (split <= 1) return nullptr;
   bool grew = false;
@@ -240,14 +293,22 @@ int forward(nasr_ctx* h, bool chunk) {
     default: break;
   }
   const int Bp = h->Bp, T = h->T, D = h->D, Hp = h->Hp;
-  const int R = T * Bp;
+  const int R = T * Bp, Rv = h->Tv * Bp;   // rows by frame; rows of the LSTM stack (the same but for a chunked batch)
+  const bool lc = h->lc_live;
+  if (lc && h->rec_use != RecKind::Step && h->lc_uf_seq != h->repack_seq) {
+    // (the per-step operand images, which repack() keeps only while the per-step kernels run the handle's batches: as a
+    // stream feed does, nasr_stream.hip)
+    for (size_t k = 0; k < h->off_u.size(); ++k)
+      launch_repack_u(h->P + h->off_u[k], h->Uf + k * h->Hp * h->N4, h->Ub + k * h->Hp * h->N4, h->Hp, h->st);
+    h->lc_uf_seq = h->repack_seq;
+  }
   h->n_fwd_launch = 0;
   std::fill(h->ott_valid.begin(), h->ott_valid.end(), 0);
   // the fault word of the pass that starts here (a training step or a forward-only call); what an unread earlier word
   // said is gone with it
   if (!chunk) HIPCHK(h, hipMemsetAsync(h->Gbase, 0, GRAD_HEAD * 4, h->st));
   // the control blocks of this pass's persistent launches, cleared in one go (one per layer: run_steps)
-  if (h->rec_use == RecKind::Persist && !chunk) {
+  if (h->rec_use == RecKind::Persist && !chunk && !lc) {
     HIPCHK(h, hipMemsetAsync(h->pctl + 1, 0, (size_t)h->L * sizeof(PersistCtl), h->st));
     HIPCHK(h, hipMemsetAsync(h->xchf, 0, (size_t)h->L * persist_hx_bytes(h->Hp), h->st));   // epoch 0 everywhere (lstm_persist.hip)
   }
@@ -259,12 +320,18 @@ int forward(nasr_ctx* h, bool chunk) {
   for (int l = 0; l < h->L; ++l) {
     {
       PhaseScope ps(h, PH_XPROJ);
-      gemm_xproj(h, l, R, h->st);
+      gemm_xproj(h, l, Rv, h->st);
       HIPCHK(h, hipGetLastError());
     }
     PhaseScope ps(h, PH_RECF);
-    int rc = chunk ? run_chunk_steps(h, l, h->st) : run_steps(h, l, false, 0, T, h->st, &h->n_fwd_launch);
+    int rc = chunk ? run_chunk_steps(h, l, h->st)
+             : lc  ? lc_run_steps(h, l, false, h->st, &h->n_fwd_launch)
+                   : run_steps(h, l, false, 0, T, h->st, &h->n_fwd_launch);
     if (rc) return rc;
+  }
+  if (lc) {   // the rows the windows emit, by frame: what the projection, and everything behind it, reads
+    PhaseScope ps(h, PH_RECF);
+    launch_lc_emit(h->outb[h->L - 1].as<float>(), h->seq_p, h->lc_top.as<float>(), h->lcg, D * Hp, h->st);
   }
   if (h->has_post) {
     PhaseScope ps(h, PH_XPROJ);
@@ -276,7 +343,7 @@ int forward(nasr_ctx* h, bool chunk) {
     PhaseScope ps(h, PH_PROJCTC);
     const bool sr = h->cfg.merge == NASR_MERGE_STACK_RESHAPE && D == 2;
     GemmDesc g{};
-    g.A = h->has_post ? h->Ybuf[h->npre].as<float>() : h->outb[h->L - 1].as<float>();
+    g.A = h->has_post ? h->Ybuf[h->npre].as<float>() : lc ? h->lc_top.as<float>() : h->outb[h->L - 1].as<float>();
     g.B = h->P + h->off_w;
     g.C = h->logits.as<float>();
     g.M = h->Tp * Bp; g.N = h->Cp; g.K = h->Pinp;
@@ -360,8 +427,8 @@ int loss_pass(nasr_ctx* h, bool training) {
 // weight / bias gradients of layer l from its complete dG, on stream ws: the main stream, or (side = true) the side stream
 // with the 3-wave GEMM instantiation that shares the CUs with the persistent BPTT launch of the layer below
 int weight_grads(nasr_ctx* h, int l, hipStream_t ws, bool side) {
-  const int Bp = h->Bp, T = h->T, D = h->D, Hp = h->Hp, N4 = h->N4;
-  const int R = T * Bp;
+  const int Bp = h->Bp, D = h->D, Hp = h->Hp, N4 = h->N4;
+  const int R = h->Tv * Bp;
   float* dG = dg_of(h, l);
   unsigned char* GT = gttp_of(h, l);
   float* cs_part = csws_of(h, l);
@@ -448,9 +515,11 @@ int backward(nasr_ctx* h) {
     default: break;
   }
   const int Bp = h->Bp, T = h->T, D = h->D, Hp = h->Hp;
-  const int R = T * Bp, Rp = h->Tp * Bp;
+  const int R = T * Bp, Rp = h->Tp * Bp, Rv = h->Tv * Bp;
   const bool sr = h->cfg.merge == NASR_MERGE_STACK_RESHAPE && D == 2;
-  if (h->rec_use == RecKind::Persist) {
+  const bool lc = h->lc_live;
+  const RecKind use = lc ? RecKind::Step : h->rec_use;   // a chunked batch: the per-step kernels, whatever the handle's kind
+  if (use == RecKind::Persist) {
     HIPCHK(h, hipMemsetAsync(h->pctl + 1 + h->L, 0, (size_t)h->L * sizeof(PersistCtl), h->st));
     HIPCHK(h, hipMemsetAsync(h->xchb, 0, (size_t)h->L * persist_px_bytes(), h->st));   // epoch 0 everywhere (lstm_persist.hip)
   }
@@ -466,7 +535,7 @@ int backward(nasr_ctx* h) {
     PhaseScope ps(h, PH_PROJB);
     // dW = gather(out)^T dlogits
     GemmDesc g{};
-    g.A = h->has_post ? h->Ybuf[h->npre].as<float>() : h->outb[h->L - 1].as<float>();
+    g.A = h->has_post ? h->Ybuf[h->npre].as<float>() : lc ? h->lc_top.as<float>() : h->outb[h->L - 1].as<float>();
     g.B = h->logits.as<float>();
     g.C = h->G + h->off_w;
     g.M = h->Pinp; g.N = h->Cp; g.K = Rp;
@@ -479,11 +548,13 @@ int backward(nasr_ctx* h) {
     GemmDesc x{};
     x.A = h->logits.as<float>();
     x.B = h->P + h->off_w;
-    x.C = h->has_post ? h->dYbuf[h->npre].as<float>() : dout_of(h, h->L - 1);
+    x.C = h->has_post ? h->dYbuf[h->npre].as<float>() : lc ? h->lc_dtop.as<float>() : dout_of(h, h->L - 1);
     x.M = Rp; x.N = h->Pinp; x.K = h->Cp;
     x.lda = h->Cp; x.ldb = h->Cp; x.ldc = sr ? Hp : h->Pinp;
     x.b_col = true; x.a_rows = Rp; x.c_map = sr ? h->rowmap_p : nullptr; x.split_k = 1;
     if (int rc = gemm_f32(h, x)) return rc;
+    // ... back onto the windows' rows: the look-ahead rows get no gradient from above
+    if (lc) launch_lc_scatter(h->lc_dtop.as<float>(), h->seq_p, h->wlen_p, dout_of(h, h->L - 1), h->lcg, D * Hp, h->st);
   }
   if (h->has_post) {
     PhaseScope ps(h, PH_WGRAD);
@@ -493,10 +564,10 @@ int backward(nasr_ctx* h) {
   h->n_bwd_launch = 0;
   h->dgmax_layer = -1;
   for (int l = h->L - 1; l >= 0; --l) {
-    const bool defer = h->rec_use != RecKind::Step && h->bucket_defer;
+    const bool defer = use != RecKind::Step && h->bucket_defer;
     {
       PhaseScope ps(h, PH_RECB);
-      int rc = run_steps(h, l, true, 0, T, h->st, &h->n_bwd_launch);
+      int rc = lc ? lc_run_steps(h, l, true, h->st, &h->n_bwd_launch) : run_steps(h, l, true, 0, T, h->st, &h->n_bwd_launch);
       if (rc) return rc;
     }
     if (defer && l + 1 < h->L && h->bucket_of_layer[l + 1] >= 0) {   // the layer above's bucket, held back over this launch
@@ -507,10 +578,10 @@ int backward(nasr_ctx* h) {
     // layer l+2's side-stream weight gradients read the plane buffers this layer's passes are about to rewrite (they
     // finished a BPTT launch ago: the wait costs nothing, it only makes the order formal)
     if (int rc = wg_join(h, l + 2)) return rc;
-    if (l > 0 || h->npre > 0) gemm_dx(h, l, R, h->st);   // critical path first
+    if (l > 0 || h->npre > 0) gemm_dx(h, l, Rv, h->st);   // critical path first
     // layer l's weight gradients feed nothing before Adam: with the overlap on they leave the main stream here and run
     // beside the persistent BPTT launch of layer l-1 (tfnetwork.py:120-128: the gradients are a set, nothing orders them)
-    const bool side = h->wg_overlap && h->rec_use == RecKind::Persist && l > 0 && h->gttp_layer == l;
+    const bool side = h->wg_overlap && use == RecKind::Persist && l > 0 && h->gttp_layer == l;
     if (side) {
       HIPCHK(h, hipEventRecord(h->ev_dx, h->st));
       HIPCHK(h, hipStreamWaitEvent(h->wst, h->ev_dx, 0));

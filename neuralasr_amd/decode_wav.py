@@ -96,8 +96,14 @@ def parse_args(argv=None):
                         help='feed the file in chunks to a causal network and log partial hypotheses: its samples when the '
                              'config says normalization=causal (a file at another rate is resampled whole on the GPU '
                              'first and then chunked), else the frames of the features computed over the whole file')
-    parser.add_argument('--chunk-frames', type=int, default=50,
-                        help='frames per chunk with --stream (default 50 = 0.5 s); samples are fed chunk-frames * frame_step at a time')
+    class _Given(argparse.Action):      # (main() tells a --chunk-frames that was given from the default)
+        def __call__(self, parser, namespace, values, option_string=None):
+            setattr(namespace, self.dest, values)
+            setattr(namespace, self.dest + '_given', True)
+    parser.set_defaults(chunk_frames_given=False)
+    parser.add_argument('--chunk-frames', type=int, default=50, action=_Given,
+                        help='frames per chunk with --stream (default: the config key chunk_frames when it is set, else 50 = 0.5 s); '
+                             'samples are fed chunk-frames * frame_step at a time')
     parser.add_argument('--lookahead-frames', type=int, default=None,
                         help='with --stream on a bidirectional network: frames of right context the backward direction gets '
                              'beyond the frames a feed emits (overrides the config key stream_lookahead)')
@@ -113,6 +119,8 @@ def main(argv=None):
     args = parse_args(argv)
     config = Config(args.config, True)
     network = config.load_network(fortraining=False)
+    if not args.chunk_frames_given and getattr(config, 'chunk_frames', 0) > 0:
+        args.chunk_frames = config.chunk_frames   # a model trained in windows is served with the chunk it was trained with
     if args.stream:
         if not hasattr(network, 'stream'):
             raise SystemExit('--stream: network %s cannot stream' % type(network).__name__)

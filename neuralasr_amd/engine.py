@@ -440,6 +440,20 @@ class Engine:
         number = tf.clip_by_global_norm's threshold, inf = measure the norm and skip non-finite gradients, never scale."""
         self._ck(self.lib.nasr_set_grad_clip(self.h, float(max_norm)))
 
+    def set_chunking(self, chunk_frames, lookahead=0):
+        """Latency-controlled training (include/nasr.h, nasr_set_chunking): from here on every whole-batch pass
+        (forward, loss, gradients, train_step, greedy decode, alignment) runs each utterance as the windows of a look-ahead
+        session fed chunk_frames + lookahead rows, then chunk_frames per feed.  chunk_frames = 0: off.  The library's
+        refusals (unidirectional, stack_reshape, dense stages, dropout, an open stream session) raise with its reason."""
+        self._ck(self.lib.nasr_set_chunking(self.h, int(chunk_frames), int(lookahead)))
+
+    @property
+    def chunking(self):
+        """(chunk_frames, lookahead) as set_chunking() set them; (0, 0) = off"""
+        c, r = c_int(), c_int()
+        self._ck(self.lib.nasr_get_chunking(self.h, byref(c), byref(r)))
+        return int(c.value), int(r.value)
+
     @property
     def grad_clip(self):
         """the threshold set_grad_clip() set; 0.0 = clipping is off"""

@@ -99,6 +99,10 @@ class HipNetwork(Network):
         self.engine = self.make_engine(config, device, stream)
         if fortraining and getattr(config, 'max_grad_norm', 0.0) > 0:
             self.engine.set_grad_clip(config.max_grad_norm)     # every apply_adam of every step path clips from here on
+        if getattr(config, 'chunk_frames', 0) > 0:
+            # chunk_frames: train, validate, evaluate, decode and align all run the graph a look-ahead session
+            # serves; a network that cannot (the library says why) fails here, on every rank alike
+            self.engine.set_chunking(config.chunk_frames, config.stream_lookahead)
         self.engine.set_step_decode(True)
         self.engine.set_params(self.initial_params(self.engine.tensors(), seed=1))
         self._grad_tensor = None
