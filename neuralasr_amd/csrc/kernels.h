@@ -101,19 +101,7 @@ int gemm_tph_pick_split(int M, int N, int K, int nbatch = 1);
 void launch_gemm_tph(const GemmTPHDesc& g, hipStream_t st);
 
 // ---- LSTM recurrence (lstm.hip) ----
-struct LstmDims {
-  int T, B, Bp, H, Hp, D;   // D directions
-};
-void launch_pack_feats(const float* feats_bm, float* X0, int B, int Bp, int T, int F, int Fp, hipStream_t st);
-void launch_expand_context(const float* centre, const float* pad, const int* seq_len, float* X0, int B, int Bp, int T,
-                           int ctx, int ncep, int Fp, hipStream_t st);
-// The same with SpecAugment masks on the centre frames (no counterpart in the reference): masks [B][nm] of
-// {t0, tw, f0, fw}, utterance b's k-th time mask over frames [t0, t0 + tw) and its k-th frequency mask over columns
-// [f0, f0 + fw) of each static_width-wide block of a frame; width 0 = no mask.  Masked centre values are 0, pads stay.
-// Uses 2*ctx+1 + ncep bytes of dynamic LDS.
-void launch_expand_context_masked(const float* centre, const float* pad, const int* seq_len, const int* masks, int nm,
-                                  int static_width, float* X0, int B, int Bp, int T, int ctx, int ncep, int Fp,
-                                  hipStream_t st);
+struct LstmDims { int T, B, Bp, H, Hp, D; };   // D directions
 // Contract of every recurrence launcher below and in the two sections that follow, on what is not computed
 // (tests/test_gpu_rec_kernels.py holds each of them to it):
 //   seq_len   Bp entries, 0 in the rows b >= B.  Frame t of row b is computed iff t < seq_len[b].  A row b < B may have
@@ -132,12 +120,34 @@ void launch_expand_context_masked(const float* centre, const float* pad, const i
 //             NOT been checked; the requirement above that U's padding is 0 rests on it.
 // repack canonical U [Hp][N4] of every (layer,dir) into the forward / backward MFMA B-operand images
 void launch_repack_u(const float* U, float* Uf, float* Ub, int Hp, hipStream_t st);
-void launch_lstm_fwd_step(const LstmDims& dm, int s, const float* Uf, const float* hin, float* hout, float* gates,
-                          float* cbuf, float* out, const int* seq_len, float forget_bias, hipStream_t st);
-// step 0 of a stream feed (nasr_stream.hip): the same kernel, continuing from hin = the saved h (operand image) and
-// c0 = the saved c [D][Bp][Hp] instead of starting a sequence
-void launch_lstm_fwd_step_carry(const LstmDims& dm, const float* Uf, const float* hin, float* hout, float* gates, float* cbuf,
-                                float* out, const int* seq_len, float forget_bias, const float* c0, hipStream_t st);
+// One layer's buffers as the per-step kernels see a window of dm.T steps: a whole batch, a stream feed's chunk, or one
+// window of a chunked batch (rows [k*W, (k+1)*W) of the layer's buffers with wlen[k] as its seq_len).
+int lstm_bwd_partials(int Hp);   // partial sums a BPTT step hands to the next, per output
+struct StepWindow {
+  LstmDims dm;
+  const float *Uf, *Ub;                 // [D] operand images of launch_repack_u
+  float *hstate, *partial, *dcstate;    // two images each, handed launch to launch: h [D][Bp*Hp] (operand layout), partial sums
+                                        // [D][lstm_bwd_partials(Hp)][Bp][Hp] of dh, dc [D][Bp][Hp]
+  float *gates, *cbuf, *out;            // [T*Bp][..]: forward in place / out; BPTT reads gates and cbuf
+  float* dg;                            // BPTT out: dG, frame indexed
+  const float* dout;                    // BPTT in: the gradient from above
+  const int* seq_len;
+  float forget_bias;
+  // NULL: the window starts a sequence, from an h image the forward runner zeroes itself.  Else step 0 runs in its carry
+  // form: forward from the h image already in hstate[0] and c0 [D][Bp][Hp] (launch_stream_load_state, launch_lc_load_carry)
+  // instead of zeros, and BPTT step 0 with the forget gate's derivative reading c0.  What BPTT step 0 leaves is then the
+  // gradient with respect to the carried (h, c): dG x U^T in its partial sums, dc . f in its dc image.
+  const float* c0;
+};
+// forward: steps [s0, s1), in order.  BPTT: steps s1-1 .. s0; the range that starts at the window's last step (s1 == dm.T)
+// first zeroes the partial-sum and dc images that step reads - once per window, however the window is cut into ranges (an
+// empty range enqueues nothing).  Ranges of one window run in order, with no other window between them.
+void lstm_steps_fwd(const StepWindow& w, int s0, int s1, hipStream_t st);
+void lstm_steps_bwd(const StepWindow& w, int s0, int s1, hipStream_t st);
+// the dc image [D][Bp][Hp] BPTT step s of the window will read, and the images step s has written
+struct StepLeft { float *partial, *dc; };
+float* lstm_steps_dcin(const StepWindow& w, int s);
+StepLeft lstm_steps_left(const StepWindow& w, int s);
 // A stream session's feed as the kernels see it (nasr_stream.hip), per slot: rows held before the feed,
 // new rows, rows the feed emits (without a look-ahead: 0, n, n).  Passed by value: a feed needs no upload of its own for them.
 constexpr int LA_MAX_SLOTS = 64;
@@ -149,24 +159,8 @@ struct LaSlots { int held[LA_MAX_SLOTS], n[LA_MAX_SLOTS], emit[LA_MAX_SLOTS]; };
 void launch_stream_load_state(const float* state, float* himg, float* cimg, int S, int H, int Bp, int Hp, hipStream_t st, int D = 1);
 void launch_stream_save_state(const float* out, const float* cbuf, const LaSlots& sl, float* state, int S, int H, int Bp, int DH,
                               hipStream_t st);
-// Window assembly: pending row t of slot b is hold_in [S][R][F] row t (t < held) or fresh [S][Tc][F] row t - held; rows
-// [0, P) of an emitting slot go to win [S][T][F] (zeros elsewhere; win NULL: nothing emits), rows [emit, P) to hold_out
-// [S][R][F], which must not be hold_in.  rows = the largest P, >= 1.
-void launch_la_window(const float* hold_in, const float* fresh, const LaSlots& sl, float* win, float* hold_out, int S, int R,
-                      int Tc, int T, int rows, int F, hipStream_t st);
-// BPTT step: pin/pout = [D][lstm_bwd_partials(Hp)][Bp][Hp] partial sums handed launch to launch, dcin/dcout = [D][Bp][Hp]
-int lstm_bwd_partials(int Hp);
-void launch_lstm_bwd_step(const LstmDims& dm, int s, const float* Ub, const float* pin, float* pout,
-                          const float* gates, float* dgbuf, const float* cbuf, const float* dout, const float* dcin,
-                          float* dcout, const int* seq_len, hipStream_t st);
-// step 0 of a window's BPTT (below): the same kernels in their carry form - the forward step started from the carried c0
-// [D][Bp][Hp] (zeros for a backward direction) instead of 0.  What the launch leaves in pout and dcout is, as after every
-// step, dG x U^T and dc . f: here the gradient with respect to the carried (h, c).
-void launch_lstm_bwd_step_carry(const LstmDims& dm, const float* Ub, const float* pin, float* pout, const float* gates,
-                                float* dgbuf, const float* cbuf, const float* dout, const float* dcin, float* dcout,
-                                const int* seq_len, const float* c0, hipStream_t st);
 
-// ---- latency-controlled training (lstm.hip): the batch as the windows of a look-ahead session ----
+// Latency-controlled training: the batch as the windows of a look-ahead session.
 // Window k of an utterance of len frames holds frames [k*C, min(k*C + W, len)), W = C + R (or the batch's T when that is
 // less: one window then); the first window that reaches
 // the utterance's end is its last and emits all its rows, every earlier one emits its first C.  The windows of a batch lie on
@@ -177,15 +171,9 @@ __host__ __device__ inline int lc_window_rows(int len, int k, int C, int W) {
   if (len < 1 || k > lc_last_window(len, C, W)) return 0;
   return len - k * C < W ? len - k * C : W;
 }
-// src [T*Bp][F] by frame -> dst [K*W*Bp][F] by window row (zeros where wlen [K][Bp] gives a window no such row)
-void launch_lc_gather(const float* src, const int* wlen, float* dst, const LcGeom& g, int F, hipStream_t st);
-// the emitted rows of outv [K*W*Bp][DH] by frame into top [T*Bp][DH] (zeros from seq_len[b] on), and the transpose: doutv
-// gets dtop's row in every emitted window row and zeros in the look-ahead rows and the rows no window has
-void launch_lc_emit(const float* outv, const int* seq_len, float* top, const LcGeom& g, int DH, hipStream_t st);
-void launch_lc_scatter(const float* dtop, const int* seq_len, const int* wlen, float* doutv, const LcGeom& g, int DH,
-                       hipStream_t st);
-// what step 0 of window k starts from, as launch_stream_load_state writes it: direction 0 from row C-1 of window k-1 of
-// out / cbuf (this layer's, [K*W*Bp][D*Hp]); zeros for window 0, the other directions and utterances without rows in window k
+// what step 0 of window k starts from, as launch_stream_load_state writes it (the same kernel): direction 0 from row C-1 of
+// window k-1 of out / cbuf (this layer's, [K*W*Bp][D*Hp]); zeros for window 0, the other directions and utterances without
+// rows in window k (wlen [K][Bp])
 void launch_lc_load_carry(const float* out, const float* cbuf, const int* wlen, int k, const LcGeom& g, float* himg, float* cimg,
                           int Hp, int D, hipStream_t st);
 // behind step 0 of window k's BPTT: drow [Bp][DH] (row C-1 of window k-1 of dout) += the sum of direction 0's np partial
@@ -194,6 +182,30 @@ void launch_lc_load_carry(const float* out, const float* cbuf, const int* wlen, 
 void launch_lc_carry_out(const float* part, int np, const float* dcs, const int* wlen_k, float* drow, float* dcc, int Bp, int Hp,
                          int DH, hipStream_t st);
 void launch_lc_carry_dc(float* dcin, const float* dcc, int n, hipStream_t st);
+
+// ---- row movers (rows.hip): features into the stack's rows, a look-ahead session's windows, a chunked batch's windows ----
+void launch_pack_feats(const float* feats_bm, float* X0, int B, int Bp, int T, int F, int Fp, hipStream_t st);
+void launch_expand_context(const float* centre, const float* pad, const int* seq_len, float* X0, int B, int Bp, int T,
+                           int ctx, int ncep, int Fp, hipStream_t st);
+// The same with SpecAugment masks on the centre frames (no counterpart in the reference): masks [B][nm] of
+// {t0, tw, f0, fw}, utterance b's k-th time mask over frames [t0, t0 + tw) and its k-th frequency mask over columns
+// [f0, f0 + fw) of each static_width-wide block of a frame; width 0 = no mask.  Masked centre values are 0, pads stay.
+// Uses 2*ctx+1 + ncep bytes of dynamic LDS.
+void launch_expand_context_masked(const float* centre, const float* pad, const int* seq_len, const int* masks, int nm,
+                                  int static_width, float* X0, int B, int Bp, int T, int ctx, int ncep, int Fp,
+                                  hipStream_t st);
+// Window assembly: pending row t of slot b is hold_in [S][R][F] row t (t < held) or fresh [S][Tc][F] row t - held; rows
+// [0, P) of an emitting slot go to win [S][T][F] (zeros elsewhere; win NULL: nothing emits), rows [emit, P) to hold_out
+// [S][R][F], which must not be hold_in.  rows = the largest P, >= 1.
+void launch_la_window(const float* hold_in, const float* fresh, const LaSlots& sl, float* win, float* hold_out, int S, int R,
+                      int Tc, int T, int rows, int F, hipStream_t st);
+// src [T*Bp][F] by frame -> dst [K*W*Bp][F] by window row (zeros where wlen [K][Bp] gives a window no such row)
+void launch_lc_gather(const float* src, const int* wlen, float* dst, const LcGeom& g, int F, hipStream_t st);
+// the emitted rows of outv [K*W*Bp][DH] by frame into top [T*Bp][DH] (zeros from seq_len[b] on), and the transpose: doutv
+// gets dtop's row in every emitted window row and zeros in the look-ahead rows and the rows no window has
+void launch_lc_emit(const float* outv, const int* seq_len, float* top, const LcGeom& g, int DH, hipStream_t st);
+void launch_lc_scatter(const float* dtop, const int* seq_len, const int* wlen, float* doutv, const LcGeom& g, int DH,
+                       hipStream_t st);
 
 // ---- persistent recurrence (lstm_persist.hip): one launch per layer pass, one XCD per (direction, utterance slice) ----
 // the head of every resident kernel's control block (the first bytes of PersistCtl and WideCtl): placement and abort,

@@ -1,4 +1,6 @@
-// lstm.hip — the per-timestep LSTM recurrence and its BPTT as gfx950 kernels.
+// lstm.hip — the per-timestep LSTM recurrence and its BPTT as gfx950 kernels: the repack of U into their operand images,
+// the step and cell kernels, the state a window of steps is carried in from and out to (a stream feed's, a training
+// window's), and the two runners that chain the launches of a window (StepWindow, kernels.h).
 //
 // Semantics (call sites networks/bilstm_ctc_net.py:17-28,
 // networks/lstm_ctc_net.py:17-23): g = [x,h]·kernel + bias, gates i,j,f,o,
@@ -34,109 +36,6 @@ namespace nasr {
 // contiguous 256-byte run (coalesced state write).
 __device__ __forceinline__ int sw_index(int Kd, int mt, int b16, int k) {
   return ((((mt * (Kd >> 4) + (k >> 4)) * 64) + ((k >> 2) & 3) * 16 + b16) << 2) + (k & 3);
-}
-
-// ------------------------------------------------------------------ feature transpose + pad
-// feats [B][T][F] batch-major (dataset.py:75-82) -> X0 [(t*Bp+b)][Fp], zero padded
-__global__ __launch_bounds__(256) void pack_feats_kernel(const float* __restrict__ f, float* __restrict__ x, int B,
-                                                         int Bp, int T, int F, int Fp) {
-  const int r = blockIdx.x;  // t*Bp + b
-  const int t = r / Bp, b = r % Bp;
-  float* dst = x + (size_t)r * Fp;
-  if (b >= B) {
-    for (int i = threadIdx.x; i < Fp; i += blockDim.x) dst[i] = 0.f;
-    return;
-  }
-  const float* src = f + ((size_t)b * T + t) * F;
-  for (int i = threadIdx.x; i < Fp; i += blockDim.x) dst[i] = i < F ? src[i] : 0.f;
-}
-
-void launch_pack_feats(const float* feats_bm, float* X0, int B, int Bp, int T, int F, int Fp, hipStream_t st) {
-  hipLaunchKernelGGL(pack_feats_kernel, dim3(T * Bp), dim3(256), 0, st, feats_bm, X0, B, Bp, T, F, Fp);
-}
-
-// include_context on the device (utils.py:8-21): the caller ships only the centre frame [B][T][numcep]; every
-// time-major row gets its (2*ctx+1)-frame window, out-of-range frames of an utterance filled with that
-// utterance's pad value (0 before the utterance-level normalisation of utils.py:29, (0-mean)/std after it),
-// frames past seq_len zero (dataset.py:75-77).  21x fewer bytes over PCIe for numcontext = 10.
-__global__ __launch_bounds__(256) void expand_context_kernel(const float* __restrict__ centre,
-                                                             const float* __restrict__ pad, const int* __restrict__ seq_len,
-                                                             float* __restrict__ x, int B, int Bp, int T, int ctx,
-                                                             int ncep, int Fp) {
-  const int r = blockIdx.x;  // t*Bp + b
-  const int t = r / Bp, b = r % Bp;
-  float* dst = x + (size_t)r * Fp;
-  const int len = b < B ? seq_len[b] : 0;
-  const int F = (2 * ctx + 1) * ncep;
-  for (int i = threadIdx.x; i < Fp; i += blockDim.x) {
-    float v = 0.f;
-    if (i < F && t < len) {
-      const int wdw = i / ncep, c = i - wdw * ncep;
-      const int ts = t + wdw - ctx;
-      v = (ts >= 0 && ts < len) ? centre[((size_t)b * T + ts) * ncep + c] : pad[b];
-    }
-    dst[i] = v;
-  }
-}
-
-void launch_expand_context(const float* centre, const float* pad, const int* seq_len, float* X0, int B, int Bp, int T,
-                           int ctx, int ncep, int Fp, hipStream_t st) {
-  hipLaunchKernelGGL(expand_context_kernel, dim3(T * Bp), dim3(256), 0, st, centre, pad, seq_len, X0, B, Bp, T, ctx,
-                     ncep, Fp);
-}
-
-// expand_context_kernel with SpecAugment masks (the reference has no augmentation but rand_shift): the
-// masks are applied to the utterance's normalised centre frames - 0 is their mean - and include_context runs on the
-// result, so a masked frame is masked in every window it appears in and the pads stay what they were.  masks [B][nm]:
-// {t0, tw, f0, fw}, validated on the host to lie inside the utterance and the static block.  The row's workgroup
-// decides one flag per window and one per column (the mask list is walked nw + ncep times, not once per element) and
-// keeps them in LDS: flag [nw] windows | [ncep] columns.
-__global__ __launch_bounds__(256) void expand_context_masked_kernel(const float* __restrict__ centre,
-                                                                    const float* __restrict__ pad,
-                                                                    const int* __restrict__ seq_len,
-                                                                    const int4* __restrict__ masks, int nm, int sw,
-                                                                    float* __restrict__ x, int B, int Bp, int T, int ctx,
-                                                                    int ncep, int Fp) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char flag[];
-  const int r = blockIdx.x;  // t*Bp + b
-  const int t = r / Bp, b = r % Bp;
-  float* dst = x + (size_t)r * Fp;
-  const int len = b < B ? seq_len[b] : 0;
-  if (t >= len) {            // (the whole workgroup: no barrier is skipped by a part of it)
-    for (int i = threadIdx.x; i < Fp; i += blockDim.x) dst[i] = 0.f;
-    return;
-  }
-  const int nw = 2 * ctx + 1, F = nw * ncep;
-  const int4* mk = masks + (size_t)b * nm;
-  for (int j = threadIdx.x; j < nw + ncep; j += blockDim.x) {
-    bool hit = false;
-    if (j < nw) {
-      const int ts = t + j - ctx;     // outside [0, len): a pad, and no mask reaches there
-      for (int k = 0; k < nm; ++k) hit |= ts >= mk[k].x && ts < mk[k].x + mk[k].y;
-    } else {
-      const int c = (j - nw) % sw;
-      for (int k = 0; k < nm; ++k) hit |= c >= mk[k].z && c < mk[k].z + mk[k].w;
-    }
-    flag[j] = hit;
-  }
-  __syncthreads();
-  for (int i = threadIdx.x; i < Fp; i += blockDim.x) {
-    float v = 0.f;
-    if (i < F) {
-      const int wdw = i / ncep, c = i - wdw * ncep;
-      const int ts = t + wdw - ctx;
-      if (ts < 0 || ts >= len) v = pad[b];
-      else if (!(flag[wdw] | flag[nw + c])) v = centre[((size_t)b * T + ts) * ncep + c];
-    }
-    dst[i] = v;
-  }
-}
-
-void launch_expand_context_masked(const float* centre, const float* pad, const int* seq_len, const int* masks, int nm,
-                                  int static_width, float* X0, int B, int Bp, int T, int ctx, int ncep, int Fp,
-                                  hipStream_t st) {
-  hipLaunchKernelGGL(expand_context_masked_kernel, dim3(T * Bp), dim3(256), (size_t)(2 * ctx + 1 + ncep), st, centre, pad,
-                     seq_len, reinterpret_cast<const int4*>(masks), nm, static_width, X0, B, Bp, T, ctx, ncep, Fp);
 }
 
 // ------------------------------------------------------------------ recurrent weight repack
@@ -179,7 +78,7 @@ void launch_repack_u(const float* U, float* Uf, float* Ub, int Hp, hipStream_t s
 // straight-line, so hipcc emits counted vmcnt waits and the MFMA chain starts when the first pair lands;
 // NQ = 0 is the generic (runtime) form.
 // CARRY: the state-carrying form of a stream feed (nasr_stream.hip).  Step 0 continues a sequence instead of starting
-// one: hin is the saved h, written in the layout of sw_index by stream_load_state_kernel, and c_{-1} is c0 [D][Bp][Hp]
+// one: hin is the saved h, written in the layout of sw_index by load_carry_kernel, and c_{-1} is c0 [D][Bp][Hp]
 // instead of 0.  Everything else, and every step s > 0, is the batch form, which never reads c0.
 template <int MT, int NQ, bool CARRY = false>
 __global__ __launch_bounds__(256) void lstm_fwd_step_kernel(
@@ -296,51 +195,62 @@ __global__ __launch_bounds__(256) void lstm_fwd_step_kernel(
 
 using StepMT = std::integer_sequence<int, 1, 2, 3, 4>;   // MT = Bp/16 M tiles of the step kernels
 
-void launch_lstm_fwd_step(const LstmDims& dm, int s, const float* Uf, const float* hin, float* hout, float* gates,
-                          float* cbuf, float* out, const int* seq_len, float forget_bias, hipStream_t st) {
+// c0 == NULL: step s of a sequence; c0 != NULL (s = 0): the first step of a stream feed or of a training window, from
+// hin = the carried h as an operand image and c0 = the carried c [D][Bp][Hp]
+static void fwd_step(const LstmDims& dm, int s, const float* Uf, const float* hin, float* hout, float* gates, float* cbuf,
+                     float* out, const int* seq_len, float forget_bias, const float* c0, hipStream_t st) {
   dim3 grid(dm.Hp / 4, dm.D), block(256);
   dispatch_int(StepMT{}, dm.Bp / 16, [&](auto mt) {
     dispatch_int(std::integer_sequence<int, 1, 2, 4, 8, 16, 0>{}, dm.Hp / 64, [&](auto nq) {   // NQ = Hp/64, 0 = the generic form
-      hipLaunchKernelGGL((lstm_fwd_step_kernel<mt(), nq()>), grid, block, 0, st, Uf, hin, hout, gates, cbuf, out, seq_len, s,
-                         dm.T, dm.Bp, dm.Hp, dm.D, forget_bias, static_cast<const float*>(nullptr));
+      if (c0)
+        hipLaunchKernelGGL((lstm_fwd_step_kernel<mt(), nq(), true>), grid, block, 0, st, Uf, hin, hout, gates, cbuf, out, seq_len,
+                           0, dm.T, dm.Bp, dm.Hp, dm.D, forget_bias, c0);
+      else
+        hipLaunchKernelGGL((lstm_fwd_step_kernel<mt(), nq()>), grid, block, 0, st, Uf, hin, hout, gates, cbuf, out, seq_len, s,
+                           dm.T, dm.Bp, dm.Hp, dm.D, forget_bias, static_cast<const float*>(nullptr));
     });
   });
 }
 
-// the first step of a stream feed: hin = the saved h as an operand image, c0 = the saved c [D][Bp][Hp]
-void launch_lstm_fwd_step_carry(const LstmDims& dm, const float* Uf, const float* hin, float* hout, float* gates, float* cbuf,
-                                float* out, const int* seq_len, float forget_bias, const float* c0, hipStream_t st) {
-  dim3 grid(dm.Hp / 4, dm.D), block(256);
-  dispatch_int(StepMT{}, dm.Bp / 16, [&](auto mt) {
-    dispatch_int(std::integer_sequence<int, 1, 2, 4, 8, 16, 0>{}, dm.Hp / 64, [&](auto nq) {
-      hipLaunchKernelGGL((lstm_fwd_step_kernel<mt(), nq(), true>), grid, block, 0, st, Uf, hin, hout, gates, cbuf, out, seq_len,
-                         0, dm.T, dm.Bp, dm.Hp, dm.D, forget_bias, c0);
-    });
-  });
-}
-
-// ------------------------------------------------------------------ stream state (nasr_stream.hip)
-// One layer's saved forward state, natural layout [S][2][H] (c, then h), into what step 0 of a feed reads, for every
-// direction (blockIdx.y): the h operand image [Bp/16][Hp/16][64][4] in the layout of sw_index and c [Bp][Hp].  Direction 0
-// comes from the saved state; a backward direction starts every window anew, from zeros.  Padded units and padded slots:
-// zeros.  Every element is written on every launch.
-__global__ __launch_bounds__(256) void stream_load_state_kernel(const float* __restrict__ state, float* __restrict__ himg,
-                                                                float* __restrict__ cimg, int S, int H, int Bp, int Hp) {
+// ------------------------------------------------------------------ carried state (nasr_stream.hip; nasr_pass.hip)
+// What step 0 of a stream feed or of a training window reads, for every direction (blockIdx.y): the h operand image
+// [Bp/16][Hp/16][64][4] in the layout of sw_index and c [Bp][Hp].  Direction 0 comes from the source: row b's c and h are
+// `units` floats at c / h + b * stride, for the rows b < rows with live[b] > 0 (live == NULL: all of them).  A backward
+// direction starts every window anew, from zeros; padded units and every other row: zeros.  Every element of both images is
+// written on every launch.
+struct CarrySrc { const float *c, *h; int stride, rows, units; const int* live; };
+__global__ __launch_bounds__(256) void load_carry_kernel(CarrySrc src, float* __restrict__ himg, float* __restrict__ cimg, int Bp,
+                                                         int Hp) {
   const int e = blockIdx.x * 256 + threadIdx.x, d = blockIdx.y;
   if (e >= Bp * Hp) return;
   const int b = e / Hp, j = e - b * Hp;
   float c = 0.f, hv = 0.f;
-  if (d == 0 && b < S && j < H) {
-    c = state[((size_t)b * 2 + 0) * H + j];
-    hv = state[((size_t)b * 2 + 1) * H + j];
+  if (d == 0 && b < src.rows && j < src.units && (!src.live || src.live[b] > 0)) {
+    c = src.c[(size_t)b * src.stride + j];
+    hv = src.h[(size_t)b * src.stride + j];
   }
   cimg[(size_t)d * Bp * Hp + e] = c;
   himg[(size_t)d * Bp * Hp + sw_index(Hp, b >> 4, b & 15, j)] = hv;
 }
+static void load_carry(const CarrySrc& src, float* himg, float* cimg, int Bp, int Hp, int D, hipStream_t st) {
+  hipLaunchKernelGGL(load_carry_kernel, dim3((Bp * Hp + 255) / 256, D), dim3(256), 0, st, src, himg, cimg, Bp, Hp);
+}
 
-// ... and back: the forward direction's state after every slot's last EMITTED row, the first Hp of row
-// (emit[b] - 1) * Bp + b of cbuf / out [T * Bp][DH]; the look-ahead rows behind it are run again by the next window.  A
-// slot that emits nothing keeps what it had.
+// a stream session's saved forward state of one layer, natural layout [S][2][H] (c, then h): slots b < S, units j < H
+void launch_stream_load_state(const float* state, float* himg, float* cimg, int S, int H, int Bp, int Hp, hipStream_t st, int D) {
+  load_carry({state, state + H, 2 * H, S, H, nullptr}, himg, cimg, Bp, Hp, D, st);
+}
+// window k of a chunked batch continues from row C-1 of window k-1 of this layer's out / cbuf [K*W*Bp][DH] (the state after
+// the last row that window emitted), for the utterances with rows in window k; nothing is live for window 0
+void launch_lc_load_carry(const float* out, const float* cbuf, const int* wlen, int k, const LcGeom& g, float* himg, float* cimg,
+                          int Hp, int D, hipStream_t st) {
+  const size_t r = k > 0 ? (size_t)((k - 1) * g.W + g.C - 1) * g.Bp * D * Hp : 0;
+  load_carry({cbuf + r, out + r, D * Hp, k > 0 ? g.Bp : 0, Hp, wlen + (size_t)k * g.Bp}, himg, cimg, g.Bp, Hp, D, st);
+}
+
+// ... and back into a stream session's state [S][2][H]: the forward direction's (c, h) after every slot's last EMITTED row,
+// the first Hp of row (emit[b] - 1) * Bp + b of cbuf / out [T * Bp][DH]; the look-ahead rows behind it are run again by the
+// next window.  A slot that emits nothing keeps what it had.
 __global__ __launch_bounds__(256) void stream_save_state_kernel(const float* __restrict__ out, const float* __restrict__ cbuf,
                                                                 LaSlots sl, float* __restrict__ state, int S, int H, int Bp, int DH) {
   const int e = blockIdx.x * 256 + threadIdx.x;
@@ -353,37 +263,9 @@ __global__ __launch_bounds__(256) void stream_save_state_kernel(const float* __r
   state[((size_t)b * 2 + 1) * H + j] = out[r * DH + j];
 }
 
-void launch_stream_load_state(const float* state, float* himg, float* cimg, int S, int H, int Bp, int Hp, hipStream_t st, int D) {
-  hipLaunchKernelGGL(stream_load_state_kernel, dim3((Bp * Hp + 255) / 256, D), dim3(256), 0, st, state, himg, cimg, S, H, Bp, Hp);
-}
 void launch_stream_save_state(const float* out, const float* cbuf, const LaSlots& sl, float* state, int S, int H, int Bp, int DH,
                               hipStream_t st) {
   hipLaunchKernelGGL(stream_save_state_kernel, dim3((S * H + 255) / 256), dim3(256), 0, st, out, cbuf, sl, state, S, H, Bp, DH);
-}
-
-// ------------------------------------------------------------------ look-ahead session (nasr_stream.hip)
-// Every slot's window = its held rows, then its new rows; block (t, b) moves pending row t of slot b.  An emitting slot's
-// window goes into the chunk's stacked rows win [S][T][F] (zeros behind it, and in the whole of a slot that emits
-// nothing: its seq_len is 0), and the rows that stay held, pending rows [emit, P), into the OTHER hold buffer: shifted
-// in place they would overlap whenever fewer rows arrive than are held.  win == NULL: no slot emits, the rows only move.
-__global__ __launch_bounds__(256) void la_window_kernel(const float* __restrict__ hold_in, const float* __restrict__ fresh,
-                                                        LaSlots sl, float* __restrict__ win, float* __restrict__ hold_out,
-                                                        int R, int Tc, int T, int F) {
-  const int t = blockIdx.x, b = blockIdx.y;
-  const int held = sl.held[b], P = held + sl.n[b], E = sl.emit[b];
-  const float* src = t < held ? hold_in + ((size_t)b * R + t) * F : t < P ? fresh + ((size_t)b * Tc + (t - held)) * F : nullptr;
-  float* wdst = (win && t < T) ? win + ((size_t)b * T + t) * F : nullptr;
-  float* hdst = (src && t >= E) ? hold_out + ((size_t)b * R + (t - E)) * F : nullptr;   // t - E < P - E <= R
-  for (int i = threadIdx.x; i < F; i += blockDim.x) {
-    const float v = src ? src[i] : 0.f;
-    if (wdst) wdst[i] = E > 0 ? v : 0.f;
-    if (hdst) hdst[i] = v;
-  }
-}
-
-void launch_la_window(const float* hold_in, const float* fresh, const LaSlots& sl, float* win, float* hold_out, int S, int R,
-                      int Tc, int T, int rows, int F, hipStream_t st) {
-  hipLaunchKernelGGL(la_window_kernel, dim3(rows, S), dim3(256), 0, st, hold_in, fresh, sl, win, hold_out, R, Tc, T, F);
 }
 
 // ------------------------------------------------------------------ BPTT step
@@ -675,83 +557,41 @@ static void bwd_step(const LstmDims& dm, int s, const float* Ub, const float* pi
   });
 }
 
-void launch_lstm_bwd_step(const LstmDims& dm, int s, const float* Ub, const float* pin, float* pout,
-                          const float* gates, float* dgbuf, const float* cbuf, const float* dout, const float* dcin,
-                          float* dcout, const int* seq_len, hipStream_t st) {
-  bwd_step(dm, s, Ub, pin, pout, gates, dgbuf, cbuf, dout, dcin, dcout, seq_len, nullptr, st);
+// ------------------------------------------------------------------ a window of steps (StepWindow, kernels.h)
+// How the per-step launches chain, here and nowhere else: forward step s reads h image s & 1 and writes the other; BPTT
+// step s, the (T-1-s)-th of its chain, reads that parity's partial-sum and dc images and writes the other.
+static size_t h_image(const StepWindow& w) { return (size_t)w.dm.D * w.dm.Bp * w.dm.Hp; }
+static size_t p_image(const StepWindow& w) { return h_image(w) * lstm_bwd_partials(w.dm.Hp); }
+
+float* lstm_steps_dcin(const StepWindow& w, int s) { return w.dcstate + ((w.dm.T - 1 - s) & 1) * h_image(w); }
+StepLeft lstm_steps_left(const StepWindow& w, int s) {
+  const int wr = (w.dm.T - s) & 1;
+  return {w.partial + wr * p_image(w), w.dcstate + wr * h_image(w)};
 }
 
-// step 0 of a window's BPTT: c0 = the carried c [D][Bp][Hp] its forward step 0 started from
-void launch_lstm_bwd_step_carry(const LstmDims& dm, const float* Ub, const float* pin, float* pout, const float* gates,
-                                float* dgbuf, const float* cbuf, const float* dout, const float* dcin, float* dcout,
-                                const int* seq_len, const float* c0, hipStream_t st) {
-  bwd_step(dm, 0, Ub, pin, pout, gates, dgbuf, cbuf, dout, dcin, dcout, seq_len, c0, st);
+void lstm_steps_fwd(const StepWindow& w, int s0, int s1, hipStream_t st) {
+  const size_t hs = h_image(w);
+  if (s0 == 0 && s1 > 0 && !w.c0) (void)hipMemsetAsync(w.hstate, 0, hs * 4, st);
+  for (int s = s0; s < s1; ++s)
+    fwd_step(w.dm, s, w.Uf, w.hstate + (s & 1) * hs, w.hstate + ((s + 1) & 1) * hs, w.gates, w.cbuf, w.out, w.seq_len,
+             w.forget_bias, s == 0 ? w.c0 : nullptr, st);
+}
+
+void lstm_steps_bwd(const StepWindow& w, int s0, int s1, hipStream_t st) {
+  if (s1 == w.dm.T && s0 < s1) {   // the chain starts here: once per window, however its steps are cut into ranges
+    (void)hipMemsetAsync(w.partial, 0, p_image(w) * 4, st);
+    (void)hipMemsetAsync(w.dcstate, 0, h_image(w) * 4, st);
+  }
+  for (int s = s1 - 1; s >= s0; --s) {
+    const StepLeft o = lstm_steps_left(w, s);
+    bwd_step(w.dm, s, w.Ub, lstm_steps_left(w, s + 1).partial, o.partial, w.gates, w.dg, w.cbuf, w.dout, lstm_steps_dcin(w, s),
+             o.dc, w.seq_len, s == 0 ? w.c0 : nullptr, st);
+  }
 }
 
 // ------------------------------------------------------------------ latency-controlled training (nasr_pass.hip)
-// The windows of every utterance lie one behind the other on a virtual time axis of K windows x W = C + R rows: row
-// (k*W + tl)*Bp + b is row tl of window k of utterance b, which is frame k*C + tl.  wlen [K][Bp] = the rows of each window
-// (lc_window_rows: 0 behind an utterance's last window and in the padded batch rows).
-
-// src [T*Bp][F] by frame -> dst [K*W*Bp][F] by window row, zeros where a window has no row.  One block per window row.
-__global__ __launch_bounds__(256) void lc_gather_kernel(const float* __restrict__ src, const int* __restrict__ wlen,
-                                                        float* __restrict__ dst, LcGeom g, int F) {
-  const int r = blockIdx.x, b = r % g.Bp, vt = r / g.Bp;
-  const int k = vt / g.W, tl = vt - k * g.W;
-  const float* sp = tl < wlen[k * g.Bp + b] ? src + ((size_t)(k * g.C + tl) * g.Bp + b) * F : nullptr;
-  float* dp = dst + (size_t)r * F;
-  for (int i = threadIdx.x; i < F; i += blockDim.x) dp[i] = sp ? sp[i] : 0.f;
-}
-
-// The top layer's EMITTED rows by frame: top [T*Bp][DH] <- outv [K*W*Bp][DH]; frame t of utterance b is row t - k*C of
-// window k = min(t / C, its last window); zeros from seq_len[b] on.  One block per frame row.
-__global__ __launch_bounds__(256) void lc_emit_kernel(const float* __restrict__ outv, const int* __restrict__ seq_len,
-                                                      float* __restrict__ top, LcGeom g, int DH) {
-  const int r = blockIdx.x, b = r % g.Bp, t = r / g.Bp;
-  const int len = seq_len[b];
-  const float* sp = nullptr;
-  if (t < len) {
-    const int k = min(t / g.C, lc_last_window(len, g.C, g.W));
-    sp = outv + ((size_t)(k * g.W + t - k * g.C) * g.Bp + b) * DH;
-  }
-  float* dp = top + (size_t)r * DH;
-  for (int i = threadIdx.x; i < DH; i += blockDim.x) dp[i] = sp ? sp[i] : 0.f;
-}
-
-// ... and its transpose: the gradient of the top layer's window rows from the gradient by frame.  An emitted row gets its
-// frame's gradient, a look-ahead row (tl >= C in a window that is not the utterance's last) and a row no window has get 0.
-// Every window row is written by its own block: no sum, no atomics.
-__global__ __launch_bounds__(256) void lc_scatter_kernel(const float* __restrict__ dtop, const int* __restrict__ seq_len,
-                                                         const int* __restrict__ wlen, float* __restrict__ doutv, LcGeom g,
-                                                         int DH) {
-  const int r = blockIdx.x, b = r % g.Bp, vt = r / g.Bp;
-  const int k = vt / g.W, tl = vt - k * g.W;
-  const int P = wlen[k * g.Bp + b];
-  const int E = k == lc_last_window(seq_len[b], g.C, g.W) ? P : min(P, g.C);
-  const float* sp = tl < E ? dtop + ((size_t)(k * g.C + tl) * g.Bp + b) * DH : nullptr;
-  float* dp = doutv + (size_t)r * DH;
-  for (int i = threadIdx.x; i < DH; i += blockDim.x) dp[i] = sp ? sp[i] : 0.f;
-}
-
-// What step 0 of window k reads, for every direction (blockIdx.y), as stream_load_state_kernel writes it for a feed: the h
-// operand image and c [Bp][Hp].  Direction 0 continues from row C-1 of window k-1 of this layer's out / cbuf [K*W*Bp][DH]
-// (the state after the last row that window emitted); window 0, a backward direction and an utterance without rows in
-// window k start from zeros.  Every element is written.
-__global__ __launch_bounds__(256) void lc_load_carry_kernel(const float* __restrict__ out, const float* __restrict__ cbuf,
-                                                            const int* __restrict__ wlen, int k, LcGeom g,
-                                                            float* __restrict__ himg, float* __restrict__ cimg, int Hp, int DH) {
-  const int e = blockIdx.x * 256 + threadIdx.x, d = blockIdx.y;
-  if (e >= g.Bp * Hp) return;
-  const int b = e / Hp, j = e - b * Hp;
-  float c = 0.f, hv = 0.f;
-  if (d == 0 && k > 0 && wlen[k * g.Bp + b] > 0) {
-    const size_t r = (size_t)((k - 1) * g.W + g.C - 1) * g.Bp + b;
-    c = cbuf[r * DH + j];
-    hv = out[r * DH + j];
-  }
-  cimg[(size_t)d * g.Bp * Hp + e] = c;
-  himg[(size_t)d * g.Bp * Hp + sw_index(Hp, b >> 4, b & 15, j)] = hv;
-}
+// The windows of every utterance lie one behind the other on a virtual time axis of K windows x W = C + R rows (rows.hip
+// moves the rows there and back); wlen [K][Bp] = the rows of each window.  Here: what crosses a window boundary in BPTT.
 
 // Behind step 0 of window k's BPTT (k >= 1): the gradient with respect to the forward direction's carried (h, c) goes to
 // where the state came from.  dh = the NP partial sums that launch left (direction 0: the head of `part`), summed in their
@@ -780,21 +620,6 @@ __global__ __launch_bounds__(256) void lc_carry_dc_kernel(float* __restrict__ dc
   if (e < n) dcin[e] += dcc[e];
 }
 
-void launch_lc_gather(const float* src, const int* wlen, float* dst, const LcGeom& g, int F, hipStream_t st) {
-  hipLaunchKernelGGL(lc_gather_kernel, dim3(g.K * g.W * g.Bp), dim3(256), 0, st, src, wlen, dst, g, F);
-}
-void launch_lc_emit(const float* outv, const int* seq_len, float* top, const LcGeom& g, int DH, hipStream_t st) {
-  hipLaunchKernelGGL(lc_emit_kernel, dim3(g.T * g.Bp), dim3(256), 0, st, outv, seq_len, top, g, DH);
-}
-void launch_lc_scatter(const float* dtop, const int* seq_len, const int* wlen, float* doutv, const LcGeom& g, int DH,
-                       hipStream_t st) {
-  hipLaunchKernelGGL(lc_scatter_kernel, dim3(g.K * g.W * g.Bp), dim3(256), 0, st, dtop, seq_len, wlen, doutv, g, DH);
-}
-void launch_lc_load_carry(const float* out, const float* cbuf, const int* wlen, int k, const LcGeom& g, float* himg, float* cimg,
-                          int Hp, int D, hipStream_t st) {
-  hipLaunchKernelGGL(lc_load_carry_kernel, dim3((g.Bp * Hp + 255) / 256, D), dim3(256), 0, st, out, cbuf, wlen, k, g, himg, cimg,
-                     Hp, D * Hp);
-}
 void launch_lc_carry_out(const float* part, int np, const float* dcs, const int* wlen_k, float* drow, float* dcc, int Bp, int Hp,
                          int DH, hipStream_t st) {
   hipLaunchKernelGGL(lc_carry_out_kernel, dim3((Bp * Hp + 255) / 256), dim3(256), 0, st, part, np, dcs, wlen_k, drow, dcc, Bp, Hp, DH);

@@ -138,12 +138,11 @@ constexpr int GRAD_HEAD = 32;   // floats in front of the gradients (h->G = h->G
 constexpr int MAX_BUCKETS = 16;
 
 struct GraphKey {
-  int T, l, bwd, s0;
+  int T, l, bwd;
   bool operator<(const GraphKey& o) const {
     if (T != o.T) return T < o.T;
     if (l != o.l) return l < o.l;
-    if (bwd != o.bwd) return bwd < o.bwd;
-    return s0 < o.s0;
+    return bwd < o.bwd;
   }
 };
 
@@ -220,7 +219,6 @@ struct StreamState {
   std::vector<uint8_t> done;         // [S] the slot has had `last` and no reset
   LaSlots sl{};                      // the feed that is running (run_chunk_steps: which row's state to save)
   std::vector<int64_t> frames;       // [S] frames emitted since the slot's reset
-  uint64_t uf_seq = ~0ull;           // repack_seq of the per-step operand images the session built itself (see stream_feed)
 };
 
 }  // namespace nasr_impl
@@ -256,6 +254,7 @@ struct nasr_ctx {
   int64_t rearm_after = 0, rearm_wait = 0, clean_steps = 0;
   int persist_aborts = 0, persist_rearms = 0;
   uint64_t repack_seq = 0;             // counts repack(): the parameters' operand images changed
+  uint64_t step_img_seq = ~0ull;       // repack_seq of the per-step operand images Uf / Ub (ensure_step_images)
   std::unique_ptr<StreamState> stream; // the open stream session, or none
   Pinned<unsigned> perr;               // host-mapped sticky error word of the resident launches
   DevPtr<float> Ucs, Ucinv;            // [L*D][N4] column scales / inverse scales of every (layer, direction) recurrent matrix
@@ -382,7 +381,6 @@ struct nasr_ctx {
   int32_t* wlen_p = nullptr;                 // [K][Bp] rows of every window (inside cur->dmeta)
   DevBuf lc_x0, lc_top, lc_dtop;             // features by frame [T*Bp][Fp]; top layer's emitted rows / their gradient [T*Bp][Pinp]
   DevBuf lc_cimg, lc_dcc;                    // the carried c of the window being run [D][Bp][Hp]; carried dc [Bp][Hp]
-  uint64_t lc_uf_seq = ~0ull;                // repack_seq of the per-step operand images the chunked passes built themselves
   int64_t frames = 0;
   std::vector<int32_t> h_seq;
   BatchSlot slots[NSLOT];
@@ -560,6 +558,9 @@ int rec_check(nasr_ctx* h);
 void rec_rearm(nasr_ctx* h);
 std::vector<TphScaleJob> rec_scale_jobs(const nasr_ctx* h);   // repack: scale jobs, then images of the recurrent matrices
 void rec_images(nasr_ctx* h);
+// repack() keeps the per-step operand images Uf / Ub only while the per-step kernels run the handle's batches.  A stream feed
+// and a chunked pass need them whatever the kind: rebuilt here iff a resident kind is in use and they are older than repack_seq.
+void ensure_step_images(nasr_ctx* h);
 
 // ---- nasr_batch.hip
 // chunked: the batch is laid out in the windows of nasr_set_chunking (h->lcC, h->lcR)

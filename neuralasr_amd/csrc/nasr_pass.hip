@@ -9,44 +9,33 @@ using namespace nasr_impl;
 
 namespace nasr_impl {
 
+// ---- the per-step kernels' view of layer l (StepWindow, kernels.h): T steps over the layer's buffers from row `row` on,
+// with seq as their seq_len; c0: the carried c of a window that continues a sequence, or NULL
+static StepWindow step_window(nasr_ctx* h, int l, int T, size_t row, const int* seq, const float* c0) {
+  const size_t sU = (size_t)l * h->D * h->Hp * h->N4, DH = (size_t)h->D * h->Hp, DN = (size_t)h->D * h->N4;
+  StepWindow w{};
+  w.dm = {T, h->B, h->Bp, h->H, h->Hp, h->D};
+  w.Uf = h->Uf + sU; w.Ub = h->Ub + sU;
+  w.hstate = h->hstate.as<float>(); w.partial = h->partial.as<float>(); w.dcstate = h->dcstate.as<float>();
+  w.gates = h->gates[l].as<float>() + row * DN; w.cbuf = h->cbuf[l].as<float>() + row * DH; w.out = h->outb[l].as<float>() + row * DH;
+  w.dg = dg_of(h, l) + row * DN; w.dout = dout_of(h, l) + row * DH;
+  w.seq_len = seq; w.forget_bias = h->cfg.forget_bias; w.c0 = c0;
+  return w;
+}
+
 // ---- one layer pass of the recurrence: the whole pass in the resident kind in use (nasr_rec.hip), or the per-timestep
-// loops over steps [s0, s1), optionally replayed from a hipGraph.  *launches += the recurrence launches it enqueued.
-int run_steps(nasr_ctx* h, int l, bool bwd, int s0, int s1, hipStream_t st, int* launches) {
-  if (h->rec_use != RecKind::Step && s0 == 0 && s1 == h->T) return rec_launch(h, l, bwd, st, launches);
-  *launches += s1 - s0;
-  const LstmDims dm{h->T, h->B, h->Bp, h->H, h->Hp, h->D};
-  const size_t sU = (size_t)l * h->D * h->Hp * h->N4;
-  const size_t hs = (size_t)h->D * h->Bp * h->Hp;   // one h-state image
-  const size_t ps = (size_t)h->D * lstm_bwd_partials(h->Hp) * h->Bp * h->Hp;   // one partial-sum image
-  float* hst = h->hstate.as<float>();
-  float* par = h->partial.as<float>();
-  float* dcs = h->dcstate.as<float>();
-  auto body = [&]() {
-    if (!bwd) {
-      if (s0 == 0) (void)hipMemsetAsync(hst, 0, hs * 4, st);
-      for (int s = s0; s < s1; ++s)
-        launch_lstm_fwd_step(dm, s, h->Uf + sU, hst + (s & 1) * hs, hst + ((s + 1) & 1) * hs,
-                             h->gates[l].as<float>(), h->cbuf[l].as<float>(), h->outb[l].as<float>(),
-                             h->seq_p, h->cfg.forget_bias, st);
-    } else {
-      if (s1 == h->T) {
-        (void)hipMemsetAsync(par, 0, ps * 4, st);
-        (void)hipMemsetAsync(dcs, 0, hs * 4, st);
-      }
-      for (int s = s1 - 1; s >= s0; --s) {
-        const int k = h->T - 1 - s;
-        launch_lstm_bwd_step(dm, s, h->Ub + sU, par + (k & 1) * ps, par + ((k + 1) & 1) * ps,
-                             h->gates[l].as<float>(), dg_of(h, l), h->cbuf[l].as<float>(), dout_of(h, l),
-                             dcs + (k & 1) * hs, dcs + ((k + 1) & 1) * hs, h->seq_p, st);
-      }
-    }
-  };
+// launches of the batch's T steps, optionally replayed from a hipGraph.  *launches += the recurrence launches it enqueued.
+static int run_steps(nasr_ctx* h, int l, bool bwd, hipStream_t st, int* launches) {
+  if (h->rec_use != RecKind::Step) return rec_launch(h, l, bwd, st, launches);
+  *launches += h->T;
+  const StepWindow w = step_window(h, l, h->T, 0, h->seq_p, nullptr);
+  auto body = [&]() { bwd ? lstm_steps_bwd(w, 0, h->T, st) : lstm_steps_fwd(w, 0, h->T, st); };
   if (!h->graph_mode) {
     body();
     HIPCHK(h, hipGetLastError());
     return NASR_OK;
   }
-  const GraphKey key{h->T, l, bwd ? 1 : 0, s0 * 4096 + (s1 - s0)};
+  const GraphKey key{h->T, l, bwd ? 1 : 0};
   auto it = h->graphs.find(key);
   if (it == h->graphs.end()) {
     if (h->graphs.size() > 256) drop_graphs(h);
@@ -64,52 +53,34 @@ int run_steps(nasr_ctx* h, int l, bool bwd, int s0, int s1, hipStream_t st, int*
 }
 
 // The same over the windows of a chunked batch (h->lc_live).  Window k of layer l is rows [k*W, (k+1)*W) of
-// the layer's buffers with wlen[k] as its seq_len: to the step kernels a batch of W frames.  No graph, as a stream feed has
-// none: step 0 is another kernel than the rest.
+// the layer's buffers with wlen[k] as its seq_len: to the step kernels a batch of W frames that continues from the carried
+// state.  No graph, as a stream feed has none: step 0 is another kernel than the rest.
 int lc_run_steps(nasr_ctx* h, int l, bool bwd, hipStream_t st, int* launches) {
   const LcGeom& g = h->lcg;
-  const int Bp = h->Bp, Hp = h->Hp, D = h->D, W = g.W;
-  const LstmDims dm{W, h->B, Bp, h->H, Hp, D};
-  const int np = lstm_bwd_partials(Hp);
-  const size_t sU = (size_t)l * D * Hp * h->N4, hs = (size_t)D * Bp * Hp, ps = (size_t)D * np * Bp * Hp;
-  const size_t wr = (size_t)W * Bp;                  // rows of a window
-  const int DH = D * Hp, DN = D * h->N4;
-  float *hst = h->hstate.as<float>(), *par = h->partial.as<float>(), *dcs = h->dcstate.as<float>();
+  const int Bp = h->Bp, Hp = h->Hp, D = h->D, W = g.W, DH = D * Hp;
+  const int Ce = std::min(g.C, W);                   // W <= C: the one window of a batch no longer than a chunk
   float *cimg = h->lc_cimg.as<float>(), *dcc = h->lc_dcc.as<float>();
-  float *gt = h->gates[l].as<float>(), *cb = h->cbuf[l].as<float>(), *ob = h->outb[l].as<float>();
-  if (!bwd) {
-    for (int k = 0; k < g.K; ++k) {
-      const int* wl = h->wlen_p + (size_t)k * Bp;
-      float *gk = gt + k * wr * DN, *ck = cb + k * wr * DH, *ok = ob + k * wr * DH;
-      launch_lc_load_carry(ob, cb, h->wlen_p, k, g, hst, cimg, Hp, D, st);
-      launch_lstm_fwd_step_carry(dm, h->Uf + sU, hst, hst + hs, gk, ck, ok, wl, h->cfg.forget_bias, cimg, st);
-      for (int s = 1; s < W; ++s)
-        launch_lstm_fwd_step(dm, s, h->Uf + sU, hst + (s & 1) * hs, hst + ((s + 1) & 1) * hs, gk, ck, ok, wl, h->cfg.forget_bias, st);
+  float *cb = h->cbuf[l].as<float>(), *ob = h->outb[l].as<float>();
+  for (int i = 0; i < g.K; ++i) {
+    const int k = bwd ? g.K - 1 - i : i;
+    const int* wl = h->wlen_p + (size_t)k * Bp;
+    const StepWindow w = step_window(h, l, W, (size_t)k * W * Bp, wl, cimg);
+    if (!bwd) {
+      launch_lc_load_carry(ob, cb, h->wlen_p, k, g, w.hstate, cimg, Hp, D, st);
+      lstm_steps_fwd(w, 0, W, st);
+      continue;
     }
-  } else {
-    float* dov = dout_of(h, l);
-    for (int k = g.K - 1; k >= 0; --k) {
-      const int* wl = h->wlen_p + (size_t)k * Bp;
-      const float *gk = gt + k * wr * DN, *ck = cb + k * wr * DH;
-      float *dgk = dg_of(h, l) + k * wr * DN, *dok = dov + k * wr * DH;
-      (void)hipMemsetAsync(par, 0, ps * 4, st);
-      (void)hipMemsetAsync(dcs, 0, hs * 4, st);
-      for (int s = W - 1; s >= 1; --s) {
-        const int kk = W - 1 - s;
-        // the forward state after row C-1 went on into window k+1: so does its dc come back, into the chain at that step
-        if (s == g.C - 1 && k + 1 < g.K) launch_lc_carry_dc(dcs + (kk & 1) * hs, dcc, Bp * Hp, st);
-        launch_lstm_bwd_step(dm, s, h->Ub + sU, par + (kk & 1) * ps, par + ((kk + 1) & 1) * ps, gk, dgk, ck, dok,
-                             dcs + (kk & 1) * hs, dcs + ((kk + 1) & 1) * hs, wl, st);
-      }
-      const int k0 = W - 1;                            // step 0, in the carry form
-      if (g.C == 1 && k + 1 < g.K) launch_lc_carry_dc(dcs + (k0 & 1) * hs, dcc, Bp * Hp, st);
-      launch_lc_load_carry(ob, cb, h->wlen_p, k, g, hst, cimg, Hp, D, st);   // (hst: free during BPTT; only cimg is read)
-      launch_lstm_bwd_step_carry(dm, h->Ub + sU, par + (k0 & 1) * ps, par + ((k0 + 1) & 1) * ps, gk, dgk, ck, dok,
-                                 dcs + (k0 & 1) * hs, dcs + ((k0 + 1) & 1) * hs, wl, cimg, st);
-      if (k > 0)
-        launch_lc_carry_out(par + ((k0 + 1) & 1) * ps, np, dcs + ((k0 + 1) & 1) * hs, wl,
-                            dov + ((size_t)(k - 1) * W + g.C - 1) * Bp * DH, dcc, Bp, Hp, DH, st);
-    }
+    lstm_steps_bwd(w, Ce, W, st);
+    // the forward state after step C-1 went on into window k+1: so does its dc come back (that window's BPTT left it in
+    // dcc), into the chain at the step that reads it
+    if (k + 1 < g.K) launch_lc_carry_dc(lstm_steps_dcin(w, Ce - 1), dcc, Bp * Hp, st);
+    lstm_steps_bwd(w, 1, Ce, st);
+    launch_lc_load_carry(ob, cb, h->wlen_p, k, g, w.hstate, cimg, Hp, D, st);   // (hstate: free during BPTT; only cimg is read)
+    lstm_steps_bwd(w, 0, 1, st);                     // step 0, in the carry form
+    const StepLeft left = lstm_steps_left(w, 0);     // what step 0 left: the gradient with respect to the carried (h, c)
+    if (k > 0)
+      launch_lc_carry_out(left.partial, lstm_bwd_partials(Hp), left.dc, wl, dout_of(h, l) + ((size_t)(k - 1) * W + g.C - 1) * Bp * DH,
+                          dcc, Bp, Hp, DH, st);
   }
   *launches += g.K * W;
   HIPCHK(h, hipGetLastError());
@@ -270,16 +241,11 @@ int dense_backward(nasr_ctx* h, int i, const float* X, float* dX) {
 // the rest, and a chunk is a few dozen launches.
 static int run_chunk_steps(nasr_ctx* h, int l, hipStream_t st) {
   StreamState& ss = *h->stream;
-  const LstmDims dm{h->T, h->B, h->Bp, h->H, h->Hp, h->D};
-  const size_t sU = (size_t)l * h->D * h->Hp * h->N4, hs = (size_t)h->D * h->Bp * h->Hp;
-  float* hst = h->hstate.as<float>();
   float* state = ss.state.as<float>() + (size_t)l * ss.S * 2 * h->H;
-  float *g = h->gates[l].as<float>(), *c = h->cbuf[l].as<float>(), *o = h->outb[l].as<float>();
-  launch_stream_load_state(state, hst, ss.cimg.as<float>(), ss.S, h->H, h->Bp, h->Hp, st, h->D);
-  launch_lstm_fwd_step_carry(dm, h->Uf + sU, hst, hst + hs, g, c, o, h->seq_p, h->cfg.forget_bias, ss.cimg.as<float>(), st);
-  for (int s = 1; s < h->T; ++s)
-    launch_lstm_fwd_step(dm, s, h->Uf + sU, hst + (s & 1) * hs, hst + ((s + 1) & 1) * hs, g, c, o, h->seq_p, h->cfg.forget_bias, st);
-  launch_stream_save_state(o, c, ss.sl, state, ss.S, h->H, h->Bp, h->D * h->Hp, st);
+  const StepWindow w = step_window(h, l, h->T, 0, h->seq_p, ss.cimg.as<float>());
+  launch_stream_load_state(state, w.hstate, ss.cimg.as<float>(), ss.S, h->H, h->Bp, h->Hp, st, h->D);
+  lstm_steps_fwd(w, 0, h->T, st);
+  launch_stream_save_state(w.out, w.cbuf, ss.sl, state, ss.S, h->H, h->Bp, h->D * h->Hp, st);
   h->n_fwd_launch += h->T;
   HIPCHK(h, hipGetLastError());
   return NASR_OK;
@@ -295,13 +261,7 @@ int forward(nasr_ctx* h, bool chunk) {
   const int Bp = h->Bp, T = h->T, D = h->D, Hp = h->Hp;
   const int R = T * Bp, Rv = h->Tv * Bp;   // rows by frame; rows of the LSTM stack (the same but for a chunked batch)
   const bool lc = h->lc_live;
-  if (lc && h->rec_use != RecKind::Step && h->lc_uf_seq != h->repack_seq) {
-    // (the per-step operand images, which repack() keeps only while the per-step kernels run the handle's batches: as a
-    // stream feed does, nasr_stream.hip)
-    for (size_t k = 0; k < h->off_u.size(); ++k)
-      launch_repack_u(h->P + h->off_u[k], h->Uf + k * h->Hp * h->N4, h->Ub + k * h->Hp * h->N4, h->Hp, h->st);
-    h->lc_uf_seq = h->repack_seq;
-  }
+  if (lc) ensure_step_images(h);   // a chunked batch runs on the per-step kernels, whatever the handle's kind
   h->n_fwd_launch = 0;
   std::fill(h->ott_valid.begin(), h->ott_valid.end(), 0);
   // the fault word of the pass that starts here (a training step or a forward-only call); what an unread earlier word
@@ -326,7 +286,7 @@ int forward(nasr_ctx* h, bool chunk) {
     PhaseScope ps(h, PH_RECF);
     int rc = chunk ? run_chunk_steps(h, l, h->st)
              : lc  ? lc_run_steps(h, l, false, h->st, &h->n_fwd_launch)
-                   : run_steps(h, l, false, 0, T, h->st, &h->n_fwd_launch);
+                   : run_steps(h, l, false, h->st, &h->n_fwd_launch);
     if (rc) return rc;
   }
   if (lc) {   // the rows the windows emit, by frame: what the projection, and everything behind it, reads
@@ -567,7 +527,7 @@ int backward(nasr_ctx* h) {
     const bool defer = use != RecKind::Step && h->bucket_defer;
     {
       PhaseScope ps(h, PH_RECB);
-      int rc = lc ? lc_run_steps(h, l, true, h->st, &h->n_bwd_launch) : run_steps(h, l, true, 0, T, h->st, &h->n_bwd_launch);
+      int rc = lc ? lc_run_steps(h, l, true, h->st, &h->n_bwd_launch) : run_steps(h, l, true, h->st, &h->n_bwd_launch);
       if (rc) return rc;
     }
     if (defer && l + 1 < h->L && h->bucket_of_layer[l + 1] >= 0) {   // the layer above's bucket, held back over this launch

@@ -167,20 +167,29 @@ std::vector<TphScaleJob> rec_scale_jobs(const nasr_ctx* h) {
   return jobs;
 }
 
+// the per-step kernels' images of every recurrent matrix, from the parameters as they are
+static void step_images(nasr_ctx* h) {
+  for (size_t k = 0; k < h->off_u.size(); ++k)
+    launch_repack_u(h->P + h->off_u[k], h->Uf + k * h->Hp * h->N4, h->Ub + k * h->Hp * h->N4, h->Hp, h->st);
+  h->step_img_seq = h->repack_seq;
+}
+
 void rec_images(nasr_ctx* h) {
   if (h->rec_use == RecKind::Persist) {
     launch_repack_persist(h->P, h->off_u.data(), (int)h->off_u.size(), h->Upf, h->Upb, h->Hp, h->rec_f16 ? h->Ucs : nullptr, h->st);
-    return;
-  }
-  for (size_t k = 0; k < h->off_u.size(); ++k) {
-    const float* U = h->P + h->off_u[k];
-    if (h->rec_use == RecKind::Wide) {   // fp16-plane images under the scales of rec_scale_jobs
+  } else if (h->rec_use == RecKind::Wide) {   // fp16-plane images under the scales of rec_scale_jobs
+    for (size_t k = 0; k < h->off_u.size(); ++k) {
+      const float* U = h->P + h->off_u[k];
       launch_repack_wide(U, h->Ucs + k * h->N4, h->Uw + k * wide_image_bytes(h->Hp), h->Hp, h->st);
       launch_repack_wide_bwd(U, h->Urs + k * h->Hp, h->Uwb + k * wide_image_bytes(h->Hp), h->Hp, h->st);
-    } else {
-      launch_repack_u(U, h->Uf + k * h->Hp * h->N4, h->Ub + k * h->Hp * h->N4, h->Hp, h->st);
     }
+  } else {
+    step_images(h);
   }
+}
+
+void ensure_step_images(nasr_ctx* h) {
+  if (h->rec_use != RecKind::Step && h->step_img_seq != h->repack_seq) step_images(h);
 }
 
 }  // namespace nasr_impl

@@ -4,9 +4,9 @@
 // One rule serves every session.  A session has a look-ahead of R frames and holds, per slot, its last rows on the device.
 // With P = held + n pending rows a feed emits E = last ? P : max(0, P - R) rows: it runs an ordinary forward pass
 // (nasr_pass.hip: forward(h, true)) over the pending rows of the slots that emit, the forward direction from the saved
-// state (lstm.hip: stream_load_state_kernel, the state-carrying step), the backward direction of a bidirectional concat
+// state (lstm.hip: load_carry_kernel, the state-carrying step), the backward direction of a bidirectional concat
 // network from zero at the slot's last pending row; it saves the forward state after row E - 1
-// (stream_save_state_kernel) and holds the last P - E rows (la_window_kernel).  A session of nasr_stream_open is the case
+// (stream_save_state_kernel) and holds the last P - E rows (rows.hip: la_window_kernel).  A session of nasr_stream_open is the case
 // R = 0 on a unidirectional network: nothing is ever held, E = n, the window is the chunk, and the state after the last
 // emitted row is the state after the slot's last frame.  nasr_stream_open_lookahead opens the sessions with R >= 1.
 // The rows of a feed come from the caller (nasr_stream_feed, nasr_stream_feed_lookahead) or, on a session that takes
@@ -141,13 +141,7 @@ int run_feed(nasr_ctx* h, const char* fn, const FeedPlan& f, const RowSource& sr
     ss.sl = f.sl;
     rc = upload(h, b);
     if (!rc) {
-      // The per-step operand images of the recurrent matrices are kept by repack() only while the per-step kernels run the
-      // handle's batches; with a resident kind in use the session keeps them itself, rebuilt when the parameters have changed.
-      if (h->rec_use != RecKind::Step && ss.uf_seq != h->repack_seq) {
-        for (size_t k = 0; k < h->off_u.size(); ++k)
-          launch_repack_u(h->P + h->off_u[k], h->Uf + k * h->Hp * h->N4, h->Ub + k * h->Hp * h->N4, h->Hp, h->st);
-        ss.uf_seq = h->repack_seq;
-      }
+      ensure_step_images(h);   // a chunk runs on the per-step kernels, whatever the handle's kind
       rc = forward(h, true);
       if (!rc) rc = fetch_logits(h, logits_out, f.Te);
       // the chunk is no batch the *_resident calls could run (a slot may have no frame at all): the handle has none until

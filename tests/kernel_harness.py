@@ -14,7 +14,7 @@ KT_PATH = os.path.join(ROOT, 'neuralasr_amd', 'libnasr_kt.so')
 SYMBOLS = ['kt_gemm_pick_split', 'kt_gemm_tp_tile_rows', 'kt_gemm_tph_pick_split', 'kt_tp_split2_parts', 'kt_tph_bytes',
            'kt_gemm_f32', 'kt_tph_scales', 'kt_tph_scales_batch', 'kt_tph_scales_from_parts', 'kt_tph_split2', 'kt_gemm_tph',
            'kt_colsum', 'kt_colsum_parts', 'kt_reduce_slabs', 'kt_reduce_slabs_rows',
-           'kt_persist_dgmax_floats', 'kt_lstm_step_fwd', 'kt_lstm_step_bwd',
+           'kt_persist_dgmax_floats', 'kt_lstm_step_fwd', 'kt_lstm_step_bwd', 'kt_lstm_step_bwd_carry',
            'kt_lstm_persist_fwd', 'kt_lstm_persist_bwd', 'kt_lstm_wide_fwd', 'kt_lstm_wide_bwd']
 
 FILL = 0xCD                                   # pre-fill byte of every output buffer
@@ -275,7 +275,8 @@ def lstm_forward(path, inp):
 
 
 def lstm_backward(path, inp, lean=False, parts=False):
-    """Runs a BPTT path -> (dG [T][Bp][D][Hp][4], rowpart [D*32][T*Bp] or None, colpart [8/D][D*4Hp] or None)."""
+    """Runs a BPTT path -> (dG [T][Bp][D][Hp][4], rowpart [D*32][T*Bp] or None, colpart [8/D][D*4Hp] or None).
+    'step_bwd' with inp['c0'] [D][Bp][Hp]: step 0 in its carry form."""
     act = inp['act']
     T, Bp, D, Hp = act.shape[:4]
     U, a, c, do = _f32(inp['U']), _f32(act), _f32(inp['c']), _f32(inp['dout'])
@@ -284,7 +285,11 @@ def lstm_backward(path, inp, lean=False, parts=False):
     rp = cp = None
     if path == 'step_bwd':
         d = _rec_desc(inp, act)
-        _check(lib().kt_lstm_step_bwd(ctypes.byref(d), _f(U), _f(a), _f(c), _f(do), _f(dg), _i(sq)), 'kt_lstm_step_bwd')
+        if inp.get('c0') is None:
+            _check(lib().kt_lstm_step_bwd(ctypes.byref(d), _f(U), _f(a), _f(c), _f(do), _f(dg), _i(sq)), 'kt_lstm_step_bwd')
+        else:
+            rc = lib().kt_lstm_step_bwd_carry(ctypes.byref(d), _f(U), _f(a), _f(c), _f(do), _f(dg), _i(sq), _f(_f32(inp['c0'])))
+            _check(rc, 'kt_lstm_step_bwd_carry')
     elif path == 'wide_bwd':
         d = _rec_desc(inp, act)
         status = np.full(3, 0xFFFFFFFF, dtype=np.uint32)

@@ -2,7 +2,7 @@
 // lstm_wide.hip).  Linked into neuralasr_amd/libnasr_kt.so with the SAME lstm.o / lstm_persist.o / lstm_wide.o objects as
 // libnasr.so (neuralasr_amd/build.py), so the tests run the shipped code objects; no test hook is set (NASR_TEST_HOOKS
 // stays unset) and nothing is injected.  The conventions of harness.hip hold: host pointers in, allocate, upload, launch
-// on one stream in the order the library does (nasr_pass.hip: run_steps, nasr_rec.hip: rec_scale_jobs / rec_images /
+// on one stream in the order the library does (nasr_pass.hip: step_window, nasr_rec.hip: rec_scale_jobs / rec_images /
 // rec_launch), synchronise, download, free; -1 for refused arguments, a HIP error as its code.  Buffers the kernels
 // write are pre-filled with the caller's byte; `gates` of a forward call is an in-place buffer and comes in whole from the
 // caller.  The resident kernels' XcdCtl::error, the sticky word and the fault float come back in status[3]; a non-zero
@@ -66,9 +66,9 @@ struct KtRec {
 // floats of rowpart + colpart as the library sizes its dgmax buffer
 unsigned long long kt_persist_dgmax_floats(int T, int Bp, int Hp, int D) { return persist_dgmax_floats(T, Bp, Hp, D); }
 
-// ---- lstm.hip, forward: launch_repack_u, a zeroed h image, T launches over ping-pong images (run_steps).  state (or
-// NULL): [D][B][2][H] (c, then h) - step 0 is then launch_lstm_fwd_step_carry from the images launch_stream_load_state
-// builds, one direction at a time.  gates: pre-activations in, activations out, in place.
+// ---- lstm.hip, forward: launch_repack_u, then the window of T steps by lstm_steps_fwd, the runner every pass of the
+// library goes through (nasr_pass.hip).  state (or NULL): [D][B][2][H] (c, then h) - the window then continues from the
+// images launch_stream_load_state builds, one direction at a time.  gates: pre-activations in, activations out, in place.
 int kt_lstm_step_fwd(const KtRec* k, const float* U, float* gates, float* cbuf, float* out, const int* seq_len, const float* state) {
   const LstmDims dm{k->T, k->B, k->Bp, k->H, k->Hp, k->D};
   if (!U || !gates || !cbuf || !out || !dims_ok(dm, seq_len)) return -1;
@@ -77,35 +77,32 @@ int kt_lstm_step_fwd(const KtRec* k, const float* U, float* gates, float* cbuf, 
   const float* dU = a.up(U, dm.D * nU);
   float* Uf = a.filled<float>(dm.D * nU, 0xFF);
   float* Ub = a.filled<float>(dm.D * nU, 0xFF);
-  float* g = a.up(gates, R * dm.D * N4);
-  float* c = a.filled<float>(R * dm.D * dm.Hp, k->fill);
-  float* o = a.filled<float>(R * dm.D * dm.Hp, k->fill);
-  const int* sq = a.up(seq_len, dm.Bp);
-  float* hst = a.filled<float>(2 * hs, 0xFF);                     // NaN until written
+  StepWindow w{};
+  w.dm = dm; w.Uf = Uf; w.Ub = Ub; w.forget_bias = k->forget_bias;
+  w.gates = a.up(gates, R * dm.D * N4);
+  w.cbuf = a.filled<float>(R * dm.D * dm.Hp, k->fill);
+  w.out = a.filled<float>(R * dm.D * dm.Hp, k->fill);
+  w.seq_len = a.up(seq_len, dm.Bp);
+  w.hstate = a.filled<float>(2 * hs, 0xFF);                       // NaN until written
   float* cimg = state ? a.filled<float>(hs, 0xFF) : nullptr;
+  w.c0 = cimg;
   const float* st8 = a.up(state, (size_t)dm.D * dm.B * 2 * dm.H);
   if (a.err != hipSuccess) return (int)a.err;
   for (int d = 0; d < dm.D; ++d) launch_repack_u(dU + d * nU, Uf + d * nU, Ub + d * nU, dm.Hp, a.st);
-  int s = 0;
-  if (state) {
+  if (state)
     for (int d = 0; d < dm.D; ++d)
-      launch_stream_load_state(st8 + (size_t)d * dm.B * 2 * dm.H, hst + (size_t)d * dm.Bp * dm.Hp, cimg + (size_t)d * dm.Bp * dm.Hp,
+      launch_stream_load_state(st8 + (size_t)d * dm.B * 2 * dm.H, w.hstate + (size_t)d * dm.Bp * dm.Hp, cimg + (size_t)d * dm.Bp * dm.Hp,
                                dm.B, dm.H, dm.Bp, dm.Hp, a.st);
-    launch_lstm_fwd_step_carry(dm, Uf, hst, hst + hs, g, c, o, sq, k->forget_bias, cimg, a.st);
-    s = 1;
-  } else {
-    a.chk(hipMemsetAsync(hst, 0, hs * 4, a.st));
-  }
-  for (; s < dm.T; ++s)
-    launch_lstm_fwd_step(dm, s, Uf, hst + (s & 1) * hs, hst + ((s + 1) & 1) * hs, g, c, o, sq, k->forget_bias, a.st);
-  a.down(gates, g, R * dm.D * N4); a.down(cbuf, c, R * dm.D * dm.Hp); a.down(out, o, R * dm.D * dm.Hp);
+  lstm_steps_fwd(w, 0, dm.T, a.st);
+  a.down(gates, w.gates, R * dm.D * N4); a.down(cbuf, w.cbuf, R * dm.D * dm.Hp); a.down(out, w.out, R * dm.D * dm.Hp);
   return a.finish();
 }
 
-// ---- lstm.hip, BPTT: steps T-1 .. 0 over the pin/pout and dcin/dcout ping-pong, the first image of each zeroed
-// (run_steps); Hp <= 512 in one launch per step, the two-launch form above it.  gates = the saved activations.
-int kt_lstm_step_bwd(const KtRec* k, const float* U, const float* gates, const float* cbuf, const float* dout, float* dgbuf,
-                     const int* seq_len) {
+// ---- lstm.hip, BPTT: the window's steps T-1 .. 0 by lstm_steps_bwd (it zeroes the first partial-sum and dc images); Hp <=
+// 512 in one launch per step, the two-launch form above it.  gates = the saved activations.  c0 (or NULL): [D][Bp][Hp],
+// the carried c the forward window started from - step 0 then runs in its carry form.
+static int step_bwd(const KtRec* k, const float* U, const float* gates, const float* cbuf, const float* dout, float* dgbuf,
+                    const int* seq_len, const float* c0) {
   const LstmDims dm{k->T, k->B, k->Bp, k->H, k->Hp, k->D};
   if (!U || !gates || !cbuf || !dout || !dgbuf || !dims_ok(dm, seq_len)) return -1;
   const size_t N4 = (size_t)4 * dm.Hp, R = (size_t)dm.T * dm.Bp, nU = (size_t)dm.Hp * N4, hs = (size_t)dm.D * dm.Bp * dm.Hp;
@@ -114,24 +111,30 @@ int kt_lstm_step_bwd(const KtRec* k, const float* U, const float* gates, const f
   const float* dU = a.up(U, dm.D * nU);
   float* Uf = a.filled<float>(dm.D * nU, 0xFF);
   float* Ub = a.filled<float>(dm.D * nU, 0xFF);
-  const float* g = a.up(gates, R * dm.D * N4);
-  const float* c = a.up(cbuf, R * dm.D * dm.Hp);
-  const float* dO = a.up(dout, R * dm.D * dm.Hp);
-  float* dg = a.filled<float>(R * dm.D * N4, k->fill);
-  const int* sq = a.up(seq_len, dm.Bp);
-  float* par = a.filled<float>(2 * ps, 0xFF);
-  float* dcs = a.filled<float>(2 * hs, 0xFF);
+  StepWindow w{};
+  w.dm = dm; w.Uf = Uf; w.Ub = Ub; w.forget_bias = k->forget_bias;
+  w.gates = a.up(gates, R * dm.D * N4);                           // (BPTT only reads them)
+  w.cbuf = a.up(cbuf, R * dm.D * dm.Hp);
+  w.dout = a.up(dout, R * dm.D * dm.Hp);
+  w.dg = a.filled<float>(R * dm.D * N4, k->fill);
+  w.seq_len = a.up(seq_len, dm.Bp);
+  w.partial = a.filled<float>(2 * ps, 0xFF);
+  w.dcstate = a.filled<float>(2 * hs, 0xFF);
+  w.c0 = a.up(c0, hs);
   if (a.err != hipSuccess) return (int)a.err;
   for (int d = 0; d < dm.D; ++d) launch_repack_u(dU + d * nU, Uf + d * nU, Ub + d * nU, dm.Hp, a.st);
-  a.chk(hipMemsetAsync(par, 0, ps * 4, a.st));
-  a.chk(hipMemsetAsync(dcs, 0, hs * 4, a.st));
-  for (int s = dm.T - 1; s >= 0; --s) {
-    const int kk = dm.T - 1 - s;
-    launch_lstm_bwd_step(dm, s, Ub, par + (kk & 1) * ps, par + ((kk + 1) & 1) * ps, g, dg, c, dO, dcs + (kk & 1) * hs,
-                         dcs + ((kk + 1) & 1) * hs, sq, a.st);
-  }
-  a.down(dgbuf, dg, R * dm.D * N4);
+  lstm_steps_bwd(w, 0, dm.T, a.st);
+  a.down(dgbuf, w.dg, R * dm.D * N4);
   return a.finish();
+}
+// (two entry points, so that kt_lstm_step_bwd keeps the arguments every caller of it has ever passed)
+int kt_lstm_step_bwd(const KtRec* k, const float* U, const float* gates, const float* cbuf, const float* dout, float* dgbuf,
+                     const int* seq_len) {
+  return step_bwd(k, U, gates, cbuf, dout, dgbuf, seq_len, nullptr);
+}
+int kt_lstm_step_bwd_carry(const KtRec* k, const float* U, const float* gates, const float* cbuf, const float* dout, float* dgbuf,
+                           const int* seq_len, const float* c0) {
+  return c0 ? step_bwd(k, U, gates, cbuf, dout, dgbuf, seq_len, c0) : -1;
 }
 
 // the operand images of the persistent kind as repack() builds them: column scales by launch_tph_scales_batch (the jobs

@@ -219,9 +219,10 @@ def forward(U, pre, seq_len, fb, h0=None, c0=None, mutant=None):
     return act, c, h
 
 
-def backward(U, act, c, dout, seq_len, mutant=None, kind=None):
+def backward(U, act, c, dout, seq_len, mutant=None, kind=None, c0=None):
     """fp64 BPTT from the stored activations and c.  Returns dG [T][Bp][D][Hp][4] (zero where a frame is not computed);
-    with `kind` also the running bound of a correct kernel of that class: (dG, e_dG)."""
+    with `kind` also the running bound of a correct kernel of that class: (dG, e_dG).  c0 [D][Bp][Hp] or None: the carried
+    c the forward pass started from - at step 0 the forget gate's derivative reads it instead of 0."""
     T, Bp, D, Hp = _dims(act)
     U = np.asarray(U, dtype=np.float64)
     act = np.asarray(act, dtype=np.float64)
@@ -239,6 +240,7 @@ def backward(U, act, c, dout, seq_len, mutant=None, kind=None):
         egn = np.zeros((Bp, 4 * Hp))
         dc = np.zeros((Bp, Hp))
         edc = np.zeros((Bp, Hp))
+        c0d = 0.0 if c0 is None else np.asarray(c0[d], dtype=np.float64)
         if kind and kind.name == 'wide_bwd':
             dUt = np.maximum(2.0 ** -23 * aUt, 2.0 ** -39 * aUt.max(axis=0)[None, :])
             Sb = wide_dg_scale(dout[:, :, d], ln).astype(np.float64)
@@ -248,7 +250,7 @@ def backward(U, act, c, dout, seq_len, mutant=None, kind=None):
             tp = np.where(valid & (s > 0), tb + 1 if d == 1 else tb - 1, tb)
             a = act[tb, rows, d]
             cc = c[tb, rows, d]
-            cpv = np.where((s > 0), c[tp, rows, d], 0.0)
+            cpv = np.where((s > 0), c[tp, rows, d], c0d)
             do = dout[tb, rows, d]
             with np.errstate(over='ignore', invalid='ignore'):
                 rec = dgn @ Ut
@@ -407,7 +409,7 @@ def check_backward(kind, inp, got_dg, rowpart=None, colpart=None):
     the gate columns of padded units; rowpart / colpart, reduced over their parts, are max |dG| of the kernel's own dG."""
     U, ln, H = inp['U'], inp['seq_len'], inp['H']
     T, Bp, D, Hp = _dims(inp['act'])
-    ref, e = backward(U, inp['act'], inp['c'], inp['dout'], ln, kind=kind)
+    ref, e = backward(U, inp['act'], inp['c'], inp['dout'], ln, kind=kind, c0=inp.get('c0'))
     valid = (np.arange(T)[:, None] < np.asarray(ln)[None, :])
     vm = valid[:, :, None, None, None] & np.ones((1, 1, D, Hp, 4), dtype=bool)
     problems = []
@@ -531,7 +533,7 @@ def emulate_forward(kind, inp):
 
 def emulate_backward(kind, inp):
     U, ln = inp['U'], np.asarray(inp['seq_len'], np.int64)
-    act, c, dout = inp['act'], inp['c'], inp['dout']
+    act, c, dout, c0 = inp['act'], inp['c'], inp['dout'], inp.get('c0')
     T, Bp, D, Hp = _dims(act)
     dG = np.zeros(act.shape, dtype=np.float32)
     rows = np.arange(Bp)
@@ -568,7 +570,7 @@ def emulate_backward(kind, inp):
             tb = np.where(valid, (ln - 1 - s) if d == 1 else s, 0)
             tp = np.where(valid & (s > 0), tb + 1 if d == 1 else tb - 1, tb)
             a, cc, do = act[tb, rows, d], c[tb, rows, d], dout[tb, rows, d]
-            cpv = c[tp, rows, d] if s > 0 else np.zeros((Bp, Hp), np.float32)
+            cpv = c[tp, rows, d] if s > 0 else c0[d] if c0 is not None else np.zeros((Bp, Hp), np.float32)
             with np.errstate(over='ignore', invalid='ignore'):
                 if wide:
                     sv = (dgn * Sb[:, None]).astype(np.float32)
@@ -610,11 +612,12 @@ class Case:
     lean: bool = False
     parts: bool = False
     seed: int = 0
+    carry: bool = False    # step_bwd: step 0 in its carry form, from a carried c0 (a window of chunked training)
 
     @property
     def id(self):
         return (f'{self.path}-Hp{self.Hp}-H{self.H}-B{self.B}-D{self.D}-T{self.T}-{self.lens}-{self.regime}' +
-                ('-lean' if self.lean else '') + ('-parts' if self.parts else ''))
+                ('-lean' if self.lean else '') + ('-parts' if self.parts else '') + ('-carry' if self.carry else ''))
 
 
 def cases():
@@ -635,6 +638,8 @@ def cases():
         C('step_bwd', 256, 250, 16, 2, 5, 'short', 'init'), C('step_bwd', 512, 500, 64, 2, 3, 'ragged', 'init'),
         C('step_bwd', 576, 570, 1, 2, 5, 'ragged', 'init'), C('step_bwd', 640, 600, 33, 2, 4, 'short', 'sat'),
         C('step_bwd', 1024, 1000, 1, 1, 3, 'full', 'init'), C('step_bwd', 64, 50, 5, 2, 300, 'ragged', 'long'),
+        # ... with step 0 in its carry form: the one-launch kernel's CARRY instantiation, and lstm_bwd_cell_carry_kernel
+        C('step_bwd', 64, 50, 5, 2, 3, 'ragged', 'init', carry=True), C('step_bwd', 640, 600, 5, 1, 2, 'ragged', 'init', carry=True),
     ]
     # the persistent kernels: every NU = Hp/32 of the launcher's dispatch (2, 4, ..., 16)
     Bs = [5, 17, 1, 33, 16, 64, 5, 17]
@@ -689,7 +694,8 @@ def _seq_len(case, rng):
 def make_inputs(case):
     """The buffers of a case (read-only: shared between tests).  Forward paths: U, pre (poisoned where no frame is
     computed), seq_len, fb, h0 / c0 (carry).  BPTT paths: U, act / c (the fp64 forward pass of an init-like or saturated
-    input, rounded to fp32 - independent of the forward kernels), dout, all poisoned the same way."""
+    input, rounded to fp32 - independent of the forward kernels; from c0 when the case carries), dout, all poisoned the
+    same way."""
     seed = zlib.crc32(case.id.encode()) + case.seed
     rng = np.random.default_rng(seed)
     Hp, H, B, D, T = case.Hp, case.H, case.B, case.D, case.T
@@ -738,8 +744,13 @@ def make_inputs(case):
         out['c0'] = np.zeros((D, Bp, Hp), dtype=np.float32)
         out['h0'] = np.zeros((D, Bp, Hp), dtype=np.float32)
         out['c0'][:, :B, :H], out['h0'][:, :B, :H] = st[:, :, 0], st[:, :, 1]
+    if case.carry:            # the carried c of a window's BPTT, poisoned as everything else in the rows b >= B
+        c0 = np.full((D, Bp, Hp), POISON, dtype=np.float32)
+        c0[:, :B] = 0
+        c0[:, :B, :H] = rng.uniform(-3, 3, size=(D, B, H))
+        out['c0'] = c0
     if KINDS[case.path].bwd:
-        act, c, _ = forward(U, pre, ln, fb)
+        act, c, _ = forward(U, pre, ln, fb, None, out.get('c0'))
         act, c = act.astype(np.float32), c.astype(np.float32)
         # dOut ~ N(0,1) x a per-frame factor spanning 2^-20 .. 1 inside an utterance and 2^-20 .. 2^10 between utterances
         dout = np.zeros((T, Bp, D, Hp), dtype=np.float32)

@@ -101,14 +101,15 @@ int main(int argc, char** argv) {
   hipEvent_t e0, e1; CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
   float ms;
   PersistCtl hc;
+  StepWindow win{};   // the per-step kernels' side: the window of T steps on the A buffers
+  win.dm = dm; win.Uf = Uf; win.Ub = Ub; win.hstate = hst; win.partial = par; win.dcstate = dcs;
+  win.gates = gatesA; win.cbuf = cA; win.out = outA; win.dg = dgA; win.dout = dout; win.seq_len = seq; win.forget_bias = 1.0f;
 
   for (int rep = 0; rep < 3; ++rep) {
     // ---- forward, per-step
     CK(hipMemcpyAsync(gatesA, gates0, R * D * N4 * 4, hipMemcpyDeviceToDevice, st));
-    CK(hipMemsetAsync(hst, 0, hs * 4, st));
     CK(hipEventRecord(e0, st));
-    for (int s = 0; s < T; ++s)
-      launch_lstm_fwd_step(dm, s, Uf, hst + (s & 1) * hs, hst + ((s + 1) & 1) * hs, gatesA, cA, outA, seq, 1.0f, st);
+    lstm_steps_fwd(win, 0, T, st);                   // (with the memset of the first h image, as in a pass of the library)
     CK(hipEventRecord(e1, st)); CK(hipEventSynchronize(e1)); CK(hipEventElapsedTime(&ms, e0, e1));
     const float fstep = ms;
     // ---- forward, persistent
@@ -145,13 +146,8 @@ int main(int argc, char** argv) {
 #endif
     if (hc.error) return 1;
     // ---- backward, per-step (on the per-step forward's buffers)
-    CK(hipMemsetAsync(par, 0, ps * 4, st)); CK(hipMemsetAsync(dcs, 0, hs * 4, st));
     CK(hipEventRecord(e0, st));
-    for (int s = T - 1; s >= 0; --s) {
-      const int k = T - 1 - s;
-      launch_lstm_bwd_step(dm, s, Ub, par + (k & 1) * ps, par + ((k + 1) & 1) * ps, gatesA, dgA, cA, dout, dcs + (k & 1) * hs,
-                           dcs + ((k + 1) & 1) * hs, seq, st);
-    }
+    lstm_steps_bwd(win, 0, T, st);                   // (with the memsets of the first partial-sum and dc images)
     CK(hipEventRecord(e1, st)); CK(hipEventSynchronize(e1)); CK(hipEventElapsedTime(&ms, e0, e1));
     const float bstep = ms;
     CK(hipEventRecord(e0, st));

@@ -71,14 +71,15 @@ int main(int argc, char** argv) {
   hipEvent_t a, b; CK(hipEventCreate(&a)); CK(hipEventCreate(&b));
   const size_t hsz = (size_t)D * Bp * Hp;
   float msA = 0, msB = 0;
+  StepWindow win{};   // the per-step kernels' side: the window of T steps on the A buffers
+  win.dm = dm; win.Uf = Uf; win.Ub = Ub; win.hstate = hst;
+  win.gates = gatesA; win.cbuf = cA; win.out = oA; win.seq_len = seq; win.forget_bias = 1.f;
   // ---- reference: per-timestep kernels
   for (int rep = 0; rep < 2; ++rep) {
     CK(hipMemcpyAsync(gatesA, gates0, hg.size() * 4, hipMemcpyDeviceToDevice, st));
     CK(hipMemsetAsync(cA, 0, R * DH * 4, st)); CK(hipMemsetAsync(oA, 0xff, R * DH * 4, st));
-    CK(hipMemsetAsync(hst, 0, 2 * hsz * 4, st));
     CK(hipEventRecord(a, st));
-    for (int s = 0; s < T; ++s)
-      launch_lstm_fwd_step(dm, s, Uf, hst + (s & 1) * hsz, hst + ((s + 1) & 1) * hsz, gatesA, cA, oA, seq, 1.f, st);
+    lstm_steps_fwd(win, 0, T, st);                   // (with the memset of the first h image, as in a pass of the library)
     CK(hipEventRecord(b, st)); CK(hipEventSynchronize(b));
     CK(hipEventElapsedTime(&msA, a, b));
   }
@@ -208,13 +209,9 @@ int main(int argc, char** argv) {
     float msC = 0, msD = 0;
     for (int rep = 0; rep < 2; ++rep) {
       CK(hipMemsetAsync(dgA, 0xff, hg.size() * 4, st));
-      CK(hipMemsetAsync(par, 0, 2 * ps * 4, st)); CK(hipMemsetAsync(dcs, 0, 2 * hsz * 4, st));
+      win.partial = par; win.dcstate = dcs; win.dg = dgA; win.dout = dout;
       CK(hipEventRecord(a, st));
-      for (int s = T - 1; s >= 0; --s) {
-        const int k = T - 1 - s;
-        launch_lstm_bwd_step(dm, s, Ub, par + (k & 1) * ps, par + ((k + 1) & 1) * ps, gatesA, dgA, cA, dout, dcs + (k & 1) * hsz,
-                             dcs + ((k + 1) & 1) * hsz, seq, st);
-      }
+      lstm_steps_bwd(win, 0, T, st);                 // (with the memsets of the first partial-sum and dc images)
       CK(hipEventRecord(b, st)); CK(hipEventSynchronize(b));
       CK(hipEventElapsedTime(&msC, a, b));
     }
