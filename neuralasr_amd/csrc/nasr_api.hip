@@ -429,93 +429,6 @@ int nasr_stage_batch_context(nasr_handle h, const float* centre, const float* pa
   return stage(h, centre_batch(centre, pad_value, numcontext, numcep, seq_len, labels, label_len, B, T, Lmax, nullptr), ticket);
 }
 
-// The six nasr_*_batch_audio* calls (utils.py:24-31 feeding dataset.py:33-40), fn the one that was called: the checks, the
-// host-side plan (seq_len, T), and the front end as the producer of the slot's centre frames.  staged: into *ticket.
-static int audio_batch(const std::string& fn, nasr_ctx* h, nasr_ctx* fzh, const float* audio, const int64_t* offsets,
-                       const int32_t* rates, const int32_t* labels, const int32_t* label_len, int B, int Lmax,
-                       int32_t* seq_len_out, int* T_out, const nasr_batch_aug* aug, const nasr_wave_aug* wave, bool staged,
-                       int* ticket) {
-  if (!h) return NASR_ERR_ARG;
-  if (h->family == Family::Featurizer) return h->fail(NASR_ERR_STATE, fn + ": a featurizer handle has no model");   // MODEL_CALL
-  if (staged) {
-    if (!ticket) return h->fail(NASR_ERR_ARG, "null ticket");
-    *ticket = -1;
-  }
-  if (!fzh || !fzh->fz) return h->fail(NASR_ERR_STATE, fn + ": `featurizer` is not a featurizer handle");
-  if (fzh->device != h->device)
-    return h->fail(NASR_ERR_STATE, fn + ": the model is on device " + std::to_string(h->device) + ", the featurizer on device " +
-                                       std::to_string(fzh->device));
-  if (!audio || !offsets || !seq_len_out || !T_out) return h->fail(NASR_ERR_ARG, fn + ": null buffer");
-  if (B < 1 || B > 64) return validate_batch(h, nullptr, nullptr, nullptr, B, 1, 0);
-  int ctx = 0, ncep = 0;                 // ncep: the featurizer's frame width, numcep*(1+deltas)
-  if (fz_feature_width(fzh, &ctx, &ncep) != h->F)
-    return h->fail(NASR_ERR_ARG, fn + ": feature_size " + std::to_string(h->F) + " must equal (2*numcontext+1)*numcep*(1+deltas) = (2*" +
-                                     std::to_string(ctx) + "+1)*" + std::to_string(ncep) + " of the featurizer");
-  if (aug && aug->static_width != fz_static_width(fzh))
-    return h->fail(NASR_ERR_ARG, fn + ": augmentation: static_width " + std::to_string(aug->static_width) +
-                                     " is not the featurizer's numcep " + std::to_string(fz_static_width(fzh)));
-  FzPlan plan;
-  if (int rc = fz_plan(h, *fzh->fz, fn, offsets, rates, B, &plan)) return rc;
-  if (int rc = fz_wave_plan(h, *fzh->fz, fn, wave, &plan)) return rc;
-  int64_t Tmax = 0;
-  for (int b = 0; b < B; ++b) Tmax = std::max(Tmax, plan.foff[b + 1] - plan.foff[b]);
-  if (Tmax > (1 << 24)) return h->fail(NASR_ERR_ARG, fn + ": an utterance of " + std::to_string(Tmax) + " frames");
-  const int T = (int)Tmax;
-  for (int b = 0; b < B; ++b) seq_len_out[b] = (int32_t)(plan.foff[b + 1] - plan.foff[b]);
-  *T_out = T;
-  CentreProducer prod;
-  prod.stage_bytes = fz_stage_bytes(plan);
-  const float* first = audio + offsets[0];
-  prod.run = [&](float* dcentre, float* dpad, void* pinned, hipStream_t cs) {
-    return fz_produce_slot(h, fzh, plan, first, T, dcentre, dpad, pinned, cs);
-  };
-  const BatchSrc src = produced_batch(&prod, ctx, ncep, seq_len_out, labels, label_len, B, T, Lmax, aug);
-  return staged ? stage(h, src, ticket) : upload(h, src);
-}
-
-int nasr_upload_batch_audio(nasr_handle model, nasr_handle featurizer, const float* audio, const int64_t* offsets,
-                            const int32_t* rates, const int32_t* labels, const int32_t* label_len, int B, int Lmax,
-                            int32_t* seq_len_out, int* T_out) {
-  return audio_batch(__func__, model, featurizer, audio, offsets, rates, labels, label_len, B, Lmax, seq_len_out, T_out, nullptr,
-                     nullptr, false, nullptr);
-}
-
-int nasr_stage_batch_audio(nasr_handle model, nasr_handle featurizer, const float* audio, const int64_t* offsets,
-                           const int32_t* rates, const int32_t* labels, const int32_t* label_len, int B, int Lmax,
-                           int32_t* seq_len_out, int* T_out, int* ticket) {
-  return audio_batch(__func__, model, featurizer, audio, offsets, rates, labels, label_len, B, Lmax, seq_len_out, T_out, nullptr,
-                     nullptr, true, ticket);
-}
-
-int nasr_upload_batch_audio_aug(nasr_handle model, nasr_handle featurizer, const float* audio, const int64_t* offsets,
-                                const int32_t* rates, const int32_t* labels, const int32_t* label_len, int B, int Lmax,
-                                int32_t* seq_len_out, int* T_out, const nasr_batch_aug* aug) {
-  return audio_batch(__func__, model, featurizer, audio, offsets, rates, labels, label_len, B, Lmax, seq_len_out, T_out, aug,
-                     nullptr, false, nullptr);
-}
-
-int nasr_stage_batch_audio_aug(nasr_handle model, nasr_handle featurizer, const float* audio, const int64_t* offsets,
-                               const int32_t* rates, const int32_t* labels, const int32_t* label_len, int B, int Lmax,
-                               int32_t* seq_len_out, int* T_out, const nasr_batch_aug* aug, int* ticket) {
-  return audio_batch(__func__, model, featurizer, audio, offsets, rates, labels, label_len, B, Lmax, seq_len_out, T_out, aug,
-                     nullptr, true, ticket);
-}
-
-int nasr_upload_batch_audio_wave(nasr_handle model, nasr_handle featurizer, const float* audio, const int64_t* offsets,
-                                 const int32_t* rates, const int32_t* labels, const int32_t* label_len, int B, int Lmax,
-                                 int32_t* seq_len_out, int* T_out, const nasr_batch_aug* aug, const nasr_wave_aug* wave) {
-  return audio_batch(__func__, model, featurizer, audio, offsets, rates, labels, label_len, B, Lmax, seq_len_out, T_out, aug,
-                     wave, false, nullptr);
-}
-
-int nasr_stage_batch_audio_wave(nasr_handle model, nasr_handle featurizer, const float* audio, const int64_t* offsets,
-                                const int32_t* rates, const int32_t* labels, const int32_t* label_len, int B, int Lmax,
-                                int32_t* seq_len_out, int* T_out, const nasr_batch_aug* aug, const nasr_wave_aug* wave,
-                                int* ticket) {
-  return audio_batch(__func__, model, featurizer, audio, offsets, rates, labels, label_len, B, Lmax, seq_len_out, T_out, aug,
-                     wave, true, ticket);
-}
-
 int nasr_commit_batch(nasr_handle h, int ticket) {
   MODEL_CALL(h);
   if (!h) return NASR_ERR_ARG;

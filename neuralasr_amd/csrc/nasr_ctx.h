@@ -9,7 +9,8 @@
 //   nasr_comm.hip    RCCL bound with dlopen: nasr_comm_*
 //   nasr_wavenet.hip the WaveNet handle (nasr_create_wavenet): its layout, buffers, BN state and pass
 //   nasr_las.hip     the LAS handle (nasr_create_las): its layout, buffers, sampling state and pass
-//   mfcc.hip         the featurizer handle (nasr_create_featurizer): the MFCC front end's tables, buffers and kernels
+//   nasr_fz.hip      the featurizer handle (nasr_create_featurizer): the front end's tables, buffers, plans and calls, over
+//                    the kernels of mfcc.hip, resample.hip and wave_aug.hip; what a stream session needs of it: nasr_fz.h
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -33,8 +34,6 @@
 
 #include "../../include/nasr.h"
 #include "kernels.h"
-#include "resample.h"
-#include "wave_aug.h"
 
 namespace nasr_impl {
 using namespace nasr;
@@ -191,14 +190,14 @@ enum class Family { Lstm, WaveNet, Las, Featurizer };
 // What a WaveNet handle holds beyond the common parts (nasr_wavenet.hip); NULL on every other handle.
 struct WnState;
 struct WnStateDelete { void operator()(WnState* w) const; };
-// What a featurizer handle holds (mfcc.hip); NULL on every model handle.
+// What a featurizer handle holds (nasr_fz.hip); NULL on every model handle.
 struct FzState;
 struct FzStateDelete { void operator()(FzState* f) const; };
 // What a LAS handle holds beyond the common parts (nasr_las.hip); NULL on every other handle.
 struct LasState;
 struct LasStateDelete { void operator()(LasState* s) const; };
 
-// The front end of a stream session that takes samples (mfcc.hip: nasr_stream_attach_audio); NULL while the session is
+// The front end of a stream session that takes samples (nasr_fz.hip: nasr_stream_attach_audio); NULL while the session is
 // fed finished frames.
 struct FzStream;
 struct FzStreamDelete { void operator()(FzStream* f) const; };
@@ -627,54 +626,6 @@ inline BatchSrc produced_batch(const CentreProducer* producer, int ctx, int ncep
 int upload(nasr_ctx* h, const BatchSrc& b);
 BatchSlot* slot_of_ticket(nasr_ctx* h, int ticket);
 int stage(nasr_ctx* h, const BatchSrc& b, int* ticket);
-
-// ---- mfcc.hip: the front end as the device producer of a batch slot (nasr_upload_batch_audio, nasr_stage_batch_audio)
-// what a front-end call works out on the host before anything is launched
-struct FzPlan {
-  ResamplePlan rp;
-  bool rs = false;                     // some utterance is resampled: the kernels read the resampled buffer
-  int n = 0;
-  std::vector<int64_t> uoff, foff;     // [n+1] sample offsets (in the buffer the kernels read) and frame offsets
-  int64_t S_in = 0;                    // native samples
-  size_t mb = 0, meta_bytes = 0, rmeta_bytes = 0;
-  bool wave = false;                   // waveform augmentation: wp is filled, the kernels read its output
-  WavePlan wp;
-};
-int fz_plan(nasr_ctx* eh, FzState& z, const std::string& fn, const int64_t* offsets, const int32_t* rates, int n, FzPlan* p);
-// behind fz_plan: the checks of `wave` (nullable) against the featurizer's banks and its parameters into p; nothing is launched
-int fz_wave_plan(nasr_ctx* eh, FzState& z, const std::string& fn, const nasr_wave_aug* wave, FzPlan* p);
-size_t fz_stage_bytes(const FzPlan& p);
-int fz_produce_slot(nasr_ctx* eh, nasr_ctx* fzh, const FzPlan& p, const float* audio, int Tb, float* dcentre, float* dpad,
-                    void* pinned, hipStream_t st);
-int fz_feature_width(const nasr_ctx* fzh, int* numcontext, int* frame_width);   // (2*numcontext+1)*frame_width
-int fz_static_width(const nasr_ctx* fzh);                                        // the featurizer's numcep
-
-// ---- mfcc.hip: the front end of a stream session that takes samples (nasr_stream_attach_audio / _audio_rows / _feed_audio)
-// What one feed does to every slot, worked out on the host from the sample counts alone; nothing is launched or changed.
-struct FzFeedSlot {
-  // (int64 throughout: the kernels read an array of these as it is)
-  int64_t seg_off, ntail, in_off, nnew;   // the slot's segment of the work buffer: ntail carried samples, then nnew new ones
-  int64_t keep_off, nkeep;                // the part of the segment that is the next feed's tail
-  int64_t lead;                           // samples of the segment in front of the first new frame (0 or 1)
-  int64_t f_off, nfb, want;               // first new frame in the work buffers; frames before and after the feed
-  int64_t nnorm, upto, y_off;             // frames normalised before and after; first of them in the work buffer
-  int64_t T;                              // the utterance's frames when this feed completes it, else -1
-  int64_t rows0, nrows;                   // rows emitted before, and by this feed
-  int64_t n_after;                        // samples received after the feed
-};
-struct FzFeedPlan {
-  std::vector<FzFeedSlot> slot;
-  int64_t seg_total = 0, in_total = 0, f_total = 0, y_total = 0;
-  int Tc = 0;
-};
-// fzh must be a causal featurizer on device `device` whose rows are F wide: NASR_ERR_STATE / NASR_ERR_ARG as the header says
-int fz_stream_attach(nasr_ctx* eh, nasr_ctx* fzh, int S, std::unique_ptr<FzStream, FzStreamDelete>* out);
-int fz_stream_plan(nasr_ctx* eh, const FzStream& a, const std::string& fn, const int64_t* nnew, const uint8_t* last, FzFeedPlan* p);
-// the feed's kernels on stream st; dfeats [S][Tc][F] (NULL with Tc = 0: nothing is emitted) gets the stacked rows, zeros
-// behind each slot's
-int fz_stream_run(nasr_ctx* eh, FzStream& a, const FzFeedPlan& p, const float* audio, float* dfeats, hipStream_t st);
-void fz_stream_advance(FzStream& a, const FzFeedPlan& p, const uint8_t* last);   // the host's counts, once the kernels are queued
-void fz_stream_reset(FzStream& a, int slot);                                     // slot < 0: every slot
 
 inline float* dout_of(nasr_ctx* h, int) { return h->dout.as<float>(); }
 inline float* dg_of(nasr_ctx* h, int) { return h->dgbuf.as<float>(); }

@@ -10,9 +10,9 @@
 // R = 0 on a unidirectional network: nothing is ever held, E = n, the window is the chunk, and the state after the last
 // emitted row is the state after the slot's last frame.  nasr_stream_open_lookahead opens the sessions with R >= 1.
 // The rows of a feed come from the caller (nasr_stream_feed, nasr_stream_feed_lookahead) or, on a session that takes
-// samples (nasr_stream_attach_audio, nasr_stream_feed_audio), from a causal featurizer's front end (mfcc.hip:
+// samples (nasr_stream_attach_audio, nasr_stream_feed_audio), from a causal featurizer's front end (nasr_fz.hip:
 // fz_stream_*), which keeps per slot what it needs to turn the samples of a feed into stacked rows on the device.
-#include "nasr_ctx.h"
+#include "nasr_fz.h"
 
 using namespace nasr;
 using namespace nasr_impl;

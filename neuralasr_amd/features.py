@@ -7,7 +7,7 @@ returns the same samples and the file's own rate, and Featurizer resamples them 
 interpolation, then fix_length to ceil(n * sr / rate) samples.
 Featurizer runs python_speech_features 0.6's mfcc(nfilt=128), include_context and the whole-utterance normalisation (or,
 with normalization='causal', this project's running normalisation: DESIGN.md §16) on
-the GPU (neuralasr_amd/csrc/mfcc.hip), a batch of utterances per call; with `rates`, utterances at another rate are
+the GPU (the kernels of neuralasr_amd/csrc/mfcc.hip behind the featurizer handle of csrc/nasr_fz.hip), a batch of utterances per call; with `rates`, utterances at another rate are
 resampled first and the resampled samples stay on the device.  kind='logfbank' makes psf's logfbank (numcep log-mel
 filterbank energies) in the place of the MFCC, and deltas=1|2 appends psf's delta(feat, 2) columns (and their deltas)
 to every frame before the context stacking and the normalisation."""

@@ -3,7 +3,7 @@ logfbank (the log-mel filterbank energies: mfcc without the DCT, the lifter and 
 delta(feat, N=2), then include_context and the whole-utterance normalisation on the widened frames
 [static | delta | delta-delta].  Written from psf 0.6's documented procedure; psf is not installed, so neither the
 procedure nor the summation order (numpy.dot's, inside psf's delta) is pinned against the package.  The kernels of
-neuralasr_amd/csrc/mfcc.hip are checked against it."""
+neuralasr_amd/csrc/mfcc.hip (mfcc_spectral_kernel, mfcc_delta_kernel, mfcc_norm_kernel) are checked against it."""
 import numpy as np
 
 import mfcc_ref as R

@@ -1,7 +1,7 @@
 """fp64 NumPy restatement of the reference's MFCC front end (utils.py:24-31): python_speech_features 0.6's
 mfcc(audio, samplerate, numcep=numcep, nfilt=128) on float32 audio, include_context and the whole-utterance
-normalisation.  NumPy only (the DCT is an explicit cosine matrix): the kernels of neuralasr_amd/csrc/mfcc.hip are
-checked against it."""
+normalisation.  NumPy only (the DCT is an explicit cosine matrix): the kernels of neuralasr_amd/csrc/mfcc.hip
+(launched through csrc/mfcc.h by the featurizer handle, csrc/nasr_fz.hip) are checked against it."""
 import decimal
 import math
 

@@ -1,4 +1,4 @@
-"""GPU: the causal normalisation of the front end (csrc/mfcc.hip, cfg.norm = 1) against the fp64 restatement
+"""GPU: the causal normalisation of the front end (csrc/mfcc.hip: mfcc_norm_kernel<1, .>, cfg.norm = 1) against the fp64 restatement
 of tests/causal_ref.py, at the smallest shapes that can still go wrong: 8 kHz, 13 cepstra (and 8 log-mel filters),
 numcontext 0 and 2, norm_min_frames 1 and 3, utterances around every threshold of the rule, and one of 30 s (twelve
 chunks of the sequential prefix).  Tolerance: test_gpu_mfcc's TOL_MAX, TOL_MEAN - the running std of the MFCC cases is

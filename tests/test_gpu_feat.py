@@ -1,4 +1,4 @@
-"""GPU: the log-mel filterbank and the delta columns of the front end (csrc/mfcc.hip: cfg.kind, cfg.deltas) against the
+"""GPU: the log-mel filterbank and the delta columns of the front end (csrc/mfcc.hip under csrc/nasr_fz.hip: cfg.kind, cfg.deltas) against the
 fp64 restatement of tests/feat_ref.py on one ragged batch whose short utterances are shorter than the delta window
 and than the delta-delta's reach; the exact properties of the edge replication; batch invariance; buffer growth; the
 batch slot of a model handle; and preprocess_mfcc / train / train --from-audio / decode_wav on a config with the two

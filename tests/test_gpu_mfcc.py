@@ -1,4 +1,4 @@
-"""GPU: the MFCC front end (csrc/mfcc.hip) against the fp64 restatement of tests/mfcc_ref.py, for the feature shapes of
+"""GPU: the MFCC front end (kernels csrc/mfcc.hip, handle csrc/nasr_fz.hip) against the fp64 restatement of tests/mfcc_ref.py, for the feature shapes of
 the reference configs and the edge cases, plus batch invariance, run-to-run equality and the featurizer handle's
 refusal of model calls."""
 import ctypes
