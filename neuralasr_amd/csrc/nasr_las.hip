@@ -198,7 +198,8 @@ int las_ensure_shape(nasr_ctx* h, int B, int T, int Lmax) {
   ok &= s.dS.ensure((size_t)Bp * LAS_SW * 4, &grew);
   ok &= s.dcd.ensure((size_t)Bp * LAS_HD * 4, &grew);
   ok &= s.dvpart.ensure(UB * LAS_HD * 4, &grew);
-  ok &= s.csws.ensure((size_t)32 * 2 * LAS_G4E * 4, &grew);
+  // launch_colsum's 32 partial rows of the widest matrix the backward pass sums: dGe, dGd or dL (Cp has no upper bound)
+  ok &= s.csws.ensure((size_t)32 * std::max({2 * LAS_G4E, LAS_G4D, h->Cp}) * 4, &grew);
   if (!ok) return h->fail(NASR_ERR_HIP, "hipMalloc failed while sizing batch buffers");
   h->B = B; h->Bp = Bp; h->T = T; h->Lmax = Lmax; h->Tp = U; h->KS = 1;
   s.U = U;
