@@ -1,7 +1,9 @@
 // nasr_api.hip — the C ABI of include/nasr.h: every entry point names the reference interface it replaces there, and what
 // the create calls of all handle kinds share (handle_open, alloc_param_buffers, handle_finish).  The work
 // behind them lives in nasr_layout.hip (parameters, operand images), nasr_rec.hip (the recurrence, nasr_*_recurrence_mode),
-// nasr_batch.hip (batches), nasr_pass.hip (the step) and nasr_comm.hip (RCCL); the shared handle is nasr_ctx.h.
+// nasr_batch.hip (batches), nasr_pass.hip (the step) and nasr_comm.hip (RCCL); the shared handle is nasr_ctx.h.  Every call
+// here serves every model family; the set-up of a handle and the calls that only one family answers stand in that family's
+// file (nasr_lstm.hip, nasr_wavenet.hip, nasr_las.hip, nasr_fz.hip).  nasr_create is here for what it reads: the environment.
 #include "nasr_ctx.h"
 
 using namespace nasr;
@@ -41,7 +43,6 @@ int handle_open(const char* fn, Family family, int device_id, void* stream, nasr
     return refuse(NASR_ERR_HIP, std::string("device is ") + p.gcnArchName + ", libnasr is built for gfx950 only");
   if (prop) *prop = p;
   nasr_ctx* h = new nasr_ctx();
-  memset(&h->cfg, 0, sizeof(h->cfg));
   h->family = family;
   h->device = device_id;
   if (hipSetDevice(device_id) != hipSuccess) return create_fail(h, NASR_ERR_HIP, "hipSetDevice failed");
@@ -112,174 +113,25 @@ int handle_finish(nasr_ctx* h) {
 extern "C" {
 
 int nasr_create(const nasr_model_cfg* cfg, int device_id, void* stream, nasr_handle* out) {
-  if (!cfg || !out) {
-    g_create_error = "nasr_create: null argument";
-    return NASR_ERR_ARG;
-  }
-  *out = nullptr;
-  if (cfg->feature_size < 1 || cfg->hidden < 1 || cfg->num_layers < 1 || cfg->num_classes < 2) {
-    g_create_error = "nasr_create: feature_size, hidden, num_layers must be >= 1 and num_classes >= 2";
-    return NASR_ERR_ARG;
-  }
-  if (cfg->bidirectional && cfg->merge != NASR_MERGE_STACK_RESHAPE && cfg->merge != NASR_MERGE_CONCAT) {
-    g_create_error = "nasr_create: bidirectional nets need merge = STACK_RESHAPE or CONCAT";
-    return NASR_ERR_ARG;
-  }
-  if (cfg->num_pre < 0 || cfg->num_pre > 3 || cfg->post_width < 0) {
-    g_create_error = "nasr_create: num_pre must be in [0,3] and post_width >= 0";
-    return NASR_ERR_ARG;
-  }
-  for (int i = 0; i < cfg->num_pre; ++i)
-    if (cfg->pre_width[i] < 1) {
-      g_create_error = "nasr_create: pre_width[i] must be >= 1 for i < num_pre";
-      return NASR_ERR_ARG;
-    }
-  for (int i = 0; i < 4; ++i)
-    if (!(cfg->dropout[i] >= 0.f && cfg->dropout[i] < 1.f)) {
-      g_create_error = "nasr_create: dropout probabilities must be in [0,1)";
-      return NASR_ERR_ARG;
-    }
-  if ((cfg->num_pre > 0 || cfg->post_width > 0) && !(cfg->relu_clip > 0.f)) {
-    g_create_error = "nasr_create: relu_clip must be > 0 when dense stages are present";
-    return NASR_ERR_ARG;
-  }
-  if ((cfg->num_pre > 0 || cfg->post_width > 0) && cfg->bidirectional && cfg->merge != NASR_MERGE_CONCAT) {
-    g_create_error = "nasr_create: the DeepSpeech family concatenates the directions (merge = CONCAT)";
-    return NASR_ERR_ARG;
-  }
-  if (cfg->bidirectional && cfg->merge == NASR_MERGE_STACK_RESHAPE && cfg->num_layers != 1) {
-    g_create_error = "nasr_create: STACK_RESHAPE is the literal 1-layer BiLstmCTCNet; use CONCAT for stacks";
-    return NASR_ERR_ARG;
-  }
-  nasr_ctx* h = nullptr;
-  hipDeviceProp_t prop;
-  if (int rc = handle_open("nasr_create", Family::Lstm, device_id, stream, &h, &prop)) return rc;
-  h->cfg = *cfg;
-  if (!cfg->bidirectional) h->cfg.merge = NASR_MERGE_NONE;
-  h->lr = cfg->learning_rate;
-  if (build_layout(h) != NASR_OK) return create_fail(h, NASR_ERR_ARG, t_err);
-  {
-    const char* ec = getenv("NASR_COMPACT");
-    h->compactable = h->ndense == 0 && !(ec && ec[0] == '0');
-  }
-  {
-    h->sc_wr.resize(h->L); h->sc_wc.resize(h->L);
-    h->sc_dr.resize(h->ndense); h->sc_dc.resize(h->ndense); h->sc_yr.resize(h->ndense); h->sc_yc.resize(h->ndense);
-    {
-      bool ok = gemm_tph_prepare() == hipSuccess, g2 = false;
-      int rmax = 1, cmax = 1;
-      for (int l = 0; l < h->L; ++l) {
-        ok = ok && h->sc_wr[l].ensure((size_t)h->Ip[l]) && h->sc_wc[l].ensure((size_t)h->D * h->N4);
-        rmax = std::max(rmax, h->Ip[l]); cmax = std::max(cmax, h->D * h->N4);
-      }
-      for (int i = 0; i < h->ndense; ++i) {
-        ok = ok && h->sc_dr[i].ensure((size_t)h->dIp[i]) && h->sc_dc[i].ensure((size_t)h->dWp[i]);
-        rmax = std::max(rmax, h->dIp[i]); cmax = std::max(cmax, h->dWp[i]);
-      }
-      size_t wsf = 0;     // launch_tph_scales_batch works on all weight matrices at once
-      for (int l = 0; l < h->L; ++l) wsf += tph_scale_ws_floats(h->Ip[l], h->D * h->N4);
-      for (int i = 0; i < h->ndense; ++i) wsf += tph_scale_ws_floats(h->dIp[i], h->dWp[i]);
-      ok = ok && h->scws.ensure(std::max(wsf, tph_scale_ws_floats(rmax, cmax)) * 4, &g2);
-      if (!ok) return create_fail(h, NASR_ERR_HIP, "set-up of the fp16-plane GEMMs failed");
-    }
-    {
-      size_t of = 0, ob = 0;
-      h->off_wftp.resize(h->L); h->off_wbtp.resize(h->L);
-      for (int l = 0; l < h->L; ++l) {
-        h->off_wftp[l] = of; of += tph_bytes(h->D * h->N4, h->Ip[l]);
-        h->off_wbtp[l] = ob; if (l > 0 || h->npre > 0) ob += tph_bytes(h->Ip[l], h->D * h->N4);
-      }
-      size_t df = 0, db = 0;
-      h->off_dftp.assign(h->ndense, 0); h->off_dbtp.assign(h->ndense, 0);
-      for (int i = 0; i < h->ndense; ++i) {
-        h->off_dftp[i] = df; df += tph_bytes(h->dWp[i], h->dIp[i]);
-        h->off_dbtp[i] = db; if (i > 0 || h->npre == 0) db += tph_bytes(h->dIp[i], h->dWp[i]);
-      }
-      if (hipMalloc(h->WfTP.out(), of) != hipSuccess ||
-          hipMalloc(h->WbTP.out(), std::max<size_t>(ob, 1024)) != hipSuccess ||
-          hipMalloc(h->DfTP.out(), std::max<size_t>(df, 1024)) != hipSuccess ||
-          hipMalloc(h->DbTP.out(), std::max<size_t>(db, 1024)) != hipSuccess)
-        return create_fail(h, NASR_ERR_HIP, "hipMalloc of the tiled weight planes failed");
-    }
-  }
-  const size_t ub = (size_t)h->L * h->D * h->Hp * h->N4 * 4;
-  if (!alloc_param_buffers(h) || hipMalloc(h->Uf.out(), ub) != hipSuccess || hipMalloc(h->Ub.out(), ub) != hipSuccess)
-    return create_fail(h, NASR_ERR_HIP, "hipMalloc of parameter buffers failed");
-  {
-    // Buckets for an all-reduce that overlaps the rest of the backward pass (nasr_grad_bucket*): the internal layout
-    // is [head | dense stages | layer 0 | ... | layer L-1 | W | b] and backward() finishes W, b first, then the layers
-    // from the top down, then the dense stages in front of the stack.  Bucket 0 = layer L-1 + W + b, then one bucket
-    // per layer down to layer 1, and a last one with everything in front of layer 1 INCLUDING the fault word, which
-    // any launch of the step may still raise.  A one-layer net has a single bucket, unless dense stages precede it.
-    h->bucket_of_layer.assign(h->L, -1);
-    if (h->L > 1 && h->L <= MAX_BUCKETS) {
-      for (int l = h->L - 1; l >= 1; --l) {
-        const int64_t lo = h->off_wx[l], hi = l == h->L - 1 ? h->np_int : h->off_wx[l + 1];
-        h->bucket_of_layer[l] = (int)h->buckets.size();
-        h->buckets.push_back({GRAD_HEAD + lo, hi - lo});
-      }
-      h->buckets.push_back({0, GRAD_HEAD + h->off_wx[1]});
-    } else if (h->L == 1 && h->npre > 0) {
-      // a DeepSpeech-shaped net: the (Bi)LSTM's gradients (4/5 of the parameters at the reference's widths) + W + b are
-      // complete before the backward pass of the dense stages in front of it, which then hides their all-reduce
-      h->bucket_of_layer[0] = 0;
-      h->buckets.push_back({GRAD_HEAD + h->off_wx[0], h->np_int - h->off_wx[0]});
-      h->buckets.push_back({0, GRAD_HEAD + h->off_wx[0]});
-    } else {
-      h->buckets.push_back({0, GRAD_HEAD + h->np_int});
-    }
-  }
-  (void)hipMemsetAsync(h->Uf, 0, ub, h->st);
-  (void)hipMemsetAsync(h->Ub, 0, ub, h->st);
-  {
-    const char* e = getenv("NASR_PERSIST");
-    const char* er = getenv("NASR_REC");
-    if (rec_setup(h, !(e && e[0] == '0') && prop.multiProcessorCount == 256, er && std::string(er) == "f32") != NASR_OK)
-      return create_fail(h, NASR_ERR_HIP, t_err);
-  }
-  h->gates.resize(h->L);
-  h->OTT.resize(h->L);
-  h->ott_valid.assign(h->L, 0);
-  h->outb.resize(h->L);
-  h->cbuf.resize(h->L);
-  h->Ybuf.resize(h->ndense);
-  h->dYbuf.resize(h->ndense);
-  if (int rc = handle_finish(h)) return rc;
-  {
-    const char* eo = getenv("NASR_WGRAD_OVERLAP");
-    const bool eligible = h->rec_kind == RecKind::Persist && h->Hp == 512 && h->L > 1;
-    h->wg_overlap = eligible && !(eo && eo[0] == '0');          // on unless NASR_WGRAD_OVERLAP=0 (nasr_set_wgrad_overlap)
-    h->ev_wg.resize(h->L);
-    h->wg_pending.assign(h->L, 0);
-    if (eligible) {
-      int lo = 0, hi = 0;
-      (void)hipDeviceGetStreamPriorityRange(&lo, &hi);          // lo = lowest priority (largest number)
-      if (hipStreamCreateWithPriority(h->wst.out(), hipStreamNonBlocking, lo) != hipSuccess ||
-          hipEventCreateWithFlags(h->ev_dx.out(), hipEventDisableTiming) != hipSuccess)
-        return create_fail(h, NASR_ERR_HIP, "set-up of the weight-gradient side stream failed");
-      for (auto& e : h->ev_wg)
-        if (hipEventCreateWithFlags(e.out(), hipEventDisableTiming) != hipSuccess) return create_fail(h, NASR_ERR_HIP, "hipEventCreate failed");
-      h->bwd_lean = true;
-    }
-  }
-  if (h->rec_kind != RecKind::Step) {
-    const char* er = getenv("NASR_PERSIST_REARM");
-    h->rearm_after = er && *er ? std::max<long long>(0, atoll(er)) : 200;
-  }
-  if (h->rec_kind == RecKind::Persist) {
-    const char* eb = getenv("NASR_BUCKET_DEFER");
-    h->bucket_defer = !(eb && eb[0] == '0');
-  }
-  rec_start(h);   // the census, after the weight-gradient side stream that its BPTT launch makes room for
-  *out = h;
-  return NASR_OK;
+  // the create-time switches of README: the environment is read here and nowhere else; the set-up takes them as values
+  auto off = [](const char* name) { const char* e = getenv(name); return e && e[0] == '0'; };
+  const char *rec = getenv("NASR_REC"), *rearm = getenv("NASR_PERSIST_REARM");
+  LstmSwitches sw;
+  sw.compact = !off("NASR_COMPACT");
+  sw.persist = !off("NASR_PERSIST");
+  sw.rec_f32 = rec && std::string(rec) == "f32";
+  sw.wgrad_overlap = !off("NASR_WGRAD_OVERLAP");
+  sw.bucket_defer = !off("NASR_BUCKET_DEFER");
+  sw.rearm_after = rearm && *rearm ? std::max<long long>(0, atoll(rearm)) : 200;
+  return lstm_create(cfg, device_id, stream, sw, out);
 }
 
 int nasr_destroy(nasr_handle h) {
   if (!h) return NASR_OK;
   (void)hipSetDevice(h->device);
-  for (const Stream* s : {&h->st, &h->cst, &h->d2h, &h->wst})
+  for (const Stream* s : {&h->st, &h->cst, &h->d2h})
     if (*s) (void)hipStreamSynchronize(*s);
+  lstm_sync_side(h);
   (void)nasr_comm_destroy(h);
   drop_graphs(h);
   delete h;   // the owners in nasr_ctx release its memory, streams and events
@@ -384,8 +236,11 @@ int nasr_set_learning_rate(nasr_handle h, float lr) {
 int nasr_logit_frames(nasr_handle h, int T) {
   MODEL_CALL(h);
   if (!h) return NASR_ERR_ARG;
-  if (h->family == Family::Las) return h->fail(NASR_ERR_STATE, "nasr_logit_frames: a LAS handle has no CTC logit frames");
-  return (h->cfg.bidirectional && h->cfg.merge == NASR_MERGE_STACK_RESHAPE) ? 2 * T : T;
+  switch (h->family) {
+    case Family::Las: return h->fail(NASR_ERR_STATE, "nasr_logit_frames: a LAS handle has no CTC logit frames");
+    case Family::Lstm: return lstm_logit_frames(h, T);
+    default: return T;
+  }
 }
 
 int nasr_upload_batch(nasr_handle h, const float* feats, const int32_t* seq_len, const int32_t* labels,
@@ -513,10 +368,10 @@ int nasr_apply_adam(nasr_handle h, float grad_scale) {
   {
     PhaseScope ps(h, PH_ADAM);
     if (h->max_grad_norm > 0.f)   // the norm of the (all-reduced) gradient first; its second stage decides the step on the device
-      launch_adam_clipped(h->P, h->M, h->V, h->G, h->np_int, h->adam_dev, h->clip_dev, h->clip_part, h->lr, h->cfg.beta1,
-                          h->cfg.beta2, h->cfg.epsilon, grad_scale, h->max_grad_norm, h->Gbase, h->st);
+      launch_adam_clipped(h->P, h->M, h->V, h->G, h->np_int, h->adam_dev, h->clip_dev, h->clip_part, h->lr, h->beta1,
+                          h->beta2, h->epsilon, grad_scale, h->max_grad_norm, h->Gbase, h->st);
     else
-      launch_adam(h->P, h->M, h->V, h->G, h->np_int, h->adam_dev, h->lr, h->cfg.beta1, h->cfg.beta2, h->cfg.epsilon, grad_scale,
+      launch_adam(h->P, h->M, h->V, h->G, h->np_int, h->adam_dev, h->lr, h->beta1, h->beta2, h->epsilon, grad_scale,
                   h->Gbase, h->st);
     int rc = repack(h);
     if (rc) return rc;
@@ -704,55 +559,6 @@ int nasr_resident_frames(nasr_handle h, int64_t* frames) {
   MODEL_CALL(h);
   if (!h || !frames) return NASR_ERR_ARG;
   *frames = h->resident ? h->frames : 0;
-  return NASR_OK;
-}
-
-int nasr_set_row_compaction(nasr_handle h, int enabled) {
-  MODEL_CALL(h);
-  if (!h) return NASR_ERR_ARG;
-  LSTM_CALL(h, "has no recurrence to compact rows for");
-  // what the resident batch's plane buffers hold depends on it: takes effect with the next uploaded / committed batch
-  h->compactable = enabled && h->ndense == 0;
-  return NASR_OK;
-}
-
-int nasr_set_chunking(nasr_handle h, int C, int R) {
-  MODEL_CALL(h);
-  if (!h) return NASR_ERR_ARG;
-  LSTM_CALL(h, "has no bidirectional recurrence to run in windows");
-  const std::string fn = "nasr_set_chunking";
-  if (h->stream) return h->fail(NASR_ERR_STATE, fn + ": a stream session is open: close it first");
-  if (C != 0) {
-    if (C < 1 || C > 4096) return h->fail(NASR_ERR_ARG, fn + ": C = " + std::to_string(C) + " chunk frames: must be in [1,4096], or 0 = off");
-    if (R < 1 || R > 1024) return h->fail(NASR_ERR_ARG, fn + ": R = " + std::to_string(R) + " look-ahead frames: must be in [1,1024]");
-    if (!h->cfg.bidirectional)
-      return h->fail(NASR_ERR_STATE, fn + ": a unidirectional network needs no look-ahead: its graph is causal already");
-    if (h->cfg.merge != NASR_MERGE_CONCAT)
-      return h->fail(NASR_ERR_STATE, fn + ": NASR_MERGE_STACK_RESHAPE cannot stream: its logits mix frames of the whole padded batch, so "
-                                          "no chunk of it is a point in time");
-    for (int i = 0; i < 4; ++i)
-      if (h->cfg.dropout[i] != 0.f)
-        return h->fail(NASR_ERR_STATE, fn + ": dropout[" + std::to_string(i) + "] = " + std::to_string(h->cfg.dropout[i]) +
-                                           ": a network with dropout cannot stream (the reference applies dropout in every graph, "
-                                           "keyed by the pass counter)");
-    if (h->ndense)
-      return h->fail(NASR_ERR_STATE, fn + ": a network with dense stages (the DeepSpeech family) is not trained in windows yet");
-  }
-  const int Rn = C ? R : 0;
-  if (C == h->lcC && Rn == h->lcR) return NASR_OK;
-  h->lcC = C;
-  h->lcR = Rn;
-  // the resident batch is laid out for the setting it was uploaded under: the next pass needs a new upload
-  h->resident = false;
-  h->have_grads = h->have_fwd = h->have_decoded = false;
-  return NASR_OK;
-}
-
-int nasr_get_chunking(nasr_handle h, int* C, int* R) {
-  MODEL_CALL(h);
-  if (!h) return NASR_ERR_ARG;
-  if (C) *C = h->lcC;
-  if (R) *R = h->lcR;
   return NASR_OK;
 }
 
@@ -1046,56 +852,6 @@ int nasr_set_graph_mode(nasr_handle h, int enabled) {
   if (!h) return NASR_ERR_ARG;
   h->graph_mode = enabled != 0;
   if (!h->graph_mode) drop_graphs(h);
-  return NASR_OK;
-}
-
-int nasr_set_dropout_state(nasr_handle h, uint32_t seed, uint32_t counter) {
-  MODEL_CALL(h);
-  if (!h) return NASR_ERR_ARG;
-  LSTM_CALL(h, "has no dropout");
-  h->drop_seed = seed;
-  h->drop_counter = counter;
-  return NASR_OK;
-}
-
-int nasr_get_dropout_state(nasr_handle h, uint32_t* seed, uint32_t* counter) {
-  MODEL_CALL(h);
-  if (!h) return NASR_ERR_ARG;
-  LSTM_CALL(h, "has no dropout");
-  if (seed) *seed = h->drop_seed;
-  if (counter) *counter = h->drop_counter;
-  return NASR_OK;
-}
-
-int nasr_set_wgrad_overlap(nasr_handle h, int enabled) {
-  MODEL_CALL(h);
-  if (!h) return NASR_ERR_ARG;
-  LSTM_CALL(h, "has no recurrence");
-  if (enabled && !h->wst) return h->fail(NASR_ERR_STATE, "the weight-gradient side stream was not set up for this handle "
-                                                         "(needs the persistent recurrence at Hp = 512 and more than one layer)");
-  HIPCHK(h, hipStreamSynchronize(h->st));
-  h->wg_overlap = enabled != 0;
-  if (h->resident) return ensure_shape(h, h->B, h->T, h->Lmax, h->lc_live);     // the side stream's own copies of the dG planes
-  return NASR_OK;
-}
-
-int nasr_get_wgrad_overlap(nasr_handle h) {
-  MODEL_CALL(h);
-  return h && h->wg_overlap ? 1 : 0;
-}
-
-int nasr_set_bucket_defer(nasr_handle h, int defer) {
-  MODEL_CALL(h);
-  if (!h) return NASR_ERR_ARG;
-  h->bucket_defer = defer != 0;
-  return NASR_OK;
-}
-
-int nasr_get_persist_stats(nasr_handle h, int* aborts, int* rearms) {
-  MODEL_CALL(h);
-  if (!h) return NASR_ERR_ARG;
-  if (aborts) *aborts = h->persist_aborts;
-  if (rearms) *rearms = h->persist_rearms;
   return NASR_OK;
 }
 

@@ -1,7 +1,7 @@
 // nasr_batch.hip — the batch side of a handle: HBM buffers sized to the batch shape, input validation, and the batch slots
 // (synchronous upload, staging through pinned memory on the copy stream, commit).  Replaces the feed_dict of
 // TensorFlowNetwork.train (networks/tfnetwork.py:183-190) and DataSet.get_next_batch's hand-over (dataset.py:33-40).
-#include "nasr_ctx.h"
+#include "nasr_lstm.h"
 
 using namespace nasr;
 using namespace nasr_impl;
@@ -35,91 +35,95 @@ int ensure_shape(nasr_ctx* h, int B, int T, int Lmax, bool chunked) {
   switch (h->family) {
     case Family::WaveNet: return wn_ensure_shape(h, B, T, Lmax);
     case Family::Las: return las_ensure_shape(h, B, T, Lmax);
-    default: break;
+    default: return lstm_ensure_shape(h, B, T, Lmax, chunked);
   }
+}
+
+int lstm_ensure_shape(nasr_ctx* h, int B, int T, int Lmax, bool chunked) {
+  LstmState* const ls = h->lstm.get();
   const int Bp = rup(B, 16);
-  const int Tp = nasr_logit_frames(h, T);
+  const int Tp = lstm_logit_frames(h, T);
   // the LSTM stack's time axis: the batch's frames, or the rows of its windows
   LcGeom lg{};
   if (chunked) {
-    lg.C = h->lcC; lg.W = std::min(h->lcC + h->lcR, T); lg.K = lc_last_window(T, lg.C, lg.W) + 1; lg.T = T; lg.Bp = Bp;
+    lg.C = ls->lcC; lg.W = std::min(ls->lcC + ls->lcR, T); lg.K = lc_last_window(T, lg.C, lg.W) + 1; lg.T = T; lg.Bp = Bp;
     if ((int64_t)lg.K * lg.W * Bp > ((int64_t)1 << 22))
       return h->fail(NASR_ERR_ARG, "chunked batch: " + std::to_string(lg.K) + " windows of " + std::to_string(lg.W) + " rows x " +
                                        std::to_string(Bp) + " utterances are more than 2^22 rows: use a longer chunk or a shorter look-ahead");
   }
   const int Tv = chunked ? lg.K * lg.W : T;
   const size_t R = (size_t)Tv * Bp;
-  const int D = h->D, Hp = h->Hp, N4 = h->N4;
+  const int D = ls->D, Hp = ls->Hp, N4 = ls->N4;
   bool grew = false;
   bool ok = true;
   const int KSa = ensure_ctc_buffers(h, B, Bp, T, Tp, Lmax, &grew);
   if (KSa < 0) return KSa;
   ok &= h->X0.ensure(R * h->Fp * 4, &grew);
   if (chunked) {
-    ok &= h->lc_x0.ensure((size_t)T * Bp * h->Fp * 4, &grew);
-    ok &= h->lc_top.ensure((size_t)T * Bp * h->Pinp * 4, &grew) && h->lc_dtop.ensure((size_t)T * Bp * h->Pinp * 4, &grew);
-    ok &= h->lc_cimg.ensure((size_t)D * Bp * Hp * 4, &grew) && h->lc_dcc.ensure((size_t)Bp * Hp * 4, &grew);
+    ok &= ls->lc_x0.ensure((size_t)T * Bp * h->Fp * 4, &grew);
+    ok &= ls->lc_top.ensure((size_t)T * Bp * ls->Pinp * 4, &grew) && ls->lc_dtop.ensure((size_t)T * Bp * ls->Pinp * 4, &grew);
+    ok &= ls->lc_cimg.ensure((size_t)D * Bp * Hp * 4, &grew) && ls->lc_dcc.ensure((size_t)Bp * Hp * 4, &grew);
   }
   ok &= h->seqbuf.ensure((size_t)Bp * 4, &grew);
-  ok &= h->dout.ensure(R * D * Hp * 4, &grew);
-  ok &= h->hstate.ensure((size_t)2 * D * Bp * Hp * 4, &grew);
-  ok &= h->partial.ensure((size_t)2 * D * (Hp / 32) * Bp * Hp * 4, &grew);
-  ok &= h->dcstate.ensure((size_t)2 * D * Bp * Hp * 4, &grew);
-  ok &= h->dgbuf.ensure(R * D * N4 * 4, &grew);
-  if (h->rec_kind == RecKind::Persist) ok &= h->dgmax.ensure(persist_dgmax_floats(T, Bp, Hp, D) * 4, &grew);
+  ok &= ls->dout.ensure(R * D * Hp * 4, &grew);
+  ok &= ls->hstate.ensure((size_t)2 * D * Bp * Hp * 4, &grew);
+  ok &= ls->partial.ensure((size_t)2 * D * (Hp / 32) * Bp * Hp * 4, &grew);
+  ok &= ls->dcstate.ensure((size_t)2 * D * Bp * Hp * 4, &grew);
+  ok &= ls->dgbuf.ensure(R * D * N4 * 4, &grew);
+  if (ls->rec_kind == RecKind::Persist) ok &= ls->dgmax.ensure(persist_dgmax_floats(T, Bp, Hp, D) * 4, &grew);
   {
     int ipmax = h->Fp, wmax = D * N4;
-    for (int l = 0; l < h->L; ++l) ipmax = std::max(ipmax, h->Ip[l]);
-    for (int i = 0; i < h->ndense; ++i) { ipmax = std::max(ipmax, h->dIp[i]); wmax = std::max(wmax, h->dWp[i]); }
-    ok &= h->XTP.ensure(tph_bytes((int)R, ipmax), &grew);
-    ok &= h->X0TTP.ensure(tph_bytes(h->Ip[0], (int)R), &grew);
-    for (int l = 0; l < h->L; ++l) ok &= h->OTT[l].ensure(tph_bytes(D * Hp, (int)R), &grew);
-    ok &= h->GTP.ensure(tph_bytes((int)R, wmax), &grew);
-    ok &= h->GTTP.ensure(tph_bytes(wmax, (int)R), &grew);
-    if (h->wg_overlap) {
-      ok &= h->GTTP2.ensure(tph_bytes(wmax, (int)R), &grew);
-      ok &= h->sc_gc2.ensure((size_t)wmax);
+    for (int l = 0; l < ls->L; ++l) ipmax = std::max(ipmax, ls->Ip[l]);
+    for (int i = 0; i < ls->ndense; ++i) { ipmax = std::max(ipmax, ls->dIp[i]); wmax = std::max(wmax, ls->dWp[i]); }
+    ok &= ls->XTP.ensure(tph_bytes((int)R, ipmax), &grew);
+    ok &= ls->X0TTP.ensure(tph_bytes(ls->Ip[0], (int)R), &grew);
+    for (int l = 0; l < ls->L; ++l) ok &= ls->OTT[l].ensure(tph_bytes(D * Hp, (int)R), &grew);
+    ok &= ls->GTP.ensure(tph_bytes((int)R, wmax), &grew);
+    ok &= ls->GTTP.ensure(tph_bytes(wmax, (int)R), &grew);
+    if (ls->wg_overlap) {
+      ok &= ls->GTTP2.ensure(tph_bytes(wmax, (int)R), &grew);
+      ok &= ls->sc_gc2.ensure((size_t)wmax);
     }
-    if (h->ndense) ok &= h->DTP.ensure(tph_bytes(ipmax, (int)R), &grew);
+    if (ls->ndense) ok &= ls->DTP.ensure(tph_bytes(ipmax, (int)R), &grew);
     {
       const size_t n15 = std::max<size_t>(R, (size_t)std::max(ipmax, wmax));
-      if (n15 > h->sc15_n) {
-        ok &= h->sc15.ensure(n15);
+      if (n15 > ls->sc15_n) {
+        ok &= ls->sc15.ensure(n15);
         if (ok) {
-          launch_fill(h->sc15.sp(), 32768.f, (int)n15, h->st);
-          launch_fill(h->sc15.ip(), 1.f / 32768.f, (int)n15, h->st);
-          h->sc15_n = n15;
+          launch_fill(ls->sc15.sp(), 32768.f, (int)n15, h->st);
+          launch_fill(ls->sc15.ip(), 1.f / 32768.f, (int)n15, h->st);
+          ls->sc15_n = n15;
         }
       }
-      ok &= h->sc_x0r.ensure(R) && h->sc_x0c.ensure((size_t)h->Fp);
-      ok &= h->sc_gr.ensure(R) && h->sc_gc.ensure((size_t)wmax);
-      if (h->compactable || chunked) {
-        ok &= h->sc_cr.ensure(R + 64) && h->sc_cx.ensure(R + 64);
-        ok &= h->OTS.ensure((h->wg_overlap ? 2 : 1) * tph_bytes(D * Hp, (int)R), &grew);
+      ok &= ls->sc_x0r.ensure(R) && ls->sc_x0c.ensure((size_t)h->Fp);
+      ok &= ls->sc_gr.ensure(R) && ls->sc_gc.ensure((size_t)wmax);
+      if (ls->compactable || chunked) {
+        ok &= ls->sc_cr.ensure(R + 64) && ls->sc_cx.ensure(R + 64);
+        ok &= ls->OTS.ensure((ls->wg_overlap ? 2 : 1) * tph_bytes(D * Hp, (int)R), &grew);
       }
-      for (int i = 0; i < h->ndense; ++i) ok &= h->sc_yr[i].ensure(R) && h->sc_yc[i].ensure((size_t)h->dWp[i]);
+      for (int i = 0; i < ls->ndense; ++i) ok &= ls->sc_yr[i].ensure(R) && ls->sc_yc[i].ensure((size_t)ls->dWp[i]);
       bool g2 = false;
-      ok &= h->scws.ensure(tph_scale_ws_floats((int)R, std::max(ipmax, wmax)) * 4, &g2);
+      ok &= ls->scws.ensure(tph_scale_ws_floats((int)R, std::max(ipmax, wmax)) * 4, &g2);
     }
   }
   int csw = std::max(D * N4, h->Cp);
-  for (int i = 0; i < h->ndense; ++i) csw = std::max(csw, h->dWp[i]);
+  for (int i = 0; i < ls->ndense; ++i) csw = std::max(csw, ls->dWp[i]);
   // column-sum partials: 32 rows of launch_colsum, or the 64-row partials of the split pass (tp_split2_parts)
-  ok &= h->csws.ensure((size_t)std::max(32, tp_split2_parts((int)R)) * csw * 4, &grew);
-  if (h->wg_overlap) ok &= h->csws2.ensure((size_t)std::max(32, tp_split2_parts((int)R)) * csw * 4, &grew);
-  for (int i = 0; i < h->ndense; ++i) {
-    ok &= h->Ybuf[i].ensure(R * h->dWp[i] * 4, &grew);
-    ok &= h->dYbuf[i].ensure(R * h->dWp[i] * 4, &grew);
+  ok &= ls->csws.ensure((size_t)std::max(32, tp_split2_parts((int)R)) * csw * 4, &grew);
+  if (ls->wg_overlap) ok &= ls->csws2.ensure((size_t)std::max(32, tp_split2_parts((int)R)) * csw * 4, &grew);
+  for (int i = 0; i < ls->ndense; ++i) {
+    ok &= ls->Ybuf[i].ensure(R * ls->dWp[i] * 4, &grew);
+    ok &= ls->dYbuf[i].ensure(R * ls->dWp[i] * 4, &grew);
   }
-  for (int l = 0; l < h->L; ++l) {
-    ok &= h->gates[l].ensure(R * D * N4 * 4, &grew);
-    ok &= h->outb[l].ensure(R * D * Hp * 4, &grew);
-    ok &= h->cbuf[l].ensure(R * D * Hp * 4, &grew);
+  for (int l = 0; l < ls->L; ++l) {
+    ok &= ls->gates[l].ensure(R * D * N4 * 4, &grew);
+    ok &= ls->outb[l].ensure(R * D * Hp * 4, &grew);
+    ok &= ls->cbuf[l].ensure(R * D * Hp * 4, &grew);
   }
   if (!ok) return h->fail(NASR_ERR_HIP, "hipMalloc failed while sizing batch buffers");
   if (grew || Bp != h->Bp) drop_graphs(h);
   h->B = B; h->Bp = Bp; h->T = T; h->Lmax = Lmax; h->Tp = Tp; h->KS = KSa;
-  h->Tv = Tv; h->lc_live = chunked; h->lcg = lg;
+  ls->Tv = Tv; ls->lc_live = chunked; ls->lcg = lg;
   return NASR_OK;
 }
 
@@ -234,7 +238,9 @@ void slot_set_state(nasr_ctx* h, BatchSlot* s, int st) {
   s->state = st;
 }
 
-static bool stack_reshape(const nasr_ctx* h) { return h->cfg.merge == NASR_MERGE_STACK_RESHAPE && h->D == 2; }
+static bool stack_reshape(const nasr_ctx* h) {
+  return h->lstm && h->lstm->cfg.merge == NASR_MERGE_STACK_RESHAPE && h->lstm->D == 2;
+}
 
 // slot_fill (1): the argument checks, in this order; *masked: aug has a mask of non-zero width
 static int check_batch(nasr_ctx* h, const BatchSrc& b, bool* masked) {
@@ -254,6 +260,7 @@ static int check_batch(nasr_ctx* h, const BatchSrc& b, bool* masked) {
 // slot_fill (2): the slot's shape and the layout of its meta block (int32): seq [Bp] | lablen [Bp] | labels [B*Lm] |
 // cstart [B*(C+1)] | cpos [B*Lm] | rowmap [Tp*Bp] | vrow, vprev, vnext [Rvp] | masks [B*nm] of int4.  No HIP call.
 static void meta_layout(nasr_ctx* h, BatchSlot* s, const BatchSrc& b, bool masked) {
+  const LstmState* const ls = h->lstm.get();   // NULL: a handle of another family, which neither compacts rows nor runs windows
   const int B = b.B, T = b.T;
   s->B = B; s->T = T; s->Lmax = b.labels ? b.Lmax : 0; s->ctx = b.ctx; s->ncep = b.ncep;
   s->Bp = rup(B, 16);
@@ -274,12 +281,12 @@ static void meta_layout(nasr_ctx* h, BatchSlot* s, const BatchSrc& b, bool maske
   s->o_rowmap = s->o_cpos + BLm;
   // compacted rows: worth it when at least 15 % of the T x Bp rows are padding (profiles/r03_row_compaction_ab.log: even at
   // 10 %), and only for training batches
-  s->cmp = h->compactable && b.labels && s->frames * 20 <= (int64_t)T * s->Bp * 17;
+  s->cmp = ls && ls->compactable && b.labels && s->frames * 20 <= (int64_t)T * s->Bp * 17;
   s->Rv = s->cmp ? (int)s->frames : 0;
   // a batch under nasr_set_chunking: the row lists are those of its windows, always (a stream chunk is no such batch)
-  const bool lc = h->family == Family::Lstm && h->lcC > 0 && !b.chunk;
+  const bool lc = ls && ls->lcC > 0 && !b.chunk;
   s->chunk = b.chunk;
-  s->lcC = lc ? h->lcC : 0; s->lcR = lc ? h->lcR : 0;
+  s->lcC = lc ? ls->lcC : 0; s->lcR = lc ? ls->lcR : 0;
   s->lcW = lc ? std::min(s->lcC + s->lcR, T) : 0;      // (a window never has more rows than the batch has frames)
   s->lcK = lc ? lc_last_window(T, s->lcC, s->lcW) + 1 : 0;
   if (lc) {
@@ -435,9 +442,10 @@ static int slot_fill(nasr_ctx* h, BatchSlot* s, const BatchSrc& b, hipStream_t c
 // Makes the filled slot the resident batch: the compute stream waits for its copies, the previous resident slot is
 // released, and the features are laid out for the step (time-major rows, context windows, operand scales).
 int slot_commit(nasr_ctx* h, BatchSlot* s) {
+  LstmState* const ls = h->lstm.get();   // NULL: a handle of another family
   HIPCHK(h, hipSetDevice(h->device));
   // (a slot is laid out for the chunking of the moment it was filled; a stream chunk never is)
-  if (h->family == Family::Lstm && !s->chunk && (s->lcC != h->lcC || s->lcR != (h->lcC ? h->lcR : 0)))
+  if (ls && !s->chunk && (s->lcC != ls->lcC || s->lcR != (ls->lcC ? ls->lcR : 0)))
     return h->fail(NASR_ERR_STATE, "the batch was staged under another nasr_set_chunking than the handle has now: stage it again");
   int rc = ensure_shape(h, s->B, s->T, s->Lmax, s->lcC > 0);
   if (rc) return rc;
@@ -459,7 +467,8 @@ int slot_commit(nasr_ctx* h, BatchSlot* s) {
   HIPCHK(h, hipMemcpyAsync(h->seqbuf.p, md + s->o_seq, (size_t)Bp * 4, hipMemcpyDeviceToDevice, h->st));
   h->seq_p = h->seqbuf.as<int32_t>(); h->lablen_p = md + s->o_lablen; h->labels_p = md + s->o_labels;
   h->cstart_p = md + s->o_cstart; h->cpos_p = md + s->o_cpos; h->rowmap_p = md + s->o_rowmap;
-  const bool cmp = s->cmp && (h->compactable || s->lcC);   // (staged with it on, switched off since: the slot's row lists go unused)
+  // (staged with compaction on, switched off since: the slot's row lists go unused; s->cmp: only ever on an LSTM-family handle)
+  const bool cmp = s->cmp && ls && (ls->compactable || s->lcC);
   h->wlen_p = md + s->o_wlen;
   h->cmp_rows = cmp ? s->Rv : 0;
   h->cmp_rows_p = cmp ? s->Rvp : 0;
@@ -477,7 +486,8 @@ int slot_commit(nasr_ctx* h, BatchSlot* s) {
   h->frames = s->frames;
   {
     PhaseScope ps(h, PH_PACK);
-    float* x0 = (h->lc_live ? h->lc_x0 : h->X0).as<float>();   // a chunked batch: the rows by frame first
+    const bool lc = ls && ls->lc_live;
+    float* x0 = (lc ? ls->lc_x0 : h->X0).as<float>();   // a chunked batch: the rows by frame first
     if (s->centre && s->masked)
       launch_expand_context_masked(s->dfeats.as<float>(), s->dfeats.as<float>() + (size_t)B * T * s->ncep, h->seq_p,
                                    md + s->o_aug, s->aug_nm, s->aug_sw, x0, B, Bp, T, s->ctx, s->ncep,
@@ -487,16 +497,15 @@ int slot_commit(nasr_ctx* h, BatchSlot* s) {
                             x0, B, Bp, T, s->ctx, s->ncep, h->Fp, h->st);
     else
       launch_pack_feats(s->dfeats.as<float>(), x0, B, Bp, T, h->F, h->Fp, h->st);
-    if (h->lc_live) launch_lc_gather(x0, h->wlen_p, h->X0.as<float>(), h->lcg, h->Fp, h->st);   // ... and into the windows' rows
-    const bool lstm = h->family == Family::Lstm;
-    if (lstm)   // (the WaveNet's and LAS's GEMMs read the fp32 features as they are)
-      pl_scales(h, h->X0.as<float>(), h->Tv * Bp, h->Fp, h->Fp, &h->sc_x0r, &h->sc_x0c, h->st);
+    if (lc) launch_lc_gather(x0, h->wlen_p, h->X0.as<float>(), ls->lcg, h->Fp, h->st);   // ... and into the windows' rows
+    if (ls)   // (the WaveNet's and LAS's GEMMs read the fp32 features as they are)
+      pl_scales(h, h->X0.as<float>(), ls->Tv * Bp, h->Fp, h->Fp, &ls->sc_x0r, &ls->sc_x0c, h->st);
     if (h->cmp_rows)    // the feature rows' scales in the compacted order (layer 0's input GEMM)
-      launch_gather_rows(h->sc_cx.sp(), h->sc_x0r.sp(), h->vrow_p, h->cmp_rows_p, 1.f, h->st),
-      launch_gather_rows(h->sc_cx.ip(), h->sc_x0r.ip(), h->vrow_p, h->cmp_rows_p, 1.f, h->st);
-    if (s->has_labels && h->npre == 0 && lstm)   // layer-0 input with the frame index as contraction index, for dWx = X^T dG
-      launch_tph_split2(h->X0.as<float>(), nullptr, h->X0TTP.as<unsigned char>(), h->cmp_rows ? h->cmp_rows : h->Tv * Bp, h->Fp, h->Fp,
-                        nullptr, 1.f, h->sc_x0c.sp(), 1.f, nullptr, h->st, h->cmp_rows ? h->vrow_p : nullptr);
+      launch_gather_rows(ls->sc_cx.sp(), ls->sc_x0r.sp(), h->vrow_p, h->cmp_rows_p, 1.f, h->st),
+      launch_gather_rows(ls->sc_cx.ip(), ls->sc_x0r.ip(), h->vrow_p, h->cmp_rows_p, 1.f, h->st);
+    if (ls && s->has_labels && ls->npre == 0)   // layer-0 input with the frame index as contraction index, for dWx = X^T dG
+      launch_tph_split2(h->X0.as<float>(), nullptr, ls->X0TTP.as<unsigned char>(), h->cmp_rows ? h->cmp_rows : ls->Tv * Bp, h->Fp, h->Fp,
+                        nullptr, 1.f, ls->sc_x0c.sp(), 1.f, nullptr, h->st, h->cmp_rows ? h->vrow_p : nullptr);
     HIPCHK(h, hipGetLastError());
   }
   h->resident = true;

@@ -93,8 +93,6 @@ int las_layout(nasr_ctx* h) {
   h->C = C;
   h->Fp = rup(h->F, 32);
   h->Cp = rup(C, 32);
-  h->H = h->Hp = h->N4 = h->D = h->L = 0;
-  h->Pin = h->Pinp = 0;
   int64_t off = 0;
   for (int l = 0; l < LasEnc::NL; ++l) {
     s.Ip[l] = l == 0 ? h->Fp : 4 * LAS_HE;
@@ -599,11 +597,7 @@ int nasr_create_las(const nasr_las_cfg* cfg, int device_id, void* stream, nasr_h
   }
   nasr_ctx* h = nullptr;
   if (int rc = handle_open("nasr_create_las", Family::Las, device_id, stream, &h, nullptr)) return rc;
-  h->cfg.feature_size = cfg->feature_size;
-  h->cfg.num_classes = cfg->num_classes;
-  h->cfg.merge = NASR_MERGE_NONE;
-  h->cfg.learning_rate = cfg->learning_rate;
-  h->cfg.beta1 = cfg->beta1; h->cfg.beta2 = cfg->beta2; h->cfg.epsilon = cfg->epsilon;
+  h->beta1 = cfg->beta1; h->beta2 = cfg->beta2; h->epsilon = cfg->epsilon;
   h->lr = cfg->learning_rate;
   h->graph_mode = false;
   h->las.reset(new LasState());

@@ -1,7 +1,7 @@
 // nasr_layout.hip — parameter layout of a handle (TF variable order <-> the padded internal buffers), the operand images the
 // kernels keep of the weights (repack; the recurrent matrices' images are nasr_rec.hip's), host <-> device parameter
 // copies.  See include/nasr.h and DESIGN.md §3.
-#include "nasr_ctx.h"
+#include "nasr_lstm.h"
 
 using namespace nasr;
 using namespace nasr_impl;
@@ -13,9 +13,9 @@ thread_local std::string t_err;
 thread_local const void* t_err_handle = nullptr;
 
 // scales of src [rows][K]: per row into `row`, per column into `col` (either may be NULL)
-void pl_scales(nasr_ctx* h, const float* src, int rows, int K, int ld, nasr_ctx::SV* row, nasr_ctx::SV* col, hipStream_t st) {
+void pl_scales(nasr_ctx* h, const float* src, int rows, int K, int ld, SV* row, SV* col, hipStream_t st) {
   launch_tph_scales(src, rows, K, ld, row ? row->sp() : nullptr, row ? row->ip() : nullptr, col ? col->sp() : nullptr,
-                    col ? col->ip() : nullptr, h->scws.as<float>(), st);
+                    col ? col->ip() : nullptr, h->lstm->scws.as<float>(), st);
 }
 // planes of src [rows][K] (tpN, scaled per row by rs[]) and / or of its transpose (tpT, scaled per src column by cs[]);
 // colpart: 64-row partial column sums for launch_colsum_parts
@@ -82,93 +82,89 @@ int sync_checked(nasr_ctx* h) {
   return rec_check(h);
 }
 
-void drop_graphs(nasr_ctx* h) {
-  for (auto& kv : h->graphs) (void)hipGraphExecDestroy(kv.second);
-  h->graphs.clear();
-}
-
 hipEvent_t next_event(nasr_ctx* h) {
   if (h->ev_used == h->ev_pool.size()) (void)hipEventCreate(h->ev_pool.emplace_back().out());
   return h->ev_pool[h->ev_used++];
 }
 // ---- model layout ---------------------------------------------------------------------------
 int build_layout(nasr_ctx* h) {
-  const nasr_model_cfg& c = h->cfg;
+  LstmState* const ls = h->lstm.get();
+  const nasr_model_cfg& c = ls->cfg;
   h->F = c.feature_size;
-  h->H = c.hidden;
-  h->L = c.num_layers;
-  h->D = c.bidirectional ? 2 : 1;
+  ls->H = c.hidden;
+  ls->L = c.num_layers;
+  ls->D = c.bidirectional ? 2 : 1;
   h->C = c.num_classes;
   h->Fp = rup(h->F, 32);
-  h->Hp = rup(h->H, 64);
-  h->N4 = 4 * h->Hp;
+  ls->Hp = rup(ls->H, 64);
+  ls->N4 = 4 * ls->Hp;
   h->Cp = rup(h->C, 32);
   const bool concat = c.bidirectional && c.merge == NASR_MERGE_CONCAT;
-  const int D = h->D, Hp = h->Hp, N4 = h->N4, H = h->H;
+  const int D = ls->D, Hp = ls->Hp, N4 = ls->N4, H = ls->H;
   const int lstm_out = concat ? 2 * H : H, lstm_outp = concat ? 2 * Hp : Hp;
 
   // dense stages
-  h->npre = c.num_pre;
-  h->has_post = c.post_width > 0;
-  h->ndense = h->npre + (h->has_post ? 1 : 0);
-  h->dWid.assign(h->ndense, 0); h->dWp.assign(h->ndense, 0); h->dIn.assign(h->ndense, 0); h->dIp.assign(h->ndense, 0);
-  for (int i = 0; i < h->npre; ++i) {
-    h->dWid[i] = c.pre_width[i]; h->dWp[i] = rup(c.pre_width[i], 64);
-    h->dIn[i] = i == 0 ? h->F : h->dWid[i - 1];
-    h->dIp[i] = i == 0 ? h->Fp : h->dWp[i - 1];
+  ls->npre = c.num_pre;
+  ls->has_post = c.post_width > 0;
+  ls->ndense = ls->npre + (ls->has_post ? 1 : 0);
+  ls->dWid.assign(ls->ndense, 0); ls->dWp.assign(ls->ndense, 0); ls->dIn.assign(ls->ndense, 0); ls->dIp.assign(ls->ndense, 0);
+  for (int i = 0; i < ls->npre; ++i) {
+    ls->dWid[i] = c.pre_width[i]; ls->dWp[i] = rup(c.pre_width[i], 64);
+    ls->dIn[i] = i == 0 ? h->F : ls->dWid[i - 1];
+    ls->dIp[i] = i == 0 ? h->Fp : ls->dWp[i - 1];
   }
-  if (h->has_post) {
-    const int i = h->npre;
-    h->dWid[i] = c.post_width; h->dWp[i] = rup(c.post_width, 64);
-    h->dIn[i] = lstm_out; h->dIp[i] = lstm_outp;
+  if (ls->has_post) {
+    const int i = ls->npre;
+    ls->dWid[i] = c.post_width; ls->dWp[i] = rup(c.post_width, 64);
+    ls->dIn[i] = lstm_out; ls->dIp[i] = lstm_outp;
   }
-  h->F0 = h->npre ? h->dWid[h->npre - 1] : h->F;
-  h->Pin = h->has_post ? c.post_width : lstm_out;
-  h->Pinp = h->has_post ? h->dWp[h->npre] : lstm_outp;
+  ls->F0 = ls->npre ? ls->dWid[ls->npre - 1] : h->F;
+  ls->Pin = ls->has_post ? c.post_width : lstm_out;
+  ls->Pinp = ls->has_post ? ls->dWp[ls->npre] : lstm_outp;
 
   int64_t off = 0;
-  h->off_dw.assign(h->ndense, 0); h->off_db.assign(h->ndense, 0);
-  for (int i = 0; i < h->ndense; ++i) {
-    h->off_dw[i] = off; off += (int64_t)h->dIp[i] * h->dWp[i];
-    h->off_db[i] = off; off += h->dWp[i];
+  ls->off_dw.assign(ls->ndense, 0); ls->off_db.assign(ls->ndense, 0);
+  for (int i = 0; i < ls->ndense; ++i) {
+    ls->off_dw[i] = off; off += (int64_t)ls->dIp[i] * ls->dWp[i];
+    ls->off_db[i] = off; off += ls->dWp[i];
   }
-  h->Ip.resize(h->L);
-  h->off_wx.resize(h->L);
-  h->off_bias.resize(h->L);
-  h->off_u.resize((size_t)h->L * D);
-  for (int l = 0; l < h->L; ++l) {
-    h->Ip[l] = l == 0 ? (h->npre ? h->dWp[h->npre - 1] : h->Fp) : D * Hp;
-    h->off_wx[l] = off;
-    off += (int64_t)h->Ip[l] * D * N4;
-    h->off_bias[l] = off;
+  ls->Ip.resize(ls->L);
+  ls->off_wx.resize(ls->L);
+  ls->off_bias.resize(ls->L);
+  ls->off_u.resize((size_t)ls->L * D);
+  for (int l = 0; l < ls->L; ++l) {
+    ls->Ip[l] = l == 0 ? (ls->npre ? ls->dWp[ls->npre - 1] : h->Fp) : D * Hp;
+    ls->off_wx[l] = off;
+    off += (int64_t)ls->Ip[l] * D * N4;
+    ls->off_bias[l] = off;
     off += (int64_t)D * N4;
     for (int d = 0; d < D; ++d) {
-      h->off_u[(size_t)l * D + d] = off;
+      ls->off_u[(size_t)l * D + d] = off;
       off += (int64_t)Hp * N4;
     }
   }
-  h->off_w = off;
-  off += (int64_t)h->Pinp * h->Cp;
-  h->off_b = off;
+  ls->off_w = off;
+  off += (int64_t)ls->Pinp * h->Cp;
+  ls->off_b = off;
   off += h->Cp;
   h->np_int = off;  // every term is a multiple of 32
   if (off >= (int64_t)1 << 31) return h->fail(NASR_ERR_ARG, "model too large for 32-bit parameter indexing");
 
   // TF variable order + element map.  Plain (Bi)LstmCTCNet: cells, W, b.  DeepSpeech family (creation order of
   // networks/deepspeech.py): b1,h1,b2,h2,b3,h3, cells, b5,h5, b6,h6.
-  const bool ds = h->ndense > 0;
+  const bool ds = ls->ndense > 0;
   h->tensors.clear();
   int64_t tfo = 0;
   auto add = [&](const std::string& n, int64_t r, int64_t cc) {
     h->tensors.push_back({n, tfo, r, cc});
     tfo += r * cc;
   };
-  for (int i = 0; i < h->npre; ++i) {
-    add("b" + std::to_string(i + 1), h->dWid[i], 1);
-    add("h" + std::to_string(i + 1), h->dIn[i], h->dWid[i]);
+  for (int i = 0; i < ls->npre; ++i) {
+    add("b" + std::to_string(i + 1), ls->dWid[i], 1);
+    add("h" + std::to_string(i + 1), ls->dIn[i], ls->dWid[i]);
   }
-  for (int l = 0; l < h->L; ++l) {
-    const int I = l == 0 ? h->F0 : D * H;
+  for (int l = 0; l < ls->L; ++l) {
+    const int I = l == 0 ? ls->F0 : D * H;
     for (int d = 0; d < D; ++d) {
       std::string pre = "l" + std::to_string(l) + "/";
       if (D == 2) pre += d == 0 ? "fw/" : "bw/";
@@ -177,14 +173,14 @@ int build_layout(nasr_ctx* h) {
     }
   }
   if (ds) {
-    if (h->has_post) {
-      add("b5", h->dWid[h->npre], 1);
-      add("h5", h->dIn[h->npre], h->dWid[h->npre]);
+    if (ls->has_post) {
+      add("b5", ls->dWid[ls->npre], 1);
+      add("h5", ls->dIn[ls->npre], ls->dWid[ls->npre]);
     }
     add("b6", h->C, 1);
-    add("h6", h->Pin, h->C);
+    add("h6", ls->Pin, h->C);
   } else {
-    add("W", h->Pin, h->C);
+    add("W", ls->Pin, h->C);
     add("b", h->C, 1);
   }
   h->np_tf = tfo;
@@ -194,17 +190,17 @@ int build_layout(nasr_ctx* h) {
   auto cat_row = [&](int r) { return (D == 2 && concat && r >= H) ? Hp + (r - H) : r; };
   auto map_dense = [&](int i, bool from_lstm) {
     const TensorInfo& tb = h->tensors[ti++];
-    for (int cc = 0; cc < h->dWid[i]; ++cc) h->tf2int[(size_t)(tb.offset + cc)] = (int32_t)(h->off_db[i] + cc);
+    for (int cc = 0; cc < ls->dWid[i]; ++cc) h->tf2int[(size_t)(tb.offset + cc)] = (int32_t)(ls->off_db[i] + cc);
     const TensorInfo& tw = h->tensors[ti++];
-    for (int r = 0; r < h->dIn[i]; ++r) {
+    for (int r = 0; r < ls->dIn[i]; ++r) {
       const int ir = from_lstm ? cat_row(r) : r;
-      for (int cc = 0; cc < h->dWid[i]; ++cc)
-        h->tf2int[(size_t)(tw.offset + (int64_t)r * h->dWid[i] + cc)] = (int32_t)(h->off_dw[i] + (int64_t)ir * h->dWp[i] + cc);
+      for (int cc = 0; cc < ls->dWid[i]; ++cc)
+        h->tf2int[(size_t)(tw.offset + (int64_t)r * ls->dWid[i] + cc)] = (int32_t)(ls->off_dw[i] + (int64_t)ir * ls->dWp[i] + cc);
     }
   };
-  for (int i = 0; i < h->npre; ++i) map_dense(i, false);
-  for (int l = 0; l < h->L; ++l) {
-    const int I = l == 0 ? h->F0 : D * H;
+  for (int i = 0; i < ls->npre; ++i) map_dense(i, false);
+  for (int l = 0; l < ls->L; ++l) {
+    const int I = l == 0 ? ls->F0 : D * H;
     for (int d = 0; d < D; ++d) {
       const TensorInfo& tk = h->tensors[ti++];
       for (int r = 0; r < I + H; ++r) {
@@ -214,9 +210,9 @@ int build_layout(nasr_ctx* h) {
           if (r < I) {
             int ir = r;
             if (l > 0 && D == 2 && r >= H) ir = Hp + (r - H);
-            dst = h->off_wx[l] + (int64_t)ir * D * N4 + d * N4 + 4 * j + g;
+            dst = ls->off_wx[l] + (int64_t)ir * D * N4 + d * N4 + 4 * j + g;
           } else {
-            dst = h->off_u[(size_t)l * D + d] + (int64_t)(r - I) * N4 + 4 * j + g;
+            dst = ls->off_u[(size_t)l * D + d] + (int64_t)(r - I) * N4 + 4 * j + g;
           }
           h->tf2int[(size_t)(tk.offset + (int64_t)r * 4 * H + cc)] = (int32_t)dst;
         }
@@ -224,63 +220,64 @@ int build_layout(nasr_ctx* h) {
       const TensorInfo& tb = h->tensors[ti++];
       for (int cc = 0; cc < 4 * H; ++cc) {
         const int g = cc / H, j = cc % H;
-        h->tf2int[(size_t)(tb.offset + cc)] = (int32_t)(h->off_bias[l] + d * N4 + 4 * j + g);
+        h->tf2int[(size_t)(tb.offset + cc)] = (int32_t)(ls->off_bias[l] + d * N4 + 4 * j + g);
       }
     }
   }
-  if (h->has_post) map_dense(h->npre, true);
+  if (ls->has_post) map_dense(ls->npre, true);
   auto map_w = [&]() {
     const TensorInfo& tw = h->tensors[ti++];
-    for (int r = 0; r < h->Pin; ++r) {
-      const int ir = h->has_post ? r : cat_row(r);
+    for (int r = 0; r < ls->Pin; ++r) {
+      const int ir = ls->has_post ? r : cat_row(r);
       for (int cc = 0; cc < h->C; ++cc)
-        h->tf2int[(size_t)(tw.offset + (int64_t)r * h->C + cc)] = (int32_t)(h->off_w + (int64_t)ir * h->Cp + cc);
+        h->tf2int[(size_t)(tw.offset + (int64_t)r * h->C + cc)] = (int32_t)(ls->off_w + (int64_t)ir * h->Cp + cc);
     }
   };
   auto map_b = [&]() {
     const TensorInfo& tb = h->tensors[ti++];
-    for (int cc = 0; cc < h->C; ++cc) h->tf2int[(size_t)(tb.offset + cc)] = (int32_t)(h->off_b + cc);
+    for (int cc = 0; cc < h->C; ++cc) h->tf2int[(size_t)(tb.offset + cc)] = (int32_t)(ls->off_b + cc);
   };
   if (ds) { map_b(); map_w(); } else { map_w(); map_b(); }
   return NASR_OK;
 }
 
 int repack(nasr_ctx* h) {
-  if (h->family != Family::Lstm) return NASR_OK;   // the WaveNet's and LAS's GEMMs read the fp32 parameters directly: no operand images
-  h->repack_seq += 1;
+  LstmState* const ls = h->lstm.get();
+  if (!ls) return NASR_OK;   // the WaveNet's and LAS's GEMMs read the fp32 parameters directly: no operand images
+  ls->repack_seq += 1;
   // only the operand images of the kernels in use (a switch of the recurrence's kind calls repack again)
   // scales of every matrix that needs them - recurrent matrices of the persistent / wide kernels, input and dense
   // weights of the plane GEMMs - in ONE batch (two launches), then the images
   std::vector<TphScaleJob> jobs = rec_scale_jobs(h);
-  for (int l = 0; l < h->L; ++l) {
-    const bool back = l > 0 || h->npre > 0;
-    jobs.push_back({h->P + h->off_wx[l], h->Ip[l], h->D * h->N4, h->D * h->N4, back ? h->sc_wr[l].sp() : nullptr,
-                    back ? h->sc_wr[l].ip() : nullptr, h->sc_wc[l].sp(), h->sc_wc[l].ip()});
+  for (int l = 0; l < ls->L; ++l) {
+    const bool back = l > 0 || ls->npre > 0;
+    jobs.push_back({h->P + ls->off_wx[l], ls->Ip[l], ls->D * ls->N4, ls->D * ls->N4, back ? ls->sc_wr[l].sp() : nullptr,
+                    back ? ls->sc_wr[l].ip() : nullptr, ls->sc_wc[l].sp(), ls->sc_wc[l].ip()});
   }
-  for (int i = 0; i < h->ndense; ++i) {
-    const bool back = i > 0 || h->npre == 0;
-    jobs.push_back({h->P + h->off_dw[i], h->dIp[i], h->dWp[i], h->dWp[i], back ? h->sc_dr[i].sp() : nullptr,
-                    back ? h->sc_dr[i].ip() : nullptr, h->sc_dc[i].sp(), h->sc_dc[i].ip()});
+  for (int i = 0; i < ls->ndense; ++i) {
+    const bool back = i > 0 || ls->npre == 0;
+    jobs.push_back({h->P + ls->off_dw[i], ls->dIp[i], ls->dWp[i], ls->dWp[i], back ? ls->sc_dr[i].sp() : nullptr,
+                    back ? ls->sc_dr[i].ip() : nullptr, ls->sc_dc[i].sp(), ls->sc_dc[i].ip()});
   }
   {
     bool g2 = false;
-    if (!h->scws.ensure(tph_scale_batch_ws_floats(jobs.data(), (int)jobs.size()) * 4, &g2))
+    if (!ls->scws.ensure(tph_scale_batch_ws_floats(jobs.data(), (int)jobs.size()) * 4, &g2))
       return h->fail(NASR_ERR_HIP, "allocation of the scale workspace failed");
   }
-  launch_tph_scales_batch(jobs.data(), (int)jobs.size(), h->scws.as<float>(), h->st);
+  launch_tph_scales_batch(jobs.data(), (int)jobs.size(), ls->scws.as<float>(), h->st);
   rec_images(h);
-  for (int l = 0; l < h->L; ++l) {
+  for (int l = 0; l < ls->L; ++l) {
     // forward operand = planes of Wx^T, input-gradient operand = planes of Wx: one pass where both are needed
-    const bool back = l > 0 || h->npre > 0;
-    const float* W = h->P + h->off_wx[l];
-    pl_split(W, back ? h->WbTP + h->off_wbtp[l] : nullptr, h->WfTP + h->off_wftp[l], h->Ip[l], h->D * h->N4,
-             h->D * h->N4, back ? h->sc_wr[l].sp() : nullptr, h->sc_wc[l].sp(), nullptr, h->st);
+    const bool back = l > 0 || ls->npre > 0;
+    const float* W = h->P + ls->off_wx[l];
+    pl_split(W, back ? ls->WbTP + ls->off_wbtp[l] : nullptr, ls->WfTP + ls->off_wftp[l], ls->Ip[l], ls->D * ls->N4,
+             ls->D * ls->N4, back ? ls->sc_wr[l].sp() : nullptr, ls->sc_wc[l].sp(), nullptr, h->st);
   }
-  for (int i = 0; i < h->ndense; ++i) {
-    const bool back = i > 0 || h->npre == 0;   // the first pre stage reads the features: no gradient wrt its input
-    const float* W = h->P + h->off_dw[i];
-    pl_split(W, back ? h->DbTP + h->off_dbtp[i] : nullptr, h->DfTP + h->off_dftp[i], h->dIp[i], h->dWp[i], h->dWp[i],
-             back ? h->sc_dr[i].sp() : nullptr, h->sc_dc[i].sp(), nullptr, h->st);
+  for (int i = 0; i < ls->ndense; ++i) {
+    const bool back = i > 0 || ls->npre == 0;   // the first pre stage reads the features: no gradient wrt its input
+    const float* W = h->P + ls->off_dw[i];
+    pl_split(W, back ? ls->DbTP + ls->off_dbtp[i] : nullptr, ls->DfTP + ls->off_dftp[i], ls->dIp[i], ls->dWp[i], ls->dWp[i],
+             back ? ls->sc_dr[i].sp() : nullptr, ls->sc_dc[i].sp(), nullptr, h->st);
   }
   HIPCHK(h, hipGetLastError());
   return NASR_OK;

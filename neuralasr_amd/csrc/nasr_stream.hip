@@ -3,7 +3,7 @@
 // the device between feeds, so that the network recognises audio as it arrives.
 // One rule serves every session.  A session has a look-ahead of R frames and holds, per slot, its last rows on the device.
 // With P = held + n pending rows a feed emits E = last ? P : max(0, P - R) rows: it runs an ordinary forward pass
-// (nasr_pass.hip: forward(h, true)) over the pending rows of the slots that emit, the forward direction from the saved
+// (nasr_pass.hip: lstm_forward(h, true)) over the pending rows of the slots that emit, the forward direction from the saved
 // state (lstm.hip: load_carry_kernel, the state-carrying step), the backward direction of a bidirectional concat
 // network from zero at the slot's last pending row; it saves the forward state after row E - 1
 // (stream_save_state_kernel) and holds the last P - E rows (rows.hip: la_window_kernel).  A session of nasr_stream_open is the case
@@ -13,6 +13,7 @@
 // samples (nasr_stream_attach_audio, nasr_stream_feed_audio), from a causal featurizer's front end (nasr_fz.hip:
 // fz_stream_*), which keeps per slot what it needs to turn the samples of a feed into stacked rows on the device.
 #include "nasr_fz.h"
+#include "nasr_lstm.h"
 
 using namespace nasr;
 using namespace nasr_impl;
@@ -20,30 +21,30 @@ using namespace nasr_impl;
 namespace {
 
 int need_session(nasr_ctx* h, const char* fn) {
-  if (!h->stream) return h->fail(NASR_ERR_STATE, std::string(fn) + ": no open stream session (nasr_stream_open)");
+  if (!h->lstm || !h->lstm->stream) return h->fail(NASR_ERR_STATE, std::string(fn) + ": no open stream session (nasr_stream_open)");
   return NASR_OK;
 }
 
 int need_lookahead(nasr_ctx* h, const char* fn) {
   if (int rc = need_session(h, fn)) return rc;
-  if (h->stream->R == 0)
+  if (h->lstm->stream->R == 0)
     return h->fail(NASR_ERR_STATE, std::string(fn) + ": the session has no look-ahead (nasr_stream_open_lookahead); feed it with nasr_stream_feed");
   return NASR_OK;
 }
 
-int64_t state_floats(const nasr_ctx* h) { return (int64_t)h->L * h->stream->S * 2 * h->H; }
+int64_t state_floats(const nasr_ctx* h) { return (int64_t)h->lstm->L * h->lstm->stream->S * 2 * h->lstm->H; }
 
 // A session of S slots and R look-ahead frames on a handle that the ABI call `fn` has found fit for it (R = 0: the
 // unidirectional network's, whose call has no R to refuse).
 int open_session(nasr_ctx* h, const std::string& fn, int S, int R) {
   for (int i = 0; i < 4; ++i)
-    if (h->cfg.dropout[i] != 0.f)
-      return h->fail(NASR_ERR_STATE, fn + ": dropout[" + std::to_string(i) + "] = " + std::to_string(h->cfg.dropout[i]) +
+    if (h->lstm->cfg.dropout[i] != 0.f)
+      return h->fail(NASR_ERR_STATE, fn + ": dropout[" + std::to_string(i) + "] = " + std::to_string(h->lstm->cfg.dropout[i]) +
                                          ": a network with dropout cannot stream (the reference applies dropout in every graph, "
                                          "keyed by the pass counter)");
-  if (h->stream) return h->fail(NASR_ERR_STATE, fn + ": a stream session is open already");
+  if (h->lstm->stream) return h->fail(NASR_ERR_STATE, fn + ": a stream session is open already");
   if (S < 1 || S > LA_MAX_SLOTS) return h->fail(NASR_ERR_ARG, fn + ": S = " + std::to_string(S) + " streams: must be in [1,64]");
-  if (h->cfg.bidirectional && (R < 1 || R > 1024))
+  if (h->lstm->cfg.bidirectional && (R < 1 || R > 1024))
     return h->fail(NASR_ERR_ARG, fn + ": R = " + std::to_string(R) + " look-ahead frames: must be in [1,1024]");
   HIPCHK(h, hipSetDevice(h->device));
   auto ss = std::make_unique<StreamState>();
@@ -53,12 +54,12 @@ int open_session(nasr_ctx* h, const std::string& fn, int S, int R) {
   ss->held.assign((size_t)S, 0);
   ss->done.assign((size_t)S, 0);
   bool grew = false;
-  const size_t nb = (size_t)h->L * S * 2 * h->H * 4, hb = (size_t)S * R * h->F * 4;
-  if (!ss->state.ensure(nb, &grew) || !ss->cimg.ensure((size_t)h->D * rup(S, 16) * h->Hp * 4, &grew) ||
+  const size_t nb = (size_t)h->lstm->L * S * 2 * h->lstm->H * 4, hb = (size_t)S * R * h->F * 4;
+  if (!ss->state.ensure(nb, &grew) || !ss->cimg.ensure((size_t)h->lstm->D * rup(S, 16) * h->lstm->Hp * 4, &grew) ||
       (R > 0 && (!ss->hold[0].ensure(hb, &grew) || !ss->hold[1].ensure(hb, &grew))))
     return h->fail(NASR_ERR_HIP, fn + ": hipMalloc of the stream state failed");
   HIPCHK(h, hipMemsetAsync(ss->state.p, 0, nb, h->st));
-  h->stream = std::move(ss);
+  h->lstm->stream = std::move(ss);
   return NASR_OK;
 }
 
@@ -73,7 +74,7 @@ struct FeedPlan {
 
 // n [S] new rows per slot (checked by the caller), last nullable.  NASR_ERR_STATE for a slot that has had `last`.
 int plan_feed(nasr_ctx* h, const char* fn, const int32_t* n, const uint8_t* last, FeedPlan* f) {
-  const StreamState& ss = *h->stream;
+  const StreamState& ss = *h->lstm->stream;
   for (int b = 0; b < ss.S; ++b) {
     const bool fin = last && last[b];
     if (ss.done[(size_t)b] && (n[b] > 0 || fin))
@@ -102,7 +103,7 @@ struct RowSource {
 // (the upload's own copy, or run() as the slot's producer).  With R > 0 they go into ss.fresh, and la_window_kernel puts
 // held and new rows together into the chunk and the rows that stay held into the other hold buffer.
 int run_feed(nasr_ctx* h, const char* fn, const FeedPlan& f, const RowSource& src, const uint8_t* last, float* logits_out) {
-  StreamState& ss = *h->stream;
+  StreamState& ss = *h->lstm->stream;
   HIPCHK(h, hipSetDevice(h->device));
   const size_t bytes = (size_t)ss.S * src.Tc * h->F * 4;
   float* fresh = nullptr;
@@ -142,7 +143,7 @@ int run_feed(nasr_ctx* h, const char* fn, const FeedPlan& f, const RowSource& sr
     rc = upload(h, b);
     if (!rc) {
       ensure_step_images(h);   // a chunk runs on the per-step kernels, whatever the handle's kind
-      rc = forward(h, true);
+      rc = lstm_forward(h, true);
       if (!rc) rc = fetch_logits(h, logits_out, f.Te);
       // the chunk is no batch the *_resident calls could run (a slot may have no frame at all): the handle has none until
       // the next upload
@@ -165,7 +166,7 @@ int run_feed(nasr_ctx* h, const char* fn, const FeedPlan& f, const RowSource& sr
 // the frame counts of a look-ahead feed: n_frames[b] in [0, Tc]
 int la_check_rows(nasr_ctx* h, const char* fn, const int32_t* n, int Tc) {
   if (Tc < 0) return h->fail(NASR_ERR_ARG, std::string(fn) + ": Tc < 0");
-  for (int b = 0; b < h->stream->S; ++b)
+  for (int b = 0; b < h->lstm->stream->S; ++b)
     if (n[b] < 0 || n[b] > Tc)
       return h->fail(NASR_ERR_ARG, std::string(fn) + ": n_frames[" + std::to_string(b) + "] = " + std::to_string(n[b]) +
                                        " out of [0,Tc = " + std::to_string(Tc) + "]");
@@ -175,7 +176,7 @@ int la_check_rows(nasr_ctx* h, const char* fn, const int32_t* n, int Tc) {
 // the session takes samples: the front end's plan for the per-slot counts of new samples, its rows per slot
 int audio_plan(nasr_ctx* h, const char* fn, const int64_t* nnew, const uint8_t* last, int32_t* rows_out, int* Tc_out, FzFeedPlan* p) {
   if (int rc = need_session(h, fn)) return rc;
-  StreamState& ss = *h->stream;
+  StreamState& ss = *h->lstm->stream;
   if (!ss.audio) return h->fail(NASR_ERR_STATE, std::string(fn) + ": the session takes frames (nasr_stream_attach_audio first)");
   if (int rc = fz_stream_plan(h, *ss.audio, fn, nnew, last, p)) return rc;
   for (int b = 0; b < ss.S; ++b) rows_out[b] = (int32_t)p->slot[(size_t)b].nrows;
@@ -185,7 +186,7 @@ int audio_plan(nasr_ctx* h, const char* fn, const int64_t* nnew, const uint8_t* 
 
 // what a planned feed reports: the rows every slot emits and the most of them
 void report(const nasr_ctx* h, const FeedPlan& f, int32_t* rows_out, int* Te_out) {
-  std::copy(f.sl.emit, f.sl.emit + h->stream->S, rows_out);
+  std::copy(f.sl.emit, f.sl.emit + h->lstm->stream->S, rows_out);
   *Te_out = f.Te;
 }
 
@@ -203,7 +204,7 @@ int nasr_stream_open(nasr_handle h, int S) {
   MODEL_CALL(h);
   if (!h) return NASR_ERR_ARG;
   LSTM_CALL(h, "cannot stream: only the unidirectional LSTM CTC networks carry state between chunks");
-  if (h->cfg.bidirectional || h->cfg.merge != NASR_MERGE_NONE)
+  if (h->lstm->cfg.bidirectional || h->lstm->cfg.merge != NASR_MERGE_NONE)
     return h->fail(NASR_ERR_STATE, "nasr_stream_open: a bidirectional network cannot stream: its backward direction reads the "
                                    "utterance from its end");
   return open_session(h, __func__, S, 0);
@@ -213,9 +214,9 @@ int nasr_stream_open_lookahead(nasr_handle h, int S, int R) {
   MODEL_CALL(h);
   if (!h) return NASR_ERR_ARG;
   LSTM_CALL(h, "cannot stream: only the LSTM CTC networks carry state between chunks");
-  if (!h->cfg.bidirectional)
+  if (!h->lstm->cfg.bidirectional)
     return h->fail(NASR_ERR_STATE, "nasr_stream_open_lookahead: a unidirectional network needs no look-ahead: use nasr_stream_open");
-  if (h->cfg.merge != NASR_MERGE_CONCAT)
+  if (h->lstm->cfg.merge != NASR_MERGE_CONCAT)
     return h->fail(NASR_ERR_STATE, "nasr_stream_open_lookahead: NASR_MERGE_STACK_RESHAPE cannot stream: its logits mix frames of the "
                                    "whole padded batch, so no chunk of it is a point in time");
   return open_session(h, __func__, S, R);
@@ -227,7 +228,7 @@ int nasr_stream_close(nasr_handle h) {
   if (int rc = need_session(h, __func__)) return rc;
   HIPCHK(h, hipSetDevice(h->device));
   HIPCHK(h, hipStreamSynchronize(h->st));   // the last feed's kernels read the buffers that go now
-  h->stream.reset();
+  h->lstm->stream.reset();
   return NASR_OK;
 }
 
@@ -235,7 +236,7 @@ int nasr_stream_reset(nasr_handle h, const int32_t* slots, int n) {
   MODEL_CALL(h);
   if (!h) return NASR_ERR_ARG;
   if (int rc = need_session(h, __func__)) return rc;
-  StreamState& ss = *h->stream;
+  StreamState& ss = *h->lstm->stream;
   HIPCHK(h, hipSetDevice(h->device));
   if (!slots) {
     HIPCHK(h, hipMemsetAsync(ss.state.p, 0, (size_t)state_floats(h) * 4, h->st));
@@ -249,9 +250,9 @@ int nasr_stream_reset(nasr_handle h, const int32_t* slots, int n) {
   for (int i = 0; i < n; ++i)
     if (slots[i] < 0 || slots[i] >= ss.S)
       return h->fail(NASR_ERR_ARG, "nasr_stream_reset: slot " + std::to_string(slots[i]) + " out of [0," + std::to_string(ss.S - 1) + "]");
-  const size_t row = (size_t)2 * h->H * 4;   // one slot's (c, h) of one layer
+  const size_t row = (size_t)2 * h->lstm->H * 4;   // one slot's (c, h) of one layer
   for (int i = 0; i < n; ++i) {
-    HIPCHK(h, hipMemset2DAsync(static_cast<char*>(ss.state.p) + (size_t)slots[i] * row, (size_t)ss.S * row, 0, row, (size_t)h->L, h->st));
+    HIPCHK(h, hipMemset2DAsync(static_cast<char*>(ss.state.p) + (size_t)slots[i] * row, (size_t)ss.S * row, 0, row, (size_t)h->lstm->L, h->st));
     ss.frames[(size_t)slots[i]] = 0;
     ss.held[(size_t)slots[i]] = ss.done[(size_t)slots[i]] = 0;   // its held rows are simply forgotten
     if (ss.audio) fz_stream_reset(*ss.audio, slots[i]);
@@ -263,10 +264,10 @@ int nasr_stream_feed(nasr_handle h, const float* feats, const int32_t* n_frames,
   MODEL_CALL(h);
   if (!h) return NASR_ERR_ARG;
   if (int rc = need_session(h, __func__)) return rc;
-  if (h->stream->R > 0)
+  if (h->lstm->stream->R > 0)
     return h->fail(NASR_ERR_STATE, "nasr_stream_feed: the session has a look-ahead: feed it with nasr_stream_feed_lookahead");
   if (!feats || !n_frames || !logits_out) return h->fail(NASR_ERR_ARG, "nasr_stream_feed: null buffer");
-  if (int rc = validate_chunk(h, n_frames, h->stream->S, Tc)) return rc;
+  if (int rc = validate_chunk(h, n_frames, h->lstm->stream->S, Tc)) return rc;
   FeedPlan f;
   if (int rc = plan_feed(h, __func__, n_frames, nullptr, &f)) return rc;
   // The chunk is the caller's, Tc rows and not the longest slot's: its row count decides how the bulk GEMMs split their
@@ -283,7 +284,7 @@ int nasr_stream_lookahead_rows(nasr_handle h, const int32_t* n_frames, const uin
   if (!h) return NASR_ERR_ARG;
   if (int rc = need_lookahead(h, __func__)) return rc;
   if (!n_frames || !rows_out || !Te_out) return h->fail(NASR_ERR_ARG, "nasr_stream_lookahead_rows: null buffer");
-  for (int b = 0; b < h->stream->S; ++b)
+  for (int b = 0; b < h->lstm->stream->S; ++b)
     if (n_frames[b] < 0)
       return h->fail(NASR_ERR_ARG, "nasr_stream_lookahead_rows: n_frames[" + std::to_string(b) + "] = " + std::to_string(n_frames[b]) + " < 0");
   FeedPlan f;
@@ -297,7 +298,7 @@ int nasr_stream_feed_lookahead(nasr_handle h, const float* feats, const int32_t*
   MODEL_CALL(h);
   if (!h) return NASR_ERR_ARG;
   if (int rc = need_lookahead(h, __func__)) return rc;
-  if (h->stream->audio) return h->fail(NASR_ERR_STATE, "nasr_stream_feed_lookahead: the session takes samples (nasr_stream_feed_audio)");
+  if (h->lstm->stream->audio) return h->fail(NASR_ERR_STATE, "nasr_stream_feed_lookahead: the session takes samples (nasr_stream_feed_audio)");
   if (!n_frames || !rows_out || !Te_out) return h->fail(NASR_ERR_ARG, "nasr_stream_feed_lookahead: null buffer");
   if (int rc = la_check_rows(h, __func__, n_frames, Tc)) return rc;
   FeedPlan f;
@@ -315,7 +316,7 @@ int nasr_stream_attach_audio(nasr_handle h, nasr_handle featurizer) {
   MODEL_CALL(h);
   if (!h) return NASR_ERR_ARG;
   if (int rc = need_session(h, __func__)) return rc;
-  StreamState& ss = *h->stream;
+  StreamState& ss = *h->lstm->stream;
   if (ss.audio) return h->fail(NASR_ERR_STATE, "nasr_stream_attach_audio: the session takes samples already");
   HIPCHK(h, hipSetDevice(h->device));
   return fz_stream_attach(h, featurizer, ss.S, &ss.audio);
@@ -339,7 +340,7 @@ int nasr_stream_feed_audio(nasr_handle h, const float* audio, const int64_t* off
   if (!h) return NASR_ERR_ARG;
   if (int rc = need_session(h, __func__)) return rc;
   if (!offsets || !rows_out || !Tc_out) return h->fail(NASR_ERR_ARG, "nasr_stream_feed_audio: null buffer");
-  StreamState& ss = *h->stream;
+  StreamState& ss = *h->lstm->stream;
   std::vector<int64_t> nnew((size_t)ss.S);
   for (int b = 0; b < ss.S; ++b) nnew[(size_t)b] = offsets[b + 1] - offsets[b];
   FzFeedPlan p;
@@ -368,7 +369,7 @@ int nasr_stream_frames(nasr_handle h, int64_t* frames_out) {
   if (!h) return NASR_ERR_ARG;
   if (int rc = need_session(h, __func__)) return rc;
   if (!frames_out) return h->fail(NASR_ERR_ARG, "nasr_stream_frames: null buffer");
-  std::copy(h->stream->frames.begin(), h->stream->frames.end(), frames_out);
+  std::copy(h->lstm->stream->frames.begin(), h->lstm->stream->frames.end(), frames_out);
   return NASR_OK;
 }
 
@@ -379,7 +380,7 @@ int nasr_stream_get_state(nasr_handle h, float* state, int64_t n) {
   if (!state || n != state_floats(h))
     return h->fail(NASR_ERR_ARG, "nasr_stream_get_state: expected " + std::to_string(state_floats(h)) + " floats ([L][S][2][H])");
   HIPCHK(h, hipSetDevice(h->device));
-  HIPCHK(h, hipMemcpyAsync(state, h->stream->state.p, (size_t)n * 4, hipMemcpyDeviceToHost, h->st));
+  HIPCHK(h, hipMemcpyAsync(state, h->lstm->stream->state.p, (size_t)n * 4, hipMemcpyDeviceToHost, h->st));
   return sync_checked(h);
 }
 
@@ -389,13 +390,13 @@ int nasr_stream_set_state(nasr_handle h, const float* state, int64_t n) {
   if (int rc = need_session(h, __func__)) return rc;
   if (!state || n != state_floats(h))
     return h->fail(NASR_ERR_ARG, "nasr_stream_set_state: expected " + std::to_string(state_floats(h)) + " floats ([L][S][2][H])");
-  for (int b = 0; b < h->stream->S; ++b)   // the held rows belong to the state they were held behind
-    if (h->stream->held[(size_t)b] > 0)
+  for (int b = 0; b < h->lstm->stream->S; ++b)   // the held rows belong to the state they were held behind
+    if (h->lstm->stream->held[(size_t)b] > 0)
       return h->fail(NASR_ERR_STATE, "nasr_stream_set_state: slot " + std::to_string(b) + " holds " +
-                                         std::to_string(h->stream->held[(size_t)b]) +
+                                         std::to_string(h->lstm->stream->held[(size_t)b]) +
                                          " look-ahead rows that follow the present state: finish or reset the slot first");
   HIPCHK(h, hipSetDevice(h->device));
-  HIPCHK(h, hipMemcpyAsync(h->stream->state.p, state, (size_t)n * 4, hipMemcpyHostToDevice, h->st));
+  HIPCHK(h, hipMemcpyAsync(h->lstm->stream->state.p, state, (size_t)n * 4, hipMemcpyHostToDevice, h->st));
   HIPCHK(h, hipStreamSynchronize(h->st));   // the caller's array is free again
   return NASR_OK;
 }

@@ -45,8 +45,6 @@ int wn_layout(nasr_ctx* h) {
   h->C = w.cfg.num_classes;
   h->Fp = rup(h->F, 32);
   h->Cp = rup(h->C, 32);
-  h->H = h->Hp = h->N4 = h->D = h->L = 0;
-  h->Pin = h->Pinp = 0;
   w.S = 2 + 3 * w.nblk;
   w.off_wfg.assign(w.nblk, 0); w.off_wo.assign(w.nblk, 0);
   w.off_beta.assign(w.S, 0); w.off_gamma.assign(w.S, 0); w.bessel.assign(w.S, 1);
@@ -297,11 +295,7 @@ int nasr_create_wavenet(const nasr_wavenet_cfg* cfg, int device_id, void* stream
   }
   nasr_ctx* h = nullptr;
   if (int rc = handle_open("nasr_create_wavenet", Family::WaveNet, device_id, stream, &h, nullptr)) return rc;
-  h->cfg.feature_size = cfg->feature_size;
-  h->cfg.num_classes = cfg->num_classes;
-  h->cfg.merge = NASR_MERGE_NONE;
-  h->cfg.learning_rate = cfg->learning_rate;
-  h->cfg.beta1 = cfg->beta1; h->cfg.beta2 = cfg->beta2; h->cfg.epsilon = cfg->epsilon;
+  h->beta1 = cfg->beta1; h->beta2 = cfg->beta2; h->epsilon = cfg->epsilon;
   h->lr = cfg->learning_rate;
   h->graph_mode = false;
   h->wn.reset(new WnState());
