@@ -20,7 +20,7 @@ KT_OBJS = ['gemm.o', 'gemm_tph.o', 'optim.o', 'lstm.o', 'lstm_persist.o', 'lstm_
 SOURCES = ['gemm.hip', 'gemm_tph.hip', 'lstm.hip', 'rows.hip', 'lstm_persist.hip', 'lstm_wide.hip', 'ctc.hip', 'dense.hip', 'optim.hip', 'nasr_layout.hip',
            'nasr_rec.hip', 'nasr_batch.hip', 'nasr_pass.hip', 'nasr_stream.hip', 'nasr_lstm.hip', 'nasr_api.hip', 'nasr_comm.hip', 'beam.cpp',
            'wavenet.hip', 'nasr_wavenet.hip', 'las.hip', 'las_beam.hip', 'nasr_las.hip', 'mfcc.hip', 'nasr_fz.hip', 'resample.hip', 'wave_aug.hip']
-HEADERS = [os.path.join(CSRC, 'kernels.h'), os.path.join(CSRC, 'lstm_device.h'), os.path.join(CSRC, 'nasr_ctx.h'), os.path.join(CSRC, 'nasr_lstm.h'), os.path.join(CSRC, 'wavenet.h'), os.path.join(CSRC, 'las.h'), os.path.join(CSRC, 'las_beam.h'), os.path.join(CSRC, 'resample.h'), os.path.join(CSRC, 'wave_aug.h'),
+HEADERS = [os.path.join(CSRC, 'kernels.h'), os.path.join(CSRC, 'dispatch.h'), os.path.join(CSRC, 'lstm_device.h'), os.path.join(CSRC, 'nasr_ctx.h'), os.path.join(CSRC, 'nasr_lstm.h'), os.path.join(CSRC, 'wavenet.h'), os.path.join(CSRC, 'las.h'), os.path.join(CSRC, 'las_beam.h'), os.path.join(CSRC, 'resample.h'), os.path.join(CSRC, 'wave_aug.h'),
            os.path.join(CSRC, 'mfcc.h'), os.path.join(CSRC, 'nasr_fz.h'), os.path.join(HERE, '..', 'include', 'nasr.h')]
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-Wall', '-Wno-unused-function']
 # wave_aug.hip: the FIR's 8 x 8 register window is plain v_fmac_f32; the SLP vectoriser would pack pairs of them into

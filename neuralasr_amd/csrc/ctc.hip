@@ -8,14 +8,25 @@
 //   d nll / d logit(t,k) = y(t,k) - exp(LSE_{u: l'_u = k}(alpha+beta) - log p), zero for t >= seq_len.
 //
 // Kernel split: (1) logZ per (t,b) row, one wave per row; (2) alpha and beta recursions, one workgroup per
-// utterance, wave 0 = alpha, wave 1 = beta, the lattice column lives in registers (KS consecutive states per
-// lane), neighbours come over wave shuffles, so a timestep has no barrier and no LDS; emissions are
-// prefetched four frames ahead; (3) gradient, one wave per (t,b) row, class posteriors summed in a fixed order.
+// utterance, wave 0 = alpha, wave 1 = beta, the lattice column lives in registers (KS >= 2 consecutive states per
+// lane), neighbours come over DPP moves, so a timestep has no barrier and no LDS; emissions are prefetched four
+// frames ahead; (2b) the same recursions engineered (base 2, emissions through an LDS ring), the default;
+// (3) gradient, one wave per (t,b) row, class posteriors summed in a fixed order; (4) forced alignment.
+//
+// The lattice is walked four times - alpha and beta of (2), alpha and beta of (2b), and (4)'s Viterbi pass, which is
+// alpha in (max, +) - and described once, in (0): a lane's states from the label row (lattice_state), a step forward
+// and a step backward with the combining operation as a functor (lattice_step_fwd / _bwd), the column rescale
+// (lattice_rescale) and the final column to log p (lattice_logp).  A walk keeps for itself what the others do not
+// have: where its emissions come from and how far ahead, its workspace layout and stores, its offsets' bookkeeping.
+// The engineered walk, the default and the one whose time the training step sees, also keeps its set-up and its step
+// written out: through the shared functions hipcc compiles its time loop measurably slower.
+#include "dispatch.h"
 #include "kernels.h"
 
+#include <algorithm>
+#include <cassert>
 #include <cmath>
 #include <cstdlib>
-#include <type_traits>
 
 namespace nasr {
 
@@ -79,9 +90,84 @@ __device__ __forceinline__ float wave_sum(float v) {
   return v;
 }
 
-// the engineered lattice (2b) wants its workspaces, 32-float emission rows with a spare column to park idle states on and
-// two states per lane at least; otherwise the plain one of (2) runs
-static bool ctc_fast_ok(const CtcDims& d) { return d.lprobs && d.goff && d.Cp == 32 && d.C <= 31 && d.KS >= 2; }
+// the engineered lattice (2b) wants its workspaces and 32-float emission rows with a spare column to park idle states on;
+// otherwise the plain one of (2) runs
+static bool ctc_fast_ok(const CtcDims& d) { return d.lprobs && d.goff && d.Cp == 32 && d.C <= 31; }
+
+// ------------------------------------------------------------------ (0) the lattice: what the four walks share
+// A lane holds the KS consecutive states s = lane*KS + i of the extended label l' (S = 2L+1 states, blanks at the even
+// ones).  KS >= 2 everywhere: the skip transition then never reaches past the neighbour lane, so a step exchanges exactly
+// two values with it.
+// State s from the label row: act = inside the lattice, ext = the class it emits (`idle` past S: the blank, or a column
+// that holds NEG), skip = the state takes the s-2 (fwd) / gives to the s+2 (!fwd) transition:
+//   fwd: l'_s != blank and != l'_{s-2};  !fwd: l'_{s+2} != blank and != l'_s.
+// (Per state; a walk loops over its lane's KS states.)
+template <bool fwd>
+__device__ __forceinline__ void lattice_state(const int* __restrict__ lab, int S, int s, int blank, int idle, int& ext, bool& act,
+                                              bool& skip) {
+  act = s < S;
+  ext = act ? ((s & 1) ? lab[s >> 1] : blank) : idle;
+  if (fwd) {
+    const int e2 = (act && s >= 2 && (s & 1)) ? lab[(s >> 1) - 1] : blank;   // l'_{s-2} (past S, beyond the label row)
+    skip = act && s >= 2 && ext != blank && ext != e2;
+  } else {
+    const int e2 = (s + 2 < S && (s & 1)) ? lab[(s >> 1) + 1] : blank;       // l'_{s+2}
+    skip = (s + 2 < S) && e2 != blank && e2 != ext;
+  }
+}
+// One step forward in time: na[i] = op(i, a(s), a(s-1), a(s-2) or NEG where the state does not skip), the two states below
+// the lane's first coming from the lane before.  op combines (lse3, the alignment's maximum) and adds the emission.
+template <int KS, class Op>
+__device__ __forceinline__ void lattice_step_fwd(const float (&a)[KS], const bool (&skip)[KS], float (&na)[KS], Op op) {
+  static_assert(KS >= 2, "two states per lane at least");
+  const float p1 = lane_up1(a[KS - 1], NEG), p2 = lane_up1(a[KS - 2], NEG);
+#pragma unroll
+  for (int i = 0; i < KS; ++i) {
+    const float x1 = (i >= 1) ? a[i >= 1 ? i - 1 : 0] : p1;
+    const float x2 = (i >= 2) ? a[i >= 2 ? i - 2 : 0] : (i == 1 ? p1 : p2);
+    na[i] = op(i, a[i], x1, skip[i] ? x2 : NEG);
+  }
+}
+// One step backward: nb[i] = op(i, bb(s), bb(s+1), bb(s+2) or NEG), bb = beta + emission of the frame after (the caller's
+// sum); the two states above the lane's last come from the lane after.
+template <int KS, class Op>
+__device__ __forceinline__ void lattice_step_bwd(const float (&bb)[KS], const bool (&skip)[KS], float (&nb)[KS], Op op) {
+  static_assert(KS >= 2, "two states per lane at least");
+  const float n1 = lane_down1(bb[0], NEG), n2 = lane_down1(bb[1], NEG);
+#pragma unroll
+  for (int i = 0; i < KS; ++i) {
+    const float x1 = (i + 1 < KS) ? bb[i + 1 < KS ? i + 1 : 0] : n1;
+    const float x2 = (i + 2 < KS) ? bb[i + 2 < KS ? i + 2 : 0] : (i + 1 < KS ? n1 : n2);
+    nb[i] = op(i, bb[i], x1, skip[i] ? x2 : NEG);
+  }
+}
+// The column minus its maximum over the wave, "no path" staying NEG; returns the maximum (the caller's fp64 offset takes it)
+template <int KS>
+__device__ __forceinline__ float lattice_rescale(float (&a)[KS]) {
+  float m = a[0];
+#pragma unroll
+  for (int i = 1; i < KS; ++i) m = fmaxf(m, a[i]);
+  m = wave_max_dpp(m);
+#pragma unroll
+  for (int i = 0; i < KS; ++i) a[i] = a[i] > 0.5f * NEG ? a[i] - m : NEG;
+  return m;
+}
+// The last column of alpha to log p = (A + lse(alpha(S-1), alpha(S-2))) * unit (unit: the natural logarithm of the walk's
+// base) and nll = -log p, through fin[64 * KS] in LDS
+template <int KS, class Lse>
+__device__ __forceinline__ void lattice_logp(const float (&a)[KS], float* fin, int lane, int S, double A, double unit, Lse lse,
+                                             double* logp_out, float* nll, int b) {
+#pragma unroll
+  for (int i = 0; i < KS; ++i) fin[lane * KS + i] = a[i];
+  __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0)
+  if (lane == 0) {
+    const float x = fin[S - 1];
+    const float y = S > 1 ? fin[S - 2] : NEG;
+    const double lp = (A + (double)lse(x, y, NEG)) * unit;
+    logp_out[b] = lp;
+    nll[b] = (float)(-lp);
+  }
+}
 
 // ------------------------------------------------------------------ (1) log partition per row
 // (lprobs, or NULL: the row's emissions in the form the engineered lattice (2b) reads them too, log2 y(t,k) =
@@ -120,28 +206,24 @@ void launch_ctc_logz(const CtcDims& d, const float* logits, const int* seq_len, 
 // ulp is 1.2e-4 and alpha+beta-logp (the posterior exponent) loses 3 digits; rescaled columns stay O(10).
 // The time loop runs in branch-free groups of 4 frames (loads clamped, updates selected) so the emission
 // gathers of the NEXT group are in flight behind counted waits while this group computes.
-template <int KS>
-__device__ __forceinline__ void ctc_ab_log(
+template <int KS, bool fwd>
+__device__ __forceinline__ void ctc_plain_walk(
     const float* __restrict__ logits, const float* __restrict__ logz, const int* __restrict__ labels,
-    const int* __restrict__ label_len, const int* __restrict__ seq_len, float* __restrict__ alpha,
-    float* __restrict__ beta, double* __restrict__ aoff, double* __restrict__ boff, float* __restrict__ nll,
-    double* __restrict__ logp_out, int Bp, int Cp, int C, int Lmax, int Tws, float* fin) {
+    const int* __restrict__ label_len, const int* __restrict__ seq_len, float* __restrict__ walk_ws,
+    double* __restrict__ walk_off, float* __restrict__ nll, double* __restrict__ logp_out, int Bp, int Cp, int C, int Lmax,
+    int Tws, float* fin) {
+  static_assert(KS >= 2, "two states per lane at least: the skip transition then never reaches past the neighbour lane");
   constexpr int G = 4;   // frames per branch-free group = prefetch distance of the emissions
                          // (8, rescaling every 8 frames: same time - the lattice is not waiting for its emissions)
   const int b = blockIdx.x;
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int lane = threadIdx.x & 63;
   const int L = label_len[b], Tb = seq_len[b], S = 2 * L + 1;
   const int blank = C - 1;
-  const int* lab = labels + (size_t)b * Lmax;
 
   int ext[KS];
   bool act[KS], skip[KS];
 #pragma unroll
-  for (int i = 0; i < KS; ++i) {
-    const int s = lane * KS + i;
-    act[i] = s < S;
-    ext[i] = (act[i] && (s & 1)) ? lab[s >> 1] : blank;
-  }
+  for (int i = 0; i < KS; ++i) lattice_state<fwd>(labels + (size_t)b * Lmax, S, lane * KS + i, blank, blank, ext[i], act[i], skip[i]);
   // 32-bit element offsets from wave-uniform bases (the launcher checks T' * Bp * Cp < 2^32): one v_mad_u32 per gather
   // or store instead of 64-bit address arithmetic - the lattice is bound by its instruction count
   const unsigned rstride = (unsigned)Bp * (unsigned)Cp;  // logits row stride between frames
@@ -172,129 +254,62 @@ __device__ __forceinline__ void ctc_ab_log(
       e[i] = act[i] ? x - z : NEG;
     }
   };
-  float* ws = (w == 0 ? alpha : beta) + (size_t)b * Tws * KS * 64;
-  double* off = (w == 0 ? aoff : boff) + (size_t)b * Tws;
+  float* ws = walk_ws + (size_t)b * Tws * KS * 64;
+  double* off = walk_off + (size_t)b * Tws;
   auto store = [&](int t, const float (&a)[KS], double o) {
 #pragma unroll
     for (int i = 0; i < KS; ++i) stf(ws, (((unsigned)t * KS + i) * 64u + (unsigned)lane) * 4u, a[i]);
     if (lane == 0) off[t] = o;
   };
-  auto renorm = [&](float (&a)[KS], double& o) {
-    float m = a[0];
-#pragma unroll
-    for (int i = 1; i < KS; ++i) m = fmaxf(m, a[i]);
-    m = wave_max_dpp(m);
-#pragma unroll
-    for (int i = 0; i < KS; ++i) a[i] = a[i] > 0.5f * NEG ? a[i] - m : NEG;
-    o += (double)m;
-  };
 
-  if (w == 0) {
-    // ---------------- alpha, forward in time
-#pragma unroll
-    for (int i = 0; i < KS; ++i) {
-      const int s = lane * KS + i;
-      const int e2 = (act[i] && s >= 2 && (s & 1)) ? lab[(s >> 1) - 1] : blank;   // l'_{s-2} (past S, beyond the label row)
-      skip[i] = act[i] && s >= 2 && ext[i] != blank && ext[i] != e2;
-    }
-    float a[KS], e[G][KS];
-    double A = 0.0;
+  // positions p = 0 .. Tb-2 of the walk, as in (2b): position p reads the emission of frame p+1 and produces alpha of that
+  // frame, or reads the emission of frame Tb-1-p and produces beta of frame Tb-2-p (beta excludes the emission at t)
+  const int npos = Tb - 1;
+  auto eframe = [&](int p) { return fwd ? min(p + 1, Tb - 1) : max(Tb - 1 - p, 0); };   // clamped to a valid frame
+  float a[KS], e[G][KS];
+  double A = 0.0;
+  if (fwd) {
     emit(0, e[0]);
 #pragma unroll
-    for (int i = 0; i < KS; ++i) {
-      const int s = lane * KS + i;
-      a[i] = (s < 2 && act[i]) ? e[0][i] : NEG;
-    }
+    for (int i = 0; i < KS; ++i) a[i] = (lane * KS + i < 2 && act[i]) ? e[0][i] : NEG;
     store(0, a, A);
-#pragma unroll
-    for (int k = 0; k < G; ++k) emit(min(1 + k, Tb - 1), e[k]);
-    for (int t0 = 1; t0 < Tb; t0 += G) {
-      float vn[G][KS], zn[G];
-#pragma unroll
-      for (int k = 0; k < G; ++k) emit_raw(min(t0 + G + k, Tb - 1), vn[k], zn[k]);
-      renorm(a, A);
-#pragma unroll
-      for (int k = 0; k < G; ++k) {
-        const int t = t0 + k;
-        const bool live = t < Tb;
-        float p1 = lane_up1(a[KS - 1], NEG);
-        float p2 = (KS >= 2) ? lane_up1(a[KS >= 2 ? KS - 2 : 0], NEG) : __shfl_up(a[0], 2);
-        if (KS == 1 && lane <= 1) p2 = NEG;
-        float na[KS];
-#pragma unroll
-        for (int i = 0; i < KS; ++i) {
-          const float x1 = (i >= 1) ? a[i >= 1 ? i - 1 : 0] : p1;
-          const float x2 = (i >= 2) ? a[i >= 2 ? i - 2 : 0] : (i == 1 ? p1 : p2);
-          na[i] = e[k][i] + lse3(a[i], x1, skip[i] ? x2 : NEG);
-        }
-#pragma unroll
-        for (int i = 0; i < KS; ++i) a[i] = live ? na[i] : a[i];   // a state past S has e = NEG: its na is ~NEG by itself
-        store(t, a, A);              // rows Tb .. Tb+G-2 of the workspace take dead copies (Tws = T+8)
-      }
-      asm volatile("" ::: "memory");
-#pragma unroll
-      for (int k = 0; k < G; ++k) emit_finish(vn[k], zn[k], e[k]);
-    }
-#pragma unroll
-    for (int i = 0; i < KS; ++i) fin[lane * KS + i] = a[i];
-    __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0)
-    if (lane == 0) {
-      const float x = fin[S - 1];
-      const float y = S > 1 ? fin[S - 2] : NEG;
-      const double lp = A + (double)lse3(x, y, NEG);
-      logp_out[b] = lp;
-      nll[b] = (float)(-lp);
-    }
   } else {
-    // ---------------- beta, backward in time (excludes the emission at t)
 #pragma unroll
     for (int i = 0; i < KS; ++i) {
       const int s = lane * KS + i;
-      const int e2 = (s + 2 < S && (s & 1)) ? lab[(s >> 1) + 1] : blank;   // l'_{s+2}
-      skip[i] = (s + 2 < S) && e2 != blank && e2 != ext[i];
+      a[i] = (act[i] && (s == S - 1 || s == S - 2)) ? 0.f : NEG;
     }
-    float bt[KS], e[G][KS];
-    double Bo = 0.0;
+    store(Tb - 1, a, A);
+  }
 #pragma unroll
-    for (int i = 0; i < KS; ++i) {
-      const int s = lane * KS + i;
-      bt[i] = (act[i] && (s == S - 1 || s == S - 2)) ? 0.f : NEG;
-    }
-    store(Tb - 1, bt, Bo);
-    // e[k] holds the emission of frame (t+1) for the k-th step of a group
+  for (int k = 0; k < G; ++k) emit(eframe(k), e[k]);
+  for (int p0 = 0; p0 < npos; p0 += G) {
+    float vn[G][KS], zn[G];
 #pragma unroll
-    for (int k = 0; k < G; ++k) emit(max(Tb - 1 - k, 0), e[k]);
-    for (int t0 = Tb - 2; t0 >= 0; t0 -= G) {
-      float vn[G][KS], zn[G];
+    for (int k = 0; k < G; ++k) emit_raw(eframe(p0 + G + k), vn[k], zn[k]);
+    A += (double)lattice_rescale(a);
 #pragma unroll
-      for (int k = 0; k < G; ++k) emit_raw(max(t0 - G - k + 1, 0), vn[k], zn[k]);
-      renorm(bt, Bo);
-#pragma unroll
-      for (int k = 0; k < G; ++k) {
-        const int t = t0 - k;
-        const bool live = t >= 0;
+    for (int k = 0; k < G; ++k) {
+      const bool live = p0 + k < npos;
+      float na[KS];
+      if (fwd) {
+        lattice_step_fwd(a, skip, na, [&](int i, float s0, float x1, float x2) { return e[k][i] + lse3(s0, x1, x2); });
+      } else {
         float bb[KS];
 #pragma unroll
-        for (int i = 0; i < KS; ++i) bb[i] = bt[i] + e[k][i];      // states past S: NEG + NEG, rescaled back to NEG every group
-        float n1 = lane_down1(bb[0], NEG);
-        float n2 = (KS >= 2) ? lane_down1(bb[KS >= 2 ? 1 : 0], NEG) : __shfl_down(bb[0], 2);
-        if (KS == 1 && lane >= 62) n2 = NEG;
-        float nb[KS];
-#pragma unroll
-        for (int i = 0; i < KS; ++i) {
-          const float x1 = (i + 1 < KS) ? bb[i + 1 < KS ? i + 1 : 0] : n1;
-          const float x2 = (i + 2 < KS) ? bb[i + 2 < KS ? i + 2 : 0] : (i + 1 < KS ? n1 : n2);
-          nb[i] = lse3(bb[i], x1, skip[i] ? x2 : NEG);
-        }
-#pragma unroll
-        for (int i = 0; i < KS; ++i) bt[i] = live ? nb[i] : bt[i];
-        if (live) store(t, bt, Bo);
+        for (int i = 0; i < KS; ++i) bb[i] = a[i] + e[k][i];      // states past S: NEG + NEG, rescaled back to NEG every group
+        lattice_step_bwd(bb, skip, na, [&](int, float s0, float x1, float x2) { return lse3(s0, x1, x2); });
       }
-      asm volatile("" ::: "memory");
 #pragma unroll
-      for (int k = 0; k < G; ++k) emit_finish(vn[k], zn[k], e[k]);
+      for (int i = 0; i < KS; ++i) a[i] = live ? na[i] : a[i];   // a state past S has e = NEG: its na is ~NEG by itself
+      if (fwd) store(p0 + k + 1, a, A);          // rows Tb .. Tb+G-2 of the workspace take dead copies (Tws = T+8)
+      else if (live) store(Tb - 2 - p0 - k, a, A);
     }
+    asm volatile("" ::: "memory");
+#pragma unroll
+    for (int k = 0; k < G; ++k) emit_finish(vn[k], zn[k], e[k]);
   }
+  if (fwd) lattice_logp(a, fin, lane, S, A, 1.0, [](float x, float y, float z) { return lse3(x, y, z); }, logp_out, nll, b);
 }
 
 // ------------------------------------------------------------------ (2b) the same recursions, engineered: the default
@@ -342,10 +357,6 @@ __device__ __forceinline__ void fast_store(float* base, unsigned voff, const flo
     asm volatile("global_store_dword %0, %1, %2 offset:%3" : : "v"(voff), "v"(a[j]), "s"(base), "n"(j * 4) : "memory");
   }
 }
-// lane l <- lane l-1 / l+1 with `edge` at the wave's first / last lane, as in lane_up1 / lane_down1
-__device__ __forceinline__ float fast_up(float v) { return lane_up1(v, NEG); }
-__device__ __forceinline__ float fast_down(float v) { return lane_down1(v, NEG); }
-
 // log2(2^a + 2^b + 2^c)
 __device__ __forceinline__ float lse3_2(float a, float b, float c) {
   const float mx = __builtin_fmaxf(a, __builtin_fmaxf(b, c));                   // (v_max3_f32)
@@ -368,6 +379,10 @@ __device__ __forceinline__ void ctc_fast_walk(const int* __restrict__ labels, co
   const int lane = threadIdx.x & 63, w = fwd ? 0 : 1;
   const int L = label_len[b], Tb = seq_len[b], S = 2 * L + 1;
   const int blank = C - 1;
+  // This walk keeps the set-up and the step of (0) written out, idle states parked on column 31 (NEG in every emission
+  // row): called through lattice_state / lattice_step_* hipcc orders and allocates the time loop another way, 0.6 to 0.9 %
+  // slower (2.5 % with the set-up loop inside a function); as written the kernel is the one measured in §4.5
+  // (DESIGN.md §21).  The rescale and the final column are (0)'s.
   const int* lab = labels + (size_t)b * Lmax;
   int ext[KS];
   bool skip[KS];
@@ -375,12 +390,12 @@ __device__ __forceinline__ void ctc_fast_walk(const int* __restrict__ labels, co
   for (int i = 0; i < KS; ++i) {
     const int s = lane * KS + i;
     const bool act = s < S;
-    ext[i] = act ? ((s & 1) ? lab[s >> 1] : blank) : 31;      // column 31 of an emission row is NEG
+    ext[i] = act ? ((s & 1) ? lab[s >> 1] : blank) : 31;
     if (fwd) {
       const int e2 = (act && s >= 2 && (s & 1)) ? lab[(s >> 1) - 1] : blank;   // l'_{s-2} (past S, beyond the label row)
       skip[i] = act && s >= 2 && ext[i] != blank && ext[i] != e2;
     } else {
-      const int e2 = (s + 2 < S && (s & 1)) ? lab[(s >> 1) + 1] : blank;   // l'_{s+2}
+      const int e2 = (s + 2 < S && (s & 1)) ? lab[(s >> 1) + 1] : blank;       // l'_{s+2}
       skip[i] = (s + 2 < S) && e2 != blank && e2 != ext[i];
     }
   }
@@ -439,21 +454,13 @@ __device__ __forceinline__ void ctc_fast_walk(const int* __restrict__ labels, co
     constexpr bool MASKED = decltype(maskedc)::value;
     const int p0 = G * g;
     read_group(g + 1, en);
-    {
-      float m = a[0];
-#pragma unroll
-      for (int i = 1; i < KS; ++i) m = fmaxf(m, a[i]);
-      m = wave_max_dpp(m);
-#pragma unroll
-      for (int i = 0; i < KS; ++i) a[i] = a[i] > 0.5f * NEG ? a[i] - m : NEG;
-      A += (double)m;
-      if (lane == 0) go[g + 1] = A;
-    }
+    A += (double)lattice_rescale(a);
+    if (lane == 0) go[g + 1] = A;
 #pragma unroll
     for (int k = 0; k < G; ++k) {
       float na[KS];
       if (fwd) {
-        const float p1 = fast_up(a[KS - 1]), p2 = fast_up(a[KS - 2]);
+        const float p1 = lane_up1(a[KS - 1], NEG), p2 = lane_up1(a[KS - 2], NEG);
 #pragma unroll
         for (int i = 0; i < KS; ++i) {
           const float x1 = (i >= 1) ? a[i >= 1 ? i - 1 : 0] : p1;
@@ -464,7 +471,7 @@ __device__ __forceinline__ void ctc_fast_walk(const int* __restrict__ labels, co
         float bb[KS];
 #pragma unroll
         for (int i = 0; i < KS; ++i) bb[i] = a[i] + e[k][i];      // states past S: NEG + NEG, rescaled back to NEG every group
-        const float n1 = fast_down(bb[0]), n2 = fast_down(bb[1]);
+        const float n1 = lane_down1(bb[0], NEG), n2 = lane_down1(bb[1], NEG);
 #pragma unroll
         for (int i = 0; i < KS; ++i) {
           const float x1 = (i + 1 < KS) ? bb[i + 1 < KS ? i + 1 : 0] : n1;
@@ -506,18 +513,7 @@ __device__ __forceinline__ void ctc_fast_walk(const int* __restrict__ labels, co
       asm volatile("s_waitcnt lgkmcnt(0)\n\tds_write_b32 %0, %1 offset:%2" : : "v"(sync_lds), "v"(c + 1), "n"(4 * (1 + w)) : "memory");
     }
   }
-  if (fwd) {
-#pragma unroll
-    for (int i = 0; i < KS; ++i) fin[lane * KS + i] = a[i];
-    __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0)
-    if (lane == 0) {
-      const float x = fin[S - 1];
-      const float y = S > 1 ? fin[S - 2] : NEG;
-      const double lp = (A + (double)lse3_2(x, y, NEG)) * LN2;
-      logp_out[b] = lp;
-      nll[b] = (float)(-lp);
-    }
-  }
+  if (fwd) lattice_logp(a, fin, lane, S, A, LN2, [](float x, float y, float z) { return lse3_2(x, y, z); }, logp_out, nll, b);
 }
 
 // wave 2: the emissions' way into LDS.  Chunk n (32 positions of both walks) goes to the ring half chunk n-2 was in, once both
@@ -562,44 +558,38 @@ __global__ __launch_bounds__(FAST ? 192 : 128) void ctc_alpha_beta_kernel(
     __shared__ int sync[3];
     if (threadIdx.x < 3) sync[threadIdx.x] = 0;
     __syncthreads();
-    constexpr int K2 = KS >= 2 ? KS : 2;
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     if (w == 0)
-      ctc_fast_walk<K2, true>(labels, label_len, seq_len, alpha, beta, goff, nll, logp_out, lprobs, Bp, C, Lmax, Tws, KG, ring, fin, sync);
+      ctc_fast_walk<KS, true>(labels, label_len, seq_len, alpha, beta, goff, nll, logp_out, lprobs, Bp, C, Lmax, Tws, KG, ring, fin, sync);
     else if (w == 1)
-      ctc_fast_walk<K2, false>(labels, label_len, seq_len, alpha, beta, goff, nll, logp_out, lprobs, Bp, C, Lmax, Tws, KG, ring, fin, sync);
+      ctc_fast_walk<KS, false>(labels, label_len, seq_len, alpha, beta, goff, nll, logp_out, lprobs, Bp, C, Lmax, Tws, KG, ring, fin, sync);
     else
       ctc_fast_loader(lprobs, seq_len, Bp, ring, sync);
   } else {
-    ctc_ab_log<KS>(logits, logz, labels, label_len, seq_len, alpha, beta, aoff, boff, nll, logp_out, Bp, Cp, C, Lmax, Tws, fin);
+    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    if (w == 0)
+      ctc_plain_walk<KS, true>(logits, logz, labels, label_len, seq_len, alpha, aoff, nll, logp_out, Bp, Cp, C, Lmax, Tws, fin);
+    else
+      ctc_plain_walk<KS, false>(logits, logz, labels, label_len, seq_len, beta, boff, nll, logp_out, Bp, Cp, C, Lmax, Tws, fin);
   }
 }
+
+// f(std::integral_constant<int, KS>{}) for the instantiation KS in {2 .. 8, 12, 16} (ctc_states_per_lane's values)
+using CtcKS = std::integer_sequence<int, 2, 3, 4, 5, 6, 7, 8, 12, 16>;
 
 void launch_ctc_alpha_beta(const CtcDims& d, const float* logits, const float* logz, const int* labels,
                            const int* label_len, const int* seq_len, float* alpha, float* beta, double* aoff,
                            double* boff, float* nll, double* logp, hipStream_t st) {
-  const bool fast = ctc_fast_ok(d);
-  const int KG = d.Tws / FAST_G + 3;
-#define NASR_AB2(K, F)                                                                                                   \
-  hipLaunchKernelGGL((ctc_alpha_beta_kernel<K, F>), dim3(d.B), dim3(F ? 192 : 128), 0, st, logits, logz, d.lprobs, labels, \
-                     label_len, seq_len, alpha, beta, aoff, boff, d.goff, nll, logp, d.Bp, d.Cp, d.C, d.Lmax, d.Tws, KG)
-#define NASR_AB(K)                                                                                                       \
-  if (fast) NASR_AB2(K, true);                                                                                           \
-  else NASR_AB2(K, false)
-  switch (d.KS) {
-    case 1: NASR_AB2(1, false); break;
-    case 2: NASR_AB(2); break;
-    case 3: NASR_AB(3); break;
-    case 4: NASR_AB(4); break;
-    case 5: NASR_AB(5); break;
-    case 6: NASR_AB(6); break;
-    case 7: NASR_AB(7); break;
-    case 8: NASR_AB(8); break;
-    case 9: case 10: case 11: case 12: NASR_AB(12); break;
-    default: NASR_AB(16); break;
-  }
-#undef NASR_AB2
-#undef NASR_AB
+  assert(d.KS == ctc_states_per_lane(d.Lmax) && d.KS <= 16);   // the workspaces were sized for this instantiation
+  const int KG = ctc_group_rows(d.Tws);
+  dispatch_int(CtcKS{}, d.KS, [&](auto ks) {
+    auto launch = [&](auto fast) {
+      hipLaunchKernelGGL((ctc_alpha_beta_kernel<ks(), fast()>), dim3(d.B), dim3(fast() ? 192 : 128), 0, st, logits, logz, d.lprobs,
+                         labels, label_len, seq_len, alpha, beta, aoff, boff, d.goff, nll, logp, d.Bp, d.Cp, d.C, d.Lmax, d.Tws, KG);
+    };
+    if (ctc_fast_ok(d)) launch(std::true_type{});
+    else launch(std::false_type{});
+  });
 }
 
 // ------------------------------------------------------------------ (3) gradient, in place over the logits
@@ -680,7 +670,7 @@ void launch_ctc_grad(const CtcDims& d, float* logits, const float* logz, const i
   const int rpb = 4;
   hipLaunchKernelGGL(ctc_grad_kernel, dim3((rows + rpb - 1) / rpb), dim3(64 * rpb), (size_t)rpb * d.KS * 64 * 4, st, logits,
                      logz, label_len, seq_len, cstart, cpos, alpha, beta, aoff, boff, logp, ctc_fast_ok(d) ? d.goff : nullptr, scale,
-                     d.Tp, d.B, d.Bp, d.C, d.Cp, d.Lmax, d.KS, d.Tws, d.Tws / FAST_G + 3);
+                     d.Tp, d.B, d.Bp, d.C, d.Cp, d.Lmax, d.KS, d.Tws, ctc_group_rows(d.Tws));
 }
 
 // mean of n floats (n small: the batch), fixed order
@@ -768,15 +758,13 @@ constexpr int ALIGN_G = 4;                      // frames per group: rescaling p
 constexpr int ALIGN_LDS_BYTES = 56 * 1024;      // back-pointers kept in LDS up to this (beside 4 KB of the final column)
 constexpr int align_bpf(int KS) { return KS <= 4 ? 8 : KS <= 8 ? 16 : 32; }   // back-pointer bits per lane and frame
 constexpr int align_words(int KS) { return align_bpf(KS) * ALIGN_G / 32; }    // words per lane and group
-static int align_ks(int L) {                                                 // the instantiation for labels up to L (as the loss's)
-  const int KS = std::max(1, (2 * std::max(L, 0) + 1 + 63) / 64);
-  return KS <= 1 ? 2 : KS <= 8 ? KS : (KS <= 12 ? 12 : 16);
-}
 static int align_groups(int F) { return (std::max(F, 1) - 1 + ALIGN_G - 1) / ALIGN_G; }
 
-bool ctc_align_bp_in_lds(int F, int L) { return (size_t)align_groups(F) * 256 * align_words(align_ks(L)) <= (size_t)ALIGN_LDS_BYTES; }
+bool ctc_align_bp_in_lds(int F, int L) {
+  return (size_t)align_groups(F) * 256 * align_words(ctc_states_per_lane(L)) <= (size_t)ALIGN_LDS_BYTES;
+}
 size_t ctc_align_ws_words(int B, int F, int L) {
-  return ctc_align_bp_in_lds(F, L) ? 0 : (size_t)B * align_groups(F) * 64 * align_words(align_ks(L));
+  return ctc_align_bp_in_lds(F, L) ? 0 : (size_t)B * align_groups(F) * 64 * align_words(ctc_states_per_lane(L));
 }
 
 template <int KS, bool LDSBP>
@@ -796,13 +784,7 @@ __global__ __launch_bounds__(64) void ctc_align_kernel(const float* __restrict__
   int ext[KS];
   bool act[KS], skip[KS];
 #pragma unroll
-  for (int i = 0; i < KS; ++i) {
-    const int s = lane * KS + i;
-    act[i] = s < S;
-    ext[i] = (act[i] && (s & 1)) ? lab[s >> 1] : blank;
-    const int e2 = (act[i] && s >= 2 && (s & 1)) ? lab[(s >> 1) - 1] : blank;   // l'_{s-2}
-    skip[i] = act[i] && s >= 2 && ext[i] != blank && ext[i] != e2;
-  }
+  for (int i = 0; i < KS; ++i) lattice_state<true>(lab, S, lane * KS + i, blank, blank, ext[i], act[i], skip[i]);
   const unsigned rstride = (unsigned)Bp * (unsigned)Cp;     // (the launcher checks T' * Bp * Cp * 4 < 2^32)
   const float* lg = logits + (size_t)b * Cp;
   auto gather = [&](int t, float (&x)[KS]) {                // t must be a valid frame (callers clamp); ext is always a class id
@@ -831,35 +813,22 @@ __global__ __launch_bounds__(64) void ctc_align_kernel(const float* __restrict__
       const int g = g0 + sub;
       if (g < ngroups) {
         const int t0 = 1 + G * g;
-        {
-          float m = v[0];
-#pragma unroll
-          for (int i = 1; i < KS; ++i) m = fmaxf(m, v[i]);
-          m = wave_max_dpp(m);
-#pragma unroll
-          for (int i = 0; i < KS; ++i) v[i] = v[i] > 0.5f * NEG ? v[i] - m : NEG;
-        }
+        lattice_rescale(v);                                    // (the score is summed on the way back: no offset kept)
         unsigned w[W];
 #pragma unroll
         for (int j = 0; j < W; ++j) w[j] = 0u;
 #pragma unroll
         for (int k = 0; k < G; ++k) {
           const bool live = t0 + k < F;
-          const float p1 = lane_up1(v[KS - 1], NEG), p2 = lane_up1(v[KS - 2], NEG);
           float nv[KS];
           unsigned code = 0u;
-#pragma unroll
-          for (int i = 0; i < KS; ++i) {
-            const float x1 = (i >= 1) ? v[i >= 1 ? i - 1 : 0] : p1;
-            const float x2r = (i >= 2) ? v[i >= 2 ? i - 2 : 0] : (i == 1 ? p1 : p2);
-            const float x2 = skip[i] ? x2r : NEG;
-            float best = v[i];
+          lattice_step_fwd(v, skip, nv, [&](int i, float best, float x1, float x2) {
             unsigned c = 0u;
             if (x1 > best) { best = x1; c = 1u; }
             if (x2 > best) { best = x2; c = 2u; }
-            nv[i] = act[i] ? best + e[sub * G + k][i] : NEG;   // (no path: NEG + x is NEG again, exactly)
             code |= c << (2 * i);
-          }
+            return act[i] ? best + e[sub * G + k][i] : NEG;    // (no path: NEG + x is NEG again, exactly)
+          });
 #pragma unroll
           for (int i = 0; i < KS; ++i) v[i] = live ? nv[i] : v[i];
           w[(k * BPF) / 32] |= code << ((k * BPF) % 32);       // (frames past the end leave words nobody reads)
@@ -932,31 +901,20 @@ __global__ __launch_bounds__(64) void ctc_align_kernel(const float* __restrict__
 int launch_ctc_align(const CtcDims& d, int Fmax, const float* logits, const float* logz, const int* labels, const int* label_len,
                      const int* seq_len, unsigned* bpws, int* path, double* score, hipStream_t st) {
   if ((size_t)d.Tp * d.Bp * d.Cp * 4 >= ((size_t)1 << 32)) return -1;
-  const int KS = align_ks(d.Lmax);
+  const int KS = ctc_states_per_lane(d.Lmax);
   const bool lds = ctc_align_bp_in_lds(Fmax, d.Lmax);
   const int W = align_words(KS);
   const size_t stride = (size_t)align_groups(Fmax) * 64 * W;
   const size_t shm = lds ? std::max<size_t>(stride * 4, 16) : (size_t)16 * 64 * W * 4;
   if (!lds && !bpws) return -2;
-#define NASR_AL2(K, LD)                                                                                                     \
-  hipLaunchKernelGGL((ctc_align_kernel<K, LD>), dim3(d.B), dim3(64), shm, st, logits, logz, labels, label_len, seq_len, bpws, \
-                     stride, path, score, d.Tp, d.Bp, d.Cp, d.C, d.Lmax)
-#define NASR_AL(K)                                                                                                          \
-  if (lds) NASR_AL2(K, true);                                                                                               \
-  else NASR_AL2(K, false)
-  switch (KS) {
-    case 2: NASR_AL(2); break;
-    case 3: NASR_AL(3); break;
-    case 4: NASR_AL(4); break;
-    case 5: NASR_AL(5); break;
-    case 6: NASR_AL(6); break;
-    case 7: NASR_AL(7); break;
-    case 8: NASR_AL(8); break;
-    case 12: NASR_AL(12); break;
-    default: NASR_AL(16); break;
-  }
-#undef NASR_AL2
-#undef NASR_AL
+  dispatch_int(CtcKS{}, KS, [&](auto ks) {
+    auto launch = [&](auto in_lds) {
+      hipLaunchKernelGGL((ctc_align_kernel<ks(), in_lds()>), dim3(d.B), dim3(64), shm, st, logits, logz, labels, label_len, seq_len,
+                         bpws, stride, path, score, d.Tp, d.Bp, d.Cp, d.C, d.Lmax);
+    };
+    if (lds) launch(std::true_type{});
+    else launch(std::false_type{});
+  });
   return 0;
 }
 

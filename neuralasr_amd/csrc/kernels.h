@@ -292,12 +292,22 @@ void launch_dense_act_bwd(float* dy, const float* y, int64_t n, float clip, floa
 struct CtcDims {
   int Tp;      // logit frames T'
   int B, Bp, C, Cp, Lmax;
-  int KS;      // states per lane: ceil((2*Lmax+1)/64)
+  int KS;      // states per lane: ctc_states_per_lane(Lmax)
   int Tws;     // rows of the alpha/beta workspace per utterance (T + 8: a group of up to 8 frames may run past the last one)
   // workspaces of the engineered lattice (ctc.hip (2b)), or NULL (the plain one only):
   float* lprobs = nullptr;  // [T'][Bp][Cp] emission rows log2 y(t,k) (launch_ctc_logz writes them)
-  double* goff = nullptr;   // [B][2][Tws/4 + 3] column offsets per walk and group of 4 frames
+  double* goff = nullptr;   // [B][2][ctc_group_rows(Tws)] column offsets per walk and group of 4 frames
 };
+// The lattice kernels' instantiation for a label array of width Lmax: ceil((2 Lmax + 1) / 64) states per lane, two at least
+// (a step then never reaches past the neighbour lane), rounded up to one of 2 .. 8, 12, 16.  More than 16 (Lmax > 511):
+// no instantiation - the caller reports it.
+constexpr int ctc_states_per_lane(int Lmax) {
+  const int KS = (2 * (Lmax > 0 ? Lmax : 0) + 1 + 63) / 64;
+  return KS <= 1 ? 2 : KS <= 8 ? KS : KS <= 12 ? 12 : KS <= 16 ? 16 : KS;
+}
+// column offsets the engineered lattice keeps per utterance and walk: one per group of 4 frames of the Tws workspace rows
+// (group 0 = the start column) and room for the masked last group
+constexpr int ctc_group_rows(int Tws) { return Tws / 4 + 3; }
 void launch_ctc_logz(const CtcDims& d, const float* logits, const int* seq_len, float* logz, hipStream_t st);
 void launch_ctc_alpha_beta(const CtcDims& d, const float* logits, const float* logz, const int* labels,
                            const int* label_len, const int* seq_len, float* alpha, float* beta, double* aoff,

@@ -3,14 +3,15 @@
 // once, here: the activations and the c / h update of the forward pass (lstm_gates, lstm_state) and the gate derivatives
 // of BPTT (lstm_cell_bwd); every kernel calls these.  So does the protocol around the cell that the resident kernels have
 // in common: placement (join_xcd), abort (raise_error), the epoch rule of the self-validating exchange buffers (use_epoch),
-// the two-plane fp16 split (split_f16x2) and the phase stamps of the diagnostic builds (Stamps); and, for the hosts'
-// launchers, the dispatch over a compile-time list of template values (dispatch_int / for_each_int).
+// the two-plane fp16 split (split_f16x2) and the phase stamps of the diagnostic builds (Stamps).  (The launchers' dispatch
+// over a compile-time list of template values, dispatch_int / for_each_int, is in dispatch.h: the CTC launchers use it too.)
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <type_traits>
 #include <utility>
 
+#include "dispatch.h"
 #include "kernels.h"
 
 namespace nasr {
@@ -167,22 +168,5 @@ struct Stamps<N, false> {
   __device__ __forceinline__ void add(int, unsigned) {}
   __device__ __forceinline__ void flush(unsigned*) {}
 };
-
-// ------------------------------------------------------------------ host: a run-time value picks a template argument
-// f(std::integral_constant<int, V>{}) for the V of the list that equals v; the LAST value of the list is the default
-template <class F, int V0, int... Vs>
-inline void dispatch_int(std::integer_sequence<int, V0, Vs...>, int v, F&& f) {
-  if constexpr (sizeof...(Vs) == 0) {
-    f(std::integral_constant<int, V0>{});
-  } else {
-    if (v == V0) f(std::integral_constant<int, V0>{});
-    else dispatch_int(std::integer_sequence<int, Vs...>{}, v, f);
-  }
-}
-// f for every value of the list
-template <class F, int... Vs>
-inline void for_each_int(std::integer_sequence<int, Vs...>, F&& f) {
-  (f(std::integral_constant<int, Vs>{}), ...);
-}
 
 }  // namespace nasr

@@ -9,9 +9,8 @@ using namespace nasr_impl;
 namespace nasr_impl {
 
 int ensure_ctc_buffers(nasr_ctx* h, int B, int Bp, int T, int Tp, int Lmax, bool* grew) {
-  const int KS = std::max(1, (2 * std::max(Lmax, 0) + 1 + 63) / 64);
-  if (KS > 16) return h->fail(NASR_ERR_ARG, "label length > 511 not supported by the CTC lattice kernel");
-  const int KSa = KS <= 1 ? 2 : KS <= 8 ? KS : (KS <= 12 ? 12 : 16);   // kernel instantiations (two states per lane at least: ctc.hip (2b))
+  const int KSa = ctc_states_per_lane(Lmax);
+  if (KSa > 16) return h->fail(NASR_ERR_ARG, "label length > 511 not supported by the CTC lattice kernel");
   bool ok = true;
   ok &= h->logits.ensure((size_t)Tp * Bp * h->Cp * 4, grew);
   ok &= h->logz.ensure((size_t)Tp * Bp * 4, grew);
@@ -21,7 +20,7 @@ int ensure_ctc_buffers(nasr_ctx* h, int B, int Bp, int T, int Tp, int Lmax, bool
   ok &= h->boff.ensure((size_t)B * (T + 8) * 8, grew);
   ok &= h->logp.ensure((size_t)Bp * 8, grew);
   ok &= h->ctcprobs.ensure((size_t)Tp * Bp * h->Cp * 4, grew);              // emission rows of the CTC lattice (ctc.hip (2b))
-  ok &= h->ctckexp.ensure((size_t)B * 2 * ((T + 8) / 4 + 3) * 8, grew);     // its column offsets per group of frames
+  ok &= h->ctckexp.ensure((size_t)B * 2 * ctc_group_rows(T + 8) * 8, grew);   // its column offsets per group of frames
   ok &= h->nll.ensure((size_t)Bp * 4, grew);
   ok &= h->loss.ensure(16, grew);
   ok &= h->amax.ensure((size_t)Tp * Bp * 4, grew);

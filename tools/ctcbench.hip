@@ -41,15 +41,15 @@ int main(int argc, char** argv) {
   }
   CtcDims d{};
   d.Tp = T; d.B = B; d.Bp = Bp; d.C = C; d.Cp = Cp; d.Lmax = Lmax;
-  const int KS = std::max(1, (2 * Lmax + 1 + 63) / 64);
-  d.KS = KS <= 1 ? 2 : KS <= 8 ? KS : (KS <= 12 ? 12 : 16);
+  d.KS = ctc_states_per_lane(Lmax);
+  if (d.KS > 16) { printf("Lmax %d: more than 511 labels\n", Lmax); return 1; }
   d.Tws = T + 8;
   const size_t nl = (size_t)T * Bp * Cp, nws = (size_t)B * d.Tws * d.KS * 64;
   float *logits = dev<float>(nl), *logz = dev<float>((size_t)T * Bp), *alpha = dev<float>(nws), *beta = dev<float>(nws), *nll = dev<float>(Bp);
   double *aoff = dev<double>((size_t)B * d.Tws), *boff = dev<double>((size_t)B * d.Tws), *logp = dev<double>(Bp);
   int *dseq = dev<int>(Bp), *dll = dev<int>(B), *dlab = dev<int>(lab.size()), *dcs = dev<int>(cstart.size()), *dcp = dev<int>(cpos.size());
   float* lprobs = dev<float>(nl);
-  double* goff = dev<double>((size_t)B * 2 * (d.Tws / 4 + 3));
+  double* goff = dev<double>((size_t)B * 2 * ctc_group_rows(d.Tws));
   CK(hipMemcpy(dseq, seq.data(), Bp * 4, hipMemcpyHostToDevice));
   CK(hipMemcpy(dll, ll.data(), B * 4, hipMemcpyHostToDevice));
   CK(hipMemcpy(dlab, lab.data(), lab.size() * 4, hipMemcpyHostToDevice));
