@@ -589,6 +589,46 @@ int nasr_ctc_align_logits(nasr_handle h, const float* logits, const int32_t* seq
  * [0,511].  No counterpart in the reference. */
 int nasr_ctc_align_lds(int F, int L);
 
+/* ---- teacher-student distillation beside the CTC loss (not part of the reference) -------------------
+ * With student logits z and teacher logits y [T',B,C], weight a, temperature tau, p = softmax(y / tau) and
+ * q = softmax(z / tau) over the C classes, and len_b the logit frames of utterance b that the CTC loss uses:
+ *   kd_b = sum_{t < len_b, c} p_c (log p_c - log q_c),   KD = tau^2 mean_b kd_b,   loss = (1 - a) CTC + a KD,
+ *   dloss/dz[t,b,c] = (1 - a) dCTC/dz[t,b,c] + a tau (q_c - p_c) / B,   exactly 0 where the CTC gradient is 0 by layout
+ * (frames t >= len_b, padding utterances, padded class columns).  The term is computed in the loss pass, row-wise in
+ * fp32 with max-subtracted log-softmaxes and summed per utterance in fp64 in a fixed order: two runs give the same bits.
+ * The loss that nasr_get_loss, nasr_get_step_results, nasr_loss* and nasr_train_step report is then the combined one.
+ *
+ * nasr_set_distill: weight in [0, 1), temperature in [0.25, 16], both finite, else NASR_ERR_ARG.  weight = 0 is off, the
+ * default: every step is bit for bit the step without this section, and nothing of it is launched or allocated.
+ * NASR_ERR_STATE with the reason: a LAS or featurizer handle; a NASR_MERGE_STACK_RESHAPE network, whose logit rows are
+ * no frames.  With weight > 0 the term takes part in every loss pass for which teacher logits are valid:
+ *   - teacher logits belong to the resident batch; any upload, commit or stream feed drops them;
+ *   - nasr_compute_grads (and nasr_train_step, nasr_loss_and_grads through it) without them is NASR_ERR_STATE, nothing
+ *     changed; nasr_loss_resident and nasr_loss without them return the plain CTC loss.
+ * The teacher logits are never written by a step: loss and gradient passes on the same resident batch repeat bit for bit. */
+int nasr_set_distill(nasr_handle h, float weight, float temperature);
+/* either pointer nullable */
+int nasr_get_distill(nasr_handle h, float* weight, float* temperature);
+/* Teacher logits for the resident batch from host memory, time-major [T',B,C] as nasr_forward returns them.
+ * Synchronises.  NASR_ERR_STATE without a resident batch. */
+int nasr_set_teacher_logits(nasr_handle h, const float* logits);
+/* The same from device to device, without a host synchronisation: the logits of `teacher`'s last forward pass
+ * (nasr_forward*, nasr_greedy_decode*; not a gradient pass, which consumes them) on its own resident batch.  The teacher
+ * is any CTC handle (either family, whole-utterance or chunked) on the same device whose resident batch agrees with h's
+ * in B, logit frames, C and every seq_len[b]; anything else is NASR_ERR_STATE with the reason, nothing changed.  The two
+ * handles may run on different streams: h's stream waits for the teacher's forward pass, and the teacher's stream waits
+ * for the copy before it runs anything enqueued later.  The teacher's step fault word travels with the logits and the
+ * student's step takes it into its own: a teacher whose persistent recurrence gave up makes the student's step void. */
+int nasr_take_teacher_logits(nasr_handle h, nasr_handle teacher);
+/* Synchronises.  The two parts of the last loss pass: *ctc the batch-mean CTC loss, *kd = KD above, or 0 when the term
+ * took no part; with the term, (1 - a) * ctc + a * kd evaluated in double and rounded to float is the published loss. */
+int nasr_get_distill_loss(nasr_handle h, float* ctc, float* kd);
+/* The term's kernels on the caller's logits (host, [Tp,B,C] with C the handle's num_classes; seq_len in logit frames,
+ * each in [1,Tp]): dlogits_out [Tp,B,C] = a tau (q - p) / B and kd_out [B] = kd_b.  weight in [0, 1).  The handle's
+ * resident batch, teacher logits, settings and results stay as they were. */
+int nasr_distill_logits(nasr_handle h, const float* student, const float* teacher, const int32_t* seq_len, int B, int Tp,
+                        float weight, float temperature, float* dlogits_out, double* kd_out);
+
 /* create_metric (networks/tfnetwork.py:66-70): mean over the batch of Levenshtein(hyp, truth)/len(truth)
  * (tf.edit_distance normalize=True, Appendix A.7).  Host code, no GPU work.  hyp_ids [B,hyp_stride],
  * labels [B,Lmax].  An empty truth gives inf for a non-empty hypothesis and 0 otherwise, as TF does. */

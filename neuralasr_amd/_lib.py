@@ -53,6 +53,8 @@ SYMBOLS = [
     'nasr_featurizer_set_noise', 'nasr_featurizer_set_rirs', 'nasr_upload_batch_audio_wave', 'nasr_stage_batch_audio_wave',
     'nasr_augment_audio',
     'nasr_set_chunking', 'nasr_get_chunking',
+    'nasr_set_distill', 'nasr_get_distill', 'nasr_set_teacher_logits', 'nasr_take_teacher_logits', 'nasr_get_distill_loss',
+    'nasr_distill_logits',
 ]
 
 
@@ -288,6 +290,12 @@ def load():
         'nasr_ctc_beam_feed': (c_int, [c_void_p, fp, c_int64, c_int]),
         'nasr_ctc_beam_best': (c_int, [c_void_p, ip, c_int, ip, fp]),
         'nasr_ctc_beam_close': (c_int, [c_void_p]),
+        'nasr_set_distill': (c_int, [H, c_float, c_float]),
+        'nasr_get_distill': (c_int, [H, fp, fp]),
+        'nasr_set_teacher_logits': (c_int, [H, fp]),
+        'nasr_take_teacher_logits': (c_int, [H, H]),
+        'nasr_get_distill_loss': (c_int, [H, fp, fp]),
+        'nasr_distill_logits': (c_int, [H, fp, fp, ip, c_int, c_int, c_float, c_float, fp, POINTER(c_double)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

@@ -18,7 +18,7 @@ KT_HEADERS = [os.path.join(KT_DIR, 'arena.h')]
 # the objects of libnasr.so the kernel tests link against (optim.o also holds test_hook(), which the recurrence launchers call)
 KT_OBJS = ['gemm.o', 'gemm_tph.o', 'optim.o', 'lstm.o', 'lstm_persist.o', 'lstm_wide.o']
 SOURCES = ['gemm.hip', 'gemm_tph.hip', 'lstm.hip', 'rows.hip', 'lstm_persist.hip', 'lstm_wide.hip', 'ctc.hip', 'dense.hip', 'optim.hip', 'nasr_layout.hip',
-           'nasr_rec.hip', 'nasr_batch.hip', 'nasr_pass.hip', 'nasr_stream.hip', 'nasr_lstm.hip', 'nasr_api.hip', 'nasr_comm.hip', 'beam.cpp',
+           'nasr_rec.hip', 'nasr_batch.hip', 'nasr_pass.hip', 'nasr_stream.hip', 'nasr_lstm.hip', 'nasr_api.hip', 'nasr_distill.hip', 'nasr_comm.hip', 'beam.cpp',
            'wavenet.hip', 'nasr_wavenet.hip', 'las.hip', 'las_beam.hip', 'nasr_las.hip', 'mfcc.hip', 'nasr_fz.hip', 'resample.hip', 'wave_aug.hip']
 HEADERS = [os.path.join(CSRC, 'kernels.h'), os.path.join(CSRC, 'dispatch.h'), os.path.join(CSRC, 'lstm_device.h'), os.path.join(CSRC, 'nasr_ctx.h'), os.path.join(CSRC, 'nasr_lstm.h'), os.path.join(CSRC, 'wavenet.h'), os.path.join(CSRC, 'las.h'), os.path.join(CSRC, 'las_beam.h'), os.path.join(CSRC, 'resample.h'), os.path.join(CSRC, 'wave_aug.h'),
            os.path.join(CSRC, 'mfcc.h'), os.path.join(CSRC, 'nasr_fz.h'), os.path.join(HERE, '..', 'include', 'nasr.h')]

@@ -27,7 +27,11 @@ bidirectional network streams (HipNetwork.stream, decode_wav --stream; DESIGN.md
 utterances); unidirectional networks ignore it.  One more optional [Parameters] key, chunk_frames (frames, 0..4096, default
 0 = off), trains and evaluates a bidirectional network as a look-ahead session runs it: windows of
 chunk_frames + stream_lookahead rows, the forward state carried from window to window, the backward direction restarted
-in each; it needs stream_lookahead >= 1, and train, validate, evaluate, decode and align all read it."""
+in each; it needs stream_lookahead >= 1, and train, validate, evaluate, decode and align all read it.  Three more optional
+[Parameters] keys distil a teacher network into the one that is trained (the reference has nothing like
+it): teacher_config (the teacher's config file: its network and model_dir are used, its data sections are not),
+distill_weight (the share of the distillation term in the loss, in (0,1), default 0.5) and distill_temperature (in
+[0.25,16], default 1.0); the last two need teacher_config, only training reads them, and without them nothing changes."""
 import importlib
 import math
 from configparser import ConfigParser, ExtendedInterpolation
@@ -108,6 +112,7 @@ class Config(object):
         self.lm_bonus = float(par['lm_bonus']) if 'lm_bonus' in par else 0.0
         self._read_augment(par, configfile)
         self.max_grad_norm = self._read_max_grad_norm(par, configfile)
+        self._read_distill(par, configfile)
         # the configured batch is per GPU (reference: config.py:35-36)
         self.batch_size *= self.num_gpus if self.num_gpus > 0 else 1
         self.symbols = Symbols(self.label_context, self.sym_file) if isTraining else Symbols(self.label_context)
@@ -191,6 +196,28 @@ class Config(object):
             if len(snr) != 2 or not all(math.isfinite(v) for v in snr) or not snr[0] <= snr[1]:
                 raise ValueError("'noise_snr' must be lo,hi in dB with lo <= hi, not %r, in %s" % (par['noise_snr'], configfile))
             self.noise_snr = snr
+
+    def _read_distill(self, par, configfile):
+        """teacher_config (None: no distillation), distill_weight and distill_temperature"""
+        self.teacher_config = par['teacher_config'].strip() if 'teacher_config' in par else None
+        if self.teacher_config is not None and not self.teacher_config:
+            raise ValueError("'teacher_config' must name the teacher's config file, in %s" % configfile)
+        for key in ('distill_weight', 'distill_temperature'):
+            if key in par and self.teacher_config is None:
+                raise ValueError("'%s' needs 'teacher_config', in %s" % (key, configfile))
+
+        def number(key, default, ok, what):
+            if key not in par:
+                return default
+            try:
+                v = float(par[key].strip())
+            except ValueError:
+                v = float('nan')
+            if not ok(v):       # out of range, NaN, or not a number at all
+                raise ValueError("'%s' must be %s, not %r, in %s" % (key, what, par[key], configfile))
+            return v
+        self.distill_weight = number('distill_weight', 0.5, lambda v: 0.0 < v < 1.0, 'a number in (0,1)')
+        self.distill_temperature = number('distill_temperature', 1.0, lambda v: 0.25 <= v <= 16.0, 'a number in [0.25,16]')
 
     @staticmethod
     def _read_max_grad_norm(par, configfile):

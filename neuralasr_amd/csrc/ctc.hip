@@ -11,7 +11,8 @@
 // utterance, wave 0 = alpha, wave 1 = beta, the lattice column lives in registers (KS >= 2 consecutive states per
 // lane), neighbours come over DPP moves, so a timestep has no barrier and no LDS; emissions are prefetched four
 // frames ahead; (2b) the same recursions engineered (base 2, emissions through an LDS ring), the default;
-// (3) gradient, one wave per (t,b) row, class posteriors summed in a fixed order; (4) forced alignment.
+// (3) gradient, one wave per (t,b) row, class posteriors summed in a fixed order; (4) forced alignment; (5) the
+// distillation term beside the loss: row-wise KL against a teacher's logits and its gradient.
 //
 // The lattice is walked four times - alpha and beta of (2), alpha and beta of (2b), and (4)'s Viterbi pass, which is
 // alpha in (max, +) - and described once, in (0): a lane's states from the label row (lattice_state), a step forward
@@ -916,6 +917,115 @@ int launch_ctc_align(const CtcDims& d, int Fmax, const float* logits, const floa
     else launch(std::false_type{});
   });
   return 0;
+}
+
+// ------------------------------------------------------------------ (5) distillation term
+// One wave per (t,b) row, as (1) and (3): with p = softmax(y / tau) of the teacher's row and q = softmax(z / tau) of the
+// student's over the C real classes, the row's KL(p || q) goes to klrow[row] and gscale * (q - p) to dgrad's row.  Both
+// log-softmaxes are max-subtracted, so the exponents are <= 0 and log p, log q are finite sums: a class with p = 0
+// contributes 0 * (finite), never 0 * log 0, and no inf - inf appears at any magnitude.  expf / logf, not the bare
+// instructions: the pass is a few microseconds either way.  Rows outside the batch (b >= B, t >= seq_len[b]) and the
+// columns from C on get exactly 0.  z == y gives q == p bit for bit (the two are computed by the same expressions).
+__global__ __launch_bounds__(256) void distill_rows_kernel(const float* __restrict__ z, const float* __restrict__ y,
+                                                           const int* __restrict__ seq_len, float* __restrict__ dgrad,
+                                                           float* __restrict__ klrow, float inv_tau, float gscale, int Tp, int B,
+                                                           int Bp, int C, int Cp) {
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  if (row >= Tp * Bp) return;
+  const int t = row / Bp, b = row % Bp;
+  float* d = dgrad + (size_t)row * Cp;
+  if (b >= B || t >= seq_len[b]) {
+    for (int c = lane; c < Cp; c += 64) d[c] = 0.f;
+    if (lane == 0) klrow[row] = 0.f;
+    return;
+  }
+  const float* zr = z + (size_t)row * Cp;
+  const float* yr = y + (size_t)row * Cp;
+  float mz = -INFINITY, my = -INFINITY;
+  for (int c = lane; c < C; c += 64) {
+    mz = fmaxf(mz, zr[c]);
+    my = fmaxf(my, yr[c]);
+  }
+  mz = wave_max(mz);
+  my = wave_max(my);
+  float sz = 0.f, sy = 0.f;
+  for (int c = lane; c < C; c += 64) {
+    sz += expf((zr[c] - mz) * inv_tau);
+    sy += expf((yr[c] - my) * inv_tau);
+  }
+  sz = wave_sum(sz);                                 // fixed xor tree
+  sy = wave_sum(sy);
+  const float lsz = logf(sz), lsy = logf(sy);
+  float kl = 0.f;
+  for (int c = lane; c < Cp; c += 64) {
+    float g = 0.f;
+    if (c < C) {
+      const float uz = (zr[c] - mz) * inv_tau, uy = (yr[c] - my) * inv_tau;
+      const float q = expf(uz) / sz, p = expf(uy) / sy;
+      kl += p * ((uy - lsy) - (uz - lsz));
+      g = gscale * (q - p);
+    }
+    d[c] = g;
+  }
+  kl = wave_sum(kl);
+  if (lane == 0) klrow[row] = kl;
+}
+
+// kd[b] = sum over t < seq_len[b] of klrow[t][b], in fp64 and a fixed order: lane l takes frames l, l + 64, ..., then the
+// wave's xor tree.  One wave per utterance.
+__global__ __launch_bounds__(64) void distill_sum_kernel(const float* __restrict__ klrow, const int* __restrict__ seq_len,
+                                                         double* __restrict__ kd, int Tp, int Bp) {
+  const int b = blockIdx.x, lane = threadIdx.x;
+  const int Tb = min(seq_len[b], Tp);
+  double s = 0.0;
+  for (int t = lane; t < Tb; t += 64) s += (double)klrow[(size_t)t * Bp + b];
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+  if (lane == 0) kd[b] = s;
+}
+
+// parts = {CTC, KD = tau^2 mean_b kd[b]} and loss <- (1 - a) CTC + a KD, from the ROUNDED parts (so they recombine to
+// the published loss exactly); a teacher's fault word is carried into the step's own.
+__global__ void distill_combine_kernel(const double* __restrict__ kd, int B, float a, float tau, float* __restrict__ loss,
+                                       float* __restrict__ parts, const float* __restrict__ teacher_fault,
+                                       float* __restrict__ fault) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  double s = 0.0;
+  for (int b = 0; b < B; ++b) s += kd[b];
+  const float ctc = *loss, kdf = (float)((double)tau * (double)tau * s / (double)B);
+  parts[0] = ctc;
+  parts[1] = kdf;
+  *loss = (float)((1.0 - (double)a) * (double)ctc + (double)a * (double)kdf);
+  if (*teacher_fault != 0.f && *fault == 0.f) *fault = *teacher_fault;
+}
+
+__global__ __launch_bounds__(256) void distill_add_kernel(float4* __restrict__ g, const float4* __restrict__ d, int64_t n4) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n4) return;
+  float4 a = g[i];
+  const float4 b = d[i];
+  a.x += b.x; a.y += b.y; a.z += b.z; a.w += b.w;
+  g[i] = a;
+}
+
+void launch_distill_rows(const CtcDims& d, const float* student, const float* teacher, const int* seq_len, float weight,
+                         float tau, float* dgrad, float* klrow, double* kd, hipStream_t st) {
+  const int rows = d.Tp * d.Bp;
+  hipLaunchKernelGGL(distill_rows_kernel, dim3((rows + 3) / 4), dim3(256), 0, st, student, teacher, seq_len, dgrad, klrow,
+                     1.f / tau, weight * tau / (float)d.B, d.Tp, d.B, d.Bp, d.C, d.Cp);
+  hipLaunchKernelGGL(distill_sum_kernel, dim3(d.B), dim3(64), 0, st, klrow, seq_len, kd, d.Tp, d.Bp);
+}
+
+void launch_distill_combine(const double* kd, int B, float weight, float tau, float* loss, float* parts,
+                            const float* teacher_fault, float* fault, hipStream_t st) {
+  hipLaunchKernelGGL(distill_combine_kernel, dim3(1), dim3(64), 0, st, kd, B, weight, tau, loss, parts, teacher_fault, fault);
+}
+
+void launch_distill_add(const CtcDims& d, float* grad, const float* dgrad, hipStream_t st) {
+  const int64_t n4 = (int64_t)d.Tp * d.Bp * d.Cp / 4;   // Cp is a multiple of 32
+  hipLaunchKernelGGL(distill_add_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st, reinterpret_cast<float4*>(grad),
+                     reinterpret_cast<const float4*>(dgrad), n4);
 }
 
 }  // namespace nasr

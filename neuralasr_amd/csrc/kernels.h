@@ -331,6 +331,16 @@ size_t ctc_align_ws_words(int B, int F, int L);
 int launch_ctc_align(const CtcDims& d, int F, const float* logits, const float* logz, const int* labels, const int* label_len,
                      const int* seq_len, unsigned* bpws, int* path, double* score, hipStream_t st);
 
+// distillation term (ctc.hip (5)) over student and teacher logits [T'*Bp][Cp]; uses d.Tp, B, Bp, C, Cp.
+// rows: dgrad [T'*Bp][Cp] = weight * tau * (q - p) / B (0 on rows outside the batch and columns from C on), klrow [T'*Bp]
+// the rows' KL(p || q), kd [B] their sum per utterance in fp64 and a fixed order.  combine: parts = {CTC = *loss,
+// KD = tau^2 mean_b kd[b]}, *loss = (1 - weight) CTC + weight KD, *fault takes a non-zero *teacher_fault.  add: grad += dgrad.
+void launch_distill_rows(const CtcDims& d, const float* student, const float* teacher, const int* seq_len, float weight,
+                         float tau, float* dgrad, float* klrow, double* kd, hipStream_t st);
+void launch_distill_combine(const double* kd, int B, float weight, float tau, float* loss, float* parts,
+                            const float* teacher_fault, float* fault, hipStream_t st);
+void launch_distill_add(const CtcDims& d, float* grad, const float* dgrad, hipStream_t st);
+
 // ---- optimiser / reductions (optim.hip) ----
 // Adam's step count and the step size derived from it, on the device: a launch whose `fault` word (device float, or NULL)
 // is non-zero is a no-op AND leaves the count alone, so a void step never enters the bias correction.

@@ -307,6 +307,9 @@ int nasr_compute_grads(nasr_handle h) {
   MODEL_CALL(h);
   if (!h) return NASR_ERR_ARG;
   if (!h->resident) return h->fail(NASR_ERR_STATE, "no resident batch");
+  if (h->kd_weight > 0.f && !h->teach_valid)   // a silently plain step would hide a broken training loop
+    return h->fail(NASR_ERR_STATE, "nasr_compute_grads: distillation is on (nasr_set_distill) and the resident batch has no teacher "
+                                   "logits: call nasr_set_teacher_logits or nasr_take_teacher_logits after the upload");
   HIPCHK(h, hipSetDevice(h->device));
   if (h->profiling && !h->window_open) {  // a fresh timing window per step when the batch stays resident
     h->ev_used = 0;

@@ -511,6 +511,7 @@ int slot_commit(nasr_ctx* h, BatchSlot* s) {
   h->have_grads = false;
   h->have_fwd = false;
   h->have_decoded = false;
+  h->teach_valid = false;   // teacher logits belong to the batch they were given for
   return NASR_OK;
 }
 

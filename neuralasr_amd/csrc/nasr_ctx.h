@@ -13,6 +13,7 @@
 //   nasr_stream.hip  (L) streaming sessions (nasr_stream_*): recurrent state that survives between chunks
 //   nasr_api.hip     the C ABI entry points that serve every family (and nasr_create's reading of the environment); what the
 //                    create calls share (handle_open, alloc_param_buffers, handle_finish)
+//   nasr_distill.hip distillation beside the CTC loss (nasr_set_distill, teacher logits from another handle); both CTC families
 //   nasr_comm.hip    RCCL bound with dlopen: nasr_comm_*
 //   nasr_wavenet.hip the WaveNet handle (nasr_create_wavenet): its layout, buffers, BN state and pass
 //   nasr_las.hip     the LAS handle (nasr_create_las): its layout, buffers, sampling state and pass
@@ -296,6 +297,16 @@ struct nasr_ctx {
   // back-pointers that do not fit in LDS, path and score; and for nasr_ctc_align_logits the caller's logits and labels
   DevBuf al_logz, al_bp, al_path, al_score, al_logits, al_meta;
 
+  // distillation (nasr_set_distill; kd_weight = 0 = off: nothing below is allocated or launched).
+  // teach: the teacher's logits of the resident batch [Tp*Bp][Cp], never written by a step; kd_grad: the term's logit
+  // gradient from the loss pass until the backward pass adds it; kd_rows / kd_sum: the rows' KL and its sums per
+  // utterance (double [B]); kd_parts: {CTC, KD} of the last loss pass with the term, then the teacher's fault word.
+  float kd_weight = 0.f, kd_tau = 1.f;
+  bool teach_valid = false;                  // teach holds logits for the resident batch (slot_commit drops them)
+  bool kd_live = false;                      // the last loss pass added the term
+  DevBuf teach, kd_grad, kd_rows, kd_sum, kd_parts;
+  Event ev_teach_ready, ev_teach_taken;      // nasr_take_teacher_logits: the order between the two handles' streams
+
   bool graph_mode = true;                    // nasr_set_graph_mode: read by every family's pass (the graph cache: LstmState)
   bool step_decode = false, step_logits = false, have_decoded = false;   // nasr_set_step_decode: any bit / bit 1
   bool step_greedy = false;                                              // ... bit 0
@@ -490,6 +501,11 @@ int loss_pass(nasr_ctx* h, bool training);
 CtcDims ctc_dims(nasr_ctx* h);
 int ctc_forward(nasr_ctx* h);
 int backward(nasr_ctx* h);
+// the distillation term is part of the resident batch's loss and gradient: a weight > 0 and teacher logits for this batch
+inline bool distill_on(const nasr_ctx* h) { return h->kd_weight > 0.f && h->resident && h->teach_valid; }
+// both CTC families' backward passes start here: the logits, in place, become d(loss)/dlogits - the CTC gradient, and
+// with the term on (1 - weight) times it plus what the loss pass left in kd_grad
+int logit_grads(nasr_ctx* h);
 // rows >= 0: the first `rows` logit frames only
 int fetch_logits(nasr_ctx* h, float* logits_out, int rows = -1);
 

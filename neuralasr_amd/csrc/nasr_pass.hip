@@ -348,6 +348,20 @@ int ctc_forward(nasr_ctx* h) {
                         h->seq_p, h->alpha.as<float>(), h->beta.as<float>(), h->aoff.as<double>(),
                         h->boff.as<double>(), h->nll.as<float>(), h->logp.as<double>(), h->st);
   launch_mean(h->nll.as<float>(), h->B, h->loss.as<float>(), h->st);
+  // the distillation term, while the student's logits are still logits: its gradient waits in kd_grad
+  // for logit_grads, the loss becomes the combined one before anything publishes it
+  h->kd_live = distill_on(h);
+  if (h->kd_live) {
+    const size_t rows = (size_t)h->Tp * h->Bp;
+    bool grew = false;
+    if (!h->kd_grad.ensure(rows * h->Cp * 4, &grew) || !h->kd_rows.ensure(rows * 4, &grew) ||
+        !h->kd_sum.ensure((size_t)h->Bp * 8, &grew))
+      return h->fail(NASR_ERR_HIP, "hipMalloc of the distillation term's buffers failed");
+    launch_distill_rows(d, h->logits.as<float>(), h->teach.as<float>(), h->seq_p, h->kd_weight, h->kd_tau, h->kd_grad.as<float>(),
+                        h->kd_rows.as<float>(), h->kd_sum.as<double>(), h->st);
+    launch_distill_combine(h->kd_sum.as<double>(), h->B, h->kd_weight, h->kd_tau, h->loss.as<float>(), h->kd_parts.as<float>(),
+                           h->kd_parts.as<float>() + 2, h->Gbase, h->st);
+  }
   if (h->step_decode) {
     if (h->step_greedy)
       launch_greedy(d, h->logits.as<float>(), h->seq_p, h->amax.as<int>(), h->ids.as<int>(), h->lens.as<int>(), h->st);
@@ -491,6 +505,19 @@ int backward(nasr_ctx* h) {
   }
 }
 
+int logit_grads(nasr_ctx* h) {
+  PhaseScope ps(h, PH_PROJCTC);
+  const CtcDims d = ctc_dims(h);
+  const float scale = h->kd_live ? (1.f - h->kd_weight) / (float)h->B : 1.f / (float)h->B;
+  launch_ctc_grad(d, h->logits.as<float>(), h->logz.as<float>(), h->lablen_p, h->seq_p, h->cstart_p, h->cpos_p,
+                  h->alpha.as<float>(), h->beta.as<float>(), h->aoff.as<double>(), h->boff.as<double>(), h->logp.as<double>(),
+                  scale, h->st);
+  if (h->kd_live) launch_distill_add(d, h->logits.as<float>(), h->kd_grad.as<float>(), h->st);
+  HIPCHK(h, hipGetLastError());
+  h->have_fwd = false;   // the logits are gone (nasr_take_teacher_logits asks)
+  return NASR_OK;
+}
+
 int lstm_backward(nasr_ctx* h) {
   LstmState* const ls = h->lstm.get();
   const int Bp = h->Bp, T = h->T, D = ls->D, Hp = ls->Hp;
@@ -502,14 +529,7 @@ int lstm_backward(nasr_ctx* h) {
     HIPCHK(h, hipMemsetAsync(ls->pctl + 1 + ls->L, 0, (size_t)ls->L * sizeof(PersistCtl), h->st));
     HIPCHK(h, hipMemsetAsync(ls->xchb, 0, (size_t)ls->L * persist_px_bytes(), h->st));   // epoch 0 everywhere (lstm_persist.hip)
   }
-  {
-    PhaseScope ps(h, PH_PROJCTC);
-    const CtcDims d = ctc_dims(h);
-    launch_ctc_grad(d, h->logits.as<float>(), h->logz.as<float>(), h->lablen_p, h->seq_p,
-                    h->cstart_p, h->cpos_p, h->alpha.as<float>(), h->beta.as<float>(),
-                    h->aoff.as<double>(), h->boff.as<double>(), h->logp.as<double>(), 1.f / (float)h->B, h->st);
-    HIPCHK(h, hipGetLastError());
-  }
+  if (int rc = logit_grads(h)) return rc;
   {
     PhaseScope ps(h, PH_PROJB);
     // dW = gather(out)^T dlogits

@@ -205,14 +205,7 @@ int wn_backward(nasr_ctx* h) {
   float* G = h->G;
   const float eps = w.eps;
   hipStream_t st = h->st;
-  {
-    PhaseScope ps(h, PH_PROJCTC);
-    const CtcDims d = ctc_dims(h);
-    launch_ctc_grad(d, h->logits.as<float>(), h->logz.as<float>(), h->lablen_p, h->seq_p, h->cstart_p, h->cpos_p,
-                    h->alpha.as<float>(), h->beta.as<float>(), h->aoff.as<double>(), h->boff.as<double>(),
-                    h->logp.as<double>(), 1.f / (float)h->B, st);
-    HIPCHK(h, hipGetLastError());
-  }
+  if (int rc = logit_grads(h)) return rc;
   PhaseScope ps(h, PH_WGRAD);
   // batch-norm backward of site s over y [R][nch] with dy (the gradient wrt its output, activation derivative applied)
   auto bn_bwd = [&](int s, const float* y, float* dy, int nch) {

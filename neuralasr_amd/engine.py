@@ -357,8 +357,12 @@ class Engine:
         rc, seq, T = self._audio_call(fn, featurizer, audios, labels, label_len, rates, *tail, byref(ticket))
         return seq, T, self._ticket(rc, ticket)
 
-    def forward_resident(self, B, T):
-        """logits [T',B,C] of the resident batch (forward() without its upload)"""
+    def forward_resident(self, B, T, fetch=True):
+        """logits [T',B,C] of the resident batch (forward() without its upload); fetch=False: the pass alone, they stay on
+        the device (take_teacher_logits() reads them there) and None is returned"""
+        if not fetch:
+            self._ck(self.lib.nasr_forward_resident(self.h, None))
+            return None
         out = np.empty((self.logit_frames(T), B, self.num_classes), np.float32)
         self._ck(self.lib.nasr_forward_resident(self.h, _fp(out)))
         return out
@@ -453,6 +457,57 @@ class Engine:
         c, r = c_int(), c_int()
         self._ck(self.lib.nasr_get_chunking(self.h, byref(c), byref(r)))
         return int(c.value), int(r.value)
+
+    # ------------------------------------------------------------------ distillation
+    def set_distill(self, weight, temperature=1.0):
+        """Teacher-student distillation beside the CTC loss (include/nasr.h, nasr_set_distill): loss = (1 - weight) CTC +
+        weight KD against the teacher logits of the resident batch.  weight = 0: off, the step of an engine that never
+        heard of it.  The library's refusals (LAS, stack_reshape, values out of range) raise with its reason."""
+        self._ck(self.lib.nasr_set_distill(self.h, float(weight), float(temperature)))
+
+    @property
+    def distill(self):
+        """(weight, temperature) as set_distill() set them; weight 0.0 = off"""
+        w, t = c_float(), c_float()
+        self._ck(self.lib.nasr_get_distill(self.h, byref(w), byref(t)))
+        return float(w.value), float(t.value)
+
+    def set_teacher_logits(self, logits_tm):
+        """teacher logits [T',B,C] (as forward() returns them) for the resident batch; the next upload drops them"""
+        logits = _f32(logits_tm)
+        rb, rt = ctypes.c_int(), ctypes.c_int()
+        self._ck(self.lib.nasr_resident_shape(self.h, byref(rb), byref(rt)))
+        if rb.value and logits.shape != (self.logit_frames(rt.value), rb.value, self.num_classes):
+            raise ValueError('set_teacher_logits: logits %s, the resident batch needs %s'
+                             % (logits.shape, (self.logit_frames(rt.value), rb.value, self.num_classes)))
+        self._ck(self.lib.nasr_set_teacher_logits(self.h, _fp(logits)))
+
+    def take_teacher_logits(self, teacher):
+        """the same from `teacher`'s last forward pass on its own resident batch, device to device, no host wait"""
+        self._ck(self.lib.nasr_take_teacher_logits(self.h, teacher.h))
+
+    def distill_loss(self):
+        """(ctc, kd) of the last loss pass: the batch-mean CTC loss and the distillation term (0.0 when it took no part)"""
+        c, k = c_float(), c_float()
+        self._ck(self.lib.nasr_get_distill_loss(self.h, byref(c), byref(k)))
+        return float(c.value), float(k.value)
+
+    def distill_logits(self, student_tm, teacher_tm, seq_len, weight, temperature, out=None, kd_out=None):
+        """The term's kernels on the caller's logits [T',B,C] (C = this engine's num_classes; seq_len in logit frames):
+        (weight * temperature * (q - p) / B as [T',B,C] float32, kd_b as [B] float64).  out / kd_out: arrays to write into
+        (C-contiguous, at least that large).  The engine's state is untouched."""
+        z, y = _f32(student_tm), _f32(teacher_tm)
+        assert z.ndim == 3 and z.shape == y.shape and z.shape[2] == self.num_classes, 'logits must be [T\',B,num_classes]'
+        Tp, B, _ = z.shape
+        seq = _i32(np.asarray([int(x) for x in seq_len])).ravel()
+        assert seq.size == B
+        d = np.empty(z.shape, np.float32) if out is None else out
+        kd = np.empty(B, np.float64) if kd_out is None else kd_out
+        assert d.dtype == np.float32 and d.flags.c_contiguous and d.size >= z.size
+        assert kd.dtype == np.float64 and kd.flags.c_contiguous and kd.size >= B
+        self._ck(self.lib.nasr_distill_logits(self.h, _fp(z), _fp(y), _ip(seq), B, Tp, float(weight), float(temperature),
+                                              _fp(d), kd.ctypes.data_as(POINTER(c_double))))
+        return d, kd
 
     @property
     def grad_clip(self):

@@ -84,8 +84,9 @@ class HipNetwork(Network):
         self.num_classes = config.symbols.counter
         self.coll = Collective()
         device = int(os.environ.get('LOCAL_RANK', '0')) if self.coll.world > 1 else 0
-        stream = None
-        if self.coll.world > 1:
+        # (a teacher network, DESIGN.md §22, is given the stream of the network it teaches)
+        stream = getattr(config, 'engine_stream', None)
+        if stream is None and self.coll.world > 1:
             # a dedicated non-default torch stream, made current: the engine launches on it and the RCCL
             # all-reduce is ordered against it (the legacy default stream is neither capturable nor shared)
             import torch
@@ -93,6 +94,12 @@ class HipNetwork(Network):
             self._torch_stream = torch.cuda.Stream(device=device)
             torch.cuda.set_stream(self._torch_stream)
             stream = self._torch_stream.cuda_stream
+        elif stream is None and fortraining and getattr(config, 'teacher_config', None):
+            # student and teacher share one stream (_load_teacher says why): one that has a name outside the library
+            import torch
+            self._torch_stream = torch.cuda.Stream(device=device)
+            stream = self._torch_stream.cuda_stream
+        self._stream = stream
         self.logger.info('Initializing network for %s.' % ('training' if fortraining else 'inference'))
         self._device = device
         self._featurizer = None                 # the front end of the *_audio calls, made at the first of them
@@ -117,9 +124,65 @@ class HipNetwork(Network):
         self._lm = None                         # config.lm_file's model, loaded at the first evaluate / decode
         self.global_step = self.config.start_step
         self.load_checkpoint(self.global_step if fortraining else 1, self.config.model_dir)
+        self._teacher = None                    # config.teacher_config's network: every training batch goes to it too
+        if fortraining and getattr(config, 'teacher_config', None):
+            self.engine.set_distill(config.distill_weight, config.distill_temperature)     # (the library refuses a student that cannot)
+            self._teacher = self._load_teacher()
         if fortraining and self.coll.rank == 0:
             self.write_config()
             self.config.symbols.write(os.path.join(self.config.model_dir, os.path.basename(self.config.sym_file)))
+
+    # ------------------------------------------------------------------ distillation
+    TEACHER_MUST_MATCH = ('feature_size', 'samplerate', 'numcep', 'numcontext', 'features', 'deltas', 'normalization')
+
+    def _load_teacher(self):
+        """config.teacher_config's network, built for inference on this network's device from its latest checkpoint (none is
+        an error: a random teacher is a mistake).  It must read what the student reads and write what the student writes:
+        the same features and the same symbol table."""
+        from ..config import Config, network_class
+        from ..engine import LasEngine
+        cfg = self.config
+        tcfg = Config(cfg.teacher_config, isTraining=True)      # (isTraining: the symbol table is read from its sym_file)
+        if tcfg.symbols.sym_to_id != cfg.symbols.sym_to_id:
+            raise ValueError("teacher_config %s: 'symbols' differ from the student's: the teacher's posteriors are over another "
+                             'table (%d symbols, the student has %d)' % (cfg.teacher_config, tcfg.symbols.counter, cfg.symbols.counter))
+        for key in self.TEACHER_MUST_MATCH:
+            if getattr(tcfg, key) != getattr(cfg, key):
+                raise ValueError("teacher_config %s: '%s' is %r, the student's is %r: both must see the same features"
+                                 % (cfg.teacher_config, key, getattr(tcfg, key), getattr(cfg, key)))
+        # On the student's stream: the teacher's forward pass then runs between two of the student's steps, never beside
+        # one.  On a stream of its own it would meet the step before, which train() leaves running on the device, and two
+        # persistent recurrences that each want every compute unit can take each other's places: one that gives up is a
+        # void step, and the per-step kernels for the next 200 (DESIGN.md §22).
+        tcfg.engine_stream = self._stream
+        teacher = network_class(tcfg.network)(tcfg, fortraining=False)     # (inference: restores the latest checkpoint)
+        why = None
+        if isinstance(teacher.engine, LasEngine):
+            why = 'a LAS network has no CTC posteriors to distil'
+        elif teacher.engine.logit_frames(1) != 1:
+            why = 'a stack_reshape network has no logit frames to compare'
+        if why:
+            teacher.engine.close()
+            raise ValueError("teacher_config %s: 'network' %s cannot teach: %s" % (cfg.teacher_config, tcfg.network, why))
+        teacher.featurizer = self.featurizer                    # one front end: the same audio gives both the same features
+        return teacher
+
+    def _feed_teacher(self, f, s):
+        """The shard that has just become the student's resident batch, by the same route to the teacher (uploaded the
+        synchronous way, also where the student committed a staged batch): the same features, or the same audio with the
+        same augmentation draws; then the teacher's forward pass, and its logits device to device."""
+        t = self._teacher
+        if t is None:
+            return
+
+        def run():
+            if isinstance(f, AudioBatch):
+                t._upload_audio(f, None, None, f.aug(self.config.numcep), self._wave(f))
+            else:
+                t._upload(f, None, s, None)
+            t.engine.forward_resident(len(s), np.shape(f)[1], fetch=False)
+        self._retry_aborted(run)
+        self.engine.take_teacher_logits(t.engine)
 
     # the two hooks a model family overrides (DeepSpeech does): how the engine is shaped, how variables start
     def make_engine(self, config, device, stream):
@@ -375,6 +438,7 @@ class HipNetwork(Network):
             self.engine.commit_batch(ticket)
         else:
             self._upload(f, l, s, ll)
+        self._feed_teacher(f, s)
         beam = self.train_ler_decoder == 'beam'
         self.engine.set_step_decode(True, logits=beam, greedy=not beam)     # (the beam search reads the logits; no greedy pass then)
         self.engine.compute_grads()
@@ -526,6 +590,7 @@ class HipNetwork(Network):
             for k in mine:
                 f, l, s, ll = take_shard(mfccs, labels, seq_len, labels_len, n, k)
                 self._upload(f, l, s, ll)
+                self._feed_teacher(f, s)
                 beam = self.train_ler_decoder == 'beam'
                 self.engine.set_step_decode(True, logits=beam, greedy=not beam)
                 self.engine.compute_grads()

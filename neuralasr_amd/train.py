@@ -1,6 +1,7 @@
 """Training loop (reference: train.py:14-63): epochs x batches, cumulative wall time, checkpoint + log +
 one validation batch every report_step, same log-line formats (plus one "Grad:" line behind every "Step:" line when the
-config's max_grad_norm switches gradient clipping on).
+config's max_grad_norm switches gradient clipping on, and one "Distill:" line when its teacher_config switches
+distillation on).
 
   python -m neuralasr_amd.train <config>
   python -m neuralasr_amd.train <config> --from-audio     # from the [MFCC Featurizer] input CSV: features made on the GPU per batch
@@ -64,6 +65,10 @@ def train_model(dataTrain, datavalid, config, prefetch=2):
                 if gc['skipped'] > 0:
                     logger.warning('%d optimiser step(s) skipped: their gradient had a non-finite norm (parameters and Adam '
                                    'state were left as they were)' % gc['skipped'])
+            if getattr(config, 'teacher_config', None):
+                # teacher_config: the two parts of the last step's loss, read behind the same wait
+                ctc, kd = network.engine.distill_loss()
+                logger.info('Distill: ctc = %.4f' % ctc + ', kd = %.4f' % kd)
             if datavalid:
                 if not datavalid.has_more_batches():
                     datavalid.reset_epoch()
