@@ -106,6 +106,9 @@ int nasr_get_params(nasr_handle h, float* flat, int64_t n);
 int nasr_set_adam_state(nasr_handle h, const float* m, const float* v, int64_t n, int64_t step);
 int nasr_get_adam_state(nasr_handle h, float* m, float* v, int64_t n, int64_t* step);
 int nasr_set_learning_rate(nasr_handle h, float lr);
+/* the step size the next nasr_apply_adam is launched with: the create call's, or what nasr_set_learning_rate set last (a
+ * launch argument: a step already enqueued keeps its own) */
+int nasr_get_learning_rate(nasr_handle h, float* lr);
 
 /* ---- one-call entry points over host buffers -------------------------------------------
  * nasr_train_step replaces sess.run([optimizer, loss]) of TensorFlowNetwork.train
@@ -315,6 +318,31 @@ typedef struct {
 int nasr_set_grad_clip(nasr_handle h, float max_norm);
 int nasr_get_grad_clip(nasr_handle h, float* max_norm);
 int nasr_get_grad_clip_stats(nasr_handle h, nasr_clip_stats* out, int reset);
+/* Parameter averaging (not part of the reference, which checkpoints and decodes the last iterate only):
+ * tf.train.ExponentialMovingAverage(decay, num_updates) of every trainable variable.  With decay in (0,1) the handle holds a
+ * second parameter image E, and every nasr_apply_adam that is applied updates it inside the Adam sweep, from the
+ * parameters P that sweep has just written:
+ *   E <- E + (1 - d_n)(P - E),  d_n = min(decay, (1 + n) / (10 + n)),  n = updates applied so far, then n + 1
+ * (d_n and 1 - d_n in double on the device, rounded to fp32; per element e = fma(1 - d_n, p - e, e)).  A void step (fault
+ * word set) and a skipped step (non-finite norm under nasr_set_grad_clip) leave E and n as they leave P, M, V and Adam's
+ * count.  P, M, V get the bits they get without averaging.
+ * nasr_set_ema: 0 = off (the default; frees E: nasr_apply_adam launches exactly what it launched before).  The first call
+ * with a decay in (0,1) allocates E, copies P into it (TF's initial shadow value) and sets n = 0; a later one only changes
+ * the decay.  Anything else: NASR_ERR_ARG.  nasr_set_params does not touch E.
+ * nasr_get_ema: the decay (0 = off), n (synchronises; 0 when off) and whether the average is live (below); each may be NULL. */
+int nasr_set_ema(nasr_handle h, float decay);
+int nasr_get_ema(nasr_handle h, float* decay, int64_t* updates, int* live);
+/* E and n out of / into the handle, in the TF variable order of nasr_get_params / nasr_set_params (a checkpoint's view);
+ * updates may be NULL in the getter.  NASR_ERR_STATE while averaging is off. */
+int nasr_get_ema_state(nasr_handle h, float* flat, int64_t n, int64_t* updates);
+int nasr_set_ema_state(nasr_handle h, const float* flat, int64_t n, int64_t updates);
+/* Exchanges the CONTENTS of P and E on the handle's stream and rebuilds the operand images derived from P, so that every
+ * forward-only call (nasr_forward*, nasr_loss*, nasr_greedy_decode*, nasr_ctc_align*, nasr_stream_feed*, the beam searches,
+ * a distillation teacher's pass) runs on the average; nasr_get_params then returns the average and nasr_get_ema_state the
+ * training parameters.  While the average is live (an odd number of swaps) nasr_compute_grads, nasr_apply_adam,
+ * nasr_train_step, nasr_set_ema_state and nasr_set_ema(h, 0) return NASR_ERR_STATE and name themselves.  A second swap puts
+ * P, E and every derived image back bit for bit.  NASR_ERR_STATE while averaging is off. */
+int nasr_ema_swap(nasr_handle h);
 /* Diagnostics - what ONE GPU can show of a collective that co-runs with the step (average_gradients moved under the
  * backward pass, tfnetwork.py:72-86): waits on `hip_stream` for bucket i like nasr_grad_bucket_wait, then launches there a
  * kernel shaped like a ring all-reduce step over that bucket - nblocks workgroups of 256 threads, each sweeping its slice

@@ -55,6 +55,7 @@ SYMBOLS = [
     'nasr_set_chunking', 'nasr_get_chunking',
     'nasr_set_distill', 'nasr_get_distill', 'nasr_set_teacher_logits', 'nasr_take_teacher_logits', 'nasr_get_distill_loss',
     'nasr_distill_logits',
+    'nasr_get_learning_rate', 'nasr_set_ema', 'nasr_get_ema', 'nasr_get_ema_state', 'nasr_set_ema_state', 'nasr_ema_swap',
 ]
 
 
@@ -157,6 +158,12 @@ def load():
         'nasr_set_adam_state': (c_int, [H, fp, fp, c_int64, c_int64]),
         'nasr_get_adam_state': (c_int, [H, fp, fp, c_int64, POINTER(c_int64)]),
         'nasr_set_learning_rate': (c_int, [H, c_float]),
+        'nasr_get_learning_rate': (c_int, [H, fp]),
+        'nasr_set_ema': (c_int, [H, c_float]),
+        'nasr_get_ema': (c_int, [H, fp, POINTER(c_int64), POINTER(c_int)]),
+        'nasr_get_ema_state': (c_int, [H, fp, c_int64, POINTER(c_int64)]),
+        'nasr_set_ema_state': (c_int, [H, fp, c_int64, c_int64]),
+        'nasr_ema_swap': (c_int, [H]),
         'nasr_train_step': (c_int, [H, fp, ip, ip, ip, c_int, c_int, c_int, fp]),
         'nasr_forward': (c_int, [H, fp, ip, c_int, c_int, fp]),
         'nasr_logit_frames': (c_int, [H, c_int]),

@@ -3,6 +3,7 @@ no aligner).  `python -m neuralasr_amd.align CONFIG WAV TXT`: the transcript bec
 audio_dataset make them (read_label_text, label_context n-grams, the start and end markers) against the model's symbol
 table - a symbol the table does not hold is an error, nothing is inserted; the network's align() / align_audio() finds the
 best CTC path on the GPU; the output is one log line per symbol, `sym start end`, and the path's log-probability.
+With ema_decay in the config the network loads the checkpoint's averaged parameters.
 
 Times are seconds, frame x 0.01 (the front end's winstep), when the network has one logit frame per feature frame.  The
 literal BiLstmCTCNet (merge 'stack_reshape') has 2T logit frames that its reshape of the (fw, bw) tuple scrambles over

@@ -31,10 +31,18 @@ in each; it needs stream_lookahead >= 1, and train, validate, evaluate, decode a
 [Parameters] keys distil a teacher network into the one that is trained (the reference has nothing like
 it): teacher_config (the teacher's config file: its network and model_dir are used, its data sections are not),
 distill_weight (the share of the distillation term in the loss, in (0,1), default 0.5) and distill_temperature (in
-[0.25,16], default 1.0); the last two need teacher_config, only training reads them, and without them nothing changes."""
+[0.25,16], default 1.0); the last two need teacher_config, only training reads them, and without them nothing changes.  Five more optional
+[Parameters] keys shape the optimiser (the reference trains at a fixed learningrate and keeps the last
+iterate): ema_decay (in (0,1); default off) keeps tf.train.ExponentialMovingAverage's average of the parameters, which
+validate / evaluate / decode / align then run on and which a network built for inference loads from the checkpoint;
+lr_warmup_steps (>= 0, default 0), lr_decay_steps (>= 0, 0 = no decay), lr_decay_rate (in (0,1], default 1) and lr_staircase
+(0 or 1) make the step size of global step s learningrate * min(1, s / warmup) * rate ** (max(0, s - warmup) / decay_steps);
+without them nothing changes."""
 import importlib
 import math
 from configparser import ConfigParser, ExtendedInterpolation
+
+import numpy as np
 
 from .logger import get_logger
 from .symbols import Symbols
@@ -113,6 +121,7 @@ class Config(object):
         self._read_augment(par, configfile)
         self.max_grad_norm = self._read_max_grad_norm(par, configfile)
         self._read_distill(par, configfile)
+        self._read_optimiser(par, configfile)
         # the configured batch is per GPU (reference: config.py:35-36)
         self.batch_size *= self.num_gpus if self.num_gpus > 0 else 1
         self.symbols = Symbols(self.label_context, self.sym_file) if isTraining else Symbols(self.label_context)
@@ -149,17 +158,47 @@ class Config(object):
             raise ValueError("'normalization=causal' needs deltas=0 (the delta columns look ahead; DESIGN.md §16), in %s"
                              % configfile)
 
+    @staticmethod
+    def _number(par, configfile, key, kind, default, lo, hi, what, open_lo=False, open_hi=False):
+        """an optional numeric key of [Parameters] in [lo,hi] (open_lo / open_hi: that end excluded), or its default"""
+        if key not in par:
+            return default
+        try:
+            v = kind(par[key].strip())
+        except ValueError:
+            v = None
+        if v is None or not lo <= v <= hi or (open_lo and v == lo) or (open_hi and v == hi):
+            raise ValueError("'%s' must be %s, not %r, in %s" % (key, what, par[key], configfile))
+        return v
+
+    def _read_optimiser(self, par, configfile):
+        """ema_decay (0.0: no parameter averaging) and the learning-rate schedule's keys; all optional"""
+        def number(*a, **k):
+            return self._number(par, configfile, *a, **k)
+        big = 1 << 62
+        self.ema_decay = number('ema_decay', float, 0.0, 0.0, 1.0, 'a number in (0,1)', open_lo=True, open_hi=True)
+        self.lr_warmup_steps = number('lr_warmup_steps', int, 0, 0, big, 'an integer >= 0')
+        self.lr_decay_steps = number('lr_decay_steps', int, 0, 0, big, 'an integer >= 0')
+        self.lr_decay_rate = number('lr_decay_rate', float, 1.0, 0.0, 1.0, 'a number in (0,1]', open_lo=True)
+        self.lr_staircase = number('lr_staircase', int, 0, 0, 1, '0 or 1')
+        # some schedule key is in the file: train logs an "LR:" line behind each "Step:" line
+        self.lr_schedule_on = any(k in par for k in ('lr_warmup_steps', 'lr_decay_steps', 'lr_decay_rate', 'lr_staircase'))
+
+    def learning_rate_at(self, step):
+        """The step size of optimiser step `step` (the 1-based global_step about to be applied): tf.train.exponential_decay
+        behind a linear warm-up, in float64, rounded to fp32.
+          lr(s) = learningrate * min(1, s / warmup) * rate ** (max(0, s - warmup) / decay_steps)   (staircase: floored)"""
+        lr = float(self.learningrate)
+        if self.lr_warmup_steps > 0:
+            lr *= min(1.0, step / float(self.lr_warmup_steps))
+        if self.lr_decay_steps > 0:
+            e = max(0, step - self.lr_warmup_steps) / float(self.lr_decay_steps)
+            lr *= float(self.lr_decay_rate) ** (math.floor(e) if self.lr_staircase else e)
+        return float(np.float32(lr))
+
     def _read_augment(self, par, configfile):
-        def number(key, kind, default, lo, hi, what):
-            if key not in par:
-                return default
-            try:
-                v = kind(par[key].strip())
-            except ValueError:
-                v = None
-            if v is None or not lo <= v <= hi:
-                raise ValueError("'%s' must be %s, not %r, in %s" % (key, what, par[key], configfile))
-            return v
+        def number(*a):
+            return self._number(par, configfile, *a)
         big = 1 << 62
         self.spec_time_masks = number('spec_time_masks', int, 0, 0, 8, 'an integer in [0,8]')
         self.spec_time_width = number('spec_time_width', int, 0, 0, big, 'an integer >= 0')

@@ -345,8 +345,14 @@ void launch_distill_add(const CtcDims& d, float* grad, const float* dgrad, hipSt
 // Adam's step count and the step size derived from it, on the device: a launch whose `fault` word (device float, or NULL)
 // is non-zero is a no-op AND leaves the count alone, so a void step never enters the bias correction.
 struct AdamDev { long long step; float lr_t; int applied; };
+// Parameter averaging (nasr_set_ema): the number of updates applied so far and omd = (float)(1 - d_n) of the step in flight,
+// d_n = min(decay, (1 + n) / (10 + n)), advanced on the device wherever Adam's count is - never by a void or skipped step.
+struct EmaDev { long long updates; float omd; };
+constexpr int ADAM_MAX_BLOCKS = 2048;   // the grid of the Adam and swap sweeps; above 2048 * 256 float4s their loops go round again
+// e: the average of p, updated in the same sweep from `ema` and `decay`, or NULL: the sweep without it
 void launch_adam(float* p, float* m, float* v, const float* g, int64_t n, AdamDev* state, float lr, float beta1, float beta2,
-                 float eps, float gscale, const float* fault, hipStream_t st);
+                 float eps, float gscale, const float* fault, float* e, EmaDev* ema, float decay, hipStream_t st);
+void launch_swap16(float* a, float* b, int64_t n, hipStream_t st);   // the contents of a and b change places (n % 4 == 0)
 // Global-norm clipping (nasr_set_grad_clip): what the second stage of the norm decides for the step, on the device.  s is
 // the multiplier the Adam pass reads (grad_scale * coef); skip = 1: the norm was not finite, the step touches nothing.
 // window_max_norm .. skipped are the window nasr_get_grad_clip_stats(reset) clears.
@@ -356,7 +362,7 @@ int grad_sumsq_blocks(int64_t n);   // workgroups (= partial sums) of the norm's
 // launch_adam behind the norm of g: `part` holds GRAD_SUMSQ_MAX_BLOCKS doubles.  max_norm > 0 or +inf.
 void launch_adam_clipped(float* p, float* m, float* v, const float* g, int64_t n, AdamDev* state, ClipDev* clip, double* part,
                          float lr, float beta1, float beta2, float eps, float gscale, float max_norm, const float* fault,
-                         hipStream_t st);
+                         float* e, EmaDev* ema, float decay, hipStream_t st);
 // out[n] = sum_r M[r*ld + n], deterministic two-stage; ws holds 32*N floats
 void launch_colsum(const float* M, int R, int N, int ld, float* out, float* ws, hipStream_t st);
 void launch_colsum_parts(const float* part, int nparts, int N, float* out, hipStream_t st);   // out[n] = sum_k part[k][n]

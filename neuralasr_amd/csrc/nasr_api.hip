@@ -10,6 +10,14 @@ using namespace nasr;
 using namespace nasr_impl;
 
 namespace {
+// the first check of a call that trains: while nasr_ema_swap has the average in P's place there is nothing to train
+#define NOT_EMA_LIVE(h)                                                                                              \
+  do {                                                                                                               \
+    if ((h)->ema_live)                                                                                               \
+      return (h)->fail(NASR_ERR_STATE, std::string(__func__) + ": the parameters hold their average (nasr_ema_swap); " \
+                                                               "swap back first");                                   \
+  } while (0)
+
 int settle_end(nasr_ctx* h, nasr_ctx::StepEnd& e, int* void_out) {
   // the end of THAT step only
   if (!wait_stamp(e.stamp, e.seq, 60.0)) return h->fail(NASR_ERR_HIP, "nasr_settle_step: the step did not end within 60 s");
@@ -233,6 +241,99 @@ int nasr_set_learning_rate(nasr_handle h, float lr) {
   return NASR_OK;
 }
 
+int nasr_get_learning_rate(nasr_handle h, float* lr) {
+  MODEL_CALL(h);
+  if (!h || !lr) return NASR_ERR_ARG;
+  *lr = h->lr;
+  return NASR_OK;
+}
+
+// ---- parameter averaging (optim.hip) ---------------------------------------------------------------
+int nasr_set_ema(nasr_handle h, float decay) {
+  MODEL_CALL(h);
+  if (!h) return NASR_ERR_ARG;
+  if (!(decay >= 0.f && decay < 1.f)) return h->fail(NASR_ERR_ARG, "nasr_set_ema: decay must be 0 (off) or a number in (0,1)");
+  HIPCHK(h, hipSetDevice(h->device));
+  if (decay == 0.f) {
+    NOT_EMA_LIVE(h);
+    if (h->E) {
+      HIPCHK(h, hipStreamSynchronize(h->st));   // a step in flight still writes E
+      h->E.reset();
+      h->ema_dev.reset();
+    }
+    h->ema_decay = 0.f;
+    return NASR_OK;
+  }
+  if (!h->E) {   // the first switch-on: the average starts at the parameters (TF's initial shadow value), no update yet
+    const size_t nb = (size_t)h->np_int * 4;
+    if (hipMalloc(h->E.out(), nb) != hipSuccess || hipMalloc(h->ema_dev.out(), sizeof(EmaDev)) != hipSuccess) {
+      h->E.reset();
+      h->ema_dev.reset();
+      (void)hipGetLastError();
+      return h->fail(NASR_ERR_HIP, "nasr_set_ema: hipMalloc of the averaged parameters failed");
+    }
+    HIPCHK(h, hipMemcpyAsync(h->E, h->P, nb, hipMemcpyDeviceToDevice, h->st));
+    HIPCHK(h, hipMemsetAsync(h->ema_dev, 0, sizeof(EmaDev), h->st));
+  }
+  h->ema_decay = decay;
+  return NASR_OK;
+}
+
+int nasr_get_ema(nasr_handle h, float* decay, int64_t* updates, int* live) {
+  MODEL_CALL(h);
+  if (!h) return NASR_ERR_ARG;
+  if (decay) *decay = h->ema_decay;
+  if (live) *live = h->ema_live ? 1 : 0;
+  if (updates) {
+    *updates = 0;
+    if (h->E) {
+      HIPCHK(h, hipSetDevice(h->device));
+      EmaDev d{};
+      HIPCHK(h, hipMemcpyAsync(&d, h->ema_dev, sizeof(d), hipMemcpyDeviceToHost, h->st));
+      if (int rc = sync_checked(h)) return rc;
+      *updates = d.updates;
+    }
+  }
+  return NASR_OK;
+}
+
+int nasr_get_ema_state(nasr_handle h, float* flat, int64_t n, int64_t* updates) {
+  MODEL_CALL(h);
+  if (!h || !flat) return NASR_ERR_ARG;
+  if (!h->E) return h->fail(NASR_ERR_STATE, "nasr_get_ema_state: averaging is off (nasr_set_ema)");
+  if (n != h->np_tf) return h->fail(NASR_ERR_ARG, "nasr_get_ema_state: wrong length");
+  HIPCHK(h, hipSetDevice(h->device));
+  if (int rc = gather_from_device(h, h->E, flat)) return rc;
+  return updates ? nasr_get_ema(h, nullptr, updates, nullptr) : NASR_OK;
+}
+
+int nasr_set_ema_state(nasr_handle h, const float* flat, int64_t n, int64_t updates) {
+  MODEL_CALL(h);
+  if (!h || !flat) return NASR_ERR_ARG;
+  if (!h->E) return h->fail(NASR_ERR_STATE, "nasr_set_ema_state: averaging is off (nasr_set_ema)");
+  NOT_EMA_LIVE(h);
+  if (n != h->np_tf || updates < 0) return h->fail(NASR_ERR_ARG, "nasr_set_ema_state: wrong length or negative updates");
+  HIPCHK(h, hipSetDevice(h->device));
+  if (int rc = scatter_to_device(h, flat, h->E)) return rc;
+  const EmaDev init{(long long)updates, 0.f};
+  HIPCHK(h, hipMemcpyAsync(h->ema_dev, &init, sizeof(init), hipMemcpyHostToDevice, h->st));
+  HIPCHK(h, hipStreamSynchronize(h->st));
+  return NASR_OK;
+}
+
+int nasr_ema_swap(nasr_handle h) {
+  MODEL_CALL(h);
+  if (!h) return NASR_ERR_ARG;
+  if (!h->E) return h->fail(NASR_ERR_STATE, "nasr_ema_swap: averaging is off (nasr_set_ema)");
+  HIPCHK(h, hipSetDevice(h->device));
+  launch_swap16(h->P, h->E, h->np_int, h->st);
+  HIPCHK(h, hipGetLastError());
+  if (int rc = repack(h)) return rc;   // the operand images follow the parameters, as behind every Adam step
+  h->have_fwd = false;                 // (logits of the other parameters)
+  h->ema_live = !h->ema_live;
+  return NASR_OK;
+}
+
 int nasr_logit_frames(nasr_handle h, int T) {
   MODEL_CALL(h);
   if (!h) return NASR_ERR_ARG;
@@ -306,6 +407,7 @@ int nasr_discard_batch(nasr_handle h, int ticket) {
 int nasr_compute_grads(nasr_handle h) {
   MODEL_CALL(h);
   if (!h) return NASR_ERR_ARG;
+  NOT_EMA_LIVE(h);
   if (!h->resident) return h->fail(NASR_ERR_STATE, "no resident batch");
   if (h->kd_weight > 0.f && !h->teach_valid)   // a silently plain step would hide a broken training loop
     return h->fail(NASR_ERR_STATE, "nasr_compute_grads: distillation is on (nasr_set_distill) and the resident batch has no teacher "
@@ -366,16 +468,17 @@ int nasr_diag_bucket_traffic(nasr_handle h, int i, void* hip_stream, int nblocks
 int nasr_apply_adam(nasr_handle h, float grad_scale) {
   MODEL_CALL(h);
   if (!h) return NASR_ERR_ARG;
+  NOT_EMA_LIVE(h);
   if (!h->have_grads) return h->fail(NASR_ERR_STATE, "nasr_apply_adam without gradients");
   HIPCHK(h, hipSetDevice(h->device));
   {
     PhaseScope ps(h, PH_ADAM);
     if (h->max_grad_norm > 0.f)   // the norm of the (all-reduced) gradient first; its second stage decides the step on the device
       launch_adam_clipped(h->P, h->M, h->V, h->G, h->np_int, h->adam_dev, h->clip_dev, h->clip_part, h->lr, h->beta1,
-                          h->beta2, h->epsilon, grad_scale, h->max_grad_norm, h->Gbase, h->st);
+                          h->beta2, h->epsilon, grad_scale, h->max_grad_norm, h->Gbase, h->E, h->ema_dev, h->ema_decay, h->st);
     else
       launch_adam(h->P, h->M, h->V, h->G, h->np_int, h->adam_dev, h->lr, h->beta1, h->beta2, h->epsilon, grad_scale,
-                  h->Gbase, h->st);
+                  h->Gbase, h->E, h->ema_dev, h->ema_decay, h->st);
     int rc = repack(h);
     if (rc) return rc;
     // the step's fault word as it stands now (all-reduced with the gradients): read later, without a stream sync
@@ -576,6 +679,7 @@ int nasr_train_step(nasr_handle h, const float* feats, const int32_t* seq_len, c
                     const int32_t* label_len, int B, int T, int Lmax, float* loss_out) {
   MODEL_CALL(h);
   if (!h) return NASR_ERR_ARG;
+  NOT_EMA_LIVE(h);
   if (!labels) return h->fail(NASR_ERR_ARG, "nasr_train_step needs labels");
   int rc = upload(h, stacked_batch(feats, seq_len, labels, label_len, B, T, Lmax));
   if (rc) return rc;

@@ -248,6 +248,14 @@ struct nasr_ctx {
   float max_grad_norm = 0.f;
   DevPtr<ClipDev> clip_dev;
   DevPtr<double> clip_part;                  // GRAD_SUMSQ_MAX_BLOCKS partial sums of squares
+  // Parameter averaging (nasr_set_ema; ema_decay = 0 = off, the default: E and ema_dev are not allocated and
+  // nasr_apply_adam launches what it always did).  E: a second parameter image [np_int], updated inside the Adam sweep;
+  // its update count lives on the device beside AdamDev.  ema_live: nasr_ema_swap has exchanged the CONTENTS of P and E -
+  // P holds the average (every offset into h->P stays good), E the training parameters, and nothing may train.
+  float ema_decay = 0.f;
+  bool ema_live = false;
+  DevPtr<float> E;
+  DevPtr<EmaDev> ema_dev;
   // Results of a step without waiting for its end (nasr_get_step_results): loss, the fault word as it stands after the
   // forward pass, and the greedy decode are copied to pinned memory right behind the CTC forward kernels; the fault
   // word at the END of a step is copied behind its Adam launch (nasr_settle_step).  Two slots each: the host may be

@@ -10,6 +10,11 @@
 // Global-norm gradient clipping with a non-finite guard (nasr_set_grad_clip; the reference has neither): a deterministic
 // two-stage fp64 sum of squares of the gradient buffer, whose second stage decides the step on the device and leaves the
 // multiplier for the Adam pass in device memory (ClipDev).  With clipping off none of it is launched.
+//
+// Parameter averaging (nasr_set_ema; the reference has none): tf.train.ExponentialMovingAverage(decay, num_updates) of the
+// parameters, E <- E + (1 - d_n)(P_new - E) with d_n = min(decay, (1 + n) / (10 + n)), inside the same sweep on the p the
+// Adam line has just produced: 36 B/param.  n and 1 - d_n live on the device (EmaDev) and advance where Adam's count does,
+// so a void or skipped step leaves the average alone.  With averaging off the sweeps launched are the two above, unchanged.
 #include "kernels.h"
 
 #include <cstdlib>
@@ -32,17 +37,30 @@ __device__ __forceinline__ void adam_advance(AdamDev* st, float lr, float b1, fl
   st->applied = 1;
 }
 
+// n <- n + 1 and omd = 1 - min(decay, (1 + n) / (10 + n)) in double, by the same thread (em NULL: no averaging)
+__device__ __forceinline__ void ema_advance(EmaDev* em, float decay) {
+  if (!em) return;
+  const long long n = em->updates;
+  const double ramp = (1.0 + (double)n) / (10.0 + (double)n);
+  const double d = (double)decay < ramp ? (double)decay : ramp;
+  em->omd = (float)(1.0 - d);
+  em->updates = n + 1;
+}
+
 // ... unless the step is void
-__global__ void adam_prepare_kernel(AdamDev* st, const float* __restrict__ fault, float lr, float b1, float b2) {
+__global__ void adam_prepare_kernel(AdamDev* st, const float* __restrict__ fault, float lr, float b1, float b2, EmaDev* em,
+                                    float decay) {
   if (fault && *fault != 0.f) {
     st->applied = 0;
     return;
   }
   adam_advance(st, lr, b1, b2);
+  ema_advance(em, decay);
 }
 
-// the sweep of both Adam kernels, behind their void-step check; `gscale` is the step's multiplier and `lr_t` its step size
-#define NASR_ADAM_SWEEP                                                                                                   \
+// the sweep of the Adam kernels, behind their void-step check; `gscale` is the step's multiplier and `lr_t` its step size.
+// EMA (a literal): the average e follows the new p in the same trip, e <- fma(omd, p - e, e).
+#define NASR_ADAM_SWEEP(EMA)                                                                                              \
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {       \
     float4 gg = reinterpret_cast<const float4*>(g)[i];                                                                    \
     float4 mm = reinterpret_cast<float4*>(m)[i];                                                                          \
@@ -52,6 +70,17 @@ __global__ void adam_prepare_kernel(AdamDev* st, const float* __restrict__ fault
     reinterpret_cast<float4*>(m)[i] = mm;                                                                                 \
     reinterpret_cast<float4*>(v)[i] = vv;                                                                                 \
     reinterpret_cast<float4*>(p)[i] = pp;                                                                                 \
+    NASR_EMA_##EMA                                                                                                        \
+  }
+#define NASR_EMA_0
+#define NASR_EMA_1                                                                                                        \
+  {                                                                                                                       \
+    float4 ee = reinterpret_cast<float4*>(e)[i];                                                                          \
+    ee.x = fmaf(omd, pp.x - ee.x, ee.x);                                                                                  \
+    ee.y = fmaf(omd, pp.y - ee.y, ee.y);                                                                                  \
+    ee.z = fmaf(omd, pp.z - ee.z, ee.z);                                                                                  \
+    ee.w = fmaf(omd, pp.w - ee.w, ee.w);                                                                                  \
+    reinterpret_cast<float4*>(e)[i] = ee;                                                                                 \
   }
 #define NASR_ADAM1(c)                                   \
   {                                                     \
@@ -69,7 +98,18 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, float*
   // gradients, so every rank sees it): such a step must not touch the parameters, on any rank.
   if (fault && *fault != 0.f) return;
   const float lr_t = st->lr_t;
-  NASR_ADAM_SWEEP
+  NASR_ADAM_SWEEP(0)
+}
+
+// the same with the average e behind p; omd = 1 - d_n of this step (ema_advance)
+__global__ __launch_bounds__(256) void adam_ema_kernel(float* __restrict__ p, float* __restrict__ m, float* __restrict__ v,
+                                                       const float* __restrict__ g, float* __restrict__ e, int64_t n4,
+                                                       const AdamDev* __restrict__ st, const EmaDev* __restrict__ em, float b1,
+                                                       float b2, float eps, float gscale, const float* __restrict__ fault) {
+  if (fault && *fault != 0.f) return;
+  const float lr_t = st->lr_t;
+  const float omd = em->omd;
+  NASR_ADAM_SWEEP(1)
 }
 
 // the same with the multiplier of this step read from ClipDev: grad_scale * coef, or nothing at all for a skipped step
@@ -81,10 +121,34 @@ __global__ __launch_bounds__(256) void adam_clip_kernel(float* __restrict__ p, f
   if (clip->skip) return;
   const float lr_t = st->lr_t;
   const float gscale = clip->s;
-  NASR_ADAM_SWEEP
+  NASR_ADAM_SWEEP(0)
+}
+
+__global__ __launch_bounds__(256) void adam_clip_ema_kernel(float* __restrict__ p, float* __restrict__ m, float* __restrict__ v,
+                                                            const float* __restrict__ g, float* __restrict__ e, int64_t n4,
+                                                            const AdamDev* __restrict__ st, const ClipDev* __restrict__ clip,
+                                                            const EmaDev* __restrict__ em, float b1, float b2, float eps,
+                                                            const float* __restrict__ fault) {
+  if (fault && *fault != 0.f) return;
+  if (clip->skip) return;
+  const float lr_t = st->lr_t;
+  const float gscale = clip->s;
+  const float omd = em->omd;
+  NASR_ADAM_SWEEP(1)
 }
 #undef NASR_ADAM1
+#undef NASR_EMA_0
+#undef NASR_EMA_1
 #undef NASR_ADAM_SWEEP
+
+// a <-> b over n4 float4s (nasr_ema_swap: the data move, the pointers and every offset into them stay)
+__global__ __launch_bounds__(256) void swap16_kernel(float4* __restrict__ a, float4* __restrict__ b, int64_t n4) {
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
+    const float4 x = a[i], y = b[i];
+    a[i] = y;
+    b[i] = x;
+  }
+}
 
 // ---- the global norm: n2 = sum_i (double)g_i * (double)g_i, the same bits on every run ----------------------------------
 // The square of an fp32 value is exact in fp64 and every partial sum is rounded once, in an order that depends on the
@@ -128,10 +192,11 @@ __global__ __launch_bounds__(256) void grad_sumsq_part_kernel(const float* __res
 
 // One workgroup: thread j adds the partials j, j + 256, ... in index order, then the same fixed fold; thread 0 decides the
 // step.  A void step (fault word set) leaves everything alone, as adam_prepare_kernel does, whose work this kernel takes
-// over: a step that is applied advances Adam's count, a skipped one (non-finite norm) does not.
+// over: a step that is applied advances Adam's count (and the average's), a skipped one (non-finite norm) does not.
 __global__ __launch_bounds__(256) void grad_clip_final_kernel(const double* __restrict__ part, int nparts, ClipDev* clip,
                                                               AdamDev* st, const float* __restrict__ fault, float gscale,
-                                                              float max_norm, float lr, float b1, float b2) {
+                                                              float max_norm, float lr, float b1, float b2, EmaDev* em,
+                                                              float decay) {
   __shared__ double sm[4];
   if (fault && *fault != 0.f) {
     if (threadIdx.x == 0) st->applied = 0;
@@ -157,28 +222,44 @@ __global__ __launch_bounds__(256) void grad_clip_final_kernel(const double* __re
   if (coef < 1.f) clip->clipped += 1;
   if (norm > clip->window_max_norm) clip->window_max_norm = norm;
   adam_advance(st, lr, b1, b2);
+  ema_advance(em, decay);
 }
 
 void launch_adam(float* p, float* m, float* v, const float* g, int64_t n, AdamDev* state, float lr, float beta1, float beta2,
-                 float eps, float gscale, const float* fault, hipStream_t st) {
+                 float eps, float gscale, const float* fault, float* e, EmaDev* ema, float decay, hipStream_t st) {
   const int64_t n4 = n / 4;
   int blocks = (int)((n4 + 255) / 256);
-  if (blocks > 2048) blocks = 2048;
-  hipLaunchKernelGGL(adam_prepare_kernel, dim3(1), dim3(1), 0, st, state, fault, lr, beta1, beta2);
-  hipLaunchKernelGGL(adam_kernel, dim3(blocks), dim3(256), 0, st, p, m, v, g, n4, state, beta1, beta2, eps, gscale, fault);
+  if (blocks > ADAM_MAX_BLOCKS) blocks = ADAM_MAX_BLOCKS;
+  hipLaunchKernelGGL(adam_prepare_kernel, dim3(1), dim3(1), 0, st, state, fault, lr, beta1, beta2, e ? ema : nullptr, decay);
+  if (e)
+    hipLaunchKernelGGL(adam_ema_kernel, dim3(blocks), dim3(256), 0, st, p, m, v, g, e, n4, state, ema, beta1, beta2, eps, gscale,
+                       fault);
+  else
+    hipLaunchKernelGGL(adam_kernel, dim3(blocks), dim3(256), 0, st, p, m, v, g, n4, state, beta1, beta2, eps, gscale, fault);
+}
+
+void launch_swap16(float* a, float* b, int64_t n, hipStream_t st) {
+  const int64_t n4 = n / 4;
+  int blocks = (int)((n4 + 255) / 256);
+  if (blocks > ADAM_MAX_BLOCKS) blocks = ADAM_MAX_BLOCKS;
+  hipLaunchKernelGGL(swap16_kernel, dim3(blocks), dim3(256), 0, st, reinterpret_cast<float4*>(a), reinterpret_cast<float4*>(b), n4);
 }
 
 void launch_adam_clipped(float* p, float* m, float* v, const float* g, int64_t n, AdamDev* state, ClipDev* clip, double* part,
                          float lr, float beta1, float beta2, float eps, float gscale, float max_norm, const float* fault,
-                         hipStream_t st) {
+                         float* e, EmaDev* ema, float decay, hipStream_t st) {
   const int64_t n4 = n / 4;
   int blocks = (int)((n4 + 255) / 256);
-  if (blocks > 2048) blocks = 2048;
+  if (blocks > ADAM_MAX_BLOCKS) blocks = ADAM_MAX_BLOCKS;
   const int nparts = grad_sumsq_blocks(n);
   hipLaunchKernelGGL(grad_sumsq_part_kernel, dim3(nparts), dim3(256), 0, st, g, n, part, fault);
   hipLaunchKernelGGL(grad_clip_final_kernel, dim3(1), dim3(256), 0, st, part, nparts, clip, state, fault, gscale, max_norm, lr,
-                     beta1, beta2);
-  hipLaunchKernelGGL(adam_clip_kernel, dim3(blocks), dim3(256), 0, st, p, m, v, g, n4, state, clip, beta1, beta2, eps, fault);
+                     beta1, beta2, e ? ema : nullptr, decay);
+  if (e)
+    hipLaunchKernelGGL(adam_clip_ema_kernel, dim3(blocks), dim3(256), 0, st, p, m, v, g, e, n4, state, clip, ema, beta1, beta2,
+                       eps, fault);
+  else
+    hipLaunchKernelGGL(adam_clip_kernel, dim3(blocks), dim3(256), 0, st, p, m, v, g, n4, state, clip, beta1, beta2, eps, fault);
 }
 
 // ---- column sums: stage 1 writes part[rs][n] for 32 row slices, stage 2 adds them in order

@@ -1,4 +1,5 @@
 """Evaluation over the test list, one utterance at a time (reference: decode.py:14-54).
+With ema_decay in the config the network loads the checkpoint's averaged parameters.
 
   python -m neuralasr_amd.decode <config>
   python -m neuralasr_amd.decode <config> --from-audio    # the test set of the [MFCC Featurizer] input CSV: features made on the GPU"""

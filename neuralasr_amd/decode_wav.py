@@ -2,6 +2,7 @@
 `python -m neuralasr_amd.decode_wav CONFIG WAV`: the features of utils.compute_mfcc_and_read_transcription, the
 configured network's decoder, and a 'Decoded: ...' log line.  A network that takes audio (HipNetwork.takes_audio) gets the samples:
 its features are made on the GPU and stay there.  Every other network class takes features, so every one works.
+With ema_decay in the config the network loads the checkpoint's averaged parameters.
 `--stream [--chunk-frames N]`: a causal network (LstmCTCNet) is fed the file's frames N at a time (default 50 = 0.5 s), with a
 'Partial: ...' line after every chunk whose hypothesis changed.  With normalization=utterance (the default) the features
 are computed over the whole file first: the reference normalises by whole-utterance mean and std (utils.py:29), so frames a

@@ -155,6 +155,41 @@ class Engine:
     def set_learning_rate(self, lr):
         self._ck(self.lib.nasr_set_learning_rate(self.h, float(lr)))
 
+    def learning_rate(self):
+        """the step size the next apply_adam() is launched with"""
+        v = c_float()
+        self._ck(self.lib.nasr_get_learning_rate(self.h, byref(v)))
+        return float(v.value)
+
+    # ------------------------------------------------------------------ parameter averaging (include/nasr.h, nasr_set_ema)
+    def set_ema(self, decay):
+        """An exponential moving average of the parameters, updated inside every applied apply_adam() from here on
+        (tf.train.ExponentialMovingAverage's rule with its num_updates ramp): 0 = off, a number in (0,1) = on.  The first
+        switch-on starts the average at the parameters as they stand."""
+        self._ck(self.lib.nasr_set_ema(self.h, float(decay)))
+
+    def ema(self):
+        """(decay, updates, live): 0.0 = averaging is off; the updates applied so far; whether ema_swap() has the average
+        in the parameters' place.  Synchronises."""
+        decay, updates, live = c_float(), c_int64(), c_int()
+        self._ck(self.lib.nasr_get_ema(self.h, byref(decay), byref(updates), byref(live)))
+        return float(decay.value), int(updates.value), bool(live.value)
+
+    def get_ema(self):
+        """the averaged parameters, flat, in get_params()' order (while the average is live: the training parameters)"""
+        flat = np.empty(self.param_count, np.float32)
+        self._ck(self.lib.nasr_get_ema_state(self.h, _fp(flat), flat.size, None))
+        return flat
+
+    def set_ema_state(self, flat, updates):
+        flat = _f32(flat).ravel()
+        self._ck(self.lib.nasr_set_ema_state(self.h, _fp(flat), flat.size, int(updates)))
+
+    def ema_swap(self):
+        """The parameters and their average change places (the data, on the device; the operand images follow): every
+        forward-only call then runs on the average, and the calls that train are refused until the next ema_swap()."""
+        self._ck(self.lib.nasr_ema_swap(self.h))
+
     # ------------------------------------------------------------------ host-buffer entry points
     def _batch(self, feats, seq_len, labels=None, label_len=None):
         """The arrays of a batch as the library takes them.  The library reads B*T*feature_size floats behind a bare

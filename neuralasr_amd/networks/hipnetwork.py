@@ -10,8 +10,9 @@ Differences from the reference that a caller can observe, all deliberate and doc
     reference names in the comment at tfnetwork.py:62-63: no host work at all);
   * num_gpus > 1 means one process per GPU (torch.distributed.run); inside a single process the towers are
     time-sliced on one GPU with the same split / averaging arithmetic;
-  * checkpoints are `model-<step>.npz` (flat fp32 params + Adam m, v + step) with TF Saver's cadence and
-    keep-5 policy, not TF's format."""
+  * checkpoints are `model-<step>.npz` (flat fp32 params + Adam m, v + step; with ema_decay in the config also the
+    averaged parameters) with TF Saver's cadence and keep-5 policy, not TF's format."""
+import contextlib
 import glob
 import json
 import os
@@ -112,6 +113,11 @@ class HipNetwork(Network):
             self.engine.set_chunking(config.chunk_frames, config.stream_lookahead)
         self.engine.set_step_decode(True)
         self.engine.set_params(self.initial_params(self.engine.tensors(), seed=1))
+        # ema_decay: a training network keeps the average beside the parameters and validates, evaluates,
+        # decodes and aligns on it; one built for inference loads the checkpoint's average as its parameters instead
+        self._ema = fortraining and getattr(config, 'ema_decay', 0.0) > 0
+        if self._ema:
+            self.engine.set_ema(config.ema_decay)               # the average starts at the initial parameters
         self._grad_tensor = None
         self._reducer = None
         self._staged = {}                       # id(mfccs) -> (ticket, weakref to mfccs): batches stage_batch() sent ahead
@@ -226,9 +232,23 @@ class HipNetwork(Network):
             if not files:
                 raise FileNotFoundError('no checkpoint (model-<step>.npz) in ' + model_dir)
             with np.load(files[-1]) as z:
-                self.engine.set_params(z['params'])
+                params = z['params']
+                if not self.fortraining and getattr(self.config, 'ema_decay', 0.0) > 0:
+                    if 'ema' in z:
+                        params = z['ema']                       # the averaged model is the one that is decoded
+                    else:
+                        self.logger.warning("'ema_decay' is set but the checkpoint holds no average: using its parameters")
+                self.engine.set_params(params)
                 self.engine.set_adam_state(z['adam_m'], z['adam_v'], int(z['step']))
+                if self._ema and 'ema' in z:
+                    self.engine.set_ema_state(z['ema'], int(z['ema_updates']))
+                elif self._ema:
+                    self.logger.info('The checkpoint holds no average: it starts at the restored parameters.')
+                    self.engine.set_ema_state(z['params'], 0)
                 self.restore_model_state(z)
+            if self.fortraining and getattr(self.config, 'lr_schedule_on', False):
+                # the schedule is a function of the global step: the checkpoint's, whatever start_step says
+                self.global_step = int(os.path.basename(files[-1])[6:-4])
             self.logger.info('Done Restoring checkpoint: ' + files[-1])
         elif self.coll.rank == 0:
             if os.path.exists(model_dir):
@@ -248,11 +268,15 @@ class HipNetwork(Network):
             return
         m, v, step = self.engine.get_adam_state()
         path = os.path.join(self.config.model_dir, 'model-%d.npz' % self.global_step)
+        ema = {}
+        if self._ema:
+            decay, updates, _ = self.engine.ema()
+            ema = {'ema': self.engine.get_ema(), 'ema_updates': np.int64(updates), 'ema_decay': np.float32(decay)}
         np.savez(path, params=self.engine.get_params(), adam_m=m, adam_v=v, step=np.int64(step),
                  meta=json.dumps({'hidden': self.num_hidden, 'layers': self.num_layers,
                                   'bidirectional': self.bidirectional, 'merge': self.merge,
                                   'classes': self.num_classes, 'feature_size': self.config.feature_size}),
-                 **self.model_state())
+                 **ema, **self.model_state())
         for old in self._ckpt_files(self.config.model_dir)[:-self.keep_checkpoints]:
             os.remove(old)
 
@@ -451,8 +475,29 @@ class HipNetwork(Network):
                 self._reducer.all_reduce()
             else:
                 self.coll.all_reduce_sum_(self._grad_tensor)
-        self.engine.apply_adam(1.0 / n)
+        self._apply_adam(1.0 / n)
         return self.engine.step_token()
+
+    def _apply_adam(self, grad_scale):
+        """apply_adam of every step path.  With a learning-rate schedule in the config the step size of
+        global step s is set right before it: a launch argument, so steps still in flight keep theirs."""
+        if getattr(self.config, 'lr_schedule_on', False):
+            self.engine.set_learning_rate(self.config.learning_rate_at(self.global_step))
+        self.engine.apply_adam(grad_scale)
+
+    @contextlib.contextmanager
+    def _averaged(self):
+        """What is not a training step runs inside: the last step settled, and with ema_decay the average in the
+        parameters' place (swap, run, swap: the training bits come back as they were)."""
+        self._settle()
+        if not self._ema or self.engine.ema()[2]:           # (nested: the average is in place already)
+            yield
+            return
+        self.engine.ema_swap()
+        try:
+            yield
+        finally:
+            self.engine.ema_swap()
 
     # ------------------------------------------------------------------ the step's LER (tfnetwork.py:61-70)
     def _beam_ler(self, logits, s, l, ll):
@@ -607,32 +652,33 @@ class HipNetwork(Network):
                 gsum = g if gsum is None else gsum + g
             if not void:
                 self.engine.set_grads((gsum / n).astype(np.float32))
-                self.engine.apply_adam(1.0)
+                self._apply_adam(1.0)
                 if not self.engine.step_void():
                     return np.float32(np.mean(losses)), np.float32(np.mean(lers))
             self.logger.warning('step %d was void (persistent recurrence aborted): repeating it' % self.global_step)
         raise RuntimeError('training step %d stayed void after 3 attempts' % self.global_step)
 
     def validate(self, mfccs, labels, seq_len, labels_len):
-        self._settle()
-        loss, ler, _ = self._loss_ler(mfccs, labels, seq_len, labels_len)
+        with self._averaged():
+            loss, ler, _ = self._loss_ler(mfccs, labels, seq_len, labels_len)
         return [np.float32(loss), np.float32(ler)]
 
     def evaluate(self, mfccs, labels, seq_len, labels_len):
-        self._settle()
-        loss, ler, hyps = self._loss_ler(mfccs, labels, seq_len, labels_len, self.language_model())
+        with self._averaged():
+            loss, ler, hyps = self._loss_ler(mfccs, labels, seq_len, labels_len, self.language_model())
         # SparseTensorValue.values: every utterance's ids concatenated (tfnetwork.py:176-177)
         flat = np.asarray([i for h in hyps for i in h], dtype=np.int64)
         return flat, np.float32(loss), np.float32(ler)
 
     def decode(self, mfccs, seq_len):
-        self._settle()
-        hyps = self._decode(mfccs, seq_len, self.decoder, self.language_model())
+        with self._averaged():
+            hyps = self._decode(mfccs, seq_len, self.decoder, self.language_model())
         return np.asarray([i for h in hyps for i in h], dtype=np.int64)
 
     def stream(self, slots=1, lookahead=None):
         """A stream.StreamingRecognizer on this network: `slots` concurrent streams fed chunk by chunk, the LSTM state
-        carried on the GPU, the hypothesis available after every chunk.  A bidirectional network streams
+        carried on the GPU, the hypothesis available after every chunk.  On a training network with ema_decay
+        every feed of the session runs on the averaged parameters.  A bidirectional network streams
         with `lookahead` frames of right context (None: the config's stream_lookahead), a unidirectional
         one ignores both.  Raises the library's message for a network that cannot stream (stack-reshape merge, dropout,
         WaveNet, LAS)."""
@@ -651,13 +697,13 @@ class HipNetwork(Network):
         order) - the log-probability of its best CTC path and the logit frames that path spends on each label (blank
         frames belong to no symbol).  Walk and traceback run on the GPU."""
         from ..align import spans
-        self._settle()
         labels = np.asarray(labels, dtype=np.int32).reshape(len(seq_len), -1)
 
         def run():
             self._upload(mfccs, labels, seq_len, labels_len, training=False)
             return self.engine.align_resident(len(seq_len), np.shape(mfccs)[1])
-        path, score = self._retry_aborted(run)
+        with self._averaged():
+            path, score = self._retry_aborted(run)
         return [(float(score[b]), spans(path[b], labels[b, :int(labels_len[b])])) for b in range(len(seq_len))]
 
     def align_audio(self, audios, rates, labels, labels_len):

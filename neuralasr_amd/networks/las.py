@@ -195,7 +195,7 @@ class LAS(HipNetwork):
                 if self._grad_tensor is None:
                     self._grad_tensor = self.engine.grad_tensor()
                 self.coll.all_reduce_sum_(self._grad_tensor)
-            self.engine.apply_adam(1.0 / n)
+            self._apply_adam(1.0 / n)
             if self.coll.world > 1:
                 loss, ler = self.coll.mean_scalars([loss, ler])
             return np.float32(loss), np.float32(ler)
@@ -209,7 +209,7 @@ class LAS(HipNetwork):
             gsum = g if gsum is None else gsum + g
         self._next_counter(counter)
         self.engine.set_grads((gsum / n).astype(np.float32))
-        self.engine.apply_adam(1.0)
+        self._apply_adam(1.0)
         return np.float32(np.mean(losses)), np.float32(np.mean(lers))
 
     def stage_batch(self, mfccs, labels, seq_len, labels_len):
@@ -223,11 +223,12 @@ class LAS(HipNetwork):
         n, mine = self._towers()
         counter = self.engine.sampling_state()[2]
         losses, lers = [], []
-        for k in mine:
-            f, l, s, ll = take_shard(mfccs, labels, seq_len, labels_len, n, k)
-            loss, ler = self._tower_pass(f, l, s, ll, k, counter, False)
-            losses.append(loss)
-            lers.append(ler)
+        with self._averaged():                 # (ema_decay: the averaged variables; the sampling state is not one)
+            for k in mine:
+                f, l, s, ll = take_shard(mfccs, labels, seq_len, labels_len, n, k)
+                loss, ler = self._tower_pass(f, l, s, ll, k, counter, False)
+                losses.append(loss)
+                lers.append(ler)
         self._next_counter(counter)
         loss, ler = float(np.mean(losses)), float(np.mean(lers))
         if self.coll.world > 1:
@@ -244,10 +245,11 @@ class LAS(HipNetwork):
     def _beam_search(self, mfccs, seq_len, trace):
         start, end = self._markers()
         args = (self.beam_width, self.max_decode_steps, start, end, self.length_penalty_weight)
-        if isinstance(mfccs, AudioBatch):
-            self._upload_audio(mfccs)             # the front end once; the search reads the resident batch
-            return self.engine.beam_search_resident(*args, trace=trace)
-        return self.engine.beam_search(mfccs, seq_len, *args, trace=trace)
+        with self._averaged():
+            if isinstance(mfccs, AudioBatch):
+                self._upload_audio(mfccs)             # the front end once; the search reads the resident batch
+                return self.engine.beam_search_resident(*args, trace=trace)
+            return self.engine.beam_search(mfccs, seq_len, *args, trace=trace)
 
     def evaluate(self, mfccs, labels, seq_len, labels_len):
         """[model [B, T_dec], loss, ler]: beam 0 of the gathered ids, beam_sequence_loss of the step scores, and the LER of

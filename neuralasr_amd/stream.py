@@ -12,6 +12,8 @@ tail and running statistics on the GPU, and the rows a feed makes go straight in
 A bidirectional (concat) network streams with a look-ahead: StreamingRecognizer(network, slots, lookahead=R)
 opens a look-ahead session, whose feeds hold each slot's last R rows back for their right context; the beams get the rows a
 feed emits, and finish() flushes the rest.  The hypothesis then depends on how the input was split into feeds."""
+import contextlib
+
 import numpy as np
 
 from .engine import BeamStream
@@ -44,6 +46,8 @@ class StreamingRecognizer:
         kw = {} if lm is None else dict(lm=lm, lm_weight=network.config.lm_weight, lm_bonus=network.config.lm_bonus)
         self.beams = [BeamStream(network.num_classes, width, True, **kw) for _ in range(self.slots)]
         self._audio = False                      # feed_audio attached the network's featurizer to the session
+        # a training network with ema_decay runs every feed on its averaged parameters
+        self._averaged = getattr(network, '_averaged', contextlib.nullcontext)
 
     def _padded(self, arrs, n):
         """the chunk [slots, max n, F]: slot b's n[b] rows, zeros behind them"""
@@ -78,13 +82,16 @@ class StreamingRecognizer:
                 raise ValueError('a chunk must be [n, %d], not %s' % (self.feature_size, a.shape))
         n = np.asarray([0 if a is None else a.shape[0] for a in arrs], dtype=np.int32)
         if self.lookahead is not None:
-            logits, rows = self.engine.stream_feed_lookahead(self._padded(arrs, n), n, last)
+            with self._averaged():
+                logits, rows = self.engine.stream_feed_lookahead(self._padded(arrs, n), n, last)
             return self._deliver(logits, rows, n, last, 'rows')
         if last is not None and any(last):
             raise ValueError('`last` means something only with a look-ahead')
         if n.max() == 0:                         # (the library refuses a chunk without rows)
             return [beam.best()[0] for beam in self.beams]
-        return self._deliver(self.engine.stream_feed(self._padded(arrs, n), n), n, n, None, None)
+        with self._averaged():
+            logits = self.engine.stream_feed(self._padded(arrs, n), n)
+        return self._deliver(logits, n, n, None, None)
 
     def feed_audio(self, chunks, last=None):
         """chunks: one entry per slot, float32 [n_b] samples at config.samplerate (the slot's next samples) or None (the
@@ -97,7 +104,8 @@ class StreamingRecognizer:
         if not self._audio:
             self.engine.stream_attach_audio(self.network.featurizer())
             self._audio = True
-        logits, rows = self.engine.stream_feed_audio(chunks, last)
+        with self._averaged():
+            logits, rows = self.engine.stream_feed_audio(chunks, last)
         return self._deliver(logits, rows, [c is not None and np.size(c) for c in chunks], last, 'audio')
 
     def hypothesis(self, slot=0):

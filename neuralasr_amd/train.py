@@ -1,7 +1,7 @@
 """Training loop (reference: train.py:14-63): epochs x batches, cumulative wall time, checkpoint + log +
 one validation batch every report_step, same log-line formats (plus one "Grad:" line behind every "Step:" line when the
-config's max_grad_norm switches gradient clipping on, and one "Distill:" line when its teacher_config switches
-distillation on).
+config's max_grad_norm switches gradient clipping on, one "Distill:" line when its teacher_config switches
+distillation on, and one "LR:" line when one of its lr_* keys sets a learning-rate schedule).
 
   python -m neuralasr_amd.train <config>
   python -m neuralasr_amd.train <config> --from-audio     # from the [MFCC Featurizer] input CSV: features made on the GPU per batch
@@ -56,6 +56,9 @@ def train_model(dataTrain, datavalid, config, prefetch=2):
                         ', ler = %.4f' % (ler_sum / den) + ', time = %.4f' % spent)
             loss_sum = ler_sum = 0.0
             counted = 0
+            if getattr(config, 'lr_schedule_on', False):
+                # lr_warmup_steps / lr_decay_* (DESIGN.md §23): the step size this step was applied with
+                logger.info('LR: %.6g' % config.learning_rate_at(network.global_step))
             if getattr(config, 'max_grad_norm', 0.0) > 0:
                 # max_grad_norm: the optimiser steps since the last log line, read where save_checkpoint has
                 # just waited for the device anyway
