@@ -113,11 +113,13 @@ struct LstmDims { int T, B, Bp, H, Hp, D; };   // D directions
 //             there, for every row b < Bp.
 //   units     j in [H, Hp): U's padded rows and columns and the padded gate columns of the input must be 0; c and out
 //             are then exactly 0 there.  dOut must be 0 there too (it is: the layer above has zero weights for them);
-//             dG is then exactly 0 there - except in the persistent BPTT, whose partial sums carry their epoch in the
-//             last mantissa bit, so a zero partial sum can be the subnormal 2^-149: |dG| <= 32 T 2^-149 in those units.
-//             These columns of dG also enter the weight- and bias-gradient GEMMs of the padded parameters.  Whether the
-//             optimiser then keeps the padded parameters at exactly 0 (Adam divides a gradient of that size by eps) has
-//             NOT been checked; the requirement above that U's padding is 0 rests on it.
+//             dG is +0 there, on every path.  These columns of dG enter the weight- and bias-gradient passes of the
+//             padded parameters, and the Adam sweep covers the padding: the gradient of a padded parameter must be
+//             exactly 0 for the parameter to stay 0 (a sum of subnormals over T*B rows is enough to move it: Adam divides
+//             by eps), and the requirement above that U's padding is 0 rests on that.  (The persistent BPTT's partial
+//             sums carry their epoch in the last mantissa bit, so the dh it computes for a padded unit can be 32 x 2^-149:
+//             it stores +0 in dG for the units j >= dm.H, and its rowpart / colpart are the maxima of what it stores.)
+//             DESIGN.md §24; tests/test_gpu_padding.py, tests/test_gpu_rec_kernels.py.
 // repack canonical U [Hp][N4] of every (layer,dir) into the forward / backward MFMA B-operand images
 void launch_repack_u(const float* U, float* Uf, float* Ub, int Hp, hipStream_t st);
 // One layer's buffers as the per-step kernels see a window of dm.T steps: a whole batch, a stream feed's chunk, or one

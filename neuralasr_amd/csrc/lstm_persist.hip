@@ -150,6 +150,7 @@ void launch_repack_persist(const float* P, const int64_t* offs, int n, float* Up
 // ------------------------------------------------------------------ forward
 struct PersistGeom {
   int T, Bp, Hp, D;
+  int H;         // real units: the BPTT stores +0 in dG for the gate columns of units j >= H (kernels.h, "units")
   int ub;        // utterance rows per group and round (<= 4)
   int rounds;    // passes over the batch (weights stay in registers)
   int inject;    // test hook (NASR_PERSIST_FAULT=s): member 0 of every group treats the poll of step s as timed out
@@ -550,7 +551,10 @@ __global__ __launch_bounds__(320, 1) void lstm_persist_bwd_kernel(
       if (rowok) {
         const int s = T - 1 - k;
         const float* ad = adg + (k & 1) * 256 + 16 * u + q;
-        const f32x4 dg = (f32x4){ad[0], ad[4], ad[8], ad[12]};
+        // A padded unit's dG is not 0 in the A image: its dh is the sum of 32 partial sums whose last mantissa bit is the
+        // epoch, 2^-149 each where the sum itself is 0.  The products with U's zero rows make nothing of that, but the
+        // weight- and bias-gradient passes that read dG would: what is stored (and enters the maxima) is +0 there
+        const f32x4 dg = j < gm.H ? (f32x4){ad[0], ad[4], ad[8], ad[12]} : (f32x4){0.f, 0.f, 0.f, 0.f};
         row = (unsigned)(((s < len) ? (d ? (len - 1 - s) : s) : s) * Bp + b);
         *reinterpret_cast<f32x4*>(dgbuf + (row * (unsigned)DN + (unsigned)(d * N4 + 4 * j))) = dg;
         const f32x4 ab = (f32x4){fabsf(dg.x), fabsf(dg.y), fabsf(dg.z), fabsf(dg.w)};
@@ -753,7 +757,7 @@ bool persist_supported(int Hp) {
 
 static PersistGeom make_geom(const LstmDims& dm, bool bwd) {
   PersistGeom g;
-  g.T = dm.T; g.Bp = dm.Bp; g.Hp = dm.Hp; g.D = dm.D;
+  g.T = dm.T; g.Bp = dm.Bp; g.Hp = dm.Hp; g.D = dm.D; g.H = dm.H;
   const int NGD = 8 / dm.D;
   g.ub = (dm.Bp + NGD - 1) / NGD;
   if (g.ub > 4) g.ub = 4;
