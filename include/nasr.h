@@ -117,7 +117,8 @@ int nasr_get_learning_rate(nasr_handle h, float* lr);
 int nasr_train_step(nasr_handle h, const float* feats, const int32_t* seq_len, const int32_t* labels,
                     const int32_t* label_len, int B, int T, int Lmax, float* loss_out);
 /* forward only (inference graph, networks/tfnetwork.py:33-37): logits_out is time-major
- * [T',B,C] with T' = nasr_logit_frames(h,T) (2T for STACK_RESHAPE). May be NULL. */
+ * [T',B,C] with T' = nasr_logit_frames(h,T) (2T for STACK_RESHAPE; of ceil(T/s) frames under nasr_set_frame_skip(h, s)).
+ * May be NULL. */
 int nasr_forward(nasr_handle h, const float* feats, const int32_t* seq_len, int B, int T, float* logits_out);
 int nasr_logit_frames(nasr_handle h, int T);
 /* loss of validate()/evaluate() (networks/tfnetwork.py:166-177): forward + CTC, no update.
@@ -382,7 +383,7 @@ int nasr_get_step_results(nasr_handle h, float* loss_out, int* fault_out, int32_
 int nasr_settle_step(nasr_handle h, int previous, int* void_out);
 int64_t nasr_step_token(nasr_handle h);
 int nasr_settle_token(nasr_handle h, int64_t token, int* void_out);
-int nasr_resident_frames(nasr_handle h, int64_t* frames); /* sum(seq_len) of the resident batch */
+int nasr_resident_frames(nasr_handle h, int64_t* frames); /* sum(seq_len) of the resident batch: input frames, whatever the frame skip */
 /* Ragged batches.  DataSet.get_next_batch (dataset.py:75-77) pads every utterance to the longest of its batch and
  * tf.nn.(bidirectional_)dynamic_rnn (networks/bilstm_ctc_net.py:40-53) masks by sequence_length.  Here, when at least
  * 15 % of a training batch's T x B frame rows are such padding, the operand passes and GEMMs of a plain (Bi)LSTM stack work
@@ -392,7 +393,8 @@ int nasr_resident_frames(nasr_handle h, int64_t* frames); /* sum(seq_len) of the
  * the resident batch - sum(seq_len) when compacted, T x (B rounded up to 16) otherwise. */
 int nasr_set_row_compaction(nasr_handle h, int enabled);
 int nasr_resident_rows(nasr_handle h, int64_t* rows);
-/* B and T of the resident batch (0, 0 without one): what the *_resident calls size their outputs by. */
+/* B and T of the resident batch as the caller gave them (0, 0 without one): what the *_resident calls size their outputs
+ * by, through nasr_logit_frames(h, T). */
 int nasr_resident_shape(nasr_handle h, int* B, int* T);
 
 /* TensorFlowNetwork.train fetches mean_ler with every step (networks/tfnetwork.py:188-189): with
@@ -468,7 +470,8 @@ int nasr_stream_frames(nasr_handle h, int64_t* frames_out);
 int nasr_stream_get_state(nasr_handle h, float* state, int64_t n);
 /* (No counterpart in the reference: tfnetwork.py:179-181 decodes whole utterances.)  Replaces the session's state (the
  * layout of nasr_stream_get_state; the frame counts stay): continuing on another handle with the same parameters gives
- * the first handle's logits bit for bit. */
+ * the first handle's logits bit for bit.  The state does not carry a slot's frame-skip phase (nasr_set_frame_skip): every
+ * slot starts at phase 0 behind this call, as if its next input row were its utterance's first. */
 int nasr_stream_set_state(nasr_handle h, const float* state, int64_t n);
 /* (No counterpart in the reference: tfnetwork.py:179-181 decodes whole utterances, utils.py:29 normalises them whole.)  The
  * session takes SAMPLES from now on: `featurizer`, a featurizer handle with norm = 1 (the causal rule at nasr_mfcc_cfg), turns
@@ -566,6 +569,31 @@ int nasr_stream_feed_lookahead(nasr_handle h, const float* feats, const int32_t*
 int nasr_set_chunking(nasr_handle h, int C, int R);
 /* *C, *R (either nullable) as set; 0, 0 when off. */
 int nasr_get_chunking(nasr_handle h, int* C, int* R);
+
+/* ---- frame skip: low-frame-rate input for the LSTM CTC networks --------------------------------------
+ * (No counterpart in the reference: the rule is this project's own.  Its effect on the label error rate is not measured.)
+ * With skip s in [1,8] the network sees input frames 0, s, 2s, ... of every utterance: network frame j is input frame j*s,
+ * an utterance of len input frames has ceil(len/s) network frames and a batch of T input frames ceil(T/s).  A kept frame's
+ * context window is exactly what the input frame's window was (frames before 0 and from len on are the utterance's pad
+ * value, SpecAugment-masked frames stay masked); with s <= 2*numcontext+1 no input sample is lost.  Everything behind the
+ * input layout - recurrence, dense stages, projection, CTC, greedy decode, alignment, distillation, row compaction,
+ * chunked training, stream sessions - sees network frames only.
+ * Callers keep passing input T, input seq_len and input features in every upload form, and SpecAugment masks in input
+ * frames.  nasr_logit_frames(h, T) returns the logit frames of ceil(T/s) network frames, and every output sized by it is in
+ * network frames: logits, greedy ids, alignment paths, step logits.  nasr_resident_shape keeps returning the caller's
+ * input B, T and nasr_resident_frames keeps counting input frames; nasr_resident_rows counts network rows.  The CTC
+ * feasibility check (NASR_ERR_INFEASIBLE) is made against network frames.  nasr_set_chunking(C, R) and
+ * nasr_stream_open_lookahead(S, R) count network frames.
+ * In a stream session the caller feeds input rows (or samples): the session keeps, per slot, how many input rows the
+ * utterance has had, modulo s, and a feed keeps the new rows whose index in the utterance is a multiple of s.
+ * nasr_stream_feed's chunk then has ceil(Tc/s) rows (logits_out [ceil(Tc/s)][S][C]); rows_out, Te_out and
+ * nasr_stream_frames report kept rows.  nasr_stream_reset clears a slot's count; nasr_stream_set_state does not carry it.
+ * s = 1, the default, is the library without the call, bit for bit.  A change drops the resident batch, and a batch staged
+ * before the change is refused at nasr_commit_batch.  NASR_ERR_ARG: s outside [1,8].  NASR_ERR_STATE, nothing changed: a
+ * WaveNet or LAS handle with s != 1 (the convolutions need every frame; LAS has its pyramid); an open stream session. */
+int nasr_set_frame_skip(nasr_handle h, int s);
+/* *s as set; 1 on a WaveNet or LAS handle. */
+int nasr_get_frame_skip(nasr_handle h, int* s);
 
 /* The CTC beam search as a state that lives between calls - host only, the procedure and arithmetic of
  * nasr_ctc_beam_search(_lm), which is open + one feed + best + close on this very code: feeding an utterance's frames in

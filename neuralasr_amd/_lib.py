@@ -52,7 +52,7 @@ SYMBOLS = [
     'nasr_ctc_beam_open', 'nasr_ctc_beam_feed', 'nasr_ctc_beam_best', 'nasr_ctc_beam_close',
     'nasr_featurizer_set_noise', 'nasr_featurizer_set_rirs', 'nasr_upload_batch_audio_wave', 'nasr_stage_batch_audio_wave',
     'nasr_augment_audio',
-    'nasr_set_chunking', 'nasr_get_chunking',
+    'nasr_set_chunking', 'nasr_get_chunking', 'nasr_set_frame_skip', 'nasr_get_frame_skip',
     'nasr_set_distill', 'nasr_get_distill', 'nasr_set_teacher_logits', 'nasr_take_teacher_logits', 'nasr_get_distill_loss',
     'nasr_distill_logits',
     'nasr_get_learning_rate', 'nasr_set_ema', 'nasr_get_ema', 'nasr_get_ema_state', 'nasr_set_ema_state', 'nasr_ema_swap',
@@ -291,6 +291,8 @@ def load():
         'nasr_stream_open_lookahead': (c_int, [H, c_int, c_int]),
         'nasr_set_chunking': (c_int, [H, c_int, c_int]),
         'nasr_get_chunking': (c_int, [H, POINTER(c_int), POINTER(c_int)]),
+        'nasr_set_frame_skip': (c_int, [H, c_int]),
+        'nasr_get_frame_skip': (c_int, [H, POINTER(c_int)]),
         'nasr_stream_lookahead_rows': (c_int, [H, ip, POINTER(c_uint8), ip, POINTER(c_int)]),
         'nasr_stream_feed_lookahead': (c_int, [H, fp, ip, POINTER(c_uint8), c_int, ip, POINTER(c_int), fp, c_int64]),
         'nasr_ctc_beam_open': (c_int, [c_int, c_int, c_int, fp, fp, c_int, c_int, c_float, c_float, POINTER(c_void_p)]),

@@ -5,7 +5,8 @@ table - a symbol the table does not hold is an error, nothing is inserted; the n
 best CTC path on the GPU; the output is one log line per symbol, `sym start end`, and the path's log-probability.
 With ema_decay in the config the network loads the checkpoint's averaged parameters.
 
-Times are seconds, frame x 0.01 (the front end's winstep), when the network has one logit frame per feature frame.  The
+Times are seconds, frame x 0.01 (the front end's winstep), when the network has one logit frame per feature frame; with
+frame_skip = s in the config a logit frame is one of the network's frames, s x 0.01 s.  The
 literal BiLstmCTCNet (merge 'stack_reshape') has 2T logit frames that its reshape of the (fw, bw) tuple scrambles over
 utterances and directions: they have no time, so there the lines carry logit-frame indices."""
 import argparse
@@ -56,9 +57,16 @@ def text_ids(config, clean_transcription):
     return np.asarray(ids, dtype=np.int32)
 
 
+def frame_seconds(config):
+    """the seconds one network frame stands for: the front end's winstep times the config's frame_skip"""
+    return int(getattr(config, 'frame_skip', 1)) * WINSTEP
+
+
 def frames_have_time(network, T=100):
-    """one logit frame per feature frame (nasr_logit_frames(T) == T)?  Not under the stack_reshape merge."""
-    return network.engine.logit_frames(T) == T
+    """one logit frame per frame the network sees (nasr_logit_frames(T) == ceil(T / frame_skip))?  Not under the
+    stack_reshape merge."""
+    s = int(getattr(network.config, 'frame_skip', 1)) if hasattr(network, 'config') else 1
+    return network.engine.logit_frames(T) == (T + s - 1) // s
 
 
 def report(config, timed, score, symbol_spans):
@@ -66,9 +74,10 @@ def report(config, timed, score, symbol_spans):
         logger.info('This network reshapes the (fw, bw) output tuple into 2T logit frames (stack_reshape, SURVEY.md D3): a '
                     'logit frame is no point in time; printing logit-frame indices.')
     lines = []
+    step = frame_seconds(config)
     for sid, a, b in symbol_spans:
         sym = config.symbols.get_sym(sid)
-        line = '%s %.2f %.2f' % (sym, a * WINSTEP, (b + 1) * WINSTEP) if timed else '%s %d %d' % (sym, a, b)
+        line = '%s %.2f %.2f' % (sym, a * step, (b + 1) * step) if timed else '%s %d %d' % (sym, a, b)
         logger.info('Aligned: ' + line)
         lines.append(line)
     logger.info('Score: %.6f' % score)

@@ -37,7 +37,10 @@ iterate): ema_decay (in (0,1); default off) keeps tf.train.ExponentialMovingAver
 validate / evaluate / decode / align then run on and which a network built for inference loads from the checkpoint;
 lr_warmup_steps (>= 0, default 0), lr_decay_steps (>= 0, 0 = no decay), lr_decay_rate (in (0,1], default 1) and lr_staircase
 (0 or 1) make the step size of global step s learningrate * min(1, s / warmup) * rate ** (max(0, s - warmup) / decay_steps);
-without them nothing changes."""
+without them nothing changes.  One more optional [Parameters] key, frame_skip (an integer in 1..8, default 1), gives the LSTM
+CTC networks low-frame-rate input (the reference has no such key, the rule is this project's own): the
+network sees every frame_skip-th stacked frame of an utterance; train, validate, evaluate, decode, align and stream all
+read it, a checkpoint remembers it, and without the key nothing changes."""
 import importlib
 import math
 from configparser import ConfigParser, ExtendedInterpolation
@@ -113,6 +116,13 @@ class Config(object):
         if self.chunk_frames > 0 and self.stream_lookahead < 1:
             raise ValueError("'chunk_frames' needs 'stream_lookahead' >= 1 (the window is chunk_frames + stream_lookahead rows), in %s"
                              % configfile)
+        # low-frame-rate input: the network sees input frames 0, frame_skip, 2*frame_skip, ... ; 1 = every frame
+        try:
+            self.frame_skip = int(par['frame_skip'].strip()) if 'frame_skip' in par else 1
+        except ValueError:
+            self.frame_skip = 0
+        if not 1 <= self.frame_skip <= 8:
+            raise ValueError("'frame_skip' must be an integer in [1,8], not %r, in %s" % (par['frame_skip'], configfile))
         self.frame_width = self.numcep * (1 + self.deltas)
         self.feature_size = (2 * self.numcontext + 1) * self.frame_width
         self.lm_file = par['lm_file'].strip() if 'lm_file' in par else None
@@ -285,7 +295,7 @@ class Config(object):
         return network_class(self.network)(self, fortraining=fortraining)
 
     def print_config(self):
-        names = ['samplerate', 'numcep', 'numcontext', 'features', 'deltas', 'normalization', 'norm_min_frames', 'stream_lookahead', 'chunk_frames', 'rand_shift', 'batch_size', 'epochs', 'learningrate',
+        names = ['samplerate', 'numcep', 'numcontext', 'features', 'deltas', 'normalization', 'norm_min_frames', 'stream_lookahead', 'chunk_frames', 'frame_skip', 'rand_shift', 'batch_size', 'epochs', 'learningrate',
                  'model_dir', 'start_step', 'report_step', 'num_gpus', 'label_context', 'punc_regex', 'network',
                  'sym_file', 'train_input', 'test_input', 'mfcc_input', 'mfcc_output', 'start_marker', 'end_marker']
         lines = ['']

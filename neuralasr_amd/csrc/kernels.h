@@ -186,16 +186,26 @@ void launch_lc_carry_out(const float* part, int np, const float* dcs, const int*
 void launch_lc_carry_dc(float* dcin, const float* dcc, int n, hipStream_t st);
 
 // ---- row movers (rows.hip): features into the stack's rows, a look-ahead session's windows, a chunked batch's windows ----
-void launch_pack_feats(const float* feats_bm, float* X0, int B, int Bp, int T, int F, int Fp, hipStream_t st);
+// Frame skip: with skip s the network sees input frames 0, s, 2s, ... - n input frames are
+// skip_frames(n, s) network frames.  The three feature movers below take T and seq_len in INPUT frames and write
+// skip_frames(T, skip) x Bp rows: row t*Bp + b from input frame t*skip, zeros from the utterance's network length on.
+__host__ __device__ inline int skip_frames(int n, int skip) { return (n + skip - 1) / skip; }
+// seq_in [Bp] input lengths; NULL (skip 1 only): every row of the caller's is copied, padding included
+void launch_pack_feats(const float* feats_bm, float* X0, int B, int Bp, int T, int F, int Fp, hipStream_t st, int skip = 1,
+                       const int* seq_in = nullptr);
 void launch_expand_context(const float* centre, const float* pad, const int* seq_len, float* X0, int B, int Bp, int T,
-                           int ctx, int ncep, int Fp, hipStream_t st);
+                           int ctx, int ncep, int Fp, hipStream_t st, int skip = 1);
 // The same with SpecAugment masks on the centre frames (no counterpart in the reference): masks [B][nm] of
 // {t0, tw, f0, fw}, utterance b's k-th time mask over frames [t0, t0 + tw) and its k-th frequency mask over columns
 // [f0, f0 + fw) of each static_width-wide block of a frame; width 0 = no mask.  Masked centre values are 0, pads stay.
 // Uses 2*ctx+1 + ncep bytes of dynamic LDS.
 void launch_expand_context_masked(const float* centre, const float* pad, const int* seq_len, const int* masks, int nm,
                                   int static_width, float* X0, int B, int Bp, int T, int ctx, int ncep, int Fp,
-                                  hipStream_t st);
+                                  hipStream_t st, int skip = 1);
+// A stream feed's kept rows: in [S][Tc][F] -> out [S][Tk][F], slot b's row j from input row first[b] + j*skip for
+// j < kept[b] (kept[b] <= Tk and first[b] + (kept[b]-1)*skip < Tc), zeros behind them.  Tk >= 1.
+struct SkipSlots { int first[LA_MAX_SLOTS], kept[LA_MAX_SLOTS]; };
+void launch_skip_rows(const float* in, const SkipSlots& sk, float* out, int S, int Tc, int Tk, int F, int skip, hipStream_t st);
 // Window assembly: pending row t of slot b is hold_in [S][R][F] row t (t < held) or fresh [S][Tc][F] row t - held; rows
 // [0, P) of an emitting slot go to win [S][T][F] (zeros elsewhere; win NULL: nothing emits), rows [emit, P) to hold_out
 // [S][R][F], which must not be hold_in.  rows = the largest P, >= 1.

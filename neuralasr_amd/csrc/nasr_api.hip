@@ -339,7 +339,7 @@ int nasr_logit_frames(nasr_handle h, int T) {
   if (!h) return NASR_ERR_ARG;
   switch (h->family) {
     case Family::Las: return h->fail(NASR_ERR_STATE, "nasr_logit_frames: a LAS handle has no CTC logit frames");
-    case Family::Lstm: return lstm_logit_frames(h, T);
+    case Family::Lstm: return lstm_logit_frames(h, skip_frames(T, lstm_frame_skip(h)));   // T: input frames
     default: return T;
   }
 }
@@ -882,7 +882,7 @@ int nasr_resident_shape(nasr_handle h, int* B, int* T) {
   MODEL_CALL(h);
   if (!h || !B || !T) return NASR_ERR_ARG;
   *B = h->resident ? h->B : 0;
-  *T = h->resident ? h->T : 0;
+  *T = h->resident ? h->Tin : 0;   // the caller's input frames, whatever the frame skip
   return NASR_OK;
 }
 

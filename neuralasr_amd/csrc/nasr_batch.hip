@@ -127,7 +127,7 @@ int lstm_ensure_shape(nasr_ctx* h, int B, int T, int Lmax, bool chunked) {
 }
 
 int validate_batch(nasr_ctx* h, const int32_t* seq_len, const int32_t* labels, const int32_t* label_len, int B, int T,
-                   int Lmax, int num_classes) {
+                   int Lmax, int num_classes, int skip) {
   const bool las = !num_classes && h->family == Family::Las;
   const int C = num_classes ? num_classes : h->C;
   if (B < 1 || B > 64) return h->fail(NASR_ERR_ARG, "per-GPU batch must be in [1,64]");
@@ -154,9 +154,13 @@ int validate_batch(nasr_ctx* h, const int32_t* seq_len, const int32_t* labels, c
         return h->fail(NASR_ERR_ARG, "label id out of [0, num_classes-2] (blank = num_classes-1 is not a label)");
       if (i > 0 && v == labels[(size_t)b * Lmax + i - 1]) ++rep;
     }
-    if (L + rep > seq_len[b])
+    const int avail = skip_frames(seq_len[b], skip);
+    if (L + rep > avail)
       return h->fail(NASR_ERR_INFEASIBLE, "Not enough time for target transition sequence (required: " +
-                                              std::to_string(L + rep) + ", available: " + std::to_string(seq_len[b]) +
+                                              std::to_string(L + rep) + ", available: " + std::to_string(avail) +
+                                              (skip > 1 ? " network frames: " + std::to_string(seq_len[b]) + " input frames under frame_skip " +
+                                                              std::to_string(skip)
+                                                        : std::string()) +
                                               ") in sequence " + std::to_string(b));
   }
   return NASR_OK;
@@ -250,38 +254,42 @@ static int check_batch(nasr_ctx* h, const BatchSrc& b, bool* masked) {
     return h->fail(NASR_ERR_ARG, "context upload: feature_size must equal (2*numcontext+1)*numcep");
   if (b.labels && !b.label_len) return h->fail(NASR_ERR_ARG, "labels without label_len");
   if (b.chunk) return validate_chunk(h, b.seq_len, b.B, b.T);
-  if (int rc = validate_batch(h, b.seq_len, b.labels, b.label_len, b.B, b.T, b.Lmax)) return rc;
+  if (int rc = validate_batch(h, b.seq_len, b.labels, b.label_len, b.B, b.T, b.Lmax, 0, lstm_frame_skip(h))) return rc;
   if (!b.aug) return NASR_OK;
   if (!b.centre_form()) return h->fail(NASR_ERR_ARG, "augmentation masks need a batch in the centre form");
   return validate_aug(h, b.aug, b.seq_len, b.B, b.ctx, b.ncep, masked);
 }
 
-// slot_fill (2): the slot's shape and the layout of its meta block (int32): seq [Bp] | lablen [Bp] | labels [B*Lm] |
-// cstart [B*(C+1)] | cpos [B*Lm] | rowmap [Tp*Bp] | vrow, vprev, vnext [Rvp] | masks [B*nm] of int4.  No HIP call.
+// slot_fill (2): the slot's shape and the layout of its meta block (int32): seq [Bp] | seqin [Bp] | lablen [Bp] |
+// labels [B*Lm] | cstart [B*(C+1)] | cpos [B*Lm] | rowmap [Tp*Bp] | vrow, vprev, vnext [Rvp] | masks [B*nm] of int4.  seq:
+// the lengths in the frames the network sees, seqin: the caller's (the same without a frame skip).  T below is the network's
+// frame count: the caller's input T only sizes dfeats.  No HIP call.
 static void meta_layout(nasr_ctx* h, BatchSlot* s, const BatchSrc& b, bool masked) {
   const LstmState* const ls = h->lstm.get();   // NULL: a handle of another family, which neither compacts rows nor runs windows
-  const int B = b.B, T = b.T;
-  s->B = B; s->T = T; s->Lmax = b.labels ? b.Lmax : 0; s->ctx = b.ctx; s->ncep = b.ncep;
+  s->skip = b.chunk ? 1 : lstm_frame_skip(h);  // (a stream chunk's rows are the kept ones already)
+  const int B = b.B, T = skip_frames(b.T, s->skip);
+  s->B = B; s->T = b.T; s->Tn = T; s->Lmax = b.labels ? b.Lmax : 0; s->ctx = b.ctx; s->ncep = b.ncep;
   s->Bp = rup(B, 16);
-  s->Tp = h->family == Family::Las ? T : nasr_logit_frames(h, T);
+  s->Tp = ls ? lstm_logit_frames(h, T) : T;
   s->has_labels = b.labels != nullptr;
   s->centre = b.centre_form();
   s->masked = masked;
   s->aug_nm = masked ? std::max(b.aug->n_time, b.aug->n_freq) : 0;
   s->aug_sw = masked ? b.aug->static_width : 0;
-  s->frames = 0;
-  for (int i = 0; i < B; ++i) s->frames += b.seq_len[i];
+  s->frames = s->nframes = 0;
+  for (int i = 0; i < B; ++i) { s->frames += b.seq_len[i]; s->nframes += skip_frames(b.seq_len[i], s->skip); }
   const size_t BLm = (size_t)B * std::max(s->Lmax, 1);
   s->o_seq = 0;
-  s->o_lablen = s->o_seq + s->Bp;
+  s->o_seqin = s->o_seq + s->Bp;
+  s->o_lablen = s->o_seqin + s->Bp;
   s->o_labels = s->o_lablen + s->Bp;
   s->o_cstart = s->o_labels + BLm;
   s->o_cpos = s->o_cstart + (b.labels ? (size_t)B * (h->C + 1) : 0);
   s->o_rowmap = s->o_cpos + BLm;
   // compacted rows: worth it when at least 15 % of the T x Bp rows are padding (profiles/r03_row_compaction_ab.log: even at
   // 10 %), and only for training batches
-  s->cmp = ls && ls->compactable && b.labels && s->frames * 20 <= (int64_t)T * s->Bp * 17;
-  s->Rv = s->cmp ? (int)s->frames : 0;
+  s->cmp = ls && ls->compactable && b.labels && s->nframes * 20 <= (int64_t)T * s->Bp * 17;
+  s->Rv = s->cmp ? (int)s->nframes : 0;
   // a batch under nasr_set_chunking: the row lists are those of its windows, always (a stream chunk is no such batch)
   const bool lc = ls && ls->lcC > 0 && !b.chunk;
   s->chunk = b.chunk;
@@ -291,7 +299,7 @@ static void meta_layout(nasr_ctx* h, BatchSlot* s, const BatchSrc& b, bool maske
   if (lc) {
     int64_t rows = 0;
     for (int i = 0; i < B; ++i)
-      for (int k = 0; k < s->lcK; ++k) rows += lc_window_rows(b.seq_len[i], k, s->lcC, s->lcW);
+      for (int k = 0; k < s->lcK; ++k) rows += lc_window_rows(skip_frames(b.seq_len[i], s->skip), k, s->lcC, s->lcW);
     s->cmp = true;
     s->Rv = (int)std::min<int64_t>(rows, (int64_t)1 << 22);   // (more: ensure_shape refuses the batch at commit)
   }
@@ -303,17 +311,19 @@ static void meta_layout(nasr_ctx* h, BatchSlot* s, const BatchSrc& b, bool maske
   const size_t end = s->o_wlen + (size_t)s->lcK * s->Bp;
   s->o_aug = (end + 3) / 4 * 4;      // (the kernel reads a mask as one int4)
   s->nmeta = masked ? s->o_aug + (size_t)B * s->aug_nm * 4 : end;
-  s->nfeat = s->centre ? (size_t)B * T * b.ncep + B : (size_t)B * T * h->F;
+  s->nfeat = s->centre ? (size_t)B * b.T * b.ncep + B : (size_t)B * b.T * h->F;   // (the caller's frames, all of them)
 }
 
 // slot_fill (3): the meta block, as laid out, into the slot's pinned mirror
 static void write_meta(const nasr_ctx* h, BatchSlot* s, const BatchSrc& src) {
-  const int B = src.B, T = src.T, Bp = s->Bp, Tp = s->Tp, C = h->C, Lmax = src.Lmax, Lm = std::max(s->Lmax, 1), nm = s->aug_nm;
-  const int32_t *seq_len = src.seq_len, *labels = src.labels, *label_len = src.label_len;
+  const int B = src.B, T = s->Tn, Bp = s->Bp, Tp = s->Tp, C = h->C, Lmax = src.Lmax, Lm = std::max(s->Lmax, 1), nm = s->aug_nm;
+  const int32_t *labels = src.labels, *label_len = src.label_len;
   const nasr_batch_aug* aug = src.aug;
   int32_t* m = static_cast<int32_t*>(s->hmeta.get());
   memset(m, 0, s->nmeta * 4);
-  memcpy(m + s->o_seq, seq_len, (size_t)B * 4);
+  memcpy(m + s->o_seqin, src.seq_len, (size_t)B * 4);
+  for (int b = 0; b < B; ++b) m[s->o_seq + b] = skip_frames(src.seq_len[b], s->skip);
+  const int32_t* seq_len = m + s->o_seq;   // from here on: frames the network sees
   if (labels) {
     memcpy(m + s->o_lablen, label_len, (size_t)B * 4);
     if (Lmax > 0) memcpy(m + s->o_labels, labels, (size_t)B * Lmax * 4);
@@ -446,9 +456,12 @@ int slot_commit(nasr_ctx* h, BatchSlot* s) {
   // (a slot is laid out for the chunking of the moment it was filled; a stream chunk never is)
   if (ls && !s->chunk && (s->lcC != ls->lcC || s->lcR != (ls->lcC ? ls->lcR : 0)))
     return h->fail(NASR_ERR_STATE, "the batch was staged under another nasr_set_chunking than the handle has now: stage it again");
-  int rc = ensure_shape(h, s->B, s->T, s->Lmax, s->lcC > 0);
+  if (ls && !s->chunk && s->skip != ls->skip)   // (and for the frame skip of that moment)
+    return h->fail(NASR_ERR_STATE, "the batch was staged under another nasr_set_frame_skip (" + std::to_string(s->skip) +
+                                       ") than the handle has now (" + std::to_string(ls->skip) + "): stage it again");
+  int rc = ensure_shape(h, s->B, s->Tn, s->Lmax, s->lcC > 0);
   if (rc) return rc;
-  const int B = s->B, T = s->T, Bp = h->Bp;
+  const int B = s->B, T = s->T, Bp = h->Bp;   // T: the caller's input frames, as dfeats holds them
   {
     std::lock_guard<std::mutex> lk(h->slot_mu);
     if (h->cur && h->cur != s) {
@@ -462,6 +475,7 @@ int slot_commit(nasr_ctx* h, BatchSlot* s) {
   }
   HIPCHK(h, hipStreamWaitEvent(h->st, s->ev_copy, 0));
   int32_t* md = s->meta_d();
+  const int32_t* seq_in = md + s->o_seqin;   // the input lengths: what the feature movers below decide on
   // seq_len lives at a FIXED address: the hipGraphs of the per-step recurrence captured it
   HIPCHK(h, hipMemcpyAsync(h->seqbuf.p, md + s->o_seq, (size_t)Bp * 4, hipMemcpyDeviceToDevice, h->st));
   h->seq_p = h->seqbuf.as<int32_t>(); h->lablen_p = md + s->o_lablen; h->labels_p = md + s->o_labels;
@@ -483,19 +497,20 @@ int slot_commit(nasr_ctx* h, BatchSlot* s) {
   const int32_t* hm = static_cast<const int32_t*>(s->hmeta.get());
   for (int b = 0; b < B; ++b) h->h_seq[b] = hm[s->o_seq + b];
   h->frames = s->frames;
+  h->Tin = T;
   {
     PhaseScope ps(h, PH_PACK);
     const bool lc = ls && ls->lc_live;
     float* x0 = (lc ? ls->lc_x0 : h->X0).as<float>();   // a chunked batch: the rows by frame first
     if (s->centre && s->masked)
-      launch_expand_context_masked(s->dfeats.as<float>(), s->dfeats.as<float>() + (size_t)B * T * s->ncep, h->seq_p,
+      launch_expand_context_masked(s->dfeats.as<float>(), s->dfeats.as<float>() + (size_t)B * T * s->ncep, seq_in,
                                    md + s->o_aug, s->aug_nm, s->aug_sw, x0, B, Bp, T, s->ctx, s->ncep,
-                                   h->Fp, h->st);
+                                   h->Fp, h->st, s->skip);
     else if (s->centre)
-      launch_expand_context(s->dfeats.as<float>(), s->dfeats.as<float>() + (size_t)B * T * s->ncep, h->seq_p,
-                            x0, B, Bp, T, s->ctx, s->ncep, h->Fp, h->st);
+      launch_expand_context(s->dfeats.as<float>(), s->dfeats.as<float>() + (size_t)B * T * s->ncep, seq_in,
+                            x0, B, Bp, T, s->ctx, s->ncep, h->Fp, h->st, s->skip);
     else
-      launch_pack_feats(s->dfeats.as<float>(), x0, B, Bp, T, h->F, h->Fp, h->st);
+      launch_pack_feats(s->dfeats.as<float>(), x0, B, Bp, T, h->F, h->Fp, h->st, s->skip, s->skip > 1 ? seq_in : nullptr);
     if (lc) launch_lc_gather(x0, h->wlen_p, h->X0.as<float>(), ls->lcg, h->Fp, h->st);   // ... and into the windows' rows
     if (ls)   // (the WaveNet's and LAS's GEMMs read the fp32 features as they are)
       pl_scales(h, h->X0.as<float>(), ls->Tv * Bp, h->Fp, h->Fp, &ls->sc_x0r, &ls->sc_x0c, h->st);

@@ -162,6 +162,13 @@ struct BatchSlot {
   int B = 0, T = 0, Lmax = 0, Bp = 0, Tp = 0, ctx = 0, ncep = 0;
   bool has_labels = false, centre = false;
   int64_t frames = 0;
+  // Frame skip (nasr_set_frame_skip as it stood when the slot was filled; 1 for a stream chunk, whose rows
+  // the session has skipped already).  T, frames and dfeats are the caller's INPUT frames; Tn = skip_frames(T, skip) and
+  // nframes count the frames the network sees, and everything the meta block lays out is in those: o_seq holds the network
+  // lengths, o_seqin the input lengths beside them, which only the three feature movers read.
+  int skip = 1, Tn = 0;
+  int64_t nframes = 0;
+  size_t o_seqin = 0;
   size_t o_seq = 0, o_lablen = 0, o_labels = 0, o_cstart = 0, o_cpos = 0, o_rowmap = 0;   // int offsets into meta
   size_t o_vrow = 0, o_vprev = 0, o_vnext = 0;   // compacted rows of a ragged batch (Rv of them, padded to Rvp with -1), or unused
   int Rv = 0, Rvp = 0;
@@ -273,8 +280,9 @@ struct nasr_ctx {
 
   // resident batch
   bool resident = false, have_grads = false, have_fwd = false;
-  int B = 0, Bp = 0, T = 0, Lmax = 0, Tp = 0, KS = 1;
-  int64_t frames = 0;
+  int B = 0, Bp = 0, T = 0, Lmax = 0, Tp = 0, KS = 1;   // T: the frames the network sees (the slot's Tn)
+  int Tin = 0;                               // the caller's input frames (nasr_resident_shape); T again without a frame skip
+  int64_t frames = 0;                        // input frames (nasr_resident_frames)
   std::vector<int32_t> h_seq;
   BatchSlot slots[NSLOT];
   BatchSlot* cur = nullptr;                  // the resident batch
@@ -425,7 +433,8 @@ int lstm_create(const nasr_model_cfg* cfg, int device_id, void* stream, const Ls
 // what the common calls run on every model handle (nothing where there is no LstmState)
 void drop_graphs(nasr_ctx* h);        // the graphs of the per-step recurrence's layer passes
 void lstm_sync_side(nasr_ctx* h);     // waits for the weight-gradient side stream
-int lstm_logit_frames(const nasr_ctx* h, int T);
+int lstm_logit_frames(const nasr_ctx* h, int T);   // T: network frames
+int lstm_frame_skip(const nasr_ctx* h);             // 1 on a handle of another family
 
 // ---- nasr_batch.hip
 // chunked: the batch is laid out in the windows of nasr_set_chunking
@@ -434,8 +443,9 @@ int ensure_shape(nasr_ctx* h, int B, int T, int Lmax, bool chunked = false);
 // lattice kernel's instantiation for labels up to Lmax (h->KS), or the code of a failure (< 0)
 int ensure_ctc_buffers(nasr_ctx* h, int B, int Bp, int T, int Tp, int Lmax, bool* grew);
 // num_classes: 0 = the handle's (and its family's rules); > 0: CTC labels over that many classes (nasr_ctc_align_logits)
+// skip: the CTC feasibility check is made against skip_frames(seq_len[b], skip), the frames the network sees
 int validate_batch(nasr_ctx* h, const int32_t* seq_len, const int32_t* labels, const int32_t* label_len, int B, int T, int Lmax,
-                   int num_classes = 0);
+                   int num_classes = 0, int skip = 1);
 // a chunk of a stream session: S slots, Tc frames, n_frames[b] in [0, Tc] (0 = the slot is idle in this chunk)
 int validate_chunk(nasr_ctx* h, const int32_t* n_frames, int S, int Tc);
 bool pinned_ensure(Pinned<void>& p, size_t* cap, size_t bytes);

@@ -39,6 +39,10 @@ struct StreamState {
   std::vector<uint8_t> done;         // [S] the slot has had `last` and no reset
   LaSlots sl{};                      // the feed that is running (run_chunk_steps: which row's state to save)
   std::vector<int64_t> frames;       // [S] frames emitted since the slot's reset
+  // Frame skip: the input rows the slot's utterance has had so far, modulo the skip.  A feed keeps the new
+  // rows whose index in the utterance is a multiple of the skip; everything above counts kept rows.
+  std::vector<int32_t> phase;        // [S]
+  DevBuf raw;                        // skip > 1: [S][Tc][F] the feed's new input rows, before skip_rows_kernel
 };
 
 // Every operand row of a plane GEMM carries a power-of-two scale (device floats, scale and 1/scale), measured per step
@@ -148,6 +152,9 @@ struct LstmState {
   // state was carried from) - while the projection and the CTC stay on the T frames: lc_top / lc_dtop hold the top layer's
   // emitted rows and their gradient by frame.  Tv = T and lc_live = false for every other batch (a stream chunk included).
   int lcC = 0, lcR = 0;
+  // Frame skip (nasr_set_frame_skip): the network sees input frames 0, skip, 2*skip, ... of every utterance.
+  // Only the batch funnel's layout (nasr_batch.hip) and a stream session's row source (nasr_stream.hip) read it.
+  int skip = 1;
   int Tv = 0;
   bool lc_live = false;                      // the resident batch is laid out in windows
   LcGeom lcg{};

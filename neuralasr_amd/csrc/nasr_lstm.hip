@@ -28,6 +28,8 @@ int lstm_logit_frames(const nasr_ctx* h, int T) {
   return (c.bidirectional && c.merge == NASR_MERGE_STACK_RESHAPE) ? 2 * T : T;
 }
 
+int lstm_frame_skip(const nasr_ctx* h) { return h->lstm ? h->lstm->skip : 1; }
+
 int lstm_create(const nasr_model_cfg* cfg, int device_id, void* stream, const LstmSwitches& sw, nasr_ctx** out) {
   if (!cfg || !out) {
     g_create_error = "nasr_create: null argument";
@@ -231,6 +233,33 @@ int nasr_get_chunking(nasr_handle h, int* C, int* R) {
   if (!h) return NASR_ERR_ARG;
   if (C) *C = h->lstm ? h->lstm->lcC : 0;   // (a WaveNet or LAS handle: never chunked)
   if (R) *R = h->lstm ? h->lstm->lcR : 0;
+  return NASR_OK;
+}
+
+int nasr_set_frame_skip(nasr_handle h, int s) {
+  MODEL_CALL(h);
+  if (!h) return NASR_ERR_ARG;
+  const std::string fn = "nasr_set_frame_skip";
+  if (s < 1 || s > 8) return h->fail(NASR_ERR_ARG, fn + ": frame_skip = " + std::to_string(s) + ": must be in [1,8]");
+  if (!h->lstm) {
+    if (s == 1) return NASR_OK;
+    return h->fail(NASR_ERR_STATE, fn + ": a WaveNet or LAS handle takes every frame (frame_skip = 1): the convolutions need each "
+                                        "one, and LAS has its pyramid");
+  }
+  LstmState* const ls = h->lstm.get();
+  if (ls->stream) return h->fail(NASR_ERR_STATE, fn + ": a stream session is open: close it first");
+  if (s == ls->skip) return NASR_OK;
+  ls->skip = s;
+  // the resident batch is laid out for the skip it was uploaded under: the next pass needs a new upload
+  h->resident = false;
+  h->have_grads = h->have_fwd = h->have_decoded = false;
+  return NASR_OK;
+}
+
+int nasr_get_frame_skip(nasr_handle h, int* s) {
+  MODEL_CALL(h);
+  if (!h || !s) return NASR_ERR_ARG;
+  *s = lstm_frame_skip(h);   // (a WaveNet or LAS handle: 1)
   return NASR_OK;
 }
 

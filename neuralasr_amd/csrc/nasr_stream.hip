@@ -12,6 +12,9 @@
 // The rows of a feed come from the caller (nasr_stream_feed, nasr_stream_feed_lookahead) or, on a session that takes
 // samples (nasr_stream_attach_audio, nasr_stream_feed_audio), from a causal featurizer's front end (nasr_fz.hip:
 // fz_stream_*), which keeps per slot what it needs to turn the samples of a feed into stacked rows on the device.
+// Under a frame skip (nasr_set_frame_skip) the caller's rows are input rows and everything above counts KEPT
+// rows: keep_rows works out, from each slot's phase alone, which of a feed's new rows the network sees, plan_feed plans on
+// those counts, and run_feed's row source passes the new rows through skip_rows_kernel (rows.hip) on their way in.
 #include "nasr_fz.h"
 #include "nasr_lstm.h"
 
@@ -53,6 +56,7 @@ int open_session(nasr_ctx* h, const std::string& fn, int S, int R) {
   ss->frames.assign((size_t)S, 0);
   ss->held.assign((size_t)S, 0);
   ss->done.assign((size_t)S, 0);
+  ss->phase.assign((size_t)S, 0);
   bool grew = false;
   const size_t nb = (size_t)h->lstm->L * S * 2 * h->lstm->H * 4, hb = (size_t)S * R * h->F * 4;
   if (!ss->state.ensure(nb, &grew) || !ss->cimg.ensure((size_t)h->lstm->D * rup(S, 16) * h->lstm->Hp * 4, &grew) ||
@@ -70,7 +74,24 @@ struct FeedPlan {
   int Te = 0;           // the logit rows fetched: the most rows a slot emits
   int rows = 0;         // the most pending rows of any slot
   bool fresh = false;   // some slot got new rows
+  // the frame skip: which input rows of the feed are kept (sl.n = sk.kept), and every slot's phase behind the feed
+  SkipSlots sk{};
+  int phase[LA_MAX_SLOTS] = {};
 };
+
+// n_in [S] new INPUT rows per slot (checked by the caller) -> f->sk, f->phase, and kept [S], the rows of them that the
+// network sees: those whose index in the slot's utterance is a multiple of the skip.  Without a skip: all of them.
+// kept may be n_in itself.
+void keep_rows(const nasr_ctx* h, const int32_t* n_in, FeedPlan* f, int32_t* kept) {
+  const StreamState& ss = *h->lstm->stream;
+  const int s = h->lstm->skip;
+  for (int b = 0; b < ss.S; ++b) {
+    const int n = n_in[b], ph = ss.phase[(size_t)b], first = (s - ph) % s;
+    f->sk.first[b] = first;
+    f->sk.kept[b] = kept[b] = n > first ? skip_frames(n - first, s) : 0;
+    f->phase[b] = (int)(((int64_t)ph + n) % s);
+  }
+}
 
 // n [S] new rows per slot (checked by the caller), last nullable.  NASR_ERR_STATE for a slot that has had `last`.
 int plan_feed(nasr_ctx* h, const char* fn, const int32_t* n, const uint8_t* last, FeedPlan* f) {
@@ -91,7 +112,8 @@ int plan_feed(nasr_ctx* h, const char* fn, const int32_t* n, const uint8_t* last
 }
 
 // Where a feed's new rows [S][Tc][F] come from: the caller's host memory, or run(), which enqueues on stream cs whatever
-// writes them, every element, to `rows` (NULL with Tc = 0: the front end only takes the samples in).
+// writes them, every element, to `rows` (NULL with Tc = 0: the front end only takes the samples in).  Tc counts INPUT rows:
+// under a frame skip run_feed hands on [S][skip_frames(Tc, skip)][F] kept rows.
 struct RowSource {
   const float* host = nullptr;
   std::function<int(float* rows, hipStream_t cs)> run;
@@ -105,7 +127,14 @@ struct RowSource {
 int run_feed(nasr_ctx* h, const char* fn, const FeedPlan& f, const RowSource& src, const uint8_t* last, float* logits_out) {
   StreamState& ss = *h->lstm->stream;
   HIPCHK(h, hipSetDevice(h->device));
-  const size_t bytes = (size_t)ss.S * src.Tc * h->F * 4;
+  const int skip = h->lstm->skip, Tk = skip_frames(src.Tc, skip);   // Tk: the row stride of what make_rows hands on
+  const size_t raw_bytes = (size_t)ss.S * src.Tc * h->F * 4, bytes = (size_t)ss.S * Tk * h->F * 4;
+  float* raw = nullptr;   // skip > 1: the new input rows, all of them, before skip_rows_kernel
+  if (skip > 1 && src.Tc > 0) {
+    bool grew = false;
+    if (!ss.raw.ensure(raw_bytes, &grew)) return h->fail(NASR_ERR_HIP, std::string(fn) + ": hipMalloc of the new rows failed");
+    raw = ss.raw.as<float>();
+  }
   float* fresh = nullptr;
   if (ss.R > 0 && f.fresh) {
     bool grew = false;
@@ -115,13 +144,18 @@ int run_feed(nasr_ctx* h, const char* fn, const FeedPlan& f, const RowSource& sr
   bool moved = false;   // the window kernel is queued: the held rows are in the other hold buffer
   auto make_rows = [&](float* chunk, hipStream_t cs) -> int {
     float* dst = ss.R > 0 ? fresh : chunk;
+    float* in = skip > 1 ? raw : dst;   // (a front end makes every input row: its running normaliser needs them all)
     if (src.run) {
-      if (int rc = src.run(dst, cs)) return rc;
-    } else if (f.fresh) {
-      HIPCHK(h, hipMemcpyAsync(dst, src.host, bytes, hipMemcpyHostToDevice, cs));
+      if (int rc = src.run(in, cs)) return rc;
+    } else if (in && src.host) {
+      HIPCHK(h, hipMemcpyAsync(in, src.host, raw_bytes, hipMemcpyHostToDevice, cs));
+    }
+    if (skip > 1 && in && dst) {   // into the look-ahead's new rows [S][Tk][F], or straight into the chunk [S][f.T][F]
+      launch_skip_rows(in, f.sk, dst, ss.S, src.Tc, ss.R > 0 ? Tk : f.T, h->F, skip, cs);
+      HIPCHK(h, hipGetLastError());
     }
     if (ss.R > 0 && (chunk || f.fresh)) {   // (neither: only `last` on slots without rows, or all idle - nothing moves)
-      launch_la_window(ss.hold[ss.cur].as<float>(), fresh, f.sl, chunk, ss.hold[ss.cur ^ 1].as<float>(), ss.S, ss.R, src.Tc, f.T,
+      launch_la_window(ss.hold[ss.cur].as<float>(), fresh, f.sl, chunk, ss.hold[ss.cur ^ 1].as<float>(), ss.S, ss.R, Tk, f.T,
                        f.rows, h->F, cs);
       HIPCHK(h, hipGetLastError());
       moved = true;
@@ -136,7 +170,7 @@ int run_feed(nasr_ctx* h, const char* fn, const FeedPlan& f, const RowSource& sr
     for (int b = 0; b < ss.S; ++b) seq[(size_t)b] = f.sl.emit[b] > 0 ? f.sl.held[b] + f.sl.n[b] : 0;
     StackedProducer prod;
     prod.run = make_rows;
-    BatchSrc b = stacked_batch(ss.R == 0 && !src.run ? src.host : nullptr, seq.data(), nullptr, nullptr, ss.S, f.T, 0);
+    BatchSrc b = stacked_batch(ss.R == 0 && !src.run && skip == 1 ? src.host : nullptr, seq.data(), nullptr, nullptr, ss.S, f.T, 0);
     if (!b.feats) b.stacked = &prod;
     b.chunk = true;   // (its own check first: seq[b] = 0 is an idle slot, and nothing is replaced when it fails)
     ss.sl = f.sl;
@@ -157,6 +191,7 @@ int run_feed(nasr_ctx* h, const char* fn, const FeedPlan& f, const RowSource& sr
     ss.held[(size_t)b] = f.sl.held[b] + f.sl.n[b] - f.sl.emit[b];
     if (last && last[b]) ss.done[(size_t)b] = 1;
     ss.frames[(size_t)b] += f.sl.emit[b];
+    ss.phase[(size_t)b] = f.phase[b];
   }
   // the hold buffers alternate: shifted in place, the rows that stay held would overlap whenever fewer arrive than are held
   if (moved) ss.cur ^= 1;
@@ -243,6 +278,7 @@ int nasr_stream_reset(nasr_handle h, const int32_t* slots, int n) {
     std::fill(ss.frames.begin(), ss.frames.end(), 0);
     std::fill(ss.held.begin(), ss.held.end(), 0);
     std::fill(ss.done.begin(), ss.done.end(), 0);
+    std::fill(ss.phase.begin(), ss.phase.end(), 0);
     if (ss.audio) fz_stream_reset(*ss.audio, -1);
     return NASR_OK;
   }
@@ -255,6 +291,7 @@ int nasr_stream_reset(nasr_handle h, const int32_t* slots, int n) {
     HIPCHK(h, hipMemset2DAsync(static_cast<char*>(ss.state.p) + (size_t)slots[i] * row, (size_t)ss.S * row, 0, row, (size_t)h->lstm->L, h->st));
     ss.frames[(size_t)slots[i]] = 0;
     ss.held[(size_t)slots[i]] = ss.done[(size_t)slots[i]] = 0;   // its held rows are simply forgotten
+    ss.phase[(size_t)slots[i]] = 0;
     if (ss.audio) fz_stream_reset(*ss.audio, slots[i]);
   }
   return NASR_OK;
@@ -269,10 +306,13 @@ int nasr_stream_feed(nasr_handle h, const float* feats, const int32_t* n_frames,
   if (!feats || !n_frames || !logits_out) return h->fail(NASR_ERR_ARG, "nasr_stream_feed: null buffer");
   if (int rc = validate_chunk(h, n_frames, h->lstm->stream->S, Tc)) return rc;
   FeedPlan f;
-  if (int rc = plan_feed(h, __func__, n_frames, nullptr, &f)) return rc;
-  // The chunk is the caller's, Tc rows and not the longest slot's: its row count decides how the bulk GEMMs split their
-  // sums.  So a chunk in which every slot is idle runs as well, and replaces the resident batch.
-  f.T = f.Te = Tc;
+  std::vector<int32_t> kept((size_t)h->lstm->stream->S);
+  keep_rows(h, n_frames, &f, kept.data());
+  if (int rc = plan_feed(h, __func__, kept.data(), nullptr, &f)) return rc;
+  // The chunk is the caller's, Tc rows (skip_frames(Tc, skip) of them kept) and not the longest slot's: its row count
+  // decides how the bulk GEMMs split their sums.  So a chunk in which every slot is idle runs as well, and replaces the
+  // resident batch.
+  f.T = f.Te = skip_frames(Tc, h->lstm->skip);
   RowSource src;
   src.host = feats;
   src.Tc = Tc;
@@ -288,7 +328,9 @@ int nasr_stream_lookahead_rows(nasr_handle h, const int32_t* n_frames, const uin
     if (n_frames[b] < 0)
       return h->fail(NASR_ERR_ARG, "nasr_stream_lookahead_rows: n_frames[" + std::to_string(b) + "] = " + std::to_string(n_frames[b]) + " < 0");
   FeedPlan f;
-  if (int rc = plan_feed(h, __func__, n_frames, last, &f)) return rc;
+  std::vector<int32_t> kept((size_t)h->lstm->stream->S);
+  keep_rows(h, n_frames, &f, kept.data());
+  if (int rc = plan_feed(h, __func__, kept.data(), last, &f)) return rc;
   report(h, f, rows_out, Te_out);
   return NASR_OK;
 }
@@ -302,7 +344,9 @@ int nasr_stream_feed_lookahead(nasr_handle h, const float* feats, const int32_t*
   if (!n_frames || !rows_out || !Te_out) return h->fail(NASR_ERR_ARG, "nasr_stream_feed_lookahead: null buffer");
   if (int rc = la_check_rows(h, __func__, n_frames, Tc)) return rc;
   FeedPlan f;
-  if (int rc = plan_feed(h, __func__, n_frames, last, &f)) return rc;
+  std::vector<int32_t> kept((size_t)h->lstm->stream->S);
+  keep_rows(h, n_frames, &f, kept.data());
+  if (int rc = plan_feed(h, __func__, kept.data(), last, &f)) return rc;
   if (f.fresh && !feats) return h->fail(NASR_ERR_ARG, "nasr_stream_feed_lookahead: null feats");
   if (int rc = short_logits(h, __func__, "nasr_stream_lookahead_rows", f.Te, logits_out, logits_rows)) return rc;
   report(h, f, rows_out, Te_out);
@@ -328,7 +372,8 @@ int nasr_stream_audio_rows(nasr_handle h, const int64_t* n_samples, const uint8_
   if (!n_samples || !rows_out || !Tc_out) return h->fail(NASR_ERR_ARG, "nasr_stream_audio_rows: null buffer");
   FzFeedPlan p;
   if (int rc = audio_plan(h, __func__, n_samples, last, rows_out, Tc_out, &p)) return rc;
-  FeedPlan f;   // the front end's rows join the pending ones: what leaves after the look-ahead's hold-back
+  FeedPlan f;   // the front end's rows, those the frame skip keeps, join the pending ones: what leaves after the look-ahead's hold-back
+  keep_rows(h, rows_out, &f, rows_out);
   if (int rc = plan_feed(h, __func__, rows_out, last, &f)) return rc;
   report(h, f, rows_out, Tc_out);
   return NASR_OK;
@@ -347,6 +392,7 @@ int nasr_stream_feed_audio(nasr_handle h, const float* audio, const int64_t* off
   if (int rc = audio_plan(h, __func__, nnew.data(), last, rows_out, Tc_out, &p)) return rc;
   if (p.in_total > 0 && !audio) return h->fail(NASR_ERR_ARG, "nasr_stream_feed_audio: null audio");
   FeedPlan f;
+  keep_rows(h, rows_out, &f, rows_out);
   if (int rc = plan_feed(h, __func__, rows_out, last, &f)) return rc;
   if (int rc = short_logits(h, __func__, "nasr_stream_audio_rows", f.Te, logits_out, logits_rows)) return rc;
   report(h, f, rows_out, Tc_out);
@@ -398,6 +444,7 @@ int nasr_stream_set_state(nasr_handle h, const float* state, int64_t n) {
   HIPCHK(h, hipSetDevice(h->device));
   HIPCHK(h, hipMemcpyAsync(h->lstm->stream->state.p, state, (size_t)n * 4, hipMemcpyHostToDevice, h->st));
   HIPCHK(h, hipStreamSynchronize(h->st));   // the caller's array is free again
+  std::fill(h->lstm->stream->phase.begin(), h->lstm->stream->phase.end(), 0);   // the state carries no frame-skip phase
   return NASR_OK;
 }
 

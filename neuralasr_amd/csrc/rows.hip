@@ -6,34 +6,41 @@
 namespace nasr {
 
 // ------------------------------------------------------------------ feature transpose + pad
-// feats [B][T][F] batch-major (dataset.py:75-82) -> X0 [(t*Bp+b)][Fp], zero padded
+// feats [B][T][F] batch-major (dataset.py:75-82) -> X0 [(t*Bp+b)][Fp], zero padded.  With a frame skip
+// network row t is input frame t*skip, and rows from the utterance's network length on - t*skip >= seq_in[b] - are zero;
+// seq_in NULL (skip 1): the caller's rows as they are, padding included.
 __global__ __launch_bounds__(256) void pack_feats_kernel(const float* __restrict__ f, float* __restrict__ x, int B,
-                                                         int Bp, int T, int F, int Fp) {
+                                                         int Bp, int T, int F, int Fp, int skip,
+                                                         const int* __restrict__ seq_in) {
   const int r = blockIdx.x;  // t*Bp + b
   const int t = r / Bp, b = r % Bp;
   float* dst = x + (size_t)r * Fp;
-  if (b >= B) {
+  if (b >= B || (seq_in && t * skip >= seq_in[b])) {
     for (int i = threadIdx.x; i < Fp; i += blockDim.x) dst[i] = 0.f;
     return;
   }
-  const float* src = f + ((size_t)b * T + t) * F;
+  const float* src = f + ((size_t)b * T + (size_t)t * skip) * F;
   for (int i = threadIdx.x; i < Fp; i += blockDim.x) dst[i] = i < F ? src[i] : 0.f;
 }
 
-void launch_pack_feats(const float* feats_bm, float* X0, int B, int Bp, int T, int F, int Fp, hipStream_t st) {
-  hipLaunchKernelGGL(pack_feats_kernel, dim3(T * Bp), dim3(256), 0, st, feats_bm, X0, B, Bp, T, F, Fp);
+void launch_pack_feats(const float* feats_bm, float* X0, int B, int Bp, int T, int F, int Fp, hipStream_t st, int skip,
+                       const int* seq_in) {
+  hipLaunchKernelGGL(pack_feats_kernel, dim3(skip_frames(T, skip) * Bp), dim3(256), 0, st, feats_bm, X0, B, Bp, T, F, Fp, skip,
+                     seq_in);
 }
 
 // include_context on the device (utils.py:8-21): the caller ships only the centre frame [B][T][numcep]; every
 // time-major row gets its (2*ctx+1)-frame window, out-of-range frames of an utterance filled with that
 // utterance's pad value (0 before the utterance-level normalisation of utils.py:29, (0-mean)/std after it),
 // frames past seq_len zero (dataset.py:75-77).  21x fewer bytes over PCIe for numcontext = 10.
+// With a frame skip network row t is input frame t*skip: its window is that input frame's, decided on input frame
+// indices against the input length seq_len[b] (t*skip >= seq_len[b] is a row from the network length on: zero).
 __global__ __launch_bounds__(256) void expand_context_kernel(const float* __restrict__ centre,
                                                              const float* __restrict__ pad, const int* __restrict__ seq_len,
                                                              float* __restrict__ x, int B, int Bp, int T, int ctx,
-                                                             int ncep, int Fp) {
+                                                             int ncep, int Fp, int skip) {
   const int r = blockIdx.x;  // t*Bp + b
-  const int t = r / Bp, b = r % Bp;
+  const int t = (r / Bp) * skip, b = r % Bp;   // t: the input frame
   float* dst = x + (size_t)r * Fp;
   const int len = b < B ? seq_len[b] : 0;
   const int F = (2 * ctx + 1) * ncep;
@@ -49,9 +56,9 @@ __global__ __launch_bounds__(256) void expand_context_kernel(const float* __rest
 }
 
 void launch_expand_context(const float* centre, const float* pad, const int* seq_len, float* X0, int B, int Bp, int T,
-                           int ctx, int ncep, int Fp, hipStream_t st) {
-  hipLaunchKernelGGL(expand_context_kernel, dim3(T * Bp), dim3(256), 0, st, centre, pad, seq_len, X0, B, Bp, T, ctx,
-                     ncep, Fp);
+                           int ctx, int ncep, int Fp, hipStream_t st, int skip) {
+  hipLaunchKernelGGL(expand_context_kernel, dim3(skip_frames(T, skip) * Bp), dim3(256), 0, st, centre, pad, seq_len, X0, B, Bp,
+                     T, ctx, ncep, Fp, skip);
 }
 
 // expand_context_kernel with SpecAugment masks (the reference has no augmentation but rand_shift): the
@@ -59,16 +66,17 @@ void launch_expand_context(const float* centre, const float* pad, const int* seq
 // result, so a masked frame is masked in every window it appears in and the pads stay what they were.  masks [B][nm]:
 // {t0, tw, f0, fw}, validated on the host to lie inside the utterance and the static block.  The row's workgroup
 // decides one flag per window and one per column (the mask list is walked nw + ncep times, not once per element) and
-// keeps them in LDS: flag [nw] windows | [ncep] columns.
+// keeps them in LDS: flag [nw] windows | [ncep] columns.  The frame skip as in expand_context_kernel: the masks are in input
+// frames, like every index the row decides on.
 __global__ __launch_bounds__(256) void expand_context_masked_kernel(const float* __restrict__ centre,
                                                                     const float* __restrict__ pad,
                                                                     const int* __restrict__ seq_len,
                                                                     const int4* __restrict__ masks, int nm, int sw,
                                                                     float* __restrict__ x, int B, int Bp, int T, int ctx,
-                                                                    int ncep, int Fp) {
+                                                                    int ncep, int Fp, int skip) {
   extern __shared__ __attribute__((aligned(16))) unsigned char flag[];
   const int r = blockIdx.x;  // t*Bp + b
-  const int t = r / Bp, b = r % Bp;
+  const int t = (r / Bp) * skip, b = r % Bp;   // t: the input frame
   float* dst = x + (size_t)r * Fp;
   const int len = b < B ? seq_len[b] : 0;
   if (t >= len) {            // (the whole workgroup: no barrier is skipped by a part of it)
@@ -103,9 +111,26 @@ __global__ __launch_bounds__(256) void expand_context_masked_kernel(const float*
 
 void launch_expand_context_masked(const float* centre, const float* pad, const int* seq_len, const int* masks, int nm,
                                   int static_width, float* X0, int B, int Bp, int T, int ctx, int ncep, int Fp,
-                                  hipStream_t st) {
-  hipLaunchKernelGGL(expand_context_masked_kernel, dim3(T * Bp), dim3(256), (size_t)(2 * ctx + 1 + ncep), st, centre, pad,
-                     seq_len, reinterpret_cast<const int4*>(masks), nm, static_width, X0, B, Bp, T, ctx, ncep, Fp);
+                                  hipStream_t st, int skip) {
+  hipLaunchKernelGGL(expand_context_masked_kernel, dim3(skip_frames(T, skip) * Bp), dim3(256), (size_t)(2 * ctx + 1 + ncep), st,
+                     centre, pad, seq_len, reinterpret_cast<const int4*>(masks), nm, static_width, X0, B, Bp, T, ctx, ncep, Fp,
+                     skip);
+}
+
+// ------------------------------------------------------------------ frame skip in a stream session (nasr_stream.hip)
+// A feed's new input rows in [S][Tc][F] -> the rows the network sees, out [S][Tk][F], Tk >= every kept[b]: kept row j of
+// slot b is input row first[b] + j*skip for j < kept[b] (both worked out on the host from the slot's phase), zeros
+// behind them.  Block (j, b) moves one row.
+__global__ __launch_bounds__(256) void skip_rows_kernel(const float* __restrict__ in, SkipSlots sk, float* __restrict__ out,
+                                                        int Tc, int Tk, int F, int skip) {
+  const int j = blockIdx.x, b = blockIdx.y;
+  const float* src = j < sk.kept[b] ? in + ((size_t)b * Tc + sk.first[b] + (size_t)j * skip) * F : nullptr;
+  float* dst = out + ((size_t)b * Tk + j) * F;
+  for (int i = threadIdx.x; i < F; i += blockDim.x) dst[i] = src ? src[i] : 0.f;
+}
+
+void launch_skip_rows(const float* in, const SkipSlots& sk, float* out, int S, int Tc, int Tk, int F, int skip, hipStream_t st) {
+  hipLaunchKernelGGL(skip_rows_kernel, dim3(Tk, S), dim3(256), 0, st, in, sk, out, Tc, Tk, F, skip);
 }
 
 // ------------------------------------------------------------------ look-ahead session (nasr_stream.hip)

@@ -104,7 +104,7 @@ def parse_args(argv=None):
     parser.set_defaults(chunk_frames_given=False)
     parser.add_argument('--chunk-frames', type=int, default=50, action=_Given,
                         help='frames per chunk with --stream (default: the config key chunk_frames when it is set, else 50 = 0.5 s); '
-                             'samples are fed chunk-frames * frame_step at a time')
+                             'samples are fed chunk-frames * frame_step at a time.  Input frames, whatever frame_skip says')
     parser.add_argument('--lookahead-frames', type=int, default=None,
                         help='with --stream on a bidirectional network: frames of right context the backward direction gets '
                              'beyond the frames a feed emits (overrides the config key stream_lookahead)')
@@ -121,7 +121,9 @@ def main(argv=None):
     config = Config(args.config, True)
     network = config.load_network(fortraining=False)
     if not args.chunk_frames_given and getattr(config, 'chunk_frames', 0) > 0:
-        args.chunk_frames = config.chunk_frames   # a model trained in windows is served with the chunk it was trained with
+        # a model trained in windows is served with the chunk it was trained with: chunk_frames counts the
+        # network's frames, --chunk-frames input frames
+        args.chunk_frames = config.chunk_frames * getattr(config, 'frame_skip', 1)
     if args.stream:
         if not hasattr(network, 'stream'):
             raise SystemExit('--stream: network %s cannot stream' % type(network).__name__)

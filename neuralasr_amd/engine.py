@@ -26,6 +26,27 @@ def _ip(a):
     return None if a is None else a.ctypes.data_as(POINTER(c_int32))
 
 
+def skip_frames(n, frame_skip):
+    """The frames the network sees of n input frames under a frame skip: frames 0, s, 2s, ... - ceil(n/s).
+    n: an int or an integer array."""
+    s = int(frame_skip)
+    if not 1 <= s <= 8:
+        raise ValueError('frame_skip = %d: must be in [1,8]' % s)
+    if isinstance(n, (int, np.integer)):
+        return (int(n) + s - 1) // s
+    return (np.asarray(n).astype(np.int64) + s - 1) // s
+
+
+def stream_keep(phase, n, frame_skip):
+    """A stream slot's bookkeeping under a frame skip, as the library does it (nasr_stream.hip, keep_rows): the slot's
+    utterance has had `phase` input rows so far, modulo the skip, and n new ones arrive.  Returns (first, kept, phase after):
+    the new rows first, first + s, ... - `kept` of them - are those whose index in the utterance is a multiple of the skip."""
+    s, phase, n = int(frame_skip), int(phase), int(n)
+    first = (s - phase) % s
+    kept = skip_frames(n - first, s) if n > first else 0
+    return first, kept, (phase + n) % s
+
+
 class BatchAug(collections.namedtuple('BatchAug', 'static_width time_masks freq_masks')):
     """SpecAugment masks of one batch (nasr_batch_aug, include/nasr.h): time_masks int32 [B, nt, 2] of (first frame, width),
     freq_masks int32 [B, nf, 2] of (first static column, width), either may be None; static_width is the width of the
@@ -211,7 +232,28 @@ class Engine:
         return feats, seq, labels, ll, B, T, labels.shape[1]
 
     def logit_frames(self, T):
+        """the logit frames of a batch of T input frames (of ceil(T / frame_skip) network frames; 2x for stack_reshape)"""
         return int(self.lib.nasr_logit_frames(self.h, int(T)))
+
+    # ------------------------------------------------------------------ frame skip (include/nasr.h, nasr_set_frame_skip)
+    def set_frame_skip(self, frame_skip):
+        """Low-frame-rate input: from the next upload on the network sees input frames 0, s, 2s, ... of
+        every utterance.  Callers keep passing input frames and input lengths; logits, decoded ids and alignment paths
+        come back in network frames (logit_frames, logit_lens).  The library's refusals (outside [1,8], a WaveNet or LAS
+        handle, an open stream session) raise with its reason."""
+        self._ck(self.lib.nasr_set_frame_skip(self.h, int(frame_skip)))
+
+    @property
+    def frame_skip(self):
+        s = c_int(1)
+        self._ck(self.lib.nasr_get_frame_skip(self.h, byref(s)))
+        return int(s.value)
+
+    def logit_lens(self, seq_len):
+        """input lengths -> the lengths that go with the logits (int32 [B]): ceil(len / frame_skip) network frames, what
+        the beam searches, align_logits and distill_logits take as seq_len.  (stack_reshape's 2T logit frames mix the
+        utterances: its decoders take these lengths too, as they always took seq_len.)"""
+        return skip_frames(np.asarray([int(x) for x in seq_len]), self.frame_skip).astype(np.int32)
 
     def forward(self, feats, seq_len):
         feats, seq, _, _, B, T, _ = self._batch(feats, seq_len)
@@ -648,9 +690,10 @@ class Engine:
 
     def stream_feed(self, feats, n_frames):
         """One chunk: feats [S,Tc,F], n_frames [S] in [0,Tc] (0: the slot is idle).  Returns the logits [Tc,S,C]; rows
-        t >= n_frames[b] of slot b are unspecified."""
+        t >= n_frames[b] of slot b are unspecified.  Under a frame skip s the chunk's kept rows run: logits
+        [ceil(Tc/s),S,C], of which slot b's first stream_keep(phase_b, n_frames[b], s)[1] are its new rows."""
         feats, n, _, _, S, Tc, _ = self._batch(feats, n_frames)
-        out = np.empty((Tc, S, self.num_classes), np.float32)
+        out = np.empty((skip_frames(Tc, self.frame_skip), S, self.num_classes), np.float32)
         self._ck(self.lib.nasr_stream_feed(self.h, _fp(feats), _ip(n), Tc, _fp(out)))
         return out
 

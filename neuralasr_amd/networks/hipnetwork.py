@@ -105,6 +105,10 @@ class HipNetwork(Network):
         self._device = device
         self._featurizer = None                 # the front end of the *_audio calls, made at the first of them
         self.engine = self.make_engine(config, device, stream)
+        if getattr(config, 'frame_skip', 1) != 1:
+            # frame_skip: every upload and every stream feed of this network from here on; a network that
+            # cannot (WaveNet, LAS: the library says why) fails here, on every rank alike
+            self.engine.set_frame_skip(config.frame_skip)
         if fortraining and getattr(config, 'max_grad_norm', 0.0) > 0:
             self.engine.set_grad_clip(config.max_grad_norm)     # every apply_adam of every step path clips from here on
         if getattr(config, 'chunk_frames', 0) > 0:
@@ -139,7 +143,7 @@ class HipNetwork(Network):
             self.config.symbols.write(os.path.join(self.config.model_dir, os.path.basename(self.config.sym_file)))
 
     # ------------------------------------------------------------------ distillation
-    TEACHER_MUST_MATCH = ('feature_size', 'samplerate', 'numcep', 'numcontext', 'features', 'deltas', 'normalization')
+    TEACHER_MUST_MATCH = ('feature_size', 'samplerate', 'numcep', 'numcontext', 'features', 'deltas', 'normalization', 'frame_skip')
 
     def _load_teacher(self):
         """config.teacher_config's network, built for inference on this network's device from its latest checkpoint (none is
@@ -153,9 +157,9 @@ class HipNetwork(Network):
             raise ValueError("teacher_config %s: 'symbols' differ from the student's: the teacher's posteriors are over another "
                              'table (%d symbols, the student has %d)' % (cfg.teacher_config, tcfg.symbols.counter, cfg.symbols.counter))
         for key in self.TEACHER_MUST_MATCH:
-            if getattr(tcfg, key) != getattr(cfg, key):
+            if getattr(tcfg, key, 1) != getattr(cfg, key, 1):   # (the default only ever stands in for frame_skip)
                 raise ValueError("teacher_config %s: '%s' is %r, the student's is %r: both must see the same features"
-                                 % (cfg.teacher_config, key, getattr(tcfg, key), getattr(cfg, key)))
+                                 % (cfg.teacher_config, key, getattr(tcfg, key, None), getattr(cfg, key, None)))
         # On the student's stream: the teacher's forward pass then runs between two of the student's steps, never beside
         # one.  On a stream of its own it would meet the step before, which train() leaves running on the device, and two
         # persistent recurrences that each want every compute unit can take each other's places: one that gives up is a
@@ -232,6 +236,13 @@ class HipNetwork(Network):
             if not files:
                 raise FileNotFoundError('no checkpoint (model-<step>.npz) in ' + model_dir)
             with np.load(files[-1]) as z:
+                # frame_skip changes no tensor's shape: only this field tells a model trained on every
+                # third frame from one trained on every frame.  A checkpoint without the field was trained on every frame.
+                saved = int(json.loads(str(z['meta'])).get('frame_skip', 1)) if 'meta' in z else 1
+                mine = int(getattr(self.config, 'frame_skip', 1))
+                if saved != mine:
+                    raise ValueError("checkpoint %s was trained with frame_skip = %d, the config says frame_skip = %d: the "
+                                     "network would see other frames than it was trained on" % (files[-1], saved, mine))
                 params = z['params']
                 if not self.fortraining and getattr(self.config, 'ema_decay', 0.0) > 0:
                     if 'ema' in z:
@@ -275,7 +286,8 @@ class HipNetwork(Network):
         np.savez(path, params=self.engine.get_params(), adam_m=m, adam_v=v, step=np.int64(step),
                  meta=json.dumps({'hidden': self.num_hidden, 'layers': self.num_layers,
                                   'bidirectional': self.bidirectional, 'merge': self.merge,
-                                  'classes': self.num_classes, 'feature_size': self.config.feature_size}),
+                                  'classes': self.num_classes, 'feature_size': self.config.feature_size,
+                                  'frame_skip': int(getattr(self.config, 'frame_skip', 1))}),
                  **ema, **self.model_state())
         for old in self._ckpt_files(self.config.model_dir)[:-self.keep_checkpoints]:
             os.remove(old)
@@ -373,12 +385,18 @@ class HipNetwork(Network):
             self._lm = load_for(self.config)
         return self._lm
 
+    def _logit_lens(self, seq_len):
+        """the lengths that go with the logits: seq_len itself, or under frame_skip the network's frames"""
+        if getattr(self.config, 'frame_skip', 1) == 1:
+            return seq_len
+        return self.engine.logit_lens(seq_len)
+
     def _decode(self, mfccs, seq_len, which, lm=None):
         if which == 'beam':
             logits = self._retry_aborted(lambda: self._forward(mfccs, seq_len))
             if lm is None:
-                return self.engine.beam_search(logits, seq_len, self.beam_width, merge_repeated=True)[0]
-            return self.engine.beam_search(logits, seq_len, self.beam_width, merge_repeated=True, lm=lm,
+                return self.engine.beam_search(logits, self._logit_lens(seq_len), self.beam_width, merge_repeated=True)[0]
+            return self.engine.beam_search(logits, self._logit_lens(seq_len), self.beam_width, merge_repeated=True, lm=lm,
                                            lm_weight=self.config.lm_weight, lm_bonus=self.config.lm_bonus)[0]
 
         def run():
@@ -501,7 +519,7 @@ class HipNetwork(Network):
 
     # ------------------------------------------------------------------ the step's LER (tfnetwork.py:61-70)
     def _beam_ler(self, logits, s, l, ll):
-        hyps = self.engine.beam_search(logits, s, self.beam_width, merge_repeated=True)[0]
+        hyps = self.engine.beam_search(logits, self._logit_lens(s), self.beam_width, merge_repeated=True)[0]
         return self.engine.label_error_rate(hyps, l, ll)
 
     def _step_ler(self, hyps, f, l, s, ll, lazy):

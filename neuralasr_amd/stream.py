@@ -31,6 +31,7 @@ class StreamingRecognizer:
         self.slots = int(slots)
         self.lookahead = None if lookahead is None else int(lookahead)
         self.feature_size = int(network.config.feature_size)
+        self.frame_skip = int(getattr(network.config, 'frame_skip', 1))     # (the engine has it already: HipNetwork set it)
         settle = getattr(network, '_settle', None)
         if settle:
             settle()
@@ -89,9 +90,16 @@ class StreamingRecognizer:
             raise ValueError('`last` means something only with a look-ahead')
         if n.max() == 0:                         # (the library refuses a chunk without rows)
             return [beam.best()[0] for beam in self.beams]
+        if self.frame_skip == 1:
+            with self._averaged():
+                logits = self.engine.stream_feed(self._padded(arrs, n), n)
+            return self._deliver(logits, n, n, None, None)
+        # under frame_skip a slot's new logit rows are the rows the session kept, not the rows it was given:
+        # the rows the library reports, as the growth of its per-slot count
+        before = self.engine.stream_frames()
         with self._averaged():
             logits = self.engine.stream_feed(self._padded(arrs, n), n)
-        return self._deliver(logits, n, n, None, None)
+        return self._deliver(logits, self.engine.stream_frames() - before, n, None, None)
 
     def feed_audio(self, chunks, last=None):
         """chunks: one entry per slot, float32 [n_b] samples at config.samplerate (the slot's next samples) or None (the
