@@ -9,6 +9,10 @@ from oracle import nasr_oracle as O
 pytestmark = pytest.mark.gpu
 
 
+# check()'s tolerances: logits absolute, loss and nll relative (nll with an absolute floor), the whole gradient's norm
+TOL_LOGITS, TOL_LOSS, TOL_NLL_ABS, TOL_GRAD = 2e-4, 3e-5, 1e-5, 1e-4
+
+
 def engine_for(spec):
     from neuralasr_amd.engine import Engine
     return Engine(spec.feature_size, spec.hidden, spec.num_layers, spec.bidirectional, spec.merge, spec.num_classes,
@@ -19,7 +23,7 @@ def rel(a, b):
     return np.linalg.norm(a - b) / max(np.linalg.norm(b), 1e-30)
 
 
-def check(spec, feats, seq_len, labels, label_len, seed=3, gtol=1e-4):
+def check(spec, feats, seq_len, labels, label_len, seed=3, gtol=TOL_GRAD):
     rs = np.random.RandomState(seed)
     params = [p + 0.05 * rs.randn(*p.shape) for p in O.init_params(spec, seed=seed)]
     params = [p.astype(np.float32).astype(np.float64) for p in params]
@@ -27,9 +31,9 @@ def check(spec, feats, seq_len, labels, label_len, seed=3, gtol=1e-4):
     e.set_params(O.flatten(params))
     loss, nll, grads = e.loss_and_grads(feats, seq_len, labels, label_len)
     lo, nllo, go, logits_o = O.network_loss_and_grads(spec, params, feats, seq_len, labels, label_len)
-    np.testing.assert_allclose(e.forward(feats, seq_len), logits_o, atol=2e-4)
-    assert loss == pytest.approx(lo, rel=3e-5)
-    np.testing.assert_allclose(nll, nllo, rtol=3e-5, atol=1e-5)
+    np.testing.assert_allclose(e.forward(feats, seq_len), logits_o, atol=TOL_LOGITS)
+    assert loss == pytest.approx(lo, rel=TOL_LOSS)
+    np.testing.assert_allclose(nll, nllo, rtol=TOL_LOSS, atol=TOL_NLL_ABS)
     assert rel(grads, O.flatten(go)) < gtol
     e.close()
 
