@@ -1,8 +1,8 @@
 """Builds neuralasr_amd/libnasr.so (the HIP kernels + C ABI of include/nasr.h) for gfx950 with hipcc.
 In-tree, explicit `hipcc -shared -fPIC`; cross-compiles without a GPU.  `python -m neuralasr_amd.build`.
 Also neuralasr_amd/libnasr_kt.so: the kernel tests' entry points (tests/kernel_harness/harness.hip for the GEMM layer,
-rec_harness.hip for the recurrence) over the very gemm.o / gemm_tph.o / optim.o / lstm.o / lstm_persist.o / lstm_wide.o
-objects of libnasr.so."""
+rec_harness.hip for the recurrence, ctc_harness.hip for the CTC kernels) over the very gemm.o / gemm_tph.o / optim.o /
+lstm.o / lstm_persist.o / lstm_wide.o / ctc.o objects of libnasr.so."""
 import os
 import subprocess
 import sys
@@ -13,10 +13,10 @@ CSRC = os.path.join(HERE, 'csrc')
 LIB = os.path.join(HERE, 'libnasr.so')
 KT_LIB = os.path.join(HERE, 'libnasr_kt.so')
 KT_DIR = os.path.join(HERE, '..', 'tests', 'kernel_harness')
-KT_SRCS = ['harness.hip', 'rec_harness.hip']
+KT_SRCS = ['harness.hip', 'rec_harness.hip', 'ctc_harness.hip']
 KT_HEADERS = [os.path.join(KT_DIR, 'arena.h')]
 # the objects of libnasr.so the kernel tests link against (optim.o also holds test_hook(), which the recurrence launchers call)
-KT_OBJS = ['gemm.o', 'gemm_tph.o', 'optim.o', 'lstm.o', 'lstm_persist.o', 'lstm_wide.o']
+KT_OBJS = ['gemm.o', 'gemm_tph.o', 'optim.o', 'lstm.o', 'lstm_persist.o', 'lstm_wide.o', 'ctc.o']
 SOURCES = ['gemm.hip', 'gemm_tph.hip', 'lstm.hip', 'rows.hip', 'lstm_persist.hip', 'lstm_wide.hip', 'ctc.hip', 'dense.hip', 'optim.hip', 'nasr_layout.hip',
            'nasr_rec.hip', 'nasr_batch.hip', 'nasr_pass.hip', 'nasr_stream.hip', 'nasr_lstm.hip', 'nasr_api.hip', 'nasr_distill.hip', 'nasr_comm.hip', 'beam.cpp',
            'wavenet.hip', 'nasr_wavenet.hip', 'las.hip', 'las_beam.hip', 'nasr_las.hip', 'mfcc.hip', 'nasr_fz.hip', 'resample.hip', 'wave_aug.hip']

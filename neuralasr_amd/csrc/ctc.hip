@@ -225,8 +225,9 @@ __device__ __forceinline__ void ctc_plain_walk(
   bool act[KS], skip[KS];
 #pragma unroll
   for (int i = 0; i < KS; ++i) lattice_state<fwd>(labels + (size_t)b * Lmax, S, lane * KS + i, blank, blank, ext[i], act[i], skip[i]);
-  // 32-bit element offsets from wave-uniform bases (the launcher checks T' * Bp * Cp < 2^32): one v_mad_u32 per gather
-  // or store instead of 64-bit address arithmetic - the lattice is bound by its instruction count
+  // 32-bit byte offsets from wave-uniform bases (ensure_ctc_buffers, nasr_batch.hip, refuses a batch with T' * Bp * Cp * 4
+  // >= 2^32 for every CTC handle): one v_mad_u32 per gather or store instead of 64-bit address arithmetic - the lattice
+  // is bound by its instruction count
   const unsigned rstride = (unsigned)Bp * (unsigned)Cp;  // logits row stride between frames
   const float* lg = logits + (size_t)b * Cp;
   const float* lz = logz + b;
@@ -598,7 +599,7 @@ void launch_ctc_alpha_beta(const CtcDims& d, const float* logits, const float* l
 // k, in a FIXED order (no atomics: two runs give the same bits): every lane turns its own states into weights in LDS;
 // the blank (all even states) is a per-lane sum in state order + the wave's xor tree; label k is summed by lane k over
 // the positions of k in the utterance's label in ascending order - cstart [B][C+1] / cpos [B][Lmax] is the label sorted
-// by class (a counting sort the host does once per upload, nasr_api.hip).
+// by class (a counting sort the host does once per upload: ctc_class_positions of kernels.h, from write_meta).
 __global__ __launch_bounds__(256) void ctc_grad_kernel(float* __restrict__ logits, const float* __restrict__ logz,
                                                        const int* __restrict__ label_len,
                                                        const int* __restrict__ seq_len,
@@ -786,7 +787,7 @@ __global__ __launch_bounds__(64) void ctc_align_kernel(const float* __restrict__
   bool act[KS], skip[KS];
 #pragma unroll
   for (int i = 0; i < KS; ++i) lattice_state<true>(lab, S, lane * KS + i, blank, blank, ext[i], act[i], skip[i]);
-  const unsigned rstride = (unsigned)Bp * (unsigned)Cp;     // (the launcher checks T' * Bp * Cp * 4 < 2^32)
+  const unsigned rstride = (unsigned)Bp * (unsigned)Cp;     // (launch_ctc_align and align_run, nasr_api.hip, refuse T' * Bp * Cp * 4 >= 2^32)
   const float* lg = logits + (size_t)b * Cp;
   auto gather = [&](int t, float (&x)[KS]) {                // t must be a valid frame (callers clamp); ext is always a class id
 #pragma unroll

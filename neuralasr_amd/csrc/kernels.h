@@ -9,6 +9,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <vector>
+
 namespace nasr {
 
 // Fault-injection hooks of the tests (NASR_PERSIST_FAULT, NASR_WIDE_FAULT, ...): honoured only in a process that had
@@ -301,6 +303,23 @@ void launch_dense_act(float* z, int R, int Bp, int B, int W, int ld, float clip,
 void launch_dense_act_bwd(float* dy, const float* y, int64_t n, float clip, float p, hipStream_t st);
 
 // ---- CTC (ctc.hip) ----
+// Contract of the launchers below, on what is read, what is ignored and what is written where
+// (tests/test_gpu_ctc_kernels.py holds each of them to it, launch by launch against fp64):
+//   shapes    B in [1,64], Bp = round_up(B,16), C >= 2, Cp = round_up(C,32), Lmax >= 1 with KS = ctc_states_per_lane(Lmax) <= 16,
+//             T' * Bp * Cp * 4 < 2^32 (the walks and the alignment gather at 32-bit byte offsets; ensure_ctc_buffers, align_run
+//             and the distillation entry refuse more).  seq_len [Bp]: in [1,T'] for b < B.  labels [B][Lmax] with ids in
+//             [0, C-2] in the first label_len[b] <= Lmax entries of a row, feasible in seq_len[b] frames (validate_batch).
+//   read      logits (t,b,c) with b < B, t < seq_len[b], c < C; the first label_len[b] entries of a label row; cstart / cpos
+//             of the rows b < B.  Nothing else enters a result: the columns [C,Cp), the rows b >= B, the frames
+//             t >= seq_len[b] and the label entries from label_len[b] on may hold anything (NaN, any in-range id), and so
+//             may every workspace (alpha, beta, aoff, boff, lprobs, goff, the greedy argmax) before the launch.
+//   logz      written at the rows (t,b) with b < B and t < seq_len[b]; every other row stays untouched.
+//   nll,logp  entries b < B are written, nothing behind them.
+//   gradient  in place over all T' * Bp rows and Cp columns: d(mean nll)/dlogits * scale where the logit is read, +0 in the
+//             columns [C,Cp), the rows b >= B and the frames t >= seq_len[b].
+//   greedy    ids [B][T'] hold lens[b] entries per row; the rest of a row stays untouched.
+//   placement a result of utterance b depends on its own logits, label and lengths alone: not on its slot, on B, on T' or on
+//             the stride Lmax (inside one KS).  Two runs give the same bits (fixed summation orders, no atomics).
 struct CtcDims {
   int Tp;      // logit frames T'
   int B, Bp, C, Cp, Lmax;
@@ -329,6 +348,15 @@ void launch_ctc_alpha_beta(const CtcDims& d, const float* logits, const float* l
 void launch_ctc_grad(const CtcDims& d, float* logits, const float* logz, const int* label_len, const int* seq_len,
                      const int* cstart, const int* cpos, const float* alpha, const float* beta, const double* aoff,
                      const double* boff, const double* logp, float scale, hipStream_t st);
+// One utterance's cstart [C+1] / cpos [>= L] from its label (L ids in [0, C-2]): a counting sort on the host - the fixed
+// summation order of ctc_grad.  cstart must come in zeroed; fill: scratch of the caller's, resized here.
+inline void ctc_class_positions(const int32_t* label, int L, int C, int32_t* cstart, int32_t* cpos, std::vector<int32_t>& fill) {
+  fill.resize((size_t)C);
+  for (int i = 0; i < L; ++i) cstart[label[i] + 1] += 1;
+  for (int c = 0; c < C; ++c) cstart[c + 1] += cstart[c];
+  for (int c = 0; c < C; ++c) fill[c] = cstart[c];
+  for (int i = 0; i < L; ++i) cpos[fill[label[i]]++] = i;
+}
 void launch_mean(const float* v, int n, float* out, hipStream_t st);
 void launch_greedy(const CtcDims& d, const float* logits, const int* seq_len, int* argmax_ws, int* ids, int* lens,
                    hipStream_t st);

@@ -11,6 +11,10 @@ namespace nasr_impl {
 int ensure_ctc_buffers(nasr_ctx* h, int B, int Bp, int T, int Tp, int Lmax, bool* grew) {
   const int KSa = ctc_states_per_lane(Lmax);
   if (KSa > 16) return h->fail(NASR_ERR_ARG, "label length > 511 not supported by the CTC lattice kernel");
+  // the plain walk of ctc.hip (2) gathers its emissions at 32-bit BYTE offsets from the utterance's first row
+  if ((size_t)Tp * Bp * h->Cp * 4 >= ((size_t)1 << 32))
+    return h->fail(NASR_ERR_ARG, "T' x B x C logits beyond the lattice kernels' 32-bit offsets: " + std::to_string(Tp) + " x " +
+                                     std::to_string(Bp) + " x " + std::to_string(h->Cp) + " floats");
   bool ok = true;
   ok &= h->logits.ensure((size_t)Tp * Bp * h->Cp * 4, grew);
   ok &= h->logz.ensure((size_t)Tp * Bp * 4, grew);
@@ -328,15 +332,10 @@ static void write_meta(const nasr_ctx* h, BatchSlot* s, const BatchSrc& src) {
     memcpy(m + s->o_lablen, label_len, (size_t)B * 4);
     if (Lmax > 0) memcpy(m + s->o_labels, labels, (size_t)B * Lmax * 4);
     // the label positions of every utterance sorted by class (counting sort): the fixed summation order of ctc_grad
-    std::vector<int32_t> fill((size_t)C);
-    for (int b = 0; b < B; ++b) {
-      int32_t* c0 = m + s->o_cstart + (size_t)b * (C + 1);
-      const int32_t* lb = labels + (size_t)b * Lmax;
-      for (int i = 0; i < label_len[b]; ++i) c0[lb[i] + 1] += 1;
-      for (int c = 0; c < C; ++c) c0[c + 1] += c0[c];
-      std::copy(c0, c0 + C, fill.begin());
-      for (int i = 0; i < label_len[b]; ++i) m[s->o_cpos + (size_t)b * Lm + fill[lb[i]]++] = i;
-    }
+    std::vector<int32_t> fill;
+    for (int b = 0; b < B; ++b)
+      ctc_class_positions(labels + (size_t)b * Lmax, label_len[b], C, m + s->o_cstart + (size_t)b * (C + 1),
+                          m + s->o_cpos + (size_t)b * Lm, fill);
   }
   if (stack_reshape(h)) {
     // logits[t',b'] <- flat row q = b'*2T + t' of O = stack(fw,bw) [2,B,T,H];

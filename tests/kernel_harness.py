@@ -1,9 +1,9 @@
-"""ctypes side of tests/kernel_harness/harness.hip and rec_harness.hip (neuralasr_amd/libnasr_kt.so, built by
-neuralasr_amd/build.py): the GEMM-layer and recurrence launchers of csrc/kernels.h, callable with NumPy arrays.  Every call raises on a HIP error or a refused
+"""ctypes side of tests/kernel_harness/harness.hip, rec_harness.hip and ctc_harness.hip (neuralasr_amd/libnasr_kt.so, built by
+neuralasr_amd/build.py): the GEMM-layer, recurrence and CTC launchers of csrc/kernels.h, callable with NumPy arrays.  Every call raises on a HIP error or a refused
 argument; outputs come back as fresh arrays whose untouched bytes still hold FILL."""
 import ctypes
 import os
-from ctypes import POINTER, Structure, c_float, c_int, c_longlong, c_ubyte, c_ulonglong, c_void_p
+from ctypes import POINTER, Structure, c_double, c_float, c_int, c_longlong, c_ubyte, c_ulonglong, c_void_p
 
 import numpy as np
 
@@ -15,7 +15,8 @@ SYMBOLS = ['kt_gemm_pick_split', 'kt_gemm_tp_tile_rows', 'kt_gemm_tph_pick_split
            'kt_gemm_f32', 'kt_tph_scales', 'kt_tph_scales_batch', 'kt_tph_scales_from_parts', 'kt_tph_split2', 'kt_gemm_tph',
            'kt_colsum', 'kt_colsum_parts', 'kt_reduce_slabs', 'kt_reduce_slabs_rows',
            'kt_persist_dgmax_floats', 'kt_lstm_step_fwd', 'kt_lstm_step_bwd', 'kt_lstm_step_bwd_carry',
-           'kt_lstm_persist_fwd', 'kt_lstm_persist_bwd', 'kt_lstm_wide_fwd', 'kt_lstm_wide_bwd']
+           'kt_lstm_persist_fwd', 'kt_lstm_persist_bwd', 'kt_lstm_wide_fwd', 'kt_lstm_wide_bwd',
+           'kt_ctc_pass', 'kt_ctc_greedy', 'kt_mean']
 
 FILL = 0xCD                                   # pre-fill byte of every output buffer
 FILL_F32 = np.frombuffer(bytes([FILL] * 4), dtype=np.float32)[0]
@@ -40,6 +41,11 @@ class KtTph(Structure):
 class KtRec(Structure):
     _fields_ = ([(n, c_int) for n in ('T', 'B', 'Bp', 'H', 'Hp', 'D')] + [('forget_bias', c_float)] +
                 [(n, c_int) for n in ('f16', 'lean', 'parts', 'fill')])
+
+
+class KtCtc(Structure):
+    _fields_ = ([(n, c_int) for n in ('Tp', 'B', 'Bp', 'C', 'Cp', 'Lmax')] + [('scale', c_float)] +
+                [(n, c_int) for n in ('plain', 'ws_fill', 'fill')])
 
 
 _lib = None
@@ -309,6 +315,71 @@ def lstm_backward(path, inp, lean=False, parts=False):
         if parts:
             rp, cp = rp.reshape(D * 32, T * Bp), cp.reshape(8 // D, D * 4 * Hp)
     return dg.reshape(act.shape), rp, cp
+
+
+# ------------------------------------------------------------------ the CTC kernels (ctc_harness.hip)
+FILL_I32 = np.frombuffer(bytes([FILL] * 4), dtype=np.int32)[0]
+FILL_F64 = np.frombuffer(bytes([FILL] * 8), dtype=np.float64)[0]
+
+
+def rup(x, m):
+    return (x + m - 1) // m * m
+
+
+def ctc_desc(Tp, B, C, Lmax, scale=1.0, plain=False, ws_fill=0xFF, **over):
+    """The launch's shape with the padded sizes the library derives (over: fields set to something else, for the refusals)."""
+    d = dict(Tp=Tp, B=B, Bp=rup(B, 16), C=C, Cp=rup(C, 32), Lmax=Lmax, scale=scale, plain=int(plain), ws_fill=ws_fill, fill=FILL)
+    d.update(over)
+    return KtCtc(**d)
+
+
+def ctc_pass_raw(d, logits, seq_len, labels, label_len):
+    """kt_ctc_pass on buffers taken as they are -> (rc, gradient, logz, nll, logp); the outputs hold FILL (the gradient: the
+    caller's logits) where nothing was written - all of them after a refusal."""
+    g = np.array(logits, dtype=np.float32, order='C')
+    sq, lab, ll = _i32(seq_len), _i32(labels), _i32(label_len)
+    logz = np.full(min(max(d.Tp, 1) * max(d.Bp, 1), 1 << 22), FILL_F32, np.float32)
+    nll, logp = np.full(64, FILL_F32, np.float32), np.full(64, FILL_F64, np.float64)
+    rc = lib().kt_ctc_pass(ctypes.byref(d), _f(g), _i(sq), _i(lab), _i(ll), _f(logz), _f(nll), logp.ctypes.data_as(POINTER(c_double)))
+    return rc, g, logz, nll, logp
+
+
+def ctc_pass(logits, seq_len, labels, label_len, C, scale=1.0, plain=False, ws_fill=0xFF):
+    """logZ, alpha / beta and the gradient over logits [Tp][Bp][Cp] (seq_len [Bp], labels [B][Lmax], label_len [B]) ->
+    dict(grad [Tp][Bp][Cp], logz [Tp][Bp], nll [Bp], logp [Bp]); the entries of nll / logp from B on hold FILL."""
+    Tp, Bp, Cp = logits.shape
+    B, Lmax = np.shape(labels)
+    d = ctc_desc(Tp, B, C, Lmax, scale, plain, ws_fill)
+    assert (d.Bp, d.Cp) == (Bp, Cp) and len(seq_len) == Bp and len(label_len) == B
+    rc, g, logz, nll, logp = ctc_pass_raw(d, logits, seq_len, labels, label_len)
+    _check(rc, 'kt_ctc_pass')
+    return dict(grad=g, logz=logz.reshape(Tp, Bp), nll=nll[:Bp], logp=logp[:Bp])
+
+
+def ctc_greedy_raw(d, logits, seq_len):
+    lg, sq = _f32(logits), _i32(seq_len)
+    ids = np.full(min(max(d.B, 1) * max(d.Tp, 1), 1 << 22), FILL_I32, np.int32)
+    lens = np.full(64, FILL_I32, np.int32)
+    rc = lib().kt_ctc_greedy(ctypes.byref(d), _f(lg), _i(sq), _i(ids), _i(lens))
+    return rc, ids, lens
+
+
+def ctc_greedy(logits, seq_len, B, C):
+    """argmax + collapse over logits [Tp][Bp][Cp] -> (ids [B][Tp], lens [Bp]); FILL where nothing was written."""
+    Tp, Bp, Cp = logits.shape
+    d = ctc_desc(Tp, B, C, 1)
+    assert (d.Bp, d.Cp) == (Bp, Cp) and len(seq_len) == Bp
+    rc, ids, lens = ctc_greedy_raw(d, logits, seq_len)
+    _check(rc, 'kt_ctc_greedy')
+    return ids.reshape(B, Tp), lens[:Bp]
+
+
+def mean(v, pad=3):
+    """launch_mean -> out [1 + pad]: the mean, then FILL"""
+    v = _f32(v)
+    out = _out(1 + pad)
+    _check(lib().kt_mean(_f(v), v.size, _f(out), out.size, FILL), 'kt_mean')
+    return out
 
 
 # ------------------------------------------------------------------ checks shared by the GPU tests

@@ -1,4 +1,4 @@
-// arena.h — what the entry points of harness.hip and rec_harness.hip share: one stream and the device buffers of a call,
+// arena.h — what the entry points of harness.hip, rec_harness.hip and ctc_harness.hip share: one stream and the device buffers of a call,
 // freed when the call returns; the first HIP error sticks and becomes the call's return value.
 #pragma once
 #include <hip/hip_runtime.h>

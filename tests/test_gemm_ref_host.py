@@ -211,6 +211,8 @@ def test_harness_library_builds_and_exports_its_entry_points():
         return {line.split()[-1].split('@')[0] for line in out.splitlines() if line.strip()}
     exported = {s for s in syms(H.KT_PATH, '--defined-only') if s.startswith('kt_')}
     assert exported == set(H.SYMBOLS)
+    # all three layers: the GEMMs, the recurrence, the CTC kernels
+    assert {'kt_gemm_tph', 'kt_lstm_persist_bwd', 'kt_ctc_pass', 'kt_ctc_greedy', 'kt_mean'} <= exported
     extra = syms(H.KT_PATH, '--undefined-only') - syms(_lib.LIB_PATH, '--undefined-only')
     assert not extra, f'libnasr_kt.so needs symbols libnasr.so does not: {sorted(extra)}'
     out = subprocess.run(['strings', '-a', H.KT_PATH], capture_output=True, text=True).stdout if shutil.which('strings') else 'gfx950'

@@ -108,6 +108,29 @@ def test_label_too_long_for_lattice_kernel_is_an_error():
     e.close()
 
 
+def test_logits_beyond_32_bit_offsets_are_an_error():
+    """The lattice walks gather at 32-bit byte offsets: T' x Bp x Cp x 4 >= 2^32 is refused when the batch is uploaded,
+    before anything is sized for it (only the upload runs at this shape), and the handle goes on with the next batch."""
+    from neuralasr_amd import _lib
+    spec = O.ModelSpec(4, 8, 1, True, 'concat', 4000)
+    e = engine_for(spec)
+    B, T = 64, 4200
+    assert T * B * 4000 * 4 >= 2 ** 32
+    feats = np.zeros((B, T, 4), np.float32)
+    with pytest.raises(_lib.NasrError, match='32-bit'):
+        e.upload_batch(feats, [T] * B, np.zeros((B, 1), np.int32), [1] * B)
+    feats, seq_len, labels, label_len = O.synth_batch(spec, 3, 12, seed=9, var_len=True, Lmin=2, Lmax=5)
+    params = [p.astype(np.float32).astype(np.float64) for p in O.init_params(spec, seed=3)]
+    e.set_params(O.flatten(params))
+    e.upload_batch(feats, seq_len, labels, label_len)
+    loss, nll = e.loss_resident(3)
+    lo, nllo = O.network_loss_and_grads(spec, params, feats, seq_len, labels, label_len)[:2]
+    assert loss == pytest.approx(lo, rel=TOL_LOSS)
+    np.testing.assert_allclose(nll, nllo, rtol=TOL_LOSS, atol=TOL_NLL_ABS)
+    assert e.train_step(feats, seq_len, labels, label_len) == pytest.approx(lo, rel=TOL_LOSS)
+    e.close()
+
+
 def test_large_symbol_table():
     """label_context = 1 makes tri-gram symbols: C in the thousands."""
     spec = O.ModelSpec(7, 16, 1, True, 'concat', 3000)

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """The error the CTC lattice's fp32 arithmetic alone makes at the long and sharp cases of tests/test_gpu_ctc_lattice.py, on the
 CPU: recursion (2) of csrc/ctc.hip (log domain, columns rescaled by their maximum every 4 frames, fp64 offsets) in numpy
-float32 with correctly rounded exp and log, against the fp64 oracle on the same logits.  Prints the relative error of the
+float32 with correctly rounded exp and log (ctc_fp32 of tests/ctc_ref.py), against the fp64 oracle on the same logits.  Prints the relative error of the
 projection bias gradient b (the frame sum of the logit gradient) and of the whole logit gradient, b of the fp64 lattice on
 logits with noise of 5e-6, and, for the WaveNet case, the worst network gradient when only the lattice is fp32.  The test's
 tolerances quote these numbers.
@@ -18,63 +18,7 @@ sys.path.insert(0, os.path.join(ROOT, 'tests'))
 
 from oracle import nasr_oracle as O  # noqa: E402
 
-F32 = np.float32
-NEG = F32(-1e30)
-
-
-def lse3(a, b, c):
-    m = np.maximum(a, np.maximum(b, c))
-    return (m + np.log(np.exp(a - m) + np.exp(b - m) + np.exp(c - m))).astype(F32)
-
-
-def ctc_fp32(logits, label, blank, G=4):
-    """(nll, d nll / d logits) of one utterance, logits [T, C], as recursion (2) computes them in fp32"""
-    x = np.asarray(logits, F32)
-    T, C = x.shape
-    mx = x.max(1, keepdims=True)
-    z = (mx[:, 0] + np.log(np.exp(x - mx).sum(1))).astype(F32)
-    L = len(label)
-    S = 2 * L + 1
-    ext = np.full(S, blank)
-    ext[1::2] = label
-    e = (x[:, ext] - z[:, None]).astype(F32)
-    skip = np.zeros(S, bool)
-    skip[2:] = (ext[2:] != blank) & (ext[2:] != ext[:-2])
-    skip_f = np.zeros(S, bool)
-    skip_f[:-2] = skip[2:]
-
-    def rescale(v, off):
-        m = v.max()
-        return np.where(v > NEG / 2, v - m, NEG).astype(F32), off + float(m)
-    al, ao = np.full((T, S), NEG, F32), np.zeros(T)
-    a, A = np.full(S, NEG, F32), 0.0
-    a[:2] = e[0, :2]
-    al[0] = a
-    for t in range(1, T):
-        if (t - 1) % G == 0:
-            a, A = rescale(a, A)
-        a1 = np.concatenate([[NEG], a[:-1]]).astype(F32)
-        a2 = np.where(skip, np.concatenate([[NEG, NEG], a])[:S], NEG).astype(F32)
-        a = (e[t] + lse3(a, a1, a2)).astype(F32)
-        al[t], ao[t] = a, A
-    be, bo = np.full((T, S), NEG, F32), np.zeros(T)
-    b, Bo = np.full(S, NEG, F32), 0.0
-    b[max(S - 2, 0):] = 0
-    be[T - 1] = b
-    for t in range(T - 2, -1, -1):
-        if (T - 2 - t) % G == 0:
-            b, Bo = rescale(b, Bo)
-        bb = (b + e[t + 1]).astype(F32)
-        b1 = np.concatenate([bb[1:], [NEG]]).astype(F32)
-        b2 = np.where(skip_f, np.concatenate([bb, [NEG, NEG]])[2:], NEG).astype(F32)
-        b = lse3(bb, b1, b2)
-        be[t], bo[t] = b, Bo
-    logp = A + float(lse3(a[S - 1], a[S - 2] if S > 1 else NEG, NEG))
-    w = np.exp(al.astype(np.float64) + be + (ao + bo - logp)[:, None])
-    post = np.zeros((T, C))
-    for s in range(S):
-        post[:, ext[s]] += w[:, s]
-    return -logp, np.exp(x.astype(np.float64) - z[:, None]) - post
+from ctc_ref import ctc_fp32  # noqa: E402
 
 
 def logit_grads(logits, seq_len, labels, label_len, G):
